@@ -2,7 +2,7 @@
 """Benchmark of the batch-SOM hot path on MI355X: samples/sec/epoch (BMU + update).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c3|c2|c5|c4iso|c2nn]
-                    [--scaling strong|weak] [--via backend|ctx]
+                    [--scaling strong|weak] [--via backend|ctx] [--full] [--dump-outputs DIR]
 
 One "step" = one epoch of the hot path (reference dbgsom/BaseSom.py:403-407: BMU search, sample
 kernel, per-neuron sums, [all-reduce], neighbourhood smoothing, convergence norm, per-neuron
@@ -13,10 +13,16 @@ starts from the same prototypes and computes everything again -- ONE call of the
 
 The headline uses the stateless filtered search (`algorithm="filtered"`: coarse int8-MFMA pre-pass
 -> int8 candidate sweep with a rigorous error bound -> exact float64 search on the candidates;
-results bit-identical to the all-pairs float64 search, nothing carried over between steps).  The
-same JSON line also carries the all-pairs exact search (`exact`), a training-like secondary
-regime (`fine_phase`) and, at N = 1, two weakly clustered data sets (`other_data`) that show how
-much of the headline is a property of the data.
+results bit-identical to the all-pairs float64 search, nothing carried over between steps).  A
+plain run sets up, warms up, times the K steps and prints the headline only.  With `--full` the
+same JSON line also carries per-phase HIP-event times and rooflines, the all-pairs exact search
+(`exact`), a training-like secondary regime (`fine_phase`) and, at N = 1, two weakly clustered
+data sets (`other_data`) that show how much of the headline is a property of the data, the other
+BASELINE workloads, a whole fit, and the CPU baseline with its parity gate.
+
+`--dump-outputs DIR` writes what the last timed step handed its caller -- the new prototypes, the
+per-neuron errors and hit counts, the convergence norm -- as float64 `DIR/<name>.npy` (rank 0).
+The inputs are generated from fixed seeds, so two builds can be compared output for output.
 
 `--via ctx` drives the same epoch with NumPy + ctypes only (no torch is imported): the seam a
 maintainer of the reference would bind.
@@ -384,6 +390,25 @@ def count_stats(c):
     return {"mean": float(c.mean()), "p90": float(np.percentile(c, 90)), "max": int(c.max())}
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as float64 `path/<name>.npy`, at most DUMP_LIMIT_BYTES in all.  Prototypes that
+    would pass the limit (C5: 4096 x 2048 float64 = 67 MB) are written as a fixed, seeded sample of rows, their
+    indices beside them in `new_weights_rows.npy`."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    W = arrays["new_weights"]
+    room = DUMP_LIMIT_BYTES - sum(v.nbytes + 128 for v in arrays.values()) + W.nbytes - 128   # (.npy headers)
+    if W.nbytes > room:
+        k = room // ((W.shape[1] + 1) * 8)
+        rows = np.sort(np.random.default_rng(0).choice(W.shape[0], k, replace=False))
+        arrays["new_weights"], arrays["new_weights_rows"] = W[rows], rows.astype(np.float64)
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), v)
+
+
 # ---------------------------------------------------------------------------------------------
 # --via ctx: NumPy + ctypes only
 # ---------------------------------------------------------------------------------------------
@@ -481,7 +506,8 @@ def run_via_ctx(args):
         nat.call("dbgsom_ctx_set_topology", ctx, hop.ctypes.data, M)
         chg, E, a = np.empty(1), np.empty(M), np.empty(M)
         Wn = {}
-        for algo in dict.fromkeys([args.algorithm, "exact"]):
+        dumped = None
+        for algo in (dict.fromkeys([args.algorithm, "exact"]) if args.full else [args.algorithm]):
             nat.call("dbgsom_ctx_set_option", ctx, b"algorithm", nat.ALGORITHMS[algo])
             nat.call("dbgsom_ctx_set_option", ctx, b"timing", 0)   # the timed steps run un-instrumented
             nat.call("dbgsom_ctx_set_weights", ctx, W0.ctypes.data, M)
@@ -505,6 +531,13 @@ def run_via_ctx(args):
             per = np.zeros((world, args.steps))
             per[rank] = np.diff(np.array([t0] + marks))
             per = allsum(per.reshape(-1)).reshape(world, args.steps).max(axis=0)
+            if args.dump_outputs and rank == 0 and algo == args.algorithm:
+                dumped = {"new_weights": np.empty((M, d)), "errors": E.copy(), "activations": a.copy(),
+                          "change_total": chg.copy()}
+                nat.call("dbgsom_ctx_get_weights", ctx, 1, dumped["new_weights"].ctypes.data, M)
+            if not args.full:
+                out[algo] = (elapsed, None, float(np.median(per)))
+                continue
             nat.call("dbgsom_ctx_set_option", ctx, b"timing", 1)
             for _ in range(3):   # phase times from three more (untimed) steps with HIP events
                 step()
@@ -520,7 +553,6 @@ def run_via_ctx(args):
     if rank != 0:
         return
     elapsed, ph, med = out[args.algorithm]
-    e_elapsed, e_ph, e_med = out["exact"]
     line = {
         "metric": "samples/sec/epoch (BMU+update)", "value": n_total / med,
         "unit": "samples/s/epoch", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -534,19 +566,24 @@ def run_via_ctx(args):
                    "bmu_algorithm": args.algorithm,
                    "via": "ctx: dbgsom_ctx_* through ctypes, NumPy host arrays only"
                           + ("; collective: RCCL inside the library (dbgsom_ctx_set_rccl)" if comm else "")},
-        "roofline": exact_roofline(n, d, M, e_ph["bmu"]) if args.algorithm == "exact" else
-        {"stage": "whole BMU search", "bound": "mfma", "dtype": "f64-equivalent",
-         "achieved": 2.0 * n * M * d / (ph["bmu"] * 1e-3) / 1e12, "peak": F64_MFMA_PEAK_TFLOPS,
-         "unit": "TFLOP/s (2 N M d of the search it replaces)",
-         "frac": 2.0 * n * M * d / (ph["bmu"] * 1e-3) / 1e12 / F64_MFMA_PEAK_TFLOPS, "traffic": None,
-         "kernel_ms": ph["bmu"]},
-        "phases_ms": ph,
-        "exact": {"value": n_total / e_med, "ms_per_step": e_med * 1e3,
-                  "prototypes_identical_to_headline": bool(np.array_equal(Wn["exact"], Wn[args.algorithm],
-                                                                           equal_nan=True))},
         "host_s": {"generate": t_gen, "dbgsom_ctx_load (PCIe upload + norms)": t_up},
         "torch_imported": "torch" in sys.modules,
     }
+    if args.full:
+        e_elapsed, e_ph, e_med = out["exact"]
+        line.update({
+            "roofline": exact_roofline(n, d, M, e_ph["bmu"]) if args.algorithm == "exact" else
+            {"stage": "whole BMU search", "bound": "mfma", "dtype": "f64-equivalent",
+             "achieved": 2.0 * n * M * d / (ph["bmu"] * 1e-3) / 1e12, "peak": F64_MFMA_PEAK_TFLOPS,
+             "unit": "TFLOP/s (2 N M d of the search it replaces)",
+             "frac": 2.0 * n * M * d / (ph["bmu"] * 1e-3) / 1e12 / F64_MFMA_PEAK_TFLOPS, "traffic": None,
+             "kernel_ms": ph["bmu"]},
+            "phases_ms": ph,
+            "exact": {"value": n_total / e_med, "ms_per_step": e_med * 1e3,
+                      "prototypes_identical_to_headline": bool(np.array_equal(Wn["exact"], Wn[args.algorithm],
+                                                                               equal_nan=True))}})
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, dumped)
     print(json.dumps(line))
 
 
@@ -575,11 +612,12 @@ class Harness:
             self.td.all_reduce(t, op=self.td.ReduceOp.MAX)
         return float(t.item())
 
-    def timed_epochs(self, be, step_fn, warmup, steps):
+    def timed_epochs(self, be, step_fn, warmup, steps, phases=True, after_timed=None):
         """W untimed steps, then exactly `steps` timed ones bracketed by barrier + synchronize, with
         the context's event instrumentation OFF (ten event records per epoch are worth 2-5 % at small
-        shapes); then min(steps, 5) more steps, untimed, with it ON for the per-phase HIP-event
-        times (events on the context's stream).  Returns (max-over-ranks seconds, median ms per phase)."""
+        shapes); `after_timed()` is called here; then (`phases`) min(steps, 5) more steps, untimed, with
+        it ON for the per-phase HIP-event times (events on the context's stream).  Returns
+        (max-over-ranks seconds, median ms per phase or None)."""
         be.phase_log = None
         be._set("timing", 0)
         for _ in range(warmup):
@@ -597,6 +635,10 @@ class Harness:
         if self.grouped:
             self.td.all_reduce(t, op=self.td.ReduceOp.MAX)
         self.step_seconds = t.cpu().numpy()   # of the last timed regime, max over ranks per step
+        if after_timed is not None:
+            after_timed()
+        if not phases:
+            return elapsed, None
         be._set("timing", 1)
         be.phase_log = []
         for _ in range(min(steps, 5)):
@@ -608,22 +650,35 @@ class Harness:
         return elapsed, dict(zip(PHASES, np.median(log, axis=0).tolist()))
 
 
-def frozen_map_regime(h, algorithm, X, W0, hop, sigma, gamma, steps=None, warmup=None, assignments=False):
+def frozen_map_regime(h, algorithm, X, W0, hop, sigma, gamma, steps=None, warmup=None, assignments=False,
+                      full=True, outputs=None):
     """every step = one full epoch from the SAME frozen prototypes (resident in HBM,
-    DBGSOM_EPOCH_FROZEN), new prototypes stay in HBM."""
+    DBGSOM_EPOCH_FROZEN), new prototypes stay in HBM.  `outputs` (a dict) receives what the last
+    timed step handed its caller; full=False stops after the timed steps (no phase times, filter
+    statistics or prototypes: the returned phases, counts and prototypes are None)."""
     from dbgsom_amd.backend import RESIDENT, HipBackend
 
     be = HipBackend(h.local, algorithm=algorithm)
     be.load_device(X)
     be.set_weights(W0)
     M = W0.shape[0]
+    last = {}
 
     def step():
-        be.epoch(RESIDENT, hop, sigma, gamma, "compact", False, keep_on_device=True, frozen=True)
+        last["res"] = be.epoch(RESIDENT, hop, sigma, gamma, "compact", False, keep_on_device=True, frozen=True)
+
+    def keep_outputs():
+        res = last["res"]
+        outputs.update(new_weights=be.get_weights(1), errors=res.errors, activations=res.activations,
+                       change_total=np.array([res.change_total]))
 
     elapsed, phases = h.timed_epochs(be, step, h.args.warmup if warmup is None else warmup,
-                                     h.args.steps if steps is None else steps)
+                                     h.args.steps if steps is None else steps, phases=full,
+                                     after_timed=None if outputs is None else keep_outputs)
     info = {"filter_log": be.filter_log[-1] if be.filter_log else None, "step_seconds": h.step_seconds.copy()}
+    if not full:
+        be.release()
+        return elapsed, phases, info, None, None
     counts = None
     if be.filter_log and be.filter_log[-1][0] == "filtered":
         counts = be.filter_counts()
@@ -779,20 +834,27 @@ def main():
     ap.add_argument("--samples-per-gpu", type=int, default=None, help="override N per GPU")
     ap.add_argument("--algorithm", default="filtered", choices=["filtered", "exact"],
                     help="BMU search of the headline value (both give identical results)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline, also measure and check everything else: per-phase times and "
+                         "rooflines, the all-pairs exact search, and what the options below enable")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as float64 DIR/<name>.npy (at most 64 MB)")
     ap.add_argument("--fine-phase", type=int, default=1,
-                    help="also time a trained map in the fine phase (sigma_end, evolving W) with "
+                    help="--full: also time a trained map in the fine phase (sigma_end, evolving W) with "
                          "the exact and the hinted filtered search (0 disables)")
     ap.add_argument("--other-data", type=int, default=1,
-                    help="N = 1, workload c4: also run the weakly clustered data sets c4iso and c2nn")
+                    help="--full, N = 1, workload c4: also run the weakly clustered data sets c4iso and c2nn")
     ap.add_argument("--other-workloads", type=int, default=1,
-                    help="N = 1, workload c4: also run BASELINE's c3, c2 and the c5 shard, each with its own "
-                         "rooflines, CPU leg on a bounded row sample and parity gate (`other_workloads`)")
+                    help="--full, N = 1, workload c4: also run BASELINE's c3, c2 and the c5 shard, each with its "
+                         "own rooflines, CPU leg on a bounded row sample and parity gate (`other_workloads`)")
     ap.add_argument("--fit", type=int, default=1,
-                    help="N = 1, workload c4: also time a whole SomVQ.fit on the workload's samples (`fit`)")
+                    help="--full, N = 1, workload c4: also time a whole SomVQ.fit on the workload's samples (`fit`)")
     ap.add_argument("--cpu-sample", type=int, default=1_000_000,
-                    help="upper bound of rows timed by the CPU baseline (0 disables it); the "
+                    help="--full: upper bound of rows timed by the CPU baseline (0 disables it); the "
                          "actual sample is sized for ~15 s of CPU work")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.via == "ctx":
         return run_via_ctx(args)
 
@@ -884,13 +946,16 @@ def main():
     sigma = 0.2 * np.sqrt(M)  # BaseSom.py:876 at epoch 0
 
     results = {}
-    gate = world == 1 and args.cpu_sample > 0   # the parity gate needs the CPU leg's winners
-    for algo in dict.fromkeys([args.algorithm, "exact"]):  # headline first, exact always reported
+    gate = args.full and world == 1 and args.cpu_sample > 0   # the parity gate needs the CPU leg's winners
+    outputs = {} if args.dump_outputs and rank == 0 else None
+    # headline first; with --full the all-pairs search is always reported beside it
+    for algo in (dict.fromkeys([args.algorithm, "exact"]) if args.full else [args.algorithm]):
         results[algo] = frozen_map_regime(h, algo, X, W0, hop, sigma, gamma,
-                                          assignments=gate and algo == args.algorithm)
-    fine = fine_phase_regime(h, X, W0, M, hop, gamma, n_total) if args.fine_phase else None
+                                          assignments=gate and algo == args.algorithm, full=args.full,
+                                          outputs=outputs if algo == args.algorithm else None)
+    fine = fine_phase_regime(h, X, W0, M, hop, gamma, n_total) if args.full and args.fine_phase else None
     weak = None
-    if world > 1 and args.scaling == "strong" and not args.samples_per_gpu:
+    if args.full and world > 1 and args.scaling == "strong" and not args.samples_per_gpu:
         # beside the metric's strong-scaling line: every rank with the workload's full N
         Xw = make_shard_device(torch, n_work, d, seed, device, rank=rank, kind=kind)
         if args.workload in BF16_WORKLOADS:
@@ -903,17 +968,7 @@ def main():
     out = None
     if rank == 0:
         elapsed, phases, info, counts, Wn = results[args.algorithm]
-        e_elapsed, e_phases, _, _, e_Wn = results["exact"]
-        exact_roof = exact_roofline(n_gpu, d, M, e_phases["bmu"])
-        if args.algorithm == "exact":
-            roofs, roof = [exact_roof], exact_roof
-        else:
-            roofs = rooflines(args.workload if n_gpu == n_work else None, n_gpu, d, M, xbytes, phases,
-                              int(info.get("sweep_planes", 1)), counts, bool(info.get("refined")))
-            # the dominant kernel of the step = the longest stage that is one kernel family
-            roof = max(roofs[:2], key=lambda r: r["kernel_ms"]) if len(roofs) >= 2 else roofs[0]
         med = float(np.median(info["step_seconds"]))    # the median epoch (max over ranks per step)
-        e_med = float(np.median(results["exact"][2]["step_seconds"]))
         out = {
             "metric": "samples/sec/epoch (BMU+update)",
             "value": n_total / med,
@@ -930,10 +985,8 @@ def main():
             "dtype": "f64",
             "data": ("synthetic: numpy.random.default_rng(%d [+ rank]) Gaussian blobs, SURVEY.md 8(d)" % seed
                      if os.environ.get("DBGSOM_BENCH_DATA", "numpy") != "torch" else "synthetic (torch device generator)"),
-            # the data-independent floor (all-pairs search, the same inputs) and both against F_A = 2 N M d
-            "floor": n_total / e_med,
+            # the headline against F_A = 2 N M d
             "frac_vs_2NMd": 2.0 * n_total * M * d / med / 1e12 / (F64_MFMA_PEAK_TFLOPS * world),
-            "floor_frac_vs_2NMd": 2.0 * n_total * M * d / e_med / 1e12 / (F64_MFMA_PEAK_TFLOPS * world),
             "config": {"workload": cfg_name, "samples_total": n_total, "samples_per_gpu": n_gpu,
                        "features": d, "prototypes": M,
                        "x_storage": "bf16" if args.workload in BF16_WORKLOADS else "f32",
@@ -941,11 +994,23 @@ def main():
                        "map": "frozen (same prototypes every step)",
                        "bmu_algorithm": args.algorithm,
                        "via": "HipBackend -> dbgsom_ctx_epoch (one C-ABI call per step)"},
-            "roofline": roof,
-            "rooflines": roofs,
             "build": source_hash(),
-            "phases_ms": phases,
         }
+    if rank == 0 and args.full:
+        e_elapsed, e_phases, _, _, e_Wn = results["exact"]
+        exact_roof = exact_roofline(n_gpu, d, M, e_phases["bmu"])
+        if args.algorithm == "exact":
+            roofs, roof = [exact_roof], exact_roof
+        else:
+            roofs = rooflines(args.workload if n_gpu == n_work else None, n_gpu, d, M, xbytes, phases,
+                              int(info.get("sweep_planes", 1)), counts, bool(info.get("refined")))
+            # the dominant kernel of the step = the longest stage that is one kernel family
+            roof = max(roofs[:2], key=lambda r: r["kernel_ms"]) if len(roofs) >= 2 else roofs[0]
+        e_med = float(np.median(results["exact"][2]["step_seconds"]))
+        # the data-independent floor (all-pairs search, the same inputs), also against F_A = 2 N M d
+        out.update({"floor": n_total / e_med,
+                    "floor_frac_vs_2NMd": 2.0 * n_total * M * d / e_med / 1e12 / (F64_MFMA_PEAK_TFLOPS * world),
+                    "roofline": roof, "rooflines": roofs, "phases_ms": phases})
         if info.get("candidates_per_workgroup"):
             out["filter"] = {"sweep_planes": info.get("sweep_planes"),
                              "candidates_per_workgroup": info["candidates_per_workgroup"],
@@ -958,19 +1023,19 @@ def main():
             out["fine_phase"] = fine
         if weak:
             out["weak_scaling_same_run"] = weak
-    if world == 1 and args.other_data and args.workload == "c4" and not args.samples_per_gpu:
+    if args.full and world == 1 and args.other_data and args.workload == "c4" and not args.samples_per_gpu:
         out["other_data"] = {name: other_data_regime(h, torch, device, name) for name in ("c4iso", "c2nn")}
     if rank == 0:
-        if args.cpu_sample > 0 and world == 1:  # the CPU baseline is reported at N = 1 only
+        if args.full and args.cpu_sample > 0 and world == 1:  # the CPU baseline is reported at N = 1 only
             ns = min(args.cpu_sample, X.shape[0])
             Xs = X[:ns].float().cpu().numpy()
             out["cpu_baseline"] = cpu_baseline(Xs, W0, hop, sigma, gamma, n_gpu)
             out["gpu_vs_cpu"] = out["value"] / out["cpu_baseline"]["value"]
             out["parity"] = parity_gate(X, W0, hop, sigma, gamma, results[args.algorithm][2],
                                         results[args.algorithm][4], xbytes)
-        if world == 1 and args.fit and args.workload == "c4" and not args.samples_per_gpu:
+        if args.full and world == 1 and args.fit and args.workload == "c4" and not args.samples_per_gpu:
             out["fit"] = fit_regime(X.float().cpu().numpy(), 1024)
-        if world == 1 and args.other_workloads and args.workload == "c4" and not args.samples_per_gpu:
+        if args.full and world == 1 and args.other_workloads and args.workload == "c4" and not args.samples_per_gpu:
             del X
             torch.cuda.empty_cache()
             out["other_workloads"] = {name: workload_entry(h, torch, device, name, 4.0 if args.cpu_sample > 0 else 0.0)
@@ -983,6 +1048,8 @@ def main():
             iso = out["other_data"]["c4iso"]["auto"]
             out["value_isotropic"] = iso["value"]
             out["ms_per_step_isotropic"] = iso["ms_per_step"]
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(out))
         if out.get("parity") and not out["parity"]["ok"]:
             sys.stderr.write("bench.py: PARITY GATE FAILED: %r\n" % (out["parity"],))

@@ -279,6 +279,30 @@ def test_bench_generators_in_chunks_are_the_whole_arrays():
     assert np.abs(a[:, None, :] - ca[None]).sum(axis=2).min(axis=1).max() < 8 * 6.0   # ... around the same 32 centres
 
 
+def test_bench_dump_outputs_stays_within_its_limit(tmp_path):
+    """bench.py --dump-outputs: float64 .npy files of at most 64 MB in all; prototypes of a C4 map go whole, those
+    of a C5 map (67 MB of float64) as the same seeded sample of rows on every run, their indices beside them."""
+    import bench
+
+    for M, d in ((1024, 784), (4096, 2048)):
+        W = np.random.default_rng(M).standard_normal((M, d))
+        arrays = {"new_weights": W, "errors": np.ones(M), "activations": np.arange(M), "change_total": [2.5]}
+        paths = [tmp_path / f"{M}_a", tmp_path / f"{M}_b"]
+        for p in paths:
+            bench.dump_outputs(str(p), arrays)
+        assert sum(f.stat().st_size for f in paths[0].iterdir()) <= 64_000_000
+        got = [{f.stem: np.load(f) for f in p.iterdir()} for p in paths]
+        assert all(v.dtype == np.float64 for v in got[0].values())
+        assert np.array_equal(got[0]["activations"], np.arange(M)) and got[0]["change_total"][0] == 2.5
+        if M == 1024:
+            assert "new_weights_rows" not in got[0] and np.array_equal(got[0]["new_weights"], W)
+        else:
+            rows = got[0]["new_weights_rows"].astype(np.int64)
+            assert 3000 < rows.size < M and np.all(np.diff(rows) > 0)
+            assert np.array_equal(got[0]["new_weights"], W[rows])
+            assert np.array_equal(got[1]["new_weights_rows"], got[0]["new_weights_rows"])
+
+
 def test_finite_check_keyword_follows_the_installed_scikit_learn():
     """check_array's keyword was renamed (force_all_finite -> ensure_all_finite in scikit-learn 1.6): the estimator
     passes whichever exists, and only defers the check to the device for the default backend in one process."""

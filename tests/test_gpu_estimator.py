@@ -306,7 +306,7 @@ def test_bench_under_torchrun_single_rank_rccl():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"),
            "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "c2", "--cpu-sample", "0",
-           "--fine-phase", "0"]
+           "--fine-phase", "0", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
@@ -327,7 +327,7 @@ def test_bench_via_ctx_under_torchrun_without_torch_in_the_workers():
     env = dict(os.environ, DBGSOM_FORCE_COLLECTIVE="1", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"),
-           "--gpus", "1", "--steps", "3", "--warmup", "2", "--workload", "c2", "--via", "ctx"]
+           "--gpus", "1", "--steps", "3", "--warmup", "2", "--workload", "c2", "--via", "ctx", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     js = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -350,7 +350,7 @@ def test_bench_two_ranks_strong_scaling_rehearsal_on_one_gpu():
     env = dict(os.environ, DBGSOM_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "2", "--workload", "c2", "--fine-phase", "0"]
+           "--gpus", "2", "--steps", "3", "--warmup", "2", "--workload", "c2", "--fine-phase", "0", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -361,6 +361,40 @@ def test_bench_two_ranks_strong_scaling_rehearsal_on_one_gpu():
     assert js["weak_scaling_same_run"]["samples_per_gpu"] == 60_000
     assert js["exact"]["prototypes_identical_to_headline"] is True
     assert "cpu_baseline" not in js and js["roofline"]["frac"] > 0
+
+
+def test_plain_bench_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) prints the headline line without the measurements --full adds, and
+    --dump-outputs writes what the last timed step handed its caller; the HipBackend path and the ctypes-only
+    path of the same workload hand over the same epoch (hit counts exactly, the float64 rest to rounding: gamma
+    comes from moments summed in another order)."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = {}
+    for via in ("backend", "ctx"):
+        dumps[via] = str(tmp_path / via)
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+               "--workload", "c2", "--via", via, "--dump-outputs", dumps[via]]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        js = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+        assert js["steps"] == 3 and js["warmup"] == 1 and js["ms_per_step"] > 0 and js["higher_is_better"] is True
+        assert js["value"] == pytest.approx(60_000 / (js["ms_per_step"] * 1e-3))
+        for key in ("exact", "phases_ms", "roofline", "fine_phase", "cpu_baseline", "parity"):
+            assert key not in js, key
+    n, d, rows, cols = 60_000, 784, 22, 23
+    got = {via: {f[:-4]: np.load(os.path.join(p, f)) for f in os.listdir(p)} for via, p in dumps.items()}
+    b, c = got["backend"], got["ctx"]
+    assert sorted(b) == sorted(c) == ["activations", "change_total", "errors", "new_weights"]
+    assert all(v.dtype == np.float64 for v in list(b.values()) + list(c.values()))
+    assert b["new_weights"].shape == (rows * cols, d) and b["activations"].sum() == n
+    assert np.array_equal(b["activations"], c["activations"])
+    for name in ("new_weights", "errors", "change_total"):
+        np.testing.assert_allclose(b[name], c[name], rtol=1e-9, atol=1e-12, err_msg=name)
 
 
 def test_full_size_c3_and_c2_properties():

@@ -29,13 +29,13 @@ if [ "$1" = "pmc" ]; then
   exit 0
 fi
 cd $R
-python bench.py --steps 20 --warmup 5 > $O/${TAG}_final_c4_bench.json 2> $O/c4_bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/${TAG}_final_c4_bench.json 2> $O/c4_bench.err
 echo "bench c4 done"
-for w in c3 c2 c5; do python bench.py --workload $w --steps 20 --warmup 5 --cpu-sample 0 > $O/${TAG}_final_${w}_bench.json 2>/dev/null; done
-python bench.py --via ctx --steps 20 --warmup 5 > $O/${TAG}_final_c4_bench_via_ctx.json 2>/dev/null
+for w in c3 c2 c5; do python bench.py --full --workload $w --steps 20 --warmup 5 --cpu-sample 0 > $O/${TAG}_final_${w}_bench.json 2>/dev/null; done
+python bench.py --full --via ctx --steps 20 --warmup 5 > $O/${TAG}_final_c4_bench_via_ctx.json 2>/dev/null
 echo "bench others done"
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c4 -- python3 $R/bench.py --steps 10 --warmup 5 --cpu-sample 0 --other-data 0 --other-workloads 0 --fit 0 > $O/stats_c4_bench.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c4 -- python3 $R/bench.py --full --steps 10 --warmup 5 --cpu-sample 0 --other-data 0 --other-workloads 0 --fit 0 > $O/stats_c4_bench.json 2>/dev/null
 cp $(find $O/stats_c4 -name "*kernel_stats.csv" | head -1) $O/${TAG}_final_c4_kernel_stats.csv
 rm -rf $O/stats_c4
 for w in c4 c3 c5 c2; do rocprofv3 --kernel-trace --output-format csv -d $O/kt_$w -- python3 $R/tools/run_frozen.py $w 10 filtered > /dev/null 2>&1; (cd $R && python tools/trace_epoch.py $O/kt_$w > $O/${TAG}_final_${w}_epoch_trace.txt); rm -rf $O/kt_$w; done
