@@ -31,6 +31,9 @@ COLL_ALLREDUCE, COLL_REDUCE_SCATTER, COLL_ALLGATHER = 0, 1, 2
 CENTRES_COMPACT, CENTRES_ALIGNED = 0, 1
 LAYOUTS = {"compact": CENTRES_COMPACT, "aligned": CENTRES_ALIGNED}
 MAX_PROTOTYPES = 16000
+# counters of dbgsom_sparse_code / dbgsom_ctx_sparse_code (DBGSOM_SC_COUNTS, in this order)
+SC_COUNTS = ("samples", "iterations", "max_iterations", "drops", "degenerate", "early_stops", "aa_retries",
+             "overflow", "max_active", "multi_drops", "g_rows")
 
 _i64, _vp, _ci, _dbl, _sz = (ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_double,
                              ctypes.c_size_t)
@@ -88,6 +91,12 @@ SIGNATURES = {
     "dbgsom_ctx_write_weight_rows": (_ci, [_vp, _i64, _i64, _vp]),
     "dbgsom_ctx_bmu": (_ci, [_vp, _vp, _i64, _ci, _ci, _vp, _vp]),
     "dbgsom_ctx_bmu_query": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _ci, _ci, _vp, _vp]),
+    "dbgsom_sparse_code_workspace_bytes": (_sz, [_i64, _i64, _i64, _ci]),
+    "dbgsom_sparse_code": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _i64, _i64, _ci, _ci, _vp, _i64, _vp, _vp, _vp,
+                                 _vp, _sz, _vp]),
+    "dbgsom_sparse_code_timing": (_ci, [_ci]),
+    "dbgsom_sparse_code_stage_ms": (_ci, [_vp]),
+    "dbgsom_ctx_sparse_code": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _ci, _vp, _i64, _vp, _vp, _vp]),
     "dbgsom_ctx_exp_similarity": (_ci, [_vp, _vp, _i64, _dbl, _vp]),
     "dbgsom_ctx_epoch": (_ci, [_vp, _vp, _i64, _ci, _dbl, _dbl, _ci, _ci, _vp, _vp, _vp, _vp, _vp,
                                _vp]),

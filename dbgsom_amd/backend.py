@@ -163,6 +163,24 @@ class HotPathBackend:
         np.add.at(h, (winners, self._y), 1.0)
         return self._reduce_host(h.reshape(-1)).reshape(M, n_classes).astype(np.int64)
 
+    # -- sparse coding (BaseSom.transform, SomClassifier.predict_proba); host default ----------------
+    def sparse_code(self, W, X, P=None, max_iter=1000, n_jobs=None):
+        """Non-negative LARS-lasso code of the rows of X over the rows of W, scikit-learn's
+        ``SparseCoder(normalize(W), "lasso_lars", positive_code=True, transform_alpha=0)`` on
+        ``normalize(X)`` (BaseSom.py:241-268).  P (M x C) given: returns the class probabilities
+        ``code @ P`` normalised per row (SomClassifier.py:178-220) instead of the code."""
+        from sklearn.decomposition import SparseCoder
+        from sklearn.preprocessing import normalize
+
+        coder = SparseCoder(dictionary=normalize(np.asarray(W)), n_jobs=n_jobs, positive_code=True,
+                            transform_alpha=0, transform_algorithm="lasso_lars",
+                            transform_max_iter=max_iter)
+        code = coder.transform(normalize(X))
+        if P is None:
+            return code
+        raw = code @ P
+        return raw / raw.sum(axis=1)[np.newaxis].T
+
     def release(self):
         pass
 
@@ -561,6 +579,55 @@ class HipBackend(HotPathBackend):
         """Whether a k-BMU query on N other samples would go through the filtered search."""
         return (k == 1 and self.algorithm != "exact" and N >= self._get("filter_min_query_rows")
                 and self.FILTER_MIN_PROTOTYPES <= M <= _native.MAX_PROTOTYPES and d <= 43690)
+
+    # -- sparse coding --------------------------------------------------------------------------
+    sc_chunk_rows = property(lambda self: self._get("sc_chunk_rows"), lambda self, v: self._set("sc_chunk_rows", v))
+    sc_cap = property(lambda self: self._get("sc_cap"), lambda self, v: self._set("sc_cap", v))
+
+    def sparse_code(self, W, X, P=None, max_iter=1000, n_jobs=None):
+        """The host default's result computed on the device (csrc/sparse_code.hip); n_jobs is
+        ignored.  W may be RESIDENT.  The counters of the call land in ``sparse_code_counts``;
+        like scikit-learn, one ConvergenceWarning when a row skipped a degenerate regressor or
+        stopped early."""
+        X = np.ascontiguousarray(X)
+        if X.dtype not in (np.float32, np.float64):
+            X = X.astype(np.float64)
+        if W is RESIDENT:
+            self._require_loaded()
+            keep, p, M = None, None, self._get("prototypes")
+            d = self._d
+        else:
+            keep = np.ascontiguousarray(W, dtype=np.float64)
+            if keep.ndim != 2:
+                raise ValueError("W must be 2-D")
+            p, (M, d) = keep.ctypes.data, keep.shape
+        if X.ndim != 2 or X.shape[1] != d:
+            raise ValueError("prototype / sample feature mismatch")
+        N = X.shape[0]
+        counts = np.zeros(len(_native.SC_COUNTS), dtype=np.uint64)
+        if P is None:
+            out, Pc, C, code_p, proba_p = np.empty((N, M)), None, 0, None, None
+            code_p = out.ctypes.data
+        else:
+            Pc = np.ascontiguousarray(P, dtype=np.float64)
+            if Pc.ndim != 2 or Pc.shape[0] != M:
+                raise ValueError("P must have one row per prototype")
+            C = Pc.shape[1]
+            out = np.empty((N, C))
+            code_p, proba_p = None, out.ctypes.data
+        self._call("dbgsom_ctx_sparse_code", self._ctx, X.ctypes.data if N else None, _x_dtype_code(X.dtype), N, d,
+                   p, M, int(max_iter), None if Pc is None else Pc.ctypes.data, C, code_p, proba_p,
+                   counts.ctypes.data)
+        self.sparse_code_counts = dict(zip(_native.SC_COUNTS, (int(v) for v in counts)))
+        if counts[4] or counts[5]:
+            import warnings
+
+            from sklearn.exceptions import ConvergenceWarning
+
+            warnings.warn("sparse coding: %d degenerate regressor(s) skipped, %d early stop(s) of the LARS path "
+                          "(scikit-learn warns the same way)" % (int(counts[4]), int(counts[5])),
+                          ConvergenceWarning)
+        return out
 
     # -- a2 -------------------------------------------------------------------------------------
     def exp_similarity(self, distances, gamma):

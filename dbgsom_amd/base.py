@@ -558,17 +558,12 @@ class BaseSom(BaseEstimator):
     # parts of the surface outside the accelerated path (kept for drop-in completeness)
     # ------------------------------------------------------------------------------------------
     def transform(self, X, y=None) -> np.ndarray:
-        """Non-negative LARS-lasso code of X over the prototypes (BaseSom.py:241-268;
-        scikit-learn's SparseCoder on the host -- a different algorithm, not accelerated)."""
-        from sklearn.decomposition import SparseCoder
-        from sklearn.preprocessing import normalize
-
+        """Non-negative LARS-lasso code of X over the prototypes (BaseSom.py:241-268): scikit-learn's
+        SparseCoder on normalize(X) with dictionary normalize(weights_), computed by the backend
+        (on the MI355X: csrc/sparse_code.hip; n_jobs only matters to the host default)."""
         check_is_fitted(self)
         X = check_array(X, dtype=[np.float64, np.float32])
-        coder = SparseCoder(dictionary=normalize(self.weights_), n_jobs=self.n_jobs,
-                            positive_code=True, transform_alpha=0,
-                            transform_algorithm="lasso_lars")
-        return coder.transform(normalize(X))
+        return self._engine().sparse_code(self.weights_, X, n_jobs=self.n_jobs)
 
     def _grow_vertical(self, X, y=None) -> None:
         """Fit a child map on the Voronoi set of every neuron whose error exceeds 1.5x the

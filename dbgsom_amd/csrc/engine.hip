@@ -260,6 +260,9 @@ struct dbgsom_ctx {
     bool last_refined = false;
     bool last_k2_filtered = false;  // the last k = 2 search went through the pruning form
     int64_t filter_min_query_rows = 32768;
+    int64_t sc_chunk_rows = 32768;  // sparse coding: query rows per chunk
+    int64_t sc_cap = 0;             // sparse coding: active-set cap of the LDS path (0 = library default)
+    DevBuf sc_ws, sc_x, sc_w, sc_p, sc_code, sc_proba, sc_cnt;
     int64_t max_mean_candidates = 320;
     // samples
     Samples xs, xq;
@@ -1167,7 +1170,7 @@ int dbgsom_ctx_create(int device, dbgsom_ctx **out) {
     {&(c)->y, &(c)->hop, &(c)->hop_stage, &(c)->Wb[0], &(c)->Wb[1], &(c)->ww, &(c)->idx[0], &(c)->idx[1], &(c)->dist,  \
      &(c)->kw, &(c)->sums, &(c)->acc_ws, &(c)->sm_ws, &(c)->filt_ws, &(c)->scal, &(c)->qidx, &(c)->qdist, &(c)->red,  \
      &(c)->hist, &(c)->stage_dev, &(c)->part_order, &(c)->part_ws, &(c)->part_counts, &(c)->shiftb, &(c)->shard_send,    \
-     &(c)->shard_gather}
+     &(c)->shard_gather, &(c)->sc_ws, &(c)->sc_x, &(c)->sc_w, &(c)->sc_p, &(c)->sc_code, &(c)->sc_proba, &(c)->sc_cnt}
 
 int dbgsom_ctx_destroy(dbgsom_ctx *c) {
     if (!c) return DBGSOM_OK;
@@ -1216,6 +1219,12 @@ int dbgsom_ctx_set_option(dbgsom_ctx *c, const char *name, int64_t v) {
     } else if (!strcmp(name, "filter_min_query_rows")) {
         DBGSOM_REQUIRE(v >= 0, "filter_min_query_rows must be >= 0");
         c->filter_min_query_rows = v;
+    } else if (!strcmp(name, "sc_chunk_rows")) {
+        DBGSOM_REQUIRE(v >= 1 && v <= ((int64_t)1 << 22), "sc_chunk_rows must be in [1, 2^22]");
+        c->sc_chunk_rows = v;
+    } else if (!strcmp(name, "sc_cap")) {
+        DBGSOM_REQUIRE(v >= 0 && v <= 64, "sc_cap must be in [0, 64] (0 = the library's cap)");
+        c->sc_cap = v;
     } else if (!strcmp(name, "max_mean_candidates")) {
         DBGSOM_REQUIRE(v >= 1, "max_mean_candidates must be >= 1");
         c->max_mean_candidates = v;
@@ -1246,6 +1255,8 @@ int dbgsom_ctx_get_option(dbgsom_ctx *c, const char *name, int64_t *v) {
     else if (!strcmp(name, "k2_filtered")) *v = c->last_k2_filtered ? 1 : 0;
     else if (!strcmp(name, "filter_min_query_rows")) *v = c->filter_min_query_rows;
     else if (!strcmp(name, "max_mean_candidates")) *v = c->max_mean_candidates;
+    else if (!strcmp(name, "sc_chunk_rows")) *v = c->sc_chunk_rows;
+    else if (!strcmp(name, "sc_cap")) *v = c->sc_cap;
     else if (!strcmp(name, "n_samples")) *v = c->xs.dtype < 0 ? 0 : c->xs.N;
     else if (!strcmp(name, "features")) *v = c->xs.dtype < 0 ? 0 : c->xs.d;
     else if (!strcmp(name, "padded_features")) *v = c->xs.dtype < 0 ? 0 : c->xs.dp;
@@ -1596,6 +1607,64 @@ int dbgsom_ctx_bmu_query(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_
     Wq.release(); wwq.release(); iq.release(); dq.release(); fws.release();
     if (Nq * dp * (int64_t)dtype_size(x_dtype) > ((int64_t)256 << 20)) s.release();  // do not sit on a large one-off batch
     return rc;
+}
+
+// ------------------------------------------------------------------------------------------
+// sparse coding (transform / predict_proba): csrc/sparse_code.hip, in chunks of query rows
+// ------------------------------------------------------------------------------------------
+int dbgsom_ctx_sparse_code(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                           const double *W_host, int64_t M, int max_iter, const double *P_host, int64_t C,
+                           double *code_host, double *proba_host, uint64_t *counts_host) {
+    CTX_CHECK(c);
+    DBGSOM_REQUIRE(x_dtype == DBGSOM_F32 || x_dtype == DBGSOM_F64, "x_dtype must be DBGSOM_F32 or DBGSOM_F64");
+    DBGSOM_REQUIRE(counts_host && Nq >= 0 && d >= 1 && M >= 1 && max_iter >= 0 && (Nq == 0 || Xq_host),
+                   "bad arguments");
+    DBGSOM_REQUIRE(!proba_host || (P_host && C >= 1), "proba_host needs P_host and C >= 1");
+    int64_t ldw = d;
+    const double *Wd = nullptr;
+    if (W_host) {
+        TRY(c->sc_w.reserve((size_t)M * d * 8));
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(c->sc_w.p, W_host, (size_t)M * d * 8, hipMemcpyHostToDevice, c->stream));
+        Wd = c->sc_w.as<double>();
+    } else {
+        if (c->M < 1 || c->xs.dtype < 0 || c->M != M || c->xs.d != d) {
+            set_error("dbgsom_ctx_sparse_code: no resident prototypes of %lld x %lld rows; pass W_host",
+                      (long long)M, (long long)d);
+            return DBGSOM_ESTATE;
+        }
+        Wd = c->Wb[c->cur].as<double>();
+        ldw = c->xs.dp;
+    }
+    TRY(c->sc_cnt.reserve(DBGSOM_SC_COUNTS * 8));
+    DBGSOM_HIP_CHECK(hipMemsetAsync(c->sc_cnt.p, 0, DBGSOM_SC_COUNTS * 8, c->stream));
+    if (proba_host) {
+        TRY(c->sc_p.reserve((size_t)M * C * 8));
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(c->sc_p.p, P_host, (size_t)M * C * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    const int64_t chunk = std::min<int64_t>(std::max<int64_t>(Nq, 1), c->sc_chunk_rows);
+    const size_t es = dtype_size(x_dtype);
+    TRY(c->sc_ws.reserve(dbgsom_sparse_code_workspace_bytes(chunk, d, M, max_iter)));
+    TRY(c->sc_x.reserve((size_t)chunk * d * es));
+    if (code_host) TRY(c->sc_code.reserve((size_t)chunk * M * 8));
+    if (proba_host) TRY(c->sc_proba.reserve((size_t)chunk * C * 8));
+    for (int64_t r0 = 0; r0 < Nq; r0 += chunk) {
+        const int64_t n = std::min(chunk, Nq - r0);
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(c->sc_x.p, static_cast<const char *>(Xq_host) + (size_t)r0 * d * es,
+                                        (size_t)n * d * es, hipMemcpyHostToDevice, c->stream));
+        TRY(dbgsom_sparse_code(c->sc_x.p, x_dtype, n, d, d, Wd, M, ldw, max_iter, (int)c->sc_cap,
+                               proba_host ? c->sc_p.as<double>() : nullptr, C,
+                               code_host ? c->sc_code.as<double>() : nullptr,
+                               proba_host ? c->sc_proba.as<double>() : nullptr, c->sc_cnt.as<uint64_t>(), c->sc_ws.p,
+                               c->sc_ws.cap, c->stream));
+        if (code_host)
+            DBGSOM_HIP_CHECK(hipMemcpyAsync(code_host + r0 * M, c->sc_code.p, (size_t)n * M * 8, hipMemcpyDeviceToHost,
+                                            c->stream));
+        if (proba_host)
+            DBGSOM_HIP_CHECK(hipMemcpyAsync(proba_host + r0 * C, c->sc_proba.p, (size_t)n * C * 8,
+                                            hipMemcpyDeviceToHost, c->stream));
+    }
+    DBGSOM_HIP_CHECK(hipMemcpyAsync(counts_host, c->sc_cnt.p, DBGSOM_SC_COUNTS * 8, hipMemcpyDeviceToHost, c->stream));
+    return sync(c);
 }
 
 int dbgsom_ctx_exp_similarity(dbgsom_ctx *c, const double *dist_host, int64_t n, double gamma, double *kw_host) {

@@ -2,8 +2,8 @@
 
 Mirrors ``dbgsom/SomClassifier.py`` of the reference (:19-220).  The training path is the same
 accelerated hot path; prototype labelling uses one more BMU pass; ``predict`` /
-``predict_proba`` go through ``transform`` (LARS sparse coding on the host) exactly as the
-reference does -- that part is outside the accelerated path.
+``predict_proba`` go through the LARS sparse code of ``transform`` exactly as the reference does,
+computed by the backend (on the MI355X: csrc/sparse_code.hip).
 """
 from __future__ import annotations
 
@@ -71,6 +71,6 @@ class SomClassifier(BaseSom, TransformerMixin, ClassifierMixin):
                 else:
                     rows.append(attrs["probabilities"])
             return np.array(rows)
-        code = self.transform(X)
-        raw = code @ self._extract_values_from_graph("probabilities")
-        return raw / raw.sum(axis=1)[np.newaxis].T
+        # the code never leaves the backend: it returns (code @ P) normalised per row
+        return self._engine().sparse_code(self.weights_, X, P=self._extract_values_from_graph("probabilities"),
+                                           n_jobs=self.n_jobs)

@@ -367,6 +367,42 @@ int dbgsom_ctx_bmu_query(dbgsom_ctx *ctx, const void *Xq_host, int x_dtype, int6
                          int64_t d, const double *W_host, int64_t M, int k, int round_f32,
                          int64_t *idx_host, double *dist_host);
 
+/* ---- sparse coding: BaseSom.transform / SomClassifier.predict_proba (BaseSom.py:241-268,
+ * SomClassifier.py:178-220) ------------------------------------------------------------------------
+ * scikit-learn's SparseCoder(dictionary=normalize(W), transform_algorithm="lasso_lars",
+ * positive_code=True, transform_alpha=0).transform(normalize(Xq)): one non-negative LARS-lasso path
+ * per query row over the Gram matrix of the normalised prototypes (csrc/sparse_code.hip).
+ *   code  Nq x M, or NULL
+ *   proba Nq x C = (code P) / rowsum(code P) (P: M x C class frequencies), or NULL; a zero code row
+ *         gives a NaN row, as the reference's division does
+ *   cap   active-set size solved in LDS (0 = the library's 64); rows whose active set grows past it
+ *         are solved again by the overflow pass with the factor in the workspace (same results)
+ *   counts (device) DBGSOM_SC_COUNTS uint64 counters, ADDED to (zero them before the first call):
+ *         [rows, LARS iterations, max iterations of a row, drops, degenerate regressors skipped,
+ *          lasso early stops (alpha grew), non-finite AA retries, rows of the overflow pass,
+ *          largest active set, steps that dropped more than one prototype at once, G rows read
+ *          by corr_eq_dir (sum over the iterations of the active-set size)] */
+#define DBGSOM_SC_COUNTS 11
+size_t dbgsom_sparse_code_workspace_bytes(int64_t Nq, int64_t d, int64_t M, int max_iter);
+int dbgsom_sparse_code(const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d, int64_t ldx,
+                       const double *W_dev, int64_t M, int64_t ldw, int max_iter, int cap,
+                       const double *P_dev, int64_t C, double *code_dev, double *proba_dev,
+                       uint64_t *counts_dev, void *workspace_dev, size_t workspace_bytes,
+                       void *stream);
+/* diagnostics: per-stage HIP-event timing of dbgsom_sparse_code (calls become blocking while it is on);
+ * enabling or disabling resets the sums.  ms5 = summed ms of [normalise W + Gram GEMM, normalise the
+ * queries + Cov GEMM, LARS (LDS path), first overflow pass, second overflow pass] */
+int dbgsom_sparse_code_timing(int enable);
+int dbgsom_sparse_code_stage_ms(double *ms5);
+/* The same from host arrays, in chunks of ctx option "sc_chunk_rows" query rows (workspace stays
+ * bounded); option "sc_cap" is the `cap` above.  Xq_host: Nq x d, DBGSOM_F32 or DBGSOM_F64;
+ * W_host = NULL: the resident prototypes; P_host: M x C (needed when proba_host is given);
+ * code_host / proba_host may be NULL; counts_host[DBGSOM_SC_COUNTS] is overwritten with this call's
+ * counters. */
+int dbgsom_ctx_sparse_code(dbgsom_ctx *ctx, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                           const double *W_host, int64_t M, int max_iter, const double *P_host,
+                           int64_t C, double *code_host, double *proba_host, uint64_t *counts_host);
+
 /* _calculate_exp_similarity on host values (BaseSom.py:533-538) */
 int dbgsom_ctx_exp_similarity(dbgsom_ctx *ctx, const double *dist_host, int64_t n, double gamma,
                               double *kw_host);
