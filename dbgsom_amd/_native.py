@@ -97,6 +97,12 @@ SIGNATURES = {
     "dbgsom_sparse_code_timing": (_ci, [_ci]),
     "dbgsom_sparse_code_stage_ms": (_ci, [_vp]),
     "dbgsom_ctx_sparse_code": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _ci, _vp, _i64, _vp, _vp, _vp]),
+    "dbgsom_topofn_workspace_bytes": (_sz, [_i64, _ci]),
+    "dbgsom_topofn": (_ci, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dbgsom_topofn_timing": (_ci, [_ci]),
+    "dbgsom_topofn_stage_ms": (_ci, [_vp]),
+    "dbgsom_ctx_topographic_function": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _ci, _vp, _i64, _vp, _vp,
+                                              _vp]),
     "dbgsom_ctx_exp_similarity": (_ci, [_vp, _vp, _i64, _dbl, _vp]),
     "dbgsom_ctx_epoch": (_ci, [_vp, _vp, _i64, _ci, _dbl, _dbl, _ci, _ci, _vp, _vp, _vp, _vp, _vp,
                                _vp]),

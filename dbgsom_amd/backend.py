@@ -181,6 +181,44 @@ class HotPathBackend:
         raw = code @ P
         return raw / raw.sum(axis=1)[np.newaxis].T
 
+    # -- topographic function (BaseSom.topographic_function / phi); host default ------------------------
+    def topographic_function(self, W, X, coords, want_distances=False):
+        """The two integer histograms that phi(k) of BaseSom.py:955-998 is made of, for the graph with an
+        edge {a, b} for every row (a, b) of the 2-BMU pairs of X under W:
+            hist_pos[c] (n_pos = max Chebyshev extent of coords + 1): ordered edges by the Chebyshev
+                        distance c of their lattice coordinates
+            hist_neg[t] (M + 1): ordered lattice 4-neighbour pairs by hop distance t; [M]: no path
+        -> (hist_pos, hist_neg, D or None), int64; D (M x M int32, -1 = unreachable) with want_distances.
+        Unweighted shortest paths give the integers of the reference's Floyd-Warshall without its O(M^3)."""
+        from scipy.sparse import csr_matrix
+        from scipy.sparse.csgraph import shortest_path
+
+        xy = np.asarray(coords, dtype=np.int64).reshape(-1, 2)
+        M = xy.shape[0]
+        _, idx = self.bmu(W, 2, X=X)
+        a, b = idx[:, 0], idx[:, 1]
+        keep = a != b
+        A = csr_matrix((np.ones(2 * int(keep.sum())), (np.r_[a[keep], b[keep]], np.r_[b[keep], a[keep]])),
+                       shape=(M, M))
+        A.sum_duplicates()
+        D = shortest_path(A, unweighted=True, directed=False)
+        n_pos = int((xy.max(axis=0) - xy.min(axis=0)).max()) + 1
+        r, c = A.nonzero()
+        hist_pos = np.bincount(np.abs(xy[r] - xy[c]).max(axis=1), minlength=n_pos).astype(np.int64)
+        where = {tuple(p): i for i, p in enumerate(xy.tolist())}
+        i_nb, j_nb = [], []
+        for i, (x, y) in enumerate(xy.tolist()):
+            for p in ((x - 1, y), (x + 1, y), (x, y - 1), (x, y + 1)):
+                j = where.get(p)
+                if j is not None:
+                    i_nb.append(i)
+                    j_nb.append(j)
+        t = D[np.asarray(i_nb, dtype=np.int64), np.asarray(j_nb, dtype=np.int64)]
+        t = np.where(np.isinf(t), M, t).astype(np.int64)
+        hist_neg = np.bincount(t, minlength=M + 1).astype(np.int64)
+        Dout = np.where(np.isinf(D), -1, D).astype(np.int32) if want_distances else None
+        return hist_pos, hist_neg, Dout
+
     def release(self):
         pass
 
@@ -628,6 +666,32 @@ class HipBackend(HotPathBackend):
                           "(scikit-learn warns the same way)" % (int(counts[4]), int(counts[5])),
                           ConvergenceWarning)
         return out
+
+    # -- topographic function ---------------------------------------------------------------------
+    def topographic_function(self, W, X, coords, want_distances=False):
+        """The host default's result computed on the device (csrc/topofn.hip): the k = 2 search of
+        ``bmu(W, 2, X=X)``, the edge set, a breadth-first search from every neuron and the histograms,
+        with the pairs never leaving HBM."""
+        X = np.ascontiguousarray(X)
+        if X.dtype not in (np.float32, np.float64):
+            X = X.astype(np.float64)
+        W = np.asarray(W)
+        if X.ndim != 2 or W.ndim != 2 or W.shape[1] != X.shape[1]:
+            raise ValueError("prototype / sample feature mismatch")
+        xy = np.ascontiguousarray(coords, dtype=np.int32).reshape(-1, 2)
+        M = W.shape[0]
+        if xy.shape[0] != M:
+            raise ValueError("coords must be (M, 2)")
+        rf = int(X.dtype == np.float32 and W.dtype == np.float32)
+        W64 = np.ascontiguousarray(W, dtype=np.float64)
+        n_pos = int((xy.astype(np.int64).max(axis=0) - xy.astype(np.int64).min(axis=0)).max()) + 1
+        hist_pos = np.empty(n_pos, dtype=np.int64)
+        hist_neg = np.empty(M + 1, dtype=np.int64)
+        D = np.empty((M, M), dtype=np.int32) if want_distances else None
+        self._call("dbgsom_ctx_topographic_function", self._ctx, X.ctypes.data, _x_dtype_code(X.dtype),
+                   X.shape[0], X.shape[1], W64.ctypes.data, M, rf, xy.ctypes.data, n_pos, hist_pos.ctypes.data,
+                   hist_neg.ctypes.data, None if D is None else D.ctypes.data)
+        return hist_pos, hist_neg, D
 
     # -- a2 -------------------------------------------------------------------------------------
     def exp_similarity(self, distances, gamma):

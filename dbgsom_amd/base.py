@@ -565,6 +565,42 @@ class BaseSom(BaseEstimator):
         X = check_array(X, dtype=[np.float64, np.float32])
         return self._engine().sparse_code(self.weights_, X, n_jobs=self.n_jobs)
 
+    def topographic_function(self, X) -> tuple[np.ndarray, np.ndarray]:
+        """(phi(k) / M for k = 0 .. max_dist - 1, phi(-k) / M for the same k), max_dist the largest
+        Chebyshev distance between lattice positions (BaseSom.py:955-998).  The graph is the induced
+        Delaunay triangulation of X (an edge between the two BMUs of every sample); the backend returns
+        the two histograms phi is made of (on the MI355X: csrc/topofn.hip).  Unlike the reference, no
+        dense M x M matrix is kept on the estimator (``want_distances=True`` on the backend gives D)."""
+        check_is_fitted(self)
+        X = check_array(X, dtype=[np.float64, np.float32])
+        if X.shape[1] != self.n_features_in_:
+            raise ValueError(f"X has {X.shape[1]} features, but {type(self).__name__} is expecting "
+                             f"{self.n_features_in_} features as input")
+        M = len(self.neurons_)
+        if M < 2:
+            raise ValueError(f"Expected n_neighbors <= n_samples_fit, but n_neighbors = 2, n_samples_fit = {M}")
+        hist_pos, hist_neg, _ = self._engine().topographic_function(self.weights_, X, self.neurons_)
+        self._topofn_hist_pos = np.asarray(hist_pos, dtype=np.int64)
+        self._topofn_hist_neg = np.asarray(hist_neg, dtype=np.int64)
+        max_dist = len(self._topofn_hist_pos) - 1
+        k_pos = np.array([self.phi(k) for k in range(max_dist)], dtype=np.int64)
+        k_neg = np.array([self.phi(-k) for k in range(max_dist)], dtype=np.int64)
+        return k_pos / M, k_neg / M
+
+    def phi(self, k: int) -> int:
+        """Ordered pairs of neurons (i, j) with, for k > 0, a Delaunay edge between them and a
+        Chebyshev lattice distance > k; for k < 0, lattice neighbours more than -k hops apart in the
+        Delaunay graph (or with no path); phi(0) = phi(-1) + phi(1) (BaseSom.py:983-995).  Answers
+        from the histograms of the last ``topographic_function`` call."""
+        hist_pos, hist_neg = self._topofn_hist_pos, self._topofn_hist_neg
+        k = int(k)
+        if k > 0:
+            return int(hist_pos[k + 1:].sum())
+        if k < 0:
+            M = len(hist_neg) - 1  # hist_neg[M]: no path, more than any number of hops
+            return int(hist_neg[min(-k + 1, M):].sum())
+        return self.phi(-1) + self.phi(1)
+
     def _grow_vertical(self, X, y=None) -> None:
         """Fit a child map on the Voronoi set of every neuron whose error exceeds 1.5x the
         growing threshold (BaseSom.py:157-179).  The reference's own loop cannot run: it compares

@@ -86,6 +86,9 @@ inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 inline bool is_aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
 // internal launchers (one per .hip file)
+// per-stage timing of the topographic function (topofn.hip): the context call adds its search stage
+bool topofn_timing_enabled();
+void topofn_add_search_ms(double ms);
 int launch_row_sqnorms(const void *A, int dtype, int64_t rows, int64_t d, int64_t ld, double *out,
                        hipStream_t s);
 int launch_bmu(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx,

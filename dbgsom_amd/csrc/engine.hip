@@ -1667,6 +1667,75 @@ int dbgsom_ctx_sparse_code(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int6
     return sync(c);
 }
 
+// ------------------------------------------------------------------------------------------
+// topographic function: the k = 2 query search of dbgsom_ctx_bmu_query (k = 2 never takes the
+// filtered form), its pairs left in HBM for csrc/topofn.hip
+// ------------------------------------------------------------------------------------------
+int dbgsom_ctx_topographic_function(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                    const double *W_host, int64_t M, int round_f32, const int32_t *xy_host,
+                                    int64_t n_pos, int64_t *hist_pos_host, int64_t *hist_neg_host, int32_t *D_host) {
+    CTX_CHECK(c);
+    DBGSOM_REQUIRE(x_dtype == DBGSOM_F32 || x_dtype == DBGSOM_F64, "x_dtype must be DBGSOM_F32 or DBGSOM_F64");
+    DBGSOM_REQUIRE(Xq_host && W_host && xy_host && hist_pos_host && hist_neg_host && Nq >= 1 && d >= 1 && M >= 2 &&
+                       M <= DBGSOM_MAX_PROTOTYPES && n_pos >= 1,
+                   "bad arguments");
+    Samples &s = c->xq;
+    DevBuf Wq, wwq, iq, dq, xy, hp, hn, Dd, ws;
+    const bool timed = topofn_timing_enabled();
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int rc = DBGSOM_OK;
+    const int64_t dp = pad16(d);
+    do {
+        if (timed) {
+            hipError_t e = hipEventCreate(&ev[0]);
+            if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+            if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
+            if (e != hipSuccess) { set_error("timing events: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
+        }
+        if ((rc = place_host_samples(c, s, Xq_host, x_dtype, Nq, d, x_dtype))) break;
+        if ((rc = Wq.reserve((size_t)M * dp * 8))) break;
+        if ((rc = wwq.reserve((size_t)M * 8))) break;
+        if ((rc = iq.reserve((size_t)Nq * 2 * 8))) break;
+        if ((rc = dq.reserve((size_t)Nq * 2 * 8))) break;
+        if ((rc = upload_padded(c, Wq.p, W_host, M, d, dp, 8))) break;
+        if ((rc = launch_row_sqnorms(Wq.p, DBGSOM_F64, M, dp, dp, wwq.as<double>(), c->stream))) break;
+        if ((rc = launch_bmu(s.Xb, s.bdtype, Nq, dp, dp, s.xx.as<double>(), Wq.as<double>(), M, wwq.as<double>(), 2,
+                             round_f32, iq.as<int64_t>(), dq.as<double>(), c->stream)))
+            break;
+        if (timed) {
+            float ms = 0.0f;
+            hipError_t e = hipEventRecord(ev[1], c->stream);
+            if (e == hipSuccess) e = hipEventSynchronize(ev[1]);
+            if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+            if (e != hipSuccess) { set_error("timing events: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
+            topofn_add_search_ms(ms);
+        }
+        const size_t wsb = dbgsom_topofn_workspace_bytes(M, D_host != nullptr);
+        if ((rc = xy.reserve((size_t)M * 8))) break;
+        if ((rc = hp.reserve((size_t)n_pos * 8))) break;
+        if ((rc = hn.reserve((size_t)(M + 1) * 8))) break;
+        if ((rc = ws.reserve(wsb))) break;
+        if (D_host && (rc = Dd.reserve((size_t)M * M * 4))) break;
+        hipError_t e = hipMemcpyAsync(xy.p, xy_host, (size_t)M * 8, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
+        if ((rc = dbgsom_topofn(iq.as<int64_t>(), Nq, xy.as<int32_t>(), M, n_pos, hp.as<uint64_t>(),
+                                hn.as<uint64_t>(), D_host ? Dd.as<int32_t>() : nullptr, ws.p, ws.cap, c->stream)))
+            break;
+        e = hipMemcpyAsync(hist_pos_host, hp.p, (size_t)n_pos * 8, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(hist_neg_host, hn.p, (size_t)(M + 1) * 8, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && D_host) e = hipMemcpyAsync(D_host, Dd.p, (size_t)M * M * 4, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; }
+    } while (0);
+    if (rc != DBGSOM_OK) (void)hipStreamSynchronize(c->stream);
+    for (hipEvent_t &e : ev)
+        if (e) (void)hipEventDestroy(e);
+    Wq.release(); wwq.release(); iq.release(); dq.release(); xy.release(); hp.release(); hn.release(); Dd.release();
+    ws.release();
+    if (Nq * dp * (int64_t)dtype_size(x_dtype) > ((int64_t)256 << 20)) s.release();  // do not sit on a large one-off batch
+    return rc;
+}
+
 int dbgsom_ctx_exp_similarity(dbgsom_ctx *c, const double *dist_host, int64_t n, double gamma, double *kw_host) {
     CTX_CHECK(c);
     DBGSOM_REQUIRE(n >= 0 && (n == 0 || (dist_host && kw_host)), "bad arguments");

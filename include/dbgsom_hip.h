@@ -403,6 +403,38 @@ int dbgsom_ctx_sparse_code(dbgsom_ctx *ctx, const void *Xq_host, int x_dtype, in
                            const double *W_host, int64_t M, int max_iter, const double *P_host,
                            int64_t C, double *code_host, double *proba_host, uint64_t *counts_host);
 
+/* ---- topographic function: BaseSom.topographic_function / BaseSom.phi (BaseSom.py:955-998) ------------
+ * The graph of the map's induced Delaunay triangulation (an edge {a, b} for every row (a, b) of the
+ * samples' first and second BMUs), the hop distance D on it, and the two integer histograms that
+ * phi(k) is made of (csrc/topofn.hip):
+ *   hist_pos[c], c < n_pos   ordered Delaunay edges (i, j) by the Chebyshev distance c of their lattice
+ *                            coordinates; n_pos = max(range of x, range of y) + 1
+ *   hist_neg[t], t <= M      ordered lattice 4-neighbour pairs (|dx| + |dy| == 1) by their hop distance
+ *                            t (1 .. M - 1); hist_neg[M]: the pairs with no path between them
+ *   D (may be NULL)          M x M int32 hop distances, -1 = unreachable (full mode; NULL: histogram
+ *                            mode, which stops every source's search once its lattice neighbours have
+ *                            their distances -- the histograms are the same)
+ * idx2: n x 2 int64 BMU pairs (device); xy: M x 2 int32 lattice coordinates (device), no two alike.
+ * M <= DBGSOM_MAX_PROTOTYPES.  The call is blocking (it reads back the kernels' status word):
+ * DBGSOM_ERANGE when an index is outside [0, M), DBGSOM_EINVAL when an edge spans >= n_pos or two
+ * neurons share coordinates. */
+size_t dbgsom_topofn_workspace_bytes(int64_t M, int full);
+int dbgsom_topofn(const int64_t *idx2_dev, int64_t n, const int32_t *xy_dev, int64_t M, int64_t n_pos,
+                  uint64_t *hist_pos_dev, uint64_t *hist_neg_dev, int32_t *D_dev, void *ws,
+                  size_t ws_bytes, void *stream);
+/* diagnostics: per-stage HIP-event timing of dbgsom_topofn / dbgsom_ctx_topographic_function (calls
+ * become blocking while it is on); enabling or disabling resets the sums.  ms4 = summed ms of
+ * [k = 2 search (context call only), edge set + CSR + lattice neighbours, distances, histograms] */
+int dbgsom_topofn_timing(int enable);
+int dbgsom_topofn_stage_ms(double *ms4);
+/* The same from host arrays: the k = 2 search of dbgsom_ctx_bmu_query on Xq (Nq x d, DBGSOM_F32 or
+ * DBGSOM_F64) against W_host (M x d float64), its pairs kept in HBM, then dbgsom_topofn.
+ * hist_pos_host[n_pos], hist_neg_host[M + 1]; D_host (M x M) or NULL. */
+int dbgsom_ctx_topographic_function(dbgsom_ctx *ctx, const void *Xq_host, int x_dtype, int64_t Nq,
+                                    int64_t d, const double *W_host, int64_t M, int round_f32,
+                                    const int32_t *xy_host, int64_t n_pos, int64_t *hist_pos_host,
+                                    int64_t *hist_neg_host, int32_t *D_host);
+
 /* _calculate_exp_similarity on host values (BaseSom.py:533-538) */
 int dbgsom_ctx_exp_similarity(dbgsom_ctx *ctx, const double *dist_host, int64_t n, double gamma,
                               double *kw_host);
