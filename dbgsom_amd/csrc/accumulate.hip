@@ -377,26 +377,8 @@ __global__ __launch_bounds__(AT) void segsum_kernel(
 //    in list order.  Sums, their order of additions and the scalar partials are those of segsum_kernel bit
 //    for bit (the two search forms must leave bit-identical prototypes).
 // A slice none of whose rows needs a distance skips the chain altogether.
-// Stamps and experiment switches of segsum_chain_kernel live in experiments.h, which only the experiment builds of
-// tools/build_variant.sh compile (-DDBGSOM_EXPERIMENTS ...); the shipped kernel carries four empty macros.
-#ifdef DBGSOM_EXPERIMENTS
-#include "experiments.h"
-#else
-#define CSTAMP_DECL
-#define CSTAMP(k)
-#define CSTAMP_LOADS_LANDED
-#define CSTAMP_FLUSH(dist, rows_s, n)
-#define CHAIN_PAD 0
-#endif
-#ifndef CHAIN_CB
-#define CHAIN_CB 4        // k-steps per batch of the chain's operand ring
-#endif
-#ifndef CHAIN_CW
-#define CHAIN_CW ((c >> 8) & 3u)
-#endif
-#ifndef CHAIN_OCC
-#define CHAIN_OCC 3       // wavefronts per SIMD the one-group kernel is compiled for
-#endif
+constexpr int CHAIN_CB = 4;    // k-steps per batch of the chain's operand ring
+constexpr int CHAIN_OCC = 3;   // wavefronts per SIMD the one-group kernel is compiled for
 constexpr int SR = 16;     // rows per slice = B-columns of one matrix instruction
 constexpr int SRG = 64;    // column groups (16-byte pieces) per range
 constexpr int SRP = (SRG + 1) * 16;   // bytes per row of a range buffer (one piece of padding)
@@ -453,7 +435,6 @@ __global__ __launch_bounds__(AT, G == 1 ? CHAIN_OCC : 2) void segsum_chain_kerne
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t c = blockIdx.x;
     if (c >= chunk_pre[M]) return;  // uniform per workgroup
-    CSTAMP_DECL;
     {   // the chunk's neuron: the one j with chunk_pre[j] <= c < chunk_pre[j + 1] -- every thread looks at its share of
         // the table at once (one round trip instead of the ten of a binary search by one thread)
         const int per = (M + AT - 1) / AT;
@@ -491,7 +472,7 @@ __global__ __launch_bounds__(AT, G == 1 ? CHAIN_OCC : 2) void segsum_chain_kerne
     const int rl = wide ? 0 : tid / Q, q0 = wide ? tid : tid - rl * Q;
     const bool active = wide || rl < RL;
     const int NR = (Q + SRG - 1) / SRG;          // ranges of 64 column groups
-    const int cw = (int)(CHAIN_CW);             // the chain's wavefront: spread over the SIMDs (chunks resident on one CU
+    const int cw = (int)((c >> 8) & 3u);        // the chain's wavefront: spread over the SIMDs (chunks resident on one CU
                                                  // share c mod 256 -- XCD, then CU, round robin -- so the bits above decide)
     const int lr = lane & 15, lq = lane >> 4;    // B operand: column (row of the slice) lr, k = lq
     double acc[G][VEC];
@@ -507,7 +488,6 @@ __global__ __launch_bounds__(AT, G == 1 ? CHAIN_OCC : 2) void segsum_chain_kerne
         my_range[g] = (active && q < Q) ? q / SRG : -1;
         my_off[g] = (q % SRG) * 16;
     }
-    CSTAMP(0);
 
     for (int s0 = 0; s0 < n; s0 += SR) {
         const int nrow = min(SR, n - s0);
@@ -529,8 +509,6 @@ __global__ __launch_bounds__(AT, G == 1 ? CHAIN_OCC : 2) void segsum_chain_kerne
                     raw[i][g] = *reinterpret_cast<const raw4_t *>(X + (int64_t)rows_s[s0 + i] * ldx + (int64_t)(q0 + g * AT) * VEC);
             }
         }
-        CSTAMP(1);
-        CSTAMP_LOADS_LANDED;
         if ((need_mask >> (s0 / SR)) & 1u) {   // (uniform)
             // ---- the chain: ranges of 64 column groups through two LDS buffers
             // (rows behind the slice's end: zeros, written by row lane 0 -- never garbage in a B column)
@@ -550,7 +528,6 @@ __global__ __launch_bounds__(AT, G == 1 ? CHAIN_OCC : 2) void segsum_chain_kerne
             double a4 = 0.0;   // the chain's accumulator: lanes 0 .. 15 = rows of the slice
             write_range(0);
             __syncthreads();
-            CSTAMP(3);
             for (int r = 0; r < NR; ++r) {
                 if (r + 1 < NR) write_range(r + 1);
                 if (wave == cw) {
@@ -601,12 +578,9 @@ __global__ __launch_bounds__(AT, G == 1 ? CHAIN_OCC : 2) void segsum_chain_kerne
                     }
                     for (int st = npair * 2 * CB; st < nstep; ++st)
                         a4 = __builtin_amdgcn_mfma_f64_4x4x4f64(ld_a(st), wid(ld_b(st)), a4, 0, 0, 0);
-                    CSTAMP(8);   // (the chain wave's own view: its matrix loop ...)
                 }
                 __syncthreads();
-                if (wave == cw) { CSTAMP(9); }   // (... and its wait at the range's barrier, writes of the next range included)
             }
-            CSTAMP(4);
             if (wave == cw && lane < nrow) {
                 const int p = s0 + lane;
                 if (dist_s[p] == -1.0) {
@@ -620,7 +594,6 @@ __global__ __launch_bounds__(AT, G == 1 ? CHAIN_OCC : 2) void segsum_chain_kerne
                 }
             }
             __syncthreads();
-            CSTAMP(5);
         }
         // ---- the weighted sums of the slice's rows, in list order (segsum_kernel's order), from the registers
         if (mine) {
@@ -642,10 +615,8 @@ __global__ __launch_bounds__(AT, G == 1 ? CHAIN_OCC : 2) void segsum_chain_kerne
                 }
             }
         }
-        CSTAMP(6);
     }
     __syncthreads();
-    CSTAMP_FLUSH(dist, rows_s, n);
     if (tid == AT - 1) {  // the scalar partials, in list order
         double sk = 0.0, se = 0.0;
         for (int p = 0; p < n; ++p) { sk += kw_s[p]; se += dist_s[p]; }
@@ -841,10 +812,10 @@ static int accumulate_impl(const void *X, int x_dtype, int64_t N, int64_t d, int
         static int attr_set = 0;                                                                          \
         if (attr_set < L.total) {                                                                         \
             DBGSOM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&segsum_chain_kernel<XT, V, G_>), \
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024 + CHAIN_PAD)); \
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));   \
             attr_set = 96 * 1024;                                                                         \
         }                                                                                                 \
-        hipLaunchKernelGGL((segsum_chain_kernel<XT, V, G_>), grid, block, (size_t)L.total + CHAIN_PAD, s, (const XT *)X, di, ldx, \
+        hipLaunchKernelGGL((segsum_chain_kernel<XT, V, G_>), grid, block, (size_t)L.total, s, (const XT *)X, di, ldx, \
                            w.order, gamma, const_cast<double *>(dist), w.seg_start, w.count, w.chunk_pre, Mi, \
                            w.slab, fill->W, fill->ww, fill->xx, fill->round_f32, L);                      \
     } while (0)

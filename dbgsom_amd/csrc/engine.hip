@@ -1148,8 +1148,6 @@ int dbgsom_ctx_create(int device, dbgsom_ctx **out) {
     dbgsom_ctx *c = new (std::nothrow) dbgsom_ctx();
     if (!c) { set_error("out of host memory"); return DBGSOM_ENOMEM; }
     c->device = device;
-    const char *e = getenv("DBGSOM_SWEEP_PLANES");  // diagnostic: fixes the digit planes of every context
-    if (e) { const int v = atoi(e); if (v >= 0 && v <= 4) c->sweep_planes = v; }
     // (highest priority: the side streams of the filtered search -- a few long chains off the critical
     //  path -- must not starve the short dependent kernels of this one)
     int prio_low = 0, prio_high = 0;

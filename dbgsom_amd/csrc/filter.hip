@@ -25,17 +25,6 @@
 
 #include "bmu_common.h"
 
-// (in-kernel stamps of the experiment builds: csrc/experiments.h, tools/build_variant.sh; empty in the library)
-#ifdef DBGSOM_EXPERIMENTS
-#include "experiments.h"
-#else
-#define PM_STAMP(k)
-#define XT_DECL
-#define XT_MARK(k)
-#define XT_MARK_ONCE(k)
-#define XT_FLUSH(JTL_, cnt_, dist_, isamp0_, Kk_)
-#endif
-
 namespace dbgsom {
 
 constexpr double FQ = 8323072.0;  // 127 * 2^16
@@ -1009,11 +998,8 @@ __global__ __launch_bounds__(FNT, 2) void sweep_i8_kernel(
 // to different workgroups -- they are not tied to the same barrier, and one workgroup's prologue,
 // chunk epilogues and list compaction run under the other's products.  NW = 4 wavefronts as 2 x 2
 // (wavefront tile 64 x 128, two wavefronts per SIMD) or NW = 8 as 2 x 4 (64 x 64 tiles, 64
-// accumulator registers, <= 128 VGPRs: FOUR wavefronts per SIMD -- the default).
+// accumulator registers, <= 128 VGPRs: FOUR wavefronts per SIMD -- the one launched).
 constexpr int S4_NT = 256;
-#ifndef S4_SPLIT_ISSUE
-#define S4_SPLIT_ISSUE 0  // 1: half of a tile's DMAs behind the barrier, half in the next tile's first half
-#endif
 struct Sweep4Lds {
     static constexpr int JT = 4, BJ = 256;
     static constexpr int X_BYTES = 128 * FKT, W_BYTES = BJ * FKT, STAGE = X_BYTES + W_BYTES;  // 8 + 16 KB
@@ -1293,13 +1279,11 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void sweep4_i8_kernel(  // (HIP: t
     bool tab_pending = false;  // a table DMA was issued in the previous tile's second half
     for (int t = 0; t < ntile; ++t) {
         const int r_next = (r_stage == (FSTAGES - 1) * L::STAGE) ? 0 : r_stage + L::STAGE;
-        const bool back_now = t >= 1 && t + 2 < ntile;
         products(f0, [&](int g) {
             if (g == 0) {
                 __builtin_amdgcn_sched_barrier(0);
                 load_frags(r_stage, 1, f1);
                 touch_frags(f0);
-                if (S4_SPLIT_ISSUE && back_now) issue_ops(DMA_TILE / 2, DMA_TILE);
             }
             __builtin_amdgcn_sched_barrier(0);
         });
@@ -1321,7 +1305,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void sweep4_i8_kernel(  // (HIP: t
                 // every wave is past the previous chunk's epilogue here: the table set may be
                 // replaced by this chunk's
                 if (r_kt == 0 && t > 0) { issue_tables(r_chunk); tab_pending = tab_wave; }
-                if (front_now) issue_ops(0, S4_SPLIT_ISSUE ? DMA_TILE / 2 : DMA_TILE);
+                if (front_now) issue_ops(0, DMA_TILE);
             }
             __builtin_amdgcn_sched_barrier(0);
         });
@@ -1329,8 +1313,8 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void sweep4_i8_kernel(  // (HIP: t
         if (r_kt == nkt - 1) {
             // the table pieces of this chunk: own piece landed (at most the 9 DMAs issued behind it
             // are in flight), then everybody's
-            // (the DMAs issued behind it: a tile and a half with split issue, two tiles without)
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(S4_SPLIT_ISSUE ? DMA_TILE + DMA_TILE / 2 : 2 * DMA_TILE) : "memory");
+            // (the DMAs issued behind it: two tiles)
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * DMA_TILE) : "memory");
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             const int jc = r_chunk * BJ;
@@ -1732,7 +1716,6 @@ __global__ __launch_bounds__(256, 6) void prune_mark_kernel(
         group = retry_groups[blockIdx.x];
     }
     const int64_t p0 = group * 128;
-    PM_STAMP(0);
     const int nwords = (M + 31) / 32;
     const unsigned long long INF_BITS = 0x7ff0000000000000ull;
     for (int w = tid; w < nwords; w += 256) mask[w] = 0u;
@@ -1751,7 +1734,6 @@ __global__ __launch_bounds__(256, 6) void prune_mark_kernel(
     }
     if (tid == 0) misc[0] = 0;  // 1: some sample has no bound -- every prototype is a candidate
     __syncthreads();
-    PM_STAMP(1);   // (sample ids and seeds are here)
     // |x_i - w_seed|^2 from one digit product: 8 threads per sample, 16 bytes of the row each per step
     const double yy_max = summary[2], root_d = sqrt((double)d) * (1.0 + 1e-12);
     // (the four samples of a thread side by side, two 16-byte steps each: 16 loads in flight -- one
@@ -1816,7 +1798,6 @@ __global__ __launch_bounds__(256, 6) void prune_mark_kernel(
                         awr[rh + r] = __builtin_amdgcn_sdot4(wv[r][u][e], wv[r][u][e], awr[rh + r], false);
                     }
         }
-    PM_STAMP(2);   // (the rows have been read)
     // The thread's four samples' sums over the sample's eight lanes (every lane ends up with the totals), then ONE pass
     // of the float64 bound with lane q of the eight taking sample q -- four passes with one lane in eight at work were
     // half of the instructions this kernel issues at d = 128.
@@ -1861,7 +1842,6 @@ __global__ __launch_bounds__(256, 6) void prune_mark_kernel(
         }
     }
     __syncthreads();
-    PM_STAMP(3);   // (bounds)
     const bool all = misc[0] != 0;
     if (!all) {
         // runs of equal seeds (the samples come sorted by seed; any other order only makes more runs)
@@ -1927,7 +1907,6 @@ __global__ __launch_bounds__(256, 6) void prune_mark_kernel(
         }
     }
     __syncthreads();
-    PM_STAMP(4);   // (marks)
     if (wave == 0) {  // compact the marked prototypes, ascending (as the sweeps do)
         uint32_t base = 0;
         uint16_t *out = ulist + (size_t)group * ulist_stride;
@@ -1962,7 +1941,6 @@ __global__ __launch_bounds__(256, 6) void prune_mark_kernel(
             }
         }
     }
-    PM_STAMP(5);   // (list written)
 }
 
 // ---- 3. exact arg-min over the marked prototypes (float64 MFMA on gathered rows) -----------------
@@ -1975,10 +1953,7 @@ __global__ __launch_bounds__(256, 6) void prune_mark_kernel(
 // NS = stages of the ring (NS - 1 tiles in flight).  3 where the chip is full of workgroups; the 64-sample
 // workgroups of a small sample set (one or two rounds of workgroups) take as many stages as fit four
 // workgroups per CU: 6 / 5 / 4 for JTL = 1 / 2 / 3 (C2 stage 99 -> 91 us, a 125 k-row share of C4 235 -> 212).
-#ifndef DBGSOM_QUAD_MAX
-#define DBGSOM_QUAD_MAX 3
-#endif
-constexpr int QUAD_MAX = DBGSOM_QUAD_MAX;   // a last tile with up to 4 QUAD_MAX entries goes as groups of four
+constexpr int QUAD_MAX = 3;   // a last tile with up to 4 QUAD_MAX entries goes as groups of four
 // (stages of the 64-sample workgroups' ring: what fits four workgroups per CU, 40 KB each)
 constexpr int split_ring_stages(int jtl, int xs) {
     const int n = (40 * 1024) / (64 * 16 * xs + jtl * 16 * 16 * 8);
@@ -2018,7 +1993,6 @@ __device__ __forceinline__ void subset_exact_workgroup(
     const int wg = sched[range[0] + entry];
     const int cnt = (int)ucount[wg];
 
-    XT_DECL;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // 4 waves x 32 samples
@@ -2184,7 +2158,6 @@ __device__ __forceinline__ void subset_exact_workgroup(
             }
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
-            XT_MARK_ONCE(4);   // (the first tile has landed)
             if (t + (NS - 1) < ntile) issue();
             const int a_st = r_stage + a_base, aq_st = r_stage + aq_base, b_st = r_stage + b_base;
             r_stage = (r_stage == (NS - 1) * S_STAGE) ? 0 : r_stage + S_STAGE;
@@ -2305,7 +2278,6 @@ __device__ __forceinline__ void subset_exact_workgroup(
 #undef DBGSOM_STEP
         }
     }
-    XT_MARK(5);   // (the last step's distances are pushed)
 #pragma unroll
     for (int it = 0; it < IT; ++it) {
 #pragma unroll
@@ -2329,8 +2301,6 @@ __device__ __forceinline__ void subset_exact_workgroup(
             }
         }
     }
-    XT_MARK(1);
-    XT_FLUSH(JTL, cnt, dist_out, isamp[0], K);
 }
 
 template <typename XT, int JTL, int NWV, int SPLIT = 1, int K = 1, int NS = 3>
@@ -2575,18 +2545,15 @@ size_t dbgsom_bmu_filtered_workspace_bytes(int64_t N, int64_t d, int64_t M) {
     return carve_filter(nullptr, nullptr, N, d, M);
 }
 
-/* wavefronts per workgroup of the one-product candidate sweep for this map: 4 (sweep4_i8_kernel,
- * 128 x 256 tile, two workgroups per CU) or 8 (sweep_i8_kernel<0,1,JT>, one per CU).  Measured on
- * the four BASELINE shapes (ms per launch, 8 / 4 wavefronts): C4 1.37 / 1.11, C3 1.12 / 0.88,
- * C5 shard 4.99 / 4.83, C2 0.059 / 0.058 -- the small shape everywhere, although it reads the X
- * plane once per 256 prototypes instead of once per 512 (C5: 16.4 GB per launch, 3.4 TB/s). */
+/* shape of the one-product candidate sweep for this map: always 4 (sweep4_i8_kernel, 128 x 256 tile,
+ * two workgroups per CU) rather than 8 (sweep_i8_kernel<0,1,JT>, one per CU, which only maps beyond
+ * sweep4_i8_kernel's bitmask get).  Measured on the four BASELINE shapes (ms per launch, 8 / 4):
+ * C4 1.37 / 1.11, C3 1.12 / 0.88, C5 shard 4.99 / 4.83, C2 0.059 / 0.058 -- the small shape
+ * everywhere, although it reads the X plane once per 256 prototypes instead of once per 512 (C5:
+ * 16.4 GB per launch, 3.4 TB/s). */
 int dbgsom_sweep_shape(int64_t M, int64_t d) {
-    static const int forced = [] {  // DBGSOM_SWEEP_SHAPE=4 / 8 forces one
-        const char *e = getenv("DBGSOM_SWEEP_SHAPE");
-        return e ? atoi(e) : 0;
-    }();
     (void)M; (void)d;
-    return forced == 8 ? 8 : 4;
+    return 4;
 }
 
 int dbgsom_bmu_filtered(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx,
@@ -2631,20 +2598,9 @@ int dbgsom::launch_bmu_filtered(const FilteredCall &call) {
     StageTimer &g_timer = aux.timer;
     SideStream &g_side = aux.side;
     const double *g_hint_dist = call.hint_dist, *g_hint_shift = call.hint_shift;
-    // 8 wavefronts of 64 x 64 tiles (<= 128 VGPRs: four wavefronts per SIMD, two workgroups per CU)
-    // or 4 of 64 x 128 (DBGSOM_SWEEP_WAVES=4; two wavefronts per SIMD).  Measured, ms per launch,
+    // sweep4_i8_kernel runs 8 wavefronts of 64 x 64 tiles (<= 128 VGPRs: four wavefronts per SIMD, two
+    // workgroups per CU) rather than 4 of 64 x 128 (two wavefronts per SIMD).  Measured, ms per launch,
     // 4 / 8: C4 1.13 / 1.04, C3 0.88 / 0.71, C5 shard 4.96 / 4.55
-    static const int s4_waves = [] {
-        const char *e = getenv("DBGSOM_SWEEP_WAVES");
-        return e ? atoi(e) : 8;
-    }();
-#define S4_LAUNCH(MODE_, NB, ...)                                                                   \
-    do {                                                                                           \
-        if (s4_waves == 8)                                                                         \
-            hipLaunchKernelGGL((sweep4_i8_kernel<MODE_, 8>), dim3((unsigned)(NB)), dim3(512), 0, s, __VA_ARGS__); \
-        else                                                                                       \
-            hipLaunchKernelGGL((sweep4_i8_kernel<MODE_, 4>), dim3((unsigned)(NB)), dim3(256), 0, s, __VA_ARGS__); \
-    } while (0)
     // DBGSOM_SEED_FULL: the seed pre-pass looks at EVERY prototype and every feature (as expensive
     // as the sweep it seeds; what weakly clustered data needs -- the engine's policy decides)
     const bool seed_full = (seed_stride & DBGSOM_SEED_FULL) != 0;
@@ -2698,13 +2654,9 @@ int dbgsom::launch_bmu_filtered(const FilteredCall &call) {
     const int Msub = (int)((M + seed_stride - 1) / seed_stride), Msubpad = (Msub + 255) / 256 * 256;
     // ... and at PREPASS_KTILES k-tiles (64 features each) spread evenly over the row, with the
     // matching partial |w|^2: on every workload measured the candidate lists are as short as with
-    // all features, the pre-pass costs 0.35 instead of 0.75 ms at C4 (DBGSOM_PREPASS_KTILES=0: all)
-    static const int prepass_env = [] {
-        const char *e = getenv("DBGSOM_PREPASS_KTILES");
-        return e ? atoi(e) : PREPASS_KTILES;
-    }();
+    // all features, the pre-pass costs 0.35 ms at C4 instead of 0.75 with all features
     const int nkt_full = dpad / FKT;
-    const int nkt_used = (!seed_full && prepass_env >= 2 && prepass_env < nkt_full && nkt_full <= SW_MAX_KT) ? prepass_env : nkt_full;
+    const int nkt_used = (!seed_full && PREPASS_KTILES < nkt_full && nkt_full <= SW_MAX_KT) ? PREPASS_KTILES : nkt_full;
     if (nkt_used < nkt_full) {
         hipLaunchKernelGGL(tile_partial_kernel, dim3((unsigned)nkt_full, TS_RB), dim3(256), 0, s, W_dev,
                            (int)M, (int)d, dpad, f.tile_part);
@@ -2723,7 +2675,7 @@ int dbgsom::launch_bmu_filtered(const FilteredCall &call) {
     // The gaps between the prototypes (pruning form) need the digit planes of W and nothing of the samples:
     // in a stateless search they are worked out on the second stream BESIDE the seed pre-pass and the bucket
     // sort (one wavefront per 64 x 64 tile: a few hundred small workgroups next to a launch that fills the
-    // chip or, on a rank's share of the samples, does not), DBGSOM_GAP_FORK=0 keeps them in line
+    // chip or, on a rank's share of the samples, does not)
     auto launch_gap = [&](hipStream_t gs) -> int {
         const unsigned gt = (unsigned)(f.Mg / 64);
         if (k2) DBGSOM_HIP_CHECK(hipMemsetAsync(f.nnub, 0x7f, (size_t)f.Mg * 4, gs));   // (0x7f7f7f7f: 3.4e38, "no bound")
@@ -2735,12 +2687,8 @@ int dbgsom::launch_bmu_filtered(const FilteredCall &call) {
                                (int)d, f.wscale, f.wn0, ww_dev, f.gap, (int)f.Mg, k2 ? f.nnub : (uint32_t *)nullptr);
         return DBGSOM_OK;
     };
-    static const int gap_fork_env = [] {
-        const char *e = getenv("DBGSOM_GAP_FORK");
-        return e ? atoi(e) : 1;
-    }();
     bool gap_aside = false;
-    if ((prune || prune_probe) && !prev_idx_dev && gap_fork_env != 0 && g_side.ready()) {
+    if ((prune || prune_probe) && !prev_idx_dev && g_side.ready()) {
         DBGSOM_HIP_CHECK(hipEventRecord(g_side.gap_fork, s));
         DBGSOM_HIP_CHECK(hipStreamWaitEvent(g_side.stream, g_side.gap_fork, 0));
         const int rc = launch_gap(g_side.stream);
@@ -2753,22 +2701,13 @@ int dbgsom::launch_bmu_filtered(const FilteredCall &call) {
         // the pre-pass is as coarse as the sweep it seeds: one product for the one-product sweep
         // (seeds need not be good, only cheap), three otherwise (data on which the coarse bound
         // fails also gets useless seeds from a one-product pre-pass)
-        static const int prepass_shape = [] {  // DBGSOM_PREPASS_SHAPE=8: the 8-wavefront pre-pass
-            const char *e = getenv("DBGSOM_PREPASS_SHAPE");
-            return e ? atoi(e) : 4;
-        }();
-        if (sweep_planes == 1 && prepass_shape == 4)
-            S4_LAUNCH(1, f.nb, xb.planes, xb.scale,
+        if (sweep_planes == 1)
+            hipLaunchKernelGGL((sweep4_i8_kernel<1, 8>), dim3((unsigned)f.nb), dim3(512), 0, s, xb.planes, xb.scale,
                                xb.l1, xx_dev, N, (int)d, dpad, f.wt_sub, f.tab32 + 2 * (size_t)f.Mpad,
                                f.tab32 + 3 * (size_t)f.Mpad, f.yy_sub,
                                f.ctab_sub, f.summary, Msub, (const int64_t *)nullptr, (const int32_t *)nullptr,
                                f.ulist, (int)f.Mpad, f.ucount, Msubpad, f.seed, seed_stride, nkt_used, f.kt_sel, f.sched_ctr, f.chk32,
                                (const int32_t *)nullptr, (const unsigned long long *)nullptr);
-        else if (sweep_planes == 1)
-            hipLaunchKernelGGL((sweep_i8_kernel<1, 1, 2>), dim3((unsigned)f.nb), dim3(FNT), 0, s, xb.planes,
-                           xb.scale, xb.l1, xx_dev, N, (int)d, dpad, f.wt_sub, f.yy_sub, f.ctab_sub,
-                           f.yy_sub, f.ctab_sub, f.summary, Msub, (const int64_t *)nullptr, (const int32_t *)nullptr,
-                           f.ulist, (int)f.Mpad, f.ucount, f.seed, seed_stride, Msubpad, nkt_used, f.kt_sel, f.sched_ctr);
         else
             hipLaunchKernelGGL((sweep_i8_kernel<1, 2, 2>), dim3((unsigned)f.nb), dim3(FNT), 0, s, xb.planes,
                            xb.scale, xb.l1, xx_dev, N, (int)d, dpad, f.wt_sub, f.yy_sub, f.ctab_sub,
@@ -2783,11 +2722,6 @@ int dbgsom::launch_bmu_filtered(const FilteredCall &call) {
         g_timer.mark(2, s);
     }
     g_timer.mark(3, s);
-#define DBGSOM_SWEEP(P, J)                                                                         \
-    hipLaunchKernelGGL((sweep_i8_kernel<0, P, J>), dim3((unsigned)f.nb), dim3(FNT), 0, s, xb.planes,   \
-                       xb.scale, xb.l1, xx_dev, N, (int)d, dpad, f.wt, f.yctab, f.ictab, f.yypad,    \
-                       f.ctab, f.summary, (int)M, prev_idx_dev, order_dev, f.ulist, (int)f.Mpad,     \
-                       f.ucount, (int64_t *)nullptr, 1, (int)f.Mpad, 0, (const int32_t *)nullptr, f.sched_ctr)
     if (prune || prune_probe) {
         if (gap_aside) {
             DBGSOM_HIP_CHECK(hipStreamWaitEvent(s, g_side.gap_done, 0));
@@ -2806,10 +2740,11 @@ int dbgsom::launch_bmu_filtered(const FilteredCall &call) {
                            f.retry, rlen, prune_retry ? 1 : 0, retry_above, k2 ? f.nnub : (const uint32_t *)nullptr);
         if (prune_retry) {
             // every prototype, every feature, one digit product, for the listed workgroups only
-            S4_LAUNCH(1, f.nb, xb.planes, xb.scale, xb.l1, xx_dev, N, (int)d, dpad, f.wt,
-                      f.tab32 + 4 * (size_t)f.Mpad, f.tab32 + 5 * (size_t)f.Mpad, f.yypad, f.ctab, f.summary, (int)M,
-                      (const int64_t *)nullptr, order_dev, f.ulist, (int)f.Mpad, f.ucount, (int)f.Mpad, f.seed, 1, 0,
-                      (const int32_t *)nullptr, f.sched_ctr, f.chk32, (const int32_t *)f.retry, (const unsigned long long *)rlen);
+            hipLaunchKernelGGL((sweep4_i8_kernel<1, 8>), dim3((unsigned)f.nb), dim3(512), 0, s, xb.planes, xb.scale, xb.l1,
+                               xx_dev, N, (int)d, dpad, f.wt, f.tab32 + 4 * (size_t)f.Mpad, f.tab32 + 5 * (size_t)f.Mpad,
+                               f.yypad, f.ctab, f.summary, (int)M, (const int64_t *)nullptr, order_dev, f.ulist, (int)f.Mpad,
+                               f.ucount, (int)f.Mpad, f.seed, 1, 0, (const int32_t *)nullptr, f.sched_ctr, f.chk32,
+                               (const int32_t *)f.retry, (const unsigned long long *)rlen);
             hipLaunchKernelGGL(prune_mark_kernel, dim3((unsigned)f.nb), dim3(256), 0, s, xb.planes, xb.scale, xx_dev,
                                N, (int)d, dpad, f.wt, (int)f.Mpad, f.wscale, ww_dev, f.summary, (int)M, prev_idx_dev,
                                order_dev, f.gap, (int)f.Mg, f.ulist, (int)f.Mpad, f.ucount, f.sched_ctr, sum,
@@ -2817,20 +2752,21 @@ int dbgsom::launch_bmu_filtered(const FilteredCall &call) {
                                k2 ? f.nnub : (const uint32_t *)nullptr);
         }
     }
-    // one digit product: 4-wavefront workgroups unless DBGSOM_SWEEP_SHAPE=8 (see dbgsom_sweep_shape)
-    const int sweep_shape = dbgsom_sweep_shape(M, d);
     if (prune) {
         // (no sweep)
-    } else if (sweep_planes == 1 && sweep_shape == 4 && order_dev && M <= Sweep4Lds::MAX_M) {
-        // one digit product, 4-wavefront workgroups (128 x 256 tile), two of them per CU
-        S4_LAUNCH(0, f.nb, xb.planes, xb.scale,
+    } else if (sweep_planes == 1 && M <= Sweep4Lds::MAX_M)
+        // one digit product, 128 x 256 tile, two workgroups per CU (see dbgsom_sweep_shape)
+        hipLaunchKernelGGL((sweep4_i8_kernel<0, 8>), dim3((unsigned)f.nb), dim3(512), 0, s, xb.planes, xb.scale,
                            xb.l1, xx_dev, N, (int)d, dpad, f.wt, f.tab32, f.tab32 + (size_t)f.Mpad, f.yypad, f.ctab,
                            f.summary, (int)M, prev_idx_dev, order_dev, f.ulist, (int)f.Mpad, f.ucount,
                            (int)f.Mpad, (int64_t *)nullptr, 1, 0, (const int32_t *)nullptr, f.sched_ctr, f.chk32,
                            (const int32_t *)nullptr, (const unsigned long long *)nullptr);
-    } else if (sweep_planes == 1) {  // one digit product: 128 x 512 tile (128 x 256 for small maps)
-        if (M > 256) DBGSOM_SWEEP(1, 4); else DBGSOM_SWEEP(1, 2);
-    } else if (sweep_planes == 3)
+    else if (sweep_planes == 1)  // one digit product beyond that kernel's bitmask: 128 x 512 tile, one workgroup per CU
+        hipLaunchKernelGGL((sweep_i8_kernel<0, 1, 4>), dim3((unsigned)f.nb), dim3(FNT), 0, s, xb.planes,
+                           xb.scale, xb.l1, xx_dev, N, (int)d, dpad, f.wt, f.yctab, f.ictab,
+                           f.yypad, f.ctab, f.summary, (int)M, prev_idx_dev, order_dev, f.ulist, (int)f.Mpad, f.ucount,
+                           (int64_t *)nullptr, 1, (int)f.Mpad, 0, (const int32_t *)nullptr, f.sched_ctr);
+    else if (sweep_planes == 3)
         hipLaunchKernelGGL((sweep_i8_kernel<0, 3, 1>), dim3((unsigned)f.nb), dim3(FNT), 0, s, xb.planes,
                            xb.scale, xb.l1, xx_dev, N, (int)d, dpad, f.wt, f.yctab, f.ictab,
                            f.yypad, f.ctab, f.summary, (int)M, prev_idx_dev, order_dev, f.ulist, (int)f.Mpad, f.ucount,
@@ -2859,27 +2795,11 @@ int dbgsom::launch_bmu_filtered(const FilteredCall &call) {
     // long lists on a mostly idle chip -- overlaps the others
     SideStream &side = g_side;
     // (measured also for few buckets, where the fork and join cost ~20 us of bubbles: C2 0.168 -> 0.123
-    // ms for the stage, a 125 k-row shard of C4 0.303 -> 0.265; DBGSOM_EXACT_FORK=0 runs them in a row)
-    static const int fork_env = [] {
-        const char *e = getenv("DBGSOM_EXACT_FORK");
-        return e ? atoi(e) : 1;
-    }();
-    // few sample buckets (C2, a rank's share in strong scaling): two 64-sample workgroups per bucket
-    // (DBGSOM_EXACT_SPLIT=0|1 forces).  Measured at C2 (469 buckets): stage 0.164 -> see DESIGN.md
-    static const int split_env = [] {
-        const char *e = getenv("DBGSOM_EXACT_SPLIT");
-        return e ? atoi(e) : -1;
-    }();
-    // (with the refinement: what is left to this stage is a few workgroups)
-    const bool exact_split = split_env >= 0 ? split_env != 0 : (refine || f.nb <= 1024);
-    // (k = 1 without the refinement: all three list-length classes go as ONE launch on the caller's stream -- nothing
-    //  to fork; DBGSOM_EXACT_MERGED=0: three launches on three streams)
-    static const bool merged_env = [] {
-        const char *e = getenv("DBGSOM_EXACT_MERGED");
-        return e ? atoi(e) != 0 : true;
-    }();
-    const bool merged = merged_env && !k2 && !refine;
-    const bool fork = fork_env != 0 && !merged && side.ready();
+    // ms for the stage, a 125 k-row shard of C4 0.303 -> 0.265, against running them in a row)
+    // (k = 1 without the refinement: all three list-length classes go as ONE launch on the caller's stream --
+    //  nothing to fork)
+    const bool merged = !k2 && !refine;
+    const bool fork = !merged && side.ready();
     hipStream_t s2 = fork ? side.stream : s, s3 = fork ? side.stream2 : s;
     // With the refinement the matrix-core stage only has the workgroups the refinement does not take (lists
     // beyond its tiles: a few long chains on a mostly idle chip): all of it on the second stream, beside the
@@ -2909,22 +2829,19 @@ int dbgsom::launch_bmu_filtered(const FilteredCall &call) {
             DBGSOM_HIP_CHECK(hipEventRecord(side.mid, s_mfma));
             DBGSOM_HIP_CHECK(hipStreamWaitEvent(s3, side.mid, 0));
         }
-        // every launch is a few workgroups per CU walking its class's queue
-#define DBGSOM_REFINE_LAUNCH(NJ_, JT_, CLS, WGS)                                                                  \
-    hipLaunchKernelGGL((refine_i8_kernel<NJ_, JT_>), dim3((unsigned)((f.nb + 7) / 8 * 8 < (WGS) ? (f.nb + 7) / 8 * 8 : (WGS))), dim3(NJ_ * 256), 0, s, \
-                       xb.planes, xb.scale, xb.res16, xx_dev, N, (int)d, dpad, f.wt, (int)f.Mpad, f.wscale, ww_dev,    \
-                       f.summary, order_dev, f.ulist, (int)f.Mpad, f.ucount, f.rf_queue + (size_t)(CLS) * f.nb,      \
-                       f.rf_qlen + (CLS), f.cand, f.rbest, f.rf_ctr, f.ovf, f.rf_qlen + 2, f.ovf_cand, defer_M, idx_dev, dist_dev)
-        static const int wgs_env = [] {   // DBGSOM_REFINE_WGS: workgroups per launch (diagnostics; a multiple of 8)
-            const char *e = getenv("DBGSOM_REFINE_WGS");
-            return e ? atoi(e) / 8 * 8 : 0;
-        }();
-        const int wgs1 = wgs_env >= 8 ? wgs_env : 1024, wgs2 = wgs_env >= 8 ? wgs_env : 512;
-        if (rows0 == 32) DBGSOM_REFINE_LAUNCH(1, 1, 0, wgs1);
-        else if (rows0 == 64) DBGSOM_REFINE_LAUNCH(1, 2, 0, wgs1);
-        else if (rows0 == 128) DBGSOM_REFINE_LAUNCH(2, 2, 0, wgs2);
-        DBGSOM_REFINE_LAUNCH(2, 4, 1, wgs2);
-#undef DBGSOM_REFINE_LAUNCH
+        // every launch is a few workgroups per CU walking its class's queue: workgroups of nj x 256 threads,
+        // whole rounds of the 8 XCDs, at most `wgs` of them
+        auto refine_launch = [&](auto kernel, int nj, int cls, int64_t wgs) {
+            const int64_t nb8 = (f.nb + 7) / 8 * 8;
+            hipLaunchKernelGGL(kernel, dim3((unsigned)(nb8 < wgs ? nb8 : wgs)), dim3(nj * 256), 0, s, xb.planes, xb.scale,
+                               xb.res16, xx_dev, N, (int)d, dpad, f.wt, (int)f.Mpad, f.wscale, ww_dev, f.summary, order_dev,
+                               f.ulist, (int)f.Mpad, f.ucount, f.rf_queue + (size_t)cls * f.nb, f.rf_qlen + cls, f.cand,
+                               f.rbest, f.rf_ctr, f.ovf, f.rf_qlen + 2, f.ovf_cand, defer_M, idx_dev, dist_dev);
+        };
+        if (rows0 == 32) refine_launch(refine_i8_kernel<1, 1>, 1, 0, 1024);
+        else if (rows0 == 64) refine_launch(refine_i8_kernel<1, 2>, 1, 0, 1024);
+        else if (rows0 == 128) refine_launch(refine_i8_kernel<2, 2>, 2, 0, 512);
+        refine_launch(refine_i8_kernel<2, 4>, 2, 1, 512);
         // the samples by their refined best prototype: a workgroup of the pair kernel then shares its candidates
         const int64_t Mk = defer_M ? M + 1 : M;   // (deferred: the decided samples behind every real bucket)
         const int rc = launch_bucket_sort(f.rbest, N, Mk, f.order2, f.sort_ws, s);
@@ -2953,89 +2870,41 @@ int dbgsom::launch_bmu_filtered(const FilteredCall &call) {
                                xx_dev, W_dev, ww_dev, f.ulist, (int)f.Mpad, f.ucount, f.ovf, f.rf_qlen + 2, f.ovf_cand, round_f32,
                                idx_dev, dist_dev);
     }
-    // (stages of the 64-sample workgroups' ring: what fits four workgroups per CU, 40 KB each)
-#define SPLIT_NS(JTL, XS) split_ring_stages(JTL, XS)
-#define DBGSOM_SUBSET_W(JTL, NWV_, STREAM)                                                        \
-    do {                                                                                          \
-        if (exact_split && x_dtype == DBGSOM_F32)                                                 \
-            hipLaunchKernelGGL((subset_exact_kernel<float, JTL, 4, 2, 1, SPLIT_NS(JTL, 4)>), dim3((unsigned)(2 * f.nb)), dim3(256), 0, STREAM, \
-                               (const float *)X_dev, N, (int)d, ldx, xx_dev, W_dev, (int)M, ww_dev, \
-                               order_dev, f.ulist, (int)f.Mpad, f.ucount, f.sched, f.sched_ctr + 2 * SCHED_BINS, round_f32, idx_dev, dist_dev); \
-        else if (exact_split)                                                                     \
-            hipLaunchKernelGGL((subset_exact_kernel<double, JTL, 4, 2, 1, SPLIT_NS(JTL, 8)>), dim3((unsigned)(2 * f.nb)), dim3(256), 0, STREAM, \
-                               (const double *)X_dev, N, (int)d, ldx, xx_dev, W_dev, (int)M, ww_dev, \
-                               order_dev, f.ulist, (int)f.Mpad, f.ucount, f.sched, f.sched_ctr + 2 * SCHED_BINS, round_f32, idx_dev, dist_dev); \
-        else if (x_dtype == DBGSOM_F32)                                                           \
-            hipLaunchKernelGGL((subset_exact_kernel<float, JTL, NWV_>), dim3((unsigned)f.nb), dim3(NWV_ * 64), 0, STREAM, \
-                               (const float *)X_dev, N, (int)d, ldx, xx_dev, W_dev, (int)M, ww_dev, \
-                               order_dev, f.ulist, (int)f.Mpad, f.ucount, f.sched, f.sched_ctr + 2 * SCHED_BINS, round_f32, idx_dev, dist_dev); \
-        else                                                                                      \
-            hipLaunchKernelGGL((subset_exact_kernel<double, JTL, NWV_>), dim3((unsigned)f.nb), dim3(NWV_ * 64), 0, STREAM, \
-                               (const double *)X_dev, N, (int)d, ldx, xx_dev, W_dev, (int)M, ww_dev, \
-                               order_dev, f.ulist, (int)f.Mpad, f.ucount, f.sched, f.sched_ctr + 2 * SCHED_BINS, round_f32, idx_dev, dist_dev); \
-    } while (0)
-    // Wavefronts per workgroup of the exact stage: 4 x 32 samples or 8 x 16 (half the accumulators:
-    // class 3 goes from 3 to 6 wavefronts per SIMD).  Measured (ms per stage, 4 / 8 / class 3 only):
-    // C4 1.23 / 1.23 / 1.16, C3 0.52 / 0.48, C5 shard 5.83 / 5.33 -- 8 for the long lists, 4 for the
-    // rest.  DBGSOM_EXACT_WAVES = 4 | 8 | two digits (class 3, classes 2 and 1).
-    static const int exact_waves = [] {
-        const char *e = getenv("DBGSOM_EXACT_WAVES");
-        return e ? atoi(e) : 84;
-    }();
-    // (two digits: class 3, then classes 2 and 1)
-#define DBGSOM_SUBSET(JTL, STREAM)                                                                \
-    do {                                                                                          \
-        const int w_ = exact_waves >= 10 ? (JTL == 3 ? exact_waves / 10 : exact_waves % 10) : exact_waves; \
-        if (w_ == 8) DBGSOM_SUBSET_W(JTL, 8, STREAM);                                             \
-        else DBGSOM_SUBSET_W(JTL, 4, STREAM);                                                     \
-    } while (0)
-    if (k2) {
-        // (8 wavefronts x 16 samples: with two (value, index) pairs per sample the 4 x 32 shape needed 256
-        //  registers for the long-list class and spilled in the others)
-        constexpr int K2_WAVES = 8;
-#define DBGSOM_SUBSET_K2(JTL, STREAM)                                                             \
-    do {                                                                                          \
-        if (x_dtype == DBGSOM_F32)                                                                \
-            hipLaunchKernelGGL((subset_exact_kernel<float, JTL, K2_WAVES, 1, 2>), dim3((unsigned)f.nb), dim3(K2_WAVES * 64), 0, STREAM, \
-                               (const float *)X_dev, N, (int)d, ldx, xx_dev, W_dev, (int)M, ww_dev, \
-                               order_dev, f.ulist, (int)f.Mpad, f.ucount, f.sched, f.sched_ctr + 2 * SCHED_BINS, round_f32, idx_dev, dist_dev); \
-        else                                                                                      \
-            hipLaunchKernelGGL((subset_exact_kernel<double, JTL, K2_WAVES, 1, 2>), dim3((unsigned)f.nb), dim3(K2_WAVES * 64), 0, STREAM, \
-                               (const double *)X_dev, N, (int)d, ldx, xx_dev, W_dev, (int)M, ww_dev, \
-                               order_dev, f.ulist, (int)f.Mpad, f.ucount, f.sched, f.sched_ctr + 2 * SCHED_BINS, round_f32, idx_dev, dist_dev); \
-    } while (0)
-        DBGSOM_SUBSET_K2(3, s_mfma);
-        DBGSOM_SUBSET_K2(2, s2);
-        DBGSOM_SUBSET_K2(1, s3);
-#undef DBGSOM_SUBSET_K2
-    } else if (merged && !exact_split) {
-        if (x_dtype == DBGSOM_F32)
-            hipLaunchKernelGGL((subset_exact_all_kernel<float>), dim3((unsigned)f.nb), dim3(512), 0, s,
-                               (const float *)X_dev, N, (int)d, ldx, xx_dev, W_dev, (int)M, ww_dev, order_dev, f.ulist,
-                               (int)f.Mpad, f.ucount, f.sched, f.sched_ctr + 2 * SCHED_BINS, round_f32, idx_dev, dist_dev);
-        else
-            hipLaunchKernelGGL((subset_exact_all_kernel<double>), dim3((unsigned)f.nb), dim3(512), 0, s,
-                               (const double *)X_dev, N, (int)d, ldx, xx_dev, W_dev, (int)M, ww_dev, order_dev, f.ulist,
-                               (int)f.Mpad, f.ucount, f.sched, f.sched_ctr + 2 * SCHED_BINS, round_f32, idx_dev, dist_dev);
-    } else if (merged) {
-        if (x_dtype == DBGSOM_F32)
-            hipLaunchKernelGGL((subset_exact_split_kernel<float>), dim3((unsigned)(2 * f.nb), 3), dim3(256), 0, s,
-                               (const float *)X_dev, N, (int)d, ldx, xx_dev, W_dev, (int)M, ww_dev, order_dev, f.ulist,
-                               (int)f.Mpad, f.ucount, f.sched, f.sched_ctr + 2 * SCHED_BINS, round_f32, idx_dev, dist_dev);
-        else
-            hipLaunchKernelGGL((subset_exact_split_kernel<double>), dim3((unsigned)(2 * f.nb), 3), dim3(256), 0, s,
-                               (const double *)X_dev, N, (int)d, ldx, xx_dev, W_dev, (int)M, ww_dev, order_dev, f.ulist,
-                               (int)f.Mpad, f.ucount, f.sched, f.sched_ctr + 2 * SCHED_BINS, round_f32, idx_dev, dist_dev);
-    } else {
-        DBGSOM_SUBSET(3, s_mfma);
-        DBGSOM_SUBSET(2, refine ? s3 : s2);
-        DBGSOM_SUBSET(1, s3);
-    }
-#undef DBGSOM_SUBSET
-#undef DBGSOM_SUBSET_W
-#undef SPLIT_NS
-#undef DBGSOM_SWEEP
-#undef S4_LAUNCH
+    // The matrix-core stage on the candidates, in the samples' type.  Every form takes the same arguments.
+    // (Wavefronts per 128-sample workgroup, measured as three launches, ms per stage, 4 / 8 / 8 for class 3
+    //  only: C4 1.23 / 1.23 / 1.16, C3 0.52 / 0.48, C5 shard 5.83 / 5.33 -- 8 for the long lists, 4 for the
+    //  rest; subset_exact_all_kernel runs every class as 8 in one launch, see there.)
+    auto exact_stage = [&](auto xt) {
+        using XT = decltype(xt);
+        constexpr int XS = (int)sizeof(XT);
+        auto launch = [&](auto kernel, dim3 grid, dim3 block, hipStream_t st) {
+            hipLaunchKernelGGL(kernel, grid, block, 0, st, (const XT *)X_dev, N, (int)d, ldx, xx_dev, W_dev, (int)M, ww_dev,
+                               order_dev, f.ulist, (int)f.Mpad, f.ucount, f.sched, f.sched_ctr + 2 * SCHED_BINS, round_f32,
+                               idx_dev, dist_dev);
+        };
+        const unsigned nb = (unsigned)f.nb;
+        if (k2) {
+            // (8 wavefronts x 16 samples: with two (value, index) pairs per sample the 4 x 32 shape needed 256
+            //  registers for the long-list class and spilled in the others)
+            launch(subset_exact_kernel<XT, 3, 8, 1, 2>, dim3(nb), dim3(512), s_mfma);
+            launch(subset_exact_kernel<XT, 2, 8, 1, 2>, dim3(nb), dim3(512), s2);
+            launch(subset_exact_kernel<XT, 1, 8, 1, 2>, dim3(nb), dim3(512), s3);
+        } else if (refine) {
+            // (what is left to this stage is a few workgroups: two 64-sample ones per bucket, the long lists on
+            //  the second stream, the rest on the third)
+            launch(subset_exact_kernel<XT, 3, 4, 2, 1, split_ring_stages(3, XS)>, dim3(2 * nb), dim3(256), s_mfma);
+            launch(subset_exact_kernel<XT, 2, 4, 2, 1, split_ring_stages(2, XS)>, dim3(2 * nb), dim3(256), s3);
+            launch(subset_exact_kernel<XT, 1, 4, 2, 1, split_ring_stages(1, XS)>, dim3(2 * nb), dim3(256), s3);
+        } else if (f.nb <= 1024) {
+            // few sample buckets (C2, a rank's share in strong scaling): two 64-sample workgroups per bucket.
+            // Measured at C2 (469 buckets): stage 0.164 -> see DESIGN.md
+            launch(subset_exact_split_kernel<XT>, dim3(2 * nb, 3), dim3(256), s);
+        } else {
+            launch(subset_exact_all_kernel<XT>, dim3(nb), dim3(512), s);
+        }
+    };
+    if (x_dtype == DBGSOM_F32) exact_stage(float{});
+    else exact_stage(double{});
     if (fork) {
         DBGSOM_HIP_CHECK(hipEventRecord(side.joined, s2));
         DBGSOM_HIP_CHECK(hipEventRecord(side.joined2, s3));
@@ -3095,8 +2964,3 @@ int dbgsom_bmu_filtered_counts_async(const void *workspace_dev, int64_t N, int64
 
 }  // extern "C"
 
-#if defined(DBGSOM_EXPERIMENTS) && PRUNE_STAMPS
-extern "C" int dbgsom_experiment_prune_stamps(unsigned long long *out, int n) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_prune_stamps), (size_t)n * 8, 0, hipMemcpyDeviceToHost);
-}
-#endif

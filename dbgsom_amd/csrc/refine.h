@@ -71,9 +71,6 @@ struct RefineCfg {
     static constexpr int MAX_CNT = ROWS;
 };
 
-#ifndef REFINE_DEPHASE
-#define REFINE_DEPHASE 1
-#endif
 template <int NJ, int JT>
 __global__ __launch_bounds__(NJ * 256, NJ < 2 ? 2 : NJ) void refine_i8_kernel(
     const int8_t *__restrict__ xplanes, const double *__restrict__ sx, const double *__restrict__ xres,
@@ -242,7 +239,7 @@ __global__ __launch_bounds__(NJ * 256, NJ < 2 ? 2 : NJ) void refine_i8_kernel(
         // (the two wavefronts of a SIMD -- wave w and w + 4 -- take turns: one issues its LDS-DMAs of tile
         //  t + 2 in front of its matrix products, the other behind them, so that the one's issue stalls run
         //  under the other's products instead of both stalling right behind the barrier)
-        const bool issue_first = REFINE_DEPHASE == 0 || NJ < 2 || (wj & 1) == 0;
+        const bool issue_first = NJ < 2 || (wj & 1) == 0;
         if (issue_first && t + 2 < nkt) issue();
         const char *stage = smem + r_stage;
         r_stage = (r_stage == (FSTAGES - 1) * C::STAGE) ? 0 : r_stage + C::STAGE;

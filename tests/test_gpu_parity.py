@@ -1067,21 +1067,38 @@ def test_search_arms_that_have_been_timed_are_compared_by_their_time():
     be.release(); ex.release()
 
 
-def test_eight_wavefront_sweep_and_prepass_still_agree_with_the_all_pairs_kernel():
-    """The 4-wavefront kernels are the default shape of the one-product sweep and of the seed
-    pre-pass; the 8-wavefront ones (DBGSOM_SWEEP_SHAPE=8 / DBGSOM_PREPASS_SHAPE=8, read once per
-    process) are checked in a child process by the randomised comparison against the all-pairs
-    kernel."""
-    import os
-    import subprocess
-    import sys
+def test_eight_wavefront_sweep_agrees_with_the_all_pairs_kernel_beyond_8192_prototypes():
+    """Maps of more than 8192 prototypes are too large for the bitmask of the two-workgroups-per-CU
+    sweep: their one-product sweep runs as the 8-wavefront kernel (one workgroup per CU).  Random
+    maps of 8193 .. 16000 prototypes, float32, float64 and bfloat16 samples, stateless and seeded
+    by the previous winners: winners, distances and new prototypes are those of the all-pairs
+    kernel, bit for bit."""
+    from dbgsom_amd.backend import HipBackend
 
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, DBGSOM_SWEEP_SHAPE="8", DBGSOM_PREPASS_SHAPE="8")
-    out = subprocess.run([sys.executable, os.path.join(root, "tools", "stress_filtered.py"), "7", "24"],
-                         env=env, capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert "24 cases, 0 mismatches" in out.stdout, out.stdout[-2000:]
+    rng = np.random.default_rng(8193)
+    for case in range(9):
+        dt = ("f32", "f64", "bf16")[case % 3]
+        N = int(rng.integers(1500, 4000))
+        d = int(rng.choice([16, 48, 64, 96]))
+        M = int(rng.integers(8193, 16001))
+        c = rng.normal(size=(int(rng.integers(4, 40)), d)) * 3
+        X = c[rng.integers(0, len(c), size=N)] + rng.normal(size=(N, d))
+        X = X.astype(np.float64 if dt == "f64" else np.float32)
+        W = X[rng.choice(N, M, replace=True)].astype(np.float64) + 1e-3 * rng.normal(size=(M, d))
+        hop = np.zeros((M, M))
+        storage = "bf16" if dt == "bf16" else None
+        ex = HipBackend(algorithm="exact").load(X, storage=storage)
+        fi = HipBackend(algorithm="filtered").load(X, storage=storage)
+        fi.sweep_planes = 1
+        for _ in range(2):  # stateless, then with the first epoch's winners as seeds
+            re_ = ex.epoch(W, hop, 1.0, 1e-3, "compact", True)
+            rf = fi.epoch(W, hop, 1.0, 1e-3, "compact", True)
+            assert fi.filter_log[-1][0] == "filtered" and fi.filter_log[-1][2] == 1, (case, fi.filter_log[-1])
+            assert np.array_equal(rf.winners, re_.winners), (case, dt, N, d, M)
+            assert np.array_equal(rf.distances, re_.distances), (case, dt, N, d, M)
+            assert np.array_equal(rf.new_weights, re_.new_weights, equal_nan=True), (case, dt, N, d, M)
+            fi.algorithm = "filtered_hint"
+        ex.release(); fi.release()
 
 
 @pytest.mark.parametrize("N,d,M", [(3000, 32, 8192), (3000, 32, 9000), (100, 48, 200), (129, 16, 129),
