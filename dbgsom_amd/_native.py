@@ -77,6 +77,18 @@ SIGNATURES = {
     "dbgsom_ctx_load_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64]),
     "dbgsom_ctx_read_samples": (_ci, [_vp, _vp, _i64, _vp]),
     "dbgsom_ctx_set_labels": (_ci, [_vp, _vp, _i64]),
+    "dbgsom_ctx_set_sample_weight": (_ci, [_vp, _vp, _i64]),
+    "dbgsom_ctx_weight_total": (_ci, [_vp, _vp]),
+    "dbgsom_ctx_weighted_column_sums": (_ci, [_vp, _vp, _vp]),
+    "dbgsom_ctx_class_histogram_weighted": (_ci, [_vp, _vp, _i64, _i64, _vp]),
+    "dbgsom_accumulate_weighted_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "dbgsom_accumulate_weighted": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                         _sz, _vp]),
+    "dbgsom_weighted_sum_f64": (_ci, [_vp, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "dbgsom_topographic_weight": (_ci, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "dbgsom_class_histogram_weighted": (_ci, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
+    "dbgsom_weighted_column_sums_workspace_bytes": (_sz, [_i64]),
+    "dbgsom_weighted_column_sums": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dbgsom_ctx_set_topology": (_ci, [_vp, _vp, _i64]),
     "dbgsom_ctx_set_allreduce": (_ci, [_vp, _vp, _vp]),
     "dbgsom_ctx_set_collectives": (_ci, [_vp, _vp, _vp, _ci, _ci]),

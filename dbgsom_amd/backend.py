@@ -137,15 +137,30 @@ class HotPathBackend:
         """Attach integer class labels of the resident rows (entropy criterion)."""
         self._y = None if y is None else np.ascontiguousarray(y, dtype=np.int32)
 
+    def set_sample_weight(self, w):
+        """Attach one weight per resident row (``fit(..., sample_weight=w)``: a row of weight w counts
+        as w copies of that row; None detaches).  The epoch sums and the reductions below are then the
+        weighted ones: S = sum w h x, K = sum w h, a = sum w, E = sum w dist."""
+        self._sw = None if w is None else np.ascontiguousarray(w, dtype=np.float64)
+
+    _sw = None
+
     def quantization_error(self, W) -> float:
         dist, _ = self.bmu(W, 1)
+        if self._sw is not None:
+            s = self._reduce_host(np.array([self._sw @ dist, self._sw.sum()], dtype=np.float64))
+            return float(s[0] / s[1])
         s = self._reduce_host(np.array([dist.sum(), dist.size], dtype=np.float64))
         return float(s[0] / s[1])
 
-    def topographic_error_count(self, W, coords) -> int:
+    def topographic_error_count(self, W, coords):
+        """Rows whose two best matching units are not lattice neighbours: their number, or with
+        weights attached their summed weight (a float)."""
         _, idx = self.bmu(W, 2)
         pos = np.asarray(coords, dtype=np.float64)
         apart = np.linalg.norm(pos[idx[:, 0]] - pos[idx[:, 1]], axis=1) > 1.5
+        if self._sw is not None:
+            return float(self._reduce_host(np.array([self._sw[apart].sum()], np.float64))[0])
         return int(round(self._reduce_host(np.array([np.count_nonzero(apart)], np.float64))[0]))
 
     def node_statistics(self, W, sigma):
@@ -153,15 +168,22 @@ class HotPathBackend:
         dist, win = self.bmu(W, 1)
         m = np.asarray(W).shape[0]
         terms = np.exp(-(dist ** 2) / (2 * sigma ** 2)) / (sigma * np.sqrt(2 * np.pi))
-        both = np.concatenate([np.bincount(win, minlength=m).astype(np.float64),
-                               np.bincount(win, weights=terms, minlength=m)])
+        if self._sw is not None:
+            both = np.concatenate([np.bincount(win, weights=self._sw, minlength=m),
+                                   np.bincount(win, weights=self._sw * terms, minlength=m)])
+        else:
+            both = np.concatenate([np.bincount(win, minlength=m).astype(np.float64),
+                                   np.bincount(win, weights=terms, minlength=m)])
         both = self._reduce_host(both)
         return both[:m], both[m:]
 
     def class_histogram(self, winners, n_classes, M):
+        """(M, n_classes) class counts per neuron over all ranks: int64, or with weights attached the
+        summed weights (float64)."""
         h = np.zeros((M, n_classes), dtype=np.float64)
-        np.add.at(h, (winners, self._y), 1.0)
-        return self._reduce_host(h.reshape(-1)).reshape(M, n_classes).astype(np.int64)
+        np.add.at(h, (winners, self._y), 1.0 if self._sw is None else self._sw)
+        h = self._reduce_host(h.reshape(-1)).reshape(M, n_classes)
+        return h if self._sw is not None else h.astype(np.int64)
 
     # -- sparse coding (BaseSom.transform, SomClassifier.predict_proba); host default ----------------
     def sparse_code(self, W, X, P=None, max_iter=1000, n_jobs=None):
@@ -530,6 +552,8 @@ class HipBackend(HotPathBackend):
         self._hop_key = None
         self._last_M = 0
         self._y = None
+        self._sw = None          # (a load detaches the weights of the rows that were resident)
+        self._weighted = False
 
     def read_samples(self, rows):
         """Rows of the resident samples as float64 (exactly widened)."""
@@ -842,6 +866,35 @@ class HipBackend(HotPathBackend):
         self._call("dbgsom_ctx_column_sums", self._ctx, mean.ctypes.data, s2.ctypes.data)
         return s1, s2, self._N
 
+    _weighted = False
+
+    def set_sample_weight(self, w):
+        """One float64 weight per resident row, kept in HBM next to the samples (None detaches)."""
+        self._require_loaded()
+        super().set_sample_weight(w)
+        if w is None:
+            self._call("dbgsom_ctx_set_sample_weight", self._ctx, None, 0)
+        else:
+            self._call("dbgsom_ctx_set_sample_weight", self._ctx, self._sw.ctypes.data, self._sw.size)
+        self._weighted = w is not None
+
+    def weight_total(self) -> float:
+        """Sum of the resident rows' weights (the number of rows when none are attached)."""
+        out = np.empty(1)
+        self._call("dbgsom_ctx_weight_total", self._ctx, out.ctypes.data)
+        return float(out[0])
+
+    def weighted_column_moments(self, total):
+        """(sum_i w_i x_ij, sum_i w_i (x_ij - mean_j)^2) over the resident samples, mean = the first over
+        `total` (the summed weight): accumulated in float64 whatever the storage dtype."""
+        self._require_loaded()
+        s1 = np.empty(self._d)
+        self._call("dbgsom_ctx_weighted_column_sums", self._ctx, None, s1.ctypes.data)
+        mean = np.ascontiguousarray(s1 / total)
+        s2 = np.empty(self._d)
+        self._call("dbgsom_ctx_weighted_column_sums", self._ctx, mean.ctypes.data, s2.ctypes.data)
+        return s1, s2
+
     def quantization_error(self, W) -> float:
         self._require_loaded()
         keep, p, M, rf = self._w_arg(W)
@@ -857,7 +910,7 @@ class HipBackend(HotPathBackend):
             raise ValueError("coords must be (M, 2)")
         out = np.empty(1)
         self._call("dbgsom_ctx_topographic_count", self._ctx, p, M, rf, xy.ctypes.data, out.ctypes.data)
-        return int(round(out[0]))
+        return float(out[0]) if self._weighted else int(round(out[0]))
 
     def node_statistics(self, W, sigma):
         """-> (hit_counts (M,), density_sums (M,)) of BaseSom._calculate_node_statistics."""
@@ -876,9 +929,15 @@ class HipBackend(HotPathBackend):
             self._call("dbgsom_ctx_set_labels", self._ctx, self._y.ctypes.data, self._y.size)
 
     def class_histogram(self, winners, n_classes, M):
-        """(M, n_classes) int64 over all ranks; winners=None: the last epoch's (still in HBM)."""
-        hist = np.empty((M, n_classes), dtype=np.int64)
+        """(M, n_classes) int64 over all ranks (float64 summed weights with weights attached);
+        winners=None: the last epoch's (still in HBM)."""
         idx = None if winners is None else np.ascontiguousarray(winners, dtype=np.int64)
+        if self._weighted:
+            hist = np.empty((M, n_classes), dtype=np.float64)
+            self._call("dbgsom_ctx_class_histogram_weighted", self._ctx, None if idx is None else idx.ctypes.data,
+                       int(n_classes), int(M), hist.ctypes.data)
+            return hist
+        hist = np.empty((M, n_classes), dtype=np.int64)
         self._call("dbgsom_ctx_class_histogram", self._ctx, None if idx is None else idx.ctypes.data,
                    int(n_classes), int(M), hist.ctypes.data)
         return hist
@@ -898,7 +957,9 @@ class HipBackend(HotPathBackend):
         """A backend whose resident samples are the Voronoi set of `neuron` (gathered in HBM)."""
         child = ctypes.c_void_p()
         self._call("dbgsom_ctx_subset_create", self._ctx, int(neuron), ctypes.byref(child))
-        return HipBackend(self.device_index, self.algorithm, _ctx=child)
+        sub = HipBackend(self.device_index, self.algorithm, _ctx=child)
+        sub._weighted = self._weighted   # (dbgsom_ctx_subset_create gathered the rows' weights)
+        return sub
 
     _SETTABLE = ("algorithm", "sweep_planes", "seed_stride", "timing", "graph", "refine", "defer",
                  "filter_min_query_rows", "max_mean_candidates", "shard_smooth")
@@ -916,6 +977,8 @@ class HipBackend(HotPathBackend):
         self._loaded = False
         self._borrowed = None
         self._hop_key = None
+        self._weighted = False
+        self._sw = None
 
     def __del__(self):
         try:

@@ -123,18 +123,32 @@ class BaseSom(BaseEstimator):
         state = dict(state)
         state.pop("_backend_obj", None)  # device handles are not picklable
         state.pop("_resident", None)
+        for k in ("_sw", "_sw_global"):
+            state.pop(k, None)
         return state
 
     # ------------------------------------------------------------------------------------------
     # fit
     # ------------------------------------------------------------------------------------------
-    def fit(self, X, y=None):
-        """Train the map on X (BaseSom.fit, BaseSom.py:88-131)."""
+    def fit(self, X, y=None, sample_weight=None):
+        """Train the map on X (BaseSom.fit, BaseSom.py:88-131).
+
+        sample_weight : array-like of shape (n_samples,), optional
+            A row of weight w counts as w copies of that row: for integer weights the fit equals the
+            fit on ``np.repeat(X, sample_weight, axis=0)`` for the same ``random_state`` -- start
+            prototypes, growing threshold, every epoch's sums, errors, hit counts, labels and class
+            frequencies -- while the BMU search and the stream of X are paid once per distinct row.
+            Rows of weight 0 take no part in anything.  Non-negative, finite, not all zero, at least
+            four rows of positive weight.  ``None``: every row counts once (the unweighted code path).
+            ``predict`` / ``transform`` and the other queries on new data are not weighted."""
         if isinstance(X, DeviceSamples):   # a Voronoi subset that already lives in HBM (f-4)
             if y is not None:
                 y = np.asarray(y)
+            if sample_weight is not None:
+                sample_weight = np.ascontiguousarray(sample_weight, dtype=np.float64)
         else:
             X, y = self._check_input_data(X, y)
+            sample_weight = self._check_sample_weight(sample_weight, X)
         if y is not None:
             classes, y = np.unique(y, return_inverse=True)
             self.classes_ = np.array(classes)
@@ -142,6 +156,7 @@ class BaseSom(BaseEstimator):
         engine = self._engine()
         self._load_resident(X)  # samples go to HBM once and stay there for the whole fit
         try:
+            self._attach_sample_weight(X, sample_weight)
             self._initialize_som(X)
             self._grow_som(X, y)
             self.topographic_error_ = self._calculate_topographic_error(X)
@@ -156,8 +171,82 @@ class BaseSom(BaseEstimator):
             self.n_iter_ = self._current_epoch
         finally:
             self._resident = None
+            self._sw = self._sw_global = None
+            if hasattr(engine, "set_sample_weight") and getattr(engine, "_sw", None) is not None:
+                engine.set_sample_weight(None)   # (the backend object may serve another fit)
             engine.release()
         return self
+
+    # -- sample weights -------------------------------------------------------------------------
+    _sw = None          # the weights of the rows handed to fit (None: unweighted), aligned with X as passed
+    _sw_global = None   # the weights of all rows of all ranks (differs from _sw with sharded_input only)
+    _w_total = None     # their sum
+    _w_integer = None   # every weight is an integer (the start rows are then those of the fit on repeated rows)
+    _w_offset = None    # sharded_input, integer weights: the summed weight of the ranks before this one
+
+    def _check_sample_weight(self, sample_weight, X):
+        if sample_weight is None:
+            return None
+        from sklearn.utils.validation import _check_sample_weight
+
+        w = _check_sample_weight(sample_weight, X, dtype=np.float64, ensure_non_negative=True)
+        if getattr(self, "_finite_deferred", False):
+            # (the finite check that rides on the device's column sums does not see rows of weight 0)
+            from sklearn.utils import assert_all_finite
+
+            self._finite_deferred = False
+            assert_all_finite(X)
+        return np.ascontiguousarray(w, dtype=np.float64)
+
+    def _attach_sample_weight(self, X, w) -> None:
+        """Hand this rank's rows' weights to the backend (resident next to the samples) and keep what the
+        host side needs: the weights of all rows and their sum."""
+        self._sw = w
+        self._sw_global = w
+        self._w_total = None
+        self._w_integer = self._w_offset = None
+        engine = self._engine()
+        if w is None:
+            if hasattr(engine, "set_sample_weight") and getattr(engine, "_sw", None) is not None:
+                engine.set_sample_weight(None)   # (a backend that an earlier, weighted fit used)
+            return
+        if isinstance(X, DeviceSamples):
+            if not getattr(engine, "_weighted", False):   # (a device subset brings its rows' weights along)
+                engine.set_sample_weight(w)
+        elif self._local_input():
+            engine.set_sample_weight(w)
+        else:
+            lo, hi = self._shard
+            engine.set_sample_weight(w[lo:hi])
+        # sum w, rows of positive weight, rows whose weight is no integer: all-reduced once per fit when every rank
+        # holds its own rows only
+        tot = np.array([w.sum(), np.count_nonzero(w > 0), np.count_nonzero(w != np.floor(w))], dtype=np.float64)
+        if self._local_input():
+            local_total = tot[0]
+            tot = self._all_reduce_f64(tot)
+        self._w_total, positive, self._w_integer = float(tot[0]), int(tot[1]), tot[2] == 0
+        if not self._w_total > 0:
+            raise ValueError("sample_weight is all zero")
+        if positive < 4:
+            raise ValueError(f"Found array with {positive} sample(s) of positive weight "
+                             "while a minimum of 4 is required.")
+        if self._local_input():
+            if self._w_integer:
+                # where this rank's copies begin among the sum w copies of all ranks: an exclusive scan of the totals
+                rank = dist_info()[0]
+                self._w_offset = int(sum(self._all_gather_ints(int(round(local_total)))[:rank]))
+            else:
+                # (a draw with probabilities w / sum w needs every weight: 8 bytes per row of the whole data set, gathered
+                #  for fractional weights only)
+                import torch.distributed as td
+
+                parts = [None] * td.get_world_size()
+                td.all_gather_object(parts, w)
+                self._sw_global = np.concatenate(parts)
+
+    def _n_effective(self):
+        """What "how many rows" means for this fit: their number, or the summed weight."""
+        return self._n_total if self._sw is None else self._w_total
 
     def _load_resident(self, X) -> None:
         """Make this rank's rows resident in HBM.  Default: every rank holds the same X and
@@ -263,7 +352,21 @@ class BaseSom(BaseEstimator):
         # resident copy when it is the whole data set: same values bit for bit (f-1)
         self._col_s2 = None
         on_device = isinstance(data, DeviceSamples)
-        if self._local_input():
+        if self._sw is not None:
+            # weighted population moments, divisor sum w: accumulated in float64 whatever the dtype of X
+            wt = self._w_total
+            if self._local_input():
+                loc, wc = np.asarray(data, dtype=np.float64), self._sw[:, None]
+                mean = self._all_reduce_f64((wc * loc).sum(axis=0)) / wt
+                self._col_s2 = self._all_reduce_f64((wc * (loc - mean) ** 2).sum(axis=0))
+            elif (on_device or self._shard == (0, data.shape[0])) and hasattr(engine, "weighted_column_moments"):
+                self._col_s2 = engine.weighted_column_moments(wt)[1]
+            else:
+                # (NumPy's own axis-0 sums: with all-ones weights on float64 data, np.var's arithmetic)
+                full, wc = np.asarray(data, dtype=np.float64), self._sw[:, None]
+                mean = (wc * full).sum(axis=0) / wt
+                self._col_s2 = (wc * (full - mean) ** 2).sum(axis=0)
+        elif self._local_input():
             # every rank holds its own rows: moments from two all-reduced passes in float64 (the
             # single-process values up to float64 reassociation -- not NumPy's sequential order)
             loc = np.asarray(data, dtype=np.float64)
@@ -282,7 +385,7 @@ class BaseSom(BaseEstimator):
         self.growing_threshold_ = self._calculate_growing_threshold(data)
         # keeps the dtype NumPy gives it: float32 data -> float32 variance -> float32 reciprocal
         if self._col_s2 is not None:
-            self._total_variance = np.true_divide(self._col_s2, n_total).sum()
+            self._total_variance = np.true_divide(self._col_s2, self._n_effective()).sum()
         else:
             self._total_variance = np.var(data, axis=0).sum()
         self._col_s2 = None
@@ -293,10 +396,15 @@ class BaseSom(BaseEstimator):
             seed = int(self._all_reduce_f64(np.array([float(drawn >> 31), float(drawn & (2 ** 31 - 1))]))
                        @ np.array([2.0 ** 31, 1.0]))
         rng = np.random.default_rng(seed=seed)
-        if on_device or self._local_input():
-            # rng.choice(a=data, size=4, replace=False) picks rows rng.choice(n, 4, replace=False)
-            rows = rng.choice(n_total, size=4, replace=False)
-            if on_device:
+        if on_device or self._local_input() or self._sw is not None:
+            if self._sw is None:
+                # rng.choice(a=data, size=4, replace=False) picks rows rng.choice(n, 4, replace=False)
+                rows = rng.choice(n_total, size=4, replace=False)
+            else:
+                rows = self._draw_weighted_rows(rng)
+            if not (on_device or self._local_input()):
+                start = data[rows]
+            elif on_device:
                 start = engine.read_samples(rows).astype(data.dtype)
             else:
                 lo, hi = self._shard
@@ -310,6 +418,23 @@ class BaseSom(BaseEstimator):
         self._lattice = GrowingLattice(start)
         self._sync_views(refresh_weights=True)
 
+    def _draw_weighted_rows(self, rng) -> np.ndarray:
+        """The four start rows under weights.  All weights integers: the rows that
+        rng.choice(a=np.repeat(X, w, 0), size=4, replace=False) returns -- draw from the sum w copies and
+        map each draw to its owner through cumsum(w) (all ones: the unweighted start).  Otherwise four
+        distinct rows with probabilities w / sum w."""
+        w = self._sw_global
+        if self._w_integer:
+            draws = rng.choice(int(round(self._w_total)), size=4, replace=False)
+            if self._w_offset is None:
+                return np.searchsorted(np.cumsum(w), draws, side="right")
+            # every rank holds its own rows: the owner of a draw is on the rank whose copies it falls among
+            mine = draws - self._w_offset
+            own = (mine >= 0) & (mine < int(round(w.sum())))
+            rows = np.where(own, self._shard[0] + np.searchsorted(np.cumsum(w), np.where(own, mine, 0), side="right"), 0)
+            return np.rint(self._all_reduce_f64(rows.astype(np.float64))).astype(np.int64)   # one owner per draw
+        return rng.choice(w.shape[0], size=4, replace=False, p=w / self._w_total)
+
     def _calculate_growing_threshold(self, data: np.ndarray) -> float:
         if self.growth_criterion == "entropy":
             return self.spreading_factor
@@ -317,7 +442,10 @@ class BaseSom(BaseEstimator):
             return -data.shape[1] * log(self.spreading_factor)
         if self.threshold_method == "se":
             if getattr(self, "_col_s2", None) is not None:
-                spread = np.sqrt(np.true_divide(self._col_s2, max(self._n_total - 1, 0)))
+                if self._sw is not None and not self._w_total > 1:
+                    raise ValueError("threshold_method='se' needs a summed sample_weight above 1 "
+                                     "(frequency weights: the divisor is sum w - 1)")
+                spread = np.sqrt(np.true_divide(self._col_s2, max(self._n_effective() - 1, 0)))
             else:
                 spread = np.std(data, axis=0, ddof=1)
             return float(150 * -log(self.spreading_factor) * np.linalg.norm(spread))
@@ -507,7 +635,7 @@ class BaseSom(BaseEstimator):
     def _calculate_topographic_error(self, X) -> float:
         """Fraction of samples whose two best matching units are not lattice neighbours."""
         if self._is_resident(X):
-            return self._engine().topographic_error_count(self.weights_, self.neurons_) / self._n_total
+            return self._engine().topographic_error_count(self.weights_, self.neurons_) / self._n_effective()
         _, bmu = self._get_winning_neurons(X, n_bmu=2)
         pos = np.asarray(self.neurons_, dtype=np.float64)
         apart = np.linalg.norm(pos[bmu[:, 0]] - pos[bmu[:, 1]], axis=1) > 1.5
@@ -613,23 +741,27 @@ class BaseSom(BaseEstimator):
         engine = self._engine()
         errors = self._lattice.error
         on_device = self._is_resident(X) and hasattr(engine, "subset") and dist_info()[1] == 1
+        sw = self._sw
         if on_device:
-            counts, winners = engine.partition(self.weights_, want_winners=y is not None)
+            counts, winners = engine.partition(self.weights_, want_winners=y is not None or sw is not None)
         else:
             _, winners = self._get_winning_neurons(X, n_bmu=1)
             counts = np.bincount(winners, minlength=len(self.neurons_))
+        if sw is not None:   # a Voronoi set is as large as its rows' summed weight
+            counts = np.bincount(winners, weights=sw, minlength=len(self.neurons_))
         for j, node in enumerate(self.neurons_):
             if not errors[j] > self.vertical_growing_threshold_:
                 continue
             if counts[j] > self.min_samples_vertical_growth:
                 child = clone(self)
                 y_sub = None if y is None else y[winners == j]
+                w_sub = {} if sw is None else {"sample_weight": sw[winners == j]}
                 if on_device:
                     sub = engine.subset(j)
                     child._backend_obj = sub
-                    child.fit(DeviceSamples(sub), y_sub)
+                    child.fit(DeviceSamples(sub), y_sub, **w_sub)
                 else:
-                    child.fit(X[winners == j], y_sub)
+                    child.fit(X[winners == j], y_sub, **w_sub)
                 self.som_.nodes[node]["som"] = child
 
     def plot(self, color=None, palette="magma_r", pointsize=None) -> None:

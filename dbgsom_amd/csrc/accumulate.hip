@@ -12,6 +12,18 @@
 // bucketed by winner with a stable counting sort (per-workgroup LDS histograms + a column scan),
 // each neuron's list is cut into chunks of <= CH rows, one workgroup sums one chunk in list
 // order, and a second pass adds a neuron's chunk partials in chunk order.
+//
+// Weighted form (`sw`, one float64 per row: a row of weight w counts as w copies of that row):
+//   S_j = sum w_i kw_i x_i, K_j = sum w_i kw_i, a_j = sum w_i, E_j = sum w_i dist_i.
+// The kernels' template parameter WGT: the unweighted kernels are the WGT = false instantiations
+// (nothing of the weighted form is in them: `if constexpr`, an empty argument struct) and compile to
+// what they were.  a_j is then
+// a third scalar partial per chunk (slab rows d + 3 wide), added in list, chunk and group order like
+// K and E.  The counting sort is the unweighted one (`order`, the next filtered search's visiting
+// order, stays bucketed by winner: rows of weight 0 in a bucket of their own behind the neurons made
+// that search fall back to all pairs -- 24 ms against 2.1 at C4 with a third of the rows at 0); a row
+// of weight 0 keeps its slot in its neuron's list and is skipped there: never streamed, added to
+// nothing, so a neuron that only such rows chose keeps exact zeros.
 #include <type_traits>
 
 #include "common.h"
@@ -46,7 +58,8 @@ static int finalize_groups(int64_t M) {
     return (int)(g < 1 ? 1 : (g > 32 ? 32 : g));
 }
 
-static size_t carve(AccWs *w, char *base, int64_t N, int64_t d, int64_t M) {
+// ns = scalar partials per slab row (2, weighted: 3)
+static size_t carve(AccWs *w, char *base, int64_t N, int64_t d, int64_t M, int ns = 2) {
     const int HS = hs_for(N);
     const int64_t nb = (N + HS - 1) / HS;
     const int64_t maxchunks = (N + CH - 1) / CH + M;
@@ -57,8 +70,8 @@ static size_t carve(AccWs *w, char *base, int64_t N, int64_t d, int64_t M) {
     const size_t o_count = take((size_t)M * 4);
     const size_t o_seg = take((size_t)(M + 1) * 4);
     const size_t o_chunk = take((size_t)(M + 1) * 4);
-    const size_t o_slab = take((size_t)maxchunks * (d + 2) * 8);
-    const size_t o_gslab = take((size_t)M * finalize_groups(M) * (d + 2) * 8);
+    const size_t o_slab = take((size_t)maxchunks * (d + ns) * 8);
+    const size_t o_gslab = take((size_t)M * finalize_groups(M) * (d + ns) * 8);
     const size_t o_ticket = take(256);
     if (w) {
         w->ticket = (uint32_t *)(base + o_ticket);
@@ -79,6 +92,19 @@ size_t accumulate_workspace_bytes(int64_t N, int64_t d, int64_t M) {
     if (N < 0 || d < 1 || M < 1) return 0;
     return carve(nullptr, nullptr, N, d, M);
 }
+
+size_t accumulate_weighted_workspace_bytes(int64_t N, int64_t d, int64_t M) {
+    if (N < 0 || d < 1 || M < 1) return 0;
+    return carve(nullptr, nullptr, N, d, M, 3);
+}
+
+// what the weighted instantiations take behind the unweighted kernels' arguments (nothing at all for
+// WGT = false: those kernels are the code they were before the weighted form existed)
+template <bool WGT> struct WeightArg {};
+template <> struct WeightArg<true> {
+    const double *sw;          // one weight per row
+};
+
 
 // ---- 1. per-workgroup histogram of winners ---------------------------------------------------
 __global__ __launch_bounds__(AT) void hist_kernel(const int64_t *__restrict__ win, int64_t N,
@@ -234,7 +260,6 @@ __global__ __launch_bounds__(SCW) void scatter_kernel(const int64_t *__restrict_
         __syncthreads();
     }
 }
-
 // (non-temporal: every row is read exactly once by this kernel, 16 bytes per lane and whole cache lines per
 //  wavefront instruction -- streamed past the caches, segsum_kernel's 3.4 GB at C4 take 0.57 instead of 0.64 ms)
 template <typename XT, int VEC>
@@ -262,15 +287,19 @@ __device__ __forceinline__ void load_vec(const XT *__restrict__ src, double (&v)
 }
 
 // ---- 5. one workgroup sums one chunk (<= CH rows of one neuron) in list order ----------------
-template <typename XT, int VEC>
+// (WGT: per row the factor w kw on the x-sum and K -- one rounded product, formed the same way here
+//  and in segsum_chain_kernel --, w dist on E, and the third scalar partial sum w)
+template <typename XT, int VEC, bool WGT>
 __global__ __launch_bounds__(AT) void segsum_kernel(
     const XT *__restrict__ X, int d, int64_t ldx, const int32_t *__restrict__ order,
     const double *__restrict__ kw, double gamma, const double *__restrict__ dist,
     const uint32_t *__restrict__ seg_start, const uint32_t *__restrict__ count,
-    const uint32_t *__restrict__ chunk_pre, int M, double *__restrict__ slab) {
+    const uint32_t *__restrict__ chunk_pre, int M, double *__restrict__ slab, WeightArg<WGT> wa) {
+    constexpr int NS = WGT ? 3 : 2;   // scalar partials behind the d columns of a slab row
     __shared__ int32_t rows_s[CH];
     __shared__ double kw_s[CH];
     __shared__ double dist_s[CH];
+    __shared__ double sw_s[WGT ? CH : 1];
     __shared__ double red[AT * VEC];
     __shared__ uint32_t info[3];
     const int tid = threadIdx.x;
@@ -295,16 +324,29 @@ __global__ __launch_bounds__(AT) void segsum_kernel(
         const double dd = dist[r];
         // kw == nullptr: the sample kernel of BaseSom._calculate_exp_similarity (BaseSom.py:533-538)
         // on the fly, the arithmetic of exp_similarity_kernel (bmu.hip)
-        kw_s[tid] = kw ? kw[r] : 1.0 - sqrt(1.0 - exp(-gamma * (dd * dd)));
-        dist_s[tid] = dd;
+        const double h = kw ? kw[r] : 1.0 - sqrt(1.0 - exp(-gamma * (dd * dd)));
+        if constexpr (WGT) {
+            const double w = wa.sw[r];
+            sw_s[tid] = w;
+            kw_s[tid] = __dmul_rn(w, h);
+            dist_s[tid] = __dmul_rn(w, dd);
+        } else {
+            kw_s[tid] = h;
+            dist_s[tid] = dd;
+        }
     }
     __syncthreads();
-    double *out = slab + (size_t)c * (d + 2);
+    double *out = slab + (size_t)c * (d + NS);
     if (tid == AT - 1) {  // the scalar partials, in list order
         double sk = 0.0, se = 0.0;
         for (int p = 0; p < n; ++p) { sk += kw_s[p]; se += dist_s[p]; }
         out[d] = sk;
         out[d + 1] = se;
+        if constexpr (WGT) {
+            double sa = 0.0;
+            for (int p = 0; p < n; ++p) sa += sw_s[p];
+            out[d + 2] = sa;
+        }
     }
     const int Q = d / VEC;  // column groups (VEC divides d by construction)
     if (Q >= AT) {
@@ -314,6 +356,7 @@ __global__ __launch_bounds__(AT) void segsum_kernel(
             for (int e = 0; e < VEC; ++e) acc[e] = 0.0;
 #pragma unroll 4
             for (int p = 0; p < n; ++p) {
+                if constexpr (WGT) { if (sw_s[p] == 0.0) continue; }   // (weight 0: not streamed)
                 const XT *src = X + (int64_t)rows_s[p] * ldx + (int64_t)q * VEC;
                 const double w = kw_s[p];
                 double v[VEC];
@@ -333,6 +376,7 @@ __global__ __launch_bounds__(AT) void segsum_kernel(
         if (rl < RL) {
 #pragma unroll 4
             for (int p = rl; p < n; p += RL) {
+                if constexpr (WGT) { if (sw_s[p] == 0.0) continue; }
                 const XT *src = X + (int64_t)rows_s[p] * ldx + (int64_t)q * VEC;
                 const double w = kw_s[p];
                 double v[VEC];
@@ -354,7 +398,6 @@ __global__ __launch_bounds__(AT) void segsum_kernel(
         }
     }
 }
-
 // ---- 5b. the same chunk, with the distances of the rows that do not have one yet ----------------------
 // The refinement of the filtered search (filter.hip 2d) knows the winner of a sample whose candidates it
 // could narrow down to ONE without ever touching the sample's float rows; its distance is the float64 chain
@@ -418,13 +461,16 @@ __device__ __forceinline__ void raw_vec(const raw4_t r, double (&v)[VEC]) {
 }
 
 // G = column groups per thread (rows of more than AT groups: q = tid + g AT)
-template <typename XT, int VEC, int G>
+// (WGT: the rows' weights sit in CH doubles behind ChainLds::total -- the launch asks for them)
+template <typename XT, int VEC, int G, bool WGT>
 __global__ __launch_bounds__(AT, G == 1 ? CHAIN_OCC : 2) void segsum_chain_kernel(
     const XT *__restrict__ X, int d, int64_t ldx, const int32_t *__restrict__ order, double gamma,
     double *__restrict__ dist, const uint32_t *__restrict__ seg_start, const uint32_t *__restrict__ count,
     const uint32_t *__restrict__ chunk_pre, int M, double *__restrict__ slab, const double *__restrict__ W,
-    const double *__restrict__ ww, const double *__restrict__ xx, int round_f32, ChainLds L) {
+    const double *__restrict__ ww, const double *__restrict__ xx, int round_f32, ChainLds L, WeightArg<WGT> wa) {
+    constexpr int NS = WGT ? 3 : 2;   // scalar partials behind the d columns of a slab row
     extern __shared__ __attribute__((aligned(16))) char dyn[];
+    [[maybe_unused]] double *sw_s = reinterpret_cast<double *>(dyn + L.total);
     double *w_s = reinterpret_cast<double *>(dyn + L.o_w);
     int32_t *rows_s = reinterpret_cast<int32_t *>(dyn + L.o_rows);
     double *kw_s = reinterpret_cast<double *>(dyn + L.o_kw), *dist_s = reinterpret_cast<double *>(dyn + L.o_dist);
@@ -457,6 +503,7 @@ __global__ __launch_bounds__(AT, G == 1 ? CHAIN_OCC : 2) void segsum_chain_kerne
         const double dd = dist[r];   // (-1: to be computed here)
         dist_s[tid] = dd;
         xx_s[tid] = xx[r];
+        if constexpr (WGT) sw_s[tid] = wa.sw[r];
         // the sample kernel of BaseSom._calculate_exp_similarity (BaseSom.py:533-538), the arithmetic of
         // exp_similarity_kernel (bmu.hip) and of segsum_kernel
         kw_s[tid] = 1.0 - sqrt(1.0 - exp(-gamma * (dd * dd)));
@@ -480,7 +527,7 @@ __global__ __launch_bounds__(AT, G == 1 ? CHAIN_OCC : 2) void segsum_chain_kerne
     for (int g = 0; g < G; ++g)
 #pragma unroll
         for (int e = 0; e < VEC; ++e) acc[g][e] = 0.0;
-    double *out = slab + (size_t)c * (d + 2);
+    double *out = slab + (size_t)c * (d + NS);
     int my_range[G], my_off[G];   // where this thread's column groups go in the range buffers
 #pragma unroll
     for (int g = 0; g < G; ++g) {
@@ -600,7 +647,12 @@ __global__ __launch_bounds__(AT, G == 1 ? CHAIN_OCC : 2) void segsum_chain_kerne
 #pragma unroll
             for (int i = 0; i < SR; ++i) {
                 if ((mine >> i) & 1u) {
-                    const double w = kw_s[s0 + i];
+                    double w = kw_s[s0 + i];
+                    if constexpr (WGT) {
+                        // (weight 0: in no sum, as in segsum_kernel; its row was loaded in case its distance was open)
+                        if (sw_s[s0 + i] == 0.0) continue;
+                        w = __dmul_rn(sw_s[s0 + i], w);
+                    }
 #pragma unroll
                     for (int g = 0; g < G; ++g) {
                         double v[VEC];
@@ -619,7 +671,15 @@ __global__ __launch_bounds__(AT, G == 1 ? CHAIN_OCC : 2) void segsum_chain_kerne
     __syncthreads();
     if (tid == AT - 1) {  // the scalar partials, in list order
         double sk = 0.0, se = 0.0;
-        for (int p = 0; p < n; ++p) { sk += kw_s[p]; se += dist_s[p]; }
+        if constexpr (WGT) {
+            double sa = 0.0;
+            for (int p = 0; p < n; ++p) {
+                sk += __dmul_rn(sw_s[p], kw_s[p]); se += __dmul_rn(sw_s[p], dist_s[p]); sa += sw_s[p];
+            }
+            out[d + 2] = sa;
+        } else {
+            for (int p = 0; p < n; ++p) { sk += kw_s[p]; se += dist_s[p]; }
+        }
         out[d] = sk;
         out[d + 1] = se;
     }
@@ -647,8 +707,9 @@ __global__ __launch_bounds__(AT, G == 1 ? CHAIN_OCC : 2) void segsum_chain_kerne
         }
     }
 }
-
 // ---- 6. add each neuron's chunk partials in chunk order --------------------------------------
+// (WGT: a_j is the ordered sum of the chunks' third scalar partial instead of the integer count)
+template <bool WGT>
 __global__ __launch_bounds__(AT) void finalize_kernel(const double *__restrict__ slab, int d,
                                                       int M, const uint32_t *__restrict__ count,
                                                       const uint32_t *__restrict__ chunk_pre,
@@ -656,6 +717,7 @@ __global__ __launch_bounds__(AT) void finalize_kernel(const double *__restrict__
                                                       double *__restrict__ sums,
                                                       const int32_t *__restrict__ status,
                                                       double *__restrict__ status_f64) {
+    constexpr int NS = WGT ? 3 : 2;
     const int j = blockIdx.x, g = blockIdx.y;
     if (status_f64 && j == 0 && g == 0 && blockIdx.z == 0 && threadIdx.x == 0)
         status_f64[0] = status[0] ? 1.0 : 0.0;   // the flag rides behind the sums in the all-reduce buffer
@@ -666,38 +728,44 @@ __global__ __launch_bounds__(AT) void finalize_kernel(const double *__restrict__
     double *Kp = sums + (size_t)M * d, *ap = Kp + M, *Ep = ap + M;
     // (the column blocks of a neuron are separate workgroups, gridDim.z of them: one short chain
     // per thread instead of four one after the other)
-    for (int col = threadIdx.x + AT * blockIdx.z; col < d + 2; col += AT * gridDim.z) {
+    for (int col = threadIdx.x + AT * blockIdx.z; col < d + NS; col += AT * gridDim.z) {
         double s = 0.0;
         uint32_t c = c0;
         for (; c + 8 <= c1; c += 8) {  // loads batched, additions still in chunk order
             double v[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = slab[(size_t)(c + u) * (d + 2) + col];
+            for (int u = 0; u < 8; ++u) v[u] = slab[(size_t)(c + u) * (d + NS) + col];
 #pragma unroll
             for (int u = 0; u < 8; ++u) s += v[u];
         }
-        for (; c < c1; ++c) s += slab[(size_t)c * (d + 2) + col];
-        if (NG > 1) gslab[((size_t)j * NG + g) * (d + 2) + col] = s;
+        for (; c < c1; ++c) s += slab[(size_t)c * (d + NS) + col];
+        if (NG > 1) gslab[((size_t)j * NG + g) * (d + NS) + col] = s;
         else if (col < d) S[col] = s;
         else if (col == d) Kp[j] = s;
-        else Ep[j] = s;
+        else if (!WGT || col == d + 1) Ep[j] = s;
+        else ap[j] = s;
     }
-    if (threadIdx.x == 0 && g == 0 && blockIdx.z == 0) ap[j] = (double)count[j];
+    if constexpr (!WGT) {
+        if (threadIdx.x == 0 && g == 0 && blockIdx.z == 0) ap[j] = (double)count[j];
+    }
 }
 
 // second level (NG > 1): the NG group sums of a neuron in group order
+template <bool WGT>
 __global__ __launch_bounds__(AT) void finalize_groups_kernel(const double *__restrict__ gslab, int d,
                                                              int M, int NG,
                                                              double *__restrict__ sums) {
+    constexpr int NS = WGT ? 3 : 2;
     const int j = blockIdx.x;
     double *S = sums + (size_t)j * d;
     double *Kp = sums + (size_t)M * d, *Ep = Kp + 2 * (size_t)M;
-    for (int col = threadIdx.x; col < d + 2; col += AT) {
+    for (int col = threadIdx.x; col < d + NS; col += AT) {
         double s = 0.0;
-        for (int g = 0; g < NG; ++g) s += gslab[((size_t)j * NG + g) * (d + 2) + col];
+        for (int g = 0; g < NG; ++g) s += gslab[((size_t)j * NG + g) * (d + NS) + col];
         if (col < d) S[col] = s;
         else if (col == d) Kp[j] = s;
-        else Ep[j] = s;
+        else if (!WGT || col == d + 1) Ep[j] = s;
+        else Kp[(size_t)M + j] = s;
     }
 }
 
@@ -763,10 +831,27 @@ bool accumulate_can_fill_distances(int x_dtype, int64_t d) {
     return chain_lds(d).total <= 96 * 1024 && (size_t)AT * vec * 8 <= (size_t)2 * SR * SRP;   // (`red` reuses the range buffers)
 }
 
+// one instantiation of segsum_chain_kernel: its dynamic LDS is above the default limit (asked for once), the
+// weighted form keeps the rows' weights in CH doubles behind ChainLds::total
+template <typename XT, int V, int G, bool WGT>
+static int launch_chain(dim3 grid, const XT *X, int d, int64_t ldx, const AccWs &w, double gamma, double *dist, int M,
+                        const DistFill &fill, const ChainLds &L, WeightArg<WGT> wa, hipStream_t s) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        DBGSOM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&segsum_chain_kernel<XT, V, G, WGT>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+        attr_set = true;
+    }
+    const size_t lds = (size_t)L.total + (WGT ? CH * 8 : 0);
+    hipLaunchKernelGGL((segsum_chain_kernel<XT, V, G, WGT>), grid, dim3(AT), lds, s, X, d, ldx, w.order, gamma, dist,
+                       w.seg_start, w.count, w.chunk_pre, M, w.slab, fill.W, fill.ww, fill.xx, fill.round_f32, L, wa);
+    return DBGSOM_OK;
+}
+
 static int accumulate_impl(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx,
                            const int64_t *idx, const double *kw, double gamma, const double *dist, int64_t M,
                            double *sums, int32_t *status, bool status_behind_sums, void *ws,
-                           size_t ws_bytes, hipStream_t s, const DistFill *fill = nullptr) {
+                           size_t ws_bytes, hipStream_t s, const DistFill *fill = nullptr, const double *sw = nullptr) {
     DBGSOM_REQUIRE(valid_dtype(x_dtype), "x_dtype must be DBGSOM_F32/F64/BF16");
     DBGSOM_REQUIRE(N >= 0 && N < 0x7fffffff && d >= 1 && d <= 0x7ffffff0 && ldx >= d, "bad sample shape");
     DBGSOM_REQUIRE(M >= 1 && M <= DBGSOM_MAX_PROTOTYPES, "M outside [1, DBGSOM_MAX_PROTOTYPES]");
@@ -779,13 +864,13 @@ static int accumulate_impl(const void *X, int x_dtype, int64_t N, int64_t d, int
     }
     DBGSOM_REQUIRE(X && idx && dist && ws, "null pointer");
     DBGSOM_REQUIRE(is_aligned(ws, 256), "workspace must be 256-byte aligned");
-    if (ws_bytes < accumulate_workspace_bytes(N, d, M)) {
-        set_error("dbgsom_accumulate: workspace too small (%zu < %zu)", ws_bytes,
-                  accumulate_workspace_bytes(N, d, M));
+    const size_t need = sw ? accumulate_weighted_workspace_bytes(N, d, M) : accumulate_workspace_bytes(N, d, M);
+    if (ws_bytes < need) {
+        set_error("dbgsom_accumulate: workspace too small (%zu < %zu)", ws_bytes, need);
         return DBGSOM_ENOMEM;
     }
     AccWs w;
-    carve(&w, (char *)ws, N, d, M);
+    carve(&w, (char *)ws, N, d, M, sw ? 3 : 2);
     const int Mi = (int)M, di = (int)d;
 
     hipLaunchKernelGGL(hist_kernel, dim3((unsigned)w.nb), dim3(AT), (size_t)M * 4, s, idx, N, Mi,
@@ -799,29 +884,34 @@ static int accumulate_impl(const void *X, int x_dtype, int64_t N, int64_t d, int
     const bool al16 = is_aligned(X, 16) && ((ldx * xe) % 16 == 0);
     dim3 grid((unsigned)w.maxchunks), block(AT);
 #define DBGSOM_SEGSUM(XT, V)                                                                    \
-    hipLaunchKernelGGL((segsum_kernel<XT, V>), grid, block, 0, s, (const XT *)X, di, ldx, w.order, \
-                       kw, gamma, dist, w.seg_start, w.count, w.chunk_pre, Mi, w.slab)
+    do {                                                                                        \
+        if (sw)                                                                                 \
+            hipLaunchKernelGGL((segsum_kernel<XT, V, true>), grid, block, 0, s, (const XT *)X, di, ldx, w.order, \
+                               kw, gamma, dist, w.seg_start, w.count, w.chunk_pre, Mi, w.slab,   \
+                               WeightArg<true>{sw});                                    \
+        else                                                                                    \
+            hipLaunchKernelGGL((segsum_kernel<XT, V, false>), grid, block, 0, s, (const XT *)X, di, ldx, w.order, \
+                               kw, gamma, dist, w.seg_start, w.count, w.chunk_pre, Mi, w.slab,   \
+                               WeightArg<false>{});                                              \
+    } while (0)
     if (fill) {
         // rows with dist == -1 get their distance (to their winner: this chunk's prototype) on the way
         DBGSOM_REQUIRE(!kw && al16 && accumulate_can_fill_distances(x_dtype, d) && fill->W && fill->ww && fill->xx,
                        "distances cannot be filled in for this shape");
         const ChainLds L = chain_lds(d);
         const bool two = d / (x_dtype == DBGSOM_F32 ? 4 : (x_dtype == DBGSOM_F64 ? 2 : 8)) > AT;
-#define DBGSOM_SEGDIST(XT, V, G_)                                                                         \
-    do {                                                                                                  \
-        static int attr_set = 0;                                                                          \
-        if (attr_set < L.total) {                                                                         \
-            DBGSOM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&segsum_chain_kernel<XT, V, G_>), \
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));   \
-            attr_set = 96 * 1024;                                                                         \
-        }                                                                                                 \
-        hipLaunchKernelGGL((segsum_chain_kernel<XT, V, G_>), grid, block, (size_t)L.total, s, (const XT *)X, di, ldx, \
-                           w.order, gamma, const_cast<double *>(dist), w.seg_start, w.count, w.chunk_pre, Mi, \
-                           w.slab, fill->W, fill->ww, fill->xx, fill->round_f32, L);                      \
+#define DBGSOM_SEGDIST(XT, V, G_)                                                                        \
+    do {                                                                                                 \
+        if (sw) TRY_LAUNCH((launch_chain<XT, V, G_, true>(grid, (const XT *)X, di, ldx, w, gamma, const_cast<double *>(dist), \
+                                                          Mi, *fill, L, WeightArg<true>{sw}, s)));      \
+        else TRY_LAUNCH((launch_chain<XT, V, G_, false>(grid, (const XT *)X, di, ldx, w, gamma, const_cast<double *>(dist), \
+                                                        Mi, *fill, L, WeightArg<false>{}, s)));         \
     } while (0)
+#define TRY_LAUNCH(expr) do { const int rc_ = (expr); if (rc_ != DBGSOM_OK) return rc_; } while (0)
         if (x_dtype == DBGSOM_F32) { if (two) DBGSOM_SEGDIST(float, 4, 2); else DBGSOM_SEGDIST(float, 4, 1); }
         else if (x_dtype == DBGSOM_F64) { if (two) DBGSOM_SEGDIST(double, 2, 2); else DBGSOM_SEGDIST(double, 2, 1); }
         else { if (two) DBGSOM_SEGDIST(bf16_t, 8, 2); else DBGSOM_SEGDIST(bf16_t, 8, 1); }
+#undef TRY_LAUNCH
 #undef DBGSOM_SEGDIST
     } else if (x_dtype == DBGSOM_F32) {
         if (al16 && d % 4 == 0) DBGSOM_SEGSUM(float, 4); else DBGSOM_SEGSUM(float, 1);
@@ -832,12 +922,22 @@ static int accumulate_impl(const void *X, int x_dtype, int64_t N, int64_t d, int
     }
 #undef DBGSOM_SEGSUM
     const int NG = finalize_groups(M);
+    if (sw) {
+        const unsigned col_blocks = (unsigned)((d + 3 + AT - 1) / AT < 8 ? (d + 3 + AT - 1) / AT : 8);
+        hipLaunchKernelGGL(finalize_kernel<true>, dim3((unsigned)M, (unsigned)NG, col_blocks), dim3(AT), 0, s, w.slab, di, Mi,
+                           w.count, w.chunk_pre, NG, w.gslab, sums, (const int32_t *)status,
+                           status_behind_sums ? sums + (size_t)M * (d + 3) : (double *)nullptr);
+        if (NG > 1)
+            hipLaunchKernelGGL(finalize_groups_kernel<true>, dim3((unsigned)M), dim3(AT), 0, s, w.gslab, di, Mi, NG,
+                               sums);
+        return launch_status("weighted accumulate kernels");
+    }
     const unsigned col_blocks = (unsigned)((d + 2 + AT - 1) / AT < 8 ? (d + 2 + AT - 1) / AT : 8);
-    hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)M, (unsigned)NG, col_blocks), dim3(AT), 0, s, w.slab, di, Mi,
+    hipLaunchKernelGGL(finalize_kernel<false>, dim3((unsigned)M, (unsigned)NG, col_blocks), dim3(AT), 0, s, w.slab, di, Mi,
                        w.count, w.chunk_pre, NG, w.gslab, sums, (const int32_t *)status,
                        status_behind_sums ? sums + (size_t)M * (d + 3) : (double *)nullptr);
     if (NG > 1)
-        hipLaunchKernelGGL(finalize_groups_kernel, dim3((unsigned)M), dim3(AT), 0, s, w.gslab, di, Mi, NG,
+        hipLaunchKernelGGL(finalize_groups_kernel<false>, dim3((unsigned)M), dim3(AT), 0, s, w.gslab, di, Mi, NG,
                            sums);
     return launch_status("accumulate kernels");
 }
@@ -854,6 +954,23 @@ int launch_accumulate_epoch(const void *X, int x_dtype, int64_t N, int64_t d, in
                             double *sums, int32_t *status, void *ws, size_t ws_bytes, hipStream_t s,
                             const DistFill *fill) {
     return accumulate_impl(X, x_dtype, N, d, ldx, idx, nullptr, gamma, dist, M, sums, status, true, ws, ws_bytes, s, fill);
+}
+
+// the weighted forms: `sw` = one weight per row (finite, >= 0: the caller has checked); workspace of
+// accumulate_weighted_workspace_bytes
+int launch_accumulate_weighted(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx,
+                               const int64_t *idx, const double *kw, const double *sw, const double *dist, int64_t M,
+                               double *sums, int32_t *status, void *ws, size_t ws_bytes, hipStream_t s) {
+    DBGSOM_REQUIRE(N == 0 || (kw && sw), "null sample weights");
+    return accumulate_impl(X, x_dtype, N, d, ldx, idx, kw, 0.0, dist, M, sums, status, false, ws, ws_bytes, s, nullptr, sw);
+}
+
+int launch_accumulate_epoch_weighted(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx,
+                                     const int64_t *idx, double gamma, const double *sw, const double *dist, int64_t M,
+                                     double *sums, int32_t *status, void *ws, size_t ws_bytes, hipStream_t s,
+                                     const DistFill *fill) {
+    DBGSOM_REQUIRE(N == 0 || sw, "null sample weights");
+    return accumulate_impl(X, x_dtype, N, d, ldx, idx, nullptr, gamma, dist, M, sums, status, true, ws, ws_bytes, s, fill, sw);
 }
 
 }  // namespace dbgsom

@@ -61,6 +61,17 @@ int dbgsom_accumulate(const void *X, int x_dtype, int64_t N, int64_t d, int64_t 
                              (hipStream_t)stream);
 }
 
+size_t dbgsom_accumulate_weighted_workspace_bytes(int64_t N, int64_t d, int64_t M) {
+    return accumulate_weighted_workspace_bytes(N, d, M);
+}
+
+int dbgsom_accumulate_weighted(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx,
+                               const int64_t *idx, const double *kw, const double *sw, const double *dist, int64_t M,
+                               double *sums, int32_t *status, void *ws, size_t ws_bytes, void *stream) {
+    return launch_accumulate_weighted(X, x_dtype, N, d, ldx, idx, kw, sw, dist, M, sums, status, ws, ws_bytes,
+                                      (hipStream_t)stream);
+}
+
 size_t dbgsom_smooth_workspace_bytes(int64_t M, int64_t d) { return smooth_workspace_bytes(M, d); }
 
 int dbgsom_smooth(const double *sums, int64_t M, int64_t d, const float *hop, double sigma,

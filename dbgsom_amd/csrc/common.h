@@ -114,6 +114,16 @@ int launch_accumulate_epoch(const void *X, int x_dtype, int64_t N, int64_t d, in
                             const int64_t *idx, double gamma, const double *dist, int64_t M,
                             double *sums, int32_t *status, void *ws, size_t ws_bytes, hipStream_t s,
                             const DistFill *fill = nullptr);
+// weighted forms (`sw`: one finite weight >= 0 per row; a row of weight w counts as w copies): factor
+// sw kw on S and K, sw dist on E, a = sum sw as an ordered float64 sum; rows of weight 0 are not streamed
+size_t accumulate_weighted_workspace_bytes(int64_t N, int64_t d, int64_t M);
+int launch_accumulate_weighted(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx,
+                               const int64_t *idx, const double *kw, const double *sw, const double *dist, int64_t M,
+                               double *sums, int32_t *status, void *ws, size_t ws_bytes, hipStream_t s);
+int launch_accumulate_epoch_weighted(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx,
+                                     const int64_t *idx, double gamma, const double *sw, const double *dist, int64_t M,
+                                     double *sums, int32_t *status, void *ws, size_t ws_bytes, hipStream_t s,
+                                     const DistFill *fill = nullptr);
 size_t bucket_sort_workspace_bytes(int64_t N, int64_t M);
 int launch_bucket_sort(const int64_t *idx, int64_t N, int64_t M, int32_t *order, void *ws,
                        hipStream_t s);

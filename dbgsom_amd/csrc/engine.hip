@@ -162,6 +162,11 @@ __global__ void gather_rows_kernel(const T *__restrict__ src, int64_t ld, const 
     T *d = dst + r * cols;
     for (int64_t c = threadIdx.x; c < cols; c += blockDim.x) d[c] = s[c];
 }
+__global__ void gather_f64_kernel(const double *__restrict__ src, const int32_t *__restrict__ ids, int64_t first,
+                                  int64_t n, double *__restrict__ dst) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        dst[i] = src[ids[first + i]];
+}
 __global__ void gather_i32_kernel(const int32_t *__restrict__ src, const int32_t *__restrict__ ids, int64_t first,
                                   int64_t n, int32_t *__restrict__ dst) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
@@ -268,6 +273,10 @@ struct dbgsom_ctx {
     Samples xs, xq;
     DevBuf y;
     bool has_labels = false;
+    // one float64 weight per resident row (dbgsom_ctx_set_sample_weight): the epoch, dbgsom_ctx_update and the
+    // reductions then run their weighted forms
+    DevBuf sw, wh_order, wh_ws;
+    bool has_weights = false;
     // topology
     int64_t topoM = 0;
     DevBuf hop, hop_stage;
@@ -963,6 +972,12 @@ int epoch_bmu(dbgsom_ctx *c, int64_t M, int round_f32) {
     return DBGSOM_OK;
 }
 
+// workspace of the accumulate step: the weighted form's rows are one scalar wider
+size_t acc_ws_bytes(dbgsom_ctx *c, int64_t M) {
+    return c->has_weights ? accumulate_weighted_workspace_bytes(c->xs.N, c->xs.dp, M)
+                          : accumulate_workspace_bytes(c->xs.N, c->xs.dp, M);
+}
+
 // sums = [S | K | a | E | status] of the resident samples for winners idx / distances dist and the
 // sample weights kw (kw == nullptr: the sample kernel with `gamma`, computed inside the sums kernel)
 int accumulate_and_reduce(dbgsom_ctx *c, const int64_t *idx, const double *kw, double gamma, const double *dist,
@@ -971,21 +986,31 @@ int accumulate_and_reduce(dbgsom_ctx *c, const int64_t *idx, const double *kw, d
     DBGSOM_REQUIRE(M <= DBGSOM_MAX_PROTOTYPES, "M exceeds DBGSOM_MAX_PROTOTYPES");
     const int64_t count = M * (s.dp + 3);
     TRY(c->sums.reserve((size_t)(count + 1) * 8));
-    TRY(c->acc_ws.reserve(accumulate_workspace_bytes(s.N, s.dp, M)));
+    TRY(c->acc_ws.reserve(acc_ws_bytes(c, M)));
     TRY(c->scal.reserve(256));
     int32_t *status = reinterpret_cast<int32_t *>(c->scal.as<char>() + 64);
     c->part_valid = false;
+    const double *sw = c->has_weights ? c->sw.as<double>() : nullptr;
     if (kw) {
-        TRY(launch_accumulate(s.X, s.dtype, s.N, s.dp, s.dp, idx, kw, dist, M, c->sums.as<double>(), status,
-                              c->acc_ws.p, c->acc_ws.cap, c->stream));
+        if (sw)
+            TRY(launch_accumulate_weighted(s.X, s.dtype, s.N, s.dp, s.dp, idx, kw, sw, dist, M, c->sums.as<double>(), status,
+                                           c->acc_ws.p, c->acc_ws.cap, c->stream));
+        else
+            TRY(launch_accumulate(s.X, s.dtype, s.N, s.dp, s.dp, idx, kw, dist, M, c->sums.as<double>(), status,
+                                  c->acc_ws.p, c->acc_ws.cap, c->stream));
         hipLaunchKernelGGL(status_to_f64_kernel, dim3(1), dim3(1), 0, c->stream, status, c->sums.as<double>() + count);
         TRY(launch_status("status_to_f64_kernel"));
     } else {
         DistFill fill;
         fill.W = c->Wb[c->cur].as<double>(); fill.ww = c->ww.as<double>(); fill.xx = s.xx.as<double>();
         fill.round_f32 = c->last_round_f32;
-        TRY(launch_accumulate_epoch(s.X, s.dtype, s.N, s.dp, s.dp, idx, gamma, dist, M, c->sums.as<double>(), status,
-                                    c->acc_ws.p, c->acc_ws.cap, c->stream, c->last_deferred ? &fill : nullptr));
+        if (sw)
+            TRY(launch_accumulate_epoch_weighted(s.X, s.dtype, s.N, s.dp, s.dp, idx, gamma, sw, dist, M, c->sums.as<double>(),
+                                                 status, c->acc_ws.p, c->acc_ws.cap, c->stream,
+                                                 c->last_deferred ? &fill : nullptr));
+        else
+            TRY(launch_accumulate_epoch(s.X, s.dtype, s.N, s.dp, s.dp, idx, gamma, dist, M, c->sums.as<double>(), status,
+                                        c->acc_ws.p, c->acc_ws.cap, c->stream, c->last_deferred ? &fill : nullptr));
         if (c->last_deferred) ++c->defer_epochs;
         c->last_deferred = false;
     }
@@ -1168,7 +1193,7 @@ int dbgsom_ctx_create(int device, dbgsom_ctx **out) {
     {&(c)->y, &(c)->hop, &(c)->hop_stage, &(c)->Wb[0], &(c)->Wb[1], &(c)->ww, &(c)->idx[0], &(c)->idx[1], &(c)->dist,  \
      &(c)->kw, &(c)->sums, &(c)->acc_ws, &(c)->sm_ws, &(c)->filt_ws, &(c)->scal, &(c)->qidx, &(c)->qdist, &(c)->red,  \
      &(c)->hist, &(c)->stage_dev, &(c)->part_order, &(c)->part_ws, &(c)->part_counts, &(c)->shiftb, &(c)->shard_send,    \
-     &(c)->shard_gather, &(c)->sc_ws, &(c)->sc_x, &(c)->sc_w, &(c)->sc_p, &(c)->sc_code, &(c)->sc_proba, &(c)->sc_cnt}
+     &(c)->shard_gather, &(c)->sw, &(c)->wh_order, &(c)->wh_ws, &(c)->sc_ws, &(c)->sc_x, &(c)->sc_w, &(c)->sc_p, &(c)->sc_code, &(c)->sc_proba, &(c)->sc_cnt}
 
 int dbgsom_ctx_destroy(dbgsom_ctx *c) {
     if (!c) return DBGSOM_OK;
@@ -1300,6 +1325,7 @@ int dbgsom_ctx_stream(dbgsom_ctx *c, void **stream) {
 static void reset_training_state(dbgsom_ctx *c) {
     c->hint_valid = c->last_idx_valid = c->part_valid = false;
     c->has_labels = false;
+    c->has_weights = false;
     c->filter_backoff = c->filter_fail = 0;
     c->planes_next = 1;
     c->planeM = -1;
@@ -1382,6 +1408,36 @@ int dbgsom_ctx_set_labels(dbgsom_ctx *c, const int32_t *y_host, int64_t N) {
     TRY(c->y.reserve((size_t)N * 4));
     DBGSOM_HIP_CHECK(hipMemcpyAsync(c->y.p, y_host, (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
     c->has_labels = true;
+    return sync(c);
+}
+
+int dbgsom_ctx_set_sample_weight(dbgsom_ctx *c, const double *w_host, int64_t N) {
+    CTX_CHECK(c);
+    TRY(loaded(c, __func__));
+    // (the bucket order of the last accumulate step keeps its meaning either way: a permutation of all rows)
+    if (!w_host) { c->has_weights = false; return DBGSOM_OK; }
+    DBGSOM_REQUIRE(N == c->xs.N, "one weight per resident sample");
+    for (int64_t i = 0; i < N; ++i)
+        if (!(w_host[i] >= 0.0) || w_host[i] == INFINITY) {
+            set_error("dbgsom_ctx_set_sample_weight: weight %lld is negative or not finite", (long long)i);
+            return DBGSOM_EINVAL;
+        }
+    TRY(c->sw.reserve((size_t)N * 8));
+    DBGSOM_HIP_CHECK(hipMemcpyAsync(c->sw.p, w_host, (size_t)N * 8, hipMemcpyHostToDevice, c->stream));
+    c->has_weights = true;
+    c->sumsM = 0;
+    return sync(c);
+}
+
+int dbgsom_ctx_weight_total(dbgsom_ctx *c, double *out_host) {
+    CTX_CHECK(c);
+    TRY(loaded(c, __func__));
+    DBGSOM_REQUIRE(out_host, "null pointer");
+    if (!c->has_weights) { *out_host = (double)c->xs.N; return DBGSOM_OK; }
+    TRY(c->red.reserve(256 + dbgsom_sum_workspace_bytes()));
+    double *r = c->red.as<double>();
+    TRY(dbgsom_weighted_sum_f64(nullptr, c->sw.as<double>(), c->xs.N, r, c->red.as<char>() + 256, c->red.cap - 256, c->stream));
+    DBGSOM_HIP_CHECK(hipMemcpyAsync(out_host, r, 8, hipMemcpyDeviceToHost, c->stream));
     return sync(c);
 }
 
@@ -1840,7 +1896,7 @@ int dbgsom_ctx_set_hint(dbgsom_ctx *c, const int64_t *idx_host, int64_t M) {
     TRY(c->idx[0].reserve((size_t)s.N * 8));
     TRY(c->idx[1].reserve((size_t)s.N * 8));
     // the bucket order lives where the accumulate step leaves it: the first N int32 of its workspace
-    TRY(c->acc_ws.reserve(accumulate_workspace_bytes(s.N, s.dp, M)));
+    TRY(c->acc_ws.reserve(acc_ws_bytes(c, M)));
     TRY(c->part_ws.reserve(bucket_sort_workspace_bytes(s.N, M)));
     int64_t *idx = c->idx[c->icur].as<int64_t>();
     DBGSOM_HIP_CHECK(hipMemcpyAsync(idx, idx_host, (size_t)s.N * 8, hipMemcpyHostToDevice, c->stream));
@@ -1887,6 +1943,27 @@ int dbgsom_ctx_column_sums(dbgsom_ctx *c, const void *mean_host, void *out_host)
     return sync(c);
 }
 
+int dbgsom_ctx_weighted_column_sums(dbgsom_ctx *c, const double *mean_host, double *out_host) {
+    CTX_CHECK(c);
+    TRY(loaded(c, __func__));
+    DBGSOM_REQUIRE(out_host, "null pointer");
+    if (!c->has_weights) { set_error("weighted column sums requested but no weights attached (dbgsom_ctx_set_sample_weight)"); return DBGSOM_ESTATE; }
+    Samples &s = c->xs;
+    const size_t vec = align_up((size_t)s.dp * 8);
+    TRY(c->stage_dev.reserve(2 * vec + dbgsom_weighted_column_sums_workspace_bytes(s.dp)));
+    double *mean_dev = c->stage_dev.as<double>();
+    double *out_dev = reinterpret_cast<double *>(c->stage_dev.as<char>() + vec);
+    void *ws = c->stage_dev.as<char>() + 2 * vec;
+    if (mean_host) {
+        DBGSOM_HIP_CHECK(hipMemsetAsync(mean_dev, 0, (size_t)s.dp * 8, c->stream));
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(mean_dev, mean_host, (size_t)s.d * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    TRY(dbgsom_weighted_column_sums(s.X, s.dtype, s.N, s.dp, s.dp, c->sw.as<double>(), mean_host ? mean_dev : nullptr, out_dev,
+                                    ws, c->stage_dev.cap - 2 * vec, c->stream));
+    DBGSOM_HIP_CHECK(hipMemcpyAsync(out_host, out_dev, (size_t)s.d * 8, hipMemcpyDeviceToHost, c->stream));
+    return sync(c);
+}
+
 static int reduce_small(dbgsom_ctx *c, double *buf_dev, int64_t n, double *out_host) {
     TRY(run_allreduce(c, buf_dev, n));
     DBGSOM_HIP_CHECK(hipMemcpyAsync(out_host, buf_dev, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1900,6 +1977,13 @@ int dbgsom_ctx_quantization_error(dbgsom_ctx *c, const double *W_host, int64_t M
     TRY(resident_bmu(c, W_host, M, 1, round_f32));
     TRY(c->red.reserve(256 + dbgsom_sum_workspace_bytes()));
     double *r = c->red.as<double>();
+    if (c->has_weights) {   // [sum w dist, sum w]
+        TRY(dbgsom_weighted_sum_f64(c->qdist.as<double>(), c->sw.as<double>(), c->xs.N, r, c->red.as<char>() + 256,
+                                    c->red.cap - 256, c->stream));
+        TRY(dbgsom_weighted_sum_f64(nullptr, c->sw.as<double>(), c->xs.N, r + 1, c->red.as<char>() + 256, c->red.cap - 256,
+                                    c->stream));
+        return reduce_small(c, r, 2, out2);
+    }
     TRY(dbgsom_sum_f64(c->qdist.as<double>(), c->xs.N, r, c->red.as<char>() + 256, c->red.cap - 256, c->stream));
     const double n = (double)c->xs.N;
     DBGSOM_HIP_CHECK(hipMemcpyAsync(r + 1, &n, 8, hipMemcpyHostToDevice, c->stream));
@@ -1912,9 +1996,14 @@ int dbgsom_ctx_topographic_count(dbgsom_ctx *c, const double *W_host, int64_t M,
     TRY(loaded(c, __func__));
     DBGSOM_REQUIRE(xy_host && count_host && M >= 2, "bad arguments");
     TRY(resident_bmu(c, W_host, M, 2, round_f32));
-    TRY(c->red.reserve(256 + (size_t)M * 8));
+    TRY(c->red.reserve(256 + align_up((size_t)M * 8) + dbgsom_sum_workspace_bytes()));
     int32_t *xy = reinterpret_cast<int32_t *>(c->red.as<char>() + 256);
     DBGSOM_HIP_CHECK(hipMemcpyAsync(xy, xy_host, (size_t)M * 8, hipMemcpyHostToDevice, c->stream));
+    if (c->has_weights) {   // the summed weight of such rows
+        TRY(dbgsom_topographic_weight(c->qidx.as<int64_t>(), c->sw.as<double>(), c->xs.N, xy, M, c->red.as<double>(),
+                                      c->red.as<char>() + 256 + align_up((size_t)M * 8), dbgsom_sum_workspace_bytes(), c->stream));
+        return reduce_small(c, c->red.as<double>(), 1, count_host);
+    }
     uint64_t *cnt = reinterpret_cast<uint64_t *>(c->red.as<char>() + 64);
     TRY(dbgsom_topographic_count(c->qidx.as<int64_t>(), c->xs.N, xy, M, cnt, c->stream));
     double *r = c->red.as<double>();
@@ -1937,11 +2026,16 @@ int dbgsom_ctx_node_statistics(dbgsom_ctx *c, const double *W_host, int64_t M, i
     DBGSOM_REQUIRE(M <= DBGSOM_MAX_PROTOTYPES, "M exceeds DBGSOM_MAX_PROTOTYPES");
     const int64_t count = M * (s.dp + 3);
     TRY(c->sums.reserve((size_t)(count + 1) * 8));
-    TRY(c->acc_ws.reserve(accumulate_workspace_bytes(s.N, s.dp, M)));
+    TRY(c->acc_ws.reserve(acc_ws_bytes(c, M)));
     c->part_valid = false;
     c->sumsM = 0;
-    TRY(launch_accumulate(s.X, s.dtype, s.N, s.dp, s.dp, c->qidx.as<int64_t>(), c->kw.as<double>(), c->qdist.as<double>(), M,
-                          c->sums.as<double>(), nullptr, c->acc_ws.p, c->acc_ws.cap, c->stream));
+    if (c->has_weights)   // K = sum w term, a = sum w
+        TRY(launch_accumulate_weighted(s.X, s.dtype, s.N, s.dp, s.dp, c->qidx.as<int64_t>(), c->kw.as<double>(),
+                                       c->sw.as<double>(), c->qdist.as<double>(), M, c->sums.as<double>(), nullptr, c->acc_ws.p,
+                                       c->acc_ws.cap, c->stream));
+    else
+        TRY(launch_accumulate(s.X, s.dtype, s.N, s.dp, s.dp, c->qidx.as<int64_t>(), c->kw.as<double>(), c->qdist.as<double>(), M,
+                              c->sums.as<double>(), nullptr, c->acc_ws.p, c->acc_ws.cap, c->stream));
     double *tail = c->sums.as<double>() + M * s.dp;  // [K | a]
     TRY(run_allreduce(c, tail, 2 * M));
     DBGSOM_HIP_CHECK(hipMemcpyAsync(density_host, tail, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1978,6 +2072,37 @@ int dbgsom_ctx_class_histogram(dbgsom_ctx *c, const int64_t *idx_host, int64_t n
     TRY(sync(c));
     for (int64_t e = 0; e < n; ++e) hist_host[e] = (int64_t)llround(tmp[(size_t)e]);
     return DBGSOM_OK;
+}
+
+// the weighted class histogram: hist[j, c] = sum of the weights of the rows of class c that chose neuron j, added in
+// row order (a stable bucket sort of the winners, then one workgroup per neuron walks its list)
+int dbgsom_ctx_class_histogram_weighted(dbgsom_ctx *c, const int64_t *idx_host, int64_t n_classes, int64_t M, double *hist_host) {
+    CTX_CHECK(c);
+    TRY(loaded(c, __func__));
+    DBGSOM_REQUIRE(hist_host && n_classes >= 1 && M >= 1 && M <= DBGSOM_MAX_PROTOTYPES, "bad arguments");
+    if (!c->has_labels) { set_error("class histogram requested but no labels attached (dbgsom_ctx_set_labels)"); return DBGSOM_ESTATE; }
+    if (!c->has_weights) { set_error("weighted class histogram requested but no weights attached (dbgsom_ctx_set_sample_weight)"); return DBGSOM_ESTATE; }
+    Samples &s = c->xs;
+    const int64_t *idx = nullptr;
+    if (idx_host) {
+        TRY(c->qidx.reserve((size_t)s.N * 8));
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(c->qidx.p, idx_host, (size_t)s.N * 8, hipMemcpyHostToDevice, c->stream));
+        idx = c->qidx.as<int64_t>();
+    } else {
+        if (!c->last_idx_valid) { set_error("no winners of a previous epoch in HBM"); return DBGSOM_ESTATE; }
+        idx = c->idx[c->icur].as<int64_t>();
+    }
+    const int64_t n = M * n_classes;
+    TRY(c->hist.reserve((size_t)n * 8));
+    TRY(c->wh_order.reserve((size_t)s.N * 4));
+    TRY(c->wh_ws.reserve(bucket_sort_workspace_bytes(s.N, M)));
+    double *hd = c->hist.as<double>();
+    TRY(launch_bucket_sort(idx, s.N, M, c->wh_order.as<int32_t>(), c->wh_ws.p, c->stream));
+    TRY(dbgsom_class_histogram_weighted(c->wh_order.as<int32_t>(), bucket_sort_seg_start(c->wh_ws.p, s.N, M), c->y.as<int32_t>(),
+                                        c->sw.as<double>(), s.N, M, n_classes, hd, c->stream));
+    TRY(run_allreduce(c, hd, n));
+    DBGSOM_HIP_CHECK(hipMemcpyAsync(hist_host, hd, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    return sync(c);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2047,6 +2172,12 @@ int dbgsom_ctx_subset_create(dbgsom_ctx *c, int64_t neuron, dbgsom_ctx **child_o
             hipLaunchKernelGGL(gather_i32_kernel, dim3(grid1d(n)), dim3(256), 0, c->stream, c->y.as<int32_t>(), order, first, n, k->y.as<int32_t>());
             if ((rc = launch_status("gather_i32_kernel"))) break;
             k->has_labels = true;
+        }
+        if (c->has_weights) {
+            if ((rc = k->sw.reserve((size_t)n * 8))) break;
+            hipLaunchKernelGGL(gather_f64_kernel, dim3(grid1d(n)), dim3(256), 0, c->stream, c->sw.as<double>(), order, first, n, k->sw.as<double>());
+            if ((rc = launch_status("gather_f64_kernel"))) break;
+            k->has_weights = true;
         }
         if ((rc = sync(c))) break;
         if ((rc = finish_samples(k, t, false))) break;

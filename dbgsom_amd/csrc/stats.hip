@@ -173,6 +173,112 @@ __global__ __launch_bounds__(256) void column_sums_kernel(const T *__restrict__ 
     if (t < CS_CW && live) out[j] = acc;
 }
 
+// ---- weighted forms (a row of weight w counts as w copies of that row) ------------------------------------
+// Floating-point sums with a weight per row: no atomics, fixed grids, ordered partials -> bitwise
+// reproducible run to run, like the sums of accumulate.hip.
+
+// part[b] = sum over the rows of block b's fixed stride of w_i v_i (v == nullptr: of w_i)
+__global__ __launch_bounds__(256) void wsum_partial_kernel(const double *__restrict__ v, const double *__restrict__ w,
+                                                           int64_t n, double *__restrict__ part) {
+    __shared__ double red[256];
+    const int t = threadIdx.x;
+    double s = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + t; i < n; i += (int64_t)RB * 256) s += v ? w[i] * v[i] : w[i];
+    red[t] = s;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+        if (t < k) red[t] += red[t + k];
+        __syncthreads();
+    }
+    if (t == 0) part[blockIdx.x] = red[0];
+}
+
+// part[b] = summed weight of the rows whose two best matching units are further than 1.5 apart
+__global__ __launch_bounds__(256) void topographic_w_kernel(const int64_t *__restrict__ idx2, const double *__restrict__ w,
+                                                            int64_t n, const int32_t *__restrict__ xy, int M,
+                                                            double *__restrict__ part) {
+    __shared__ double red[256];
+    const int t = threadIdx.x;
+    double s = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + t; i < n; i += (int64_t)RB * 256) {
+        const int64_t a = idx2[2 * i], b = idx2[2 * i + 1];
+        if (a >= 0 && a < M && b >= 0 && b < M) {
+            const double dx = (double)(xy[2 * a] - xy[2 * b]);
+            const double dy = (double)(xy[2 * a + 1] - xy[2 * b + 1]);
+            if (sqrt(dx * dx + dy * dy) > 1.5) s += w[i];
+        }
+    }
+    red[t] = s;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+        if (t < k) red[t] += red[t + k];
+        __syncthreads();
+    }
+    if (t == 0) part[blockIdx.x] = red[0];
+}
+
+// hist[j, c] = sum of w_i over the rows of neuron j's list (bucket order: ascending row id) with y_i = c,
+// added in list order: one workgroup per neuron, one thread per class.
+__global__ __launch_bounds__(256) void class_hist_w_kernel(const int32_t *__restrict__ order,
+                                                           const uint32_t *__restrict__ seg_start, int64_t n,
+                                                           const int32_t *__restrict__ y, const double *__restrict__ w,
+                                                           int M, int C, double *__restrict__ hist) {
+    __shared__ int32_t y_s[256];
+    __shared__ double w_s[256];
+    const int j = blockIdx.x;
+    const uint32_t b0 = seg_start[j], b1 = min(seg_start[j + 1], (uint32_t)n);   // (seg_start holds M + 1 entries)
+    const int nc = (C + 255) / 256;   // classes per thread: c = threadIdx.x + 256 u
+    for (int u = 0; u < nc; ++u) {
+        const int c = threadIdx.x + 256 * u;
+        double s = 0.0;
+        for (uint32_t t0 = b0; t0 < b1; t0 += 256) {   // a tile of the list: loaded side by side, added in list order
+            const uint32_t p = t0 + threadIdx.x;
+            __syncthreads();
+            if (p < b1) {
+                const int32_t r = order[p];
+                y_s[threadIdx.x] = y[r]; w_s[threadIdx.x] = w[r];
+            }
+            __syncthreads();
+            const int rows = (int)min((uint32_t)256, b1 - t0);
+            for (int q = 0; q < rows; ++q) {
+                if (y_s[q] == c) s += w_s[q];
+            }
+        }
+        if (c < C) hist[(size_t)j * C + c] = s;
+    }
+}
+
+// Weighted column sums in float64 whatever the storage dtype: part[b, j] = sum over the rows b, b + WC_RB,
+// ... of w_i x_ij (mean == nullptr) or w_i (x_ij - mean_j)^2; out[j] = the WC_RB partials in order.
+constexpr int WC_COLS = 64, WC_RL = 4, WC_RB = 1024;
+template <typename T>
+__global__ __launch_bounds__(WC_COLS * WC_RL) void wcol_partial_kernel(const T *__restrict__ X, int64_t N, int d, int64_t ld,
+                                                                       const double *__restrict__ w,
+                                                                       const double *__restrict__ mean,
+                                                                       double *__restrict__ part) {
+    const int col = blockIdx.x * WC_COLS + (threadIdx.x % WC_COLS);
+    const int b = blockIdx.y * WC_RL + threadIdx.x / WC_COLS;   // 0 .. WC_RB - 1
+    if (col >= d) return;
+    const double m = mean ? mean[col] : 0.0;
+    double s = 0.0;
+    for (int64_t i = b; i < N; i += WC_RB) {
+        const double wi = w[i];
+        if (wi == 0.0) continue;
+        double x = widen(X[i * ld + col]);
+        if (mean) { x = x - m; x = __dmul_rn(x, x); }
+        s += __dmul_rn(wi, x);
+    }
+    part[(size_t)b * d + col] = s;
+}
+
+__global__ __launch_bounds__(256) void wcol_final_kernel(const double *__restrict__ part, int d, double *__restrict__ out) {
+    const int col = blockIdx.x * 256 + threadIdx.x;
+    if (col >= d) return;
+    double s = 0.0;
+    for (int b = 0; b < WC_RB; ++b) s += part[(size_t)b * d + col];
+    out[col] = s;
+}
+
 }  // namespace dbgsom
 
 using namespace dbgsom;
@@ -260,6 +366,76 @@ int dbgsom_column_sums(const void *X_dev, int x_dtype, int64_t N, int64_t d, int
                            ldx, (const double *)mean_dev, (double *)out_dev);
     }
     return launch_status("column_sums_kernel");
+}
+
+/* ---- weighted forms ------------------------------------------------------------------------------- */
+
+int dbgsom_weighted_sum_f64(const double *v_dev, const double *w_dev, int64_t n, double *out_dev, void *workspace_dev,
+                            size_t workspace_bytes, void *stream) {
+    DBGSOM_REQUIRE(n >= 0 && out_dev && workspace_dev, "bad arguments");
+    DBGSOM_REQUIRE(n == 0 || w_dev, "null weights");
+    if (workspace_bytes < (size_t)RB * sizeof(double)) {
+        set_error("dbgsom_weighted_sum_f64: workspace too small");
+        return DBGSOM_ENOMEM;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    double *part = (double *)workspace_dev;
+    hipLaunchKernelGGL(wsum_partial_kernel, dim3(RB), dim3(256), 0, s, v_dev, w_dev, n, part);
+    hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(RB), 0, s, part, out_dev);
+    return launch_status("weighted sum kernels");
+}
+
+int dbgsom_topographic_weight(const int64_t *idx2_dev, const double *w_dev, int64_t n, const int32_t *xy_dev, int64_t M,
+                              double *out_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    DBGSOM_REQUIRE(n >= 0 && M >= 1 && M <= 0x7fffffff && out_dev && workspace_dev, "bad arguments");
+    DBGSOM_REQUIRE(n == 0 || (idx2_dev && xy_dev && w_dev), "null pointer");
+    if (workspace_bytes < (size_t)RB * sizeof(double)) {
+        set_error("dbgsom_topographic_weight: workspace too small");
+        return DBGSOM_ENOMEM;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    double *part = (double *)workspace_dev;
+    hipLaunchKernelGGL(topographic_w_kernel, dim3(RB), dim3(256), 0, s, idx2_dev, w_dev, n, xy_dev, (int)M, part);
+    hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(RB), 0, s, part, out_dev);
+    return launch_status("topographic_w_kernel");
+}
+
+int dbgsom_class_histogram_weighted(const int32_t *order_dev, const uint32_t *seg_start_dev, const int32_t *y_dev,
+                                    const double *w_dev, int64_t n, int64_t M, int64_t n_classes, double *hist_dev,
+                                    void *stream) {
+    DBGSOM_REQUIRE(n >= 0 && M >= 1 && M <= 0x7fffffff && n_classes >= 1 && n_classes <= 0x7fffffff && hist_dev,
+                   "bad arguments");
+    DBGSOM_REQUIRE(order_dev && seg_start_dev && y_dev && w_dev, "null pointer");
+    hipLaunchKernelGGL(class_hist_w_kernel, dim3((unsigned)M), dim3(256), 0, (hipStream_t)stream, order_dev, seg_start_dev,
+                       n, y_dev, w_dev, (int)M, (int)n_classes, hist_dev);
+    return launch_status("class_hist_w_kernel");
+}
+
+size_t dbgsom_weighted_column_sums_workspace_bytes(int64_t d) {
+    return d < 1 ? 0 : (size_t)WC_RB * (size_t)d * sizeof(double);
+}
+
+int dbgsom_weighted_column_sums(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *w_dev,
+                                const double *mean_dev, double *out_dev, void *workspace_dev, size_t workspace_bytes,
+                                void *stream) {
+    DBGSOM_REQUIRE(valid_dtype(x_dtype), "x_dtype must be DBGSOM_F32/F64/BF16");
+    DBGSOM_REQUIRE(N >= 0 && d >= 1 && d <= 0x7fffffff && ldx >= d && out_dev && workspace_dev, "bad arguments");
+    DBGSOM_REQUIRE(N == 0 || (X_dev && w_dev), "null input");
+    if (workspace_bytes < dbgsom_weighted_column_sums_workspace_bytes(d)) {
+        set_error("dbgsom_weighted_column_sums: workspace too small");
+        return DBGSOM_ENOMEM;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    double *part = (double *)workspace_dev;
+    const dim3 grid((unsigned)((d + WC_COLS - 1) / WC_COLS), WC_RB / WC_RL), block(WC_COLS * WC_RL);
+    if (x_dtype == DBGSOM_F32)
+        hipLaunchKernelGGL(wcol_partial_kernel<float>, grid, block, 0, s, (const float *)X_dev, N, (int)d, ldx, w_dev, mean_dev, part);
+    else if (x_dtype == DBGSOM_F64)
+        hipLaunchKernelGGL(wcol_partial_kernel<double>, grid, block, 0, s, (const double *)X_dev, N, (int)d, ldx, w_dev, mean_dev, part);
+    else
+        hipLaunchKernelGGL(wcol_partial_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)X_dev, N, (int)d, ldx, w_dev, mean_dev, part);
+    hipLaunchKernelGGL(wcol_final_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, s, part, (int)d, out_dev);
+    return launch_status("weighted column sums kernels");
 }
 
 }  // extern "C"

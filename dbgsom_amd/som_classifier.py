@@ -35,7 +35,23 @@ class SomClassifier(BaseSom, TransformerMixin, ClassifierMixin):
         hits = self._node_stats["hit_count"]
         labels = np.empty(m, dtype=np.int64)
         probs = np.zeros((m, n_classes))
+        sw = self._sw
         for j in range(m):
+            if sw is not None:
+                # rows of weight w count w times: weighted class counts; a tie goes to the tied class whose first
+                # row of positive weight comes first (statistics.mode on the repeated rows)
+                mask = (winners == j) & (sw > 0)
+                members = y[mask]
+                if len(members) == 0:
+                    labels[j] = -1
+                    probs[j, -1] = 0 / hits[j] if hits[j] > 0 else 1
+                    continue
+                counts = np.bincount(members, weights=sw[mask], minlength=n_classes)
+                tied = np.flatnonzero(counts == counts.max())
+                labels[j] = tied[0] if len(tied) == 1 else members[np.isin(members, tied).argmax()]
+                ids = np.flatnonzero(counts)
+                probs[j, ids] = counts[ids] / hits[j] if hits[j] > 0 else 1
+                continue
             members = y[winners == j]
             if len(members) == 0:
                 labels[j] = -1

@@ -39,3 +39,7 @@ class SomVQ(BaseSom, ClusterMixin, TransformerMixin):
 
     def _fit(self, X) -> None:
         self.labels_ = self.predict(X)
+
+    def fit_predict(self, X, y=None, sample_weight=None) -> np.ndarray:
+        """``fit(X, y, sample_weight).labels_``: the index of the best matching unit of every row of X."""
+        return self.fit(X, y, sample_weight=sample_weight).labels_

@@ -122,6 +122,19 @@ int dbgsom_accumulate(const void *X_dev, int x_dtype, int64_t N, int64_t d, int6
                       int64_t M, double *sums_dev, int32_t *status_dev, void *workspace_dev,
                       size_t workspace_bytes, void *stream);
 
+/* The same sums with a weight per row (sw_dev: N float64, finite and >= 0 -- not checked here): a row of
+ * weight w counts as w copies of that row,
+ *   S_j = sum sw_i kw_i x_i,  K_j = sum sw_i kw_i,  a_j = sum sw_i,  E_j = sum sw_i dist_i.
+ * a_j is an ordered float64 sum like K_j and E_j (list order, chunk order, group order: bitwise
+ * reproducible, independent of the grid); rows of weight 0 are not streamed and contribute to nothing.
+ * The first N int32 of the workspace hold the sample ids bucketed by winner as after dbgsom_accumulate
+ * (rows of weight 0 included: the sort does not look at weights, the sums skip those rows). */
+size_t dbgsom_accumulate_weighted_workspace_bytes(int64_t N, int64_t d, int64_t M);
+int dbgsom_accumulate_weighted(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx,
+                               const int64_t *idx_dev, const double *kw_dev, const double *sw_dev,
+                               const double *dist_dev, int64_t M, double *sums_dev, int32_t *status_dev,
+                               void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* Neighbourhood-weighted batch update: steps 3-5 of BaseSom._update_weights
  * BaseSom.py:506-522 with _calculate_gaussian_neighborhood BaseSom.py:525-531.
  *   c_j = S_j / K_j placed per `layout`;  h = exp(-(hop^2 / (2 sigma^2)));
@@ -223,6 +236,27 @@ int dbgsom_column_sums(const void *X_dev, int x_dtype, int64_t N, int64_t d, int
 int dbgsom_density_terms(const double *dist_dev, int64_t n, double sigma, double *out_dev,
                          void *stream);
 
+/* Weighted forms of the reductions above (w_dev: one float64 weight per row).  Floating-point sums without
+ * atomics: fixed grids and ordered partials, bitwise reproducible.
+ *   dbgsom_weighted_sum_f64   out = sum_i w_i v_i (v_dev == NULL: sum_i w_i); workspace as dbgsom_sum_f64
+ *   dbgsom_topographic_weight out = summed weight of the rows dbgsom_topographic_count counts
+ *   dbgsom_class_histogram_weighted  hist[j, c] = summed weight of the rows of class c in neuron j's list:
+ *       order_dev = the N sample ids bucketed by winner (stable), seg_start_dev = the M list starts; added in list order
+ *   dbgsom_weighted_column_sums  out[j] = sum_i w_i x_ij (mean_dev == NULL) or sum_i w_i (x_ij - mean_j)^2, in
+ *       float64 whatever the storage dtype (mean_dev, out_dev: d float64) */
+int dbgsom_weighted_sum_f64(const double *v_dev, const double *w_dev, int64_t n, double *out_dev,
+                            void *workspace_dev, size_t workspace_bytes, void *stream);
+int dbgsom_topographic_weight(const int64_t *idx2_dev, const double *w_dev, int64_t n, const int32_t *xy_dev,
+                              int64_t M, double *out_dev, void *workspace_dev, size_t workspace_bytes,
+                              void *stream);
+int dbgsom_class_histogram_weighted(const int32_t *order_dev, const uint32_t *seg_start_dev, const int32_t *y_dev,
+                                    const double *w_dev, int64_t n, int64_t M, int64_t n_classes,
+                                    double *hist_dev, void *stream);
+size_t dbgsom_weighted_column_sums_workspace_bytes(int64_t d);
+int dbgsom_weighted_column_sums(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx,
+                                const double *w_dev, const double *mean_dev, double *out_dev,
+                                void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* hist[j, c] = |{i : win_i = j, y_i = c}| (M x n_classes uint64, integer atomics: exact).
  * Entropy growth criterion BaseSom.py:547-551 and SomClassifier._label_prototypes
  * SomClassifier.py:130-152 (their O(N*M) boolean masks). */
@@ -289,6 +323,21 @@ int dbgsom_ctx_load_device(dbgsom_ctx *ctx, const void *X_dev, int x_dtype, int6
 int dbgsom_ctx_read_samples(dbgsom_ctx *ctx, const int64_t *rows_host, int64_t n, double *out_host);
 /* integer class labels of the resident rows (entropy criterion BaseSom.py:547-551) */
 int dbgsom_ctx_set_labels(dbgsom_ctx *ctx, const int32_t *y_host, int64_t N);
+/* One weight per resident row (float64, finite, >= 0): a row of weight w counts as w copies of that row.
+ * With weights attached dbgsom_ctx_epoch, dbgsom_ctx_update, dbgsom_ctx_quantization_error ([sum w dist, sum w]),
+ * dbgsom_ctx_topographic_count (summed weight), dbgsom_ctx_node_statistics (hits = sum w, density sums = sum w
+ * term) run their weighted forms; the BMU searches do not depend on weights.  In a multi-rank run every rank
+ * attaches its own rows' weights.  w_host == NULL detaches.  A wrong N or a negative / non-finite weight is
+ * DBGSOM_EINVAL (dbgsom_last_error says which).  dbgsom_ctx_subset_create hands the weights on. */
+int dbgsom_ctx_set_sample_weight(dbgsom_ctx *ctx, const double *w_host, int64_t N);
+/* sum of the resident rows' weights (this rank's; the number of rows when none are attached) */
+int dbgsom_ctx_weight_total(dbgsom_ctx *ctx, double *out_host);
+/* weighted column sums of the resident samples in float64 (dbgsom_weighted_column_sums): mean_host == NULL:
+ * out_j = sum_i w_i x_ij, else sum_i w_i (x_ij - mean_j)^2; d float64 each */
+int dbgsom_ctx_weighted_column_sums(dbgsom_ctx *ctx, const double *mean_host, double *out_host);
+/* dbgsom_ctx_class_histogram with weights: hist_host (M x n_classes float64) = summed weights, all ranks */
+int dbgsom_ctx_class_histogram_weighted(dbgsom_ctx *ctx, const int64_t *idx_host, int64_t n_classes, int64_t M,
+                                        double *hist_host);
 
 /* Lattice hop distances, M x M float64 as nx.floyd_warshall_numpy returns them
  * (BaseSom.py:367,401).  Call again whenever neurons were added. */

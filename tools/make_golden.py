@@ -455,6 +455,35 @@ def main():
              "est": "SomVQ(random_state=2, vertical_growth=True, n_iter=24, max_neurons=9, "
                     "min_samples_vertical_growth=150, spreading_factor=0.6)"},
         )
+    # weighted: the reference has no sample_weight; for integer weights a weighted fit IS the fit on
+    # np.repeat(X, w, 0) (tests/golden_inputs_weighted.py holds the inputs), which is what runs here
+    sys.path.insert(0, os.path.dirname(HERE))
+    from tests import golden_inputs_weighted as giw  # noqa: E402
+
+    wpath = os.path.join(OUT, "manifest_weighted.json")   # (a manifest of their own: manifest.json stays as it is)
+    wmanifest = json.load(open(wpath)) if os.path.exists(wpath) else {"versions": ref_shim.versions(), "cases": {}}
+    for name in giw.FIT_CASES + [giw.VERTICAL_CASE]:
+        if only and name not in only and "weighted" not in only:
+            continue
+        Xw, yw, ww = giw.case(name)
+        Xr, yr = giw.repeated(name)
+        cls = SomClassifier if name in giw.CLF_CASES else SomVQ
+        kw = giw.EST_KWARGS[name]
+        meta = {"X": "tests/golden_inputs_weighted.py case(%r), repeated by its weights" % name,
+                "est": "%s(%s)" % (cls.__name__, ", ".join("%s=%r" % kv for kv in kw.items())),
+                "rows": int(len(ww)), "rows_of_weight_0": int((ww == 0).sum()), "sum_w": int(ww.sum())}
+        if name == giw.VERTICAL_CASE:
+            wmanifest["cases"][name] = run_vertical_case(name, lambda: cls(**kw), Xr, meta)
+        else:
+            wmanifest["cases"][name] = run_fit_case(name, lambda: cls(**kw), Xr, yr, [0], meta)
+            # the labels of the DISTINCT rows (the rows of weight 0 included: a query, not part of the fit)
+            est = cls(**kw).fit(Xr) if yr is None else cls(**kw).fit(Xr, yr)
+            extra = dict(np.load(os.path.join(OUT, f"{name}.npz")))
+            extra["distinct_bmu"] = est._get_winning_neurons(Xw, n_bmu=1)[1]
+            np.savez_compressed(os.path.join(OUT, f"{name}.npz"), **extra)
+    if wmanifest["cases"]:
+        with open(wpath, "w") as f:
+            json.dump(wmanifest, f, indent=1, sort_keys=True)
     for name in GROW_CASES:
         if not only or name in only:
             manifest["cases"][name] = run_grow_case(name)
