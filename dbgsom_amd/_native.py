@@ -108,6 +108,17 @@ SIGNATURES = {
                                  _vp, _sz, _vp]),
     "dbgsom_sparse_code_timing": (_ci, [_ci]),
     "dbgsom_sparse_code_stage_ms": (_ci, [_vp]),
+    "dbgsom_csr_check": (_ci, [_vp, _vp, _i64, _i64, _i64]),
+    "dbgsom_csr_row_sqnorms": (_ci, [_vp, _vp, _ci, _i64, _vp, _vp]),
+    "dbgsom_csr_wt_ld": (_i64, [_i64]),
+    "dbgsom_csr_transpose_weights": (_ci, [_vp, _i64, _i64, _i64, _vp, _i64, _vp]),
+    "dbgsom_bmu_csr": (_ci, [_vp, _vp, _vp, _ci, _i64, _vp, _vp, _i64, _i64, _vp, _ci, _ci, _vp, _vp, _vp]),
+    "dbgsom_csr_densify": (_ci, [_vp, _vp, _vp, _ci, _i64, _i64, _i64, _vp, _vp]),
+    "dbgsom_accumulate_csr_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "dbgsom_accumulate_csr": (_ci, [_vp, _vp, _vp, _ci, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _sz,
+                                    _vp]),
+    "dbgsom_ctx_load_csr": (_ci, [_vp, _vp, _vp, _vp, _ci, _i64, _i64, _i64]),
+    "dbgsom_ctx_bmu_query_csr": (_ci, [_vp, _vp, _vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _ci, _ci, _vp, _vp]),
     "dbgsom_ctx_sparse_code": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _ci, _vp, _i64, _vp, _vp, _vp]),
     "dbgsom_topofn_workspace_bytes": (_sz, [_i64, _ci]),
     "dbgsom_topofn": (_ci, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),

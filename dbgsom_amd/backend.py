@@ -69,7 +69,10 @@ def _group_is_up() -> bool:
 
 class HotPathBackend:
     """Epoch template shared by the HIP backend and the test-only oracle backend:
-    local per-prototype sums -> (all-reduce across sample shards) -> smoothing."""
+    local per-prototype sums -> (all-reduce across sample shards) -> smoothing.
+
+    ``load(X)`` and ``bmu(W, k, X=...)`` may be handed a scipy sparse matrix in CSR form (the estimators
+    pass sparse input through as it is); every other argument is dense."""
 
     name = "abstract"
 
@@ -250,6 +253,36 @@ class HotPathBackend:
         return self.__class__(*getattr(self, "_init_args", ()))
 
 
+def is_sparse(X) -> bool:
+    """Whether X is a scipy sparse matrix / array (scipy is only imported when it already is)."""
+    import sys
+
+    sp = sys.modules.get("scipy.sparse")
+    return sp is not None and sp.issparse(X)
+
+
+def canonical_csr(X):
+    """X as canonical CSR for the device: column indices ascending and without duplicates within a row (made
+    so on a copy when they are not), float32 kept, anything else but float64 converted to float64 as dense
+    input is, `indices` int32, `indptr` int64 -> (csr, indptr, indices, data)."""
+    import scipy.sparse as sp
+
+    csr = sp.csr_matrix(X)   # (CSC / COO / ... are converted; a CSR matrix is not copied)
+    if csr.dtype not in (np.float32, np.float64):
+        csr = csr.astype(np.float64)
+    if csr.ndim != 2 or csr.shape[0] < 1:
+        raise ValueError("X must be a non-empty 2-D array")
+    if not csr.has_canonical_format:
+        csr = csr.copy()         # (csr_matrix(X) shares X's arrays: the caller's matrix stays as it is)
+        csr.sum_duplicates()     # (sorts the indices first)
+    if csr.shape[1] > np.iinfo(np.int32).max:
+        raise ValueError("too many features for int32 column indices")
+    indptr = np.ascontiguousarray(csr.indptr, dtype=np.int64)
+    indices = np.ascontiguousarray(csr.indices, dtype=np.int32)
+    data = np.ascontiguousarray(csr.data)
+    return csr, indptr, indices, data
+
+
 def _x_dtype_code(dt) -> int:
     if isinstance(dt, str) and dt == "bf16":
         return _native.BF16
@@ -381,6 +414,11 @@ class HipBackend(HotPathBackend):
     shard_smooth = property(lambda self: self._get("shard_smooth"), lambda self, v: self._set("shard_smooth", int(v)))
     shard_epochs = property(lambda self: self._get("shard_epochs"))
     defer_epochs = property(lambda self: self._get("defer_epochs"))
+    # CSR input of fewer features than this is expanded into dense rows on the device (0: never); results do
+    # not depend on it.  resident_csr: whether the loaded samples are a CSR resident
+    csr_densify_below = property(lambda self: self._get("csr_densify_below"),
+                                 lambda self, v: self._set("csr_densify_below", int(v)))
+    resident_csr = property(lambda self: bool(self._get("resident_csr")))
     planes_cached = property(lambda self: bool(self._get("planes_cached")))
     padded_features = property(lambda self: self._get("padded_features"))
 
@@ -503,7 +541,18 @@ class HipBackend(HotPathBackend):
     def load(self, X, storage=None):
         """Upload the samples once.  `storage="bf16"` keeps them in HBM as bfloat16 (rounded to
         nearest even on the device; all arithmetic stays float64 on the exactly widened values --
-        an extension, the reference has no bf16)."""
+        an extension, the reference has no bf16).  A scipy sparse matrix is made canonical CSR and loaded as such
+        (``dbgsom_ctx_load_csr``): below ``csr_densify_below`` features it is expanded on the device into the
+        dense resident form, at and above it the CSR kernels run -- the same results either way."""
+        if is_sparse(X):
+            if storage not in (None, "native"):
+                raise ValueError("sparse input cannot be stored as bf16")
+            csr, indptr, indices, data = canonical_csr(X)
+            self._call("dbgsom_ctx_load_csr", self._ctx, indptr.ctypes.data, indices.ctypes.data, data.ctypes.data,
+                       _x_dtype_code(data.dtype), csr.shape[0], csr.shape[1], data.size)
+            self._after_load(csr.shape, data.dtype)
+            self._borrowed = None
+            return self
         X = np.ascontiguousarray(X)
         if X.dtype not in (np.float32, np.float64):  # integer / half input: as check_array would
             X = X.astype(np.float64)
@@ -618,6 +667,19 @@ class HipBackend(HotPathBackend):
             idx = np.empty((N, k), dtype=np.int64)
             dist = np.empty((N, k), dtype=np.float64)
             self._call("dbgsom_ctx_bmu", self._ctx, p, M, int(k), rf, idx.ctypes.data, dist.ctypes.data)
+        elif is_sparse(X):
+            csr, indptr, indices, data = canonical_csr(X)
+            W = np.asarray(W)
+            if W.ndim != 2 or W.shape[1] != csr.shape[1]:
+                raise ValueError("prototype / sample feature mismatch")
+            rf = int(data.dtype == np.float32 and W.dtype == np.float32)
+            W64 = np.ascontiguousarray(W, dtype=np.float64)
+            N = csr.shape[0]
+            idx = np.empty((N, k), dtype=np.int64)
+            dist = np.empty((N, k), dtype=np.float64)
+            self._call("dbgsom_ctx_bmu_query_csr", self._ctx, indptr.ctypes.data, indices.ctypes.data, data.ctypes.data,
+                       _x_dtype_code(data.dtype), N, csr.shape[1], data.size, W64.ctypes.data, W64.shape[0], int(k), rf,
+                       idx.ctypes.data, dist.ctypes.data)
         else:
             X = np.ascontiguousarray(X)
             if X.dtype not in (np.float32, np.float64):
@@ -857,7 +919,7 @@ class HipBackend(HotPathBackend):
         np.std(X, 0, ddof=1) = sqrt(s2 / (N - 1)) bit for bit, without a host pass over X.
         None when the resident dtype has no NumPy counterpart (bfloat16)."""
         self._require_loaded()
-        if isinstance(self._x_np_dtype, str):
+        if isinstance(self._x_np_dtype, str) or self.resident_csr:
             return None
         s1 = np.empty(self._d, dtype=self._x_np_dtype)
         self._call("dbgsom_ctx_column_sums", self._ctx, None, s1.ctypes.data)
@@ -962,7 +1024,7 @@ class HipBackend(HotPathBackend):
         return sub
 
     _SETTABLE = ("algorithm", "sweep_planes", "seed_stride", "timing", "graph", "refine", "defer",
-                 "filter_min_query_rows", "max_mean_candidates", "shard_smooth")
+                 "filter_min_query_rows", "max_mean_candidates", "shard_smooth", "csr_densify_below")
 
     def release(self):
         """Give the device memory back (the backend can be loaded again afterwards; options stay)."""

@@ -16,7 +16,13 @@ Extra, build-only parameters (defaults keep reference behaviour):
     device          HIP device ordinal for the default backend
     sharded_input   False: every rank of a torch.distributed group passes the SAME full X and keeps
                     its row shard resident; True: every rank passes only ITS rows (nothing of size
-                    N is ever gathered; ``labels_`` then describes the local rows)
+                    N is ever gathered; ``labels_`` then describes the local rows); dense X only
+                    (``ValueError`` for sparse X)
+
+Sparse input: ``fit``, ``predict``, ``transform``, ``predict_proba`` and ``calculate_quantization_error``
+take a scipy sparse matrix (converted to CSR; never densified as a whole).  A fit on sparse X equals the fit
+on ``X.toarray()`` up to the column moments, which are taken in float64 from the stored entries.
+``topographic_function`` takes dense X only (``TypeError`` for sparse X).
 """
 from __future__ import annotations
 
@@ -32,7 +38,7 @@ from sklearn.utils import check_array, check_random_state
 from sklearn.utils.validation import check_is_fitted
 
 from . import schedule
-from .backend import RESIDENT, HotPathBackend, dist_info, shard_bounds
+from .backend import RESIDENT, HotPathBackend, dist_info, is_sparse, shard_bounds
 from .lattice import GrowingLattice
 
 
@@ -298,6 +304,45 @@ class BaseSom(BaseEstimator):
     def _check_input_data(self, X, y):
         raise NotImplementedError
 
+    def _check_sparse_input(self, X):
+        """What sklearn's validation leaves to do for sparse X: the finite check on the host (a pass over the
+        stored entries; nothing is deferred to the device), the modes that take dense X only, and canonical form
+        (sorted column indices, duplicates summed) on a copy when X is not in it.  -> X"""
+        if not is_sparse(X):
+            return X
+        if self.sharded_input:
+            raise ValueError("sharded_input=True takes dense X only; with sparse X every rank passes the whole "
+                             "matrix and keeps its row slice resident")
+        self._finite_deferred = False
+        from sklearn.utils import assert_all_finite
+
+        assert_all_finite(X.data)
+        if not X.has_canonical_format:   # (the column moments and the device want one stored entry per position)
+            X = X.copy()
+            X.sum_duplicates()
+        return X
+
+    @staticmethod
+    def _sparse_column_s2(X, w=None, total=None):
+        """sum_i w_i (x_ij - mean_j)^2 per column of a CSR / CSC matrix in float64 from the stored entries:
+        mean_j = sum / n,  s2_j = sum over stored (x - mean_j)^2 + (n - nnz_j) mean_j^2; with weights the same
+        with w_i in every sum, n = `total` = sum w and nnz_j the summed weight of the column's stored entries."""
+        csr = X.tocsr()
+        d = csr.shape[1]
+        val = csr.data.astype(np.float64, copy=False)
+        col = csr.indices
+        if w is None:
+            n = float(csr.shape[0])
+            wv = None
+            stored = np.bincount(col, minlength=d).astype(np.float64)
+        else:
+            n = float(total)
+            wv = np.repeat(np.asarray(w, dtype=np.float64), np.diff(csr.indptr))
+            stored = np.bincount(col, weights=wv, minlength=d)
+        mean = np.bincount(col, weights=val if wv is None else wv * val, minlength=d) / n
+        dev2 = (val - mean[col]) ** 2
+        return np.bincount(col, weights=dev2 if wv is None else wv * dev2, minlength=d) + (n - stored) * mean ** 2
+
     # -- input validation (SomVQ.py:122 / SomClassifier.py: check_array / check_X_y) -------------
     def _finite_check_on_device(self) -> bool:
         """Whether the "no NaN, no infinity" part of sklearn's input validation can ride on the column sums
@@ -352,7 +397,11 @@ class BaseSom(BaseEstimator):
         # resident copy when it is the whole data set: same values bit for bit (f-1)
         self._col_s2 = None
         on_device = isinstance(data, DeviceSamples)
-        if self._sw is not None:
+        sparse = is_sparse(data)
+        if sparse:
+            # every rank holds the whole matrix: the moments on the host, in float64, from the stored entries
+            self._col_s2 = self._sparse_column_s2(data, self._sw, self._w_total if self._sw is not None else None)
+        elif self._sw is not None:
             # weighted population moments, divisor sum w: accumulated in float64 whatever the dtype of X
             wt = self._w_total
             if self._local_input():
@@ -396,13 +445,15 @@ class BaseSom(BaseEstimator):
             seed = int(self._all_reduce_f64(np.array([float(drawn >> 31), float(drawn & (2 ** 31 - 1))]))
                        @ np.array([2.0 ** 31, 1.0]))
         rng = np.random.default_rng(seed=seed)
-        if on_device or self._local_input() or self._sw is not None:
+        if on_device or self._local_input() or self._sw is not None or sparse:
             if self._sw is None:
                 # rng.choice(a=data, size=4, replace=False) picks rows rng.choice(n, 4, replace=False)
                 rows = rng.choice(n_total, size=4, replace=False)
             else:
                 rows = self._draw_weighted_rows(rng)
-            if not (on_device or self._local_input()):
+            if sparse:
+                start = data[rows].toarray()
+            elif not (on_device or self._local_input()):
                 start = data[rows]
             elif on_device:
                 start = engine.read_samples(rows).astype(data.dtype)
@@ -628,7 +679,7 @@ class BaseSom(BaseEstimator):
         check_is_fitted(self)
         if self._is_resident(X):  # during fit: a device reduction, distances never leave HBM
             return self._engine().quantization_error(self.weights_)
-        X = check_array(X, dtype=[np.float64, np.float32])
+        X = check_array(X, dtype=[np.float64, np.float32], accept_sparse="csr")
         distances, _ = self._get_winning_neurons(X, n_bmu=1)
         return float(np.mean(distances))
 
@@ -690,15 +741,30 @@ class BaseSom(BaseEstimator):
         SparseCoder on normalize(X) with dictionary normalize(weights_), computed by the backend
         (on the MI355X: csrc/sparse_code.hip; n_jobs only matters to the host default)."""
         check_is_fitted(self)
-        X = check_array(X, dtype=[np.float64, np.float32])
-        return self._engine().sparse_code(self.weights_, X, n_jobs=self.n_jobs)
+        X = check_array(X, dtype=[np.float64, np.float32], accept_sparse="csr")
+        return self._sparse_code(X)
+
+    _SPARSE_CODE_ROWS = 4096   # rows of sparse X densified at a time for the sparse coder
+
+    def _sparse_code(self, X, P=None):
+        """The backend's sparse code (class probabilities with P) of the rows of X.  Sparse X: row chunks are
+        densified on the host into the same call -- rows are coded independently, so the result is the dense
+        call's."""
+        engine = self._engine()
+        if not is_sparse(X):
+            return engine.sparse_code(self.weights_, X, P=P, n_jobs=self.n_jobs)
+        step = self._SPARSE_CODE_ROWS
+        parts = [engine.sparse_code(self.weights_, X[lo:lo + step].toarray(), P=P, n_jobs=self.n_jobs)
+                 for lo in range(0, X.shape[0], step)]
+        return np.concatenate(parts, axis=0)
 
     def topographic_function(self, X) -> tuple[np.ndarray, np.ndarray]:
         """(phi(k) / M for k = 0 .. max_dist - 1, phi(-k) / M for the same k), max_dist the largest
         Chebyshev distance between lattice positions (BaseSom.py:955-998).  The graph is the induced
         Delaunay triangulation of X (an edge between the two BMUs of every sample); the backend returns
         the two histograms phi is made of (on the MI355X: csrc/topofn.hip).  Unlike the reference, no
-        dense M x M matrix is kept on the estimator (``want_distances=True`` on the backend gives D)."""
+        dense M x M matrix is kept on the estimator (``want_distances=True`` on the backend gives D).
+        Dense X only: sparse X raises ``TypeError``."""
         check_is_fitted(self)
         X = check_array(X, dtype=[np.float64, np.float32])
         if X.shape[1] != self.n_features_in_:
@@ -740,7 +806,8 @@ class BaseSom(BaseEstimator):
         self.vertical_growing_threshold_ = 1.5 * self.growing_threshold_
         engine = self._engine()
         errors = self._lattice.error
-        on_device = self._is_resident(X) and hasattr(engine, "subset") and dist_info()[1] == 1
+        # (sparse X: the host-subset branch -- X[winners == j] is CSR row selection)
+        on_device = self._is_resident(X) and hasattr(engine, "subset") and dist_info()[1] == 1 and not is_sparse(X)
         sw = self._sw
         if on_device:
             counts, winners = engine.partition(self.weights_, want_winners=y is not None or sw is not None)

@@ -851,7 +851,8 @@ static int launch_chain(dim3 grid, const XT *X, int d, int64_t ldx, const AccWs 
 static int accumulate_impl(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx,
                            const int64_t *idx, const double *kw, double gamma, const double *dist, int64_t M,
                            double *sums, int32_t *status, bool status_behind_sums, void *ws,
-                           size_t ws_bytes, hipStream_t s, const DistFill *fill = nullptr, const double *sw = nullptr) {
+                           size_t ws_bytes, hipStream_t s, const DistFill *fill = nullptr, const double *sw = nullptr,
+                           const CsrView *csr = nullptr) {
     DBGSOM_REQUIRE(valid_dtype(x_dtype), "x_dtype must be DBGSOM_F32/F64/BF16");
     DBGSOM_REQUIRE(N >= 0 && N < 0x7fffffff && d >= 1 && d <= 0x7ffffff0 && ldx >= d, "bad sample shape");
     DBGSOM_REQUIRE(M >= 1 && M <= DBGSOM_MAX_PROTOTYPES, "M outside [1, DBGSOM_MAX_PROTOTYPES]");
@@ -862,7 +863,7 @@ static int accumulate_impl(const void *X, int x_dtype, int64_t N, int64_t d, int
         DBGSOM_HIP_CHECK(hipMemsetAsync(sums, 0, (size_t)(M * (d + 3) + (status_behind_sums ? 1 : 0)) * sizeof(double), s));
         return DBGSOM_OK;
     }
-    DBGSOM_REQUIRE(X && idx && dist && ws, "null pointer");
+    DBGSOM_REQUIRE((X || csr) && idx && dist && ws, "null pointer");
     DBGSOM_REQUIRE(is_aligned(ws, 256), "workspace must be 256-byte aligned");
     const size_t need = sw ? accumulate_weighted_workspace_bytes(N, d, M) : accumulate_workspace_bytes(N, d, M);
     if (ws_bytes < need) {
@@ -894,7 +895,13 @@ static int accumulate_impl(const void *X, int x_dtype, int64_t N, int64_t d, int
                                kw, gamma, dist, w.seg_start, w.count, w.chunk_pre, Mi, w.slab,   \
                                WeightArg<false>{});                                              \
     } while (0)
-    if (fill) {
+    if (csr) {
+        // CSR samples: the chunk kernel of csr.hip writes the same slab rows; everything around it is shared
+        DBGSOM_REQUIRE(!fill, "distances cannot be filled in for CSR samples");
+        const int rc = launch_segsum_csr(*csr, x_dtype, d, w.order, kw, gamma, dist, w.seg_start, w.count, w.chunk_pre, M,
+                                         w.slab, sw, w.maxchunks, s);
+        if (rc != DBGSOM_OK) return rc;
+    } else if (fill) {
         // rows with dist == -1 get their distance (to their winner: this chunk's prototype) on the way
         DBGSOM_REQUIRE(!kw && al16 && accumulate_can_fill_distances(x_dtype, d) && fill->W && fill->ww && fill->xx,
                        "distances cannot be filled in for this shape");
@@ -971,6 +978,15 @@ int launch_accumulate_epoch_weighted(const void *X, int x_dtype, int64_t N, int6
                                      const DistFill *fill) {
     DBGSOM_REQUIRE(N == 0 || sw, "null sample weights");
     return accumulate_impl(X, x_dtype, N, d, ldx, idx, nullptr, gamma, dist, M, sums, status, true, ws, ws_bytes, s, fill, sw);
+}
+
+int launch_accumulate_csr(const CsrView &x, int x_dtype, int64_t N, int64_t d, const int64_t *idx, const double *kw,
+                          double gamma, const double *sw, const double *dist, int64_t M, double *sums,
+                          int32_t *status, bool status_behind_sums, void *ws, size_t ws_bytes, hipStream_t s) {
+    DBGSOM_REQUIRE(x_dtype == DBGSOM_F32 || x_dtype == DBGSOM_F64, "CSR data must be DBGSOM_F32 or DBGSOM_F64");
+    DBGSOM_REQUIRE(N == 0 || x.indptr, "null CSR arrays");
+    return accumulate_impl(nullptr, x_dtype, N, d, d, idx, kw, gamma, dist, M, sums, status, status_behind_sums, ws,
+                           ws_bytes, s, nullptr, sw, &x);
 }
 
 }  // namespace dbgsom

@@ -124,6 +124,32 @@ int launch_accumulate_epoch_weighted(const void *X, int x_dtype, int64_t N, int6
                                      const int64_t *idx, double gamma, const double *sw, const double *dist, int64_t M,
                                      double *sums, int32_t *status, void *ws, size_t ws_bytes, hipStream_t s,
                                      const DistFill *fill = nullptr);
+// CSR samples (csr.hip): canonical CSR on the device -- indptr int64 (N + 1), indices int32 strictly ascending
+// within a row, data float32 / float64.  The search reads Wt (d x ldwt, ldwt = csr_wt_ld(M)), the transposed
+// float64 prototypes; the sums go through the dense pipeline of accumulate.hip with the chunk kernel replaced.
+struct CsrView {
+    const int64_t *indptr = nullptr;
+    const int32_t *indices = nullptr;
+    const void *data = nullptr;
+};
+int64_t csr_wt_ld(int64_t M);
+int launch_csr_row_sqnorms(const CsrView &x, int dtype, int64_t N, double *out, hipStream_t s);
+int launch_transpose_weights(const double *W, int64_t M, int64_t d, int64_t ldw, double *Wt, int64_t ldwt,
+                             hipStream_t s);
+int launch_bmu_csr(const CsrView &x, int dtype, int64_t N, const double *xx, const double *Wt, int64_t ldwt,
+                   int64_t M, const double *ww, int k, int round_f32, int64_t *idx, double *dist, hipStream_t s);
+int launch_segsum_csr(const CsrView &x, int dtype, int64_t d, const int32_t *order, const double *kw, double gamma,
+                      const double *dist, const uint32_t *seg_start, const uint32_t *count,
+                      const uint32_t *chunk_pre, int64_t M, double *slab, const double *sw, int64_t maxchunks,
+                      hipStream_t s);
+int launch_csr_densify(const CsrView &x, int dtype, int64_t N, int64_t d, int64_t ld, void *out, hipStream_t s);
+int launch_csr_rows_to_f64(const CsrView &x, int dtype, const int64_t *ids, int64_t n, int64_t cols, double *dst,
+                           hipStream_t s);
+// the sums of launch_accumulate* for CSR samples (kw == nullptr: the sample kernel with `gamma` on the fly and the
+// status flag behind the sums, as launch_accumulate_epoch; sw != nullptr: the weighted form and its workspace)
+int launch_accumulate_csr(const CsrView &x, int x_dtype, int64_t N, int64_t d, const int64_t *idx, const double *kw,
+                          double gamma, const double *sw, const double *dist, int64_t M, double *sums,
+                          int32_t *status, bool status_behind_sums, void *ws, size_t ws_bytes, hipStream_t s);
 size_t bucket_sort_workspace_bytes(int64_t N, int64_t M);
 int launch_bucket_sort(const int64_t *idx, int64_t N, int64_t M, int32_t *order, void *ws,
                        hipStream_t s);

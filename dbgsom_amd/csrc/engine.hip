@@ -6,7 +6,7 @@
 // all-pairs and the filtered BMU search ("auto" / back-off), the adaptive number of digit planes,
 // previous winners as seeds, device-resident prototypes between epochs, the one all-reduce per
 // epoch (through the caller's callback).  No kernels of the hot path in this file: it drives the
-// launchers of bmu*.hip, filter.hip, accumulate.hip, smooth.hip, stats.hip.
+// launchers of bmu*.hip, filter.hip, accumulate.hip, smooth.hip, stats.hip, csr.hip (CSR residents).
 #include <dlfcn.h>
 #include <math.h>
 #include <stdlib.h>
@@ -24,10 +24,14 @@ namespace dbgsom {
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    // tight: allocate what is asked for, without the head room for a growing map (the buffers of a context whose
+    // resident samples are CSR: such data is loaded because memory is short, and a growth step then pays a
+    // reallocation of the buffers that scale with M)
+    bool tight = false;
     int reserve(size_t bytes) {
         if (bytes <= cap) return DBGSOM_OK;
         if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        const size_t want = align_up(bytes + bytes / 8, 1 << 20);
+        const size_t want = tight ? align_up(bytes) : align_up(bytes + bytes / 8, 1 << 20);
         hipError_t e = hipMalloc(&p, want);
         if (e != hipSuccess) {
             p = nullptr;
@@ -229,7 +233,16 @@ struct Samples {  // one resident sample set (training samples, or a query batch
     int bdtype = -1;
     DevBuf own, x32, xx, planes;
     bool planes_ready = false;
-    void release() { own.release(); x32.release(); xx.release(); planes.release(); planes_ready = false; dtype = -1; N = 0; X = Xb = nullptr; }
+    // CSR residents (dbgsom_ctx_load_csr at or above "csr_densify_below" features): X stays nullptr, the rows are
+    // the three arrays below; dtype F32 / F64, dp = pad16(d) as for dense rows (prototypes and sums keep their layout)
+    bool csr = false;
+    int64_t nnz = 0;
+    DevBuf indptr, indices, data;
+    CsrView view() const { return CsrView{indptr.as<int64_t>(), indices.as<int32_t>(), data.p}; }
+    void release() {
+        own.release(); x32.release(); xx.release(); planes.release(); indptr.release(); indices.release(); data.release();
+        planes_ready = false; csr = false; nnz = 0; dtype = -1; N = 0; X = Xb = nullptr;
+    }
 };
 
 }  // namespace
@@ -287,6 +300,10 @@ struct dbgsom_ctx {
     int64_t otherM = 0;  // rows of Wb[cur ^ 1]
     // per-epoch device state
     DevBuf ww, idx[2], dist, kw, sums, acc_ws, sm_ws, filt_ws, scal, qidx, qdist, red, hist, stage_dev;
+    // CSR residents: the transposed float64 prototypes the CSR search reads (rebuilt from Wb[cur] in front of every
+    // search), and the feature count below which dbgsom_ctx_load_csr expands into dense rows (0 = never)
+    DevBuf wt;
+    int64_t csr_densify_below = 1024;
     int icur = 0;            // idx[icur]: winners of the last epoch (the hint)
     bool hint_valid = false;
     int64_t hintM = 0;
@@ -433,6 +450,7 @@ int place_host_samples(dbgsom_ctx *c, Samples &s, const void *X_host, int x_dtyp
                    "storage must be the input dtype, or DBGSOM_BF16 for float32 input");
     const int64_t dp = pad16(d);
     s.N = N; s.d = d; s.dp = dp; s.dtype = storage;
+    s.csr = false; s.nnz = 0;
     bool widened = false;
     if (storage == DBGSOM_BF16 && x_dtype == DBGSOM_F32) {
         TRY(s.x32.reserve((size_t)N * dp * 4));
@@ -465,7 +483,7 @@ bool filter_shape_ok(const Samples &s, int64_t M) {
 }
 
 bool filter_applies(const dbgsom_ctx *c, int64_t M) {
-    if (c->algorithm == DBGSOM_ALG_EXACT) return false;
+    if (c->algorithm == DBGSOM_ALG_EXACT || c->xs.csr) return false;   // (no candidate pruning for CSR residents)
     if (c->algorithm == DBGSOM_ALG_AUTO && c->filter_backoff > 0) return false;
     return filter_shape_ok(c->xs, M);
 }
@@ -942,6 +960,58 @@ void mark(dbgsom_ctx *c, int k) {
     (void)hipEventRecord(c->ev[k], c->stream);
 }
 
+// CSR samples: upload the three arrays (checked on the host first) and take the norms; below
+// `densify_below` features the rows are expanded on the device into the ordinary padded form instead and `s`
+// is a dense sample set like any other (the CSR arrays are then only staged)
+int place_host_csr(dbgsom_ctx *c, Samples &s, const int64_t *indptr_host, const int32_t *indices_host,
+                   const void *data_host, int x_dtype, int64_t N, int64_t d, int64_t nnz, int64_t densify_below) {
+    DBGSOM_REQUIRE(x_dtype == DBGSOM_F32 || x_dtype == DBGSOM_F64, "CSR data must be DBGSOM_F32 or DBGSOM_F64 (no bfloat16 storage)");
+    DBGSOM_REQUIRE(indptr_host && N >= 1 && d >= 1 && nnz >= 0 && N < 0x7fffffff && d <= 0x7fffffff, "bad samples");
+    DBGSOM_REQUIRE(nnz == 0 || (indices_host && data_host), "null pointer");
+    TRY(dbgsom_csr_check(indptr_host, indices_host, N, d, nnz));
+    const size_t es = dtype_size(x_dtype);
+    const int64_t dp = pad16(d);
+    s.N = N; s.d = d; s.dp = dp; s.dtype = x_dtype; s.nnz = nnz; s.csr = false;
+    s.X = s.Xb = nullptr;
+    TRY(s.indptr.reserve((size_t)(N + 1) * 8));
+    TRY(s.indices.reserve((size_t)(nnz > 0 ? nnz : 1) * 4));
+    TRY(s.data.reserve((size_t)(nnz > 0 ? nnz : 1) * es));
+    DBGSOM_HIP_CHECK(hipMemcpyAsync(s.indptr.p, indptr_host, (size_t)(N + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (nnz > 0) {
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(s.indices.p, indices_host, (size_t)nnz * 4, hipMemcpyHostToDevice, c->stream));
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(s.data.p, data_host, (size_t)nnz * es, hipMemcpyHostToDevice, c->stream));
+    }
+    if (d < densify_below) {
+        TRY(s.own.reserve((size_t)N * dp * es));
+        TRY(launch_csr_densify(s.view(), x_dtype, N, d, dp, s.own.p, c->stream));
+        s.X = s.own.p;
+        TRY(finish_samples(c, s, false));
+        TRY(sync(c));
+        s.indptr.release(); s.indices.release(); s.data.release();
+        s.nnz = 0;
+        return DBGSOM_OK;
+    }
+    s.csr = true;
+    s.bdtype = x_dtype;
+    s.own.release(); s.x32.release(); s.planes.release();
+    s.planes_ready = false;
+    TRY(s.xx.reserve((size_t)N * 8));
+    return launch_csr_row_sqnorms(s.view(), x_dtype, N, s.xx.as<double>(), c->stream);
+}
+
+// the CSR search of `s` under the M x dp prototypes W (device) with norms ww: Wt is rebuilt from W first
+int csr_search(dbgsom_ctx *c, Samples &s, const double *W, const double *ww, DevBuf &wt, int64_t M, int k, int round_f32,
+               int64_t *idx, double *dist) {
+    const int64_t ldwt = csr_wt_ld(M);
+    TRY(wt.reserve((size_t)s.dp * ldwt * 8));
+    TRY(launch_transpose_weights(W, M, s.dp, s.dp, wt.as<double>(), ldwt, c->stream));
+    return launch_bmu_csr(s.view(), s.dtype, s.N, s.xx.as<double>(), wt.as<double>(), ldwt, M, ww, k, round_f32, idx,
+                          dist, c->stream);
+}
+int csr_search(dbgsom_ctx *c, Samples &s, const double *W, int64_t M, int k, int round_f32, int64_t *idx, double *dist) {
+    return csr_search(c, s, W, c->ww.as<double>(), c->wt, M, k, round_f32, idx, dist);
+}
+
 // BMU (k = 1) of the resident samples under Wb[cur] into idx[icur ^ 1] / dist, by policy
 int epoch_bmu(dbgsom_ctx *c, int64_t M, int round_f32) {
     Samples &s = c->xs;
@@ -952,6 +1022,15 @@ int epoch_bmu(dbgsom_ctx *c, int64_t M, int round_f32) {
     const double *W = c->Wb[c->cur].as<double>();
     c->last_hinted = false;
     c->last_deferred = false;
+    if (s.csr) {
+        c->last_filtered = false;
+        TRY(csr_search(c, s, W, M, 1, round_f32, out, c->dist.as<double>()));
+        c->icur ^= 1;
+        c->hint_valid = false;
+        c->last_idx_valid = true;
+        c->dist_bound_valid = false;
+        return DBGSOM_OK;
+    }
     if (filter_applies(c, M)) {
         const bool hint = (c->algorithm == DBGSOM_ALG_AUTO || c->algorithm == DBGSOM_ALG_FILTERED_HINT) &&
                           c->hint_valid && c->hintM <= M;
@@ -991,7 +1070,14 @@ int accumulate_and_reduce(dbgsom_ctx *c, const int64_t *idx, const double *kw, d
     int32_t *status = reinterpret_cast<int32_t *>(c->scal.as<char>() + 64);
     c->part_valid = false;
     const double *sw = c->has_weights ? c->sw.as<double>() : nullptr;
-    if (kw) {
+    if (s.csr) {
+        TRY(launch_accumulate_csr(s.view(), s.dtype, s.N, s.dp, idx, kw, gamma, sw, dist, M, c->sums.as<double>(), status,
+                                  kw == nullptr, c->acc_ws.p, c->acc_ws.cap, c->stream));
+        if (kw) {
+            hipLaunchKernelGGL(status_to_f64_kernel, dim3(1), dim3(1), 0, c->stream, status, c->sums.as<double>() + count);
+            TRY(launch_status("status_to_f64_kernel"));
+        }
+    } else if (kw) {
         if (sw)
             TRY(launch_accumulate_weighted(s.X, s.dtype, s.N, s.dp, s.dp, idx, kw, sw, dist, M, c->sums.as<double>(), status,
                                            c->acc_ws.p, c->acc_ws.cap, c->stream));
@@ -1035,6 +1121,23 @@ int accumulate_and_reduce(dbgsom_ctx *c, const int64_t *idx, const double *kw, d
     return run_allreduce(c, c->sums.as<double>(), count + 1);
 }
 
+// Workspace of the smoothing step.  CSR residents: carved out of the accumulate workspace behind its bucket order
+// when that is large enough -- its slab rows are dead once the sums are finalized, and both steps run one after
+// the other on the context's stream -- so that a wide map does not hold a second M x dp buffer for it.
+int smooth_ws(dbgsom_ctx *c, int64_t M, int64_t dp, void **ws, size_t *ws_bytes) {
+    const size_t need = smooth_workspace_bytes(M, dp);
+    const size_t head = align_up((size_t)c->xs.N * 4);
+    if (c->xs.csr && c->acc_ws.cap >= head + need) {
+        *ws = c->acc_ws.as<char>() + head;
+        *ws_bytes = c->acc_ws.cap - head;
+        return DBGSOM_OK;
+    }
+    TRY(c->sm_ws.reserve(need));
+    *ws = c->sm_ws.p;
+    *ws_bytes = c->sm_ws.cap;
+    return DBGSOM_OK;
+}
+
 // smoothing of the reduced sums: Wb[cur] -> Wb[cur ^ 1]; queues the small results D2H and waits
 int smooth_and_fetch(dbgsom_ctx *c, int64_t M, double sigma, int layout, int flags, double *W_new_host,
                      double *change_total_host, double *errors_host, double *activations_host,
@@ -1048,7 +1151,9 @@ int smooth_and_fetch(dbgsom_ctx *c, int64_t M, double sigma, int layout, int fla
     }
     const int nxt = c->cur ^ 1;
     TRY(c->Wb[nxt].reserve((size_t)M * dp * 8));
-    TRY(c->sm_ws.reserve(smooth_workspace_bytes(M, dp)));
+    void *sm_ws = nullptr;
+    size_t sm_ws_bytes = 0;
+    TRY(smooth_ws(c, M, dp, &sm_ws, &sm_ws_bytes));
     double *chg = c->scal.as<double>();
     double *sums = c->sums.as<double>();
     if (c->sums_sharded) {
@@ -1058,15 +1163,15 @@ int smooth_and_fetch(dbgsom_ctx *c, int64_t M, double sigma, int layout, int fla
         TRY(c->shard_gather.reserve((size_t)G * M * cb * 8));
         double *gather = c->shard_gather.as<double>();
         TRY(launch_smooth_block(mine, sums + (size_t)M * dp, sums + (size_t)M * dp + M, M, cb, dp, c->hop.as<float>(), sigma,
-                                layout, gather + (size_t)r * M * cb, c->sm_ws.p, c->sm_ws.cap, c->stream));
+                                layout, gather + (size_t)r * M * cb, sm_ws, sm_ws_bytes, c->stream));
         TRY(run_block_collective(c, DBGSOM_COLL_ALLGATHER, gather, M * cb));
-        TRY(launch_rowchange_blocks(gather, M, dp, cb, c->Wb[c->cur].as<double>(), c->Wb[nxt].as<double>(), chg, c->sm_ws.p,
+        TRY(launch_rowchange_blocks(gather, M, dp, cb, c->Wb[c->cur].as<double>(), c->Wb[nxt].as<double>(), chg, sm_ws,
                                     c->stream));
         c->sums_sharded = false;
         ++c->shard_epochs;
     } else {
         TRY(launch_smooth(sums, M, dp, c->hop.as<float>(), sigma, layout, c->Wb[c->cur].as<double>(),
-                          c->Wb[nxt].as<double>(), chg, c->sm_ws.p, c->sm_ws.cap, c->stream));
+                          c->Wb[nxt].as<double>(), chg, sm_ws, sm_ws_bytes, c->stream));
     }
     mark(c, 3);
     // the epoch's small results: one kernel writes them into mapped page-locked memory, one stream
@@ -1114,6 +1219,10 @@ int resident_bmu(dbgsom_ctx *c, const double *W_host, int64_t M, int k, int roun
     TRY(c->qidx.reserve((size_t)s.N * k * 8));
     TRY(c->qdist.reserve((size_t)s.N * k * 8));
     const double *W = c->Wb[c->cur].as<double>();
+    if (s.csr) {
+        c->last_k2_filtered = false;
+        return csr_search(c, s, W, M, k, round_f32, c->qidx.as<int64_t>(), c->qdist.as<double>());
+    }
     if (k == 1 && filter_applies(c, M)) {
         const bool hint = (c->algorithm == DBGSOM_ALG_AUTO || c->algorithm == DBGSOM_ALG_FILTERED_HINT) &&
                           c->hint_valid && c->hintM <= M;
@@ -1193,7 +1302,7 @@ int dbgsom_ctx_create(int device, dbgsom_ctx **out) {
     {&(c)->y, &(c)->hop, &(c)->hop_stage, &(c)->Wb[0], &(c)->Wb[1], &(c)->ww, &(c)->idx[0], &(c)->idx[1], &(c)->dist,  \
      &(c)->kw, &(c)->sums, &(c)->acc_ws, &(c)->sm_ws, &(c)->filt_ws, &(c)->scal, &(c)->qidx, &(c)->qdist, &(c)->red,  \
      &(c)->hist, &(c)->stage_dev, &(c)->part_order, &(c)->part_ws, &(c)->part_counts, &(c)->shiftb, &(c)->shard_send,    \
-     &(c)->shard_gather, &(c)->sw, &(c)->wh_order, &(c)->wh_ws, &(c)->sc_ws, &(c)->sc_x, &(c)->sc_w, &(c)->sc_p, &(c)->sc_code, &(c)->sc_proba, &(c)->sc_cnt}
+     &(c)->shard_gather, &(c)->sw, &(c)->wh_order, &(c)->wh_ws, &(c)->sc_ws, &(c)->sc_x, &(c)->sc_w, &(c)->sc_p, &(c)->sc_code, &(c)->sc_proba, &(c)->sc_cnt, &(c)->wt}
 
 int dbgsom_ctx_destroy(dbgsom_ctx *c) {
     if (!c) return DBGSOM_OK;
@@ -1251,6 +1360,9 @@ int dbgsom_ctx_set_option(dbgsom_ctx *c, const char *name, int64_t v) {
     } else if (!strcmp(name, "max_mean_candidates")) {
         DBGSOM_REQUIRE(v >= 1, "max_mean_candidates must be >= 1");
         c->max_mean_candidates = v;
+    } else if (!strcmp(name, "csr_densify_below")) {
+        DBGSOM_REQUIRE(v >= 0, "csr_densify_below must be >= 0 (0 = CSR input always stays CSR)");
+        c->csr_densify_below = v;
     } else {
         set_error("dbgsom_ctx_set_option: unknown option '%s'", name);
         return DBGSOM_EINVAL;
@@ -1280,6 +1392,9 @@ int dbgsom_ctx_get_option(dbgsom_ctx *c, const char *name, int64_t *v) {
     else if (!strcmp(name, "max_mean_candidates")) *v = c->max_mean_candidates;
     else if (!strcmp(name, "sc_chunk_rows")) *v = c->sc_chunk_rows;
     else if (!strcmp(name, "sc_cap")) *v = c->sc_cap;
+    else if (!strcmp(name, "csr_densify_below")) *v = c->csr_densify_below;
+    else if (!strcmp(name, "resident_csr")) *v = (c->xs.dtype >= 0 && c->xs.csr) ? 1 : 0;
+    else if (!strcmp(name, "resident_nnz")) *v = (c->xs.dtype >= 0 && c->xs.csr) ? c->xs.nnz : 0;
     else if (!strcmp(name, "n_samples")) *v = c->xs.dtype < 0 ? 0 : c->xs.N;
     else if (!strcmp(name, "features")) *v = c->xs.dtype < 0 ? 0 : c->xs.d;
     else if (!strcmp(name, "padded_features")) *v = c->xs.dtype < 0 ? 0 : c->xs.dp;
@@ -1300,8 +1415,9 @@ int dbgsom_ctx_get_option(dbgsom_ctx *c, const char *name, int64_t *v) {
     else if (!strcmp(name, "w_row_writes")) *v = c->w_row_writes;
     else if (!strcmp(name, "w_row_reads")) *v = c->w_row_reads;
     else if (!strcmp(name, "device_bytes")) {
-        size_t tot = c->xs.own.cap + c->xs.x32.cap + c->xs.xx.cap + c->xs.planes.cap + c->xq.own.cap + c->xq.x32.cap +
-                     c->xq.xx.cap + c->xq.planes.cap;
+        size_t tot = 0;
+        for (const Samples *q : {&c->xs, &c->xq})
+            tot += q->own.cap + q->x32.cap + q->xx.cap + q->planes.cap + q->indptr.cap + q->indices.cap + q->data.cap;
         DevBuf *bufs[] = CTX_DEVBUFS(c);
         for (DevBuf *b : bufs) tot += b->cap;
         *v = (int64_t)tot;
@@ -1322,6 +1438,14 @@ int dbgsom_ctx_stream(dbgsom_ctx *c, void **stream) {
 // ------------------------------------------------------------------------------------------
 // residency
 // ------------------------------------------------------------------------------------------
+// the allocation policy of every buffer of the context (DevBuf::tight): tight for CSR residents
+static void set_tight(dbgsom_ctx *c, bool tight) {
+    DevBuf *bufs[] = CTX_DEVBUFS(c);
+    for (DevBuf *b : bufs) b->tight = tight;
+    for (Samples *q : {&c->xs, &c->xq})
+        for (DevBuf *b : {&q->own, &q->x32, &q->xx, &q->planes, &q->indptr, &q->indices, &q->data}) b->tight = tight;
+}
+
 static void reset_training_state(dbgsom_ctx *c) {
     c->hint_valid = c->last_idx_valid = c->part_valid = false;
     c->has_labels = false;
@@ -1346,10 +1470,24 @@ static void reset_training_state(dbgsom_ctx *c) {
 int dbgsom_ctx_load(dbgsom_ctx *c, const void *X_host, int x_dtype, int64_t N, int64_t d, int storage) {
     CTX_CHECK(c);
     reset_training_state(c);
+    set_tight(c, false);
     c->xs.dtype = -1;
+    c->xs.indptr.release(); c->xs.indices.release(); c->xs.data.release();
     const int rc = place_host_samples(c, c->xs, X_host, x_dtype, N, d, storage);
     if (rc != DBGSOM_OK) { (void)hipStreamSynchronize(c->stream); c->xs.dtype = -1; return rc; }
     return sync(c);
+}
+
+int dbgsom_ctx_load_csr(dbgsom_ctx *c, const int64_t *indptr_host, const int32_t *indices_host, const void *data_host,
+                        int x_dtype, int64_t N, int64_t d, int64_t nnz) {
+    CTX_CHECK(c);
+    reset_training_state(c);
+    c->xs.dtype = -1;
+    set_tight(c, d >= c->csr_densify_below);
+    int rc = place_host_csr(c, c->xs, indptr_host, indices_host, data_host, x_dtype, N, d, nnz, c->csr_densify_below);
+    if (rc == DBGSOM_OK) rc = sync(c);
+    if (rc != DBGSOM_OK) { (void)hipStreamSynchronize(c->stream); c->xs.dtype = -1; c->xs.csr = false; }
+    return rc;
 }
 
 int dbgsom_ctx_load_device(dbgsom_ctx *c, const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx) {
@@ -1357,11 +1495,14 @@ int dbgsom_ctx_load_device(dbgsom_ctx *c, const void *X_dev, int x_dtype, int64_
     DBGSOM_REQUIRE(valid_dtype(x_dtype), "x_dtype must be DBGSOM_F32/F64/BF16");
     DBGSOM_REQUIRE(X_dev && N >= 1 && d >= 1 && ldx >= d && N < 0x7fffffff, "bad samples");
     reset_training_state(c);
+    set_tight(c, false);
     Samples &s = c->xs;
     const size_t es = dtype_size(x_dtype);
     const int64_t dp = pad16(d);
     s.dtype = -1;
     s.N = N; s.d = d; s.dp = dp;
+    s.csr = false; s.nnz = 0;
+    s.indptr.release(); s.indices.release(); s.data.release();
     if (ldx == dp && d == dp && is_aligned(X_dev, 16)) {
         s.own.release();
         s.X = X_dev;  // borrowed
@@ -1389,6 +1530,11 @@ int dbgsom_ctx_read_samples(dbgsom_ctx *c, const int64_t *rows_host, int64_t n, 
     int64_t *ids = c->stage_dev.as<int64_t>();
     double *rows = reinterpret_cast<double *>(c->stage_dev.as<char>() + align_up((size_t)n * 8));
     DBGSOM_HIP_CHECK(hipMemcpyAsync(ids, rows_host, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    if (s.csr) {   // densified rows
+        TRY(launch_csr_rows_to_f64(s.view(), s.dtype, ids, n, s.d, rows, c->stream));
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(out_host, rows, (size_t)n * s.d * 8, hipMemcpyDeviceToHost, c->stream));
+        return sync(c);
+    }
     if (s.dtype == DBGSOM_F32)
         hipLaunchKernelGGL(rows_to_f64_kernel<float>, dim3((unsigned)n), dim3(256), 0, c->stream, (const float *)s.X, s.dp, ids, n, s.d, rows);
     else if (s.dtype == DBGSOM_F64)
@@ -1617,19 +1763,18 @@ int dbgsom_ctx_bmu(dbgsom_ctx *c, const double *W_host, int64_t M, int k, int ro
     return sync(c);
 }
 
-int dbgsom_ctx_bmu_query(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d, const double *W_host,
-                         int64_t M, int k, int round_f32, int64_t *idx_host, double *dist_host) {
-    CTX_CHECK(c);
-    DBGSOM_REQUIRE(valid_dtype(x_dtype), "x_dtype must be DBGSOM_F32/F64/BF16");
-    DBGSOM_REQUIRE(Xq_host && W_host && idx_host && dist_host && Nq >= 0 && d >= 1 && M >= 1 && (k == 1 || k == 2) && M >= k,
-                   "bad arguments");
-    if (Nq == 0) return DBGSOM_OK;
+// the query search on host samples: dense rows (Xq_host), or CSR arrays (indptr_host != nullptr)
+static int bmu_query_impl(dbgsom_ctx *c, const void *Xq_host, const int64_t *indptr_host, const int32_t *indices_host,
+                          int64_t nnz, int x_dtype, int64_t Nq, int64_t d, const double *W_host, int64_t M, int k,
+                          int round_f32, int64_t *idx_host, double *dist_host) {
     Samples &s = c->xq;
-    DevBuf Wq, wwq, iq, dq, fws;  // query-sized scratch; independent of the training state
+    DevBuf Wq, wwq, iq, dq, fws, wtq;  // query-sized scratch; independent of the training state
     int rc = DBGSOM_OK;
     const int64_t dp = pad16(d);
     do {
-        if ((rc = place_host_samples(c, s, Xq_host, x_dtype, Nq, d, x_dtype))) break;
+        if (indptr_host) rc = place_host_csr(c, s, indptr_host, indices_host, Xq_host, x_dtype, Nq, d, nnz, c->csr_densify_below);
+        else rc = place_host_samples(c, s, Xq_host, x_dtype, Nq, d, x_dtype);
+        if (rc) break;
         if ((rc = Wq.reserve((size_t)M * dp * 8))) break;
         if ((rc = wwq.reserve((size_t)M * 8))) break;
         if ((rc = iq.reserve((size_t)Nq * k * 8))) break;
@@ -1637,9 +1782,11 @@ int dbgsom_ctx_bmu_query(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_
         if ((rc = upload_padded(c, Wq.p, W_host, M, d, dp, 8))) break;
         if ((rc = launch_row_sqnorms(Wq.p, DBGSOM_F64, M, dp, dp, wwq.as<double>(), c->stream))) break;
         // large k = 1 queries go through the filter (the digit planes of a one-off X cost a pass over it)
-        const bool filt = k == 1 && c->algorithm != DBGSOM_ALG_EXACT && Nq >= c->filter_min_query_rows &&
+        const bool filt = !s.csr && k == 1 && c->algorithm != DBGSOM_ALG_EXACT && Nq >= c->filter_min_query_rows &&
                           filter_shape_ok(s, M);
-        if (filt) {
+        if (s.csr) {
+            rc = csr_search(c, s, Wq.as<double>(), wwq.as<double>(), wtq, M, k, round_f32, iq.as<int64_t>(), dq.as<double>());
+        } else if (filt) {
             if ((rc = ensure_planes(c, s))) break;
             if ((rc = fws.reserve_zeroed(dbgsom_bmu_filtered_workspace_bytes(Nq, dp, M), c->stream))) break;
             int stride = c->seed_stride, planes = 1;
@@ -1658,9 +1805,32 @@ int dbgsom_ctx_bmu_query(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_
         if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; }
     } while (0);
     if (rc != DBGSOM_OK) (void)hipStreamSynchronize(c->stream);
-    Wq.release(); wwq.release(); iq.release(); dq.release(); fws.release();
-    if (Nq * dp * (int64_t)dtype_size(x_dtype) > ((int64_t)256 << 20)) s.release();  // do not sit on a large one-off batch
+    Wq.release(); wwq.release(); iq.release(); dq.release(); fws.release(); wtq.release();
+    const int64_t held = s.csr ? s.nnz * (4 + (int64_t)dtype_size(x_dtype)) + Nq * 16 : Nq * dp * (int64_t)dtype_size(x_dtype);
+    if (held > ((int64_t)256 << 20)) s.release();  // do not sit on a large one-off batch
     return rc;
+}
+
+int dbgsom_ctx_bmu_query(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d, const double *W_host,
+                         int64_t M, int k, int round_f32, int64_t *idx_host, double *dist_host) {
+    CTX_CHECK(c);
+    DBGSOM_REQUIRE(valid_dtype(x_dtype), "x_dtype must be DBGSOM_F32/F64/BF16");
+    DBGSOM_REQUIRE(Xq_host && W_host && idx_host && dist_host && Nq >= 0 && d >= 1 && M >= 1 && (k == 1 || k == 2) && M >= k,
+                   "bad arguments");
+    if (Nq == 0) return DBGSOM_OK;
+    return bmu_query_impl(c, Xq_host, nullptr, nullptr, 0, x_dtype, Nq, d, W_host, M, k, round_f32, idx_host, dist_host);
+}
+
+int dbgsom_ctx_bmu_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const int32_t *indices_host, const void *data_host,
+                             int x_dtype, int64_t Nq, int64_t d, int64_t nnz, const double *W_host, int64_t M, int k,
+                             int round_f32, int64_t *idx_host, double *dist_host) {
+    CTX_CHECK(c);
+    DBGSOM_REQUIRE(x_dtype == DBGSOM_F32 || x_dtype == DBGSOM_F64, "CSR data must be DBGSOM_F32 or DBGSOM_F64");
+    DBGSOM_REQUIRE(indptr_host && W_host && idx_host && dist_host && Nq >= 0 && d >= 1 && nnz >= 0 && M >= 1 &&
+                   (k == 1 || k == 2) && M >= k, "bad arguments");
+    if (Nq == 0) return dbgsom_csr_check(indptr_host, indices_host, 0, d, nnz);
+    return bmu_query_impl(c, data_host, indptr_host, indices_host, nnz, x_dtype, Nq, d, W_host, M, k, round_f32, idx_host,
+                          dist_host);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1929,6 +2099,7 @@ int dbgsom_ctx_column_sums(dbgsom_ctx *c, const void *mean_host, void *out_host)
     TRY(loaded(c, __func__));
     DBGSOM_REQUIRE(out_host, "null pointer");
     Samples &s = c->xs;
+    if (s.csr) { set_error("dbgsom_ctx_column_sums: the resident samples are CSR (take the column moments from the stored entries on the host)"); return DBGSOM_ESTATE; }
     DBGSOM_REQUIRE(s.dtype == DBGSOM_F32 || s.dtype == DBGSOM_F64, "float32 / float64 resident samples only");
     const size_t es = dtype_size(s.dtype);
     TRY(c->stage_dev.reserve((size_t)2 * s.dp * es + 512));
@@ -1949,6 +2120,7 @@ int dbgsom_ctx_weighted_column_sums(dbgsom_ctx *c, const double *mean_host, doub
     DBGSOM_REQUIRE(out_host, "null pointer");
     if (!c->has_weights) { set_error("weighted column sums requested but no weights attached (dbgsom_ctx_set_sample_weight)"); return DBGSOM_ESTATE; }
     Samples &s = c->xs;
+    if (s.csr) { set_error("dbgsom_ctx_weighted_column_sums: the resident samples are CSR (take the column moments from the stored entries on the host)"); return DBGSOM_ESTATE; }
     const size_t vec = align_up((size_t)s.dp * 8);
     TRY(c->stage_dev.reserve(2 * vec + dbgsom_weighted_column_sums_workspace_bytes(s.dp)));
     double *mean_dev = c->stage_dev.as<double>();
@@ -2029,7 +2201,11 @@ int dbgsom_ctx_node_statistics(dbgsom_ctx *c, const double *W_host, int64_t M, i
     TRY(c->acc_ws.reserve(acc_ws_bytes(c, M)));
     c->part_valid = false;
     c->sumsM = 0;
-    if (c->has_weights)   // K = sum w term, a = sum w
+    if (s.csr)
+        TRY(launch_accumulate_csr(s.view(), s.dtype, s.N, s.dp, c->qidx.as<int64_t>(), c->kw.as<double>(), 0.0,
+                                  c->has_weights ? c->sw.as<double>() : nullptr, c->qdist.as<double>(), M,
+                                  c->sums.as<double>(), nullptr, false, c->acc_ws.p, c->acc_ws.cap, c->stream));
+    else if (c->has_weights)   // K = sum w term, a = sum w
         TRY(launch_accumulate_weighted(s.X, s.dtype, s.N, s.dp, s.dp, c->qidx.as<int64_t>(), c->kw.as<double>(),
                                        c->sw.as<double>(), c->qdist.as<double>(), M, c->sums.as<double>(), nullptr, c->acc_ws.p,
                                        c->acc_ws.cap, c->stream));
@@ -2135,6 +2311,7 @@ int dbgsom_ctx_subset_create(dbgsom_ctx *c, int64_t neuron, dbgsom_ctx **child_o
     TRY(loaded(c, __func__));
     DBGSOM_REQUIRE(child_out, "null pointer");
     *child_out = nullptr;
+    if (c->xs.csr) { set_error("dbgsom_ctx_subset_create: the resident samples are CSR (select the rows on the host and load them)"); return DBGSOM_ESTATE; }
     if (!c->part_valid) { set_error("dbgsom_ctx_subset_create: call dbgsom_ctx_partition first"); return DBGSOM_ESTATE; }
     DBGSOM_REQUIRE(neuron >= 0 && neuron < c->partM, "neuron out of range");
     Samples &s = c->xs;

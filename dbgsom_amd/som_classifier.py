@@ -14,6 +14,7 @@ from sklearn.base import ClassifierMixin, TransformerMixin
 from sklearn.utils import check_array, check_X_y
 from sklearn.utils.validation import check_is_fitted
 
+from .backend import is_sparse
 from .base import BaseSom
 
 
@@ -23,8 +24,9 @@ class SomClassifier(BaseSom, TransformerMixin, ClassifierMixin):
     def _check_input_data(self, X, y):
         # (X's finite check rides on the device's column sums when it can; y is checked here as ever)
         self._finite_deferred = self._finite_check_on_device()
-        X, y = check_X_y(X=X, y=y, ensure_min_samples=4, dtype=[np.float64, np.float32],
+        X, y = check_X_y(X=X, y=y, ensure_min_samples=4, dtype=[np.float64, np.float32], accept_sparse="csr",
                          **self._finite_kw(not self._finite_deferred))
+        X = self._check_sparse_input(X)
         return X, y
 
     def _label_prototypes(self, X, y) -> None:
@@ -64,18 +66,19 @@ class SomClassifier(BaseSom, TransformerMixin, ClassifierMixin):
 
     def predict(self, X) -> np.ndarray:
         check_is_fitted(self)
-        X = check_array(X, dtype=[np.float64, np.float32])
+        X = check_array(X, dtype=[np.float64, np.float32], accept_sparse="csr")
         return self.classes_[np.argmax(self.predict_proba(X=X), axis=1)]
 
     def predict_proba(self, X) -> np.ndarray:
         """Class probabilities: sparse code over the prototypes times the prototypes' class
         frequencies, rows normalised (SomClassifier.py:178-220)."""
         check_is_fitted(self)
-        X = check_array(X, dtype=[np.float64, np.float32])
+        X = check_array(X, dtype=[np.float64, np.float32], accept_sparse="csr")
         if self.vertical_growth:
             _, winners = self._get_winning_neurons(X, n_bmu=1)
             rows = []
-            for sample, w in zip(X, winners):
+            for i, w in enumerate(winners):
+                sample = X[i].toarray()[0] if is_sparse(X) else X[i]
                 attrs = self.som_.nodes[self.neurons_[w]]
                 if "som" in attrs:
                     # (a child map knows the classes of its Voronoi set only, by this map's class CODES --
@@ -88,5 +91,4 @@ class SomClassifier(BaseSom, TransformerMixin, ClassifierMixin):
                     rows.append(attrs["probabilities"])
             return np.array(rows)
         # the code never leaves the backend: it returns (code @ P) normalised per row
-        return self._engine().sparse_code(self.weights_, X, P=self._extract_values_from_graph("probabilities"),
-                                           n_jobs=self.n_jobs)
+        return self._sparse_code(X, P=self._extract_values_from_graph("probabilities"))

@@ -20,8 +20,9 @@ class SomVQ(BaseSom, ClusterMixin, TransformerMixin):
         # float32 is kept as float32 (the device stores it as such); anything else -> float64
         # (the finite check rides on the device's column sums when it can: BaseSom._assert_finite_from_moments)
         self._finite_deferred = self._finite_check_on_device()
-        X = check_array(array=X, ensure_min_samples=4, dtype=[np.float64, np.float32],
+        X = check_array(array=X, ensure_min_samples=4, dtype=[np.float64, np.float32], accept_sparse="csr",
                         **self._finite_kw(not self._finite_deferred))
+        X = self._check_sparse_input(X)
         return X, None  # any y is ignored
 
     def _label_prototypes(self, X, y=None) -> None:
@@ -33,7 +34,7 @@ class SomVQ(BaseSom, ClusterMixin, TransformerMixin):
         if not self._is_resident(X):
             # integer / half input is converted like the reference's engine does (sklearn's
             # NearestNeighbors); float32 stays float32
-            X = check_array(X, dtype=[np.float64, np.float32])
+            X = check_array(X, dtype=[np.float64, np.float32], accept_sparse="csr")
         _, labels = self._get_winning_neurons(X, n_bmu=1)
         return labels
 

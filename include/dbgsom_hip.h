@@ -135,6 +135,40 @@ int dbgsom_accumulate_weighted(const void *X_dev, int x_dtype, int64_t N, int64_
                                const double *dist_dev, int64_t M, double *sums_dev, int32_t *status_dev,
                                void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* ---- CSR samples (csr.hip) ----------------------------------------------------------------------------
+ * Canonical CSR: indptr int64 (N + 1, indptr[0] = 0, indptr[N] = nnz, monotone), indices int32 in [0, d),
+ * strictly ascending within a row (no duplicates), data float32 or float64; explicitly stored zeros are allowed.
+ * Every kernel walks the stored entries of a row in ascending column order with the arithmetic of its dense
+ * namesake, so its results are the dense kernel's on the densified matrix BIT FOR BIT: a term x_k = 0 leaves a
+ * chain acc = fma(x_k, w_k, acc) and an ordered sum where they were.
+ *
+ * dbgsom_csr_check: host arrays, needs no GPU; DBGSOM_EINVAL and a message naming the first fault.
+ * dbgsom_csr_row_sqnorms: xx_i, the chain of dbgsom_row_sqnorms over the stored entries.
+ * dbgsom_csr_transpose_weights: Wt (d x ldwt float64, ldwt = dbgsom_csr_wt_ld(M), zeros behind column M) from
+ *   W (M x ldw): the layout the search reads -- one stored entry, one contiguous run of prototypes.
+ * dbgsom_bmu_csr: dbgsom_bmu for CSR samples; ww_dev from dbgsom_row_sqnorms on W.
+ * dbgsom_csr_densify: the padded dense rows (N x ld, X's own dtype).
+ * dbgsom_accumulate_csr: dbgsom_accumulate (sw_dev = NULL) / dbgsom_accumulate_weighted for CSR samples; sums_dev
+ *   holds M*(d+3) float64 with the d given here (the context passes its padded feature count).  Bit-identical to
+ *   the dense call wherever that one adds a column in list order: rows of at least 256 16-byte pieces (padded
+ *   d >= 1024 for float32, >= 512 for float64); narrower dense rows are summed over row lanes. */
+int dbgsom_csr_check(const int64_t *indptr_host, const int32_t *indices_host, int64_t N, int64_t d, int64_t nnz);
+int dbgsom_csr_row_sqnorms(const int64_t *indptr_dev, const void *data_dev, int x_dtype, int64_t N, double *out_dev,
+                           void *stream);
+int64_t dbgsom_csr_wt_ld(int64_t M);
+int dbgsom_csr_transpose_weights(const double *W_dev, int64_t M, int64_t d, int64_t ldw, double *Wt_dev, int64_t ldwt,
+                                 void *stream);
+int dbgsom_bmu_csr(const int64_t *indptr_dev, const int32_t *indices_dev, const void *data_dev, int x_dtype, int64_t N,
+                   const double *xx_dev, const double *Wt_dev, int64_t ldwt, int64_t M, const double *ww_dev, int k,
+                   int round_f32, int64_t *idx_dev, double *dist_dev, void *stream);
+int dbgsom_csr_densify(const int64_t *indptr_dev, const int32_t *indices_dev, const void *data_dev, int x_dtype,
+                       int64_t N, int64_t d, int64_t ld, void *out_dev, void *stream);
+size_t dbgsom_accumulate_csr_workspace_bytes(int64_t N, int64_t d, int64_t M);
+int dbgsom_accumulate_csr(const int64_t *indptr_dev, const int32_t *indices_dev, const void *data_dev, int x_dtype,
+                          int64_t N, int64_t d, const int64_t *idx_dev, const double *kw_dev, const double *sw_dev,
+                          const double *dist_dev, int64_t M, double *sums_dev, int32_t *status_dev,
+                          void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* Neighbourhood-weighted batch update: steps 3-5 of BaseSom._update_weights
  * BaseSom.py:506-522 with _calculate_gaussian_neighborhood BaseSom.py:525-531.
  *   c_j = S_j / K_j placed per `layout`;  h = exp(-(hop^2 / (2 sigma^2)));
@@ -295,8 +329,9 @@ int dbgsom_ctx_destroy(dbgsom_ctx *ctx);
  * "filter_min_query_rows", "max_mean_candidates", "graph" (reserved: accepted and stored, no effect in this
  * build -- an epoch is 22-23 back-to-back launches on the context's stream and two forked ones), "refine" (0 off,
  * 1 on, 2 by measurement: the per-sample refinement in front of the exact stage), "defer" (with the refinement: the
- * distance of a sample it decided is evaluated inside the epoch's sums kernel; off by default), "shard_smooth".
- * Readable besides those: "refined", "defer_epochs" (epochs whose sums kernel evaluated distances), "shard_epochs", "n_samples", "features", "padded_features", "prototypes",
+ * distance of a sample it decided is evaluated inside the epoch's sums kernel; off by default), "shard_smooth",
+ * "csr_densify_below" (see dbgsom_ctx_load_csr).
+ * Readable besides those: "resident_csr", "resident_nnz", "refined", "defer_epochs" (epochs whose sums kernel evaluated distances), "shard_epochs", "n_samples", "features", "padded_features", "prototypes",
  * "planes_cached", "planes_used" / "planes_next" (0 = no sweep), "seed_mode", "prune_retry", "hint_valid",
  * "filter_backoff", "plane_hold", "device_bytes", and the
  * PCIe traffic of the prototypes since the context was created: "w_upload_calls" / "w_upload_bytes"
@@ -312,6 +347,18 @@ int dbgsom_ctx_stream(dbgsom_ctx *ctx, void **stream);
  * an extension, the reference has no bfloat16). */
 int dbgsom_ctx_load(dbgsom_ctx *ctx, const void *X_host, int x_dtype, int64_t N, int64_t d,
                     int storage);
+/* The same for samples in canonical CSR form (see dbgsom_csr_check, which runs first: DBGSOM_EINVAL on a fault).
+ * Below option "csr_densify_below" features (default 1024, 0 = never) the rows are expanded on the device into
+ * the ordinary resident form and every call behaves as after dbgsom_ctx_load of the dense matrix.  At and above
+ * it the data stays CSR (option "resident_csr" reads 1; nothing of size N x d is allocated): the epoch, the
+ * searches and the reductions run the CSR kernels -- all-pairs search, no candidate pruning -- with the results
+ * of the dense kernels on the densified matrix bit for bit; everything behind the per-neuron sums is shared.
+ * A context with a CSR resident allocates its buffers without head room and runs the smoothing inside the
+ * accumulate workspace: it holds less than the CSR arrays, Wt, two W buffers, those two workspaces and 64 bytes per row.
+ * Not available on a CSR resident (DBGSOM_ESTATE): dbgsom_ctx_subset_create, dbgsom_ctx_column_sums,
+ * dbgsom_ctx_weighted_column_sums; bfloat16 storage is refused (DBGSOM_EINVAL). */
+int dbgsom_ctx_load_csr(dbgsom_ctx *ctx, const int64_t *indptr_host, const int32_t *indices_host,
+                        const void *data_host, int x_dtype, int64_t N, int64_t d, int64_t nnz);
 /* Adopt samples that already live in HBM on the context's device (rows of ldx elements).  Borrowed
  * without a copy when ldx is a multiple of 16 features that covers d and the rows are 16-byte
  * aligned with zeros behind column d; copied (padded) otherwise.  The caller keeps the memory alive
@@ -415,6 +462,12 @@ int dbgsom_ctx_bmu(dbgsom_ctx *ctx, const double *W_host, int64_t M, int k, int 
 int dbgsom_ctx_bmu_query(dbgsom_ctx *ctx, const void *Xq_host, int x_dtype, int64_t Nq,
                          int64_t d, const double *W_host, int64_t M, int k, int round_f32,
                          int64_t *idx_host, double *dist_host);
+
+/* the same on CSR samples (the rule of dbgsom_ctx_load_csr decides between the CSR search and expansion) */
+int dbgsom_ctx_bmu_query_csr(dbgsom_ctx *ctx, const int64_t *indptr_host, const int32_t *indices_host,
+                             const void *data_host, int x_dtype, int64_t Nq, int64_t d, int64_t nnz,
+                             const double *W_host, int64_t M, int k, int round_f32, int64_t *idx_host,
+                             double *dist_host);
 
 /* ---- sparse coding: BaseSom.transform / SomClassifier.predict_proba (BaseSom.py:241-268,
  * SomClassifier.py:178-220) ------------------------------------------------------------------------
