@@ -3,7 +3,8 @@
 ``HipBackend`` is a thin caller of the context level of the C ABI (``include/dbgsom_hip.h``,
 ``dbgsom_ctx_*``): NumPy arrays in, NumPy arrays out.  Everything else -- device memory, feature
 padding, bfloat16 storage, digit planes, the choice of BMU search, previous winners as seeds,
-device-resident prototypes -- lives behind that boundary in ``csrc/engine.hip``.  PyTorch appears
+device-resident prototypes -- lives behind that boundary in ``csrc/engine.hip`` (the policy of the filtered
+search in ``csrc/search_policy.h``, host-only and replayable on the CPU).  PyTorch appears
 in exactly one place: ``torch.distributed`` (backend ``nccl`` = RCCL over xGMI) supplies the one
 all-reduce of the per-prototype sums per epoch, plugged into the context as a callback.  There is
 no CPU fallback: constructing a ``HipBackend`` without the built library or without a GPU raises.
@@ -320,13 +321,15 @@ class HipBackend(HotPathBackend):
 
     name = "hip"
 
-    # the filtered search pays off once the all-pairs float64 work is large (mirrors engine.hip)
+    # the filtered search pays off once the all-pairs float64 work is large (mirrors csrc/search_policy.h;
+    # tests/test_search_policy_cpu.py checks every mirrored value against the header)
     FILTER_MIN_PROTOTYPES = 129
+    FILTER_MAX_FEATURES = 43690
     FILTER_MAX_MEAN_CANDIDATES = 320
     FILTER_MIN_QUERY_ROWS = 32768
-    # the PRIOR of the engine's search policy (engine.hip: adapt_arms): what an arm that has never been timed is
-    # priced at; arms that have run clean are compared by the engine's clock (arm_ms()).  Mirrored here only for
-    # the test of the prior on small inputs, where every epoch copies results to the host and nothing is timed.
+    # the PRIOR of the engine's search policy (search_policy.h: SearchPolicy::adapt_arms): what an arm that has never
+    # been timed is priced at; arms that have run clean are compared by the engine's clock (arm_ms()).  Mirrored here
+    # only for the test of the prior on small inputs, where every epoch copies results to the host and nothing is timed.
     SWEEP_COST = {1: 0.35, 2: 1.0, 3: 1.96}
     LIST_COST = 12.5
     PRUNE_PASS_COST = 60.0
@@ -702,7 +705,7 @@ class HipBackend(HotPathBackend):
     def query_filter_applies(self, N, d, M, k=1):
         """Whether a k-BMU query on N other samples would go through the filtered search."""
         return (k == 1 and self.algorithm != "exact" and N >= self._get("filter_min_query_rows")
-                and self.FILTER_MIN_PROTOTYPES <= M <= _native.MAX_PROTOTYPES and d <= 43690)
+                and self.FILTER_MIN_PROTOTYPES <= M <= _native.MAX_PROTOTYPES and d <= self.FILTER_MAX_FEATURES)
 
     # -- sparse coding --------------------------------------------------------------------------
     sc_chunk_rows = property(lambda self: self._get("sc_chunk_rows"), lambda self, v: self._set("sc_chunk_rows", v))
@@ -903,14 +906,20 @@ class HipBackend(HotPathBackend):
         return {k: self._get(k) for k in keys}
 
     def plane_cost(self, p, mean, M):
-        """Cost model of the engine's policy (engine.hip) for `p` digit planes of the candidate
-        sweep and candidate lists of `mean` entries; p = 0: no sweep, candidates from the triangle
-        inequality (one pass over the top digit plane of X and an M x M matrix of prototype gaps)."""
+        """Cost model of the engine's policy (csrc/search_policy.h, seeds = the previous winners) for `p` digit
+        planes of the candidate sweep and candidate lists of `mean` entries; p = 0: no sweep, candidates from the
+        triangle inequality (one pass over the top digit plane of X and an M x M matrix of prototype gaps)."""
+        return self.arm_cost(p, mean, M, self._N, self.padded_features)
+
+    @classmethod
+    def arm_cost(cls, p, mean, M, N, dp):
+        """plane_cost for N resident rows of dp padded features: SearchPolicy::model_cost(2, p, mean, M, N, dp),
+        term for term (tests/test_search_policy_cpu.py holds the two together)."""
         if p == 0:
-            launches = 25.0 / (2.8 * max(self._N, 1) * self.padded_features / (1.0e6 * 784.0))
-            return (self.PRUNE_PASS_COST + self.SWEEP_COST[1] * M * 9.0 * M / max(self._N, 1) + launches
-                    + self.LIST_COST * mean)
-        return self.SWEEP_COST[p] * M + self.LIST_COST * mean
+            launches = 25.0 / (2.8 * (float(max(N, 1)) * dp) / (1.0e6 * 784.0))
+            return (cls.PRUNE_PASS_COST + cls.SWEEP_COST[1] * M * 9.0 * M / max(N, 1) + launches
+                    + cls.LIST_COST * mean)
+        return cls.SWEEP_COST[p] * M + cls.LIST_COST * mean
 
     # -- f-1 .. f-3: reductions that keep the N-sized arrays in HBM -----------------------------
     def column_moments(self):

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "common.h"
+#include "search_policy.h"
 
 namespace dbgsom {
 
@@ -207,24 +208,6 @@ size_t dbgsom_bmu_filtered_workspace_bytes(int64_t N, int64_t d, int64_t M);
 
 namespace {
 
-constexpr int64_t FILTER_MIN_PROTOTYPES = 129;  // at or below 128 one chunk of the all-pairs kernel is cheaper (measured)
-constexpr int64_t FILTER_MAX_FEATURES = 43690;  // int32 digit-product accumulators: 3 x 128 x 128 x d < 2^31
-constexpr int FILTER_BACKOFF = 8;
-// epochs an arm is kept before its alternatives get another look: a map in training changes (early,
-// nearly collapsed maps want a fine sweep, organised ones the coarse one), and only running an arm
-// tells how long its lists are; a look costs one epoch of an arm that could at best be cheaper
-constexpr int PLANES_REPROBE = 16;
-// cost model of the candidate sweep (per prototype, in units of the three-product sweep) against a
-// list entry of the exact stage -- measured at C4 with this build's kernels: one product 1.00 ms,
-// three 2.87 ms per 1024 prototypes; exact stage 1.16 ms per 33 list entries
-const double SWEEP_COST[4] = {0.0, 0.35, 1.0, 1.96};
-constexpr double LIST_COST = 12.5;
-// arm 0 of the policy: no sweep, candidates from the triangle inequality (filter.hip 2c).  In the same
-// units: one pass over the X plane ~ 170 prototypes of the one-product sweep (C4: 0.17 of 1.0 ms per
-// 1024), plus the M x M gap matrix (three products, a third of the sweep's rate: ~ 9 M / N sweeps)
-constexpr double PRUNE_PASS_COST = 60.0;
-constexpr int64_t PRUNE_MAX_M = 8192;
-
 struct Samples {  // one resident sample set (training samples, or a query batch)
     int dtype = -1;            // storage dtype in HBM
     int64_t N = 0, d = 0, dp = 0;
@@ -251,37 +234,19 @@ struct dbgsom_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     // options
-    int algorithm = DBGSOM_ALG_AUTO;
-    int sweep_planes = 0;
-    int seed_stride = 0;
     int timing = 0;
     int use_graph = 0;
-    // per-sample refinement in front of the exact stage (filter.hip 2d): 0 = off, 1 = on, 2 = by measurement
-    // (per arm of the search policy, once it has settled on the arm: the first training epochs are timed with and
-    // without it -- wall clock of the whole blocking epoch call, best of two -- and the faster form kept;
-    // measured again when the arm's lists change by a quarter)
-    int refine = 2;
-    struct RefineTimes {
-        double ms[2] = {NAN, NAN};  // epoch without / with the refinement: best of two
-        int n[2] = {0, 0};
-        double mean_ref = NAN;      // the lists these were measured on
-    };
-    RefineTimes rf[12];             // [4 seeds + planes]
-    int rf_arm = 0;                 // the arm of the running call
     int defer = 0;                  // with the refinement: distances of decided samples inside the sums kernel
                                     // (experimental, off: one chain wavefront per CU cannot keep up -- NOTES.md)
     bool last_deferred = false;
     int64_t defer_epochs = 0;       // epochs whose sums kernel also evaluated the distances the refinement left open
     int last_round_f32 = 0;
-    int64_t rf_M = -1;
-    int rf_measuring = -1;          // the form the running call is timing (-1: none)
     bool last_refined = false;
     bool last_k2_filtered = false;  // the last k = 2 search went through the pruning form
     int64_t filter_min_query_rows = 32768;
     int64_t sc_chunk_rows = 32768;  // sparse coding: query rows per chunk
     int64_t sc_cap = 0;             // sparse coding: active-set cap of the LDS path (0 = library default)
     DevBuf sc_ws, sc_x, sc_w, sc_p, sc_code, sc_proba, sc_cnt;
-    int64_t max_mean_candidates = 320;
     // samples
     Samples xs, xq;
     DevBuf y;
@@ -313,45 +278,16 @@ struct dbgsom_ctx {
     DevBuf part_order, part_ws, part_counts;
     int64_t partM = 0;
     bool part_valid = false;
-    // policy
-    int filter_backoff = 0, filter_fail = 0;
-    int planes_next = 1, planes_used = 1;   // 1 .. 3 digit planes of the sweep; 0 = no sweep (triangle pruning)
-    bool probe_next = false, last_probed = false;  // a counting-only pruning launch beside the sweep
-    bool last_retry = false;
-    bool exploring_next = false;   // the next epoch runs an arm that has never run on this map (adapt_arms)
-    bool last_guarded = false;     // the last filtered search stopped at its lists and ran all pairs instead
-    int64_t guarded_calls = 0;
-    bool prune_retry = false;  // the last pruning launch met workgroups with poor seeds: re-seed those (DBGSOM_PRUNE_RETRY)
+    // which form of the filtered search runs next, and what it has learnt (search_policy.h)
+    SearchPolicy policy;
     // `dist` holds the exact distances of the resident samples to the rows idx[icur] of Wb[distW_buf]
     // (distW_M rows) as the last epoch's search left them: the hinted pruning bound (filter.hip 2c)
     bool dist_bound_valid = false;
     int distW_buf = 0;
     int64_t distW_M = 0;
     DevBuf shiftb;
-    double last_probe_mean = NAN;
-    int64_t planeM = -1;
-    double arm_known[3][4] = {{NAN, NAN, NAN, NAN}, {NAN, NAN, NAN, NAN}, {NAN, NAN, NAN, NAN}};  // [seeds][planes]
-    double arm_seen[3][4] = {{NAN, NAN, NAN, NAN}, {NAN, NAN, NAN, NAN}, {NAN, NAN, NAN, NAN}};   // last result ever
-    int arm_age[3][4] = {};   // updates of the map since the arm last ran
-    // measured: wall clock (ms) of the blocking epoch call when the arm last ran WITHOUT anything riding along (a
-    // counting-only launch, the refinement's own measurements, results copied to the host).  The re-seeding passes
-    // of the pruning arm are NOT "riding along": `prune_retry` stays on for as long as the arm's cheap seeds leave
-    // workgroups with long lists, so they are what the arm costs on this data (round 3's advisor asked to drop such
-    // epochs: with the flag sticky no arm would ever be timed again -- tests/test_gpu_parity.py
-    // test_search_arms_that_have_been_timed_...); sweep arms do not look at the flag at all.
-    // two arms that both have one are compared by it, the cost model only prices arms that have none
-    double arm_ms[3][4] = {{NAN, NAN, NAN, NAN}, {NAN, NAN, NAN, NAN}, {NAN, NAN, NAN, NAN}};
-    double last_epoch_ms = NAN;     // of the epoch update_policy is looking at (NaN: not a clean measurement)
-    int arm_duels[3][4] = {};       // clean epochs an arm was given only to be timed
-    int arm_wait[3][4] = {{16, 16, 16, 16}, {16, 16, 16, 16}, {16, 16, 16, 16}};
-    bool last_frozen = false;
-    int plane_hold = 0;
-    int seed_mode = 0;   // stateless seeds: 0 = the cheap pre-pass, 1 = the full one
-    double best_mean = NAN;  // list length of the cheapest known arm (what the back-off looks at)
-    bool last_seed_full = false;
     // last epoch
-    bool last_filtered = false, last_hinted = false;
-    double last_mean = NAN;
+    bool last_filtered = false;
     int64_t last_filter_M = 0, last_filter_N = 0, last_filter_d = 0;
     const void *last_filter_ws = nullptr;
     // staging
@@ -478,26 +414,15 @@ int ensure_planes(dbgsom_ctx *c, Samples &s) {
     return DBGSOM_OK;
 }
 
-bool filter_shape_ok(const Samples &s, int64_t M) {
-    return M >= FILTER_MIN_PROTOTYPES && M <= DBGSOM_MAX_PROTOTYPES && s.dp <= FILTER_MAX_FEATURES && s.N >= 1;
-}
+bool filter_shape_ok(const Samples &s, int64_t M) { return SearchPolicy::shape_ok(M, s.N, s.dp); }
 
 bool filter_applies(const dbgsom_ctx *c, int64_t M) {
-    if (c->algorithm == DBGSOM_ALG_EXACT || c->xs.csr) return false;   // (no candidate pruning for CSR residents)
-    if (c->algorithm == DBGSOM_ALG_AUTO && c->filter_backoff > 0) return false;
-    return filter_shape_ok(c->xs, M);
+    if (c->xs.csr) return false;   // (no candidate pruning for CSR residents)
+    return c->policy.filter_allowed() && filter_shape_ok(c->xs, M);
 }
 
-// what the next filtered search runs: 1 .. 3 digit planes, 0 = triangle pruning (option value 4)
-int planes_for_call(const dbgsom_ctx *c) {
-    return c->sweep_planes ? (c->sweep_planes == 4 ? 0 : c->sweep_planes) : c->planes_next;
-}
-// the (seed_stride, sweep_planes) arguments of dbgsom_bmu_filtered for arm `planes`
-void filter_call_args(int planes, bool probe, bool retry, int64_t M, int *stride, int *planes_arg) {
-    *planes_arg = planes ? planes : 1;
-    if (!planes && M <= PRUNE_MAX_M) *stride |= DBGSOM_PRUNE | (retry ? DBGSOM_PRUNE_RETRY : 0);
-    else if (probe && M <= PRUNE_MAX_M) *stride |= DBGSOM_PRUNE_PROBE | (retry ? DBGSOM_PRUNE_RETRY : 0);
-}
+// the previous epoch's winners seed the search of the resident samples
+bool hint_applies(const dbgsom_ctx *c, int64_t M) { return c->policy.takes_hint() && c->hint_valid && c->hintM <= M; }
 
 // prototypes: make W (host, or the resident ones) the consumed matrix Wb[cur]; norms into ww
 int stage_weights(dbgsom_ctx *c, const double *W_host, int64_t M, int64_t d, int64_t dp) {
@@ -517,28 +442,17 @@ int stage_weights(dbgsom_ctx *c, const double *W_host, int64_t M, int64_t d, int
     return launch_row_sqnorms(c->Wb[c->cur].p, DBGSOM_F64, M, dp, dp, c->ww.as<double>(), c->stream);
 }
 
-double bearable_mean(const dbgsom_ctx *c, int64_t M);
-
-// k = 1 search through the int8 filter; seeds = previous winners when `hinted`
+// k = 1 search through the int8 filter, in the form the policy plans; seeds = previous winners when `prev_idx`
 int run_filtered(dbgsom_ctx *c, Samples &s, DevBuf &ws, const double *W, int64_t M, int round_f32,
                  const int64_t *prev_idx, const int32_t *order, int64_t *idx, double *dist, bool may_probe = false,
                  bool allow_defer = false) {
     TRY(ensure_planes(c, s));
     TRY(ws.reserve_zeroed(dbgsom_bmu_filtered_workspace_bytes(s.N, s.dp, M), c->stream));
-    c->planes_used = planes_for_call(c);
-    if (c->planes_used == 0 && M > PRUNE_MAX_M) c->planes_used = 1;
-    c->last_seed_full = !prev_idx && c->seed_mode == 1 && c->seed_stride == 0;
-    int stride = c->last_seed_full ? DBGSOM_SEED_FULL : c->seed_stride, planes_arg = 1;
-    // (a probe is read by the policy after a training epoch; the first epoch of a map size always has one)
-    c->last_probed = may_probe && c->sweep_planes == 0 && (c->probe_next || c->planeM != M) && c->planes_used != 0 &&
-                     M <= PRUNE_MAX_M;
-    if (may_probe) c->probe_next = false;
-    // seeds = the last epoch's winners, and their exact distances are still around: the pruning
-    // bound need not read X for samples whose prototype has hardly moved
+    const bool bound_usable = c->dist_bound_valid && dist == c->dist.as<double>() && c->Wb[c->distW_buf].p;
+    const SearchPolicy::Plan plan = c->policy.plan(M, s.N, s.dp, prev_idx != nullptr, may_probe, bound_usable);
     FilteredCall call;
     call.aux = &c->faux;
-    if (may_probe && prev_idx && c->dist_bound_valid && dist == c->dist.as<double>() && M <= PRUNE_MAX_M &&
-        (c->planes_used == 0 || c->last_probed) && c->Wb[c->distW_buf].p) {
+    if (plan.hint_bound) {
         TRY(c->shiftb.reserve((size_t)M * 8));
         const int64_t rows = c->distW_M < M ? c->distW_M : M;
         hipLaunchKernelGGL(row_shift_kernel, dim3((unsigned)M), dim3(64), 0, c->stream, W,
@@ -547,68 +461,27 @@ int run_filtered(dbgsom_ctx *c, Samples &s, DevBuf &ws, const double *W, int64_t
         call.hint_dist = c->dist.as<double>();
         call.hint_shift = c->shiftb.as<double>();
     }
-    c->last_retry = c->prune_retry;
-    filter_call_args(c->planes_used, c->last_probed, c->prune_retry, M, &stride, &planes_arg);
     call.X = s.Xb; call.x_dtype = s.bdtype; call.N = s.N; call.d = s.dp; call.ldx = s.dp;
     call.xx = s.xx.as<double>(); call.xplanes = s.planes.p; call.W = W; call.M = M; call.ww = c->ww.as<double>();
-    call.prev_idx = prev_idx; call.order = order; call.seed_stride = stride; call.sweep_planes = planes_arg;
+    call.prev_idx = prev_idx; call.order = order; call.seed_stride = plan.seed_stride; call.sweep_planes = plan.sweep_planes;
     call.round_f32 = round_f32; call.idx = idx; call.dist = dist; call.ws = ws.p; call.ws_bytes = ws.cap;
     call.stream = c->stream;
-    // the tile of the refinement's first list-length class: what the lists were last time, with some room
-    // (longer lists go to its largest tile, beyond that to the matrix-core stage)
-    int rf_rows = 64;
-    const bool mean_known = c->last_mean == c->last_mean && c->last_filter_M == M;
-    if (mean_known) rf_rows = (int)(c->last_mean * 1.25 + 8.0);
-    bool use_refine = c->refine == 1;
-    c->rf_measuring = -1;
-    c->rf_arm = 4 * (prev_idx ? 2 : (c->last_seed_full ? 1 : 0)) + c->planes_used;
-    if (c->refine == 2 && mean_known) {
-        if (c->rf_M > 0 && llabs((long long)(M - c->rf_M)) * 4 <= (long long)c->rf_M) c->rf_M = M;   // (a growth step: see adapt_arms)
-        if (c->rf_M != M) {
-            c->rf_M = M;
-            for (auto &r : c->rf) r = dbgsom_ctx::RefineTimes();
-        }
-        dbgsom_ctx::RefineTimes &r = c->rf[c->rf_arm];
-        // (the lists of THIS arm: what it left the last time it ran, else what the last epoch had)
-        const double arm_mean = c->arm_known[c->rf_arm >> 2][c->rf_arm & 3];
-        const double lists = arm_mean == arm_mean ? arm_mean : c->last_mean;
-        if (!(fabs(lists - r.mean_ref) <= 0.25 * r.mean_ref)) { r = dbgsom_ctx::RefineTimes(); r.mean_ref = lists; }
-        // prior (what has not been measured is not tried blind): the refinement reads two digit planes and the
-        // rows once more whatever the lists are -- short lists, few features or a few workgroups never pay;
-        // lists beyond twice its largest tile stay the matrix-core stage's anyway
-        const bool eligible = lists >= 24.0 && lists <= 400.0 && s.dp >= 256 && s.N >= 65536;
-        // timed only on an arm the policy has settled on (or the caller fixed): two forms of the SAME search
-        const bool settled = c->sweep_planes != 0 || c->plane_hold > 0;
-        if (!eligible) use_refine = false;
-        else if (may_probe && settled && r.n[0] < 2) { use_refine = false; c->rf_measuring = 0; }
-        else if (may_probe && settled && r.n[1] < 2) { use_refine = true; c->rf_measuring = 1; }
-        else use_refine = r.n[0] >= 2 && r.n[1] >= 2 && r.ms[1] < r.ms[0];
-    }
-    call.refine_rows = use_refine ? rf_rows : 0;
-    c->last_refined = use_refine;
+    call.refine_rows = plan.refine_rows;
+    c->last_refined = plan.refine;
     // an epoch's accumulate step can evaluate the distances of the samples the refinement decided without
     // looking at their float rows: one pass over those rows for the distance AND the sums
-    call.defer_dist = use_refine && allow_defer && c->defer && M < 0xffff &&
+    call.defer_dist = plan.refine && allow_defer && c->defer && M < 0xffff &&
                       accumulate_can_fill_distances(s.dtype, s.dp);
     c->last_deferred = call.defer_dist;
     c->last_round_f32 = round_f32;
     if (s.dtype == DBGSOM_BF16) { call.X_store = s.X; call.store_dtype = DBGSOM_BF16; call.ld_store = s.dp; }
-    // An arm on trial (`auto`, a training epoch, nothing known of this arm on this map): the call stops at lists
-    // that average more than the policy bears and the all-pairs kernel finds the winners instead -- the policy
-    // still learns what the arm leaves, for the price of its sweep instead of an exact stage over the whole map.
-    c->last_guarded = false;
-    const int arm_row = prev_idx ? 2 : (c->last_seed_full ? 1 : 0);
-    if (may_probe && c->algorithm == DBGSOM_ALG_AUTO && call.k == 1 &&
-        (c->planeM != M || isnan(c->arm_seen[arm_row][c->planes_used])))
-        call.guard_mean = bearable_mean(c, M);
+    call.guard_mean = plan.guard_mean;
     const int rc_f = launch_bmu_filtered(call);
     c->last_filter_M = M; c->last_filter_N = s.N; c->last_filter_d = s.dp; c->last_filter_ws = ws.p;
     if (rc_f == DBGSOM_LISTS_LONG) {
-        c->last_guarded = true;
-        ++c->guarded_calls;
+        c->policy.on_guarded();
         c->last_refined = false;
         c->last_deferred = false;
-        c->rf_measuring = -1;
         return launch_bmu(s.Xb, s.bdtype, s.N, s.dp, s.dp, s.xx.as<double>(), W, M, c->ww.as<double>(), 1, round_f32, idx,
                           dist, c->stream);
     }
@@ -741,219 +614,6 @@ bool shard_smoothing(const dbgsom_ctx *c, int64_t M, int64_t dp) {
     return c->shard_smooth == 1 || 2.0 * (double)M * (double)M * (double)dp >= 8e9;
 }
 
-// The mean list length `auto` bears before it goes back to the all-pairs kernel: the option (320), and never more
-// than half the map -- in the cost model's units an arm costs (its sweep) x M + 12.5 x (mean list) against the
-// all-pairs kernel's 8.4 x M, so lists beyond ~0.5 .. 0.65 M lose to it whatever the arm.  (A young, still collapsed
-// map of a growing fit: at M = 130 .. 260 the lists were 0.75 M and a filtered epoch cost 8 .. 14 ms against 6 .. 7
-// of all pairs -- profiles/r04_fit_trace_before.txt.)
-double bearable_mean(const dbgsom_ctx *c, int64_t M) {
-    return fmin((double)c->max_mean_candidates, 0.5 * (double)M);
-}
-
-// What the next filtered search runs: an ARM = (seeds, digit planes).  Seeds: 0 = the cheap stateless
-// pre-pass (every 4th .. 64th prototype on three 64-feature blocks), 1 = the full one (every
-// prototype, every feature: one more sweep), 2 = the previous epoch's winners (not a choice: whenever
-// the caller's algorithm allows them and they exist).  Digit planes 1 .. 3 of the candidate sweep.
-// Cost model per arm: seeds {1.15, 2, 1} x SWEEP_COST[planes] x M + LIST_COST x mean list length.
-// The lists of an arm are only known once it has run, so the policy explores: from the cheapest
-// known arm it tries an unknown arm when even EMPTY lists would make it cheaper -- its neighbours
-// (one coordinate changed) first, and, when the lists are long (weakly clustered data: a seed that
-// is not nearly the winner, or a bound as wide as the spread of the distances, leaves most of the
-// map a candidate), the strong corner (full seeds, three products) directly: on isotropic data no
-// single step leads there (full seeds alone: 1024 candidates, finer planes alone: 981, both: 17).
-// When nothing is left to try it stays for PLANES_REPROBE epochs, then forgets the alternatives.
-// Results never depend on any of this.
-void adapt_arms(dbgsom_ctx *c, double mean, int64_t M, int64_t N) {
-    c->exploring_next = false;
-    const int row = c->last_hinted ? 2 : (c->last_seed_full ? 1 : 0);
-    const int p = c->planes_used;
-    // A growing map changes its size by a few neurons at a time: what the arms left on a map within a quarter of
-    // this one's size stays the best guess there is (lists and times move with it by a few per cent, and every arm
-    // is looked at again as it ages) -- forgetting it at every growth step made every step pay for the
-    // exploration again, on unclustered data an epoch or two at ten times the settled cost.
-    if (c->planeM > 0 && c->planeM != M && llabs((long long)(M - c->planeM)) * 4 <= (long long)c->planeM) c->planeM = M;
-    if (c->planeM != M) {  // another map size: what was learnt no longer applies
-        c->planeM = M;
-        for (auto &r : c->arm_known) for (double &k : r) k = NAN;
-        for (auto &r : c->arm_seen) for (double &k : r) k = NAN;
-        for (auto &r : c->arm_ms) for (double &k : r) k = NAN;
-        for (auto &r : c->arm_duels) for (int &k : r) k = 0;
-        for (auto &r : c->arm_wait) for (int &k : r) k = 16;
-        c->plane_hold = 0;
-    }
-    static const double SEED_COST[3] = {1.15, 2.0, 1.0};
-    // (arm 0: the one-product pre-pass, one pass over the X plane and the gap matrix)
-    auto fixed = [&](int s_, int q) {
-        if (q == 0)  // (+ two short dependent launches, ~25 us: what decides on small sample sets)
-            return (SEED_COST[s_] - 1.0) * SWEEP_COST[1] * (double)M + PRUNE_PASS_COST +
-                   SWEEP_COST[1] * (double)M * 9.0 * (double)M / (double)(N > 0 ? N : 1) +
-                   25.0 / (2.8 * ((double)(N > 0 ? N : 1) * (double)c->xs.dp) / (1.0e6 * 784.0));
-        return SEED_COST[s_] * SWEEP_COST[q] * (double)M;
-    };
-    // an arm's age = how often the map has been UPDATED since it ran (a frozen map -- the bench, a
-    // series of queries -- does not age what is known about it)
-    if (!c->last_frozen)
-        for (auto &r : c->arm_age) for (int &a : r) ++a;
-    const bool remeasured = !isnan(c->arm_seen[row][p]);
-    c->arm_known[row][p] = c->arm_seen[row][p] = mean;
-    c->arm_age[row][p] = 0;
-    // (an arm that left more than the policy bears gets its next look late: a look at it costs an all-pairs epoch)
-    if (mean > bearable_mean(c, M)) c->arm_wait[row][p] = 128;
-    if (!isnan(c->last_epoch_ms))   // (the mean of the last two looks: one epoch's clock jitters by a few per cent)
-        c->arm_ms[row][p] = isnan(c->arm_ms[row][p]) ? c->last_epoch_ms : 0.5 * (c->arm_ms[row][p] + c->last_epoch_ms);
-    if (c->last_probed) {  // what arm 0 would have produced from the same seeds
-        c->arm_known[row][0] = c->arm_seen[row][0] = c->last_probe_mean;
-        c->arm_age[row][0] = 0;
-    }
-    auto allowed = [&](int s_, int q) {
-        if (c->sweep_planes && q != (c->sweep_planes == 4 ? 0 : c->sweep_planes)) return false;  // fixed by the caller
-        if (q == 0 && M > PRUNE_MAX_M) return false;
-        if (row == 2) return s_ == 2;                                      // hinted: only the planes vary
-        return s_ == 0 || (s_ == 1 && c->seed_stride == 0);               // a caller's stride: cheap seeds only
-    };
-    if (c->plane_hold > 0) {
-        c->best_mean = mean;
-        // A contender the model prices within a factor of two of this arm and that has never run clean: one epoch
-        // of it, on its own, and the clock decides between the two (once per arm until it ages out).
-        if (!isnan(c->arm_ms[row][p])) {
-            int ds = -1, dq = -1;
-            double dc = 2.0 * (fixed(row, p) + LIST_COST * mean);
-            for (int s_ = 0; s_ < 3; ++s_)
-                for (int q = 0; q <= 3; ++q)
-                    if (allowed(s_, q) && !(s_ == row && q == p) && !isnan(c->arm_known[s_][q]) &&
-                        isnan(c->arm_ms[s_][q]) && c->arm_duels[s_][q] < 1) {
-                        const double cst = fixed(s_, q) + LIST_COST * c->arm_known[s_][q];
-                        if (cst < dc) { dc = cst; ds = s_; dq = q; }
-                    }
-            if (ds >= 0) {
-                ++c->arm_duels[ds][dq];
-                c->seed_mode = ds == 1 ? 1 : 0;
-                c->planes_next = dq;
-                c->plane_hold = 0;
-                c->exploring_next = true;
-                return;
-            }
-        }
-        if (--c->plane_hold == 0) {
-            // The alternatives get another look once the map has moved on: an arm whose sweep /
-            // pre-pass costs LESS than the current one after arm_wait (16, doubling up to 128 every
-            // time the look does not pay) updates of the map -- one epoch that can only be dearer by
-            // its lists; a dearer arm after 128 (a look at the full pre-pass is a whole extra sweep).
-            for (int s_ = 0; s_ < 3; ++s_)
-                for (int q = 0; q <= 3; ++q) {
-                    if ((s_ == row && q == p) || isnan(c->arm_known[s_][q])) continue;
-                    const int wait = fixed(s_, q) < fixed(row, p) ? c->arm_wait[s_][q] : 128;
-                    if (c->arm_age[s_][q] >= wait) { c->arm_known[s_][q] = c->arm_ms[s_][q] = NAN; c->arm_duels[s_][q] = 0; }
-                }
-        }
-        return;
-    }
-    // An arm that has been timed costs what it took; the model prices the others.  Both in the model's units: the
-    // timed arms give the units per millisecond (geometric mean of model cost / time over them).
-    double log_sum = 0.0;
-    int n_timed = 0;
-    for (int s_ = 0; s_ < 3; ++s_)
-        for (int q = 0; q <= 3; ++q)
-            if (!isnan(c->arm_known[s_][q]) && c->arm_ms[s_][q] > 0.0) {
-                log_sum += log((fixed(s_, q) + LIST_COST * c->arm_known[s_][q]) / c->arm_ms[s_][q]);
-                ++n_timed;
-            }
-    const double per_ms = n_timed ? exp(log_sum / n_timed) : NAN;
-    auto priced = [&](int s_, int q, double lists) {
-        return c->arm_ms[s_][q] > 0.0 ? c->arm_ms[s_][q] * per_ms : fixed(s_, q) + LIST_COST * lists;
-    };
-    int bs = row, bp = p;
-    double bc = priced(row, p, mean);
-    for (int s_ = 0; s_ < 3; ++s_)
-        for (int q = 0; q <= 3; ++q)
-            if (allowed(s_, q) && !isnan(c->arm_known[s_][q]) && !(s_ == row && q == p)) {
-                const double cst = priced(s_, q, c->arm_known[s_][q]);
-                if (cst < bc) { bc = cst; bs = s_; bp = q; }
-            }
-    // unknown arms worth a look, cheapest optimistic cost first
-    int es = -1, ep = -1;
-    double ec = bc;
-    auto consider = [&](int s_, int q) {
-        if (s_ < 0 || s_ > 2 || q < 0 || q > 3 || !allowed(s_, q) || !isnan(c->arm_known[s_][q])) return;
-        // (no list is cheaper than one step of the exact stage: 16 entries)
-        const double opt = fixed(s_, q) + LIST_COST * fmin(16.0, (double)M);
-        if (opt < ec) { ec = opt; es = s_; ep = q; }
-    };
-    const double best_mean = (bs == row && bp == p) ? mean : c->arm_known[bs][bp];
-    c->best_mean = best_mean;
-    if (best_mean > fmax(96.0, (double)M / 8.0)) {   // long lists: the strong corner first
-        consider(bs == 2 ? 2 : 1, 2);
-        if (es < 0) consider(bs == 2 ? 2 : 1, 3);
-    }
-    if (es < 0) {
-        consider(bs, 0);  // (never run blind: see below)
-        consider(bs, bp + 1); consider(bs, bp - 1);
-        if (bs != 2) consider(1 - bs, bp);
-    }
-    // arm 0 is looked at by a counting-only launch beside an arm whose lists are known to be
-    // bearable (isotropic data: the whole map survives the triangle inequality -- an exact stage
-    // over such lists would cost ten ordinary epochs)
-    // (the launch counts from the seeds of the call it rides on: that call uses the seeds of the arm
-    //  being looked at, with a sweep whose cost is known or about to be)
-    if (es >= 0 && ep == 0) {
-        c->probe_next = true;
-        ep = bp ? bp : 1;
-    }
-    if (remeasured)  // a second look at this arm: did it pay?
-        c->arm_wait[row][p] = (bs == row && bp == p) ? 16 : (c->arm_wait[row][p] >= 64 ? 128 : 2 * c->arm_wait[row][p]);
-    if (es >= 0) {
-        c->seed_mode = es == 1 ? 1 : 0;
-        c->planes_next = ep;
-        c->exploring_next = true;
-    } else {
-        c->seed_mode = bs == 1 ? 1 : 0;
-        c->planes_next = bp;
-        c->plane_hold = PLANES_REPROBE;
-    }
-}
-
-// after an epoch has completed: look at how long the candidate lists were, decide what comes next
-void update_policy(dbgsom_ctx *c, double list_sum, double probe_sum, double retry_groups, int64_t nb, int64_t M) {
-    if (!c->last_filtered) { c->last_mean = NAN; return; }
-    // Workgroups of the pruning form whose lists came out long (poor cheap seeds) while the re-seeding
-    // passes were off: what this call measured of arm 0 is not what the arm costs.  Turn them on and
-    // measure again -- the same arm once more, or another counting-only launch.
-    bool again = false;
-    if (c->planes_used == 0 || c->last_probed) {
-        const bool need = retry_groups > 0.0;
-        if (need && !c->last_retry && !c->last_hinted && !c->last_seed_full) {   // (cheap seeds: re-seeding can help)
-            c->prune_retry = true;
-            if (c->planes_used == 0) {
-                c->last_mean = nb ? list_sum / (double)nb : 0.0;
-                return;
-            }
-            c->last_probed = false;
-            again = true;
-        } else if (!c->last_hinted && !c->last_seed_full) {
-            c->prune_retry = need;
-        }
-    }
-    const double mean = nb ? list_sum / (double)nb : 0.0;
-    c->last_mean = mean;
-    c->last_probe_mean = c->last_probed && nb ? probe_sum / (double)nb : NAN;
-    adapt_arms(c, mean, M, nb * 128);
-    if (again) c->probe_next = true;
-    if (c->algorithm == DBGSOM_ALG_AUTO) {
-        // (the cheapest arm known so far, not an arm that is only being looked at)
-        // (not while an arm that has never run on this map is up next: on unclustered data the strong corner --
-        //  good seeds and a finer sweep -- is what works, and eight all-pairs epochs in front of its first try
-        //  cost forty settled ones)
-        if (c->best_mean > bearable_mean(c, M) && !c->exploring_next) {  // exponential back-off, capped
-            c->filter_fail = c->filter_fail < 6 ? c->filter_fail + 1 : 6;
-            c->filter_backoff = FILTER_BACKOFF << (c->filter_fail - 1);
-        } else if (c->best_mean > bearable_mean(c, M)) {
-            // (exploring)
-        } else {
-            c->filter_fail = 0;
-        }
-    }
-}
-
 void mark(dbgsom_ctx *c, int k) {
     if (!c->timing) return;
     if (!c->ev_created) { for (auto &e : c->ev) (void)hipEventCreate(&e); c->ev_created = true; }
@@ -1020,7 +680,7 @@ int epoch_bmu(dbgsom_ctx *c, int64_t M, int round_f32) {
     TRY(c->dist.reserve((size_t)s.N * 8));
     int64_t *out = c->idx[c->icur ^ 1].as<int64_t>();
     const double *W = c->Wb[c->cur].as<double>();
-    c->last_hinted = false;
+    c->policy.begin_epoch();
     c->last_deferred = false;
     if (s.csr) {
         c->last_filtered = false;
@@ -1032,15 +692,13 @@ int epoch_bmu(dbgsom_ctx *c, int64_t M, int round_f32) {
         return DBGSOM_OK;
     }
     if (filter_applies(c, M)) {
-        const bool hint = (c->algorithm == DBGSOM_ALG_AUTO || c->algorithm == DBGSOM_ALG_FILTERED_HINT) &&
-                          c->hint_valid && c->hintM <= M;
+        const bool hint = hint_applies(c, M);
         c->last_filtered = true;
-        c->last_hinted = hint;
         TRY(run_filtered(c, s, c->filt_ws, W, M, round_f32, hint ? c->idx[c->icur].as<int64_t>() : nullptr,
                          hint ? c->acc_ws.as<int32_t>() : nullptr, out, c->dist.as<double>(), true, true));
     } else {
         c->last_filtered = false;
-        if (c->filter_backoff > 0) --c->filter_backoff;
+        c->policy.on_exact_epoch();
         TRY(launch_bmu(s.Xb, s.bdtype, s.N, s.dp, s.dp, s.xx.as<double>(), W, M, c->ww.as<double>(), 1, round_f32,
                        out, c->dist.as<double>(), c->stream));
     }
@@ -1224,24 +882,14 @@ int resident_bmu(dbgsom_ctx *c, const double *W_host, int64_t M, int k, int roun
         return csr_search(c, s, W, M, k, round_f32, c->qidx.as<int64_t>(), c->qdist.as<double>());
     }
     if (k == 1 && filter_applies(c, M)) {
-        const bool hint = (c->algorithm == DBGSOM_ALG_AUTO || c->algorithm == DBGSOM_ALG_FILTERED_HINT) &&
-                          c->hint_valid && c->hintM <= M;
+        const bool hint = hint_applies(c, M);
         return run_filtered(c, s, c->filt_ws, W, M, round_f32, hint ? c->idx[c->icur].as<int64_t>() : nullptr,
                             hint ? c->acc_ws.as<int32_t>() : nullptr, c->qidx.as<int64_t>(), c->qdist.as<double>());
     }
     // k = 2 (topographic error, BaseSom.py:945): through the pruning form of the filtered search when the
-    // training epochs have shown that it works on this data -- arm 0 of the policy has run (or been counted)
-    // on this map size and left lists a fraction of the map (clustered data); otherwise all pairs
-    double lists0 = NAN;
-    if (c->planeM == M)
-        for (int r = 0; r < 3; ++r) {
-            const double v = c->arm_seen[r][0];
-            if (v == v && !(lists0 <= v)) lists0 = v;
-        }
-    if (k == 2 && filter_applies(c, M) && M <= PRUNE_MAX_M && M >= 2 && c->last_filter_M == M && lists0 == lists0 &&
-        lists0 <= bearable_mean(c, M)) {
-        const bool hint = (c->algorithm == DBGSOM_ALG_AUTO || c->algorithm == DBGSOM_ALG_FILTERED_HINT) &&
-                          c->hint_valid && c->hintM <= M;
+    // training epochs have shown that it works on this data (SearchPolicy::k2_prunes); otherwise all pairs
+    if (k == 2 && filter_applies(c, M) && c->policy.k2_prunes(M)) {
+        const bool hint = hint_applies(c, M);
         TRY(ensure_planes(c, s));
         TRY(c->filt_ws.reserve_zeroed(dbgsom_bmu_filtered_workspace_bytes(s.N, s.dp, M), c->stream));
         FilteredCall call;
@@ -1250,7 +898,7 @@ int resident_bmu(dbgsom_ctx *c, const double *W_host, int64_t M, int k, int roun
         call.xx = s.xx.as<double>(); call.xplanes = s.planes.p; call.W = W; call.M = M; call.ww = c->ww.as<double>();
         call.prev_idx = hint ? c->idx[c->icur].as<int64_t>() : nullptr;
         call.order = hint ? c->acc_ws.as<int32_t>() : nullptr;
-        call.seed_stride = c->seed_stride | DBGSOM_PRUNE | (c->prune_retry && !hint ? DBGSOM_PRUNE_RETRY : 0);
+        call.seed_stride = c->policy.k2_seed_stride(hint);
         call.sweep_planes = 1; call.round_f32 = round_f32; call.k = 2;
         call.idx = c->qidx.as<int64_t>(); call.dist = c->qdist.as<double>();
         call.ws = c->filt_ws.p; call.ws_bytes = c->filt_ws.cap; call.stream = c->stream;
@@ -1325,13 +973,13 @@ int dbgsom_ctx_set_option(dbgsom_ctx *c, const char *name, int64_t v) {
     DBGSOM_REQUIRE(name, "null option name");
     if (!strcmp(name, "algorithm")) {
         DBGSOM_REQUIRE(v >= DBGSOM_ALG_AUTO && v <= DBGSOM_ALG_FILTERED_HINT, "algorithm must be a DBGSOM_ALG_* value");
-        c->algorithm = (int)v;
+        c->policy.algorithm = (int)v;
     } else if (!strcmp(name, "sweep_planes")) {
         DBGSOM_REQUIRE(v >= 0 && v <= 4, "sweep_planes must be 0 .. 4 (4 = no sweep: triangle pruning)");
-        c->sweep_planes = (int)v;
+        c->policy.sweep_planes = (int)v;
     } else if (!strcmp(name, "seed_stride")) {
         DBGSOM_REQUIRE(v >= 0 && v <= 64, "seed_stride outside [0, 64]");
-        c->seed_stride = (int)v;
+        c->policy.seed_stride = (int)v;
     } else if (!strcmp(name, "timing")) {
         c->timing = v != 0;
         c->ev_valid = false;
@@ -1346,8 +994,7 @@ int dbgsom_ctx_set_option(dbgsom_ctx *c, const char *name, int64_t v) {
         c->shard_smooth = (int)v;
     } else if (!strcmp(name, "refine")) {
         DBGSOM_REQUIRE(v >= 0 && v <= 2, "refine must be 0 (off), 1 (on) or 2 (by measurement)");
-        c->refine = (int)v;
-        for (auto &r : c->rf) r = dbgsom_ctx::RefineTimes();
+        c->policy.set_refine((int)v);
     } else if (!strcmp(name, "filter_min_query_rows")) {
         DBGSOM_REQUIRE(v >= 0, "filter_min_query_rows must be >= 0");
         c->filter_min_query_rows = v;
@@ -1359,7 +1006,7 @@ int dbgsom_ctx_set_option(dbgsom_ctx *c, const char *name, int64_t v) {
         c->sc_cap = v;
     } else if (!strcmp(name, "max_mean_candidates")) {
         DBGSOM_REQUIRE(v >= 1, "max_mean_candidates must be >= 1");
-        c->max_mean_candidates = v;
+        c->policy.max_mean_candidates = v;
     } else if (!strcmp(name, "csr_densify_below")) {
         DBGSOM_REQUIRE(v >= 0, "csr_densify_below must be >= 0 (0 = CSR input always stays CSR)");
         c->csr_densify_below = v;
@@ -1373,23 +1020,23 @@ int dbgsom_ctx_set_option(dbgsom_ctx *c, const char *name, int64_t v) {
 int dbgsom_ctx_get_option(dbgsom_ctx *c, const char *name, int64_t *v) {
     CTX_CHECK(c);
     DBGSOM_REQUIRE(name && v, "null pointer");
-    if (!strcmp(name, "algorithm")) *v = c->algorithm;
-    else if (!strcmp(name, "sweep_planes")) *v = c->sweep_planes;
-    else if (!strcmp(name, "seed_stride")) *v = c->seed_stride;
+    if (!strcmp(name, "algorithm")) *v = c->policy.algorithm;
+    else if (!strcmp(name, "sweep_planes")) *v = c->policy.sweep_planes;
+    else if (!strcmp(name, "seed_stride")) *v = c->policy.seed_stride;
     else if (!strcmp(name, "timing")) *v = c->timing;
     else if (!strcmp(name, "graph")) *v = c->use_graph;
-    else if (!strcmp(name, "refine")) *v = c->refine;
+    else if (!strcmp(name, "refine")) *v = c->policy.refine;
     else if (!strcmp(name, "refined")) *v = c->last_refined ? 1 : 0;
     else if (!strcmp(name, "defer")) *v = c->defer;
     else if (!strcmp(name, "shard_smooth")) *v = c->shard_smooth;
     else if (!strcmp(name, "shard_epochs")) *v = c->shard_epochs;
     else if (!strcmp(name, "defer_epochs")) *v = c->defer_epochs;
-    else if (!strcmp(name, "guarded_calls")) *v = c->guarded_calls;
+    else if (!strcmp(name, "guarded_calls")) *v = c->policy.guarded_calls;
     else if (!strcmp(name, "collective_rank")) *v = c->coll_rank;
     else if (!strcmp(name, "collective_ranks")) *v = c->coll_nranks;
     else if (!strcmp(name, "k2_filtered")) *v = c->last_k2_filtered ? 1 : 0;
     else if (!strcmp(name, "filter_min_query_rows")) *v = c->filter_min_query_rows;
-    else if (!strcmp(name, "max_mean_candidates")) *v = c->max_mean_candidates;
+    else if (!strcmp(name, "max_mean_candidates")) *v = c->policy.max_mean_candidates;
     else if (!strcmp(name, "sc_chunk_rows")) *v = c->sc_chunk_rows;
     else if (!strcmp(name, "sc_cap")) *v = c->sc_cap;
     else if (!strcmp(name, "csr_densify_below")) *v = c->csr_densify_below;
@@ -1401,13 +1048,13 @@ int dbgsom_ctx_get_option(dbgsom_ctx *c, const char *name, int64_t *v) {
     else if (!strcmp(name, "storage")) *v = c->xs.dtype;
     else if (!strcmp(name, "prototypes")) *v = c->M;
     else if (!strcmp(name, "planes_cached")) *v = c->xs.planes_ready ? 1 : 0;
-    else if (!strcmp(name, "planes_used")) *v = c->planes_used;
-    else if (!strcmp(name, "planes_next")) *v = planes_for_call(c);
+    else if (!strcmp(name, "planes_used")) *v = c->policy.planes_used;
+    else if (!strcmp(name, "planes_next")) *v = c->policy.planes_for_call();
     else if (!strcmp(name, "hint_valid")) *v = c->hint_valid ? 1 : 0;
-    else if (!strcmp(name, "filter_backoff")) *v = c->filter_backoff;
-    else if (!strcmp(name, "plane_hold")) *v = c->plane_hold;
-    else if (!strcmp(name, "seed_mode")) *v = c->seed_mode;
-    else if (!strcmp(name, "prune_retry")) *v = c->prune_retry ? 1 : 0;
+    else if (!strcmp(name, "filter_backoff")) *v = c->policy.filter_backoff;
+    else if (!strcmp(name, "plane_hold")) *v = c->policy.plane_hold;
+    else if (!strcmp(name, "seed_mode")) *v = c->policy.seed_mode;
+    else if (!strcmp(name, "prune_retry")) *v = c->policy.prune_retry ? 1 : 0;
     else if (!strcmp(name, "w_upload_calls")) *v = c->w_up_calls;
     else if (!strcmp(name, "w_upload_bytes")) *v = c->w_up_bytes;
     else if (!strcmp(name, "w_download_calls")) *v = c->w_down_calls;
@@ -1450,21 +1097,12 @@ static void reset_training_state(dbgsom_ctx *c) {
     c->hint_valid = c->last_idx_valid = c->part_valid = false;
     c->has_labels = false;
     c->has_weights = false;
-    c->filter_backoff = c->filter_fail = 0;
-    c->planes_next = 1;
-    c->planeM = -1;
-    c->plane_hold = 0;
-    c->seed_mode = 0;
-    c->probe_next = c->last_probed = false;
-    c->prune_retry = false;
+    c->policy.reset();
     c->dist_bound_valid = false;
     c->last_filtered = false;
-    c->last_mean = NAN;
     c->sumsM = 0;
     // the resident prototypes were laid out for the old samples' padded row length: gone with them
     c->M = c->otherM = 0;
-    c->rf_M = -1;
-    for (auto &r : c->rf) r = dbgsom_ctx::RefineTimes();
 }
 
 int dbgsom_ctx_load(dbgsom_ctx *c, const void *X_host, int x_dtype, int64_t N, int64_t d, int storage) {
@@ -1782,15 +1420,15 @@ static int bmu_query_impl(dbgsom_ctx *c, const void *Xq_host, const int64_t *ind
         if ((rc = upload_padded(c, Wq.p, W_host, M, d, dp, 8))) break;
         if ((rc = launch_row_sqnorms(Wq.p, DBGSOM_F64, M, dp, dp, wwq.as<double>(), c->stream))) break;
         // large k = 1 queries go through the filter (the digit planes of a one-off X cost a pass over it)
-        const bool filt = !s.csr && k == 1 && c->algorithm != DBGSOM_ALG_EXACT && Nq >= c->filter_min_query_rows &&
+        const bool filt = !s.csr && k == 1 && c->policy.algorithm != DBGSOM_ALG_EXACT && Nq >= c->filter_min_query_rows &&
                           filter_shape_ok(s, M);
         if (s.csr) {
             rc = csr_search(c, s, Wq.as<double>(), wwq.as<double>(), wtq, M, k, round_f32, iq.as<int64_t>(), dq.as<double>());
         } else if (filt) {
             if ((rc = ensure_planes(c, s))) break;
             if ((rc = fws.reserve_zeroed(dbgsom_bmu_filtered_workspace_bytes(Nq, dp, M), c->stream))) break;
-            int stride = c->seed_stride, planes = 1;
-            filter_call_args(planes_for_call(c), false, c->prune_retry, M, &stride, &planes);
+            int stride = 0, planes = 1;
+            c->policy.query_args(M, &stride, &planes);
             rc = dbgsom_bmu_filtered(s.Xb, s.bdtype, Nq, dp, dp, s.xx.as<double>(), s.planes.p, Wq.as<double>(), M,
                                      wwq.as<double>(), nullptr, nullptr, stride, planes, round_f32,
                                      iq.as<int64_t>(), dq.as<double>(), fws.p, fws.cap, c->stream);
@@ -1995,8 +1633,7 @@ int dbgsom_ctx_epoch(dbgsom_ctx *c, const double *W_host, int64_t M, int round_f
         const auto t_begin = std::chrono::steady_clock::now();
         if ((rc = epoch_bmu(c, M, round_f32))) break;
         mark(c, 1);
-        const int measuring = c->rf_measuring;   // (the refinement's policy: this epoch times one of the two forms)
-        c->rf_measuring = -1;
+        const int measuring = c->policy.take_timing_form();   // (the refinement's policy: this epoch times one of the two forms)
         const int64_t *idx = c->idx[c->icur].as<int64_t>();
         if ((rc = accumulate_and_reduce(c, idx, nullptr, gamma, c->dist.as<double>(), M))) break;
         // the next epoch's filter visits the samples bucketed by this epoch's winners: the stable
@@ -2007,18 +1644,20 @@ int dbgsom_ctx_epoch(dbgsom_ctx *c, const double *W_host, int64_t M, int round_f
         rc = smooth_and_fetch(c, M, sigma, layout, flags, W_new_host, change_total_host, errors_host, activations_host,
                               idx, idx_host, dist_host);
         if (rc != DBGSOM_OK && rc != DBGSOM_ERANGE) break;
-        if (measuring >= 0) {   // wall clock of the blocking call behind the upload of W: BMU + sums + smoothing
-            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-            dbgsom_ctx::RefineTimes &r = c->rf[c->rf_arm];
-            r.ms[measuring] = r.n[measuring] == 0 ? ms : fmin(ms, r.ms[measuring]);
-            ++r.n[measuring];
+        SearchPolicy &pol = c->policy;
+        if (measuring >= 0)   // wall clock of the blocking call behind the upload of W: BMU + sums + smoothing
+            pol.refine_timed(measuring, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
+        if (c->last_filtered) {
+            // (a clean measurement of the arm: nothing rode along -- see SearchPolicy::arm_ms)
+            const bool clean = !pol.last_probed && !pol.last_guarded && measuring < 0 && !W_new_host && !idx_host && !dist_host;
+            const double epoch_ms =
+                clean ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count() : NAN;
+            const double *counted = c->tail.as<double>() + 2 * M + 2;   // (pack_results_kernel: lists, probe, groups to re-seed)
+            pol.observe(counted[0], counted[1], counted[2], (s.N + 127) / 128, M, s.dp, (flags & DBGSOM_EPOCH_FROZEN) != 0,
+                        epoch_ms);
+        } else {
+            pol.observe_unfiltered();
         }
-        c->last_frozen = (flags & DBGSOM_EPOCH_FROZEN) != 0;
-        c->last_epoch_ms = (c->last_filtered && !c->last_probed && !c->last_guarded && measuring < 0 && !W_new_host && !idx_host && !dist_host)
-                               ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count()
-                               : NAN;
-        update_policy(c, c->tail.as<double>()[2 * M + 2], c->tail.as<double>()[2 * M + 3], c->tail.as<double>()[2 * M + 4],
-                      (s.N + 127) / 128, M);
     } while (0);
     if (rc != DBGSOM_OK && rc != DBGSOM_ERANGE) { (void)hipStreamSynchronize(c->stream); c->hint_valid = false; }
     return rc;
@@ -2326,8 +1965,9 @@ int dbgsom_ctx_subset_create(dbgsom_ctx *c, int64_t neuron, dbgsom_ctx **child_o
     if (n < 1) { set_error("dbgsom_ctx_subset_create: neuron %lld has no samples", (long long)neuron); return DBGSOM_EINVAL; }
     dbgsom_ctx *k = nullptr;
     TRY(dbgsom_ctx_create(c->device, &k));
-    k->algorithm = c->algorithm; k->sweep_planes = c->sweep_planes; k->seed_stride = c->seed_stride;
-    k->filter_min_query_rows = c->filter_min_query_rows; k->max_mean_candidates = c->max_mean_candidates;
+    k->policy.algorithm = c->policy.algorithm; k->policy.sweep_planes = c->policy.sweep_planes;
+    k->policy.seed_stride = c->policy.seed_stride; k->policy.max_mean_candidates = c->policy.max_mean_candidates;
+    k->filter_min_query_rows = c->filter_min_query_rows;
     k->allreduce = nullptr;  // a child map is fitted on this rank's rows alone
     Samples &t = k->xs;
     int rc = DBGSOM_OK;
@@ -2372,13 +2012,14 @@ int dbgsom_ctx_epoch_info(dbgsom_ctx *c, double *info8) {
     CTX_CHECK(c);
     DBGSOM_REQUIRE(info8, "null pointer");
     info8[0] = c->last_filtered ? 1.0 : 0.0;
-    info8[1] = c->last_mean;
-    info8[2] = c->last_filtered ? (double)c->planes_used : 0.0;
-    info8[3] = c->last_hinted ? 1.0 : 0.0;
-    info8[4] = (double)c->filter_backoff;
-    info8[5] = (double)c->plane_hold;
-    info8[6] = c->last_filtered && c->last_probed ? c->last_probe_mean : NAN;
-    info8[7] = c->last_filtered && c->last_seed_full ? 1.0 : 0.0;
+    const SearchPolicy &pol = c->policy;
+    info8[1] = pol.last_mean;
+    info8[2] = c->last_filtered ? (double)pol.planes_used : 0.0;
+    info8[3] = pol.last_hinted ? 1.0 : 0.0;
+    info8[4] = (double)pol.filter_backoff;
+    info8[5] = (double)pol.plane_hold;
+    info8[6] = c->last_filtered && pol.last_probed ? pol.last_probe_mean : NAN;
+    info8[7] = c->last_filtered && pol.last_seed_full ? 1.0 : 0.0;
     return DBGSOM_OK;
 }
 
@@ -2386,7 +2027,7 @@ int dbgsom_ctx_arm_ms(dbgsom_ctx *c, double *ms12) {
     CTX_CHECK(c);
     DBGSOM_REQUIRE(ms12, "null pointer");
     for (int s_ = 0; s_ < 3; ++s_)
-        for (int q = 0; q < 4; ++q) ms12[4 * s_ + q] = c->arm_ms[s_][q];
+        for (int q = 0; q < 4; ++q) ms12[4 * s_ + q] = c->policy.arm_ms[s_][q];
     return DBGSOM_OK;
 }
 

@@ -961,7 +961,7 @@ def test_full_seed_prepass_on_weakly_clustered_data(o):
 
 
 def test_adaptive_digit_planes_settle_on_the_cheaper_sweep(o):
-    """sweep_planes = 0: the engine's arm policy (seeds x digit planes, cost model in engine.hip)
+    """sweep_planes = 0: the engine's arm policy (seeds x digit planes, cost model in csrc/search_policy.h)
     starts with cheap seeds and the one-product sweep.  On clustered data a counting-only launch
     beside the first epoch's sweep shows that the triangle inequality leaves lists as short, and
     the policy drops the sweep (arm 0); where the coarse bounds mark the whole map (a tiny spread
@@ -1007,7 +1007,7 @@ def test_adaptive_digit_planes_settle_on_the_cheaper_sweep(o):
 
 
 def test_search_arms_that_have_been_timed_are_compared_by_their_time():
-    """The arm policy (engine.hip: adapt_arms) prices an arm it has never run by the cost model, but two
+    """The arm policy (search_policy.h: adapt_arms) prices an arm it has never run by the cost model, but two
     arms that both ran clean -- nothing riding along, nothing copied to the host -- are compared by the
     measured wall clock of the epoch call (dbgsom_ctx_arm_ms).  Mid-clustered data (six clusters, lists of
     ~170 prototypes): the arm the policy settles on is, among the arms it tried, the fastest by the

@@ -1,5 +1,7 @@
 """Diagnostic: the arms the search policy runs on mid-clustered data, epoch by epoch, with the engine's clock.
-    python tools/arms_trace.py [centres = 6] [epochs = 30]"""
+    python tools/arms_trace.py [centres = 6] [epochs = 30]
+The policy is dbgsom_amd/csrc/search_policy.h; tests/policy_replay.cpp replays a sequence of its calls on the CPU
+(format at the top of that file, examples under tests/data/policy_traces/)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

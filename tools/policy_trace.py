@@ -1,6 +1,11 @@
 """What the engine's search policy does epoch by epoch on a bench workload (frozen map):
 arm (seeds, digit planes), mean candidate-list length, the counting-only pruning probe, re-seeding.
-    python tools/policy_trace.py c4 [rows] [epochs]"""
+    python tools/policy_trace.py c4 [rows] [epochs]
+The policy is dbgsom_amd/csrc/search_policy.h, host-only C++.  What it would do with the list lengths and epoch
+times printed here (or with others) can be replayed without a GPU: tests/policy_replay.cpp reads one policy call per
+line (`shape M N DP`, `plan HINTED 1 BOUND`, `observe LIST_SUM PROBE_SUM RETRY_GROUPS FROZEN MS`, ...: the format is
+at the top of that file, examples under tests/data/policy_traces/) and prints every plan and the state after it:
+    c++ -std=c++17 -I dbgsom_amd/csrc tests/policy_replay.cpp -o policy_replay && ./policy_replay < my.trace"""
 import os
 import sys
 import time
