@@ -24,32 +24,20 @@
 #include <type_traits>
 
 #include "bmu_common.h"
+#include "filter_form.h"
 
 namespace dbgsom {
 
 constexpr double FQ = 8323072.0;  // 127 * 2^16
 constexpr double F16 = 32512.0;   // 127 * 2^8: scale of the top two digit planes taken as one 16-bit digit
-constexpr int FKT = 64;           // bytes (= features) per plane row per LDS stage
 constexpr int FNT = 512;          // threads per sweep workgroup (8 wavefronts)
 constexpr int FSTAGES = 3;
-constexpr int PREPASS_KTILES = 3;  // k-tiles the seed pre-pass samples (tile_select_kernel picks them)
 constexpr int SCHED_BINS = 16;     // launch-order bins of the exact stage (section 2b)
 constexpr int SCHED_RETRY = 2 * SCHED_BINS + 10;  // u64: workgroups of the pruning form whose lists came out long (re-seeded, 2c)
 constexpr int SCHED_CTR = 2 * SCHED_BINS + 12;  // bin counts | cursors | [start, n] of classes 3, 2, 1 | sum of list lengths (u64) | the same of a counting-only pruning launch (u64)
 constexpr int SCHED_SUM = 2 * SCHED_BINS + 6;  // (8-byte aligned: the counters sit on a 256-byte boundary)
 constexpr int RF_CTR = 4;  // u64 counters of the refinement (2d): pairs | refined workgroups | left to the MFMA stage | -
 static_assert(SCHED_CTR % 2 == 0, "the 64-bit counters of the refinement sit behind the schedule's");
-constexpr int SW_MAX_KT = 1024;   // k-tiles that selection handles (d <= 65536)
-
-// plane rows are padded to whole k-tiles, at least two of them (the sweep's ring runs three tiles
-// ahead and keeps three chunk tables)
-inline int64_t filter_dpad(int64_t d) {
-    // (a 128-byte pitch -- whole cache lines per row -- was measured in round 3: prune_mark_kernel fetched
-    //  the same 1.25 GB at d = 784 either way, and the seventh part more plane cost the pre-pass and the
-    //  pruning pass 8 % each)
-    const int64_t p = (d + FKT - 1) / FKT * FKT;
-    return p < 2 * FKT ? 2 * FKT : p;
-}
 
 // ---- 1. digit planes --------------------------------------------------------------------------
 // Upper bound of |a - a16| (Euclidean) from the float64 sum r2 of the squared residuals as evaluated:
@@ -462,6 +450,187 @@ struct SweepLds {
     static constexpr int BYTES = OFF_MISC + 16;
 };
 
+// ---- stages the candidate kernels share (sweep_i8_kernel, sweep4_i8_kernel, prune_mark_kernel) ----
+// (Shaped so that every kernel keeps the registers and the instruction count it had with its own copy: the
+//  pointer parameters carry no __restrict__ -- the kernels' own qualifiers hold, a second set only adds alias
+//  scopes on inlining, which moved the sweeps' schedules -- and seed_argmin takes its lane from threadIdx and
+//  the sample order as a pointer, not as the kernel's lambda, which cost the seed sweeps one or two VGPRs.)
+template <int DMA_TILE>
+__device__ __forceinline__ void wait_vm(int n) {  // s_waitcnt vmcnt needs an immediate
+    if (n == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    else if (n == DMA_TILE) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_TILE) : "memory");
+    else if (n == DMA_TILE + 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_TILE + 1) : "memory");
+    else if (n == 2 * DMA_TILE) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * DMA_TILE) : "memory");
+    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * DMA_TILE + 1) : "memory");
+}
+
+// MODE 0 prologue of a sweep of NT threads: clears the bitmask, fills prev_s (the samples' seeds, -1: none)
+// and thr_s, and reduces the seeds to their range jlo .. jhi through misc[0..1] -- the sweep starts at the
+// chunk holding the lowest
+template <int NT, typename SampleAt>
+__device__ __forceinline__ void seed_prologue(uint32_t *mask, int *prev_s, double *thr_s, int *misc, int tid, int lane,
+                                              int wave, int nwords, int M, int64_t p0, int64_t N,
+                                              const int64_t *prev, const SampleAt &sample_at, int &jlo,
+                                              int &jhi) {
+    for (int w = tid; w < nwords; w += NT) mask[w] = 0u;
+    if (tid < 128) {
+        const int64_t p = p0 + tid;
+        int pj = -1;
+        if (p < N) pj = (int)prev[sample_at(p)];
+        prev_s[tid] = (pj >= 0 && pj < M) ? pj : -1;
+        thr_s[tid] = (p < N) ? -INFINITY : INFINITY;  // A = |x|^2 - thr: no bound yet / padding never marks
+    }
+    __syncthreads();
+    if (wave == 0) {
+        const int a = prev_s[lane], b = prev_s[lane + 64];
+        int lo = min(a >= 0 ? a : 0x7fffffff, b >= 0 ? b : 0x7fffffff), hi = max(a, b);
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {
+            lo = min(lo, __shfl_xor(lo, m, 64));
+            hi = max(hi, __shfl_xor(hi, m, 64));
+        }
+        if (lane == 0) {
+            misc[0] = (hi >= 0) ? lo : 0;
+            misc[1] = hi;
+        }
+    }
+    __syncthreads();
+    jlo = __builtin_amdgcn_readfirstlane(misc[0]);
+    jhi = __builtin_amdgcn_readfirstlane(misc[1]);
+}
+
+// The seeds of a workgroup sit in one chunk of BJ prototypes, except where the sorted order crosses a chunk
+// border.  There the samples whose seed lies in a later chunk would sweep the first chunk(s) without a
+// bound (and mark all of them): give those samples their bound up front, from the same exact integer
+// products by v_dot4 (TPS threads per sample, K split by 16-byte chunks).  Rare path: a handful of
+// workgroups per launch.  slack32: thr_i also carries the slack of the float32 chunk epilogue.
+template <int PLANES, int TPS, int BJ, typename SampleAt>
+__device__ __forceinline__ void seed_bound_ahead(double *thr_s, const int *prev_s, int tid, int jlo, int64_t p0, int64_t N,
+                                                 int d, int dpad, const int8_t *xplanes,
+                                                 const int8_t *wplanes, int w_rows,
+                                                 const double *sx, const double *l1x,
+                                                 const double *xx, const double *yraw,
+                                                 const double *craw, const double *summary,
+                                                 const SampleAt &sample_at, bool slack32) {
+    const int il = tid / TPS, q = tid % TPS;
+    const int64_t p = p0 + il;
+    const int pj = prev_s[il];
+    const bool need = p < N && pj >= 0 && pj / BJ != jlo / BJ;
+    int a0 = 0, a1 = 0, a2 = 0;
+    const int64_t i = sample_at(p < N ? p : N - 1);
+    if (need) {
+        const size_t xps = (size_t)N * dpad, wps = (size_t)w_rows * dpad;
+        const int8_t *xr = xplanes + (size_t)i * dpad;
+        const int wsw = (pj >> 2) & 3;
+        for (int ch = q; ch < dpad / 16; ch += TPS) {
+            const int8_t *wr = wplanes + ((size_t)(ch >> 2) * w_rows + pj) * FKT + (((ch & 3) ^ wsw) << 4);
+            v4i_t xv[PLANES], wv[PLANES];
+#pragma unroll
+            for (int pl = 0; pl < PLANES; ++pl) {
+                xv[pl] = *reinterpret_cast<const v4i_t *>(xr + pl * xps + ch * 16);
+                wv[pl] = *reinterpret_cast<const v4i_t *>(wr + pl * wps);
+            }
+            constexpr int P1 = PLANES >= 2 ? 1 : 0, P2 = PLANES >= 3 ? 2 : 0;  // plane indices that exist
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                a0 = __builtin_amdgcn_sdot4(xv[0][e], wv[0][e], a0, false);
+                if constexpr (PLANES >= 2) {
+                    a1 = __builtin_amdgcn_sdot4(xv[0][e], wv[P1][e], a1, false);
+                    a1 = __builtin_amdgcn_sdot4(xv[P1][e], wv[0][e], a1, false);
+                }
+                if constexpr (PLANES == 3) {
+                    a2 = __builtin_amdgcn_sdot4(xv[0][e], wv[P2][e], a2, false);
+                    a2 = __builtin_amdgcn_sdot4(xv[P1][e], wv[P1][e], a2, false);
+                    a2 = __builtin_amdgcn_sdot4(xv[P2][e], wv[0][e], a2, false);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int m = 1; m < TPS; m <<= 1) {
+        a0 += __shfl_xor(a0, m, 64);
+        if constexpr (PLANES >= 2) a1 += __shfl_xor(a1, m, 64);
+        if constexpr (PLANES == 3) a2 += __shfl_xor(a2, m, 64);
+    }
+    if (need && q == 0) {
+        const double T = sweep_T<PLANES>(a0, a1, a2);
+        const double sv = sx[i], xv2 = xx[i];
+        const double eps = filter_eps(sv, l1x[i], xv2, summary[0], summary[1], summary[2], d, PLANES);
+        const double e2 = slack32 ? 2.0 * eps + epilogue32_slack(xv2, summary[2]) : 2.0 * eps;
+        thr_s[il] = (sv * (craw[pj] * T) - yraw[pj]) - e2;  // = |x|^2 - (r~_seed + 2 eps)
+    }
+    __syncthreads();
+}
+
+// MODE 1: seed = arg-min of r~ over the 2 lane halves and the WJ prototype wavefronts (ties: the lower index);
+// V = the type r~ was kept in.  Reuses the head of the ring as [WJ][128] values | [WJ][128] indices.
+template <typename V, int WJ>
+__device__ __forceinline__ void seed_argmin(char *smem, V (&bestv)[2], int (&bestj)[2], int wi, int wj, int64_t p0,
+                                            int64_t N, const int32_t *order, int64_t *seed) {
+    const int tid = threadIdx.x, lc = tid & 31, lh = (tid >> 5) & 1;
+    __syncthreads();
+    V *sv = reinterpret_cast<V *>(smem);
+    int *sj = reinterpret_cast<int *>(smem + WJ * 128 * 8);
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        const V ov = __shfl_xor(bestv[it], 32, 64);
+        const int oj = __shfl_xor(bestj[it], 32, 64);
+        if (ov < bestv[it] || (ov == bestv[it] && oj < bestj[it])) { bestv[it] = ov; bestj[it] = oj; }
+        if (lh == 0) {
+            sv[wj * 128 + wi * 64 + it * 32 + lc] = bestv[it];
+            sj[wj * 128 + wi * 64 + it * 32 + lc] = bestj[it];
+        }
+    }
+    __syncthreads();
+    if (tid < 128 && p0 + tid < N) {
+        V bv = sv[tid];
+        int bj = sj[tid];
+#pragma unroll
+        for (int w = 1; w < WJ; ++w) {
+            const V ov = sv[w * 128 + tid];
+            const int oj = sj[w * 128 + tid];
+            if (ov < bv || (ov == bv && oj < bj)) { bv = ov; bj = oj; }
+        }
+        seed[order ? (int64_t)order[p0 + tid] : p0 + tid] = (int64_t)bj;
+    }
+}
+
+// The marked prototypes of the LDS bitmask as an ascending list: a scan of the words' bit counts over the
+// wavefront, then every lane walks its own word.  Called by ONE whole wavefront; returns the list's length
+// (in every lane).  write = false: the length only.
+__device__ __forceinline__ uint32_t compact_marked(const uint32_t *mask, int nwords, int lane, uint16_t *out,
+                                                   bool write) {
+    uint32_t base = 0;
+    for (int w0 = 0; w0 < nwords; w0 += 64) {
+        const int w = w0 + lane;
+        uint32_t bits = (w < nwords) ? mask[w] : 0u;
+        const uint32_t cnt = __popc(bits);
+        uint32_t pre = cnt;  // inclusive scan over the wavefront
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t v = __shfl_up(pre, off, 64);
+            if (lane >= off) pre += v;
+        }
+        uint32_t pos = base + pre - cnt;
+        if (write)
+            while (bits) {
+                const int b = __ffs(bits) - 1;
+                bits &= bits - 1;
+                out[pos++] = (uint16_t)(w * 32 + b);
+            }
+        base += __shfl(pre, 63, 64);
+    }
+    return base;
+}
+
+// a sweep's workgroup publishes the length of its list (one lane)
+__device__ __forceinline__ void publish_list_length(uint32_t *ucount, uint32_t *sched_ctr,
+                                                    uint32_t len) {
+    ucount[blockIdx.x] = len;
+    atomicAdd(&sched_ctr[sched_bin(len)], 1u);  // bin counts of the exact stage's schedule (2b)
+    // sum of the list lengths (what the engine's policy looks at: 8 bytes D2H instead of nb x 4)
+    atomicAdd(reinterpret_cast<unsigned long long *>(sched_ctr + SCHED_SUM), (unsigned long long)len);
+}
+
 // MODE 0 (mark): the candidate sweep described above; samples in bucket order of `prev`,
 //   candidate prototypes of every 128-sample workgroup written to ulist / ucount.
 // MODE 1 (seed): the pre-pass when there is no previous winner to start from: natural sample
@@ -522,85 +691,10 @@ __global__ __launch_bounds__(FNT, 2) void sweep_i8_kernel(
     }
     int jlo = 0, jhi = -1;
     if constexpr (MODE == 0) {
-        for (int w = tid; w < nwords; w += FNT) mask[w] = 0u;
-        if (tid < 128) {
-            const int64_t p = p0 + tid;
-            int pj = -1;
-            if (p < N) pj = (int)prev[sample_at(p)];
-            prev_s[tid] = (pj >= 0 && pj < M) ? pj : -1;
-            thr_s[tid] = (p < N) ? -INFINITY : INFINITY;  // A = |x|^2 - thr: no bound yet / padding never marks
-        }
-        __syncthreads();
-        if (wave == 0) {  // range of the seeds: the sweep starts at the chunk holding the lowest
-            const int a = prev_s[lane], b = prev_s[lane + 64];
-            int lo = min(a >= 0 ? a : 0x7fffffff, b >= 0 ? b : 0x7fffffff), hi = max(a, b);
-#pragma unroll
-            for (int m = 1; m < 64; m <<= 1) {
-                lo = min(lo, __shfl_xor(lo, m, 64));
-                hi = max(hi, __shfl_xor(hi, m, 64));
-            }
-            if (lane == 0) {
-                misc[0] = (hi >= 0) ? lo : 0;
-                misc[1] = hi;
-            }
-        }
-        __syncthreads();
-        jlo = __builtin_amdgcn_readfirstlane(misc[0]);
-        jhi = __builtin_amdgcn_readfirstlane(misc[1]);
-        // The seeds of a workgroup sit in one chunk, except where the sorted order crosses a chunk
-        // border.  There the samples whose seed lies in a later chunk would sweep the first chunk(s)
-        // without a bound (and mark all of them): give those samples their bound up front, from
-        // the same exact integer products by v_dot4 (4 threads per sample, K split by 16-byte
-        // chunks).  Rare path: a handful of workgroups per launch.
-        if (jlo / BJ != jhi / BJ) {
-            const int il = tid >> 2, q = tid & 3;
-            const int64_t p = p0 + il;
-            const int pj = prev_s[il];
-            const bool need = p < N && pj >= 0 && pj / BJ != jlo / BJ;
-            int a0 = 0, a1 = 0, a2 = 0;
-            const int64_t i = sample_at(p < N ? p : N - 1);
-            if (need) {
-                const size_t xps = (size_t)N * dpad, wps = (size_t)w_rows * dpad;
-                const int8_t *xr = xplanes + (size_t)i * dpad;
-                const int wsw = (pj >> 2) & 3;
-                for (int ch = q; ch < dpad / 16; ch += 4) {
-                    const int8_t *wr = wplanes + ((size_t)(ch >> 2) * w_rows + pj) * FKT + (((ch & 3) ^ wsw) << 4);
-                    v4i_t xv[PLANES], wv[PLANES];
-#pragma unroll
-                    for (int pl = 0; pl < PLANES; ++pl) {
-                        xv[pl] = *reinterpret_cast<const v4i_t *>(xr + pl * xps + ch * 16);
-                        wv[pl] = *reinterpret_cast<const v4i_t *>(wr + pl * wps);
-                    }
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        a0 = __builtin_amdgcn_sdot4(xv[0][e], wv[0][e], a0, false);
-                        if constexpr (PLANES >= 2) {
-                            a1 = __builtin_amdgcn_sdot4(xv[0][e], wv[PLANES >= 2 ? 1 : 0][e], a1, false);
-                            a1 = __builtin_amdgcn_sdot4(xv[PLANES >= 2 ? 1 : 0][e], wv[0][e], a1, false);
-                        }
-                        if constexpr (PLANES == 3) {
-                            constexpr int P1 = PLANES >= 2 ? 1 : 0, P2 = PLANES >= 3 ? 2 : 0;
-                            a2 = __builtin_amdgcn_sdot4(xv[0][e], wv[P2][e], a2, false);
-                            a2 = __builtin_amdgcn_sdot4(xv[P1][e], wv[P1][e], a2, false);
-                            a2 = __builtin_amdgcn_sdot4(xv[P2][e], wv[0][e], a2, false);
-                        }
-                    }
-                }
-            }
-#pragma unroll
-            for (int m = 1; m <= 2; m <<= 1) {
-                a0 += __shfl_xor(a0, m, 64);
-                a1 += __shfl_xor(a1, m, 64);
-                a2 += __shfl_xor(a2, m, 64);
-            }
-            if (need && q == 0) {
-                const double T = sweep_T<PLANES>(a0, a1, a2);
-                const double sv = sx[i], xv2 = xx[i];
-                const double e2 = 2.0 * filter_eps(sv, l1x[i], xv2, summary[0], summary[1], summary[2], d, PLANES);
-                thr_s[il] = (sv * (craw[pj] * T) - yraw[pj]) - e2;  // = |x|^2 - (r~_seed + 2 eps)
-            }
-            __syncthreads();
-        }
+        seed_prologue<FNT>(mask, prev_s, thr_s, misc, tid, lane, wave, nwords, M, p0, N, prev, sample_at, jlo, jhi);
+        if (jlo / BJ != jhi / BJ)  // (4 threads per sample)
+            seed_bound_ahead<PLANES, 4, BJ>(thr_s, prev_s, tid, jlo, p0, N, d, dpad, xplanes, wplanes, w_rows, sx, l1x, xx,
+                                            yraw, craw, summary, sample_at, false);
     }
 
     // per-lane sample constants (2 samples: one per 32-column tile)
@@ -751,13 +845,6 @@ __global__ __launch_bounds__(FNT, 2) void sweep_i8_kernel(
                 between(g++);
             }
     };
-    auto wait_vm = [&](int n) {  // s_waitcnt vmcnt needs an immediate
-        if (n == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (n == DMA_TILE) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_TILE) : "memory");
-        else if (n == DMA_TILE + 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_TILE + 1) : "memory");
-        else if (n == 2 * DMA_TILE) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * DMA_TILE) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * DMA_TILE + 1) : "memory");
-    };
 
     // ---- pipeline -------------------------------------------------------------------------------
     // tile t lives in stage t % 3.  Per tile: [read k-step 1 of t] [products of k-step 0] -- own
@@ -769,7 +856,7 @@ __global__ __launch_bounds__(FNT, 2) void sweep_i8_kernel(
     for (int u = 0; u < n_pre; ++u) issue_ops(0, DMA_TILE);
     {   // groups 1 and 2 may stay in flight (group 2 opens a chunk iff nkt == 2)
         const int g2 = DMA_TILE + (nkt == 2 ? 1 : 0);
-        wait_vm(ntile > 2 ? DMA_TILE + g2 : (ntile > 1 ? DMA_TILE : 0));
+        wait_vm<DMA_TILE>(ntile > 2 ? DMA_TILE + g2 : (ntile > 1 ? DMA_TILE : 0));
     }
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -800,8 +887,8 @@ __global__ __launch_bounds__(FNT, 2) void sweep_i8_kernel(
         __builtin_amdgcn_sched_barrier(0);
         // (after the last tile this block is a no-op on stale data: no branch, so that the
         // compiler's LDS wait counting sees one path)
-        if (t + 2 < ntile) wait_vm(DMA_TILE + ((r_kt + 2 == nkt) ? 1 : 0));
-        else wait_vm(0);
+        if (t + 2 < ntile) wait_vm<DMA_TILE>(DMA_TILE + ((r_kt + 2 == nkt) ? 1 : 0));
+        else wait_vm<DMA_TILE>(0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
@@ -931,63 +1018,15 @@ __global__ __launch_bounds__(FNT, 2) void sweep_i8_kernel(
     }
 
     if constexpr (MODE == 1) {
-        // seed = arg-min of r~ over the 2 lane halves and the 4 prototype wavefronts
-        __syncthreads();
-        double *sv = reinterpret_cast<double *>(smem);          // [4][128]
-        int *sj = reinterpret_cast<int *>(smem + 4 * 128 * 8);  // [4][128]
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const double ov = __shfl_xor(bestv[it], 32, 64);
-            const int oj = __shfl_xor(bestj[it], 32, 64);
-            if (ov < bestv[it] || (ov == bestv[it] && oj < bestj[it])) { bestv[it] = ov; bestj[it] = oj; }
-            if (lh == 0) {
-                sv[wj * 128 + wi * 64 + it * 32 + lc] = bestv[it];
-                sj[wj * 128 + wi * 64 + it * 32 + lc] = bestj[it];
-            }
-        }
-        __syncthreads();
-        if (tid < 128 && p0 + tid < N) {
-            double bv = sv[tid];
-            int bj = sj[tid];
-#pragma unroll
-            for (int w = 1; w < 4; ++w) {
-                const double ov = sv[w * 128 + tid];
-                const int oj = sj[w * 128 + tid];
-                if (ov < bv || (ov == bv && oj < bj)) { bv = ov; bj = oj; }
-            }
-            seed[sample_at(p0 + tid)] = (int64_t)bj;
-        }
+        seed_argmin<double, 4>(smem, bestv, bestj, wi, wj, p0, N, order, seed);
         return;
     }
 
     // ---- compact the marked prototypes, ascending ------------------------------------------------
     __syncthreads();
     if (wave == 0) {
-        uint32_t base = 0;
-        uint16_t *out = ulist + (size_t)blockIdx.x * ulist_stride;
-        for (int w0 = 0; w0 < nwords; w0 += 64) {
-            const int w = w0 + lane;
-            uint32_t bits = (w < nwords) ? mask[w] : 0u;
-            const uint32_t cnt = __popc(bits);
-            uint32_t pre = cnt;  // inclusive scan over the wavefront
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t v = __shfl_up(pre, off, 64);
-                if (lane >= off) pre += v;
-            }
-            uint32_t pos = base + pre - cnt;
-            while (bits) {
-                const int b = __ffs(bits) - 1;
-                bits &= bits - 1;
-                out[pos++] = (uint16_t)(w * 32 + b);
-            }
-            base += __shfl(pre, 63, 64);
-        }
-        if (lane == 0) {
-            ucount[blockIdx.x] = base;
-            atomicAdd(&sched_ctr[sched_bin(base)], 1u);  // bin counts of the exact stage's schedule (2b)
-            // sum of the list lengths (what the engine's policy looks at: 8 bytes D2H instead of nb x 4)
-            atomicAdd(reinterpret_cast<unsigned long long *>(sched_ctr + SCHED_SUM), (unsigned long long)base);
-        }
+        const uint32_t len = compact_marked(mask, nwords, lane, ulist + (size_t)blockIdx.x * ulist_stride, true);
+        if (lane == 0) publish_list_length(ucount, sched_ctr, len);
     }
 }
 
@@ -996,12 +1035,12 @@ __global__ __launch_bounds__(FNT, 2) void sweep_i8_kernel(
 // the same work: workgroup tile 128 samples x 256 prototypes, 24 KB ring stages and ONE set of chunk
 // tables, 79.5 KB of LDS in all, so that TWO workgroups share a CU: the wavefronts of a SIMD belong
 // to different workgroups -- they are not tied to the same barrier, and one workgroup's prologue,
-// chunk epilogues and list compaction run under the other's products.  NW = 4 wavefronts as 2 x 2
-// (wavefront tile 64 x 128, two wavefronts per SIMD) or NW = 8 as 2 x 4 (64 x 64 tiles, 64
-// accumulator registers, <= 128 VGPRs: FOUR wavefronts per SIMD -- the one launched).
-constexpr int S4_NT = 256;
+// chunk epilogues and list compaction run under the other's products.  8 wavefronts as 2 (samples) x 4
+// (prototypes), wavefront tile 64 x 64: 64 accumulator registers, <= 128 VGPRs, FOUR wavefronts per
+// SIMD -- rather than 4 wavefronts of 64 x 128 (two per SIMD).  Measured, ms per launch, 4 / 8
+// wavefronts: C4 1.13 / 1.04, C3 0.88 / 0.71, C5 shard 4.96 / 4.55.
 struct Sweep4Lds {
-    static constexpr int JT = 4, BJ = 256;
+    static constexpr int BJ = 256;
     static constexpr int X_BYTES = 128 * FKT, W_BYTES = BJ * FKT, STAGE = X_BYTES + W_BYTES;  // 8 + 16 KB
     static constexpr int TAB = BJ * 8;
     static constexpr int OFF_TAB = FSTAGES * STAGE;
@@ -1009,31 +1048,28 @@ struct Sweep4Lds {
     static constexpr int OFF_PREV = OFF_THR + 128 * 8;
     static constexpr int OFF_EPS = OFF_PREV + 128 * 4;   // 2 eps_i per sample (MODE 0)
     static constexpr int OFF_MASK = OFF_EPS + 128 * 8;
-    static constexpr int MAX_M = 8192;                   // bitmask of the marked prototypes: 1 KB
+    static constexpr int MAX_M = SWEEP4_MAX_M;           // bitmask of the marked prototypes: 1 KB
     static constexpr int OFF_MISC = OFF_MASK + MAX_M / 8;
     static constexpr int BYTES = OFF_MISC + 16;
 };
 static_assert(Sweep4Lds::BYTES <= 81920, "two workgroups per CU");
 
-template <int MODE, int NW>
-__global__ __launch_bounds__(NW * 64, NW / 2) void sweep4_i8_kernel(  // (HIP: the second figure is waves per SIMD)
+template <int MODE>
+__global__ __launch_bounds__(FNT, 4) void sweep4_i8_kernel(  // (HIP: the second figure is waves per SIMD)
     const int8_t *__restrict__ xplanes, const double *__restrict__ sx,
     const double *__restrict__ l1x, const double *__restrict__ xx, int64_t N, int d, int dpad,
     const int8_t *__restrict__ wplanes, const float *__restrict__ ytab_g,
     const float *__restrict__ ctab_g, const double *__restrict__ yraw,
     const double *__restrict__ craw, const double *__restrict__ summary, int M,
     const int64_t *__restrict__ prev, const int32_t *__restrict__ order,
-    uint16_t *__restrict__ ulist, int ulist_stride, uint32_t *__restrict__ ucount, int w_rows,
-    int64_t *__restrict__ seed, int jstride, int nkt_used, const int32_t *__restrict__ kt_sel,
-    uint32_t *__restrict__ sched_ctr, const float *__restrict__ chk_g,
+    uint16_t *__restrict__ ulist, int ulist_stride, uint32_t *__restrict__ ucount,
+    int64_t *__restrict__ seed, int jstride, int w_rows, int nkt_used,
+    const int32_t *__restrict__ kt_sel, uint32_t *__restrict__ sched_ctr, const float *__restrict__ chk_g,
     const int32_t *__restrict__ retry_groups, const unsigned long long *__restrict__ retry_len) {
     using L = Sweep4Lds;
-    // NW wavefronts as 2 (samples) x WJ (prototypes), wavefront tile 64 x 32 JT: 4 -> 64 x 128,
-    // 8 -> 64 x 64 (64 accumulator registers: <= 128 VGPRs, four wavefronts per SIMD)
-    constexpr int NT = NW * 64, WJ = NW / 2, JT = 8 / WJ, BJ = L::BJ, PLANES = 1;
-    static_assert(NW == 4 || NW == 8, "4 or 8 wavefronts");
-    constexpr int XI = 8 / NW, WI = 16 / NW;  // LDS-DMA instructions per wave and tile: X rows, W rows
-    constexpr int DMA_TILE = XI + WI;
+    // 2 (samples) x WJ (prototypes) wavefronts, wavefront tile 64 x 32 JT
+    constexpr int WJ = 4, JT = 2, BJ = L::BJ, PLANES = 1;
+    constexpr int DMA_TILE = 3;  // LDS-DMA instructions per wave and tile: 16 X rows, 2 x 16 W rows
     __shared__ __attribute__((aligned(16))) char smem[L::BYTES];
     double *thr_s = reinterpret_cast<double *>(smem + L::OFF_THR);
     int *prev_s = reinterpret_cast<int *>(smem + L::OFF_PREV);
@@ -1060,15 +1096,9 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void sweep4_i8_kernel(  // (HIP: t
 
     auto sample_at = [&](int64_t p) -> int64_t { return (MODE == 0 || order) ? (int64_t)order[p] : p; };
     // every thread's own loads first (see sweep_i8_kernel)
-    int64_t i_dr[XI];
-    int dc[XI];
-#pragma unroll
-    for (int u = 0; u < XI; ++u) {  // DMA: wave w loads X rows 16 XI w .., 16 per instruction
-        const int r = 16 * (XI * wave + u) + (lane >> 2);
-        const int64_t xpos = (p0 + r < N) ? (p0 + r) : (N - 1);
-        i_dr[u] = sample_at(xpos);
-        dc[u] = (lane & 3) ^ ((r >> 2) & 3);
-    }
+    const int dr = 16 * wave + (lane >> 2);  // DMA: wave w loads X rows 16 w .. 16 w + 15
+    const int64_t i_dr = sample_at((p0 + dr < N) ? (p0 + dr) : (N - 1));
+    const int dc = (lane & 3) ^ ((dr >> 2) & 3);
     int64_t i_il[2];
     double s_i[2], l1_i[2], xx_i[2];
 #pragma unroll
@@ -1084,62 +1114,11 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void sweep4_i8_kernel(  // (HIP: t
     }
     int jlo = 0, jhi = -1;
     if constexpr (MODE == 0) {
-    for (int w = tid; w < nwords; w += NT) mask[w] = 0u;
-    if (tid < 128) {
-        const int64_t p = p0 + tid;
-        int pj = -1;
-        if (p < N) pj = (int)prev[sample_at(p)];
-        prev_s[tid] = (pj >= 0 && pj < M) ? pj : -1;
-        thr_s[tid] = (p < N) ? -INFINITY : INFINITY;
+        seed_prologue<FNT>(mask, prev_s, thr_s, misc, tid, lane, wave, nwords, M, p0, N, prev, sample_at, jlo, jhi);
+        if (jlo / BJ != jhi / BJ)  // (thr_i with the slack of the float32 epilogue)
+            seed_bound_ahead<PLANES, 4, BJ>(thr_s, prev_s, tid, jlo, p0, N, d, dpad, xplanes, wplanes, w_rows, sx, l1x, xx,
+                                            yraw, craw, summary, sample_at, true);
     }
-    __syncthreads();
-    if (wave == 0) {
-        const int a = prev_s[lane], b = prev_s[lane + 64];
-        int lo = min(a >= 0 ? a : 0x7fffffff, b >= 0 ? b : 0x7fffffff), hi = max(a, b);
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            lo = min(lo, __shfl_xor(lo, m, 64));
-            hi = max(hi, __shfl_xor(hi, m, 64));
-        }
-        if (lane == 0) {
-            misc[0] = (hi >= 0) ? lo : 0;
-            misc[1] = hi;
-        }
-    }
-    __syncthreads();
-    jlo = __builtin_amdgcn_readfirstlane(misc[0]);
-    jhi = __builtin_amdgcn_readfirstlane(misc[1]);
-    if (jlo / BJ != jhi / BJ) {  // seeds in a later chunk: their bound up front (TPS threads per sample)
-        constexpr int TPS = NT / 128;
-        const int il = tid / TPS, q = tid % TPS;
-        const int64_t p = p0 + il;
-        const int pj = prev_s[il];
-        const bool need = p < N && pj >= 0 && pj / BJ != jlo / BJ;
-        int a0 = 0;
-        const int64_t i = sample_at(p < N ? p : N - 1);
-        if (need) {
-            const int8_t *xr = xplanes + (size_t)i * dpad;
-            const int wsw = (pj >> 2) & 3;
-            for (int ch = q; ch < dpad / 16; ch += TPS) {
-                const int8_t *wr = wplanes + ((size_t)(ch >> 2) * w_rows + pj) * FKT + (((ch & 3) ^ wsw) << 4);
-                const v4i_t xv = *reinterpret_cast<const v4i_t *>(xr + ch * 16);
-                const v4i_t wv = *reinterpret_cast<const v4i_t *>(wr);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) a0 = __builtin_amdgcn_sdot4(xv[e], wv[e], a0, false);
-            }
-        }
-#pragma unroll
-        for (int m = 1; m < TPS; m <<= 1) a0 += __shfl_xor(a0, m, 64);
-        if (need && q == 0) {
-            const double T = sweep_T<PLANES>(a0, 0, 0);
-            const double sv = sx[i], xv2 = xx[i];
-            const double e2 = 2.0 * filter_eps(sv, l1x[i], xv2, summary[0], summary[1], summary[2], d, PLANES) +
-                              epilogue32_slack(xv2, summary[2]);
-            thr_s[il] = (sv * (craw[pj] * T) - yraw[pj]) - e2;
-        }
-        __syncthreads();
-    }
-    }  // MODE == 0
 
     // 2 eps_i and A_i = |x_i|^2 - thr_i live in LDS between the chunk epilogues (eight registers
     // the 8-wavefront shape does not have)
@@ -1157,10 +1136,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void sweep4_i8_kernel(  // (HIP: t
     float bestv[2] = {INFINITY, INFINITY};  // MODE 1: running arg-min of r~ (float32: any seed will do)
     int bestj[2] = {0, 0};
 
-    const int8_t *xsrc[XI];
-#pragma unroll
-    for (int u = 0; u < XI; ++u) xsrc[u] = xplanes + (size_t)i_dr[u] * dpad + dc[u] * 16;
-    if constexpr (XI == 2) xsrc[XI - 1] -= 1024;  // its DMA carries the immediate offset 1024 (for the LDS side)
+    const int8_t *xsrc = xplanes + (size_t)i_dr * dpad + dc * 16;
     // MODE 1 may look at a sample of the k-tiles only (kt_sel, see dbgsom_bmu_filtered)
     const int nkt_full = dpad / FKT;  // >= 2 (filter_dpad)
     const int nkt = (MODE == 1 && nkt_used >= 2 && nkt_used < nkt_full) ? nkt_used : nkt_full;
@@ -1170,11 +1146,11 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void sweep4_i8_kernel(  // (HIP: t
     const int c0 = jlo / BJ;
 
     int i_kt = 0, i_chunk = c0, i_stage = 0;
-    // The 6 LDS-DMA instructions of a tile: X rows 16 (2 w + u) .. (ops 0, 1), then the wave's four
-    // consecutive KiB of the chunk's W rows (ops 2 + v: rows 16 (4 w + v) ..) -- ONE address and one
-    // LDS base for the four, the KiB steps sit in the instruction's immediate offset (it moves the
-    // global and the LDS address alike).  Ops [lo, hi) are issued, hi == DMA_TILE advances.
-    const int8_t *wlane = wplanes + 16u * lane + 1024u * WI * wave;  // this lane's 16 bytes of the wave's WI KiB
+    // The 3 LDS-DMA instructions of a tile: X rows 16 w .. (op 0), then the wave's two consecutive KiB
+    // of the chunk's W rows (ops 1 + v: rows 16 (2 w + v) ..) -- ONE address and one LDS base for the
+    // two, the KiB step sits in the instruction's immediate offset (it moves the global and the LDS
+    // address alike).  Ops [lo, hi) are issued, hi == DMA_TILE advances.
+    const int8_t *wlane = wplanes + 16u * lane + 2048u * wave;  // this lane's 16 bytes of the wave's 2 KiB
     const size_t w_tile_step = (size_t)w_rows * FKT;
     size_t i_woff = (size_t)c0 * BJ * FKT;  // (i_kt w_rows + i_chunk BJ) FKT, kept incrementally
     auto issue_ops = [&](int lo, int hi) {
@@ -1182,17 +1158,11 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void sweep4_i8_kernel(  // (HIP: t
         const int i_tile = tile_of(i_kt);
         const int k0 = i_tile * FKT;
         if constexpr (MODE == 1) i_woff = ((size_t)i_tile * w_rows + (size_t)i_chunk * BJ) * FKT;
-        if (0 >= lo && 0 < hi) fdma16(xsrc[0] + k0, stage + 1024 * XI * wave);
-        if constexpr (XI == 2)
-            if (1 >= lo && 1 < hi) fdma16_off<1024>(xsrc[XI - 1] + k0, stage + 1024 * XI * wave);
+        if (0 >= lo && 0 < hi) fdma16(xsrc + k0, stage + 1024 * wave);
         const int8_t *wsrc = wlane + i_woff;
-        char *wdst = stage + L::X_BYTES + 1024 * WI * wave;
-        if (XI + 0 >= lo && XI + 0 < hi) fdma16(wsrc, wdst);
-        if (XI + 1 >= lo && XI + 1 < hi) fdma16_off<1024>(wsrc, wdst);
-        if constexpr (WI == 4) {
-            if (XI + 2 >= lo && XI + 2 < hi) fdma16_off<2048>(wsrc, wdst);
-            if (XI + 3 >= lo && XI + 3 < hi) fdma16_off<3072>(wsrc, wdst);
-        }
+        char *wdst = stage + L::X_BYTES + 2048 * wave;
+        if (1 >= lo && 1 < hi) fdma16(wsrc, wdst);
+        if (2 >= lo && 2 < hi) fdma16_off<1024>(wsrc, wdst);
         if (hi == DMA_TILE) {
             i_stage = (i_stage == (FSTAGES - 1) * L::STAGE) ? 0 : i_stage + L::STAGE;
             i_woff += w_tile_step;
@@ -1258,19 +1228,12 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void sweep4_i8_kernel(  // (HIP: t
             between(jh >> 1);
         }
     };
-    auto wait_vm = [&](int n) {  // s_waitcnt vmcnt needs an immediate
-        if (n == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (n == DMA_TILE) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_TILE) : "memory");
-        else if (n == DMA_TILE + 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_TILE + 1) : "memory");
-        else if (n == 2 * DMA_TILE) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * DMA_TILE) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * DMA_TILE + 1) : "memory");
-    };
 
     // ---- pipeline: as sweep_i8_kernel (tile t in stage t % 3, one barrier per tile) ---------------
     issue_tables(c0);  // first in the queue: complete with the first tile
     const int n_pre = ntile < 3 ? ntile : 3;
     for (int u = 0; u < n_pre; ++u) issue_ops(0, DMA_TILE);
-    wait_vm(ntile > 2 ? 2 * DMA_TILE : (ntile > 1 ? DMA_TILE : 0));
+    wait_vm<DMA_TILE>(ntile > 2 ? 2 * DMA_TILE : (ntile > 1 ? DMA_TILE : 0));
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     Frags f0, f1;
@@ -1290,8 +1253,8 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void sweep4_i8_kernel(  // (HIP: t
         __builtin_amdgcn_sched_barrier(0);
         // own DMAs of tile t + 1 landed: what may stay in flight is tile t + 2 (and the table piece
         // issued behind the previous barrier, which sits between tiles t + 2 and t + 3 in the queue)
-        if (t + 2 < ntile) wait_vm(DMA_TILE + (tab_pending ? 1 : 0));
-        else wait_vm(0);
+        if (t + 2 < ntile) wait_vm<DMA_TILE>(DMA_TILE + (tab_pending ? 1 : 0));
+        else wait_vm<DMA_TILE>(0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
@@ -1334,7 +1297,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void sweep4_i8_kernel(  // (HIP: t
                             const bool sel = jl == want;
                             a0s = sel ? acc[jt][it][r] : a0s;
                             jls = sel ? jl : jls;
-                            if constexpr (NW == 8) __builtin_amdgcn_sched_barrier(0);
+                            __builtin_amdgcn_sched_barrier(0);
                         }
                     if (jls >= 0)
                         thr_s[wi * 64 + it * 32 + lc] =
@@ -1417,9 +1380,9 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void sweep4_i8_kernel(  // (HIP: t
                         if constexpr (MODE == 0) {
                             word |= (uint32_t)((uint32_t)pass != 0u) << (8 * g + i);
                             word |= (uint32_t)((uint32_t)(pass >> 32) != 0u) << (4 + 8 * g + i);
-                            // (8 wavefronts: one compare pair at a time -- the scalar masks of many
-                            // hoisted compares spill, and spilled SGPRs cost VGPRs beyond the 128)
-                            if constexpr (NW == 8) __builtin_amdgcn_sched_barrier(0);
+                            // (one compare pair at a time -- the scalar masks of many hoisted compares
+                            // spill, and spilled SGPRs cost VGPRs beyond the 128)
+                            __builtin_amdgcn_sched_barrier(0);
                         }
                     }
                 }
@@ -1448,61 +1411,13 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void sweep4_i8_kernel(  // (HIP: t
     }
 
     if constexpr (MODE == 1) {
-        // seed = arg-min of r~ over the 2 lane halves and the 2 prototype wavefronts
-        __syncthreads();
-        float *sv = reinterpret_cast<float *>(smem);             // [WJ][128]
-        int *sj = reinterpret_cast<int *>(smem + WJ * 128 * 8);  // [WJ][128]
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const float ov = __shfl_xor(bestv[it], 32, 64);
-            const int oj = __shfl_xor(bestj[it], 32, 64);
-            if (ov < bestv[it] || (ov == bestv[it] && oj < bestj[it])) { bestv[it] = ov; bestj[it] = oj; }
-            if (lh == 0) {
-                sv[wj * 128 + wi * 64 + it * 32 + lc] = bestv[it];
-                sj[wj * 128 + wi * 64 + it * 32 + lc] = bestj[it];
-            }
-        }
-        __syncthreads();
-        if (tid < 128 && p0 + tid < N) {
-            float bv = sv[tid];
-            int bj = sj[tid];
-#pragma unroll
-            for (int w = 1; w < WJ; ++w) {
-                const float ov = sv[w * 128 + tid];
-                const int oj = sj[w * 128 + tid];
-                if (ov < bv || (ov == bv && oj < bj)) { bv = ov; bj = oj; }
-            }
-            seed[sample_at(p0 + tid)] = (int64_t)bj;
-        }
+        seed_argmin<float, WJ>(smem, bestv, bestj, wi, wj, p0, N, order, seed);
         return;
     }
     __syncthreads();
     if (wave == 0) {  // compact the marked prototypes, ascending
-        uint32_t base = 0;
-        uint16_t *out = ulist + (size_t)blockIdx.x * ulist_stride;
-        for (int w0 = 0; w0 < nwords; w0 += 64) {
-            const int w = w0 + lane;
-            uint32_t bits = (w < nwords) ? mask[w] : 0u;
-            const uint32_t cnt = __popc(bits);
-            uint32_t pre = cnt;
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t v = __shfl_up(pre, off, 64);
-                if (lane >= off) pre += v;
-            }
-            uint32_t pos = base + pre - cnt;
-            while (bits) {
-                const int b = __ffs(bits) - 1;
-                bits &= bits - 1;
-                out[pos++] = (uint16_t)(w * 32 + b);
-            }
-            base += __shfl(pre, 63, 64);
-        }
-        if (lane == 0) {
-            ucount[blockIdx.x] = base;
-            atomicAdd(&sched_ctr[sched_bin(base)], 1u);  // bin counts of the exact stage's schedule (2b)
-            // sum of the list lengths (what the engine's policy looks at: 8 bytes D2H instead of nb x 4)
-            atomicAdd(reinterpret_cast<unsigned long long *>(sched_ctr + SCHED_SUM), (unsigned long long)base);
-        }
+        const uint32_t len = compact_marked(mask, nwords, lane, ulist + (size_t)blockIdx.x * ulist_stride, true);
+        if (lane == 0) publish_list_length(ucount, sched_ctr, len);
     }
 }
 
@@ -1569,7 +1484,7 @@ __global__ __launch_bounds__(256) void sched_fill_kernel(const uint32_t *__restr
 // per epoch instead of N x M digit products; what it yields depends on the data alone (blobs: the
 // sample's own cluster; isotropic data: the whole map -- the engine's policy measures it with a
 // counting-only launch before it lets the exact stage loose on such lists).
-constexpr int PRUNE_MAX_M = 8192;  // the gap matrix: 4 M^2 bytes (256 MB here)
+// (PRUNE_MAX_M prototypes at the most: the gap matrix is 4 M^2 bytes, filter_form.h)
 
 // relative size of what the lower digits and the rounding of the quantisation add to a feature:
 // (2^15 + 2^7 + 1/2 + 3 u F) / F
@@ -1907,27 +1822,8 @@ __global__ __launch_bounds__(256, 6) void prune_mark_kernel(
         }
     }
     __syncthreads();
-    if (wave == 0) {  // compact the marked prototypes, ascending (as the sweeps do)
-        uint32_t base = 0;
-        uint16_t *out = ulist + (size_t)group * ulist_stride;
-        for (int w0 = 0; w0 < nwords; w0 += 64) {
-            const int w = w0 + lane;
-            uint32_t bits = (w < nwords) ? mask[w] : 0u;
-            const uint32_t cnt = __popc(bits);
-            uint32_t pre = cnt;
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t v = __shfl_up(pre, off, 64);
-                if (lane >= off) pre += v;
-            }
-            uint32_t pos = base + pre - cnt;
-            if (!count_only)
-                while (bits) {
-                    const int b = __ffs(bits) - 1;
-                    bits &= bits - 1;
-                    out[pos++] = (uint16_t)(w * 32 + b);
-                }
-            base += __shfl(pre, 63, 64);
-        }
+    if (wave == 0) {  // (count_only: the length alone)
+        const uint32_t base = compact_marked(mask, nwords, lane, ulist + (size_t)group * ulist_stride, !count_only);
         if (lane == 0) {
             if (retry_mode == 1 && base > retry_above) {
                 retry_groups[atomicAdd(retry_len, 1ull)] = (int32_t)group;
@@ -2431,58 +2327,41 @@ struct FilterWs {
     void *sort_ws;
     int64_t nb, Mpad;
 };
-static size_t carve_filter(FilterWs *f, char *base, int64_t N, int64_t d, int64_t M) {
+// The layout of the workspace: every field takes its bytes where it is named, in this order.  base == nullptr
+// (and out == nullptr): only the total.
+static size_t carve_filter(FilterWs *out, char *base, int64_t N, int64_t d, int64_t M) {
     const int64_t Mpad = (M + 511) / 512 * 512, nb = (N + 127) / 128, dpad = filter_dpad(d);  // whole 512-prototype chunks
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
-    const size_t otk = take(256);
-    const size_t ow = take((size_t)3 * Mpad * dpad), ows = take((size_t)3 * Mpad * dpad);
-    const size_t osc = take((size_t)M * 8), ol1 = take((size_t)M * 8), on0 = take((size_t)M * 8);
-    const size_t ores = take((size_t)M * 8);
-    const size_t o0 = take((size_t)Mpad * 8), o1 = take((size_t)Mpad * 8), o2 = take(64);
-    const size_t o8 = take((size_t)Mpad * 8), o9 = take((size_t)Mpad * 8);
-    const size_t o10 = take((size_t)Mpad * 8), o11 = take((size_t)Mpad * 8), o12 = take((size_t)Mpad * 8);
-    const size_t o13 = take((size_t)(dpad / FKT) * 8), o14 = take((size_t)SW_MAX_KT * 4);
-    const size_t o18 = take((size_t)6 * Mpad * 4), o19 = take((size_t)(Mpad / 256) * 16);
-    const size_t o15 = take((size_t)TS_RB * 2 * dpad * 8);
-    const size_t o3 = take((size_t)nb * Mpad * 2), o4 = take((size_t)nb * 4);
-    const size_t o5 = take((size_t)N * 8), o6 = take((size_t)N * 4);
-    const size_t o7 = take(bucket_sort_workspace_bytes(N, M + 1));   // (+ 1: the "decided" bucket of the deferred form, 2d)
-    const size_t o16 = take((size_t)nb * 4), o17 = take((size_t)(SCHED_CTR + 2 * RF_CTR + 4) * 4);
-    const size_t o24 = take((size_t)2 * nb * 4);
-    const size_t o25 = take((size_t)N * 8), o26 = take((size_t)N * 4), o27 = take((size_t)N * 8);
-    const size_t o22 = take((size_t)N * 8), o23 = take((size_t)nb);
-    const size_t o29 = take((size_t)(N < OV_CAP ? N : OV_CAP) * OV_REC * 2);
     const int64_t Mg = (M + 63) / 64 * 64;
-    const size_t o20 = take(M <= PRUNE_MAX_M ? (size_t)Mg * Mg * 4 : 0);
-    const size_t o21 = take((size_t)nb * 4);
-    const size_t o28 = take((size_t)Mg * 4);
-    if (f) {
-        f->retry = (int32_t *)(base + o21);
-        f->nnub = (uint32_t *)(base + o28);
-        f->ovf_cand = (uint16_t *)(base + o29);
-        f->cand = (unsigned long long *)(base + o22); f->gflag = (uint8_t *)(base + o23);
-        f->rbest = (int64_t *)(base + o25); f->order2 = (int32_t *)(base + o26); f->ovf = (int32_t *)(base + o27);
-        f->rf_ctr = (unsigned long long *)(base + o17 + (size_t)SCHED_CTR * 4);
-        f->rf_qlen = (uint32_t *)(base + o17 + (size_t)(SCHED_CTR + 2 * RF_CTR) * 4);
-        f->rf_queue = (int32_t *)(base + o24);
-        f->gap = M <= PRUNE_MAX_M ? (float *)(base + o20) : nullptr; f->Mg = Mg;
-        f->tickets = (uint32_t *)(base + otk);
-        f->sched = (int32_t *)(base + o16); f->sched_ctr = (uint32_t *)(base + o17);
-        f->wt = (int8_t *)(base + ow); f->wt_sub = (int8_t *)(base + ows);
-        f->wscale = (double *)(base + osc); f->wl1 = (double *)(base + ol1); f->wn0 = (double *)(base + on0);
-        f->wres16 = (double *)(base + ores);
-        f->ctab = (double *)(base + o0); f->yypad = (double *)(base + o1);
-        f->ctab_sub = (double *)(base + o8); f->yy_sub = (double *)(base + o9);
-        f->ictab = (double *)(base + o10); f->yctab = (double *)(base + o11);
-        f->yy_part = (double *)(base + o12);
-        f->tile_score = (double *)(base + o13); f->kt_sel = (int32_t *)(base + o14);
-        f->tab32 = (float *)(base + o18); f->chk32 = (float *)(base + o19);
-        f->tile_part = (double *)(base + o15);
-        f->summary = (double *)(base + o2); f->ulist = (uint16_t *)(base + o3);
-        f->ucount = (uint32_t *)(base + o4); f->seed = (int64_t *)(base + o5);
-        f->order = (int32_t *)(base + o6); f->sort_ws = base + o7; f->nb = nb; f->Mpad = Mpad;
-    }
+    FilterWs scratch;
+    FilterWs &f = out ? *out : scratch;
+    size_t off = 0;
+    auto take = [&](auto *&field, size_t bytes) {
+        field = base ? reinterpret_cast<std::remove_reference_t<decltype(field)>>(base + off) : nullptr;
+        off += align_up(bytes);
+    };
+    const size_t planes = (size_t)3 * Mpad * dpad, m8 = (size_t)M * 8, mp8 = (size_t)Mpad * 8;
+    take(f.tickets, 256);
+    take(f.wt, planes); take(f.wt_sub, planes);
+    take(f.wscale, m8); take(f.wl1, m8); take(f.wn0, m8); take(f.wres16, m8);
+    take(f.ctab, mp8); take(f.yypad, mp8); take(f.summary, 64);
+    take(f.ctab_sub, mp8); take(f.yy_sub, mp8); take(f.ictab, mp8); take(f.yctab, mp8); take(f.yy_part, mp8);
+    take(f.tile_score, (size_t)(dpad / FKT) * 8); take(f.kt_sel, (size_t)SW_MAX_KT * 4);
+    take(f.tab32, (size_t)6 * Mpad * 4); take(f.chk32, (size_t)(Mpad / 256) * 16);
+    take(f.tile_part, (size_t)TS_RB * 2 * dpad * 8);
+    take(f.ulist, (size_t)nb * Mpad * 2); take(f.ucount, (size_t)nb * 4);
+    take(f.seed, (size_t)N * 8); take(f.order, (size_t)N * 4);
+    take(f.sort_ws, bucket_sort_workspace_bytes(N, M + 1));   // (+ 1: the "decided" bucket of the deferred form, 2d)
+    take(f.sched, (size_t)nb * 4); take(f.sched_ctr, (size_t)(SCHED_CTR + 2 * RF_CTR + 4) * 4);
+    f.rf_ctr = base ? reinterpret_cast<unsigned long long *>(f.sched_ctr + SCHED_CTR) : nullptr;   // (behind the schedule's)
+    f.rf_qlen = base ? f.sched_ctr + SCHED_CTR + 2 * RF_CTR : nullptr;
+    take(f.rf_queue, (size_t)2 * nb * 4);
+    take(f.rbest, (size_t)N * 8); take(f.order2, (size_t)N * 4); take(f.ovf, (size_t)N * 8);
+    take(f.cand, (size_t)N * 8); take(f.gflag, (size_t)nb);
+    take(f.ovf_cand, (size_t)(N < OV_CAP ? N : OV_CAP) * OV_REC * 2);
+    take(f.gap, M <= PRUNE_MAX_M ? (size_t)Mg * Mg * 4 : 0);
+    if (M > PRUNE_MAX_M) f.gap = nullptr;
+    take(f.retry, (size_t)nb * 4); take(f.nnub, (size_t)Mg * 4);
+    f.Mg = Mg; f.nb = nb; f.Mpad = Mpad;
     return off;
 }
 
@@ -2545,17 +2424,6 @@ size_t dbgsom_bmu_filtered_workspace_bytes(int64_t N, int64_t d, int64_t M) {
     return carve_filter(nullptr, nullptr, N, d, M);
 }
 
-/* shape of the one-product candidate sweep for this map: always 4 (sweep4_i8_kernel, 128 x 256 tile,
- * two workgroups per CU) rather than 8 (sweep_i8_kernel<0,1,JT>, one per CU, which only maps beyond
- * sweep4_i8_kernel's bitmask get).  Measured on the four BASELINE shapes (ms per launch, 8 / 4):
- * C4 1.37 / 1.11, C3 1.12 / 0.88, C5 shard 4.99 / 4.83, C2 0.059 / 0.058 -- the small shape
- * everywhere, although it reads the X plane once per 256 prototypes instead of once per 512 (C5:
- * 16.4 GB per launch, 3.4 TB/s). */
-int dbgsom_sweep_shape(int64_t M, int64_t d) {
-    (void)M; (void)d;
-    return 4;
-}
-
 int dbgsom_bmu_filtered(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx,
                         const double *xx_dev, const void *xplanes_dev, const double *W_dev,
                         int64_t M, const double *ww_dev, const int64_t *prev_idx_dev,
@@ -2587,333 +2455,320 @@ int dbgsom::filter_stage_ms(FilterAux &aux, double *ms5) {
     return DBGSOM_OK;
 }
 
-int dbgsom::launch_bmu_filtered(const FilteredCall &call) {
-    const void *X_dev = call.X; const int x_dtype = call.x_dtype; const int64_t N = call.N, d = call.d, ldx = call.ldx;
-    const double *xx_dev = call.xx; const void *xplanes_dev = call.xplanes; const double *W_dev = call.W;
-    const int64_t M = call.M; const double *ww_dev = call.ww; const int64_t *prev_idx_dev = call.prev_idx;
-    const int32_t *order_dev = call.order; int seed_stride = call.seed_stride, sweep_planes = call.sweep_planes;
-    const int round_f32 = call.round_f32; int64_t *idx_dev = call.idx; double *dist_dev = call.dist;
-    void *workspace_dev = call.ws; const size_t workspace_bytes = call.ws_bytes; void *stream = (void *)call.stream;
-    FilterAux &aux = call.aux ? *call.aux : g_aux;
-    StageTimer &g_timer = aux.timer;
-    SideStream &g_side = aux.side;
-    const double *g_hint_dist = call.hint_dist, *g_hint_shift = call.hint_shift;
-    // sweep4_i8_kernel runs 8 wavefronts of 64 x 64 tiles (<= 128 VGPRs: four wavefronts per SIMD, two
-    // workgroups per CU) rather than 4 of 64 x 128 (two wavefronts per SIMD).  Measured, ms per launch,
-    // 4 / 8: C4 1.13 / 1.04, C3 0.88 / 0.71, C5 shard 4.96 / 4.55
-    // DBGSOM_SEED_FULL: the seed pre-pass looks at EVERY prototype and every feature (as expensive
-    // as the sweep it seeds; what weakly clustered data needs -- the engine's policy decides)
-    const bool seed_full = (seed_stride & DBGSOM_SEED_FULL) != 0;
-    // DBGSOM_PRUNE: candidates from the triangle inequality instead of the sweep (section 2c);
-    // DBGSOM_PRUNE_PROBE: the sweep as usual, and beside it what DBGSOM_PRUNE's lists would add up to
-    const bool prune = (seed_stride & DBGSOM_PRUNE) != 0 && M <= PRUNE_MAX_M;
-    const bool prune_probe = !prune && (seed_stride & DBGSOM_PRUNE_PROBE) != 0 && M <= PRUNE_MAX_M;
-    // DBGSOM_PRUNE_RETRY (stateless searches with cheap seeds): workgroups whose pruned lists come out
-    // long are re-seeded against every prototype and pruned again (two more short launches)
-    const bool prune_retry = (seed_stride & DBGSOM_PRUNE_RETRY) != 0 && !seed_full && !prev_idx_dev;
-    // k = 2 (the two nearest prototypes: topographic error, BaseSom.py:945): the pruning form only
-    const bool k2 = call.k == 2;
-    DBGSOM_REQUIRE(call.k == 1 || call.k == 2, "k must be 1 or 2");
-    DBGSOM_REQUIRE(!call.defer_dist || (call.refine_rows > 0 && M < 0xffff), "deferred distances need the refinement");
-    DBGSOM_REQUIRE(!k2 || (prune && call.refine_rows == 0 && M >= 2),
-                   "k = 2 needs the pruning form (DBGSOM_PRUNE, M <= 8192) without the refinement");
-    seed_stride &= ~(DBGSOM_PRUNE | DBGSOM_PRUNE_PROBE | DBGSOM_PRUNE_RETRY);
-    seed_stride = seed_full ? 1 : seed_stride;
-    DBGSOM_REQUIRE(seed_stride >= 0 && seed_stride <= 64, "seed_stride outside [0, 64]");
-    DBGSOM_REQUIRE(sweep_planes >= 0 && sweep_planes <= 3, "sweep_planes must be 0 .. 3");
-    if (sweep_planes == 0) sweep_planes = 2;
-    DBGSOM_REQUIRE(x_dtype == DBGSOM_F32 || x_dtype == DBGSOM_F64, "the filtered search takes float32 or float64 samples");
-    DBGSOM_REQUIRE(N >= 1 && N < 0x7fffffff && d >= 1 && d % KT == 0 && ldx >= d, "bad sample shape (d must be a multiple of 16)");
-    DBGSOM_REQUIRE(M >= 1 && M <= SW_MAX_M, "M outside [1, 16000]");
-    DBGSOM_REQUIRE(X_dev && xx_dev && xplanes_dev && W_dev && ww_dev && idx_dev && dist_dev &&
-                       workspace_dev, "null pointer");
-    DBGSOM_REQUIRE((prev_idx_dev == nullptr) == (order_dev == nullptr),
-                   "prev_idx and order come as a pair (both NULL = stateless two-pass search)");
-    DBGSOM_REQUIRE(is_aligned(X_dev, 16) && (ldx * (int64_t)dtype_size(x_dtype)) % 16 == 0 && is_aligned(W_dev, 16) &&
-                       is_aligned(workspace_dev, 256) && is_aligned(xplanes_dev, 256), "alignment");
-    if (workspace_bytes < dbgsom_bmu_filtered_workspace_bytes(N, d, M)) {
-        set_error("dbgsom_bmu_filtered: workspace too small");
-        return DBGSOM_ENOMEM;
+// ---- one filtered search: what its stages share, the three candidate kernels' launches, the stages in launch order
+namespace {
+struct FilterRun {
+    const FilteredCall &c;
+    const FilterForm &fm;
+    FilterAux &aux;
+    hipStream_t s;
+    int d, dpad;
+    PlaneBuf xb;             // the samples' digit planes
+    FilterWs f;              // the carved workspace
+    const int64_t *seeds;    // the caller's previous winners, or the pre-pass's arg-min
+    const int32_t *order;    // the samples bucketed by them
+    bool gap_aside = false;  // the prototype gaps are under way on the side stream
+
+    unsigned long long *retry_len() const { return reinterpret_cast<unsigned long long *>(f.sched_ctr + SCHED_RETRY); }
+
+    // sweep_i8_kernel in the form `kernel`: the seed pre-pass over the subset (MODE 1) or the marking sweep (MODE 0)
+    template <typename Kernel>
+    void sweep_i8(Kernel kernel, bool seeding) const {
+        const int32_t *no_sel = nullptr;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)f.nb), dim3(FNT), 0, s, xb.planes, xb.scale, xb.l1, c.xx, c.N, d, dpad,
+                           seeding ? f.wt_sub : f.wt, seeding ? f.yy_sub : f.yctab, seeding ? f.ctab_sub : f.ictab,
+                           seeding ? f.yy_sub : f.yypad, seeding ? f.ctab_sub : f.ctab, f.summary, seeding ? fm.Msub : (int)c.M,
+                           seeding ? nullptr : seeds, seeding ? nullptr : order, f.ulist, (int)f.Mpad, f.ucount,
+                           seeding ? f.seed : nullptr, seeding ? fm.seed_stride : 1, seeding ? fm.Msubpad : (int)f.Mpad,
+                           seeding ? fm.nkt_used : 0, seeding ? f.kt_sel : no_sel, f.sched_ctr);
     }
-    hipStream_t s = (hipStream_t)stream;
-    PlaneBuf xb;
-    carve_planes(&xb, (char *)const_cast<void *>(xplanes_dev), N, d);
-    FilterWs f;
-    carve_filter(&f, (char *)workspace_dev, N, d, M);
-    const int dpad = (int)filter_dpad(d);
-    g_timer.mark(0, s);
-    // the seed pre-pass looks at every `seed_stride`-th prototype (any seed keeps the result exact;
-    // a coarser pre-pass is cheaper, its seeds are a little further from the minimum)
-    // default (0): the stride that makes the subset ONE 256-prototype chunk of the pre-pass, at
-    // least 4 -- list lengths barely depend on it (C3: 58 -> 62 from stride 4 to 8, C4 / C5: none)
-    if (seed_stride == 0) {
-        seed_stride = (int)((M + 255) / 256);
-        seed_stride = seed_stride < 4 ? 4 : (seed_stride > 64 ? 64 : seed_stride);
+
+    // sweep4_i8_kernel's three passes: seeds from the subset of the prototypes (stateless search), seeds from every
+    // prototype and every feature for the listed workgroups only (re-seeding, 2c), the marking sweep
+    enum Sweep4Pass { PREPASS, RESEED, MARK };
+    void sweep4(Sweep4Pass pass) const {
+        const bool sub = pass == PREPASS, mark = pass == MARK, reseed = pass == RESEED;
+        const float *tab = f.tab32 + (size_t)(mark ? 0 : (sub ? 2 : 4)) * f.Mpad;   // [|w|^2 | c] tables of the pass
+        const int32_t *no_sel = nullptr, *retry = f.retry;
+        hipLaunchKernelGGL(mark ? sweep4_i8_kernel<0> : sweep4_i8_kernel<1>, dim3((unsigned)f.nb), dim3(FNT), 0, s, xb.planes,
+                           xb.scale, xb.l1, c.xx, c.N, d, dpad, sub ? f.wt_sub : f.wt, tab, tab + (size_t)f.Mpad,
+                           sub ? f.yy_sub : f.yypad, sub ? f.ctab_sub : f.ctab, f.summary, sub ? fm.Msub : (int)c.M,
+                           mark ? seeds : nullptr, sub ? nullptr : order, f.ulist, (int)f.Mpad, f.ucount,
+                           mark ? nullptr : f.seed, sub ? fm.seed_stride : 1, sub ? fm.Msubpad : (int)f.Mpad,
+                           sub ? fm.nkt_used : 0, sub ? f.kt_sel : no_sel, f.sched_ctr, f.chk32, reseed ? retry : no_sel,
+                           reseed ? retry_len() : nullptr);
     }
-    while (seed_stride > 1 && (M + seed_stride - 1) / seed_stride < 128) seed_stride >>= 1;
-    const int Msub = (int)((M + seed_stride - 1) / seed_stride), Msubpad = (Msub + 255) / 256 * 256;
-    // ... and at PREPASS_KTILES k-tiles (64 features each) spread evenly over the row, with the
-    // matching partial |w|^2: on every workload measured the candidate lists are as short as with
-    // all features, the pre-pass costs 0.35 ms at C4 instead of 0.75 with all features
-    const int nkt_full = dpad / FKT;
-    const int nkt_used = (!seed_full && PREPASS_KTILES < nkt_full && nkt_full <= SW_MAX_KT) ? PREPASS_KTILES : nkt_full;
-    if (nkt_used < nkt_full) {
-        hipLaunchKernelGGL(tile_partial_kernel, dim3((unsigned)nkt_full, TS_RB), dim3(256), 0, s, W_dev,
-                           (int)M, (int)d, dpad, f.tile_part);
-        hipLaunchKernelGGL(tile_score_select_kernel, dim3((unsigned)nkt_full), dim3(64), 0, s, f.tile_part, (int)M,
-                           dpad, f.tile_score, nkt_full, nkt_used, f.kt_sel, f.tickets + 0);
+
+    // prune_mark_kernel: retry_mode as there; hinted: with the caller's bound on the seed distances, if it brought
+    // one.  The pruning form writes the lists and adds to their sum; the probe beside a sweep only counts, into the
+    // sum's twin.  (The count of long lists is kept either way: the engine turns the re-seeding on when a call reports any.)
+    void prune_mark(int retry_mode, bool hinted) const {
+        const bool hint = hinted && c.hint_shift;
+        unsigned long long *sum = reinterpret_cast<unsigned long long *>(f.sched_ctr + SCHED_SUM) + (fm.prune ? 0 : 1);
+        hipLaunchKernelGGL(prune_mark_kernel, dim3((unsigned)f.nb), dim3(256), 0, s, xb.planes, xb.scale, c.xx, c.N, d, dpad,
+                           f.wt, (int)f.Mpad, f.wscale, c.ww, f.summary, (int)c.M, seeds, order, f.gap, (int)f.Mg, f.ulist,
+                           (int)f.Mpad, f.ucount, f.sched_ctr, sum, fm.prune ? 0 : 1, hint ? c.hint_dist : nullptr,
+                           hint ? c.hint_shift : nullptr, f.retry, retry_len(), retry_mode,
+                           (uint32_t)(c.M / 8 > 96 ? c.M / 8 : 96), fm.k2 ? f.nnub : nullptr);
     }
-    WTables tables;
-    tables.ww = ww_dev; tables.ctab = f.ctab; tables.yypad = f.yypad; tables.ctab_sub = f.ctab_sub;
-    tables.yy_sub = f.yy_sub; tables.ictab = f.ictab; tables.yctab = f.yctab; tables.summary = f.summary;
-    tables.sched_ctr = f.sched_ctr; tables.tscale = sweep_tscale(sweep_planes); tables.tab32 = f.tab32; tables.chk32 = f.chk32;
-    hipLaunchKernelGGL(slice_w_tiled_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, W_dev,
-                       (int)M, (int)d, dpad, (int)f.Mpad, seed_stride, Msubpad, nkt_used,
-                       nkt_used < nkt_full ? f.kt_sel : (const int32_t *)nullptr, f.wt,
-                       f.wt_sub, f.wscale, f.wl1, f.yy_part, f.wn0, f.wres16, f.tickets + 1, tables);
-    g_timer.mark(1, s);
-    // The gaps between the prototypes (pruning form) need the digit planes of W and nothing of the samples:
-    // in a stateless search they are worked out on the second stream BESIDE the seed pre-pass and the bucket
-    // sort (one wavefront per 64 x 64 tile: a few hundred small workgroups next to a launch that fills the
-    // chip or, on a rank's share of the samples, does not)
-    auto launch_gap = [&](hipStream_t gs) -> int {
+
+    // the gaps between the prototypes (pruning form): they need the digit planes of W and nothing of the samples
+    int gaps(hipStream_t gs) const {
         const unsigned gt = (unsigned)(f.Mg / 64);
-        if (k2) DBGSOM_HIP_CHECK(hipMemsetAsync(f.nnub, 0x7f, (size_t)f.Mg * 4, gs));   // (0x7f7f7f7f: 3.4e38, "no bound")
-        if (gt * gt >= 1024u)   // (four 64 x 64 tiles per CU and more: M >= 2048)
-            hipLaunchKernelGGL(proto_gap_kernel<2>, dim3(gt, gt), dim3(64), 0, gs, f.wt, (int)f.Mpad, dpad, (int)M, (int)d,
-                               f.wscale, f.wn0, ww_dev, f.gap, (int)f.Mg, k2 ? f.nnub : (uint32_t *)nullptr);
-        else
-            hipLaunchKernelGGL(proto_gap_kernel<1>, dim3(2 * gt, 2 * gt), dim3(64), 0, gs, f.wt, (int)f.Mpad, dpad, (int)M,
-                               (int)d, f.wscale, f.wn0, ww_dev, f.gap, (int)f.Mg, k2 ? f.nnub : (uint32_t *)nullptr);
+        uint32_t *nnub = fm.k2 ? f.nnub : nullptr;
+        if (nnub) DBGSOM_HIP_CHECK(hipMemsetAsync(nnub, 0x7f, (size_t)f.Mg * 4, gs));   // (0x7f7f7f7f: 3.4e38, "no bound")
+        hipLaunchKernelGGL(fm.gap_nb == 2 ? proto_gap_kernel<2> : proto_gap_kernel<1>,
+                           fm.gap_nb == 2 ? dim3(gt, gt) : dim3(2 * gt, 2 * gt), dim3(64), 0, gs, f.wt, (int)f.Mpad, dpad,
+                           (int)c.M, d, f.wscale, f.wn0, c.ww, f.gap, (int)f.Mg, nnub);
         return DBGSOM_OK;
-    };
-    bool gap_aside = false;
-    if ((prune || prune_probe) && !prev_idx_dev && g_side.ready()) {
-        DBGSOM_HIP_CHECK(hipEventRecord(g_side.gap_fork, s));
-        DBGSOM_HIP_CHECK(hipStreamWaitEvent(g_side.stream, g_side.gap_fork, 0));
-        const int rc = launch_gap(g_side.stream);
-        if (rc != DBGSOM_OK) return rc;
-        DBGSOM_HIP_CHECK(hipEventRecord(g_side.gap_done, g_side.stream));
-        gap_aside = true;
     }
-    if (!prev_idx_dev) {
-        // no previous winners: seed = arg-min of a coarser (3-product) sweep, then bucket the samples
+
+    // 1. the prototypes' digit planes and tables (and which k-tiles the seed pre-pass looks at)
+    void prepare_prototypes() const {
+        const bool select = fm.nkt_used < fm.nkt_full;
+        if (select) {
+            hipLaunchKernelGGL(tile_partial_kernel, dim3((unsigned)fm.nkt_full, TS_RB), dim3(256), 0, s, c.W, (int)c.M, d,
+                               dpad, f.tile_part);
+            hipLaunchKernelGGL(tile_score_select_kernel, dim3((unsigned)fm.nkt_full), dim3(64), 0, s, f.tile_part, (int)c.M,
+                               dpad, f.tile_score, fm.nkt_full, fm.nkt_used, f.kt_sel, f.tickets + 0);
+        }
+        WTables tables;
+        tables.ww = c.ww; tables.ctab = f.ctab; tables.yypad = f.yypad; tables.ctab_sub = f.ctab_sub;
+        tables.yy_sub = f.yy_sub; tables.ictab = f.ictab; tables.yctab = f.yctab; tables.summary = f.summary;
+        tables.sched_ctr = f.sched_ctr; tables.tscale = sweep_tscale(fm.sweep_planes); tables.tab32 = f.tab32; tables.chk32 = f.chk32;
+        hipLaunchKernelGGL(slice_w_tiled_kernel, dim3((unsigned)((c.M + 3) / 4)), dim3(256), 0, s, c.W, (int)c.M, d, dpad,
+                           (int)f.Mpad, fm.seed_stride, fm.Msubpad, fm.nkt_used, select ? f.kt_sel : (const int32_t *)nullptr,
+                           f.wt, f.wt_sub, f.wscale, f.wl1, f.yy_part, f.wn0, f.wres16, f.tickets + 1, tables);
+    }
+
+    // 2. no previous winners: seed = arg-min of a coarse pre-pass, then bucket the samples by it
+    int seed_and_sort() {
+        if (seeds) {
+            aux.timer.mark(2, s);
+            return DBGSOM_OK;
+        }
+        // the gaps of the pruning form are worked out on the second stream BESIDE the seed pre-pass and the bucket
+        // sort (one wavefront per 64 x 64 tile: a few hundred small workgroups next to a launch that fills the
+        // chip or, on a rank's share of the samples, does not)
+        SideStream &side = aux.side;
+        if (fm.gap_nb && side.ready()) {
+            DBGSOM_HIP_CHECK(hipEventRecord(side.gap_fork, s));
+            DBGSOM_HIP_CHECK(hipStreamWaitEvent(side.stream, side.gap_fork, 0));
+            const int rc = gaps(side.stream);
+            if (rc != DBGSOM_OK) return rc;
+            DBGSOM_HIP_CHECK(hipEventRecord(side.gap_done, side.stream));
+            gap_aside = true;
+        }
         // the pre-pass is as coarse as the sweep it seeds: one product for the one-product sweep
         // (seeds need not be good, only cheap), three otherwise (data on which the coarse bound
         // fails also gets useless seeds from a one-product pre-pass)
-        if (sweep_planes == 1)
-            hipLaunchKernelGGL((sweep4_i8_kernel<1, 8>), dim3((unsigned)f.nb), dim3(512), 0, s, xb.planes, xb.scale,
-                               xb.l1, xx_dev, N, (int)d, dpad, f.wt_sub, f.tab32 + 2 * (size_t)f.Mpad,
-                               f.tab32 + 3 * (size_t)f.Mpad, f.yy_sub,
-                               f.ctab_sub, f.summary, Msub, (const int64_t *)nullptr, (const int32_t *)nullptr,
-                               f.ulist, (int)f.Mpad, f.ucount, Msubpad, f.seed, seed_stride, nkt_used, f.kt_sel, f.sched_ctr, f.chk32,
-                               (const int32_t *)nullptr, (const unsigned long long *)nullptr);
-        else
-            hipLaunchKernelGGL((sweep_i8_kernel<1, 2, 2>), dim3((unsigned)f.nb), dim3(FNT), 0, s, xb.planes,
-                           xb.scale, xb.l1, xx_dev, N, (int)d, dpad, f.wt_sub, f.yy_sub, f.ctab_sub,
-                           f.yy_sub, f.ctab_sub, f.summary, Msub, (const int64_t *)nullptr, (const int32_t *)nullptr,
-                           f.ulist, (int)f.Mpad, f.ucount, f.seed, seed_stride, Msubpad, nkt_used, f.kt_sel, f.sched_ctr);
-        g_timer.mark(2, s);
-        const int rc = launch_bucket_sort(f.seed, N, M, f.order, f.sort_ws, s);
-        if (rc != DBGSOM_OK) return rc;
-        prev_idx_dev = f.seed;
-        order_dev = f.order;
-    } else {
-        g_timer.mark(2, s);
+        if (fm.sweep_planes == 1) sweep4(PREPASS);
+        else sweep_i8(sweep_i8_kernel<1, 2, 2>, true);
+        aux.timer.mark(2, s);
+        seeds = f.seed;
+        order = f.order;
+        return launch_bucket_sort(f.seed, c.N, c.M, f.order, f.sort_ws, s);
     }
-    g_timer.mark(3, s);
-    if (prune || prune_probe) {
-        if (gap_aside) {
-            DBGSOM_HIP_CHECK(hipStreamWaitEvent(s, g_side.gap_done, 0));
-        } else {
-            const int rc = launch_gap(s);
-            if (rc != DBGSOM_OK) return rc;
+
+    // 3. the candidate lists of the 128-sample workgroups
+    int mark_candidates() const {
+        if (fm.gap_nb) {   // (the pruning form, or its counting-only launch beside a sweep)
+            if (gap_aside) {
+                DBGSOM_HIP_CHECK(hipStreamWaitEvent(s, aux.side.gap_done, 0));
+            } else {
+                const int rc = gaps(s);
+                if (rc != DBGSOM_OK) return rc;
+            }
+            prune_mark(fm.prune_retry ? 1 : 0, true);
+            if (fm.prune_retry) {
+                sweep4(RESEED);
+                prune_mark(2, false);
+            }
         }
-        unsigned long long *sum = reinterpret_cast<unsigned long long *>(f.sched_ctr + SCHED_SUM) + (prune ? 0 : 1);
-        unsigned long long *rlen = reinterpret_cast<unsigned long long *>(f.sched_ctr + SCHED_RETRY);
-        const uint32_t retry_above = (uint32_t)(M / 8 > 96 ? M / 8 : 96);
-        // (the count is kept either way: the engine turns the re-seeding on when a call reports any)
-        hipLaunchKernelGGL(prune_mark_kernel, dim3((unsigned)f.nb), dim3(256), 0, s, xb.planes, xb.scale, xx_dev,
-                           N, (int)d, dpad, f.wt, (int)f.Mpad, f.wscale, ww_dev, f.summary, (int)M, prev_idx_dev,
-                           order_dev, f.gap, (int)f.Mg, f.ulist, (int)f.Mpad, f.ucount, f.sched_ctr, sum,
-                           prune ? 0 : 1, g_hint_shift ? g_hint_dist : (const double *)nullptr, g_hint_shift,
-                           f.retry, rlen, prune_retry ? 1 : 0, retry_above, k2 ? f.nnub : (const uint32_t *)nullptr);
-        if (prune_retry) {
-            // every prototype, every feature, one digit product, for the listed workgroups only
-            hipLaunchKernelGGL((sweep4_i8_kernel<1, 8>), dim3((unsigned)f.nb), dim3(512), 0, s, xb.planes, xb.scale, xb.l1,
-                               xx_dev, N, (int)d, dpad, f.wt, f.tab32 + 4 * (size_t)f.Mpad, f.tab32 + 5 * (size_t)f.Mpad,
-                               f.yypad, f.ctab, f.summary, (int)M, (const int64_t *)nullptr, order_dev, f.ulist, (int)f.Mpad,
-                               f.ucount, (int)f.Mpad, f.seed, 1, 0, (const int32_t *)nullptr, f.sched_ctr, f.chk32,
-                               (const int32_t *)f.retry, (const unsigned long long *)rlen);
-            hipLaunchKernelGGL(prune_mark_kernel, dim3((unsigned)f.nb), dim3(256), 0, s, xb.planes, xb.scale, xx_dev,
-                               N, (int)d, dpad, f.wt, (int)f.Mpad, f.wscale, ww_dev, f.summary, (int)M, prev_idx_dev,
-                               order_dev, f.gap, (int)f.Mg, f.ulist, (int)f.Mpad, f.ucount, f.sched_ctr, sum,
-                               prune ? 0 : 1, (const double *)nullptr, (const double *)nullptr, f.retry, rlen, 2, retry_above,
-                               k2 ? f.nnub : (const uint32_t *)nullptr);
+        switch (fm.marking) {
+        case FilterForm::MARK_PRUNE: break;   // (no sweep)
+        case FilterForm::MARK_SWEEP4: sweep4(MARK); break;
+        case FilterForm::MARK_SWEEP_1_4: sweep_i8(sweep_i8_kernel<0, 1, 4>, false); break;
+        case FilterForm::MARK_SWEEP_3_1: sweep_i8(sweep_i8_kernel<0, 3, 1>, false); break;
+        case FilterForm::MARK_SWEEP_2_2: sweep_i8(sweep_i8_kernel<0, 2, 2>, false); break;
         }
+        return DBGSOM_OK;
     }
-    if (prune) {
-        // (no sweep)
-    } else if (sweep_planes == 1 && M <= Sweep4Lds::MAX_M)
-        // one digit product, 128 x 256 tile, two workgroups per CU (see dbgsom_sweep_shape)
-        hipLaunchKernelGGL((sweep4_i8_kernel<0, 8>), dim3((unsigned)f.nb), dim3(512), 0, s, xb.planes, xb.scale,
-                           xb.l1, xx_dev, N, (int)d, dpad, f.wt, f.tab32, f.tab32 + (size_t)f.Mpad, f.yypad, f.ctab,
-                           f.summary, (int)M, prev_idx_dev, order_dev, f.ulist, (int)f.Mpad, f.ucount,
-                           (int)f.Mpad, (int64_t *)nullptr, 1, 0, (const int32_t *)nullptr, f.sched_ctr, f.chk32,
-                           (const int32_t *)nullptr, (const unsigned long long *)nullptr);
-    else if (sweep_planes == 1)  // one digit product beyond that kernel's bitmask: 128 x 512 tile, one workgroup per CU
-        hipLaunchKernelGGL((sweep_i8_kernel<0, 1, 4>), dim3((unsigned)f.nb), dim3(FNT), 0, s, xb.planes,
-                           xb.scale, xb.l1, xx_dev, N, (int)d, dpad, f.wt, f.yctab, f.ictab,
-                           f.yypad, f.ctab, f.summary, (int)M, prev_idx_dev, order_dev, f.ulist, (int)f.Mpad, f.ucount,
-                           (int64_t *)nullptr, 1, (int)f.Mpad, 0, (const int32_t *)nullptr, f.sched_ctr);
-    else if (sweep_planes == 3)
-        hipLaunchKernelGGL((sweep_i8_kernel<0, 3, 1>), dim3((unsigned)f.nb), dim3(FNT), 0, s, xb.planes,
-                           xb.scale, xb.l1, xx_dev, N, (int)d, dpad, f.wt, f.yctab, f.ictab,
-                           f.yypad, f.ctab, f.summary, (int)M, prev_idx_dev, order_dev, f.ulist, (int)f.Mpad, f.ucount,
-                           (int64_t *)nullptr, 1, (int)f.Mpad, 0, (const int32_t *)nullptr, f.sched_ctr);
-    else
-        hipLaunchKernelGGL((sweep_i8_kernel<0, 2, 2>), dim3((unsigned)f.nb), dim3(FNT), 0, s, xb.planes,
-                           xb.scale, xb.l1, xx_dev, N, (int)d, dpad, f.wt, f.yctab, f.ictab,
-                           f.yypad, f.ctab, f.summary, (int)M, prev_idx_dev, order_dev, f.ulist, (int)f.Mpad, f.ucount,
-                           (int64_t *)nullptr, 1, (int)f.Mpad, 0, (const int32_t *)nullptr, f.sched_ctr);
-    g_timer.mark(4, s);
-    if (call.guard_mean > 0.0) {   // (an arm on trial: see FilteredCall::guard_mean)
+
+    // 4. an arm on trial (FilteredCall::guard_mean): wait for the lists; DBGSOM_LISTS_LONG when they average more
+    int guard_lists() const {
         unsigned long long sum_h = 0;
         DBGSOM_HIP_CHECK(hipMemcpyAsync(&sum_h, f.sched_ctr + SCHED_SUM, 8, hipMemcpyDeviceToHost, s));
         DBGSOM_HIP_CHECK(hipStreamSynchronize(s));
-        if ((double)sum_h > call.guard_mean * (double)f.nb) {
-            g_timer.mark(5, s);
-            g_timer.valid = g_timer.enabled;
-            return DBGSOM_LISTS_LONG;
-        }
+        return (double)sum_h > c.guard_mean * (double)f.nb ? DBGSOM_LISTS_LONG : DBGSOM_OK;
     }
-    // per-sample refinement of the lists (section 2d): workgroups it takes leave the MFMA stage's schedule
-    const int rf_rows = call.refine_rows;
-    const bool refine = rf_rows > 0;
-    // the three list-length classes of the matrix-core stage write disjoint samples: they run side by side
-    // (classes 1 and 2 on a second stream forked from the caller's), so that the tail of one launch -- a few
-    // long lists on a mostly idle chip -- overlaps the others
-    SideStream &side = g_side;
-    // (measured also for few buckets, where the fork and join cost ~20 us of bubbles: C2 0.168 -> 0.123
-    // ms for the stage, a 125 k-row shard of C4 0.303 -> 0.265, against running them in a row)
-    // (k = 1 without the refinement: all three list-length classes go as ONE launch on the caller's stream --
-    //  nothing to fork)
-    const bool merged = !k2 && !refine;
-    const bool fork = !merged && side.ready();
-    hipStream_t s2 = fork ? side.stream : s, s3 = fork ? side.stream2 : s;
-    // With the refinement the matrix-core stage only has the workgroups the refinement does not take (lists
-    // beyond its tiles: a few long chains on a mostly idle chip): all of it on the second stream, beside the
-    // refinement and the pair kernel on the caller's; the samples whose candidates overflowed on the third.
-    hipStream_t s_mfma = refine ? s2 : s;
-    const int rows0 = rf_rows <= 32 ? 32 : (rf_rows <= 64 ? 64 : (rf_rows <= 128 ? 128 : 0));
-    const int defer_M = (refine && call.defer_dist) ? (int)M : 0;
-    if (refine)
-        // list-length classes of the refinement: a small tile for the bulk (what the caller expects the
-        // lists to be), the largest for the rest; workgroups in neither stay the matrix-core stage's
-        hipLaunchKernelGGL(class_fill_kernel, dim3((unsigned)((f.nb + 255) / 256)), dim3(256), 0, s, f.ucount, (int)f.nb,
-                           rows0, RF_SEGS * (int)RefineCfg<2, 4>::MAX_CNT, f.rf_queue, f.rf_qlen, f.gflag, f.sched_ctr, order_dev,
-                           prev_idx_dev, N, (int)M, f.cand, f.rbest, defer_M);
-    else
-        // (the bin counts were added up by the sweep's workgroups as they wrote their list lengths)
-        hipLaunchKernelGGL(sched_fill_kernel, dim3((unsigned)((f.nb + 255) / 256)), dim3(256), 0, s, f.ucount,
-                           (int)f.nb, f.sched_ctr, f.sched, (const uint8_t *)nullptr);
-    if (fork) {
-        DBGSOM_HIP_CHECK(hipEventRecord(side.forked, s));
-        DBGSOM_HIP_CHECK(hipStreamWaitEvent(s2, side.forked, 0));
-        DBGSOM_HIP_CHECK(hipStreamWaitEvent(s3, side.forked, 0));
-    }
-    if (refine) {
-        hipLaunchKernelGGL(sched_fill_kernel, dim3((unsigned)((f.nb + 255) / 256)), dim3(256), 0, s_mfma, f.ucount,
-                           (int)f.nb, f.sched_ctr, f.sched, (const uint8_t *)f.gflag);
-        if (fork) {  // (classes 2 and 1 run on the third stream: behind the schedule)
-            DBGSOM_HIP_CHECK(hipEventRecord(side.mid, s_mfma));
-            DBGSOM_HIP_CHECK(hipStreamWaitEvent(s3, side.mid, 0));
-        }
-        // every launch is a few workgroups per CU walking its class's queue: workgroups of nj x 256 threads,
-        // whole rounds of the 8 XCDs, at most `wgs` of them
-        auto refine_launch = [&](auto kernel, int nj, int cls, int64_t wgs) {
-            const int64_t nb8 = (f.nb + 7) / 8 * 8;
-            hipLaunchKernelGGL(kernel, dim3((unsigned)(nb8 < wgs ? nb8 : wgs)), dim3(nj * 256), 0, s, xb.planes, xb.scale,
-                               xb.res16, xx_dev, N, (int)d, dpad, f.wt, (int)f.Mpad, f.wscale, ww_dev, f.summary, order_dev,
-                               f.ulist, (int)f.Mpad, f.ucount, f.rf_queue + (size_t)cls * f.nb, f.rf_qlen + cls, f.cand,
-                               f.rbest, f.rf_ctr, f.ovf, f.rf_qlen + 2, f.ovf_cand, defer_M, idx_dev, dist_dev);
-        };
-        if (rows0 == 32) refine_launch(refine_i8_kernel<1, 1>, 1, 0, 1024);
-        else if (rows0 == 64) refine_launch(refine_i8_kernel<1, 2>, 1, 0, 1024);
-        else if (rows0 == 128) refine_launch(refine_i8_kernel<2, 2>, 2, 0, 512);
-        refine_launch(refine_i8_kernel<2, 4>, 2, 1, 512);
-        // the samples by their refined best prototype: a workgroup of the pair kernel then shares its candidates
-        const int64_t Mk = defer_M ? M + 1 : M;   // (deferred: the decided samples behind every real bucket)
-        const int rc = launch_bucket_sort(f.rbest, N, Mk, f.order2, f.sort_ws, s);
-        if (rc != DBGSOM_OK) return rc;
-        const uint32_t *n_active = defer_M ? bucket_sort_seg_start(f.sort_ws, N, Mk) + M : (const uint32_t *)nullptr;
-        // (bfloat16-resident samples: the pair kernel reads the stored rows -- half the bytes of the widened
-        //  copy the matrix kernels use, the same values)
-        const unsigned pgrid = (unsigned)(((N + PS - 1) / PS + 7) / 8 * 8);   // (whole rounds of the 8 XCDs: xcd_group)
-        if (call.X_store && call.store_dtype == DBGSOM_BF16 && x_dtype == DBGSOM_F32)
-            hipLaunchKernelGGL((pair_exact_kernel<bf16_t, 32, 128>), dim3(pgrid), dim3(256), 0, s, (const bf16_t *)call.X_store, N,
-                               (int)d, call.ld_store, xx_dev, W_dev, ww_dev, f.order2, f.cand, round_f32, idx_dev, dist_dev, f.rf_ctr, n_active);
-        else if (x_dtype == DBGSOM_F32)
-            hipLaunchKernelGGL((pair_exact_kernel<float, 16, 256>), dim3(pgrid), dim3(256), 0, s, (const float *)X_dev, N,
-                               (int)d, ldx, xx_dev, W_dev, ww_dev, f.order2, f.cand, round_f32, idx_dev, dist_dev, f.rf_ctr, n_active);
+
+    // 5. the exact arg-min of every sample over its workgroup's list
+    int exact_on_candidates() const {
+        const int64_t N = c.N, M = c.M;
+        // per-sample refinement of the lists (section 2d): workgroups it takes leave the MFMA stage's schedule
+        const bool refine = fm.refine;
+        // the three list-length classes of the matrix-core stage write disjoint samples: they run side by side
+        // (classes 1 and 2 on a second stream forked from the caller's), so that the tail of one launch -- a few
+        // long lists on a mostly idle chip -- overlaps the others
+        SideStream &side = aux.side;
+        // (measured also for few buckets, where the fork and join cost ~20 us of bubbles: C2 0.168 -> 0.123
+        // ms for the stage, a 125 k-row shard of C4 0.303 -> 0.265, against running them in a row)
+        // (k = 1 without the refinement: all three list-length classes go as ONE launch on the caller's stream --
+        //  nothing to fork)
+        const bool merged = fm.exact == FilterForm::EXACT_SPLIT || fm.exact == FilterForm::EXACT_ALL;
+        const bool fork = !merged && side.ready();
+        hipStream_t s2 = fork ? side.stream : s, s3 = fork ? side.stream2 : s;
+        // With the refinement the matrix-core stage only has the workgroups the refinement does not take (lists
+        // beyond its tiles: a few long chains on a mostly idle chip): all of it on the second stream, beside the
+        // refinement and the pair kernel on the caller's; the samples whose candidates overflowed on the third.
+        hipStream_t s_mfma = refine ? s2 : s;
+        const int defer_M = (refine && c.defer_dist) ? (int)M : 0;
+        const dim3 fill_grid((unsigned)((f.nb + 255) / 256));
+        if (refine)
+            // list-length classes of the refinement: a small tile for the bulk (what the caller expects the
+            // lists to be), the largest for the rest; workgroups in neither stay the matrix-core stage's
+            hipLaunchKernelGGL(class_fill_kernel, fill_grid, dim3(256), 0, s, f.ucount, (int)f.nb, fm.rows0,
+                               RF_SEGS * (int)RefineCfg<2, 4>::MAX_CNT, f.rf_queue, f.rf_qlen, f.gflag, f.sched_ctr, order, seeds,
+                               N, (int)M, f.cand, f.rbest, defer_M);
         else
-            hipLaunchKernelGGL((pair_exact_kernel<double, 16, 256>), dim3(pgrid), dim3(256), 0, s, (const double *)X_dev, N,
-                               (int)d, ldx, xx_dev, W_dev, ww_dev, f.order2, f.cand, round_f32, idx_dev, dist_dev, f.rf_ctr, n_active);
-        // (the samples whose candidates overflowed: behind the pair kernel, not beside it -- its uncoalesced
-        //  row walks slowed the sort and the pair kernel by more than it takes)
-        if (x_dtype == DBGSOM_F32)
-            hipLaunchKernelGGL((overflow_exact_kernel<float>), dim3(512), dim3(256), 0, s, (const float *)X_dev, (int)d, ldx,
-                               xx_dev, W_dev, ww_dev, f.ulist, (int)f.Mpad, f.ucount, f.ovf, f.rf_qlen + 2, f.ovf_cand, round_f32,
-                               idx_dev, dist_dev);
-        else
-            hipLaunchKernelGGL((overflow_exact_kernel<double>), dim3(512), dim3(256), 0, s, (const double *)X_dev, (int)d, ldx,
-                               xx_dev, W_dev, ww_dev, f.ulist, (int)f.Mpad, f.ucount, f.ovf, f.rf_qlen + 2, f.ovf_cand, round_f32,
-                               idx_dev, dist_dev);
-    }
-    // The matrix-core stage on the candidates, in the samples' type.  Every form takes the same arguments.
-    // (Wavefronts per 128-sample workgroup, measured as three launches, ms per stage, 4 / 8 / 8 for class 3
-    //  only: C4 1.23 / 1.23 / 1.16, C3 0.52 / 0.48, C5 shard 5.83 / 5.33 -- 8 for the long lists, 4 for the
-    //  rest; subset_exact_all_kernel runs every class as 8 in one launch, see there.)
-    auto exact_stage = [&](auto xt) {
-        using XT = decltype(xt);
-        constexpr int XS = (int)sizeof(XT);
-        auto launch = [&](auto kernel, dim3 grid, dim3 block, hipStream_t st) {
-            hipLaunchKernelGGL(kernel, grid, block, 0, st, (const XT *)X_dev, N, (int)d, ldx, xx_dev, W_dev, (int)M, ww_dev,
-                               order_dev, f.ulist, (int)f.Mpad, f.ucount, f.sched, f.sched_ctr + 2 * SCHED_BINS, round_f32,
-                               idx_dev, dist_dev);
-        };
-        const unsigned nb = (unsigned)f.nb;
-        if (k2) {
-            // (8 wavefronts x 16 samples: with two (value, index) pairs per sample the 4 x 32 shape needed 256
-            //  registers for the long-list class and spilled in the others)
-            launch(subset_exact_kernel<XT, 3, 8, 1, 2>, dim3(nb), dim3(512), s_mfma);
-            launch(subset_exact_kernel<XT, 2, 8, 1, 2>, dim3(nb), dim3(512), s2);
-            launch(subset_exact_kernel<XT, 1, 8, 1, 2>, dim3(nb), dim3(512), s3);
-        } else if (refine) {
-            // (what is left to this stage is a few workgroups: two 64-sample ones per bucket, the long lists on
-            //  the second stream, the rest on the third)
-            launch(subset_exact_kernel<XT, 3, 4, 2, 1, split_ring_stages(3, XS)>, dim3(2 * nb), dim3(256), s_mfma);
-            launch(subset_exact_kernel<XT, 2, 4, 2, 1, split_ring_stages(2, XS)>, dim3(2 * nb), dim3(256), s3);
-            launch(subset_exact_kernel<XT, 1, 4, 2, 1, split_ring_stages(1, XS)>, dim3(2 * nb), dim3(256), s3);
-        } else if (f.nb <= 1024) {
-            // few sample buckets (C2, a rank's share in strong scaling): two 64-sample workgroups per bucket.
-            // Measured at C2 (469 buckets): stage 0.164 -> see DESIGN.md
-            launch(subset_exact_split_kernel<XT>, dim3(2 * nb, 3), dim3(256), s);
-        } else {
-            launch(subset_exact_all_kernel<XT>, dim3(nb), dim3(512), s);
+            // (the bin counts were added up by the sweep's workgroups as they wrote their list lengths)
+            hipLaunchKernelGGL(sched_fill_kernel, fill_grid, dim3(256), 0, s, f.ucount, (int)f.nb, f.sched_ctr, f.sched,
+                               (const uint8_t *)nullptr);
+        if (fork) {
+            DBGSOM_HIP_CHECK(hipEventRecord(side.forked, s));
+            DBGSOM_HIP_CHECK(hipStreamWaitEvent(s2, side.forked, 0));
+            DBGSOM_HIP_CHECK(hipStreamWaitEvent(s3, side.forked, 0));
         }
-    };
-    if (x_dtype == DBGSOM_F32) exact_stage(float{});
-    else exact_stage(double{});
-    if (fork) {
-        DBGSOM_HIP_CHECK(hipEventRecord(side.joined, s2));
-        DBGSOM_HIP_CHECK(hipEventRecord(side.joined2, s3));
-        DBGSOM_HIP_CHECK(hipStreamWaitEvent(s, side.joined, 0));
-        DBGSOM_HIP_CHECK(hipStreamWaitEvent(s, side.joined2, 0));
+        if (refine) {
+            hipLaunchKernelGGL(sched_fill_kernel, fill_grid, dim3(256), 0, s_mfma, f.ucount, (int)f.nb, f.sched_ctr, f.sched,
+                               (const uint8_t *)f.gflag);
+            if (fork) {  // (classes 2 and 1 run on the third stream: behind the schedule)
+                DBGSOM_HIP_CHECK(hipEventRecord(side.mid, s_mfma));
+                DBGSOM_HIP_CHECK(hipStreamWaitEvent(s3, side.mid, 0));
+            }
+            // every launch is a few workgroups per CU walking its class's queue: workgroups of nj x 256 threads,
+            // whole rounds of the 8 XCDs, at most `wgs` of them
+            auto refine_launch = [&](auto kernel, int nj, int cls, int64_t wgs) {
+                const int64_t nb8 = (f.nb + 7) / 8 * 8;
+                hipLaunchKernelGGL(kernel, dim3((unsigned)(nb8 < wgs ? nb8 : wgs)), dim3(nj * 256), 0, s, xb.planes, xb.scale,
+                                   xb.res16, c.xx, N, d, dpad, f.wt, (int)f.Mpad, f.wscale, c.ww, f.summary, order, f.ulist,
+                                   (int)f.Mpad, f.ucount, f.rf_queue + (size_t)cls * f.nb, f.rf_qlen + cls, f.cand, f.rbest,
+                                   f.rf_ctr, f.ovf, f.rf_qlen + 2, f.ovf_cand, defer_M, c.idx, c.dist);
+            };
+            if (fm.rows0 == 32) refine_launch(refine_i8_kernel<1, 1>, 1, 0, 1024);
+            else if (fm.rows0 == 64) refine_launch(refine_i8_kernel<1, 2>, 1, 0, 1024);
+            else if (fm.rows0 == 128) refine_launch(refine_i8_kernel<2, 2>, 2, 0, 512);
+            refine_launch(refine_i8_kernel<2, 4>, 2, 1, 512);
+            // the samples by their refined best prototype: a workgroup of the pair kernel then shares its candidates
+            const int64_t Mk = defer_M ? M + 1 : M;   // (deferred: the decided samples behind every real bucket)
+            const int rc = launch_bucket_sort(f.rbest, N, Mk, f.order2, f.sort_ws, s);
+            if (rc != DBGSOM_OK) return rc;
+            const uint32_t *n_active = defer_M ? bucket_sort_seg_start(f.sort_ws, N, Mk) + M : (const uint32_t *)nullptr;
+            // (bfloat16-resident samples: the pair kernel reads the stored rows -- half the bytes of the widened
+            //  copy the matrix kernels use, the same values)
+            auto pair_launch = [&](auto kernel, auto *rows, int64_t ld) {
+                const unsigned pgrid = (unsigned)(((N + PS - 1) / PS + 7) / 8 * 8);   // (whole rounds of the 8 XCDs: xcd_group)
+                hipLaunchKernelGGL(kernel, dim3(pgrid), dim3(256), 0, s, rows, N, d, ld, c.xx, c.W, c.ww, f.order2, f.cand,
+                                   c.round_f32, c.idx, c.dist, f.rf_ctr, n_active);
+            };
+            if (c.X_store && c.store_dtype == DBGSOM_BF16 && c.x_dtype == DBGSOM_F32)
+                pair_launch(pair_exact_kernel<bf16_t, 32, 128>, (const bf16_t *)c.X_store, c.ld_store);
+            else if (c.x_dtype == DBGSOM_F32) pair_launch(pair_exact_kernel<float, 16, 256>, (const float *)c.X, c.ldx);
+            else pair_launch(pair_exact_kernel<double, 16, 256>, (const double *)c.X, c.ldx);
+        }
+        // The matrix-core stage on the candidates, in the samples' type.  Every form takes the same arguments.
+        // (Wavefronts per 128-sample workgroup, measured as three launches, ms per stage, 4 / 8 / 8 for class 3
+        //  only: C4 1.23 / 1.23 / 1.16, C3 0.52 / 0.48, C5 shard 5.83 / 5.33 -- 8 for the long lists, 4 for the
+        //  rest; subset_exact_all_kernel runs every class as 8 in one launch, see there.)
+        auto exact_stage = [&](auto xt) {
+            using XT = decltype(xt);
+            constexpr int XS = (int)sizeof(XT);
+            const XT *X = (const XT *)c.X;
+            // (the samples whose candidates overflowed the refinement: behind the pair kernel, not beside it -- its
+            //  uncoalesced row walks slowed the sort and the pair kernel by more than it takes)
+            if (refine)
+                hipLaunchKernelGGL((overflow_exact_kernel<XT>), dim3(512), dim3(256), 0, s, X, d, c.ldx, c.xx, c.W, c.ww, f.ulist,
+                                   (int)f.Mpad, f.ucount, f.ovf, f.rf_qlen + 2, f.ovf_cand, c.round_f32, c.idx, c.dist);
+            auto launch = [&](auto kernel, dim3 grid, dim3 block, hipStream_t st) {
+                hipLaunchKernelGGL(kernel, grid, block, 0, st, X, N, d, c.ldx, c.xx, c.W, (int)M, c.ww, order, f.ulist,
+                                   (int)f.Mpad, f.ucount, f.sched, f.sched_ctr + 2 * SCHED_BINS, c.round_f32, c.idx, c.dist);
+            };
+            const unsigned nb = (unsigned)f.nb;
+            switch (fm.exact) {
+            case FilterForm::EXACT_K2:
+                // (8 wavefronts x 16 samples: with two (value, index) pairs per sample the 4 x 32 shape needed 256
+                //  registers for the long-list class and spilled in the others)
+                launch(subset_exact_kernel<XT, 3, 8, 1, 2>, dim3(nb), dim3(512), s_mfma);
+                launch(subset_exact_kernel<XT, 2, 8, 1, 2>, dim3(nb), dim3(512), s2);
+                launch(subset_exact_kernel<XT, 1, 8, 1, 2>, dim3(nb), dim3(512), s3);
+                break;
+            case FilterForm::EXACT_BESIDE_REFINE:
+                // (what is left to this stage is a few workgroups: two 64-sample ones per bucket, the long lists on
+                //  the second stream, the rest on the third)
+                launch(subset_exact_kernel<XT, 3, 4, 2, 1, split_ring_stages(3, XS)>, dim3(2 * nb), dim3(256), s_mfma);
+                launch(subset_exact_kernel<XT, 2, 4, 2, 1, split_ring_stages(2, XS)>, dim3(2 * nb), dim3(256), s3);
+                launch(subset_exact_kernel<XT, 1, 4, 2, 1, split_ring_stages(1, XS)>, dim3(2 * nb), dim3(256), s3);
+                break;
+            case FilterForm::EXACT_SPLIT:
+                // few sample buckets (C2, a rank's share in strong scaling): two 64-sample workgroups per bucket.
+                // Measured at C2 (469 buckets): stage 0.164 -> see DESIGN.md
+                launch(subset_exact_split_kernel<XT>, dim3(2 * nb, 3), dim3(256), s);
+                break;
+            case FilterForm::EXACT_ALL: launch(subset_exact_all_kernel<XT>, dim3(nb), dim3(512), s); break;
+            }
+        };
+        if (c.x_dtype == DBGSOM_F32) exact_stage(float{});
+        else exact_stage(double{});
+        if (fork) {
+            DBGSOM_HIP_CHECK(hipEventRecord(side.joined, s2));
+            DBGSOM_HIP_CHECK(hipEventRecord(side.joined2, s3));
+            DBGSOM_HIP_CHECK(hipStreamWaitEvent(s, side.joined, 0));
+            DBGSOM_HIP_CHECK(hipStreamWaitEvent(s, side.joined2, 0));
+        }
+        return DBGSOM_OK;
     }
-    g_timer.mark(5, s);
-    g_timer.valid = g_timer.enabled;
-    return launch_status("filtered bmu kernels");
+};
+}  // namespace
+
+int dbgsom::launch_bmu_filtered(const FilteredCall &call) {
+    FilterForm form;
+    const char *rejected = form.resolve(call.seed_stride, call.sweep_planes, call.k, call.refine_rows, call.defer_dist, call.N,
+                                        call.d, call.M, call.prev_idx != nullptr);
+    DBGSOM_REQUIRE(!rejected, rejected);
+    DBGSOM_REQUIRE(call.x_dtype == DBGSOM_F32 || call.x_dtype == DBGSOM_F64, "the filtered search takes float32 or float64 samples");
+    DBGSOM_REQUIRE(call.N >= 1 && call.N < 0x7fffffff && call.d >= 1 && call.d % KT == 0 && call.ldx >= call.d,
+                   "bad sample shape (d must be a multiple of 16)");
+    DBGSOM_REQUIRE(call.M >= 1 && call.M <= SW_MAX_M, "M outside [1, 16000]");
+    DBGSOM_REQUIRE(call.X && call.xx && call.xplanes && call.W && call.ww && call.idx && call.dist && call.ws, "null pointer");
+    DBGSOM_REQUIRE((call.prev_idx == nullptr) == (call.order == nullptr),
+                   "prev_idx and order come as a pair (both NULL = stateless two-pass search)");
+    DBGSOM_REQUIRE(is_aligned(call.X, 16) && (call.ldx * (int64_t)dtype_size(call.x_dtype)) % 16 == 0 &&
+                       is_aligned(call.W, 16) && is_aligned(call.ws, 256) && is_aligned(call.xplanes, 256), "alignment");
+    if (call.ws_bytes < dbgsom_bmu_filtered_workspace_bytes(call.N, call.d, call.M)) {
+        set_error("dbgsom_bmu_filtered: workspace too small");
+        return DBGSOM_ENOMEM;
+    }
+    FilterAux &aux = call.aux ? *call.aux : g_aux;
+    FilterRun r{call, form, aux, call.stream, (int)call.d, (int)filter_dpad(call.d), {}, {}, call.prev_idx, call.order};
+    carve_planes(&r.xb, (char *)const_cast<void *>(call.xplanes), call.N, call.d);
+    carve_filter(&r.f, (char *)call.ws, call.N, call.d, call.M);
+    StageTimer &timer = aux.timer;
+    timer.mark(0, r.s);
+    r.prepare_prototypes();
+    timer.mark(1, r.s);
+    int rc = r.seed_and_sort();
+    if (rc != DBGSOM_OK) return rc;
+    timer.mark(3, r.s);
+    rc = r.mark_candidates();
+    if (rc != DBGSOM_OK) return rc;
+    timer.mark(4, r.s);
+    rc = call.guard_mean > 0.0 ? r.guard_lists() : DBGSOM_OK;
+    if (rc == DBGSOM_OK) rc = r.exact_on_candidates();
+    if (rc != DBGSOM_OK && rc != DBGSOM_LISTS_LONG) return rc;
+    timer.mark(5, r.s);
+    timer.valid = timer.enabled;
+    return rc == DBGSOM_LISTS_LONG ? rc : launch_status("filtered bmu kernels");
 }
 
 extern "C" {
@@ -2926,19 +2781,6 @@ const unsigned long long *dbgsom_filter_count_sum_ptr(const void *workspace_dev,
     return reinterpret_cast<const unsigned long long *>(f.sched_ctr + SCHED_SUM);
 }
 
-/* diagnostics: sizes of the per-workgroup candidate lists of the last dbgsom_bmu_filtered call */
-int dbgsom_bmu_filtered_counts(const void *workspace_dev, int64_t N, int64_t d, int64_t M,
-                               uint32_t *counts_host, int64_t n_counts, void *stream) {
-    DBGSOM_REQUIRE(workspace_dev && counts_host, "null pointer");
-    FilterWs f;
-    carve_filter(&f, (char *)const_cast<void *>(workspace_dev), N, d, M);
-    DBGSOM_REQUIRE(n_counts == f.nb, "n_counts must be ceil(N / 128)");
-    DBGSOM_HIP_CHECK(hipMemcpyAsync(counts_host, f.ucount, (size_t)f.nb * 4, hipMemcpyDeviceToHost,
-                                    (hipStream_t)stream));
-    DBGSOM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-    return DBGSOM_OK;
-}
-
 int dbgsom_bmu_filtered_refine_counts(const void *workspace_dev, int64_t N, int64_t d, int64_t M,
                                       uint64_t *out4, void *stream) {
     DBGSOM_REQUIRE(workspace_dev && out4, "null pointer");
@@ -2949,8 +2791,9 @@ int dbgsom_bmu_filtered_refine_counts(const void *workspace_dev, int64_t N, int6
     return DBGSOM_OK;
 }
 
-/* the same copy, only queued on the stream: counts_host must be page-locked, the caller
- * synchronises (the estimator fetches it in the round trip that brings back the epoch's results) */
+/* diagnostics: sizes of the per-workgroup candidate lists of the last dbgsom_bmu_filtered call.  Only queued on
+ * the stream: counts_host must be page-locked, the caller synchronises (the estimator fetches it in the round trip
+ * that brings back the epoch's results) */
 int dbgsom_bmu_filtered_counts_async(const void *workspace_dev, int64_t N, int64_t d, int64_t M,
                                      uint32_t *counts_host, int64_t n_counts, void *stream) {
     DBGSOM_REQUIRE(workspace_dev && counts_host, "null pointer");
@@ -2959,6 +2802,15 @@ int dbgsom_bmu_filtered_counts_async(const void *workspace_dev, int64_t N, int64
     DBGSOM_REQUIRE(n_counts == f.nb, "n_counts must be ceil(N / 128)");
     DBGSOM_HIP_CHECK(hipMemcpyAsync(counts_host, f.ucount, (size_t)f.nb * 4, hipMemcpyDeviceToHost,
                                     (hipStream_t)stream));
+    return DBGSOM_OK;
+}
+
+/* the same, and waits for it */
+int dbgsom_bmu_filtered_counts(const void *workspace_dev, int64_t N, int64_t d, int64_t M,
+                               uint32_t *counts_host, int64_t n_counts, void *stream) {
+    const int rc = dbgsom_bmu_filtered_counts_async(workspace_dev, N, d, M, counts_host, n_counts, stream);
+    if (rc != DBGSOM_OK) return rc;
+    DBGSOM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
     return DBGSOM_OK;
 }
 
