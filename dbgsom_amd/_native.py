@@ -119,6 +119,10 @@ SIGNATURES = {
     "dbgsom_ctx_load_csr": (_ci, [_vp, _vp, _vp, _vp, _ci, _i64, _i64, _i64]),
     "dbgsom_ctx_bmu_query_csr": (_ci, [_vp, _vp, _vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _ci, _ci, _vp, _vp]),
     "dbgsom_ctx_sparse_code": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _ci, _vp, _i64, _vp, _vp, _vp]),
+    "dbgsom_bmu_masked_workspace_bytes": (_sz, [_ci, _i64, _i64, _i64]),
+    "dbgsom_bmu_masked": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _i64, _i64, _ci, _vp, _vp, _vp, _sz, _vp]),
+    "dbgsom_fill_missing": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp]),
+    "dbgsom_ctx_bmu_query_masked": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _ci, _vp, _vp, _vp]),
     "dbgsom_topofn_workspace_bytes": (_sz, [_i64, _ci]),
     "dbgsom_topofn": (_ci, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dbgsom_topofn_timing": (_ci, [_ci]),

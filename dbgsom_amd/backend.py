@@ -84,6 +84,13 @@ class HotPathBackend:
     def bmu(self, W, k=1, X=None):
         raise NotImplementedError
 
+    def bmu_masked(self, W, k, X, want_filled=False):
+        """``bmu(W, k, X=X)`` for dense rows with missing entries (NaN): the distance of a row x to a prototype w
+        is ``sqrt(d / n_obs * sum over the observed entries of (x - w) ** 2)`` in float64, direct form
+        (scikit-learn's ``nan_euclidean_distances``); ties go to the lowest index.  -> (distances, winners) in
+        ``bmu``'s shapes, and with ``want_filled`` a copy of X with every hole filled from the row's first winner."""
+        raise NotImplementedError
+
     def exp_similarity(self, distances, gamma):
         raise NotImplementedError
 
@@ -701,6 +708,30 @@ class HipBackend(HotPathBackend):
         if k == 1:
             return dist.reshape(-1), idx.reshape(-1)
         return dist, idx
+
+    # -- rows with missing entries ------------------------------------------------------------------
+    masked_chunk_rows = property(lambda self: self._get("masked_chunk_rows"),
+                                 lambda self, v: self._set("masked_chunk_rows", v))
+
+    def bmu_masked(self, W, k, X, want_filled=False):
+        """The search over the observed entries of every row on the device (csrc/masked.hip), in chunks of
+        ``masked_chunk_rows`` rows; with ``want_filled`` each chunk is filled there after its search."""
+        X = np.ascontiguousarray(X)
+        if X.dtype not in (np.float32, np.float64):
+            X = X.astype(np.float64)
+        W64 = np.ascontiguousarray(W, dtype=np.float64)
+        if X.ndim != 2 or W64.ndim != 2 or W64.shape[1] != X.shape[1]:
+            raise ValueError("prototype / sample feature mismatch")
+        N = X.shape[0]
+        idx = np.empty((N, k), dtype=np.int64)
+        dist = np.empty((N, k), dtype=np.float64)
+        filled = np.empty_like(X) if want_filled else None
+        self._call("dbgsom_ctx_bmu_query_masked", self._ctx, X.ctypes.data if N else None, _x_dtype_code(X.dtype), N,
+                   X.shape[1], W64.ctypes.data, W64.shape[0], int(k), idx.ctypes.data, dist.ctypes.data,
+                   None if filled is None else filled.ctypes.data)
+        if k == 1:
+            dist, idx = dist.reshape(-1), idx.reshape(-1)
+        return (dist, idx, filled) if want_filled else (dist, idx)
 
     def query_filter_applies(self, N, d, M, k=1):
         """Whether a k-BMU query on N other samples would go through the filtered search."""

@@ -82,6 +82,7 @@ class BaseSom(BaseEstimator):
         centres_layout: str = "compact",
         device=None,
         sharded_input: bool = False,
+        missing_values=None,
     ) -> None:
         self.n_iter = n_iter
         self.convergence_iter = convergence_iter
@@ -105,6 +106,7 @@ class BaseSom(BaseEstimator):
         self.centres_layout = centres_layout
         self.device = device
         self.sharded_input = sharded_input
+        self.missing_values = missing_values
 
     # ------------------------------------------------------------------------------------------
     # backend plumbing
@@ -146,7 +148,12 @@ class BaseSom(BaseEstimator):
             frequencies -- while the BMU search and the stream of X are paid once per distinct row.
             Rows of weight 0 take no part in anything.  Non-negative, finite, not all zero, at least
             four rows of positive weight.  ``None``: every row counts once (the unweighted code path).
-            ``predict`` / ``transform`` and the other queries on new data are not weighted."""
+            ``predict`` / ``transform`` and the other queries on new data are not weighted.
+
+        X must be complete: NaN is refused whatever ``missing_values`` says (that parameter opens the queries on
+        a fitted map to rows with missing entries -- fit on the complete cases, then place, score and fill in
+        the incomplete ones)."""
+        self._accepts_nan()   # (validates the parameter; fit itself takes complete rows only)
         if isinstance(X, DeviceSamples):   # a Voronoi subset that already lives in HBM (f-4)
             if y is not None:
                 y = np.asarray(y)
@@ -641,7 +648,86 @@ class BaseSom(BaseEstimator):
         if self._is_resident(data):
             dist, idx = engine.bmu(self.weights_, n_bmu)
             return self._gather_rows(dist), self._gather_rows(idx)
+        if self._accepts_nan() and isinstance(data, np.ndarray):
+            rows = self._incomplete_rows(data)
+            if rows.size:
+                return self._winning_neurons_with_holes(engine, data, rows, n_bmu)
         return engine.bmu(self.weights_, n_bmu, X=data)
+
+    # ------------------------------------------------------------------------------------------
+    # queries on rows with missing entries (missing_values="nan")
+    # ------------------------------------------------------------------------------------------
+    def _accepts_nan(self) -> bool:
+        """Whether the queries take NaN as "missing" (``missing_values="nan"``); None: NaN is refused."""
+        if self.missing_values is None:
+            return False
+        if isinstance(self.missing_values, str) and self.missing_values == "nan":
+            return True
+        raise ValueError(f"missing_values must be None or 'nan', got {self.missing_values!r}")
+
+    def _check_query(self, X, accept_sparse="csr"):
+        """check_array of a query: float32 kept, anything else float64; with ``missing_values="nan"`` NaN passes in
+        dense X (infinities never do, and a NaN among the stored entries of sparse X is refused as ever)."""
+        if not self._accepts_nan():
+            return check_array(X, dtype=[np.float64, np.float32], accept_sparse=accept_sparse)
+        X = check_array(X, dtype=[np.float64, np.float32], accept_sparse=accept_sparse, **self._finite_kw("allow-nan"))
+        if is_sparse(X):
+            from sklearn.utils import assert_all_finite
+
+            assert_all_finite(X.data)
+        return X
+
+    @staticmethod
+    def _incomplete_rows(X) -> np.ndarray:
+        """Indices of the rows of dense X with a NaN; a row with nothing but NaN is refused here, on the host."""
+        holes = np.isnan(X)
+        rows = np.flatnonzero(holes.any(axis=1))
+        if rows.size:
+            empty = holes[rows].all(axis=1)
+            if empty.any():
+                raise ValueError(f"row {int(rows[np.argmax(empty)])} of X has no observed entry: a row needs at "
+                                 "least one value that is not NaN")
+        return rows
+
+    def _winning_neurons_with_holes(self, engine, data, rows, n_bmu):
+        """The rows `rows` of data go through the search over their observed entries (``bmu_masked``), the complete
+        rows through ``bmu`` as ever -- their results are those of a call on just them -- and both are put back in
+        row order."""
+        n = data.shape[0]
+        shape = (n,) if n_bmu == 1 else (n, n_bmu)
+        dist, idx = np.empty(shape, dtype=np.float64), np.empty(shape, dtype=np.int64)
+        dist[rows], idx[rows] = engine.bmu_masked(self.weights_, n_bmu, data[rows])
+        if rows.size < n:
+            complete = np.ones(n, dtype=bool)
+            complete[rows] = False
+            complete = np.flatnonzero(complete)
+            dist[complete], idx[complete] = engine.bmu(self.weights_, n_bmu, X=data[complete])
+        return dist, idx
+
+    def impute(self, X) -> np.ndarray:
+        """A copy of X (float32 kept, anything else float64) with every NaN replaced by that entry of the row's
+        best matching prototype, the nearest one over the row's observed entries.  Observed entries and complete
+        rows come back bit for bit, X itself is never written.  Needs ``missing_values="nan"``; dense X; only this
+        map's prototypes are used (not the child maps of vertical growth)."""
+        check_is_fitted(self)
+        if not self._accepts_nan():
+            raise ValueError("impute needs missing_values='nan'")
+        return self._impute_checked(self._check_query(X, accept_sparse=False), copy=True)
+
+    def _impute_checked(self, X, copy=False):
+        rows = self._incomplete_rows(X)
+        if copy or rows.size:
+            X = X.copy()
+        if rows.size:
+            X[rows] = self._engine().bmu_masked(self.weights_, 1, X[rows], want_filled=True)[2]
+        return X
+
+    def _complete_query(self, X):
+        """A validated query for the coder: rows with NaN are completed by ``impute`` (the sparse code works on
+        normalised rows and has no meaning for a hole)."""
+        if self._accepts_nan() and isinstance(X, np.ndarray):
+            return self._impute_checked(X)
+        return X
 
     def _calculate_exp_similarity(self, distances):
         """Per-sample weight 1 - sqrt(1 - exp(-gamma d^2)) (BaseSom.py:533-538)."""
@@ -679,7 +765,7 @@ class BaseSom(BaseEstimator):
         check_is_fitted(self)
         if self._is_resident(X):  # during fit: a device reduction, distances never leave HBM
             return self._engine().quantization_error(self.weights_)
-        X = check_array(X, dtype=[np.float64, np.float32], accept_sparse="csr")
+        X = self._check_query(X)
         distances, _ = self._get_winning_neurons(X, n_bmu=1)
         return float(np.mean(distances))
 
@@ -741,7 +827,7 @@ class BaseSom(BaseEstimator):
         SparseCoder on normalize(X) with dictionary normalize(weights_), computed by the backend
         (on the MI355X: csrc/sparse_code.hip; n_jobs only matters to the host default)."""
         check_is_fitted(self)
-        X = check_array(X, dtype=[np.float64, np.float32], accept_sparse="csr")
+        X = self._complete_query(self._check_query(X))
         return self._sparse_code(X)
 
     _SPARSE_CODE_ROWS = 4096   # rows of sparse X densified at a time for the sparse coder

@@ -150,6 +150,15 @@ int launch_csr_rows_to_f64(const CsrView &x, int dtype, const int64_t *ids, int6
 int launch_accumulate_csr(const CsrView &x, int x_dtype, int64_t N, int64_t d, const int64_t *idx, const double *kw,
                           double gamma, const double *sw, const double *dist, int64_t M, double *sums,
                           int32_t *status, bool status_behind_sums, void *ws, size_t ws_bytes, hipStream_t s);
+// rows with missing entries (masked.hip): NaN marks a hole, F32 / F64 rows; the search reads the transposed float64
+// prototypes launch_masked_weights leaves in front of the workspace (one transposition serves many row chunks)
+size_t bmu_masked_workspace_bytes(int x_dtype, int64_t N, int64_t d, int64_t M);
+int masked_check_shape(int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, int k);
+int launch_masked_weights(const double *W, int64_t M, int64_t d, int64_t ldw, void *ws, hipStream_t s);
+int launch_bmu_masked_rows(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, int k,
+                           int64_t *idx, double *dist, void *ws, size_t ws_bytes, hipStream_t s);
+int launch_fill_missing(void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *W, int64_t M,
+                        int64_t ldw, const int64_t *idx, int64_t idx_stride, hipStream_t s);
 size_t bucket_sort_workspace_bytes(int64_t N, int64_t M);
 int launch_bucket_sort(const int64_t *idx, int64_t N, int64_t M, int32_t *order, void *ws,
                        hipStream_t s);

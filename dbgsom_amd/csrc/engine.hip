@@ -247,6 +247,8 @@ struct dbgsom_ctx {
     int64_t sc_chunk_rows = 32768;  // sparse coding: query rows per chunk
     int64_t sc_cap = 0;             // sparse coding: active-set cap of the LDS path (0 = library default)
     DevBuf sc_ws, sc_x, sc_w, sc_p, sc_code, sc_proba, sc_cnt;
+    int64_t masked_chunk_rows = 32768;  // rows with missing entries: query rows per chunk
+    DevBuf mk_ws, mk_x, mk_w, mk_idx, mk_dist;
     // samples
     Samples xs, xq;
     DevBuf y;
@@ -950,7 +952,8 @@ int dbgsom_ctx_create(int device, dbgsom_ctx **out) {
     {&(c)->y, &(c)->hop, &(c)->hop_stage, &(c)->Wb[0], &(c)->Wb[1], &(c)->ww, &(c)->idx[0], &(c)->idx[1], &(c)->dist,  \
      &(c)->kw, &(c)->sums, &(c)->acc_ws, &(c)->sm_ws, &(c)->filt_ws, &(c)->scal, &(c)->qidx, &(c)->qdist, &(c)->red,  \
      &(c)->hist, &(c)->stage_dev, &(c)->part_order, &(c)->part_ws, &(c)->part_counts, &(c)->shiftb, &(c)->shard_send,    \
-     &(c)->shard_gather, &(c)->sw, &(c)->wh_order, &(c)->wh_ws, &(c)->sc_ws, &(c)->sc_x, &(c)->sc_w, &(c)->sc_p, &(c)->sc_code, &(c)->sc_proba, &(c)->sc_cnt, &(c)->wt}
+     &(c)->shard_gather, &(c)->sw, &(c)->wh_order, &(c)->wh_ws, &(c)->sc_ws, &(c)->sc_x, &(c)->sc_w, &(c)->sc_p, &(c)->sc_code, &(c)->sc_proba, &(c)->sc_cnt, &(c)->wt,  \
+     &(c)->mk_ws, &(c)->mk_x, &(c)->mk_w, &(c)->mk_idx, &(c)->mk_dist}
 
 int dbgsom_ctx_destroy(dbgsom_ctx *c) {
     if (!c) return DBGSOM_OK;
@@ -1001,6 +1004,9 @@ int dbgsom_ctx_set_option(dbgsom_ctx *c, const char *name, int64_t v) {
     } else if (!strcmp(name, "sc_chunk_rows")) {
         DBGSOM_REQUIRE(v >= 1 && v <= ((int64_t)1 << 22), "sc_chunk_rows must be in [1, 2^22]");
         c->sc_chunk_rows = v;
+    } else if (!strcmp(name, "masked_chunk_rows")) {
+        DBGSOM_REQUIRE(v >= 1 && v <= ((int64_t)1 << 22), "masked_chunk_rows must be in [1, 2^22]");
+        c->masked_chunk_rows = v;
     } else if (!strcmp(name, "sc_cap")) {
         DBGSOM_REQUIRE(v >= 0 && v <= 64, "sc_cap must be in [0, 64] (0 = the library's cap)");
         c->sc_cap = v;
@@ -1039,6 +1045,7 @@ int dbgsom_ctx_get_option(dbgsom_ctx *c, const char *name, int64_t *v) {
     else if (!strcmp(name, "max_mean_candidates")) *v = c->policy.max_mean_candidates;
     else if (!strcmp(name, "sc_chunk_rows")) *v = c->sc_chunk_rows;
     else if (!strcmp(name, "sc_cap")) *v = c->sc_cap;
+    else if (!strcmp(name, "masked_chunk_rows")) *v = c->masked_chunk_rows;
     else if (!strcmp(name, "csr_densify_below")) *v = c->csr_densify_below;
     else if (!strcmp(name, "resident_csr")) *v = (c->xs.dtype >= 0 && c->xs.csr) ? 1 : 0;
     else if (!strcmp(name, "resident_nnz")) *v = (c->xs.dtype >= 0 && c->xs.csr) ? c->xs.nnz : 0;
@@ -1469,6 +1476,80 @@ int dbgsom_ctx_bmu_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const in
     if (Nq == 0) return dbgsom_csr_check(indptr_host, indices_host, 0, d, nnz);
     return bmu_query_impl(c, data_host, indptr_host, indices_host, nnz, x_dtype, Nq, d, W_host, M, k, round_f32, idx_host,
                           dist_host);
+}
+
+// ------------------------------------------------------------------------------------------
+// query rows with missing entries (NaN): csrc/masked.hip, in chunks of query rows
+// ------------------------------------------------------------------------------------------
+static int64_t first_row_without_entries(const void *X, int x_dtype, int64_t N, int64_t d) {
+    for (int64_t i = 0; i < N; ++i) {
+        int64_t c = 0;
+        if (x_dtype == DBGSOM_F32) {
+            const float *x = static_cast<const float *>(X) + i * d;
+            while (c < d && x[c] != x[c]) ++c;
+        } else {
+            const double *x = static_cast<const double *>(X) + i * d;
+            while (c < d && x[c] != x[c]) ++c;
+        }
+        if (c == d) return i;
+    }
+    return -1;
+}
+
+int dbgsom_ctx_bmu_query_masked(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host,
+                                void *Xfilled_host) {
+    CTX_CHECK(c);
+    TRY(masked_check_shape(x_dtype, Nq, d, d, M, k));
+    if (Nq == 0) return DBGSOM_OK;
+    DBGSOM_REQUIRE(Xq_host && W_host && idx_host && dist_host, "null pointer");
+    const int64_t bad = first_row_without_entries(Xq_host, x_dtype, Nq, d);
+    if (bad >= 0) {
+        set_error("dbgsom_ctx_bmu_query_masked: row %lld has no observed entry", (long long)bad);
+        return DBGSOM_EINVAL;
+    }
+    const int64_t chunk = std::min<int64_t>(Nq, c->masked_chunk_rows);
+    const size_t es = dtype_size(x_dtype);
+    int rc = DBGSOM_OK;
+    do {
+        if ((rc = c->mk_ws.reserve(bmu_masked_workspace_bytes(x_dtype, chunk, d, M)))) break;
+        if ((rc = c->mk_x.reserve((size_t)chunk * d * es))) break;
+        if ((rc = c->mk_w.reserve((size_t)M * d * 8))) break;
+        if ((rc = c->mk_idx.reserve((size_t)chunk * k * 8))) break;
+        if ((rc = c->mk_dist.reserve((size_t)chunk * k * 8))) break;
+        hipError_t e = hipMemcpyAsync(c->mk_w.p, W_host, (size_t)M * d * 8, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
+        if ((rc = launch_masked_weights(c->mk_w.as<double>(), M, d, d, c->mk_ws.p, c->stream))) break;
+        for (int64_t r0 = 0; r0 < Nq && rc == DBGSOM_OK; r0 += chunk) {
+            const int64_t n = std::min(chunk, Nq - r0);
+            e = hipMemcpyAsync(c->mk_x.p, static_cast<const char *>(Xq_host) + (size_t)r0 * d * es, (size_t)n * d * es,
+                               hipMemcpyHostToDevice, c->stream);
+            if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
+            if ((rc = launch_bmu_masked_rows(c->mk_x.p, x_dtype, n, d, d, M, k, c->mk_idx.as<int64_t>(),
+                                             c->mk_dist.as<double>(), c->mk_ws.p, c->mk_ws.cap, c->stream)))
+                break;
+            e = hipMemcpyAsync(idx_host + r0 * k, c->mk_idx.p, (size_t)n * k * 8, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(dist_host + r0 * k, c->mk_dist.p, (size_t)n * k * 8, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess && Xfilled_host) {
+                if ((rc = launch_fill_missing(c->mk_x.p, x_dtype, n, d, d, c->mk_w.as<double>(), M, d,
+                                              c->mk_idx.as<int64_t>(), k, c->stream)))
+                    break;
+                e = hipMemcpyAsync(static_cast<char *>(Xfilled_host) + (size_t)r0 * d * es, c->mk_x.p, (size_t)n * d * es,
+                                   hipMemcpyDeviceToHost, c->stream);
+            }
+            if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; }
+        }
+    } while (0);
+    const hipError_t es_ = hipStreamSynchronize(c->stream);
+    if (rc == DBGSOM_OK && es_ != hipSuccess) {
+        set_error("hipStreamSynchronize failed: %s", hipGetErrorString(es_));
+        rc = DBGSOM_EHIP;
+    }
+    if (c->mk_ws.cap + c->mk_x.cap > ((size_t)256 << 20)) {   // do not sit on a large one-off batch
+        c->mk_ws.release(); c->mk_x.release(); c->mk_idx.release(); c->mk_dist.release();
+    }
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------------

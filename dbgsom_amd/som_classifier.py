@@ -11,7 +11,7 @@ from statistics import mode
 
 import numpy as np
 from sklearn.base import ClassifierMixin, TransformerMixin
-from sklearn.utils import check_array, check_X_y
+from sklearn.utils import check_X_y
 from sklearn.utils.validation import check_is_fitted
 
 from .backend import is_sparse
@@ -66,15 +66,17 @@ class SomClassifier(BaseSom, TransformerMixin, ClassifierMixin):
 
     def predict(self, X) -> np.ndarray:
         check_is_fitted(self)
-        X = check_array(X, dtype=[np.float64, np.float32], accept_sparse="csr")
+        X = self._check_query(X)
         return self.classes_[np.argmax(self.predict_proba(X=X), axis=1)]
 
     def predict_proba(self, X) -> np.ndarray:
         """Class probabilities: sparse code over the prototypes times the prototypes' class
         frequencies, rows normalised (SomClassifier.py:178-220)."""
         check_is_fitted(self)
-        X = check_array(X, dtype=[np.float64, np.float32], accept_sparse="csr")
+        X = self._check_query(X)
         if self.vertical_growth:
+            if self._accepts_nan() and isinstance(X, np.ndarray) and np.isnan(X).any():
+                raise ValueError("predict_proba with vertical_growth=True takes complete rows only (impute them first)")
             _, winners = self._get_winning_neurons(X, n_bmu=1)
             rows = []
             for i, w in enumerate(winners):
@@ -91,4 +93,5 @@ class SomClassifier(BaseSom, TransformerMixin, ClassifierMixin):
                     rows.append(attrs["probabilities"])
             return np.array(rows)
         # the code never leaves the backend: it returns (code @ P) normalised per row
+        X = self._complete_query(X)
         return self._sparse_code(X, P=self._extract_values_from_graph("probabilities"))

@@ -34,7 +34,7 @@ class SomVQ(BaseSom, ClusterMixin, TransformerMixin):
         if not self._is_resident(X):
             # integer / half input is converted like the reference's engine does (sklearn's
             # NearestNeighbors); float32 stays float32
-            X = check_array(X, dtype=[np.float64, np.float32], accept_sparse="csr")
+            X = self._check_query(X)
         _, labels = self._get_winning_neurons(X, n_bmu=1)
         return labels
 

@@ -465,6 +465,33 @@ int dbgsom_ctx_bmu_query_csr(dbgsom_ctx *ctx, const int64_t *indptr_host, const 
                              const double *W_host, int64_t M, int k, int round_f32, int64_t *idx_host,
                              double *dist_host);
 
+/* ---- query rows with missing entries (csrc/masked.hip) ---------------------------------------------
+ * A NaN in a row of X marks a missing entry; prototypes are complete.  With O(x) the observed entries of a
+ * row and n_obs their number,
+ *   dist(x, w) = sqrt((d / n_obs) * sum_{k in O(x)} (x_k - w_k)^2)
+ * (scikit-learn's nan_euclidean_distances; a complete row gets the plain distance).  Direct form in
+ * float64 -- t = x_k - w_k, acc = fma(t, t, acc), k ascending -- so a row that equals a prototype on its
+ * observed entries is at 0.0 exactly, and a (row, prototype) pair's bits depend on that row and that
+ * prototype only.  arg-k-min over j on (sum, j), ties to the lowest j, k in {1, 2}; idx N x k int64, dist
+ * N x k float64 as dbgsom_bmu.  There is no float32 rounding of these distances.
+ *   X: N x d, DBGSOM_F32 or DBGSOM_F64 (DBGSOM_BF16 is DBGSOM_EINVAL), ldx <= 2^27; W: M x d float64.
+ *   A row without any observed entry gets dist = NaN (the context call refuses such rows beforehand).
+ * dbgsom_fill_missing writes (x_dtype) W[idx[i * idx_stride]][c] into every NaN position (i, c) of X and
+ * leaves everything else as it is (rows whose index is outside [0, M) too). */
+size_t dbgsom_bmu_masked_workspace_bytes(int x_dtype, int64_t N, int64_t d, int64_t M);
+int dbgsom_bmu_masked(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx,
+                      const double *W_dev, int64_t M, int64_t ldw, int k, int64_t *idx_dev,
+                      double *dist_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+int dbgsom_fill_missing(void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *W_dev,
+                        int64_t M, int64_t ldw, const int64_t *idx_dev, int64_t idx_stride, void *stream);
+/* The same from host arrays, in chunks of ctx option "masked_chunk_rows" rows on the context's stream.
+ * Xfilled_host (Nq x d, x_dtype; may be NULL): the rows with their holes filled from the first winner
+ * (filled on the device after each chunk's search).  A row without any observed entry is DBGSOM_EINVAL,
+ * found on the host before anything is launched; the message names the first such row. */
+int dbgsom_ctx_bmu_query_masked(dbgsom_ctx *ctx, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                const double *W_host, int64_t M, int k, int64_t *idx_host,
+                                double *dist_host, void *Xfilled_host);
+
 /* ---- sparse coding: BaseSom.transform / SomClassifier.predict_proba (BaseSom.py:241-268,
  * SomClassifier.py:178-220) ------------------------------------------------------------------------
  * scikit-learn's SparseCoder(dictionary=normalize(W), transform_algorithm="lasso_lars",
