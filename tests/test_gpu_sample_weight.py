@@ -81,8 +81,9 @@ def _check_against_repeated_rows(o, be, Xr, W, hop, w, sigma, tv, ref_win, ref_d
     return res
 
 
-# shapes of segsum_kernel: narrow rows with row lanes / the scalar path (d = 37) / wide rows; M on both sides of
-# the second-level sum of finalize_kernel (finalize_groups: M <= 256) and of 512
+# shapes of segsum_kernel: narrow rows with row lanes (d = 37 too: the context pads it to 48, so it takes the vector
+# loads and row lanes -- the scalar instantiations are run by tests/test_gpu_device_abi.py) / wide rows; M on both
+# sides of the second-level sum of finalize_kernel (finalize_groups: M <= 256) and of 512
 @pytest.mark.parametrize("dt,N,d,M", [("f32", 6000, 48, 30), ("f64", 5000, 37, 300), ("bf16", 7000, 64, 600),
                                       ("f32", 3000, 1040, 140)])
 def test_weighted_epoch_matches_the_oracle_on_repeated_rows(o, dt, N, d, M):
