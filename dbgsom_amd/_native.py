@@ -59,6 +59,7 @@ SIGNATURES = {
     "dbgsom_bmu_filtered_counts": (_ci, [_vp, _i64, _i64, _i64, _vp, _i64, _vp]),
     "dbgsom_bmu_filtered_counts_async": (_ci, [_vp, _i64, _i64, _i64, _vp, _i64, _vp]),
     "dbgsom_bmu_filtered_refine_counts": (_ci, [_vp, _i64, _i64, _i64, _vp, _vp]),
+    "dbgsom_bmu_filtered_gaps": (_ci, [_vp, _i64, _i64, _i64, _vp, _vp]),
     "dbgsom_filter_timing": (_ci, [_ci]),
     "dbgsom_bmu_filtered_stage_ms": (_ci, [_vp]),
     "dbgsom_sum_workspace_bytes": (_sz, []),

@@ -1496,6 +1496,12 @@ constexpr double PLANE0_ERR = 32897.0 / (127.0 * 65536.0) * (1.0 + 1e-6);
 // k loop and a float64 epilogue of 64 values per lane with nothing to overlap them with (141 us at C4, on the
 // critical path of every epoch that starts from hints) -- and take NB = 1: four times the wavefronts, a quarter
 // of the epilogue each
+// The per-row terms of a gap, each rounded on its own and formed the same way for the row and for the column of a
+// pair: with them joined by one addition each, gap[p][j] and gap[j][p] are the same bits (left to the compiler, one
+// side's product was fused into the sum and the two tiles that hold a pair rounded it differently)
+__device__ __forceinline__ double gap_row_sq(double t, double B) { return __dmul_rn(__dmul_rn(t, t), B); }
+__device__ __forceinline__ double gap_row_err(double root_d, double t) { return __dmul_rn(__dmul_rn(root_d, t), PLANE0_ERR); }
+
 template <int NB>
 __global__ __launch_bounds__(64) void proto_gap_kernel(const int8_t *__restrict__ wt, int w_rows, int dpad, int M, int d,
                                                        const double *__restrict__ tw, const double *__restrict__ wn0,
@@ -1556,21 +1562,23 @@ __global__ __launch_bounds__(64) void proto_gap_kernel(const int8_t *__restrict_
     }
     const double root_d = sqrt((double)d) * (1.0 + 1e-12);
     // the tile's 64 column prototypes: scale and digit norm once, through LDS (every lane needs 32 of them)
-    __shared__ double tj_s[64], bj_s[64];
+    __shared__ double tj_s[64], aj_s[64], ej_s[64];
     {
         const int j = jb + lane;   // (NB = 1: the upper half is filled and never read)
-        tj_s[lane] = j < M ? tw[j] : 0.0;
+        const double tj = j < M ? tw[j] : 0.0;
+        tj_s[lane] = tj;
         // (a row with a NaN or an infinity has digits that mean nothing: 0 |w|^2 turns into a NaN and
         //  the pair gets "no gap known")
-        bj_s[lane] = j < M ? wn0[j] + 0.0 * ww[j] : 0.0;
+        aj_s[lane] = gap_row_sq(tj, j < M ? wn0[j] + 0.0 * ww[j] : 0.0);
+        ej_s[lane] = gap_row_err(root_d, tj);
     }
     __syncthreads();
 #pragma unroll
     for (int it = 0; it < NB; ++it) {
         const int p = pb + it * 32 + lc;
         const bool pok = p < M;
-        const double tp = pok ? tw[p] : 0.0, Bp = pok ? wn0[p] + 0.0 * ww[p] : 0.0;
-        const double ep = root_d * tp * PLANE0_ERR;
+        const double tp = pok ? tw[p] : 0.0, Ap = gap_row_sq(tp, pok ? wn0[p] + 0.0 * ww[p] : 0.0);
+        const double ep = gap_row_err(root_d, tp);
         float near_ub = INFINITY;
 #pragma unroll
         for (int jt = 0; jt < NB; ++jt)
@@ -1578,20 +1586,20 @@ __global__ __launch_bounds__(64) void proto_gap_kernel(const int8_t *__restrict_
             for (int r = 0; r < 16; ++r) {
                 const int jl = jt * 32 + 4 * lh + (r & 3) + 8 * (r >> 2), j = jb + jl;
                 if (!pok || j >= M) continue;
-                const double tj = tj_s[jl], Bj = bj_s[jl], Pv = (double)P[jt][it][r];
-                const double sq = tp * tp * Bp + tj * tj * Bj, cr = 2.0 * tp * tj * Pv;
+                const double tj = tj_s[jl], Pv = (double)P[jt][it][r];
+                const double sq = __dadd_rn(Ap, aj_s[jl]), cr = 2.0 * tp * tj * Pv, epj = __dadd_rn(ep, ej_s[jl]);
                 if (nnub && j != p) {
                     const double uh2 = ((sq - cr) + 1e-12 * (sq + fabs(cr))) * (1.0 / 16129.0) * (1.0 + 1e-12);
                     // (a NaN -- a row with a NaN or an infinity, whose digits mean nothing -- stays a NaN and never
                     //  becomes the minimum: no bound from that pair)
                     const double dh = uh2 > 0.0 ? sqrt(uh2) * (1.0 + 1e-12) : (uh2 == uh2 ? 0.0 : uh2);
-                    const double ub = (dh + (ep + root_d * tj * PLANE0_ERR)) * (1.0 + 1e-6);
+                    const double ub = (dh + epj) * (1.0 + 1e-6);
                     if (ub < 3.0e38) near_ub = fminf(near_ub, __double2float_ru(ub));
                 }
                 // (the division by 127^2 as a product by its rounded reciprocal: 2^-53 relative, far
                 //  inside the 1e-12 margins taken just before and after)
                 const double dh2 = ((sq - cr) - 1e-12 * (sq + fabs(cr))) * (1.0 / 16129.0);
-                const double lo = (dh2 > 0.0 ? sqrt(dh2) * (1.0 - 1e-12) : 0.0) - (ep + root_d * tj * PLANE0_ERR);
+                const double lo = (dh2 > 0.0 ? sqrt(dh2) * (1.0 - 1e-12) : 0.0) - epj;
                 const double v = lo > 0.0 ? lo * lo * (1.0 - 1e-6) : 0.0;
                 // (anything that is not a positive finite number: no gap known)
                 gap[(size_t)j * ldg + p] = (v > 0.0 && v < 3.0e38) ? __double2float_rz(v) : 0.f;
@@ -2810,6 +2818,19 @@ int dbgsom_bmu_filtered_counts(const void *workspace_dev, int64_t N, int64_t d, 
                                uint32_t *counts_host, int64_t n_counts, void *stream) {
     const int rc = dbgsom_bmu_filtered_counts_async(workspace_dev, N, d, M, counts_host, n_counts, stream);
     if (rc != DBGSOM_OK) return rc;
+    DBGSOM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    return DBGSOM_OK;
+}
+
+/* diagnostics: the M x M corner of the gap table (2c) the last call with DBGSOM_PRUNE or DBGSOM_PRUNE_PROBE left in
+ * the workspace; synchronises the stream */
+int dbgsom_bmu_filtered_gaps(const void *workspace_dev, int64_t N, int64_t d, int64_t M, float *gap_host, void *stream) {
+    DBGSOM_REQUIRE(workspace_dev && gap_host, "null pointer");
+    DBGSOM_REQUIRE(N >= 1 && d >= 1 && M >= 1 && M <= PRUNE_MAX_M, "no gap table: M outside [1, 8192]");
+    FilterWs f;
+    carve_filter(&f, (char *)const_cast<void *>(workspace_dev), N, d, M);
+    DBGSOM_HIP_CHECK(hipMemcpy2DAsync(gap_host, (size_t)M * 4, f.gap, (size_t)f.Mg * 4, (size_t)M * 4, (size_t)M,
+                                      hipMemcpyDeviceToHost, (hipStream_t)stream));
     DBGSOM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
     return DBGSOM_OK;
 }

@@ -228,6 +228,12 @@ int dbgsom_bmu_filtered_counts(const void *workspace_dev, int64_t N, int64_t d, 
  * valid once the caller has synchronised the stream */
 int dbgsom_bmu_filtered_counts_async(const void *workspace_dev, int64_t N, int64_t d, int64_t M,
                                      uint32_t *counts_host, int64_t n_counts, void *stream);
+/* diagnostics: the gap table of the triangle-inequality form, gap_host[p * M + j] <= |w_p - w_j|^2 (M x M float32,
+ * symmetric bit for bit; 0 = no gap known: the diagonal, duplicates, rows with a NaN or an infinity).  Valid after a call with DBGSOM_PRUNE
+ * or DBGSOM_PRUNE_PROBE on this workspace with the same N, d, M; M > 8192 (no table) is DBGSOM_EINVAL.  Synchronises
+ * the stream. */
+int dbgsom_bmu_filtered_gaps(const void *workspace_dev, int64_t N, int64_t d, int64_t M, float *gap_host,
+                             void *stream);
 
 /* diagnostics of the per-sample refinement (DBGSOM_REFINE) of the last filtered call:
  * out4 = [(sample, prototype) pairs evaluated exactly, 128-sample workgroups refined (the others went

@@ -142,6 +142,31 @@ def test_coarse_prepass_is_a_valid_seed_source():
 PLANE0_ERR = 32897.0 / (127.0 * 65536.0) * (1.0 + 1e-6)
 
 
+def hat_dist2(a0, sa, b0, sb, sign):
+    """|a^ - b^|^2 of rows a^ = sa a0 / 127, nudged down (sign -1) or up (+1) by the rounding margin"""
+    A = (a0 * a0).sum(1).astype(np.float64)
+    B = (b0 * b0).sum(1).astype(np.float64)
+    P = a0.astype(np.float64) @ b0.T.astype(np.float64)      # (exact: |P| <= 127^2 d, far below 2^53)
+    sq = (sa * sa * A)[:, None] + (sb * sb * B)[None, :]
+    cr = 2.0 * sa[:, None] * sb[None, :] * P
+    return ((sq - cr) + sign * 1e-12 * (sq + np.abs(cr))) / 16129.0
+
+
+def proto_gap(W):
+    """NumPy statement of proto_gap_kernel -> (gap, lo, e): gap[p, j] the float32 table as float64, lo[p, j] =
+    |w^_p - w^_j| (1 - 1e-12) - e[p, j] what it is the square of, e[p, j] = e_p + e_j the two rows' top-plane errors"""
+    d = W.shape[1]
+    (w0, _, _), tw, _ = slice_rows(W)
+    root_d = np.sqrt(float(d)) * (1 + 1e-12)
+    dh2 = hat_dist2(w0, tw, w0, tw, -1)
+    e = root_d * (tw[:, None] + tw[None, :]) * PLANE0_ERR
+    lo = np.where(dh2 > 0, np.sqrt(np.maximum(dh2, 0)) * (1 - 1e-12), 0.0) - e
+    gap = np.where(lo > 0, lo * lo * (1 - 1e-6), 0.0)
+    g32 = gap.astype(np.float32)
+    g32 = np.where(g32.astype(np.float64) > gap, np.nextafter(g32, np.float32(0)), g32)   # rounded towards zero
+    return g32.astype(np.float64), lo, e
+
+
 def prune_survivors(X, W, seeds):
     """NumPy statement of proto_gap_kernel + prune_mark_kernel (top digit plane only): survivors[i, j]
     is False only where the rule PROVES r(i, j) > r(i, seed_i)."""
@@ -149,23 +174,7 @@ def prune_survivors(X, W, seeds):
     (x0, _, _), sx, _ = slice_rows(X)
     (w0, _, _), tw, _ = slice_rows(W)
     root_d = np.sqrt(float(d)) * (1 + 1e-12)
-
-    def hat_dist2(a0, sa, b0, sb, sign):
-        """|a^ - b^|^2 of rows a^ = sa a0 / 127, nudged down (sign -1) or up (+1) by the rounding margin"""
-        A = (a0 * a0).sum(1).astype(np.float64)
-        B = (b0 * b0).sum(1).astype(np.float64)
-        P = (a0 @ b0.T).astype(np.float64)
-        sq = (sa * sa * A)[:, None] + (sb * sb * B)[None, :]
-        cr = 2.0 * sa[:, None] * sb[None, :] * P
-        return ((sq - cr) + sign * 1e-12 * (sq + np.abs(cr))) / 16129.0
-
-    dh2 = hat_dist2(w0, tw, w0, tw, -1)
-    lo = np.where(dh2 > 0, np.sqrt(np.maximum(dh2, 0)) * (1 - 1e-12), 0.0) \
-        - root_d * (tw[:, None] + tw[None, :]) * PLANE0_ERR
-    gap = np.where(lo > 0, lo * lo * (1 - 1e-6), 0.0)
-    g32 = gap.astype(np.float32)
-    g32 = np.where(g32.astype(np.float64) > gap, np.nextafter(g32, np.float32(0)), g32)   # rounded towards zero
-    gap = g32.astype(np.float64)
+    gap, _, _ = proto_gap(W)
     n = X.shape[0]
     xx = (X ** 2).sum(1)
     yy = (W ** 2).sum(1)
