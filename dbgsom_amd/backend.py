@@ -430,6 +430,14 @@ class HipBackend(HotPathBackend):
                                  lambda self, v: self._set("csr_densify_below", int(v)))
     resident_csr = property(lambda self: bool(self._get("resident_csr")))
     planes_cached = property(lambda self: bool(self._get("planes_cached")))
+    # the stateless pruning search of the resident samples takes its seeds from anchor buckets built once per load
+    # (filter.hip 2e) instead of a seed pre-pass per epoch: 1 (default) / 0; results do not depend on it.
+    # anchor_builds: how often they were built; anchor_state: 0 none, 1 in use, 2 dropped (longer lists than the
+    # pre-pass's on this sample set).  A caller's seed_stride keeps the policy on the cheap seeds (no full pre-pass).
+    anchor_seeds = property(lambda self: self._get("anchor_seeds"), lambda self, v: self._set("anchor_seeds", int(v)))
+    anchor_builds = property(lambda self: self._get("anchor_builds"))
+    anchor_searches = property(lambda self: self._get("anchor_searches"))   # searches seeded from them so far
+    anchor_state = property(lambda self: self._get("anchor_state"))
     padded_features = property(lambda self: self._get("padded_features"))
 
     @property
@@ -1064,7 +1072,7 @@ class HipBackend(HotPathBackend):
         return sub
 
     _SETTABLE = ("algorithm", "sweep_planes", "seed_stride", "timing", "graph", "refine", "defer",
-                 "filter_min_query_rows", "max_mean_candidates", "shard_smooth", "csr_densify_below")
+                 "filter_min_query_rows", "max_mean_candidates", "shard_smooth", "csr_densify_below", "anchor_seeds")
 
     def release(self):
         """Give the device memory back (the backend can be loaded again afterwards; options stay)."""

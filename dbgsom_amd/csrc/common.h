@@ -261,6 +261,17 @@ struct FilteredCall {
     // never run on this map may leave the whole map a candidate, and the exact stage over such lists costs
     // twice the all-pairs search the caller can run instead
     double guard_mean = 0.0;
+    // Seeds from per-load anchor buckets (filter.hip 2e; prev_idx == nullptr, the pruning form): `anchors` are
+    // n_anchors rows of the samples as float64 (n_anchors x d), anchor_of[i] the anchor sample i was grouped with
+    // and `order` the samples bucketed by it -- all three functions of the samples alone.  The call finds the
+    // nearest prototype of every anchor, seeds each sample with its anchor's and runs neither the seed pre-pass
+    // nor the bucket sort.
+    const double *anchors = nullptr;
+    const int32_t *anchor_of = nullptr;
+    int n_anchors = 0;
+    // Only the seed pre-pass and the bucket sort (how the anchor buckets are built: W = the anchors): the arg-min
+    // of the pre-pass goes to seeds_out, the bucket order to order_out (N int32 each); idx / dist are not written
+    int32_t *seeds_out = nullptr, *order_out = nullptr;
     // stage timer and side streams of the caller (a context's own); nullptr: this thread's
     FilterAux *aux = nullptr;
 };

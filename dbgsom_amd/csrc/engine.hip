@@ -185,6 +185,10 @@ __global__ void rows_to_f64_kernel(const T *__restrict__ src, int64_t ld, const 
     const T *s = src + ids[r] * ld;
     for (int64_t c = threadIdx.x; c < cols; c += blockDim.x) dst[r * cols + c] = widen(s[c]);
 }
+__global__ void iota_i32_kernel(int32_t *__restrict__ a, int32_t *__restrict__ b, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        a[i] = b[i] = (int32_t)i;
+}
 __global__ void seg_counts_kernel(const uint32_t *__restrict__ seg_start, int64_t M, int64_t N, int64_t *__restrict__ counts) {
     for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += (int64_t)gridDim.x * blockDim.x)
         counts[j] = (int64_t)((j + 1 < M ? seg_start[j + 1] : (uint32_t)N) - seg_start[j]);
@@ -216,6 +220,18 @@ struct Samples {  // one resident sample set (training samples, or a query batch
     int bdtype = -1;
     DevBuf own, x32, xx, planes;
     bool planes_ready = false;
+    // Anchor buckets of the stateless pruning search (filter.hip 2e), built on first use and valid as long as the
+    // planes are: n_anchors rows of X as float64 with their norms behind them, the anchor every row was grouped
+    // with and the rows bucketed by it.  A function of X alone.  anchor_state: 0 none, 1 in use, 2 dropped (their
+    // lists came out longer than the pre-pass's: the pre-pass seeds this sample set again)
+    DevBuf anchors, anchor_of, anchor_order;
+    int64_t n_anchors = 0;
+    int anchor_state = 0;
+    void drop_anchors(int state) {
+        anchors.release(); anchor_of.release(); anchor_order.release();
+        n_anchors = 0; anchor_state = state;
+    }
+    void drop_planes() { planes_ready = false; drop_anchors(0); }
     // CSR residents (dbgsom_ctx_load_csr at or above "csr_densify_below" features): X stays nullptr, the rows are
     // the three arrays below; dtype F32 / F64, dp = pad16(d) as for dense rows (prototypes and sums keep their layout)
     bool csr = false;
@@ -224,7 +240,7 @@ struct Samples {  // one resident sample set (training samples, or a query batch
     CsrView view() const { return CsrView{indptr.as<int64_t>(), indices.as<int32_t>(), data.p}; }
     void release() {
         own.release(); x32.release(); xx.release(); planes.release(); indptr.release(); indices.release(); data.release();
-        planes_ready = false; csr = false; nnz = 0; dtype = -1; N = 0; X = Xb = nullptr;
+        drop_planes(); csr = false; nnz = 0; dtype = -1; N = 0; X = Xb = nullptr;
     }
 };
 
@@ -319,6 +335,15 @@ struct dbgsom_ctx {
     double filter_ms[5] = {0, 0, 0, 0, 0};
     bool filter_ms_valid = false;
     FilterAux faux;   // this context's stage timer and side streams of the filtered search (FilteredCall::aux)
+    // anchor buckets seed the stateless pruning search of the resident samples ("anchor_seeds", default on)
+    int anchor_seeds = 1;
+    int64_t anchor_builds = 0, anchor_searches = 0;   // buckets built / searches seeded from them so far
+    bool anchors_built_now = false;     // the running epoch built the buckets: its clock is not the arm's
+    bool last_anchor_seeded = false;    // the last filtered search of an epoch took its seeds from the anchors
+    // mean list length of the last pruning epoch the cheap pre-pass seeded, and the map it ran on: what the
+    // anchors' lists are held against (dbgsom_ctx_epoch)
+    double prepass_mean = NAN;
+    int64_t prepass_M = 0;
 };
 
 namespace {
@@ -377,7 +402,7 @@ int finish_samples(dbgsom_ctx *c, Samples &s, bool x32_is_widened) {
     }
     TRY(s.xx.reserve((size_t)s.N * 8));
     TRY(launch_row_sqnorms(s.Xb, s.bdtype, s.N, s.dp, s.dp, s.xx.as<double>(), c->stream));
-    s.planes_ready = false;
+    s.drop_planes();
     return DBGSOM_OK;
 }
 
@@ -413,6 +438,94 @@ int ensure_planes(dbgsom_ctx *c, Samples &s) {
     TRY(s.planes.reserve(nbytes));
     TRY(dbgsom_filter_prepare(s.Xb, s.bdtype, s.N, s.dp, s.dp, s.planes.p, s.planes.cap, c->stream));
     s.planes_ready = true;
+    return DBGSOM_OK;
+}
+
+// The anchor buckets of a dense sample set (filter.hip 2e), once per load: A = min(256, N) anchors, rows
+// floor(k N / A) of X; every sample goes to its nearest anchor by the seed pre-pass run against the anchors as if
+// they were a map of A prototypes (every anchor, every feature: about four of an epoch's pre-passes), and the bucket
+// sort behind it leaves the samples grouped by anchor.  N < 256: every row is its own anchor.
+// The anchors are numbered along a greedy nearest-neighbour chain (from row 0 to the nearest anchor not yet taken,
+// ties to the lower row; on the host, A^2 distances once per load): a 128-sample workgroup that straddles buckets
+// then holds the samples of anchors that lie close together, where the strided rows themselves come in no order.
+void chain_anchors(const std::vector<double> &a, int64_t A, int64_t dp, std::vector<int64_t> &rows) {
+    std::vector<double> d2((size_t)A * A, 0.0);
+    for (int64_t i = 0; i < A; ++i)
+        for (int64_t j = i + 1; j < A; ++j) {
+            const double *x = &a[(size_t)i * dp], *y = &a[(size_t)j * dp];
+            double acc = 0.0;
+            for (int64_t k = 0; k < dp; ++k) { const double t = x[k] - y[k]; acc += t * t; }
+            d2[(size_t)i * A + j] = d2[(size_t)j * A + i] = acc;
+        }
+    std::vector<char> taken((size_t)A, 0);
+    std::vector<int64_t> chain;
+    int64_t cur = 0;
+    for (int64_t n = 0; n < A; ++n) {
+        taken[(size_t)cur] = 1;
+        chain.push_back(rows[(size_t)cur]);
+        int64_t best = -1;
+        for (int64_t j = 0; j < A; ++j)   // (a distance that is not a number is never the nearer one)
+            if (!taken[(size_t)j] && (best < 0 || d2[(size_t)cur * A + j] < d2[(size_t)cur * A + best])) best = j;
+        cur = best;
+    }
+    rows = chain;
+}
+
+// rows `rows` of the samples as float64 (rows.size() x dp), waited for
+int gather_anchor_rows(dbgsom_ctx *c, Samples &s, const std::vector<int64_t> &rows, double *anchors) {
+    const int64_t A = (int64_t)rows.size(), dp = s.dp;
+    TRY(c->stage_dev.reserve((size_t)A * 8));
+    int64_t *ids = c->stage_dev.as<int64_t>();
+    DBGSOM_HIP_CHECK(hipMemcpyAsync(ids, rows.data(), (size_t)A * 8, hipMemcpyHostToDevice, c->stream));
+    DBGSOM_HIP_CHECK(hipStreamSynchronize(c->stream));   // (pageable memory: the caller's vector may go)
+    if (s.dtype == DBGSOM_F32)
+        hipLaunchKernelGGL(rows_to_f64_kernel<float>, dim3((unsigned)A), dim3(256), 0, c->stream, (const float *)s.X, dp, ids, A, dp, anchors);
+    else if (s.dtype == DBGSOM_F64)
+        hipLaunchKernelGGL(rows_to_f64_kernel<double>, dim3((unsigned)A), dim3(256), 0, c->stream, (const double *)s.X, dp, ids, A, dp, anchors);
+    else
+        hipLaunchKernelGGL(rows_to_f64_kernel<bf16_t>, dim3((unsigned)A), dim3(256), 0, c->stream, (const bf16_t *)s.X, dp, ids, A, dp, anchors);
+    TRY(launch_status("rows_to_f64_kernel"));
+    return DBGSOM_OK;
+}
+
+int ensure_anchors(dbgsom_ctx *c, Samples &s) {
+    if (s.anchor_state != 0) return DBGSOM_OK;
+    TRY(ensure_planes(c, s));
+    const int64_t A = s.N < 256 ? s.N : 256, dp = s.dp;
+    TRY(s.anchors.reserve((size_t)A * dp * 8 + (size_t)A * 8));
+    TRY(s.anchor_of.reserve((size_t)s.N * 4));
+    TRY(s.anchor_order.reserve((size_t)s.N * 4));
+    std::vector<int64_t> rows((size_t)A);
+    for (int64_t k = 0; k < A; ++k) rows[(size_t)k] = k * s.N / A;
+    double *anchors = s.anchors.as<double>(), *anorm = anchors + (size_t)A * dp;
+    TRY(gather_anchor_rows(c, s, rows, anchors));
+    if (A < s.N && A > 2) {   // the same rows again, in chain order (every row its own anchor: no buckets to order)
+        std::vector<double> host((size_t)A * dp);
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(host.data(), anchors, (size_t)A * dp * 8, hipMemcpyDeviceToHost, c->stream));
+        DBGSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
+        chain_anchors(host, A, dp, rows);
+        TRY(gather_anchor_rows(c, s, rows, anchors));
+    }
+    if (A == s.N) {
+        hipLaunchKernelGGL(iota_i32_kernel, dim3(grid1d(s.N)), dim3(256), 0, c->stream, s.anchor_of.as<int32_t>(),
+                           s.anchor_order.as<int32_t>(), s.N);
+        TRY(launch_status("iota_i32_kernel"));
+    } else {
+        TRY(launch_row_sqnorms(anchors, DBGSOM_F64, A, dp, dp, anorm, c->stream));
+        TRY(c->filt_ws.reserve_zeroed(dbgsom_bmu_filtered_workspace_bytes(s.N, dp, A), c->stream));
+        FilteredCall call;
+        call.aux = &c->faux;
+        call.X = s.Xb; call.x_dtype = s.bdtype; call.N = s.N; call.d = dp; call.ldx = dp;
+        call.xx = s.xx.as<double>(); call.xplanes = s.planes.p; call.W = anchors; call.M = A; call.ww = anorm;
+        call.seed_stride = DBGSOM_SEED_FULL; call.sweep_planes = 1;
+        call.seeds_out = s.anchor_of.as<int32_t>(); call.order_out = s.anchor_order.as<int32_t>();
+        call.ws = c->filt_ws.p; call.ws_bytes = c->filt_ws.cap; call.stream = c->stream;
+        TRY(launch_bmu_filtered(call));
+    }
+    s.n_anchors = A;
+    s.anchor_state = 1;
+    ++c->anchor_builds;
+    c->anchors_built_now = true;
     return DBGSOM_OK;
 }
 
@@ -466,6 +579,22 @@ int run_filtered(dbgsom_ctx *c, Samples &s, DevBuf &ws, const double *W, int64_t
     call.X = s.Xb; call.x_dtype = s.bdtype; call.N = s.N; call.d = s.dp; call.ldx = s.dp;
     call.xx = s.xx.as<double>(); call.xplanes = s.planes.p; call.W = W; call.M = M; call.ww = c->ww.as<double>();
     call.prev_idx = prev_idx; call.order = order; call.seed_stride = plan.seed_stride; call.sweep_planes = plan.sweep_planes;
+    // A stateless search of the resident samples in the pruning form with the cheap seeds: the seeds come from the
+    // anchor buckets instead of the pre-pass.  Nothing the policy sees changes: it planned a stateless call.
+    // Only once the pre-pass has seeded a pruning epoch (or a counting-only pruning launch) of this sample set on a
+    // map about this size: what it left is what the anchors' lists are held against (the valve, dbgsom_ctx_epoch),
+    // and the policy's own first looks at the arm -- are its cheap seeds poor, does it need the re-seeding passes --
+    // are looks at the pre-pass.
+    c->last_anchor_seeded = false;
+    const bool has_ref = c->prepass_mean == c->prepass_mean && SearchPolicy::near_size(M, c->prepass_M);
+    if (!prev_idx && &s == &c->xs && c->anchor_seeds && s.anchor_state != 2 && has_ref && plan.planes == 0 &&
+        !plan.seed_full && (plan.seed_stride & DBGSOM_PRUNE)) {
+        TRY(ensure_anchors(c, s));   // (may grow `ws` for its own call: call.ws is taken below)
+        ++c->anchor_searches;
+        call.anchors = s.anchors.as<double>(); call.n_anchors = (int)s.n_anchors;
+        call.anchor_of = s.anchor_of.as<int32_t>(); call.order = s.anchor_order.as<int32_t>();
+        c->last_anchor_seeded = true;
+    }
     call.round_f32 = round_f32; call.idx = idx; call.dist = dist; call.ws = ws.p; call.ws_bytes = ws.cap;
     call.stream = c->stream;
     call.refine_rows = plan.refine_rows;
@@ -656,7 +785,7 @@ int place_host_csr(dbgsom_ctx *c, Samples &s, const int64_t *indptr_host, const 
     s.csr = true;
     s.bdtype = x_dtype;
     s.own.release(); s.x32.release(); s.planes.release();
-    s.planes_ready = false;
+    s.drop_planes();
     TRY(s.xx.reserve((size_t)N * 8));
     return launch_csr_row_sqnorms(s.view(), x_dtype, N, s.xx.as<double>(), c->stream);
 }
@@ -1016,6 +1145,9 @@ int dbgsom_ctx_set_option(dbgsom_ctx *c, const char *name, int64_t v) {
     } else if (!strcmp(name, "csr_densify_below")) {
         DBGSOM_REQUIRE(v >= 0, "csr_densify_below must be >= 0 (0 = CSR input always stays CSR)");
         c->csr_densify_below = v;
+    } else if (!strcmp(name, "anchor_seeds")) {
+        DBGSOM_REQUIRE(v == 0 || v == 1, "anchor_seeds must be 0 or 1");
+        c->anchor_seeds = (int)v;
     } else {
         set_error("dbgsom_ctx_set_option: unknown option '%s'", name);
         return DBGSOM_EINVAL;
@@ -1055,6 +1187,10 @@ int dbgsom_ctx_get_option(dbgsom_ctx *c, const char *name, int64_t *v) {
     else if (!strcmp(name, "storage")) *v = c->xs.dtype;
     else if (!strcmp(name, "prototypes")) *v = c->M;
     else if (!strcmp(name, "planes_cached")) *v = c->xs.planes_ready ? 1 : 0;
+    else if (!strcmp(name, "anchor_seeds")) *v = c->anchor_seeds;
+    else if (!strcmp(name, "anchor_builds")) *v = c->anchor_builds;
+    else if (!strcmp(name, "anchor_searches")) *v = c->anchor_searches;
+    else if (!strcmp(name, "anchor_state")) *v = c->xs.dtype < 0 ? 0 : c->xs.anchor_state;
     else if (!strcmp(name, "planes_used")) *v = c->policy.planes_used;
     else if (!strcmp(name, "planes_next")) *v = c->policy.planes_for_call();
     else if (!strcmp(name, "hint_valid")) *v = c->hint_valid ? 1 : 0;
@@ -1071,7 +1207,8 @@ int dbgsom_ctx_get_option(dbgsom_ctx *c, const char *name, int64_t *v) {
     else if (!strcmp(name, "device_bytes")) {
         size_t tot = 0;
         for (const Samples *q : {&c->xs, &c->xq})
-            tot += q->own.cap + q->x32.cap + q->xx.cap + q->planes.cap + q->indptr.cap + q->indices.cap + q->data.cap;
+            tot += q->own.cap + q->x32.cap + q->xx.cap + q->planes.cap + q->indptr.cap + q->indices.cap + q->data.cap +
+                   q->anchors.cap + q->anchor_of.cap + q->anchor_order.cap;
         DevBuf *bufs[] = CTX_DEVBUFS(c);
         for (DevBuf *b : bufs) tot += b->cap;
         *v = (int64_t)tot;
@@ -1097,7 +1234,9 @@ static void set_tight(dbgsom_ctx *c, bool tight) {
     DevBuf *bufs[] = CTX_DEVBUFS(c);
     for (DevBuf *b : bufs) b->tight = tight;
     for (Samples *q : {&c->xs, &c->xq})
-        for (DevBuf *b : {&q->own, &q->x32, &q->xx, &q->planes, &q->indptr, &q->indices, &q->data}) b->tight = tight;
+        for (DevBuf *b : {&q->own, &q->x32, &q->xx, &q->planes, &q->indptr, &q->indices, &q->data, &q->anchors, &q->anchor_of,
+                          &q->anchor_order})
+            b->tight = tight;
 }
 
 static void reset_training_state(dbgsom_ctx *c) {
@@ -1105,6 +1244,8 @@ static void reset_training_state(dbgsom_ctx *c) {
     c->has_labels = false;
     c->has_weights = false;
     c->policy.reset();
+    c->prepass_mean = NAN;
+    c->last_anchor_seeded = false;
     c->dist_bound_valid = false;
     c->last_filtered = false;
     c->sumsM = 0;
@@ -1712,6 +1853,7 @@ int dbgsom_ctx_epoch(dbgsom_ctx *c, const double *W_host, int64_t M, int round_f
         if ((rc = stage_weights(c, W_host, M, s.d, s.dp))) break;
         mark(c, 0);
         const auto t_begin = std::chrono::steady_clock::now();
+        c->anchors_built_now = false;
         if ((rc = epoch_bmu(c, M, round_f32))) break;
         mark(c, 1);
         const int measuring = c->policy.take_timing_form();   // (the refinement's policy: this epoch times one of the two forms)
@@ -1730,12 +1872,33 @@ int dbgsom_ctx_epoch(dbgsom_ctx *c, const double *W_host, int64_t M, int round_f
             pol.refine_timed(measuring, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
         if (c->last_filtered) {
             // (a clean measurement of the arm: nothing rode along -- see SearchPolicy::arm_ms)
-            const bool clean = !pol.last_probed && !pol.last_guarded && measuring < 0 && !W_new_host && !idx_host && !dist_host;
+            // (... and the epoch did not build the anchor buckets on the way)
+            const bool clean = !pol.last_probed && !pol.last_guarded && measuring < 0 && !W_new_host && !idx_host && !dist_host &&
+                               !c->anchors_built_now;
             const double epoch_ms =
                 clean ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count() : NAN;
             const double *counted = c->tail.as<double>() + 2 * M + 2;   // (pack_results_kernel: lists, probe, groups to re-seed)
-            pol.observe(counted[0], counted[1], counted[2], (s.N + 127) / 128, M, s.dp, (flags & DBGSOM_EPOCH_FROZEN) != 0,
-                        epoch_ms);
+            // The valve of the anchor seeds: their lists against those of the last pruning epoch the cheap pre-pass
+            // seeded on a map within a quarter of this size (run_filtered waits for one).  More than 1.25 times
+            // that -- a quarter of the exact stage lost at the most -- and the pre-pass seeds this sample set
+            // again.  (An epoch whose long lists the policy is about to re-seed is not what either form costs.)
+            const int64_t nb = (s.N + 127) / 128;
+            const bool settled = !(counted[2] > 0.0 && !pol.last_retry);
+            if (pol.last_probed && !pol.last_hinted && !pol.last_seed_full && settled) {
+                // (a counting-only pruning launch beside a sweep: the lists the pre-pass's seeds would have left)
+                c->prepass_mean = counted[1] / (double)nb;
+                c->prepass_M = M;
+            }
+            if (pol.planes_used == 0 && !pol.last_hinted && !pol.last_seed_full && settled) {
+                const double mean = counted[0] / (double)nb;
+                if (c->last_anchor_seeded) {   // (run_filtered took them because a reference exists)
+                    if (mean > 1.25 * c->prepass_mean) s.drop_anchors(2);
+                } else {
+                    c->prepass_mean = mean;
+                    c->prepass_M = M;
+                }
+            }
+            pol.observe(counted[0], counted[1], counted[2], nb, M, s.dp, (flags & DBGSOM_EPOCH_FROZEN) != 0, epoch_ms);
         } else {
             pol.observe_unfiltered();
         }

@@ -1847,6 +1847,108 @@ __global__ __launch_bounds__(256, 6) void prune_mark_kernel(
     }
 }
 
+// ---- 2e. seeds of a stateless search from anchor buckets -------------------------------------------
+// The seed pre-pass and the bucket sort behind it do one job: samples that lie close together share a 128-sample
+// workgroup, and the workgroup gets a prototype near them.  Only the second half depends on the prototypes.  The
+// engine therefore groups the resident samples ONCE per load around A <= 256 rows of the samples themselves (the
+// anchors; engine.hip ensure_anchors), and a search then needs the nearest prototype of each anchor -- A x M pairs
+// instead of the pre-pass's N x M / stride -- and one gather.  Any seed keeps the search exact: prune_mark_kernel
+// certifies its own bound of |x - w_seed| whatever the seed is.
+//
+// aseed[a] = arg-min_j (|w_j|^2 - 2 a . w_j) in float64 on W itself, one v_mfma_f64_16x16x4_f64 tile (16 prototypes
+// x 16 anchors) per wavefront, operands straight from L2 (32 bytes of a row per lane and step: four k slots of four
+// consecutive features -- both operands permute k alike).  Tile-parallel over (prototypes / 64) x (anchors / 16)
+// workgroups; each leaves the (value, index) minimum of its 64 prototypes per anchor, and the workgroup of an anchor
+// block that finishes last takes the minimum over the blocks: by (value, index), no float atomics, the same bits
+// whatever the order of arrival.  A prototype row with a NaN or an infinity (|w|^2 not finite) compares as +inf, a
+// finite row whose product is not a number as DBL_MAX: a non-finite row is never the seed while a finite one exists.
+typedef double ad4_t __attribute__((ext_vector_type(4)));
+constexpr int ANCHOR_MAX = 256;      // anchors per sample set
+constexpr int ANCHOR_TICKET0 = 16;   // FilterWs::tickets[16 .. 32): one per block of 16 anchors
+
+__device__ __forceinline__ bool seed_less(double v, int j, double bv, int bj) { return v < bv || (v == bv && j < bj); }
+
+__global__ __launch_bounds__(256) void anchor_seed_kernel(const double *__restrict__ anchors, int A,
+                                                          const double *__restrict__ W, int M, int d,
+                                                          const double *__restrict__ ww, double *__restrict__ part_val,
+                                                          int32_t *__restrict__ part_idx, uint32_t *__restrict__ tickets,
+                                                          int32_t *__restrict__ aseed) {
+    __shared__ double val_s[4][16];
+    __shared__ int idx_s[4][16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
+    const int npart = gridDim.x, ab = blockIdx.y * 16, jb = blockIdx.x * 64 + wave * 16;
+    const int jrow = min(jb + r, M - 1), arow = min(ab + r, A - 1);   // (rows past the end: loaded, never compared)
+    const double *wp = W + (size_t)jrow * d + 4 * q, *ap = anchors + (size_t)arow * d + 4 * q;
+    ad4_t c = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 4
+    for (int k = 0; k < d; k += 16) {   // d is a multiple of 16
+        const ad4_t wv = *reinterpret_cast<const ad4_t *>(wp + k), av = *reinterpret_cast<const ad4_t *>(ap + k);
+        c = __builtin_amdgcn_mfma_f64_16x16x4f64(wv[0], av[0], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f64_16x16x4f64(wv[1], av[1], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f64_16x16x4f64(wv[2], av[2], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f64_16x16x4f64(wv[3], av[3], c, 0, 0, 0);
+    }
+    // element u of lane l: prototype jb + 4 u + (l >> 4), anchor ab + (l & 15)
+    double bv = INFINITY;
+    int bj = 0x7fffffff;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int j = jb + 4 * u + q;
+        if (j >= M) continue;
+        const double y = ww[j], v = y - 2.0 * c[u];
+        const double key = fabs(y) < INFINITY ? (fabs(v) < INFINITY ? v : 1.7976931348623157e308) : INFINITY;
+        if (seed_less(key, j, bv, bj)) { bv = key; bj = j; }
+    }
+#pragma unroll
+    for (int off = 16; off < 64; off <<= 1) {
+        const double ov = __shfl_xor(bv, off, 64);
+        const int oj = __shfl_xor(bj, off, 64);
+        if (seed_less(ov, oj, bv, bj)) { bv = ov; bj = oj; }
+    }
+    if (q == 0) { val_s[wave][r] = bv; idx_s[wave][r] = bj; }
+    __syncthreads();
+    if (tid < 16 && ab + tid < A) {
+        bv = val_s[0][tid]; bj = idx_s[0][tid];
+#pragma unroll
+        for (int w = 1; w < 4; ++w)
+            if (seed_less(val_s[w][tid], idx_s[w][tid], bv, bj)) { bv = val_s[w][tid]; bj = idx_s[w][tid]; }
+        part_val[(size_t)(ab + tid) * npart + blockIdx.x] = bv;
+        part_idx[(size_t)(ab + tid) * npart + blockIdx.x] = bj;
+    }
+    if (!last_workgroup_done(tickets + ANCHOR_TICKET0 + blockIdx.y, (uint32_t)npart)) return;
+    // the anchor block's 16 anchors, 16 threads each over the prototype blocks
+    const int a = ab + (tid >> 4), sub = tid & 15;
+    bv = INFINITY; bj = 0x7fffffff;
+    if (a < A)
+        for (int p = sub; p < npart; p += 16) {
+            const double v = part_val[(size_t)a * npart + p];
+            const int j = part_idx[(size_t)a * npart + p];
+            if (seed_less(v, j, bv, bj)) { bv = v; bj = j; }
+        }
+#pragma unroll
+    for (int off = 1; off < 16; off <<= 1) {
+        const double ov = __shfl_xor(bv, off, 64);
+        const int oj = __shfl_xor(bj, off, 64);
+        if (seed_less(ov, oj, bv, bj)) { bv = ov; bj = oj; }
+    }
+    if (sub == 0 && a < A) aseed[a] = bj;   // (every block holds a prototype below M: bj is one)
+}
+
+// seed[i] = the seed of the anchor sample i was grouped with
+__global__ __launch_bounds__(256) void anchor_gather_kernel(const int32_t *__restrict__ aseed,
+                                                            const int32_t *__restrict__ anchor_of, int64_t N,
+                                                            int64_t *__restrict__ seed) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 256)
+        seed[i] = (int64_t)aseed[anchor_of[i]];
+}
+
+// the seeds of the pre-pass as the anchor of every sample (the anchor buckets being built: seeds_out)
+__global__ __launch_bounds__(256) void narrow_seeds_kernel(const int64_t *__restrict__ seed, int64_t N,
+                                                           int32_t *__restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 256)
+        out[i] = (int32_t)seed[i];
+}
+
 // ---- 3. exact arg-min over the marked prototypes (float64 MFMA on gathered rows) -----------------
 // 128 gathered samples x SJ = 16 JTL listed prototypes per step; 4 wavefronts x 32 samples or 8 x 16
 // (NWV), 3-stage LDS-DMA ring.  Three instantiations (JTL = 1, 2, 3), each for the workgroups whose list
@@ -2301,8 +2403,9 @@ static size_t carve_planes(PlaneBuf *b, char *base, int64_t rows, int64_t d) {
 }
 
 struct FilterWs {
-    uint32_t *tickets;     // [0] tile score/select, [1] slice W/tables: "last workgroup" tickets (offset 0 of
-                           // the workspace whatever its shape; 0 between launches, see last_workgroup_done)
+    uint32_t *tickets;     // [0] tile score/select, [1] slice W/tables, [16 .. 32) anchor seeds: "last workgroup"
+                           // tickets (offset 0 of the workspace whatever its shape; 0 between launches, see
+                           // last_workgroup_done)
     int8_t *wt, *wt_sub;   // k-tile-major digit planes of the prototypes / of the pre-pass subset
     double *wscale, *wl1;  // M each
     double *wn0;           // M: sum of the squared top digits of a row (section 2c)
@@ -2321,6 +2424,9 @@ struct FilterWs {
     int32_t *order;    // N   bucket order of the samples by seed
     float *gap;        // Mg x Mg lower bounds of the squared distances between prototypes (2c); M <= PRUNE_MAX_M
     int32_t *retry;    // nb: workgroups of the pruning form to be re-seeded
+    int32_t *aseed;    // ANCHOR_MAX: the nearest prototype of every anchor (2e)
+    double *apart_val; // ANCHOR_MAX x ceil(M / 64): its minimum per block of 64 prototypes, value ...
+    int32_t *apart_idx;  // ... and index
     uint32_t *nnub;    // Mg float32 bit patterns: upper bounds of the prototypes' nearest-neighbour distances (k = 2)
     unsigned long long *cand;  // N: per-sample candidates (four prototype ids) after the refinement (2d)
     int64_t *rbest;    // N: the refinement's best prototype per sample (bucket key of the pair kernel)
@@ -2369,6 +2475,8 @@ static size_t carve_filter(FilterWs *out, char *base, int64_t N, int64_t d, int6
     take(f.gap, M <= PRUNE_MAX_M ? (size_t)Mg * Mg * 4 : 0);
     if (M > PRUNE_MAX_M) f.gap = nullptr;
     take(f.retry, (size_t)nb * 4); take(f.nnub, (size_t)Mg * 4);
+    take(f.aseed, (size_t)ANCHOR_MAX * 4);
+    take(f.apart_val, (size_t)ANCHOR_MAX * (Mg / 64) * 8); take(f.apart_idx, (size_t)ANCHOR_MAX * (Mg / 64) * 4);
     f.Mg = Mg; f.nb = nb; f.Mpad = Mpad;
     return off;
 }
@@ -2533,7 +2641,8 @@ struct FilterRun {
 
     // 1. the prototypes' digit planes and tables (and which k-tiles the seed pre-pass looks at)
     void prepare_prototypes() const {
-        const bool select = fm.nkt_used < fm.nkt_full;
+        // (seeds from the anchors: no pre-pass, so nothing selects k-tiles for it)
+        const bool select = fm.nkt_used < fm.nkt_full && !c.anchor_of;
         if (select) {
             hipLaunchKernelGGL(tile_partial_kernel, dim3((unsigned)fm.nkt_full, TS_RB), dim3(256), 0, s, c.W, (int)c.M, d,
                                dpad, f.tile_part);
@@ -2555,6 +2664,7 @@ struct FilterRun {
             aux.timer.mark(2, s);
             return DBGSOM_OK;
         }
+        if (c.anchor_of) return seed_from_anchors();
         // the gaps of the pruning form are worked out on the second stream BESIDE the seed pre-pass and the bucket
         // sort (one wavefront per 64 x 64 tile: a few hundred small workgroups next to a launch that fills the
         // chip or, on a rank's share of the samples, does not)
@@ -2575,7 +2685,33 @@ struct FilterRun {
         aux.timer.mark(2, s);
         seeds = f.seed;
         order = f.order;
+        if (c.seeds_out) {   // (the anchor buckets being built: the order goes where the caller keeps it)
+            hipLaunchKernelGGL(narrow_seeds_kernel, dim3(seed_grid()), dim3(256), 0, s, f.seed, c.N, c.seeds_out);
+            return launch_bucket_sort(f.seed, c.N, c.M, c.order_out, f.sort_ws, s);
+        }
         return launch_bucket_sort(f.seed, c.N, c.M, f.order, f.sort_ws, s);
+    }
+
+    unsigned seed_grid() const { const int64_t g = (c.N + 255) / 256; return (unsigned)(g < 2048 ? g : 2048); }
+
+    // 2'. seeds from the anchor buckets (2e): the gaps on the second stream beside the two kernels, the samples in
+    // the caller's bucket order -- no pre-pass, no sort
+    int seed_from_anchors() {
+        SideStream &side = aux.side;
+        if (fm.gap_nb && side.ready()) {
+            DBGSOM_HIP_CHECK(hipEventRecord(side.gap_fork, s));
+            DBGSOM_HIP_CHECK(hipStreamWaitEvent(side.stream, side.gap_fork, 0));
+            const int rc = gaps(side.stream);
+            if (rc != DBGSOM_OK) return rc;
+            DBGSOM_HIP_CHECK(hipEventRecord(side.gap_done, side.stream));
+            gap_aside = true;
+        }
+        hipLaunchKernelGGL(anchor_seed_kernel, dim3((unsigned)(f.Mg / 64), (unsigned)((c.n_anchors + 15) / 16)), dim3(256),
+                           0, s, c.anchors, c.n_anchors, c.W, (int)c.M, d, c.ww, f.apart_val, f.apart_idx, f.tickets, f.aseed);
+        hipLaunchKernelGGL(anchor_gather_kernel, dim3(seed_grid()), dim3(256), 0, s, f.aseed, c.anchor_of, c.N, f.seed);
+        aux.timer.mark(2, s);
+        seeds = f.seed;
+        return DBGSOM_OK;
     }
 
     // 3. the candidate lists of the 128-sample workgroups
@@ -2748,8 +2884,15 @@ int dbgsom::launch_bmu_filtered(const FilteredCall &call) {
     DBGSOM_REQUIRE(call.N >= 1 && call.N < 0x7fffffff && call.d >= 1 && call.d % KT == 0 && call.ldx >= call.d,
                    "bad sample shape (d must be a multiple of 16)");
     DBGSOM_REQUIRE(call.M >= 1 && call.M <= SW_MAX_M, "M outside [1, 16000]");
-    DBGSOM_REQUIRE(call.X && call.xx && call.xplanes && call.W && call.ww && call.idx && call.dist && call.ws, "null pointer");
-    DBGSOM_REQUIRE((call.prev_idx == nullptr) == (call.order == nullptr),
+    const bool seeds_only = call.seeds_out != nullptr;
+    DBGSOM_REQUIRE(call.X && call.xx && call.xplanes && call.W && call.ww && call.ws, "null pointer");
+    DBGSOM_REQUIRE(seeds_only || (call.idx && call.dist), "null pointer");
+    DBGSOM_REQUIRE(!seeds_only || (call.order_out && !call.prev_idx && !call.anchor_of && call.k == 1),
+                   "seeds_out comes with order_out, on a stateless k = 1 call");
+    DBGSOM_REQUIRE(!call.anchor_of || (call.anchors && call.order && !call.prev_idx && call.n_anchors >= 1 &&
+                                       call.n_anchors <= ANCHOR_MAX && form.prune && !form.seed_full && call.k == 1),
+                   "anchor seeds: the stateless k = 1 pruning form, with the anchors and the bucket order");
+    DBGSOM_REQUIRE(call.anchor_of || (call.prev_idx == nullptr) == (call.order == nullptr),
                    "prev_idx and order come as a pair (both NULL = stateless two-pass search)");
     DBGSOM_REQUIRE(is_aligned(call.X, 16) && (call.ldx * (int64_t)dtype_size(call.x_dtype)) % 16 == 0 &&
                        is_aligned(call.W, 16) && is_aligned(call.ws, 256) && is_aligned(call.xplanes, 256), "alignment");
@@ -2767,6 +2910,7 @@ int dbgsom::launch_bmu_filtered(const FilteredCall &call) {
     timer.mark(1, r.s);
     int rc = r.seed_and_sort();
     if (rc != DBGSOM_OK) return rc;
+    if (seeds_only) return launch_status("seed pre-pass and bucket sort");
     timer.mark(3, r.s);
     rc = r.mark_candidates();
     if (rc != DBGSOM_OK) return rc;

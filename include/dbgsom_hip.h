@@ -332,10 +332,13 @@ int dbgsom_ctx_destroy(dbgsom_ctx *ctx);
  * build -- an epoch is 22-23 back-to-back launches on the context's stream and two forked ones), "refine" (0 off,
  * 1 on, 2 by measurement: the per-sample refinement in front of the exact stage), "defer" (with the refinement: the
  * distance of a sample it decided is evaluated inside the epoch's sums kernel; off by default), "shard_smooth",
- * "csr_densify_below" (see dbgsom_ctx_load_csr).
+ * "csr_densify_below" (see dbgsom_ctx_load_csr), "anchor_seeds" (1, the default: a stateless search of the resident
+ * samples in the pruning form takes its seeds from anchor buckets built once per load instead of a seed pre-pass per
+ * call; 0: the pre-pass.  Results do not depend on it).
  * Readable besides those: "resident_csr", "resident_nnz", "refined", "defer_epochs" (epochs whose sums kernel evaluated distances), "shard_epochs", "n_samples", "features", "padded_features", "prototypes",
  * "planes_cached", "planes_used" / "planes_next" (0 = no sweep), "seed_mode", "prune_retry", "hint_valid",
- * "filter_backoff", "plane_hold", "device_bytes", and the
+ * "filter_backoff", "plane_hold", "device_bytes", "anchor_builds" (anchor buckets built so far), "anchor_searches" (searches seeded from them), "anchor_state" (of
+ * the resident samples: 0 none, 1 in use, 2 dropped -- their lists came out longer than the pre-pass's), and the
  * PCIe traffic of the prototypes since the context was created: "w_upload_calls" / "w_upload_bytes"
  * (whole matrices host -> HBM), "w_download_calls" / "w_download_bytes", "w_row_writes", "w_row_reads". */
 int dbgsom_ctx_set_option(dbgsom_ctx *ctx, const char *name, int64_t value);
