@@ -60,6 +60,9 @@ SIGNATURES = {
     "dbgsom_bmu_filtered_counts_async": (_ci, [_vp, _i64, _i64, _i64, _vp, _i64, _vp]),
     "dbgsom_bmu_filtered_refine_counts": (_ci, [_vp, _i64, _i64, _i64, _vp, _vp]),
     "dbgsom_bmu_filtered_gaps": (_ci, [_vp, _i64, _i64, _i64, _vp, _vp]),
+    "dbgsom_bmu_filtered_anchored": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _ci, _vp, _vp,
+                                           _ci, _ci, _ci, _vp, _vp, _vp, _sz, _vp]),
+    "dbgsom_bmu_filtered_anchor_seeds": (_ci, [_vp, _i64, _i64, _i64, _ci, _vp, _vp, _vp]),
     "dbgsom_filter_timing": (_ci, [_ci]),
     "dbgsom_bmu_filtered_stage_ms": (_ci, [_vp]),
     "dbgsom_sum_workspace_bytes": (_sz, []),
@@ -146,6 +149,7 @@ SIGNATURES = {
     "dbgsom_ctx_epoch_info": (_ci, [_vp, _vp]),
     "dbgsom_ctx_arm_ms": (_ci, [_vp, _vp]),
     "dbgsom_ctx_filter_counts": (_ci, [_vp, _vp, _i64]),
+    "dbgsom_ctx_read_anchors": (_ci, [_vp, ctypes.POINTER(_i64), _vp, _vp, _vp, _vp]),
     "dbgsom_ctx_refine_counts": (_ci, [_vp, _vp]),
     "dbgsom_ctx_phase_ms": (_ci, [_vp, _vp]),
 }

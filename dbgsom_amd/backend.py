@@ -931,6 +931,20 @@ class HipBackend(HotPathBackend):
         self._call("dbgsom_ctx_filter_counts", self._ctx, out.ctypes.data, nb)
         return out
 
+    def read_anchors(self, aseed=False):
+        """The anchor buckets of the resident samples (`anchor_state` 1): dict of `anchors` (A x padded features,
+        chain order), `anchor_of` and `order` (one int32 per row) and, with `aseed`, the prototype the last search
+        chose for every anchor (that search must have been seeded from the anchors)."""
+        n = ctypes.c_int64(0)
+        self._call("dbgsom_ctx_read_anchors", self._ctx, ctypes.byref(n), None, None, None, None)
+        out = {"anchors": np.empty((n.value, self.padded_features)), "anchor_of": np.empty(self._N, dtype=np.int32),
+               "order": np.empty(self._N, dtype=np.int32)}
+        if aseed:
+            out["aseed"] = np.empty(n.value, dtype=np.int32)
+        self._call("dbgsom_ctx_read_anchors", self._ctx, None, out["anchors"].ctypes.data, out["anchor_of"].ctypes.data,
+                   out["order"].ctypes.data, out["aseed"].ctypes.data if aseed else None)
+        return out
+
     def refine_counts(self):
         """[(sample, prototype) pairs evaluated exactly, 128-sample workgroups refined, samples whose
         candidates overflowed the four slots] of the last filtered search."""

@@ -16,6 +16,7 @@
 #include <new>
 #include <vector>
 
+#include "anchor_chain.h"
 #include "common.h"
 #include "search_policy.h"
 
@@ -445,32 +446,7 @@ int ensure_planes(dbgsom_ctx *c, Samples &s) {
 // floor(k N / A) of X; every sample goes to its nearest anchor by the seed pre-pass run against the anchors as if
 // they were a map of A prototypes (every anchor, every feature: about four of an epoch's pre-passes), and the bucket
 // sort behind it leaves the samples grouped by anchor.  N < 256: every row is its own anchor.
-// The anchors are numbered along a greedy nearest-neighbour chain (from row 0 to the nearest anchor not yet taken,
-// ties to the lower row; on the host, A^2 distances once per load): a 128-sample workgroup that straddles buckets
-// then holds the samples of anchors that lie close together, where the strided rows themselves come in no order.
-void chain_anchors(const std::vector<double> &a, int64_t A, int64_t dp, std::vector<int64_t> &rows) {
-    std::vector<double> d2((size_t)A * A, 0.0);
-    for (int64_t i = 0; i < A; ++i)
-        for (int64_t j = i + 1; j < A; ++j) {
-            const double *x = &a[(size_t)i * dp], *y = &a[(size_t)j * dp];
-            double acc = 0.0;
-            for (int64_t k = 0; k < dp; ++k) { const double t = x[k] - y[k]; acc += t * t; }
-            d2[(size_t)i * A + j] = d2[(size_t)j * A + i] = acc;
-        }
-    std::vector<char> taken((size_t)A, 0);
-    std::vector<int64_t> chain;
-    int64_t cur = 0;
-    for (int64_t n = 0; n < A; ++n) {
-        taken[(size_t)cur] = 1;
-        chain.push_back(rows[(size_t)cur]);
-        int64_t best = -1;
-        for (int64_t j = 0; j < A; ++j)   // (a distance that is not a number is never the nearer one)
-            if (!taken[(size_t)j] && (best < 0 || d2[(size_t)cur * A + j] < d2[(size_t)cur * A + best])) best = j;
-        cur = best;
-    }
-    rows = chain;
-}
-
+// The anchors are numbered along a greedy nearest-neighbour chain (anchor_chain.h: anchor_rows, chain_anchors).
 // rows `rows` of the samples as float64 (rows.size() x dp), waited for
 int gather_anchor_rows(dbgsom_ctx *c, Samples &s, const std::vector<int64_t> &rows, double *anchors) {
     const int64_t A = (int64_t)rows.size(), dp = s.dp;
@@ -495,8 +471,7 @@ int ensure_anchors(dbgsom_ctx *c, Samples &s) {
     TRY(s.anchors.reserve((size_t)A * dp * 8 + (size_t)A * 8));
     TRY(s.anchor_of.reserve((size_t)s.N * 4));
     TRY(s.anchor_order.reserve((size_t)s.N * 4));
-    std::vector<int64_t> rows((size_t)A);
-    for (int64_t k = 0; k < A; ++k) rows[(size_t)k] = k * s.N / A;
+    std::vector<int64_t> rows = anchor_rows(s.N, A);
     double *anchors = s.anchors.as<double>(), *anorm = anchors + (size_t)A * dp;
     TRY(gather_anchor_rows(c, s, rows, anchors));
     if (A < s.N && A > 2) {   // the same rows again, in chain order (every row its own anchor: no buckets to order)
@@ -2289,6 +2264,30 @@ int dbgsom_ctx_refine_counts(dbgsom_ctx *c, uint64_t *out4) {
     if (!c->last_filter_ws) { set_error("dbgsom_ctx_refine_counts: no filtered search has run"); return DBGSOM_ESTATE; }
     return dbgsom_bmu_filtered_refine_counts(c->last_filter_ws, c->last_filter_N, c->last_filter_d, c->last_filter_M, out4,
                                              c->stream);
+}
+
+int dbgsom_ctx_read_anchors(dbgsom_ctx *c, int64_t *n_anchors, double *anchors_host, int32_t *anchor_of_host,
+                            int32_t *order_host, int32_t *aseed_host) {
+    CTX_CHECK(c);
+    TRY(loaded(c, __func__));
+    Samples &s = c->xs;
+    if (s.anchor_state != 1) { set_error("dbgsom_ctx_read_anchors: the resident samples have no anchor buckets"); return DBGSOM_ESTATE; }
+    if (aseed_host && !(c->last_anchor_seeded && c->last_filter_ws)) {
+        set_error("dbgsom_ctx_read_anchors: the last search was not seeded from the anchors");
+        return DBGSOM_ESTATE;
+    }
+    const int64_t A = s.n_anchors;
+    if (n_anchors) *n_anchors = A;
+    if (anchors_host)
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(anchors_host, s.anchors.p, (size_t)A * s.dp * 8, hipMemcpyDeviceToHost, c->stream));
+    if (anchor_of_host)
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(anchor_of_host, s.anchor_of.p, (size_t)s.N * 4, hipMemcpyDeviceToHost, c->stream));
+    if (order_host)
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(order_host, s.anchor_order.p, (size_t)s.N * 4, hipMemcpyDeviceToHost, c->stream));
+    if (aseed_host)
+        return dbgsom_bmu_filtered_anchor_seeds(c->last_filter_ws, c->last_filter_N, c->last_filter_d, c->last_filter_M, (int)A,
+                                                aseed_host, nullptr, c->stream);
+    return sync(c);
 }
 
 int dbgsom_ctx_phase_ms(dbgsom_ctx *c, double *ms8) {

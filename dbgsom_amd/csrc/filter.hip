@@ -2556,6 +2556,26 @@ int dbgsom_bmu_filtered(const void *X_dev, int x_dtype, int64_t N, int64_t d, in
     return launch_bmu_filtered(a);
 }
 
+/* the stateless call seeded from the caller's anchor buckets (2e) instead of the seed pre-pass */
+int dbgsom_bmu_filtered_anchored(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx,
+                                 const double *xx_dev, const void *xplanes_dev, const double *W_dev,
+                                 int64_t M, const double *ww_dev, const double *anchors_dev, int n_anchors,
+                                 const int32_t *anchor_of_dev, const int32_t *order_dev, int seed_stride,
+                                 int sweep_planes, int round_f32, int64_t *idx_dev, double *dist_dev,
+                                 void *workspace_dev, size_t workspace_bytes, void *stream) {
+    DBGSOM_REQUIRE(anchor_of_dev, "anchor seeds: null anchor_of");
+    DBGSOM_REQUIRE(is_aligned(anchors_dev, 16), "alignment");
+    FilteredCall a;
+    a.X = X_dev; a.x_dtype = x_dtype; a.N = N; a.d = d; a.ldx = ldx; a.xx = xx_dev; a.xplanes = xplanes_dev;
+    a.W = W_dev; a.M = M; a.ww = ww_dev; a.order = order_dev;
+    a.anchors = anchors_dev; a.n_anchors = n_anchors; a.anchor_of = anchor_of_dev;
+    a.seed_stride = seed_stride & ~DBGSOM_REFINE; a.sweep_planes = sweep_planes; a.round_f32 = round_f32;
+    a.idx = idx_dev; a.dist = dist_dev; a.ws = workspace_dev; a.ws_bytes = workspace_bytes;
+    a.stream = (hipStream_t)stream;
+    a.refine_rows = (seed_stride & DBGSOM_REFINE) ? 192 : 0;
+    return launch_bmu_filtered(a);
+}
+
 }  // extern "C"
 
 int dbgsom::filter_stage_ms(FilterAux &aux, double *ms5) {
@@ -2979,5 +2999,22 @@ int dbgsom_bmu_filtered_gaps(const void *workspace_dev, int64_t N, int64_t d, in
     return DBGSOM_OK;
 }
 
-}  // extern "C"
+/* diagnostics: what the last dbgsom_bmu_filtered_anchored call on this workspace (same N, d, M) left of its seeds:
+ * aseed_host[a] the prototype anchor_seed_kernel chose for anchor a (n_anchors int32), seed_host[i] the seed sample i
+ * went into prune_mark_kernel with (N int64, may be NULL; with DBGSOM_PRUNE_RETRY the re-seeding pass has overwritten
+ * some).  Synchronises the stream. */
+int dbgsom_bmu_filtered_anchor_seeds(const void *workspace_dev, int64_t N, int64_t d, int64_t M, int n_anchors,
+                                     int32_t *aseed_host, int64_t *seed_host, void *stream) {
+    DBGSOM_REQUIRE(workspace_dev && aseed_host, "null pointer");
+    DBGSOM_REQUIRE(N >= 1 && d >= 1 && M >= 1 && M <= PRUNE_MAX_M, "no anchor seeds: M outside [1, 8192]");
+    DBGSOM_REQUIRE(n_anchors >= 1 && n_anchors <= ANCHOR_MAX, "n_anchors outside [1, 256]");
+    FilterWs f;
+    carve_filter(&f, (char *)const_cast<void *>(workspace_dev), N, d, M);
+    DBGSOM_HIP_CHECK(hipMemcpyAsync(aseed_host, f.aseed, (size_t)n_anchors * 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    if (seed_host)
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(seed_host, f.seed, (size_t)N * 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    DBGSOM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    return DBGSOM_OK;
+}
 
+}  // extern "C"

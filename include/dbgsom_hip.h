@@ -234,6 +234,25 @@ int dbgsom_bmu_filtered_counts_async(const void *workspace_dev, int64_t N, int64
  * the stream. */
 int dbgsom_bmu_filtered_gaps(const void *workspace_dev, int64_t N, int64_t d, int64_t M, float *gap_host,
                              void *stream);
+/* The stateless call seeded from anchor buckets the caller built (what the context does once per load, see
+ * "anchor_seeds"): no seed pre-pass and no sort.  anchors_dev: n_anchors x d float64, contiguous, 16-byte aligned
+ * (rows of the samples, or any points near them), 1 <= n_anchors <= 256; anchor_of_dev[i] in [0, n_anchors): the
+ * anchor sample i is grouped with; order_dev: the N sample ids bucketed by anchor_of.  Each anchor's nearest prototype
+ * (float64, the lowest index among equals; a row with a NaN, an infinity or an overflowing norm only when no finite
+ * row exists) seeds the samples grouped with it.  Only the pruning form: seed_stride carries DBGSOM_PRUNE and not
+ * DBGSOM_SEED_FULL, otherwise DBGSOM_EINVAL.  Winners and distances are dbgsom_bmu_filtered's, whatever the buckets. */
+int dbgsom_bmu_filtered_anchored(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx,
+                                 const double *xx_dev, const void *xplanes_dev, const double *W_dev,
+                                 int64_t M, const double *ww_dev, const double *anchors_dev, int n_anchors,
+                                 const int32_t *anchor_of_dev, const int32_t *order_dev, int seed_stride,
+                                 int sweep_planes, int round_f32, int64_t *idx_dev, double *dist_dev,
+                                 void *workspace_dev, size_t workspace_bytes, void *stream);
+/* diagnostics: the seeds of the last dbgsom_bmu_filtered_anchored call on this workspace with the same N, d, M:
+ * aseed_host[a] the prototype chosen for anchor a (n_anchors int32), seed_host[i] the seed of sample i (N int64; may
+ * be NULL; with DBGSOM_PRUNE_RETRY the re-seeding pass has overwritten some).  M > 8192 is DBGSOM_EINVAL.
+ * Synchronises the stream. */
+int dbgsom_bmu_filtered_anchor_seeds(const void *workspace_dev, int64_t N, int64_t d, int64_t M, int n_anchors,
+                                     int32_t *aseed_host, int64_t *seed_host, void *stream);
 
 /* diagnostics of the per-sample refinement (DBGSOM_REFINE) of the last filtered call:
  * out4 = [(sample, prototype) pairs evaluated exactly, 128-sample workgroups refined (the others went
@@ -638,6 +657,12 @@ int dbgsom_ctx_epoch_info(dbgsom_ctx *ctx, double *info8);
 int dbgsom_ctx_arm_ms(dbgsom_ctx *ctx, double *ms12);
 /* candidate-list length per 128-sample workgroup of the last filtered search (n = ceil(N/128)) */
 int dbgsom_ctx_filter_counts(dbgsom_ctx *ctx, uint32_t *counts_host, int64_t n);
+/* diagnostics: the anchor buckets of the resident samples ("anchor_state" 1, else DBGSOM_ESTATE); every array may be
+ * NULL.  n_anchors: A = min(256, rows); anchors_host: A x padded features float64 (the anchor rows in chain order);
+ * anchor_of_host, order_host: one int32 per resident row; aseed_host: A int32, the prototype the last search chose
+ * for every anchor -- DBGSOM_ESTATE unless that search was seeded from the anchors. */
+int dbgsom_ctx_read_anchors(dbgsom_ctx *ctx, int64_t *n_anchors, double *anchors_host, int32_t *anchor_of_host,
+                            int32_t *order_host, int32_t *aseed_host);
 /* dbgsom_bmu_filtered_refine_counts of the context's last filtered search */
 int dbgsom_ctx_refine_counts(dbgsom_ctx *ctx, uint64_t *out4);
 /* ms8 = [bmu, accumulate, smooth, slice W + tables, seed pre-pass, bucket sort, candidate sweep,

@@ -237,3 +237,26 @@ def test_lists_stay_at_one_cluster():
         be.release()
     print("mean list length: pre-pass %.2f, anchors %.2f" % (mean[0], mean[1]))
     assert mean[1] <= 64.0 and mean[1] <= 1.25 * mean[0]
+
+
+def test_lists_stay_at_one_cluster_when_tiles_span_the_clusters():
+    """The same eight clusters with prototype j in cluster j % 8: every 16-prototype tile of the anchor-seed kernel now
+    holds two prototypes of each cluster, so a seed that is the wrong prototype of the right tile lies in another
+    cluster and its workgroup's list takes that cluster in.  Renumbering the prototypes changes neither the buckets
+    nor the geometry: the lists are as long as on the map laid out cluster by cluster."""
+    X, W0 = _eight_blobs()
+    gamma, M = _gamma(X), 256
+    hop = gi.lattice_hops(*MAPS[M])
+    j = np.arange(M)
+    Wp = np.ascontiguousarray(W0[(j % 8) * 32 + j // 8])
+    assert np.array_equal(np.sort(Wp, axis=0), np.sort(W0, axis=0)) and np.array_equal(Wp[8], W0[1])
+    mean = {}
+    for name, W in (("by cluster", W0), ("interleaved", Wp)):
+        be = _backend(X, "filtered", 1)
+        for _ in range(4):
+            be.epoch(W, hop, SIGMA, gamma, "compact", False)
+        mean[name] = float(be.filter_counts().mean())
+        assert be.anchor_state == 1 and be.anchor_searches >= 1
+        be.release()
+    print("mean list length with the anchors: by cluster %.2f, interleaved %.2f" % (mean["by cluster"], mean["interleaved"]))
+    assert mean["interleaved"] <= 64.0 and mean["interleaved"] <= 1.25 * mean["by cluster"]
