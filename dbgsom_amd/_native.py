@@ -127,6 +127,12 @@ SIGNATURES = {
     "dbgsom_bmu_masked": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _i64, _i64, _ci, _vp, _vp, _vp, _sz, _vp]),
     "dbgsom_fill_missing": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp]),
     "dbgsom_ctx_bmu_query_masked": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _ci, _vp, _vp, _vp]),
+    "dbgsom_accumulate_masked_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "dbgsom_accumulate_masked": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "dbgsom_smooth_masked_workspace_bytes": (_sz, [_i64, _i64]),
+    "dbgsom_smooth_masked": (_ci, [_vp, _i64, _i64, _vp, _dbl, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dbgsom_ctx_bmu_masked": (_ci, [_vp, _vp, _i64, _ci, _vp, _vp]),
+    "dbgsom_ctx_epoch_masked": (_ci, [_vp, _vp, _i64, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dbgsom_topofn_workspace_bytes": (_sz, [_i64, _ci]),
     "dbgsom_topofn": (_ci, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dbgsom_topofn_timing": (_ci, [_ci]),

@@ -133,6 +133,13 @@ class HotPathBackend:
         sums = self._all_reduce(sums)
         return self._smooth(sums, W, hop, sigma, layout)
 
+    def epoch_masked(self, W, hop, sigma, gamma, want_assignments=False, n_classes=0):
+        """``epoch`` on resident rows with missing entries (``load(X, incomplete=True)``): the search of
+        ``bmu_masked`` for every row, sums per (neuron, feature) over the rows that observe the feature, and a
+        smoothing with a denominator per (neuron, feature) -- always the aligned form; an entry nobody in reach
+        observed keeps its value.  -> EpochResult.  The prototypes are handed over with every call."""
+        raise NotImplementedError
+
     # -- post-fit consumers of the BMU step (SURVEY.md 8(f-2), 8(f-3)); host defaults ----------
     def _reduce_host(self, arr):
         """Sum a small host array over the ranks (identity for one process)."""
@@ -556,12 +563,18 @@ class HipBackend(HotPathBackend):
         _native.call("dbgsom_ctx_set_collectives", self._ctx, self._cb, None, rank, world)
 
     # -- a8: residency --------------------------------------------------------------------------
-    def load(self, X, storage=None):
+    def load(self, X, storage=None, incomplete=False):
         """Upload the samples once.  `storage="bf16"` keeps them in HBM as bfloat16 (rounded to
         nearest even on the device; all arithmetic stays float64 on the exactly widened values --
         an extension, the reference has no bf16).  A scipy sparse matrix is made canonical CSR and loaded as such
         (``dbgsom_ctx_load_csr``): below ``csr_densify_below`` features it is expanded on the device into the
-        dense resident form, at and above it the CSR kernels run -- the same results either way."""
+        dense resident form, at and above it the CSR kernels run -- the same results either way.
+        ``incomplete=True``: NaN in X (dense float32 / float64, native storage) marks a missing entry.  The rows'
+        observed-entry counts and, for float32 rows, a float64 copy (N x d x 8 bytes of HBM) are made once;
+        ``bmu(W, k)`` is then the masked search, ``epoch_masked`` the epoch, and the ordinary epoch / update /
+        partition calls raise."""
+        if incomplete and (is_sparse(X) or storage not in (None, "native")):
+            raise ValueError("incomplete=True takes dense rows in their own dtype")
         if is_sparse(X):
             if storage not in (None, "native"):
                 raise ValueError("sparse input cannot be stored as bf16")
@@ -589,6 +602,9 @@ class HipBackend(HotPathBackend):
         self._call("dbgsom_ctx_load", self._ctx, X.ctypes.data, code, X.shape[0], X.shape[1], st)
         self._after_load(X.shape, "bf16" if st == _native.BF16 else X.dtype)
         self._borrowed = None
+        if incomplete:
+            self._set("incomplete", 1)
+            self._incomplete = True
         return self
 
     def load_device(self, X_dev):
@@ -621,6 +637,7 @@ class HipBackend(HotPathBackend):
         self._y = None
         self._sw = None          # (a load detaches the weights of the rows that were resident)
         self._weighted = False
+        self._incomplete = False
 
     def read_samples(self, rows):
         """Rows of the resident samples as float64 (exactly widened)."""
@@ -680,11 +697,16 @@ class HipBackend(HotPathBackend):
         (N, k) otherwise."""
         if X is None:
             self._require_loaded()
-            keep, p, M, rf = self._w_arg(W)
+            if self._incomplete and W is RESIDENT:
+                raise ValueError("no prototypes stay resident between masked epochs")
+            keep, p, M, rf = self._w_arg(W, d=self._d if self._incomplete else None)
             N = self._N
             idx = np.empty((N, k), dtype=np.int64)
             dist = np.empty((N, k), dtype=np.float64)
-            self._call("dbgsom_ctx_bmu", self._ctx, p, M, int(k), rf, idx.ctypes.data, dist.ctypes.data)
+            if self._incomplete:   # rows with missing entries: the search over the observed entries of every row
+                self._call("dbgsom_ctx_bmu_masked", self._ctx, p, M, int(k), idx.ctypes.data, dist.ctypes.data)
+            else:
+                self._call("dbgsom_ctx_bmu", self._ctx, p, M, int(k), rf, idx.ctypes.data, dist.ctypes.data)
         elif is_sparse(X):
             csr, indptr, indices, data = canonical_csr(X)
             W = np.asarray(W)
@@ -867,6 +889,27 @@ class HipBackend(HotPathBackend):
         self._log_epoch()
         return res
 
+    def epoch_masked(self, W, hop, sigma, gamma, want_assignments=False, n_classes=0):
+        """One epoch on resident rows with missing entries as ONE call of the C ABI (csrc/masked.hip,
+        csrc/masked_fit.hip, csrc/smooth.hip): dbgsom_ctx_epoch_masked."""
+        self._require_loaded()
+        if W is RESIDENT:
+            raise ValueError("no prototypes stay resident between masked epochs")
+        keep, p, M, _ = self._w_arg(W, d=self._d)
+        self._topology(hop, M)
+        Wn, chg, E, a = np.empty((M, self._d)), np.empty(1), np.empty(M), np.empty(M)
+        want = want_assignments or n_classes > 0
+        win = np.empty(self._N, dtype=np.int64) if want else None
+        dist = np.empty(self._N) if want else None
+        self._call("dbgsom_ctx_epoch_masked", self._ctx, p, M, float(gamma), float(sigma), Wn.ctypes.data,
+                   chg.ctypes.data, E.ctypes.data, a.ctypes.data, None if win is None else win.ctypes.data,
+                   None if dist is None else dist.ctypes.data)
+        self._last_M = M
+        res = EpochResult(Wn, float(chg[0]), E, a, win if want_assignments else None, dist if want_assignments else None)
+        if n_classes > 0:
+            res.class_hist = self.class_histogram(win, n_classes, M)
+        return res
+
     def epoch_info(self):
         """dbgsom_ctx_epoch_info of the last epoch: [filtered (0/1), mean candidate-list length,
         digit planes (0 = no sweep), hinted (0/1), back-off epochs left, policy hold, mean list length
@@ -991,6 +1034,7 @@ class HipBackend(HotPathBackend):
         return s1, s2, self._N
 
     _weighted = False
+    _incomplete = False
 
     def set_sample_weight(self, w):
         """One float64 weight per resident row, kept in HBM next to the samples (None detaches)."""
@@ -1019,8 +1063,11 @@ class HipBackend(HotPathBackend):
         self._call("dbgsom_ctx_weighted_column_sums", self._ctx, mean.ctypes.data, s2.ctypes.data)
         return s1, s2
 
+    # (rows with missing entries: the O(N)-per-fit reductions are HotPathBackend's host defaults over the masked bmu)
     def quantization_error(self, W) -> float:
         self._require_loaded()
+        if self._incomplete:
+            return super().quantization_error(W)
         keep, p, M, rf = self._w_arg(W)
         out = np.empty(2)
         self._call("dbgsom_ctx_quantization_error", self._ctx, p, M, rf, out.ctypes.data)
@@ -1028,6 +1075,8 @@ class HipBackend(HotPathBackend):
 
     def topographic_error_count(self, W, coords) -> int:
         self._require_loaded()
+        if self._incomplete:
+            return super().topographic_error_count(W, coords)
         keep, p, M, rf = self._w_arg(W)
         xy = np.ascontiguousarray(coords, dtype=np.int32)
         if xy.shape != (M, 2):
@@ -1039,6 +1088,8 @@ class HipBackend(HotPathBackend):
     def node_statistics(self, W, sigma):
         """-> (hit_counts (M,), density_sums (M,)) of BaseSom._calculate_node_statistics."""
         self._require_loaded()
+        if self._incomplete:
+            return super().node_statistics(W, sigma)
         keep, p, M, rf = self._w_arg(W)
         hits, dens = np.empty(M), np.empty(M)
         self._call("dbgsom_ctx_node_statistics", self._ctx, p, M, rf, float(sigma), hits.ctypes.data,
@@ -1055,6 +1106,8 @@ class HipBackend(HotPathBackend):
     def class_histogram(self, winners, n_classes, M):
         """(M, n_classes) int64 over all ranks (float64 summed weights with weights attached);
         winners=None: the last epoch's (still in HBM)."""
+        if self._incomplete:
+            return super().class_histogram(winners, n_classes, M)
         idx = None if winners is None else np.ascontiguousarray(winners, dtype=np.int64)
         if self._weighted:
             hist = np.empty((M, n_classes), dtype=np.float64)
@@ -1102,6 +1155,7 @@ class HipBackend(HotPathBackend):
         self._borrowed = None
         self._hop_key = None
         self._weighted = False
+        self._incomplete = False
         self._sw = None
 
     def __del__(self):

@@ -150,10 +150,21 @@ class BaseSom(BaseEstimator):
             four rows of positive weight.  ``None``: every row counts once (the unweighted code path).
             ``predict`` / ``transform`` and the other queries on new data are not weighted.
 
-        X must be complete: NaN is refused whatever ``missing_values`` says (that parameter opens the queries on
-        a fitted map to rows with missing entries -- fit on the complete cases, then place, score and fill in
-        the incomplete ones)."""
-        self._accepts_nan()   # (validates the parameter; fit itself takes complete rows only)
+        Under ``missing_values=None`` and ``"nan"`` X must be complete (``"nan"`` opens only the queries on a
+        fitted map to rows with missing entries).  ``missing_values="nan-fit"``: NaN in dense X marks a missing
+        entry in ``fit`` as well.  Without any NaN the fit is the ordinary one, bit for bit.  With at least one,
+        every row -- complete ones included -- goes through the search over its observed entries
+        (``sqrt(d / n_obs * sum over observed (x - w)^2)``, float64, direct form), the epoch sums run per
+        (neuron, feature) over the rows that observe the feature, and the smoothing divides per (neuron, feature):
+        ``W'_jc = sum_l h_jl A_lc C_lc / sum_l h_jl A_lc`` with A the observation counts and C = S / K the centres;
+        an entry whose denominator is 0 keeps its value.  That is the aligned form of the update, always:
+        ``centres_layout`` is not consulted (the compacted layout has no per-feature meaning).  The variance
+        behind gamma, the "se" threshold and the start rows use ``np.nanvar`` / ``np.nanstd(ddof=1)`` /
+        ``np.nanmean`` for the start rows' holes.  Refused (``ValueError``): an infinity, a row without any
+        observed entry, a column with fewer than two observed values, ``sample_weight``,
+        ``vertical_growth=True``, ``sharded_input`` or more than one rank, sparse X with a stored NaN."""
+        self._accepts_nan()   # (validates the parameter)
+        self._incomplete_fit = False
         if isinstance(X, DeviceSamples):   # a Voronoi subset that already lives in HBM (f-4)
             if y is not None:
                 y = np.asarray(y)
@@ -161,6 +172,7 @@ class BaseSom(BaseEstimator):
                 sample_weight = np.ascontiguousarray(sample_weight, dtype=np.float64)
         else:
             X, y = self._check_input_data(X, y)
+            self._incomplete_fit = self._check_incomplete_fit(X, sample_weight)
             sample_weight = self._check_sample_weight(sample_weight, X)
         if y is not None:
             classes, y = np.unique(y, return_inverse=True)
@@ -184,11 +196,55 @@ class BaseSom(BaseEstimator):
             self.n_iter_ = self._current_epoch
         finally:
             self._resident = None
+            self._incomplete_fit = False
             self._sw = self._sw_global = None
             if hasattr(engine, "set_sample_weight") and getattr(engine, "_sw", None) is not None:
                 engine.set_sample_weight(None)   # (the backend object may serve another fit)
             engine.release()
         return self
+
+    # -- rows with missing entries in fit (missing_values="nan-fit") ---------------------------------
+    _incomplete_fit = False   # this fit runs in incomplete mode: X is dense and holds at least one NaN
+
+    def _fits_nan(self) -> bool:
+        return self._accepts_nan() and self.missing_values == "nan-fit"
+
+    def _check_incomplete_fit(self, X, sample_weight) -> bool:
+        """Whether this fit runs in incomplete mode; its refusals, on the host before anything is uploaded."""
+        if not self._fits_nan() or is_sparse(X):
+            return False
+        holes = np.isnan(X)
+        if not holes.any():
+            return False
+        self._incomplete_rows(X)   # (a row without any observed entry: the queries' message, which names the row)
+        short = np.flatnonzero((~holes).sum(axis=0) < 2)
+        if short.size:
+            raise ValueError(f"column {int(short[0])} of X has fewer than two observed values: its variance is undefined")
+        if sample_weight is not None:
+            raise ValueError("sample_weight is not supported on rows with missing entries (missing_values='nan-fit')")
+        if self.vertical_growth:
+            raise ValueError("vertical_growth=True is not supported on rows with missing entries "
+                             "(missing_values='nan-fit')")
+        if self.sharded_input or dist_info()[1] > 1:
+            raise ValueError("rows with missing entries (missing_values='nan-fit') take one process: no sharded_input, "
+                             "no process group of more than one rank")
+        return True
+
+    def _check_fit_array(self, X, y=None, supervised=False):
+        """check_array / check_X_y of fit's X.  ``missing_values="nan-fit"``: NaN passes in dense X, an infinity
+        never does, and the finite check is not deferred to the device."""
+        kw = dict(ensure_min_samples=4, dtype=[np.float64, np.float32], accept_sparse="csr")
+        if self._fits_nan():
+            self._finite_deferred = False
+            kw.update(self._finite_kw("allow-nan"))
+        else:
+            self._finite_deferred = self._finite_check_on_device()
+            kw.update(self._finite_kw(not self._finite_deferred))
+        if not supervised:
+            return check_array(array=X, **kw), None
+        from sklearn.utils import check_X_y
+
+        return check_X_y(X=X, y=y, **kw)
 
     # -- sample weights -------------------------------------------------------------------------
     _sw = None          # the weights of the rows handed to fit (None: unweighted), aligned with X as passed
@@ -277,7 +333,10 @@ class BaseSom(BaseEstimator):
             self._engine().load(X)
         else:
             self._shard = shard_bounds(X.shape[0], rank, world)
-            self._engine().load(X[self._shard[0]:self._shard[1]])
+            if self._incomplete_fit:
+                self._engine().load(X, incomplete=True)
+            else:
+                self._engine().load(X[self._shard[0]:self._shard[1]])
         self._resident = X
 
     def _local_input(self) -> bool:
@@ -400,6 +459,18 @@ class BaseSom(BaseEstimator):
         engine = self._engine()
         rank, world = dist_info()
         n_total = self._n_total
+        if self._incomplete_fit:
+            # moments and start on the host, one pass each, NumPy's own dtype rules
+            self._col_s2 = None
+            self.growing_threshold_ = self._calculate_growing_threshold(data)
+            self._total_variance = np.nanvar(data, axis=0).sum()
+            rng = np.random.default_rng(seed=self.random_state)
+            start = data[rng.choice(n_total, size=4, replace=False)]
+            fill = np.nanmean(data, axis=0, dtype=np.float64).astype(data.dtype)
+            start = np.where(np.isnan(start), fill[None, :], start)
+            self._lattice = GrowingLattice(start)
+            self._sync_views(refresh_weights=True)
+            return
         # np.var / np.std over the samples (two host passes over X, 1.4 s at 1e6 x 784) from the
         # resident copy when it is the whole data set: same values bit for bit (f-1)
         self._col_s2 = None
@@ -499,7 +570,9 @@ class BaseSom(BaseEstimator):
         if self.threshold_method == "classical":
             return -data.shape[1] * log(self.spreading_factor)
         if self.threshold_method == "se":
-            if getattr(self, "_col_s2", None) is not None:
+            if self._incomplete_fit:
+                spread = np.nanstd(data, axis=0, ddof=1)
+            elif getattr(self, "_col_s2", None) is not None:
                 if self._sw is not None and not self._w_total > 1:
                     raise ValueError("threshold_method='se' needs a summed sample_weight above 1 "
                                      "(frequency weights: the divisor is sum w - 1)")
@@ -543,7 +616,9 @@ class BaseSom(BaseEstimator):
         # growth step writes only the inserted rows (and the new hop matrix); the host copy is
         # refreshed at growth steps and at the end.  Backends without resident prototypes (the
         # oracle's CPU stand-in in the tests) get the matrix handed over every epoch.
-        resident = hasattr(engine, "write_weight_rows")
+        # Rows with missing entries: nothing stays resident between masked epochs, whatever the backend can do.
+        incomplete = self._incomplete_fit
+        resident = hasattr(engine, "write_weight_rows") and not incomplete
         on_device = False     # the current prototypes are in HBM, lat.W is stale
         ran = False
         self._growth_epochs = []
@@ -554,10 +629,14 @@ class BaseSom(BaseEstimator):
             self._sync_views(refresh_weights=not on_device)  # hop matrix recomputed only after growth
             w_in = RESIDENT if on_device else self.weights_
 
-            res = engine.epoch(w_in, self._distance_matrix, self._calculate_current_sigma(),
-                               self._gamma(), self.centres_layout,
-                               n_classes=n_classes if need_assign else 0,
-                               **({"keep_on_device": True} if resident else {}))
+            if incomplete:
+                res = engine.epoch_masked(w_in, self._distance_matrix, self._calculate_current_sigma(),
+                                          self._gamma(), n_classes=n_classes if need_assign else 0)
+            else:
+                res = engine.epoch(w_in, self._distance_matrix, self._calculate_current_sigma(),
+                                   self._gamma(), self.centres_layout,
+                                   n_classes=n_classes if need_assign else 0,
+                                   **({"keep_on_device": True} if resident else {}))
             ran = True
             if resident:
                 on_device = True
@@ -593,6 +672,10 @@ class BaseSom(BaseEstimator):
         if on_device and ran:
             self.weights_ = engine.get_weights(1)   # the snapshot the last epoch consumed (Q3)
             lat.set_weights(engine.get_weights(0))
+        if incomplete and ran:
+            # (the statistics behind the loop are taken on the last update: the reference has no fit on incomplete
+            #  rows whose snapshot of the last epoch's input (Q3) there would be to reproduce)
+            self._sync_views(refresh_weights=True)
         if hasattr(engine, "traffic"):
             self._training_traffic = engine.traffic()   # what crossed PCIe during the epoch loop
         lat.write_attributes()
@@ -658,12 +741,13 @@ class BaseSom(BaseEstimator):
     # queries on rows with missing entries (missing_values="nan")
     # ------------------------------------------------------------------------------------------
     def _accepts_nan(self) -> bool:
-        """Whether the queries take NaN as "missing" (``missing_values="nan"``); None: NaN is refused."""
+        """Whether the queries take NaN as "missing" (``missing_values="nan"``, or ``"nan-fit"``, which opens ``fit``
+        as well); None: NaN is refused."""
         if self.missing_values is None:
             return False
-        if isinstance(self.missing_values, str) and self.missing_values == "nan":
+        if isinstance(self.missing_values, str) and self.missing_values in ("nan", "nan-fit"):
             return True
-        raise ValueError(f"missing_values must be None or 'nan', got {self.missing_values!r}")
+        raise ValueError(f"missing_values must be None, 'nan' or 'nan-fit', got {self.missing_values!r}")
 
     def _check_query(self, X, accept_sparse="csr"):
         """check_array of a query: float32 kept, anything else float64; with ``missing_values="nan"`` NaN passes in
@@ -711,7 +795,7 @@ class BaseSom(BaseEstimator):
         map's prototypes are used (not the child maps of vertical growth)."""
         check_is_fitted(self)
         if not self._accepts_nan():
-            raise ValueError("impute needs missing_values='nan'")
+            raise ValueError("impute needs missing_values='nan' (or 'nan-fit')")
         return self._impute_checked(self._check_query(X, accept_sparse=False), copy=True)
 
     def _impute_checked(self, X, copy=False):

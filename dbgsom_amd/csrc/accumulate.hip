@@ -790,6 +790,21 @@ const uint32_t *bucket_sort_seg_start(const void *ws, int64_t N, int64_t M) {
     return reinterpret_cast<const uint32_t *>((const char *)ws + align_up((size_t)nb * M * 4) + align_up((size_t)M * 4));
 }
 
+// all three tables launch_bucket_sort leaves in its workspace (M, M + 1 and M + 1 entries), and the chunk length
+// chunk_pre is cut by: what a sibling of segsum_kernel in another source needs (masked_fit.hip)
+void bucket_sort_tables(const void *ws, int64_t N, int64_t M, const uint32_t **count, const uint32_t **seg_start,
+                        const uint32_t **chunk_pre) {
+    const int HS = hs_for(N);
+    const int64_t nb = (N + HS - 1) / HS;
+    const char *base = (const char *)ws + align_up((size_t)nb * M * 4);
+    *count = reinterpret_cast<const uint32_t *>(base);
+    base += align_up((size_t)M * 4);
+    *seg_start = reinterpret_cast<const uint32_t *>(base);
+    base += align_up((size_t)(M + 1) * 4);
+    *chunk_pre = reinterpret_cast<const uint32_t *>(base);
+}
+int accumulate_chunk_rows() { return CH; }
+
 static void launch_scatter(const int64_t *idx, int64_t N, int Mi, int64_t nb, const uint32_t *blk,
                            const uint32_t *seg_start, int32_t *order, hipStream_t s) {
     if (hs_for(N) == 512)

@@ -159,6 +159,25 @@ int launch_bmu_masked_rows(const void *X, int x_dtype, int64_t N, int64_t d, int
                            int64_t *idx, double *dist, void *ws, size_t ws_bytes, hipStream_t s);
 int launch_fill_missing(void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *W, int64_t M,
                         int64_t ldw, const int64_t *idx, int64_t idx_stride, hipStream_t s);
+// the halves of launch_bmu_masked_rows for rows that stay resident: n_obs and the float64 copy of float32 rows (N x d)
+// once, then any number of searches of the float64 rows X64 (ld64 apart) against Wt (masked_weights_bytes(d, M))
+int launch_masked_prepare(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int32_t *nobs, double *Xw,
+                          hipStream_t s);
+int launch_bmu_masked_prepared(const double *X64, int64_t N, int64_t d, int64_t ld64, const int32_t *nobs,
+                               const double *Wt, int64_t M, int k, int64_t *idx, double *dist, hipStream_t s);
+size_t masked_weights_bytes(int64_t d, int64_t M);
+// fit on rows with missing entries: sums [S (M x d) | K (M x d) | A (M x d) | a | E] over the observed entries
+// (masked_fit.hip), and the smoothing with a denominator per (neuron, feature) (smooth.hip)
+size_t accumulate_masked_workspace_bytes(int64_t N, int64_t d, int64_t M);
+int launch_accumulate_masked(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const int64_t *idx,
+                             const double *kw, const double *dist, int64_t M, double *sums, int32_t *status, void *ws,
+                             size_t ws_bytes, hipStream_t s);
+size_t smooth_masked_workspace_bytes(int64_t M, int64_t d);
+int launch_smooth_masked(const double *sums, int64_t M, int64_t d, const float *hop, double sigma, const double *W_old,
+                         double *W_new, double *change_total, void *ws, size_t ws_bytes, hipStream_t s);
+void bucket_sort_tables(const void *ws, int64_t N, int64_t M, const uint32_t **count, const uint32_t **seg_start,
+                        const uint32_t **chunk_pre);
+int accumulate_chunk_rows();
 size_t bucket_sort_workspace_bytes(int64_t N, int64_t M);
 int launch_bucket_sort(const int64_t *idx, int64_t N, int64_t M, int32_t *order, void *ws,
                        hipStream_t s);

@@ -266,6 +266,13 @@ struct dbgsom_ctx {
     DevBuf sc_ws, sc_x, sc_w, sc_p, sc_code, sc_proba, sc_cnt;
     int64_t masked_chunk_rows = 32768;  // rows with missing entries: query rows per chunk
     DevBuf mk_ws, mk_x, mk_w, mk_idx, mk_dist;
+    // The resident rows have missing entries (NaN): option "incomplete", set after a load and cleared by the next one.
+    // What depends on the rows alone is made when the option is set, once per load: n_obs per row (mf_nobs) and, for
+    // float32 rows, their float64 copy (mf_x64, N x d x 8 bytes of HBM).  The ordinary calls then refuse to compute
+    // on the rows; dbgsom_ctx_bmu_masked / dbgsom_ctx_epoch_masked take their place (prototypes M x d, unpadded,
+    // handed over with every call).
+    bool incomplete = false;
+    DevBuf mf_nobs, mf_x64, mf_wt, mf_w, mf_wn, mf_idx, mf_dist, mf_kw, mf_sums, mf_acc_ws, mf_sm_ws, mf_scal;
     // samples
     Samples xs, xq;
     DevBuf y;
@@ -975,6 +982,44 @@ int loaded(const dbgsom_ctx *c, const char *fn) {
     return DBGSOM_OK;
 }
 
+// the ordinary calls never compute on rows with missing entries: a NaN would run through every distance and sum
+int complete_rows(const dbgsom_ctx *c, const char *fn) {
+    if (c->incomplete) {
+        set_error("%s: the resident rows have missing entries (option \"incomplete\"): use dbgsom_ctx_bmu_masked / "
+                  "dbgsom_ctx_epoch_masked", fn);
+        return DBGSOM_EINVAL;
+    }
+    return DBGSOM_OK;
+}
+
+// what the masked calls need: rows marked incomplete (dense float32 / float64 by construction), no weights, one rank
+int masked_ready(const dbgsom_ctx *c, const char *fn) {
+    TRY(loaded(c, fn));
+    const char *why = nullptr;
+    if (c->xs.csr || c->xs.dtype == DBGSOM_BF16) why = "CSR and bfloat16 residents cannot have missing entries";
+    else if (!c->incomplete) why = "the resident rows are not marked incomplete (option \"incomplete\")";
+    else if (c->has_weights) why = "sample weights are attached";
+    else if (c->coll_nranks > 1 || c->allreduce) why = "more than one rank";
+    if (why) { set_error("%s: %s", fn, why); return DBGSOM_EINVAL; }
+    return DBGSOM_OK;
+}
+
+// the k nearest prototypes of every resident row over its observed entries: W_host (M x d) -> mf_w, mf_idx, mf_dist
+int resident_bmu_masked(dbgsom_ctx *c, const double *W_host, int64_t M, int k) {
+    Samples &s = c->xs;
+    TRY(masked_check_shape(s.dtype, s.N, s.d, s.dp, M, k));
+    TRY(c->mf_w.reserve((size_t)M * s.d * 8));
+    TRY(c->mf_wt.reserve(masked_weights_bytes(s.d, M)));
+    TRY(c->mf_idx.reserve((size_t)s.N * k * 8));
+    TRY(c->mf_dist.reserve((size_t)s.N * k * 8));
+    DBGSOM_HIP_CHECK(hipMemcpyAsync(c->mf_w.p, W_host, (size_t)M * s.d * 8, hipMemcpyHostToDevice, c->stream));
+    TRY(launch_masked_weights(c->mf_w.as<double>(), M, s.d, s.d, c->mf_wt.p, c->stream));
+    const bool f32 = s.dtype == DBGSOM_F32;
+    return launch_bmu_masked_prepared(f32 ? c->mf_x64.as<double>() : (const double *)s.X, s.N, s.d, f32 ? s.d : s.dp,
+                                      c->mf_nobs.as<int32_t>(), c->mf_wt.as<double>(), M, k, c->mf_idx.as<int64_t>(),
+                                      c->mf_dist.as<double>(), c->stream);
+}
+
 // BMU of the resident samples for the reductions around the path: k = 1 by policy, k = 2 all-pairs.
 // Results in qidx / qdist (N x k); the training hint (idx[icur], bucket order) is left alone.
 int resident_bmu(dbgsom_ctx *c, const double *W_host, int64_t M, int k, int round_f32) {
@@ -1057,7 +1102,8 @@ int dbgsom_ctx_create(int device, dbgsom_ctx **out) {
      &(c)->kw, &(c)->sums, &(c)->acc_ws, &(c)->sm_ws, &(c)->filt_ws, &(c)->scal, &(c)->qidx, &(c)->qdist, &(c)->red,  \
      &(c)->hist, &(c)->stage_dev, &(c)->part_order, &(c)->part_ws, &(c)->part_counts, &(c)->shiftb, &(c)->shard_send,    \
      &(c)->shard_gather, &(c)->sw, &(c)->wh_order, &(c)->wh_ws, &(c)->sc_ws, &(c)->sc_x, &(c)->sc_w, &(c)->sc_p, &(c)->sc_code, &(c)->sc_proba, &(c)->sc_cnt, &(c)->wt,  \
-     &(c)->mk_ws, &(c)->mk_x, &(c)->mk_w, &(c)->mk_idx, &(c)->mk_dist}
+     &(c)->mk_ws, &(c)->mk_x, &(c)->mk_w, &(c)->mk_idx, &(c)->mk_dist, &(c)->mf_nobs, &(c)->mf_x64, &(c)->mf_wt, &(c)->mf_w,   \
+     &(c)->mf_wn, &(c)->mf_idx, &(c)->mf_dist, &(c)->mf_kw, &(c)->mf_sums, &(c)->mf_acc_ws, &(c)->mf_sm_ws, &(c)->mf_scal}
 
 int dbgsom_ctx_destroy(dbgsom_ctx *c) {
     if (!c) return DBGSOM_OK;
@@ -1123,6 +1169,22 @@ int dbgsom_ctx_set_option(dbgsom_ctx *c, const char *name, int64_t v) {
     } else if (!strcmp(name, "anchor_seeds")) {
         DBGSOM_REQUIRE(v == 0 || v == 1, "anchor_seeds must be 0 or 1");
         c->anchor_seeds = (int)v;
+    } else if (!strcmp(name, "incomplete")) {
+        // 1: NaN in the resident rows marks a missing entry (set after the load; the next load clears it)
+        DBGSOM_REQUIRE(v == 0 || v == 1, "incomplete must be 0 or 1");
+        c->incomplete = false;
+        if (v == 0) { c->mf_nobs.release(); c->mf_x64.release(); return DBGSOM_OK; }
+        TRY(loaded(c, __func__));
+        Samples &s = c->xs;
+        DBGSOM_REQUIRE(!s.csr && (s.dtype == DBGSOM_F32 || s.dtype == DBGSOM_F64),
+                       "only dense float32 / float64 residents can be marked incomplete");
+        DBGSOM_REQUIRE(!c->has_weights && c->coll_nranks == 1 && !c->allreduce,
+                       "incomplete rows take neither sample weights nor more than one rank");
+        TRY(c->mf_nobs.reserve((size_t)s.N * 4));
+        if (s.dtype == DBGSOM_F32) TRY(c->mf_x64.reserve((size_t)s.N * s.d * 8));
+        TRY(launch_masked_prepare(s.X, s.dtype, s.N, s.d, s.dp, c->mf_nobs.as<int32_t>(), c->mf_x64.as<double>(), c->stream));
+        TRY(sync(c));
+        c->incomplete = true;
     } else {
         set_error("dbgsom_ctx_set_option: unknown option '%s'", name);
         return DBGSOM_EINVAL;
@@ -1163,6 +1225,7 @@ int dbgsom_ctx_get_option(dbgsom_ctx *c, const char *name, int64_t *v) {
     else if (!strcmp(name, "prototypes")) *v = c->M;
     else if (!strcmp(name, "planes_cached")) *v = c->xs.planes_ready ? 1 : 0;
     else if (!strcmp(name, "anchor_seeds")) *v = c->anchor_seeds;
+    else if (!strcmp(name, "incomplete")) *v = c->incomplete ? 1 : 0;
     else if (!strcmp(name, "anchor_builds")) *v = c->anchor_builds;
     else if (!strcmp(name, "anchor_searches")) *v = c->anchor_searches;
     else if (!strcmp(name, "anchor_state")) *v = c->xs.dtype < 0 ? 0 : c->xs.anchor_state;
@@ -1218,6 +1281,7 @@ static void reset_training_state(dbgsom_ctx *c) {
     c->hint_valid = c->last_idx_valid = c->part_valid = false;
     c->has_labels = false;
     c->has_weights = false;
+    c->incomplete = false;
     c->policy.reset();
     c->prepass_mean = NAN;
     c->last_anchor_seeded = false;
@@ -1516,6 +1580,7 @@ int dbgsom_ctx_bmu(dbgsom_ctx *c, const double *W_host, int64_t M, int k, int ro
                    double *dist_host) {
     CTX_CHECK(c);
     TRY(loaded(c, __func__));
+    TRY(complete_rows(c, __func__));
     DBGSOM_REQUIRE(idx_host && dist_host && (k == 1 || k == 2), "bad arguments");
     DBGSOM_REQUIRE(M >= k, "need k <= M");
     TRY(resident_bmu(c, W_host, M, k, round_f32));
@@ -1795,6 +1860,79 @@ int dbgsom_ctx_topographic_function(dbgsom_ctx *c, const void *Xq_host, int x_dt
     return rc;
 }
 
+// ------------------------------------------------------------------------------------------
+// fit on rows with missing entries: the resident masked search, and one epoch (masked.hip, masked_fit.hip, smooth.hip)
+// ------------------------------------------------------------------------------------------
+int dbgsom_ctx_bmu_masked(dbgsom_ctx *c, const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host) {
+    CTX_CHECK(c);
+    TRY(masked_ready(c, __func__));
+    DBGSOM_REQUIRE(W_host && idx_host && dist_host && (k == 1 || k == 2), "bad arguments");
+    DBGSOM_REQUIRE(M >= k, "need k <= M");
+    int rc = resident_bmu_masked(c, W_host, M, k);
+    if (rc == DBGSOM_OK) {
+        hipError_t e = hipMemcpyAsync(idx_host, c->mf_idx.p, (size_t)c->xs.N * k * 8, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(dist_host, c->mf_dist.p, (size_t)c->xs.N * k * 8, hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; }
+    }
+    const hipError_t es = hipStreamSynchronize(c->stream);   // (W_host is pageable: never return with its copy in flight)
+    if (rc == DBGSOM_OK && es != hipSuccess) { set_error("hipStreamSynchronize failed: %s", hipGetErrorString(es)); rc = DBGSOM_EHIP; }
+    return rc;
+}
+
+int dbgsom_ctx_epoch_masked(dbgsom_ctx *c, const double *W_host, int64_t M, double gamma, double sigma, double *W_new_host,
+                            double *change_total_host, double *errors_host, double *activations_host, int64_t *idx_host,
+                            double *dist_host) {
+    CTX_CHECK(c);
+    TRY(masked_ready(c, __func__));
+    DBGSOM_REQUIRE(W_host && W_new_host && change_total_host && errors_host && activations_host, "null pointer");
+    DBGSOM_REQUIRE(M >= 1 && sigma > 0.0, "bad arguments");
+    if (c->topoM != M) {
+        set_error("dbgsom_ctx_epoch_masked: topology holds %lld neurons, weights %lld (call "
+                  "dbgsom_ctx_set_topology after growth)", (long long)c->topoM, (long long)M);
+        return DBGSOM_ESTATE;
+    }
+    Samples &s = c->xs;
+    const int64_t N = s.N, d = s.d;
+    int32_t status = 0;
+    int rc = DBGSOM_OK;
+    do {
+        if ((rc = c->mf_kw.reserve((size_t)N * 8))) break;
+        if ((rc = c->mf_sums.reserve((size_t)M * (3 * d + 2) * 8))) break;
+        if ((rc = c->mf_acc_ws.reserve(accumulate_masked_workspace_bytes(N, d, M)))) break;
+        if ((rc = c->mf_sm_ws.reserve(smooth_masked_workspace_bytes(M, d)))) break;
+        if ((rc = c->mf_wn.reserve((size_t)M * d * 8))) break;
+        if ((rc = c->mf_scal.reserve(256))) break;
+        if ((rc = resident_bmu_masked(c, W_host, M, 1))) break;
+        const int64_t *idx = c->mf_idx.as<int64_t>();
+        const double *dist = c->mf_dist.as<double>();
+        double *sums = c->mf_sums.as<double>();
+        double *chg = c->mf_scal.as<double>();
+        int32_t *st = reinterpret_cast<int32_t *>(c->mf_scal.as<char>() + 64);
+        if ((rc = launch_exp_similarity(dist, N, gamma, c->mf_kw.as<double>(), c->stream))) break;
+        if ((rc = launch_accumulate_masked(s.X, s.dtype, N, d, s.dp, idx, c->mf_kw.as<double>(), dist, M, sums, st,
+                                           c->mf_acc_ws.p, c->mf_acc_ws.cap, c->stream)))
+            break;
+        if ((rc = launch_smooth_masked(sums, M, d, c->hop.as<float>(), sigma, c->mf_w.as<double>(), c->mf_wn.as<double>(), chg,
+                                       c->mf_sm_ws.p, c->mf_sm_ws.cap, c->stream)))
+            break;
+        hipError_t e = hipMemcpyAsync(W_new_host, c->mf_wn.p, (size_t)M * d * 8, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(change_total_host, chg, 8, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&status, st, 4, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(activations_host, sums + 3 * M * d, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(errors_host, sums + 3 * M * d + M, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && idx_host) e = hipMemcpyAsync(idx_host, idx, (size_t)N * 8, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && dist_host) e = hipMemcpyAsync(dist_host, dist, (size_t)N * 8, hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; }
+    } while (0);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (rc == DBGSOM_OK && es != hipSuccess) { set_error("hipStreamSynchronize failed: %s", hipGetErrorString(es)); rc = DBGSOM_EHIP; }
+    if (rc == DBGSOM_OK && status) { set_error("dbgsom_ctx_epoch_masked: a winner outside [0, M)"); rc = DBGSOM_ERANGE; }
+    return rc;
+}
+
 int dbgsom_ctx_exp_similarity(dbgsom_ctx *c, const double *dist_host, int64_t n, double gamma, double *kw_host) {
     CTX_CHECK(c);
     DBGSOM_REQUIRE(n >= 0 && (n == 0 || (dist_host && kw_host)), "bad arguments");
@@ -1815,6 +1953,7 @@ int dbgsom_ctx_epoch(dbgsom_ctx *c, const double *W_host, int64_t M, int round_f
                      double *activations_host, int64_t *idx_host, double *dist_host) {
     CTX_CHECK(c);
     TRY(loaded(c, __func__));
+    TRY(complete_rows(c, __func__));
     DBGSOM_REQUIRE(change_total_host && errors_host && activations_host, "null output");
     DBGSOM_REQUIRE(layout == DBGSOM_CENTRES_COMPACT || layout == DBGSOM_CENTRES_ALIGNED, "bad layout");
     if (c->topoM != M) {
@@ -1887,6 +2026,7 @@ int dbgsom_ctx_update(dbgsom_ctx *c, const double *W_host, int64_t M, const int6
                       double *change_total_host, double *errors_host, double *activations_host) {
     CTX_CHECK(c);
     TRY(loaded(c, __func__));
+    TRY(complete_rows(c, __func__));
     DBGSOM_REQUIRE(idx_host && kw_host && dist_host && change_total_host && errors_host && activations_host, "null pointer");
     DBGSOM_REQUIRE(layout == DBGSOM_CENTRES_COMPACT || layout == DBGSOM_CENTRES_ALIGNED, "bad layout");
     Samples &s = c->xs;
@@ -1918,6 +2058,7 @@ int dbgsom_ctx_update(dbgsom_ctx *c, const double *W_host, int64_t M, const int6
 int dbgsom_ctx_set_hint(dbgsom_ctx *c, const int64_t *idx_host, int64_t M) {
     CTX_CHECK(c);
     TRY(loaded(c, __func__));
+    TRY(complete_rows(c, __func__));
     DBGSOM_REQUIRE(idx_host && M >= 1 && M <= DBGSOM_MAX_PROTOTYPES, "bad arguments");
     Samples &s = c->xs;
     for (int64_t i = 0; i < s.N; ++i) DBGSOM_REQUIRE(idx_host[i] >= 0 && idx_host[i] < M, "seed index out of range");
@@ -1955,6 +2096,7 @@ int dbgsom_ctx_read_sums(dbgsom_ctx *c, double *sums_host, int64_t M) {
 int dbgsom_ctx_column_sums(dbgsom_ctx *c, const void *mean_host, void *out_host) {
     CTX_CHECK(c);
     TRY(loaded(c, __func__));
+    TRY(complete_rows(c, __func__));
     DBGSOM_REQUIRE(out_host, "null pointer");
     Samples &s = c->xs;
     if (s.csr) { set_error("dbgsom_ctx_column_sums: the resident samples are CSR (take the column moments from the stored entries on the host)"); return DBGSOM_ESTATE; }
@@ -1975,6 +2117,7 @@ int dbgsom_ctx_column_sums(dbgsom_ctx *c, const void *mean_host, void *out_host)
 int dbgsom_ctx_weighted_column_sums(dbgsom_ctx *c, const double *mean_host, double *out_host) {
     CTX_CHECK(c);
     TRY(loaded(c, __func__));
+    TRY(complete_rows(c, __func__));
     DBGSOM_REQUIRE(out_host, "null pointer");
     if (!c->has_weights) { set_error("weighted column sums requested but no weights attached (dbgsom_ctx_set_sample_weight)"); return DBGSOM_ESTATE; }
     Samples &s = c->xs;
@@ -2003,6 +2146,7 @@ static int reduce_small(dbgsom_ctx *c, double *buf_dev, int64_t n, double *out_h
 int dbgsom_ctx_quantization_error(dbgsom_ctx *c, const double *W_host, int64_t M, int round_f32, double *out2) {
     CTX_CHECK(c);
     TRY(loaded(c, __func__));
+    TRY(complete_rows(c, __func__));
     DBGSOM_REQUIRE(out2, "null pointer");
     TRY(resident_bmu(c, W_host, M, 1, round_f32));
     TRY(c->red.reserve(256 + dbgsom_sum_workspace_bytes()));
@@ -2024,6 +2168,7 @@ int dbgsom_ctx_topographic_count(dbgsom_ctx *c, const double *W_host, int64_t M,
                                  double *count_host) {
     CTX_CHECK(c);
     TRY(loaded(c, __func__));
+    TRY(complete_rows(c, __func__));
     DBGSOM_REQUIRE(xy_host && count_host && M >= 2, "bad arguments");
     TRY(resident_bmu(c, W_host, M, 2, round_f32));
     TRY(c->red.reserve(256 + align_up((size_t)M * 8) + dbgsom_sum_workspace_bytes()));
@@ -2046,6 +2191,7 @@ int dbgsom_ctx_node_statistics(dbgsom_ctx *c, const double *W_host, int64_t M, i
                                double *hits_host, double *density_host) {
     CTX_CHECK(c);
     TRY(loaded(c, __func__));
+    TRY(complete_rows(c, __func__));
     DBGSOM_REQUIRE(hits_host && density_host && sigma > 0.0, "bad arguments");
     Samples &s = c->xs;
     TRY(resident_bmu(c, W_host, M, 1, round_f32));
@@ -2146,6 +2292,7 @@ int dbgsom_ctx_partition(dbgsom_ctx *c, const double *W_host, int64_t M, int rou
                          int64_t *idx_host) {
     CTX_CHECK(c);
     TRY(loaded(c, __func__));
+    TRY(complete_rows(c, __func__));
     DBGSOM_REQUIRE(counts_host && M >= 1 && M <= DBGSOM_MAX_PROTOTYPES, "bad arguments");
     Samples &s = c->xs;
     TRY(resident_bmu(c, W_host, M, 1, round_f32));
@@ -2167,6 +2314,7 @@ int dbgsom_ctx_partition(dbgsom_ctx *c, const double *W_host, int64_t M, int rou
 int dbgsom_ctx_subset_create(dbgsom_ctx *c, int64_t neuron, dbgsom_ctx **child_out) {
     CTX_CHECK(c);
     TRY(loaded(c, __func__));
+    TRY(complete_rows(c, __func__));
     DBGSOM_REQUIRE(child_out, "null pointer");
     *child_out = nullptr;
     if (c->xs.csr) { set_error("dbgsom_ctx_subset_create: the resident samples are CSR (select the rows on the host and load them)"); return DBGSOM_ESTATE; }
@@ -2270,6 +2418,7 @@ int dbgsom_ctx_read_anchors(dbgsom_ctx *c, int64_t *n_anchors, double *anchors_h
                             int32_t *order_host, int32_t *aseed_host) {
     CTX_CHECK(c);
     TRY(loaded(c, __func__));
+    TRY(complete_rows(c, __func__));
     Samples &s = c->xs;
     if (s.anchor_state != 1) { set_error("dbgsom_ctx_read_anchors: the resident samples have no anchor buckets"); return DBGSOM_ESTATE; }
     if (aseed_host && !(c->last_anchor_seeded && c->last_filter_ws)) {

@@ -247,6 +247,41 @@ int launch_bmu_masked_rows(const void *X, int x_dtype, int64_t N, int64_t d, int
     return launch_status("masked_bmu_kernel");
 }
 
+// The two halves of launch_bmu_masked_rows on their own, for rows that stay where they are (the resident rows of a
+// fit on incomplete data): what depends on the rows alone -- n_obs and, for float32 rows, the float64 copy
+// (N x d, no padding) -- is made once per load, and every search reads it.
+int launch_masked_prepare(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int32_t *nobs, double *Xw,
+                          hipStream_t s) {
+    TRY_STATUS(masked_check_shape(x_dtype, N, d, ldx, 1, 1));
+    if (N == 0) return DBGSOM_OK;
+    DBGSOM_REQUIRE(X && nobs && (x_dtype == DBGSOM_F64 || Xw), "null pointer");
+    const dim3 pgrid((unsigned)((N + 3) / 4));
+    if (x_dtype == DBGSOM_F32)
+        hipLaunchKernelGGL(masked_prepare_kernel<float>, pgrid, dim3(256), 0, s, (const float *)X, N, (int)d, ldx, nobs, Xw);
+    else
+        hipLaunchKernelGGL(masked_prepare_kernel<double>, pgrid, dim3(256), 0, s, (const double *)X, N, (int)d, ldx, nobs,
+                           (double *)nullptr);
+    return launch_status("masked_prepare_kernel");
+}
+
+// X64: the rows as float64 (ld64 values apart), nobs: their observed entries; Wt: launch_masked_weights' output
+int launch_bmu_masked_prepared(const double *X64, int64_t N, int64_t d, int64_t ld64, const int32_t *nobs,
+                               const double *Wt, int64_t M, int k, int64_t *idx, double *dist, hipStream_t s) {
+    TRY_STATUS(masked_check_shape(DBGSOM_F64, N, d, ld64, M, k));
+    if (N == 0) return DBGSOM_OK;
+    DBGSOM_REQUIRE(X64 && nobs && Wt && idx && dist, "null pointer");
+    const int64_t ldwt = csr_wt_ld(M);
+#define DBGSOM_BMU_MASKED(KK, RR)                                                                                \
+    hipLaunchKernelGGL((masked_bmu_kernel<KK, RR>), dim3((unsigned)((N + RR - 1) / RR)), dim3(MT), 0, s, X64, N, \
+                       (int)d, ld64, nobs, Wt, ldwt, (int)M, idx, dist)
+    if (N < MASKED_FEW_ROWS) { if (k == 1) DBGSOM_BMU_MASKED(1, MRS); else DBGSOM_BMU_MASKED(2, MRS); }
+    else { if (k == 1) DBGSOM_BMU_MASKED(1, MR); else DBGSOM_BMU_MASKED(2, MR); }
+#undef DBGSOM_BMU_MASKED
+    return launch_status("masked_bmu_kernel");
+}
+
+size_t masked_weights_bytes(int64_t d, int64_t M) { return masked_wt_bytes(d, M); }
+
 int launch_fill_missing(void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *W, int64_t M,
                         int64_t ldw, const int64_t *idx, int64_t idx_stride, hipStream_t s) {
     DBGSOM_REQUIRE(masked_dtype_ok(x_dtype), "x_dtype must be DBGSOM_F32 or DBGSOM_F64");

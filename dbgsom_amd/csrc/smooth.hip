@@ -550,4 +550,112 @@ int launch_smooth(const double *sums, int64_t M, int64_t d, const float *hop, do
     return launch_status("smooth kernels");
 }
 
+// ---- smoothing of a fit on rows with missing entries (masked_fit.hip) ------------------------------------------
+// sums = [S (M x d) | K (M x d) | A (M x d) | a | E]: per (neuron, feature) over the rows that observe the feature.
+//   C_lc  = S_lc / K_lc                                    where A_lc > 0
+//   W'_jc = sum_l h_jl A_lc C_lc / sum_l h_jl A_lc         over the l with A_lc > 0,  h = exp(-(hop^2 / (2 sigma^2)))
+//   W'_jc = W_jc bit for bit                               where that denominator is 0
+// Every feature has its own denominator, so nothing of a is folded into G: G = h, and numerator and denominator
+// are ONE product G [A o C | A] (M x M x 2 d) on smooth_gemm_kernel -- rows of 2 d float64 are always 16-byte
+// multiples, so the LDS-DMA kernel takes every shape; its division is by den = 1 (exact).  An element-wise
+// kernel puts the split-K pieces together in piece order, divides, keeps W where the denominator is 0; then
+// rowchange_kernel for the convergence norm.  The aligned form always: a centre sits in its neuron's row.
+struct SmoothMaskedWs {
+    double *B;       // Mp x 2 d   [A o C | A], zero rows behind row M, one tile of slack
+    double *G;       // M x Mp     h, zeros behind column M
+    double *ones;    // M          the GEMM's divisor
+    double *rowchg;  // M
+    uint32_t *ticket;
+    double *part;    // splits x M x 2 d   the product (its split-K pieces)
+};
+
+static size_t carve_smooth_masked(SmoothMaskedWs *w, char *base, int64_t M, int64_t d) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
+    const int64_t Mp = smooth_mp(M);
+    const size_t oB = take(((size_t)Mp * 2 * d + 64) * 8), oG = take(((size_t)M * Mp + 16) * 8);
+    const size_t oD = take((size_t)M * 8), oR = take((size_t)M * 8), oK = take((size_t)M * 4);
+    const size_t oP = take((size_t)gemm_splits(M, 2 * d) * M * 2 * d * 8);
+    if (w) {
+        w->B = (double *)(base + oB); w->G = (double *)(base + oG);
+        w->ones = (double *)(base + oD); w->rowchg = (double *)(base + oR);
+        w->ticket = (uint32_t *)(base + oK);
+        w->part = (double *)(base + oP);
+    }
+    return off;
+}
+
+size_t smooth_masked_workspace_bytes(int64_t M, int64_t d) {
+    if (M < 1 || d < 1) return 0;
+    return carve_smooth_masked(nullptr, nullptr, M, d);
+}
+
+// workgroup i: row i of [A o C | A], row i of G = h and ones[i]; workgroup 0 also the zero rows of B behind row M
+__global__ __launch_bounds__(256) void smooth_masked_prep_kernel(const double *__restrict__ S, const double *__restrict__ K,
+                                                                 const double *__restrict__ A,
+                                                                 const float *__restrict__ hop, int M, int d,
+                                                                 double two_sigma_sq, double *__restrict__ B,
+                                                                 double *__restrict__ G, double *__restrict__ ones,
+                                                                 uint32_t *__restrict__ ticket, int Mp) {
+    const int i = blockIdx.x, t = threadIdx.x;
+    if (i == 0 && t == 0) *ticket = 0u;  // of the row-change kernel behind the GEMM
+    if (t == 0) ones[i] = 1.0;
+    for (int c = t; c < d; c += 256) {
+        const double a = A[(size_t)i * d + c];
+        B[(size_t)i * 2 * d + c] = a > 0.0 ? a * (S[(size_t)i * d + c] / K[(size_t)i * d + c]) : 0.0;
+        B[(size_t)i * 2 * d + d + c] = a;
+    }
+    if (i == 0)
+        for (int64_t e = t; e < (int64_t)(Mp - M) * 2 * d; e += 256) B[(size_t)M * 2 * d + e] = 0.0;
+    for (int j = t; j < Mp; j += 256) {
+        double g = 0.0;
+        if (j < M) {
+            const double h = (double)hop[(size_t)i * M + j];
+            g = exp(-((h * h) / two_sigma_sq));
+        }
+        G[(size_t)i * Mp + j] = g;
+    }
+}
+
+// W'[i, c] = num / den from the pieces of the product (piece order), W[i, c] where den is 0
+__global__ __launch_bounds__(256) void smooth_masked_divide_kernel(const double *__restrict__ part, int M, int d, int splits,
+                                                                   const double *__restrict__ Wo, double *__restrict__ Wn) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)M * d) return;
+    const int64_t i = e / d, c = e - i * d;
+    const size_t row = (size_t)i * 2 * d, piece = (size_t)M * 2 * d;
+    double num = part[row + c], den = part[row + d + c];
+    for (int z = 1; z < splits; ++z) { num += part[z * piece + row + c]; den += part[z * piece + row + d + c]; }
+    Wn[e] = den > 0.0 ? num / den : Wo[e];
+}
+
+int launch_smooth_masked(const double *sums, int64_t M, int64_t d, const float *hop, double sigma, const double *W_old,
+                         double *W_new, double *change_total, void *ws, size_t ws_bytes, hipStream_t s) {
+    DBGSOM_REQUIRE(M >= 1 && M <= 0x7fff && d >= 1 && d <= 0x3ffffff0, "bad shape");
+    DBGSOM_REQUIRE(sums && hop && W_old && W_new && change_total && ws, "null pointer");
+    DBGSOM_REQUIRE(W_old != W_new, "W_new must not alias W_old");
+    DBGSOM_REQUIRE(is_aligned(ws, 256), "workspace must be 256-byte aligned");
+    DBGSOM_REQUIRE(sigma > 0.0, "sigma must be positive");
+    if (ws_bytes < smooth_masked_workspace_bytes(M, d)) {
+        set_error("dbgsom_smooth_masked: workspace too small (%zu < %zu)", ws_bytes, smooth_masked_workspace_bytes(M, d));
+        return DBGSOM_ENOMEM;
+    }
+    SmoothMaskedWs w;
+    carve_smooth_masked(&w, (char *)ws, M, d);
+    const int Mi = (int)M, di = (int)d, d2 = 2 * di, Mp = (int)smooth_mp(M);
+    const double *S = sums, *K = sums + (size_t)M * d, *A = K + (size_t)M * d;
+    hipLaunchKernelGGL(smooth_masked_prep_kernel, dim3((unsigned)M), dim3(256), 0, s, S, K, A, hop, Mi, di,
+                       2.0 * (sigma * sigma), w.B, w.G, w.ones, w.ticket, Mp);
+    const int splits = gemm_splits(M, 2 * d);
+    // (splits == 1: the kernel stores product / 1 where the pieces would go)
+    hipLaunchKernelGGL(smooth_gemm_kernel, dim3((unsigned)((d2 + GT - 1) / GT), (unsigned)((M + GR - 1) / GR), (unsigned)splits),
+                       dim3(256), 0, s, w.G, w.B, w.ones, Mi, Mp, d2, splits, splits == 1 ? (double *)nullptr : w.part,
+                       splits == 1 ? w.part : (double *)nullptr);
+    hipLaunchKernelGGL(smooth_masked_divide_kernel, dim3((unsigned)((M * d + 255) / 256)), dim3(256), 0, s, w.part, Mi, di,
+                       splits, W_old, W_new);
+    hipLaunchKernelGGL(rowchange_kernel, dim3((unsigned)((M + RC_ROWS - 1) / RC_ROWS)), dim3(256), 0, s, W_old, W_new, Mi, di,
+                       1, (const double *)nullptr, w.ones, w.rowchg, w.ticket, change_total);
+    return launch_status("masked smooth kernels");
+}
+
 }  // namespace dbgsom

@@ -11,7 +11,6 @@ from statistics import mode
 
 import numpy as np
 from sklearn.base import ClassifierMixin, TransformerMixin
-from sklearn.utils import check_X_y
 from sklearn.utils.validation import check_is_fitted
 
 from .backend import is_sparse
@@ -23,9 +22,8 @@ class SomClassifier(BaseSom, TransformerMixin, ClassifierMixin):
 
     def _check_input_data(self, X, y):
         # (X's finite check rides on the device's column sums when it can; y is checked here as ever)
-        self._finite_deferred = self._finite_check_on_device()
-        X, y = check_X_y(X=X, y=y, ensure_min_samples=4, dtype=[np.float64, np.float32], accept_sparse="csr",
-                         **self._finite_kw(not self._finite_deferred))
+        # (missing_values="nan-fit": NaN passes in dense X -- BaseSom._check_fit_array)
+        X, y = self._check_fit_array(X, y, supervised=True)
         X = self._check_sparse_input(X)
         return X, y
 

@@ -7,7 +7,6 @@ from __future__ import annotations
 
 import numpy as np
 from sklearn.base import ClusterMixin, TransformerMixin
-from sklearn.utils import check_array
 from sklearn.utils.validation import check_is_fitted
 
 from .base import BaseSom
@@ -19,9 +18,8 @@ class SomVQ(BaseSom, ClusterMixin, TransformerMixin):
     def _check_input_data(self, X, y=None):
         # float32 is kept as float32 (the device stores it as such); anything else -> float64
         # (the finite check rides on the device's column sums when it can: BaseSom._assert_finite_from_moments)
-        self._finite_deferred = self._finite_check_on_device()
-        X = check_array(array=X, ensure_min_samples=4, dtype=[np.float64, np.float32], accept_sparse="csr",
-                        **self._finite_kw(not self._finite_deferred))
+        # (missing_values="nan-fit": NaN passes in dense X -- BaseSom._check_fit_array)
+        X, _ = self._check_fit_array(X)
         X = self._check_sparse_input(X)
         return X, None  # any y is ignored
 

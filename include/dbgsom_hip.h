@@ -520,6 +520,61 @@ int dbgsom_ctx_bmu_query_masked(dbgsom_ctx *ctx, const void *Xq_host, int x_dtyp
                                 const double *W_host, int64_t M, int k, int64_t *idx_host,
                                 double *dist_host, void *Xfilled_host);
 
+/* ---- fit on rows with missing entries (csrc/masked_fit.hip, csrc/smooth.hip) ---------------------------
+ * One epoch on prototypes W (M x d, complete), hop matrix and sigma, NaN marking a missing entry of X:
+ *   1. (dist_i, win_i): the masked search above with k = 1 -- every row goes through it, complete rows
+ *      included; kw_i = 1 - sqrt(1 - exp(-gamma dist_i^2)) (dbgsom_exp_similarity).
+ *   2. per neuron j and feature c, over the rows with win_i = j whose entry c is observed:
+ *        S_jc = sum kw_i x_ic,  K_jc = sum kw_i,  A_jc = their number;
+ *      per neuron over all of its rows: a_j = their number, E_j = sum dist_i.
+ *   3. centres C_jc = S_jc / K_jc where A_jc > 0.
+ *   4. h = exp(-(hop^2 / (2 sigma^2))),  W'_jc = sum_l h_jl A_lc C_lc / sum_l h_jl A_lc over the l with
+ *      A_lc > 0; where that denominator is 0 (a disconnected lattice, underflow) W'_jc = W_jc bit for bit.
+ *      Always the aligned form (row = neuron id; on complete rows: DBGSOM_CENTRES_ALIGNED of dbgsom_smooth);
+ *      the compacted layout has no per-feature meaning and is not offered.
+ *   5. change_total = sum_j |W_j - W'_j|_2; the epoch's errors are E, its activations a.
+ *
+ * dbgsom_accumulate_masked is step 2 with the caller's winners, sample kernel values and distances:
+ *   sums_dev: M (3 d + 2) float64 = [S (M x d) | K (M x d) | A (M x d) | a (M) | E (M)], every part a sum over
+ *   rows (all-reducible).  Stable counting sort by winner, chunks of <= 128 rows summed in list order, chunk
+ *   partials in chunk order, groups in group order: bitwise reproducible, independent of the grid, no
+ *   floating-point atomics.  A (neuron, feature) nobody observed keeps exact zeros in S, K and A; A and a are
+ *   exact integers.  Only the first d columns of a row are data (whatever sits between d and ldx is never
+ *   added).  X: DBGSOM_F32 or DBGSOM_F64 (DBGSOM_BF16 is DBGSOM_EINVAL), any ldx >= d, any alignment of its
+ *   element type (16-byte aligned rows take the vector loads).  A winner outside [0, M) sets *status_dev (may
+ *   be NULL) to 1 and its row is skipped, as in dbgsom_accumulate.  Workspace 256-byte aligned.
+ * dbgsom_smooth_masked is steps 3-5 on such sums: hop_dev M x M float32, W_old / W_new M x d float64 (no
+ * padding; W_new must not alias W_old), change_total_dev one float64. */
+size_t dbgsom_accumulate_masked_workspace_bytes(int64_t N, int64_t d, int64_t M);
+int dbgsom_accumulate_masked(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx,
+                             const int64_t *idx_dev, const double *kw_dev, const double *dist_dev, int64_t M,
+                             double *sums_dev, int32_t *status_dev, void *workspace_dev, size_t workspace_bytes,
+                             void *stream);
+size_t dbgsom_smooth_masked_workspace_bytes(int64_t M, int64_t d);
+int dbgsom_smooth_masked(const double *sums_dev, int64_t M, int64_t d, const float *hop_dev, double sigma,
+                         const double *W_old_dev, double *W_new_dev, double *change_total_dev,
+                         void *workspace_dev, size_t workspace_bytes, void *stream);
+/* Context level.  dbgsom_ctx_set_option(ctx, "incomplete", 1) after a dbgsom_ctx_load marks the resident rows
+ * as rows with missing entries (the next load clears it; dense DBGSOM_F32 / DBGSOM_F64 residents only, no
+ * sample weights, one rank -- DBGSOM_EINVAL otherwise).  What depends on the rows alone is made then, once
+ * per load: n_obs per row and, for float32 rows, their float64 copy (N x d x 8 bytes of HBM).  From then on
+ * every ordinary context call that would compute on the rows (dbgsom_ctx_epoch, _bmu, _update, _partition,
+ * _subset_create, _column_sums, _weighted_column_sums, _quantization_error, _topographic_count,
+ * _node_statistics, _set_hint, _read_anchors, and the filter planes and anchors behind them) returns
+ * DBGSOM_EINVAL with a message instead of a result computed from NaN.  In their place:
+ *   dbgsom_ctx_bmu_masked    the masked search of the resident rows, k in {1, 2}; idx / dist N x k
+ *   dbgsom_ctx_epoch_masked  steps 1-5, one call per epoch.  W_host, W_new_host: M x d; the prototypes are
+ *                            handed over with every call (nothing stays resident between masked epochs);
+ *                            errors_host / activations_host: M; idx_host / dist_host (N each) may be NULL.
+ *                            Needs dbgsom_ctx_set_topology for M neurons (DBGSOM_ESTATE otherwise).
+ * Both return DBGSOM_EINVAL on rows not marked incomplete (CSR and bfloat16 residents never are), with
+ * sample weights attached, or with more than one rank. */
+int dbgsom_ctx_bmu_masked(dbgsom_ctx *ctx, const double *W_host, int64_t M, int k, int64_t *idx_host,
+                          double *dist_host);
+int dbgsom_ctx_epoch_masked(dbgsom_ctx *ctx, const double *W_host, int64_t M, double gamma, double sigma,
+                            double *W_new_host, double *change_total_host, double *errors_host,
+                            double *activations_host, int64_t *idx_host, double *dist_host);
+
 /* ---- sparse coding: BaseSom.transform / SomClassifier.predict_proba (BaseSom.py:241-268,
  * SomClassifier.py:178-220) ------------------------------------------------------------------------
  * scikit-learn's SparseCoder(dictionary=normalize(W), transform_algorithm="lasso_lars",
