@@ -106,6 +106,11 @@ SIGNATURES = {
     "dbgsom_ctx_write_weight_rows": (_ci, [_vp, _i64, _i64, _vp]),
     "dbgsom_ctx_bmu": (_ci, [_vp, _vp, _i64, _ci, _ci, _vp, _vp]),
     "dbgsom_ctx_bmu_query": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _ci, _ci, _vp, _vp]),
+    "dbgsom_ctx_bmu_query_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _ci, _ci, _vp, _vp]),
+    "dbgsom_ctx_sparse_code_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _ci, _vp, _i64, _vp, _vp,
+                                            _vp]),
+    "dbgsom_ctx_topographic_function_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _ci, _vp, _i64, _vp,
+                                                     _vp, _vp]),
     "dbgsom_sparse_code_workspace_bytes": (_sz, [_i64, _i64, _i64, _ci]),
     "dbgsom_sparse_code": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _i64, _i64, _ci, _ci, _vp, _i64, _vp, _vp, _vp,
                                  _vp, _sz, _vp]),

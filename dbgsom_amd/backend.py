@@ -73,7 +73,11 @@ class HotPathBackend:
     local per-prototype sums -> (all-reduce across sample shards) -> smoothing.
 
     ``load(X)`` and ``bmu(W, k, X=...)`` may be handed a scipy sparse matrix in CSR form (the estimators
-    pass sparse input through as it is); every other argument is dense."""
+    pass sparse input through as it is); every other argument is dense.
+
+    A backend that can adopt rows living in GPU memory (``is_device_array``) has ``load_device(X)`` and takes such
+    an X in ``bmu``, ``sparse_code`` and ``topographic_function``; per-row results then come back as arrays next
+    to X.  ``device_index`` is the GPU it runs on."""
 
     name = "abstract"
 
@@ -276,6 +280,37 @@ def is_sparse(X) -> bool:
     return sp is not None and sp.issparse(X)
 
 
+def is_device_array(X) -> bool:
+    """Whether X is an array that lives in GPU memory: anything with ``data_ptr()``, ``shape``, ``stride()``,
+    ``dtype`` and a ``device`` whose ``type`` is ``"cuda"`` -- a torch tensor on a GPU (ROCm builds of PyTorch
+    call the device "cuda" too).  A CPU tensor is not one: it goes through ``check_array`` like any host array."""
+    if not all(hasattr(X, a) for a in ("data_ptr", "shape", "stride", "dtype", "device")):
+        return False
+    return getattr(X.device, "type", None) == "cuda"
+
+
+def array_namespace(X):
+    """The module whose functions make arrays like X (``empty``, ``asarray``, ``isfinite``, ...): what X names
+    through the array API's ``__array_namespace__``, else the package its class comes from (``torch``)."""
+    if hasattr(X, "__array_namespace__"):
+        return X.__array_namespace__()
+    import importlib
+
+    return importlib.import_module(type(X).__module__.split(".")[0])
+
+
+def dtype_name(X) -> str:
+    """"float32" for torch.float32, numpy.float32 and the like."""
+    return str(X.dtype).split(".")[-1]
+
+
+def device_empty(like, shape, dtype: str):
+    """An uninitialised array of `shape` and dtype `dtype` ("int64", "float64") next to `like`, made by like's
+    own namespace."""
+    ns = array_namespace(like)
+    return ns.empty(tuple(int(v) for v in shape), dtype=getattr(ns, dtype), device=like.device)
+
+
 def canonical_csr(X):
     """X as canonical CSR for the device: column indices ascending and without duplicates within a row (made
     so on a copy when they are not), float32 kept, anything else but float64 converted to float64 as dense
@@ -383,6 +418,7 @@ class HipBackend(HotPathBackend):
         self._cb = None
         self._cb_error = None
         self._last_M = 0
+        self._x_traffic = {k: 0 for k in self._X_TRAFFIC}   # of contexts released since, and of fetch / put
         self.filter_log = []        # (epoch kind, mean candidates, digit planes) of the last epochs
         self.phase_log = None       # bench hook: a list collects the per-epoch phase times (ms)
         if _ctx is not None:
@@ -607,6 +643,27 @@ class HipBackend(HotPathBackend):
             self._incomplete = True
         return self
 
+    @staticmethod
+    def _producer_done(X_dev):
+        """Wait for the torch stream X_dev was produced on (its producer may still be running)."""
+        if type(X_dev).__module__.split(".")[0] == "torch":
+            import torch
+
+            torch.cuda.current_stream(X_dev.device).synchronize()
+
+    def _device_rows(self, X_dev, dtypes=("float32", "float64")):
+        """-> (dtype code, N, d, row stride) of rows in HBM a *_device entry point can take as they are."""
+        code = {"float32": _native.F32, "float64": _native.F64, "bfloat16": _native.BF16}.get(dtype_name(X_dev))
+        if code is None or dtype_name(X_dev) not in dtypes or len(X_dev.shape) != 2:
+            raise ValueError("device rows must be a 2-D array of " + " / ".join(dtypes))
+        N, d = int(X_dev.shape[0]), int(X_dev.shape[1])
+        if X_dev.stride(1) != 1 or (N > 1 and X_dev.stride(0) < d):
+            raise ValueError("device rows need unit column stride and a row stride of at least their length")
+        index = getattr(X_dev.device, "index", None)
+        if index is not None and index != self.device_index:
+            raise ValueError(f"the rows live on GPU {index}, this backend runs on GPU {self.device_index}")
+        return code, N, d, int(X_dev.stride(0)) if N > 1 else d
+
     def load_device(self, X_dev):
         """Adopt samples that already live in HBM: anything with `data_ptr()`, `shape`, `stride()`
         and a float32 / float64 / bfloat16 dtype (a torch tensor; bench: generated on the device).
@@ -617,10 +674,10 @@ class HipBackend(HotPathBackend):
         if code is None or len(X_dev.shape) != 2 or X_dev.stride(1) != 1:
             raise ValueError("X_dev must be a 2-D float32/float64/bfloat16 array with unit column stride")
         N, d = int(X_dev.shape[0]), int(X_dev.shape[1])
-        if type(X_dev).__module__.split(".")[0] == "torch":   # its producer may still be running
-            import torch
-
-            torch.cuda.current_stream(X_dev.device).synchronize()
+        index = getattr(getattr(X_dev, "device", None), "index", None)
+        if index is not None and index != self.device_index:
+            raise ValueError(f"the rows live on GPU {index}, this backend runs on GPU {self.device_index}")
+        self._producer_done(X_dev)
         self._call("dbgsom_ctx_load_device", self._ctx, ctypes.c_void_p(X_dev.data_ptr()), code, N, d,
                    int(X_dev.stride(0)))
         self._after_load((N, d), {_native.F32: np.dtype(np.float32), _native.F64: np.dtype(np.float64),
@@ -707,6 +764,8 @@ class HipBackend(HotPathBackend):
                 self._call("dbgsom_ctx_bmu_masked", self._ctx, p, M, int(k), idx.ctypes.data, dist.ctypes.data)
             else:
                 self._call("dbgsom_ctx_bmu", self._ctx, p, M, int(k), rf, idx.ctypes.data, dist.ctypes.data)
+        elif is_device_array(X):
+            return self._bmu_device(W, k, X)
         elif is_sparse(X):
             csr, indptr, indices, data = canonical_csr(X)
             W = np.asarray(W)
@@ -738,6 +797,49 @@ class HipBackend(HotPathBackend):
         if k == 1:
             return dist.reshape(-1), idx.reshape(-1)
         return dist, idx
+
+    def _bmu_device(self, W, k, X):
+        """``bmu(W, k, X=X)`` for rows in HBM (dbgsom_ctx_bmu_query_device): the searches of the host-array call on
+        X's own bytes; distances and winners are arrays on X's device that the search writes itself."""
+        code, N, d, ldx = self._device_rows(X)
+        W = np.asarray(W)
+        if W.ndim != 2 or W.shape[1] != d:
+            raise ValueError("prototype / sample feature mismatch")
+        rf = int(code == _native.F32 and W.dtype == np.float32)
+        W64 = np.ascontiguousarray(W, dtype=np.float64)
+        idx = device_empty(X, (N, k), "int64")
+        dist = device_empty(X, (N, k), "float64")
+        self._producer_done(X)
+        self._call("dbgsom_ctx_bmu_query_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code, N, d, ldx,
+                   W64.ctypes.data, W64.shape[0], int(k), rf, ctypes.c_void_p(idx.data_ptr()),
+                   ctypes.c_void_p(dist.data_ptr()))
+        if k == 1:
+            return dist.reshape(-1), idx.reshape(-1)
+        return dist, idx
+
+    def resident_winners(self, W):
+        """``bmu(W, 1)[1]`` of the resident samples without the distances' trip to the host."""
+        self._require_loaded()
+        if self._incomplete:
+            return self.bmu(W, 1)[1]
+        keep, p, M, rf = self._w_arg(W)
+        idx = np.empty(self._N, dtype=np.int64)
+        self._call("dbgsom_ctx_bmu", self._ctx, p, M, 1, rf, idx.ctypes.data, None)
+        return idx
+
+    # -- per-row results between HBM and the host ------------------------------------------------------
+    def fetch(self, t) -> np.ndarray:
+        """A per-row result that lives in HBM as a NumPy array (counted as sample traffic)."""
+        out = t.cpu().numpy()
+        self._x_traffic["x_download_bytes"] += out.nbytes
+        return out
+
+    def put(self, a, like):
+        """A per-row result on the host as an array next to `like` (counted as sample traffic)."""
+        a = np.ascontiguousarray(a)
+        self._x_traffic["x_upload_bytes"] += a.nbytes
+        self._x_traffic["x_upload_calls"] += 1
+        return array_namespace(like).asarray(a, device=like.device)
 
     # -- rows with missing entries ------------------------------------------------------------------
     masked_chunk_rows = property(lambda self: self._get("masked_chunk_rows"),
@@ -776,10 +878,15 @@ class HipBackend(HotPathBackend):
         """The host default's result computed on the device (csrc/sparse_code.hip); n_jobs is
         ignored.  W may be RESIDENT.  The counters of the call land in ``sparse_code_counts``;
         like scikit-learn, one ConvergenceWarning when a row skipped a degenerate regressor or
-        stopped early."""
-        X = np.ascontiguousarray(X)
-        if X.dtype not in (np.float32, np.float64):
-            X = X.astype(np.float64)
+        stopped early.  Rows in HBM (``is_device_array``) are coded where they lie, chunk by chunk, and the
+        result is an array on their device that the coder writes itself (dbgsom_ctx_sparse_code_device)."""
+        on_device = is_device_array(X)
+        if on_device:
+            code, N, d_x, ldx = self._device_rows(X)
+        else:
+            X = np.ascontiguousarray(X)
+            if X.dtype not in (np.float32, np.float64):
+                X = X.astype(np.float64)
         if W is RESIDENT:
             self._require_loaded()
             keep, p, M = None, None, self._get("prototypes")
@@ -789,23 +896,30 @@ class HipBackend(HotPathBackend):
             if keep.ndim != 2:
                 raise ValueError("W must be 2-D")
             p, (M, d) = keep.ctypes.data, keep.shape
-        if X.ndim != 2 or X.shape[1] != d:
+        if len(X.shape) != 2 or X.shape[1] != d:
             raise ValueError("prototype / sample feature mismatch")
         N = X.shape[0]
         counts = np.zeros(len(_native.SC_COUNTS), dtype=np.uint64)
         if P is None:
-            out, Pc, C, code_p, proba_p = np.empty((N, M)), None, 0, None, None
-            code_p = out.ctypes.data
+            Pc, C = None, 0
         else:
             Pc = np.ascontiguousarray(P, dtype=np.float64)
             if Pc.ndim != 2 or Pc.shape[0] != M:
                 raise ValueError("P must have one row per prototype")
             C = Pc.shape[1]
-            out = np.empty((N, C))
-            code_p, proba_p = None, out.ctypes.data
-        self._call("dbgsom_ctx_sparse_code", self._ctx, X.ctypes.data if N else None, _x_dtype_code(X.dtype), N, d,
-                   p, M, int(max_iter), None if Pc is None else Pc.ctypes.data, C, code_p, proba_p,
-                   counts.ctypes.data)
+        if on_device:
+            out = device_empty(X, (N, M if P is None else C), "float64")
+            out_p = ctypes.c_void_p(out.data_ptr()) if N else None
+            self._producer_done(X)
+            self._call("dbgsom_ctx_sparse_code_device", self._ctx, ctypes.c_void_p(X.data_ptr()) if N else None, code, N,
+                       d, ldx, p, M, int(max_iter), None if Pc is None else Pc.ctypes.data, C,
+                       out_p if P is None else None, None if P is None else out_p, counts.ctypes.data)
+        else:
+            out = np.empty((N, M if P is None else C))
+            out_p = out.ctypes.data
+            self._call("dbgsom_ctx_sparse_code", self._ctx, X.ctypes.data if N else None, _x_dtype_code(X.dtype), N, d,
+                       p, M, int(max_iter), None if Pc is None else Pc.ctypes.data, C, out_p if P is None else None,
+                       None if P is None else out_p, counts.ctypes.data)
         self.sparse_code_counts = dict(zip(_native.SC_COUNTS, (int(v) for v in counts)))
         if counts[4] or counts[5]:
             import warnings
@@ -821,23 +935,34 @@ class HipBackend(HotPathBackend):
     def topographic_function(self, W, X, coords, want_distances=False):
         """The host default's result computed on the device (csrc/topofn.hip): the k = 2 search of
         ``bmu(W, 2, X=X)``, the edge set, a breadth-first search from every neuron and the histograms,
-        with the pairs never leaving HBM."""
-        X = np.ascontiguousarray(X)
-        if X.dtype not in (np.float32, np.float64):
-            X = X.astype(np.float64)
+        with the pairs never leaving HBM.  Rows in HBM (``is_device_array``) are searched where they lie
+        (dbgsom_ctx_topographic_function_device); the histograms are host arrays either way."""
+        on_device = is_device_array(X)
+        if on_device:
+            code, N, d_x, ldx = self._device_rows(X)
+        else:
+            X = np.ascontiguousarray(X)
+            if X.dtype not in (np.float32, np.float64):
+                X = X.astype(np.float64)
         W = np.asarray(W)
-        if X.ndim != 2 or W.ndim != 2 or W.shape[1] != X.shape[1]:
+        if len(X.shape) != 2 or W.ndim != 2 or W.shape[1] != X.shape[1]:
             raise ValueError("prototype / sample feature mismatch")
         xy = np.ascontiguousarray(coords, dtype=np.int32).reshape(-1, 2)
         M = W.shape[0]
         if xy.shape[0] != M:
             raise ValueError("coords must be (M, 2)")
-        rf = int(X.dtype == np.float32 and W.dtype == np.float32)
+        rf = int(dtype_name(X) == "float32" and W.dtype == np.float32)
         W64 = np.ascontiguousarray(W, dtype=np.float64)
         n_pos = int((xy.astype(np.int64).max(axis=0) - xy.astype(np.int64).min(axis=0)).max()) + 1
         hist_pos = np.empty(n_pos, dtype=np.int64)
         hist_neg = np.empty(M + 1, dtype=np.int64)
         D = np.empty((M, M), dtype=np.int32) if want_distances else None
+        if on_device:
+            self._producer_done(X)
+            self._call("dbgsom_ctx_topographic_function_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code, N, d_x,
+                       ldx, W64.ctypes.data, M, rf, xy.ctypes.data, n_pos, hist_pos.ctypes.data, hist_neg.ctypes.data,
+                       None if D is None else D.ctypes.data)
+            return hist_pos, hist_neg, D
         self._call("dbgsom_ctx_topographic_function", self._ctx, X.ctypes.data, _x_dtype_code(X.dtype),
                    X.shape[0], X.shape[1], W64.ctypes.data, M, rf, xy.ctypes.data, n_pos, hist_pos.ctypes.data,
                    hist_neg.ctypes.data, None if D is None else D.ctypes.data)
@@ -1001,6 +1126,16 @@ class HipBackend(HotPathBackend):
                 "w_row_writes", "w_row_reads")
         return {k: self._get(k) for k in keys}
 
+    _X_TRAFFIC = ("x_upload_bytes", "x_upload_calls", "x_download_bytes")
+
+    def sample_traffic(self):
+        """PCIe traffic of the samples since this backend was made (``release`` does not reset it):
+        ``x_upload_bytes`` / ``x_upload_calls`` -- sample rows host -> HBM (``load``, every query handed over as a
+        host array), ``x_download_bytes`` -- per-row results HBM -> host (winners, distances, codes, class
+        probabilities, filled rows; ``fetch``).  Rows that are in HBM already (``load_device``, a device array
+        as X) move neither."""
+        return {k: self._x_traffic[k] + (self._get(k) if self._ctx else 0) for k in self._X_TRAFFIC}
+
     def plane_cost(self, p, mean, M):
         """Cost model of the engine's policy (csrc/search_policy.h, seeds = the previous winners) for `p` digit
         planes of the candidate sweep and candidate lists of `mean` entries; p = 0: no sweep, candidates from the
@@ -1145,6 +1280,8 @@ class HipBackend(HotPathBackend):
         """Give the device memory back (the backend can be loaded again afterwards; options stay)."""
         if self._ctx:
             opts = {k: self._get(k) for k in self._SETTABLE}
+            for k in self._X_TRAFFIC:
+                self._x_traffic[k] += self._get(k)
             _native.call("dbgsom_ctx_destroy", self._ctx)
             self._ctx = ctypes.c_void_p()
             _native.call("dbgsom_ctx_create", self.device_index, ctypes.byref(self._ctx))

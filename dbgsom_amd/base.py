@@ -23,6 +23,18 @@ Sparse input: ``fit``, ``predict``, ``transform``, ``predict_proba`` and ``calcu
 take a scipy sparse matrix (converted to CSR; never densified as a whole).  A fit on sparse X equals the fit
 on ``X.toarray()`` up to the column moments, which are taken in float64 from the stored entries.
 ``topographic_function`` takes dense X only (``TypeError`` for sparse X).
+
+Device arrays: every method that takes complete dense rows also takes a ``torch.Tensor`` that lives on the
+estimator's GPU (anything ``backend.is_device_array`` accepts) and gives the result of the same call on
+``X.cpu().numpy()`` bit for bit, without X crossing PCIe.  Per-row results (``predict``, ``fit_predict``,
+``transform``, ``predict_proba``) come back as tensors on X's device, scalars as Python floats, fitted attributes
+stay NumPy; ``SomClassifier.predict`` returns a NumPy array of class labels.  float32 / float64 rows are used as
+they are (borrowed during ``fit`` when they have a multiple of 16 features, contiguous rows and a 16-byte aligned
+base -- do not write to the tensor until ``fit`` returns --, copied on the device otherwise); float16 / bfloat16
+rows are widened with ``.float()`` (an N x d x 4 byte device copy), integer and bool rows with ``.double()``.
+Refused, with a message that says to pass a host array: a tensor on another GPU, a sparse tensor, a tensor with
+NaN under ``missing_values="nan"`` / ``"nan-fit"``, more than one rank or ``sharded_input=True``, and
+``predict`` / ``predict_proba`` of a classifier fitted with ``vertical_growth=True``.
 """
 from __future__ import annotations
 
@@ -38,17 +50,20 @@ from sklearn.utils import check_array, check_random_state
 from sklearn.utils.validation import check_is_fitted
 
 from . import schedule
-from .backend import RESIDENT, HotPathBackend, dist_info, is_sparse, shard_bounds
+from .backend import (RESIDENT, HotPathBackend, array_namespace, dist_info, dtype_name, is_device_array, is_sparse,
+                      shard_bounds)
 from .lattice import GrowingLattice
 
 
 class DeviceSamples:
-    """Samples that live in HBM only (a Voronoi subset gathered on the device): what ``fit`` and
-    ``predict`` see in place of a NumPy array.  Carries shape and dtype; rows are fetched on
-    demand."""
+    """Samples that live in HBM only (a Voronoi subset gathered on the device, or the caller's device array
+    adopted by ``load_device``): what ``fit`` and ``predict`` see in place of a NumPy array.  Carries shape and
+    dtype; rows are fetched on demand.  ``source``: the caller's validated device array, kept alive (and, when
+    borrowed, read in place) for as long as the fit runs; None for a subset."""
 
-    def __init__(self, backend):
+    def __init__(self, backend, source=None):
         self.backend = backend
+        self.source = source
         self.shape = (backend.n_samples, backend._d)
         self.dtype = backend._x_np_dtype if not isinstance(backend._x_np_dtype, str) else np.dtype(np.float32)
         self.ndim = 2
@@ -162,7 +177,13 @@ class BaseSom(BaseEstimator):
         behind gamma, the "se" threshold and the start rows use ``np.nanvar`` / ``np.nanstd(ddof=1)`` /
         ``np.nanmean`` for the start rows' holes.  Refused (``ValueError``): an infinity, a row without any
         observed entry, a column with fewer than two observed values, ``sample_weight``,
-        ``vertical_growth=True``, ``sharded_input`` or more than one rank, sparse X with a stored NaN."""
+        ``vertical_growth=True``, ``sharded_input`` or more than one rank, sparse X with a stored NaN.
+
+        X may be a device array (a ``torch.Tensor`` on the estimator's GPU, complete rows): the fit is the fit on
+        ``X.cpu().numpy()`` bit for bit and X never crosses PCIe.  A float32 / float64 tensor of a multiple of 16
+        features with contiguous rows and a 16-byte aligned base is read in place for the whole fit: do not write
+        to it until ``fit`` returns.  ``y`` and ``sample_weight`` may be host arrays or tensors (they go to the
+        host)."""
         self._accepts_nan()   # (validates the parameter)
         self._incomplete_fit = False
         if isinstance(X, DeviceSamples):   # a Voronoi subset that already lives in HBM (f-4)
@@ -179,6 +200,13 @@ class BaseSom(BaseEstimator):
             self.classes_ = np.array(classes)
         self.random_state_ = check_random_state(self.random_state)
         engine = self._engine()
+        if is_device_array(X):
+            # rows that are in HBM already: adopted where they are (or pad-copied on the device), and from here on
+            # the fit is the one vertical-growth children run on their device subsets
+            if not hasattr(engine, "load_device"):
+                raise TypeError(f"the {engine.name} backend takes host arrays only: pass X.cpu().numpy()")
+            engine.load_device(X)
+            X = DeviceSamples(engine, source=X)
         self._load_resident(X)  # samples go to HBM once and stay there for the whole fit
         try:
             self._attach_sample_weight(X, sample_weight)
@@ -211,7 +239,7 @@ class BaseSom(BaseEstimator):
 
     def _check_incomplete_fit(self, X, sample_weight) -> bool:
         """Whether this fit runs in incomplete mode; its refusals, on the host before anything is uploaded."""
-        if not self._fits_nan() or is_sparse(X):
+        if not self._fits_nan() or is_sparse(X) or is_device_array(X):   # (a device array is complete: validated)
             return False
         holes = np.isnan(X)
         if not holes.any():
@@ -233,6 +261,9 @@ class BaseSom(BaseEstimator):
     def _check_fit_array(self, X, y=None, supervised=False):
         """check_array / check_X_y of fit's X.  ``missing_values="nan-fit"``: NaN passes in dense X, an infinity
         never does, and the finite check is not deferred to the device."""
+        if is_device_array(X):
+            X = self._check_device_array(X, fit=True)
+            return X, (self._check_device_y(X, y) if supervised else None)
         kw = dict(ensure_min_samples=4, dtype=[np.float64, np.float32], accept_sparse="csr")
         if self._fits_nan():
             self._finite_deferred = False
@@ -246,6 +277,97 @@ class BaseSom(BaseEstimator):
 
         return check_X_y(X=X, y=y, **kw)
 
+    # -- device arrays: the counterpart of check_array, with the array's own operations on its device ----------
+    def _host(self, a) -> np.ndarray:
+        """A small per-row array (y, sample_weight, winners ...) on the host, whatever it was handed over as."""
+        if is_device_array(a):
+            engine = self._engine()
+            return engine.fetch(a) if hasattr(engine, "fetch") else np.asarray(a.cpu())
+        if hasattr(a, "detach") and hasattr(a, "numpy"):   # a CPU tensor
+            return a.detach().numpy()
+        return a
+
+    def _like(self, a, like):
+        """The host array `a` as an array next to the device array `like`."""
+        engine = self._engine()
+        if hasattr(engine, "put"):
+            return engine.put(a, like)
+        return array_namespace(like).asarray(np.ascontiguousarray(a), device=like.device)
+
+    _HOST_ARRAY = "pass a host array instead (X.cpu().numpy())"
+
+    def _check_device_array(self, X, fit: bool):
+        """Validate rows that live in GPU memory (``backend.is_device_array``) -> the array the backend is handed:
+        2-D, at least 4 rows for ``fit`` and 1 for a query, the fitted feature count for a query; float32 / float64
+        kept, float16 / bfloat16 widened with ``.float()``, integers and bool with ``.double()``; unit column
+        stride (``.contiguous()`` otherwise); finite.  Refusals come first, before anything is launched."""
+        name = type(self).__name__
+        layout = str(getattr(X, "layout", "strided"))
+        if getattr(X, "is_sparse", False) or not layout.endswith("strided"):
+            raise TypeError(f"{name} takes dense device arrays only; for sparse rows pass a host array instead "
+                            "(a scipy CSR matrix)")
+        if self.sharded_input or dist_info()[1] > 1:
+            raise ValueError(f"device arrays take one process: no sharded_input, no process group of more than one "
+                             f"rank; {self._HOST_ARRAY}")
+        engine = self._engine()
+        index, mine = getattr(X.device, "index", None), getattr(engine, "device_index", None)
+        if index is not None and mine is not None and index != mine:
+            raise ValueError(f"X lives on GPU {index}, this estimator runs on GPU {mine}: move it there, or "
+                             f"{self._HOST_ARRAY}")
+        if len(X.shape) != 2:
+            raise ValueError(f"Expected 2D array, got {len(X.shape)}D array instead (shape={tuple(X.shape)})")
+        n, d = int(X.shape[0]), int(X.shape[1])
+        need = 4 if fit else 1
+        if n < need:
+            raise ValueError(f"Found array with {n} sample(s) (shape={(n, d)}) while a minimum of {need} is required.")
+        if d < 1:
+            raise ValueError(f"Found array with {d} feature(s) (shape={(n, d)}) while a minimum of 1 is required.")
+        if not fit and d != self.n_features_in_:
+            raise ValueError(f"X has {d} features, but {name} is expecting {self.n_features_in_} features as input")
+        dt = dtype_name(X)
+        if dt in ("float16", "bfloat16"):
+            X = X.float()          # exact; an N x d x 4 byte copy on the device
+        elif dt.startswith(("int", "uint", "bool")):
+            X = X.double()         # as check_array converts integer input
+        elif dt not in ("float32", "float64"):
+            raise TypeError(f"device arrays of dtype {dt} are not supported; {self._HOST_ARRAY}")
+        if X.stride(1) != 1 or (n > 1 and X.stride(0) < d):
+            X = X.contiguous()
+        if fit and not self._fits_nan() and self._finite_check_on_device():
+            self._finite_deferred = True   # rides on the device's column sums (_assert_finite_from_moments)
+        else:
+            self._finite_deferred = False
+            self._device_assert_finite(X)
+        return X
+
+    def _device_assert_finite(self, X) -> None:
+        """sklearn's "no NaN, no infinity" on a device array: one reduction on the device, its ValueError."""
+        ns = array_namespace(X)
+        if bool(ns.isfinite(X).all()):
+            return
+        has_nan = bool(ns.isnan(X).any())
+        if has_nan and self._accepts_nan():
+            raise ValueError(f"X holds NaN: rows with missing entries (missing_values={self.missing_values!r}) are "
+                             f"taken from host arrays only; {self._HOST_ARRAY}")
+        from sklearn.utils import assert_all_finite
+
+        np_dtype = np.float32 if dtype_name(X) == "float32" else np.float64
+        assert_all_finite(np.array([np.nan if has_nan else np.inf], dtype=np_dtype))   # (raises, in sklearn's words)
+
+    def _check_device_y(self, X, y) -> np.ndarray:
+        """What check_X_y does for y next to a device array X: y on the host, 1-D, finite, one per row."""
+        from sklearn.utils import assert_all_finite, column_or_1d
+
+        if y is None:
+            raise ValueError(f"{type(self).__name__} requires y to be passed, but the target y is None")
+        y = column_or_1d(np.asarray(self._host(y)), warn=True)
+        if y.dtype.kind in "fc":
+            assert_all_finite(y, input_name="y")
+        if y.shape[0] != X.shape[0]:
+            raise ValueError(f"Found input variables with inconsistent numbers of samples: "
+                             f"{[int(X.shape[0]), int(y.shape[0])]}")
+        return y
+
     # -- sample weights -------------------------------------------------------------------------
     _sw = None          # the weights of the rows handed to fit (None: unweighted), aligned with X as passed
     _sw_global = None   # the weights of all rows of all ranks (differs from _sw with sharded_input only)
@@ -258,13 +380,16 @@ class BaseSom(BaseEstimator):
             return None
         from sklearn.utils.validation import _check_sample_weight
 
-        w = _check_sample_weight(sample_weight, X, dtype=np.float64, ensure_non_negative=True)
+        w = _check_sample_weight(self._host(sample_weight), X, dtype=np.float64, ensure_non_negative=True)
         if getattr(self, "_finite_deferred", False):
             # (the finite check that rides on the device's column sums does not see rows of weight 0)
             from sklearn.utils import assert_all_finite
 
             self._finite_deferred = False
-            assert_all_finite(X)
+            if is_device_array(X):
+                self._device_assert_finite(X)
+            else:
+                assert_all_finite(X)
         return np.ascontiguousarray(w, dtype=np.float64)
 
     def _attach_sample_weight(self, X, w) -> None:
@@ -438,6 +563,9 @@ class BaseSom(BaseEstimator):
             return
         self._finite_deferred = False
         if mom is None or not (np.isfinite(mom[0]).all() and np.isfinite(mom[1]).all()):
+            if isinstance(X, DeviceSamples):   # the caller's device array: the same check, on the device
+                self._device_assert_finite(X.source)
+                return
             from sklearn.utils import assert_all_finite
 
             assert_all_finite(X)
@@ -501,7 +629,7 @@ class BaseSom(BaseEstimator):
             self._col_s2 = self._all_reduce_f64(((loc - mean) ** 2).sum(axis=0)).astype(data.dtype)
         elif self._shard == (0, data.shape[0]) and hasattr(engine, "column_moments"):
             mom = engine.column_moments()
-            if not on_device:
+            if not on_device or data.source is not None:
                 self._assert_finite_from_moments(data, mom)
             if mom is not None:
                 self._col_s2 = mom[1]
@@ -725,6 +853,14 @@ class BaseSom(BaseEstimator):
         return np.concatenate([p.cpu().numpy()[: hi - lo] for p, (lo, hi) in zip(parts, bounds)],
                               axis=0)
 
+    def _resident_winners(self, data) -> np.ndarray:
+        """The winners of the resident samples on the host; for rows that live in HBM only, without their
+        distances' trip across PCIe where the backend can."""
+        engine = self._engine()
+        if isinstance(data, DeviceSamples) and hasattr(engine, "resident_winners"):
+            return engine.resident_winners(self.weights_)
+        return self._get_winning_neurons(data, n_bmu=1)[1]
+
     def _get_winning_neurons(self, data, n_bmu: int):
         """Distances and indices of the n_bmu best matching units (BaseSom.py:446-464)."""
         engine = self._engine()
@@ -752,6 +888,8 @@ class BaseSom(BaseEstimator):
     def _check_query(self, X, accept_sparse="csr"):
         """check_array of a query: float32 kept, anything else float64; with ``missing_values="nan"`` NaN passes in
         dense X (infinities never do, and a NaN among the stored entries of sparse X is refused as ever)."""
+        if is_device_array(X):
+            return self._check_device_array(X, fit=False)
         if not self._accepts_nan():
             return check_array(X, dtype=[np.float64, np.float32], accept_sparse=accept_sparse)
         X = check_array(X, dtype=[np.float64, np.float32], accept_sparse=accept_sparse, **self._finite_kw("allow-nan"))
@@ -851,7 +989,8 @@ class BaseSom(BaseEstimator):
             return self._engine().quantization_error(self.weights_)
         X = self._check_query(X)
         distances, _ = self._get_winning_neurons(X, n_bmu=1)
-        return float(np.mean(distances))
+        # (a device array's distances go to the host for the mean: NumPy's pairwise sum, bit for bit -- N x 8 bytes)
+        return float(np.mean(self._host(distances)))
 
     def _calculate_topographic_error(self, X) -> float:
         """Fraction of samples whose two best matching units are not lattice neighbours."""
@@ -936,7 +1075,7 @@ class BaseSom(BaseEstimator):
         dense M x M matrix is kept on the estimator (``want_distances=True`` on the backend gives D).
         Dense X only: sparse X raises ``TypeError``."""
         check_is_fitted(self)
-        X = check_array(X, dtype=[np.float64, np.float32])
+        X = self._check_device_array(X, fit=False) if is_device_array(X) else check_array(X, dtype=[np.float64, np.float32])
         if X.shape[1] != self.n_features_in_:
             raise ValueError(f"X has {X.shape[1]} features, but {type(self).__name__} is expecting "
                              f"{self.n_features_in_} features as input")
@@ -979,6 +1118,9 @@ class BaseSom(BaseEstimator):
         # (sparse X: the host-subset branch -- X[winners == j] is CSR row selection)
         on_device = self._is_resident(X) and hasattr(engine, "subset") and dist_info()[1] == 1 and not is_sparse(X)
         sw = self._sw
+        if isinstance(X, DeviceSamples) and not on_device:
+            raise ValueError("vertical_growth=True on device rows needs a backend that gathers Voronoi subsets on the "
+                             "device and one process; " + self._HOST_ARRAY)
         if on_device:
             counts, winners = engine.partition(self.weights_, want_winners=y is not None or sw is not None)
         else:

@@ -337,6 +337,12 @@ struct dbgsom_ctx {
     // traffic of the prototypes across PCIe (f-4 evidence: whole matrices only at the first epoch, at
     // growth steps and at the end of a fit)
     int64_t w_up_calls = 0, w_up_bytes = 0, w_down_calls = 0, w_down_bytes = 0, w_row_writes = 0, w_row_reads = 0;
+    // traffic of the samples across PCIe: rows host -> HBM (loads, query placements, the chunks of the coder and of
+    // the masked search) and per-row results HBM -> host (winners, distances, codes, probabilities, filled rows).
+    // Rows that are in HBM already (dbgsom_ctx_load_device, the *_device queries) move neither.
+    int64_t x_up_bytes = 0, x_up_calls = 0, x_down_bytes = 0;
+    void x_up(size_t bytes) { x_up_bytes += (int64_t)bytes; ++x_up_calls; }
+    void x_down(size_t bytes) { x_down_bytes += (int64_t)bytes; }
     // timing
     hipEvent_t ev[4] = {};
     bool ev_created = false, ev_valid = false;
@@ -437,7 +443,56 @@ int place_host_samples(dbgsom_ctx *c, Samples &s, const void *X_host, int x_dtyp
         TRY(upload_padded(c, s.own.p, X_host, N, d, dp, es));
     }
     s.X = s.own.p;
+    c->x_up((size_t)N * d * dtype_size(x_dtype));
     return finish_samples(c, s, widened);
+}
+
+// rows that already live in HBM on the context's device (ldx elements apart): borrowed when they are what the kernels
+// want -- rows of a multiple of 16 features, contiguous, 16-byte aligned --, else copied (padded) into s.own on the
+// device.  A borrowed s.X is the caller's memory: whoever places a query this way clears it before returning.
+bool device_rows_conform(const void *X_dev, int64_t d, int64_t ldx) {
+    return ldx == pad16(d) && d == ldx && is_aligned(X_dev, 16);
+}
+
+int place_device_samples(dbgsom_ctx *c, Samples &s, const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx) {
+    DBGSOM_REQUIRE(valid_dtype(x_dtype), "x_dtype must be DBGSOM_F32/F64/BF16");
+    DBGSOM_REQUIRE(X_dev && N >= 1 && d >= 1 && ldx >= d && N < 0x7fffffff, "bad samples");
+    const size_t es = dtype_size(x_dtype);
+    const int64_t dp = pad16(d);
+    s.dtype = -1;
+    s.N = N; s.d = d; s.dp = dp;
+    s.csr = false; s.nnz = 0;
+    s.indptr.release(); s.indices.release(); s.data.release();
+    if (device_rows_conform(X_dev, d, ldx)) {
+        s.own.release();
+        s.X = X_dev;  // borrowed
+    } else {
+        TRY(s.own.reserve((size_t)N * dp * es));
+        if (d != dp) DBGSOM_HIP_CHECK(hipMemsetAsync(s.own.p, 0, (size_t)N * dp * es, c->stream));
+        DBGSOM_HIP_CHECK(hipMemcpy2DAsync(s.own.p, (size_t)dp * es, X_dev, (size_t)ldx * es, (size_t)d * es, (size_t)N,
+                                          hipMemcpyDeviceToDevice, c->stream));
+        s.X = s.own.p;
+    }
+    s.dtype = x_dtype;
+    return finish_samples(c, s, false);
+}
+
+// The rows of a query: a host pointer (Nq x d, contiguous) or a device pointer (rows ldx elements apart).
+struct QueryRows {
+    const void *p;
+    bool on_device;
+    int64_t ldx;
+};
+
+int place_query_rows(dbgsom_ctx *c, Samples &s, const QueryRows &q, int x_dtype, int64_t Nq, int64_t d) {
+    if (q.on_device) return place_device_samples(c, s, q.p, x_dtype, Nq, d, q.ldx);
+    return place_host_samples(c, s, q.p, x_dtype, Nq, d, x_dtype);
+}
+
+// after a query: nothing of the caller's stays referenced, and a large one-off batch is not sat on
+void drop_query_rows(Samples &s, const QueryRows &q, int64_t held_bytes) {
+    if (q.on_device && s.X != s.own.p) { s.X = s.Xb = nullptr; s.dtype = -1; s.drop_planes(); }
+    if (held_bytes > ((int64_t)256 << 20)) s.release();
 }
 
 int ensure_planes(dbgsom_ctx *c, Samples &s) {
@@ -1242,6 +1297,9 @@ int dbgsom_ctx_get_option(dbgsom_ctx *c, const char *name, int64_t *v) {
     else if (!strcmp(name, "w_download_bytes")) *v = c->w_down_bytes;
     else if (!strcmp(name, "w_row_writes")) *v = c->w_row_writes;
     else if (!strcmp(name, "w_row_reads")) *v = c->w_row_reads;
+    else if (!strcmp(name, "x_upload_bytes")) *v = c->x_up_bytes;
+    else if (!strcmp(name, "x_upload_calls")) *v = c->x_up_calls;
+    else if (!strcmp(name, "x_download_bytes")) *v = c->x_down_bytes;
     else if (!strcmp(name, "device_bytes")) {
         size_t tot = 0;
         for (const Samples *q : {&c->xs, &c->xq})
@@ -1312,6 +1370,7 @@ int dbgsom_ctx_load_csr(dbgsom_ctx *c, const int64_t *indptr_host, const int32_t
     int rc = place_host_csr(c, c->xs, indptr_host, indices_host, data_host, x_dtype, N, d, nnz, c->csr_densify_below);
     if (rc == DBGSOM_OK) rc = sync(c);
     if (rc != DBGSOM_OK) { (void)hipStreamSynchronize(c->stream); c->xs.dtype = -1; c->xs.csr = false; }
+    else c->x_up((size_t)nnz * (4 + dtype_size(x_dtype)) + (size_t)(N + 1) * 8);
     return rc;
 }
 
@@ -1322,24 +1381,7 @@ int dbgsom_ctx_load_device(dbgsom_ctx *c, const void *X_dev, int x_dtype, int64_
     reset_training_state(c);
     set_tight(c, false);
     Samples &s = c->xs;
-    const size_t es = dtype_size(x_dtype);
-    const int64_t dp = pad16(d);
-    s.dtype = -1;
-    s.N = N; s.d = d; s.dp = dp;
-    s.csr = false; s.nnz = 0;
-    s.indptr.release(); s.indices.release(); s.data.release();
-    if (ldx == dp && d == dp && is_aligned(X_dev, 16)) {
-        s.own.release();
-        s.X = X_dev;  // borrowed
-    } else {
-        TRY(s.own.reserve((size_t)N * dp * es));
-        if (d != dp) DBGSOM_HIP_CHECK(hipMemsetAsync(s.own.p, 0, (size_t)N * dp * es, c->stream));
-        DBGSOM_HIP_CHECK(hipMemcpy2DAsync(s.own.p, (size_t)dp * es, X_dev, (size_t)ldx * es, (size_t)d * es, (size_t)N,
-                                          hipMemcpyDeviceToDevice, c->stream));
-        s.X = s.own.p;
-    }
-    s.dtype = x_dtype;
-    const int rc = finish_samples(c, s, false);
+    const int rc = place_device_samples(c, s, X_dev, x_dtype, N, d, ldx);
     if (rc != DBGSOM_OK) { (void)hipStreamSynchronize(c->stream); s.dtype = -1; return rc; }
     return sync(c);
 }
@@ -1581,37 +1623,53 @@ int dbgsom_ctx_bmu(dbgsom_ctx *c, const double *W_host, int64_t M, int k, int ro
     CTX_CHECK(c);
     TRY(loaded(c, __func__));
     TRY(complete_rows(c, __func__));
-    DBGSOM_REQUIRE(idx_host && dist_host && (k == 1 || k == 2), "bad arguments");
+    DBGSOM_REQUIRE(idx_host && (k == 1 || k == 2), "bad arguments");
     DBGSOM_REQUIRE(M >= k, "need k <= M");
     TRY(resident_bmu(c, W_host, M, k, round_f32));
     DBGSOM_HIP_CHECK(hipMemcpyAsync(idx_host, c->qidx.p, (size_t)c->xs.N * k * 8, hipMemcpyDeviceToHost, c->stream));
-    DBGSOM_HIP_CHECK(hipMemcpyAsync(dist_host, c->qdist.p, (size_t)c->xs.N * k * 8, hipMemcpyDeviceToHost, c->stream));
+    c->x_down((size_t)c->xs.N * k * 8);
+    if (dist_host) {
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(dist_host, c->qdist.p, (size_t)c->xs.N * k * 8, hipMemcpyDeviceToHost, c->stream));
+        c->x_down((size_t)c->xs.N * k * 8);
+    }
     return sync(c);
 }
 
-// the query search on host samples: dense rows (Xq_host), or CSR arrays (indptr_host != nullptr)
-static int bmu_query_impl(dbgsom_ctx *c, const void *Xq_host, const int64_t *indptr_host, const int32_t *indices_host,
+// the query search on samples that are not resident: dense rows from the host or from HBM (q), or CSR arrays from
+// the host (indptr_host != nullptr, q.p = their data).  Rows from the host: idx_out / dist_out are host arrays,
+// filled by a copy behind the search.  Rows in HBM: they are device arrays and the search writes them itself.
+static int bmu_query_impl(dbgsom_ctx *c, const QueryRows &q, const int64_t *indptr_host, const int32_t *indices_host,
                           int64_t nnz, int x_dtype, int64_t Nq, int64_t d, const double *W_host, int64_t M, int k,
-                          int round_f32, int64_t *idx_host, double *dist_host) {
+                          int round_f32, int64_t *idx_out, double *dist_out) {
     Samples &s = c->xq;
     DevBuf Wq, wwq, iq, dq, fws, wtq;  // query-sized scratch; independent of the training state
     int rc = DBGSOM_OK;
     const int64_t dp = pad16(d);
     do {
-        if (indptr_host) rc = place_host_csr(c, s, indptr_host, indices_host, Xq_host, x_dtype, Nq, d, nnz, c->csr_densify_below);
-        else rc = place_host_samples(c, s, Xq_host, x_dtype, Nq, d, x_dtype);
+        if (indptr_host) {
+            rc = place_host_csr(c, s, indptr_host, indices_host, q.p, x_dtype, Nq, d, nnz, c->csr_densify_below);
+            if (rc == DBGSOM_OK) c->x_up((size_t)nnz * (4 + dtype_size(x_dtype)) + (size_t)(Nq + 1) * 8);
+        } else {
+            rc = place_query_rows(c, s, q, x_dtype, Nq, d);
+        }
         if (rc) break;
         if ((rc = Wq.reserve((size_t)M * dp * 8))) break;
         if ((rc = wwq.reserve((size_t)M * 8))) break;
-        if ((rc = iq.reserve((size_t)Nq * k * 8))) break;
-        if ((rc = dq.reserve((size_t)Nq * k * 8))) break;
+        int64_t *idx_dev = idx_out;
+        double *dist_dev = dist_out;
+        if (!q.on_device) {
+            if ((rc = iq.reserve((size_t)Nq * k * 8))) break;
+            if ((rc = dq.reserve((size_t)Nq * k * 8))) break;
+            idx_dev = iq.as<int64_t>();
+            dist_dev = dq.as<double>();
+        }
         if ((rc = upload_padded(c, Wq.p, W_host, M, d, dp, 8))) break;
         if ((rc = launch_row_sqnorms(Wq.p, DBGSOM_F64, M, dp, dp, wwq.as<double>(), c->stream))) break;
         // large k = 1 queries go through the filter (the digit planes of a one-off X cost a pass over it)
         const bool filt = !s.csr && k == 1 && c->policy.algorithm != DBGSOM_ALG_EXACT && Nq >= c->filter_min_query_rows &&
                           filter_shape_ok(s, M);
         if (s.csr) {
-            rc = csr_search(c, s, Wq.as<double>(), wwq.as<double>(), wtq, M, k, round_f32, iq.as<int64_t>(), dq.as<double>());
+            rc = csr_search(c, s, Wq.as<double>(), wwq.as<double>(), wtq, M, k, round_f32, idx_dev, dist_dev);
         } else if (filt) {
             if ((rc = ensure_planes(c, s))) break;
             if ((rc = fws.reserve_zeroed(dbgsom_bmu_filtered_workspace_bytes(Nq, dp, M), c->stream))) break;
@@ -1619,21 +1677,25 @@ static int bmu_query_impl(dbgsom_ctx *c, const void *Xq_host, const int64_t *ind
             c->policy.query_args(M, &stride, &planes);
             rc = dbgsom_bmu_filtered(s.Xb, s.bdtype, Nq, dp, dp, s.xx.as<double>(), s.planes.p, Wq.as<double>(), M,
                                      wwq.as<double>(), nullptr, nullptr, stride, planes, round_f32,
-                                     iq.as<int64_t>(), dq.as<double>(), fws.p, fws.cap, c->stream);
+                                     idx_dev, dist_dev, fws.p, fws.cap, c->stream);
         } else {
             rc = launch_bmu(s.Xb, s.bdtype, Nq, dp, dp, s.xx.as<double>(), Wq.as<double>(), M, wwq.as<double>(), k,
-                            round_f32, iq.as<int64_t>(), dq.as<double>(), c->stream);
+                            round_f32, idx_dev, dist_dev, c->stream);
         }
         if (rc) break;
-        hipError_t e = hipMemcpyAsync(idx_host, iq.p, (size_t)Nq * k * 8, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dist_host, dq.p, (size_t)Nq * k * 8, hipMemcpyDeviceToHost, c->stream);
+        hipError_t e = hipSuccess;
+        if (!q.on_device) {
+            e = hipMemcpyAsync(idx_out, iq.p, (size_t)Nq * k * 8, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(dist_out, dq.p, (size_t)Nq * k * 8, hipMemcpyDeviceToHost, c->stream);
+            c->x_down((size_t)Nq * k * 16);
+        }
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; }
     } while (0);
     if (rc != DBGSOM_OK) (void)hipStreamSynchronize(c->stream);
     Wq.release(); wwq.release(); iq.release(); dq.release(); fws.release(); wtq.release();
     const int64_t held = s.csr ? s.nnz * (4 + (int64_t)dtype_size(x_dtype)) + Nq * 16 : Nq * dp * (int64_t)dtype_size(x_dtype);
-    if (held > ((int64_t)256 << 20)) s.release();  // do not sit on a large one-off batch
+    drop_query_rows(s, q, held);
     return rc;
 }
 
@@ -1644,7 +1706,20 @@ int dbgsom_ctx_bmu_query(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_
     DBGSOM_REQUIRE(Xq_host && W_host && idx_host && dist_host && Nq >= 0 && d >= 1 && M >= 1 && (k == 1 || k == 2) && M >= k,
                    "bad arguments");
     if (Nq == 0) return DBGSOM_OK;
-    return bmu_query_impl(c, Xq_host, nullptr, nullptr, 0, x_dtype, Nq, d, W_host, M, k, round_f32, idx_host, dist_host);
+    return bmu_query_impl(c, QueryRows{Xq_host, false, d}, nullptr, nullptr, 0, x_dtype, Nq, d, W_host, M, k, round_f32,
+                          idx_host, dist_host);
+}
+
+int dbgsom_ctx_bmu_query_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d, int64_t ldx,
+                                const double *W_host, int64_t M, int k, int round_f32, int64_t *idx_dev, double *dist_dev) {
+    CTX_CHECK(c);
+    DBGSOM_REQUIRE(valid_dtype(x_dtype), "x_dtype must be DBGSOM_F32/F64/BF16");
+    DBGSOM_REQUIRE(Xq_dev && W_host && idx_dev && dist_dev && Nq >= 0 && d >= 1 && ldx >= d && M >= 1 &&
+                       (k == 1 || k == 2) && M >= k,
+                   "bad arguments");
+    if (Nq == 0) return DBGSOM_OK;
+    return bmu_query_impl(c, QueryRows{Xq_dev, true, ldx}, nullptr, nullptr, 0, x_dtype, Nq, d, W_host, M, k, round_f32,
+                          idx_dev, dist_dev);
 }
 
 int dbgsom_ctx_bmu_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const int32_t *indices_host, const void *data_host,
@@ -1655,8 +1730,8 @@ int dbgsom_ctx_bmu_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const in
     DBGSOM_REQUIRE(indptr_host && W_host && idx_host && dist_host && Nq >= 0 && d >= 1 && nnz >= 0 && M >= 1 &&
                    (k == 1 || k == 2) && M >= k, "bad arguments");
     if (Nq == 0) return dbgsom_csr_check(indptr_host, indices_host, 0, d, nnz);
-    return bmu_query_impl(c, data_host, indptr_host, indices_host, nnz, x_dtype, Nq, d, W_host, M, k, round_f32, idx_host,
-                          dist_host);
+    return bmu_query_impl(c, QueryRows{data_host, false, d}, indptr_host, indices_host, nnz, x_dtype, Nq, d, W_host, M, k,
+                          round_f32, idx_host, dist_host);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1706,6 +1781,8 @@ int dbgsom_ctx_bmu_query_masked(dbgsom_ctx *c, const void *Xq_host, int x_dtype,
             e = hipMemcpyAsync(c->mk_x.p, static_cast<const char *>(Xq_host) + (size_t)r0 * d * es, (size_t)n * d * es,
                                hipMemcpyHostToDevice, c->stream);
             if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
+            c->x_up((size_t)n * d * es);
+            c->x_down((size_t)n * k * 16 + (Xfilled_host ? (size_t)n * d * es : 0));
             if ((rc = launch_bmu_masked_rows(c->mk_x.p, x_dtype, n, d, d, M, k, c->mk_idx.as<int64_t>(),
                                              c->mk_dist.as<double>(), c->mk_ws.p, c->mk_ws.cap, c->stream)))
                 break;
@@ -1736,14 +1813,13 @@ int dbgsom_ctx_bmu_query_masked(dbgsom_ctx *c, const void *Xq_host, int x_dtype,
 // ------------------------------------------------------------------------------------------
 // sparse coding (transform / predict_proba): csrc/sparse_code.hip, in chunks of query rows
 // ------------------------------------------------------------------------------------------
-int dbgsom_ctx_sparse_code(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
-                           const double *W_host, int64_t M, int max_iter, const double *P_host, int64_t C,
-                           double *code_host, double *proba_host, uint64_t *counts_host) {
-    CTX_CHECK(c);
-    DBGSOM_REQUIRE(x_dtype == DBGSOM_F32 || x_dtype == DBGSOM_F64, "x_dtype must be DBGSOM_F32 or DBGSOM_F64");
-    DBGSOM_REQUIRE(counts_host && Nq >= 0 && d >= 1 && M >= 1 && max_iter >= 0 && (Nq == 0 || Xq_host),
-                   "bad arguments");
-    DBGSOM_REQUIRE(!proba_host || (P_host && C >= 1), "proba_host needs P_host and C >= 1");
+// Rows from the host (q.on_device false): every chunk is staged in sc_x, coded into sc_code / sc_proba and copied to
+// the host arrays code_host / proba_host.  Rows in HBM: the coder walks them where they are, q.ldx elements apart,
+// and writes the caller's device arrays (code_host / proba_host are then device pointers) chunk by chunk.
+static int sparse_code_impl(dbgsom_ctx *c, const QueryRows &q, int x_dtype, int64_t Nq, int64_t d,
+                            const double *W_host, int64_t M, int max_iter, const double *P_host, int64_t C,
+                            double *code_host, double *proba_host, uint64_t *counts_host) {
+    const void *Xq_host = q.p;
     int64_t ldw = d;
     const double *Wd = nullptr;
     if (W_host) {
@@ -1768,6 +1844,17 @@ int dbgsom_ctx_sparse_code(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int6
     const int64_t chunk = std::min<int64_t>(std::max<int64_t>(Nq, 1), c->sc_chunk_rows);
     const size_t es = dtype_size(x_dtype);
     TRY(c->sc_ws.reserve(dbgsom_sparse_code_workspace_bytes(chunk, d, M, max_iter)));
+    if (q.on_device) {
+        for (int64_t r0 = 0; r0 < Nq; r0 += chunk) {
+            const int64_t n = std::min(chunk, Nq - r0);
+            TRY(dbgsom_sparse_code(static_cast<const char *>(q.p) + (size_t)r0 * q.ldx * es, x_dtype, n, d, q.ldx, Wd, M, ldw,
+                                   max_iter, (int)c->sc_cap, proba_host ? c->sc_p.as<double>() : nullptr, C,
+                                   code_host ? code_host + r0 * M : nullptr, proba_host ? proba_host + r0 * C : nullptr,
+                                   c->sc_cnt.as<uint64_t>(), c->sc_ws.p, c->sc_ws.cap, c->stream));
+        }
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(counts_host, c->sc_cnt.p, DBGSOM_SC_COUNTS * 8, hipMemcpyDeviceToHost, c->stream));
+        return sync(c);
+    }
     TRY(c->sc_x.reserve((size_t)chunk * d * es));
     if (code_host) TRY(c->sc_code.reserve((size_t)chunk * M * 8));
     if (proba_host) TRY(c->sc_proba.reserve((size_t)chunk * C * 8));
@@ -1775,34 +1862,58 @@ int dbgsom_ctx_sparse_code(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int6
         const int64_t n = std::min(chunk, Nq - r0);
         DBGSOM_HIP_CHECK(hipMemcpyAsync(c->sc_x.p, static_cast<const char *>(Xq_host) + (size_t)r0 * d * es,
                                         (size_t)n * d * es, hipMemcpyHostToDevice, c->stream));
+        c->x_up((size_t)n * d * es);
         TRY(dbgsom_sparse_code(c->sc_x.p, x_dtype, n, d, d, Wd, M, ldw, max_iter, (int)c->sc_cap,
                                proba_host ? c->sc_p.as<double>() : nullptr, C,
                                code_host ? c->sc_code.as<double>() : nullptr,
                                proba_host ? c->sc_proba.as<double>() : nullptr, c->sc_cnt.as<uint64_t>(), c->sc_ws.p,
                                c->sc_ws.cap, c->stream));
-        if (code_host)
+        if (code_host) {
             DBGSOM_HIP_CHECK(hipMemcpyAsync(code_host + r0 * M, c->sc_code.p, (size_t)n * M * 8, hipMemcpyDeviceToHost,
                                             c->stream));
-        if (proba_host)
+            c->x_down((size_t)n * M * 8);
+        }
+        if (proba_host) {
             DBGSOM_HIP_CHECK(hipMemcpyAsync(proba_host + r0 * C, c->sc_proba.p, (size_t)n * C * 8,
                                             hipMemcpyDeviceToHost, c->stream));
+            c->x_down((size_t)n * C * 8);
+        }
     }
     DBGSOM_HIP_CHECK(hipMemcpyAsync(counts_host, c->sc_cnt.p, DBGSOM_SC_COUNTS * 8, hipMemcpyDeviceToHost, c->stream));
     return sync(c);
+}
+
+int dbgsom_ctx_sparse_code(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                           const double *W_host, int64_t M, int max_iter, const double *P_host, int64_t C,
+                           double *code_host, double *proba_host, uint64_t *counts_host) {
+    CTX_CHECK(c);
+    DBGSOM_REQUIRE(x_dtype == DBGSOM_F32 || x_dtype == DBGSOM_F64, "x_dtype must be DBGSOM_F32 or DBGSOM_F64");
+    DBGSOM_REQUIRE(counts_host && Nq >= 0 && d >= 1 && M >= 1 && max_iter >= 0 && (Nq == 0 || Xq_host),
+                   "bad arguments");
+    DBGSOM_REQUIRE(!proba_host || (P_host && C >= 1), "proba_host needs P_host and C >= 1");
+    return sparse_code_impl(c, QueryRows{Xq_host, false, d}, x_dtype, Nq, d, W_host, M, max_iter, P_host, C, code_host,
+                            proba_host, counts_host);
+}
+
+int dbgsom_ctx_sparse_code_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d, int64_t ldx,
+                                  const double *W_host, int64_t M, int max_iter, const double *P_host, int64_t C,
+                                  double *code_dev, double *proba_dev, uint64_t *counts_host) {
+    CTX_CHECK(c);
+    DBGSOM_REQUIRE(x_dtype == DBGSOM_F32 || x_dtype == DBGSOM_F64, "x_dtype must be DBGSOM_F32 or DBGSOM_F64");
+    DBGSOM_REQUIRE(counts_host && Nq >= 0 && d >= 1 && ldx >= d && M >= 1 && max_iter >= 0 && (Nq == 0 || Xq_dev),
+                   "bad arguments");
+    DBGSOM_REQUIRE(!proba_dev || (P_host && C >= 1), "proba_dev needs P_host and C >= 1");
+    return sparse_code_impl(c, QueryRows{Xq_dev, true, ldx}, x_dtype, Nq, d, W_host, M, max_iter, P_host, C, code_dev,
+                            proba_dev, counts_host);
 }
 
 // ------------------------------------------------------------------------------------------
 // topographic function: the k = 2 query search of dbgsom_ctx_bmu_query (k = 2 never takes the
 // filtered form), its pairs left in HBM for csrc/topofn.hip
 // ------------------------------------------------------------------------------------------
-int dbgsom_ctx_topographic_function(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
-                                    const double *W_host, int64_t M, int round_f32, const int32_t *xy_host,
-                                    int64_t n_pos, int64_t *hist_pos_host, int64_t *hist_neg_host, int32_t *D_host) {
-    CTX_CHECK(c);
-    DBGSOM_REQUIRE(x_dtype == DBGSOM_F32 || x_dtype == DBGSOM_F64, "x_dtype must be DBGSOM_F32 or DBGSOM_F64");
-    DBGSOM_REQUIRE(Xq_host && W_host && xy_host && hist_pos_host && hist_neg_host && Nq >= 1 && d >= 1 && M >= 2 &&
-                       M <= DBGSOM_MAX_PROTOTYPES && n_pos >= 1,
-                   "bad arguments");
+static int topographic_function_impl(dbgsom_ctx *c, const QueryRows &q, int x_dtype, int64_t Nq, int64_t d,
+                                     const double *W_host, int64_t M, int round_f32, const int32_t *xy_host,
+                                     int64_t n_pos, int64_t *hist_pos_host, int64_t *hist_neg_host, int32_t *D_host) {
     Samples &s = c->xq;
     DevBuf Wq, wwq, iq, dq, xy, hp, hn, Dd, ws;
     const bool timed = topofn_timing_enabled();
@@ -1816,7 +1927,7 @@ int dbgsom_ctx_topographic_function(dbgsom_ctx *c, const void *Xq_host, int x_dt
             if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
             if (e != hipSuccess) { set_error("timing events: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
         }
-        if ((rc = place_host_samples(c, s, Xq_host, x_dtype, Nq, d, x_dtype))) break;
+        if ((rc = place_query_rows(c, s, q, x_dtype, Nq, d))) break;
         if ((rc = Wq.reserve((size_t)M * dp * 8))) break;
         if ((rc = wwq.reserve((size_t)M * 8))) break;
         if ((rc = iq.reserve((size_t)Nq * 2 * 8))) break;
@@ -1856,8 +1967,33 @@ int dbgsom_ctx_topographic_function(dbgsom_ctx *c, const void *Xq_host, int x_dt
         if (e) (void)hipEventDestroy(e);
     Wq.release(); wwq.release(); iq.release(); dq.release(); xy.release(); hp.release(); hn.release(); Dd.release();
     ws.release();
-    if (Nq * dp * (int64_t)dtype_size(x_dtype) > ((int64_t)256 << 20)) s.release();  // do not sit on a large one-off batch
+    drop_query_rows(s, q, Nq * dp * (int64_t)dtype_size(x_dtype));
     return rc;
+}
+
+int dbgsom_ctx_topographic_function(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                    const double *W_host, int64_t M, int round_f32, const int32_t *xy_host,
+                                    int64_t n_pos, int64_t *hist_pos_host, int64_t *hist_neg_host, int32_t *D_host) {
+    CTX_CHECK(c);
+    DBGSOM_REQUIRE(x_dtype == DBGSOM_F32 || x_dtype == DBGSOM_F64, "x_dtype must be DBGSOM_F32 or DBGSOM_F64");
+    DBGSOM_REQUIRE(Xq_host && W_host && xy_host && hist_pos_host && hist_neg_host && Nq >= 1 && d >= 1 && M >= 2 &&
+                       M <= DBGSOM_MAX_PROTOTYPES && n_pos >= 1,
+                   "bad arguments");
+    return topographic_function_impl(c, QueryRows{Xq_host, false, d}, x_dtype, Nq, d, W_host, M, round_f32, xy_host, n_pos,
+                                     hist_pos_host, hist_neg_host, D_host);
+}
+
+int dbgsom_ctx_topographic_function_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d,
+                                           int64_t ldx, const double *W_host, int64_t M, int round_f32,
+                                           const int32_t *xy_host, int64_t n_pos, int64_t *hist_pos_host,
+                                           int64_t *hist_neg_host, int32_t *D_host) {
+    CTX_CHECK(c);
+    DBGSOM_REQUIRE(x_dtype == DBGSOM_F32 || x_dtype == DBGSOM_F64, "x_dtype must be DBGSOM_F32 or DBGSOM_F64");
+    DBGSOM_REQUIRE(Xq_dev && ldx >= d && W_host && xy_host && hist_pos_host && hist_neg_host && Nq >= 1 && d >= 1 && M >= 2 &&
+                       M <= DBGSOM_MAX_PROTOTYPES && n_pos >= 1,
+                   "bad arguments");
+    return topographic_function_impl(c, QueryRows{Xq_dev, true, ldx}, x_dtype, Nq, d, W_host, M, round_f32, xy_host, n_pos,
+                                     hist_pos_host, hist_neg_host, D_host);
 }
 
 // ------------------------------------------------------------------------------------------

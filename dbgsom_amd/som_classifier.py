@@ -13,7 +13,7 @@ import numpy as np
 from sklearn.base import ClassifierMixin, TransformerMixin
 from sklearn.utils.validation import check_is_fitted
 
-from .backend import is_sparse
+from .backend import is_device_array, is_sparse
 from .base import BaseSom
 
 
@@ -30,7 +30,7 @@ class SomClassifier(BaseSom, TransformerMixin, ClassifierMixin):
     def _label_prototypes(self, X, y) -> None:
         """Majority label and class frequencies of every prototype's Voronoi set
         (SomClassifier.py:130-152); a dead prototype gets label -1."""
-        _, winners = self._get_winning_neurons(X, n_bmu=1)
+        winners = self._resident_winners(X)
         m, n_classes = len(self.neurons_), self.classes_.shape[0]
         hits = self._node_stats["hit_count"]
         labels = np.empty(m, dtype=np.int64)
@@ -62,15 +62,26 @@ class SomClassifier(BaseSom, TransformerMixin, ClassifierMixin):
             probs[j, ids] = counts / hits[j] if hits[j] > 0 else 1
         self._lattice.write_attributes({"label": labels, "probabilities": probs})
 
+    def _refuse_vertical_device_query(self, X) -> None:
+        if self.vertical_growth and is_device_array(X):
+            raise ValueError("predict_proba / predict with vertical_growth=True walk the child maps row by row on the "
+                             "host; " + self._HOST_ARRAY)
+
     def predict(self, X) -> np.ndarray:
+        """The class of the largest probability.  A device array: the arg-max runs on its device and N indices
+        come to the host (class labels need not be numbers: the result is a NumPy array)."""
         check_is_fitted(self)
+        self._refuse_vertical_device_query(X)
         X = self._check_query(X)
+        if is_device_array(X):
+            return self.classes_[self._host(self.predict_proba(X=X).argmax(1))]
         return self.classes_[np.argmax(self.predict_proba(X=X), axis=1)]
 
     def predict_proba(self, X) -> np.ndarray:
         """Class probabilities: sparse code over the prototypes times the prototypes' class
         frequencies, rows normalised (SomClassifier.py:178-220)."""
         check_is_fitted(self)
+        self._refuse_vertical_device_query(X)
         X = self._check_query(X)
         if self.vertical_growth:
             if self._accepts_nan() and isinstance(X, np.ndarray) and np.isnan(X).any():

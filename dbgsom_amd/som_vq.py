@@ -2,6 +2,7 @@
 
 Mirrors ``dbgsom/SomVQ.py`` of the reference (:16-152): ``fit`` / ``predict`` / ``fit_predict``
 (from ``ClusterMixin``) / ``labels_``; a sample's label is the index of its best matching unit.
+``predict`` and ``fit_predict`` of a device array (see ``base``) return an int64 tensor on its device.
 """
 from __future__ import annotations
 
@@ -9,6 +10,7 @@ import numpy as np
 from sklearn.base import ClusterMixin, TransformerMixin
 from sklearn.utils.validation import check_is_fitted
 
+from .backend import is_device_array
 from .base import BaseSom
 
 
@@ -29,10 +31,11 @@ class SomVQ(BaseSom, ClusterMixin, TransformerMixin):
     def predict(self, X) -> np.ndarray:
         """Index of the closest prototype for every sample (SomVQ.py:130-148)."""
         check_is_fitted(self)
-        if not self._is_resident(X):
-            # integer / half input is converted like the reference's engine does (sklearn's
-            # NearestNeighbors); float32 stays float32
-            X = self._check_query(X)
+        if self._is_resident(X):
+            return self._resident_winners(X)
+        # integer / half input is converted like the reference's engine does (sklearn's
+        # NearestNeighbors); float32 stays float32.  A device array gives a tensor on its device.
+        X = self._check_query(X)
         _, labels = self._get_winning_neurons(X, n_bmu=1)
         return labels
 
@@ -41,4 +44,5 @@ class SomVQ(BaseSom, ClusterMixin, TransformerMixin):
 
     def fit_predict(self, X, y=None, sample_weight=None) -> np.ndarray:
         """``fit(X, y, sample_weight).labels_``: the index of the best matching unit of every row of X."""
-        return self.fit(X, y, sample_weight=sample_weight).labels_
+        labels = self.fit(X, y, sample_weight=sample_weight).labels_
+        return self._like(labels, X) if is_device_array(X) else labels

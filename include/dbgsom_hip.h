@@ -359,7 +359,11 @@ int dbgsom_ctx_destroy(dbgsom_ctx *ctx);
  * "filter_backoff", "plane_hold", "device_bytes", "anchor_builds" (anchor buckets built so far), "anchor_searches" (searches seeded from them), "anchor_state" (of
  * the resident samples: 0 none, 1 in use, 2 dropped -- their lists came out longer than the pre-pass's), and the
  * PCIe traffic of the prototypes since the context was created: "w_upload_calls" / "w_upload_bytes"
- * (whole matrices host -> HBM), "w_download_calls" / "w_download_bytes", "w_row_writes", "w_row_reads". */
+ * (whole matrices host -> HBM), "w_download_calls" / "w_download_bytes", "w_row_writes", "w_row_reads";
+ * and the PCIe traffic of the samples since then: "x_upload_bytes" / "x_upload_calls" (sample rows host -> HBM:
+ * dbgsom_ctx_load, dbgsom_ctx_load_csr, the rows of every query handed over as host arrays, chunk by chunk where a
+ * call works in chunks) and "x_download_bytes" (per-row results HBM -> host: winners, distances, codes, class
+ * probabilities, filled rows).  dbgsom_ctx_load_device and the *_device queries below move neither. */
 int dbgsom_ctx_set_option(dbgsom_ctx *ctx, const char *name, int64_t value);
 int dbgsom_ctx_get_option(dbgsom_ctx *ctx, const char *name, int64_t *value);
 /* the HIP stream (hipStream_t) every call of this context enqueues its work on */
@@ -478,7 +482,8 @@ int dbgsom_ctx_read_weight_rows(dbgsom_ctx *ctx, int which, const int64_t *rows_
 int dbgsom_ctx_write_weight_rows(dbgsom_ctx *ctx, int64_t row0, int64_t n, const double *rows_host);
 
 /* _get_winning_neurons on the resident samples.  BaseSom.py:446-464.  W_host = NULL: the resident
- * prototypes.  k = 1 goes through the filtered search where it pays. */
+ * prototypes.  k = 1 goes through the filtered search where it pays.  dist_host may be NULL (the winners alone
+ * come back). */
 int dbgsom_ctx_bmu(dbgsom_ctx *ctx, const double *W_host, int64_t M, int k, int round_f32,
                    int64_t *idx_host, double *dist_host);
 
@@ -486,6 +491,17 @@ int dbgsom_ctx_bmu(dbgsom_ctx *ctx, const double *W_host, int64_t M, int k, int 
 int dbgsom_ctx_bmu_query(dbgsom_ctx *ctx, const void *Xq_host, int x_dtype, int64_t Nq,
                          int64_t d, const double *W_host, int64_t M, int k, int round_f32,
                          int64_t *idx_host, double *dist_host);
+
+/* The same on rows that already live in HBM on the context's device (rows ldx >= d elements apart, any alignment
+ * of the element type): nothing of Xq crosses PCIe in either direction.  The rows are read where they are when they
+ * meet the condition of dbgsom_ctx_load_device (d a multiple of 16, ldx == d, 16-byte aligned base) and copied
+ * (padded) on the device into the context's query buffer otherwise; the searches, the filtered one included
+ * ("filter_min_query_rows"), and their results are those of dbgsom_ctx_bmu_query on the same bytes.  idx_dev /
+ * dist_dev: Nq x k device arrays the search writes itself.  The caller has finished writing Xq; the call returns
+ * after the context's stream has drained, and no pointer is retained. */
+int dbgsom_ctx_bmu_query_device(dbgsom_ctx *ctx, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d,
+                                int64_t ldx, const double *W_host, int64_t M, int k, int round_f32,
+                                int64_t *idx_dev, double *dist_dev);
 
 /* the same on CSR samples (the rule of dbgsom_ctx_load_csr decides between the CSR search and expansion) */
 int dbgsom_ctx_bmu_query_csr(dbgsom_ctx *ctx, const int64_t *indptr_host, const int32_t *indices_host,
@@ -610,6 +626,14 @@ int dbgsom_sparse_code_stage_ms(double *ms5);
 int dbgsom_ctx_sparse_code(dbgsom_ctx *ctx, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
                            const double *W_host, int64_t M, int max_iter, const double *P_host,
                            int64_t C, double *code_host, double *proba_host, uint64_t *counts_host);
+/* The same on rows in HBM (ldx >= d elements apart, any alignment of the element type): every chunk of
+ * "sc_chunk_rows" rows is coded where it lies and written to code_dev + r0 * M / proba_dev + r0 * C (Nq x M / Nq x C
+ * float64 device arrays, contiguous) without a staging buffer; W_host, P_host and counts_host are host arrays as above.
+ * Blocking; no pointer is retained. */
+int dbgsom_ctx_sparse_code_device(dbgsom_ctx *ctx, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d,
+                                  int64_t ldx, const double *W_host, int64_t M, int max_iter,
+                                  const double *P_host, int64_t C, double *code_dev, double *proba_dev,
+                                  uint64_t *counts_host);
 
 /* ---- topographic function: BaseSom.topographic_function / BaseSom.phi (BaseSom.py:955-998) ------------
  * The graph of the map's induced Delaunay triangulation (an edge {a, b} for every row (a, b) of the
@@ -642,6 +666,12 @@ int dbgsom_ctx_topographic_function(dbgsom_ctx *ctx, const void *Xq_host, int x_
                                     int64_t d, const double *W_host, int64_t M, int round_f32,
                                     const int32_t *xy_host, int64_t n_pos, int64_t *hist_pos_host,
                                     int64_t *hist_neg_host, int32_t *D_host);
+/* The same with the query rows in HBM (placed as dbgsom_ctx_bmu_query_device places them); the histograms and D
+ * are host arrays as above. */
+int dbgsom_ctx_topographic_function_device(dbgsom_ctx *ctx, const void *Xq_dev, int x_dtype, int64_t Nq,
+                                           int64_t d, int64_t ldx, const double *W_host, int64_t M,
+                                           int round_f32, const int32_t *xy_host, int64_t n_pos,
+                                           int64_t *hist_pos_host, int64_t *hist_neg_host, int32_t *D_host);
 
 /* _calculate_exp_similarity on host values (BaseSom.py:533-538) */
 int dbgsom_ctx_exp_similarity(dbgsom_ctx *ctx, const double *dist_host, int64_t n, double gamma,
