@@ -132,6 +132,12 @@ SIGNATURES = {
     "dbgsom_bmu_masked": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _i64, _i64, _ci, _vp, _vp, _vp, _sz, _vp]),
     "dbgsom_fill_missing": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp]),
     "dbgsom_ctx_bmu_query_masked": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _ci, _vp, _vp, _vp]),
+    "dbgsom_distances": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "dbgsom_distances_masked": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _sz, _vp]),
+    "dbgsom_ctx_distances_query": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _vp]),
+    "dbgsom_ctx_distances_query_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _vp, _i64]),
+    "dbgsom_ctx_distances_query_csr": (_ci, [_vp, _vp, _vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _vp]),
+    "dbgsom_ctx_distances_query_masked": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _vp]),
     "dbgsom_accumulate_masked_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "dbgsom_accumulate_masked": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "dbgsom_smooth_masked_workspace_bytes": (_sz, [_i64, _i64]),

@@ -95,6 +95,16 @@ class HotPathBackend:
         ``bmu``'s shapes, and with ``want_filled`` a copy of X with every hole filled from the row's first winner."""
         raise NotImplementedError
 
+    def distances(self, W, X):
+        """The (rows of X, rows of W) float64 matrix of distances in the arithmetic of ``bmu(W, k, X=X)``, bit for
+        bit -- ``bmu``'s distances are its smallest entries per row.  X: a dense host array, a scipy sparse matrix
+        or (a backend that takes them) a device array; the result is a NumPy array, next to X for a device array."""
+        raise NotImplementedError
+
+    def distances_masked(self, W, X):
+        """``distances(W, X)`` for dense host rows with missing entries (NaN), in the arithmetic of ``bmu_masked``."""
+        raise NotImplementedError
+
     def exp_similarity(self, distances, gamma):
         raise NotImplementedError
 
@@ -864,6 +874,60 @@ class HipBackend(HotPathBackend):
         if k == 1:
             dist, idx = dist.reshape(-1), idx.reshape(-1)
         return (dist, idx, filled) if want_filled else (dist, idx)
+
+    # -- the distance matrix of a query ----------------------------------------------------------------
+    # rows per chunk of the host-array calls (0, the default: as many as keep a chunk's staged result at 256 MiB)
+    distances_chunk_rows = property(lambda self: self._get("distances_chunk_rows"),
+                                    lambda self, v: self._set("distances_chunk_rows", v))
+
+    def distances(self, W, X):
+        """Every distance the all-pairs search of ``bmu(W, k, X=X)`` computes (csrc/distances.hip), stored instead of
+        reduced.  Host rows go up and the matrix comes down in chunks of ``distances_chunk_rows`` rows; CSR rows are
+        expanded on the device chunk by chunk; for rows in HBM the result is a float64 array on their device that
+        the kernel writes itself (dbgsom_ctx_distances_query_device)."""
+        W64 = np.ascontiguousarray(W, dtype=np.float64)
+        if W64.ndim != 2 or len(X.shape) != 2 or W64.shape[1] != X.shape[1]:
+            raise ValueError("prototype / sample feature mismatch")
+        M, N = W64.shape[0], int(X.shape[0])
+        if is_device_array(X):
+            code, N, d, ldx = self._device_rows(X)
+            out = device_empty(X, (N, M), "float64")
+            if N:
+                self._producer_done(X)
+                self._call("dbgsom_ctx_distances_query_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code, N, d, ldx,
+                           W64.ctypes.data, M, ctypes.c_void_p(out.data_ptr()), M)
+            return out
+        out = np.empty((N, M), dtype=np.float64)
+        if N == 0:
+            return out
+        if is_sparse(X):
+            csr, indptr, indices, data = canonical_csr(X)
+            self._call("dbgsom_ctx_distances_query_csr", self._ctx, indptr.ctypes.data, indices.ctypes.data,
+                       data.ctypes.data, _x_dtype_code(data.dtype), N, csr.shape[1], data.size, W64.ctypes.data, M,
+                       out.ctypes.data)
+            return out
+        X = np.ascontiguousarray(X)
+        if X.dtype not in (np.float32, np.float64):
+            X = X.astype(np.float64)
+        self._call("dbgsom_ctx_distances_query", self._ctx, X.ctypes.data, _x_dtype_code(X.dtype), N, X.shape[1],
+                   W64.ctypes.data, M, out.ctypes.data)
+        return out
+
+    def distances_masked(self, W, X):
+        """The distances over the observed entries of every row on the device (csrc/distances.hip), in chunks of
+        ``distances_chunk_rows`` rows."""
+        X = np.ascontiguousarray(X)
+        if X.dtype not in (np.float32, np.float64):
+            X = X.astype(np.float64)
+        W64 = np.ascontiguousarray(W, dtype=np.float64)
+        if X.ndim != 2 or W64.ndim != 2 or W64.shape[1] != X.shape[1]:
+            raise ValueError("prototype / sample feature mismatch")
+        N, M = X.shape[0], W64.shape[0]
+        out = np.empty((N, M), dtype=np.float64)
+        if N:
+            self._call("dbgsom_ctx_distances_query_masked", self._ctx, X.ctypes.data, _x_dtype_code(X.dtype), N,
+                       X.shape[1], W64.ctypes.data, M, out.ctypes.data)
+        return out
 
     def query_filter_applies(self, N, d, M, k=1):
         """Whether a k-BMU query on N other samples would go through the filtered search."""

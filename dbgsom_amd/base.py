@@ -926,6 +926,41 @@ class BaseSom(BaseEstimator):
             dist[complete], idx[complete] = engine.bmu(self.weights_, n_bmu, X=data[complete])
         return dist, idx
 
+    def prototype_distances(self, X):
+        """The distance from every row of X to every prototype: ``(n_samples, n_prototypes)`` float64, entry
+        ``[i, j]`` from row ``i`` to ``weights_[j]`` (the order of ``neurons_``) -- the cluster-distance space
+        of ``KMeans.transform``.  The arithmetic is that of the best-matching-unit search, bit for bit, so a row's
+        smallest entry is its distance to the unit ``predict`` names; there is no float32 rounding.  X is what
+        ``predict`` takes: a dense array (the result is a NumPy array), a device array (a float64 tensor on X's
+        device that the GPU writes itself; X and the result never touch the host), scipy sparse rows (the result
+        of the dense call on ``X.toarray()``), and with ``missing_values`` set rows with NaN, whose entries are
+        ``sqrt(d / n_obs * sum over the observed (x_k - w_k)^2)``.  Only this map's prototypes are used (not the
+        child maps of vertical growth); the call is local to the process."""
+        check_is_fitted(self)
+        W = self.weights_
+        if not is_device_array(X) and not is_sparse(X) and np.ndim(X) == 2 and np.shape(X)[0] == 0:
+            X = check_array(X, dtype=[np.float64, np.float32], ensure_min_samples=0)   # (no rows: no launch)
+        else:
+            X = self._check_query(X)
+        if X.shape[1] != self.n_features_in_:
+            raise ValueError(f"X has {X.shape[1]} features, but {type(self).__name__} is expecting "
+                             f"{self.n_features_in_} features as input")
+        if X.shape[0] == 0:
+            return np.empty((0, len(W)), dtype=np.float64)
+        engine = self._engine()
+        if self._accepts_nan() and isinstance(X, np.ndarray):
+            rows = self._incomplete_rows(X)
+            if rows.size:   # split and scatter as _winning_neurons_with_holes
+                out = np.empty((X.shape[0], len(W)), dtype=np.float64)
+                out[rows] = engine.distances_masked(W, X[rows])
+                if rows.size < X.shape[0]:
+                    complete = np.ones(X.shape[0], dtype=bool)
+                    complete[rows] = False
+                    complete = np.flatnonzero(complete)
+                    out[complete] = engine.distances(W, X[complete])
+                return out
+        return engine.distances(W, X)
+
     def impute(self, X) -> np.ndarray:
         """A copy of X (float32 kept, anything else float64) with every NaN replaced by that entry of the row's
         best matching prototype, the nearest one over the row's observed entries.  Observed entries and complete

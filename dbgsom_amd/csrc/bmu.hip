@@ -23,47 +23,9 @@
 #include <stdlib.h>
 
 #include "bmu_common.h"
+#include "bmu_tiles.h"
 
 namespace dbgsom {
-
-constexpr int LS = KT + 2;  // LDS row stride (doubles)
-
-template <typename T>
-__device__ __forceinline__ void load8(const T *__restrict__ base, int64_t row, int64_t nrows,
-                                      int64_t ld, int k, int d, int vec_ok, T (&v)[8]) {
-    if (row < nrows && k < d) {
-        const T *p = base + row * ld + k;
-        if (vec_ok && k + 8 <= d) {
-            if constexpr (sizeof(T) == 2) {
-                const uint4 a = *reinterpret_cast<const uint4 *>(p);
-                const uint32_t w[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v[2 * e].bits = (uint16_t)(w[e] & 0xffffu);
-                    v[2 * e + 1].bits = (uint16_t)(w[e] >> 16);
-                }
-            } else if constexpr (sizeof(T) == 4) {
-                const float4 a = *reinterpret_cast<const float4 *>(p);
-                const float4 b = *reinterpret_cast<const float4 *>(p + 4);
-                v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-                v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const double2 a = *reinterpret_cast<const double2 *>(p + 2 * e);
-                    v[2 * e] = a.x;
-                    v[2 * e + 1] = a.y;
-                }
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = (k + e < d) ? p[e] : T(0);
-        }
-    } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = T(0);
-    }
-}
 
 template <typename XT, int K>
 __global__ __launch_bounds__(NT, 2) void bmu_kernel(

@@ -1,5 +1,6 @@
 // Pieces shared by the two BMU kernels (bmu.hip: register-staged, any shape; bmu_dma.hip:
-// LDS-DMA ring for 16-byte aligned rows with d % 16 == 0).
+// LDS-DMA ring for 16-byte aligned rows with d % 16 == 0) and by their siblings that store every
+// distance (distances.hip).
 #pragma once
 #include <math.h>
 
@@ -60,5 +61,7 @@ int launch_bmu_dma(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx
                    const double *W, int64_t M, const double *ww, int k, int round_f32,
                    int64_t *idx, double *dist, hipStream_t s);
 bool bmu_dma_usable(const void *X, int x_dtype, int64_t d, int64_t ldx, const void *W, int64_t M);
+// 16-prototype tiles per wavefront of the LDS-DMA form for a map of M prototypes (1, 2 or 4; 0: register-staged)
+int dma_chunk_tiles(int x_dtype, int64_t M);
 
 }  // namespace dbgsom

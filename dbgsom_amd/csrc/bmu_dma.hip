@@ -17,27 +17,9 @@
 #include <stdlib.h>
 
 #include "bmu_common.h"
+#include "bmu_tiles.h"
 
 namespace dbgsom {
-
-constexpr int NSTAGE = 3;
-
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
-typedef const __attribute__((address_space(1))) void *gbl_ptr_t;
-
-__device__ __forceinline__ void dma16(const void *src, void *lds_dst) {
-    __builtin_amdgcn_global_load_lds((gbl_ptr_t)src, (lds_ptr_t)lds_dst, 16, 0, 0);
-}
-
-template <typename XT>
-struct XTile {
-    static constexpr int ROW_BYTES = KT * (int)sizeof(XT);  // 64 (f32) or 128 (f64)
-    static constexpr int CHUNKS = ROW_BYTES / 16;            // 4 or 8
-    static constexpr int BYTES = BI * ROW_BYTES;             // 8 KB or 16 KB
-    static constexpr int DMA_PER_WAVE = BYTES / 1024 / 4;    // wave-instructions per tile per wave
-};
-
-constexpr int W_ROW_BYTES = KT * 8, W_CHUNKS = 8;
 
 // JTW = 16-prototype tiles per wavefront: the workgroup sweeps the prototypes in chunks of
 // BJW = 32 JTW (128 for the general case; 64 / 32 for small maps, where a 128-wide chunk would
@@ -267,7 +249,7 @@ __global__ __launch_bounds__(NT, 2) void bmu_dma_kernel(
 // 1 : 1.74 : 3.33 (N = 1e6, d = 784: 0.93 / 1.62 / 3.10 ms); float64 samples 1 : 1.66 and no
 // 128-wide form here (X tile 16 KB + W tile 16 KB = one workgroup per CU: the register-staged
 // kernel is faster, 3.6 on this scale per 128 prototypes).  0 = take the register-staged kernel.
-static int dma_chunk_tiles(int x_dtype, int64_t M) {
+int dma_chunk_tiles(int x_dtype, int64_t M) {
     const double n1 = (double)((M + 31) / 32), n2 = (double)((M + 63) / 64), n4 = (double)((M + 127) / 128);
     if (x_dtype == DBGSOM_F32) {
         const double c1 = 1.00 * n1, c2 = 1.74 * n2, c4 = 3.33 * n4;

@@ -166,6 +166,12 @@ int launch_masked_prepare(const void *X, int x_dtype, int64_t N, int64_t d, int6
 int launch_bmu_masked_prepared(const double *X64, int64_t N, int64_t d, int64_t ld64, const int32_t *nobs,
                                const double *Wt, int64_t M, int k, int64_t *idx, double *dist, hipStream_t s);
 size_t masked_weights_bytes(int64_t d, int64_t M);
+// the N x M distance matrix (distances.hip): dense rows (the chain of launch_bmu, every pair stored; rows ldo >= M
+// apart) and rows with missing entries (the chain of launch_bmu_masked_rows, same workspace, Wt in front of it)
+int launch_distances(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx, const double *W,
+                     int64_t M, const double *ww, double *out, int64_t ldo, hipStream_t s);
+int launch_distances_masked_rows(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, double *out,
+                                 int64_t ldo, void *ws, size_t ws_bytes, hipStream_t s);
 // fit on rows with missing entries: sums [S (M x d) | K (M x d) | A (M x d) | a | E] over the observed entries
 // (masked_fit.hip), and the smoothing with a denominator per (neuron, feature) (smooth.hip)
 size_t accumulate_masked_workspace_bytes(int64_t N, int64_t d, int64_t M);

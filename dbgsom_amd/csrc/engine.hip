@@ -266,6 +266,10 @@ struct dbgsom_ctx {
     DevBuf sc_ws, sc_x, sc_w, sc_p, sc_code, sc_proba, sc_cnt;
     int64_t masked_chunk_rows = 32768;  // rows with missing entries: query rows per chunk
     DevBuf mk_ws, mk_x, mk_w, mk_idx, mk_dist;
+    // the distance matrix of a query (distances.hip): rows per chunk of the host-facing calls (0: as many as keep a
+    // chunk's staged result at 256 MiB) and the staged result of a chunk
+    int64_t distances_chunk_rows = 0;
+    DevBuf pd_out;
     // The resident rows have missing entries (NaN): option "incomplete", set after a load and cleared by the next one.
     // What depends on the rows alone is made when the option is set, once per load: n_obs per row (mf_nobs) and, for
     // float32 rows, their float64 copy (mf_x64, N x d x 8 bytes of HBM).  The ordinary calls then refuse to compute
@@ -1158,7 +1162,8 @@ int dbgsom_ctx_create(int device, dbgsom_ctx **out) {
      &(c)->hist, &(c)->stage_dev, &(c)->part_order, &(c)->part_ws, &(c)->part_counts, &(c)->shiftb, &(c)->shard_send,    \
      &(c)->shard_gather, &(c)->sw, &(c)->wh_order, &(c)->wh_ws, &(c)->sc_ws, &(c)->sc_x, &(c)->sc_w, &(c)->sc_p, &(c)->sc_code, &(c)->sc_proba, &(c)->sc_cnt, &(c)->wt,  \
      &(c)->mk_ws, &(c)->mk_x, &(c)->mk_w, &(c)->mk_idx, &(c)->mk_dist, &(c)->mf_nobs, &(c)->mf_x64, &(c)->mf_wt, &(c)->mf_w,   \
-     &(c)->mf_wn, &(c)->mf_idx, &(c)->mf_dist, &(c)->mf_kw, &(c)->mf_sums, &(c)->mf_acc_ws, &(c)->mf_sm_ws, &(c)->mf_scal}
+     &(c)->mf_wn, &(c)->mf_idx, &(c)->mf_dist, &(c)->mf_kw, &(c)->mf_sums, &(c)->mf_acc_ws, &(c)->mf_sm_ws, &(c)->mf_scal, \
+     &(c)->pd_out}
 
 int dbgsom_ctx_destroy(dbgsom_ctx *c) {
     if (!c) return DBGSOM_OK;
@@ -1212,6 +1217,9 @@ int dbgsom_ctx_set_option(dbgsom_ctx *c, const char *name, int64_t v) {
     } else if (!strcmp(name, "masked_chunk_rows")) {
         DBGSOM_REQUIRE(v >= 1 && v <= ((int64_t)1 << 22), "masked_chunk_rows must be in [1, 2^22]");
         c->masked_chunk_rows = v;
+    } else if (!strcmp(name, "distances_chunk_rows")) {
+        DBGSOM_REQUIRE(v >= 0 && v <= ((int64_t)1 << 22), "distances_chunk_rows must be in [0, 2^22] (0 = by the result's size)");
+        c->distances_chunk_rows = v;
     } else if (!strcmp(name, "sc_cap")) {
         DBGSOM_REQUIRE(v >= 0 && v <= 64, "sc_cap must be in [0, 64] (0 = the library's cap)");
         c->sc_cap = v;
@@ -1270,6 +1278,7 @@ int dbgsom_ctx_get_option(dbgsom_ctx *c, const char *name, int64_t *v) {
     else if (!strcmp(name, "sc_chunk_rows")) *v = c->sc_chunk_rows;
     else if (!strcmp(name, "sc_cap")) *v = c->sc_cap;
     else if (!strcmp(name, "masked_chunk_rows")) *v = c->masked_chunk_rows;
+    else if (!strcmp(name, "distances_chunk_rows")) *v = c->distances_chunk_rows;
     else if (!strcmp(name, "csr_densify_below")) *v = c->csr_densify_below;
     else if (!strcmp(name, "resident_csr")) *v = (c->xs.dtype >= 0 && c->xs.csr) ? 1 : 0;
     else if (!strcmp(name, "resident_nnz")) *v = (c->xs.dtype >= 0 && c->xs.csr) ? c->xs.nnz : 0;
@@ -1807,6 +1816,205 @@ int dbgsom_ctx_bmu_query_masked(dbgsom_ctx *c, const void *Xq_host, int x_dtype,
     if (c->mk_ws.cap + c->mk_x.cap > ((size_t)256 << 20)) {   // do not sit on a large one-off batch
         c->mk_ws.release(); c->mk_x.release(); c->mk_idx.release(); c->mk_dist.release();
     }
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------
+// the distance matrix of a query: csrc/distances.hip.  The host-facing calls work in chunks of rows: a chunk goes up
+// (dense rows through the query placement, masked rows through mk_x), its Nc x M result is staged in pd_out and
+// comes down behind the kernel.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int64_t DISTANCES_STAGE_BYTES = (int64_t)256 << 20;
+
+// rows per chunk: the option, or as many as keep the staged result -- and the staged rows -- of a chunk at 256 MiB
+int64_t distances_chunk(const dbgsom_ctx *c, int64_t Nq, int64_t M, int64_t row_bytes) {
+    int64_t rows = c->distances_chunk_rows;
+    if (rows < 1) rows = std::max<int64_t>(128, std::min(DISTANCES_STAGE_BYTES / (M * 8), DISTANCES_STAGE_BYTES / row_bytes));
+    return std::max<int64_t>(1, std::min(rows, Nq));
+}
+
+int distances_args(const char *fn, const dbgsom_ctx *c, int x_dtype, bool masked_or_csr, int64_t Nq, int64_t d, int64_t M) {
+    if (!c) { set_error("%s: null context", fn); return DBGSOM_EINVAL; }
+    const bool dt_ok = masked_or_csr ? (x_dtype == DBGSOM_F32 || x_dtype == DBGSOM_F64) : valid_dtype(x_dtype);
+    if (!dt_ok) {
+        set_error("%s: x_dtype must be %s", fn, masked_or_csr ? "DBGSOM_F32 or DBGSOM_F64" : "DBGSOM_F32/F64/BF16");
+        return DBGSOM_EINVAL;
+    }
+    if (Nq < 0 || Nq >= 0x7fffffff || d < 1 || d > 0x7fffffff) { set_error("%s: bad sample shape", fn); return DBGSOM_EINVAL; }
+    if (M < 1 || M > DBGSOM_MAX_PROTOTYPES) { set_error("%s: need 1 <= M <= DBGSOM_MAX_PROTOTYPES", fn); return DBGSOM_EINVAL; }
+    return DBGSOM_OK;
+}
+
+// the prototypes of a query on the device, padded, with their norms
+int place_query_weights(dbgsom_ctx *c, DevBuf &Wq, DevBuf &wwq, const double *W_host, int64_t M, int64_t d, int64_t dp) {
+    TRY(Wq.reserve((size_t)M * dp * 8));
+    TRY(wwq.reserve((size_t)M * 8));
+    TRY(upload_padded(c, Wq.p, W_host, M, d, dp, 8));
+    return launch_row_sqnorms(Wq.p, DBGSOM_F64, M, dp, dp, wwq.as<double>(), c->stream);
+}
+
+// the placed rows of `s` against Wq into the staged result, and that down to out_host
+int distances_chunk_down(dbgsom_ctx *c, Samples &s, const DevBuf &Wq, const DevBuf &wwq, int64_t M, double *out_host) {
+    TRY(launch_distances(s.Xb, s.bdtype, s.N, s.dp, s.dp, s.xx.as<double>(), Wq.as<double>(), M, wwq.as<double>(),
+                         c->pd_out.as<double>(), M, c->stream));
+    DBGSOM_HIP_CHECK(hipMemcpyAsync(out_host, c->pd_out.p, (size_t)s.N * M * 8, hipMemcpyDeviceToHost, c->stream));
+    c->x_down((size_t)s.N * M * 8);
+    return DBGSOM_OK;
+}
+
+int distances_finish(dbgsom_ctx *c, int rc) {
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (rc == DBGSOM_OK && e != hipSuccess) {
+        set_error("hipStreamSynchronize failed: %s", hipGetErrorString(e));
+        rc = DBGSOM_EHIP;
+    }
+    if (c->pd_out.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->pd_out.release();   // do not sit on a large one-off batch
+    return rc;
+}
+
+}  // namespace
+
+int dbgsom_ctx_distances_query(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                               const double *W_host, int64_t M, double *out_host) {
+    TRY(distances_args(__func__, c, x_dtype, false, Nq, d, M));
+    if (Nq == 0) return DBGSOM_OK;
+    DBGSOM_REQUIRE(Xq_host && W_host && out_host, "null pointer");
+    CTX_CHECK(c);
+    Samples &s = c->xq;
+    DevBuf Wq, wwq;
+    const int64_t dp = pad16(d);
+    const size_t es = dtype_size(x_dtype);
+    const int64_t chunk = distances_chunk(c, Nq, M, dp * (int64_t)es);
+    int rc = DBGSOM_OK;
+    do {
+        if ((rc = place_query_weights(c, Wq, wwq, W_host, M, d, dp))) break;
+        if ((rc = c->pd_out.reserve((size_t)chunk * M * 8))) break;
+        for (int64_t r0 = 0; r0 < Nq && rc == DBGSOM_OK; r0 += chunk) {
+            const int64_t n = std::min(chunk, Nq - r0);
+            if ((rc = place_host_samples(c, s, static_cast<const char *>(Xq_host) + (size_t)r0 * d * es, x_dtype, n, d, x_dtype)))
+                break;
+            rc = distances_chunk_down(c, s, Wq, wwq, M, out_host + r0 * M);
+        }
+    } while (0);
+    rc = distances_finish(c, rc);
+    Wq.release(); wwq.release();
+    drop_query_rows(s, QueryRows{Xq_host, false, d}, chunk * dp * (int64_t)es);
+    return rc;
+}
+
+int dbgsom_ctx_distances_query_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d, int64_t ldx,
+                                      const double *W_host, int64_t M, double *out_dev, int64_t ldo) {
+    TRY(distances_args(__func__, c, x_dtype, false, Nq, d, M));
+    DBGSOM_REQUIRE(ldx >= d, "ldx must be >= d");
+    DBGSOM_REQUIRE(ldo >= M, "ldo must be >= M");
+    if (Nq == 0) return DBGSOM_OK;
+    DBGSOM_REQUIRE(Xq_dev && W_host && out_dev, "null pointer");
+    CTX_CHECK(c);
+    Samples &s = c->xq;
+    DevBuf Wq, wwq;
+    const int64_t dp = pad16(d);
+    const QueryRows q{Xq_dev, true, ldx};
+    int rc = DBGSOM_OK;
+    do {
+        if ((rc = place_query_rows(c, s, q, x_dtype, Nq, d))) break;
+        if ((rc = place_query_weights(c, Wq, wwq, W_host, M, d, dp))) break;
+        rc = launch_distances(s.Xb, s.bdtype, Nq, dp, dp, s.xx.as<double>(), Wq.as<double>(), M, wwq.as<double>(), out_dev,
+                              ldo, c->stream);
+    } while (0);
+    rc = distances_finish(c, rc);
+    Wq.release(); wwq.release();
+    drop_query_rows(s, q, Nq * dp * (int64_t)dtype_size(x_dtype));
+    return rc;
+}
+
+int dbgsom_ctx_distances_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const int32_t *indices_host,
+                                   const void *data_host, int x_dtype, int64_t Nq, int64_t d, int64_t nnz,
+                                   const double *W_host, int64_t M, double *out_host) {
+    TRY(distances_args(__func__, c, x_dtype, true, Nq, d, M));
+    DBGSOM_REQUIRE(indptr_host && nnz >= 0 && (nnz == 0 || (indices_host && data_host)), "bad arguments");
+    TRY(dbgsom_csr_check(indptr_host, indices_host, Nq, d, nnz));
+    if (Nq == 0) return DBGSOM_OK;
+    DBGSOM_REQUIRE(W_host && out_host, "null pointer");
+    CTX_CHECK(c);
+    Samples &s = c->xq;
+    DevBuf Wq, wwq;
+    const int64_t dp = pad16(d);
+    const size_t es = dtype_size(x_dtype);
+    const int64_t chunk = distances_chunk(c, Nq, M, dp * (int64_t)es);
+    int rc = DBGSOM_OK;
+    do {
+        // the three arrays go up whole; row chunks of them are expanded into the dense rows the kernel reads
+        s.release();
+        if ((rc = s.indptr.reserve((size_t)(Nq + 1) * 8))) break;
+        if ((rc = s.indices.reserve((size_t)(nnz > 0 ? nnz : 1) * 4))) break;
+        if ((rc = s.data.reserve((size_t)(nnz > 0 ? nnz : 1) * es))) break;
+        hipError_t e = hipMemcpyAsync(s.indptr.p, indptr_host, (size_t)(Nq + 1) * 8, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess && nnz > 0)
+            e = hipMemcpyAsync(s.indices.p, indices_host, (size_t)nnz * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess && nnz > 0)
+            e = hipMemcpyAsync(s.data.p, data_host, (size_t)nnz * es, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
+        c->x_up((size_t)nnz * (4 + es) + (size_t)(Nq + 1) * 8);
+        if ((rc = place_query_weights(c, Wq, wwq, W_host, M, d, dp))) break;
+        if ((rc = c->pd_out.reserve((size_t)chunk * M * 8))) break;
+        if ((rc = s.own.reserve((size_t)chunk * dp * es))) break;
+        for (int64_t r0 = 0; r0 < Nq && rc == DBGSOM_OK; r0 += chunk) {
+            const int64_t n = std::min(chunk, Nq - r0);
+            const CsrView rows{s.indptr.as<int64_t>() + r0, s.indices.as<int32_t>(), s.data.p};   // (indptr is absolute)
+            if ((rc = launch_csr_densify(rows, x_dtype, n, d, dp, s.own.p, c->stream))) break;
+            s.N = n; s.d = d; s.dp = dp; s.dtype = x_dtype; s.csr = false; s.nnz = 0;
+            s.X = s.own.p;
+            if ((rc = finish_samples(c, s, false))) break;
+            rc = distances_chunk_down(c, s, Wq, wwq, M, out_host + r0 * M);
+        }
+    } while (0);
+    rc = distances_finish(c, rc);
+    Wq.release(); wwq.release();
+    s.release();
+    return rc;
+}
+
+int dbgsom_ctx_distances_query_masked(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                      const double *W_host, int64_t M, double *out_host) {
+    TRY(distances_args(__func__, c, x_dtype, true, Nq, d, M));
+    TRY(masked_check_shape(x_dtype, Nq, d, d, M, 1));
+    if (Nq == 0) return DBGSOM_OK;
+    DBGSOM_REQUIRE(Xq_host && W_host && out_host, "null pointer");
+    const int64_t bad = first_row_without_entries(Xq_host, x_dtype, Nq, d);
+    if (bad >= 0) {
+        set_error("dbgsom_ctx_distances_query_masked: row %lld has no observed entry", (long long)bad);
+        return DBGSOM_EINVAL;
+    }
+    CTX_CHECK(c);
+    const int64_t chunk = distances_chunk(c, Nq, M, d * 8);
+    const size_t es = dtype_size(x_dtype);
+    int rc = DBGSOM_OK;
+    do {
+        if ((rc = c->mk_ws.reserve(bmu_masked_workspace_bytes(x_dtype, chunk, d, M)))) break;
+        if ((rc = c->mk_x.reserve((size_t)chunk * d * es))) break;
+        if ((rc = c->mk_w.reserve((size_t)M * d * 8))) break;
+        if ((rc = c->pd_out.reserve((size_t)chunk * M * 8))) break;
+        hipError_t e = hipMemcpyAsync(c->mk_w.p, W_host, (size_t)M * d * 8, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
+        if ((rc = launch_masked_weights(c->mk_w.as<double>(), M, d, d, c->mk_ws.p, c->stream))) break;
+        for (int64_t r0 = 0; r0 < Nq && rc == DBGSOM_OK; r0 += chunk) {
+            const int64_t n = std::min(chunk, Nq - r0);
+            e = hipMemcpyAsync(c->mk_x.p, static_cast<const char *>(Xq_host) + (size_t)r0 * d * es, (size_t)n * d * es,
+                               hipMemcpyHostToDevice, c->stream);
+            if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
+            c->x_up((size_t)n * d * es);
+            if ((rc = launch_distances_masked_rows(c->mk_x.p, x_dtype, n, d, d, M, c->pd_out.as<double>(), M, c->mk_ws.p,
+                                                   c->mk_ws.cap, c->stream)))
+                break;
+            e = hipMemcpyAsync(out_host + r0 * M, c->pd_out.p, (size_t)n * M * 8, hipMemcpyDeviceToHost, c->stream);
+            if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
+            c->x_down((size_t)n * M * 8);
+        }
+    } while (0);
+    rc = distances_finish(c, rc);
+    if (c->mk_ws.cap + c->mk_x.cap > ((size_t)256 << 20)) { c->mk_ws.release(); c->mk_x.release(); }
     return rc;
 }
 

@@ -536,6 +536,47 @@ int dbgsom_ctx_bmu_query_masked(dbgsom_ctx *ctx, const void *Xq_host, int x_dtyp
                                 const double *W_host, int64_t M, int k, int64_t *idx_host,
                                 double *dist_host, void *Xfilled_host);
 
+/* ---- the distance matrix of a query (csrc/distances.hip) ------------------------------------------------
+ * out[i * ldo + j] = the distance from row i of X to prototype j, float64, in the arithmetic of the search bit for
+ * bit: sqrt(max((|x_i|^2 + (-2 <x_i, w_j>)) + |w_j|^2, 0)) with each of the three sums a sequential fma chain over
+ * the features from +0 (oracle/bmu_chain.c); no float32 rounding.  What dbgsom_bmu returns for a row are this
+ * matrix's smallest entries of that row.
+ *   X: N x d (DBGSOM_F32 / F64 / BF16), rows ldx >= d elements apart, any d, any element-aligned base; xx / ww:
+ *   the squared norms of dbgsom_row_sqnorms; W: M x d float64, contiguous, 1 <= M <= DBGSOM_MAX_PROTOTYPES;
+ *   out: rows ldo >= M apart, 8-byte aligned (16-byte stores are used where the base and ldo allow them).
+ * Columns [M, ldo) of a row and everything behind row N - 1 are never written.  A NaN in a row gives NaN for
+ * that row. */
+int dbgsom_distances(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx_dev,
+                     const double *W_dev, int64_t M, const double *ww_dev, double *out_dev, int64_t ldo,
+                     void *stream);
+/* Rows with missing entries (NaN): out[i * ldo + j] = sqrt((d / n_obs) * sum over the observed entries of
+ * (x_k - w_k)^2), the chain, the scale and the square root of dbgsom_bmu_masked, whose distances are this
+ * matrix's smallest entries per row.  X: DBGSOM_F32 or DBGSOM_F64; W: M x d float64, rows ldw >= d apart; the
+ * workspace is that of dbgsom_bmu_masked_workspace_bytes (too small: DBGSOM_ENOMEM).  A row without an
+ * observed entry gets NaN. */
+int dbgsom_distances_masked(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx,
+                            const double *W_dev, int64_t M, int64_t ldw, double *out_dev, int64_t ldo,
+                            void *workspace_dev, size_t workspace_bytes, void *stream);
+/* The same on a context, each call staging its rows as its dbgsom_ctx_bmu_query* namesake does; W_host: M x d.
+ * The host-facing calls (out_host: Nq x M, contiguous) work in chunks of ctx option "distances_chunk_rows" rows
+ * (0, the default: as many as keep a chunk's staged result at 256 MiB): a chunk's rows go up, its result comes
+ * down.  _device: rows in HBM, read in place under the condition of dbgsom_ctx_load_device and pad-copied on
+ * the device otherwise; out_dev (rows ldo >= M apart) is written by the kernel itself and nothing of X or of
+ * the result crosses PCIe.  _csr: row chunks are expanded on the device (dbgsom_csr_densify) into the dense
+ * kernel, so the result is the dense call's on the expanded rows bit for bit.  _masked: rows with NaN; a row
+ * without an observed entry is DBGSOM_EINVAL, found on the host.  Argument errors are reported before any
+ * device work. */
+int dbgsom_ctx_distances_query(dbgsom_ctx *ctx, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                               const double *W_host, int64_t M, double *out_host);
+int dbgsom_ctx_distances_query_device(dbgsom_ctx *ctx, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d,
+                                      int64_t ldx, const double *W_host, int64_t M, double *out_dev,
+                                      int64_t ldo);
+int dbgsom_ctx_distances_query_csr(dbgsom_ctx *ctx, const int64_t *indptr_host, const int32_t *indices_host,
+                                   const void *data_host, int x_dtype, int64_t Nq, int64_t d, int64_t nnz,
+                                   const double *W_host, int64_t M, double *out_host);
+int dbgsom_ctx_distances_query_masked(dbgsom_ctx *ctx, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                      const double *W_host, int64_t M, double *out_host);
+
 /* ---- fit on rows with missing entries (csrc/masked_fit.hip, csrc/smooth.hip) ---------------------------
  * One epoch on prototypes W (M x d, complete), hop matrix and sigma, NaN marking a missing entry of X:
  *   1. (dist_i, win_i): the masked search above with k = 1 -- every row goes through it, complete rows
