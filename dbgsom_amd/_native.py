@@ -31,6 +31,7 @@ COLL_ALLREDUCE, COLL_REDUCE_SCATTER, COLL_ALLGATHER = 0, 1, 2
 CENTRES_COMPACT, CENTRES_ALIGNED = 0, 1
 LAYOUTS = {"compact": CENTRES_COMPACT, "aligned": CENTRES_ALIGNED}
 MAX_PROTOTYPES = 16000
+MAX_NEIGHBORS = 32      # DBGSOM_MAX_NEIGHBORS
 # counters of dbgsom_sparse_code / dbgsom_ctx_sparse_code (DBGSOM_SC_COUNTS, in this order)
 SC_COUNTS = ("samples", "iterations", "max_iterations", "drops", "degenerate", "early_stops", "aa_retries",
              "overflow", "max_active", "multi_drops", "g_rows")
@@ -138,6 +139,15 @@ SIGNATURES = {
     "dbgsom_ctx_distances_query_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _vp, _i64]),
     "dbgsom_ctx_distances_query_csr": (_ci, [_vp, _vp, _vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _vp]),
     "dbgsom_ctx_distances_query_masked": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _vp]),
+    "dbgsom_topk_rows": (_ci, [_vp, _i64, _i64, _i64, _ci, _vp, _vp, _vp]),
+    "dbgsom_kneighbors_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "dbgsom_kneighbors_masked_workspace_bytes": (_sz, [_ci, _i64, _i64, _i64, _i64]),
+    "dbgsom_kneighbors": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _ci, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "dbgsom_kneighbors_masked": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _i64, _i64, _ci, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "dbgsom_ctx_kneighbors_query": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _ci, _vp, _vp]),
+    "dbgsom_ctx_kneighbors_query_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _ci, _vp, _vp]),
+    "dbgsom_ctx_kneighbors_query_csr": (_ci, [_vp, _vp, _vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _ci, _vp, _vp]),
+    "dbgsom_ctx_kneighbors_query_masked": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _ci, _vp, _vp]),
     "dbgsom_accumulate_masked_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "dbgsom_accumulate_masked": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "dbgsom_smooth_masked_workspace_bytes": (_sz, [_i64, _i64]),

@@ -105,6 +105,19 @@ class HotPathBackend:
         """``distances(W, X)`` for dense host rows with missing entries (NaN), in the arithmetic of ``bmu_masked``."""
         raise NotImplementedError
 
+    def kneighbors(self, W, k, X):
+        """The k rows of W nearest to every row of X -> (distances, indices), both (rows of X, k), float64 and
+        int64: the k smallest ``(r, j)`` per row in lexicographic order, ascending, r the squared value of
+        ``bmu(W, k, X=X)``'s arithmetic and the distance its square root -- ``distances(W, X)`` gathered at the
+        indices, bit for bit.  Slots without a pair below +inf hold (inf, -1).  X as for ``distances``; the results
+        are NumPy arrays, next to X for a device array."""
+        raise NotImplementedError
+
+    def kneighbors_masked(self, W, k, X):
+        """``kneighbors(W, k, X)`` for dense host rows with missing entries (NaN), in the arithmetic of
+        ``bmu_masked``."""
+        raise NotImplementedError
+
     def exp_similarity(self, distances, gamma):
         raise NotImplementedError
 
@@ -928,6 +941,70 @@ class HipBackend(HotPathBackend):
             self._call("dbgsom_ctx_distances_query_masked", self._ctx, X.ctypes.data, _x_dtype_code(X.dtype), N,
                        X.shape[1], W64.ctypes.data, M, out.ctypes.data)
         return out
+
+    # -- the k nearest prototypes of a query -----------------------------------------------------------
+    # rows per slab of squared distances (0, the default: as many, in multiples of 128, as keep the slab at 64 MiB)
+    kneighbors_slab_rows = property(lambda self: self._get("kneighbors_slab_rows"),
+                                    lambda self, v: self._set("kneighbors_slab_rows", v))
+
+    @staticmethod
+    def _check_neighbors(k, M):
+        if not 1 <= k <= M:
+            raise ValueError(f"need 1 <= k <= {M} prototypes, got k = {k}")
+        if k > _native.MAX_NEIGHBORS:
+            raise ValueError(f"k = {k} is above DBGSOM_MAX_NEIGHBORS = {_native.MAX_NEIGHBORS}")
+
+    def kneighbors(self, W, k, X):
+        """The k nearest prototypes of every row (csrc/kneighbors.hip): the squared distances of a slab of
+        ``kneighbors_slab_rows`` rows stay on the device, the selection kernel reads them back from cache, and only
+        (rows, k) distances and indices are the result.  Host rows go up in chunks of ``distances_chunk_rows``
+        rows; CSR rows are expanded on the device chunk by chunk; for rows in HBM both results are arrays on their
+        device that the kernel writes itself (dbgsom_ctx_kneighbors_query_device)."""
+        W64 = np.ascontiguousarray(W, dtype=np.float64)
+        if W64.ndim != 2 or len(X.shape) != 2 or W64.shape[1] != X.shape[1]:
+            raise ValueError("prototype / sample feature mismatch")
+        M, N, k = W64.shape[0], int(X.shape[0]), int(k)
+        self._check_neighbors(k, M)
+        if is_device_array(X):
+            code, N, d, ldx = self._device_rows(X)
+            dist, idx = device_empty(X, (N, k), "float64"), device_empty(X, (N, k), "int64")
+            if N:
+                self._producer_done(X)
+                self._call("dbgsom_ctx_kneighbors_query_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code, N, d,
+                           ldx, W64.ctypes.data, M, k, ctypes.c_void_p(idx.data_ptr()), ctypes.c_void_p(dist.data_ptr()))
+            return dist, idx
+        dist, idx = np.empty((N, k), dtype=np.float64), np.empty((N, k), dtype=np.int64)
+        if N == 0:
+            return dist, idx
+        if is_sparse(X):
+            csr, indptr, indices, data = canonical_csr(X)
+            self._call("dbgsom_ctx_kneighbors_query_csr", self._ctx, indptr.ctypes.data, indices.ctypes.data,
+                       data.ctypes.data, _x_dtype_code(data.dtype), N, csr.shape[1], data.size, W64.ctypes.data, M, k,
+                       idx.ctypes.data, dist.ctypes.data)
+            return dist, idx
+        X = np.ascontiguousarray(X)
+        if X.dtype not in (np.float32, np.float64):
+            X = X.astype(np.float64)
+        self._call("dbgsom_ctx_kneighbors_query", self._ctx, X.ctypes.data, _x_dtype_code(X.dtype), N, X.shape[1],
+                   W64.ctypes.data, M, k, idx.ctypes.data, dist.ctypes.data)
+        return dist, idx
+
+    def kneighbors_masked(self, W, k, X):
+        """The k nearest prototypes over the observed entries of every row on the device (csrc/kneighbors.hip on the
+        masked chain of csrc/distances.hip), in chunks of ``distances_chunk_rows`` rows."""
+        X = np.ascontiguousarray(X)
+        if X.dtype not in (np.float32, np.float64):
+            X = X.astype(np.float64)
+        W64 = np.ascontiguousarray(W, dtype=np.float64)
+        if X.ndim != 2 or W64.ndim != 2 or W64.shape[1] != X.shape[1]:
+            raise ValueError("prototype / sample feature mismatch")
+        N, M, k = X.shape[0], W64.shape[0], int(k)
+        self._check_neighbors(k, M)
+        dist, idx = np.empty((N, k), dtype=np.float64), np.empty((N, k), dtype=np.int64)
+        if N:
+            self._call("dbgsom_ctx_kneighbors_query_masked", self._ctx, X.ctypes.data, _x_dtype_code(X.dtype), N,
+                       X.shape[1], W64.ctypes.data, M, k, idx.ctypes.data, dist.ctypes.data)
+        return dist, idx
 
     def query_filter_applies(self, N, d, M, k=1):
         """Whether a k-BMU query on N other samples would go through the filtered search."""

@@ -39,6 +39,7 @@ NaN under ``missing_values="nan"`` / ``"nan-fit"``, more than one rank or ``shar
 from __future__ import annotations
 
 import copy
+import numbers
 from math import log, pi, sqrt
 
 import networkx as nx
@@ -50,6 +51,7 @@ from sklearn.utils import check_array, check_random_state
 from sklearn.utils.validation import check_is_fitted
 
 from . import schedule
+from ._native import MAX_NEIGHBORS
 from .backend import (RESIDENT, HotPathBackend, array_namespace, dist_info, dtype_name, is_device_array, is_sparse,
                       shard_bounds)
 from .lattice import GrowingLattice
@@ -960,6 +962,66 @@ class BaseSom(BaseEstimator):
                     out[complete] = engine.distances(W, X[complete])
                 return out
         return engine.distances(W, X)
+
+    def kneighbors(self, X, n_neighbors=5, return_distance=True):
+        """The ``n_neighbors`` nearest prototypes of every row of X: ``(dist, idx)``, or ``idx`` alone with
+        ``return_distance=False``, both ``(n_samples, n_neighbors)``, float64 and int64 (indices into ``weights_``,
+        the order of ``neurons_``) -- ``NearestNeighbors.kneighbors`` on the prototypes.
+
+        Row ``i`` holds the prototypes with the smallest ``(r_ij, j)`` in lexicographic order, ascending, where
+        ``r_ij = max((|x_i|^2 + (-2 <x_i, w_j>)) + |w_j|^2, 0)`` is the squared value of the best-matching-unit
+        search's own arithmetic; ``dist = sqrt(r)`` is taken after the selection and there is no float32 rounding.
+        The selection is on ``r``: of two different ``r`` under one square root the smaller comes first, whatever
+        the indices; equal ``r`` go by the lower index.  So ``idx[:, :2]`` are the two units of the topographic
+        error, ``idx[:, 0]`` equals ``predict(X)``, and ``dist[i, t] == prototype_distances(X)[i, idx[i, t]]`` bit
+        for bit.  A pair whose ``r`` is not below +inf is never reported; slots left unfilled hold ``(inf, -1)``.
+        With ``missing_values`` set, rows with NaN are ordered by ``d / n_obs * sum over the observed
+        (x_k - w_k)^2`` with the same tie rule.
+
+        ``1 <= n_neighbors <= min(len(weights_), 32)``; the selection runs on the GPU for every such value, and
+        above 32 ``prototype_distances(X)`` and a sort of one's own is the route.  X is what ``predict`` takes: a
+        dense array (NumPy results), a device array (tensors on X's device that the GPU writes itself; X and the
+        results never touch the host), scipy sparse rows, rows with NaN under ``missing_values``.  The N x M
+        matrix is never held: squared distances live one slab of rows at a time on the device.  Only this map's
+        prototypes are used (not the child maps of vertical growth); the call is local to the process."""
+        check_is_fitted(self)
+        W = self.weights_
+        if isinstance(n_neighbors, (bool, np.bool_)) or not isinstance(n_neighbors, (numbers.Integral, np.integer)):
+            raise ValueError("n_neighbors does not take %s value, enter integer value" % type(n_neighbors))
+        k = int(n_neighbors)
+        if k <= 0:
+            raise ValueError("Expected n_neighbors > 0. Got %d" % k)
+        if not is_device_array(X) and not is_sparse(X) and np.ndim(X) == 2 and np.shape(X)[0] == 0:
+            X = check_array(X, dtype=[np.float64, np.float32], ensure_min_samples=0)   # (no rows: no launch)
+        else:
+            X = self._check_query(X)
+        if X.shape[1] != self.n_features_in_:
+            raise ValueError(f"X has {X.shape[1]} features, but {type(self).__name__} is expecting "
+                             f"{self.n_features_in_} features as input")
+        if k > len(W):
+            raise ValueError("Expected n_neighbors <= n_samples_fit, but n_neighbors = %d, n_samples_fit = %d "
+                             "(the prototypes), n_samples = %d" % (k, len(W), X.shape[0]))
+        if k > MAX_NEIGHBORS:
+            raise ValueError(f"n_neighbors = {k} is above the {MAX_NEIGHBORS} the selection on the GPU keeps per row: "
+                             "use prototype_distances(X) and sort its rows")
+        if X.shape[0] == 0:
+            dist, idx = np.empty((0, k), dtype=np.float64), np.empty((0, k), dtype=np.int64)
+            return (dist, idx) if return_distance else idx
+        engine = self._engine()
+        dist = idx = None
+        if self._accepts_nan() and isinstance(X, np.ndarray):
+            rows = self._incomplete_rows(X)
+            if rows.size:   # split and scatter as _winning_neurons_with_holes
+                dist, idx = np.empty((X.shape[0], k), dtype=np.float64), np.empty((X.shape[0], k), dtype=np.int64)
+                dist[rows], idx[rows] = engine.kneighbors_masked(W, k, X[rows])
+                if rows.size < X.shape[0]:
+                    complete = np.ones(X.shape[0], dtype=bool)
+                    complete[rows] = False
+                    complete = np.flatnonzero(complete)
+                    dist[complete], idx[complete] = engine.kneighbors(W, k, X[complete])
+        if idx is None:
+            dist, idx = engine.kneighbors(W, k, X)
+        return (dist, idx) if return_distance else idx
 
     def impute(self, X) -> np.ndarray:
         """A copy of X (float32 kept, anything else float64) with every NaN replaced by that entry of the row's

@@ -172,6 +172,25 @@ int launch_distances(const void *X, int x_dtype, int64_t N, int64_t d, int64_t l
                      int64_t M, const double *ww, double *out, int64_t ldo, hipStream_t s);
 int launch_distances_masked_rows(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, double *out,
                                  int64_t ldo, void *ws, size_t ws_bytes, hipStream_t s);
+// the same storing the clamped squared value instead of its square root, with ordinary stores (the slab of
+// kneighbors.hip, read back at once)
+int launch_distances_squared(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx,
+                             const double *W, int64_t M, const double *ww, double *out, int64_t ldo, hipStream_t s);
+int launch_distances_masked_rows_squared(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M,
+                                         double *out, int64_t ldo, void *ws, size_t ws_bytes, hipStream_t s);
+// the k nearest prototypes of every row (kneighbors.hip): the selection on a matrix of squared values, and the driver
+// over slabs of rows (squared distances into the workspace, selection on the slab; slab_rows 0 = the default)
+int launch_topk_rows(const double *R, int64_t N, int64_t M, int64_t ldr, int k, int64_t *idx, double *dist,
+                     hipStream_t s);
+int64_t kneighbors_slab_rows(int64_t N, int64_t M, int64_t slab_rows);
+size_t kneighbors_workspace_bytes(int64_t N, int64_t M, int64_t slab_rows);
+size_t kneighbors_masked_workspace_bytes(int x_dtype, int64_t N, int64_t d, int64_t M, int64_t slab_rows);
+int launch_kneighbors(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx, const double *W,
+                      int64_t M, const double *ww, int k, int64_t slab_rows, int64_t *idx, double *dist, void *ws,
+                      size_t ws_bytes, hipStream_t s);
+int launch_kneighbors_masked_rows(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, int k,
+                                  int64_t slab_rows, int64_t *idx, double *dist, void *ws, size_t ws_bytes,
+                                  hipStream_t s);
 // fit on rows with missing entries: sums [S (M x d) | K (M x d) | A (M x d) | a | E] over the observed entries
 // (masked_fit.hip), and the smoothing with a denominator per (neuron, feature) (smooth.hip)
 size_t accumulate_masked_workspace_bytes(int64_t N, int64_t d, int64_t M);

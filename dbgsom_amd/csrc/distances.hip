@@ -16,9 +16,18 @@
 // on 16-byte boundaries; where they are not, the values are stored as they lie, 8 bytes each (the four lanes of a
 // row still cover 32 contiguous bytes per instruction).  The matrix is never read again here: non-temporal stores.
 //
+// Squared form (template switch SQ, the slab of kneighbors.hip): the clamped squared value is stored in place of its
+// square root, with ordinary stores -- the selection kernel reads the slab back at once, while it is still in cache.
+// A slab has few rows (64 MiB of it at M = 1024 are 8192 rows: 64 workgroups of BI rows on 256 CUs), so the squared
+// form also splits the prototypes over blockIdx.y, sq_share(M, gridDim.y) of them (a multiple of BJ) per workgroup:
+// a workgroup shifts W, ww and out to its first prototype and runs the unchanged loop on its share.  A pair's chain does not depend on the
+// workgroup that runs it.
+//
 // Rows with missing entries: sibling of masked_bmu_kernel (masked.hip).  The lanes own prototypes there, so the 256
 // distances of a row and prototype block are one coalesced store; same chain, same d / n_obs scale, same square root.
 #include <math.h>
+
+#include <algorithm>
 
 #include "bmu_common.h"
 #include "bmu_tiles.h"
@@ -29,6 +38,11 @@
 namespace dbgsom {
 
 typedef double d2_t __attribute__((ext_vector_type(2)));
+constexpr int64_t SQ_FILL_BLOCKS = 512;   // squared form: the grid launch_distances_form aims at (2 x 256 CUs)
+// squared form: prototypes per workgroup when `shares` workgroups divide M among them, in whole chunks of BJ
+__host__ __device__ __forceinline__ int sq_share(int M, int shares) {
+    return ((M + BJ - 1) / BJ + shares - 1) / shares * BJ;
+}
 
 __device__ __forceinline__ void swap_halves(uint32_t &a, uint32_t &b) {   // a's lanes 32..63 <-> b's lanes 0..31
     const auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
@@ -57,6 +71,13 @@ __device__ __forceinline__ void exchange4(double (&v)[4]) {
 // ovec (wave-uniform): after the exchange this lane stores prototypes jt0 + 4 lq .. + 3 of row i, 16 bytes at a
 // time; otherwise the values go out where they are, 8 bytes each -- the four lanes of a row then write 32
 // contiguous bytes per instruction, and the exchange would buy nothing.
+template <bool SQ, typename T>
+__device__ __forceinline__ void put(T v, T *p) {
+    if constexpr (SQ) *p = v;
+    else __builtin_nontemporal_store(v, p);
+}
+
+template <bool SQ>
 __device__ __forceinline__ void store_tile(const d4_t &a, double xi, const double (&y)[4], double *__restrict__ out,
                                            int64_t i, int64_t N, int64_t ldo, int jt0, int lq, int M, int ovec) {
     double v[4];
@@ -64,7 +85,7 @@ __device__ __forceinline__ void store_tile(const d4_t &a, double xi, const doubl
     for (int r = 0; r < 4; ++r) {
         double rv = (xi + (-2.0 * a[r])) + y[r];
         if (!(rv > 0.0)) rv = (rv != rv) ? rv : 0.0;  // max(r, 0), NaN kept
-        v[r] = sqrt(rv);
+        v[r] = SQ ? rv : sqrt(rv);
     }
     if (ovec) {
         exchange4(v);
@@ -72,30 +93,35 @@ __device__ __forceinline__ void store_tile(const d4_t &a, double xi, const doubl
         if (i < N && j0 < M) {
             double *p = out + i * ldo + j0;
             if (j0 + 4 <= M) {
-                __builtin_nontemporal_store(d2_t{v[0], v[1]}, reinterpret_cast<d2_t *>(p));
-                __builtin_nontemporal_store(d2_t{v[2], v[3]}, reinterpret_cast<d2_t *>(p + 2));
+                put<SQ>(d2_t{v[0], v[1]}, reinterpret_cast<d2_t *>(p));
+                put<SQ>(d2_t{v[2], v[3]}, reinterpret_cast<d2_t *>(p + 2));
             } else {
 #pragma unroll
                 for (int c = 0; c < 4; ++c)
-                    if (j0 + c < M) __builtin_nontemporal_store(v[c], p + c);
+                    if (j0 + c < M) put<SQ>(v[c], p + c);
             }
         }
     } else if (i < N) {
         double *p = out + i * ldo + jt0 + lq;
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-            if (jt0 + 4 * r + lq < M) __builtin_nontemporal_store(v[r], p + 4 * r);
+            if (jt0 + 4 * r + lq < M) put<SQ>(v[r], p + 4 * r);
     }
 }
 
 // ---------------------------------------------------------------------------------------------
 // register-staged form: the product loop of bmu_kernel
 // ---------------------------------------------------------------------------------------------
-template <typename XT>
+template <typename XT, bool SQ>
 __global__ __launch_bounds__(NT, 2) void dist_kernel(
     const XT *__restrict__ X, int64_t N, int d, int64_t ldx, const double *__restrict__ xx,
     const double *__restrict__ W, int M, const double *__restrict__ ww, int xvec, int wvec,
     double *__restrict__ out, int64_t ldo, int ovec) {
+    if constexpr (SQ) {   // this workgroup's share of the prototypes (launch_distances_form: no share is empty)
+        const int jsplit = sq_share(M, gridDim.y), j0 = blockIdx.y * jsplit;
+        W += (int64_t)j0 * d; ww += j0; out += j0;
+        M = min(M - j0, jsplit);
+    }
     __shared__ __attribute__((aligned(16))) double xs[2][BI * LS];
     __shared__ __attribute__((aligned(16))) double wsm[2][BJ * LS];
     __shared__ double yy_s[2][BJ];
@@ -182,7 +208,7 @@ __global__ __launch_bounds__(NT, 2) void dist_kernel(
                 for (int r = 0; r < 4; ++r) y[r] = yy_s[parity][jl + 4 * r + lq];
 #pragma unroll
                 for (int it = 0; it < 4; ++it) {
-                    store_tile(acc[jt][it], xi[it], y, out, i0 + wi * 64 + it * 16 + lr, N, ldo, jc + jl, lq, M,
+                    store_tile<SQ>(acc[jt][it], xi[it], y, out, i0 + wi * 64 + it * 16 + lr, N, ldo, jc + jl, lq, M,
                                ovec);
                     acc[jt][it] = d4_t{0.0, 0.0, 0.0, 0.0};
                 }
@@ -200,11 +226,16 @@ __global__ __launch_bounds__(NT, 2) void dist_kernel(
 // vmcnt as the DMA loads do; loads return in order among themselves, so "all but the youngest tile's worth"
 // still means that the older tile has landed -- the wait behind a chunk's epilogue is merely longer than needed.
 // ---------------------------------------------------------------------------------------------
-template <typename XT, int JTW>
+template <typename XT, int JTW, bool SQ>
 __global__ __launch_bounds__(NT, 2) void dist_dma_kernel(
     const XT *__restrict__ X, int64_t N, int d, int64_t ldx, const double *__restrict__ xx,
     const double *__restrict__ W, int M, const double *__restrict__ ww, double *__restrict__ out,
     int64_t ldo, int ovec) {
+    if constexpr (SQ) {   // this workgroup's share of the prototypes (launch_distances_form: no share is empty)
+        const int jsplit = sq_share(M, gridDim.y), j0 = blockIdx.y * jsplit;
+        W += (int64_t)j0 * d; ww += j0; out += j0;
+        M = min(M - j0, jsplit);
+    }
     using XL = XTile<XT>;
     constexpr int BJW = 32 * JTW, W_BYTES = BJW * W_ROW_BYTES, W_DMA_PER_WAVE = JTW;
     constexpr int STAGE_BYTES = XL::BYTES + W_BYTES;
@@ -340,7 +371,7 @@ __global__ __launch_bounds__(NT, 2) void dist_dma_kernel(
                 }
 #pragma unroll
                 for (int it = 0; it < 4; ++it) {
-                    store_tile(acc[jt][it], xi[it], y, out, i0 + wi * 64 + it * 16 + lr, N, ldo, jb, lq, M, ovec);
+                    store_tile<SQ>(acc[jt][it], xi[it], y, out, i0 + wi * 64 + it * 16 + lr, N, ldo, jb, lq, M, ovec);
                     acc[jt][it] = d4_t{0.0, 0.0, 0.0, 0.0};
                 }
             }
@@ -355,7 +386,7 @@ __global__ __launch_bounds__(NT, 2) void dist_dma_kernel(
 // ---------------------------------------------------------------------------------------------
 // rows with missing entries: the chain of masked_bmu_kernel, every (row, prototype) stored
 // ---------------------------------------------------------------------------------------------
-template <int R>
+template <int R, bool SQ>
 __global__ __launch_bounds__(MT) void masked_dist_kernel(const double *__restrict__ X, int64_t N, int d, int64_t ldx,
                                                          const int32_t *__restrict__ nobs,
                                                          const double *__restrict__ Wt, int64_t ldwt, int M,
@@ -383,7 +414,7 @@ __global__ __launch_bounds__(MT) void masked_dist_kernel(const double *__restric
         if (j < M) {
 #pragma unroll
             for (int r = 0; r < R; ++r)
-                if (r < nrows) __builtin_nontemporal_store(sqrt(acc[r] * scale[r]), out + (i0 + r) * ldo + j);
+                if (r < nrows) put<SQ>(SQ ? acc[r] * scale[r] : sqrt(acc[r] * scale[r]), out + (i0 + r) * ldo + j);
         }
     }
 }
@@ -397,8 +428,9 @@ static int distances_check(int x_dtype, int64_t N, int64_t d, int64_t ldx, int64
     return DBGSOM_OK;
 }
 
-int launch_distances(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx, const double *W,
-                     int64_t M, const double *ww, double *out, int64_t ldo, hipStream_t s) {
+template <bool SQ>
+static int launch_distances_form(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx,
+                                 const double *W, int64_t M, const double *ww, double *out, int64_t ldo, hipStream_t s) {
     TRY_STATUS(distances_check(x_dtype, N, d, ldx, M, ldo));
     if (N == 0) return DBGSOM_OK;
     DBGSOM_REQUIRE(X && xx && W && ww && out, "null pointer");
@@ -407,12 +439,20 @@ int launch_distances(const void *X, int x_dtype, int64_t N, int64_t d, int64_t l
     DBGSOM_REQUIRE(nb <= 0x7fffffff, "too many samples for one launch");
     // 16-byte stores: every row base and every group of four prototypes on a 16-byte boundary
     const int ovec = is_aligned(out, 16) && (ldo % 2 == 0);
-    dim3 grid((unsigned)nb), block(NT);
-    if (bmu_dma_usable(X, x_dtype, d, ldx, W, M)) {
+    // squared form: as many shares of the prototypes (multiples of BJ) as bring the grid to two workgroups per CU
+    int shares = 1;
+    if (SQ && nb < SQ_FILL_BLOCKS) {
+        const int nch = (int)((M + BJ - 1) / BJ);
+        shares = (int)std::min<int64_t>((SQ_FILL_BLOCKS + nb - 1) / nb, nch);
+        shares = (nch + sq_share((int)M, shares) / BJ - 1) / (sq_share((int)M, shares) / BJ);   // none of them empty
+    }
+    const int64_t Mb = SQ ? std::min<int64_t>(M, sq_share((int)M, shares)) : M;   // prototypes per workgroup
+    dim3 grid((unsigned)nb, (unsigned)shares), block(NT);
+    if (bmu_dma_usable(X, x_dtype, d, ldx, W, Mb)) {
         // (dma_chunk_tiles' cost ratios were measured for the search; this epilogue has not been measured apart)
-        const int jtw = dma_chunk_tiles(x_dtype, M);
+        const int jtw = dma_chunk_tiles(x_dtype, Mb);
 #define DBGSOM_DIST_DMA(XT, JTW)                                                                          \
-    hipLaunchKernelGGL((dist_dma_kernel<XT, JTW>), grid, block, 0, s, (const XT *)X, N, (int)d, ldx, xx, W, \
+    hipLaunchKernelGGL((dist_dma_kernel<XT, JTW, SQ>), grid, block, 0, s, (const XT *)X, N, (int)d, ldx, xx, W, \
                        (int)M, ww, out, ldo, ovec)
         if (x_dtype == DBGSOM_F32) {
             if (jtw == 1) DBGSOM_DIST_DMA(float, 1);
@@ -429,13 +469,23 @@ int launch_distances(const void *X, int x_dtype, int64_t N, int64_t d, int64_t l
     const int xvec = is_aligned(X, 16) && ((ldx * xe) % 16 == 0);
     const int wvec = is_aligned(W, 16) && ((d * 8) % 16 == 0);
 #define DBGSOM_DIST(XT)                                                                                      \
-    hipLaunchKernelGGL((dist_kernel<XT>), grid, block, 0, s, (const XT *)X, N, (int)d, ldx, xx, W, (int)M, ww, \
+    hipLaunchKernelGGL((dist_kernel<XT, SQ>), grid, block, 0, s, (const XT *)X, N, (int)d, ldx, xx, W, (int)M, ww, \
                        xvec, wvec, out, ldo, ovec)
     if (x_dtype == DBGSOM_F32) DBGSOM_DIST(float);
     else if (x_dtype == DBGSOM_F64) DBGSOM_DIST(double);
     else DBGSOM_DIST(bf16_t);
 #undef DBGSOM_DIST
     return launch_status("dist_kernel");
+}
+
+int launch_distances(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx, const double *W,
+                     int64_t M, const double *ww, double *out, int64_t ldo, hipStream_t s) {
+    return launch_distances_form<false>(X, x_dtype, N, d, ldx, xx, W, M, ww, out, ldo, s);
+}
+
+int launch_distances_squared(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx,
+                             const double *W, int64_t M, const double *ww, double *out, int64_t ldo, hipStream_t s) {
+    return launch_distances_form<true>(X, x_dtype, N, d, ldx, xx, W, M, ww, out, ldo, s);
 }
 
 static int distances_masked_check(int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, int64_t ldo) {
@@ -447,8 +497,9 @@ static int distances_masked_check(int x_dtype, int64_t N, int64_t d, int64_t ldx
 
 // the distances of N rows to the transposed prototypes launch_masked_weights left in front of `ws` (the workspace
 // of bmu_masked_workspace_bytes: [Wt | n_obs | float32 rows only: their float64 copy])
-int launch_distances_masked_rows(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, double *out,
-                                 int64_t ldo, void *ws, size_t ws_bytes, hipStream_t s) {
+template <bool SQ>
+static int launch_distances_masked_form(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M,
+                                        double *out, int64_t ldo, void *ws, size_t ws_bytes, hipStream_t s) {
     TRY_STATUS(distances_masked_check(x_dtype, N, d, ldx, M, ldo));
     if (N == 0) return DBGSOM_OK;
     DBGSOM_REQUIRE(X && out && ws, "null pointer");
@@ -466,12 +517,22 @@ int launch_distances_masked_rows(const void *X, int x_dtype, int64_t N, int64_t 
     const double *X64 = f32 ? Xw : static_cast<const double *>(X);
     const int64_t ld64 = f32 ? d : ldx, ldwt = csr_wt_ld(M);
     if (N < MASKED_FEW_ROWS)
-        hipLaunchKernelGGL((masked_dist_kernel<MRS>), dim3((unsigned)((N + MRS - 1) / MRS)), dim3(MT), 0, s, X64, N, (int)d,
+        hipLaunchKernelGGL((masked_dist_kernel<MRS, SQ>), dim3((unsigned)((N + MRS - 1) / MRS)), dim3(MT), 0, s, X64, N, (int)d,
                            ld64, nobs, Wt, ldwt, (int)M, out, ldo);
     else
-        hipLaunchKernelGGL((masked_dist_kernel<MR>), dim3((unsigned)((N + MR - 1) / MR)), dim3(MT), 0, s, X64, N, (int)d,
+        hipLaunchKernelGGL((masked_dist_kernel<MR, SQ>), dim3((unsigned)((N + MR - 1) / MR)), dim3(MT), 0, s, X64, N, (int)d,
                            ld64, nobs, Wt, ldwt, (int)M, out, ldo);
     return launch_status("masked_dist_kernel");
+}
+
+int launch_distances_masked_rows(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, double *out,
+                                 int64_t ldo, void *ws, size_t ws_bytes, hipStream_t s) {
+    return launch_distances_masked_form<false>(X, x_dtype, N, d, ldx, M, out, ldo, ws, ws_bytes, s);
+}
+
+int launch_distances_masked_rows_squared(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M,
+                                         double *out, int64_t ldo, void *ws, size_t ws_bytes, hipStream_t s) {
+    return launch_distances_masked_form<true>(X, x_dtype, N, d, ldx, M, out, ldo, ws, ws_bytes, s);
 }
 
 }  // namespace dbgsom

@@ -270,6 +270,10 @@ struct dbgsom_ctx {
     // chunk's staged result at 256 MiB) and the staged result of a chunk
     int64_t distances_chunk_rows = 0;
     DevBuf pd_out;
+    // the k nearest prototypes of a query (kneighbors.hip): rows per slab of squared distances (0: as many as keep
+    // the slab at 64 MiB), the slab (masked rows: the masked search's workspace in front of it) and a chunk's result
+    int64_t kneighbors_slab_rows = 0;
+    DevBuf kn_ws, kn_idx, kn_dist;
     // The resident rows have missing entries (NaN): option "incomplete", set after a load and cleared by the next one.
     // What depends on the rows alone is made when the option is set, once per load: n_obs per row (mf_nobs) and, for
     // float32 rows, their float64 copy (mf_x64, N x d x 8 bytes of HBM).  The ordinary calls then refuse to compute
@@ -1163,7 +1167,7 @@ int dbgsom_ctx_create(int device, dbgsom_ctx **out) {
      &(c)->shard_gather, &(c)->sw, &(c)->wh_order, &(c)->wh_ws, &(c)->sc_ws, &(c)->sc_x, &(c)->sc_w, &(c)->sc_p, &(c)->sc_code, &(c)->sc_proba, &(c)->sc_cnt, &(c)->wt,  \
      &(c)->mk_ws, &(c)->mk_x, &(c)->mk_w, &(c)->mk_idx, &(c)->mk_dist, &(c)->mf_nobs, &(c)->mf_x64, &(c)->mf_wt, &(c)->mf_w,   \
      &(c)->mf_wn, &(c)->mf_idx, &(c)->mf_dist, &(c)->mf_kw, &(c)->mf_sums, &(c)->mf_acc_ws, &(c)->mf_sm_ws, &(c)->mf_scal, \
-     &(c)->pd_out}
+     &(c)->pd_out, &(c)->kn_ws, &(c)->kn_idx, &(c)->kn_dist}
 
 int dbgsom_ctx_destroy(dbgsom_ctx *c) {
     if (!c) return DBGSOM_OK;
@@ -1220,6 +1224,9 @@ int dbgsom_ctx_set_option(dbgsom_ctx *c, const char *name, int64_t v) {
     } else if (!strcmp(name, "distances_chunk_rows")) {
         DBGSOM_REQUIRE(v >= 0 && v <= ((int64_t)1 << 22), "distances_chunk_rows must be in [0, 2^22] (0 = by the result's size)");
         c->distances_chunk_rows = v;
+    } else if (!strcmp(name, "kneighbors_slab_rows")) {
+        DBGSOM_REQUIRE(v >= 0 && v <= ((int64_t)1 << 22), "kneighbors_slab_rows must be in [0, 2^22] (0 = by the slab's size)");
+        c->kneighbors_slab_rows = v;
     } else if (!strcmp(name, "sc_cap")) {
         DBGSOM_REQUIRE(v >= 0 && v <= 64, "sc_cap must be in [0, 64] (0 = the library's cap)");
         c->sc_cap = v;
@@ -1279,6 +1286,7 @@ int dbgsom_ctx_get_option(dbgsom_ctx *c, const char *name, int64_t *v) {
     else if (!strcmp(name, "sc_cap")) *v = c->sc_cap;
     else if (!strcmp(name, "masked_chunk_rows")) *v = c->masked_chunk_rows;
     else if (!strcmp(name, "distances_chunk_rows")) *v = c->distances_chunk_rows;
+    else if (!strcmp(name, "kneighbors_slab_rows")) *v = c->kneighbors_slab_rows;
     else if (!strcmp(name, "csr_densify_below")) *v = c->csr_densify_below;
     else if (!strcmp(name, "resident_csr")) *v = (c->xs.dtype >= 0 && c->xs.csr) ? 1 : 0;
     else if (!strcmp(name, "resident_nnz")) *v = (c->xs.dtype >= 0 && c->xs.csr) ? c->xs.nnz : 0;
@@ -2015,6 +2023,198 @@ int dbgsom_ctx_distances_query_masked(dbgsom_ctx *c, const void *Xq_host, int x_
     } while (0);
     rc = distances_finish(c, rc);
     if (c->mk_ws.cap + c->mk_x.cap > ((size_t)256 << 20)) { c->mk_ws.release(); c->mk_x.release(); }
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------
+// the k nearest prototypes of a query: csrc/kneighbors.hip.  Rows are staged as for the distance matrix above (same
+// chunks of host rows, same query placement, CSR rows expanded chunk by chunk); a chunk's squared distances live
+// slab by slab in kn_ws and only its Nc x k result comes down.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+int kneighbors_args(const char *fn, const dbgsom_ctx *c, int x_dtype, bool masked_or_csr, int64_t Nq, int64_t d, int64_t M,
+                    int k) {
+    TRY(distances_args(fn, c, x_dtype, masked_or_csr, Nq, d, M));
+    if (k < 1 || k > M) { set_error("%s: need 1 <= k <= M", fn); return DBGSOM_EINVAL; }
+    if (k > DBGSOM_MAX_NEIGHBORS) { set_error("%s: k must be <= DBGSOM_MAX_NEIGHBORS", fn); return DBGSOM_EINVAL; }
+    return DBGSOM_OK;
+}
+
+int kneighbors_reserve(dbgsom_ctx *c, int64_t rows, int64_t M, int k, bool staged) {
+    TRY(c->kn_ws.reserve(kneighbors_workspace_bytes(rows, M, c->kneighbors_slab_rows)));
+    if (!staged) return DBGSOM_OK;
+    TRY(c->kn_idx.reserve((size_t)rows * k * 8));
+    return c->kn_dist.reserve((size_t)rows * k * 8);
+}
+
+int kneighbors_down(dbgsom_ctx *c, int64_t n, int k, int64_t *idx_host, double *dist_host) {
+    DBGSOM_HIP_CHECK(hipMemcpyAsync(idx_host, c->kn_idx.p, (size_t)n * k * 8, hipMemcpyDeviceToHost, c->stream));
+    DBGSOM_HIP_CHECK(hipMemcpyAsync(dist_host, c->kn_dist.p, (size_t)n * k * 8, hipMemcpyDeviceToHost, c->stream));
+    c->x_down((size_t)n * k * 16);
+    return DBGSOM_OK;
+}
+
+// the placed rows of `s` against Wq: the result staged in kn_idx / kn_dist, and that down to the host
+int kneighbors_chunk_down(dbgsom_ctx *c, Samples &s, const DevBuf &Wq, const DevBuf &wwq, int64_t M, int k,
+                          int64_t *idx_host, double *dist_host) {
+    TRY(launch_kneighbors(s.Xb, s.bdtype, s.N, s.dp, s.dp, s.xx.as<double>(), Wq.as<double>(), M, wwq.as<double>(), k,
+                          c->kneighbors_slab_rows, c->kn_idx.as<int64_t>(), c->kn_dist.as<double>(), c->kn_ws.p,
+                          c->kn_ws.cap, c->stream));
+    return kneighbors_down(c, s.N, k, idx_host, dist_host);
+}
+
+int kneighbors_finish(dbgsom_ctx *c, int rc) {
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (rc == DBGSOM_OK && e != hipSuccess) {
+        set_error("hipStreamSynchronize failed: %s", hipGetErrorString(e));
+        rc = DBGSOM_EHIP;
+    }
+    if (c->kn_ws.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->kn_ws.release();   // do not sit on a large one-off slab
+    return rc;
+}
+
+}  // namespace
+
+int dbgsom_ctx_kneighbors_query(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host) {
+    TRY(kneighbors_args(__func__, c, x_dtype, false, Nq, d, M, k));
+    if (Nq == 0) return DBGSOM_OK;
+    DBGSOM_REQUIRE(Xq_host && W_host && idx_host && dist_host, "null pointer");
+    CTX_CHECK(c);
+    Samples &s = c->xq;
+    DevBuf Wq, wwq;
+    const int64_t dp = pad16(d);
+    const size_t es = dtype_size(x_dtype);
+    const int64_t chunk = distances_chunk(c, Nq, M, dp * (int64_t)es);
+    int rc = DBGSOM_OK;
+    do {
+        if ((rc = place_query_weights(c, Wq, wwq, W_host, M, d, dp))) break;
+        if ((rc = kneighbors_reserve(c, chunk, M, k, true))) break;
+        for (int64_t r0 = 0; r0 < Nq && rc == DBGSOM_OK; r0 += chunk) {
+            const int64_t n = std::min(chunk, Nq - r0);
+            if ((rc = place_host_samples(c, s, static_cast<const char *>(Xq_host) + (size_t)r0 * d * es, x_dtype, n, d, x_dtype)))
+                break;
+            rc = kneighbors_chunk_down(c, s, Wq, wwq, M, k, idx_host + r0 * k, dist_host + r0 * k);
+        }
+    } while (0);
+    rc = kneighbors_finish(c, rc);
+    Wq.release(); wwq.release();
+    drop_query_rows(s, QueryRows{Xq_host, false, d}, chunk * dp * (int64_t)es);
+    return rc;
+}
+
+int dbgsom_ctx_kneighbors_query_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d, int64_t ldx,
+                                       const double *W_host, int64_t M, int k, int64_t *idx_dev, double *dist_dev) {
+    TRY(kneighbors_args(__func__, c, x_dtype, false, Nq, d, M, k));
+    DBGSOM_REQUIRE(ldx >= d, "ldx must be >= d");
+    if (Nq == 0) return DBGSOM_OK;
+    DBGSOM_REQUIRE(Xq_dev && W_host && idx_dev && dist_dev, "null pointer");
+    CTX_CHECK(c);
+    Samples &s = c->xq;
+    DevBuf Wq, wwq;
+    const int64_t dp = pad16(d);
+    const QueryRows q{Xq_dev, true, ldx};
+    int rc = DBGSOM_OK;
+    do {
+        if ((rc = place_query_rows(c, s, q, x_dtype, Nq, d))) break;
+        if ((rc = place_query_weights(c, Wq, wwq, W_host, M, d, dp))) break;
+        if ((rc = kneighbors_reserve(c, Nq, M, k, false))) break;
+        rc = launch_kneighbors(s.Xb, s.bdtype, Nq, dp, dp, s.xx.as<double>(), Wq.as<double>(), M, wwq.as<double>(), k,
+                               c->kneighbors_slab_rows, idx_dev, dist_dev, c->kn_ws.p, c->kn_ws.cap, c->stream);
+    } while (0);
+    rc = kneighbors_finish(c, rc);
+    Wq.release(); wwq.release();
+    drop_query_rows(s, q, Nq * dp * (int64_t)dtype_size(x_dtype));
+    return rc;
+}
+
+int dbgsom_ctx_kneighbors_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const int32_t *indices_host,
+                                    const void *data_host, int x_dtype, int64_t Nq, int64_t d, int64_t nnz,
+                                    const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host) {
+    TRY(kneighbors_args(__func__, c, x_dtype, true, Nq, d, M, k));
+    DBGSOM_REQUIRE(indptr_host && nnz >= 0 && (nnz == 0 || (indices_host && data_host)), "bad arguments");
+    TRY(dbgsom_csr_check(indptr_host, indices_host, Nq, d, nnz));
+    if (Nq == 0) return DBGSOM_OK;
+    DBGSOM_REQUIRE(W_host && idx_host && dist_host, "null pointer");
+    CTX_CHECK(c);
+    Samples &s = c->xq;
+    DevBuf Wq, wwq;
+    const int64_t dp = pad16(d);
+    const size_t es = dtype_size(x_dtype);
+    const int64_t chunk = distances_chunk(c, Nq, M, dp * (int64_t)es);
+    int rc = DBGSOM_OK;
+    do {
+        // the three arrays go up whole; row chunks of them are expanded into the dense rows the kernel reads
+        s.release();
+        if ((rc = s.indptr.reserve((size_t)(Nq + 1) * 8))) break;
+        if ((rc = s.indices.reserve((size_t)(nnz > 0 ? nnz : 1) * 4))) break;
+        if ((rc = s.data.reserve((size_t)(nnz > 0 ? nnz : 1) * es))) break;
+        hipError_t e = hipMemcpyAsync(s.indptr.p, indptr_host, (size_t)(Nq + 1) * 8, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess && nnz > 0)
+            e = hipMemcpyAsync(s.indices.p, indices_host, (size_t)nnz * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess && nnz > 0)
+            e = hipMemcpyAsync(s.data.p, data_host, (size_t)nnz * es, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
+        c->x_up((size_t)nnz * (4 + es) + (size_t)(Nq + 1) * 8);
+        if ((rc = place_query_weights(c, Wq, wwq, W_host, M, d, dp))) break;
+        if ((rc = kneighbors_reserve(c, chunk, M, k, true))) break;
+        if ((rc = s.own.reserve((size_t)chunk * dp * es))) break;
+        for (int64_t r0 = 0; r0 < Nq && rc == DBGSOM_OK; r0 += chunk) {
+            const int64_t n = std::min(chunk, Nq - r0);
+            const CsrView rows{s.indptr.as<int64_t>() + r0, s.indices.as<int32_t>(), s.data.p};   // (indptr is absolute)
+            if ((rc = launch_csr_densify(rows, x_dtype, n, d, dp, s.own.p, c->stream))) break;
+            s.N = n; s.d = d; s.dp = dp; s.dtype = x_dtype; s.csr = false; s.nnz = 0;
+            s.X = s.own.p;
+            if ((rc = finish_samples(c, s, false))) break;
+            rc = kneighbors_chunk_down(c, s, Wq, wwq, M, k, idx_host + r0 * k, dist_host + r0 * k);
+        }
+    } while (0);
+    rc = kneighbors_finish(c, rc);
+    Wq.release(); wwq.release();
+    s.release();
+    return rc;
+}
+
+int dbgsom_ctx_kneighbors_query_masked(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                       const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host) {
+    TRY(kneighbors_args(__func__, c, x_dtype, true, Nq, d, M, k));
+    TRY(masked_check_shape(x_dtype, Nq, d, d, M, 1));
+    if (Nq == 0) return DBGSOM_OK;
+    DBGSOM_REQUIRE(Xq_host && W_host && idx_host && dist_host, "null pointer");
+    const int64_t bad = first_row_without_entries(Xq_host, x_dtype, Nq, d);
+    if (bad >= 0) {
+        set_error("dbgsom_ctx_kneighbors_query_masked: row %lld has no observed entry", (long long)bad);
+        return DBGSOM_EINVAL;
+    }
+    CTX_CHECK(c);
+    const int64_t chunk = distances_chunk(c, Nq, M, d * 8);
+    const size_t es = dtype_size(x_dtype);
+    int rc = DBGSOM_OK;
+    do {
+        if ((rc = c->kn_ws.reserve(kneighbors_masked_workspace_bytes(x_dtype, chunk, d, M, c->kneighbors_slab_rows)))) break;
+        if ((rc = c->mk_x.reserve((size_t)chunk * d * es))) break;
+        if ((rc = c->mk_w.reserve((size_t)M * d * 8))) break;
+        if ((rc = c->kn_idx.reserve((size_t)chunk * k * 8))) break;
+        if ((rc = c->kn_dist.reserve((size_t)chunk * k * 8))) break;
+        hipError_t e = hipMemcpyAsync(c->mk_w.p, W_host, (size_t)M * d * 8, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
+        if ((rc = launch_masked_weights(c->mk_w.as<double>(), M, d, d, c->kn_ws.p, c->stream))) break;
+        for (int64_t r0 = 0; r0 < Nq && rc == DBGSOM_OK; r0 += chunk) {
+            const int64_t n = std::min(chunk, Nq - r0);
+            e = hipMemcpyAsync(c->mk_x.p, static_cast<const char *>(Xq_host) + (size_t)r0 * d * es, (size_t)n * d * es,
+                               hipMemcpyHostToDevice, c->stream);
+            if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
+            c->x_up((size_t)n * d * es);
+            if ((rc = launch_kneighbors_masked_rows(c->mk_x.p, x_dtype, n, d, d, M, k, c->kneighbors_slab_rows,
+                                                    c->kn_idx.as<int64_t>(), c->kn_dist.as<double>(), c->kn_ws.p,
+                                                    c->kn_ws.cap, c->stream)))
+                break;
+            rc = kneighbors_down(c, n, k, idx_host + r0 * k, dist_host + r0 * k);
+        }
+    } while (0);
+    rc = kneighbors_finish(c, rc);
+    if (c->mk_x.cap > ((size_t)256 << 20)) c->mk_x.release();
     return rc;
 }
 

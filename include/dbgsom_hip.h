@@ -74,6 +74,8 @@ extern "C" {
 
 /* prototype-count limit of the accumulate step (per-block LDS histogram) */
 #define DBGSOM_MAX_PROTOTYPES 16000
+/* most neighbours per row of the dbgsom_kneighbors* calls (the selection keeps them in registers) */
+#define DBGSOM_MAX_NEIGHBORS 32
 
 int dbgsom_abi_version(void);
 const char *dbgsom_last_error(void);
@@ -576,6 +578,55 @@ int dbgsom_ctx_distances_query_csr(dbgsom_ctx *ctx, const int64_t *indptr_host, 
                                    const double *W_host, int64_t M, double *out_host);
 int dbgsom_ctx_distances_query_masked(dbgsom_ctx *ctx, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
                                       const double *W_host, int64_t M, double *out_host);
+
+/* ---- the k nearest prototypes of every row (csrc/kneighbors.hip) -------------------------------------------
+ * idx[i * k + t], dist[i * k + t], t = 0 .. k - 1: the k prototypes of row i with the smallest (r_ij, j) in
+ * lexicographic order, ascending, where r_ij = max((|x_i|^2 + (-2 <x_i, w_j>)) + |w_j|^2, 0) is the squared value
+ * of the search's own fma chain (for rows with missing entries: d / n_obs * sum over the observed (x_k - w_k)^2),
+ * and dist = sqrt(r), taken after the selection, float64, no float32 rounding.  The selection is on r: of two
+ * distinct r under one square root the smaller comes first whatever the indices.  So columns 0..1 are what
+ * dbgsom_bmu reports for k = 2, and dist[i * k + t] is entry idx[i * k + t] of row i of dbgsom_distances, bit for
+ * bit.  A pair whose r is not below +inf (NaN, +inf) is never reported; slots left unfilled hold (inf, -1).
+ * 1 <= k <= min(M, DBGSOM_MAX_NEIGHBORS).  Argument errors (k, ldr < M, a null pointer, a short workspace:
+ * DBGSOM_ENOMEM with both sizes in the message) are reported before any launch.
+ *
+ * dbgsom_topk_rows: the selection alone on a caller's matrix R of squared values, N rows of M entries ldr >= M
+ * apart; idx (int64) and dist (float64) are N x k, contiguous.
+ * dbgsom_kneighbors: arguments as dbgsom_distances.  The rows are worked in slabs of slab_rows rows (0: as many,
+ * in multiples of 128, as keep a slab at 64 MiB): the squared distances of a slab go into the workspace (rows
+ * M rounded up to even apart, ordinary stores), the selection reads them back while they are still in cache.
+ * Nothing grows with N x M: dbgsom_kneighbors_workspace_bytes(N, M, slab_rows) is one slab.  The workspace
+ * must be 16-byte aligned.
+ * dbgsom_kneighbors_masked: rows with missing entries (NaN), arguments as dbgsom_distances_masked; the workspace
+ * is that of dbgsom_kneighbors_masked_workspace_bytes (the masked search's for one slab of rows, then the slab). */
+int dbgsom_topk_rows(const double *R_dev, int64_t N, int64_t M, int64_t ldr, int k, int64_t *idx_dev,
+                     double *dist_dev, void *stream);
+size_t dbgsom_kneighbors_workspace_bytes(int64_t N, int64_t M, int64_t slab_rows);
+size_t dbgsom_kneighbors_masked_workspace_bytes(int x_dtype, int64_t N, int64_t d, int64_t M, int64_t slab_rows);
+int dbgsom_kneighbors(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx_dev,
+                      const double *W_dev, int64_t M, const double *ww_dev, int k, int64_t slab_rows,
+                      int64_t *idx_dev, double *dist_dev, void *workspace_dev, size_t workspace_bytes,
+                      void *stream);
+int dbgsom_kneighbors_masked(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx,
+                             const double *W_dev, int64_t M, int64_t ldw, int k, int64_t slab_rows,
+                             int64_t *idx_dev, double *dist_dev, void *workspace_dev, size_t workspace_bytes,
+                             void *stream);
+/* The same on a context, each call staging its rows as its dbgsom_ctx_distances_query* namesake does (chunks of
+ * "distances_chunk_rows" host rows, query placement, CSR expanded chunk by chunk, traffic counters, status codes);
+ * the slab is ctx option "kneighbors_slab_rows" rows (0, the default: as above).  idx / dist: Nq x k, contiguous;
+ * only Nq x k x 16 bytes of result come down per host-facing call.  _device: idx_dev / dist_dev are written by
+ * the kernel; nothing of X or of the result crosses PCIe. */
+int dbgsom_ctx_kneighbors_query(dbgsom_ctx *ctx, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host);
+int dbgsom_ctx_kneighbors_query_device(dbgsom_ctx *ctx, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d,
+                                       int64_t ldx, const double *W_host, int64_t M, int k, int64_t *idx_dev,
+                                       double *dist_dev);
+int dbgsom_ctx_kneighbors_query_csr(dbgsom_ctx *ctx, const int64_t *indptr_host, const int32_t *indices_host,
+                                    const void *data_host, int x_dtype, int64_t Nq, int64_t d, int64_t nnz,
+                                    const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host);
+int dbgsom_ctx_kneighbors_query_masked(dbgsom_ctx *ctx, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                       const double *W_host, int64_t M, int k, int64_t *idx_host,
+                                       double *dist_host);
 
 /* ---- fit on rows with missing entries (csrc/masked_fit.hip, csrc/smooth.hip) ---------------------------
  * One epoch on prototypes W (M x d, complete), hop matrix and sigma, NaN marking a missing entry of X:
