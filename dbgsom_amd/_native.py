@@ -154,6 +154,19 @@ SIGNATURES = {
     "dbgsom_smooth_masked": (_ci, [_vp, _i64, _i64, _vp, _dbl, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dbgsom_ctx_bmu_masked": (_ci, [_vp, _vp, _i64, _ci, _vp, _vp]),
     "dbgsom_ctx_epoch_masked": (_ci, [_vp, _vp, _i64, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dbgsom_bmu_manhattan_workspace_bytes": (_sz, [_ci, _i64, _i64, _i64]),
+    "dbgsom_bmu_manhattan": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _i64, _i64, _ci, _vp, _vp, _vp, _sz, _vp]),
+    "dbgsom_distances_manhattan": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _sz, _vp]),
+    "dbgsom_kneighbors_manhattan_workspace_bytes": (_sz, [_ci, _i64, _i64, _i64, _i64]),
+    "dbgsom_kneighbors_manhattan": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _i64, _i64, _ci, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "dbgsom_ctx_bmu_manhattan": (_ci, [_vp, _vp, _i64, _ci, _vp, _vp]),
+    "dbgsom_ctx_epoch_manhattan": (_ci, [_vp, _vp, _i64, _dbl, _dbl, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dbgsom_ctx_bmu_query_manhattan": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _ci, _vp, _vp]),
+    "dbgsom_ctx_bmu_query_manhattan_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _ci, _vp, _vp]),
+    "dbgsom_ctx_distances_query_manhattan": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _vp]),
+    "dbgsom_ctx_distances_query_manhattan_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _vp, _i64]),
+    "dbgsom_ctx_kneighbors_query_manhattan": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _ci, _vp, _vp]),
+    "dbgsom_ctx_kneighbors_query_manhattan_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _ci, _vp, _vp]),
     "dbgsom_topofn_workspace_bytes": (_sz, [_i64, _ci]),
     "dbgsom_topofn": (_ci, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dbgsom_topofn_timing": (_ci, [_ci]),

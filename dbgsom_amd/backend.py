@@ -118,6 +118,37 @@ class HotPathBackend:
         ``bmu_masked``."""
         raise NotImplementedError
 
+    # -- metric="manhattan": dist(x, w) = sum_k |x_k - w_k| in float64, k ascending, one accumulator per pair; float32
+    # rows widened exactly first; no square root, no clamp; winners by (dist, index); a pair whose distance is not
+    # below +inf is never reported (index -1, distance inf).  X: a dense host array or a device array.
+    _metric = "euclidean"
+
+    def set_metric(self, metric):
+        """The metric of the search of the RESIDENT rows from here to the next ``load`` / ``release``: "euclidean",
+        or "manhattan" -- ``bmu(W, k)`` is then the L1 search, ``epoch_manhattan`` the epoch, and the reductions over
+        the resident rows are the host defaults of this class over that ``bmu``."""
+        if metric not in ("euclidean", "manhattan"):
+            raise ValueError(f"metric must be 'euclidean' or 'manhattan', got {metric!r}")
+        self._metric = metric
+
+    def bmu_manhattan(self, W, k, X):
+        """``bmu(W, k, X=X)`` under the Manhattan metric -> (distances, winners) in ``bmu``'s shapes."""
+        raise NotImplementedError
+
+    def distances_manhattan(self, W, X):
+        """``distances(W, X)`` under the Manhattan metric: ``bmu_manhattan``'s distances are its smallest entries."""
+        raise NotImplementedError
+
+    def kneighbors_manhattan(self, W, k, X):
+        """``kneighbors(W, k, X)`` under the Manhattan metric: the k smallest ``(dist, j)`` per row, ascending;
+        ``distances_manhattan(W, X)`` gathered at the indices, bit for bit."""
+        raise NotImplementedError
+
+    def epoch_manhattan(self, W, hop, sigma, gamma, layout="compact", want_assignments=False, n_classes=0):
+        """``epoch`` with the L1 search in front of the unchanged sums and smoothing -> EpochResult.  The prototypes
+        are handed over with every call."""
+        raise NotImplementedError
+
     def exp_similarity(self, distances, gamma):
         raise NotImplementedError
 
@@ -718,6 +749,7 @@ class HipBackend(HotPathBackend):
         self._sw = None          # (a load detaches the weights of the rows that were resident)
         self._weighted = False
         self._incomplete = False
+        self._metric = "euclidean"
 
     def read_samples(self, rows):
         """Rows of the resident samples as float64 (exactly widened)."""
@@ -779,11 +811,15 @@ class HipBackend(HotPathBackend):
             self._require_loaded()
             if self._incomplete and W is RESIDENT:
                 raise ValueError("no prototypes stay resident between masked epochs")
-            keep, p, M, rf = self._w_arg(W, d=self._d if self._incomplete else None)
+            if self._manhattan and W is RESIDENT:
+                raise ValueError("no prototypes stay resident between Manhattan epochs")
+            keep, p, M, rf = self._w_arg(W, d=self._d if self._incomplete or self._manhattan else None)
             N = self._N
             idx = np.empty((N, k), dtype=np.int64)
             dist = np.empty((N, k), dtype=np.float64)
-            if self._incomplete:   # rows with missing entries: the search over the observed entries of every row
+            if self._manhattan:    # metric="manhattan": the L1 search of the resident rows
+                self._call("dbgsom_ctx_bmu_manhattan", self._ctx, p, M, int(k), idx.ctypes.data, dist.ctypes.data)
+            elif self._incomplete:   # rows with missing entries: the search over the observed entries of every row
                 self._call("dbgsom_ctx_bmu_masked", self._ctx, p, M, int(k), idx.ctypes.data, dist.ctypes.data)
             else:
                 self._call("dbgsom_ctx_bmu", self._ctx, p, M, int(k), rf, idx.ctypes.data, dist.ctypes.data)
@@ -843,7 +879,7 @@ class HipBackend(HotPathBackend):
     def resident_winners(self, W):
         """``bmu(W, 1)[1]`` of the resident samples without the distances' trip to the host."""
         self._require_loaded()
-        if self._incomplete:
+        if self._incomplete or self._manhattan:
             return self.bmu(W, 1)[1]
         keep, p, M, rf = self._w_arg(W)
         idx = np.empty(self._N, dtype=np.int64)
@@ -1005,6 +1041,108 @@ class HipBackend(HotPathBackend):
             self._call("dbgsom_ctx_kneighbors_query_masked", self._ctx, X.ctypes.data, _x_dtype_code(X.dtype), N,
                        X.shape[1], W64.ctypes.data, M, k, idx.ctypes.data, dist.ctypes.data)
         return dist, idx
+
+    # -- metric="manhattan" (csrc/manhattan.hip) --------------------------------------------------------
+    _manhattan = property(lambda self: self._metric == "manhattan")
+
+    def _manhattan_args(self, W, X):
+        """-> (W64, X as the calls take it, on_device, (code, N, d, ldx))"""
+        W64 = np.ascontiguousarray(W, dtype=np.float64)
+        if is_sparse(X):
+            raise TypeError("the Manhattan calls take dense rows")
+        if is_device_array(X):
+            rows = self._device_rows(X)
+            on_device = True
+        else:
+            X = np.ascontiguousarray(X)
+            if X.dtype not in (np.float32, np.float64):
+                X = X.astype(np.float64)
+            if X.ndim != 2:
+                raise ValueError("prototype / sample feature mismatch")
+            rows = (_x_dtype_code(X.dtype), X.shape[0], X.shape[1], X.shape[1])
+            on_device = False
+        if W64.ndim != 2 or W64.shape[1] != rows[2]:
+            raise ValueError("prototype / sample feature mismatch")
+        return W64, X, on_device, rows
+
+    def bmu_manhattan(self, W, k, X):
+        """The L1 search on the device, host rows in chunks of ``masked_chunk_rows`` rows; for rows in HBM distances
+        and winners are arrays on X's device that the search writes itself."""
+        W64, X, on_device, (code, N, d, ldx) = self._manhattan_args(W, X)
+        k = int(k)
+        if on_device:
+            idx, dist = device_empty(X, (N, k), "int64"), device_empty(X, (N, k), "float64")
+            if N:
+                self._producer_done(X)
+                self._call("dbgsom_ctx_bmu_query_manhattan_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code, N, d,
+                           ldx, W64.ctypes.data, W64.shape[0], k, ctypes.c_void_p(idx.data_ptr()),
+                           ctypes.c_void_p(dist.data_ptr()))
+        else:
+            idx, dist = np.empty((N, k), dtype=np.int64), np.empty((N, k), dtype=np.float64)
+            self._call("dbgsom_ctx_bmu_query_manhattan", self._ctx, X.ctypes.data if N else None, code, N, d,
+                       W64.ctypes.data, W64.shape[0], k, idx.ctypes.data, dist.ctypes.data)
+        if k == 1:
+            return dist.reshape(-1), idx.reshape(-1)
+        return dist, idx
+
+    def distances_manhattan(self, W, X):
+        """Every distance of the L1 search, stored: host rows in chunks of ``distances_chunk_rows`` rows; for rows in
+        HBM the result is a float64 array on their device that the kernel writes itself."""
+        W64, X, on_device, (code, N, d, ldx) = self._manhattan_args(W, X)
+        M = W64.shape[0]
+        if on_device:
+            out = device_empty(X, (N, M), "float64")
+            if N:
+                self._producer_done(X)
+                self._call("dbgsom_ctx_distances_query_manhattan_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code,
+                           N, d, ldx, W64.ctypes.data, M, ctypes.c_void_p(out.data_ptr()), M)
+            return out
+        out = np.empty((N, M), dtype=np.float64)
+        if N:
+            self._call("dbgsom_ctx_distances_query_manhattan", self._ctx, X.ctypes.data, code, N, d, W64.ctypes.data, M,
+                       out.ctypes.data)
+        return out
+
+    def kneighbors_manhattan(self, W, k, X):
+        """The k nearest prototypes under the L1 distance: a slab of ``kneighbors_slab_rows`` rows of distances stays
+        on the device, the selection kernel of csrc/kneighbors.hip reads it back and stores what it selected on."""
+        W64, X, on_device, (code, N, d, ldx) = self._manhattan_args(W, X)
+        M, k = W64.shape[0], int(k)
+        self._check_neighbors(k, M)
+        if on_device:
+            dist, idx = device_empty(X, (N, k), "float64"), device_empty(X, (N, k), "int64")
+            if N:
+                self._producer_done(X)
+                self._call("dbgsom_ctx_kneighbors_query_manhattan_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code,
+                           N, d, ldx, W64.ctypes.data, M, k, ctypes.c_void_p(idx.data_ptr()),
+                           ctypes.c_void_p(dist.data_ptr()))
+            return dist, idx
+        dist, idx = np.empty((N, k), dtype=np.float64), np.empty((N, k), dtype=np.int64)
+        if N:
+            self._call("dbgsom_ctx_kneighbors_query_manhattan", self._ctx, X.ctypes.data, code, N, d, W64.ctypes.data, M, k,
+                       idx.ctypes.data, dist.ctypes.data)
+        return dist, idx
+
+    def epoch_manhattan(self, W, hop, sigma, gamma, layout="compact", want_assignments=False, n_classes=0):
+        """One epoch under the Manhattan metric as ONE call of the C ABI: the L1 search of the resident rows
+        (csrc/manhattan.hip) in front of the sums and the smoothing of ``epoch`` (dbgsom_ctx_epoch_manhattan)."""
+        self._require_loaded()
+        if W is RESIDENT:
+            raise ValueError("no prototypes stay resident between Manhattan epochs")
+        keep, p, M, _ = self._w_arg(W, d=self._d)
+        self._topology(hop, M)
+        Wn, chg, E, a = np.empty((M, self._d)), np.empty(1), np.empty(M), np.empty(M)
+        want = want_assignments or n_classes > 0
+        win = np.empty(self._N, dtype=np.int64) if want else None
+        dist = np.empty(self._N) if want else None
+        self._call("dbgsom_ctx_epoch_manhattan", self._ctx, p, M, float(gamma), float(sigma), _native.LAYOUTS[layout],
+                   Wn.ctypes.data, chg.ctypes.data, E.ctypes.data, a.ctypes.data,
+                   None if win is None else win.ctypes.data, None if dist is None else dist.ctypes.data)
+        self._last_M = M
+        res = EpochResult(Wn, float(chg[0]), E, a, win if want_assignments else None, dist if want_assignments else None)
+        if n_classes > 0:
+            res.class_hist = self.class_histogram(win, n_classes, M)
+        return res
 
     def query_filter_applies(self, N, d, M, k=1):
         """Whether a k-BMU query on N other samples would go through the filtered search."""
@@ -1339,10 +1477,11 @@ class HipBackend(HotPathBackend):
         self._call("dbgsom_ctx_weighted_column_sums", self._ctx, mean.ctypes.data, s2.ctypes.data)
         return s1, s2
 
-    # (rows with missing entries: the O(N)-per-fit reductions are HotPathBackend's host defaults over the masked bmu)
+    # (rows with missing entries, metric="manhattan": the O(N)-per-fit reductions are HotPathBackend's host defaults
+    #  over the masked / the L1 bmu)
     def quantization_error(self, W) -> float:
         self._require_loaded()
-        if self._incomplete:
+        if self._incomplete or self._manhattan:
             return super().quantization_error(W)
         keep, p, M, rf = self._w_arg(W)
         out = np.empty(2)
@@ -1351,7 +1490,7 @@ class HipBackend(HotPathBackend):
 
     def topographic_error_count(self, W, coords) -> int:
         self._require_loaded()
-        if self._incomplete:
+        if self._incomplete or self._manhattan:
             return super().topographic_error_count(W, coords)
         keep, p, M, rf = self._w_arg(W)
         xy = np.ascontiguousarray(coords, dtype=np.int32)
@@ -1364,7 +1503,7 @@ class HipBackend(HotPathBackend):
     def node_statistics(self, W, sigma):
         """-> (hit_counts (M,), density_sums (M,)) of BaseSom._calculate_node_statistics."""
         self._require_loaded()
-        if self._incomplete:
+        if self._incomplete or self._manhattan:
             return super().node_statistics(W, sigma)
         keep, p, M, rf = self._w_arg(W)
         hits, dens = np.empty(M), np.empty(M)
@@ -1382,7 +1521,7 @@ class HipBackend(HotPathBackend):
     def class_histogram(self, winners, n_classes, M):
         """(M, n_classes) int64 over all ranks (float64 summed weights with weights attached);
         winners=None: the last epoch's (still in HBM)."""
-        if self._incomplete:
+        if self._incomplete or self._manhattan:
             return super().class_histogram(winners, n_classes, M)
         idx = None if winners is None else np.ascontiguousarray(winners, dtype=np.int64)
         if self._weighted:
@@ -1434,6 +1573,7 @@ class HipBackend(HotPathBackend):
         self._hop_key = None
         self._weighted = False
         self._incomplete = False
+        self._metric = "euclidean"
         self._sw = None
 
     def __del__(self):

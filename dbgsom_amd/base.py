@@ -114,7 +114,8 @@ class BaseSom(BaseEstimator):
         self.random_state = random_state
         self.convergence_treshold = convergence_treshold
         self.max_neurons = max_neurons
-        self.metric = metric  # stored, never read: distances are always Euclidean (as in the reference)
+        self.metric = metric  # read by the BMU search alone: "manhattan" / "cityblock" / "l1" is the L1 search, every
+        #                       other string the Euclidean one (BaseSom._is_manhattan); the update is the same
         self.threshold_method = threshold_method
         self.growth_criterion = growth_criterion
         self.min_samples_vertical_growth = min_samples_vertical_growth
@@ -188,6 +189,7 @@ class BaseSom(BaseEstimator):
         host)."""
         self._accepts_nan()   # (validates the parameter)
         self._incomplete_fit = False
+        self._manhattan_fit = False
         if isinstance(X, DeviceSamples):   # a Voronoi subset that already lives in HBM (f-4)
             if y is not None:
                 y = np.asarray(y)
@@ -195,6 +197,7 @@ class BaseSom(BaseEstimator):
                 sample_weight = np.ascontiguousarray(sample_weight, dtype=np.float64)
         else:
             X, y = self._check_input_data(X, y)
+            self._manhattan_fit = self._check_manhattan_fit(X, sample_weight)
             self._incomplete_fit = self._check_incomplete_fit(X, sample_weight)
             sample_weight = self._check_sample_weight(sample_weight, X)
         if y is not None:
@@ -211,6 +214,8 @@ class BaseSom(BaseEstimator):
             X = DeviceSamples(engine, source=X)
         self._load_resident(X)  # samples go to HBM once and stay there for the whole fit
         try:
+            if self._manhattan_fit:
+                engine.set_metric("manhattan")   # (the search of the resident rows, until the release below)
             self._attach_sample_weight(X, sample_weight)
             self._initialize_som(X)
             self._grow_som(X, y)
@@ -227,11 +232,51 @@ class BaseSom(BaseEstimator):
         finally:
             self._resident = None
             self._incomplete_fit = False
+            if self._manhattan_fit:
+                self._manhattan_fit = False
+                engine.set_metric("euclidean")   # (the backend object may serve another fit)
             self._sw = self._sw_global = None
             if hasattr(engine, "set_sample_weight") and getattr(engine, "_sw", None) is not None:
                 engine.set_sample_weight(None)   # (the backend object may serve another fit)
             engine.release()
         return self
+
+    # -- metric="manhattan" ----------------------------------------------------------------------------
+    _MANHATTAN = ("manhattan", "cityblock", "l1")
+    _manhattan_fit = False    # this fit runs under the Manhattan metric
+
+    def _is_manhattan(self) -> bool:
+        """Whether the best-matching-unit search is the L1 one: ``dist(x, w) = sum_k |x_k - w_k|`` in float64.
+        ``metric`` must be a string; "manhattan", "cityblock" and "l1" name the L1 search, every other string is the
+        Euclidean search as ever."""
+        if not isinstance(self.metric, str):
+            raise ValueError(f"metric must be a string, got {self.metric!r}")
+        return self.metric in self._MANHATTAN
+
+    def _refuse_manhattan(self, what: str, way_out: str = "") -> None:
+        raise ValueError(f"metric={self.metric!r} (Manhattan) does not support {what}" + (f": {way_out}" if way_out else ""))
+
+    def _check_manhattan_query(self, X) -> None:
+        """The refusals of a query under the Manhattan metric, on the host before anything is uploaded.  (A device
+        array never holds NaN here: ``_check_device_array`` has refused it, under ``missing_values`` by name.)"""
+        if is_sparse(X):
+            self._refuse_manhattan("scipy sparse X", "pass X.toarray()")
+        if self._accepts_nan() and isinstance(X, np.ndarray) and np.isnan(X).any():
+            self._refuse_manhattan(f"rows with missing entries (missing_values={self.missing_values!r} and NaN in X)",
+                                   "impute them first, or use metric='euclidean'")
+
+    def _check_manhattan_fit(self, X, sample_weight) -> bool:
+        """Whether this fit runs under the Manhattan metric; its refusals, on the host before anything is uploaded."""
+        if not self._is_manhattan():
+            return False
+        self._check_manhattan_query(X)
+        if sample_weight is not None:
+            self._refuse_manhattan("sample_weight", "repeat the rows instead (np.repeat(X, w, axis=0))")
+        if self.vertical_growth:
+            self._refuse_manhattan("vertical_growth=True")
+        if self.sharded_input or dist_info()[1] > 1:
+            self._refuse_manhattan("sharded_input or a process group of more than one rank", "it takes one process")
+        return True
 
     # -- rows with missing entries in fit (missing_values="nan-fit") ---------------------------------
     _incomplete_fit = False   # this fit runs in incomplete mode: X is dense and holds at least one NaN
@@ -747,8 +792,10 @@ class BaseSom(BaseEstimator):
         # refreshed at growth steps and at the end.  Backends without resident prototypes (the
         # oracle's CPU stand-in in the tests) get the matrix handed over every epoch.
         # Rows with missing entries: nothing stays resident between masked epochs, whatever the backend can do.
+        # The same under metric="manhattan": the L1 search reads the prototypes it is handed.
         incomplete = self._incomplete_fit
-        resident = hasattr(engine, "write_weight_rows") and not incomplete
+        manhattan = self._manhattan_fit
+        resident = hasattr(engine, "write_weight_rows") and not incomplete and not manhattan
         on_device = False     # the current prototypes are in HBM, lat.W is stale
         ran = False
         self._growth_epochs = []
@@ -762,12 +809,25 @@ class BaseSom(BaseEstimator):
             if incomplete:
                 res = engine.epoch_masked(w_in, self._distance_matrix, self._calculate_current_sigma(),
                                           self._gamma(), n_classes=n_classes if need_assign else 0)
+            elif manhattan:
+                res = engine.epoch_manhattan(w_in, self._distance_matrix, self._calculate_current_sigma(),
+                                             self._gamma(), self.centres_layout,
+                                             n_classes=n_classes if need_assign else 0)
             else:
                 res = engine.epoch(w_in, self._distance_matrix, self._calculate_current_sigma(),
                                    self._gamma(), self.centres_layout,
                                    n_classes=n_classes if need_assign else 0,
                                    **({"keep_on_device": True} if resident else {}))
             ran = True
+            if manhattan and not np.isfinite(res.new_weights).all():
+                # L1 distances grow with the number of features while gamma = 1 / total variance does not: once
+                # gamma d^2 is above 53 ln 2 = 36.7 the sample kernel 1 - sqrt(1 - exp(-gamma d^2)) is 0.0 exactly,
+                # and a neuron all of whose rows are that far has the centre 0 / 0 (as in the reference's update)
+                raise ValueError(f"metric={self.metric!r} (Manhattan): the update gave prototypes that are not finite in "
+                                 f"epoch {epoch}: the sample kernel 1 - sqrt(1 - exp(-d^2 / total variance)) is 0 for "
+                                 "every row of a neuron, because squared L1 distances grow with the square of the number of "
+                                 "features and the variance only with the number; reduce the features (a projection) or "
+                                 "use metric='euclidean'")
             if resident:
                 on_device = True
             else:
@@ -867,8 +927,11 @@ class BaseSom(BaseEstimator):
         """Distances and indices of the n_bmu best matching units (BaseSom.py:446-464)."""
         engine = self._engine()
         if self._is_resident(data):
-            dist, idx = engine.bmu(self.weights_, n_bmu)
+            dist, idx = engine.bmu(self.weights_, n_bmu)   # (a fit under metric="manhattan": the L1 search, set_metric)
             return self._gather_rows(dist), self._gather_rows(idx)
+        if self._is_manhattan():
+            self._check_manhattan_query(data)
+            return engine.bmu_manhattan(self.weights_, n_bmu, data)
         if self._accepts_nan() and isinstance(data, np.ndarray):
             rows = self._incomplete_rows(data)
             if rows.size:
@@ -936,7 +999,8 @@ class BaseSom(BaseEstimator):
         ``predict`` takes: a dense array (the result is a NumPy array), a device array (a float64 tensor on X's
         device that the GPU writes itself; X and the result never touch the host), scipy sparse rows (the result
         of the dense call on ``X.toarray()``), and with ``missing_values`` set rows with NaN, whose entries are
-        ``sqrt(d / n_obs * sum over the observed (x_k - w_k)^2)``.  Only this map's prototypes are used (not the
+        ``sqrt(d / n_obs * sum over the observed (x_k - w_k)^2)``.  Under ``metric="manhattan"`` the entries are
+        ``sum_k |x_k - w_k|`` in float64 (dense X and tensors only).  Only this map's prototypes are used (not the
         child maps of vertical growth); the call is local to the process."""
         check_is_fitted(self)
         W = self.weights_
@@ -950,6 +1014,9 @@ class BaseSom(BaseEstimator):
         if X.shape[0] == 0:
             return np.empty((0, len(W)), dtype=np.float64)
         engine = self._engine()
+        if self._is_manhattan():   # sum_k |x_k - w_k|, the arithmetic of the L1 search bit for bit
+            self._check_manhattan_query(X)
+            return engine.distances_manhattan(W, X)
         if self._accepts_nan() and isinstance(X, np.ndarray):
             rows = self._incomplete_rows(X)
             if rows.size:   # split and scatter as _winning_neurons_with_holes
@@ -976,7 +1043,8 @@ class BaseSom(BaseEstimator):
         error, ``idx[:, 0]`` equals ``predict(X)``, and ``dist[i, t] == prototype_distances(X)[i, idx[i, t]]`` bit
         for bit.  A pair whose ``r`` is not below +inf is never reported; slots left unfilled hold ``(inf, -1)``.
         With ``missing_values`` set, rows with NaN are ordered by ``d / n_obs * sum over the observed
-        (x_k - w_k)^2`` with the same tie rule.
+        (x_k - w_k)^2`` with the same tie rule.  Under ``metric="manhattan"`` the order is on
+        ``(sum_k |x_k - w_k|, j)`` and ``dist`` is that sum: no square root is taken (dense X and tensors only).
 
         ``1 <= n_neighbors <= min(len(weights_), 32)``; the selection runs on the GPU for every such value, and
         above 32 ``prototype_distances(X)`` and a sort of one's own is the route.  X is what ``predict`` takes: a
@@ -1009,6 +1077,10 @@ class BaseSom(BaseEstimator):
             return (dist, idx) if return_distance else idx
         engine = self._engine()
         dist = idx = None
+        if self._is_manhattan():   # the k smallest (sum_k |x_k - w_k|, j): no square root behind the selection
+            self._check_manhattan_query(X)
+            dist, idx = engine.kneighbors_manhattan(W, k, X)
+            return (dist, idx) if return_distance else idx
         if self._accepts_nan() and isinstance(X, np.ndarray):
             rows = self._incomplete_rows(X)
             if rows.size:   # split and scatter as _winning_neurons_with_holes
@@ -1172,6 +1244,8 @@ class BaseSom(BaseEstimator):
         dense M x M matrix is kept on the estimator (``want_distances=True`` on the backend gives D).
         Dense X only: sparse X raises ``TypeError``."""
         check_is_fitted(self)
+        if self._is_manhattan():
+            self._refuse_manhattan("topographic_function", "its induced Delaunay graph is built on the Euclidean search")
         X = self._check_device_array(X, fit=False) if is_device_array(X) else check_array(X, dtype=[np.float64, np.float32])
         if X.shape[1] != self.n_features_in_:
             raise ValueError(f"X has {X.shape[1]} features, but {type(self).__name__} is expecting "

@@ -182,6 +182,8 @@ int launch_distances_masked_rows_squared(const void *X, int x_dtype, int64_t N, 
 // over slabs of rows (squared distances into the workspace, selection on the slab; slab_rows 0 = the default)
 int launch_topk_rows(const double *R, int64_t N, int64_t M, int64_t ldr, int k, int64_t *idx, double *dist,
                      hipStream_t s);
+int launch_topk_rows_plain(const double *R, int64_t N, int64_t M, int64_t ldr, int k, int64_t *idx, double *dist,
+                           hipStream_t s);   // (no square root behind the selection: R holds distances)
 int64_t kneighbors_slab_rows(int64_t N, int64_t M, int64_t slab_rows);
 size_t kneighbors_workspace_bytes(int64_t N, int64_t M, int64_t slab_rows);
 size_t kneighbors_masked_workspace_bytes(int x_dtype, int64_t N, int64_t d, int64_t M, int64_t slab_rows);
@@ -191,6 +193,19 @@ int launch_kneighbors(const void *X, int x_dtype, int64_t N, int64_t d, int64_t 
 int launch_kneighbors_masked_rows(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, int k,
                                   int64_t slab_rows, int64_t *idx, double *dist, void *ws, size_t ws_bytes,
                                   hipStream_t s);
+// metric="manhattan" (manhattan.hip): sum_k |x_k - w_k| in float64, F32 / F64 rows; search, matrix and selection read
+// the transposed float64 prototypes launch_manhattan_weights leaves in front of the workspace
+size_t bmu_manhattan_workspace_bytes(int x_dtype, int64_t N, int64_t d, int64_t M);
+int launch_manhattan_weights(const double *W, int64_t M, int64_t d, int64_t ldw, void *ws, hipStream_t s);
+int launch_bmu_manhattan_rows(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, int k,
+                              int64_t *idx, double *dist, void *ws, size_t ws_bytes, hipStream_t s);
+int launch_distances_manhattan_rows(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, double *out,
+                                    int64_t ldo, void *ws, size_t ws_bytes, hipStream_t s);
+size_t kneighbors_manhattan_workspace_bytes(int x_dtype, int64_t N, int64_t d, int64_t M, int64_t slab_rows);
+int kneighbors_manhattan_check(int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, int k, int64_t slab_rows);
+int launch_kneighbors_manhattan_rows(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, int k,
+                                     int64_t slab_rows, int64_t *idx, double *dist, void *ws, size_t ws_bytes,
+                                     hipStream_t s);
 // fit on rows with missing entries: sums [S (M x d) | K (M x d) | A (M x d) | a | E] over the observed entries
 // (masked_fit.hip), and the smoothing with a denominator per (neuron, feature) (smooth.hip)
 size_t accumulate_masked_workspace_bytes(int64_t N, int64_t d, int64_t M);

@@ -110,8 +110,9 @@ __device__ __forceinline__ void wave_lex_min(double &v, int &j) {
     j = h.j;
 }
 
-// R: N rows of M squared values, ldr >= M apart.  idx / dist: N x k, contiguous.
-template <int K>
+// R: N rows of M squared values, ldr >= M apart.  idx / dist: N x k, contiguous.  ROOT: the distance stored is the
+// square root of the value selected on; without it the value itself (manhattan.hip: its slab holds distances).
+template <int K, bool ROOT = true>
 __global__ __launch_bounds__(TOPK_NT) void topk_rows_kernel(const double *__restrict__ R, int64_t N, int M, int64_t ldr,
                                                             int k, int64_t *__restrict__ idx, double *__restrict__ dist) {
     const int lane = threadIdx.x & 63;
@@ -143,7 +144,7 @@ __global__ __launch_bounds__(TOPK_NT) void topk_rows_kernel(const double *__rest
     }
     if (lane < k) {
         idx[row * k + lane] = (mine_j == TOPK_EMPTY) ? (int64_t)-1 : (int64_t)mine_j;
-        dist[row * k + lane] = sqrt(mine);
+        dist[row * k + lane] = ROOT ? sqrt(mine) : mine;
     }
 }
 
@@ -157,8 +158,9 @@ static int topk_check(int64_t N, int64_t M, int64_t ldr, int k) {
     return DBGSOM_OK;
 }
 
-int launch_topk_rows(const double *R, int64_t N, int64_t M, int64_t ldr, int k, int64_t *idx, double *dist,
-                     hipStream_t s) {
+template <bool ROOT>
+static int launch_topk_form(const double *R, int64_t N, int64_t M, int64_t ldr, int k, int64_t *idx, double *dist,
+                            hipStream_t s) {
     TRY_STATUS(topk_check(N, M, ldr, k));
     if (N == 0) return DBGSOM_OK;
     DBGSOM_REQUIRE(R && idx && dist, "null pointer");
@@ -167,7 +169,7 @@ int launch_topk_rows(const double *R, int64_t N, int64_t M, int64_t ldr, int k, 
     DBGSOM_REQUIRE(nb <= 0x7fffffff, "too many samples for one launch");
     dim3 grid((unsigned)nb), block(TOPK_NT);
 #define DBGSOM_TOPK(K) \
-    hipLaunchKernelGGL((topk_rows_kernel<K>), grid, block, 0, s, R, N, (int)M, ldr, k, idx, dist)
+    hipLaunchKernelGGL((topk_rows_kernel<K, ROOT>), grid, block, 0, s, R, N, (int)M, ldr, k, idx, dist)
     if (k <= 1) DBGSOM_TOPK(1);
     else if (k <= 2) DBGSOM_TOPK(2);
     else if (k <= 4) DBGSOM_TOPK(4);
@@ -176,6 +178,17 @@ int launch_topk_rows(const double *R, int64_t N, int64_t M, int64_t ldr, int k, 
     else DBGSOM_TOPK(32);
 #undef DBGSOM_TOPK
     return launch_status("topk_rows_kernel");
+}
+
+int launch_topk_rows(const double *R, int64_t N, int64_t M, int64_t ldr, int k, int64_t *idx, double *dist,
+                     hipStream_t s) {
+    return launch_topk_form<true>(R, N, M, ldr, k, idx, dist, s);
+}
+
+// the same selection on a matrix of distances: what is stored is the value selected on, no square root
+int launch_topk_rows_plain(const double *R, int64_t N, int64_t M, int64_t ldr, int k, int64_t *idx, double *dist,
+                           hipStream_t s) {
+    return launch_topk_form<false>(R, N, M, ldr, k, idx, dist, s);
 }
 
 // rows between two slabs' pitch: M rounded up to even, so that every row of the slab starts on 16 bytes

@@ -683,6 +683,60 @@ int dbgsom_ctx_epoch_masked(dbgsom_ctx *ctx, const double *W_host, int64_t M, do
                             double *W_new_host, double *change_total_host, double *errors_host,
                             double *activations_host, int64_t *idx_host, double *dist_host);
 
+/* ---- metric="manhattan" (csrc/manhattan.hip) ---------------------------------------------------------
+ * dist(x, w) = sum_k |x_k - w_k| in float64, one accumulator per (row, prototype) pair, k ascending:
+ * t = x_k - w_k; acc = acc + |t|.  float32 rows are widened exactly first; there is no square root and no
+ * clamp.  Winners are the lexicographic minimum on (dist, index); a pair whose distance is not below +inf (a
+ * NaN or an infinity in the row) is never reported: index -1, distance +inf.  A pair's bits depend on that row
+ * and that prototype only -- not on the batch, the grid, the chunk or the slab.
+ * Device level: the arguments of the _masked namesakes above (X DBGSOM_F32 / DBGSOM_F64 with ldx >= d, W
+ * float64 with ldw >= d; k in {1, 2} for the search, 1 <= k <= DBGSOM_MAX_NEIGHBORS for the selection, which
+ * stores the distance it selected on).  Workspace: dbgsom_bmu_manhattan_workspace_bytes (search and matrix),
+ * dbgsom_kneighbors_manhattan_workspace_bytes (16-byte aligned); a short one is DBGSOM_ENOMEM. */
+size_t dbgsom_bmu_manhattan_workspace_bytes(int x_dtype, int64_t N, int64_t d, int64_t M);
+int dbgsom_bmu_manhattan(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *W_dev,
+                         int64_t M, int64_t ldw, int k, int64_t *idx_dev, double *dist_dev, void *workspace_dev,
+                         size_t workspace_bytes, void *stream);
+int dbgsom_distances_manhattan(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx,
+                               const double *W_dev, int64_t M, int64_t ldw, double *out_dev, int64_t ldo,
+                               void *workspace_dev, size_t workspace_bytes, void *stream);
+size_t dbgsom_kneighbors_manhattan_workspace_bytes(int x_dtype, int64_t N, int64_t d, int64_t M, int64_t slab_rows);
+int dbgsom_kneighbors_manhattan(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx,
+                                const double *W_dev, int64_t M, int64_t ldw, int k, int64_t slab_rows,
+                                int64_t *idx_dev, double *dist_dev, void *workspace_dev, size_t workspace_bytes,
+                                void *stream);
+/* Context level, resident rows.  dbgsom_ctx_bmu_manhattan: the search of the resident rows, k in {1, 2}, idx /
+ * dist N x k to the host.  dbgsom_ctx_epoch_manhattan: that search with k = 1 in front of the sums and the
+ * smoothing of dbgsom_ctx_epoch (same kernels, `layout` honoured, same outputs); the prototypes (M x d) are
+ * handed over with every call; idx_host / dist_host (N each) may be NULL; needs dbgsom_ctx_set_topology for M
+ * neurons (DBGSOM_ESTATE otherwise).  Both return DBGSOM_EINVAL, with the reason in the message, on CSR
+ * residents, bfloat16 storage, rows marked incomplete, attached sample weights and more than one rank. */
+int dbgsom_ctx_bmu_manhattan(dbgsom_ctx *ctx, const double *W_host, int64_t M, int k, int64_t *idx_host,
+                             double *dist_host);
+int dbgsom_ctx_epoch_manhattan(dbgsom_ctx *ctx, const double *W_host, int64_t M, double gamma, double sigma,
+                               int layout, double *W_new_host, double *change_total_host, double *errors_host,
+                               double *activations_host, int64_t *idx_host, double *dist_host);
+/* Context level, queries: host rows (Nq x d, contiguous) go up in chunks -- "masked_chunk_rows" rows for the
+ * search, "distances_chunk_rows" for the matrix and the selection -- and only the results come down; the traffic
+ * counters count both.  _device: rows in HBM, ldx >= d elements apart, read where they are; the results are
+ * device arrays the kernels write (out_dev rows ldo >= M apart); nothing of X or of the result crosses PCIe. */
+int dbgsom_ctx_bmu_query_manhattan(dbgsom_ctx *ctx, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                   const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host);
+int dbgsom_ctx_bmu_query_manhattan_device(dbgsom_ctx *ctx, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d,
+                                          int64_t ldx, const double *W_host, int64_t M, int k, int64_t *idx_dev,
+                                          double *dist_dev);
+int dbgsom_ctx_distances_query_manhattan(dbgsom_ctx *ctx, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                         const double *W_host, int64_t M, double *out_host);
+int dbgsom_ctx_distances_query_manhattan_device(dbgsom_ctx *ctx, const void *Xq_dev, int x_dtype, int64_t Nq,
+                                                int64_t d, int64_t ldx, const double *W_host, int64_t M,
+                                                double *out_dev, int64_t ldo);
+int dbgsom_ctx_kneighbors_query_manhattan(dbgsom_ctx *ctx, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                          const double *W_host, int64_t M, int k, int64_t *idx_host,
+                                          double *dist_host);
+int dbgsom_ctx_kneighbors_query_manhattan_device(dbgsom_ctx *ctx, const void *Xq_dev, int x_dtype, int64_t Nq,
+                                                 int64_t d, int64_t ldx, const double *W_host, int64_t M, int k,
+                                                 int64_t *idx_dev, double *dist_dev);
+
 /* ---- sparse coding: BaseSom.transform / SomClassifier.predict_proba (BaseSom.py:241-268,
  * SomClassifier.py:178-220) ------------------------------------------------------------------------
  * scikit-learn's SparseCoder(dictionary=normalize(W), transform_algorithm="lasso_lars",
