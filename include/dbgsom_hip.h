@@ -151,9 +151,12 @@ int dbgsom_accumulate_weighted(const void *X_dev, int x_dtype, int64_t N, int64_
  * dbgsom_bmu_csr: dbgsom_bmu for CSR samples; ww_dev from dbgsom_row_sqnorms on W.
  * dbgsom_csr_densify: the padded dense rows (N x ld, X's own dtype).
  * dbgsom_accumulate_csr: dbgsom_accumulate (sw_dev = NULL) / dbgsom_accumulate_weighted for CSR samples; sums_dev
- *   holds M*(d+3) float64 with the d given here (the context passes its padded feature count).  Bit-identical to
- *   the dense call wherever that one adds a column in list order: rows of at least 256 16-byte pieces (padded
- *   d >= 1024 for float32, >= 512 for float64); narrower dense rows are summed over row lanes. */
+ *   holds M*(d+3) float64 with the d given here, any d >= 1 (the context passes its padded feature count); the
+ *   status word, the skipped rows and the first N int32 of the workspace are the dense calls'; the workspace size
+ *   is that of the weighted call for both forms.  Bit-identical to the dense call wherever that one adds a column
+ *   in list order, which is from 256 pieces per row on: 16-byte pieces when X_dev and ldx are 16-byte aligned and
+ *   d is a multiple of the piece (d >= 1024 for float32, >= 512 for float64, as with the context's padded rows),
+ *   single elements otherwise (any d >= 256); narrower dense rows are summed over row lanes, in another order. */
 int dbgsom_csr_check(const int64_t *indptr_host, const int32_t *indices_host, int64_t N, int64_t d, int64_t nnz);
 int dbgsom_csr_row_sqnorms(const int64_t *indptr_dev, const void *data_dev, int x_dtype, int64_t N, double *out_dev,
                            void *stream);
