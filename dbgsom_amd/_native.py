@@ -167,6 +167,19 @@ SIGNATURES = {
     "dbgsom_ctx_distances_query_manhattan_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _vp, _i64]),
     "dbgsom_ctx_kneighbors_query_manhattan": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _ci, _vp, _vp]),
     "dbgsom_ctx_kneighbors_query_manhattan_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _ci, _vp, _vp]),
+    "dbgsom_inv_norms": (_ci, [_vp, _i64, _vp, _vp]),
+    "dbgsom_bmu_cosine": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _ci, _vp, _vp, _vp]),
+    "dbgsom_distances_cosine": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "dbgsom_kneighbors_cosine_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "dbgsom_kneighbors_cosine": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _ci, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "dbgsom_ctx_bmu_cosine": (_ci, [_vp, _vp, _i64, _ci, _vp, _vp]),
+    "dbgsom_ctx_epoch_cosine": (_ci, [_vp, _vp, _i64, _dbl, _dbl, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dbgsom_ctx_bmu_query_cosine": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _ci, _vp, _vp]),
+    "dbgsom_ctx_bmu_query_cosine_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _ci, _vp, _vp]),
+    "dbgsom_ctx_distances_query_cosine": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _vp]),
+    "dbgsom_ctx_distances_query_cosine_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _vp, _i64]),
+    "dbgsom_ctx_kneighbors_query_cosine": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _ci, _vp, _vp]),
+    "dbgsom_ctx_kneighbors_query_cosine_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _ci, _vp, _vp]),
     "dbgsom_topofn_workspace_bytes": (_sz, [_i64, _ci]),
     "dbgsom_topofn": (_ci, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dbgsom_topofn_timing": (_ci, [_ci]),

@@ -126,9 +126,10 @@ class HotPathBackend:
     def set_metric(self, metric):
         """The metric of the search of the RESIDENT rows from here to the next ``load`` / ``release``: "euclidean",
         or "manhattan" -- ``bmu(W, k)`` is then the L1 search, ``epoch_manhattan`` the epoch, and the reductions over
-        the resident rows are the host defaults of this class over that ``bmu``."""
-        if metric not in ("euclidean", "manhattan"):
-            raise ValueError(f"metric must be 'euclidean' or 'manhattan', got {metric!r}")
+        the resident rows are the host defaults of this class over that ``bmu`` -- or "cosine", likewise with the
+        cosine search and ``epoch_cosine``."""
+        if metric not in ("euclidean", "manhattan", "cosine"):
+            raise ValueError(f"metric must be 'euclidean', 'manhattan' or 'cosine', got {metric!r}")
         self._metric = metric
 
     def bmu_manhattan(self, W, k, X):
@@ -147,6 +148,28 @@ class HotPathBackend:
     def epoch_manhattan(self, W, hop, sigma, gamma, layout="compact", want_assignments=False, n_classes=0):
         """``epoch`` with the L1 search in front of the unchanged sums and smoothing -> EpochResult.  The prototypes
         are handed over with every call."""
+        raise NotImplementedError
+
+    # -- metric="cosine": c(x, w) = 1 - (<x, w> * inv(|x|^2)) * inv(|w|^2) in float64, every operation rounded on its
+    # own, clamped to [0, 2]; <x, w>, |x|^2, |w|^2 the sequential fma chains of ``bmu``; inv(t) = 0 for t == 0,
+    # 1 / sqrt(t) for 0 < t < inf, NaN otherwise; no square root of c; winners by (c, index); a pair whose c is not below
+    # +inf is never reported (index -1, distance inf).  X: a dense host array or a device array.
+    def bmu_cosine(self, W, k, X):
+        """``bmu(W, k, X=X)`` under the cosine metric -> (distances, winners) in ``bmu``'s shapes."""
+        raise NotImplementedError
+
+    def distances_cosine(self, W, X):
+        """``distances(W, X)`` under the cosine metric: ``bmu_cosine``'s distances are its smallest entries."""
+        raise NotImplementedError
+
+    def kneighbors_cosine(self, W, k, X):
+        """``kneighbors(W, k, X)`` under the cosine metric: the k smallest ``(c, j)`` per row, ascending;
+        ``distances_cosine(W, X)`` gathered at the indices, bit for bit."""
+        raise NotImplementedError
+
+    def epoch_cosine(self, W, hop, sigma, gamma, layout="compact", want_assignments=False, n_classes=0):
+        """``epoch`` with the cosine search in front of the unchanged sums and smoothing -> EpochResult.  The
+        prototypes are handed over with every call."""
         raise NotImplementedError
 
     def exp_similarity(self, distances, gamma):
@@ -813,12 +836,16 @@ class HipBackend(HotPathBackend):
                 raise ValueError("no prototypes stay resident between masked epochs")
             if self._manhattan and W is RESIDENT:
                 raise ValueError("no prototypes stay resident between Manhattan epochs")
-            keep, p, M, rf = self._w_arg(W, d=self._d if self._incomplete or self._manhattan else None)
+            if self._cosine and W is RESIDENT:
+                raise ValueError("no prototypes stay resident between cosine epochs")
+            keep, p, M, rf = self._w_arg(W, d=self._d if self._incomplete or self._other_metric else None)
             N = self._N
             idx = np.empty((N, k), dtype=np.int64)
             dist = np.empty((N, k), dtype=np.float64)
             if self._manhattan:    # metric="manhattan": the L1 search of the resident rows
                 self._call("dbgsom_ctx_bmu_manhattan", self._ctx, p, M, int(k), idx.ctypes.data, dist.ctypes.data)
+            elif self._cosine:     # metric="cosine": the cosine search of the resident rows
+                self._call("dbgsom_ctx_bmu_cosine", self._ctx, p, M, int(k), idx.ctypes.data, dist.ctypes.data)
             elif self._incomplete:   # rows with missing entries: the search over the observed entries of every row
                 self._call("dbgsom_ctx_bmu_masked", self._ctx, p, M, int(k), idx.ctypes.data, dist.ctypes.data)
             else:
@@ -879,7 +906,7 @@ class HipBackend(HotPathBackend):
     def resident_winners(self, W):
         """``bmu(W, 1)[1]`` of the resident samples without the distances' trip to the host."""
         self._require_loaded()
-        if self._incomplete or self._manhattan:
+        if self._incomplete or self._other_metric:
             return self.bmu(W, 1)[1]
         keep, p, M, rf = self._w_arg(W)
         idx = np.empty(self._N, dtype=np.int64)
@@ -1044,12 +1071,15 @@ class HipBackend(HotPathBackend):
 
     # -- metric="manhattan" (csrc/manhattan.hip) --------------------------------------------------------
     _manhattan = property(lambda self: self._metric == "manhattan")
+    _cosine = property(lambda self: self._metric == "cosine")
+    _other_metric = property(lambda self: self._metric != "euclidean")   # the resident search is not the Euclidean one
+    _METRIC_NAME = {"manhattan": "Manhattan", "cosine": "cosine"}
 
-    def _manhattan_args(self, W, X):
+    def _manhattan_args(self, W, X, name="Manhattan"):
         """-> (W64, X as the calls take it, on_device, (code, N, d, ldx))"""
         W64 = np.ascontiguousarray(W, dtype=np.float64)
         if is_sparse(X):
-            raise TypeError("the Manhattan calls take dense rows")
+            raise TypeError(f"the {name} calls take dense rows")
         if is_device_array(X):
             rows = self._device_rows(X)
             on_device = True
@@ -1065,77 +1095,78 @@ class HipBackend(HotPathBackend):
             raise ValueError("prototype / sample feature mismatch")
         return W64, X, on_device, rows
 
-    def bmu_manhattan(self, W, k, X):
-        """The L1 search on the device, host rows in chunks of ``masked_chunk_rows`` rows; for rows in HBM distances
-        and winners are arrays on X's device that the search writes itself."""
-        W64, X, on_device, (code, N, d, ldx) = self._manhattan_args(W, X)
+    def _metric_bmu(self, metric, W, k, X):
+        """The search of ``metric`` ("manhattan", "cosine") on the device, host rows in chunks of ``masked_chunk_rows``
+        rows; for rows in HBM distances and winners are arrays on X's device that the search writes itself."""
+        W64, X, on_device, (code, N, d, ldx) = self._manhattan_args(W, X, self._METRIC_NAME[metric])
         k = int(k)
         if on_device:
             idx, dist = device_empty(X, (N, k), "int64"), device_empty(X, (N, k), "float64")
             if N:
                 self._producer_done(X)
-                self._call("dbgsom_ctx_bmu_query_manhattan_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code, N, d,
+                self._call(f"dbgsom_ctx_bmu_query_{metric}_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code, N, d,
                            ldx, W64.ctypes.data, W64.shape[0], k, ctypes.c_void_p(idx.data_ptr()),
                            ctypes.c_void_p(dist.data_ptr()))
         else:
             idx, dist = np.empty((N, k), dtype=np.int64), np.empty((N, k), dtype=np.float64)
-            self._call("dbgsom_ctx_bmu_query_manhattan", self._ctx, X.ctypes.data if N else None, code, N, d,
+            self._call(f"dbgsom_ctx_bmu_query_{metric}", self._ctx, X.ctypes.data if N else None, code, N, d,
                        W64.ctypes.data, W64.shape[0], k, idx.ctypes.data, dist.ctypes.data)
         if k == 1:
             return dist.reshape(-1), idx.reshape(-1)
         return dist, idx
 
-    def distances_manhattan(self, W, X):
-        """Every distance of the L1 search, stored: host rows in chunks of ``distances_chunk_rows`` rows; for rows in
+    def _metric_distances(self, metric, W, X):
+        """Every distance of that search, stored: host rows in chunks of ``distances_chunk_rows`` rows; for rows in
         HBM the result is a float64 array on their device that the kernel writes itself."""
-        W64, X, on_device, (code, N, d, ldx) = self._manhattan_args(W, X)
+        W64, X, on_device, (code, N, d, ldx) = self._manhattan_args(W, X, self._METRIC_NAME[metric])
         M = W64.shape[0]
         if on_device:
             out = device_empty(X, (N, M), "float64")
             if N:
                 self._producer_done(X)
-                self._call("dbgsom_ctx_distances_query_manhattan_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code,
+                self._call(f"dbgsom_ctx_distances_query_{metric}_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code,
                            N, d, ldx, W64.ctypes.data, M, ctypes.c_void_p(out.data_ptr()), M)
             return out
         out = np.empty((N, M), dtype=np.float64)
         if N:
-            self._call("dbgsom_ctx_distances_query_manhattan", self._ctx, X.ctypes.data, code, N, d, W64.ctypes.data, M,
+            self._call(f"dbgsom_ctx_distances_query_{metric}", self._ctx, X.ctypes.data, code, N, d, W64.ctypes.data, M,
                        out.ctypes.data)
         return out
 
-    def kneighbors_manhattan(self, W, k, X):
-        """The k nearest prototypes under the L1 distance: a slab of ``kneighbors_slab_rows`` rows of distances stays
+    def _metric_kneighbors(self, metric, W, k, X):
+        """The k nearest prototypes under that distance: a slab of ``kneighbors_slab_rows`` rows of distances stays
         on the device, the selection kernel of csrc/kneighbors.hip reads it back and stores what it selected on."""
-        W64, X, on_device, (code, N, d, ldx) = self._manhattan_args(W, X)
+        W64, X, on_device, (code, N, d, ldx) = self._manhattan_args(W, X, self._METRIC_NAME[metric])
         M, k = W64.shape[0], int(k)
         self._check_neighbors(k, M)
         if on_device:
             dist, idx = device_empty(X, (N, k), "float64"), device_empty(X, (N, k), "int64")
             if N:
                 self._producer_done(X)
-                self._call("dbgsom_ctx_kneighbors_query_manhattan_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code,
+                self._call(f"dbgsom_ctx_kneighbors_query_{metric}_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code,
                            N, d, ldx, W64.ctypes.data, M, k, ctypes.c_void_p(idx.data_ptr()),
                            ctypes.c_void_p(dist.data_ptr()))
             return dist, idx
         dist, idx = np.empty((N, k), dtype=np.float64), np.empty((N, k), dtype=np.int64)
         if N:
-            self._call("dbgsom_ctx_kneighbors_query_manhattan", self._ctx, X.ctypes.data, code, N, d, W64.ctypes.data, M, k,
+            self._call(f"dbgsom_ctx_kneighbors_query_{metric}", self._ctx, X.ctypes.data, code, N, d, W64.ctypes.data, M, k,
                        idx.ctypes.data, dist.ctypes.data)
         return dist, idx
 
-    def epoch_manhattan(self, W, hop, sigma, gamma, layout="compact", want_assignments=False, n_classes=0):
-        """One epoch under the Manhattan metric as ONE call of the C ABI: the L1 search of the resident rows
-        (csrc/manhattan.hip) in front of the sums and the smoothing of ``epoch`` (dbgsom_ctx_epoch_manhattan)."""
+    def _metric_epoch(self, metric, W, hop, sigma, gamma, layout, want_assignments, n_classes):
+        """One epoch under ``metric`` as ONE call of the C ABI: its search of the resident rows (csrc/manhattan.hip;
+        the cosine forms of the MFMA kernels) in front of the sums and the smoothing of ``epoch``
+        (dbgsom_ctx_epoch_manhattan, dbgsom_ctx_epoch_cosine)."""
         self._require_loaded()
         if W is RESIDENT:
-            raise ValueError("no prototypes stay resident between Manhattan epochs")
+            raise ValueError(f"no prototypes stay resident between {self._METRIC_NAME[metric]} epochs")
         keep, p, M, _ = self._w_arg(W, d=self._d)
         self._topology(hop, M)
         Wn, chg, E, a = np.empty((M, self._d)), np.empty(1), np.empty(M), np.empty(M)
         want = want_assignments or n_classes > 0
         win = np.empty(self._N, dtype=np.int64) if want else None
         dist = np.empty(self._N) if want else None
-        self._call("dbgsom_ctx_epoch_manhattan", self._ctx, p, M, float(gamma), float(sigma), _native.LAYOUTS[layout],
+        self._call(f"dbgsom_ctx_epoch_{metric}", self._ctx, p, M, float(gamma), float(sigma), _native.LAYOUTS[layout],
                    Wn.ctypes.data, chg.ctypes.data, E.ctypes.data, a.ctypes.data,
                    None if win is None else win.ctypes.data, None if dist is None else dist.ctypes.data)
         self._last_M = M
@@ -1143,6 +1174,31 @@ class HipBackend(HotPathBackend):
         if n_classes > 0:
             res.class_hist = self.class_histogram(win, n_classes, M)
         return res
+
+    def bmu_manhattan(self, W, k, X):
+        return self._metric_bmu("manhattan", W, k, X)
+
+    def distances_manhattan(self, W, X):
+        return self._metric_distances("manhattan", W, X)
+
+    def kneighbors_manhattan(self, W, k, X):
+        return self._metric_kneighbors("manhattan", W, k, X)
+
+    def epoch_manhattan(self, W, hop, sigma, gamma, layout="compact", want_assignments=False, n_classes=0):
+        return self._metric_epoch("manhattan", W, hop, sigma, gamma, layout, want_assignments, n_classes)
+
+    # -- metric="cosine" (csrc/cosine.hip and the cosine forms of bmu.hip, bmu_dma.hip, distances.hip) ----
+    def bmu_cosine(self, W, k, X):
+        return self._metric_bmu("cosine", W, k, X)
+
+    def distances_cosine(self, W, X):
+        return self._metric_distances("cosine", W, X)
+
+    def kneighbors_cosine(self, W, k, X):
+        return self._metric_kneighbors("cosine", W, k, X)
+
+    def epoch_cosine(self, W, hop, sigma, gamma, layout="compact", want_assignments=False, n_classes=0):
+        return self._metric_epoch("cosine", W, hop, sigma, gamma, layout, want_assignments, n_classes)
 
     def query_filter_applies(self, N, d, M, k=1):
         """Whether a k-BMU query on N other samples would go through the filtered search."""
@@ -1477,11 +1533,11 @@ class HipBackend(HotPathBackend):
         self._call("dbgsom_ctx_weighted_column_sums", self._ctx, mean.ctypes.data, s2.ctypes.data)
         return s1, s2
 
-    # (rows with missing entries, metric="manhattan": the O(N)-per-fit reductions are HotPathBackend's host defaults
-    #  over the masked / the L1 bmu)
+    # (rows with missing entries, metric="manhattan" / "cosine": the O(N)-per-fit reductions are HotPathBackend's host
+    #  defaults over the masked bmu / the bmu of that metric)
     def quantization_error(self, W) -> float:
         self._require_loaded()
-        if self._incomplete or self._manhattan:
+        if self._incomplete or self._other_metric:
             return super().quantization_error(W)
         keep, p, M, rf = self._w_arg(W)
         out = np.empty(2)
@@ -1490,7 +1546,7 @@ class HipBackend(HotPathBackend):
 
     def topographic_error_count(self, W, coords) -> int:
         self._require_loaded()
-        if self._incomplete or self._manhattan:
+        if self._incomplete or self._other_metric:
             return super().topographic_error_count(W, coords)
         keep, p, M, rf = self._w_arg(W)
         xy = np.ascontiguousarray(coords, dtype=np.int32)
@@ -1503,7 +1559,7 @@ class HipBackend(HotPathBackend):
     def node_statistics(self, W, sigma):
         """-> (hit_counts (M,), density_sums (M,)) of BaseSom._calculate_node_statistics."""
         self._require_loaded()
-        if self._incomplete or self._manhattan:
+        if self._incomplete or self._other_metric:
             return super().node_statistics(W, sigma)
         keep, p, M, rf = self._w_arg(W)
         hits, dens = np.empty(M), np.empty(M)
@@ -1521,7 +1577,7 @@ class HipBackend(HotPathBackend):
     def class_histogram(self, winners, n_classes, M):
         """(M, n_classes) int64 over all ranks (float64 summed weights with weights attached);
         winners=None: the last epoch's (still in HBM)."""
-        if self._incomplete or self._manhattan:
+        if self._incomplete or self._other_metric:
             return super().class_histogram(winners, n_classes, M)
         idx = None if winners is None else np.ascontiguousarray(winners, dtype=np.int64)
         if self._weighted:

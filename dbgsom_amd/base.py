@@ -114,8 +114,9 @@ class BaseSom(BaseEstimator):
         self.random_state = random_state
         self.convergence_treshold = convergence_treshold
         self.max_neurons = max_neurons
-        self.metric = metric  # read by the BMU search alone: "manhattan" / "cityblock" / "l1" is the L1 search, every
-        #                       other string the Euclidean one (BaseSom._is_manhattan); the update is the same
+        self.metric = metric  # read by the BMU search alone: "manhattan" / "cityblock" / "l1" is the L1 search, "cosine"
+        #                       the cosine search, every other string the Euclidean one (BaseSom._search_metric); the
+        #                       update is the same
         self.threshold_method = threshold_method
         self.growth_criterion = growth_criterion
         self.min_samples_vertical_growth = min_samples_vertical_growth
@@ -189,7 +190,7 @@ class BaseSom(BaseEstimator):
         host)."""
         self._accepts_nan()   # (validates the parameter)
         self._incomplete_fit = False
-        self._manhattan_fit = False
+        self._metric_fit = None
         if isinstance(X, DeviceSamples):   # a Voronoi subset that already lives in HBM (f-4)
             if y is not None:
                 y = np.asarray(y)
@@ -197,7 +198,7 @@ class BaseSom(BaseEstimator):
                 sample_weight = np.ascontiguousarray(sample_weight, dtype=np.float64)
         else:
             X, y = self._check_input_data(X, y)
-            self._manhattan_fit = self._check_manhattan_fit(X, sample_weight)
+            self._metric_fit = self._check_metric_fit(X, sample_weight)
             self._incomplete_fit = self._check_incomplete_fit(X, sample_weight)
             sample_weight = self._check_sample_weight(sample_weight, X)
         if y is not None:
@@ -214,8 +215,8 @@ class BaseSom(BaseEstimator):
             X = DeviceSamples(engine, source=X)
         self._load_resident(X)  # samples go to HBM once and stay there for the whole fit
         try:
-            if self._manhattan_fit:
-                engine.set_metric("manhattan")   # (the search of the resident rows, until the release below)
+            if self._metric_fit:
+                engine.set_metric(self._metric_fit)   # (the search of the resident rows, until the release below)
             self._attach_sample_weight(X, sample_weight)
             self._initialize_som(X)
             self._grow_som(X, y)
@@ -232,8 +233,8 @@ class BaseSom(BaseEstimator):
         finally:
             self._resident = None
             self._incomplete_fit = False
-            if self._manhattan_fit:
-                self._manhattan_fit = False
+            if self._metric_fit:
+                self._metric_fit = None
                 engine.set_metric("euclidean")   # (the backend object may serve another fit)
             self._sw = self._sw_global = None
             if hasattr(engine, "set_sample_weight") and getattr(engine, "_sw", None) is not None:
@@ -241,42 +242,53 @@ class BaseSom(BaseEstimator):
             engine.release()
         return self
 
-    # -- metric="manhattan" ----------------------------------------------------------------------------
+    # -- metric="manhattan", metric="cosine" -------------------------------------------------------------
     _MANHATTAN = ("manhattan", "cityblock", "l1")
-    _manhattan_fit = False    # this fit runs under the Manhattan metric
+    _COSINE = ("cosine",)
+    _METRIC_LABEL = {"manhattan": "Manhattan", "cosine": "cosine"}
+    _metric_fit = None    # the metric this fit runs under when it is not the Euclidean one: "manhattan" or "cosine"
 
-    def _is_manhattan(self) -> bool:
-        """Whether the best-matching-unit search is the L1 one: ``dist(x, w) = sum_k |x_k - w_k|`` in float64.
-        ``metric`` must be a string; "manhattan", "cityblock" and "l1" name the L1 search, every other string is the
-        Euclidean search as ever."""
+    def _search_metric(self):
+        """The metric of the best-matching-unit search when it is not the Euclidean one, else None.  "manhattan",
+        "cityblock" and "l1" name the L1 search, ``dist(x, w) = sum_k |x_k - w_k|`` in float64; "cosine" the cosine
+        search, ``1 - <x, w> / (|x| |w|)`` in float64 (a zero row is at distance 1 from everything).  ``metric`` must
+        be a string; every other string is the Euclidean search as ever."""
         if not isinstance(self.metric, str):
             raise ValueError(f"metric must be a string, got {self.metric!r}")
-        return self.metric in self._MANHATTAN
+        if self.metric in self._MANHATTAN:
+            return "manhattan"
+        if self.metric in self._COSINE:
+            return "cosine"
+        return None
 
-    def _refuse_manhattan(self, what: str, way_out: str = "") -> None:
-        raise ValueError(f"metric={self.metric!r} (Manhattan) does not support {what}" + (f": {way_out}" if way_out else ""))
+    def _refuse_metric(self, kind: str, what: str, way_out: str = "") -> None:
+        raise ValueError(f"metric={self.metric!r} ({self._METRIC_LABEL[kind]}) does not support {what}"
+                         + (f": {way_out}" if way_out else ""))
 
-    def _check_manhattan_query(self, X) -> None:
-        """The refusals of a query under the Manhattan metric, on the host before anything is uploaded.  (A device
-        array never holds NaN here: ``_check_device_array`` has refused it, under ``missing_values`` by name.)"""
+    def _check_metric_query(self, kind: str, X) -> None:
+        """The refusals of a query under the Manhattan or the cosine metric, on the host before anything is uploaded.
+        (A device array never holds NaN here: ``_check_device_array`` has refused it, under ``missing_values`` by
+        name.)"""
         if is_sparse(X):
-            self._refuse_manhattan("scipy sparse X", "pass X.toarray()")
+            self._refuse_metric(kind, "scipy sparse X", "pass X.toarray()")
         if self._accepts_nan() and isinstance(X, np.ndarray) and np.isnan(X).any():
-            self._refuse_manhattan(f"rows with missing entries (missing_values={self.missing_values!r} and NaN in X)",
-                                   "impute them first, or use metric='euclidean'")
+            self._refuse_metric(kind, f"rows with missing entries (missing_values={self.missing_values!r} and NaN in X)",
+                                "impute them first, or use metric='euclidean'")
 
-    def _check_manhattan_fit(self, X, sample_weight) -> bool:
-        """Whether this fit runs under the Manhattan metric; its refusals, on the host before anything is uploaded."""
-        if not self._is_manhattan():
-            return False
-        self._check_manhattan_query(X)
+    def _check_metric_fit(self, X, sample_weight):
+        """The metric this fit runs under when it is not the Euclidean one, else None; its refusals, on the host
+        before anything is uploaded."""
+        kind = self._search_metric()
+        if kind is None:
+            return None
+        self._check_metric_query(kind, X)
         if sample_weight is not None:
-            self._refuse_manhattan("sample_weight", "repeat the rows instead (np.repeat(X, w, axis=0))")
+            self._refuse_metric(kind, "sample_weight", "repeat the rows instead (np.repeat(X, w, axis=0))")
         if self.vertical_growth:
-            self._refuse_manhattan("vertical_growth=True")
+            self._refuse_metric(kind, "vertical_growth=True")
         if self.sharded_input or dist_info()[1] > 1:
-            self._refuse_manhattan("sharded_input or a process group of more than one rank", "it takes one process")
-        return True
+            self._refuse_metric(kind, "sharded_input or a process group of more than one rank", "it takes one process")
+        return kind
 
     # -- rows with missing entries in fit (missing_values="nan-fit") ---------------------------------
     _incomplete_fit = False   # this fit runs in incomplete mode: X is dense and holds at least one NaN
@@ -792,10 +804,11 @@ class BaseSom(BaseEstimator):
         # refreshed at growth steps and at the end.  Backends without resident prototypes (the
         # oracle's CPU stand-in in the tests) get the matrix handed over every epoch.
         # Rows with missing entries: nothing stays resident between masked epochs, whatever the backend can do.
-        # The same under metric="manhattan": the L1 search reads the prototypes it is handed.
+        # The same under metric="manhattan" and metric="cosine": their searches read the prototypes they are handed.
         incomplete = self._incomplete_fit
-        manhattan = self._manhattan_fit
-        resident = hasattr(engine, "write_weight_rows") and not incomplete and not manhattan
+        manhattan = self._metric_fit == "manhattan"
+        cosine = self._metric_fit == "cosine"
+        resident = hasattr(engine, "write_weight_rows") and not incomplete and not self._metric_fit
         on_device = False     # the current prototypes are in HBM, lat.W is stale
         ran = False
         self._growth_epochs = []
@@ -813,6 +826,10 @@ class BaseSom(BaseEstimator):
                 res = engine.epoch_manhattan(w_in, self._distance_matrix, self._calculate_current_sigma(),
                                              self._gamma(), self.centres_layout,
                                              n_classes=n_classes if need_assign else 0)
+            elif cosine:
+                res = engine.epoch_cosine(w_in, self._distance_matrix, self._calculate_current_sigma(),
+                                          self._gamma(), self.centres_layout,
+                                          n_classes=n_classes if need_assign else 0)
             else:
                 res = engine.epoch(w_in, self._distance_matrix, self._calculate_current_sigma(),
                                    self._gamma(), self.centres_layout,
@@ -828,6 +845,15 @@ class BaseSom(BaseEstimator):
                                  "every row of a neuron, because squared L1 distances grow with the square of the number of "
                                  "features and the variance only with the number; reduce the features (a projection) or "
                                  "use metric='euclidean'")
+            if cosine and not np.isfinite(res.new_weights).all():
+                # cosine distances lie in [0, 2] whatever the scale of the data while gamma = 1 / total variance follows
+                # it: on data of a tiny total variance the sample kernel is 0.0 for every row of a neuron and its
+                # centre is 0 / 0 (as in the reference's update)
+                raise ValueError(f"metric={self.metric!r} (cosine): the update gave prototypes that are not finite in "
+                                 f"epoch {epoch}: the sample kernel 1 - sqrt(1 - exp(-d^2 / total variance)) is 0 for "
+                                 "every row of a neuron, because cosine distances do not scale with the data while "
+                                 "the total variance does; rescale X (e.g. to unit total variance) or use "
+                                 "metric='euclidean'")
             if resident:
                 on_device = True
             else:
@@ -927,11 +953,12 @@ class BaseSom(BaseEstimator):
         """Distances and indices of the n_bmu best matching units (BaseSom.py:446-464)."""
         engine = self._engine()
         if self._is_resident(data):
-            dist, idx = engine.bmu(self.weights_, n_bmu)   # (a fit under metric="manhattan": the L1 search, set_metric)
+            dist, idx = engine.bmu(self.weights_, n_bmu)   # (a fit under metric="manhattan" / "cosine": that search, set_metric)
             return self._gather_rows(dist), self._gather_rows(idx)
-        if self._is_manhattan():
-            self._check_manhattan_query(data)
-            return engine.bmu_manhattan(self.weights_, n_bmu, data)
+        kind = self._search_metric()
+        if kind:
+            self._check_metric_query(kind, data)
+            return getattr(engine, f"bmu_{kind}")(self.weights_, n_bmu, data)
         if self._accepts_nan() and isinstance(data, np.ndarray):
             rows = self._incomplete_rows(data)
             if rows.size:
@@ -1000,7 +1027,8 @@ class BaseSom(BaseEstimator):
         device that the GPU writes itself; X and the result never touch the host), scipy sparse rows (the result
         of the dense call on ``X.toarray()``), and with ``missing_values`` set rows with NaN, whose entries are
         ``sqrt(d / n_obs * sum over the observed (x_k - w_k)^2)``.  Under ``metric="manhattan"`` the entries are
-        ``sum_k |x_k - w_k|`` in float64 (dense X and tensors only).  Only this map's prototypes are used (not the
+        ``sum_k |x_k - w_k|`` in float64, under ``metric="cosine"`` ``1 - <x, w> / (|x| |w|)`` clamped to [0, 2]
+        (dense X and tensors only).  Only this map's prototypes are used (not the
         child maps of vertical growth); the call is local to the process."""
         check_is_fitted(self)
         W = self.weights_
@@ -1014,9 +1042,10 @@ class BaseSom(BaseEstimator):
         if X.shape[0] == 0:
             return np.empty((0, len(W)), dtype=np.float64)
         engine = self._engine()
-        if self._is_manhattan():   # sum_k |x_k - w_k|, the arithmetic of the L1 search bit for bit
-            self._check_manhattan_query(X)
-            return engine.distances_manhattan(W, X)
+        kind = self._search_metric()
+        if kind:   # sum_k |x_k - w_k| / the cosine distance, the arithmetic of that search bit for bit
+            self._check_metric_query(kind, X)
+            return getattr(engine, f"distances_{kind}")(W, X)
         if self._accepts_nan() and isinstance(X, np.ndarray):
             rows = self._incomplete_rows(X)
             if rows.size:   # split and scatter as _winning_neurons_with_holes
@@ -1044,7 +1073,8 @@ class BaseSom(BaseEstimator):
         for bit.  A pair whose ``r`` is not below +inf is never reported; slots left unfilled hold ``(inf, -1)``.
         With ``missing_values`` set, rows with NaN are ordered by ``d / n_obs * sum over the observed
         (x_k - w_k)^2`` with the same tie rule.  Under ``metric="manhattan"`` the order is on
-        ``(sum_k |x_k - w_k|, j)`` and ``dist`` is that sum: no square root is taken (dense X and tensors only).
+        ``(sum_k |x_k - w_k|, j)`` and ``dist`` is that sum, under ``metric="cosine"`` likewise with the cosine distance:
+        no square root is taken (dense X and tensors only).
 
         ``1 <= n_neighbors <= min(len(weights_), 32)``; the selection runs on the GPU for every such value, and
         above 32 ``prototype_distances(X)`` and a sort of one's own is the route.  X is what ``predict`` takes: a
@@ -1077,9 +1107,10 @@ class BaseSom(BaseEstimator):
             return (dist, idx) if return_distance else idx
         engine = self._engine()
         dist = idx = None
-        if self._is_manhattan():   # the k smallest (sum_k |x_k - w_k|, j): no square root behind the selection
-            self._check_manhattan_query(X)
-            dist, idx = engine.kneighbors_manhattan(W, k, X)
+        kind = self._search_metric()
+        if kind:   # the k smallest (sum_k |x_k - w_k|, j) / (cosine distance, j): no square root behind the selection
+            self._check_metric_query(kind, X)
+            dist, idx = getattr(engine, f"kneighbors_{kind}")(W, k, X)
             return (dist, idx) if return_distance else idx
         if self._accepts_nan() and isinstance(X, np.ndarray):
             rows = self._incomplete_rows(X)
@@ -1244,8 +1275,9 @@ class BaseSom(BaseEstimator):
         dense M x M matrix is kept on the estimator (``want_distances=True`` on the backend gives D).
         Dense X only: sparse X raises ``TypeError``."""
         check_is_fitted(self)
-        if self._is_manhattan():
-            self._refuse_manhattan("topographic_function", "its induced Delaunay graph is built on the Euclidean search")
+        if self._search_metric():
+            self._refuse_metric(self._search_metric(), "topographic_function",
+                                "its induced Delaunay graph is built on the Euclidean search")
         X = self._check_device_array(X, fit=False) if is_device_array(X) else check_array(X, dtype=[np.float64, np.float32])
         if X.shape[1] != self.n_features_in_:
             raise ValueError(f"X has {X.shape[1]} features, but {type(self).__name__} is expecting "

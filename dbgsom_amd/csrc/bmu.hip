@@ -27,7 +27,9 @@
 
 namespace dbgsom {
 
-template <typename XT, int K>
+// ME = Metric::COSINE: xx holds u, ww holds v, the epilogue is pair_value_cosine and the winners' values go out as
+// they are (no square root, no float32 rounding)
+template <typename XT, int K, Metric ME = Metric::L2>
 __global__ __launch_bounds__(NT, 2) void bmu_kernel(
     const XT *__restrict__ X, int64_t N, int d, int64_t ldx, const double *__restrict__ xx,
     const double *__restrict__ W, int M, const double *__restrict__ ww, int round_f32, int xvec,
@@ -126,8 +128,13 @@ __global__ __launch_bounds__(NT, 2) void bmu_kernel(
                     if (j < M) {
 #pragma unroll
                         for (int it = 0; it < 4; ++it) {
-                            double rv = (xi[it] + (-2.0 * acc[jt][it][r])) + y;
-                            if (!(rv > 0.0)) rv = (rv != rv) ? rv : 0.0;  // max(r, 0), NaN kept
+                            double rv;
+                            if constexpr (ME == Metric::COSINE) {
+                                rv = pair_value_cosine(acc[jt][it][r], xi[it], y);
+                            } else {
+                                rv = (xi[it] + (-2.0 * acc[jt][it][r])) + y;
+                                if (!(rv > 0.0)) rv = (rv != rv) ? rv : 0.0;  // max(r, 0), NaN kept
+                            }
                             best[it].push(rv, j);
                         }
                     }
@@ -191,8 +198,11 @@ __global__ __launch_bounds__(NT, 2) void bmu_kernel(
             b.merge(ov, oj);
 #pragma unroll
             for (int t = 0; t < K; ++t) {
-                double dv = sqrt(b.v[t]);
-                if (round_f32) dv = (double)(float)dv;
+                double dv = b.v[t];
+                if constexpr (ME == Metric::L2) {
+                    dv = sqrt(dv);
+                    if (round_f32) dv = (double)(float)dv;
+                }
                 idx_out[i * K + t] = (b.j[t] == 0x7fffffff) ? (int64_t)-1 : (int64_t)b.j[t];
                 dist_out[i * K + t] = dv;
             }
@@ -281,10 +291,12 @@ int launch_row_sqnorms(const void *A, int dtype, int64_t rows, int64_t d, int64_
     return launch_status("row_sqnorms_kernel");
 }
 
-int launch_bmu(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx,
-               const double *W, int64_t M, const double *ww, int k, int round_f32, int64_t *idx,
-               double *dist, hipStream_t s) {
+template <Metric ME>
+static int launch_bmu_form(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx,
+                           const double *W, int64_t M, const double *ww, int k, int round_f32, int64_t *idx,
+                           double *dist, hipStream_t s) {
     DBGSOM_REQUIRE(valid_dtype(x_dtype), "x_dtype must be DBGSOM_F32/F64/BF16");
+    if (ME == Metric::COSINE) DBGSOM_REQUIRE(x_dtype != DBGSOM_BF16, "the cosine search takes DBGSOM_F32 or DBGSOM_F64 rows");
     DBGSOM_REQUIRE(k == 1 || k == 2, "k must be 1 or 2");
     DBGSOM_REQUIRE(N >= 0 && d >= 1 && ldx >= d && d <= 0x7fffffff, "bad sample shape");
     DBGSOM_REQUIRE(M >= k && M <= 0x7fffff00, "need k <= M < 2^31");
@@ -293,23 +305,38 @@ int launch_bmu(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, co
     const int64_t nb = (N + BI - 1) / BI;
     DBGSOM_REQUIRE(nb <= 0x7fffffff, "too many samples for one launch");
     if (bmu_dma_usable(X, x_dtype, d, ldx, W, M))
-        return launch_bmu_dma(X, x_dtype, N, d, ldx, xx, W, M, ww, k, round_f32, idx, dist, s);
+        return ME == Metric::COSINE ? launch_bmu_dma_cosine(X, x_dtype, N, d, ldx, xx, W, M, ww, k, idx, dist, s)
+                                    : launch_bmu_dma(X, x_dtype, N, d, ldx, xx, W, M, ww, k, round_f32, idx, dist, s);
     const size_t xe = dtype_size(x_dtype);
     const int xvec = is_aligned(X, 16) && ((ldx * xe) % 16 == 0);
     const int wvec = is_aligned(W, 16) && ((d * 8) % 16 == 0);
     dim3 grid((unsigned)nb), block(NT);
 #define DBGSOM_BMU_LAUNCH(XT, KK)                                                              \
-    hipLaunchKernelGGL((bmu_kernel<XT, KK>), grid, block, 0, s, (const XT *)X, N, (int)d, ldx, \
+    hipLaunchKernelGGL((bmu_kernel<XT, KK, ME>), grid, block, 0, s, (const XT *)X, N, (int)d, ldx, \
                        xx, W, (int)M, ww, round_f32, xvec, wvec, idx, dist)
     if (x_dtype == DBGSOM_F32) {
         if (k == 1) DBGSOM_BMU_LAUNCH(float, 1); else DBGSOM_BMU_LAUNCH(float, 2);
     } else if (x_dtype == DBGSOM_F64) {
         if (k == 1) DBGSOM_BMU_LAUNCH(double, 1); else DBGSOM_BMU_LAUNCH(double, 2);
-    } else {
+    } else if constexpr (ME == Metric::L2) {
         if (k == 1) DBGSOM_BMU_LAUNCH(bf16_t, 1); else DBGSOM_BMU_LAUNCH(bf16_t, 2);
     }
 #undef DBGSOM_BMU_LAUNCH
     return launch_status("bmu_kernel");
+}
+
+int launch_bmu(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx,
+               const double *W, int64_t M, const double *ww, int k, int round_f32, int64_t *idx,
+               double *dist, hipStream_t s) {
+    return launch_bmu_form<Metric::L2>(X, x_dtype, N, d, ldx, xx, W, M, ww, k, round_f32, idx, dist, s);
+}
+
+// metric="cosine": u = inv(|x|^2) for xx, v = inv(|w|^2) for ww (cosine.hip: launch_inv_norms); same kernel choice,
+// same grid, same chain per pair
+int launch_bmu_cosine(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *u,
+                      const double *W, int64_t M, const double *v, int k, int64_t *idx, double *dist,
+                      hipStream_t s) {
+    return launch_bmu_form<Metric::COSINE>(X, x_dtype, N, d, ldx, u, W, M, v, k, 0, idx, dist, s);
 }
 
 int launch_exp_similarity(const double *dist, int64_t N, double gamma, double *kw, hipStream_t s) {

@@ -24,7 +24,7 @@ namespace dbgsom {
 // JTW = 16-prototype tiles per wavefront: the workgroup sweeps the prototypes in chunks of
 // BJW = 32 JTW (128 for the general case; 64 / 32 for small maps, where a 128-wide chunk would
 // be mostly padding -- a growing map spends most of its epochs below 100 neurons).
-template <typename XT, int K, int JTW>
+template <typename XT, int K, int JTW, Metric ME = Metric::L2>
 __global__ __launch_bounds__(NT, 2) void bmu_dma_kernel(
     const XT *__restrict__ X, int64_t N, int d, int64_t ldx, const double *__restrict__ xx,
     const double *__restrict__ W, int M, const double *__restrict__ ww, int round_f32,
@@ -171,8 +171,13 @@ __global__ __launch_bounds__(NT, 2) void bmu_dma_kernel(
                         const double y = ww[j];
 #pragma unroll
                         for (int it = 0; it < 4; ++it) {
-                            double rv = (xi[it] + (-2.0 * acc[jt][it][r])) + y;
-                            if (!(rv > 0.0)) rv = (rv != rv) ? rv : 0.0;
+                            double rv;
+                            if constexpr (ME == Metric::COSINE) {
+                                rv = pair_value_cosine(acc[jt][it][r], xi[it], y);
+                            } else {
+                                rv = (xi[it] + (-2.0 * acc[jt][it][r])) + y;
+                                if (!(rv > 0.0)) rv = (rv != rv) ? rv : 0.0;
+                            }
                             best[it].push(rv, j);
                         }
                     }
@@ -235,8 +240,11 @@ __global__ __launch_bounds__(NT, 2) void bmu_dma_kernel(
             bb.merge(ov, oj);
 #pragma unroll
             for (int u = 0; u < K; ++u) {
-                double dv = sqrt(bb.v[u]);
-                if (round_f32) dv = (double)(float)dv;
+                double dv = bb.v[u];
+                if constexpr (ME == Metric::L2) {
+                    dv = sqrt(dv);
+                    if (round_f32) dv = (double)(float)dv;
+                }
                 idx_out[i * K + u] = (bb.j[u] == 0x7fffffff) ? (int64_t)-1 : (int64_t)bb.j[u];
                 dist_out[i * K + u] = dv;
             }
@@ -267,13 +275,14 @@ bool bmu_dma_usable(const void *X, int x_dtype, int64_t d, int64_t ldx, const vo
            dma_chunk_tiles(x_dtype, M) != 0;
 }
 
-int launch_bmu_dma(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx,
-                   const double *W, int64_t M, const double *ww, int k, int round_f32,
-                   int64_t *idx, double *dist, hipStream_t s) {
+template <Metric ME>
+static int launch_bmu_dma_form(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx,
+                               const double *W, int64_t M, const double *ww, int k, int round_f32,
+                               int64_t *idx, double *dist, hipStream_t s) {
     const int64_t nb = (N + BI - 1) / BI;
     dim3 grid((unsigned)nb), block(NT);
 #define DBGSOM_DMA_LAUNCH(XT, KK, JTW)                                                            \
-    hipLaunchKernelGGL((bmu_dma_kernel<XT, KK, JTW>), grid, block, 0, s, (const XT *)X, N, (int)d, \
+    hipLaunchKernelGGL((bmu_dma_kernel<XT, KK, JTW, ME>), grid, block, 0, s, (const XT *)X, N, (int)d, \
                        ldx, xx, W, (int)M, ww, round_f32, idx, dist)
     const int jtw = dma_chunk_tiles(x_dtype, M);
 #define DBGSOM_DMA_WIDTH(XT, KK)                                                                  \
@@ -290,6 +299,18 @@ int launch_bmu_dma(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx
 #undef DBGSOM_DMA_WIDTH
 #undef DBGSOM_DMA_LAUNCH
     return launch_status("bmu_dma_kernel");
+}
+
+int launch_bmu_dma(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx,
+                   const double *W, int64_t M, const double *ww, int k, int round_f32,
+                   int64_t *idx, double *dist, hipStream_t s) {
+    return launch_bmu_dma_form<Metric::L2>(X, x_dtype, N, d, ldx, xx, W, M, ww, k, round_f32, idx, dist, s);
+}
+
+int launch_bmu_dma_cosine(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *u,
+                          const double *W, int64_t M, const double *v, int k, int64_t *idx, double *dist,
+                          hipStream_t s) {
+    return launch_bmu_dma_form<Metric::COSINE>(X, x_dtype, N, d, ldx, u, W, M, v, k, 0, idx, dist, s);
 }
 
 }  // namespace dbgsom

@@ -206,6 +206,20 @@ int kneighbors_manhattan_check(int x_dtype, int64_t N, int64_t d, int64_t ldx, i
 int launch_kneighbors_manhattan_rows(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, int k,
                                      int64_t slab_rows, int64_t *idx, double *dist, void *ws, size_t ws_bytes,
                                      hipStream_t s);
+// metric="cosine" (cosine.hip; the cosine forms of the kernels of bmu.hip, bmu_dma.hip, distances.hip): c = 1 - (a u) v
+// clamped to [0, 2], a the chain of launch_bmu, u = inv(|x|^2), v = inv(|w|^2) from launch_inv_norms; F32 / F64 rows.
+// The launchers take u where their Euclidean namesakes take xx and v where they take ww.
+int launch_inv_norms(const double *sq, int64_t n, double *out, hipStream_t s);
+int launch_bmu_cosine(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *u, const double *W,
+                      int64_t M, const double *v, int k, int64_t *idx, double *dist, hipStream_t s);
+int launch_distances_cosine(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *u, const double *W,
+                            int64_t M, const double *v, double *out, int64_t ldo, hipStream_t s);
+// (the slab form: ordinary stores, the prototypes split over blockIdx.y)
+int launch_distances_cosine_slab(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *u,
+                                 const double *W, int64_t M, const double *v, double *out, int64_t ldo, hipStream_t s);
+int launch_kneighbors_cosine(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *u, const double *W,
+                             int64_t M, const double *v, int k, int64_t slab_rows, int64_t *idx, double *dist, void *ws,
+                             size_t ws_bytes, hipStream_t s);
 // fit on rows with missing entries: sums [S (M x d) | K (M x d) | A (M x d) | a | E] over the observed entries
 // (masked_fit.hip), and the smoothing with a denominator per (neuron, feature) (smooth.hip)
 size_t accumulate_masked_workspace_bytes(int64_t N, int64_t d, int64_t M);

@@ -77,15 +77,19 @@ __device__ __forceinline__ void put(T v, T *p) {
     else __builtin_nontemporal_store(v, p);
 }
 
-template <bool SQ>
+template <bool SQ, Metric ME>
 __device__ __forceinline__ void store_tile(const d4_t &a, double xi, const double (&y)[4], double *__restrict__ out,
                                            int64_t i, int64_t N, int64_t ldo, int jt0, int lq, int M, int ovec) {
     double v[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        double rv = (xi + (-2.0 * a[r])) + y[r];
-        if (!(rv > 0.0)) rv = (rv != rv) ? rv : 0.0;  // max(r, 0), NaN kept
-        v[r] = SQ ? rv : sqrt(rv);
+        if constexpr (ME == Metric::COSINE) {   // xi = u_i, y = v_j: the value of the cosine search, no root
+            v[r] = pair_value_cosine(a[r], xi, y[r]);
+        } else {
+            double rv = (xi + (-2.0 * a[r])) + y[r];
+            if (!(rv > 0.0)) rv = (rv != rv) ? rv : 0.0;  // max(r, 0), NaN kept
+            v[r] = SQ ? rv : sqrt(rv);
+        }
     }
     if (ovec) {
         exchange4(v);
@@ -112,7 +116,7 @@ __device__ __forceinline__ void store_tile(const d4_t &a, double xi, const doubl
 // ---------------------------------------------------------------------------------------------
 // register-staged form: the product loop of bmu_kernel
 // ---------------------------------------------------------------------------------------------
-template <typename XT, bool SQ>
+template <typename XT, bool SQ, Metric ME = Metric::L2>
 __global__ __launch_bounds__(NT, 2) void dist_kernel(
     const XT *__restrict__ X, int64_t N, int d, int64_t ldx, const double *__restrict__ xx,
     const double *__restrict__ W, int M, const double *__restrict__ ww, int xvec, int wvec,
@@ -208,7 +212,7 @@ __global__ __launch_bounds__(NT, 2) void dist_kernel(
                 for (int r = 0; r < 4; ++r) y[r] = yy_s[parity][jl + 4 * r + lq];
 #pragma unroll
                 for (int it = 0; it < 4; ++it) {
-                    store_tile<SQ>(acc[jt][it], xi[it], y, out, i0 + wi * 64 + it * 16 + lr, N, ldo, jc + jl, lq, M,
+                    store_tile<SQ, ME>(acc[jt][it], xi[it], y, out, i0 + wi * 64 + it * 16 + lr, N, ldo, jc + jl, lq, M,
                                ovec);
                     acc[jt][it] = d4_t{0.0, 0.0, 0.0, 0.0};
                 }
@@ -226,7 +230,7 @@ __global__ __launch_bounds__(NT, 2) void dist_kernel(
 // vmcnt as the DMA loads do; loads return in order among themselves, so "all but the youngest tile's worth"
 // still means that the older tile has landed -- the wait behind a chunk's epilogue is merely longer than needed.
 // ---------------------------------------------------------------------------------------------
-template <typename XT, int JTW, bool SQ>
+template <typename XT, int JTW, bool SQ, Metric ME = Metric::L2>
 __global__ __launch_bounds__(NT, 2) void dist_dma_kernel(
     const XT *__restrict__ X, int64_t N, int d, int64_t ldx, const double *__restrict__ xx,
     const double *__restrict__ W, int M, const double *__restrict__ ww, double *__restrict__ out,
@@ -371,7 +375,7 @@ __global__ __launch_bounds__(NT, 2) void dist_dma_kernel(
                 }
 #pragma unroll
                 for (int it = 0; it < 4; ++it) {
-                    store_tile<SQ>(acc[jt][it], xi[it], y, out, i0 + wi * 64 + it * 16 + lr, N, ldo, jb, lq, M, ovec);
+                    store_tile<SQ, ME>(acc[jt][it], xi[it], y, out, i0 + wi * 64 + it * 16 + lr, N, ldo, jb, lq, M, ovec);
                     acc[jt][it] = d4_t{0.0, 0.0, 0.0, 0.0};
                 }
             }
@@ -428,10 +432,13 @@ static int distances_check(int x_dtype, int64_t N, int64_t d, int64_t ldx, int64
     return DBGSOM_OK;
 }
 
-template <bool SQ>
+// SQ: the slab form (ordinary stores, the prototypes split over blockIdx.y; under L2 the squared value).  ME =
+// Metric::COSINE: xx holds u, ww holds v (cosine.hip), F32 / F64 rows only; full-matrix and slab form store the same value
+template <bool SQ, Metric ME = Metric::L2>
 static int launch_distances_form(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx,
                                  const double *W, int64_t M, const double *ww, double *out, int64_t ldo, hipStream_t s) {
     TRY_STATUS(distances_check(x_dtype, N, d, ldx, M, ldo));
+    if (ME == Metric::COSINE) DBGSOM_REQUIRE(x_dtype != DBGSOM_BF16, "the cosine matrix takes DBGSOM_F32 or DBGSOM_F64 rows");
     if (N == 0) return DBGSOM_OK;
     DBGSOM_REQUIRE(X && xx && W && ww && out, "null pointer");
     DBGSOM_REQUIRE(is_aligned(out, 8), "out_dev must be 8-byte aligned");
@@ -452,7 +459,7 @@ static int launch_distances_form(const void *X, int x_dtype, int64_t N, int64_t 
         // (dma_chunk_tiles' cost ratios were measured for the search; this epilogue has not been measured apart)
         const int jtw = dma_chunk_tiles(x_dtype, Mb);
 #define DBGSOM_DIST_DMA(XT, JTW)                                                                          \
-    hipLaunchKernelGGL((dist_dma_kernel<XT, JTW, SQ>), grid, block, 0, s, (const XT *)X, N, (int)d, ldx, xx, W, \
+    hipLaunchKernelGGL((dist_dma_kernel<XT, JTW, SQ, ME>), grid, block, 0, s, (const XT *)X, N, (int)d, ldx, xx, W, \
                        (int)M, ww, out, ldo, ovec)
         if (x_dtype == DBGSOM_F32) {
             if (jtw == 1) DBGSOM_DIST_DMA(float, 1);
@@ -469,11 +476,11 @@ static int launch_distances_form(const void *X, int x_dtype, int64_t N, int64_t 
     const int xvec = is_aligned(X, 16) && ((ldx * xe) % 16 == 0);
     const int wvec = is_aligned(W, 16) && ((d * 8) % 16 == 0);
 #define DBGSOM_DIST(XT)                                                                                      \
-    hipLaunchKernelGGL((dist_kernel<XT, SQ>), grid, block, 0, s, (const XT *)X, N, (int)d, ldx, xx, W, (int)M, ww, \
+    hipLaunchKernelGGL((dist_kernel<XT, SQ, ME>), grid, block, 0, s, (const XT *)X, N, (int)d, ldx, xx, W, (int)M, ww, \
                        xvec, wvec, out, ldo, ovec)
     if (x_dtype == DBGSOM_F32) DBGSOM_DIST(float);
     else if (x_dtype == DBGSOM_F64) DBGSOM_DIST(double);
-    else DBGSOM_DIST(bf16_t);
+    else if constexpr (ME == Metric::L2) DBGSOM_DIST(bf16_t);
 #undef DBGSOM_DIST
     return launch_status("dist_kernel");
 }
@@ -486,6 +493,16 @@ int launch_distances(const void *X, int x_dtype, int64_t N, int64_t d, int64_t l
 int launch_distances_squared(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx,
                              const double *W, int64_t M, const double *ww, double *out, int64_t ldo, hipStream_t s) {
     return launch_distances_form<true>(X, x_dtype, N, d, ldx, xx, W, M, ww, out, ldo, s);
+}
+
+int launch_distances_cosine(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *u, const double *W,
+                            int64_t M, const double *v, double *out, int64_t ldo, hipStream_t s) {
+    return launch_distances_form<false, Metric::COSINE>(X, x_dtype, N, d, ldx, u, W, M, v, out, ldo, s);
+}
+
+int launch_distances_cosine_slab(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *u,
+                                 const double *W, int64_t M, const double *v, double *out, int64_t ldo, hipStream_t s) {
+    return launch_distances_form<true, Metric::COSINE>(X, x_dtype, N, d, ldx, u, W, M, v, out, ldo, s);
 }
 
 static int distances_masked_check(int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, int64_t ldo) {

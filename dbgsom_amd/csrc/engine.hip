@@ -285,6 +285,10 @@ struct dbgsom_ctx {
     // and, for float32 rows, their float64 copy; its contents are made per call, the allocation is kept between the
     // epochs of a fit and goes with the context, counted in "device_bytes" like every buffer of CTX_DEVBUFS)
     DevBuf l1_ws;
+    // metric="cosine" (cosine.hip): u = inv(|x|^2) of the resident rows, made once per load from their resident norms
+    // (cos_u_ready), and [|w|^2 | v] of the prototypes of the call; both go with the context, counted in "device_bytes"
+    DevBuf cos_u, cos_v;
+    bool cos_u_ready = false;
     // samples
     Samples xs, xq;
     DevBuf y;
@@ -1109,6 +1113,36 @@ int resident_bmu_manhattan(dbgsom_ctx *c, const double *W, int64_t ldw, int64_t 
     return launch_bmu_manhattan_rows(s.X, s.dtype, s.N, s.d, s.dp, M, k, idx, dist, c->l1_ws.p, c->l1_ws.cap, c->stream);
 }
 
+// what the cosine calls on the resident rows need: dense float32 / float64 rows, complete, no weights, one rank
+int cosine_ready(const dbgsom_ctx *c, const char *fn) {
+    TRY(loaded(c, fn));
+    const char *why = nullptr;
+    if (c->xs.csr) why = "CSR residents have no cosine search";
+    else if (c->xs.dtype == DBGSOM_BF16) why = "bfloat16 storage has no cosine search";
+    else if (c->incomplete) why = "the resident rows have missing entries (option \"incomplete\")";
+    else if (c->has_weights) why = "sample weights are attached";
+    else if (c->coll_nranks > 1 || c->allreduce) why = "more than one rank";
+    if (why) { set_error("%s: %s", fn, why); return DBGSOM_EINVAL; }
+    return DBGSOM_OK;
+}
+
+// the k nearest prototypes of every resident row under 1 - cos: W (device, M rows of dp values) -> idx / dist (N x k).
+// u = inv(|x|^2) of the resident rows is made from their resident norms on the first call after a load and kept;
+// the prototypes' norms and v are made per call.
+int resident_bmu_cosine(dbgsom_ctx *c, const double *W, int64_t M, int k, int64_t *idx, double *dist) {
+    Samples &s = c->xs;
+    if (!c->cos_u_ready) {
+        TRY(c->cos_u.reserve((size_t)s.N * 8));
+        TRY(launch_inv_norms(s.xx.as<double>(), s.N, c->cos_u.as<double>(), c->stream));
+        c->cos_u_ready = true;
+    }
+    TRY(c->cos_v.reserve((size_t)M * 16));   // [squared norms | their inverses]
+    double *pp = c->cos_v.as<double>(), *v = pp + M;
+    TRY(launch_row_sqnorms(W, DBGSOM_F64, M, s.dp, s.dp, pp, c->stream));
+    TRY(launch_inv_norms(pp, M, v, c->stream));
+    return launch_bmu_cosine(s.Xb, s.bdtype, s.N, s.dp, s.dp, c->cos_u.as<double>(), W, M, v, k, idx, dist, c->stream);
+}
+
 // BMU of the resident samples for the reductions around the path: k = 1 by policy, k = 2 all-pairs.
 // Results in qidx / qdist (N x k); the training hint (idx[icur], bucket order) is left alone.
 int resident_bmu(dbgsom_ctx *c, const double *W_host, int64_t M, int k, int round_f32) {
@@ -1193,7 +1227,7 @@ int dbgsom_ctx_create(int device, dbgsom_ctx **out) {
      &(c)->shard_gather, &(c)->sw, &(c)->wh_order, &(c)->wh_ws, &(c)->sc_ws, &(c)->sc_x, &(c)->sc_w, &(c)->sc_p, &(c)->sc_code, &(c)->sc_proba, &(c)->sc_cnt, &(c)->wt,  \
      &(c)->mk_ws, &(c)->mk_x, &(c)->mk_w, &(c)->mk_idx, &(c)->mk_dist, &(c)->mf_nobs, &(c)->mf_x64, &(c)->mf_wt, &(c)->mf_w,   \
      &(c)->mf_wn, &(c)->mf_idx, &(c)->mf_dist, &(c)->mf_kw, &(c)->mf_sums, &(c)->mf_acc_ws, &(c)->mf_sm_ws, &(c)->mf_scal, \
-     &(c)->pd_out, &(c)->kn_ws, &(c)->kn_idx, &(c)->kn_dist, &(c)->l1_ws}
+     &(c)->pd_out, &(c)->kn_ws, &(c)->kn_idx, &(c)->kn_dist, &(c)->l1_ws, &(c)->cos_u, &(c)->cos_v}
 
 int dbgsom_ctx_destroy(dbgsom_ctx *c) {
     if (!c) return DBGSOM_OK;
@@ -1383,6 +1417,7 @@ static void reset_training_state(dbgsom_ctx *c) {
     c->has_labels = false;
     c->has_weights = false;
     c->incomplete = false;
+    c->cos_u_ready = false;   // (u belongs to the rows that were resident)
     c->policy.reset();
     c->prepass_mean = NAN;
     c->last_anchor_seeded = false;
@@ -2702,6 +2737,217 @@ int dbgsom_ctx_kneighbors_query_manhattan_device(dbgsom_ctx *c, const void *Xq_d
     DBGSOM_REQUIRE(Xq_dev && W_host && idx_dev && dist_dev, "null pointer");
     CTX_CHECK(c);
     return manhattan_query(c, L1_KNEIGHBORS, QueryRows{Xq_dev, true, ldx}, x_dtype, Nq, d, W_host, M, k, idx_dev, dist_dev, 0);
+}
+
+// ------------------------------------------------------------------------------------------
+// metric="cosine": the search of the resident rows and one epoch on it, and the queries (cosine.hip and the cosine
+// forms of the MFMA kernels)
+// ------------------------------------------------------------------------------------------
+int dbgsom_ctx_bmu_cosine(dbgsom_ctx *c, const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host) {
+    CTX_CHECK(c);
+    TRY(cosine_ready(c, __func__));
+    DBGSOM_REQUIRE(W_host && idx_host && dist_host && (k == 1 || k == 2), "bad arguments");
+    DBGSOM_REQUIRE(M >= k && M <= 0x7fffff00, "need k <= M < 2^31");
+    Samples &s = c->xs;
+    int rc = DBGSOM_OK;
+    do {
+        if ((rc = c->mk_w.reserve((size_t)M * s.dp * 8))) break;
+        if ((rc = c->qidx.reserve((size_t)s.N * k * 8))) break;
+        if ((rc = c->qdist.reserve((size_t)s.N * k * 8))) break;
+        if ((rc = upload_padded(c, c->mk_w.p, W_host, M, s.d, s.dp, 8))) break;
+        if ((rc = resident_bmu_cosine(c, c->mk_w.as<double>(), M, k, c->qidx.as<int64_t>(), c->qdist.as<double>()))) break;
+        hipError_t e = hipMemcpyAsync(idx_host, c->qidx.p, (size_t)s.N * k * 8, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(dist_host, c->qdist.p, (size_t)s.N * k * 8, hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
+        c->x_down((size_t)s.N * k * 16);
+    } while (0);
+    const hipError_t es = hipStreamSynchronize(c->stream);   // (W_host is pageable: never return with its copy in flight)
+    if (rc == DBGSOM_OK && es != hipSuccess) { set_error("hipStreamSynchronize failed: %s", hipGetErrorString(es)); rc = DBGSOM_EHIP; }
+    return rc;
+}
+
+// The cosine search of the resident rows in front of the ordinary sums and smoothing of dbgsom_ctx_epoch.  The winners
+// are no seeds and the distances no bounds of a later Euclidean search: hint and bound are dropped, and the search
+// policy is not consulted (there is no filtered form of this metric).
+int dbgsom_ctx_epoch_cosine(dbgsom_ctx *c, const double *W_host, int64_t M, double gamma, double sigma, int layout,
+                            double *W_new_host, double *change_total_host, double *errors_host,
+                            double *activations_host, int64_t *idx_host, double *dist_host) {
+    CTX_CHECK(c);
+    TRY(cosine_ready(c, __func__));
+    DBGSOM_REQUIRE(W_host && W_new_host && change_total_host && errors_host && activations_host, "null pointer");
+    DBGSOM_REQUIRE(M >= 1 && sigma > 0.0, "bad arguments");
+    DBGSOM_REQUIRE(layout == DBGSOM_CENTRES_COMPACT || layout == DBGSOM_CENTRES_ALIGNED, "bad layout");
+    if (c->topoM != M) {
+        set_error("dbgsom_ctx_epoch_cosine: topology holds %lld neurons, weights %lld (call "
+                  "dbgsom_ctx_set_topology after growth)", (long long)c->topoM, (long long)M);
+        return DBGSOM_ESTATE;
+    }
+    Samples &s = c->xs;
+    int rc = DBGSOM_OK;
+    do {
+        if ((rc = stage_weights(c, W_host, M, s.d, s.dp))) break;
+        if ((rc = c->idx[0].reserve((size_t)s.N * 8))) break;
+        if ((rc = c->idx[1].reserve((size_t)s.N * 8))) break;
+        if ((rc = c->dist.reserve((size_t)s.N * 8))) break;
+        int64_t *idx = c->idx[c->icur ^ 1].as<int64_t>();
+        c->last_filtered = false;
+        c->last_deferred = false;
+        c->hint_valid = false;
+        c->dist_bound_valid = false;
+        if ((rc = resident_bmu_cosine(c, c->Wb[c->cur].as<double>(), M, 1, idx, c->dist.as<double>()))) break;
+        c->icur ^= 1;
+        c->last_idx_valid = true;
+        if ((rc = accumulate_and_reduce(c, idx, nullptr, gamma, c->dist.as<double>(), M))) break;
+        rc = smooth_and_fetch(c, M, sigma, layout, 0, W_new_host, change_total_host, errors_host, activations_host, idx,
+                              idx_host, dist_host);
+    } while (0);
+    if (rc != DBGSOM_OK && rc != DBGSOM_ERANGE) (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+namespace {
+
+enum CosOp { COS_BMU, COS_DISTANCES, COS_KNEIGHBORS };
+
+// One cosine query in chunks of rows.  Rows from the host (q.on_device false): a chunk goes up into mk_x, its result
+// is staged (mk_idx / mk_dist, pd_out, kn_idx / kn_dist as for the Manhattan calls) and comes down behind the kernel.
+// Rows in HBM: the kernels read them where they are, q.ldx elements apart (no padded copy: the register-staged form
+// takes any row pitch), and write the caller's device arrays.  Squared norms and their inverses are made per chunk
+// (rows) and per call (prototypes) in query-sized scratch.  idx_out / dist_out: Nq x k (COS_DISTANCES: dist_out is the
+// matrix, rows ldo apart).
+int cosine_query(dbgsom_ctx *c, CosOp op, const QueryRows &q, int x_dtype, int64_t Nq, int64_t d, const double *W_host,
+                 int64_t M, int k, int64_t *idx_out, double *dist_out, int64_t ldo) {
+    const size_t es = dtype_size(x_dtype);
+    const int64_t chunk = op == COS_BMU ? std::min<int64_t>(Nq, c->masked_chunk_rows) : distances_chunk(c, Nq, M, d * 8);
+    const bool knn = op == COS_KNEIGHBORS;
+    DevBuf &si = knn ? c->kn_idx : c->mk_idx, &sd = op == COS_DISTANCES ? c->pd_out : (knn ? c->kn_dist : c->mk_dist);
+    const int64_t per_row = op == COS_DISTANCES ? M : k;   // values of a row's result
+    DevBuf vq, uq;   // [squared norms | their inverses] of the prototypes and of one chunk of rows
+    int rc = DBGSOM_OK;
+    do {
+        if (knn && (rc = c->kn_ws.reserve(kneighbors_workspace_bytes(chunk, M, c->kneighbors_slab_rows)))) break;
+        if ((rc = c->mk_w.reserve((size_t)M * d * 8))) break;
+        if ((rc = vq.reserve((size_t)M * 16))) break;
+        if ((rc = uq.reserve((size_t)chunk * 16))) break;
+        if (!q.on_device) {
+            if ((rc = c->mk_x.reserve((size_t)chunk * d * es))) break;
+            if (op != COS_DISTANCES && (rc = si.reserve((size_t)chunk * k * 8))) break;
+            if ((rc = sd.reserve((size_t)chunk * per_row * 8))) break;
+        }
+        hipError_t e = hipMemcpyAsync(c->mk_w.p, W_host, (size_t)M * d * 8, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
+        const double *W = c->mk_w.as<double>(), *v = vq.as<double>() + M;
+        double *u = uq.as<double>() + chunk;
+        if ((rc = launch_row_sqnorms(W, DBGSOM_F64, M, d, d, vq.as<double>(), c->stream))) break;
+        if ((rc = launch_inv_norms(vq.as<double>(), M, vq.as<double>() + M, c->stream))) break;
+        for (int64_t r0 = 0; r0 < Nq && rc == DBGSOM_OK; r0 += chunk) {
+            const int64_t n = std::min(chunk, Nq - r0);
+            const void *X = static_cast<const char *>(q.p) + (size_t)r0 * q.ldx * es;
+            int64_t ldx = q.ldx, ld_res = op == COS_DISTANCES ? ldo : k;
+            int64_t *idx = idx_out ? idx_out + r0 * k : nullptr;
+            double *res = dist_out + r0 * ld_res;
+            if (!q.on_device) {
+                e = hipMemcpyAsync(c->mk_x.p, X, (size_t)n * d * es, hipMemcpyHostToDevice, c->stream);
+                if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
+                c->x_up((size_t)n * d * es);
+                X = c->mk_x.p; ldx = d;
+                idx = si.as<int64_t>(); res = sd.as<double>(); ld_res = per_row;
+            }
+            if ((rc = launch_row_sqnorms(X, x_dtype, n, d, ldx, uq.as<double>(), c->stream))) break;
+            if ((rc = launch_inv_norms(uq.as<double>(), n, u, c->stream))) break;
+            if (op == COS_BMU)
+                rc = launch_bmu_cosine(X, x_dtype, n, d, ldx, u, W, M, v, k, idx, res, c->stream);
+            else if (op == COS_DISTANCES)
+                rc = launch_distances_cosine(X, x_dtype, n, d, ldx, u, W, M, v, res, ld_res, c->stream);
+            else
+                rc = launch_kneighbors_cosine(X, x_dtype, n, d, ldx, u, W, M, v, k, c->kneighbors_slab_rows, idx, res,
+                                              c->kn_ws.p, c->kn_ws.cap, c->stream);
+            if (rc || q.on_device) continue;
+            if (op != COS_DISTANCES) {
+                e = hipMemcpyAsync(idx_out + r0 * k, idx, (size_t)n * k * 8, hipMemcpyDeviceToHost, c->stream);
+                c->x_down((size_t)n * k * 8);
+            }
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(dist_out + r0 * per_row, res, (size_t)n * per_row * 8, hipMemcpyDeviceToHost, c->stream);
+            if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
+            c->x_down((size_t)n * per_row * 8);
+        }
+    } while (0);
+    const hipError_t es_ = hipStreamSynchronize(c->stream);
+    if (rc == DBGSOM_OK && es_ != hipSuccess) {
+        set_error("hipStreamSynchronize failed: %s", hipGetErrorString(es_));
+        rc = DBGSOM_EHIP;
+    }
+    vq.release(); uq.release();
+    // do not sit on a large one-off batch
+    if (c->mk_x.cap > ((size_t)256 << 20)) { c->mk_x.release(); c->mk_idx.release(); c->mk_dist.release(); }
+    if (c->pd_out.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->pd_out.release();
+    if (c->kn_ws.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->kn_ws.release();
+    return rc;
+}
+
+}  // namespace
+
+int dbgsom_ctx_bmu_query_cosine(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host) {
+    if (!c) { set_error("%s: null context", __func__); return DBGSOM_EINVAL; }
+    TRY(masked_check_shape(x_dtype, Nq, d, d, M, k));
+    if (Nq == 0) return DBGSOM_OK;
+    DBGSOM_REQUIRE(Xq_host && W_host && idx_host && dist_host, "null pointer");
+    CTX_CHECK(c);
+    return cosine_query(c, COS_BMU, QueryRows{Xq_host, false, d}, x_dtype, Nq, d, W_host, M, k, idx_host, dist_host, 0);
+}
+
+int dbgsom_ctx_bmu_query_cosine_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d, int64_t ldx,
+                                       const double *W_host, int64_t M, int k, int64_t *idx_dev, double *dist_dev) {
+    if (!c) { set_error("%s: null context", __func__); return DBGSOM_EINVAL; }
+    TRY(masked_check_shape(x_dtype, Nq, d, ldx, M, k));
+    if (Nq == 0) return DBGSOM_OK;
+    DBGSOM_REQUIRE(Xq_dev && W_host && idx_dev && dist_dev, "null pointer");
+    CTX_CHECK(c);
+    return cosine_query(c, COS_BMU, QueryRows{Xq_dev, true, ldx}, x_dtype, Nq, d, W_host, M, k, idx_dev, dist_dev, 0);
+}
+
+int dbgsom_ctx_distances_query_cosine(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                      const double *W_host, int64_t M, double *out_host) {
+    TRY(distances_args(__func__, c, x_dtype, true, Nq, d, M));
+    TRY(masked_check_shape(x_dtype, Nq, d, d, M, 1));
+    if (Nq == 0) return DBGSOM_OK;
+    DBGSOM_REQUIRE(Xq_host && W_host && out_host, "null pointer");
+    CTX_CHECK(c);
+    return cosine_query(c, COS_DISTANCES, QueryRows{Xq_host, false, d}, x_dtype, Nq, d, W_host, M, 1, nullptr, out_host, M);
+}
+
+int dbgsom_ctx_distances_query_cosine_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d,
+                                             int64_t ldx, const double *W_host, int64_t M, double *out_dev, int64_t ldo) {
+    TRY(distances_args(__func__, c, x_dtype, true, Nq, d, M));
+    TRY(masked_check_shape(x_dtype, Nq, d, ldx, M, 1));
+    DBGSOM_REQUIRE(ldo >= M, "ldo must be >= M");
+    if (Nq == 0) return DBGSOM_OK;
+    DBGSOM_REQUIRE(Xq_dev && W_host && out_dev, "null pointer");
+    CTX_CHECK(c);
+    return cosine_query(c, COS_DISTANCES, QueryRows{Xq_dev, true, ldx}, x_dtype, Nq, d, W_host, M, 1, nullptr, out_dev, ldo);
+}
+
+int dbgsom_ctx_kneighbors_query_cosine(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                       const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host) {
+    TRY(kneighbors_args(__func__, c, x_dtype, true, Nq, d, M, k));
+    TRY(masked_check_shape(x_dtype, Nq, d, d, M, 1));
+    if (Nq == 0) return DBGSOM_OK;
+    DBGSOM_REQUIRE(Xq_host && W_host && idx_host && dist_host, "null pointer");
+    CTX_CHECK(c);
+    return cosine_query(c, COS_KNEIGHBORS, QueryRows{Xq_host, false, d}, x_dtype, Nq, d, W_host, M, k, idx_host, dist_host, 0);
+}
+
+int dbgsom_ctx_kneighbors_query_cosine_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d,
+                                              int64_t ldx, const double *W_host, int64_t M, int k, int64_t *idx_dev,
+                                              double *dist_dev) {
+    TRY(kneighbors_args(__func__, c, x_dtype, true, Nq, d, M, k));
+    TRY(masked_check_shape(x_dtype, Nq, d, ldx, M, 1));
+    if (Nq == 0) return DBGSOM_OK;
+    DBGSOM_REQUIRE(Xq_dev && W_host && idx_dev && dist_dev, "null pointer");
+    CTX_CHECK(c);
+    return cosine_query(c, COS_KNEIGHBORS, QueryRows{Xq_dev, true, ldx}, x_dtype, Nq, d, W_host, M, k, idx_dev, dist_dev, 0);
 }
 
 int dbgsom_ctx_exp_similarity(dbgsom_ctx *c, const double *dist_host, int64_t n, double gamma, double *kw_host) {

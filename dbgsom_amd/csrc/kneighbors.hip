@@ -246,6 +246,29 @@ int launch_kneighbors(const void *X, int x_dtype, int64_t N, int64_t d, int64_t 
     return DBGSOM_OK;
 }
 
+// metric="cosine": slabs of the cosine matrix (u, v: cosine.hip), then the selection that stores what it selected on
+int launch_kneighbors_cosine(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *u, const double *W,
+                             int64_t M, const double *v, int k, int64_t slab_rows, int64_t *idx, double *dist, void *ws,
+                             size_t ws_bytes, hipStream_t s) {
+    DBGSOM_REQUIRE(x_dtype == DBGSOM_F32 || x_dtype == DBGSOM_F64, "x_dtype must be DBGSOM_F32 or DBGSOM_F64");
+    DBGSOM_REQUIRE(N >= 0 && d >= 1 && ldx >= d && d <= 0x7fffffff, "bad sample shape");
+    TRY_STATUS(topk_check(N, M, M, k));
+    DBGSOM_REQUIRE(slab_rows >= 0, "slab_rows must be >= 0 (0 = the default)");
+    if (N == 0) return DBGSOM_OK;
+    DBGSOM_REQUIRE(X && u && W && v && idx && dist && ws, "null pointer");
+    TRY_STATUS(kneighbors_workspace_check("dbgsom_kneighbors_cosine", N, M, slab_rows, ws, ws_bytes, 0));
+    const int64_t rows = kneighbors_slab_rows(N, M, slab_rows), ldr = slab_ld(M);
+    double *slab = static_cast<double *>(ws);
+    const size_t es = dtype_size(x_dtype);
+    for (int64_t r0 = 0; r0 < N; r0 += rows) {
+        const int64_t n = std::min(rows, N - r0);
+        TRY_STATUS(launch_distances_cosine_slab(static_cast<const char *>(X) + (size_t)r0 * ldx * es, x_dtype, n, d, ldx,
+                                                u + r0, W, M, v, slab, ldr, s));
+        TRY_STATUS(launch_topk_rows_plain(slab, n, M, ldr, k, idx + r0 * k, dist + r0 * k, s));
+    }
+    return DBGSOM_OK;
+}
+
 // workspace: [that of bmu_masked_workspace_bytes for one slab of rows, Wt in front | the slab]
 size_t kneighbors_masked_workspace_bytes(int x_dtype, int64_t N, int64_t d, int64_t M, int64_t slab_rows) {
     if (N < 1 || M < 1 || d < 1) return 0;

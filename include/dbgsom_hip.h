@@ -740,6 +740,69 @@ int dbgsom_ctx_kneighbors_query_manhattan_device(dbgsom_ctx *ctx, const void *Xq
                                                  int64_t d, int64_t ldx, const double *W_host, int64_t M, int k,
                                                  int64_t *idx_dev, double *dist_dev);
 
+/* ---- metric="cosine" (csrc/cosine.hip; the cosine forms of the kernels of bmu.hip, bmu_dma.hip, distances.hip) ----
+ * With a_ij = <x_i, w_j>, q_i = |x_i|^2 and p_j = |w_j|^2 the sequential chains of dbgsom_bmu and
+ * dbgsom_row_sqnorms (acc = fma(x_k, w_k, acc), k ascending, float32 rows widened exactly), in float64, every
+ * operation rounded on its own:
+ *     inv(t) = 0 if t == 0;  1 / sqrt(t) if 0 < t < +inf;  NaN otherwise     (sqrt, then the division)
+ *     u_i = inv(q_i), v_j = inv(p_j);   s_ij = (a_ij * u_i) * v_j;   c_ij = 1 - s_ij  (never a fused multiply-add)
+ *     c > 2 -> 2;  not (c > 0) -> 0, except that NaN stays NaN
+ * No square root of c, no float32 rounding.  Winners are the lexicographic minimum on (c, index); a pair whose c
+ * is not below +inf (NaN or an infinity in the row, a squared norm that overflows) is never reported: index -1,
+ * distance +inf; the matrix keeps its NaN.  A zero row, or one whose squared norm underflows to 0, is at distance
+ * 1 from every prototype (the lowest index wins).  A pair's bits depend on that row and that prototype only --
+ * not on the batch, the grid, the chunk or the slab.
+ * Device level: the arguments of the Euclidean namesakes with u_dev for xx_dev, v_dev for ww_dev and without
+ * round_f32; X DBGSOM_F32 / DBGSOM_F64 (DBGSOM_BF16: DBGSOM_EINVAL).  dbgsom_inv_norms: out[i] = inv(sq[i]) for n
+ * values (both 8-byte aligned; in place is not supported).  dbgsom_kneighbors_cosine stores the distance it selected
+ * on; its workspace is that of dbgsom_kneighbors (16-byte aligned; a short one is DBGSOM_ENOMEM). */
+int dbgsom_inv_norms(const double *sq_dev, int64_t n, double *out_dev, void *stream);
+int dbgsom_bmu_cosine(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *u_dev,
+                      const double *W_dev, int64_t M, const double *v_dev, int k, int64_t *idx_dev,
+                      double *dist_dev, void *stream);
+int dbgsom_distances_cosine(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *u_dev,
+                            const double *W_dev, int64_t M, const double *v_dev, double *out_dev, int64_t ldo,
+                            void *stream);
+size_t dbgsom_kneighbors_cosine_workspace_bytes(int64_t N, int64_t M, int64_t slab_rows);
+int dbgsom_kneighbors_cosine(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *u_dev,
+                             const double *W_dev, int64_t M, const double *v_dev, int k, int64_t slab_rows,
+                             int64_t *idx_dev, double *dist_dev, void *workspace_dev, size_t workspace_bytes,
+                             void *stream);
+/* Context level, resident rows.  dbgsom_ctx_bmu_cosine: the search of the resident rows, k in {1, 2}, idx / dist
+ * N x k to the host.  dbgsom_ctx_epoch_cosine: that search with k = 1 in front of the sums and the smoothing of
+ * dbgsom_ctx_epoch (same kernels, `layout` honoured, same outputs); the prototypes (M x d) are handed over with
+ * every call, hint and bound are dropped, the search policy is not consulted; idx_host / dist_host (N each) may
+ * be NULL; needs dbgsom_ctx_set_topology for M neurons (DBGSOM_ESTATE otherwise).  u of the resident rows is made
+ * once per load, on the first of these calls, and stays in HBM (8 N bytes, counted in "device_bytes").  Both
+ * return DBGSOM_EINVAL, with the reason in the message, on CSR residents, bfloat16 storage, rows marked
+ * incomplete, attached sample weights and more than one rank. */
+int dbgsom_ctx_bmu_cosine(dbgsom_ctx *ctx, const double *W_host, int64_t M, int k, int64_t *idx_host,
+                          double *dist_host);
+int dbgsom_ctx_epoch_cosine(dbgsom_ctx *ctx, const double *W_host, int64_t M, double gamma, double sigma,
+                            int layout, double *W_new_host, double *change_total_host, double *errors_host,
+                            double *activations_host, int64_t *idx_host, double *dist_host);
+/* Context level, queries: as the _manhattan queries above -- host rows (Nq x d, contiguous) go up in chunks of
+ * "masked_chunk_rows" rows for the search and "distances_chunk_rows" for the matrix and the selection, only the
+ * results come down, the traffic counters count both.  _device: rows in HBM, ldx >= d elements apart, read where
+ * they are (no copy, whatever ldx and the alignment); the results are device arrays the kernels write (out_dev
+ * rows ldo >= M apart); nothing of X or of the result crosses PCIe. */
+int dbgsom_ctx_bmu_query_cosine(dbgsom_ctx *ctx, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host);
+int dbgsom_ctx_bmu_query_cosine_device(dbgsom_ctx *ctx, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d,
+                                       int64_t ldx, const double *W_host, int64_t M, int k, int64_t *idx_dev,
+                                       double *dist_dev);
+int dbgsom_ctx_distances_query_cosine(dbgsom_ctx *ctx, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                      const double *W_host, int64_t M, double *out_host);
+int dbgsom_ctx_distances_query_cosine_device(dbgsom_ctx *ctx, const void *Xq_dev, int x_dtype, int64_t Nq,
+                                             int64_t d, int64_t ldx, const double *W_host, int64_t M,
+                                             double *out_dev, int64_t ldo);
+int dbgsom_ctx_kneighbors_query_cosine(dbgsom_ctx *ctx, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                       const double *W_host, int64_t M, int k, int64_t *idx_host,
+                                       double *dist_host);
+int dbgsom_ctx_kneighbors_query_cosine_device(dbgsom_ctx *ctx, const void *Xq_dev, int x_dtype, int64_t Nq,
+                                              int64_t d, int64_t ldx, const double *W_host, int64_t M, int k,
+                                              int64_t *idx_dev, double *dist_dev);
+
 /* ---- sparse coding: BaseSom.transform / SomClassifier.predict_proba (BaseSom.py:241-268,
  * SomClassifier.py:178-220) ------------------------------------------------------------------------
  * scikit-learn's SparseCoder(dictionary=normalize(W), transform_algorithm="lasso_lars",

@@ -1,6 +1,7 @@
 # registers, scratch, occupancy and LDS of every kernel of a source file, from the compiler's own remarks
 #   bash tools/resource_usage.sh filter      (CPU only: hipcc cross-compiles)
 #   bash tools/resource_usage.sh manhattan   (the table of DESIGN 4j)
+#   bash tools/resource_usage.sh bmu_dma     (with bmu, distances, cosine: the table of DESIGN 4k)
 f=${1:-filter}
 cd "$(dirname "$0")/../dbgsom_amd/csrc"
 /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -ffp-contract=on -Rpass-analysis=kernel-resource-usage \
