@@ -934,22 +934,7 @@ class HipBackend(HotPathBackend):
     def bmu_masked(self, W, k, X, want_filled=False):
         """The search over the observed entries of every row on the device (csrc/masked.hip), in chunks of
         ``masked_chunk_rows`` rows; with ``want_filled`` each chunk is filled there after its search."""
-        X = np.ascontiguousarray(X)
-        if X.dtype not in (np.float32, np.float64):
-            X = X.astype(np.float64)
-        W64 = np.ascontiguousarray(W, dtype=np.float64)
-        if X.ndim != 2 or W64.ndim != 2 or W64.shape[1] != X.shape[1]:
-            raise ValueError("prototype / sample feature mismatch")
-        N = X.shape[0]
-        idx = np.empty((N, k), dtype=np.int64)
-        dist = np.empty((N, k), dtype=np.float64)
-        filled = np.empty_like(X) if want_filled else None
-        self._call("dbgsom_ctx_bmu_query_masked", self._ctx, X.ctypes.data if N else None, _x_dtype_code(X.dtype), N,
-                   X.shape[1], W64.ctypes.data, W64.shape[0], int(k), idx.ctypes.data, dist.ctypes.data,
-                   None if filled is None else filled.ctypes.data)
-        if k == 1:
-            dist, idx = dist.reshape(-1), idx.reshape(-1)
-        return (dist, idx, filled) if want_filled else (dist, idx)
+        return self._metric_bmu("masked", W, k, X, want_filled)
 
     # -- the distance matrix of a query ----------------------------------------------------------------
     # rows per chunk of the host-array calls (0, the default: as many as keep a chunk's staged result at 256 MiB)
@@ -992,18 +977,7 @@ class HipBackend(HotPathBackend):
     def distances_masked(self, W, X):
         """The distances over the observed entries of every row on the device (csrc/distances.hip), in chunks of
         ``distances_chunk_rows`` rows."""
-        X = np.ascontiguousarray(X)
-        if X.dtype not in (np.float32, np.float64):
-            X = X.astype(np.float64)
-        W64 = np.ascontiguousarray(W, dtype=np.float64)
-        if X.ndim != 2 or W64.ndim != 2 or W64.shape[1] != X.shape[1]:
-            raise ValueError("prototype / sample feature mismatch")
-        N, M = X.shape[0], W64.shape[0]
-        out = np.empty((N, M), dtype=np.float64)
-        if N:
-            self._call("dbgsom_ctx_distances_query_masked", self._ctx, X.ctypes.data, _x_dtype_code(X.dtype), N,
-                       X.shape[1], W64.ctypes.data, M, out.ctypes.data)
-        return out
+        return self._metric_distances("masked", W, X)
 
     # -- the k nearest prototypes of a query -----------------------------------------------------------
     # rows per slab of squared distances (0, the default: as many, in multiples of 128, as keep the slab at 64 MiB)
@@ -1055,32 +1029,24 @@ class HipBackend(HotPathBackend):
     def kneighbors_masked(self, W, k, X):
         """The k nearest prototypes over the observed entries of every row on the device (csrc/kneighbors.hip on the
         masked chain of csrc/distances.hip), in chunks of ``distances_chunk_rows`` rows."""
-        X = np.ascontiguousarray(X)
-        if X.dtype not in (np.float32, np.float64):
-            X = X.astype(np.float64)
-        W64 = np.ascontiguousarray(W, dtype=np.float64)
-        if X.ndim != 2 or W64.ndim != 2 or W64.shape[1] != X.shape[1]:
-            raise ValueError("prototype / sample feature mismatch")
-        N, M, k = X.shape[0], W64.shape[0], int(k)
-        self._check_neighbors(k, M)
-        dist, idx = np.empty((N, k), dtype=np.float64), np.empty((N, k), dtype=np.int64)
-        if N:
-            self._call("dbgsom_ctx_kneighbors_query_masked", self._ctx, X.ctypes.data, _x_dtype_code(X.dtype), N,
-                       X.shape[1], W64.ctypes.data, M, k, idx.ctypes.data, dist.ctypes.data)
-        return dist, idx
+        return self._metric_kneighbors("masked", W, k, X)
 
     # -- metric="manhattan" (csrc/manhattan.hip) --------------------------------------------------------
     _manhattan = property(lambda self: self._metric == "manhattan")
     _cosine = property(lambda self: self._metric == "cosine")
     _other_metric = property(lambda self: self._metric != "euclidean")   # the resident search is not the Euclidean one
-    _METRIC_NAME = {"manhattan": "Manhattan", "cosine": "cosine"}
+    _METRIC_NAME = {"manhattan": "Manhattan", "cosine": "cosine", "masked": "masked"}
 
-    def _manhattan_args(self, W, X, name="Manhattan"):
-        """-> (W64, X as the calls take it, on_device, (code, N, d, ldx))"""
+    def _dense_rows_args(self, W, X, form):
+        """The arguments of a query on dense rows, host or device ("masked": host only)
+        -> (W64, X as the calls take it, on_device, (code, N, d, ldx))"""
         W64 = np.ascontiguousarray(W, dtype=np.float64)
+        name = self._METRIC_NAME[form]
         if is_sparse(X):
             raise TypeError(f"the {name} calls take dense rows")
         if is_device_array(X):
+            if form == "masked":
+                raise TypeError("the masked calls take host rows")
             rows = self._device_rows(X)
             on_device = True
         else:
@@ -1095,11 +1061,14 @@ class HipBackend(HotPathBackend):
             raise ValueError("prototype / sample feature mismatch")
         return W64, X, on_device, rows
 
-    def _metric_bmu(self, metric, W, k, X):
-        """The search of ``metric`` ("manhattan", "cosine") on the device, host rows in chunks of ``masked_chunk_rows``
-        rows; for rows in HBM distances and winners are arrays on X's device that the search writes itself."""
-        W64, X, on_device, (code, N, d, ldx) = self._manhattan_args(W, X, self._METRIC_NAME[metric])
+    def _metric_bmu(self, metric, W, k, X, want_filled=False):
+        """The search of ``metric`` ("manhattan", "cosine", or "masked": over the observed entries) on the device, host
+        rows in chunks of ``masked_chunk_rows`` rows; for rows in HBM distances and winners are arrays on X's device
+        that the search writes itself.  ``want_filled`` ("masked"): the filled rows are a third result."""
+        W64, X, on_device, (code, N, d, ldx) = self._dense_rows_args(W, X, metric)
         k = int(k)
+        filled = np.empty_like(X) if want_filled else None
+        extra = (None if filled is None else filled.ctypes.data,) if metric == "masked" else ()
         if on_device:
             idx, dist = device_empty(X, (N, k), "int64"), device_empty(X, (N, k), "float64")
             if N:
@@ -1110,15 +1079,15 @@ class HipBackend(HotPathBackend):
         else:
             idx, dist = np.empty((N, k), dtype=np.int64), np.empty((N, k), dtype=np.float64)
             self._call(f"dbgsom_ctx_bmu_query_{metric}", self._ctx, X.ctypes.data if N else None, code, N, d,
-                       W64.ctypes.data, W64.shape[0], k, idx.ctypes.data, dist.ctypes.data)
+                       W64.ctypes.data, W64.shape[0], k, idx.ctypes.data, dist.ctypes.data, *extra)
         if k == 1:
-            return dist.reshape(-1), idx.reshape(-1)
-        return dist, idx
+            dist, idx = dist.reshape(-1), idx.reshape(-1)
+        return (dist, idx, filled) if want_filled else (dist, idx)
 
     def _metric_distances(self, metric, W, X):
         """Every distance of that search, stored: host rows in chunks of ``distances_chunk_rows`` rows; for rows in
         HBM the result is a float64 array on their device that the kernel writes itself."""
-        W64, X, on_device, (code, N, d, ldx) = self._manhattan_args(W, X, self._METRIC_NAME[metric])
+        W64, X, on_device, (code, N, d, ldx) = self._dense_rows_args(W, X, metric)
         M = W64.shape[0]
         if on_device:
             out = device_empty(X, (N, M), "float64")
@@ -1136,7 +1105,7 @@ class HipBackend(HotPathBackend):
     def _metric_kneighbors(self, metric, W, k, X):
         """The k nearest prototypes under that distance: a slab of ``kneighbors_slab_rows`` rows of distances stays
         on the device, the selection kernel of csrc/kneighbors.hip reads it back and stores what it selected on."""
-        W64, X, on_device, (code, N, d, ldx) = self._manhattan_args(W, X, self._METRIC_NAME[metric])
+        W64, X, on_device, (code, N, d, ldx) = self._dense_rows_args(W, X, metric)
         M, k = W64.shape[0], int(k)
         self._check_neighbors(k, M)
         if on_device:

@@ -804,6 +804,21 @@ void mark(dbgsom_ctx *c, int k) {
     (void)hipEventRecord(c->ev[k], c->stream);
 }
 
+// the three arrays of host CSR rows into s.indptr / s.indices / s.data, behind whatever runs on the context's stream
+int upload_csr_arrays(dbgsom_ctx *c, Samples &s, const int64_t *indptr_host, const int32_t *indices_host,
+                      const void *data_host, int x_dtype, int64_t N, int64_t nnz) {
+    const size_t es = dtype_size(x_dtype);
+    TRY(s.indptr.reserve((size_t)(N + 1) * 8));
+    TRY(s.indices.reserve((size_t)(nnz > 0 ? nnz : 1) * 4));
+    TRY(s.data.reserve((size_t)(nnz > 0 ? nnz : 1) * es));
+    DBGSOM_HIP_CHECK(hipMemcpyAsync(s.indptr.p, indptr_host, (size_t)(N + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (nnz > 0) {
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(s.indices.p, indices_host, (size_t)nnz * 4, hipMemcpyHostToDevice, c->stream));
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(s.data.p, data_host, (size_t)nnz * es, hipMemcpyHostToDevice, c->stream));
+    }
+    return DBGSOM_OK;
+}
+
 // CSR samples: upload the three arrays (checked on the host first) and take the norms; below
 // `densify_below` features the rows are expanded on the device into the ordinary padded form instead and `s`
 // is a dense sample set like any other (the CSR arrays are then only staged)
@@ -817,14 +832,7 @@ int place_host_csr(dbgsom_ctx *c, Samples &s, const int64_t *indptr_host, const 
     const int64_t dp = pad16(d);
     s.N = N; s.d = d; s.dp = dp; s.dtype = x_dtype; s.nnz = nnz; s.csr = false;
     s.X = s.Xb = nullptr;
-    TRY(s.indptr.reserve((size_t)(N + 1) * 8));
-    TRY(s.indices.reserve((size_t)(nnz > 0 ? nnz : 1) * 4));
-    TRY(s.data.reserve((size_t)(nnz > 0 ? nnz : 1) * es));
-    DBGSOM_HIP_CHECK(hipMemcpyAsync(s.indptr.p, indptr_host, (size_t)(N + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    if (nnz > 0) {
-        DBGSOM_HIP_CHECK(hipMemcpyAsync(s.indices.p, indices_host, (size_t)nnz * 4, hipMemcpyHostToDevice, c->stream));
-        DBGSOM_HIP_CHECK(hipMemcpyAsync(s.data.p, data_host, (size_t)nnz * es, hipMemcpyHostToDevice, c->stream));
-    }
+    TRY(upload_csr_arrays(c, s, indptr_host, indices_host, data_host, x_dtype, N, nnz));
     if (d < densify_below) {
         TRY(s.own.reserve((size_t)N * dp * es));
         TRY(launch_csr_densify(s.view(), x_dtype, N, d, dp, s.own.p, c->stream));
@@ -1091,13 +1099,17 @@ int resident_bmu_masked(dbgsom_ctx *c, const double *W_host, int64_t M, int k) {
                                       c->mf_dist.as<double>(), c->stream);
 }
 
-// what the Manhattan calls on the resident rows need: dense float32 / float64 rows, complete, no weights, one rank
-int manhattan_ready(const dbgsom_ctx *c, const char *fn) {
+enum Metric { METRIC_MANHATTAN, METRIC_COSINE };
+
+// what the Manhattan and cosine calls on the resident rows need: dense float32 / float64 rows, complete, no weights,
+// one rank
+int metric_ready(const dbgsom_ctx *c, const char *fn, Metric metric) {
     TRY(loaded(c, fn));
+    const char *name = metric == METRIC_MANHATTAN ? "Manhattan" : "cosine";
+    if (c->xs.csr) { set_error("%s: CSR residents have no %s search", fn, name); return DBGSOM_EINVAL; }
+    if (c->xs.dtype == DBGSOM_BF16) { set_error("%s: bfloat16 storage has no %s search", fn, name); return DBGSOM_EINVAL; }
     const char *why = nullptr;
-    if (c->xs.csr) why = "CSR residents have no Manhattan search";
-    else if (c->xs.dtype == DBGSOM_BF16) why = "bfloat16 storage has no Manhattan search";
-    else if (c->incomplete) why = "the resident rows have missing entries (option \"incomplete\")";
+    if (c->incomplete) why = "the resident rows have missing entries (option \"incomplete\")";
     else if (c->has_weights) why = "sample weights are attached";
     else if (c->coll_nranks > 1 || c->allreduce) why = "more than one rank";
     if (why) { set_error("%s: %s", fn, why); return DBGSOM_EINVAL; }
@@ -1111,19 +1123,6 @@ int resident_bmu_manhattan(dbgsom_ctx *c, const double *W, int64_t ldw, int64_t 
     TRY(c->l1_ws.reserve(bmu_manhattan_workspace_bytes(s.dtype, s.N, s.d, M)));
     TRY(launch_manhattan_weights(W, M, s.d, ldw, c->l1_ws.p, c->stream));
     return launch_bmu_manhattan_rows(s.X, s.dtype, s.N, s.d, s.dp, M, k, idx, dist, c->l1_ws.p, c->l1_ws.cap, c->stream);
-}
-
-// what the cosine calls on the resident rows need: dense float32 / float64 rows, complete, no weights, one rank
-int cosine_ready(const dbgsom_ctx *c, const char *fn) {
-    TRY(loaded(c, fn));
-    const char *why = nullptr;
-    if (c->xs.csr) why = "CSR residents have no cosine search";
-    else if (c->xs.dtype == DBGSOM_BF16) why = "bfloat16 storage has no cosine search";
-    else if (c->incomplete) why = "the resident rows have missing entries (option \"incomplete\")";
-    else if (c->has_weights) why = "sample weights are attached";
-    else if (c->coll_nranks > 1 || c->allreduce) why = "more than one rank";
-    if (why) { set_error("%s: %s", fn, why); return DBGSOM_EINVAL; }
-    return DBGSOM_OK;
 }
 
 // the k nearest prototypes of every resident row under 1 - cos: W (device, M rows of dp values) -> idx / dist (N x k).
@@ -1813,9 +1812,52 @@ int dbgsom_ctx_bmu_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const in
 }
 
 // ------------------------------------------------------------------------------------------
-// query rows with missing entries (NaN): csrc/masked.hip, in chunks of query rows
+// The chunked query drivers.  Every query beside the plain BMU search above -- the distance matrix and the k nearest
+// prototypes under every metric, and the search itself over rows with missing entries and under metric="manhattan"
+// and metric="cosine" -- is one of two loops over chunks of rows:
+//   raw_rows_query     masked / Manhattan / cosine: kernels that read the rows as they are stored (any row pitch)
+//   placed_rows_query  Euclidean distances and neighbours: the rows go through the query placement first
+// A chunk of host rows goes up, its result is staged on the device and comes down behind the kernel; rows in HBM are
+// read where they are and the kernels write the caller's device arrays.  Both drivers synchronise before they return,
+// on error too (W_host and the rows are pageable), and end on drop_large_query_scratch.  The exported calls further
+// down are their argument checks (query_args and the three *_checked functions) and one call of a driver.
 // ------------------------------------------------------------------------------------------
-static int64_t first_row_without_entries(const void *X, int x_dtype, int64_t N, int64_t d) {
+namespace {
+
+enum QueryOp { Q_BMU, Q_DISTANCES, Q_KNEIGHBORS };
+enum RowsForm { ROWS_MASKED, ROWS_MANHATTAN, ROWS_COSINE };
+
+// DBGSOM_REQUIRE under the name of the exported call `fn` (checks shared by several of them)
+#define REQUIRE_FN(fn, cond, msg) \
+    do { if (!(cond)) { set_error("%s: %s", fn, msg); return DBGSOM_EINVAL; } } while (0)
+
+constexpr int64_t DISTANCES_STAGE_BYTES = (int64_t)256 << 20;
+
+// rows per chunk: the option, or as many as keep the staged result -- and the staged rows -- of a chunk at 256 MiB
+int64_t distances_chunk(const dbgsom_ctx *c, int64_t Nq, int64_t M, int64_t row_bytes) {
+    int64_t rows = c->distances_chunk_rows;
+    if (rows < 1) rows = std::max<int64_t>(128, std::min(DISTANCES_STAGE_BYTES / (M * 8), DISTANCES_STAGE_BYTES / row_bytes));
+    return std::max<int64_t>(1, std::min(rows, Nq));
+}
+
+// shape checks of the distance matrix and of the k nearest prototypes
+int query_args(const char *fn, const dbgsom_ctx *c, QueryOp op, int x_dtype, bool masked_or_csr, int64_t Nq, int64_t d,
+               int64_t M, int k) {
+    if (!c) { set_error("%s: null context", fn); return DBGSOM_EINVAL; }
+    const bool dt_ok = masked_or_csr ? (x_dtype == DBGSOM_F32 || x_dtype == DBGSOM_F64) : valid_dtype(x_dtype);
+    if (!dt_ok) {
+        set_error("%s: x_dtype must be %s", fn, masked_or_csr ? "DBGSOM_F32 or DBGSOM_F64" : "DBGSOM_F32/F64/BF16");
+        return DBGSOM_EINVAL;
+    }
+    REQUIRE_FN(fn, Nq >= 0 && Nq < 0x7fffffff && d >= 1 && d <= 0x7fffffff, "bad sample shape");
+    REQUIRE_FN(fn, M >= 1 && M <= DBGSOM_MAX_PROTOTYPES, "need 1 <= M <= DBGSOM_MAX_PROTOTYPES");
+    if (op == Q_DISTANCES) return DBGSOM_OK;
+    REQUIRE_FN(fn, k >= 1 && k <= M, "need 1 <= k <= M");
+    REQUIRE_FN(fn, k <= DBGSOM_MAX_NEIGHBORS, "k must be <= DBGSOM_MAX_NEIGHBORS");
+    return DBGSOM_OK;
+}
+
+int64_t first_row_without_entries(const void *X, int x_dtype, int64_t N, int64_t d) {
     for (int64_t i = 0; i < N; ++i) {
         int64_t c = 0;
         if (x_dtype == DBGSOM_F32) {
@@ -1830,93 +1872,171 @@ static int64_t first_row_without_entries(const void *X, int x_dtype, int64_t N, 
     return -1;
 }
 
-int dbgsom_ctx_bmu_query_masked(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
-                                const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host,
-                                void *Xfilled_host) {
-    CTX_CHECK(c);
-    TRY(masked_check_shape(x_dtype, Nq, d, d, M, k));
-    if (Nq == 0) return DBGSOM_OK;
-    DBGSOM_REQUIRE(Xq_host && W_host && idx_host && dist_host, "null pointer");
-    const int64_t bad = first_row_without_entries(Xq_host, x_dtype, Nq, d);
-    if (bad >= 0) {
-        set_error("dbgsom_ctx_bmu_query_masked: row %lld has no observed entry", (long long)bad);
-        return DBGSOM_EINVAL;
+// after a query: do not sit on the scratch of a large one-off batch
+void drop_large_query_scratch(dbgsom_ctx *c) {
+    if (c->mk_ws.cap + c->mk_x.cap > ((size_t)256 << 20)) {
+        c->mk_ws.release(); c->mk_x.release(); c->mk_idx.release(); c->mk_dist.release();
     }
-    const int64_t chunk = std::min<int64_t>(Nq, c->masked_chunk_rows);
+    if (c->pd_out.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->pd_out.release();
+    if (c->kn_ws.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->kn_ws.release();
+}
+
+// the end of both drivers
+int finish_query(dbgsom_ctx *c, int rc) {
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (rc == DBGSOM_OK && e != hipSuccess) {
+        set_error("hipStreamSynchronize failed: %s", hipGetErrorString(e));
+        rc = DBGSOM_EHIP;
+    }
+    drop_large_query_scratch(c);
+    return rc;
+}
+
+// One raw-rows query: what it computes, on what, and the scratch that is its form's own.  What the forms do
+// differently are the three switches below; a new metric is a case in each.
+struct RawQuery {
+    QueryOp op;
+    RowsForm form;
+    int x_dtype;
+    int64_t d, M;
+    int k;
+    int64_t chunk;   // rows per chunk
+    DevBuf *ws;      // masked, Manhattan: the form's workspace, the prepared prototypes in front (kn_ws for the
+                     // neighbours, mk_ws otherwise); cosine: kn_ws, used for the neighbours only
+    DevBuf vq, uq;   // cosine (call-local): [squared norms | their inverses] of the prototypes, of one chunk of rows
+};
+
+// reserve and size the workspace
+int raw_rows_reserve(dbgsom_ctx *c, RawQuery &r) {
+    const bool knn = r.op == Q_KNEIGHBORS;
+    const int64_t slab = c->kneighbors_slab_rows;
+    switch (r.form) {
+    case ROWS_MASKED:
+        return r.ws->reserve(knn ? kneighbors_masked_workspace_bytes(r.x_dtype, r.chunk, r.d, r.M, slab)
+                                 : bmu_masked_workspace_bytes(r.x_dtype, r.chunk, r.d, r.M));
+    case ROWS_MANHATTAN:
+        return r.ws->reserve(knn ? kneighbors_manhattan_workspace_bytes(r.x_dtype, r.chunk, r.d, r.M, slab)
+                                 : bmu_manhattan_workspace_bytes(r.x_dtype, r.chunk, r.d, r.M));
+    case ROWS_COSINE:
+        if (knn) TRY(r.ws->reserve(kneighbors_workspace_bytes(r.chunk, r.M, slab)));
+        TRY(r.vq.reserve((size_t)r.M * 16));
+        return r.uq.reserve((size_t)r.chunk * 16);
+    }
+    return DBGSOM_OK;
+}
+
+// prepare the prototypes once per call, from their copy W (M x d)
+int raw_rows_prepare(dbgsom_ctx *c, RawQuery &r, const double *W) {
+    switch (r.form) {
+    case ROWS_MASKED: return launch_masked_weights(W, r.M, r.d, r.d, r.ws->p, c->stream);
+    case ROWS_MANHATTAN: return launch_manhattan_weights(W, r.M, r.d, r.d, r.ws->p, c->stream);
+    case ROWS_COSINE:
+        TRY(launch_row_sqnorms(W, DBGSOM_F64, r.M, r.d, r.d, r.vq.as<double>(), c->stream));
+        return launch_inv_norms(r.vq.as<double>(), r.M, r.vq.as<double>() + r.M, c->stream);
+    }
+    return DBGSOM_OK;
+}
+
+// launch the op on one chunk: n rows at X (ldx apart) -> idx (n x k) and res (n x k, or the matrix with rows ld_res apart)
+int raw_rows_launch(dbgsom_ctx *c, RawQuery &r, const double *W, const void *X, int64_t n, int64_t ldx, int64_t *idx,
+                    double *res, int64_t ld_res) {
+    const int64_t slab = c->kneighbors_slab_rows;
+    void *ws = r.ws->p;
+    const size_t cap = r.ws->cap;
+    hipStream_t s = c->stream;
+    switch (r.form) {
+    case ROWS_MASKED:
+        if (r.op == Q_BMU) return launch_bmu_masked_rows(X, r.x_dtype, n, r.d, ldx, r.M, r.k, idx, res, ws, cap, s);
+        if (r.op == Q_DISTANCES) return launch_distances_masked_rows(X, r.x_dtype, n, r.d, ldx, r.M, res, ld_res, ws, cap, s);
+        return launch_kneighbors_masked_rows(X, r.x_dtype, n, r.d, ldx, r.M, r.k, slab, idx, res, ws, cap, s);
+    case ROWS_MANHATTAN:
+        if (r.op == Q_BMU) return launch_bmu_manhattan_rows(X, r.x_dtype, n, r.d, ldx, r.M, r.k, idx, res, ws, cap, s);
+        if (r.op == Q_DISTANCES) return launch_distances_manhattan_rows(X, r.x_dtype, n, r.d, ldx, r.M, res, ld_res, ws, cap, s);
+        return launch_kneighbors_manhattan_rows(X, r.x_dtype, n, r.d, ldx, r.M, r.k, slab, idx, res, ws, cap, s);
+    case ROWS_COSINE: {
+        // (no padded copy of the rows: the register-staged form takes any row pitch; their norms are made per chunk)
+        const double *v = r.vq.as<double>() + r.M;
+        double *u = r.uq.as<double>() + r.chunk;
+        TRY(launch_row_sqnorms(X, r.x_dtype, n, r.d, ldx, r.uq.as<double>(), s));
+        TRY(launch_inv_norms(r.uq.as<double>(), n, u, s));
+        if (r.op == Q_BMU) return launch_bmu_cosine(X, r.x_dtype, n, r.d, ldx, u, W, r.M, v, r.k, idx, res, s);
+        if (r.op == Q_DISTANCES) return launch_distances_cosine(X, r.x_dtype, n, r.d, ldx, u, W, r.M, v, res, ld_res, s);
+        return launch_kneighbors_cosine(X, r.x_dtype, n, r.d, ldx, u, W, r.M, v, r.k, slab, idx, res, ws, cap, s);
+    }
+    }
+    return DBGSOM_OK;
+}
+
+// One masked, Manhattan or cosine query in chunks of rows: masked_chunk_rows for the search, distances_chunk for the
+// matrix and the neighbours.  Rows from the host (q.on_device false): a chunk goes up into mk_x, its result is staged
+// (mk_idx / mk_dist, pd_out, kn_idx / kn_dist) and comes down behind the kernel.  Rows in HBM (Manhattan, cosine): the
+// kernels read them where they are, q.ldx elements apart, and write the caller's device arrays.  idx_out / dist_out:
+// Nq x k (Q_DISTANCES: dist_out is the matrix, rows ldo apart).  Masked rows: a row without an observed entry is
+// refused under the name `fn`; Xfilled_host (Q_BMU, or null): every chunk is filled from its winners where it was
+// staged and copied there.
+int raw_rows_query(dbgsom_ctx *c, const char *fn, QueryOp op, RowsForm form, const QueryRows &q, int x_dtype, int64_t Nq,
+                   int64_t d, const double *W_host, int64_t M, int k, int64_t *idx_out, double *dist_out, int64_t ldo,
+                   void *Xfilled_host) {
+    if (form == ROWS_MASKED) {
+        const int64_t bad = first_row_without_entries(q.p, x_dtype, Nq, d);
+        if (bad >= 0) { set_error("%s: row %lld has no observed entry", fn, (long long)bad); return DBGSOM_EINVAL; }
+    }
     const size_t es = dtype_size(x_dtype);
+    const bool knn = op == Q_KNEIGHBORS;
+    RawQuery r{op, form, x_dtype, d, M, k, 0, knn ? &c->kn_ws : &c->mk_ws, DevBuf(), DevBuf()};
+    r.chunk = op == Q_BMU ? std::min<int64_t>(Nq, c->masked_chunk_rows) : distances_chunk(c, Nq, M, d * 8);
+    DevBuf &si = knn ? c->kn_idx : c->mk_idx, &sd = op == Q_DISTANCES ? c->pd_out : (knn ? c->kn_dist : c->mk_dist);
+    const int64_t per_row = op == Q_DISTANCES ? M : k;   // values of a row's result
     int rc = DBGSOM_OK;
     do {
-        if ((rc = c->mk_ws.reserve(bmu_masked_workspace_bytes(x_dtype, chunk, d, M)))) break;
-        if ((rc = c->mk_x.reserve((size_t)chunk * d * es))) break;
+        if ((rc = raw_rows_reserve(c, r))) break;
         if ((rc = c->mk_w.reserve((size_t)M * d * 8))) break;
-        if ((rc = c->mk_idx.reserve((size_t)chunk * k * 8))) break;
-        if ((rc = c->mk_dist.reserve((size_t)chunk * k * 8))) break;
+        if (!q.on_device) {
+            if ((rc = c->mk_x.reserve((size_t)r.chunk * d * es))) break;
+            if (op != Q_DISTANCES && (rc = si.reserve((size_t)r.chunk * k * 8))) break;
+            if ((rc = sd.reserve((size_t)r.chunk * per_row * 8))) break;
+        }
         hipError_t e = hipMemcpyAsync(c->mk_w.p, W_host, (size_t)M * d * 8, hipMemcpyHostToDevice, c->stream);
         if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
-        if ((rc = launch_masked_weights(c->mk_w.as<double>(), M, d, d, c->mk_ws.p, c->stream))) break;
-        for (int64_t r0 = 0; r0 < Nq && rc == DBGSOM_OK; r0 += chunk) {
-            const int64_t n = std::min(chunk, Nq - r0);
-            e = hipMemcpyAsync(c->mk_x.p, static_cast<const char *>(Xq_host) + (size_t)r0 * d * es, (size_t)n * d * es,
-                               hipMemcpyHostToDevice, c->stream);
-            if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
-            c->x_up((size_t)n * d * es);
-            c->x_down((size_t)n * k * 16 + (Xfilled_host ? (size_t)n * d * es : 0));
-            if ((rc = launch_bmu_masked_rows(c->mk_x.p, x_dtype, n, d, d, M, k, c->mk_idx.as<int64_t>(),
-                                             c->mk_dist.as<double>(), c->mk_ws.p, c->mk_ws.cap, c->stream)))
-                break;
-            e = hipMemcpyAsync(idx_host + r0 * k, c->mk_idx.p, (size_t)n * k * 8, hipMemcpyDeviceToHost, c->stream);
+        const double *W = c->mk_w.as<double>();
+        if ((rc = raw_rows_prepare(c, r, W))) break;
+        for (int64_t r0 = 0; r0 < Nq && rc == DBGSOM_OK; r0 += r.chunk) {
+            const int64_t n = std::min(r.chunk, Nq - r0);
+            const void *X = static_cast<const char *>(q.p) + (size_t)r0 * q.ldx * es;
+            int64_t ldx = q.ldx, ld_res = op == Q_DISTANCES ? ldo : k;
+            int64_t *idx = idx_out ? idx_out + r0 * k : nullptr;
+            double *res = dist_out + r0 * ld_res;
+            if (!q.on_device) {
+                e = hipMemcpyAsync(c->mk_x.p, X, (size_t)n * d * es, hipMemcpyHostToDevice, c->stream);
+                if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
+                c->x_up((size_t)n * d * es);
+                X = c->mk_x.p; ldx = d;
+                idx = si.as<int64_t>(); res = sd.as<double>(); ld_res = per_row;
+            }
+            rc = raw_rows_launch(c, r, W, X, n, ldx, idx, res, ld_res);
+            if (rc || q.on_device) continue;
+            if (op != Q_DISTANCES) {
+                e = hipMemcpyAsync(idx_out + r0 * k, idx, (size_t)n * k * 8, hipMemcpyDeviceToHost, c->stream);
+                c->x_down((size_t)n * k * 8);
+            }
             if (e == hipSuccess)
-                e = hipMemcpyAsync(dist_host + r0 * k, c->mk_dist.p, (size_t)n * k * 8, hipMemcpyDeviceToHost, c->stream);
+                e = hipMemcpyAsync(dist_out + r0 * per_row, res, (size_t)n * per_row * 8, hipMemcpyDeviceToHost, c->stream);
+            c->x_down((size_t)n * per_row * 8);
             if (e == hipSuccess && Xfilled_host) {
-                if ((rc = launch_fill_missing(c->mk_x.p, x_dtype, n, d, d, c->mk_w.as<double>(), M, d,
-                                              c->mk_idx.as<int64_t>(), k, c->stream)))
-                    break;
+                if ((rc = launch_fill_missing(c->mk_x.p, x_dtype, n, d, d, W, M, d, idx, k, c->stream))) break;
                 e = hipMemcpyAsync(static_cast<char *>(Xfilled_host) + (size_t)r0 * d * es, c->mk_x.p, (size_t)n * d * es,
                                    hipMemcpyDeviceToHost, c->stream);
+                c->x_down((size_t)n * d * es);
             }
             if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; }
         }
     } while (0);
-    const hipError_t es_ = hipStreamSynchronize(c->stream);
-    if (rc == DBGSOM_OK && es_ != hipSuccess) {
-        set_error("hipStreamSynchronize failed: %s", hipGetErrorString(es_));
-        rc = DBGSOM_EHIP;
-    }
-    if (c->mk_ws.cap + c->mk_x.cap > ((size_t)256 << 20)) {   // do not sit on a large one-off batch
-        c->mk_ws.release(); c->mk_x.release(); c->mk_idx.release(); c->mk_dist.release();
-    }
+    rc = finish_query(c, rc);
+    r.vq.release(); r.uq.release();
     return rc;
 }
 
-// ------------------------------------------------------------------------------------------
-// the distance matrix of a query: csrc/distances.hip.  The host-facing calls work in chunks of rows: a chunk goes up
-// (dense rows through the query placement, masked rows through mk_x), its Nc x M result is staged in pd_out and
-// comes down behind the kernel.
-// ------------------------------------------------------------------------------------------
-namespace {
-
-constexpr int64_t DISTANCES_STAGE_BYTES = (int64_t)256 << 20;
-
-// rows per chunk: the option, or as many as keep the staged result -- and the staged rows -- of a chunk at 256 MiB
-int64_t distances_chunk(const dbgsom_ctx *c, int64_t Nq, int64_t M, int64_t row_bytes) {
-    int64_t rows = c->distances_chunk_rows;
-    if (rows < 1) rows = std::max<int64_t>(128, std::min(DISTANCES_STAGE_BYTES / (M * 8), DISTANCES_STAGE_BYTES / row_bytes));
-    return std::max<int64_t>(1, std::min(rows, Nq));
-}
-
-int distances_args(const char *fn, const dbgsom_ctx *c, int x_dtype, bool masked_or_csr, int64_t Nq, int64_t d, int64_t M) {
-    if (!c) { set_error("%s: null context", fn); return DBGSOM_EINVAL; }
-    const bool dt_ok = masked_or_csr ? (x_dtype == DBGSOM_F32 || x_dtype == DBGSOM_F64) : valid_dtype(x_dtype);
-    if (!dt_ok) {
-        set_error("%s: x_dtype must be %s", fn, masked_or_csr ? "DBGSOM_F32 or DBGSOM_F64" : "DBGSOM_F32/F64/BF16");
-        return DBGSOM_EINVAL;
-    }
-    if (Nq < 0 || Nq >= 0x7fffffff || d < 1 || d > 0x7fffffff) { set_error("%s: bad sample shape", fn); return DBGSOM_EINVAL; }
-    if (M < 1 || M > DBGSOM_MAX_PROTOTYPES) { set_error("%s: need 1 <= M <= DBGSOM_MAX_PROTOTYPES", fn); return DBGSOM_EINVAL; }
-    return DBGSOM_OK;
-}
-
-// the prototypes of a query on the device, padded, with their norms
+// the prototypes of a Euclidean query on the device, padded, with their norms
 int place_query_weights(dbgsom_ctx *c, DevBuf &Wq, DevBuf &wwq, const double *W_host, int64_t M, int64_t d, int64_t dp) {
     TRY(Wq.reserve((size_t)M * dp * 8));
     TRY(wwq.reserve((size_t)M * 8));
@@ -1924,359 +2044,190 @@ int place_query_weights(dbgsom_ctx *c, DevBuf &Wq, DevBuf &wwq, const double *W_
     return launch_row_sqnorms(Wq.p, DBGSOM_F64, M, dp, dp, wwq.as<double>(), c->stream);
 }
 
-// the placed rows of `s` against Wq into the staged result, and that down to out_host
-int distances_chunk_down(dbgsom_ctx *c, Samples &s, const DevBuf &Wq, const DevBuf &wwq, int64_t M, double *out_host) {
-    TRY(launch_distances(s.Xb, s.bdtype, s.N, s.dp, s.dp, s.xx.as<double>(), Wq.as<double>(), M, wwq.as<double>(),
-                         c->pd_out.as<double>(), M, c->stream));
-    DBGSOM_HIP_CHECK(hipMemcpyAsync(out_host, c->pd_out.p, (size_t)s.N * M * 8, hipMemcpyDeviceToHost, c->stream));
-    c->x_down((size_t)s.N * M * 8);
-    return DBGSOM_OK;
-}
+// host CSR rows: the index arrays beside q.p, their data
+struct CsrHost {
+    const int64_t *indptr;
+    const int32_t *indices;
+    int64_t nnz;
+};
 
-int distances_finish(dbgsom_ctx *c, int rc) {
-    const hipError_t e = hipStreamSynchronize(c->stream);
-    if (rc == DBGSOM_OK && e != hipSuccess) {
-        set_error("hipStreamSynchronize failed: %s", hipGetErrorString(e));
-        rc = DBGSOM_EHIP;
-    }
-    if (c->pd_out.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->pd_out.release();   // do not sit on a large one-off batch
-    return rc;
-}
-
-}  // namespace
-
-int dbgsom_ctx_distances_query(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
-                               const double *W_host, int64_t M, double *out_host) {
-    TRY(distances_args(__func__, c, x_dtype, false, Nq, d, M));
-    if (Nq == 0) return DBGSOM_OK;
-    DBGSOM_REQUIRE(Xq_host && W_host && out_host, "null pointer");
-    CTX_CHECK(c);
+// The Euclidean distance matrix (csrc/distances.hip) or k nearest prototypes (csrc/kneighbors.hip: a chunk's squared
+// distances live slab by slab in kn_ws and only its n x k result exists) of rows that go through the query placement.
+// Host rows: in chunks of distances_chunk rows, each placed, its result staged (pd_out; kn_idx / kn_dist) and copied
+// down.  Rows in HBM: placed whole, and the kernels write the caller's device arrays (the matrix with rows ldo apart).
+// CSR rows (csr != nullptr): the three arrays go up whole, and chunks of rows are expanded into the dense rows the
+// kernels read.
+int placed_rows_query(dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHost *csr, int x_dtype, int64_t Nq, int64_t d,
+                      const double *W_host, int64_t M, int k, int64_t *idx_out, double *dist_out, int64_t ldo) {
     Samples &s = c->xq;
     DevBuf Wq, wwq;
     const int64_t dp = pad16(d);
     const size_t es = dtype_size(x_dtype);
-    const int64_t chunk = distances_chunk(c, Nq, M, dp * (int64_t)es);
+    const bool staged = !q.on_device, knn = op == Q_KNEIGHBORS;
+    const int64_t chunk = staged ? distances_chunk(c, Nq, M, dp * (int64_t)es) : Nq;
+    const int64_t per_row = knn ? k : M;   // values of a row's result
     int rc = DBGSOM_OK;
     do {
+        if (csr) {
+            s.release();
+            if ((rc = upload_csr_arrays(c, s, csr->indptr, csr->indices, q.p, x_dtype, Nq, csr->nnz))) break;
+            c->x_up((size_t)csr->nnz * (4 + es) + (size_t)(Nq + 1) * 8);
+            if ((rc = s.own.reserve((size_t)chunk * dp * es))) break;
+        }
         if ((rc = place_query_weights(c, Wq, wwq, W_host, M, d, dp))) break;
-        if ((rc = c->pd_out.reserve((size_t)chunk * M * 8))) break;
+        if (knn) {
+            if ((rc = c->kn_ws.reserve(kneighbors_workspace_bytes(chunk, M, c->kneighbors_slab_rows)))) break;
+            if (staged && (rc = c->kn_idx.reserve((size_t)chunk * k * 8))) break;
+            if (staged && (rc = c->kn_dist.reserve((size_t)chunk * k * 8))) break;
+        } else if (staged && (rc = c->pd_out.reserve((size_t)chunk * M * 8))) {
+            break;
+        }
         for (int64_t r0 = 0; r0 < Nq && rc == DBGSOM_OK; r0 += chunk) {
             const int64_t n = std::min(chunk, Nq - r0);
-            if ((rc = place_host_samples(c, s, static_cast<const char *>(Xq_host) + (size_t)r0 * d * es, x_dtype, n, d, x_dtype)))
-                break;
-            rc = distances_chunk_down(c, s, Wq, wwq, M, out_host + r0 * M);
+            if (csr) {
+                const CsrView rows{s.indptr.as<int64_t>() + r0, s.indices.as<int32_t>(), s.data.p};   // (indptr is absolute)
+                if ((rc = launch_csr_densify(rows, x_dtype, n, d, dp, s.own.p, c->stream))) break;
+                s.N = n; s.d = d; s.dp = dp; s.dtype = x_dtype; s.csr = false; s.nnz = 0;
+                s.X = s.own.p;
+                rc = finish_samples(c, s, false);
+            } else if (q.on_device) {
+                rc = place_query_rows(c, s, q, x_dtype, Nq, d);
+            } else {
+                rc = place_host_samples(c, s, static_cast<const char *>(q.p) + (size_t)r0 * d * es, x_dtype, n, d, x_dtype);
+            }
+            if (rc) break;
+            int64_t *idx = staged ? c->kn_idx.as<int64_t>() : idx_out;
+            double *res = !staged ? dist_out : (knn ? c->kn_dist.as<double>() : c->pd_out.as<double>());
+            if (knn)
+                rc = launch_kneighbors(s.Xb, s.bdtype, n, dp, dp, s.xx.as<double>(), Wq.as<double>(), M, wwq.as<double>(), k,
+                                       c->kneighbors_slab_rows, idx, res, c->kn_ws.p, c->kn_ws.cap, c->stream);
+            else
+                rc = launch_distances(s.Xb, s.bdtype, n, dp, dp, s.xx.as<double>(), Wq.as<double>(), M, wwq.as<double>(), res,
+                                      staged ? M : ldo, c->stream);
+            if (rc || !staged) continue;
+            hipError_t e = hipSuccess;
+            if (knn) e = hipMemcpyAsync(idx_out + r0 * k, idx, (size_t)n * k * 8, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(dist_out + r0 * per_row, res, (size_t)n * per_row * 8, hipMemcpyDeviceToHost, c->stream);
+            if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; }
+            c->x_down((size_t)n * per_row * (knn ? 16 : 8));
         }
     } while (0);
-    rc = distances_finish(c, rc);
+    rc = finish_query(c, rc);
     Wq.release(); wwq.release();
-    drop_query_rows(s, QueryRows{Xq_host, false, d}, chunk * dp * (int64_t)es);
+    if (csr) s.release();
+    else drop_query_rows(s, q, chunk * dp * (int64_t)es);
     return rc;
+}
+
+// ---- the argument checks of the exported calls, shared where a host / device pair or the forms have the same ones ----
+
+#define SET_DEVICE(c) DBGSOM_HIP_CHECK(hipSetDevice((c)->device))
+
+// the masked, Manhattan and cosine search (k = 1 or 2)
+int raw_bmu_checked(const char *fn, dbgsom_ctx *c, RowsForm form, const QueryRows &q, int x_dtype, int64_t Nq, int64_t d,
+                    const double *W_host, int64_t M, int k, int64_t *idx_out, double *dist_out, void *Xfilled_host) {
+    if (!c) { set_error("%s: null context", fn); return DBGSOM_EINVAL; }
+    TRY(masked_check_shape(x_dtype, Nq, d, q.ldx, M, k));
+    if (Nq == 0) return DBGSOM_OK;
+    REQUIRE_FN(fn, q.p && W_host && idx_out && dist_out, "null pointer");
+    SET_DEVICE(c);
+    return raw_rows_query(c, fn, Q_BMU, form, q, x_dtype, Nq, d, W_host, M, k, idx_out, dist_out, 0, Xfilled_host);
+}
+
+// their distance matrix (rows of the result ldo apart; k = 1) and k nearest prototypes
+int raw_rows_checked(const char *fn, dbgsom_ctx *c, QueryOp op, RowsForm form, const QueryRows &q, int x_dtype, int64_t Nq, int64_t d,
+                     const double *W_host, int64_t M, int k, int64_t *idx_out, double *dist_out, int64_t ldo) {
+    TRY(query_args(fn, c, op, x_dtype, true, Nq, d, M, k));
+    TRY(masked_check_shape(x_dtype, Nq, d, q.ldx, M, 1));
+    if (op == Q_DISTANCES) REQUIRE_FN(fn, ldo >= M, "ldo must be >= M");
+    if (Nq == 0) return DBGSOM_OK;
+    REQUIRE_FN(fn, q.p && W_host && (op == Q_DISTANCES || idx_out) && dist_out, "null pointer");
+    SET_DEVICE(c);
+    return raw_rows_query(c, fn, op, form, q, x_dtype, Nq, d, W_host, M, k, idx_out, dist_out, ldo, nullptr);
+}
+
+// the Euclidean distance matrix and k nearest prototypes of dense rows (csr == nullptr) or host CSR rows
+int placed_rows_checked(const char *fn, dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHost *csr, int x_dtype, int64_t Nq,
+                        int64_t d, const double *W_host, int64_t M, int k, int64_t *idx_out, double *dist_out, int64_t ldo) {
+    TRY(query_args(fn, c, op, x_dtype, csr != nullptr, Nq, d, M, k));
+    if (q.on_device) REQUIRE_FN(fn, q.ldx >= d, "ldx must be >= d");
+    if (op == Q_DISTANCES) REQUIRE_FN(fn, ldo >= M, "ldo must be >= M");
+    if (csr) {
+        REQUIRE_FN(fn, csr->indptr && csr->nnz >= 0 && (csr->nnz == 0 || (csr->indices && q.p)), "bad arguments");
+        TRY(dbgsom_csr_check(csr->indptr, csr->indices, Nq, d, csr->nnz));
+    }
+    if (Nq == 0) return DBGSOM_OK;
+    REQUIRE_FN(fn, (csr || q.p) && W_host && (op == Q_DISTANCES || idx_out) && dist_out, "null pointer");
+    SET_DEVICE(c);
+    return placed_rows_query(c, op, q, csr, x_dtype, Nq, d, W_host, M, k, idx_out, dist_out, ldo);
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------
+// query rows with missing entries (NaN): csrc/masked.hip and the masked forms of distances.hip / kneighbors.hip
+// ------------------------------------------------------------------------------------------
+int dbgsom_ctx_bmu_query_masked(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host,
+                                void *Xfilled_host) {
+    return raw_bmu_checked(__func__, c, ROWS_MASKED, QueryRows{Xq_host, false, d}, x_dtype, Nq, d, W_host, M, k, idx_host,
+                           dist_host, Xfilled_host);
+}
+
+int dbgsom_ctx_distances_query_masked(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                      const double *W_host, int64_t M, double *out_host) {
+    return raw_rows_checked(__func__, c, Q_DISTANCES, ROWS_MASKED, QueryRows{Xq_host, false, d}, x_dtype, Nq, d, W_host, M,
+                            1, nullptr, out_host, M);
+}
+
+int dbgsom_ctx_kneighbors_query_masked(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                       const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host) {
+    return raw_rows_checked(__func__, c, Q_KNEIGHBORS, ROWS_MASKED, QueryRows{Xq_host, false, d}, x_dtype, Nq, d, W_host, M,
+                            k, idx_host, dist_host, 0);
+}
+
+// ------------------------------------------------------------------------------------------
+// the Euclidean distance matrix and k nearest prototypes of a query: csrc/distances.hip, csrc/kneighbors.hip
+// ------------------------------------------------------------------------------------------
+int dbgsom_ctx_distances_query(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                               const double *W_host, int64_t M, double *out_host) {
+    return placed_rows_checked(__func__, c, Q_DISTANCES, QueryRows{Xq_host, false, d}, nullptr, x_dtype, Nq, d, W_host, M,
+                               1, nullptr, out_host, M);
 }
 
 int dbgsom_ctx_distances_query_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d, int64_t ldx,
                                       const double *W_host, int64_t M, double *out_dev, int64_t ldo) {
-    TRY(distances_args(__func__, c, x_dtype, false, Nq, d, M));
-    DBGSOM_REQUIRE(ldx >= d, "ldx must be >= d");
-    DBGSOM_REQUIRE(ldo >= M, "ldo must be >= M");
-    if (Nq == 0) return DBGSOM_OK;
-    DBGSOM_REQUIRE(Xq_dev && W_host && out_dev, "null pointer");
-    CTX_CHECK(c);
-    Samples &s = c->xq;
-    DevBuf Wq, wwq;
-    const int64_t dp = pad16(d);
-    const QueryRows q{Xq_dev, true, ldx};
-    int rc = DBGSOM_OK;
-    do {
-        if ((rc = place_query_rows(c, s, q, x_dtype, Nq, d))) break;
-        if ((rc = place_query_weights(c, Wq, wwq, W_host, M, d, dp))) break;
-        rc = launch_distances(s.Xb, s.bdtype, Nq, dp, dp, s.xx.as<double>(), Wq.as<double>(), M, wwq.as<double>(), out_dev,
-                              ldo, c->stream);
-    } while (0);
-    rc = distances_finish(c, rc);
-    Wq.release(); wwq.release();
-    drop_query_rows(s, q, Nq * dp * (int64_t)dtype_size(x_dtype));
-    return rc;
+    return placed_rows_checked(__func__, c, Q_DISTANCES, QueryRows{Xq_dev, true, ldx}, nullptr, x_dtype, Nq, d, W_host, M,
+                               1, nullptr, out_dev, ldo);
 }
 
 int dbgsom_ctx_distances_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const int32_t *indices_host,
                                    const void *data_host, int x_dtype, int64_t Nq, int64_t d, int64_t nnz,
                                    const double *W_host, int64_t M, double *out_host) {
-    TRY(distances_args(__func__, c, x_dtype, true, Nq, d, M));
-    DBGSOM_REQUIRE(indptr_host && nnz >= 0 && (nnz == 0 || (indices_host && data_host)), "bad arguments");
-    TRY(dbgsom_csr_check(indptr_host, indices_host, Nq, d, nnz));
-    if (Nq == 0) return DBGSOM_OK;
-    DBGSOM_REQUIRE(W_host && out_host, "null pointer");
-    CTX_CHECK(c);
-    Samples &s = c->xq;
-    DevBuf Wq, wwq;
-    const int64_t dp = pad16(d);
-    const size_t es = dtype_size(x_dtype);
-    const int64_t chunk = distances_chunk(c, Nq, M, dp * (int64_t)es);
-    int rc = DBGSOM_OK;
-    do {
-        // the three arrays go up whole; row chunks of them are expanded into the dense rows the kernel reads
-        s.release();
-        if ((rc = s.indptr.reserve((size_t)(Nq + 1) * 8))) break;
-        if ((rc = s.indices.reserve((size_t)(nnz > 0 ? nnz : 1) * 4))) break;
-        if ((rc = s.data.reserve((size_t)(nnz > 0 ? nnz : 1) * es))) break;
-        hipError_t e = hipMemcpyAsync(s.indptr.p, indptr_host, (size_t)(Nq + 1) * 8, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess && nnz > 0)
-            e = hipMemcpyAsync(s.indices.p, indices_host, (size_t)nnz * 4, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess && nnz > 0)
-            e = hipMemcpyAsync(s.data.p, data_host, (size_t)nnz * es, hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
-        c->x_up((size_t)nnz * (4 + es) + (size_t)(Nq + 1) * 8);
-        if ((rc = place_query_weights(c, Wq, wwq, W_host, M, d, dp))) break;
-        if ((rc = c->pd_out.reserve((size_t)chunk * M * 8))) break;
-        if ((rc = s.own.reserve((size_t)chunk * dp * es))) break;
-        for (int64_t r0 = 0; r0 < Nq && rc == DBGSOM_OK; r0 += chunk) {
-            const int64_t n = std::min(chunk, Nq - r0);
-            const CsrView rows{s.indptr.as<int64_t>() + r0, s.indices.as<int32_t>(), s.data.p};   // (indptr is absolute)
-            if ((rc = launch_csr_densify(rows, x_dtype, n, d, dp, s.own.p, c->stream))) break;
-            s.N = n; s.d = d; s.dp = dp; s.dtype = x_dtype; s.csr = false; s.nnz = 0;
-            s.X = s.own.p;
-            if ((rc = finish_samples(c, s, false))) break;
-            rc = distances_chunk_down(c, s, Wq, wwq, M, out_host + r0 * M);
-        }
-    } while (0);
-    rc = distances_finish(c, rc);
-    Wq.release(); wwq.release();
-    s.release();
-    return rc;
+    const CsrHost csr{indptr_host, indices_host, nnz};
+    return placed_rows_checked(__func__, c, Q_DISTANCES, QueryRows{data_host, false, d}, &csr, x_dtype, Nq, d, W_host, M,
+                               1, nullptr, out_host, M);
 }
-
-int dbgsom_ctx_distances_query_masked(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
-                                      const double *W_host, int64_t M, double *out_host) {
-    TRY(distances_args(__func__, c, x_dtype, true, Nq, d, M));
-    TRY(masked_check_shape(x_dtype, Nq, d, d, M, 1));
-    if (Nq == 0) return DBGSOM_OK;
-    DBGSOM_REQUIRE(Xq_host && W_host && out_host, "null pointer");
-    const int64_t bad = first_row_without_entries(Xq_host, x_dtype, Nq, d);
-    if (bad >= 0) {
-        set_error("dbgsom_ctx_distances_query_masked: row %lld has no observed entry", (long long)bad);
-        return DBGSOM_EINVAL;
-    }
-    CTX_CHECK(c);
-    const int64_t chunk = distances_chunk(c, Nq, M, d * 8);
-    const size_t es = dtype_size(x_dtype);
-    int rc = DBGSOM_OK;
-    do {
-        if ((rc = c->mk_ws.reserve(bmu_masked_workspace_bytes(x_dtype, chunk, d, M)))) break;
-        if ((rc = c->mk_x.reserve((size_t)chunk * d * es))) break;
-        if ((rc = c->mk_w.reserve((size_t)M * d * 8))) break;
-        if ((rc = c->pd_out.reserve((size_t)chunk * M * 8))) break;
-        hipError_t e = hipMemcpyAsync(c->mk_w.p, W_host, (size_t)M * d * 8, hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
-        if ((rc = launch_masked_weights(c->mk_w.as<double>(), M, d, d, c->mk_ws.p, c->stream))) break;
-        for (int64_t r0 = 0; r0 < Nq && rc == DBGSOM_OK; r0 += chunk) {
-            const int64_t n = std::min(chunk, Nq - r0);
-            e = hipMemcpyAsync(c->mk_x.p, static_cast<const char *>(Xq_host) + (size_t)r0 * d * es, (size_t)n * d * es,
-                               hipMemcpyHostToDevice, c->stream);
-            if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
-            c->x_up((size_t)n * d * es);
-            if ((rc = launch_distances_masked_rows(c->mk_x.p, x_dtype, n, d, d, M, c->pd_out.as<double>(), M, c->mk_ws.p,
-                                                   c->mk_ws.cap, c->stream)))
-                break;
-            e = hipMemcpyAsync(out_host + r0 * M, c->pd_out.p, (size_t)n * M * 8, hipMemcpyDeviceToHost, c->stream);
-            if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
-            c->x_down((size_t)n * M * 8);
-        }
-    } while (0);
-    rc = distances_finish(c, rc);
-    if (c->mk_ws.cap + c->mk_x.cap > ((size_t)256 << 20)) { c->mk_ws.release(); c->mk_x.release(); }
-    return rc;
-}
-
-// ------------------------------------------------------------------------------------------
-// the k nearest prototypes of a query: csrc/kneighbors.hip.  Rows are staged as for the distance matrix above (same
-// chunks of host rows, same query placement, CSR rows expanded chunk by chunk); a chunk's squared distances live
-// slab by slab in kn_ws and only its Nc x k result comes down.
-// ------------------------------------------------------------------------------------------
-namespace {
-
-int kneighbors_args(const char *fn, const dbgsom_ctx *c, int x_dtype, bool masked_or_csr, int64_t Nq, int64_t d, int64_t M,
-                    int k) {
-    TRY(distances_args(fn, c, x_dtype, masked_or_csr, Nq, d, M));
-    if (k < 1 || k > M) { set_error("%s: need 1 <= k <= M", fn); return DBGSOM_EINVAL; }
-    if (k > DBGSOM_MAX_NEIGHBORS) { set_error("%s: k must be <= DBGSOM_MAX_NEIGHBORS", fn); return DBGSOM_EINVAL; }
-    return DBGSOM_OK;
-}
-
-int kneighbors_reserve(dbgsom_ctx *c, int64_t rows, int64_t M, int k, bool staged) {
-    TRY(c->kn_ws.reserve(kneighbors_workspace_bytes(rows, M, c->kneighbors_slab_rows)));
-    if (!staged) return DBGSOM_OK;
-    TRY(c->kn_idx.reserve((size_t)rows * k * 8));
-    return c->kn_dist.reserve((size_t)rows * k * 8);
-}
-
-int kneighbors_down(dbgsom_ctx *c, int64_t n, int k, int64_t *idx_host, double *dist_host) {
-    DBGSOM_HIP_CHECK(hipMemcpyAsync(idx_host, c->kn_idx.p, (size_t)n * k * 8, hipMemcpyDeviceToHost, c->stream));
-    DBGSOM_HIP_CHECK(hipMemcpyAsync(dist_host, c->kn_dist.p, (size_t)n * k * 8, hipMemcpyDeviceToHost, c->stream));
-    c->x_down((size_t)n * k * 16);
-    return DBGSOM_OK;
-}
-
-// the placed rows of `s` against Wq: the result staged in kn_idx / kn_dist, and that down to the host
-int kneighbors_chunk_down(dbgsom_ctx *c, Samples &s, const DevBuf &Wq, const DevBuf &wwq, int64_t M, int k,
-                          int64_t *idx_host, double *dist_host) {
-    TRY(launch_kneighbors(s.Xb, s.bdtype, s.N, s.dp, s.dp, s.xx.as<double>(), Wq.as<double>(), M, wwq.as<double>(), k,
-                          c->kneighbors_slab_rows, c->kn_idx.as<int64_t>(), c->kn_dist.as<double>(), c->kn_ws.p,
-                          c->kn_ws.cap, c->stream));
-    return kneighbors_down(c, s.N, k, idx_host, dist_host);
-}
-
-int kneighbors_finish(dbgsom_ctx *c, int rc) {
-    const hipError_t e = hipStreamSynchronize(c->stream);
-    if (rc == DBGSOM_OK && e != hipSuccess) {
-        set_error("hipStreamSynchronize failed: %s", hipGetErrorString(e));
-        rc = DBGSOM_EHIP;
-    }
-    if (c->kn_ws.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->kn_ws.release();   // do not sit on a large one-off slab
-    return rc;
-}
-
-}  // namespace
 
 int dbgsom_ctx_kneighbors_query(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
                                 const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host) {
-    TRY(kneighbors_args(__func__, c, x_dtype, false, Nq, d, M, k));
-    if (Nq == 0) return DBGSOM_OK;
-    DBGSOM_REQUIRE(Xq_host && W_host && idx_host && dist_host, "null pointer");
-    CTX_CHECK(c);
-    Samples &s = c->xq;
-    DevBuf Wq, wwq;
-    const int64_t dp = pad16(d);
-    const size_t es = dtype_size(x_dtype);
-    const int64_t chunk = distances_chunk(c, Nq, M, dp * (int64_t)es);
-    int rc = DBGSOM_OK;
-    do {
-        if ((rc = place_query_weights(c, Wq, wwq, W_host, M, d, dp))) break;
-        if ((rc = kneighbors_reserve(c, chunk, M, k, true))) break;
-        for (int64_t r0 = 0; r0 < Nq && rc == DBGSOM_OK; r0 += chunk) {
-            const int64_t n = std::min(chunk, Nq - r0);
-            if ((rc = place_host_samples(c, s, static_cast<const char *>(Xq_host) + (size_t)r0 * d * es, x_dtype, n, d, x_dtype)))
-                break;
-            rc = kneighbors_chunk_down(c, s, Wq, wwq, M, k, idx_host + r0 * k, dist_host + r0 * k);
-        }
-    } while (0);
-    rc = kneighbors_finish(c, rc);
-    Wq.release(); wwq.release();
-    drop_query_rows(s, QueryRows{Xq_host, false, d}, chunk * dp * (int64_t)es);
-    return rc;
+    return placed_rows_checked(__func__, c, Q_KNEIGHBORS, QueryRows{Xq_host, false, d}, nullptr, x_dtype, Nq, d, W_host, M,
+                               k, idx_host, dist_host, 0);
 }
 
 int dbgsom_ctx_kneighbors_query_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d, int64_t ldx,
                                        const double *W_host, int64_t M, int k, int64_t *idx_dev, double *dist_dev) {
-    TRY(kneighbors_args(__func__, c, x_dtype, false, Nq, d, M, k));
-    DBGSOM_REQUIRE(ldx >= d, "ldx must be >= d");
-    if (Nq == 0) return DBGSOM_OK;
-    DBGSOM_REQUIRE(Xq_dev && W_host && idx_dev && dist_dev, "null pointer");
-    CTX_CHECK(c);
-    Samples &s = c->xq;
-    DevBuf Wq, wwq;
-    const int64_t dp = pad16(d);
-    const QueryRows q{Xq_dev, true, ldx};
-    int rc = DBGSOM_OK;
-    do {
-        if ((rc = place_query_rows(c, s, q, x_dtype, Nq, d))) break;
-        if ((rc = place_query_weights(c, Wq, wwq, W_host, M, d, dp))) break;
-        if ((rc = kneighbors_reserve(c, Nq, M, k, false))) break;
-        rc = launch_kneighbors(s.Xb, s.bdtype, Nq, dp, dp, s.xx.as<double>(), Wq.as<double>(), M, wwq.as<double>(), k,
-                               c->kneighbors_slab_rows, idx_dev, dist_dev, c->kn_ws.p, c->kn_ws.cap, c->stream);
-    } while (0);
-    rc = kneighbors_finish(c, rc);
-    Wq.release(); wwq.release();
-    drop_query_rows(s, q, Nq * dp * (int64_t)dtype_size(x_dtype));
-    return rc;
+    return placed_rows_checked(__func__, c, Q_KNEIGHBORS, QueryRows{Xq_dev, true, ldx}, nullptr, x_dtype, Nq, d, W_host, M,
+                               k, idx_dev, dist_dev, 0);
 }
 
 int dbgsom_ctx_kneighbors_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const int32_t *indices_host,
                                     const void *data_host, int x_dtype, int64_t Nq, int64_t d, int64_t nnz,
                                     const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host) {
-    TRY(kneighbors_args(__func__, c, x_dtype, true, Nq, d, M, k));
-    DBGSOM_REQUIRE(indptr_host && nnz >= 0 && (nnz == 0 || (indices_host && data_host)), "bad arguments");
-    TRY(dbgsom_csr_check(indptr_host, indices_host, Nq, d, nnz));
-    if (Nq == 0) return DBGSOM_OK;
-    DBGSOM_REQUIRE(W_host && idx_host && dist_host, "null pointer");
-    CTX_CHECK(c);
-    Samples &s = c->xq;
-    DevBuf Wq, wwq;
-    const int64_t dp = pad16(d);
-    const size_t es = dtype_size(x_dtype);
-    const int64_t chunk = distances_chunk(c, Nq, M, dp * (int64_t)es);
-    int rc = DBGSOM_OK;
-    do {
-        // the three arrays go up whole; row chunks of them are expanded into the dense rows the kernel reads
-        s.release();
-        if ((rc = s.indptr.reserve((size_t)(Nq + 1) * 8))) break;
-        if ((rc = s.indices.reserve((size_t)(nnz > 0 ? nnz : 1) * 4))) break;
-        if ((rc = s.data.reserve((size_t)(nnz > 0 ? nnz : 1) * es))) break;
-        hipError_t e = hipMemcpyAsync(s.indptr.p, indptr_host, (size_t)(Nq + 1) * 8, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess && nnz > 0)
-            e = hipMemcpyAsync(s.indices.p, indices_host, (size_t)nnz * 4, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess && nnz > 0)
-            e = hipMemcpyAsync(s.data.p, data_host, (size_t)nnz * es, hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
-        c->x_up((size_t)nnz * (4 + es) + (size_t)(Nq + 1) * 8);
-        if ((rc = place_query_weights(c, Wq, wwq, W_host, M, d, dp))) break;
-        if ((rc = kneighbors_reserve(c, chunk, M, k, true))) break;
-        if ((rc = s.own.reserve((size_t)chunk * dp * es))) break;
-        for (int64_t r0 = 0; r0 < Nq && rc == DBGSOM_OK; r0 += chunk) {
-            const int64_t n = std::min(chunk, Nq - r0);
-            const CsrView rows{s.indptr.as<int64_t>() + r0, s.indices.as<int32_t>(), s.data.p};   // (indptr is absolute)
-            if ((rc = launch_csr_densify(rows, x_dtype, n, d, dp, s.own.p, c->stream))) break;
-            s.N = n; s.d = d; s.dp = dp; s.dtype = x_dtype; s.csr = false; s.nnz = 0;
-            s.X = s.own.p;
-            if ((rc = finish_samples(c, s, false))) break;
-            rc = kneighbors_chunk_down(c, s, Wq, wwq, M, k, idx_host + r0 * k, dist_host + r0 * k);
-        }
-    } while (0);
-    rc = kneighbors_finish(c, rc);
-    Wq.release(); wwq.release();
-    s.release();
-    return rc;
-}
-
-int dbgsom_ctx_kneighbors_query_masked(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
-                                       const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host) {
-    TRY(kneighbors_args(__func__, c, x_dtype, true, Nq, d, M, k));
-    TRY(masked_check_shape(x_dtype, Nq, d, d, M, 1));
-    if (Nq == 0) return DBGSOM_OK;
-    DBGSOM_REQUIRE(Xq_host && W_host && idx_host && dist_host, "null pointer");
-    const int64_t bad = first_row_without_entries(Xq_host, x_dtype, Nq, d);
-    if (bad >= 0) {
-        set_error("dbgsom_ctx_kneighbors_query_masked: row %lld has no observed entry", (long long)bad);
-        return DBGSOM_EINVAL;
-    }
-    CTX_CHECK(c);
-    const int64_t chunk = distances_chunk(c, Nq, M, d * 8);
-    const size_t es = dtype_size(x_dtype);
-    int rc = DBGSOM_OK;
-    do {
-        if ((rc = c->kn_ws.reserve(kneighbors_masked_workspace_bytes(x_dtype, chunk, d, M, c->kneighbors_slab_rows)))) break;
-        if ((rc = c->mk_x.reserve((size_t)chunk * d * es))) break;
-        if ((rc = c->mk_w.reserve((size_t)M * d * 8))) break;
-        if ((rc = c->kn_idx.reserve((size_t)chunk * k * 8))) break;
-        if ((rc = c->kn_dist.reserve((size_t)chunk * k * 8))) break;
-        hipError_t e = hipMemcpyAsync(c->mk_w.p, W_host, (size_t)M * d * 8, hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
-        if ((rc = launch_masked_weights(c->mk_w.as<double>(), M, d, d, c->kn_ws.p, c->stream))) break;
-        for (int64_t r0 = 0; r0 < Nq && rc == DBGSOM_OK; r0 += chunk) {
-            const int64_t n = std::min(chunk, Nq - r0);
-            e = hipMemcpyAsync(c->mk_x.p, static_cast<const char *>(Xq_host) + (size_t)r0 * d * es, (size_t)n * d * es,
-                               hipMemcpyHostToDevice, c->stream);
-            if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
-            c->x_up((size_t)n * d * es);
-            if ((rc = launch_kneighbors_masked_rows(c->mk_x.p, x_dtype, n, d, d, M, k, c->kneighbors_slab_rows,
-                                                    c->kn_idx.as<int64_t>(), c->kn_dist.as<double>(), c->kn_ws.p,
-                                                    c->kn_ws.cap, c->stream)))
-                break;
-            rc = kneighbors_down(c, n, k, idx_host + r0 * k, dist_host + r0 * k);
-        }
-    } while (0);
-    rc = kneighbors_finish(c, rc);
-    if (c->mk_x.cap > ((size_t)256 << 20)) c->mk_x.release();
-    return rc;
+    const CsrHost csr{indptr_host, indices_host, nnz};
+    return placed_rows_checked(__func__, c, Q_KNEIGHBORS, QueryRows{data_host, false, d}, &csr, x_dtype, Nq, d, W_host, M,
+                               k, idx_host, dist_host, 0);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2539,223 +2490,36 @@ int dbgsom_ctx_epoch_masked(dbgsom_ctx *c, const double *W_host, int64_t M, doub
 }
 
 // ------------------------------------------------------------------------------------------
-// metric="manhattan": the search of the resident rows and one epoch on it, and the queries (manhattan.hip)
+// metric="manhattan" (manhattan.hip) and metric="cosine" (cosine.hip and the cosine forms of the MFMA kernels): the
+// search of the resident rows and one epoch on it, one body each for both metrics, and the queries (raw_rows_query)
 // ------------------------------------------------------------------------------------------
-int dbgsom_ctx_bmu_manhattan(dbgsom_ctx *c, const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host) {
-    CTX_CHECK(c);
-    TRY(manhattan_ready(c, __func__));
-    DBGSOM_REQUIRE(W_host && idx_host && dist_host && (k == 1 || k == 2), "bad arguments");
-    DBGSOM_REQUIRE(M >= k, "need k <= M");
-    Samples &s = c->xs;
-    int rc = DBGSOM_OK;
-    do {
-        if ((rc = c->mk_w.reserve((size_t)M * s.d * 8))) break;
-        if ((rc = c->qidx.reserve((size_t)s.N * k * 8))) break;
-        if ((rc = c->qdist.reserve((size_t)s.N * k * 8))) break;
-        hipError_t e = hipMemcpyAsync(c->mk_w.p, W_host, (size_t)M * s.d * 8, hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
-        if ((rc = resident_bmu_manhattan(c, c->mk_w.as<double>(), s.d, M, k, c->qidx.as<int64_t>(), c->qdist.as<double>()))) break;
-        e = hipMemcpyAsync(idx_host, c->qidx.p, (size_t)s.N * k * 8, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dist_host, c->qdist.p, (size_t)s.N * k * 8, hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
-        c->x_down((size_t)s.N * k * 16);
-    } while (0);
-    const hipError_t es = hipStreamSynchronize(c->stream);   // (W_host is pageable: never return with its copy in flight)
-    if (rc == DBGSOM_OK && es != hipSuccess) { set_error("hipStreamSynchronize failed: %s", hipGetErrorString(es)); rc = DBGSOM_EHIP; }
-    return rc;
-}
-
-// The L1 search of the resident rows in front of the ordinary sums and smoothing of dbgsom_ctx_epoch.  The winners are
-// no seeds and the distances no bounds of a later Euclidean search: hint and bound are dropped.
-int dbgsom_ctx_epoch_manhattan(dbgsom_ctx *c, const double *W_host, int64_t M, double gamma, double sigma, int layout,
-                               double *W_new_host, double *change_total_host, double *errors_host,
-                               double *activations_host, int64_t *idx_host, double *dist_host) {
-    CTX_CHECK(c);
-    TRY(manhattan_ready(c, __func__));
-    DBGSOM_REQUIRE(W_host && W_new_host && change_total_host && errors_host && activations_host, "null pointer");
-    DBGSOM_REQUIRE(M >= 1 && sigma > 0.0, "bad arguments");
-    DBGSOM_REQUIRE(layout == DBGSOM_CENTRES_COMPACT || layout == DBGSOM_CENTRES_ALIGNED, "bad layout");
-    if (c->topoM != M) {
-        set_error("dbgsom_ctx_epoch_manhattan: topology holds %lld neurons, weights %lld (call "
-                  "dbgsom_ctx_set_topology after growth)", (long long)c->topoM, (long long)M);
-        return DBGSOM_ESTATE;
-    }
-    Samples &s = c->xs;
-    int rc = DBGSOM_OK;
-    do {
-        if ((rc = stage_weights(c, W_host, M, s.d, s.dp))) break;
-        if ((rc = c->idx[0].reserve((size_t)s.N * 8))) break;
-        if ((rc = c->idx[1].reserve((size_t)s.N * 8))) break;
-        if ((rc = c->dist.reserve((size_t)s.N * 8))) break;
-        int64_t *idx = c->idx[c->icur ^ 1].as<int64_t>();
-        c->last_filtered = false;
-        c->last_deferred = false;
-        c->hint_valid = false;
-        c->dist_bound_valid = false;
-        if ((rc = resident_bmu_manhattan(c, c->Wb[c->cur].as<double>(), s.dp, M, 1, idx, c->dist.as<double>()))) break;
-        c->icur ^= 1;
-        c->last_idx_valid = true;
-        if ((rc = accumulate_and_reduce(c, idx, nullptr, gamma, c->dist.as<double>(), M))) break;
-        rc = smooth_and_fetch(c, M, sigma, layout, 0, W_new_host, change_total_host, errors_host, activations_host, idx,
-                              idx_host, dist_host);
-    } while (0);
-    if (rc != DBGSOM_OK && rc != DBGSOM_ERANGE) (void)hipStreamSynchronize(c->stream);
-    return rc;
-}
-
 namespace {
 
-enum L1Op { L1_BMU, L1_DISTANCES, L1_KNEIGHBORS };
-
-// One Manhattan query in chunks of rows.  Rows from the host (q.on_device false): a chunk goes up into mk_x, its
-// result is staged (mk_idx / mk_dist, pd_out, kn_idx / kn_dist as for the masked calls) and comes down behind the
-// kernel.  Rows in HBM: the kernels read them where they are, q.ldx elements apart, and write the caller's device
-// arrays.  idx_out / dist_out: Nq x k (L1_DISTANCES: dist_out is the matrix, rows ldo apart).
-int manhattan_query(dbgsom_ctx *c, L1Op op, const QueryRows &q, int x_dtype, int64_t Nq, int64_t d, const double *W_host,
-                    int64_t M, int k, int64_t *idx_out, double *dist_out, int64_t ldo) {
-    const size_t es = dtype_size(x_dtype);
-    const int64_t chunk = op == L1_BMU ? std::min<int64_t>(Nq, c->masked_chunk_rows) : distances_chunk(c, Nq, M, d * 8);
-    const bool knn = op == L1_KNEIGHBORS;
-    DevBuf &ws = knn ? c->kn_ws : c->mk_ws;
-    DevBuf &si = knn ? c->kn_idx : c->mk_idx, &sd = op == L1_DISTANCES ? c->pd_out : (knn ? c->kn_dist : c->mk_dist);
-    const int64_t per_row = op == L1_DISTANCES ? M : k;   // values of a row's result
-    int rc = DBGSOM_OK;
-    do {
-        if ((rc = ws.reserve(knn ? kneighbors_manhattan_workspace_bytes(x_dtype, chunk, d, M, c->kneighbors_slab_rows)
-                                 : bmu_manhattan_workspace_bytes(x_dtype, chunk, d, M)))) break;
-        if ((rc = c->mk_w.reserve((size_t)M * d * 8))) break;
-        if (!q.on_device) {
-            if ((rc = c->mk_x.reserve((size_t)chunk * d * es))) break;
-            if (op != L1_DISTANCES && (rc = si.reserve((size_t)chunk * k * 8))) break;
-            if ((rc = sd.reserve((size_t)chunk * per_row * 8))) break;
-        }
-        hipError_t e = hipMemcpyAsync(c->mk_w.p, W_host, (size_t)M * d * 8, hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
-        if ((rc = launch_manhattan_weights(c->mk_w.as<double>(), M, d, d, ws.p, c->stream))) break;
-        for (int64_t r0 = 0; r0 < Nq && rc == DBGSOM_OK; r0 += chunk) {
-            const int64_t n = std::min(chunk, Nq - r0);
-            const void *X = static_cast<const char *>(q.p) + (size_t)r0 * q.ldx * es;
-            int64_t ldx = q.ldx, ld_res = op == L1_DISTANCES ? ldo : k;
-            int64_t *idx = idx_out ? idx_out + r0 * k : nullptr;
-            double *res = dist_out + r0 * ld_res;
-            if (!q.on_device) {
-                e = hipMemcpyAsync(c->mk_x.p, X, (size_t)n * d * es, hipMemcpyHostToDevice, c->stream);
-                if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
-                c->x_up((size_t)n * d * es);
-                X = c->mk_x.p; ldx = d;
-                idx = si.as<int64_t>(); res = sd.as<double>(); ld_res = per_row;
-            }
-            if (op == L1_BMU)
-                rc = launch_bmu_manhattan_rows(X, x_dtype, n, d, ldx, M, k, idx, res, ws.p, ws.cap, c->stream);
-            else if (op == L1_DISTANCES)
-                rc = launch_distances_manhattan_rows(X, x_dtype, n, d, ldx, M, res, ld_res, ws.p, ws.cap, c->stream);
-            else
-                rc = launch_kneighbors_manhattan_rows(X, x_dtype, n, d, ldx, M, k, c->kneighbors_slab_rows, idx, res, ws.p,
-                                                      ws.cap, c->stream);
-            if (rc || q.on_device) continue;
-            if (op != L1_DISTANCES) {
-                e = hipMemcpyAsync(idx_out + r0 * k, idx, (size_t)n * k * 8, hipMemcpyDeviceToHost, c->stream);
-                c->x_down((size_t)n * k * 8);
-            }
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(dist_out + r0 * per_row, res, (size_t)n * per_row * 8, hipMemcpyDeviceToHost, c->stream);
-            if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
-            c->x_down((size_t)n * per_row * 8);
-        }
-    } while (0);
-    const hipError_t es_ = hipStreamSynchronize(c->stream);
-    if (rc == DBGSOM_OK && es_ != hipSuccess) {
-        set_error("hipStreamSynchronize failed: %s", hipGetErrorString(es_));
-        rc = DBGSOM_EHIP;
-    }
-    // do not sit on a large one-off batch
-    if (c->mk_ws.cap + c->mk_x.cap > ((size_t)256 << 20)) { c->mk_ws.release(); c->mk_x.release(); c->mk_idx.release(); c->mk_dist.release(); }
-    if (c->pd_out.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->pd_out.release();
-    if (c->kn_ws.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->kn_ws.release();
-    return rc;
+// the search of the resident rows under W (device, M rows ldw apart; cosine: ldw is the rows' dp)
+int resident_bmu_metric(dbgsom_ctx *c, Metric metric, const double *W, int64_t ldw, int64_t M, int k, int64_t *idx,
+                        double *dist) {
+    if (metric == METRIC_MANHATTAN) return resident_bmu_manhattan(c, W, ldw, M, k, idx, dist);
+    return resident_bmu_cosine(c, W, M, k, idx, dist);
 }
 
-}  // namespace
-
-int dbgsom_ctx_bmu_query_manhattan(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
-                                   const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host) {
-    if (!c) { set_error("%s: null context", __func__); return DBGSOM_EINVAL; }
-    TRY(masked_check_shape(x_dtype, Nq, d, d, M, k));
-    if (Nq == 0) return DBGSOM_OK;
-    DBGSOM_REQUIRE(Xq_host && W_host && idx_host && dist_host, "null pointer");
-    CTX_CHECK(c);
-    return manhattan_query(c, L1_BMU, QueryRows{Xq_host, false, d}, x_dtype, Nq, d, W_host, M, k, idx_host, dist_host, 0);
-}
-
-int dbgsom_ctx_bmu_query_manhattan_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d, int64_t ldx,
-                                          const double *W_host, int64_t M, int k, int64_t *idx_dev, double *dist_dev) {
-    if (!c) { set_error("%s: null context", __func__); return DBGSOM_EINVAL; }
-    TRY(masked_check_shape(x_dtype, Nq, d, ldx, M, k));
-    if (Nq == 0) return DBGSOM_OK;
-    DBGSOM_REQUIRE(Xq_dev && W_host && idx_dev && dist_dev, "null pointer");
-    CTX_CHECK(c);
-    return manhattan_query(c, L1_BMU, QueryRows{Xq_dev, true, ldx}, x_dtype, Nq, d, W_host, M, k, idx_dev, dist_dev, 0);
-}
-
-int dbgsom_ctx_distances_query_manhattan(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
-                                         const double *W_host, int64_t M, double *out_host) {
-    TRY(distances_args(__func__, c, x_dtype, true, Nq, d, M));
-    TRY(masked_check_shape(x_dtype, Nq, d, d, M, 1));
-    if (Nq == 0) return DBGSOM_OK;
-    DBGSOM_REQUIRE(Xq_host && W_host && out_host, "null pointer");
-    CTX_CHECK(c);
-    return manhattan_query(c, L1_DISTANCES, QueryRows{Xq_host, false, d}, x_dtype, Nq, d, W_host, M, 1, nullptr, out_host, M);
-}
-
-int dbgsom_ctx_distances_query_manhattan_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d,
-                                                int64_t ldx, const double *W_host, int64_t M, double *out_dev, int64_t ldo) {
-    TRY(distances_args(__func__, c, x_dtype, true, Nq, d, M));
-    TRY(masked_check_shape(x_dtype, Nq, d, ldx, M, 1));
-    DBGSOM_REQUIRE(ldo >= M, "ldo must be >= M");
-    if (Nq == 0) return DBGSOM_OK;
-    DBGSOM_REQUIRE(Xq_dev && W_host && out_dev, "null pointer");
-    CTX_CHECK(c);
-    return manhattan_query(c, L1_DISTANCES, QueryRows{Xq_dev, true, ldx}, x_dtype, Nq, d, W_host, M, 1, nullptr, out_dev, ldo);
-}
-
-int dbgsom_ctx_kneighbors_query_manhattan(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
-                                          const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host) {
-    TRY(kneighbors_args(__func__, c, x_dtype, true, Nq, d, M, k));
-    TRY(masked_check_shape(x_dtype, Nq, d, d, M, 1));
-    if (Nq == 0) return DBGSOM_OK;
-    DBGSOM_REQUIRE(Xq_host && W_host && idx_host && dist_host, "null pointer");
-    CTX_CHECK(c);
-    return manhattan_query(c, L1_KNEIGHBORS, QueryRows{Xq_host, false, d}, x_dtype, Nq, d, W_host, M, k, idx_host, dist_host, 0);
-}
-
-int dbgsom_ctx_kneighbors_query_manhattan_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d,
-                                                 int64_t ldx, const double *W_host, int64_t M, int k, int64_t *idx_dev,
-                                                 double *dist_dev) {
-    TRY(kneighbors_args(__func__, c, x_dtype, true, Nq, d, M, k));
-    TRY(masked_check_shape(x_dtype, Nq, d, ldx, M, 1));
-    if (Nq == 0) return DBGSOM_OK;
-    DBGSOM_REQUIRE(Xq_dev && W_host && idx_dev && dist_dev, "null pointer");
-    CTX_CHECK(c);
-    return manhattan_query(c, L1_KNEIGHBORS, QueryRows{Xq_dev, true, ldx}, x_dtype, Nq, d, W_host, M, k, idx_dev, dist_dev, 0);
-}
-
-// ------------------------------------------------------------------------------------------
-// metric="cosine": the search of the resident rows and one epoch on it, and the queries (cosine.hip and the cosine
-// forms of the MFMA kernels)
-// ------------------------------------------------------------------------------------------
-int dbgsom_ctx_bmu_cosine(dbgsom_ctx *c, const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host) {
-    CTX_CHECK(c);
-    TRY(cosine_ready(c, __func__));
-    DBGSOM_REQUIRE(W_host && idx_host && dist_host && (k == 1 || k == 2), "bad arguments");
-    DBGSOM_REQUIRE(M >= k && M <= 0x7fffff00, "need k <= M < 2^31");
+// dbgsom_ctx_bmu_manhattan / dbgsom_ctx_bmu_cosine (`fn`).  The prototypes go up as each search reads them: M x d for
+// the Manhattan one, padded to the rows' dp for the cosine one.
+int metric_bmu(dbgsom_ctx *c, const char *fn, Metric metric, const double *W_host, int64_t M, int k, int64_t *idx_host,
+               double *dist_host) {
+    TRY(metric_ready(c, fn, metric));
+    REQUIRE_FN(fn, W_host && idx_host && dist_host && (k == 1 || k == 2), "bad arguments");
+    if (metric == METRIC_MANHATTAN) REQUIRE_FN(fn, M >= k, "need k <= M");
+    else REQUIRE_FN(fn, M >= k && M <= 0x7fffff00, "need k <= M < 2^31");
     Samples &s = c->xs;
+    const int64_t ldw = metric == METRIC_MANHATTAN ? s.d : s.dp;
     int rc = DBGSOM_OK;
     do {
-        if ((rc = c->mk_w.reserve((size_t)M * s.dp * 8))) break;
+        if ((rc = c->mk_w.reserve((size_t)M * ldw * 8))) break;
         if ((rc = c->qidx.reserve((size_t)s.N * k * 8))) break;
         if ((rc = c->qdist.reserve((size_t)s.N * k * 8))) break;
-        if ((rc = upload_padded(c, c->mk_w.p, W_host, M, s.d, s.dp, 8))) break;
-        if ((rc = resident_bmu_cosine(c, c->mk_w.as<double>(), M, k, c->qidx.as<int64_t>(), c->qdist.as<double>()))) break;
+        if ((rc = upload_padded(c, c->mk_w.p, W_host, M, s.d, ldw, 8))) break;
+        if ((rc = resident_bmu_metric(c, metric, c->mk_w.as<double>(), ldw, M, k, c->qidx.as<int64_t>(), c->qdist.as<double>())))
+            break;
         hipError_t e = hipMemcpyAsync(idx_host, c->qidx.p, (size_t)s.N * k * 8, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(dist_host, c->qdist.p, (size_t)s.N * k * 8, hipMemcpyDeviceToHost, c->stream);
         if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
@@ -2766,20 +2530,20 @@ int dbgsom_ctx_bmu_cosine(dbgsom_ctx *c, const double *W_host, int64_t M, int k,
     return rc;
 }
 
-// The cosine search of the resident rows in front of the ordinary sums and smoothing of dbgsom_ctx_epoch.  The winners
-// are no seeds and the distances no bounds of a later Euclidean search: hint and bound are dropped, and the search
-// policy is not consulted (there is no filtered form of this metric).
-int dbgsom_ctx_epoch_cosine(dbgsom_ctx *c, const double *W_host, int64_t M, double gamma, double sigma, int layout,
-                            double *W_new_host, double *change_total_host, double *errors_host,
-                            double *activations_host, int64_t *idx_host, double *dist_host) {
-    CTX_CHECK(c);
-    TRY(cosine_ready(c, __func__));
-    DBGSOM_REQUIRE(W_host && W_new_host && change_total_host && errors_host && activations_host, "null pointer");
-    DBGSOM_REQUIRE(M >= 1 && sigma > 0.0, "bad arguments");
-    DBGSOM_REQUIRE(layout == DBGSOM_CENTRES_COMPACT || layout == DBGSOM_CENTRES_ALIGNED, "bad layout");
+// dbgsom_ctx_epoch_manhattan / dbgsom_ctx_epoch_cosine (`fn`): the metric's search of the resident rows in front of the
+// ordinary sums and smoothing of dbgsom_ctx_epoch.  The winners are no seeds and the distances no bounds of a later
+// Euclidean search: hint and bound are dropped, and the search policy is not consulted (neither metric has a filtered
+// form).
+int metric_epoch(dbgsom_ctx *c, const char *fn, Metric metric, const double *W_host, int64_t M, double gamma, double sigma,
+                 int layout, double *W_new_host, double *change_total_host, double *errors_host, double *activations_host,
+                 int64_t *idx_host, double *dist_host) {
+    TRY(metric_ready(c, fn, metric));
+    REQUIRE_FN(fn, W_host && W_new_host && change_total_host && errors_host && activations_host, "null pointer");
+    REQUIRE_FN(fn, M >= 1 && sigma > 0.0, "bad arguments");
+    REQUIRE_FN(fn, layout == DBGSOM_CENTRES_COMPACT || layout == DBGSOM_CENTRES_ALIGNED, "bad layout");
     if (c->topoM != M) {
-        set_error("dbgsom_ctx_epoch_cosine: topology holds %lld neurons, weights %lld (call "
-                  "dbgsom_ctx_set_topology after growth)", (long long)c->topoM, (long long)M);
+        set_error("%s: topology holds %lld neurons, weights %lld (call dbgsom_ctx_set_topology after growth)", fn,
+                  (long long)c->topoM, (long long)M);
         return DBGSOM_ESTATE;
     }
     Samples &s = c->xs;
@@ -2794,7 +2558,7 @@ int dbgsom_ctx_epoch_cosine(dbgsom_ctx *c, const double *W_host, int64_t M, doub
         c->last_deferred = false;
         c->hint_valid = false;
         c->dist_bound_valid = false;
-        if ((rc = resident_bmu_cosine(c, c->Wb[c->cur].as<double>(), M, 1, idx, c->dist.as<double>()))) break;
+        if ((rc = resident_bmu_metric(c, metric, c->Wb[c->cur].as<double>(), s.dp, M, 1, idx, c->dist.as<double>()))) break;
         c->icur ^= 1;
         c->last_idx_valid = true;
         if ((rc = accumulate_and_reduce(c, idx, nullptr, gamma, c->dist.as<double>(), M))) break;
@@ -2805,152 +2569,111 @@ int dbgsom_ctx_epoch_cosine(dbgsom_ctx *c, const double *W_host, int64_t M, doub
     return rc;
 }
 
-namespace {
+}  // namespace
 
-enum CosOp { COS_BMU, COS_DISTANCES, COS_KNEIGHBORS };
-
-// One cosine query in chunks of rows.  Rows from the host (q.on_device false): a chunk goes up into mk_x, its result
-// is staged (mk_idx / mk_dist, pd_out, kn_idx / kn_dist as for the Manhattan calls) and comes down behind the kernel.
-// Rows in HBM: the kernels read them where they are, q.ldx elements apart (no padded copy: the register-staged form
-// takes any row pitch), and write the caller's device arrays.  Squared norms and their inverses are made per chunk
-// (rows) and per call (prototypes) in query-sized scratch.  idx_out / dist_out: Nq x k (COS_DISTANCES: dist_out is the
-// matrix, rows ldo apart).
-int cosine_query(dbgsom_ctx *c, CosOp op, const QueryRows &q, int x_dtype, int64_t Nq, int64_t d, const double *W_host,
-                 int64_t M, int k, int64_t *idx_out, double *dist_out, int64_t ldo) {
-    const size_t es = dtype_size(x_dtype);
-    const int64_t chunk = op == COS_BMU ? std::min<int64_t>(Nq, c->masked_chunk_rows) : distances_chunk(c, Nq, M, d * 8);
-    const bool knn = op == COS_KNEIGHBORS;
-    DevBuf &si = knn ? c->kn_idx : c->mk_idx, &sd = op == COS_DISTANCES ? c->pd_out : (knn ? c->kn_dist : c->mk_dist);
-    const int64_t per_row = op == COS_DISTANCES ? M : k;   // values of a row's result
-    DevBuf vq, uq;   // [squared norms | their inverses] of the prototypes and of one chunk of rows
-    int rc = DBGSOM_OK;
-    do {
-        if (knn && (rc = c->kn_ws.reserve(kneighbors_workspace_bytes(chunk, M, c->kneighbors_slab_rows)))) break;
-        if ((rc = c->mk_w.reserve((size_t)M * d * 8))) break;
-        if ((rc = vq.reserve((size_t)M * 16))) break;
-        if ((rc = uq.reserve((size_t)chunk * 16))) break;
-        if (!q.on_device) {
-            if ((rc = c->mk_x.reserve((size_t)chunk * d * es))) break;
-            if (op != COS_DISTANCES && (rc = si.reserve((size_t)chunk * k * 8))) break;
-            if ((rc = sd.reserve((size_t)chunk * per_row * 8))) break;
-        }
-        hipError_t e = hipMemcpyAsync(c->mk_w.p, W_host, (size_t)M * d * 8, hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
-        const double *W = c->mk_w.as<double>(), *v = vq.as<double>() + M;
-        double *u = uq.as<double>() + chunk;
-        if ((rc = launch_row_sqnorms(W, DBGSOM_F64, M, d, d, vq.as<double>(), c->stream))) break;
-        if ((rc = launch_inv_norms(vq.as<double>(), M, vq.as<double>() + M, c->stream))) break;
-        for (int64_t r0 = 0; r0 < Nq && rc == DBGSOM_OK; r0 += chunk) {
-            const int64_t n = std::min(chunk, Nq - r0);
-            const void *X = static_cast<const char *>(q.p) + (size_t)r0 * q.ldx * es;
-            int64_t ldx = q.ldx, ld_res = op == COS_DISTANCES ? ldo : k;
-            int64_t *idx = idx_out ? idx_out + r0 * k : nullptr;
-            double *res = dist_out + r0 * ld_res;
-            if (!q.on_device) {
-                e = hipMemcpyAsync(c->mk_x.p, X, (size_t)n * d * es, hipMemcpyHostToDevice, c->stream);
-                if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
-                c->x_up((size_t)n * d * es);
-                X = c->mk_x.p; ldx = d;
-                idx = si.as<int64_t>(); res = sd.as<double>(); ld_res = per_row;
-            }
-            if ((rc = launch_row_sqnorms(X, x_dtype, n, d, ldx, uq.as<double>(), c->stream))) break;
-            if ((rc = launch_inv_norms(uq.as<double>(), n, u, c->stream))) break;
-            if (op == COS_BMU)
-                rc = launch_bmu_cosine(X, x_dtype, n, d, ldx, u, W, M, v, k, idx, res, c->stream);
-            else if (op == COS_DISTANCES)
-                rc = launch_distances_cosine(X, x_dtype, n, d, ldx, u, W, M, v, res, ld_res, c->stream);
-            else
-                rc = launch_kneighbors_cosine(X, x_dtype, n, d, ldx, u, W, M, v, k, c->kneighbors_slab_rows, idx, res,
-                                              c->kn_ws.p, c->kn_ws.cap, c->stream);
-            if (rc || q.on_device) continue;
-            if (op != COS_DISTANCES) {
-                e = hipMemcpyAsync(idx_out + r0 * k, idx, (size_t)n * k * 8, hipMemcpyDeviceToHost, c->stream);
-                c->x_down((size_t)n * k * 8);
-            }
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(dist_out + r0 * per_row, res, (size_t)n * per_row * 8, hipMemcpyDeviceToHost, c->stream);
-            if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
-            c->x_down((size_t)n * per_row * 8);
-        }
-    } while (0);
-    const hipError_t es_ = hipStreamSynchronize(c->stream);
-    if (rc == DBGSOM_OK && es_ != hipSuccess) {
-        set_error("hipStreamSynchronize failed: %s", hipGetErrorString(es_));
-        rc = DBGSOM_EHIP;
-    }
-    vq.release(); uq.release();
-    // do not sit on a large one-off batch
-    if (c->mk_x.cap > ((size_t)256 << 20)) { c->mk_x.release(); c->mk_idx.release(); c->mk_dist.release(); }
-    if (c->pd_out.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->pd_out.release();
-    if (c->kn_ws.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->kn_ws.release();
-    return rc;
+int dbgsom_ctx_bmu_manhattan(dbgsom_ctx *c, const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host) {
+    CTX_CHECK(c);
+    return metric_bmu(c, __func__, METRIC_MANHATTAN, W_host, M, k, idx_host, dist_host);
 }
 
-}  // namespace
+int dbgsom_ctx_bmu_cosine(dbgsom_ctx *c, const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host) {
+    CTX_CHECK(c);
+    return metric_bmu(c, __func__, METRIC_COSINE, W_host, M, k, idx_host, dist_host);
+}
+
+int dbgsom_ctx_epoch_manhattan(dbgsom_ctx *c, const double *W_host, int64_t M, double gamma, double sigma, int layout,
+                               double *W_new_host, double *change_total_host, double *errors_host,
+                               double *activations_host, int64_t *idx_host, double *dist_host) {
+    CTX_CHECK(c);
+    return metric_epoch(c, __func__, METRIC_MANHATTAN, W_host, M, gamma, sigma, layout, W_new_host, change_total_host,
+                        errors_host, activations_host, idx_host, dist_host);
+}
+
+int dbgsom_ctx_epoch_cosine(dbgsom_ctx *c, const double *W_host, int64_t M, double gamma, double sigma, int layout,
+                            double *W_new_host, double *change_total_host, double *errors_host,
+                            double *activations_host, int64_t *idx_host, double *dist_host) {
+    CTX_CHECK(c);
+    return metric_epoch(c, __func__, METRIC_COSINE, W_host, M, gamma, sigma, layout, W_new_host, change_total_host,
+                        errors_host, activations_host, idx_host, dist_host);
+}
+
+// the queries of both metrics: host rows, and rows in HBM (*_device: ldx elements apart, results in device arrays)
+int dbgsom_ctx_bmu_query_manhattan(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                   const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host) {
+    return raw_bmu_checked(__func__, c, ROWS_MANHATTAN, QueryRows{Xq_host, false, d}, x_dtype, Nq, d, W_host, M, k,
+                           idx_host, dist_host, nullptr);
+}
+
+int dbgsom_ctx_bmu_query_manhattan_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d, int64_t ldx,
+                                          const double *W_host, int64_t M, int k, int64_t *idx_dev, double *dist_dev) {
+    return raw_bmu_checked(__func__, c, ROWS_MANHATTAN, QueryRows{Xq_dev, true, ldx}, x_dtype, Nq, d, W_host, M, k, idx_dev,
+                           dist_dev, nullptr);
+}
+
+int dbgsom_ctx_distances_query_manhattan(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                         const double *W_host, int64_t M, double *out_host) {
+    return raw_rows_checked(__func__, c, Q_DISTANCES, ROWS_MANHATTAN, QueryRows{Xq_host, false, d}, x_dtype, Nq, d, W_host,
+                            M, 1, nullptr, out_host, M);
+}
+
+int dbgsom_ctx_distances_query_manhattan_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d,
+                                                int64_t ldx, const double *W_host, int64_t M, double *out_dev, int64_t ldo) {
+    return raw_rows_checked(__func__, c, Q_DISTANCES, ROWS_MANHATTAN, QueryRows{Xq_dev, true, ldx}, x_dtype, Nq, d, W_host,
+                            M, 1, nullptr, out_dev, ldo);
+}
+
+int dbgsom_ctx_kneighbors_query_manhattan(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                          const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host) {
+    return raw_rows_checked(__func__, c, Q_KNEIGHBORS, ROWS_MANHATTAN, QueryRows{Xq_host, false, d}, x_dtype, Nq, d, W_host,
+                            M, k, idx_host, dist_host, 0);
+}
+
+int dbgsom_ctx_kneighbors_query_manhattan_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d,
+                                                 int64_t ldx, const double *W_host, int64_t M, int k, int64_t *idx_dev,
+                                                 double *dist_dev) {
+    return raw_rows_checked(__func__, c, Q_KNEIGHBORS, ROWS_MANHATTAN, QueryRows{Xq_dev, true, ldx}, x_dtype, Nq, d, W_host,
+                            M, k, idx_dev, dist_dev, 0);
+}
 
 int dbgsom_ctx_bmu_query_cosine(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
                                 const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host) {
-    if (!c) { set_error("%s: null context", __func__); return DBGSOM_EINVAL; }
-    TRY(masked_check_shape(x_dtype, Nq, d, d, M, k));
-    if (Nq == 0) return DBGSOM_OK;
-    DBGSOM_REQUIRE(Xq_host && W_host && idx_host && dist_host, "null pointer");
-    CTX_CHECK(c);
-    return cosine_query(c, COS_BMU, QueryRows{Xq_host, false, d}, x_dtype, Nq, d, W_host, M, k, idx_host, dist_host, 0);
+    return raw_bmu_checked(__func__, c, ROWS_COSINE, QueryRows{Xq_host, false, d}, x_dtype, Nq, d, W_host, M, k, idx_host,
+                           dist_host, nullptr);
 }
 
 int dbgsom_ctx_bmu_query_cosine_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d, int64_t ldx,
                                        const double *W_host, int64_t M, int k, int64_t *idx_dev, double *dist_dev) {
-    if (!c) { set_error("%s: null context", __func__); return DBGSOM_EINVAL; }
-    TRY(masked_check_shape(x_dtype, Nq, d, ldx, M, k));
-    if (Nq == 0) return DBGSOM_OK;
-    DBGSOM_REQUIRE(Xq_dev && W_host && idx_dev && dist_dev, "null pointer");
-    CTX_CHECK(c);
-    return cosine_query(c, COS_BMU, QueryRows{Xq_dev, true, ldx}, x_dtype, Nq, d, W_host, M, k, idx_dev, dist_dev, 0);
+    return raw_bmu_checked(__func__, c, ROWS_COSINE, QueryRows{Xq_dev, true, ldx}, x_dtype, Nq, d, W_host, M, k, idx_dev,
+                           dist_dev, nullptr);
 }
 
 int dbgsom_ctx_distances_query_cosine(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
                                       const double *W_host, int64_t M, double *out_host) {
-    TRY(distances_args(__func__, c, x_dtype, true, Nq, d, M));
-    TRY(masked_check_shape(x_dtype, Nq, d, d, M, 1));
-    if (Nq == 0) return DBGSOM_OK;
-    DBGSOM_REQUIRE(Xq_host && W_host && out_host, "null pointer");
-    CTX_CHECK(c);
-    return cosine_query(c, COS_DISTANCES, QueryRows{Xq_host, false, d}, x_dtype, Nq, d, W_host, M, 1, nullptr, out_host, M);
+    return raw_rows_checked(__func__, c, Q_DISTANCES, ROWS_COSINE, QueryRows{Xq_host, false, d}, x_dtype, Nq, d, W_host, M,
+                            1, nullptr, out_host, M);
 }
 
 int dbgsom_ctx_distances_query_cosine_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d,
                                              int64_t ldx, const double *W_host, int64_t M, double *out_dev, int64_t ldo) {
-    TRY(distances_args(__func__, c, x_dtype, true, Nq, d, M));
-    TRY(masked_check_shape(x_dtype, Nq, d, ldx, M, 1));
-    DBGSOM_REQUIRE(ldo >= M, "ldo must be >= M");
-    if (Nq == 0) return DBGSOM_OK;
-    DBGSOM_REQUIRE(Xq_dev && W_host && out_dev, "null pointer");
-    CTX_CHECK(c);
-    return cosine_query(c, COS_DISTANCES, QueryRows{Xq_dev, true, ldx}, x_dtype, Nq, d, W_host, M, 1, nullptr, out_dev, ldo);
+    return raw_rows_checked(__func__, c, Q_DISTANCES, ROWS_COSINE, QueryRows{Xq_dev, true, ldx}, x_dtype, Nq, d, W_host, M,
+                            1, nullptr, out_dev, ldo);
 }
 
 int dbgsom_ctx_kneighbors_query_cosine(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
                                        const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host) {
-    TRY(kneighbors_args(__func__, c, x_dtype, true, Nq, d, M, k));
-    TRY(masked_check_shape(x_dtype, Nq, d, d, M, 1));
-    if (Nq == 0) return DBGSOM_OK;
-    DBGSOM_REQUIRE(Xq_host && W_host && idx_host && dist_host, "null pointer");
-    CTX_CHECK(c);
-    return cosine_query(c, COS_KNEIGHBORS, QueryRows{Xq_host, false, d}, x_dtype, Nq, d, W_host, M, k, idx_host, dist_host, 0);
+    return raw_rows_checked(__func__, c, Q_KNEIGHBORS, ROWS_COSINE, QueryRows{Xq_host, false, d}, x_dtype, Nq, d, W_host, M,
+                            k, idx_host, dist_host, 0);
 }
 
 int dbgsom_ctx_kneighbors_query_cosine_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d,
                                               int64_t ldx, const double *W_host, int64_t M, int k, int64_t *idx_dev,
                                               double *dist_dev) {
-    TRY(kneighbors_args(__func__, c, x_dtype, true, Nq, d, M, k));
-    TRY(masked_check_shape(x_dtype, Nq, d, ldx, M, 1));
-    if (Nq == 0) return DBGSOM_OK;
-    DBGSOM_REQUIRE(Xq_dev && W_host && idx_dev && dist_dev, "null pointer");
-    CTX_CHECK(c);
-    return cosine_query(c, COS_KNEIGHBORS, QueryRows{Xq_dev, true, ldx}, x_dtype, Nq, d, W_host, M, k, idx_dev, dist_dev, 0);
+    return raw_rows_checked(__func__, c, Q_KNEIGHBORS, ROWS_COSINE, QueryRows{Xq_dev, true, ldx}, x_dtype, Nq, d, W_host, M,
+                            k, idx_dev, dist_dev, 0);
 }
 
 int dbgsom_ctx_exp_similarity(dbgsom_ctx *c, const double *dist_host, int64_t n, double gamma, double *kw_host) {
+
     CTX_CHECK(c);
     DBGSOM_REQUIRE(n >= 0 && (n == 0 || (dist_host && kw_host)), "bad arguments");
     if (n == 0) return DBGSOM_OK;
