@@ -64,6 +64,13 @@ SIGNATURES = {
     "dbgsom_bmu_filtered_anchored": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _ci, _vp, _vp,
                                            _ci, _ci, _ci, _vp, _vp, _vp, _sz, _vp]),
     "dbgsom_bmu_filtered_anchor_seeds": (_ci, [_vp, _i64, _i64, _i64, _ci, _vp, _vp, _vp]),
+    "dbgsom_anchor_runs_bytes": (_sz, [_i64, _ci]),
+    "dbgsom_anchor_runs_build": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _vp, _ci, _vp, _vp, _vp, _sz, _vp]),
+    "dbgsom_anchor_runs_read": (_ci, [_vp, _i64, _ci, _vp, _vp, _vp, _vp, _vp]),
+    "dbgsom_bmu_filtered_anchor_runs": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _ci, _vp, _vp,
+                                              _vp, _ci, _ci, _ci, _vp, _vp, _vp, _sz, _vp]),
+    "dbgsom_bmu_filtered_anchor_bounds": (_ci, [_vp, _i64, _i64, _i64, _ci, _vp, _vp, _vp, _vp]),
+    "dbgsom_bmu_filtered_lists": (_ci, [_vp, _i64, _i64, _i64, _vp, _vp]),
     "dbgsom_filter_timing": (_ci, [_ci]),
     "dbgsom_bmu_filtered_stage_ms": (_ci, [_vp]),
     "dbgsom_sum_workspace_bytes": (_sz, []),
@@ -203,6 +210,7 @@ SIGNATURES = {
     "dbgsom_ctx_arm_ms": (_ci, [_vp, _vp]),
     "dbgsom_ctx_filter_counts": (_ci, [_vp, _vp, _i64]),
     "dbgsom_ctx_read_anchors": (_ci, [_vp, ctypes.POINTER(_i64), _vp, _vp, _vp, _vp]),
+    "dbgsom_ctx_read_anchor_runs": (_ci, [_vp, ctypes.POINTER(_i64), _vp, _vp, _vp, _vp]),
     "dbgsom_ctx_refine_counts": (_ci, [_vp, _vp]),
     "dbgsom_ctx_phase_ms": (_ci, [_vp, _vp]),
 }

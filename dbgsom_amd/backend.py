@@ -1417,6 +1417,20 @@ class HipBackend(HotPathBackend):
                    out["order"].ctypes.data, out["aseed"].ctypes.data if aseed else None)
         return out
 
+    def read_anchor_runs(self):
+        """The run table of the anchor buckets (`anchor_state` 1): dict of `run_start` (one int32 per 128-row workgroup
+        of `order`, plus one) and per run `anchor`, `R` (>= the largest distance from a row of the run to its anchor) and
+        `xx_max` (the largest squared norm of the run's rows)."""
+        g = ctypes.c_int64(0)
+        self._call("dbgsom_ctx_read_anchor_runs", self._ctx, ctypes.byref(g), None, None, None, None)
+        cap = g.value + 256
+        start = np.empty(g.value + 1, dtype=np.int32)
+        anchor, R, xx = np.full(cap, -1, dtype=np.int32), np.full(cap, np.nan), np.full(cap, np.nan)
+        self._call("dbgsom_ctx_read_anchor_runs", self._ctx, None, start.ctypes.data, anchor.ctypes.data, R.ctypes.data,
+                   xx.ctypes.data)
+        n = int(start[-1])
+        return {"run_start": start, "anchor": anchor[:n], "R": R[:n], "xx_max": xx[:n]}
+
     def refine_counts(self):
         """[(sample, prototype) pairs evaluated exactly, 128-sample workgroups refined, samples whose
         candidates overflowed the four slots] of the last filtered search."""

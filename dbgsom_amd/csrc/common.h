@@ -342,6 +342,9 @@ struct FilteredCall {
     const double *anchors = nullptr;
     const int32_t *anchor_of = nullptr;
     int n_anchors = 0;
+    // ... and the run table of those buckets (launch_anchor_runs, filter.hip 2f; a function of the samples alone as
+    // well): the candidate lists then come from the anchors' distances, without a pass over the samples' plane
+    const void *anchor_runs = nullptr;
     // Only the seed pre-pass and the bucket sort (how the anchor buckets are built: W = the anchors): the arg-min
     // of the pre-pass goes to seeds_out, the bucket order to order_out (N int32 each); idx / dist are not written
     int32_t *seeds_out = nullptr, *order_out = nullptr;
@@ -350,6 +353,11 @@ struct FilteredCall {
 };
 constexpr int DBGSOM_LISTS_LONG = 1000;   // (internal status of launch_bmu_filtered, never crosses the ABI)
 int launch_bmu_filtered(const FilteredCall &call);
+// the run table of anchor buckets (filter.hip 2f): per 128-sample workgroup of `order` its runs of equal anchor
+size_t anchor_runs_bytes(int64_t N, int n_anchors);
+int launch_anchor_runs(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx,
+                       const double *anchors, int n_anchors, const int32_t *anchor_of, const int32_t *order, void *runs,
+                       size_t runs_bytes, hipStream_t s);
 size_t smooth_workspace_bytes(int64_t M, int64_t d);
 int launch_smooth(const double *sums, int64_t M, int64_t d, const float *hop, double sigma,
                   int layout, const double *W_old, double *W_new, double *change_total, void *ws,

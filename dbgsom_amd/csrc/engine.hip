@@ -225,11 +225,12 @@ struct Samples {  // one resident sample set (training samples, or a query batch
     // planes are: n_anchors rows of X as float64 with their norms behind them, the anchor every row was grouped
     // with and the rows bucketed by it.  A function of X alone.  anchor_state: 0 none, 1 in use, 2 dropped (their
     // lists came out longer than the pre-pass's: the pre-pass seeds this sample set again)
-    DevBuf anchors, anchor_of, anchor_order;
+    // anchor_runs: the run table of the bucket order (filter.hip 2f), built and dropped with the buckets
+    DevBuf anchors, anchor_of, anchor_order, anchor_runs;
     int64_t n_anchors = 0;
     int anchor_state = 0;
     void drop_anchors(int state) {
-        anchors.release(); anchor_of.release(); anchor_order.release();
+        anchors.release(); anchor_of.release(); anchor_order.release(); anchor_runs.release();
         n_anchors = 0; anchor_state = state;
     }
     void drop_planes() { planes_ready = false; drop_anchors(0); }
@@ -575,6 +576,11 @@ int ensure_anchors(dbgsom_ctx *c, Samples &s) {
         call.ws = c->filt_ws.p; call.ws_bytes = c->filt_ws.cap; call.stream = c->stream;
         TRY(launch_bmu_filtered(call));
     }
+    // the run table of the bucket order: what the candidate lists need of the samples, once per load (the stored
+    // rows: the values the search reads, at the storage's width)
+    TRY(s.anchor_runs.reserve(anchor_runs_bytes(s.N, (int)A)));
+    TRY(launch_anchor_runs(s.X, s.dtype, s.N, dp, dp, s.xx.as<double>(), anchors, (int)A, s.anchor_of.as<int32_t>(),
+                           s.anchor_order.as<int32_t>(), s.anchor_runs.p, s.anchor_runs.cap, c->stream));
     s.n_anchors = A;
     s.anchor_state = 1;
     ++c->anchor_builds;
@@ -646,6 +652,7 @@ int run_filtered(dbgsom_ctx *c, Samples &s, DevBuf &ws, const double *W, int64_t
         ++c->anchor_searches;
         call.anchors = s.anchors.as<double>(); call.n_anchors = (int)s.n_anchors;
         call.anchor_of = s.anchor_of.as<int32_t>(); call.order = s.anchor_order.as<int32_t>();
+        call.anchor_runs = s.anchor_runs.p;
         c->last_anchor_seeded = true;
     }
     call.round_f32 = round_f32; call.idx = idx; call.dist = dist; call.ws = ws.p; call.ws_bytes = ws.cap;
@@ -1380,7 +1387,7 @@ int dbgsom_ctx_get_option(dbgsom_ctx *c, const char *name, int64_t *v) {
         size_t tot = 0;
         for (const Samples *q : {&c->xs, &c->xq})
             tot += q->own.cap + q->x32.cap + q->xx.cap + q->planes.cap + q->indptr.cap + q->indices.cap + q->data.cap +
-                   q->anchors.cap + q->anchor_of.cap + q->anchor_order.cap;
+                   q->anchors.cap + q->anchor_of.cap + q->anchor_order.cap + q->anchor_runs.cap;
         DevBuf *bufs[] = CTX_DEVBUFS(c);
         for (DevBuf *b : bufs) tot += b->cap;
         *v = (int64_t)tot;
@@ -1407,7 +1414,7 @@ static void set_tight(dbgsom_ctx *c, bool tight) {
     for (DevBuf *b : bufs) b->tight = tight;
     for (Samples *q : {&c->xs, &c->xq})
         for (DevBuf *b : {&q->own, &q->x32, &q->xx, &q->planes, &q->indptr, &q->indices, &q->data, &q->anchors, &q->anchor_of,
-                          &q->anchor_order})
+                          &q->anchor_order, &q->anchor_runs})
             b->tight = tight;
 }
 
@@ -3177,6 +3184,19 @@ int dbgsom_ctx_read_anchors(dbgsom_ctx *c, int64_t *n_anchors, double *anchors_h
         return dbgsom_bmu_filtered_anchor_seeds(c->last_filter_ws, c->last_filter_N, c->last_filter_d, c->last_filter_M, (int)A,
                                                 aseed_host, nullptr, c->stream);
     return sync(c);
+}
+
+int dbgsom_ctx_read_anchor_runs(dbgsom_ctx *c, int64_t *n_groups, int32_t *run_start_host, int32_t *run_anchor_host,
+                                double *run_R_host, double *run_xx_host) {
+    CTX_CHECK(c);
+    TRY(loaded(c, __func__));
+    TRY(complete_rows(c, __func__));
+    Samples &s = c->xs;
+    if (s.anchor_state != 1) { set_error("dbgsom_ctx_read_anchor_runs: the resident samples have no anchor buckets"); return DBGSOM_ESTATE; }
+    if (n_groups) *n_groups = (s.N + 127) / 128;
+    if (!run_start_host) return DBGSOM_OK;
+    return dbgsom_anchor_runs_read(s.anchor_runs.p, s.N, (int)s.n_anchors, run_start_host, run_anchor_host, run_R_host,
+                                   run_xx_host, c->stream);
 }
 
 int dbgsom_ctx_phase_ms(dbgsom_ctx *c, double *ms8) {

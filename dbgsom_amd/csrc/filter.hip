@@ -34,7 +34,8 @@ constexpr int FNT = 512;          // threads per sweep workgroup (8 wavefronts)
 constexpr int FSTAGES = 3;
 constexpr int SCHED_BINS = 16;     // launch-order bins of the exact stage (section 2b)
 constexpr int SCHED_RETRY = 2 * SCHED_BINS + 10;  // u64: workgroups of the pruning form whose lists came out long (re-seeded, 2c)
-constexpr int SCHED_CTR = 2 * SCHED_BINS + 12;  // bin counts | cursors | [start, n] of classes 3, 2, 1 | sum of list lengths (u64) | the same of a counting-only pruning launch (u64)
+constexpr int SCHED_HANDED = 2 * SCHED_BINS + 12;  // u64: workgroups anchor_mark_kernel handed to the per-sample pass (2f)
+constexpr int SCHED_CTR = 2 * SCHED_BINS + 14;  // bin counts | cursors | [start, n] of classes 3, 2, 1 | sum of list lengths (u64) | the same of a counting-only pruning launch (u64) | long lists (u64) | handed over (u64)
 constexpr int SCHED_SUM = 2 * SCHED_BINS + 6;  // (8-byte aligned: the counters sit on a 256-byte boundary)
 constexpr int RF_CTR = 4;  // u64 counters of the refinement (2d): pairs | refined workgroups | left to the MFMA stage | -
 static_assert(SCHED_CTR % 2 == 0, "the 64-bit counters of the refinement sit behind the schedule's");
@@ -1618,7 +1619,8 @@ __global__ __launch_bounds__(256, 6) void prune_mark_kernel(
     uint16_t *__restrict__ ulist, int ulist_stride, uint32_t *__restrict__ ucount, uint32_t *__restrict__ sched_ctr,
     unsigned long long *__restrict__ sum_out, int count_only, const double *__restrict__ dist_prev,
     const double *__restrict__ shift, int32_t *__restrict__ retry_groups, unsigned long long *__restrict__ retry_len,
-    int retry_mode, uint32_t retry_above, const uint32_t *__restrict__ nnub) {
+    int retry_mode, uint32_t retry_above, const uint32_t *__restrict__ nnub, const int32_t *__restrict__ work_groups,
+    const unsigned long long *__restrict__ work_len) {
     // nnub != nullptr: the lists of a k = 2 search.  With p2 the seed's nearest other prototype, |x - w_p2| <=
     // |x - w_p| + nnub[p]: TWO prototypes are at most that far, so everything at least m further cannot be
     // among the two nearest -- the bound of k = 1 with nnub[p] added to twice the seed distance.
@@ -1626,7 +1628,9 @@ __global__ __launch_bounds__(256, 6) void prune_mark_kernel(
     // to retry_groups (its samples' seeds were poor: a cluster none of whose prototypes is in the cheap
     // pre-pass's subset sends its samples to seeds in OTHER clusters, and twice that distance rules
     // nothing out); the launcher re-seeds those workgroups against every prototype and calls again with
-    // retry_mode 2: the listed workgroups only, final whatever comes out.
+    // retry_mode 2: final whatever comes out.
+    // work_len != nullptr: only the *work_len workgroups listed in work_groups (the re-seeded ones; or the ones
+    // anchor_mark_kernel left to this pass, 2f) -- the other blocks of the grid return at once.
     __shared__ int prev_s[128], run_p[128];
     __shared__ int64_t samp_s[128];
     __shared__ unsigned long long bound_s[128], run_t[128];  // non-negative doubles by their bit patterns
@@ -1634,9 +1638,9 @@ __global__ __launch_bounds__(256, 6) void prune_mark_kernel(
     __shared__ int misc[2];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int64_t group = blockIdx.x;
-    if (retry_mode == 2) {
-        if ((unsigned long long)blockIdx.x >= *retry_len) return;
-        group = retry_groups[blockIdx.x];
+    if (work_len) {
+        if ((unsigned long long)blockIdx.x >= *work_len) return;
+        group = work_groups[blockIdx.x];
     }
     const int64_t p0 = group * 128;
     const int nwords = (M + 31) / 32;
@@ -1868,11 +1872,24 @@ constexpr int ANCHOR_TICKET0 = 16;   // FilterWs::tickets[16 .. 32): one per blo
 
 __device__ __forceinline__ bool seed_less(double v, int j, double bv, int bj) { return v < bv || (v == bv && j < bj); }
 
+// What |a|^2 + (|w_j|^2 - 2 a . w_j) as this kernel forms it can be off the real |a - w_j|^2 by, generously: the two
+// norms and the product are sums of d terms ((d + 2) u relative to |a|^2, |w|^2 and |a||w| <= (|a|^2 + |w|^2) / 2 each),
+// the two additions add 3 u (|a|^2 + |w|^2): (2 d + 8) u (|a|^2 + |w|^2) in all, under half of the rho of section 2c
+// with the anchor in the sample's place.
+__device__ __forceinline__ double anchor_rho(int d, double aa, double yy_max) {
+    return 4.0 * (double)(d + 16) * 1.1102230246251565e-16 * (aa + yy_max);
+}
+
 __global__ __launch_bounds__(256) void anchor_seed_kernel(const double *__restrict__ anchors, int A,
                                                           const double *__restrict__ W, int M, int d,
                                                           const double *__restrict__ ww, double *__restrict__ part_val,
                                                           int32_t *__restrict__ part_idx, uint32_t *__restrict__ tickets,
-                                                          int32_t *__restrict__ aseed) {
+                                                          int32_t *__restrict__ aseed, const double *__restrict__ anorm,
+                                                          const double *__restrict__ summary, float *__restrict__ alow,
+                                                          int ldl, double *__restrict__ aup) {
+    // alow != nullptr (the call brings the anchors' run table, 2f): the values the arg-min is taken over are kept as
+    // certified bounds -- alow[a ldl + j] <= |a - w_j|^2 (float32, rounded down; 0 = no bound known) and aup[a] >=
+    // |a - w_seed(a)|.  anorm[a] = |a|^2 (float64), summary[2] = max |w|^2.
     __shared__ double val_s[4][16];
     __shared__ int idx_s[4][16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
@@ -1891,6 +1908,8 @@ __global__ __launch_bounds__(256) void anchor_seed_kernel(const double *__restri
     // element u of lane l: prototype jb + 4 u + (l >> 4), anchor ab + (l & 15)
     double bv = INFINITY;
     int bj = 0x7fffffff;
+    const bool keep = alow != nullptr && ab + r < A;
+    const double aa = keep ? anorm[ab + r] : 0.0, rho_a = keep ? anchor_rho(d, aa, summary[2]) : 0.0;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const int j = jb + 4 * u + q;
@@ -1898,6 +1917,12 @@ __global__ __launch_bounds__(256) void anchor_seed_kernel(const double *__restri
         const double y = ww[j], v = y - 2.0 * c[u];
         const double key = fabs(y) < INFINITY ? (fabs(v) < INFINITY ? v : 1.7976931348623157e308) : INFINITY;
         if (seed_less(key, j, bv, bj)) { bv = key; bj = j; }
+        if (keep) {
+            // (anything that is not a positive finite number -- a row or an anchor with a NaN or an infinity among
+            //  them: no bound known, and the comparison in anchor_mark_kernel keeps j)
+            const double lo2 = ((aa + v) - rho_a) * (1.0 - 1e-12);
+            alow[(size_t)(ab + r) * ldl + j] = (lo2 > 0.0 && lo2 < 3.0e38) ? __double2float_rz(lo2) : 0.f;
+        }
     }
 #pragma unroll
     for (int off = 16; off < 64; off <<= 1) {
@@ -1931,7 +1956,14 @@ __global__ __launch_bounds__(256) void anchor_seed_kernel(const double *__restri
         const int oj = __shfl_xor(bj, off, 64);
         if (seed_less(ov, oj, bv, bj)) { bv = ov; bj = oj; }
     }
-    if (sub == 0 && a < A) aseed[a] = bj;   // (every block holds a prototype below M: bj is one)
+    if (sub == 0 && a < A) {
+        aseed[a] = bj;   // (every block holds a prototype below M: bj is one)
+        if (aup) {       // (bv is the seed's value, or DBL_MAX / +inf when no finite value exists: then no bound)
+            const double an = anorm[a], up2 = ((an + bv) + anchor_rho(d, an, summary[2])) * (1.0 + 1e-12);
+            const double up = up2 > 0.0 ? sqrt(up2) * (1.0 + 1e-12) : 0.0;
+            aup[a] = (up2 == up2 && up < INFINITY) ? up : INFINITY;
+        }
+    }
 }
 
 // seed[i] = the seed of the anchor sample i was grouped with
@@ -1947,6 +1979,274 @@ __global__ __launch_bounds__(256) void narrow_seeds_kernel(const int64_t *__rest
                                                            int32_t *__restrict__ out) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 256)
         out[i] = (int32_t)seed[i];
+}
+
+// ---- 2f. candidates from the anchors: no pass over the samples ----------------------------------------
+// With seeds from anchor buckets (2e) the bound of 2c can be moved to the anchor.  With a = the anchor sample i was
+// grouped with, p = the anchor's seed and r_i >= |x_i - a|  (real arithmetic, Euclidean norms):
+//     |x_i - w_j| >= |a - w_j| - r_i,      |x_i - w_p| <= |a - w_p| + r_i,
+// so a prototype j with  L[a][j] - U[a] >= 2 r_i + m_i,  L[a][j] <= |a - w_j|,  U[a] >= |a - w_p|,  is at least m_i
+// further from x_i than the seed: |x_i - w_j|^2 >= |x_i - w_p|^2 + m_i^2, m_i = sqrt(2 rho_i) as in 2c, and j can
+// neither win nor tie in the exact stage's chain.  Anchors, buckets and r_i are functions of the samples alone: the
+// per-load RUN TABLE holds, for every 128-sample workgroup of the bucket order, its runs of equal anchor as
+//     (anchor, R >= max r_i over the run, XXmax = max |x_i|^2 over the run)
+// -- workgroups + anchors runs at the most, CSR-like (run_start per workgroup).  Everything that depends on the
+// prototypes is A x M values anchor_seed_kernel forms anyway and now keeps:
+//     alow[a][j] <= |a - w_j|^2   float32, rounded down: ((|a|^2 + v) - rho_a)(1 - 1e-12), v = |w_j|^2 - 2 a . w_j the
+//                                 value its arg-min compares, rho_a = anchor_rho (cancellation, as rho in 2c);
+//     aup[a]     >= |a - w_p|     sqrt(((|a|^2 + v_p) + rho_a)(1 + 1e-12)) (1 + 1e-12).
+// anchor_mark_kernel rules j out for a run when  alow[a][j] >= T^2,  T = (aup[a] + 2 R)(1 + 1e-12) + sqrt(2 rho) 1.0001,
+// rho = 4 (d + 16) 2^-53 (XXmax + max |w|^2) -- the run's largest margin; T^2 rounded up by (1 + 1e-12) and never
+// below the smallest normal number, so that "no bound known" (0) rules nothing out.  R is formed in float64 as a sum
+// of squared differences (no cancellation) and widened by RUN_R_MARGIN, which covers the d + 2 roundings of the sum
+// and the square root.  A run whose R or XXmax is not finite (a row or an anchor with a NaN or an infinity) or whose
+// T^2 is not leaves the whole map to the workgroup, as misc[0] does in prune_mark_kernel.
+// The lists are those of 2c with |x_i - w_p| bounded through the anchor instead of measured: as short where the
+// buckets are tight against the distances between the clusters, longer where they are not.  A workgroup whose list
+// comes out longer than the threshold of 2c's re-seeding is therefore not final: it is handed to prune_mark_kernel,
+// which reads the plane rows of those workgroups only.
+constexpr double RUN_R_MARGIN_PER_D = 2.220446049250313e-16;   // R = sqrt(sum) (1 + (d + 8) 2^-52)
+
+// the run table, carved from one allocation (base == nullptr: only the total)
+struct AnchorRuns {
+    uint32_t *ticket;      // "last workgroup" ticket of anchor_run_count_kernel (0 between launches)
+    int32_t *run_start;    // nb + 1: the runs of workgroup g are [run_start[g], run_start[g + 1])
+    int32_t *run_anchor;   // cap
+    double *run_R, *run_xx;  // cap each
+    double *anorm;         // A: |a|^2
+    int64_t nb, cap;
+};
+static size_t carve_anchor_runs(AnchorRuns *out, char *base, int64_t N, int n_anchors) {
+    AnchorRuns scratch;
+    AnchorRuns &t = out ? *out : scratch;
+    t.nb = (N + 127) / 128;
+    t.cap = t.nb + n_anchors;   // (buckets in ascending order: a workgroup opens one run, every further anchor one more)
+    size_t off = 0;
+    auto take = [&](auto *&field, size_t bytes) {
+        field = base ? reinterpret_cast<std::remove_reference_t<decltype(field)>>(base + off) : nullptr;
+        off += align_up(bytes);
+    };
+    take(t.ticket, 256);
+    take(t.run_start, (size_t)(t.nb + 1) * 4);
+    take(t.run_anchor, (size_t)t.cap * 4);
+    take(t.run_R, (size_t)t.cap * 8); take(t.run_xx, (size_t)t.cap * 8);
+    take(t.anorm, (size_t)n_anchors * 8);
+    return off;
+}
+
+// (a negative anchor id is no anchor: it becomes one that fails every range check, and its run gets no bound)
+__device__ __forceinline__ int run_key(int a) { return a < 0 ? 0x7fffffff : a; }
+
+// the heads of the runs of one workgroup: thread t < 128 holds position p0 + t of the bucket order; a_s[t] = its
+// anchor (-1 past the end).  -> (run index of thread t's sample, number of runs), by ballots of the two wavefronts.
+__device__ __forceinline__ int run_index_128(const int *a_s, int *cnt_s, int tid, int *nrun) {
+    const int lane = tid & 63, wave = tid >> 6;
+    const int a = tid < 128 ? a_s[tid] : -1;
+    const bool head = tid < 128 && a != -1 && (tid == 0 || a_s[tid - 1] != a);
+    const uint64_t b = __builtin_amdgcn_ballot_w64(head);
+    if (lane == 0 && wave < 2) cnt_s[wave] = __popcll(b);
+    __syncthreads();
+    const uint64_t below = (lane == 63) ? ~0ull : ((1ull << (lane + 1)) - 1ull);   // positions <= lane
+    *nrun = cnt_s[0] + cnt_s[1];
+    return (wave == 1 ? cnt_s[0] : 0) + __popcll(b & below) - 1;
+}
+
+// run_start: the number of runs per workgroup, then (the last workgroup to finish) their running sum
+__global__ __launch_bounds__(128) void anchor_run_count_kernel(const int32_t *__restrict__ anchor_of,
+                                                               const int32_t *__restrict__ order, int64_t N, int nb,
+                                                               int32_t *__restrict__ run_start, uint32_t *__restrict__ ticket) {
+    __shared__ int a_s[128], cnt_s[2], part_s[128];
+    const int tid = threadIdx.x;
+    const int64_t p = (int64_t)blockIdx.x * 128 + tid;
+    a_s[tid] = p < N ? run_key(anchor_of[order[p]]) : -1;
+    __syncthreads();
+    int nrun;
+    (void)run_index_128(a_s, cnt_s, tid, &nrun);
+    if (tid == 0) {
+        run_start[blockIdx.x + 1] = nrun;
+        if (blockIdx.x == 0) run_start[0] = 0;
+    }
+    if (!last_workgroup_done(ticket, gridDim.x)) return;
+    // thread t: entries 1 + t per .. of run_start, per = ceil(nb / 128)
+    const int per = (nb + 127) / 128, lo = 1 + tid * per, hi = min(lo + per, nb + 1);
+    int sum = 0;
+    for (int g = lo; g < hi; ++g) sum += run_start[g];
+    part_s[tid] = sum;
+    __syncthreads();
+    int pre = 0;
+    for (int u = 0; u < tid; ++u) pre += part_s[u];
+    for (int g = lo; g < hi; ++g) { pre += run_start[g]; run_start[g] = pre; }
+}
+
+// the runs of every workgroup: anchor, R and XXmax (see above); 4 wavefronts, a sample's row per wavefront and step
+template <typename XT>
+__global__ __launch_bounds__(256) void anchor_run_fill_kernel(const XT *__restrict__ X, int64_t N, int d, int64_t ldx,
+                                                              const double *__restrict__ xx,
+                                                              const double *__restrict__ anchors, int A,
+                                                              const int32_t *__restrict__ anchor_of,
+                                                              const int32_t *__restrict__ order,
+                                                              const int32_t *__restrict__ run_start, int cap,
+                                                              int32_t *__restrict__ run_anchor, double *__restrict__ run_R,
+                                                              double *__restrict__ run_xx) {
+    __shared__ int a_s[128], cnt_s[2];
+    __shared__ int64_t samp_s[128];
+    __shared__ unsigned long long r_s[128], x_s[128], run_r[128], run_x[128];   // non-negative doubles by their bit patterns
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t p0 = (int64_t)blockIdx.x * 128;
+    const unsigned long long INF_BITS = 0x7ff0000000000000ull;
+    if (tid < 128) {
+        const int64_t p = p0 + tid;
+        const int64_t i = p < N ? (int64_t)order[p] : 0;
+        samp_s[tid] = i;
+        a_s[tid] = p < N ? run_key(anchor_of[i]) : -1;
+        run_r[tid] = 0ull; run_x[tid] = 0ull;
+    }
+    __syncthreads();
+    const double widen_R = 1.0 + (double)(d + 8) * RUN_R_MARGIN_PER_D;
+    for (int t = wave; t < 128; t += 4) {
+        const int a = a_s[t];
+        if (a == -1) break;   // (past the end: so is every later position)
+        const bool a_ok = a < A;
+        const XT *xr = X + (size_t)samp_s[t] * ldx;
+        const double *ar = anchors + (size_t)(a_ok ? a : 0) * d;
+        double acc = 0.0;
+        for (int k = lane; k < d; k += 64) {
+            const double t_ = widen(xr[k]) - ar[k];
+            acc = fma(t_, t_, acc);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+        if (lane == 0) {
+            const double xv = xx[samp_s[t]], R = sqrt(acc) * widen_R;
+            const bool ok = a_ok && R >= 0.0 && R < INFINITY && xv >= 0.0 && xv < INFINITY;   // (a NaN fails)
+            r_s[t] = ok ? (unsigned long long)__double_as_longlong(R) : INF_BITS;
+            x_s[t] = ok ? (unsigned long long)__double_as_longlong(xv) : INF_BITS;
+        }
+    }
+    __syncthreads();
+    int nrun;
+    const int run = run_index_128(a_s, cnt_s, tid, &nrun);
+    if (tid < 128 && a_s[tid] != -1) {
+        atomicMax(&run_r[run], r_s[tid]);
+        atomicMax(&run_x[run], x_s[tid]);
+    }
+    __syncthreads();
+    const int base = run_start[blockIdx.x];
+    if (tid < 128 && a_s[tid] != -1 && (tid == 0 || a_s[tid - 1] != a_s[tid]) && base + run < cap) {
+        const int a = a_s[tid];
+        run_anchor[base + run] = (a >= 0 && a < A) ? a : 0;   // (out of range: R is infinite, the anchor is not looked at)
+        run_R[base + run] = __longlong_as_double((long long)run_r[run]);
+        run_xx[base + run] = __longlong_as_double((long long)run_x[run]);
+    }
+}
+
+// the candidate lists of the 128-sample workgroups by the rule above; the outputs of prune_mark_kernel.  A list
+// longer than hand_above: the workgroup's id goes to `handed` instead, for prune_mark_kernel's per-sample pass.
+// ONE WAVEFRONT per 128-sample workgroup, sixteen to a block, and the block adds up its lists' bin counts and lengths
+// in LDS before it touches the schedule's counters: the work of a list is a few dependent round trips to L2 (run table
+// -> bounds of the runs' anchors -> their rows of alow) and 16 compares per lane at M = 1024, and what bounded the
+// kernel with a block (or a wavefront) publishing every list on its own were the 2 x 7813 atomic adds of C4 on three
+// or four addresses -- ~100 us at C4 and at C3 alike, whatever the blocks' shape.
+constexpr int AM_WAVES = 16;
+__global__ __launch_bounds__(64 * AM_WAVES) void anchor_mark_kernel(
+    const int32_t *__restrict__ run_start, const int32_t *__restrict__ run_anchor, const double *__restrict__ run_R,
+    const double *__restrict__ run_xx, int cap, int A, const int32_t *__restrict__ aseed, const double *__restrict__ aup,
+    const float *__restrict__ alow, int ldl, const double *__restrict__ summary, int M, int d, int nb,
+    uint16_t *__restrict__ ulist, int ulist_stride, uint32_t *__restrict__ ucount, uint32_t *__restrict__ sched_ctr,
+    unsigned long long *__restrict__ sum_out, int32_t *__restrict__ handed, unsigned long long *__restrict__ handed_len,
+    uint32_t hand_above) {
+    __shared__ int run_a_s[AM_WAVES][128], run_p_s[AM_WAVES][128];
+    __shared__ double run_t_s[AM_WAVES][128];
+    __shared__ uint32_t mask_s[AM_WAVES][PRUNE_MAX_M / 32];
+    __shared__ int misc_s[AM_WAVES];
+    __shared__ uint32_t bin_s[SCHED_BINS];
+    __shared__ unsigned long long sum_s;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int group = blockIdx.x * AM_WAVES + wave, nwords = (M + 31) / 32;
+    if (tid < SCHED_BINS) bin_s[tid] = 0u;
+    if (tid == SCHED_BINS) sum_s = 0ull;
+    const bool live = group < nb;   // (the last block's spare wavefronts only keep the barriers company)
+    int *run_a = run_a_s[wave], *run_p = run_p_s[wave], *misc = &misc_s[wave];
+    double *run_t = run_t_s[wave];
+    uint32_t *mask = mask_s[wave];
+    const int rs = live ? run_start[group] : 0, nrun = live ? run_start[group + 1] - rs : 0;
+    if (lane == 0) misc[0] = (nrun < 1 || nrun > 128 || rs < 0 || rs + nrun > cap) ? 1 : 0;   // 1: every prototype is a candidate
+    __syncthreads();
+    if (!misc[0])
+        for (int t = lane; t < nrun; t += 64) {
+            const int a = run_anchor[rs + t];
+            const double R = run_R[rs + t], xm = run_xx[rs + t], yy_max = summary[2];
+            const bool a_ok = a >= 0 && a < A;
+            const double rho = 4.0 * (double)(d + 16) * 1.1102230246251565e-16 * (xm + yy_max);
+            const double T = ((a_ok ? aup[a] : INFINITY) + 2.0 * R) * (1.0 + 1e-12) + sqrt(2.0 * rho) * 1.0001;
+            const double T2 = T * T * (1.0 + 1e-12);
+            run_a[t] = a_ok ? a : 0;
+            run_p[t] = a_ok ? aseed[a] : -1;
+            run_t[t] = fmax(T2, 2.2250738585072014e-308);
+            if (!(T2 < INFINITY)) misc[0] = 1;   // (a NaN fails this too)
+        }
+    __syncthreads();
+    if (live && !misc[0]) {
+        // as in prune_mark_kernel: four steps of 64 prototypes against four runs at a time, 16 loads in flight per lane
+        constexpr int JU = 4;
+        for (int jb = 0; jb < M; jb += 64 * JU) {
+            bool keep[JU] = {false, false, false, false};
+            for (int r = 0; r < nrun; r += 4) {
+                int pr[4], ra[4];
+                double T[4];
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    const int rr = r + v < nrun ? r + v : r;
+                    pr[v] = run_p[rr]; ra[v] = run_a[rr]; T[v] = run_t[rr];
+                }
+                float g[JU][4];
+#pragma unroll
+                for (int u = 0; u < JU; ++u) {
+                    const int j = jb + 64 * u + lane;
+                    const int jc = j < M ? j : M - 1;
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) g[u][v] = alow[(size_t)ra[v] * ldl + jc];
+                }
+#pragma unroll
+                for (int u = 0; u < JU; ++u) {
+                    const int j = jb + 64 * u + lane;
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) keep[u] |= (j == pr[v]) || !((double)g[u][v] >= T[v]);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < JU; ++u) {
+                const int j0 = jb + 64 * u;
+                if (j0 >= M) break;
+                const uint64_t b = __builtin_amdgcn_ballot_w64(keep[u] && j0 + lane < M);
+                if (lane == 0) {
+                    mask[j0 >> 5] = (uint32_t)b;
+                    if ((j0 >> 5) + 1 < nwords) mask[(j0 >> 5) + 1] = (uint32_t)(b >> 32);
+                }
+            }
+        }
+    } else if (live) {
+        for (int w = lane; w < nwords; w += 64) {
+            const int left = M - w * 32;
+            mask[w] = left >= 32 ? 0xffffffffu : ((1u << left) - 1u);
+        }
+    }
+    __syncthreads();
+    if (live) {
+        const uint32_t base = compact_marked(mask, nwords, lane, ulist + (size_t)group * ulist_stride, true);
+        if (lane == 0) {
+            if (base > hand_above) {
+                handed[atomicAdd(handed_len, 1ull)] = group;
+            } else {
+                ucount[group] = base;
+                atomicAdd(&bin_s[sched_bin(base)], 1u);
+                atomicAdd(&sum_s, (unsigned long long)base);
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < SCHED_BINS && bin_s[tid]) atomicAdd(&sched_ctr[tid], bin_s[tid]);
+    if (tid == SCHED_BINS && sum_s) atomicAdd(sum_out, sum_s);
 }
 
 // ---- 3. exact arg-min over the marked prototypes (float64 MFMA on gathered rows) -----------------
@@ -2427,6 +2727,9 @@ struct FilterWs {
     int32_t *aseed;    // ANCHOR_MAX: the nearest prototype of every anchor (2e)
     double *apart_val; // ANCHOR_MAX x ceil(M / 64): its minimum per block of 64 prototypes, value ...
     int32_t *apart_idx;  // ... and index
+    float *alow;       // ANCHOR_MAX x Mg: lower bounds of the squared distances from the anchors to the prototypes (2f)
+    double *aup;       // ANCHOR_MAX: upper bounds of the distances from the anchors to their seeds
+    int32_t *handed;   // nb: workgroups anchor_mark_kernel left to prune_mark_kernel
     uint32_t *nnub;    // Mg float32 bit patterns: upper bounds of the prototypes' nearest-neighbour distances (k = 2)
     unsigned long long *cand;  // N: per-sample candidates (four prototype ids) after the refinement (2d)
     int64_t *rbest;    // N: the refinement's best prototype per sample (bucket key of the pair kernel)
@@ -2477,6 +2780,8 @@ static size_t carve_filter(FilterWs *out, char *base, int64_t N, int64_t d, int6
     take(f.retry, (size_t)nb * 4); take(f.nnub, (size_t)Mg * 4);
     take(f.aseed, (size_t)ANCHOR_MAX * 4);
     take(f.apart_val, (size_t)ANCHOR_MAX * (Mg / 64) * 8); take(f.apart_idx, (size_t)ANCHOR_MAX * (Mg / 64) * 4);
+    take(f.alow, M <= PRUNE_MAX_M ? (size_t)ANCHOR_MAX * Mg * 4 : 0); take(f.aup, (size_t)ANCHOR_MAX * 8);
+    take(f.handed, (size_t)nb * 4);
     f.Mg = Mg; f.nb = nb; f.Mpad = Mpad;
     return off;
 }
@@ -2492,6 +2797,39 @@ static int launch_slice(const void *A, int dtype, int64_t rows, int64_t d, int64
     else
         hipLaunchKernelGGL(slice_rows_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)A, rows, (int)d, ld, dpad, b.planes, b.scale, b.l1, b.res16);
     return launch_status("slice_rows_kernel");
+}
+
+size_t anchor_runs_bytes(int64_t N, int n_anchors) {
+    if (N < 1 || n_anchors < 1) return 0;
+    return carve_anchor_runs(nullptr, nullptr, N, n_anchors);
+}
+
+int launch_anchor_runs(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx,
+                       const double *anchors, int n_anchors, const int32_t *anchor_of, const int32_t *order, void *runs,
+                       size_t runs_bytes, hipStream_t s) {
+    DBGSOM_REQUIRE(valid_dtype(x_dtype) && N >= 1 && N < 0x7fffffff && d >= 1 && ldx >= d, "bad samples");
+    DBGSOM_REQUIRE(n_anchors >= 1 && n_anchors <= ANCHOR_MAX, "n_anchors outside [1, 256]");
+    DBGSOM_REQUIRE(X && xx && anchors && anchor_of && order && runs && is_aligned(runs, 256), "bad pointer");
+    if (runs_bytes < anchor_runs_bytes(N, n_anchors)) {
+        set_error("anchor runs: table buffer too small");
+        return DBGSOM_ENOMEM;
+    }
+    AnchorRuns t;
+    carve_anchor_runs(&t, (char *)runs, N, n_anchors);
+    DBGSOM_HIP_CHECK(hipMemsetAsync(t.ticket, 0, 256, s));
+    const int rc = launch_row_sqnorms(anchors, DBGSOM_F64, n_anchors, d, d, t.anorm, s);
+    if (rc != DBGSOM_OK) return rc;
+    const dim3 grid((unsigned)t.nb);
+    hipLaunchKernelGGL(anchor_run_count_kernel, grid, dim3(128), 0, s, anchor_of, order, N, (int)t.nb, t.run_start, t.ticket);
+    auto fill = [&](auto *rows) {
+        hipLaunchKernelGGL(anchor_run_fill_kernel<std::remove_cv_t<std::remove_pointer_t<decltype(rows)>>>, grid, dim3(256), 0,
+                           s, rows, N, (int)d, ldx, xx, anchors, n_anchors, anchor_of, order, t.run_start, (int)t.cap,
+                           t.run_anchor, t.run_R, t.run_xx);
+    };
+    if (x_dtype == DBGSOM_F32) fill((const float *)X);
+    else if (x_dtype == DBGSOM_F64) fill((const double *)X);
+    else fill((const bf16_t *)X);
+    return launch_status("anchor run table");
 }
 
 }  // namespace dbgsom
@@ -2576,6 +2914,53 @@ int dbgsom_bmu_filtered_anchored(const void *X_dev, int x_dtype, int64_t N, int6
     return launch_bmu_filtered(a);
 }
 
+/* the run table of anchor buckets (2f) and the anchored call that brings it */
+size_t dbgsom_anchor_runs_bytes(int64_t N, int n_anchors) { return dbgsom::anchor_runs_bytes(N, n_anchors); }
+
+int dbgsom_anchor_runs_build(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx_dev,
+                             const double *anchors_dev, int n_anchors, const int32_t *anchor_of_dev,
+                             const int32_t *order_dev, void *runs_dev, size_t runs_bytes, void *stream) {
+    return launch_anchor_runs(X_dev, x_dtype, N, d, ldx, xx_dev, anchors_dev, n_anchors, anchor_of_dev, order_dev, runs_dev,
+                              runs_bytes, (hipStream_t)stream);
+}
+
+int dbgsom_anchor_runs_read(const void *runs_dev, int64_t N, int n_anchors, int32_t *run_start_host,
+                            int32_t *run_anchor_host, double *run_R_host, double *run_xx_host, void *stream) {
+    DBGSOM_REQUIRE(runs_dev && run_start_host, "null pointer");
+    DBGSOM_REQUIRE(N >= 1 && n_anchors >= 1 && n_anchors <= ANCHOR_MAX, "bad shape");
+    AnchorRuns t;
+    carve_anchor_runs(&t, (char *)const_cast<void *>(runs_dev), N, n_anchors);
+    hipStream_t s = (hipStream_t)stream;
+    DBGSOM_HIP_CHECK(hipMemcpyAsync(run_start_host, t.run_start, (size_t)(t.nb + 1) * 4, hipMemcpyDeviceToHost, s));
+    DBGSOM_HIP_CHECK(hipStreamSynchronize(s));
+    int64_t n = run_start_host[t.nb];
+    n = n < 0 ? 0 : (n > t.cap ? t.cap : n);   // (runs beyond the capacity were never written)
+    if (run_anchor_host) DBGSOM_HIP_CHECK(hipMemcpyAsync(run_anchor_host, t.run_anchor, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    if (run_R_host) DBGSOM_HIP_CHECK(hipMemcpyAsync(run_R_host, t.run_R, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    if (run_xx_host) DBGSOM_HIP_CHECK(hipMemcpyAsync(run_xx_host, t.run_xx, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    DBGSOM_HIP_CHECK(hipStreamSynchronize(s));
+    return DBGSOM_OK;
+}
+
+int dbgsom_bmu_filtered_anchor_runs(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx,
+                                    const double *xx_dev, const void *xplanes_dev, const double *W_dev,
+                                    int64_t M, const double *ww_dev, const double *anchors_dev, int n_anchors,
+                                    const int32_t *anchor_of_dev, const int32_t *order_dev, const void *runs_dev,
+                                    int seed_stride, int sweep_planes, int round_f32, int64_t *idx_dev, double *dist_dev,
+                                    void *workspace_dev, size_t workspace_bytes, void *stream) {
+    DBGSOM_REQUIRE(anchor_of_dev && runs_dev, "anchor runs: null anchor_of or table");
+    DBGSOM_REQUIRE(is_aligned(anchors_dev, 16), "alignment");
+    FilteredCall a;
+    a.X = X_dev; a.x_dtype = x_dtype; a.N = N; a.d = d; a.ldx = ldx; a.xx = xx_dev; a.xplanes = xplanes_dev;
+    a.W = W_dev; a.M = M; a.ww = ww_dev; a.order = order_dev;
+    a.anchors = anchors_dev; a.n_anchors = n_anchors; a.anchor_of = anchor_of_dev; a.anchor_runs = runs_dev;
+    a.seed_stride = seed_stride & ~DBGSOM_REFINE; a.sweep_planes = sweep_planes; a.round_f32 = round_f32;
+    a.idx = idx_dev; a.dist = dist_dev; a.ws = workspace_dev; a.ws_bytes = workspace_bytes;
+    a.stream = (hipStream_t)stream;
+    a.refine_rows = (seed_stride & DBGSOM_REFINE) ? 192 : 0;
+    return launch_bmu_filtered(a);
+}
+
 }  // extern "C"
 
 int dbgsom::filter_stage_ms(FilterAux &aux, double *ms5) {
@@ -2638,14 +3023,30 @@ struct FilterRun {
     // prune_mark_kernel: retry_mode as there; hinted: with the caller's bound on the seed distances, if it brought
     // one.  The pruning form writes the lists and adds to their sum; the probe beside a sweep only counts, into the
     // sum's twin.  (The count of long lists is kept either way: the engine turns the re-seeding on when a call reports any.)
-    void prune_mark(int retry_mode, bool hinted) const {
+    // work: every workgroup, or only those listed by the pass before (re-seeded ones; the ones anchor_mark left)
+    enum WorkList { WHOLE_GRID, RESEEDED, HANDED };
+    unsigned long long *handed_len() const { return reinterpret_cast<unsigned long long *>(f.sched_ctr + SCHED_HANDED); }
+    void prune_mark(int retry_mode, bool hinted, WorkList work = WHOLE_GRID) const {
         const bool hint = hinted && c.hint_shift;
+        const int32_t *work_groups = work == RESEEDED ? f.retry : (work == HANDED ? f.handed : nullptr);
+        const unsigned long long *work_len = work == RESEEDED ? retry_len() : (work == HANDED ? handed_len() : nullptr);
         unsigned long long *sum = reinterpret_cast<unsigned long long *>(f.sched_ctr + SCHED_SUM) + (fm.prune ? 0 : 1);
         hipLaunchKernelGGL(prune_mark_kernel, dim3((unsigned)f.nb), dim3(256), 0, s, xb.planes, xb.scale, c.xx, c.N, d, dpad,
                            f.wt, (int)f.Mpad, f.wscale, c.ww, f.summary, (int)c.M, seeds, order, f.gap, (int)f.Mg, f.ulist,
                            (int)f.Mpad, f.ucount, f.sched_ctr, sum, fm.prune ? 0 : 1, hint ? c.hint_dist : nullptr,
                            hint ? c.hint_shift : nullptr, f.retry, retry_len(), retry_mode,
-                           (uint32_t)(c.M / 8 > 96 ? c.M / 8 : 96), fm.k2 ? f.nnub : nullptr);
+                           long_above(), fm.k2 ? f.nnub : nullptr, work_groups, work_len);
+    }
+    uint32_t long_above() const { return (uint32_t)(c.M / 8 > 96 ? c.M / 8 : 96); }   // a list longer than this is "long"
+
+    // anchor_mark_kernel (2f): the lists from the anchors' bounds and the run table; long ones go to `handed`
+    void anchor_mark() const {
+        AnchorRuns t;
+        carve_anchor_runs(&t, (char *)const_cast<void *>(c.anchor_runs), c.N, c.n_anchors);
+        hipLaunchKernelGGL(anchor_mark_kernel, dim3((unsigned)((f.nb + AM_WAVES - 1) / AM_WAVES)), dim3(64 * AM_WAVES), 0, s,
+                           t.run_start, t.run_anchor, t.run_R, t.run_xx, (int)t.cap, c.n_anchors, f.aseed, f.aup, f.alow,
+                           (int)f.Mg, f.summary, (int)c.M, d, (int)f.nb, f.ulist, (int)f.Mpad, f.ucount, f.sched_ctr,
+                           reinterpret_cast<unsigned long long *>(f.sched_ctr + SCHED_SUM), f.handed, handed_len(), long_above());
     }
 
     // the gaps between the prototypes (pruning form): they need the digit planes of W and nothing of the samples
@@ -2727,26 +3128,49 @@ struct FilterRun {
             gap_aside = true;
         }
         hipLaunchKernelGGL(anchor_seed_kernel, dim3((unsigned)(f.Mg / 64), (unsigned)((c.n_anchors + 15) / 16)), dim3(256),
-                           0, s, c.anchors, c.n_anchors, c.W, (int)c.M, d, c.ww, f.apart_val, f.apart_idx, f.tickets, f.aseed);
+                           0, s, c.anchors, c.n_anchors, c.W, (int)c.M, d, c.ww, f.apart_val, f.apart_idx, f.tickets, f.aseed,
+                           run_anorm(), f.summary, fm.anchor_mark ? f.alow : nullptr, (int)f.Mg,
+                           fm.anchor_mark ? f.aup : nullptr);
+        // (the gather stays: the per-sample pass of the handed workgroups and the diagnostics read f.seed)
         hipLaunchKernelGGL(anchor_gather_kernel, dim3(seed_grid()), dim3(256), 0, s, f.aseed, c.anchor_of, c.N, f.seed);
         aux.timer.mark(2, s);
         seeds = f.seed;
         return DBGSOM_OK;
     }
 
+    const double *run_anorm() const {
+        if (!fm.anchor_mark) return nullptr;
+        AnchorRuns t;
+        carve_anchor_runs(&t, (char *)const_cast<void *>(c.anchor_runs), c.N, c.n_anchors);
+        return t.anorm;
+    }
+
     // 3. the candidate lists of the 128-sample workgroups
     int mark_candidates() const {
-        if (fm.gap_nb) {   // (the pruning form, or its counting-only launch beside a sweep)
-            if (gap_aside) {
-                DBGSOM_HIP_CHECK(hipStreamWaitEvent(s, aux.side.gap_done, 0));
-            } else {
-                const int rc = gaps(s);
-                if (rc != DBGSOM_OK) return rc;
+        // the pruning form, or its counting-only launch beside a sweep: the passes FilterForm::prune_passes lists.
+        // Behind anchor_mark_kernel the per-sample pass sees the handed workgroups only, and counts and re-seeds as
+        // it does over the whole grid: the count of long lists the policy reads is the count AFTER that pass, not
+        // what anchor_mark_kernel handed over.
+        FilterForm::Pass passes[4];
+        const int n_passes = fm.prune_passes(passes);
+        bool gaps_ready = false;
+        for (int k = 0; k < n_passes; ++k) {
+            // (the lists from the anchors need no gaps: the side stream's are the per-sample pass's to wait for)
+            if (passes[k] != FilterForm::PASS_ANCHOR_MARK && !gaps_ready) {
+                if (gap_aside) {
+                    DBGSOM_HIP_CHECK(hipStreamWaitEvent(s, aux.side.gap_done, 0));
+                } else {
+                    const int rc = gaps(s);
+                    if (rc != DBGSOM_OK) return rc;
+                }
+                gaps_ready = true;
             }
-            prune_mark(fm.prune_retry ? 1 : 0, true);
-            if (fm.prune_retry) {
-                sweep4(RESEED);
-                prune_mark(2, false);
+            switch (passes[k]) {
+            case FilterForm::PASS_ANCHOR_MARK: anchor_mark(); break;
+            case FilterForm::PASS_PRUNE_GRID: prune_mark(fm.prune_retry ? 1 : 0, true, WHOLE_GRID); break;
+            case FilterForm::PASS_PRUNE_HANDED: prune_mark(fm.prune_retry ? 1 : 0, true, HANDED); break;
+            case FilterForm::PASS_RESEED: sweep4(RESEED); break;
+            case FilterForm::PASS_PRUNE_RESEEDED: prune_mark(2, false, RESEEDED); break;
             }
         }
         switch (fm.marking) {
@@ -2898,8 +3322,11 @@ struct FilterRun {
 int dbgsom::launch_bmu_filtered(const FilteredCall &call) {
     FilterForm form;
     const char *rejected = form.resolve(call.seed_stride, call.sweep_planes, call.k, call.refine_rows, call.defer_dist, call.N,
-                                        call.d, call.M, call.prev_idx != nullptr);
+                                        call.d, call.M, call.prev_idx != nullptr, call.anchor_of != nullptr,
+                                        call.anchor_runs != nullptr);
     DBGSOM_REQUIRE(!rejected, rejected);
+    DBGSOM_REQUIRE(!call.anchor_runs || (call.anchor_of && is_aligned(call.anchor_runs, 256)),
+                   "anchor runs: the table comes with the anchor buckets it was built from");
     DBGSOM_REQUIRE(call.x_dtype == DBGSOM_F32 || call.x_dtype == DBGSOM_F64, "the filtered search takes float32 or float64 samples");
     DBGSOM_REQUIRE(call.N >= 1 && call.N < 0x7fffffff && call.d >= 1 && call.d % KT == 0 && call.ldx >= call.d,
                    "bad sample shape (d must be a multiple of 16)");
@@ -3014,6 +3441,45 @@ int dbgsom_bmu_filtered_anchor_seeds(const void *workspace_dev, int64_t N, int64
     if (seed_host)
         DBGSOM_HIP_CHECK(hipMemcpyAsync(seed_host, f.seed, (size_t)N * 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
     DBGSOM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    return DBGSOM_OK;
+}
+
+/* diagnostics: the candidate lists of the last filtered call on this workspace (same N, d, M): lists_host[g * M + k],
+ * k < counts[g] (dbgsom_bmu_filtered_counts), the ascending prototype ids of workgroup g (ceil(N / 128) x M uint16;
+ * entries behind a list's length are whatever earlier passes left).  Synchronises the stream. */
+int dbgsom_bmu_filtered_lists(const void *workspace_dev, int64_t N, int64_t d, int64_t M, uint16_t *lists_host,
+                              void *stream) {
+    DBGSOM_REQUIRE(workspace_dev && lists_host, "null pointer");
+    DBGSOM_REQUIRE(N >= 1 && d >= 1 && M >= 1 && M <= SW_MAX_M, "M outside [1, 16000]");
+    FilterWs f;
+    carve_filter(&f, (char *)const_cast<void *>(workspace_dev), N, d, M);
+    DBGSOM_HIP_CHECK(hipMemcpy2DAsync(lists_host, (size_t)M * 2, f.ulist, (size_t)f.Mpad * 2, (size_t)M * 2, (size_t)f.nb,
+                                      hipMemcpyDeviceToHost, (hipStream_t)stream));
+    DBGSOM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    return DBGSOM_OK;
+}
+
+/* diagnostics: what the last dbgsom_bmu_filtered_anchor_runs call on this workspace (same N, d, M) left of its bounds
+ * (2f): low_host[a * M + j] <= |a - w_j|^2 (n_anchors x M float32, 0 = no bound known), up_host[a] >= |a - w_seed(a)|
+ * (n_anchors float64), counts2_host = [workgroups anchor_mark_kernel handed to the per-sample pass, workgroups whose
+ * lists were long after that pass].  Every array may be NULL.  Synchronises the stream. */
+int dbgsom_bmu_filtered_anchor_bounds(const void *workspace_dev, int64_t N, int64_t d, int64_t M, int n_anchors,
+                                      float *low_host, double *up_host, uint64_t *counts2_host, void *stream) {
+    DBGSOM_REQUIRE(workspace_dev, "null pointer");
+    DBGSOM_REQUIRE(N >= 1 && d >= 1 && M >= 1 && M <= PRUNE_MAX_M, "no anchor bounds: M outside [1, 8192]");
+    DBGSOM_REQUIRE(n_anchors >= 1 && n_anchors <= ANCHOR_MAX, "n_anchors outside [1, 256]");
+    FilterWs f;
+    carve_filter(&f, (char *)const_cast<void *>(workspace_dev), N, d, M);
+    hipStream_t s = (hipStream_t)stream;
+    if (low_host)
+        DBGSOM_HIP_CHECK(hipMemcpy2DAsync(low_host, (size_t)M * 4, f.alow, (size_t)f.Mg * 4, (size_t)M * 4, (size_t)n_anchors,
+                                          hipMemcpyDeviceToHost, s));
+    if (up_host) DBGSOM_HIP_CHECK(hipMemcpyAsync(up_host, f.aup, (size_t)n_anchors * 8, hipMemcpyDeviceToHost, s));
+    if (counts2_host) {
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(counts2_host, f.sched_ctr + SCHED_HANDED, 8, hipMemcpyDeviceToHost, s));
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(counts2_host + 1, f.sched_ctr + SCHED_RETRY, 8, hipMemcpyDeviceToHost, s));
+    }
+    DBGSOM_HIP_CHECK(hipStreamSynchronize(s));
     return DBGSOM_OK;
 }
 

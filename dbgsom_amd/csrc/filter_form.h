@@ -51,6 +51,11 @@ struct __attribute__((visibility("hidden"))) FilterForm {
         MARK_SWEEP_2_2, // sweep_i8_kernel<0, 2, 2>
         MARK_SWEEP_3_1  // sweep_i8_kernel<0, 3, 1>
     } marking = MARK_SWEEP_2_2;
+    // MARK_PRUNE on a stateless k = 1 call that brings anchor buckets AND their run table: anchor_mark_kernel writes
+    // the lists from the anchors' distances alone (filter.hip 2f), prune_mark_kernel only sees the workgroups whose
+    // lists that leaves long.  Everything else -- k = 2, hints, the counting-only probe, anchors without a table --
+    // takes prune_mark_kernel over the whole grid.
+    bool anchor_mark = false;
     int gap_nb = 0;  // proto_gap_kernel<gap_nb> (prune, prune_probe): 2 = 64 x 64 tiles, 1 = 32 x 32; 0 = none
     // per-sample refinement (2d): the small tile of its list-length classes, 0 = only the largest
     bool refine = false;
@@ -63,12 +68,35 @@ struct __attribute__((visibility("hidden"))) FilterForm {
         EXACT_ALL             // one launch of all three classes
     } exact = EXACT_ALL;
 
+    // The passes that write the lists of the pruning form (or count them beside a sweep), in launch order.
+    // Which pass reports "long lists" to the policy (the count behind pack_results_kernel's third figure, which turns
+    // the re-seeding on): the per-sample pass -- PASS_PRUNE_GRID, or PASS_PRUNE_HANDED behind anchor_mark_kernel --
+    // and only where it is the last word on a list (prune_retry off); with prune_retry on it lists the workgroups
+    // to re-seed instead, and the figure is their number, as ever.  PASS_ANCHOR_MARK never reports: a workgroup it
+    // hands to the per-sample pass is not a long list yet.
+    enum Pass {
+        PASS_ANCHOR_MARK,     // anchor_mark_kernel: every workgroup, from the anchors' bounds; long lists handed on
+        PASS_PRUNE_GRID,      // prune_mark_kernel over every workgroup
+        PASS_PRUNE_HANDED,    // prune_mark_kernel over the workgroups PASS_ANCHOR_MARK handed on
+        PASS_RESEED,          // sweep4_i8_kernel<1> over the workgroups the per-sample pass listed
+        PASS_PRUNE_RESEEDED   // prune_mark_kernel over those, final
+    };
+    int prune_passes(Pass out[4]) const {
+        int n = 0;
+        if (!gap_nb) return 0;
+        if (anchor_mark) out[n++] = PASS_ANCHOR_MARK;
+        out[n++] = anchor_mark ? PASS_PRUNE_HANDED : PASS_PRUNE_GRID;
+        if (prune_retry) { out[n++] = PASS_RESEED; out[n++] = PASS_PRUNE_RESEEDED; }
+        return n;
+    }
+    static bool reports_long_lists(Pass p) { return p == PASS_PRUNE_GRID || p == PASS_PRUNE_HANDED; }
+
     // nullptr, or why the call is rejected (nothing of *this is then meaningful).  flags: FilteredCall::seed_stride,
     // the stride with DBGSOM_SEED_FULL / DBGSOM_PRUNE / DBGSOM_PRUNE_PROBE / DBGSOM_PRUNE_RETRY OR-ed in;
     // has_hint: the caller brings previous winners (no seed pre-pass).  The shape itself (N, d, M in range) is
-    // the launcher's to check.
+    // the launcher's to check.  has_anchors / has_runs: the call brings anchor buckets / their run table.
     const char *resolve(int flags, int planes, int k, int refine_rows, bool defer, int64_t N, int64_t d, int64_t M,
-                        bool has_hint) {
+                        bool has_hint, bool has_anchors = false, bool has_runs = false) {
         seed_full = (flags & DBGSOM_SEED_FULL) != 0;
         prune = (flags & DBGSOM_PRUNE) != 0 && M <= PRUNE_MAX_M;
         prune_probe = !prune && (flags & DBGSOM_PRUNE_PROBE) != 0 && M <= PRUNE_MAX_M;
@@ -107,6 +135,7 @@ struct __attribute__((visibility("hidden"))) FilterForm {
         if (prune) marking = MARK_PRUNE;
         else if (sweep_planes == 1) marking = M <= SWEEP4_MAX_M ? MARK_SWEEP4 : MARK_SWEEP_1_4;
         else marking = sweep_planes == 3 ? MARK_SWEEP_3_1 : MARK_SWEEP_2_2;
+        anchor_mark = prune && has_anchors && has_runs && k == 1 && !has_hint && !seed_full;
         // (gaps: 64 x 64 tiles where there are four per CU and more, M >= 2048)
         const int64_t gt = ((M + 63) / 64 * 64) / 64;
         gap_nb = (prune || prune_probe) ? (gt * gt >= 1024 ? 2 : 1) : 0;

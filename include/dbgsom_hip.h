@@ -258,6 +258,43 @@ int dbgsom_bmu_filtered_anchored(const void *X_dev, int x_dtype, int64_t N, int6
  * Synchronises the stream. */
 int dbgsom_bmu_filtered_anchor_seeds(const void *workspace_dev, int64_t N, int64_t d, int64_t M, int n_anchors,
                                      int32_t *aseed_host, int64_t *seed_host, void *stream);
+/* The run table of anchor buckets: for every 128-sample workgroup g of order_dev its runs of equal anchor,
+ * [run_start[g], run_start[g + 1]), each as (anchor, R, XXmax): R >= max |x_i - a| over the run's samples (float64 sum of
+ * squared differences, widened by the relative margin (d + 8) 2^-52), XXmax = max xx_dev[i].  A run with a row, a norm
+ * or an anchor that is not finite has R = XXmax = +inf.  A function of the samples and the buckets alone: build it
+ * once, pass it to any number of dbgsom_bmu_filtered_anchor_runs calls.  X_dev: F32 / F64 / BF16 rows, the values the
+ * search reads.  runs_dev: dbgsom_anchor_runs_bytes(N, n_anchors) bytes, 256-byte aligned.  The table holds N / 128 +
+ * n_anchors runs (rounded up) -- enough for buckets in ascending order of the anchor; a workgroup whose runs did not
+ * fit takes the whole map as candidates. */
+size_t dbgsom_anchor_runs_bytes(int64_t N, int n_anchors);
+int dbgsom_anchor_runs_build(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx_dev,
+                             const double *anchors_dev, int n_anchors, const int32_t *anchor_of_dev,
+                             const int32_t *order_dev, void *runs_dev, size_t runs_bytes, void *stream);
+/* diagnostics: the table on the host.  run_start_host: ceil(N / 128) + 1 int32; the other arrays (each may be NULL):
+ * ceil(N / 128) + n_anchors entries at the most, the first min(run_start[last], that) are written.  Synchronises. */
+int dbgsom_anchor_runs_read(const void *runs_dev, int64_t N, int n_anchors, int32_t *run_start_host,
+                            int32_t *run_anchor_host, double *run_R_host, double *run_xx_host, void *stream);
+/* dbgsom_bmu_filtered_anchored with the run table of its buckets (k = 1, stateless, DBGSOM_PRUNE): the candidate lists
+ * come from certified bounds of the distances between the anchors and the prototypes and the table -- no pass over the
+ * samples' planes; only workgroups whose lists that leaves longer than max(M / 8, 96) get the per-sample pass of
+ * dbgsom_bmu_filtered_anchored.  Winners and distances are the same bits. */
+int dbgsom_bmu_filtered_anchor_runs(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx,
+                                    const double *xx_dev, const void *xplanes_dev, const double *W_dev,
+                                    int64_t M, const double *ww_dev, const double *anchors_dev, int n_anchors,
+                                    const int32_t *anchor_of_dev, const int32_t *order_dev, const void *runs_dev,
+                                    int seed_stride, int sweep_planes, int round_f32, int64_t *idx_dev, double *dist_dev,
+                                    void *workspace_dev, size_t workspace_bytes, void *stream);
+/* diagnostics: the candidate lists of the last filtered call on this workspace with the same N, d, M: lists_host[g * M
+ * + k], k < counts[g] (dbgsom_bmu_filtered_counts), the ascending prototype ids of workgroup g (ceil(N / 128) x M
+ * uint16; what lies behind a list's length is not defined).  Synchronises the stream. */
+int dbgsom_bmu_filtered_lists(const void *workspace_dev, int64_t N, int64_t d, int64_t M, uint16_t *lists_host,
+                              void *stream);
+/* diagnostics: the bounds of the last dbgsom_bmu_filtered_anchor_runs call on this workspace with the same N, d, M:
+ * low_host[a * M + j] <= |a - w_j|^2 (n_anchors x M float32; 0 = no bound known), up_host[a] >= |a - w_seed(a)|
+ * (n_anchors float64; +inf = none), counts2_host = [workgroups handed to the per-sample pass, workgroups whose lists
+ * were still long after it].  Every array may be NULL.  Synchronises the stream. */
+int dbgsom_bmu_filtered_anchor_bounds(const void *workspace_dev, int64_t N, int64_t d, int64_t M, int n_anchors,
+                                      float *low_host, double *up_host, uint64_t *counts2_host, void *stream);
 
 /* diagnostics of the per-sample refinement (DBGSOM_REFINE) of the last filtered call:
  * out4 = [(sample, prototype) pairs evaluated exactly, 128-sample workgroups refined (the others went
@@ -960,6 +997,11 @@ int dbgsom_ctx_filter_counts(dbgsom_ctx *ctx, uint32_t *counts_host, int64_t n);
  * for every anchor -- DBGSOM_ESTATE unless that search was seeded from the anchors. */
 int dbgsom_ctx_read_anchors(dbgsom_ctx *ctx, int64_t *n_anchors, double *anchors_host, int32_t *anchor_of_host,
                             int32_t *order_host, int32_t *aseed_host);
+/* diagnostics: the run table of those buckets (dbgsom_anchor_runs_read of the context's table; "anchor_state" 1, else
+ * DBGSOM_ESTATE).  n_groups: ceil(rows / 128); run_start_host: n_groups + 1 int32 (NULL: only n_groups); the other
+ * arrays hold n_groups + n_anchors entries at the most and may be NULL. */
+int dbgsom_ctx_read_anchor_runs(dbgsom_ctx *ctx, int64_t *n_groups, int32_t *run_start_host, int32_t *run_anchor_host,
+                                double *run_R_host, double *run_xx_host);
 /* dbgsom_bmu_filtered_refine_counts of the context's last filtered search */
 int dbgsom_ctx_refine_counts(dbgsom_ctx *ctx, uint64_t *out4);
 /* ms8 = [bmu, accumulate, smooth, slice W + tables, seed pre-pass, bucket sort, candidate sweep,
