@@ -330,7 +330,12 @@ int dbgsom_topofn(const int64_t *idx2, int64_t n, const int32_t *xy, int64_t M, 
     DBGSOM_REQUIRE(M >= 1 && M <= DBGSOM_MAX_PROTOTYPES, "M must be in [1, DBGSOM_MAX_PROTOTYPES]");
     DBGSOM_REQUIRE(n >= 0 && n_pos >= 1, "bad shape");
     DBGSOM_REQUIRE(xy && hist_pos && hist_neg && (n == 0 || idx2), "null pointer");
-    DBGSOM_REQUIRE(ws && ws_bytes >= dbgsom_topofn_workspace_bytes(M, D != nullptr), "workspace too small");
+    DBGSOM_REQUIRE(ws, "null pointer");
+    DBGSOM_REQUIRE(is_aligned(ws, 256), "workspace must be 256-byte aligned");
+    if (ws_bytes < dbgsom_topofn_workspace_bytes(M, D != nullptr)) {
+        set_error("dbgsom_topofn: workspace too small");
+        return DBGSOM_ENOMEM;
+    }
     const bool full = D != nullptr;
     TfWs w;
     carve_ws(&w, static_cast<char *>(ws), M);

@@ -338,7 +338,8 @@ int dbgsom_density_terms(const double *dist_dev, int64_t n, double sigma, double
  *   dbgsom_weighted_sum_f64   out = sum_i w_i v_i (v_dev == NULL: sum_i w_i); workspace as dbgsom_sum_f64
  *   dbgsom_topographic_weight out = summed weight of the rows dbgsom_topographic_count counts
  *   dbgsom_class_histogram_weighted  hist[j, c] = summed weight of the rows of class c in neuron j's list:
- *       order_dev = the N sample ids bucketed by winner (stable), seg_start_dev = the M list starts; added in list order
+ *       order_dev = the N sample ids bucketed by winner (stable), seg_start_dev = the M + 1 exclusive list starts
+ *       (seg_start[M] = N); added in list order
  *   dbgsom_weighted_column_sums  out[j] = sum_i w_i x_ij (mean_dev == NULL) or sum_i w_i (x_ij - mean_j)^2, in
  *       float64 whatever the storage dtype (mean_dev, out_dev: d float64) */
 int dbgsom_weighted_sum_f64(const double *v_dev, const double *w_dev, int64_t n, double *out_dev,
@@ -896,7 +897,9 @@ int dbgsom_ctx_sparse_code_device(dbgsom_ctx *ctx, const void *Xq_dev, int x_dty
  *                            mode, which stops every source's search once its lattice neighbours have
  *                            their distances -- the histograms are the same)
  * idx2: n x 2 int64 BMU pairs (device); xy: M x 2 int32 lattice coordinates (device), no two alike.
- * M <= DBGSOM_MAX_PROTOTYPES.  The call is blocking (it reads back the kernels' status word):
+ * M <= DBGSOM_MAX_PROTOTYPES.  ws: dbgsom_topofn_workspace_bytes(M, full) bytes on the device, 256-byte
+ * aligned (a misaligned one is DBGSOM_EINVAL, a short one DBGSOM_ENOMEM; both before any launch); its
+ * contents on entry do not matter.  The call is blocking (it reads back the kernels' status word):
  * DBGSOM_ERANGE when an index is outside [0, M), DBGSOM_EINVAL when an edge spans >= n_pos or two
  * neurons share coordinates. */
 size_t dbgsom_topofn_workspace_bytes(int64_t M, int full);
