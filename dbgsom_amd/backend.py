@@ -557,6 +557,7 @@ class HipBackend(HotPathBackend):
     anchor_seeds = property(lambda self: self._get("anchor_seeds"), lambda self, v: self._set("anchor_seeds", int(v)))
     anchor_builds = property(lambda self: self._get("anchor_builds"))
     anchor_searches = property(lambda self: self._get("anchor_searches"))   # searches seeded from them so far
+    lean_searches = property(lambda self: self._get("lean_searches"))   # epochs among them in the lean form
     anchor_state = property(lambda self: self._get("anchor_state"))
     padded_features = property(lambda self: self._get("padded_features"))
 

@@ -18,6 +18,7 @@
 
 #include "anchor_chain.h"
 #include "common.h"
+#include "lean_gate.h"
 #include "search_policy.h"
 
 namespace dbgsom {
@@ -122,7 +123,8 @@ __global__ void u64_to_f64_kernel(const unsigned long long *__restrict__ in, dou
 // The epoch's small results in ONE kernel straight into page-locked host memory (no copy engine
 // round trips behind the last kernel: four queued D2H copies cost ~30 us per epoch):
 // out = [a (M) | E (M) | change_total | status | sum of candidate-list lengths | the same of a pruning probe |
-//        workgroups of the pruning form with long lists]
+//        workgroups of the pruning form with long lists | workgroups anchor_mark_kernel handed over (the lean form:
+//        long lists it kept)]
 __global__ void pack_results_kernel(const double *__restrict__ aE, int64_t M, const double *__restrict__ chg,
                                     const double *__restrict__ status, const unsigned long long *__restrict__ list_sum,
                                     double *__restrict__ out) {
@@ -134,6 +136,7 @@ __global__ void pack_results_kernel(const double *__restrict__ aE, int64_t M, co
         out[2 * M + 2] = list_sum ? (double)list_sum[0] : 0.0;
         out[2 * M + 3] = list_sum ? (double)list_sum[1] : 0.0;  // (of a counting-only pruning launch)
         out[2 * M + 4] = list_sum ? (double)list_sum[2] : 0.0;  // (workgroups whose pruned lists came out long)
+        out[2 * M + 5] = list_sum ? (double)list_sum[3] : 0.0;  // (workgroups whose lists from the anchors came out long)
     }
     __threadfence_system();
 }
@@ -229,9 +232,10 @@ struct Samples {  // one resident sample set (training samples, or a query batch
     DevBuf anchors, anchor_of, anchor_order, anchor_runs;
     int64_t n_anchors = 0;
     int anchor_state = 0;
+    int64_t anchor_generation = 0;   // goes up whenever the buckets go (a load, a rebuild, the valve): LeanGate
     void drop_anchors(int state) {
         anchors.release(); anchor_of.release(); anchor_order.release(); anchor_runs.release();
-        n_anchors = 0; anchor_state = state;
+        n_anchors = 0; anchor_state = state; ++anchor_generation;
     }
     void drop_planes() { planes_ready = false; drop_anchors(0); }
     // CSR residents (dbgsom_ctx_load_csr at or above "csr_densify_below" features): X stays nullptr, the rows are
@@ -371,6 +375,12 @@ struct dbgsom_ctx {
     int64_t anchor_builds = 0, anchor_searches = 0;   // buckets built / searches seeded from them so far
     bool anchors_built_now = false;     // the running epoch built the buckets: its clock is not the arm's
     bool last_anchor_seeded = false;    // the last filtered search of an epoch took its seeds from the anchors
+    // the lean form of the anchor-seeded search (DBGSOM_ANCHOR_LISTS_ONLY): when an epoch takes it (lean_gate.h),
+    // whether the last search did, the plan of the last search, and how many epochs did so far ("lean_searches")
+    LeanGate lean_gate;
+    bool last_lean = false;
+    int last_plan_key = 0;
+    int64_t lean_searches = 0;
     // mean list length of the last pruning epoch the cheap pre-pass seeded, and the map it ran on: what the
     // anchors' lists are held against (dbgsom_ctx_epoch)
     double prepass_mean = NAN;
@@ -645,6 +655,10 @@ int run_filtered(dbgsom_ctx *c, Samples &s, DevBuf &ws, const double *W, int64_t
     // and the policy's own first looks at the arm -- are its cheap seeds poor, does it need the re-seeding passes --
     // are looks at the pre-pass.
     c->last_anchor_seeded = false;
+    c->last_lean = false;
+    // (without the re-seeding bit: an epoch whose re-seeding passes found nothing to do is evidence for the same
+    //  plan without them, which is what the policy plans next; a plan WITH them is never lean)
+    c->last_plan_key = LeanGate::plan_key(plan.seed_stride & ~DBGSOM_PRUNE_RETRY, plan.sweep_planes);
     const bool has_ref = c->prepass_mean == c->prepass_mean && SearchPolicy::near_size(M, c->prepass_M);
     if (!prev_idx && &s == &c->xs && c->anchor_seeds && s.anchor_state != 2 && has_ref && plan.planes == 0 &&
         !plan.seed_full && (plan.seed_stride & DBGSOM_PRUNE)) {
@@ -654,6 +668,14 @@ int run_filtered(dbgsom_ctx *c, Samples &s, DevBuf &ws, const double *W, int64_t
         call.anchor_of = s.anchor_of.as<int32_t>(); call.order = s.anchor_order.as<int32_t>();
         call.anchor_runs = s.anchor_runs.p;
         c->last_anchor_seeded = true;
+        // The search of an epoch behind an anchor-seeded epoch of the same samples, map size and plan that handed
+        // nothing to the per-sample pass: nothing is made for that pass (the lean form).  (ensure_anchors above has
+        // bumped the generation if it had to build the buckets: that epoch is a full one.)
+        if (may_probe && c->lean_gate.allows(M, s.anchor_generation, c->last_plan_key, plan.retry, plan.refine)) {
+            call.seed_stride |= DBGSOM_ANCHOR_LISTS_ONLY;
+            c->last_lean = true;
+            ++c->lean_searches;
+        }
     }
     call.round_f32 = round_f32; call.idx = idx; call.dist = dist; call.ws = ws.p; call.ws_bytes = ws.cap;
     call.stream = c->stream;
@@ -1033,7 +1055,7 @@ int smooth_and_fetch(dbgsom_ctx *c, int64_t M, double sigma, int layout, int fla
     mark(c, 3);
     // the epoch's small results: one kernel writes them into mapped page-locked memory, one stream
     // synchronisation
-    TRY(c->tail.reserve((size_t)(2 * M + 5) * 8));
+    TRY(c->tail.reserve((size_t)(2 * M + 6) * 8));
     double *tail = c->tail.as<double>();
     const unsigned long long *list_sum =
         c->last_filtered ? dbgsom_filter_count_sum_ptr(c->filt_ws.p, s.N, dp, M) : nullptr;
@@ -1366,6 +1388,7 @@ int dbgsom_ctx_get_option(dbgsom_ctx *c, const char *name, int64_t *v) {
     else if (!strcmp(name, "incomplete")) *v = c->incomplete ? 1 : 0;
     else if (!strcmp(name, "anchor_builds")) *v = c->anchor_builds;
     else if (!strcmp(name, "anchor_searches")) *v = c->anchor_searches;
+    else if (!strcmp(name, "lean_searches")) *v = c->lean_searches;
     else if (!strcmp(name, "anchor_state")) *v = c->xs.dtype < 0 ? 0 : c->xs.anchor_state;
     else if (!strcmp(name, "planes_used")) *v = c->policy.planes_used;
     else if (!strcmp(name, "planes_next")) *v = c->policy.planes_for_call();
@@ -2734,17 +2757,22 @@ int dbgsom_ctx_epoch(dbgsom_ctx *c, const double *W_host, int64_t M, int round_f
         if (c->last_filtered) {
             // (a clean measurement of the arm: nothing rode along -- see SearchPolicy::arm_ms)
             // (... and the epoch did not build the anchor buckets on the way)
+            const double *counted = c->tail.as<double>() + 2 * M + 2;   // (pack_results_kernel: lists, probe, groups to re-seed, handed over)
+            // A lean epoch that kept long lists guessed wrong: what it measured is neither what the anchors' lists
+            // cost (the per-sample pass would have shortened them) nor a clock of the arm.  The next one is full.
+            const bool lean_missed = c->last_lean && counted[3] > 0.0;
+            if (c->last_anchor_seeded) c->lean_gate.record(M, s.anchor_generation, c->last_plan_key, counted[3], counted[2]);
+            else c->lean_gate.forget();
             const bool clean = !pol.last_probed && !pol.last_guarded && measuring < 0 && !W_new_host && !idx_host && !dist_host &&
-                               !c->anchors_built_now;
+                               !c->anchors_built_now && !lean_missed;
             const double epoch_ms =
                 clean ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count() : NAN;
-            const double *counted = c->tail.as<double>() + 2 * M + 2;   // (pack_results_kernel: lists, probe, groups to re-seed)
             // The valve of the anchor seeds: their lists against those of the last pruning epoch the cheap pre-pass
             // seeded on a map within a quarter of this size (run_filtered waits for one).  More than 1.25 times
             // that -- a quarter of the exact stage lost at the most -- and the pre-pass seeds this sample set
             // again.  (An epoch whose long lists the policy is about to re-seed is not what either form costs.)
             const int64_t nb = (s.N + 127) / 128;
-            const bool settled = !(counted[2] > 0.0 && !pol.last_retry);
+            const bool settled = !(counted[2] > 0.0 && !pol.last_retry) && !lean_missed;
             if (pol.last_probed && !pol.last_hinted && !pol.last_seed_full && settled) {
                 // (a counting-only pruning launch beside a sweep: the lists the pre-pass's seeds would have left)
                 c->prepass_mean = counted[1] / (double)nb;
@@ -2761,6 +2789,7 @@ int dbgsom_ctx_epoch(dbgsom_ctx *c, const double *W_host, int64_t M, int round_f
             }
             pol.observe(counted[0], counted[1], counted[2], nb, M, s.dp, (flags & DBGSOM_EPOCH_FROZEN) != 0, epoch_ms);
         } else {
+            c->lean_gate.forget();
             pol.observe_unfiltered();
         }
     } while (0);

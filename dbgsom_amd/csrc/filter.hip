@@ -1860,15 +1860,20 @@ __global__ __launch_bounds__(256, 6) void prune_mark_kernel(
 // certifies its own bound of |x - w_seed| whatever the seed is.
 //
 // aseed[a] = arg-min_j (|w_j|^2 - 2 a . w_j) in float64 on W itself, one v_mfma_f64_16x16x4_f64 tile (16 prototypes
-// x 16 anchors) per wavefront, operands straight from L2 (32 bytes of a row per lane and step: four k slots of four
-// consecutive features -- both operands permute k alike).  Tile-parallel over (prototypes / 64) x (anchors / 16)
-// workgroups; each leaves the (value, index) minimum of its 64 prototypes per anchor, and the workgroup of an anchor
-// block that finishes last takes the minimum over the blocks: by (value, index), no float atomics, the same bits
-// whatever the order of arrival.  A prototype row with a NaN or an infinity (|w|^2 not finite) compares as +inf, a
-// finite row whose product is not a number as DBL_MAX: a non-finite row is never the seed while a finite one exists.
+// x 16 anchors) per WORKGROUP, operands straight from L2 (32 bytes of a row per lane and step: four k slots of four
+// consecutive features -- both operands permute k alike).  The d / 16 k-steps of the tile are split over the four
+// wavefronts in contiguous ranges (13 / 12 / 12 / 12 at d = 784; a wavefront without a step holds the exact zero),
+// and the four partial tiles are added through LDS in wavefront order, ((p0 + p1) + p2) + p3: a pair's value is a
+// function of its two rows and d alone, wherever the prototype sits -- copies of a row tie bit for bit.  (One
+// wavefront per 16 x 16 tile walking all of d was ONE dependent chain of d / 4 matrix instructions per SIMD with
+// nothing to hide the L2 latency behind: 45 us at C4 for 3 us of matrix work.  Four times the wavefronts, each
+// with a quarter of the chain.)  Tile-parallel over ceil(M / 16) x (anchors / 16) workgroups; each leaves the
+// (value, index) minimum of its 16 prototypes per anchor, and anchor_seed_min_kernel behind it takes the minimum over
+// the blocks: by (value, index), no float atomics, no tickets, the same bits whatever the order.  A prototype row with
+// a NaN or an infinity (|w|^2 not finite) compares as +inf, a finite row whose product is not a number as DBL_MAX: a
+// non-finite row is never the seed while a finite one exists.
 typedef double ad4_t __attribute__((ext_vector_type(4)));
 constexpr int ANCHOR_MAX = 256;      // anchors per sample set
-constexpr int ANCHOR_TICKET0 = 16;   // FilterWs::tickets[16 .. 32): one per block of 16 anchors
 
 __device__ __forceinline__ bool seed_less(double v, int j, double bv, int bj) { return v < bv || (v == bv && j < bj); }
 
@@ -1876,6 +1881,10 @@ __device__ __forceinline__ bool seed_less(double v, int j, double bv, int bj) { 
 // norms and the product are sums of d terms ((d + 2) u relative to |a|^2, |w|^2 and |a||w| <= (|a|^2 + |w|^2) / 2 each),
 // the two additions add 3 u (|a|^2 + |w|^2): (2 d + 8) u (|a|^2 + |w|^2) in all, under half of the rho of section 2c
 // with the anchor in the sample's place.
+// The product as four partial chains and three additions: a chain holds L = 16 ceil(d / 64) <= d terms, each of the
+// three additions rounds a partial sum that |a||w| bounds, so the product is off by (L + 2 + 3) u |a||w| at the most
+// instead of (d + 2) u |a||w| -- smaller from d = 80 on (L <= d / 4 + 12), three u larger below (L = d at d = 16):
+// (2 d + 11) u (|a|^2 + |w|^2) in all at the worst, still under half of 4 (d + 16) u.  The constant stays.
 __device__ __forceinline__ double anchor_rho(int d, double aa, double yy_max) {
     return 4.0 * (double)(d + 16) * 1.1102230246251565e-16 * (aa + yy_max);
 }
@@ -1883,40 +1892,86 @@ __device__ __forceinline__ double anchor_rho(int d, double aa, double yy_max) {
 __global__ __launch_bounds__(256) void anchor_seed_kernel(const double *__restrict__ anchors, int A,
                                                           const double *__restrict__ W, int M, int d,
                                                           const double *__restrict__ ww, double *__restrict__ part_val,
-                                                          int32_t *__restrict__ part_idx, uint32_t *__restrict__ tickets,
-                                                          int32_t *__restrict__ aseed, const double *__restrict__ anorm,
-                                                          const double *__restrict__ summary, float *__restrict__ alow,
-                                                          int ldl, double *__restrict__ aup) {
+                                                          int32_t *__restrict__ part_idx, const double *__restrict__ anorm,
+                                                          float *__restrict__ alow, int ldl,
+                                                          uint32_t *__restrict__ head_ctr, double *__restrict__ head_summary) {
     // alow != nullptr (the call brings the anchors' run table, 2f): the values the arg-min is taken over are kept as
-    // certified bounds -- alow[a ldl + j] <= |a - w_j|^2 (float32, rounded down; 0 = no bound known) and aup[a] >=
-    // |a - w_seed(a)|.  anorm[a] = |a|^2 (float64), summary[2] = max |w|^2.
-    __shared__ double val_s[4][16];
+    // certified bounds -- alow[a ldl + j] <= |a - w_j|^2 (float32, rounded down; 0 = no bound known) -- and
+    // anchor_seed_min_kernel adds aup[a] >= |a - w_seed(a)|.  anorm[a] = |a|^2 (float64); max |w|^2 every workgroup forms from ww beside its chain.
+    // head_ctr != nullptr (the lean form, no slice_w_tiled_kernel in front): workgroup (0, 0) zeroes the schedule's
+    // counters and leaves max |w|^2 in head_summary[2] for anchor_seed_min_kernel and anchor_mark_kernel.
+    __shared__ double part_s[4][4][64];   // [wavefront][accumulator slot][lane]: the four partial tiles
+    __shared__ double val_s[4][16], ymax_s[4];
     __shared__ int idx_s[4][16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
-    const int npart = gridDim.x, ab = blockIdx.y * 16, jb = blockIdx.x * 64 + wave * 16;
+    const int npart = gridDim.x, ab = blockIdx.y * 16, jb = blockIdx.x * 16;
     const int jrow = min(jb + r, M - 1), arow = min(ab + r, A - 1);   // (rows past the end: loaded, never compared)
     const double *wp = W + (size_t)jrow * d + 4 * q, *ap = anchors + (size_t)arow * d + 4 * q;
-    ad4_t c = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll 4
-    for (int k = 0; k < d; k += 16) {   // d is a multiple of 16
-        const ad4_t wv = *reinterpret_cast<const ad4_t *>(wp + k), av = *reinterpret_cast<const ad4_t *>(ap + k);
+    // this wavefront's k-steps (16 features each; d is a multiple of 16): a function of d and the wavefront alone
+    const int steps = d >> 4, base = steps >> 2, rem = steps & 3;
+    const int k0 = (wave * base + min(wave, rem)) * 16, nstep = base + (wave < rem ? 1 : 0);
+    ad4_t c = {0.0, 0.0, 0.0, 0.0};   // (no step: the exact zero)
+    auto step = [&](const ad4_t &wv, const ad4_t &av) {
         c = __builtin_amdgcn_mfma_f64_16x16x4f64(wv[0], av[0], c, 0, 0, 0);
         c = __builtin_amdgcn_mfma_f64_16x16x4f64(wv[1], av[1], c, 0, 0, 0);
         c = __builtin_amdgcn_mfma_f64_16x16x4f64(wv[2], av[2], c, 0, 0, 0);
         c = __builtin_amdgcn_mfma_f64_16x16x4f64(wv[3], av[3], c, 0, 0, 0);
+    };
+    wp += k0; ap += k0;
+    int i = 0;
+    for (; i + 4 <= nstep; i += 4, wp += 64, ap += 64) {   // four steps' loads in flight, the chain in k order
+        ad4_t wv[4], av[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            wv[t] = *reinterpret_cast<const ad4_t *>(wp + 16 * t);
+            av[t] = *reinterpret_cast<const ad4_t *>(ap + 16 * t);
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) step(wv[t], av[t]);
     }
-    // element u of lane l: prototype jb + 4 u + (l >> 4), anchor ab + (l & 15)
+    {   // (the last one to three steps, their loads together as well)
+        const int rest = nstep - i;
+        ad4_t wv[3], av[3];
+#pragma unroll
+        for (int t = 0; t < 3; ++t)
+            if (t < rest) {
+                wv[t] = *reinterpret_cast<const ad4_t *>(wp + 16 * t);
+                av[t] = *reinterpret_cast<const ad4_t *>(ap + 16 * t);
+            }
+#pragma unroll
+        for (int t = 0; t < 3; ++t)
+            if (t < rest) step(wv[t], av[t]);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) part_s[wave][u][lane] = c[u];
+    // max |w|^2 (the bounds' rho; summary[2] of wtables_body, the same bits: a maximum of the same M numbers with
+    // the same fmax -- a NaN norm is dropped, an infinite one makes it infinite -- whatever the order)
+    const bool bounds = alow != nullptr;
+    if (bounds) {
+        double ym = 0.0;
+        for (int j = tid; j < M; j += 256) ym = fmax(ym, ww[j]);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) ym = fmax(ym, __shfl_xor(ym, off, 64));
+        if (lane == 0) ymax_s[wave] = ym;
+    }
+    __syncthreads();
+    const double yy_max = bounds ? fmax(fmax(ymax_s[0], ymax_s[1]), fmax(ymax_s[2], ymax_s[3])) : 0.0;
+    if (head_ctr && blockIdx.x == 0 && blockIdx.y == 0) {   // the lean form: what wtables_body does for the full one
+        if (tid < SCHED_CTR + 2 * RF_CTR + 4) head_ctr[tid] = 0u;
+        if (tid == 0) head_summary[2] = yy_max;
+    }
+    // The tile's 256 values, one per thread: wavefront w adds up accumulator slot u = w of the four partial tiles, in
+    // wavefront order -- prototype jb + 4 w + (l >> 4), anchor ab + (l & 15) for lane l.
+    const double dot = __dadd_rn(__dadd_rn(__dadd_rn(part_s[0][wave][lane], part_s[1][wave][lane]), part_s[2][wave][lane]),
+                                 part_s[3][wave][lane]);
     double bv = INFINITY;
     int bj = 0x7fffffff;
-    const bool keep = alow != nullptr && ab + r < A;
-    const double aa = keep ? anorm[ab + r] : 0.0, rho_a = keep ? anchor_rho(d, aa, summary[2]) : 0.0;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int j = jb + 4 * u + q;
-        if (j >= M) continue;
-        const double y = ww[j], v = y - 2.0 * c[u];
+    const bool keep = bounds && ab + r < A;
+    const double aa = keep ? anorm[ab + r] : 0.0, rho_a = keep ? anchor_rho(d, aa, yy_max) : 0.0;
+    if (const int j = jb + 4 * wave + q; j < M) {
+        const double y = ww[j], v = y - 2.0 * dot;
         const double key = fabs(y) < INFINITY ? (fabs(v) < INFINITY ? v : 1.7976931348623157e308) : INFINITY;
-        if (seed_less(key, j, bv, bj)) { bv = key; bj = j; }
+        bv = key; bj = j;
         if (keep) {
             // (anything that is not a positive finite number -- a row or an anchor with a NaN or an infinity among
             //  them: no bound known, and the comparison in anchor_mark_kernel keeps j)
@@ -1940,10 +1995,20 @@ __global__ __launch_bounds__(256) void anchor_seed_kernel(const double *__restri
         part_val[(size_t)(ab + tid) * npart + blockIdx.x] = bv;
         part_idx[(size_t)(ab + tid) * npart + blockIdx.x] = bj;
     }
-    if (!last_workgroup_done(tickets + ANCHOR_TICKET0 + blockIdx.y, (uint32_t)npart)) return;
-    // the anchor block's 16 anchors, 16 threads each over the prototype blocks
-    const int a = ab + (tid >> 4), sub = tid & 15;
-    bv = INFINITY; bj = 0x7fffffff;
+}
+
+// aseed[a] (and aup[a]) from the partial minima: 16 anchors per workgroup, 16 threads each over the prototype blocks.
+// A launch of its own, not the tail of the seed kernel's workgroup that finishes last: the ticket costs EVERY workgroup
+// a release fence, a write-back of its XCD's L2, and those queue up per XCD -- measured with one 16 x 16 tile per
+// workgroup: 54 us at C4 (1024 workgroups) and 65 us at C3 (2032 workgroups with two k-steps each), a quarter of a
+// microsecond per workgroup and XCD, against 44 / 29 us of the kernel this one replaced.  summary[2]: max |w|^2.
+__global__ __launch_bounds__(256) void anchor_seed_min_kernel(const double *__restrict__ part_val,
+                                                              const int32_t *__restrict__ part_idx, int npart, int A, int d,
+                                                              int32_t *__restrict__ aseed, const double *__restrict__ anorm,
+                                                              const double *__restrict__ summary, double *__restrict__ aup) {
+    const int tid = threadIdx.x, a = blockIdx.x * 16 + (tid >> 4), sub = tid & 15;
+    double bv = INFINITY;
+    int bj = 0x7fffffff;
     if (a < A)
         for (int p = sub; p < npart; p += 16) {
             const double v = part_val[(size_t)a * npart + p];
@@ -2141,7 +2206,8 @@ __global__ __launch_bounds__(256) void anchor_run_fill_kernel(const XT *__restri
 }
 
 // the candidate lists of the 128-sample workgroups by the rule above; the outputs of prune_mark_kernel.  A list
-// longer than hand_above: the workgroup's id goes to `handed` instead, for prune_mark_kernel's per-sample pass.
+// longer than hand_above: the workgroup's id goes to `handed` instead, for prune_mark_kernel's per-sample pass
+// (the lean form, handed == nullptr: the list is published like the others and the workgroup only counted).
 // ONE WAVEFRONT per 128-sample workgroup, sixteen to a block, and the block adds up its lists' bin counts and lengths
 // in LDS before it touches the schedule's counters: the work of a list is a few dependent round trips to L2 (run table
 // -> bounds of the runs' anchors -> their rows of alow) and 16 compares per lane at M = 1024, and what bounded the
@@ -2235,9 +2301,12 @@ __global__ __launch_bounds__(64 * AM_WAVES) void anchor_mark_kernel(
     if (live) {
         const uint32_t base = compact_marked(mask, nwords, lane, ulist + (size_t)group * ulist_stride, true);
         if (lane == 0) {
-            if (base > hand_above) {
+            // (handed == nullptr, the lean form: nobody is behind this kernel.  The long list is a valid candidate
+            //  set and stays as written; the workgroup is only counted, for the caller to see)
+            if (base > hand_above && handed) {
                 handed[atomicAdd(handed_len, 1ull)] = group;
             } else {
+                if (base > hand_above) atomicAdd(handed_len, 1ull);
                 ucount[group] = base;
                 atomicAdd(&bin_s[sched_bin(base)], 1u);
                 atomicAdd(&sum_s, (unsigned long long)base);
@@ -2703,7 +2772,7 @@ static size_t carve_planes(PlaneBuf *b, char *base, int64_t rows, int64_t d) {
 }
 
 struct FilterWs {
-    uint32_t *tickets;     // [0] tile score/select, [1] slice W/tables, [16 .. 32) anchor seeds: "last workgroup"
+    uint32_t *tickets;     // [0] tile score/select, [1] slice W/tables: "last workgroup"
                            // tickets (offset 0 of the workspace whatever its shape; 0 between launches, see
                            // last_workgroup_done)
     int8_t *wt, *wt_sub;   // k-tile-major digit planes of the prototypes / of the pre-pass subset
@@ -2725,7 +2794,7 @@ struct FilterWs {
     float *gap;        // Mg x Mg lower bounds of the squared distances between prototypes (2c); M <= PRUNE_MAX_M
     int32_t *retry;    // nb: workgroups of the pruning form to be re-seeded
     int32_t *aseed;    // ANCHOR_MAX: the nearest prototype of every anchor (2e)
-    double *apart_val; // ANCHOR_MAX x ceil(M / 64): its minimum per block of 64 prototypes, value ...
+    double *apart_val; // ANCHOR_MAX x ceil(M / 16): its minimum per block of 16 prototypes, value ...
     int32_t *apart_idx;  // ... and index
     float *alow;       // ANCHOR_MAX x Mg: lower bounds of the squared distances from the anchors to the prototypes (2f)
     double *aup;       // ANCHOR_MAX: upper bounds of the distances from the anchors to their seeds
@@ -2779,7 +2848,7 @@ static size_t carve_filter(FilterWs *out, char *base, int64_t N, int64_t d, int6
     if (M > PRUNE_MAX_M) f.gap = nullptr;
     take(f.retry, (size_t)nb * 4); take(f.nnub, (size_t)Mg * 4);
     take(f.aseed, (size_t)ANCHOR_MAX * 4);
-    take(f.apart_val, (size_t)ANCHOR_MAX * (Mg / 64) * 8); take(f.apart_idx, (size_t)ANCHOR_MAX * (Mg / 64) * 4);
+    take(f.apart_val, (size_t)ANCHOR_MAX * (Mg / 16) * 8); take(f.apart_idx, (size_t)ANCHOR_MAX * (Mg / 16) * 4);
     take(f.alow, M <= PRUNE_MAX_M ? (size_t)ANCHOR_MAX * Mg * 4 : 0); take(f.aup, (size_t)ANCHOR_MAX * 8);
     take(f.handed, (size_t)nb * 4);
     f.Mg = Mg; f.nb = nb; f.Mpad = Mpad;
@@ -3046,7 +3115,8 @@ struct FilterRun {
         hipLaunchKernelGGL(anchor_mark_kernel, dim3((unsigned)((f.nb + AM_WAVES - 1) / AM_WAVES)), dim3(64 * AM_WAVES), 0, s,
                            t.run_start, t.run_anchor, t.run_R, t.run_xx, (int)t.cap, c.n_anchors, f.aseed, f.aup, f.alow,
                            (int)f.Mg, f.summary, (int)c.M, d, (int)f.nb, f.ulist, (int)f.Mpad, f.ucount, f.sched_ctr,
-                           reinterpret_cast<unsigned long long *>(f.sched_ctr + SCHED_SUM), f.handed, handed_len(), long_above());
+                           reinterpret_cast<unsigned long long *>(f.sched_ctr + SCHED_SUM),
+                           fm.lists_only ? (int32_t *)nullptr : f.handed, handed_len(), long_above());
     }
 
     // the gaps between the prototypes (pruning form): they need the digit planes of W and nothing of the samples
@@ -3127,12 +3197,19 @@ struct FilterRun {
             DBGSOM_HIP_CHECK(hipEventRecord(side.gap_done, side.stream));
             gap_aside = true;
         }
-        hipLaunchKernelGGL(anchor_seed_kernel, dim3((unsigned)(f.Mg / 64), (unsigned)((c.n_anchors + 15) / 16)), dim3(256),
-                           0, s, c.anchors, c.n_anchors, c.W, (int)c.M, d, c.ww, f.apart_val, f.apart_idx, f.tickets, f.aseed,
-                           run_anorm(), f.summary, fm.anchor_mark ? f.alow : nullptr, (int)f.Mg,
+        // (the lean form has no slice_w_tiled_kernel in front: this kernel zeroes the schedule's counters and leaves
+        //  summary[2], see there)
+        hipLaunchKernelGGL(anchor_seed_kernel, dim3((unsigned)((c.M + 15) / 16), (unsigned)((c.n_anchors + 15) / 16)), dim3(256),
+                           0, s, c.anchors, c.n_anchors, c.W, (int)c.M, d, c.ww, f.apart_val, f.apart_idx, run_anorm(),
+                           fm.anchor_mark ? f.alow : nullptr, (int)f.Mg, fm.lists_only ? f.sched_ctr : nullptr,
+                           fm.lists_only ? f.summary : nullptr);
+        hipLaunchKernelGGL(anchor_seed_min_kernel, dim3((unsigned)((c.n_anchors + 15) / 16)), dim3(256), 0, s, f.apart_val,
+                           f.apart_idx, (int)((c.M + 15) / 16), c.n_anchors, d, f.aseed, run_anorm(), f.summary,
                            fm.anchor_mark ? f.aup : nullptr);
-        // (the gather stays: the per-sample pass of the handed workgroups and the diagnostics read f.seed)
-        hipLaunchKernelGGL(anchor_gather_kernel, dim3(seed_grid()), dim3(256), 0, s, f.aseed, c.anchor_of, c.N, f.seed);
+        // (the gather: the per-sample pass of the handed workgroups and the diagnostics read f.seed; the lean form
+        //  has no per-sample pass)
+        if (!fm.lists_only)
+            hipLaunchKernelGGL(anchor_gather_kernel, dim3(seed_grid()), dim3(256), 0, s, f.aseed, c.anchor_of, c.N, f.seed);
         aux.timer.mark(2, s);
         seeds = f.seed;
         return DBGSOM_OK;
@@ -3353,7 +3430,7 @@ int dbgsom::launch_bmu_filtered(const FilteredCall &call) {
     carve_filter(&r.f, (char *)call.ws, call.N, call.d, call.M);
     StageTimer &timer = aux.timer;
     timer.mark(0, r.s);
-    r.prepare_prototypes();
+    if (form.w_planes) r.prepare_prototypes();
     timer.mark(1, r.s);
     int rc = r.seed_and_sort();
     if (rc != DBGSOM_OK) return rc;

@@ -56,6 +56,12 @@ struct __attribute__((visibility("hidden"))) FilterForm {
     // lists that leaves long.  Everything else -- k = 2, hints, the counting-only probe, anchors without a table --
     // takes prune_mark_kernel over the whole grid.
     bool anchor_mark = false;
+    // DBGSOM_ANCHOR_LISTS_ONLY on such a call without the re-seeding and without the refinement: the lean form.
+    // anchor_mark_kernel's lists are the lists, long ones included (each is a valid candidate set; the workgroup is
+    // only counted as handed over), and nothing that serves the per-sample pass alone is made: no digit planes of
+    // W (w_planes), no gap table (gap_nb = 0), no per-sample seeds.  Ignored everywhere else.
+    bool lists_only = false;
+    bool w_planes = true;   // the call slices W into digit planes (slice_w_tiled_kernel and its tables)
     int gap_nb = 0;  // proto_gap_kernel<gap_nb> (prune, prune_probe): 2 = 64 x 64 tiles, 1 = 32 x 32; 0 = none
     // per-sample refinement (2d): the small tile of its list-length classes, 0 = only the largest
     bool refine = false;
@@ -83,6 +89,7 @@ struct __attribute__((visibility("hidden"))) FilterForm {
     };
     int prune_passes(Pass out[4]) const {
         int n = 0;
+        if (lists_only) { out[0] = PASS_ANCHOR_MARK; return 1; }
         if (!gap_nb) return 0;
         if (anchor_mark) out[n++] = PASS_ANCHOR_MARK;
         out[n++] = anchor_mark ? PASS_PRUNE_HANDED : PASS_PRUNE_GRID;
@@ -92,7 +99,8 @@ struct __attribute__((visibility("hidden"))) FilterForm {
     static bool reports_long_lists(Pass p) { return p == PASS_PRUNE_GRID || p == PASS_PRUNE_HANDED; }
 
     // nullptr, or why the call is rejected (nothing of *this is then meaningful).  flags: FilteredCall::seed_stride,
-    // the stride with DBGSOM_SEED_FULL / DBGSOM_PRUNE / DBGSOM_PRUNE_PROBE / DBGSOM_PRUNE_RETRY OR-ed in;
+    // the stride with DBGSOM_SEED_FULL / DBGSOM_PRUNE / DBGSOM_PRUNE_PROBE / DBGSOM_PRUNE_RETRY /
+    // DBGSOM_ANCHOR_LISTS_ONLY OR-ed in;
     // has_hint: the caller brings previous winners (no seed pre-pass).  The shape itself (N, d, M in range) is
     // the launcher's to check.  has_anchors / has_runs: the call brings anchor buckets / their run table.
     const char *resolve(int flags, int planes, int k, int refine_rows, bool defer, int64_t N, int64_t d, int64_t M,
@@ -106,7 +114,7 @@ struct __attribute__((visibility("hidden"))) FilterForm {
         if (!(!defer || (refine_rows > 0 && M < 0xffff))) return "deferred distances need the refinement";
         if (!(!k2 || (prune && refine_rows == 0 && M >= 2)))
             return "k = 2 needs the pruning form (DBGSOM_PRUNE, M <= 8192) without the refinement";
-        seed_stride = flags & ~(DBGSOM_PRUNE | DBGSOM_PRUNE_PROBE | DBGSOM_PRUNE_RETRY);
+        seed_stride = flags & ~(DBGSOM_PRUNE | DBGSOM_PRUNE_PROBE | DBGSOM_PRUNE_RETRY | DBGSOM_ANCHOR_LISTS_ONLY);
         seed_stride = seed_full ? 1 : seed_stride;
         if (!(seed_stride >= 0 && seed_stride <= 64)) return "seed_stride outside [0, 64]";
         if (!(planes >= 0 && planes <= 3)) return "sweep_planes must be 0 .. 3";
@@ -140,6 +148,10 @@ struct __attribute__((visibility("hidden"))) FilterForm {
         const int64_t gt = ((M + 63) / 64 * 64) / 64;
         gap_nb = (prune || prune_probe) ? (gt * gt >= 1024 ? 2 : 1) : 0;
         refine = refine_rows > 0;
+        // (the re-seeding pass and refine_i8_kernel read the planes of W: no lean form beside either)
+        lists_only = (flags & DBGSOM_ANCHOR_LISTS_ONLY) != 0 && anchor_mark && !prune_retry && !refine && k == 1;
+        w_planes = !lists_only;
+        if (lists_only) gap_nb = 0;
         rows0 = refine_rows <= 32 ? 32 : (refine_rows <= 64 ? 64 : (refine_rows <= 128 ? 128 : 0));
         const int64_t nb = (N + 127) / 128;
         exact = k2 ? EXACT_K2 : (refine ? EXACT_BESIDE_REFINE : (nb <= 1024 ? EXACT_SPLIT : EXACT_ALL));

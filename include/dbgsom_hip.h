@@ -64,6 +64,14 @@ extern "C" {
  * whose pruned lists come out longer than max(96, M / 8) -- their seeds were poor -- are seeded again
  * against every prototype and pruned again (two more short launches) */
 #define DBGSOM_PRUNE_RETRY 0x800
+/* with DBGSOM_PRUNE on a stateless k = 1 call that brings anchor buckets and their run table
+ * (dbgsom_bmu_filtered_anchor_runs), without DBGSOM_PRUNE_RETRY and without DBGSOM_REFINE: the lean form.  The lists
+ * written from the anchors' bounds are final, long ones included (each is a valid candidate set: same winners, same
+ * distances, only longer lists for those workgroups, which dbgsom_bmu_filtered_anchor_bounds still counts as handed
+ * over), and the call makes nothing that only the per-sample pass reads: no digit planes of W, no gap table, no
+ * per-sample seeds (dbgsom_bmu_filtered_gaps and the seed_host of dbgsom_bmu_filtered_anchor_seeds are then not
+ * those of this call).  Ignored on every other call. */
+#define DBGSOM_ANCHOR_LISTS_ONLY 0x2000
 /* per-SAMPLE refinement in front of the exact stage: the four int8 digit products of the top two digit
  * planes over each workgroup's candidate list leave every sample the few prototypes a certified bound
  * cannot separate (<= 4, else its whole list); the samples are bucketed again by their likely winner and
@@ -399,7 +407,7 @@ int dbgsom_ctx_destroy(dbgsom_ctx *ctx);
  * call; 0: the pre-pass.  Results do not depend on it).
  * Readable besides those: "resident_csr", "resident_nnz", "refined", "defer_epochs" (epochs whose sums kernel evaluated distances), "shard_epochs", "n_samples", "features", "padded_features", "prototypes",
  * "planes_cached", "planes_used" / "planes_next" (0 = no sweep), "seed_mode", "prune_retry", "hint_valid",
- * "filter_backoff", "plane_hold", "device_bytes", "anchor_builds" (anchor buckets built so far), "anchor_searches" (searches seeded from them), "anchor_state" (of
+ * "filter_backoff", "plane_hold", "device_bytes", "anchor_builds" (anchor buckets built so far), "anchor_searches" (searches seeded from them), "lean_searches" (of those, epochs in the lean form DBGSOM_ANCHOR_LISTS_ONLY), "anchor_state" (of
  * the resident samples: 0 none, 1 in use, 2 dropped -- their lists came out longer than the pre-pass's), and the
  * PCIe traffic of the prototypes since the context was created: "w_upload_calls" / "w_upload_bytes"
  * (whole matrices host -> HBM), "w_download_calls" / "w_download_bytes", "w_row_writes", "w_row_reads";
