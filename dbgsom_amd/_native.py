@@ -155,6 +155,11 @@ SIGNATURES = {
     "dbgsom_ctx_kneighbors_query_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _ci, _vp, _vp]),
     "dbgsom_ctx_kneighbors_query_csr": (_ci, [_vp, _vp, _vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _ci, _vp, _vp]),
     "dbgsom_ctx_kneighbors_query_masked": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _ci, _vp, _vp]),
+    "dbgsom_energy_rows": (_ci, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "dbgsom_neighborhood_energy": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "dbgsom_ctx_distortion_query": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "dbgsom_ctx_distortion_query_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "dbgsom_ctx_distortion_query_csr": (_ci, [_vp, _vp, _vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
     "dbgsom_accumulate_masked_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "dbgsom_accumulate_masked": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "dbgsom_smooth_masked_workspace_bytes": (_sz, [_i64, _i64]),

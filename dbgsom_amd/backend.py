@@ -118,6 +118,15 @@ class HotPathBackend:
         ``bmu_masked``."""
         raise NotImplementedError
 
+    def neighborhood_energy(self, W, H, X):
+        """The distortion measure of every row of X -> (e, bmu), both (rows of X,), float64 and int64: ``bmu`` is the
+        index of the smallest ``(r, j)`` in lexicographic order among ``r < inf``, r the squared value of
+        ``bmu(W, k, X=X)``'s arithmetic (``kneighbors``' first index), and ``e = sum_j H[bmu, j] * r_j`` with H the
+        (rows of W, rows of W) float64 neighbourhood factors.  The order of the sum is fixed (include/dbgsom_hip.h):
+        64 strided partials of rounded products, ascending, then six xor rounds.  A row without an ``r`` below +inf
+        has (NaN, -1).  X as for ``distances``; the results are NumPy arrays, next to X for a device array."""
+        raise NotImplementedError
+
     # -- metric="manhattan": dist(x, w) = sum_k |x_k - w_k| in float64, k ascending, one accumulator per pair; float32
     # rows widened exactly first; no square root, no clamp; winners by (dist, index); a pair whose distance is not
     # below +inf is never reported (index -1, distance inf).  X: a dense host array or a device array.
@@ -1031,6 +1040,46 @@ class HipBackend(HotPathBackend):
         """The k nearest prototypes over the observed entries of every row on the device (csrc/kneighbors.hip on the
         masked chain of csrc/distances.hip), in chunks of ``distances_chunk_rows`` rows."""
         return self._metric_kneighbors("masked", W, k, X)
+
+    # -- the distortion measure of a query -------------------------------------------------------------
+    def neighborhood_energy(self, W, H, X):
+        """The distortion measure of every row (csrc/distortion.hip): the squared distances of a slab of
+        ``kneighbors_slab_rows`` rows stay on the device, the energy kernel reads them back from cache against row
+        ``bmu`` of H, and only (rows,) values and units are the result.  H goes up once per call.  Host rows go up
+        in chunks of ``distances_chunk_rows`` rows; CSR rows are expanded on the device chunk by chunk; for rows in
+        HBM both results are arrays on their device that the kernel writes itself
+        (dbgsom_ctx_distortion_query_device)."""
+        W64 = np.ascontiguousarray(W, dtype=np.float64)
+        if W64.ndim != 2 or len(X.shape) != 2 or W64.shape[1] != X.shape[1]:
+            raise ValueError("prototype / sample feature mismatch")
+        M, N = W64.shape[0], int(X.shape[0])
+        H64 = np.ascontiguousarray(H, dtype=np.float64)
+        if H64.shape != (M, M):
+            raise ValueError(f"H must be ({M}, {M}), one row per prototype, got {H64.shape}")
+        if is_device_array(X):
+            code, N, d, ldx = self._device_rows(X)
+            e, bmu = device_empty(X, (N,), "float64"), device_empty(X, (N,), "int64")
+            if N:
+                self._producer_done(X)
+                self._call("dbgsom_ctx_distortion_query_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code, N, d,
+                           ldx, W64.ctypes.data, M, H64.ctypes.data, ctypes.c_void_p(bmu.data_ptr()),
+                           ctypes.c_void_p(e.data_ptr()))
+            return e, bmu
+        e, bmu = np.empty(N, dtype=np.float64), np.empty(N, dtype=np.int64)
+        if N == 0:
+            return e, bmu
+        if is_sparse(X):
+            csr, indptr, indices, data = canonical_csr(X)
+            self._call("dbgsom_ctx_distortion_query_csr", self._ctx, indptr.ctypes.data, indices.ctypes.data,
+                       data.ctypes.data, _x_dtype_code(data.dtype), N, csr.shape[1], data.size, W64.ctypes.data, M,
+                       H64.ctypes.data, bmu.ctypes.data, e.ctypes.data)
+            return e, bmu
+        X = np.ascontiguousarray(X)
+        if X.dtype not in (np.float32, np.float64):
+            X = X.astype(np.float64)
+        self._call("dbgsom_ctx_distortion_query", self._ctx, X.ctypes.data, _x_dtype_code(X.dtype), N, X.shape[1],
+                   W64.ctypes.data, M, H64.ctypes.data, bmu.ctypes.data, e.ctypes.data)
+        return e, bmu
 
     # -- metric="manhattan" (csrc/manhattan.hip) --------------------------------------------------------
     _manhattan = property(lambda self: self._metric == "manhattan")

@@ -1192,6 +1192,71 @@ class BaseSom(BaseEstimator):
         # (a device array's distances go to the host for the mean: NumPy's pairwise sum, bit for bit -- N x 8 bytes)
         return float(np.mean(self._host(distances)))
 
+    def _neighborhood_factors(self, sigma) -> np.ndarray:
+        """``H = exp(-(hop^2 / (2 sigma^2)))`` on the host, hop the hop distances of the fitted lattice in the order of
+        ``neurons_`` (``inf`` between disconnected components: h = 0).  ``sigma=None``: the bandwidth of the last
+        training epoch."""
+        if sigma is None:
+            sigma = self._calculate_current_sigma()
+        elif isinstance(sigma, (bool, np.bool_)) or not isinstance(sigma, (numbers.Real, np.floating, np.integer)):
+            raise ValueError(f"sigma must be None or a finite float > 0, got {sigma!r}")
+        sigma = float(sigma)
+        if not (np.isfinite(sigma) and sigma > 0.0):
+            raise ValueError(f"sigma must be None or a finite float > 0, got {sigma!r}")
+        hop = self._distance_matrix   # (of the map as it is after the dead units were removed: _sync_views)
+        if hop.shape != (len(self.weights_),) * 2:
+            hop = self._lattice.hop_distances()
+        return np.exp(-(hop ** 2 / (2 * sigma ** 2)))
+
+    def sample_distortion(self, X, sigma=None):
+        """The SOM distortion measure row by row: ``(e, bmu)``, both ``(n_samples,)``, float64 and int64, with
+        ``e_i = sum_j h(b_i, j) * ||x_i - w_j||^2``, ``b_i`` the best matching unit of row ``i`` (``predict``'s
+        unit for ``SomVQ``, an index into ``weights_``) and ``h(b, j) = exp(-(hop(b, j)^2 / (2 sigma^2)))`` over the
+        hop distances of the lattice -- the quantity the batch rule descends on (Kohonen's energy with a fixed
+        neighbourhood; SOM Toolbox ``som_distortion``).  Large ``e`` at small quantization error marks rows whose
+        unit's lattice neighbours are far away in the input space: where the map is folded.
+
+        ``sigma=None`` is the bandwidth of the last training epoch, otherwise a finite float > 0.  The squared
+        distances are those of the best-matching-unit search's own arithmetic, ``r_ij = max((|x_i|^2 + (-2 <x_i,
+        w_j>)) + |w_j|^2, 0)``, without float32 rounding, and the order of the sum is fixed (64 strided partials of
+        rounded products, then six xor rounds), so the result does not depend on chunks, slabs or where X lives.
+        H is computed on the host and uploaded once per call (8 M^2 bytes); the N x M matrix is never held.
+
+        X is what ``kneighbors`` takes under the Euclidean metric: a dense array (NumPy results), a tensor on the
+        estimator's GPU (tensors on X's device that the GPU writes itself; X never touches the host), scipy sparse
+        rows (the dense call's result on ``X.toarray()``).  Refused with a ``ValueError``: ``metric="manhattan"`` /
+        ``"cosine"`` (the measure is defined on squared Euclidean distances), rows with NaN (also under
+        ``missing_values``: impute them first), a feature-count mismatch.  Only this map's prototypes are used (not
+        the child maps of vertical growth); the call is local to the process."""
+        check_is_fitted(self)
+        kind = self._search_metric()
+        if kind:
+            self._refuse_metric(kind, "sample_distortion / calculate_distortion",
+                                "the measure is defined on squared Euclidean distances")
+        H = self._neighborhood_factors(sigma)
+        if not is_device_array(X) and not is_sparse(X) and np.ndim(X) == 2 and np.shape(X)[0] == 0:
+            X = check_array(X, dtype=[np.float64, np.float32], ensure_min_samples=0)   # (no rows: no launch)
+        else:
+            X = self._check_query(X)
+        if X.shape[1] != self.n_features_in_:
+            raise ValueError(f"X has {X.shape[1]} features, but {type(self).__name__} is expecting "
+                             f"{self.n_features_in_} features as input")
+        if isinstance(X, np.ndarray) and np.isnan(X).any():   # (passed _check_query: missing_values is set)
+            raise ValueError(f"X holds NaN: the distortion measure is not defined on rows with missing entries "
+                             f"(missing_values={self.missing_values!r}); impute them first (impute(X))")
+        if X.shape[0] == 0:
+            return np.empty(0, dtype=np.float64), np.empty(0, dtype=np.int64)
+        return self._engine().neighborhood_energy(self.weights_, H, X)
+
+    def calculate_distortion(self, X, sigma=None) -> float:
+        """The SOM distortion measure of X: the mean of ``sample_distortion(X, sigma)[0]``.  The per-row values come
+        to the host (8 bytes per row) and NumPy sums them, so a host array and a tensor holding the same rows give
+        the same float."""
+        e, _ = self.sample_distortion(X, sigma)
+        if e.shape[0] == 0:
+            check_array(X, dtype=[np.float64, np.float32])   # (no rows: refused in check_array's words, as a mean is)
+        return float(np.sum(self._host(e))) / e.shape[0]
+
     def _calculate_topographic_error(self, X) -> float:
         """Fraction of samples whose two best matching units are not lattice neighbours."""
         if self._is_resident(X):

@@ -185,6 +185,8 @@ int launch_topk_rows(const double *R, int64_t N, int64_t M, int64_t ldr, int k, 
 int launch_topk_rows_plain(const double *R, int64_t N, int64_t M, int64_t ldr, int k, int64_t *idx, double *dist,
                            hipStream_t s);   // (no square root behind the selection: R holds distances)
 int64_t kneighbors_slab_rows(int64_t N, int64_t M, int64_t slab_rows);
+// rows of a slab are M rounded up to even apart, so that every row starts on 16 bytes
+inline int64_t kneighbors_slab_ld(int64_t M) { return M + (M & 1); }
 size_t kneighbors_workspace_bytes(int64_t N, int64_t M, int64_t slab_rows);
 size_t kneighbors_masked_workspace_bytes(int x_dtype, int64_t N, int64_t d, int64_t M, int64_t slab_rows);
 int launch_kneighbors(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx, const double *W,
@@ -193,6 +195,13 @@ int launch_kneighbors(const void *X, int x_dtype, int64_t N, int64_t d, int64_t 
 int launch_kneighbors_masked_rows(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, int k,
                                   int64_t slab_rows, int64_t *idx, double *dist, void *ws, size_t ws_bytes,
                                   hipStream_t s);
+// the distortion measure of every row (distortion.hip): b = the row's best matching unit, e = sum_j H[b, j] r_j, on a
+// matrix of squared values, and the driver over slabs of rows (the slabs and the workspace of launch_kneighbors)
+int launch_energy_rows(const double *R, int64_t N, int64_t M, int64_t ldr, const double *H, int64_t ldh, int64_t *bmu,
+                       double *e, hipStream_t s);
+int launch_neighborhood_energy(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx,
+                               const double *W, int64_t M, const double *ww, const double *H, int64_t ldh,
+                               int64_t slab_rows, int64_t *bmu, double *e, void *ws, size_t ws_bytes, hipStream_t s);
 // metric="manhattan" (manhattan.hip): sum_k |x_k - w_k| in float64, F32 / F64 rows; search, matrix and selection read
 // the transposed float64 prototypes launch_manhattan_weights leaves in front of the workspace
 size_t bmu_manhattan_workspace_bytes(int x_dtype, int64_t N, int64_t d, int64_t M);

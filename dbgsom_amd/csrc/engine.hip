@@ -279,6 +279,9 @@ struct dbgsom_ctx {
     // the slab at 64 MiB), the slab (masked rows: the masked search's workspace in front of it) and a chunk's result
     int64_t kneighbors_slab_rows = 0;
     DevBuf kn_ws, kn_idx, kn_dist;
+    // the distortion measure of a query (distortion.hip): the M x M neighbourhood factors of the call (the slab and a
+    // chunk's staged result are kn_ws, kn_idx and kn_dist)
+    DevBuf de_h;
     // The resident rows have missing entries (NaN): option "incomplete", set after a load and cleared by the next one.
     // What depends on the rows alone is made when the option is set, once per load: n_obs per row (mf_nobs) and, for
     // float32 rows, their float64 copy (mf_x64, N x d x 8 bytes of HBM).  The ordinary calls then refuse to compute
@@ -1255,7 +1258,7 @@ int dbgsom_ctx_create(int device, dbgsom_ctx **out) {
      &(c)->shard_gather, &(c)->sw, &(c)->wh_order, &(c)->wh_ws, &(c)->sc_ws, &(c)->sc_x, &(c)->sc_w, &(c)->sc_p, &(c)->sc_code, &(c)->sc_proba, &(c)->sc_cnt, &(c)->wt,  \
      &(c)->mk_ws, &(c)->mk_x, &(c)->mk_w, &(c)->mk_idx, &(c)->mk_dist, &(c)->mf_nobs, &(c)->mf_x64, &(c)->mf_wt, &(c)->mf_w,   \
      &(c)->mf_wn, &(c)->mf_idx, &(c)->mf_dist, &(c)->mf_kw, &(c)->mf_sums, &(c)->mf_acc_ws, &(c)->mf_sm_ws, &(c)->mf_scal, \
-     &(c)->pd_out, &(c)->kn_ws, &(c)->kn_idx, &(c)->kn_dist, &(c)->l1_ws, &(c)->cos_u, &(c)->cos_v}
+     &(c)->pd_out, &(c)->kn_ws, &(c)->kn_idx, &(c)->kn_dist, &(c)->de_h, &(c)->l1_ws, &(c)->cos_u, &(c)->cos_v}
 
 int dbgsom_ctx_destroy(dbgsom_ctx *c) {
     if (!c) return DBGSOM_OK;
@@ -1846,7 +1849,7 @@ int dbgsom_ctx_bmu_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const in
 // prototypes under every metric, and the search itself over rows with missing entries and under metric="manhattan"
 // and metric="cosine" -- is one of two loops over chunks of rows:
 //   raw_rows_query     masked / Manhattan / cosine: kernels that read the rows as they are stored (any row pitch)
-//   placed_rows_query  Euclidean distances and neighbours: the rows go through the query placement first
+//   placed_rows_query  Euclidean distances, neighbours and distortion: the rows go through the query placement first
 // A chunk of host rows goes up, its result is staged on the device and comes down behind the kernel; rows in HBM are
 // read where they are and the kernels write the caller's device arrays.  Both drivers synchronise before they return,
 // on error too (W_host and the rows are pageable), and end on drop_large_query_scratch.  The exported calls further
@@ -1854,7 +1857,7 @@ int dbgsom_ctx_bmu_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const in
 // ------------------------------------------------------------------------------------------
 namespace {
 
-enum QueryOp { Q_BMU, Q_DISTANCES, Q_KNEIGHBORS };
+enum QueryOp { Q_BMU, Q_DISTANCES, Q_KNEIGHBORS, Q_DISTORTION };
 enum RowsForm { ROWS_MASKED, ROWS_MANHATTAN, ROWS_COSINE };
 
 // DBGSOM_REQUIRE under the name of the exported call `fn` (checks shared by several of them)
@@ -1881,7 +1884,7 @@ int query_args(const char *fn, const dbgsom_ctx *c, QueryOp op, int x_dtype, boo
     }
     REQUIRE_FN(fn, Nq >= 0 && Nq < 0x7fffffff && d >= 1 && d <= 0x7fffffff, "bad sample shape");
     REQUIRE_FN(fn, M >= 1 && M <= DBGSOM_MAX_PROTOTYPES, "need 1 <= M <= DBGSOM_MAX_PROTOTYPES");
-    if (op == Q_DISTANCES) return DBGSOM_OK;
+    if (op == Q_DISTANCES || op == Q_DISTORTION) return DBGSOM_OK;
     REQUIRE_FN(fn, k >= 1 && k <= M, "need 1 <= k <= M");
     REQUIRE_FN(fn, k <= DBGSOM_MAX_NEIGHBORS, "k must be <= DBGSOM_MAX_NEIGHBORS");
     return DBGSOM_OK;
@@ -1909,6 +1912,7 @@ void drop_large_query_scratch(dbgsom_ctx *c) {
     }
     if (c->pd_out.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->pd_out.release();
     if (c->kn_ws.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->kn_ws.release();
+    if (c->de_h.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->de_h.release();
 }
 
 // the end of both drivers
@@ -2086,14 +2090,16 @@ struct CsrHost {
 // Host rows: in chunks of distances_chunk rows, each placed, its result staged (pd_out; kn_idx / kn_dist) and copied
 // down.  Rows in HBM: placed whole, and the kernels write the caller's device arrays (the matrix with rows ldo apart).
 // CSR rows (csr != nullptr): the three arrays go up whole, and chunks of rows are expanded into the dense rows the
-// kernels read.
+// kernels read.  Q_DISTORTION (csrc/distortion.hip; k = 1): the neighbours' slab and staging with the energy kernel
+// behind the product; idx_out / dist_out take a row's unit and its e, and H_host (M x M) goes up once per call.
 int placed_rows_query(dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHost *csr, int x_dtype, int64_t Nq, int64_t d,
-                      const double *W_host, int64_t M, int k, int64_t *idx_out, double *dist_out, int64_t ldo) {
+                      const double *W_host, int64_t M, int k, int64_t *idx_out, double *dist_out, int64_t ldo,
+                      const double *H_host) {
     Samples &s = c->xq;
     DevBuf Wq, wwq;
     const int64_t dp = pad16(d);
     const size_t es = dtype_size(x_dtype);
-    const bool staged = !q.on_device, knn = op == Q_KNEIGHBORS;
+    const bool staged = !q.on_device, knn = op != Q_DISTANCES;   // (knn: a slab per chunk, k values per row and array)
     const int64_t chunk = staged ? distances_chunk(c, Nq, M, dp * (int64_t)es) : Nq;
     const int64_t per_row = knn ? k : M;   // values of a row's result
     int rc = DBGSOM_OK;
@@ -2105,6 +2111,12 @@ int placed_rows_query(dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHo
             if ((rc = s.own.reserve((size_t)chunk * dp * es))) break;
         }
         if ((rc = place_query_weights(c, Wq, wwq, W_host, M, d, dp))) break;
+        if (op == Q_DISTORTION) {
+            if ((rc = c->de_h.reserve((size_t)M * M * 8))) break;
+            const hipError_t e = hipMemcpyAsync(c->de_h.p, H_host, (size_t)M * M * 8, hipMemcpyHostToDevice, c->stream);
+            if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
+            c->x_up((size_t)M * M * 8);
+        }
         if (knn) {
             if ((rc = c->kn_ws.reserve(kneighbors_workspace_bytes(chunk, M, c->kneighbors_slab_rows)))) break;
             if (staged && (rc = c->kn_idx.reserve((size_t)chunk * k * 8))) break;
@@ -2128,7 +2140,11 @@ int placed_rows_query(dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHo
             if (rc) break;
             int64_t *idx = staged ? c->kn_idx.as<int64_t>() : idx_out;
             double *res = !staged ? dist_out : (knn ? c->kn_dist.as<double>() : c->pd_out.as<double>());
-            if (knn)
+            if (op == Q_DISTORTION)
+                rc = launch_neighborhood_energy(s.Xb, s.bdtype, n, dp, dp, s.xx.as<double>(), Wq.as<double>(), M,
+                                                wwq.as<double>(), c->de_h.as<double>(), M, c->kneighbors_slab_rows, idx, res,
+                                                c->kn_ws.p, c->kn_ws.cap, c->stream);
+            else if (knn)
                 rc = launch_kneighbors(s.Xb, s.bdtype, n, dp, dp, s.xx.as<double>(), Wq.as<double>(), M, wwq.as<double>(), k,
                                        c->kneighbors_slab_rows, idx, res, c->kn_ws.p, c->kn_ws.cap, c->stream);
             else
@@ -2179,7 +2195,8 @@ int raw_rows_checked(const char *fn, dbgsom_ctx *c, QueryOp op, RowsForm form, c
 
 // the Euclidean distance matrix and k nearest prototypes of dense rows (csr == nullptr) or host CSR rows
 int placed_rows_checked(const char *fn, dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHost *csr, int x_dtype, int64_t Nq,
-                        int64_t d, const double *W_host, int64_t M, int k, int64_t *idx_out, double *dist_out, int64_t ldo) {
+                        int64_t d, const double *W_host, int64_t M, int k, int64_t *idx_out, double *dist_out, int64_t ldo,
+                        const double *H_host = nullptr) {
     TRY(query_args(fn, c, op, x_dtype, csr != nullptr, Nq, d, M, k));
     if (q.on_device) REQUIRE_FN(fn, q.ldx >= d, "ldx must be >= d");
     if (op == Q_DISTANCES) REQUIRE_FN(fn, ldo >= M, "ldo must be >= M");
@@ -2189,8 +2206,9 @@ int placed_rows_checked(const char *fn, dbgsom_ctx *c, QueryOp op, const QueryRo
     }
     if (Nq == 0) return DBGSOM_OK;
     REQUIRE_FN(fn, (csr || q.p) && W_host && (op == Q_DISTANCES || idx_out) && dist_out, "null pointer");
+    if (op == Q_DISTORTION) REQUIRE_FN(fn, H_host, "null pointer");
     SET_DEVICE(c);
-    return placed_rows_query(c, op, q, csr, x_dtype, Nq, d, W_host, M, k, idx_out, dist_out, ldo);
+    return placed_rows_query(c, op, q, csr, x_dtype, Nq, d, W_host, M, k, idx_out, dist_out, ldo, H_host);
 }
 
 }  // namespace
@@ -2258,6 +2276,31 @@ int dbgsom_ctx_kneighbors_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, c
     const CsrHost csr{indptr_host, indices_host, nnz};
     return placed_rows_checked(__func__, c, Q_KNEIGHBORS, QueryRows{data_host, false, d}, &csr, x_dtype, Nq, d, W_host, M,
                                k, idx_host, dist_host, 0);
+}
+
+// ------------------------------------------------------------------------------------------
+// the distortion measure of a query: csrc/distortion.hip
+// ------------------------------------------------------------------------------------------
+int dbgsom_ctx_distortion_query(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                const double *W_host, int64_t M, const double *H_host, int64_t *bmu_host, double *e_host) {
+    return placed_rows_checked(__func__, c, Q_DISTORTION, QueryRows{Xq_host, false, d}, nullptr, x_dtype, Nq, d, W_host, M,
+                               1, bmu_host, e_host, 0, H_host);
+}
+
+int dbgsom_ctx_distortion_query_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d, int64_t ldx,
+                                       const double *W_host, int64_t M, const double *H_host, int64_t *bmu_dev,
+                                       double *e_dev) {
+    return placed_rows_checked(__func__, c, Q_DISTORTION, QueryRows{Xq_dev, true, ldx}, nullptr, x_dtype, Nq, d, W_host, M,
+                               1, bmu_dev, e_dev, 0, H_host);
+}
+
+int dbgsom_ctx_distortion_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const int32_t *indices_host,
+                                    const void *data_host, int x_dtype, int64_t Nq, int64_t d, int64_t nnz,
+                                    const double *W_host, int64_t M, const double *H_host, int64_t *bmu_host,
+                                    double *e_host) {
+    const CsrHost csr{indptr_host, indices_host, nnz};
+    return placed_rows_checked(__func__, c, Q_DISTORTION, QueryRows{data_host, false, d}, &csr, x_dtype, Nq, d, W_host, M,
+                               1, bmu_host, e_host, 0, H_host);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -22,6 +22,7 @@
 #include <algorithm>
 
 #include "bmu_common.h"
+#include "wave_lex.h"
 
 #define TRY_STATUS(expr) do { int _rc = (expr); if (_rc != DBGSOM_OK) return _rc; } while (0)
 
@@ -62,53 +63,6 @@ struct SortedList {
         j[K - 1] = won ? TOPK_EMPTY : j[K - 1];
     }
 };
-
-struct Head {
-    uint32_t lo, hi;
-    int j;
-    __device__ __forceinline__ double value() const { return __hiloint2double((int)hi, (int)lo); }
-};
-
-__device__ __forceinline__ Head lex_min(const Head &a, const Head &b) {
-    return lex_lt(b.value(), b.j, a.value(), a.j) ? b : a;
-}
-
-// the head of another lane of this row of 16 lanes (every lane is active: `old` is never taken)
-template <int CTRL>
-__device__ __forceinline__ Head from_lane(const Head &h) {
-    Head o;
-    o.lo = (uint32_t)__builtin_amdgcn_update_dpp((int)h.lo, (int)h.lo, CTRL, 0xf, 0xf, false);
-    o.hi = (uint32_t)__builtin_amdgcn_update_dpp((int)h.hi, (int)h.hi, CTRL, 0xf, 0xf, false);
-    o.j = __builtin_amdgcn_update_dpp(h.j, h.j, CTRL, 0xf, 0xf, false);
-    return o;
-}
-
-// the lexicographic minimum of (v, j) over the 64 lanes, in every lane.  Each step folds in the lane (or the group
-// already folded) across: lanes ^ 1, ^ 2 (quad_perm), the other quad of eight (row_half_mirror), the other half of
-// sixteen (row_mirror), the neighbouring row of 16 (v_permlane16_swap: a's odd rows <-> b's even rows, so of (a, b)
-// one is this lane's own and one the other row's), the other half of the wavefront (v_permlane32_swap likewise).
-__device__ __forceinline__ void wave_lex_min(double &v, int &j) {
-    constexpr int QUAD_1032 = 0xB1, QUAD_2301 = 0x4E, ROW_MIRROR = 0x140, ROW_HALF_MIRROR = 0x141;
-    Head h{(uint32_t)__double2loint(v), (uint32_t)__double2hiint(v), j};
-    h = lex_min(h, from_lane<QUAD_1032>(h));
-    h = lex_min(h, from_lane<QUAD_2301>(h));
-    h = lex_min(h, from_lane<ROW_HALF_MIRROR>(h));
-    h = lex_min(h, from_lane<ROW_MIRROR>(h));
-    {
-        const auto lo = __builtin_amdgcn_permlane16_swap(h.lo, h.lo, false, false);
-        const auto hi = __builtin_amdgcn_permlane16_swap(h.hi, h.hi, false, false);
-        const auto jj = __builtin_amdgcn_permlane16_swap((uint32_t)h.j, (uint32_t)h.j, false, false);
-        h = lex_min(Head{lo[0], hi[0], (int)jj[0]}, Head{lo[1], hi[1], (int)jj[1]});
-    }
-    {
-        const auto lo = __builtin_amdgcn_permlane32_swap(h.lo, h.lo, false, false);
-        const auto hi = __builtin_amdgcn_permlane32_swap(h.hi, h.hi, false, false);
-        const auto jj = __builtin_amdgcn_permlane32_swap((uint32_t)h.j, (uint32_t)h.j, false, false);
-        h = lex_min(Head{lo[0], hi[0], (int)jj[0]}, Head{lo[1], hi[1], (int)jj[1]});
-    }
-    v = h.value();
-    j = h.j;
-}
 
 // R: N rows of M squared values, ldr >= M apart.  idx / dist: N x k, contiguous.  ROOT: the distance stored is the
 // square root of the value selected on; without it the value itself (manhattan.hip: its slab holds distances).
@@ -191,8 +145,7 @@ int launch_topk_rows_plain(const double *R, int64_t N, int64_t M, int64_t ldr, i
     return launch_topk_form<false>(R, N, M, ldr, k, idx, dist, s);
 }
 
-// rows between two slabs' pitch: M rounded up to even, so that every row of the slab starts on 16 bytes
-static int64_t slab_ld(int64_t M) { return M + (M & 1); }
+static int64_t slab_ld(int64_t M) { return kneighbors_slab_ld(M); }
 
 // The default: as many rows, in multiples of 128, as keep the slab at 64 MiB -- and where that is more than one full
 // grid of the product kernel (KNEIGHBORS_WAVE_ROWS: two workgroups of 128 rows on each of 256 CUs), whole grids only:

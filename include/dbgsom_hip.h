@@ -677,6 +677,44 @@ int dbgsom_ctx_kneighbors_query_masked(dbgsom_ctx *ctx, const void *Xq_host, int
                                        const double *W_host, int64_t M, int k, int64_t *idx_host,
                                        double *dist_host);
 
+/* ---- the distortion measure of every row (csrc/distortion.hip) ----------------------------------------------
+ * bmu[i] = b, e[i] = sum_j H[b * ldh + j] * r_ij over j < M: b is the index of the smallest (r_ij, j) in
+ * lexicographic order among r_ij < +inf, r_ij = max((|x_i|^2 + (-2 <x_i, w_j>)) + |w_j|^2, 0) the squared value of
+ * the search's own fma chain (no float32 rounding), H a caller's M x M matrix of float64 neighbourhood factors
+ * (rows ldh >= M apart).  The order of the sum is fixed: lane l of 64 adds its terms j = l, l + 64, ... ascending
+ * into p_l = p_l + (H[b, j] * r_ij) from +0.0, the product rounded and then the sum (never a fused
+ * multiply-add); six rounds m = 1, 2, 4, 8, 16, 32 in which every lane takes p_l + p_(l ^ m) follow, and e is
+ * p_0.  Otherwise plain IEEE: a +inf or NaN r_ij enters the sum as it is (0 * inf = NaN).  A row without any
+ * r_ij below +inf has (bmu, e) = (-1, NaN).  Argument errors (M, ldr < M, ldh < M, slab_rows < 0, a null or
+ * misaligned pointer, a short workspace: DBGSOM_ENOMEM with both sizes in the message) are reported before any
+ * launch; N == 0 returns DBGSOM_OK without one.
+ *
+ * dbgsom_energy_rows: the kernel alone on a caller's matrix R of squared values, N rows of M entries ldr >= M
+ * apart; nothing of a row past M is read.  bmu (int64) and e (float64) hold N values each.
+ * dbgsom_neighborhood_energy: arguments as dbgsom_kneighbors with H for k: the rows are worked in the same
+ * slabs, in the same workspace (dbgsom_kneighbors_workspace_bytes(N, M, slab_rows), 16-byte aligned). */
+int dbgsom_energy_rows(const double *R_dev, int64_t N, int64_t M, int64_t ldr, const double *H_dev, int64_t ldh,
+                       int64_t *bmu_dev, double *e_dev, void *stream);
+int dbgsom_neighborhood_energy(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx,
+                               const double *xx_dev, const double *W_dev, int64_t M, const double *ww_dev,
+                               const double *H_dev, int64_t ldh, int64_t slab_rows, int64_t *bmu_dev,
+                               double *e_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+/* The same on a context, each call staging its rows as its dbgsom_ctx_kneighbors_query* namesake does (chunks,
+ * query placement, CSR expanded chunk by chunk, the slab of "kneighbors_slab_rows" rows, status codes).  H_host
+ * (M x M, contiguous) goes up once per call and counts as upload traffic; Nq x 16 bytes of result come down per
+ * host-facing call.  _device: bmu_dev / e_dev are written by the kernel; nothing of X or of the result crosses
+ * PCIe. */
+int dbgsom_ctx_distortion_query(dbgsom_ctx *ctx, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                const double *W_host, int64_t M, const double *H_host, int64_t *bmu_host,
+                                double *e_host);
+int dbgsom_ctx_distortion_query_device(dbgsom_ctx *ctx, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d,
+                                       int64_t ldx, const double *W_host, int64_t M, const double *H_host,
+                                       int64_t *bmu_dev, double *e_dev);
+int dbgsom_ctx_distortion_query_csr(dbgsom_ctx *ctx, const int64_t *indptr_host, const int32_t *indices_host,
+                                    const void *data_host, int x_dtype, int64_t Nq, int64_t d, int64_t nnz,
+                                    const double *W_host, int64_t M, const double *H_host, int64_t *bmu_host,
+                                    double *e_host);
+
 /* ---- fit on rows with missing entries (csrc/masked_fit.hip, csrc/smooth.hip) ---------------------------
  * One epoch on prototypes W (M x d, complete), hop matrix and sigma, NaN marking a missing entry of X:
  *   1. (dist_i, win_i): the masked search above with k = 1 -- every row goes through it, complete rows
