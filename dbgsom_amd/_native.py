@@ -160,6 +160,14 @@ SIGNATURES = {
     "dbgsom_ctx_distortion_query": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
     "dbgsom_ctx_distortion_query_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
     "dbgsom_ctx_distortion_query_csr": (_ci, [_vp, _vp, _vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "dbgsom_topk_cols_workspace_bytes": (_sz, [_i64, _i64, _ci]),
+    "dbgsom_topk_cols_init": (_ci, [_vp, _vp, _i64, _ci, _vp]),
+    "dbgsom_topk_cols": (_ci, [_vp, _i64, _i64, _i64, _vp, _i64, _ci, _vp, _vp, _vp, _sz, _vp]),
+    "dbgsom_exemplars_workspace_bytes": (_sz, [_i64, _i64, _ci, _i64]),
+    "dbgsom_exemplars": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _ci, _ci, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "dbgsom_ctx_exemplars_query": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _ci, _ci, _vp, _vp]),
+    "dbgsom_ctx_exemplars_query_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _ci, _ci, _vp, _vp]),
+    "dbgsom_ctx_exemplars_query_csr": (_ci, [_vp, _vp, _vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _ci, _ci, _vp, _vp]),
     "dbgsom_accumulate_masked_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "dbgsom_accumulate_masked": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "dbgsom_smooth_masked_workspace_bytes": (_sz, [_i64, _i64]),

@@ -127,6 +127,18 @@ class HotPathBackend:
         has (NaN, -1).  X as for ``distances``; the results are NumPy arrays, next to X for a device array."""
         raise NotImplementedError
 
+    def exemplars(self, W, k, X, own_cell=False):
+        """The k nearest rows of X to every prototype -> (dist, idx), both (rows of W, k), float64 and int64: row ``j``
+        holds the rows of X with the smallest ``(r_ij, i)`` in lexicographic order, ascending, r the squared value of
+        ``bmu(W, k, X=X)``'s arithmetic (what ``kneighbors`` selects on), ``dist = sqrt(r)`` taken after the selection
+        and ``idx`` row numbers of X.  Equal r go by the lower row; a pair whose r is not below +inf is never
+        reported; slots left unfilled hold ``(inf, -1)`` (k may exceed the rows of X, 1 <= k <= MAX_NEIGHBORS).
+        ``own_cell``: row ``i`` is a candidate for prototype ``j`` only if ``j`` is the row's unit, the index of its
+        smallest ``(r_ij, j)`` (``kneighbors(W, 1, X)``); a row without an r below +inf belongs to no unit.  ``(r, i)``
+        is a total order: the result does not depend on chunks or slabs.  X as for ``distances``; the results are
+        NumPy arrays, next to X for a device array."""
+        raise NotImplementedError
+
     # -- metric="manhattan": dist(x, w) = sum_k |x_k - w_k| in float64, k ascending, one accumulator per pair; float32
     # rows widened exactly first; no square root, no clamp; winners by (dist, index); a pair whose distance is not
     # below +inf is never reported (index -1, distance inf).  X: a dense host array or a device array.
@@ -1080,6 +1092,48 @@ class HipBackend(HotPathBackend):
         self._call("dbgsom_ctx_distortion_query", self._ctx, X.ctypes.data, _x_dtype_code(X.dtype), N, X.shape[1],
                    W64.ctypes.data, M, H64.ctypes.data, bmu.ctypes.data, e.ctypes.data)
         return e, bmu
+
+    # -- the k nearest rows to every prototype ---------------------------------------------------------
+    def exemplars(self, W, k, X, own_cell=False):
+        """The k nearest rows to every prototype (csrc/exemplars.hip): the squared distances of a slab of
+        ``kneighbors_slab_rows`` rows stay on the device, the fold reads them back from cache down their columns into
+        a state of (rows of W, k) pairs that lives on the device for the length of the call, and only that state is
+        the result.  Host rows go up in chunks of ``distances_chunk_rows`` rows, every chunk folding into the state
+        under its first row's number; CSR rows are expanded on the device chunk by chunk; rows of W x k x 16 bytes
+        come down, once.  For rows in HBM both results are arrays on their device that the kernel writes itself
+        (dbgsom_ctx_exemplars_query_device).  X without rows: all ``(inf, -1)``, no launch."""
+        W64 = np.ascontiguousarray(W, dtype=np.float64)
+        if W64.ndim != 2 or len(X.shape) != 2 or W64.shape[1] != X.shape[1]:
+            raise ValueError("prototype / sample feature mismatch")
+        M, N, k, own = W64.shape[0], int(X.shape[0]), int(k), int(bool(own_cell))
+        if not 1 <= k <= _native.MAX_NEIGHBORS:
+            raise ValueError(f"need 1 <= k <= DBGSOM_MAX_NEIGHBORS = {_native.MAX_NEIGHBORS}, got k = {k}")
+        if is_device_array(X):
+            if N == 0:
+                ns = array_namespace(X)
+                return (ns.full((M, k), float("inf"), dtype=ns.float64, device=X.device),
+                        ns.full((M, k), -1, dtype=ns.int64, device=X.device))
+            code, N, d, ldx = self._device_rows(X)
+            dist, idx = device_empty(X, (M, k), "float64"), device_empty(X, (M, k), "int64")
+            self._producer_done(X)
+            self._call("dbgsom_ctx_exemplars_query_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code, N, d, ldx,
+                       W64.ctypes.data, M, k, own, ctypes.c_void_p(idx.data_ptr()), ctypes.c_void_p(dist.data_ptr()))
+            return dist, idx
+        if N == 0:
+            return np.full((M, k), np.inf), np.full((M, k), -1, dtype=np.int64)
+        dist, idx = np.empty((M, k), dtype=np.float64), np.empty((M, k), dtype=np.int64)
+        if is_sparse(X):
+            csr, indptr, indices, data = canonical_csr(X)
+            self._call("dbgsom_ctx_exemplars_query_csr", self._ctx, indptr.ctypes.data, indices.ctypes.data,
+                       data.ctypes.data, _x_dtype_code(data.dtype), N, csr.shape[1], data.size, W64.ctypes.data, M, k,
+                       own, idx.ctypes.data, dist.ctypes.data)
+            return dist, idx
+        X = np.ascontiguousarray(X)
+        if X.dtype not in (np.float32, np.float64):
+            X = X.astype(np.float64)
+        self._call("dbgsom_ctx_exemplars_query", self._ctx, X.ctypes.data, _x_dtype_code(X.dtype), N, X.shape[1],
+                   W64.ctypes.data, M, k, own, idx.ctypes.data, dist.ctypes.data)
+        return dist, idx
 
     # -- metric="manhattan" (csrc/manhattan.hip) --------------------------------------------------------
     _manhattan = property(lambda self: self._metric == "manhattan")

@@ -1257,6 +1257,68 @@ class BaseSom(BaseEstimator):
             check_array(X, dtype=[np.float64, np.float32])   # (no rows: refused in check_array's words, as a mean is)
         return float(np.sum(self._host(e))) / e.shape[0]
 
+    def prototype_exemplars(self, X, n_exemplars=1, own_cell=False, return_distance=True):
+        """The ``n_exemplars`` nearest rows of X to every prototype: ``(dist, idx)``, or ``idx`` alone with
+        ``return_distance=False``, both ``(len(weights_), n_exemplars)``, float64 and int64 (row numbers of X) -- the
+        records that stand for a unit: its medoid, the exemplar images of a map, the documents of a cell;
+        ``pairwise_distances_argmin_min(weights_, X)`` for ``n_exemplars=1``.
+
+        Row ``j`` holds the rows of X with the smallest ``(r_ij, i)`` in lexicographic order, ascending, where
+        ``r_ij = max((|x_i|^2 + (-2 <x_i, w_j>)) + |w_j|^2, 0)`` is the squared value of the best-matching-unit
+        search's own arithmetic, the one ``kneighbors`` selects on; ``dist = sqrt(r)`` is taken after the selection.
+        Equal ``r`` go by the lower row number, and of two different ``r`` under one square root the smaller comes
+        first.  A pair whose ``r`` is not below +inf is never reported; slots left unfilled hold ``(inf, -1)``: with
+        fewer rows than ``n_exemplars``, or with an empty cell under ``own_cell``.  Invariants:
+
+        * ``dist[j, t] == prototype_distances(X)[idx[j, t], j]`` bit for bit;
+        * ``own_cell=True``: row ``i`` is a candidate for unit ``j`` only if ``j`` is the row's best matching unit,
+          the index of the smallest ``(r_ij, j)`` -- what ``SomVQ.predict`` and ``kneighbors(X, 1)`` name (a row
+          without any ``r`` below +inf belongs to no cell).  Every filled slot then satisfies
+          ``kneighbors(X[idx[j, t]], 1)[1] == j``, row ``j`` has ``min(n_exemplars, rows whose unit is j)`` filled
+          slots, and ``dist[j, 0]`` is the smallest distance in the cell;
+        * ``(r, i)`` is a total order, so the result does not depend on chunks, slabs or where X lives: a host
+          array, a tensor and CSR rows of the same data give the same bits.
+
+        ``1 <= n_exemplars <= 32``; it may exceed the number of rows, and above 32 ``prototype_distances(X)`` and a
+        sort of its columns is the route.  X is what ``kneighbors`` takes under the Euclidean metric: a dense array
+        (NumPy results; ``len(weights_) * n_exemplars * 16`` bytes come down, once, at the end of the call), a tensor
+        on the estimator's GPU (tensors on X's device that the GPU writes itself; X never touches the host), scipy
+        sparse rows (the dense call's result on ``X.toarray()``).  X without rows gives all ``(inf, -1)`` without a
+        launch.  The N x M matrix is never held: squared distances live one slab of rows at a time on the device
+        and a selection down its columns folds them into the result.  Refused with a ``ValueError``:
+        ``metric="manhattan"`` / ``"cosine"``, rows with NaN (also under ``missing_values``: impute them first), a
+        feature-count mismatch.  Only this map's prototypes are used (not the child maps of vertical growth); the
+        call is local to the process."""
+        check_is_fitted(self)
+        if isinstance(n_exemplars, (bool, np.bool_)) or not isinstance(n_exemplars, (numbers.Integral, np.integer)):
+            raise ValueError("n_exemplars does not take %s value, enter integer value" % type(n_exemplars))
+        k = int(n_exemplars)
+        if k <= 0:
+            raise ValueError("Expected n_exemplars > 0. Got %d" % k)
+        if k > MAX_NEIGHBORS:
+            raise ValueError(f"n_exemplars = {k} is above the {MAX_NEIGHBORS} the selection on the GPU keeps per "
+                             "prototype: use prototype_distances(X) and sort its columns")
+        kind = self._search_metric()
+        if kind:
+            self._refuse_metric(kind, "prototype_exemplars",
+                                "the selection runs on the squared Euclidean distances of the search")
+        if not is_device_array(X) and not is_sparse(X) and np.ndim(X) == 2 and np.shape(X)[0] == 0:
+            X = check_array(X, dtype=[np.float64, np.float32], ensure_min_samples=0)   # (no rows: no launch)
+        else:
+            X = self._check_query(X)
+        if X.shape[1] != self.n_features_in_:
+            raise ValueError(f"X has {X.shape[1]} features, but {type(self).__name__} is expecting "
+                             f"{self.n_features_in_} features as input")
+        if isinstance(X, np.ndarray) and np.isnan(X).any():   # (passed _check_query: missing_values is set)
+            raise ValueError(f"X holds NaN: the exemplars of a unit are not defined on rows with missing entries "
+                             f"(missing_values={self.missing_values!r}); impute them first (impute(X))")
+        M = len(self.weights_)
+        if X.shape[0] == 0 and not is_device_array(X):
+            dist, idx = np.full((M, k), np.inf), np.full((M, k), -1, dtype=np.int64)
+        else:
+            dist, idx = self._engine().exemplars(self.weights_, k, X, own_cell=bool(own_cell))
+        return (dist, idx) if return_distance else idx
+
     def _calculate_topographic_error(self, X) -> float:
         """Fraction of samples whose two best matching units are not lattice neighbours."""
         if self._is_resident(X):

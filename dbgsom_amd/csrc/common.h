@@ -202,6 +202,24 @@ int launch_energy_rows(const double *R, int64_t N, int64_t M, int64_t ldr, const
 int launch_neighborhood_energy(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx,
                                const double *W, int64_t M, const double *ww, const double *H, int64_t ldh,
                                int64_t slab_rows, int64_t *bmu, double *e, void *ws, size_t ws_bytes, hipStream_t s);
+// the k nearest rows to every prototype (exemplars.hip): the fold down the columns of a matrix of squared values --
+// state_r / state_i (M x k) hold per column the k smallest (r, global row) so far --, the slab loop of launch_kneighbors
+// with that fold behind the product (rows row0 .. row0 + N - 1 into a caller's state), the kernel that stores the state
+// as (sqrt(r), row), and the whole call with the state behind its workspace
+size_t topk_cols_workspace_bytes(int64_t N, int64_t M, int k);
+int launch_topk_cols_init(double *state_r, int64_t *state_i, int64_t M, int k, hipStream_t s);
+int launch_topk_cols(const double *R, int64_t N, int64_t M, int64_t ldr, const int64_t *owner, int64_t row0, int k,
+                     double *state_r, int64_t *state_i, void *ws, size_t ws_bytes, hipStream_t s);
+size_t exemplars_fold_workspace_bytes(int64_t N, int64_t M, int k, int64_t slab_rows);
+size_t exemplars_workspace_bytes(int64_t N, int64_t M, int k, int64_t slab_rows);
+int launch_exemplars_fold(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx, const double *W,
+                          int64_t M, const double *ww, int k, int own_cell, int64_t slab_rows, int64_t row0, double *state_r,
+                          int64_t *state_i, void *ws, size_t ws_bytes, hipStream_t s);
+int launch_exemplars_store(const double *state_r, const int64_t *state_i, int64_t M, int k, int64_t *idx, double *dist,
+                           hipStream_t s);
+int launch_exemplars(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx, const double *W,
+                     int64_t M, const double *ww, int k, int own_cell, int64_t slab_rows, int64_t *idx, double *dist,
+                     void *ws, size_t ws_bytes, hipStream_t s);
 // metric="manhattan" (manhattan.hip): sum_k |x_k - w_k| in float64, F32 / F64 rows; search, matrix and selection read
 // the transposed float64 prototypes launch_manhattan_weights leaves in front of the workspace
 size_t bmu_manhattan_workspace_bytes(int x_dtype, int64_t N, int64_t d, int64_t M);

@@ -282,6 +282,9 @@ struct dbgsom_ctx {
     // the distortion measure of a query (distortion.hip): the M x M neighbourhood factors of the call (the slab and a
     // chunk's staged result are kn_ws, kn_idx and kn_dist)
     DevBuf de_h;
+    // the k nearest rows to every prototype (exemplars.hip): the state of the call's fold, [r: M x k float64 | i: M x k
+    // int64] (the slab and the fold's scratch are kn_ws; a host-facing call's result is staged in kn_idx and kn_dist)
+    DevBuf ex_state;
     // The resident rows have missing entries (NaN): option "incomplete", set after a load and cleared by the next one.
     // What depends on the rows alone is made when the option is set, once per load: n_obs per row (mf_nobs) and, for
     // float32 rows, their float64 copy (mf_x64, N x d x 8 bytes of HBM).  The ordinary calls then refuse to compute
@@ -1258,7 +1261,7 @@ int dbgsom_ctx_create(int device, dbgsom_ctx **out) {
      &(c)->shard_gather, &(c)->sw, &(c)->wh_order, &(c)->wh_ws, &(c)->sc_ws, &(c)->sc_x, &(c)->sc_w, &(c)->sc_p, &(c)->sc_code, &(c)->sc_proba, &(c)->sc_cnt, &(c)->wt,  \
      &(c)->mk_ws, &(c)->mk_x, &(c)->mk_w, &(c)->mk_idx, &(c)->mk_dist, &(c)->mf_nobs, &(c)->mf_x64, &(c)->mf_wt, &(c)->mf_w,   \
      &(c)->mf_wn, &(c)->mf_idx, &(c)->mf_dist, &(c)->mf_kw, &(c)->mf_sums, &(c)->mf_acc_ws, &(c)->mf_sm_ws, &(c)->mf_scal, \
-     &(c)->pd_out, &(c)->kn_ws, &(c)->kn_idx, &(c)->kn_dist, &(c)->de_h, &(c)->l1_ws, &(c)->cos_u, &(c)->cos_v}
+     &(c)->pd_out, &(c)->kn_ws, &(c)->kn_idx, &(c)->kn_dist, &(c)->de_h, &(c)->ex_state, &(c)->l1_ws, &(c)->cos_u, &(c)->cos_v}
 
 int dbgsom_ctx_destroy(dbgsom_ctx *c) {
     if (!c) return DBGSOM_OK;
@@ -1849,7 +1852,8 @@ int dbgsom_ctx_bmu_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const in
 // prototypes under every metric, and the search itself over rows with missing entries and under metric="manhattan"
 // and metric="cosine" -- is one of two loops over chunks of rows:
 //   raw_rows_query     masked / Manhattan / cosine: kernels that read the rows as they are stored (any row pitch)
-//   placed_rows_query  Euclidean distances, neighbours and distortion: the rows go through the query placement first
+//   placed_rows_query  Euclidean distances, neighbours, distortion and exemplars: the rows go through the query placement
+//                      first
 // A chunk of host rows goes up, its result is staged on the device and comes down behind the kernel; rows in HBM are
 // read where they are and the kernels write the caller's device arrays.  Both drivers synchronise before they return,
 // on error too (W_host and the rows are pageable), and end on drop_large_query_scratch.  The exported calls further
@@ -1857,7 +1861,7 @@ int dbgsom_ctx_bmu_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const in
 // ------------------------------------------------------------------------------------------
 namespace {
 
-enum QueryOp { Q_BMU, Q_DISTANCES, Q_KNEIGHBORS, Q_DISTORTION };
+enum QueryOp { Q_BMU, Q_DISTANCES, Q_KNEIGHBORS, Q_DISTORTION, Q_EXEMPLARS };
 enum RowsForm { ROWS_MASKED, ROWS_MANHATTAN, ROWS_COSINE };
 
 // DBGSOM_REQUIRE under the name of the exported call `fn` (checks shared by several of them)
@@ -1885,7 +1889,8 @@ int query_args(const char *fn, const dbgsom_ctx *c, QueryOp op, int x_dtype, boo
     REQUIRE_FN(fn, Nq >= 0 && Nq < 0x7fffffff && d >= 1 && d <= 0x7fffffff, "bad sample shape");
     REQUIRE_FN(fn, M >= 1 && M <= DBGSOM_MAX_PROTOTYPES, "need 1 <= M <= DBGSOM_MAX_PROTOTYPES");
     if (op == Q_DISTANCES || op == Q_DISTORTION) return DBGSOM_OK;
-    REQUIRE_FN(fn, k >= 1 && k <= M, "need 1 <= k <= M");
+    if (op == Q_EXEMPLARS) REQUIRE_FN(fn, k >= 1, "need k >= 1");   // (k counts rows: it may exceed M, and Nq)
+    else REQUIRE_FN(fn, k >= 1 && k <= M, "need 1 <= k <= M");
     REQUIRE_FN(fn, k <= DBGSOM_MAX_NEIGHBORS, "k must be <= DBGSOM_MAX_NEIGHBORS");
     return DBGSOM_OK;
 }
@@ -1913,6 +1918,7 @@ void drop_large_query_scratch(dbgsom_ctx *c) {
     if (c->pd_out.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->pd_out.release();
     if (c->kn_ws.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->kn_ws.release();
     if (c->de_h.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->de_h.release();
+    if (c->ex_state.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->ex_state.release();
 }
 
 // the end of both drivers
@@ -2092,14 +2098,18 @@ struct CsrHost {
 // CSR rows (csr != nullptr): the three arrays go up whole, and chunks of rows are expanded into the dense rows the
 // kernels read.  Q_DISTORTION (csrc/distortion.hip; k = 1): the neighbours' slab and staging with the energy kernel
 // behind the product; idx_out / dist_out take a row's unit and its e, and H_host (M x M) goes up once per call.
+// Q_EXEMPLARS (csrc/exemplars.hip): every chunk folds into the state in ex_state with row0 the chunk's first row --
+// nothing per chunk is staged or copied down --, and after the last one the state is stored as the M x k result: into
+// kn_idx / kn_dist and down in one piece (M * k * 16 bytes), or into the caller's device arrays.
 int placed_rows_query(dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHost *csr, int x_dtype, int64_t Nq, int64_t d,
                       const double *W_host, int64_t M, int k, int64_t *idx_out, double *dist_out, int64_t ldo,
-                      const double *H_host) {
+                      const double *H_host, int own_cell) {
     Samples &s = c->xq;
     DevBuf Wq, wwq;
     const int64_t dp = pad16(d);
     const size_t es = dtype_size(x_dtype);
     const bool staged = !q.on_device, knn = op != Q_DISTANCES;   // (knn: a slab per chunk, k values per row and array)
+    const bool cols = op == Q_EXEMPLARS;                         // (the result is M x k, after the last chunk)
     const int64_t chunk = staged ? distances_chunk(c, Nq, M, dp * (int64_t)es) : Nq;
     const int64_t per_row = knn ? k : M;   // values of a row's result
     int rc = DBGSOM_OK;
@@ -2117,7 +2127,13 @@ int placed_rows_query(dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHo
             if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
             c->x_up((size_t)M * M * 8);
         }
-        if (knn) {
+        if (cols) {
+            if ((rc = c->kn_ws.reserve(exemplars_fold_workspace_bytes(chunk, M, k, c->kneighbors_slab_rows)))) break;
+            if ((rc = c->ex_state.reserve((size_t)M * k * 16))) break;
+            if (staged && (rc = c->kn_idx.reserve((size_t)M * k * 8))) break;
+            if (staged && (rc = c->kn_dist.reserve((size_t)M * k * 8))) break;
+            if ((rc = launch_topk_cols_init(c->ex_state.as<double>(), c->ex_state.as<int64_t>() + M * k, M, k, c->stream))) break;
+        } else if (knn) {
             if ((rc = c->kn_ws.reserve(kneighbors_workspace_bytes(chunk, M, c->kneighbors_slab_rows)))) break;
             if (staged && (rc = c->kn_idx.reserve((size_t)chunk * k * 8))) break;
             if (staged && (rc = c->kn_dist.reserve((size_t)chunk * k * 8))) break;
@@ -2140,6 +2156,12 @@ int placed_rows_query(dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHo
             if (rc) break;
             int64_t *idx = staged ? c->kn_idx.as<int64_t>() : idx_out;
             double *res = !staged ? dist_out : (knn ? c->kn_dist.as<double>() : c->pd_out.as<double>());
+            if (cols) {
+                rc = launch_exemplars_fold(s.Xb, s.bdtype, n, dp, dp, s.xx.as<double>(), Wq.as<double>(), M, wwq.as<double>(), k,
+                                           own_cell, c->kneighbors_slab_rows, r0, c->ex_state.as<double>(),
+                                           c->ex_state.as<int64_t>() + M * k, c->kn_ws.p, c->kn_ws.cap, c->stream);
+                continue;
+            }
             if (op == Q_DISTORTION)
                 rc = launch_neighborhood_energy(s.Xb, s.bdtype, n, dp, dp, s.xx.as<double>(), Wq.as<double>(), M,
                                                 wwq.as<double>(), c->de_h.as<double>(), M, c->kneighbors_slab_rows, idx, res,
@@ -2158,6 +2180,16 @@ int placed_rows_query(dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHo
             if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; }
             c->x_down((size_t)n * per_row * (knn ? 16 : 8));
         }
+        if (rc || !cols) break;
+        int64_t *idx = staged ? c->kn_idx.as<int64_t>() : idx_out;
+        double *res = staged ? c->kn_dist.as<double>() : dist_out;
+        if ((rc = launch_exemplars_store(c->ex_state.as<double>(), c->ex_state.as<int64_t>() + M * k, M, k, idx, res, c->stream)))
+            break;
+        if (!staged) break;
+        hipError_t e = hipMemcpyAsync(idx_out, idx, (size_t)M * k * 8, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(dist_out, res, (size_t)M * k * 8, hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; }
+        c->x_down((size_t)M * k * 16);
     } while (0);
     rc = finish_query(c, rc);
     Wq.release(); wwq.release();
@@ -2193,10 +2225,11 @@ int raw_rows_checked(const char *fn, dbgsom_ctx *c, QueryOp op, RowsForm form, c
     return raw_rows_query(c, fn, op, form, q, x_dtype, Nq, d, W_host, M, k, idx_out, dist_out, ldo, nullptr);
 }
 
-// the Euclidean distance matrix and k nearest prototypes of dense rows (csr == nullptr) or host CSR rows
+// the Euclidean distance matrix, k nearest prototypes, distortion and exemplars of dense rows (csr == nullptr) or host
+// CSR rows
 int placed_rows_checked(const char *fn, dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHost *csr, int x_dtype, int64_t Nq,
                         int64_t d, const double *W_host, int64_t M, int k, int64_t *idx_out, double *dist_out, int64_t ldo,
-                        const double *H_host = nullptr) {
+                        const double *H_host = nullptr, int own_cell = 0) {
     TRY(query_args(fn, c, op, x_dtype, csr != nullptr, Nq, d, M, k));
     if (q.on_device) REQUIRE_FN(fn, q.ldx >= d, "ldx must be >= d");
     if (op == Q_DISTANCES) REQUIRE_FN(fn, ldo >= M, "ldo must be >= M");
@@ -2208,7 +2241,7 @@ int placed_rows_checked(const char *fn, dbgsom_ctx *c, QueryOp op, const QueryRo
     REQUIRE_FN(fn, (csr || q.p) && W_host && (op == Q_DISTANCES || idx_out) && dist_out, "null pointer");
     if (op == Q_DISTORTION) REQUIRE_FN(fn, H_host, "null pointer");
     SET_DEVICE(c);
-    return placed_rows_query(c, op, q, csr, x_dtype, Nq, d, W_host, M, k, idx_out, dist_out, ldo, H_host);
+    return placed_rows_query(c, op, q, csr, x_dtype, Nq, d, W_host, M, k, idx_out, dist_out, ldo, H_host, own_cell);
 }
 
 }  // namespace
@@ -2301,6 +2334,31 @@ int dbgsom_ctx_distortion_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, c
     const CsrHost csr{indptr_host, indices_host, nnz};
     return placed_rows_checked(__func__, c, Q_DISTORTION, QueryRows{data_host, false, d}, &csr, x_dtype, Nq, d, W_host, M,
                                1, bmu_host, e_host, 0, H_host);
+}
+
+// ------------------------------------------------------------------------------------------
+// the k nearest rows of a query to every prototype: csrc/exemplars.hip (idx / dist: M x k; Nq == 0 writes nothing)
+// ------------------------------------------------------------------------------------------
+int dbgsom_ctx_exemplars_query(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d, const double *W_host,
+                               int64_t M, int k, int own_cell, int64_t *idx_host, double *dist_host) {
+    return placed_rows_checked(__func__, c, Q_EXEMPLARS, QueryRows{Xq_host, false, d}, nullptr, x_dtype, Nq, d, W_host, M, k,
+                               idx_host, dist_host, 0, nullptr, own_cell);
+}
+
+int dbgsom_ctx_exemplars_query_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d, int64_t ldx,
+                                      const double *W_host, int64_t M, int k, int own_cell, int64_t *idx_dev,
+                                      double *dist_dev) {
+    return placed_rows_checked(__func__, c, Q_EXEMPLARS, QueryRows{Xq_dev, true, ldx}, nullptr, x_dtype, Nq, d, W_host, M, k,
+                               idx_dev, dist_dev, 0, nullptr, own_cell);
+}
+
+int dbgsom_ctx_exemplars_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const int32_t *indices_host,
+                                   const void *data_host, int x_dtype, int64_t Nq, int64_t d, int64_t nnz,
+                                   const double *W_host, int64_t M, int k, int own_cell, int64_t *idx_host,
+                                   double *dist_host) {
+    const CsrHost csr{indptr_host, indices_host, nnz};
+    return placed_rows_checked(__func__, c, Q_EXEMPLARS, QueryRows{data_host, false, d}, &csr, x_dtype, Nq, d, W_host, M, k,
+                               idx_host, dist_host, 0, nullptr, own_cell);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -29,40 +29,8 @@
 namespace dbgsom {
 
 constexpr int TOPK_NT = 256;              // four wavefronts, four rows per workgroup
-constexpr int TOPK_EMPTY = 0x7fffffff;    // the index of an unfilled slot (Best<K>::init)
 constexpr int64_t KNEIGHBORS_SLAB_BYTES = (int64_t)64 << 20;
 constexpr int64_t KNEIGHBORS_WAVE_ROWS = 512 * 128;
-
-template <int K>
-struct SortedList {
-    double v[K];
-    int j[K];
-    __device__ __forceinline__ void init() {
-#pragma unroll
-        for (int t = 0; t < K; ++t) { v[t] = INFINITY; j[t] = TOPK_EMPTY; }
-    }
-    // (r, idx) takes its place behind every entry <= r; the last entry drops out.  NaN and +inf never enter.
-    __device__ __forceinline__ void push(double r, int idx) {
-        if (r < v[K - 1]) {
-#pragma unroll
-            for (int t = K - 1; t >= 1; --t) {
-                const bool up = r < v[t - 1], here = r < v[t];
-                v[t] = up ? v[t - 1] : (here ? r : v[t]);
-                j[t] = up ? j[t - 1] : (here ? idx : j[t]);
-            }
-            if (r < v[0]) { v[0] = r; j[0] = idx; }
-        }
-    }
-    __device__ __forceinline__ void pop(bool won) {
-#pragma unroll
-        for (int t = 0; t + 1 < K; ++t) {
-            v[t] = won ? v[t + 1] : v[t];
-            j[t] = won ? j[t + 1] : j[t];
-        }
-        v[K - 1] = won ? (double)INFINITY : v[K - 1];
-        j[K - 1] = won ? TOPK_EMPTY : j[K - 1];
-    }
-};
 
 // R: N rows of M squared values, ldr >= M apart.  idx / dist: N x k, contiguous.  ROOT: the distance stored is the
 // square root of the value selected on; without it the value itself (manhattan.hip: its slab holds distances).

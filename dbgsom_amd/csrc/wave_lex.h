@@ -1,9 +1,55 @@
-// The wave-wide lexicographic arg-min over (value, index) pairs, one pair per lane, without LDS: shared by the
-// selection kernel of kneighbors.hip and the energy kernel of distortion.hip.
+// The wave-wide lexicographic arg-min over (value, index) pairs, one pair per lane, without LDS, and the sorted list of
+// K pairs a lane keeps in registers: shared by the selection kernels of kneighbors.hip and exemplars.hip and the energy
+// kernel of distortion.hip.
 #pragma once
 #include "bmu_common.h"
 
 namespace dbgsom {
+
+constexpr int TOPK_EMPTY = 0x7fffffff;    // the index of an unfilled slot (Best<K>::init)
+
+template <int K>
+struct SortedList {
+    double v[K];
+    int j[K];
+    __device__ __forceinline__ void init() {
+#pragma unroll
+        for (int t = 0; t < K; ++t) { v[t] = INFINITY; j[t] = TOPK_EMPTY; }
+    }
+    // (r, idx) takes its place behind every entry <= r; the last entry drops out.  NaN and +inf never enter.
+    __device__ __forceinline__ void push(double r, int idx) {
+        if (r < v[K - 1]) {
+#pragma unroll
+            for (int t = K - 1; t >= 1; --t) {
+                const bool up = r < v[t - 1], here = r < v[t];
+                v[t] = up ? v[t - 1] : (here ? r : v[t]);
+                j[t] = up ? j[t - 1] : (here ? idx : j[t]);
+            }
+            if (r < v[0]) { v[0] = r; j[0] = idx; }
+        }
+    }
+    // the same for pairs that arrive in any order of idx: (r, idx) takes its place by the lexicographic order
+    __device__ __forceinline__ void push_lex(double r, int idx) {
+        if (r < (double)INFINITY && lex_lt(r, idx, v[K - 1], j[K - 1])) {
+#pragma unroll
+            for (int t = K - 1; t >= 1; --t) {
+                const bool up = lex_lt(r, idx, v[t - 1], j[t - 1]), here = lex_lt(r, idx, v[t], j[t]);
+                v[t] = up ? v[t - 1] : (here ? r : v[t]);
+                j[t] = up ? j[t - 1] : (here ? idx : j[t]);
+            }
+            if (lex_lt(r, idx, v[0], j[0])) { v[0] = r; j[0] = idx; }
+        }
+    }
+    __device__ __forceinline__ void pop(bool won) {
+#pragma unroll
+        for (int t = 0; t + 1 < K; ++t) {
+            v[t] = won ? v[t + 1] : v[t];
+            j[t] = won ? j[t + 1] : j[t];
+        }
+        v[K - 1] = won ? (double)INFINITY : v[K - 1];
+        j[K - 1] = won ? TOPK_EMPTY : j[K - 1];
+    }
+};
 
 struct Head {
     uint32_t lo, hi;

@@ -715,6 +715,55 @@ int dbgsom_ctx_distortion_query_csr(dbgsom_ctx *ctx, const int64_t *indptr_host,
                                     const double *W_host, int64_t M, const double *H_host, int64_t *bmu_host,
                                     double *e_host);
 
+/* ---- the k nearest rows to every prototype (csrc/exemplars.hip) ----------------------------------------------
+ * The all-pairs search read down its columns: idx[j * k + t], dist[j * k + t] are, for prototype j, the rows i of
+ * X with the smallest (r_ij, i) in lexicographic order, ascending, r_ij = max((|x_i|^2 + (-2 <x_i, w_j>)) +
+ * |w_j|^2, 0) the squared value dbgsom_kneighbors selects on, and dist = sqrt(r) taken after the selection: equal
+ * r go by the lower row, and of two different r under one square root the smaller comes first.  A pair whose r is
+ * not below +inf (NaN, +inf) is never reported; slots left unfilled hold (inf, -1).  1 <= k <=
+ * DBGSOM_MAX_NEIGHBORS; k may exceed M and N.  With own_cell != 0 row i is a candidate for prototype j only if j
+ * is the row's unit, the index of its smallest (r_ij, j) (dbgsom_kneighbors at k = 1); a row without any r below
+ * +inf belongs to no unit.  (r, i) is a total order, so the result does not depend on slabs or chunks.
+ *
+ * dbgsom_topk_cols: the selection alone, as a fold.  R holds N rows of M squared values, ldr >= M apart, with the
+ * global row numbers row0 .. row0 + N - 1, row0 >= 0 and row0 + N <= 2^31 - 1.  state_r (M x k float64) and
+ * state_i (M x k int64) hold per column the k smallest (r, i) seen so far, ascending, (+inf, -1) in empty slots
+ * (dbgsom_topk_cols_init fills them so); after the call they hold the k smallest among what they held and the new
+ * rows.  owner_dev is null or N int64 values: row i is folded into column j only if owner[i] == j.  The scratch
+ * of one fold is dbgsom_topk_cols_workspace_bytes(N, M, k) bytes, 16-byte aligned; what it held before, and what
+ * lies in a row past M, is never read into a result.  N == 0 returns DBGSOM_OK without a launch.
+ * dbgsom_exemplars: arguments as dbgsom_kneighbors, idx / dist M x k: it fills the state, runs that call's slab
+ * loop (the squared product; with own_cell the selection of dbgsom_topk_rows at k = 1 for the units; the fold)
+ * and stores (sqrt(r), i).  The workspace, dbgsom_exemplars_workspace_bytes(N, M, k, slab_rows) bytes, 16-byte
+ * aligned, covers the slab, the units of one slab, the fold's scratch and the state.  N == 0 stores (inf, -1).
+ * Argument errors (k out of range, ldr < M, slab_rows < 0, row0 + N too large, a null or misaligned pointer; a
+ * short workspace: DBGSOM_ENOMEM with both sizes in the message) are reported before any launch. */
+size_t dbgsom_topk_cols_workspace_bytes(int64_t N, int64_t M, int k);
+int dbgsom_topk_cols_init(double *state_r_dev, int64_t *state_i_dev, int64_t M, int k, void *stream);
+int dbgsom_topk_cols(const double *R_dev, int64_t N, int64_t M, int64_t ldr, const int64_t *owner_dev, int64_t row0,
+                     int k, double *state_r_dev, int64_t *state_i_dev, void *workspace_dev, size_t workspace_bytes,
+                     void *stream);
+size_t dbgsom_exemplars_workspace_bytes(int64_t N, int64_t M, int k, int64_t slab_rows);
+int dbgsom_exemplars(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx_dev,
+                     const double *W_dev, int64_t M, const double *ww_dev, int k, int own_cell, int64_t slab_rows,
+                     int64_t *idx_dev, double *dist_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+/* The same on a context, each call staging its rows as its dbgsom_ctx_kneighbors_query* namesake does (chunks,
+ * query placement, CSR expanded chunk by chunk, the slab of "kneighbors_slab_rows" rows, status codes).  The state
+ * lives on the device for the length of the call and every chunk folds into it under its first row's number;
+ * nothing per chunk is staged or copied down.  M * k * 16 bytes of result come down, once, per host-facing call.
+ * _device: idx_dev / dist_dev are written by the kernel; nothing of X or of the result crosses PCIe.  Nq == 0
+ * returns DBGSOM_OK and writes nothing. */
+int dbgsom_ctx_exemplars_query(dbgsom_ctx *ctx, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                               const double *W_host, int64_t M, int k, int own_cell, int64_t *idx_host,
+                               double *dist_host);
+int dbgsom_ctx_exemplars_query_device(dbgsom_ctx *ctx, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d,
+                                      int64_t ldx, const double *W_host, int64_t M, int k, int own_cell,
+                                      int64_t *idx_dev, double *dist_dev);
+int dbgsom_ctx_exemplars_query_csr(dbgsom_ctx *ctx, const int64_t *indptr_host, const int32_t *indices_host,
+                                   const void *data_host, int x_dtype, int64_t Nq, int64_t d, int64_t nnz,
+                                   const double *W_host, int64_t M, int k, int own_cell, int64_t *idx_host,
+                                   double *dist_host);
+
 /* ---- fit on rows with missing entries (csrc/masked_fit.hip, csrc/smooth.hip) ---------------------------
  * One epoch on prototypes W (M x d, complete), hop matrix and sigma, NaN marking a missing entry of X:
  *   1. (dist_i, win_i): the masked search above with k = 1 -- every row goes through it, complete rows
