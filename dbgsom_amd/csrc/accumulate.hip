@@ -31,10 +31,10 @@
 namespace dbgsom {
 
 constexpr int AT = 256;          // threads per workgroup
-// samples per histogram / scatter workgroup: the scatter walks its samples 64 per round, one
-// dependent round after the other -- 2048 samples are 32 rounds (fine when there are thousands of
-// workgroups), a small sample set (C2, a rank's share in strong scaling) gets 512 = 8 rounds and
-// four times the workgroups (scatter_kernel 19 -> see DESIGN.md).  A function of N alone.
+// samples per histogram / scatter workgroup: a scatter wavefront walks its samples 64 per round, one
+// dependent round after the other -- 2048 samples are 32 rounds for one wavefront (scatter_kernel), 8 for
+// each of four (scatter4_kernel); a small sample set (C2, a rank's share in strong scaling) gets 512 =
+// 8 / 2 rounds and four times the workgroups.  A function of N alone.
 static int hs_for(int64_t N) { return N <= 300000 ? 512 : 2048; }
 constexpr int CH = 128;          // rows per segmented-sum chunk
 
@@ -47,6 +47,7 @@ struct AccWs {
     double *slab;         // maxchunks * (d + 2)   [partial S | partial K | partial E]
     double *gslab;        // M * finalize_groups(M) * (d + 2): second level of the ordered sum
     uint32_t *ticket;     // "last workgroup" ticket of the fused column / segment scan
+    uint32_t *oob;        // nb         per histogram workgroup: one of its winners is outside [0, M)
     int64_t nb, maxchunks;
 };
 
@@ -73,8 +74,10 @@ static size_t carve(AccWs *w, char *base, int64_t N, int64_t d, int64_t M, int n
     const size_t o_slab = take((size_t)maxchunks * (d + ns) * 8);
     const size_t o_gslab = take((size_t)M * finalize_groups(M) * (d + ns) * 8);
     const size_t o_ticket = take(256);
+    const size_t o_oob = take((size_t)nb * 4);
     if (w) {
         w->ticket = (uint32_t *)(base + o_ticket);
+        w->oob = (uint32_t *)(base + o_oob);
         w->order = (int32_t *)(base + o_order);
         w->blk = (uint32_t *)(base + o_blk);
         w->count = (uint32_t *)(base + o_count);
@@ -107,12 +110,17 @@ template <> struct WeightArg<true> {
 
 
 // ---- 1. per-workgroup histogram of winners ---------------------------------------------------
+// A winner outside [0, M) is counted nowhere; the workgroup leaves "I saw one" in oob[blockIdx.x], and the last
+// workgroup of the scan kernel STORES the status word from these flags: nothing has to clear the word in front of
+// the sort (that was a memset of four bytes, a 5 us hole in the stream), and every call gets its own status.
 __global__ __launch_bounds__(AT) void hist_kernel(const int64_t *__restrict__ win, int64_t N,
                                                   int M, uint32_t *__restrict__ blk,
-                                                  int32_t *__restrict__ status,
+                                                  uint32_t *__restrict__ oob,
                                                   uint32_t *__restrict__ ticket, int HS) {
     extern __shared__ uint32_t h[];
+    __shared__ uint32_t bad;
     if (blockIdx.x == 0 && threadIdx.x == 0) *ticket = 0u;  // of the scan kernel that follows
+    if (threadIdx.x == 0) bad = 0u;
     for (int j = threadIdx.x; j < M; j += AT) h[j] = 0;
     __syncthreads();
     const int64_t base = (int64_t)blockIdx.x * HS;
@@ -121,60 +129,91 @@ __global__ __launch_bounds__(AT) void hist_kernel(const int64_t *__restrict__ wi
         if (i < N) {
             const int64_t j = win[i];
             if (j >= 0 && j < M) atomicAdd(&h[j], 1u);
-            else if (status) atomicOr(status, 1);
+            else bad = 1u;
         }
     }
     __syncthreads();
     uint32_t *dst = blk + (size_t)blockIdx.x * M;
     for (int j = threadIdx.x; j < M; j += AT) dst[j] = h[j];
+    if (threadIdx.x == 0) oob[blockIdx.x] = bad;
 }
 
 // ---- 2. column scan over workgroups: blk -> exclusive offsets, count[j] ----------------------
 // A column is nb = N / HS entries long and its prefix is serial: CS_GROUPS threads share it (sum of
 // a group of consecutive workgroups each, prefix over the groups in LDS, then every thread rewrites
-// its group) -- 8 x fewer dependent load rounds than one thread per column.
-constexpr int CS_COLS = 32, CS_GROUPS = 8;
+// its group).  1024 threads per workgroup: 32 columns (one 128-byte line per row of the table) x 32 groups --
+// a thread's share of a column is nb / 32 entries.  Up to CS_BATCH of them are ONE batch of loads and stay in
+// registers for the rewrite (C4, C3: 489 rows, 16 per thread -- two memory round trips where 8 groups and two passes
+// of 8-entry batches made sixteen); longer shares walk twice in batches of 8.
+constexpr int CS_COLS = 32, CS_GROUPS = 32, CS_BATCH = 16;
+constexpr int CS_THREADS = CS_COLS * CS_GROUPS;
 __device__ __forceinline__ void colscan_body(uint32_t *__restrict__ blk, int64_t nb, int M,
                                              uint32_t *__restrict__ count) {
     __shared__ uint32_t part[CS_GROUPS][CS_COLS];
     const int c = threadIdx.x % CS_COLS, g = threadIdx.x / CS_COLS;
     const int j = blockIdx.x * CS_COLS + c;
+    const int jc = min(j, M - 1);   // (columns behind M: loads clamped, nothing stored)
     const int64_t len = (nb + CS_GROUPS - 1) / CS_GROUPS;
     const int64_t b0 = min(nb, (int64_t)g * len), b1 = min(nb, b0 + len);
+    const bool one = len <= CS_BATCH;   // (uniform)
     uint32_t sum = 0;
-    if (j < M) {
+    uint32_t v[CS_BATCH];
+    if (one) {
+#pragma unroll
+        for (int u = 0; u < CS_BATCH; ++u) v[u] = blk[(size_t)min(b0 + u, nb - 1) * M + jc];
+#pragma unroll
+        for (int u = 0; u < CS_BATCH; ++u) {
+            v[u] = (b0 + u < b1) ? v[u] : 0u;
+            sum += v[u];
+        }
+    } else if (j < M) {
         int64_t b = b0;
         for (; b + 8 <= b1; b += 8) {  // 8 independent loads in flight
-            uint32_t v[8];
+            uint32_t x[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = blk[(size_t)(b + u) * M + j];
+            for (int u = 0; u < 8; ++u) x[u] = blk[(size_t)(b + u) * M + j];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) sum += v[u];
+            for (int u = 0; u < 8; ++u) sum += x[u];
         }
         for (; b < b1; ++b) sum += blk[(size_t)b * M + j];
     }
     part[g][c] = sum;
     __syncthreads();
     uint32_t run = 0;
-    for (int u = 0; u < g; ++u) run += part[u][c];
+#pragma unroll
+    for (int u = 0; u < CS_GROUPS; ++u) {   // (every read issued, the groups in front selected)
+        const uint32_t x = part[u][c];
+        run += (u < g) ? x : 0u;
+    }
     if (j >= M) return;
     if (g == CS_GROUPS - 1) count[j] = run + sum;
+    if (one) {
+#pragma unroll
+        for (int u = 0; u < CS_BATCH; ++u) {
+            if (b0 + u < b1) blk[(size_t)(b0 + u) * M + j] = run;
+            run += v[u];
+        }
+        return;
+    }
     int64_t b = b0;
     for (; b + 8 <= b1; b += 8) {
-        uint32_t v[8];
+        uint32_t x[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = blk[(size_t)(b + u) * M + j];
+        for (int u = 0; u < 8; ++u) x[u] = blk[(size_t)(b + u) * M + j];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) { blk[(size_t)(b + u) * M + j] = run; run += v[u]; }
+        for (int u = 0; u < 8; ++u) { blk[(size_t)(b + u) * M + j] = run; run += x[u]; }
     }
     for (; b < b1; ++b) {
-        const uint32_t v = blk[(size_t)b * M + j];
+        const uint32_t x = blk[(size_t)b * M + j];
         blk[(size_t)b * M + j] = run;
-        run += v;
+        run += x;
     }
 }
 
 // ---- 3. exclusive scans over the M neurons (one workgroup of NTHR threads) ----------------------
+// A thread's range of neurons is SS_BATCH counts at most on any map the library takes (one batch of loads, kept
+// for the second walk); longer ranges walk the table twice.
+constexpr int SS_BATCH = 16;
 template <int NTHR>
 __device__ __forceinline__ void segscan_body(const uint32_t *__restrict__ count, int M,
                                              uint32_t *__restrict__ seg_start,
@@ -184,8 +223,20 @@ __device__ __forceinline__ void segscan_body(const uint32_t *__restrict__ count,
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     const int per = (M + NTHR - 1) / NTHR;
     const int lo = min(M, t * per), hi = min(M, lo + per);
+    const bool one = per <= SS_BATCH;   // (uniform)
+    uint32_t cv[SS_BATCH];
     uint32_t a = 0, b = 0;
-    for (int j = lo; j < hi; ++j) { a += count[j]; b += (count[j] + CH - 1) / CH; }
+    if (one) {
+#pragma unroll
+        for (int u = 0; u < SS_BATCH; ++u) cv[u] = count[min(lo + u, M - 1)];
+#pragma unroll
+        for (int u = 0; u < SS_BATCH; ++u) {
+            cv[u] = (lo + u < hi) ? cv[u] : 0u;
+            a += cv[u]; b += (cv[u] + CH - 1) / CH;
+        }
+    } else {
+        for (int j = lo; j < hi; ++j) { a += count[j]; b += (count[j] + CH - 1) / CH; }
+    }
     uint32_t ia = a, ib = b;  // inclusive scan over the wavefront, then over the wavefronts
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
@@ -195,9 +246,21 @@ __device__ __forceinline__ void segscan_body(const uint32_t *__restrict__ count,
     if (lane == 63) { wa[wv] = ia; wb[wv] = ib; }
     __syncthreads();
     uint32_t pa = 0, pb = 0;
-    for (int u = 0; u < wv; ++u) { pa += wa[u]; pb += wb[u]; }
+#pragma unroll
+    for (int u = 0; u < NWAVE; ++u) {
+        const uint32_t xa = wa[u], xb = wb[u];
+        pa += (u < wv) ? xa : 0u; pb += (u < wv) ? xb : 0u;
+    }
     if (t == NTHR - 1) { seg_start[M] = pa + ia; chunk_pre[M] = pb + ib; }
     a = pa + ia - a; b = pb + ib - b;  // exclusive prefix of this thread's range
+    if (one) {
+#pragma unroll
+        for (int u = 0; u < SS_BATCH; ++u) {
+            if (lo + u < hi) { seg_start[lo + u] = a; chunk_pre[lo + u] = b; }
+            a += cv[u]; b += (cv[u] + CH - 1) / CH;
+        }
+        return;
+    }
     for (int j = lo; j < hi; ++j) {
         seg_start[j] = a; chunk_pre[j] = b;
         a += count[j]; b += (count[j] + CH - 1) / CH;
@@ -205,14 +268,30 @@ __device__ __forceinline__ void segscan_body(const uint32_t *__restrict__ count,
 }
 
 // column scan (2.) and, in the workgroup that finishes last, the scans over the neurons (3.): they
-// need every column's count, and a kernel of their own is one 5 us launch more per sort
-__global__ __launch_bounds__(CS_COLS * CS_GROUPS) void scan_kernel(uint32_t *__restrict__ blk, int64_t nb, int M,
-                                                                   uint32_t *__restrict__ count,
-                                                                   uint32_t *__restrict__ seg_start,
-                                                                   uint32_t *__restrict__ chunk_pre,
-                                                                   uint32_t *__restrict__ ticket) {
+// need every column's count, and a kernel of their own is one 5 us launch more per sort.  The same workgroup
+// stores the status word from the histogram workgroups' flags (hist_kernel).
+__global__ __launch_bounds__(CS_THREADS) void scan_kernel(uint32_t *__restrict__ blk, int64_t nb, int M,
+                                                         uint32_t *__restrict__ count,
+                                                         uint32_t *__restrict__ seg_start,
+                                                         uint32_t *__restrict__ chunk_pre,
+                                                         uint32_t *__restrict__ ticket,
+                                                         const uint32_t *__restrict__ oob,
+                                                         int32_t *__restrict__ status) {
     colscan_body(blk, nb, M, count);
-    if (last_workgroup_done(ticket, gridDim.x)) segscan_body<CS_COLS * CS_GROUPS>(count, M, seg_start, chunk_pre);
+    if (!last_workgroup_done(ticket, gridDim.x)) return;
+    uint32_t any = 0;
+    if (status) {
+        for (int64_t b0 = 0; b0 < nb; b0 += 4 * CS_THREADS) {
+            uint32_t f[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) f[u] = oob[min(b0 + u * CS_THREADS + threadIdx.x, nb - 1)];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) any |= f[u];   // (a clamped load repeats the last flag: the OR is the same)
+        }
+    }
+    segscan_body<CS_THREADS>(count, M, seg_start, chunk_pre);
+    const int bad = __syncthreads_or((int)any);
+    if (status && threadIdx.x == 0) *status = bad ? 1 : 0;
 }
 
 // ---- 4. stable scatter of sample ids into their neuron's segment -----------------------------
@@ -258,6 +337,84 @@ __global__ __launch_bounds__(SCW) void scatter_kernel(const int64_t *__restrict_
         __syncthreads();  // every position of this round has been read from cnt
         if (key >= 0 && before == 0) cnt[key] += (uint32_t)__popcll(peers);  // one lane per key
         __syncthreads();
+    }
+}
+
+// Four wavefronts per workgroup of HS samples: wavefront w takes the w-th quarter, in sample order, with running
+// write positions of its OWN in LDS (cnt[w][.]) -- HS / 256 dependent rounds instead of HS / 64, and no workgroup
+// barrier inside them: the LDS operations of one wavefront complete in program order, so the round's reads of
+// cnt[w][key] are served before its adds, and those before the next round's reads.
+// A first pass counts every wavefront's keys (integer LDS atomics: any order, the same counts); wavefront w then
+// starts key k at seg_start[k] + this workgroup's block offset + the counts of the wavefronts in front of it: the
+// order stays the stable one by (winner, row).
+// 4 M counters = 16 M bytes of LDS: maps above SC4_MAX_M (where that leaves fewer than two workgroups per CU) keep
+// the one-wavefront kernel.
+constexpr int SC4 = 4;
+constexpr int SC4_MAX_M = 160 * 1024 / 2 / (SC4 * 4);
+template <int HS>
+__global__ __launch_bounds__(SC4 * SCW) void scatter4_kernel(const int64_t *__restrict__ win, int64_t N,
+                                                             int M, int nbits,
+                                                             const uint32_t *__restrict__ blk,
+                                                             const uint32_t *__restrict__ seg_start,
+                                                             int32_t *__restrict__ order) {
+    extern __shared__ uint32_t cnt[];  // [SC4][M]
+    constexpr int Q = HS / SC4, R = Q / SCW;
+    const int t = threadIdx.x, lane = t & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int64_t base = (int64_t)blockIdx.x * HS + wv * Q;
+    int keys[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {  // all of the wavefront's keys are in flight at once
+        const int64_t i = base + r * SCW + lane;
+        int64_t j = -1;
+        if (i < N) j = win[i];
+        keys[r] = (j >= 0 && j < M) ? (int)j : -1;
+    }
+    for (int j = t; j < SC4 * M; j += SC4 * SCW) cnt[j] = 0u;
+    __syncthreads();
+    uint32_t *mine = cnt + (size_t)wv * M;
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+        if (keys[r] >= 0) atomicAdd(&mine[keys[r]], 1u);
+    __syncthreads();
+    const uint32_t *off = blk + (size_t)blockIdx.x * M;
+    for (int j0 = 0; j0 < M; j0 += 4 * SC4 * SCW) {
+        uint32_t p[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int jc = min(j0 + u * SC4 * SCW + t, M - 1);
+            p[u] = seg_start[jc] + off[jc];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int j = j0 + u * SC4 * SCW + t;
+            if (j < M) {
+                uint32_t run = p[u];
+#pragma unroll
+                for (int w = 0; w < SC4; ++w) {
+                    const uint32_t c = cnt[(size_t)w * M + j];
+                    cnt[(size_t)w * M + j] = run;
+                    run += c;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const uint64_t lt = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int key = keys[r];
+        uint64_t peers = __builtin_amdgcn_ballot_w64(key >= 0);
+        for (int b = 0; b < nbits; ++b) {
+            const bool bit = (key >> b) & 1;
+            const uint64_t m = __builtin_amdgcn_ballot_w64(bit);
+            peers &= bit ? m : ~m;
+        }
+        const uint64_t before = peers & lt;
+        if (key >= 0) order[mine[key] + (uint32_t)__popcll(before)] = (int32_t)(base + r * SCW + lane);
+        __builtin_amdgcn_wave_barrier();   // (program order of the LDS read above and the add below)
+        if (key >= 0 && before == 0) mine[key] += (uint32_t)__popcll(peers);  // one lane per key
+        __builtin_amdgcn_wave_barrier();
     }
 }
 // (non-temporal: every row is read exactly once by this kernel, 16 bytes per lane and whole cache lines per
@@ -780,7 +937,8 @@ static int key_bits(int64_t M) {  // bits that tell the keys 0 .. M - 1 apart
 size_t bucket_sort_workspace_bytes(int64_t N, int64_t M) {
     const int HS = hs_for(N);
     const int64_t nb = (N + HS - 1) / HS;
-    return align_up((size_t)nb * M * 4) + align_up((size_t)M * 4) + 2 * align_up((size_t)(M + 1) * 4) + 256;
+    return align_up((size_t)nb * M * 4) + align_up((size_t)M * 4) + 2 * align_up((size_t)(M + 1) * 4) + 256 +
+           align_up((size_t)nb * 4);   // (blk, count, seg_start, chunk_pre, ticket, the histogram workgroups' flags)
 }
 
 // where launch_bucket_sort leaves the exclusive segment starts (M + 1 entries) in its workspace
@@ -805,14 +963,32 @@ void bucket_sort_tables(const void *ws, int64_t N, int64_t M, const uint32_t **c
 }
 int accumulate_chunk_rows() { return CH; }
 
-static void launch_scatter(const int64_t *idx, int64_t N, int Mi, int64_t nb, const uint32_t *blk,
+template <int HS>
+static int launch_scatter4(const int64_t *idx, int64_t N, int Mi, int64_t nb, const uint32_t *blk,
                            const uint32_t *seg_start, int32_t *order, hipStream_t s) {
+    static bool attr_set = false;   // (16 M bytes of LDS: above the default limit from M = 4097 on)
+    if (!attr_set) {
+        DBGSOM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&scatter4_kernel<HS>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, SC4_MAX_M * SC4 * 4));
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(scatter4_kernel<HS>, dim3((unsigned)nb), dim3(SC4 * SCW), (size_t)Mi * SC4 * 4, s, idx, N, Mi,
+                       key_bits(Mi), blk, seg_start, order);
+    return DBGSOM_OK;
+}
+
+static int launch_scatter(const int64_t *idx, int64_t N, int Mi, int64_t nb, const uint32_t *blk,
+                          const uint32_t *seg_start, int32_t *order, hipStream_t s) {
+    if (Mi <= SC4_MAX_M)
+        return hs_for(N) == 512 ? launch_scatter4<512>(idx, N, Mi, nb, blk, seg_start, order, s)
+                                : launch_scatter4<2048>(idx, N, Mi, nb, blk, seg_start, order, s);
     if (hs_for(N) == 512)
         hipLaunchKernelGGL(scatter_kernel<512>, dim3((unsigned)nb), dim3(SCW), (size_t)Mi * 4, s, idx, N, Mi,
                            key_bits(Mi), blk, seg_start, order);
     else
         hipLaunchKernelGGL(scatter_kernel<2048>, dim3((unsigned)nb), dim3(SCW), (size_t)Mi * 4, s, idx, N, Mi,
                            key_bits(Mi), blk, seg_start, order);
+    return DBGSOM_OK;
 }
 
 int launch_bucket_sort(const int64_t *idx, int64_t N, int64_t M, int32_t *order, void *ws,
@@ -829,12 +1005,14 @@ int launch_bucket_sort(const int64_t *idx, int64_t N, int64_t M, int32_t *order,
     uint32_t *chunk_pre = (uint32_t *)base;
     base += align_up((size_t)(M + 1) * 4);
     uint32_t *ticket = (uint32_t *)base;
+    base += 256;
+    uint32_t *oob = (uint32_t *)base;
     const int Mi = (int)M;
-    hipLaunchKernelGGL(hist_kernel, dim3((unsigned)nb), dim3(AT), (size_t)M * 4, s, idx, N, Mi, blk,
-                       (int32_t *)nullptr, ticket, HS);
-    hipLaunchKernelGGL(scan_kernel, dim3((unsigned)((M + CS_COLS - 1) / CS_COLS)),
-                       dim3(CS_COLS * CS_GROUPS), 0, s, blk, nb, Mi, count, seg_start, chunk_pre, ticket);
-    launch_scatter(idx, N, Mi, nb, blk, seg_start, order, s);
+    hipLaunchKernelGGL(hist_kernel, dim3((unsigned)nb), dim3(AT), (size_t)M * 4, s, idx, N, Mi, blk, oob, ticket, HS);
+    hipLaunchKernelGGL(scan_kernel, dim3((unsigned)((M + CS_COLS - 1) / CS_COLS)), dim3(CS_THREADS), 0, s, blk, nb, Mi,
+                       count, seg_start, chunk_pre, ticket, (const uint32_t *)oob, (int32_t *)nullptr);
+    const int rc = launch_scatter(idx, N, Mi, nb, blk, seg_start, order, s);
+    if (rc != DBGSOM_OK) return rc;
     return launch_status("bucket sort kernels");
 }
 
@@ -873,8 +1051,8 @@ static int accumulate_impl(const void *X, int x_dtype, int64_t N, int64_t d, int
     DBGSOM_REQUIRE(M >= 1 && M <= DBGSOM_MAX_PROTOTYPES, "M outside [1, DBGSOM_MAX_PROTOTYPES]");
     DBGSOM_REQUIRE(sums, "null sums");
     DBGSOM_REQUIRE(!status_behind_sums || status, "the status flag is needed behind the sums");
-    if (status) DBGSOM_HIP_CHECK(hipMemsetAsync(status, 0, sizeof(int32_t), s));
-    if (N == 0) {
+    if (N == 0) {   // (no sort, nobody to store the status word)
+        if (status) DBGSOM_HIP_CHECK(hipMemsetAsync(status, 0, sizeof(int32_t), s));
         DBGSOM_HIP_CHECK(hipMemsetAsync(sums, 0, (size_t)(M * (d + 3) + (status_behind_sums ? 1 : 0)) * sizeof(double), s));
         return DBGSOM_OK;
     }
@@ -890,11 +1068,13 @@ static int accumulate_impl(const void *X, int x_dtype, int64_t N, int64_t d, int
     const int Mi = (int)M, di = (int)d;
 
     hipLaunchKernelGGL(hist_kernel, dim3((unsigned)w.nb), dim3(AT), (size_t)M * 4, s, idx, N, Mi,
-                       w.blk, status, w.ticket, hs_for(N));
-    hipLaunchKernelGGL(scan_kernel, dim3((unsigned)((M + CS_COLS - 1) / CS_COLS)),
-                       dim3(CS_COLS * CS_GROUPS), 0, s, w.blk, w.nb, Mi, w.count, w.seg_start, w.chunk_pre,
-                       w.ticket);
-    launch_scatter(idx, N, Mi, w.nb, w.blk, w.seg_start, w.order, s);
+                       w.blk, w.oob, w.ticket, hs_for(N));
+    hipLaunchKernelGGL(scan_kernel, dim3((unsigned)((M + CS_COLS - 1) / CS_COLS)), dim3(CS_THREADS), 0, s, w.blk, w.nb,
+                       Mi, w.count, w.seg_start, w.chunk_pre, w.ticket, (const uint32_t *)w.oob, status);
+    {
+        const int rc = launch_scatter(idx, N, Mi, w.nb, w.blk, w.seg_start, w.order, s);
+        if (rc != DBGSOM_OK) return rc;
+    }
 
     const size_t xe = dtype_size(x_dtype);
     const bool al16 = is_aligned(X, 16) && ((ldx * xe) % 16 == 0);

@@ -79,6 +79,38 @@ __device__ __forceinline__ bool last_workgroup_done(uint32_t *ticket, uint32_t n
     return is_last_ != 0;
 }
 
+// A value loaded ahead of a guarded use counts as used where this stands: the compiler cannot move its load behind the
+// guard (where it would be waited for on its own); the wait for the value moves up to here instead.
+__device__ __forceinline__ void keep_load(const double &v) { asm volatile("" ::"v"(v)); }
+__device__ __forceinline__ void keep_load(const float &v) { asm volatile("" ::"v"(v)); }
+
+// change_total = sum_i rowchg[i] by ONE workgroup of 256 threads, in the fixed order of a 1024-leaf strided binary
+// tree: leaf l adds rowchg[l], rowchg[l + 1024], ... in that order, thread t holds the leaves t + 256 u and joins
+// them as (p0 + p2) + (p1 + p3) (tree levels 512 and 256), then the levels 128 .. 1 in LDS -- bitwise reproducible.
+// The four leaves' loads of a trip go out together.  The sum is returned in thread 0.
+__device__ __forceinline__ double change_total_tree(const double *__restrict__ rowchg, int M) {
+    __shared__ double tot_[256];
+    const int t = threadIdx.x;
+    double p[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int j0 = 0; j0 < M; j0 += 1024) {
+        double v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = rowchg[min(j0 + 256 * u + t, M - 1)];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            keep_load(v[u]);
+            if (j0 + 256 * u + t < M) p[u] += v[u];
+        }
+    }
+    tot_[t] = (p[0] + p[2]) + (p[1] + p[3]);
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (t < w) tot_[t] += tot_[t + w];
+        __syncthreads();
+    }
+    return tot_[0];
+}
+
 inline bool valid_dtype(int dt) { return dt == DBGSOM_F32 || dt == DBGSOM_F64 || dt == DBGSOM_BF16; }
 inline size_t dtype_size(int dt) { return dt == DBGSOM_F64 ? 8 : (dt == DBGSOM_F32 ? 4 : 2); }
 
@@ -388,7 +420,11 @@ int launch_anchor_runs(const void *X, int x_dtype, int64_t N, int64_t d, int64_t
 size_t smooth_workspace_bytes(int64_t M, int64_t d);
 int launch_smooth(const double *sums, int64_t M, int64_t d, const float *hop, double sigma,
                   int layout, const double *W_old, double *W_new, double *change_total, void *ws,
-                  size_t ws_bytes, hipStream_t s);
+                  size_t ws_bytes, hipStream_t s, bool total_by_caller = false);
+// The row changes |W_i - W'_i|_2 a smoothing launch left in its workspace (M values).  total_by_caller (above) and a
+// null change_total of launch_rowchange_blocks: no launch forms their sum -- a later kernel of the caller's does, with
+// change_total_tree (the epoch's pack_results_kernel: one launch less per epoch).
+const double *smooth_rowchg(const void *ws, int64_t M, int64_t d);
 // smoothing sharded over the ranks (smooth.hip): column blocks of cb = smooth_block_cols columns; one block
 // of the reduce-scatter buffer = S block (M x cb) = smooth_block_elems values; [K | a | E | status] stay in `sums`
 int64_t smooth_block_cols(int64_t d, int nranks);

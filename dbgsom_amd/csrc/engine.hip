@@ -125,13 +125,19 @@ __global__ void u64_to_f64_kernel(const unsigned long long *__restrict__ in, dou
 // out = [a (M) | E (M) | change_total | status | sum of candidate-list lengths | the same of a pruning probe |
 //        workgroups of the pruning form with long lists | workgroups anchor_mark_kernel handed over (the lean form:
 //        long lists it kept)]
-__global__ void pack_results_kernel(const double *__restrict__ aE, int64_t M, const double *__restrict__ chg,
-                                    const double *__restrict__ status, const unsigned long long *__restrict__ list_sum,
-                                    double *__restrict__ out) {
+// change_total is formed here, by the first workgroup, from the row changes the smoothing left (change_total_tree:
+// the launch and the ticket the row-change kernel used to spend on it are gone).  Workgroups of 256 threads.
+__global__ __launch_bounds__(256) void pack_results_kernel(const double *__restrict__ aE, int64_t M,
+                                                           const double *__restrict__ rowchg,
+                                                           const double *__restrict__ status,
+                                                           const unsigned long long *__restrict__ list_sum,
+                                                           double *__restrict__ out) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < 2 * M; i += (int64_t)gridDim.x * blockDim.x)
         out[i] = aE[i];
+    double chg = 0.0;
+    if (blockIdx.x == 0) chg = change_total_tree(rowchg, (int)M);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        out[2 * M] = chg[0];
+        out[2 * M] = chg;
         out[2 * M + 1] = status[0];
         out[2 * M + 2] = list_sum ? (double)list_sum[0] : 0.0;
         out[2 * M + 3] = list_sum ? (double)list_sum[1] : 0.0;  // (of a counting-only pruning launch)
@@ -1039,7 +1045,6 @@ int smooth_and_fetch(dbgsom_ctx *c, int64_t M, double sigma, int layout, int fla
     void *sm_ws = nullptr;
     size_t sm_ws_bytes = 0;
     TRY(smooth_ws(c, M, dp, &sm_ws, &sm_ws_bytes));
-    double *chg = c->scal.as<double>();
     double *sums = c->sums.as<double>();
     if (c->sums_sharded) {
         const int G = c->coll_nranks, r = c->coll_rank;
@@ -1050,13 +1055,13 @@ int smooth_and_fetch(dbgsom_ctx *c, int64_t M, double sigma, int layout, int fla
         TRY(launch_smooth_block(mine, sums + (size_t)M * dp, sums + (size_t)M * dp + M, M, cb, dp, c->hop.as<float>(), sigma,
                                 layout, gather + (size_t)r * M * cb, sm_ws, sm_ws_bytes, c->stream));
         TRY(run_block_collective(c, DBGSOM_COLL_ALLGATHER, gather, M * cb));
-        TRY(launch_rowchange_blocks(gather, M, dp, cb, c->Wb[c->cur].as<double>(), c->Wb[nxt].as<double>(), chg, sm_ws,
+        TRY(launch_rowchange_blocks(gather, M, dp, cb, c->Wb[c->cur].as<double>(), c->Wb[nxt].as<double>(), nullptr, sm_ws,
                                     c->stream));
         c->sums_sharded = false;
         ++c->shard_epochs;
     } else {
         TRY(launch_smooth(sums, M, dp, c->hop.as<float>(), sigma, layout, c->Wb[c->cur].as<double>(),
-                          c->Wb[nxt].as<double>(), chg, sm_ws, sm_ws_bytes, c->stream));
+                          c->Wb[nxt].as<double>(), nullptr, sm_ws, sm_ws_bytes, c->stream, true));
     }
     mark(c, 3);
     // the epoch's small results: one kernel writes them into mapped page-locked memory, one stream
@@ -1066,7 +1071,7 @@ int smooth_and_fetch(dbgsom_ctx *c, int64_t M, double sigma, int layout, int fla
     const unsigned long long *list_sum =
         c->last_filtered ? dbgsom_filter_count_sum_ptr(c->filt_ws.p, s.N, dp, M) : nullptr;
     hipLaunchKernelGGL(pack_results_kernel, dim3((unsigned)((2 * M + 255) / 256 < 64 ? (2 * M + 255) / 256 : 64)), dim3(256), 0,
-                       c->stream, sums + (size_t)M * dp + M, M, chg, sums + (size_t)M * (dp + 3), list_sum,
+                       c->stream, sums + (size_t)M * dp + M, M, smooth_rowchg(sm_ws, M, dp), sums + (size_t)M * (dp + 3), list_sum,
                        reinterpret_cast<double *>(c->tail.dev));
     TRY(launch_status("pack_results_kernel"));
     if (W_new_host) {

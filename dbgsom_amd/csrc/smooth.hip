@@ -24,7 +24,6 @@ struct SmoothWs {
     double *G;      // M x Mp  h * a^T
     double *den;    // M
     double *rowchg; // M
-    uint32_t *ticket;  // "last workgroup" ticket of the row-change kernel
     double *part;   // splits x M x d   partial products of the split-K GEMM (splits > 1)
 };
 
@@ -45,16 +44,21 @@ static size_t carve_smooth(SmoothWs *w, char *base, int64_t M, int64_t d) {
     auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
     const int64_t Mp = smooth_mp(M);
     const size_t oC = take(((size_t)Mp * d + 64) * 8), oG = take(((size_t)M * Mp + 16) * 8);
-    const size_t oD = take((size_t)M * 8), oR = take((size_t)M * 8), oK = take((size_t)M * 4);
+    const size_t oD = take((size_t)M * 8), oR = take((size_t)M * 8);
     const int ks = gemm_splits(M, d);
     const size_t oP = take(ks > 1 ? (size_t)ks * M * d * 8 : 0);
     if (w) {
         w->part = (double *)(base + oP);
         w->C = (double *)(base + oC); w->G = (double *)(base + oG);
         w->den = (double *)(base + oD); w->rowchg = (double *)(base + oR);
-        w->ticket = (uint32_t *)(base + oK);
     }
     return off;
+}
+
+const double *smooth_rowchg(const void *ws, int64_t M, int64_t d) {
+    SmoothWs w;
+    carve_smooth(&w, (char *)const_cast<void *>(ws), M, d);
+    return w.rowchg;
 }
 
 size_t smooth_workspace_bytes(int64_t M, int64_t d) {
@@ -69,38 +73,56 @@ size_t smooth_workspace_bytes(int64_t M, int64_t d) {
 //                     neurons') are zero-filled by the workgroup of the same number;
 //                     row j of G = exp(-(hop^2 / (2 sigma^2))) * a and den[j] = its sum (fixed tree).
 // The rank of a neuron is a count over a[0 .. j): every workgroup counts for itself (M reads).
+// Every stage issues the loads of PB trips of its loop before the first use (a trip's load used to be waited for on
+// its own: the kernel was a chain of memory round trips); indices behind the end are clamped for the load and the
+// value is dropped (keep_load: or the compiler moves a load behind the guard of its use, a round trip of its own).
+// The counts are integers -- per-wavefront ballots and popcounts, one LDS step across the four wavefronts; the sum
+// behind den[i] keeps its order (thread partials over j = t, t + 256, ..., then the tree).
+constexpr int PB = 4;
 __global__ __launch_bounds__(256) void smooth_prep_kernel(const double *__restrict__ S,
                                                           const double *__restrict__ K,
                                                           const double *__restrict__ a,
                                                           const float *__restrict__ hop, int M, int d,
                                                           int layout, double two_sigma_sq,
                                                           double *__restrict__ C, double *__restrict__ G,
-                                                          double *__restrict__ den,
-                                                          uint32_t *__restrict__ ticket, int Mp) {
+                                                          double *__restrict__ den, int Mp) {
     __shared__ double red[256];
-    __shared__ int cnt[256], cnt_all[256];
+    __shared__ int cnt[4], cnt_all[4];
     const int i = blockIdx.x, t = threadIdx.x;
-    if (i == 0 && t == 0) *ticket = 0u;  // of the row-change kernel behind the GEMM
+    const double a_i = a[i], k = K[i];
     // non-empty neurons before i, and in all
-    int before = 0, all = 0;
-    for (int j = t; j < M; j += 256) {
-        const int ne = a[j] > 0.0;
-        all += ne;
-        before += (j < i) ? ne : 0;
+    int before = 0, all = 0;   // (of this wavefront: uniform)
+    for (int j0 = 0; j0 < M; j0 += 256 * PB) {
+        double av[PB];
+#pragma unroll
+        for (int u = 0; u < PB; ++u) av[u] = a[min(j0 + 256 * u + t, M - 1)];
+#pragma unroll
+        for (int u = 0; u < PB; ++u) {
+            const int j = j0 + 256 * u + t;
+            const bool ne = j < M && av[u] > 0.0;
+            all += __popcll(__builtin_amdgcn_ballot_w64(ne));
+            before += __popcll(__builtin_amdgcn_ballot_w64(ne && j < i));
+        }
     }
-    cnt[t] = before;
-    cnt_all[t] = all;
+    if ((t & 63) == 0) { cnt[t >> 6] = before; cnt_all[t >> 6] = all; }
     __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (t < w) { cnt[t] += cnt[t + w]; cnt_all[t] += cnt_all[t + w]; }
-        __syncthreads();
-    }
-    const int rank = cnt[0], nne = cnt_all[0];
-    const bool alive = a[i] > 0.0;
+    const int rank = (cnt[0] + cnt[1]) + (cnt[2] + cnt[3]), nne = (cnt_all[0] + cnt_all[1]) + (cnt_all[2] + cnt_all[3]);
+    const bool alive = a_i > 0.0;
     if (alive) {
         const int dst = (layout == DBGSOM_CENTRES_COMPACT) ? rank : i;
-        const double k = K[i];
-        for (int c = t; c < d; c += 256) C[(size_t)dst * d + c] = S[(size_t)i * d + c] / k;
+        const double *src = S + (size_t)i * d;
+        double *out = C + (size_t)dst * d;
+        for (int c0 = 0; c0 < d; c0 += 256 * PB) {
+            double sv[PB];
+#pragma unroll
+            for (int u = 0; u < PB; ++u) sv[u] = src[min(c0 + 256 * u + t, d - 1)];
+#pragma unroll
+            for (int u = 0; u < PB; ++u) {
+                const int c = c0 + 256 * u + t;
+                keep_load(sv[u]);
+                if (c < d) out[c] = sv[u] / k;
+            }
+        }
     }
     const bool zero_row = (layout == DBGSOM_CENTRES_COMPACT) ? (i >= nne) : !alive;
     if (zero_row)
@@ -108,14 +130,31 @@ __global__ __launch_bounds__(256) void smooth_prep_kernel(const double *__restri
     if (i == 0)  // (the zero rows of C behind row M)
         for (int e = t; e < (Mp - M) * d; e += 256) C[(size_t)M * d + e] = 0.0;
     double s = 0.0;
-    for (int j = t; j < Mp; j += 256) {
-        double g = 0.0;
-        if (j < M) {
-            const double h = (double)hop[(size_t)i * M + j];
-            g = exp(-((h * h) / two_sigma_sq)) * a[j];
-            s += g;
+    const float *hrow = hop + (size_t)i * M;
+    for (int j0 = 0; j0 < Mp; j0 += 256 * PB) {
+        float hv[PB];
+        double av[PB];
+#pragma unroll
+        for (int u = 0; u < PB; ++u) {
+            const int jc = min(j0 + 256 * u + t, M - 1);
+            hv[u] = hrow[jc];
+            av[u] = a[jc];
         }
-        G[(size_t)i * Mp + j] = g;
+#pragma unroll
+        for (int u = 0; u < PB; ++u) {
+            const int j = j0 + 256 * u + t;
+            keep_load(hv[u]);
+            keep_load(av[u]);
+            if (j < Mp) {
+                double g = 0.0;
+                if (j < M) {
+                    const double h = (double)hv[u];
+                    g = exp(-((h * h) / two_sigma_sq)) * av[u];
+                    s += g;
+                }
+                G[(size_t)i * Mp + j] = g;
+            }
+        }
     }
     red[t] = s;
     __syncthreads();
@@ -340,57 +379,86 @@ __global__ __launch_bounds__(256) void smooth_gemm_generic_kernel(const double *
 }
 
 // rowchg[i] = |W_i - W'_i|_2; with a split-K GEMM, W'_i is first put together from the pieces (in
-// piece order) and divided by den[i].  One wavefront per row, four rows per workgroup (a quarter of the
-// tickets, no LDS tree per row: the launch took 28 us for 1024 rows of 784 with a workgroup per row); the
-// squares are added per lane in column order and across the lanes in a fixed butterfly.
-constexpr int RC_ROWS = 4;
+// piece order) and divided by den[i].  One wavefront per row, four rows per workgroup (no LDS tree per row: the
+// launch took 28 us for 1024 rows of 784 with a workgroup per row); the squares are added per lane in column
+// order and across the lanes in a fixed butterfly.
+// A wavefront walks its row in batches of RC_TRIPS column trips and issues every load of a batch -- all NP pieces
+// and W -- before the first dependent add (one round trip per batch instead of NP + 1 per trip); columns behind
+// the row's end are clamped for the load and take no part in anything else (keep_load: or the compiler moves a
+// trip's loads behind the guard of their use -- a round trip per trip again).  NP = split-K pieces (1: W' is read).
+constexpr int RC_ROWS = 4, RC_TRIPS = 4, RC_MAX_PIECES = 8;
+template <int NP>
 __global__ __launch_bounds__(256) void rowchange_kernel(const double *__restrict__ Wo,
                                                         double *__restrict__ Wn, int M, int d,
-                                                        int splits, const double *__restrict__ part,
+                                                        const double *__restrict__ part,
                                                         const double *__restrict__ den,
-                                                        double *__restrict__ rowchg,
-                                                        uint32_t *__restrict__ ticket,
-                                                        double *__restrict__ change_total) {
+                                                        double *__restrict__ rowchg) {
     const int t = threadIdx.x, lane = t & 63;
     const int i = blockIdx.x * RC_ROWS + (t >> 6);
-    if (i < M) {
-        double s = 0.0;
-        const double dn = den[i];
-        for (int c = lane; c < d; c += 64) {
-            double wn;
-            if (splits == 1) {
-                wn = Wn[(size_t)i * d + c];
+    if (i >= M) return;
+    double s = 0.0;
+    const double dn = den[i];
+    const size_t row = (size_t)i * d, piece = (size_t)M * d;
+    for (int c0 = lane; c0 < d; c0 += 64 * RC_TRIPS) {
+        double pv[RC_TRIPS][NP], wo[RC_TRIPS];
+#pragma unroll
+        for (int u = 0; u < RC_TRIPS; ++u) {
+            const int cc = min(c0 + 64 * u, d - 1);
+            if constexpr (NP == 1) {
+                pv[u][0] = Wn[row + cc];
             } else {
-                double p = part[(size_t)i * d + c];
-                for (int z = 1; z < splits; ++z) p += part[((size_t)z * M + i) * d + c];
-                wn = p / dn;
-                Wn[(size_t)i * d + c] = wn;
+#pragma unroll
+                for (int z = 0; z < NP; ++z) pv[u][z] = part[(size_t)z * piece + row + cc];
             }
-            const double df = Wo[(size_t)i * d + c] - wn;
-            s += df * df;
+            wo[u] = Wo[row + cc];
         }
 #pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
-        if (lane == 0) rowchg[i] = sqrt(s);
-    }
-    // change_total = sum_i rowchg[i]: the workgroup that finishes last adds them up, in the fixed
-    // order of a 1024-leaf strided binary tree -- bitwise reproducible
-    if (!last_workgroup_done(ticket, gridDim.x)) return;
-    __shared__ double tot[256];
-    double p[4];
+        for (int u = 0; u < RC_TRIPS; ++u) {
+            const int c = c0 + 64 * u;
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        double v = 0.0;
-        for (int j = t + 256 * u; j < M; j += 1024) v += rowchg[j];
-        p[u] = v;
+            for (int z = 0; z < NP; ++z) keep_load(pv[u][z]);
+            keep_load(wo[u]);
+            if (c < d) {
+                double wn;
+                if constexpr (NP == 1) {
+                    wn = pv[u][0];
+                } else {
+                    double p = pv[u][0];
+#pragma unroll
+                    for (int z = 1; z < NP; ++z) p += pv[u][z];
+                    wn = p / dn;
+                    Wn[row + c] = wn;
+                }
+                const double df = wo[u] - wn;
+                s += df * df;
+            }
+        }
     }
-    tot[t] = (p[0] + p[2]) + (p[1] + p[3]);   // tree levels 512 and 256 of the 1024-leaf tree
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (t < w) tot[t] += tot[t + w];
-        __syncthreads();
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+    if (lane == 0) rowchg[i] = sqrt(s);
+}
+
+// change_total = sum_i rowchg[i] behind a row-change launch, where no later kernel of the call forms it (the epoch's
+// pack_results_kernel does): one workgroup, change_total_tree (common.h)
+__global__ __launch_bounds__(256) void change_total_kernel(const double *__restrict__ rowchg, int M,
+                                                           double *__restrict__ change_total) {
+    const double v = change_total_tree(rowchg, M);
+    if (threadIdx.x == 0) change_total[0] = v;
+}
+
+static void launch_rowchange(const double *Wo, double *Wn, int M, int d, int splits, const double *part, const double *den,
+                             double *rowchg, double *change_total, hipStream_t s) {
+    const dim3 grid((unsigned)((M + RC_ROWS - 1) / RC_ROWS)), block(256);
+    switch (splits) {
+#define DBGSOM_ROWCHANGE(NP) \
+    case NP: hipLaunchKernelGGL(rowchange_kernel<NP>, grid, block, 0, s, Wo, Wn, M, d, part, den, rowchg); break
+        DBGSOM_ROWCHANGE(1); DBGSOM_ROWCHANGE(2); DBGSOM_ROWCHANGE(3); DBGSOM_ROWCHANGE(4);
+        DBGSOM_ROWCHANGE(5); DBGSOM_ROWCHANGE(6); DBGSOM_ROWCHANGE(7); DBGSOM_ROWCHANGE(8);
+#undef DBGSOM_ROWCHANGE
     }
-    if (t == 0) change_total[0] = tot[0];
+    static_assert(RC_MAX_PIECES == 8, "one case per split count of gemm_splits");
+    if (change_total) hipLaunchKernelGGL(change_total_kernel, dim3(1), dim3(256), 0, s, rowchg, M, change_total);
 }
 
 // ---- smoothing sharded over the ranks of a sample-sharded job (columns of W') -------------------
@@ -426,43 +494,40 @@ __global__ __launch_bounds__(256) void combine_block_kernel(const double *__rest
 }
 
 // the gathered blocks [nblk][M][cb] -> W' row-major (M x d), and the row changes as rowchange_kernel forms them
+// (its batches of column trips as well)
 __global__ __launch_bounds__(256) void rowchange_blocks_kernel(const double *__restrict__ Wo, double *__restrict__ Wn,
                                                                int M, int d, int cb,
                                                                const double *__restrict__ blocks,
-                                                               double *__restrict__ rowchg,
-                                                               uint32_t *__restrict__ ticket,
-                                                               double *__restrict__ change_total) {
+                                                               double *__restrict__ rowchg) {
     const int t = threadIdx.x, lane = t & 63;
     const int i = blockIdx.x * RC_ROWS + (t >> 6);
-    if (i < M) {
-        double s = 0.0;
-        for (int c = lane; c < d; c += 64) {
-            const int b = c / cb;
-            const double wn = blocks[((size_t)b * M + i) * cb + (c - b * cb)];
-            Wn[(size_t)i * d + c] = wn;
-            const double df = Wo[(size_t)i * d + c] - wn;
-            s += df * df;
+    if (i >= M) return;
+    double s = 0.0;
+    const size_t row = (size_t)i * d;
+    for (int c0 = lane; c0 < d; c0 += 64 * RC_TRIPS) {
+        double wv[RC_TRIPS], wo[RC_TRIPS];
+#pragma unroll
+        for (int u = 0; u < RC_TRIPS; ++u) {
+            const int cc = min(c0 + 64 * u, d - 1), b = cc / cb;
+            wv[u] = blocks[((size_t)b * M + i) * cb + (cc - b * cb)];
+            wo[u] = Wo[row + cc];
         }
 #pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
-        if (lane == 0) rowchg[i] = sqrt(s);
+        for (int u = 0; u < RC_TRIPS; ++u) {
+            const int c = c0 + 64 * u;
+            keep_load(wv[u]);
+            keep_load(wo[u]);
+            if (c < d) {
+                const double wn = wv[u];
+                Wn[row + c] = wn;
+                const double df = wo[u] - wn;
+                s += df * df;
+            }
+        }
     }
-    if (!last_workgroup_done(ticket, gridDim.x)) return;
-    __shared__ double tot[256];
-    double p[4];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        double v = 0.0;
-        for (int j = t + 256 * u; j < M; j += 1024) v += rowchg[j];
-        p[u] = v;
-    }
-    tot[t] = (p[0] + p[2]) + (p[1] + p[3]);
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (t < w) tot[t] += tot[t + w];
-        __syncthreads();
-    }
-    if (t == 0) change_total[0] = tot[0];
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+    if (lane == 0) rowchg[i] = sqrt(s);
 }
 
 int64_t smooth_block_cols(int64_t d, int nranks) {
@@ -491,7 +556,7 @@ int launch_smooth_block(const double *S_b, const double *K, const double *a, int
     carve_smooth(&w, (char *)ws, M, d_full);
     const int Mi = (int)M, ci = (int)cb, Mp = (int)smooth_mp(M);
     hipLaunchKernelGGL(smooth_prep_kernel, dim3((unsigned)M), dim3(256), 0, s, S_b, K, a, hop, Mi, ci, layout,
-                       2.0 * (sigma * sigma), w.C, w.G, w.den, w.ticket, Mp);
+                       2.0 * (sigma * sigma), w.C, w.G, w.den, Mp);
     const int splits = gemm_splits(M, d_full);   // (the pieces of the whole matrix: the same bits in either form)
     hipLaunchKernelGGL(smooth_gemm_kernel, dim3((unsigned)((cb + GT - 1) / GT), (unsigned)((M + GR - 1) / GR), (unsigned)splits),
                        dim3(256), 0, s, w.G, w.C, w.den, Mi, Mp, ci, splits, w.part, Wb);
@@ -507,17 +572,18 @@ int launch_rowchange_blocks(const double *blocks, int64_t M, int64_t d, int64_t 
     SmoothWs w;
     carve_smooth(&w, (char *)ws, M, d);
     hipLaunchKernelGGL(rowchange_blocks_kernel, dim3((unsigned)((M + RC_ROWS - 1) / RC_ROWS)), dim3(256), 0, s, W_old, W_new,
-                       (int)M, (int)d, (int)cb, blocks, w.rowchg, w.ticket, change_total);
+                       (int)M, (int)d, (int)cb, blocks, w.rowchg);
+    if (change_total) hipLaunchKernelGGL(change_total_kernel, dim3(1), dim3(256), 0, s, w.rowchg, (int)M, change_total);
     return launch_status("rowchange_blocks_kernel");
 }
 
 int launch_smooth(const double *sums, int64_t M, int64_t d, const float *hop, double sigma,
                   int layout, const double *W_old, double *W_new, double *change_total, void *ws,
-                  size_t ws_bytes, hipStream_t s) {
+                  size_t ws_bytes, hipStream_t s, bool total_by_caller) {
     DBGSOM_REQUIRE(M >= 1 && M <= 0x7fff && d >= 1 && d <= 0x7ffffff0, "bad shape");
     DBGSOM_REQUIRE(layout == DBGSOM_CENTRES_COMPACT || layout == DBGSOM_CENTRES_ALIGNED,
                    "layout must be DBGSOM_CENTRES_COMPACT/ALIGNED");
-    DBGSOM_REQUIRE(sums && hop && W_old && W_new && change_total && ws, "null pointer");
+    DBGSOM_REQUIRE(sums && hop && W_old && W_new && (change_total || total_by_caller) && ws, "null pointer");
     DBGSOM_REQUIRE(W_old != W_new, "W_new must not alias W_old");
     DBGSOM_REQUIRE(is_aligned(ws, 256), "workspace must be 256-byte aligned");
     DBGSOM_REQUIRE(sigma > 0.0, "sigma must be positive");
@@ -532,7 +598,7 @@ int launch_smooth(const double *sums, int64_t M, int64_t d, const float *hop, do
     const double *S = sums, *K = sums + (size_t)M * d, *a = K + M;
     const int Mp = (int)smooth_mp(M);
     hipLaunchKernelGGL(smooth_prep_kernel, dim3((unsigned)M), dim3(256), 0, s, S, K, a, hop, Mi, di, layout,
-                       2.0 * (sigma * sigma), w.C, w.G, w.den, w.ticket, Mp);
+                       2.0 * (sigma * sigma), w.C, w.G, w.den, Mp);
     const int splits = gemm_splits(M, d);
     dim3 grid((unsigned)((d + GT - 1) / GT), (unsigned)((M + GT - 1) / GT), (unsigned)splits);
     static const bool force_generic = [] {   // DBGSOM_SMOOTH_GENERIC=1: the register-staged kernel everywhere (tests)
@@ -545,8 +611,7 @@ int launch_smooth(const double *sums, int64_t M, int64_t d, const float *hop, do
     else
         hipLaunchKernelGGL(smooth_gemm_generic_kernel, grid, dim3(256), 0, s, w.G, w.C, w.den, Mi, Mp, di, splits,
                            w.part, W_new);
-    hipLaunchKernelGGL(rowchange_kernel, dim3((unsigned)((M + RC_ROWS - 1) / RC_ROWS)), dim3(256), 0, s, W_old, W_new, Mi, di,
-                       splits, w.part, w.den, w.rowchg, w.ticket, change_total);
+    launch_rowchange(W_old, W_new, Mi, di, splits, w.part, w.den, w.rowchg, total_by_caller ? nullptr : change_total, s);
     return launch_status("smooth kernels");
 }
 
@@ -565,7 +630,6 @@ struct SmoothMaskedWs {
     double *G;       // M x Mp     h, zeros behind column M
     double *ones;    // M          the GEMM's divisor
     double *rowchg;  // M
-    uint32_t *ticket;
     double *part;    // splits x M x 2 d   the product (its split-K pieces)
 };
 
@@ -574,12 +638,11 @@ static size_t carve_smooth_masked(SmoothMaskedWs *w, char *base, int64_t M, int6
     auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
     const int64_t Mp = smooth_mp(M);
     const size_t oB = take(((size_t)Mp * 2 * d + 64) * 8), oG = take(((size_t)M * Mp + 16) * 8);
-    const size_t oD = take((size_t)M * 8), oR = take((size_t)M * 8), oK = take((size_t)M * 4);
+    const size_t oD = take((size_t)M * 8), oR = take((size_t)M * 8);
     const size_t oP = take((size_t)gemm_splits(M, 2 * d) * M * 2 * d * 8);
     if (w) {
         w->B = (double *)(base + oB); w->G = (double *)(base + oG);
         w->ones = (double *)(base + oD); w->rowchg = (double *)(base + oR);
-        w->ticket = (uint32_t *)(base + oK);
         w->part = (double *)(base + oP);
     }
     return off;
@@ -595,10 +658,8 @@ __global__ __launch_bounds__(256) void smooth_masked_prep_kernel(const double *_
                                                                  const double *__restrict__ A,
                                                                  const float *__restrict__ hop, int M, int d,
                                                                  double two_sigma_sq, double *__restrict__ B,
-                                                                 double *__restrict__ G, double *__restrict__ ones,
-                                                                 uint32_t *__restrict__ ticket, int Mp) {
+                                                                 double *__restrict__ G, double *__restrict__ ones, int Mp) {
     const int i = blockIdx.x, t = threadIdx.x;
-    if (i == 0 && t == 0) *ticket = 0u;  // of the row-change kernel behind the GEMM
     if (t == 0) ones[i] = 1.0;
     for (int c = t; c < d; c += 256) {
         const double a = A[(size_t)i * d + c];
@@ -645,7 +706,7 @@ int launch_smooth_masked(const double *sums, int64_t M, int64_t d, const float *
     const int Mi = (int)M, di = (int)d, d2 = 2 * di, Mp = (int)smooth_mp(M);
     const double *S = sums, *K = sums + (size_t)M * d, *A = K + (size_t)M * d;
     hipLaunchKernelGGL(smooth_masked_prep_kernel, dim3((unsigned)M), dim3(256), 0, s, S, K, A, hop, Mi, di,
-                       2.0 * (sigma * sigma), w.B, w.G, w.ones, w.ticket, Mp);
+                       2.0 * (sigma * sigma), w.B, w.G, w.ones, Mp);
     const int splits = gemm_splits(M, 2 * d);
     // (splits == 1: the kernel stores product / 1 where the pieces would go)
     hipLaunchKernelGGL(smooth_gemm_kernel, dim3((unsigned)((d2 + GT - 1) / GT), (unsigned)((M + GR - 1) / GR), (unsigned)splits),
@@ -653,8 +714,7 @@ int launch_smooth_masked(const double *sums, int64_t M, int64_t d, const float *
                        splits == 1 ? w.part : (double *)nullptr);
     hipLaunchKernelGGL(smooth_masked_divide_kernel, dim3((unsigned)((M * d + 255) / 256)), dim3(256), 0, s, w.part, Mi, di,
                        splits, W_old, W_new);
-    hipLaunchKernelGGL(rowchange_kernel, dim3((unsigned)((M + RC_ROWS - 1) / RC_ROWS)), dim3(256), 0, s, W_old, W_new, Mi, di,
-                       1, (const double *)nullptr, w.ones, w.rowchg, w.ticket, change_total);
+    launch_rowchange(W_old, W_new, Mi, di, 1, nullptr, w.ones, w.rowchg, change_total, s);
     return launch_status("masked smooth kernels");
 }
 
