@@ -168,6 +168,14 @@ SIGNATURES = {
     "dbgsom_ctx_exemplars_query": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _ci, _ci, _vp, _vp]),
     "dbgsom_ctx_exemplars_query_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _ci, _ci, _vp, _vp]),
     "dbgsom_ctx_exemplars_query_csr": (_ci, [_vp, _vp, _vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _ci, _ci, _vp, _vp]),
+    "dbgsom_edge_lengths": (_ci, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "dbgsom_geodesics_workspace_bytes": (_sz, [_i64, _i64]),
+    "dbgsom_geodesics": (_ci, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _sz, _vp]),
+    "dbgsom_combined_error_rows": (_ci, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "dbgsom_ctx_geodesics": (_ci, [_vp, _vp, _i64, _i64, _vp, _i64, _vp]),
+    "dbgsom_ctx_combined_error_query": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "dbgsom_ctx_combined_error_query_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "dbgsom_ctx_combined_error_query_csr": (_ci, [_vp, _vp, _vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "dbgsom_accumulate_masked_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "dbgsom_accumulate_masked": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "dbgsom_smooth_masked_workspace_bytes": (_sz, [_i64, _i64]),

@@ -139,6 +139,28 @@ class HotPathBackend:
         NumPy arrays, next to X for a device array."""
         raise NotImplementedError
 
+    def geodesics(self, W, edges):
+        """The weighted geodesics of the lattice -> G, (rows of W, rows of W) float64.  ``edges`` is an (E, 2) integer
+        array of undirected lattice edges, indices into the rows of W.  An edge is as long as its two prototypes are
+        apart: ``len(a, b) = sqrt(s)`` with ``s = 0`` and then, k ascending, ``t = W[a, k] - W[b, k]``, ``p = t * t``,
+        ``s = s + p``, each operation rounded on its own in float64 (no fma), so ``len(a, b) == len(b, a)`` bit for
+        bit.  ``G[s, t]`` is the minimum over lattice paths ``s = v0, .., vn = t`` of the left fold ``((0 + len(v0,
+        v1)) + len(v1, v2)) + ...``; ``G[s, s] = 0`` and ``G[s, t] = +inf`` without a path.  Rounded addition of a
+        non-negative length is monotone, so the minimum is the unique least fixed point of ``dist[v] = min(dist[v],
+        dist[u] + len(u, v))`` from ``dist[s] = 0`` and every relaxation order ends in the same bits.  ``G[s, t]`` and
+        ``G[t, s]`` fold from different ends and differ in their last bits for most pairs: row s is the fold from s,
+        nothing is symmetrised.  Self-loops are ignored, repeated edges are harmless."""
+        raise NotImplementedError
+
+    def combined_error(self, W, edges, X):
+        """The combined error of Kaski and Lagus (1996) of every row of X -> (e, units), (rows of X,) float64 and
+        (rows of X, 2) int64: ``units[i] = (b1, b2)`` and ``(d1, d2)`` are the first and second result of
+        ``bmu(W, 2, X=X)``'s arithmetic without float32 rounding (ties to the lower index), and ``e_i = d1_i +
+        G[b1_i, b2_i]``, one rounded addition, G as in ``geodesics(W, edges)``.  A row with index -1 in either slot
+        has NaN; ``+inf`` when the two units lie in different components.  X as for ``distances``; the results are
+        NumPy arrays, next to X for a device array."""
+        raise NotImplementedError
+
     # -- metric="manhattan": dist(x, w) = sum_k |x_k - w_k| in float64, k ascending, one accumulator per pair; float32
     # rows widened exactly first; no square root, no clamp; winners by (dist, index); a pair whose distance is not
     # below +inf is never reported (index -1, distance inf).  X: a dense host array or a device array.
@@ -1134,6 +1156,71 @@ class HipBackend(HotPathBackend):
         self._call("dbgsom_ctx_exemplars_query", self._ctx, X.ctypes.data, _x_dtype_code(X.dtype), N, X.shape[1],
                    W64.ctypes.data, M, k, own, idx.ctypes.data, dist.ctypes.data)
         return dist, idx
+
+    # -- weighted geodesics and the combined error of a query ------------------------------------------
+    @staticmethod
+    def _edge_array(edges, M):
+        """-> (E, 2) contiguous int32; indices are checked here, so that the device meets none outside [0, M)"""
+        E = np.asarray(edges)
+        if E.size == 0:
+            return np.empty((0, 2), dtype=np.int32)
+        if E.ndim != 2 or E.shape[1] != 2 or not np.issubdtype(E.dtype, np.integer):
+            raise ValueError(f"edges must be an (E, 2) integer array, got shape {E.shape} of {E.dtype}")
+        if E.min() < 0 or E.max() >= M:
+            raise ValueError(f"edges hold an index outside [0, {M})")
+        return np.ascontiguousarray(E, dtype=np.int32)
+
+    def geodesics(self, W, edges):
+        """The M x M geodesics of the lattice (csrc/geodesics.hip): W and the edges go up, the lengths are formed on
+        the device, one workgroup per source relaxes its vector in LDS, and the matrix comes down (8 M^2 bytes)."""
+        W64 = np.ascontiguousarray(W, dtype=np.float64)
+        if W64.ndim != 2:
+            raise ValueError("W must be 2-D")
+        M, d = W64.shape
+        E = self._edge_array(edges, M)
+        G = np.empty((M, M), dtype=np.float64)
+        self._call("dbgsom_ctx_geodesics", self._ctx, W64.ctypes.data, M, d, E.ctypes.data if len(E) else None, len(E),
+                   G.ctypes.data)
+        return G
+
+    def combined_error(self, W, edges, X):
+        """The combined error of every row (csrc/geodesics.hip): the geodesics of the map are computed once per call
+        into a buffer the context owns, the all-pairs k = 2 search runs chunk by chunk (``distances_chunk_rows``) and
+        the rows kernel behind it reads a chunk's pairs and distances where the search left them.  Host rows go up
+        in chunks; CSR rows are expanded on the device chunk by chunk; for rows in HBM both results are arrays on
+        their device that the kernels write themselves (dbgsom_ctx_combined_error_query_device)."""
+        W64 = np.ascontiguousarray(W, dtype=np.float64)
+        if W64.ndim != 2 or len(X.shape) != 2 or W64.shape[1] != X.shape[1]:
+            raise ValueError("prototype / sample feature mismatch")
+        M, N = W64.shape[0], int(X.shape[0])
+        if M < 2:
+            raise ValueError("the combined error needs a map of at least two prototypes")
+        E = self._edge_array(edges, M)
+        ep, ne = (E.ctypes.data if len(E) else None), len(E)
+        if is_device_array(X):
+            code, N, d, ldx = self._device_rows(X)
+            e, units = device_empty(X, (N,), "float64"), device_empty(X, (N, 2), "int64")
+            if N:
+                self._producer_done(X)
+                self._call("dbgsom_ctx_combined_error_query_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code, N, d,
+                           ldx, W64.ctypes.data, M, ep, ne, ctypes.c_void_p(units.data_ptr()),
+                           ctypes.c_void_p(e.data_ptr()))
+            return e, units
+        e, units = np.empty(N, dtype=np.float64), np.empty((N, 2), dtype=np.int64)
+        if N == 0:
+            return e, units
+        if is_sparse(X):
+            csr, indptr, indices, data = canonical_csr(X)
+            self._call("dbgsom_ctx_combined_error_query_csr", self._ctx, indptr.ctypes.data, indices.ctypes.data,
+                       data.ctypes.data, _x_dtype_code(data.dtype), N, csr.shape[1], data.size, W64.ctypes.data, M,
+                       ep, ne, units.ctypes.data, e.ctypes.data)
+            return e, units
+        X = np.ascontiguousarray(X)
+        if X.dtype not in (np.float32, np.float64):
+            X = X.astype(np.float64)
+        self._call("dbgsom_ctx_combined_error_query", self._ctx, X.ctypes.data, _x_dtype_code(X.dtype), N, X.shape[1],
+                   W64.ctypes.data, M, ep, ne, units.ctypes.data, e.ctypes.data)
+        return e, units
 
     # -- metric="manhattan" (csrc/manhattan.hip) --------------------------------------------------------
     _manhattan = property(lambda self: self._metric == "manhattan")

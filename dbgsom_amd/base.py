@@ -1319,6 +1319,76 @@ class BaseSom(BaseEstimator):
             dist, idx = self._engine().exemplars(self.weights_, k, X, own_cell=bool(own_cell))
         return (dist, idx) if return_distance else idx
 
+    def _lattice_edges(self) -> np.ndarray:
+        """The undirected edges of the fitted lattice as an (E, 2) int32 array of indices into ``weights_`` /
+        ``neurons_`` (the graph as it is after the dead units were removed; it survives a pickle)."""
+        index = {n: i for i, n in enumerate(self.neurons_)}
+        edges = [(index[a], index[b]) for a, b in self.som_.edges]
+        return np.asarray(edges, dtype=np.int32).reshape(-1, 2)
+
+    def prototype_geodesics(self) -> np.ndarray:
+        """The weighted geodesic distances over the lattice: an ``(M, M)`` float64 array in the order of ``weights_``
+        / ``neurons_``.  A lattice edge is as long as its two prototypes are apart in the input space, ``len(a, b) =
+        sqrt(sum_k (w_ak - w_bk)^2)`` summed k ascending with every operation rounded on its own, and ``G[s, t]`` is
+        the length of the shortest path from s to t, its lengths added from s on; ``G[s, s] = 0`` and ``+inf``
+        between components.  The minimum is unique whatever order the edges are relaxed in (rounded addition of a
+        non-negative length is monotone).  ``G[s, t]`` and ``G[t, s]`` add the same lengths from different ends and
+        differ in their last bits for most pairs; the matrix is not symmetrised.  This is what geodesic clustering of
+        the prototypes and U-matrix-style views are built from.  Only this map's prototypes are used; the call is
+        local to the process."""
+        check_is_fitted(self)
+        return self._engine().geodesics(self.weights_, self._lattice_edges())
+
+    def sample_combined_error(self, X):
+        """The combined error of Kaski and Lagus (1996) row by row: ``(e, units)``, ``(n_samples,)`` float64 and
+        ``(n_samples, 2)`` int64, with ``units[i] = (b1, b2)`` the best and second-best matching unit of row ``i``
+        (``units[:, 0]`` is ``predict``'s unit for ``SomVQ``) and ``e_i = ||x_i - w_b1|| + G[b1, b2]``, G the
+        ``prototype_geodesics()`` of the map: the quantization error of the row plus the way along the map from its
+        unit to the runner-up.  Continuous and free of a bandwidth, so the usual choice for comparing maps of
+        different size; ``+inf`` where the two units lie in different components of the lattice.
+
+        The two distances are those of the best-matching-unit search's own arithmetic without float32 rounding, ties
+        go to the lower index, and the sum is one rounded addition, so the result does not depend on chunks or where X
+        lives.  G is computed on the GPU once per call.
+
+        X is what ``kneighbors`` takes under the Euclidean metric: a dense array (NumPy results), a tensor on the
+        estimator's GPU (tensors on X's device), scipy sparse rows (the dense call's result on ``X.toarray()``).
+        Refused with a ``ValueError``: ``metric="manhattan"`` / ``"cosine"`` (the measure is defined on Euclidean
+        distances), rows with NaN (also under ``missing_values``: impute them first), a feature-count mismatch, a
+        map of fewer than two prototypes.  Only this map's prototypes are used (not the child maps of vertical
+        growth); the call is local to the process."""
+        check_is_fitted(self)
+        kind = self._search_metric()
+        if kind:
+            self._refuse_metric(kind, "sample_combined_error / calculate_combined_error",
+                                "the measure is defined on Euclidean distances")
+        if len(self.weights_) < 2:
+            raise ValueError(f"the combined error needs a map of at least two prototypes, this one has "
+                             f"{len(self.weights_)}")
+        if not is_device_array(X) and not is_sparse(X) and np.ndim(X) == 2 and np.shape(X)[0] == 0:
+            X = check_array(X, dtype=[np.float64, np.float32], ensure_min_samples=0)   # (no rows: no launch)
+        else:
+            X = self._check_query(X)
+        if X.shape[1] != self.n_features_in_:
+            raise ValueError(f"X has {X.shape[1]} features, but {type(self).__name__} is expecting "
+                             f"{self.n_features_in_} features as input")
+        if isinstance(X, np.ndarray) and np.isnan(X).any():   # (passed _check_query: missing_values is set)
+            raise ValueError(f"X holds NaN: the combined error is not defined on rows with missing entries "
+                             f"(missing_values={self.missing_values!r}); impute them first (impute(X))")
+        if X.shape[0] == 0:
+            return np.empty(0, dtype=np.float64), np.empty((0, 2), dtype=np.int64)
+        return self._engine().combined_error(self.weights_, self._lattice_edges(), X)
+
+    def calculate_combined_error(self, X) -> float:
+        """The combined error of X: the mean of ``sample_combined_error(X)[0]``.  The per-row values come to the host
+        (8 bytes per row) and NumPy sums them, so a host array, a tensor and sparse rows holding the same data give
+        the same float.  ``+inf`` when some row's two units lie in different components of the lattice: that is the
+        measure's value there."""
+        e, _ = self.sample_combined_error(X)
+        if e.shape[0] == 0:
+            check_array(X, dtype=[np.float64, np.float32])   # (no rows: refused in check_array's words, as a mean is)
+        return float(np.sum(self._host(e))) / e.shape[0]
+
     def _calculate_topographic_error(self, X) -> float:
         """Fraction of samples whose two best matching units are not lattice neighbours."""
         if self._is_resident(X):

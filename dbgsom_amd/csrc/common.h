@@ -252,6 +252,16 @@ int launch_exemplars_store(const double *state_r, const int64_t *state_i, int64_
 int launch_exemplars(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx, const double *W,
                      int64_t M, const double *ww, int k, int own_cell, int64_t slab_rows, int64_t *idx, double *dist,
                      void *ws, size_t ws_bytes, hipStream_t s);
+// weighted geodesics over the lattice and the combined error read off them (geodesics.hip).  `status` is a zeroed
+// device word the kernels OR their findings into; geodesics_status reads it back (blocking) and names the call `what`
+size_t geodesics_workspace_bytes(int64_t M, int64_t E);
+int launch_edge_lengths(const double *W, int64_t M, int64_t d, int64_t ldw, const int32_t *edges, int64_t E, double *len,
+                        uint32_t *status, hipStream_t s);
+int launch_geodesic_rows(const int32_t *edges, const double *len, int64_t E, int64_t M, const int32_t *sources, int64_t S,
+                         double *G, int64_t ldg, uint32_t *status, hipStream_t s);
+int launch_combined_error_rows(const int64_t *idx2, const double *dist, int64_t ldd, int64_t N, const double *G, int64_t ldg,
+                               int64_t M, double *e, uint32_t *status, hipStream_t s);
+int geodesics_status(const char *what, uint32_t *status_dev, int64_t M, hipStream_t s);
 // metric="manhattan" (manhattan.hip): sum_k |x_k - w_k| in float64, F32 / F64 rows; search, matrix and selection read
 // the transposed float64 prototypes launch_manhattan_weights leaves in front of the workspace
 size_t bmu_manhattan_workspace_bytes(int x_dtype, int64_t N, int64_t d, int64_t M);

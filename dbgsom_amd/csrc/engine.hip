@@ -288,6 +288,9 @@ struct dbgsom_ctx {
     // the distortion measure of a query (distortion.hip): the M x M neighbourhood factors of the call (the slab and a
     // chunk's staged result are kn_ws, kn_idx and kn_dist)
     DevBuf de_h;
+    // the combined error of a query (geodesics.hip): the M x M geodesics of the call, and the edges, their lengths and
+    // the status word in front of a chunk's distances (the pairs and e are staged in kn_idx / kn_dist)
+    DevBuf ce_g, ce_ws;
     // the k nearest rows to every prototype (exemplars.hip): the state of the call's fold, [r: M x k float64 | i: M x k
     // int64] (the slab and the fold's scratch are kn_ws; a host-facing call's result is staged in kn_idx and kn_dist)
     DevBuf ex_state;
@@ -1266,7 +1269,7 @@ int dbgsom_ctx_create(int device, dbgsom_ctx **out) {
      &(c)->shard_gather, &(c)->sw, &(c)->wh_order, &(c)->wh_ws, &(c)->sc_ws, &(c)->sc_x, &(c)->sc_w, &(c)->sc_p, &(c)->sc_code, &(c)->sc_proba, &(c)->sc_cnt, &(c)->wt,  \
      &(c)->mk_ws, &(c)->mk_x, &(c)->mk_w, &(c)->mk_idx, &(c)->mk_dist, &(c)->mf_nobs, &(c)->mf_x64, &(c)->mf_wt, &(c)->mf_w,   \
      &(c)->mf_wn, &(c)->mf_idx, &(c)->mf_dist, &(c)->mf_kw, &(c)->mf_sums, &(c)->mf_acc_ws, &(c)->mf_sm_ws, &(c)->mf_scal, \
-     &(c)->pd_out, &(c)->kn_ws, &(c)->kn_idx, &(c)->kn_dist, &(c)->de_h, &(c)->ex_state, &(c)->l1_ws, &(c)->cos_u, &(c)->cos_v}
+     &(c)->pd_out, &(c)->kn_ws, &(c)->kn_idx, &(c)->kn_dist, &(c)->de_h, &(c)->ce_g, &(c)->ce_ws, &(c)->ex_state, &(c)->l1_ws, &(c)->cos_u, &(c)->cos_v}
 
 int dbgsom_ctx_destroy(dbgsom_ctx *c) {
     if (!c) return DBGSOM_OK;
@@ -1866,7 +1869,7 @@ int dbgsom_ctx_bmu_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const in
 // ------------------------------------------------------------------------------------------
 namespace {
 
-enum QueryOp { Q_BMU, Q_DISTANCES, Q_KNEIGHBORS, Q_DISTORTION, Q_EXEMPLARS };
+enum QueryOp { Q_BMU, Q_DISTANCES, Q_KNEIGHBORS, Q_DISTORTION, Q_EXEMPLARS, Q_COMBINED };
 enum RowsForm { ROWS_MASKED, ROWS_MANHATTAN, ROWS_COSINE };
 
 // DBGSOM_REQUIRE under the name of the exported call `fn` (checks shared by several of them)
@@ -1923,6 +1926,8 @@ void drop_large_query_scratch(dbgsom_ctx *c) {
     if (c->pd_out.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->pd_out.release();
     if (c->kn_ws.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->kn_ws.release();
     if (c->de_h.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->de_h.release();
+    if (c->ce_g.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->ce_g.release();
+    if (c->ce_ws.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->ce_ws.release();
     if (c->ex_state.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->ex_state.release();
 }
 
@@ -2089,6 +2094,40 @@ int place_query_weights(dbgsom_ctx *c, DevBuf &Wq, DevBuf &wwq, const double *W_
     return launch_row_sqnorms(Wq.p, DBGSOM_F64, M, dp, dp, wwq.as<double>(), c->stream);
 }
 
+// The geodesics of a map on the device (csrc/geodesics.hip): the edges go up into ce_ws behind its status word, their
+// lengths are formed over Wq (rows dp apart) and G over all M sources lands in ce_g, rows M apart.  `tail` bytes are
+// kept free behind the lengths.  The launches are queued; the status word is read with geodesics_status(ce_status).
+struct GeoScratch {
+    uint32_t *status;
+    int32_t *edges;
+    double *len;
+    char *tail;
+};
+
+GeoScratch carve_geodesics(dbgsom_ctx *c, int64_t E) {
+    char *base = static_cast<char *>(c->ce_ws.p);
+    GeoScratch g;
+    g.status = reinterpret_cast<uint32_t *>(base);
+    g.edges = reinterpret_cast<int32_t *>(base + 256);
+    g.len = reinterpret_cast<double *>(base + 256 + align_up((size_t)E * 8));
+    g.tail = base + 256 + 2 * align_up((size_t)E * 8);
+    return g;
+}
+
+int queue_geodesics(dbgsom_ctx *c, const double *Wq, int64_t M, int64_t d, int64_t dp, const int32_t *edges_host, int64_t E,
+                    size_t tail) {
+    TRY(c->ce_ws.reserve(256 + 2 * align_up((size_t)E * 8) + tail));
+    TRY(c->ce_g.reserve((size_t)M * M * 8));
+    const GeoScratch g = carve_geodesics(c, E);
+    DBGSOM_HIP_CHECK(hipMemsetAsync(g.status, 0, 4, c->stream));
+    if (E > 0) {
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(g.edges, edges_host, (size_t)E * 8, hipMemcpyHostToDevice, c->stream));
+        c->x_up((size_t)E * 8);
+        TRY(launch_edge_lengths(Wq, M, d, dp, g.edges, E, g.len, g.status, c->stream));
+    }
+    return launch_geodesic_rows(g.edges, g.len, E, M, nullptr, M, c->ce_g.as<double>(), M, g.status, c->stream);
+}
+
 // host CSR rows: the index arrays beside q.p, their data
 struct CsrHost {
     const int64_t *indptr;
@@ -2106,9 +2145,12 @@ struct CsrHost {
 // Q_EXEMPLARS (csrc/exemplars.hip): every chunk folds into the state in ex_state with row0 the chunk's first row --
 // nothing per chunk is staged or copied down --, and after the last one the state is stored as the M x k result: into
 // kn_idx / kn_dist and down in one piece (M * k * 16 bytes), or into the caller's device arrays.
+// Q_COMBINED (csrc/geodesics.hip; k = 2): the geodesics of the map are queued once in front of the chunks (edges_host,
+// E); a chunk's all-pairs search leaves its pairs in idx (staged: kn_idx) and its distances in ce_ws, the rows kernel
+// reads both and G and writes e (one value per row; staged: kn_dist).  The status word is read after the last chunk.
 int placed_rows_query(dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHost *csr, int x_dtype, int64_t Nq, int64_t d,
                       const double *W_host, int64_t M, int k, int64_t *idx_out, double *dist_out, int64_t ldo,
-                      const double *H_host, int own_cell) {
+                      const double *H_host, int own_cell, const int32_t *edges_host = nullptr, int64_t E = 0) {
     Samples &s = c->xq;
     DevBuf Wq, wwq;
     const int64_t dp = pad16(d);
@@ -2116,7 +2158,8 @@ int placed_rows_query(dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHo
     const bool staged = !q.on_device, knn = op != Q_DISTANCES;   // (knn: a slab per chunk, k values per row and array)
     const bool cols = op == Q_EXEMPLARS;                         // (the result is M x k, after the last chunk)
     const int64_t chunk = staged ? distances_chunk(c, Nq, M, dp * (int64_t)es) : Nq;
-    const int64_t per_row = knn ? k : M;   // values of a row's result
+    const bool comb = op == Q_COMBINED;
+    const int64_t per_row = comb ? 1 : (knn ? k : M);   // values of a row's result (beside its k indices)
     int rc = DBGSOM_OK;
     do {
         if (csr) {
@@ -2132,7 +2175,11 @@ int placed_rows_query(dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHo
             if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
             c->x_up((size_t)M * M * 8);
         }
-        if (cols) {
+        if (comb) {
+            if ((rc = queue_geodesics(c, Wq.as<double>(), M, d, dp, edges_host, E, (size_t)chunk * 16))) break;
+            if (staged && (rc = c->kn_idx.reserve((size_t)chunk * 16))) break;
+            if (staged && (rc = c->kn_dist.reserve((size_t)chunk * 8))) break;
+        } else if (cols) {
             if ((rc = c->kn_ws.reserve(exemplars_fold_workspace_bytes(chunk, M, k, c->kneighbors_slab_rows)))) break;
             if ((rc = c->ex_state.reserve((size_t)M * k * 16))) break;
             if (staged && (rc = c->kn_idx.reserve((size_t)M * k * 8))) break;
@@ -2167,7 +2214,14 @@ int placed_rows_query(dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHo
                                            c->ex_state.as<int64_t>() + M * k, c->kn_ws.p, c->kn_ws.cap, c->stream);
                 continue;
             }
-            if (op == Q_DISTORTION)
+            if (comb) {
+                const GeoScratch g = carve_geodesics(c, E);
+                double *d2 = reinterpret_cast<double *>(g.tail);
+                rc = launch_bmu(s.Xb, s.bdtype, n, dp, dp, s.xx.as<double>(), Wq.as<double>(), M, wwq.as<double>(), 2, 0, idx,
+                                d2, c->stream);
+                if (rc == DBGSOM_OK)
+                    rc = launch_combined_error_rows(idx, d2, 2, n, c->ce_g.as<double>(), M, M, res, g.status, c->stream);
+            } else if (op == Q_DISTORTION)
                 rc = launch_neighborhood_energy(s.Xb, s.bdtype, n, dp, dp, s.xx.as<double>(), Wq.as<double>(), M,
                                                 wwq.as<double>(), c->de_h.as<double>(), M, c->kneighbors_slab_rows, idx, res,
                                                 c->kn_ws.p, c->kn_ws.cap, c->stream);
@@ -2183,8 +2237,9 @@ int placed_rows_query(dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHo
             if (e == hipSuccess)
                 e = hipMemcpyAsync(dist_out + r0 * per_row, res, (size_t)n * per_row * 8, hipMemcpyDeviceToHost, c->stream);
             if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; }
-            c->x_down((size_t)n * per_row * (knn ? 16 : 8));
+            c->x_down(comb ? (size_t)n * 24 : (size_t)n * per_row * (knn ? 16 : 8));
         }
+        if (rc == DBGSOM_OK && comb) rc = geodesics_status("dbgsom_ctx_combined_error_query", carve_geodesics(c, E).status, M, c->stream);
         if (rc || !cols) break;
         int64_t *idx = staged ? c->kn_idx.as<int64_t>() : idx_out;
         double *res = staged ? c->kn_dist.as<double>() : dist_out;
@@ -2234,8 +2289,9 @@ int raw_rows_checked(const char *fn, dbgsom_ctx *c, QueryOp op, RowsForm form, c
 // CSR rows
 int placed_rows_checked(const char *fn, dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHost *csr, int x_dtype, int64_t Nq,
                         int64_t d, const double *W_host, int64_t M, int k, int64_t *idx_out, double *dist_out, int64_t ldo,
-                        const double *H_host = nullptr, int own_cell = 0) {
+                        const double *H_host = nullptr, int own_cell = 0, const int32_t *edges_host = nullptr, int64_t E = 0) {
     TRY(query_args(fn, c, op, x_dtype, csr != nullptr, Nq, d, M, k));
+    if (op == Q_COMBINED) REQUIRE_FN(fn, E >= 0 && E <= 0x7fffffff, "need 0 <= E < 2^31");
     if (q.on_device) REQUIRE_FN(fn, q.ldx >= d, "ldx must be >= d");
     if (op == Q_DISTANCES) REQUIRE_FN(fn, ldo >= M, "ldo must be >= M");
     if (csr) {
@@ -2245,8 +2301,10 @@ int placed_rows_checked(const char *fn, dbgsom_ctx *c, QueryOp op, const QueryRo
     if (Nq == 0) return DBGSOM_OK;
     REQUIRE_FN(fn, (csr || q.p) && W_host && (op == Q_DISTANCES || idx_out) && dist_out, "null pointer");
     if (op == Q_DISTORTION) REQUIRE_FN(fn, H_host, "null pointer");
+    if (op == Q_COMBINED) REQUIRE_FN(fn, E == 0 || edges_host, "null pointer");
     SET_DEVICE(c);
-    return placed_rows_query(c, op, q, csr, x_dtype, Nq, d, W_host, M, k, idx_out, dist_out, ldo, H_host, own_cell);
+    return placed_rows_query(c, op, q, csr, x_dtype, Nq, d, W_host, M, k, idx_out, dist_out, ldo, H_host, own_cell, edges_host,
+                             E);
 }
 
 }  // namespace
@@ -2364,6 +2422,55 @@ int dbgsom_ctx_exemplars_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, co
     const CsrHost csr{indptr_host, indices_host, nnz};
     return placed_rows_checked(__func__, c, Q_EXEMPLARS, QueryRows{data_host, false, d}, &csr, x_dtype, Nq, d, W_host, M, k,
                                idx_host, dist_host, 0, nullptr, own_cell);
+}
+
+// ------------------------------------------------------------------------------------------
+// weighted geodesics of the map and the combined error of a query: csrc/geodesics.hip
+// ------------------------------------------------------------------------------------------
+int dbgsom_ctx_geodesics(dbgsom_ctx *c, const double *W_host, int64_t M, int64_t d, const int32_t *edges_host, int64_t E,
+                         double *G_host) {
+    if (!c) { set_error("%s: null context", __func__); return DBGSOM_EINVAL; }
+    DBGSOM_REQUIRE(M >= 1 && M <= DBGSOM_MAX_PROTOTYPES, "need 1 <= M <= DBGSOM_MAX_PROTOTYPES");
+    DBGSOM_REQUIRE(d >= 1 && d <= 0x7fffffff, "bad prototype shape");
+    DBGSOM_REQUIRE(E >= 0 && E <= 0x7fffffff, "need 0 <= E < 2^31");
+    DBGSOM_REQUIRE(W_host && G_host && (E == 0 || edges_host), "null pointer");
+    SET_DEVICE(c);
+    DevBuf Wq, wwq;
+    const int64_t dp = pad16(d);
+    int rc = place_query_weights(c, Wq, wwq, W_host, M, d, dp);
+    if (rc == DBGSOM_OK) rc = queue_geodesics(c, Wq.as<double>(), M, d, dp, edges_host, E, 0);
+    if (rc == DBGSOM_OK) rc = geodesics_status(__func__, carve_geodesics(c, E).status, M, c->stream);
+    if (rc == DBGSOM_OK) {
+        const hipError_t e = hipMemcpyAsync(G_host, c->ce_g.p, (size_t)M * M * 8, hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; }
+        c->x_down((size_t)M * M * 8);
+    }
+    rc = finish_query(c, rc);
+    Wq.release(); wwq.release();
+    return rc;
+}
+
+int dbgsom_ctx_combined_error_query(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                    const double *W_host, int64_t M, const int32_t *edges_host, int64_t E,
+                                    int64_t *idx2_host, double *e_host) {
+    return placed_rows_checked(__func__, c, Q_COMBINED, QueryRows{Xq_host, false, d}, nullptr, x_dtype, Nq, d, W_host, M, 2,
+                               idx2_host, e_host, 0, nullptr, 0, edges_host, E);
+}
+
+int dbgsom_ctx_combined_error_query_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d, int64_t ldx,
+                                           const double *W_host, int64_t M, const int32_t *edges_host, int64_t E,
+                                           int64_t *idx2_dev, double *e_dev) {
+    return placed_rows_checked(__func__, c, Q_COMBINED, QueryRows{Xq_dev, true, ldx}, nullptr, x_dtype, Nq, d, W_host, M, 2,
+                               idx2_dev, e_dev, 0, nullptr, 0, edges_host, E);
+}
+
+int dbgsom_ctx_combined_error_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const int32_t *indices_host,
+                                        const void *data_host, int x_dtype, int64_t Nq, int64_t d, int64_t nnz,
+                                        const double *W_host, int64_t M, const int32_t *edges_host, int64_t E,
+                                        int64_t *idx2_host, double *e_host) {
+    const CsrHost csr{indptr_host, indices_host, nnz};
+    return placed_rows_checked(__func__, c, Q_COMBINED, QueryRows{data_host, false, d}, &csr, x_dtype, Nq, d, W_host, M, 2,
+                               idx2_host, e_host, 0, nullptr, 0, edges_host, E);
 }
 
 // ------------------------------------------------------------------------------------------

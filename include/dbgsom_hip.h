@@ -764,6 +764,67 @@ int dbgsom_ctx_exemplars_query_csr(dbgsom_ctx *ctx, const int64_t *indptr_host, 
                                    const double *W_host, int64_t M, int k, int own_cell, int64_t *idx_host,
                                    double *dist_host);
 
+/* ---- weighted geodesics over the lattice and the combined error (csrc/geodesics.hip) -------------------------
+ * The combined error of Kaski and Lagus (1996): e_i = d1_i + G[b1_i, b2_i], the distance of row i to its best
+ * matching unit plus the length of the shortest path along the map from that unit to the second-best one, a
+ * lattice edge being as long as its two prototypes are apart in the input space.  Euclidean metric, complete rows.
+ *
+ * Edge length.  len(a, b) = sqrt(s) with s = 0 and then, for k ascending, t = W[a, k] - W[b, k], p = t * t,
+ * s = s + p: the subtraction, the product and the sum each rounded on their own in float64 (never a fused
+ * multiply-add), so len(a, b) == len(b, a) bit for bit.
+ * Geodesic.  G[s, t] is the minimum over lattice paths s = v0, v1, .., vn = t of the left fold
+ * ((0 + len(v0, v1)) + len(v1, v2)) + ... in float64; G[s, s] = 0, and G[s, t] = +inf when no path exists.
+ * Rounded addition of a non-negative length is monotone, so this minimum is the unique least fixed point of
+ * dist[v] = min(dist[v], dist[u] + len(u, v)) from dist[s] = 0: every relaxation order ends in the same bits.
+ * G[s, t] and G[t, s] fold from different ends and differ in their last bits for most pairs; row s is the fold
+ * from s, and nothing is symmetrised.
+ * Combined error.  e_i = d1_i + G[b1_i * ldg + b2_i], one rounded addition; NaN for a row with index -1 in
+ * either slot.
+ *
+ * dbgsom_edge_lengths: E undirected edges as int32 pairs (a, b) -> E float64 lengths over W (M rows of d values,
+ * ldw >= d apart).  An index outside [0, M) reads nothing, leaves NaN and is DBGSOM_ERANGE.  Blocking.
+ * dbgsom_geodesics: row r of G (S rows, ldg >= M apart) is the vector of source sources[r]; sources_dev == NULL
+ * means all M sources in order, and then S == M.  One source per workgroup with its vector in LDS (8 M bytes),
+ * relaxed by a push over the edge list with 64-bit unsigned atomic minima (non-negative doubles and +inf order
+ * as their bit patterns) until a round lowers nothing, at most M - 1 rounds.  Self-loops are ignored, repeated
+ * edges are harmless, degree is not bounded, +inf is a legal length and connects nothing.  An edge or source index
+ * outside [0, M) is DBGSOM_ERANGE (nothing is read or written through it), a length that is NaN or negative is
+ * DBGSOM_EINVAL; the result is then unspecified.  The workspace holds dbgsom_geodesics_workspace_bytes(M, E) bytes
+ * (0 for a bad M or E), 256-byte aligned; what it holds on entry does not matter.  Blocking: the status word is
+ * read back.
+ * dbgsom_combined_error_rows: idx2 holds N pairs (b1, b2) of int64, dist N rows ldd >= 1 apart whose first
+ * value is d1.  An index outside [0, M) other than -1 reads nothing, leaves NaN and is DBGSOM_ERANGE.  Blocking.
+ * Argument errors (null pointers, M < 1 or M > DBGSOM_MAX_PROTOTYPES, E < 0, ldg < M, a short workspace:
+ * DBGSOM_ENOMEM, a misaligned one) are reported before any launch. */
+int dbgsom_edge_lengths(const double *W_dev, int64_t M, int64_t d, int64_t ldw, const int32_t *edges_dev, int64_t E,
+                        double *len_dev, void *stream);
+size_t dbgsom_geodesics_workspace_bytes(int64_t M, int64_t E);
+int dbgsom_geodesics(const int32_t *edges_dev, const double *len_dev, int64_t E, int64_t M,
+                     const int32_t *sources_dev, int64_t S, double *G_dev, int64_t ldg, void *workspace_dev,
+                     size_t workspace_bytes, void *stream);
+int dbgsom_combined_error_rows(const int64_t *idx2_dev, const double *dist_dev, int64_t ldd, int64_t N,
+                               const double *G_dev, int64_t ldg, int64_t M, double *e_dev, void *stream);
+/* The same on a context.  dbgsom_ctx_geodesics: W_host (M x d, contiguous) and edges_host (E int32 pairs) go up,
+ * the whole M x M matrix comes down into G_host.  dbgsom_ctx_combined_error_query*: the rows and W_host are taken
+ * as the dbgsom_ctx_bmu_query* namesake takes them (CSR rows are expanded on the device chunk by chunk); each call
+ * runs G over all sources once into a buffer the context owns, then, chunk by chunk ("distances_chunk_rows"), the
+ * all-pairs k = 2 search of dbgsom_ctx_bmu_query with round_f32 = 0 (the query search takes its filtered form at
+ * k = 1 only) and the rows kernel behind it: pairs and distances stay in HBM.  idx2 is Nq x 2 int64 (best, second),
+ * e Nq float64; M >= 2.  Host results (24 bytes per row) go to host memory; _device: both are device arrays the
+ * kernels write, and nothing but W and the edges crosses PCIe. */
+int dbgsom_ctx_geodesics(dbgsom_ctx *ctx, const double *W_host, int64_t M, int64_t d, const int32_t *edges_host,
+                         int64_t E, double *G_host);
+int dbgsom_ctx_combined_error_query(dbgsom_ctx *ctx, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                    const double *W_host, int64_t M, const int32_t *edges_host, int64_t E,
+                                    int64_t *idx2_host, double *e_host);
+int dbgsom_ctx_combined_error_query_device(dbgsom_ctx *ctx, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d,
+                                           int64_t ldx, const double *W_host, int64_t M, const int32_t *edges_host,
+                                           int64_t E, int64_t *idx2_dev, double *e_dev);
+int dbgsom_ctx_combined_error_query_csr(dbgsom_ctx *ctx, const int64_t *indptr_host, const int32_t *indices_host,
+                                        const void *data_host, int x_dtype, int64_t Nq, int64_t d, int64_t nnz,
+                                        const double *W_host, int64_t M, const int32_t *edges_host, int64_t E,
+                                        int64_t *idx2_host, double *e_host);
+
 /* ---- fit on rows with missing entries (csrc/masked_fit.hip, csrc/smooth.hip) ---------------------------
  * One epoch on prototypes W (M x d, complete), hop matrix and sigma, NaN marking a missing entry of X:
  *   1. (dist_i, win_i): the masked search above with k = 1 -- every row goes through it, complete rows
