@@ -32,6 +32,7 @@ CENTRES_COMPACT, CENTRES_ALIGNED = 0, 1
 LAYOUTS = {"compact": CENTRES_COMPACT, "aligned": CENTRES_ALIGNED}
 MAX_PROTOTYPES = 16000
 MAX_NEIGHBORS = 32      # DBGSOM_MAX_NEIGHBORS
+MAX_DIRECTIONS = 8      # DBGSOM_MAX_DIRECTIONS
 # counters of dbgsom_sparse_code / dbgsom_ctx_sparse_code (DBGSOM_SC_COUNTS, in this order)
 SC_COUNTS = ("samples", "iterations", "max_iterations", "drops", "degenerate", "early_stops", "aa_retries",
              "overflow", "max_active", "multi_drops", "g_rows")
@@ -100,7 +101,10 @@ SIGNATURES = {
     "dbgsom_class_histogram_weighted": (_ci, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     "dbgsom_weighted_column_sums_workspace_bytes": (_sz, [_i64]),
     "dbgsom_weighted_column_sums": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "dbgsom_ctx_set_topology": (_ci, [_vp, _vp, _i64]),
+    "dbgsom_covariance_apply_workspace_bytes": (_sz, [_i64, _i64, _ci]),
+    "dbgsom_covariance_apply": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _vp, _ci, _vp, _vp, _vp, _sz, _vp]),
+    "dbgsom_ctx_covariance_apply": (_ci, [_vp, _vp, _vp, _ci, _vp, _vp]),
+    "dbgsom_ctx_set_topology":(_ci, [_vp, _vp, _i64]),
     "dbgsom_ctx_set_allreduce": (_ci, [_vp, _vp, _vp]),
     "dbgsom_ctx_set_collectives": (_ci, [_vp, _vp, _vp, _ci, _ci]),
     "dbgsom_rccl_unique_id": (_ci, [_vp]),

@@ -161,6 +161,13 @@ class HotPathBackend:
         NumPy arrays, next to X for a device array."""
         raise NotImplementedError
 
+    def covariance_apply(self, mean, V):
+        """One pass over the resident rows for the linear initialisation (``dbgsom_amd.linear_init``): with
+        ``C = X - mean`` (rows widened to float64, the difference rounded once) -> ``(Z, colsum)``, ``Z = C^T (C V)``
+        of V's shape (d, p), 1 <= p <= MAX_DIRECTIONS, and ``colsum = sum_i C_i`` (d,), all float64.  Dense complete
+        float32 / float64 rows, no weights, one rank.  A backend without it raises: no quiet fallback."""
+        raise NotImplementedError(f"the {self.name} backend has no covariance_apply")
+
     # -- metric="manhattan": dist(x, w) = sum_k |x_k - w_k| in float64, k ascending, one accumulator per pair; float32
     # rows widened exactly first; no square root, no clamp; winners by (dist, index); a pair whose distance is not
     # below +inf is never reported (index -1, distance inf).  X: a dense host array or a device array.
@@ -1676,6 +1683,22 @@ class HipBackend(HotPathBackend):
         s2 = np.empty_like(s1)
         self._call("dbgsom_ctx_column_sums", self._ctx, mean.ctypes.data, s2.ctypes.data)
         return s1, s2, self._N
+
+    def covariance_apply(self, mean, V):
+        """``HotPathBackend.covariance_apply`` on the resident rows (csrc/covariance.hip): mean, V up and Z, colsum
+        down are all that crosses PCIe (2 d p + 2 d doubles)."""
+        self._require_loaded()
+        V64 = np.ascontiguousarray(V, dtype=np.float64)
+        m64 = np.ascontiguousarray(mean, dtype=np.float64)
+        if V64.ndim != 2 or V64.shape[0] != self._d or not 1 <= V64.shape[1] <= _native.MAX_DIRECTIONS:
+            raise ValueError(f"V must be ({self._d}, p) with 1 <= p <= {_native.MAX_DIRECTIONS}, got {V64.shape}")
+        if m64.shape != (self._d,):
+            raise ValueError(f"mean must have shape ({self._d},), got {m64.shape}")
+        Z = np.empty_like(V64)
+        colsum = np.empty(self._d)
+        self._call("dbgsom_ctx_covariance_apply", self._ctx, m64.ctypes.data, V64.ctypes.data, int(V64.shape[1]),
+                   Z.ctypes.data, colsum.ctypes.data)
+        return Z, colsum
 
     _weighted = False
     _incomplete = False

@@ -18,6 +18,20 @@ Extra, build-only parameters (defaults keep reference behaviour):
                     its row shard resident; True: every rank passes only ITS rows (nothing of size
                     N is ever gathered; ``labels_`` then describes the local rows); dense X only
                     (``ValueError`` for sparse X)
+    init            "random" (default): four random rows of X on a 2 x 2 square, as the reference starts.  "pca"
+                    (alias "linear"): the linear initialisation of SOM Toolbox / MiniSom / somoclu -- prototype
+                    ``(a, b)`` of an ``initial_shape = (rows, cols)`` grid starts at ``mean + (2a/(rows-1) - 1)
+                    sqrt(l1) e1 + (2b/(cols-1) - 1) sqrt(l2) e2`` in float64, ``l1 >= l2`` the two largest
+                    eigenvalues of the population covariance of X and ``e1``, ``e2`` their unit eigenvectors (largest
+                    entry positive), found on the device by a block subspace iteration over the resident rows
+                    (``dbgsom_amd.linear_init``).  ``random_state`` plays no part in that start.  Growth and everything
+                    after the start are unchanged; with ``max_neurons <= rows * cols`` the map keeps its shape: a
+                    fixed-grid batch SOM.  Fitted attributes under "pca" only: ``init_mean_`` (d,),
+                    ``init_directions_`` (2, d), ``init_variances_`` (2,), ``init_n_passes_``.  Refused
+                    (``ValueError`` in ``fit``): sparse X, NaN under ``missing_values="nan-fit"``, ``sample_weight``,
+                    ``vertical_growth=True``, ``sharded_input`` or more than one rank, X with fewer than two
+                    directions of variance.  Host arrays and device tensors both work.
+    initial_shape   (rows, cols) of the start grid, both >= 2; anything but (2, 2) needs ``init="pca"``
 
 Sparse input: ``fit``, ``predict``, ``transform``, ``predict_proba`` and ``calculate_quantization_error``
 take a scipy sparse matrix (converted to CSR; never densified as a whole).  A fit on sparse X equals the fit
@@ -99,6 +113,8 @@ class BaseSom(BaseEstimator):
         centres_layout: str = "compact",
         device=None,
         sharded_input: bool = False,
+        init: str = "random",
+        initial_shape=(2, 2),
         missing_values=None,
     ) -> None:
         self.n_iter = n_iter
@@ -125,6 +141,8 @@ class BaseSom(BaseEstimator):
         self.centres_layout = centres_layout
         self.device = device
         self.sharded_input = sharded_input
+        self.init = init
+        self.initial_shape = initial_shape
         self.missing_values = missing_values
 
     # ------------------------------------------------------------------------------------------
@@ -198,6 +216,7 @@ class BaseSom(BaseEstimator):
                 sample_weight = np.ascontiguousarray(sample_weight, dtype=np.float64)
         else:
             X, y = self._check_input_data(X, y)
+            self._check_init_fit(X, sample_weight)
             self._metric_fit = self._check_metric_fit(X, sample_weight)
             self._incomplete_fit = self._check_incomplete_fit(X, sample_weight)
             sample_weight = self._check_sample_weight(sample_weight, X)
@@ -289,6 +308,49 @@ class BaseSom(BaseEstimator):
         if self.sharded_input or dist_info()[1] > 1:
             self._refuse_metric(kind, "sharded_input or a process group of more than one rank", "it takes one process")
         return kind
+
+    # -- init="pca", initial_shape ----------------------------------------------------------------------
+    _PCA_INIT = ("pca", "linear")
+
+    def _init_kind(self) -> str:
+        """"random" or "pca" (its alias "linear" included); validates ``init`` and ``initial_shape``."""
+        if self.init == "random":
+            kind = "random"
+        elif isinstance(self.init, str) and self.init in self._PCA_INIT:
+            kind = "pca"
+        else:
+            raise ValueError(f"init must be 'random' or 'pca' (alias 'linear'), got {self.init!r}")
+        shape = self.initial_shape
+        try:
+            ok = len(shape) == 2 and all(isinstance(v, numbers.Integral) and not isinstance(v, bool) and v >= 2
+                                         for v in shape)
+        except TypeError:
+            ok = False
+        if not ok:
+            raise ValueError(f"initial_shape must be (rows, cols), both integers >= 2, got {shape!r}")
+        if kind == "random" and tuple(int(v) for v in shape) != (2, 2):
+            raise ValueError(f"initial_shape={shape!r} needs init=\"pca\": init={self.init!r} starts from a 2 x 2 square "
+                             "of four random rows")
+        return kind
+
+    def _refuse_pca(self, what: str, way_out: str = "") -> None:
+        raise ValueError(f'init="pca" does not support {what}' + (f": {way_out}" if way_out else ""))
+
+    def _check_init_fit(self, X, sample_weight) -> None:
+        """The refusals of the linear initialisation, on the host before anything is uploaded."""
+        if self._init_kind() != "pca":
+            return
+        if is_sparse(X):
+            self._refuse_pca("scipy sparse X", "pass X.toarray(), or use init='random'")
+        if self._fits_nan() and isinstance(X, np.ndarray) and np.isnan(X).any():
+            self._refuse_pca(f"rows with missing entries (missing_values={self.missing_values!r} and NaN in X)",
+                             "impute them first, or use init='random'")
+        if sample_weight is not None:
+            self._refuse_pca("sample_weight", "repeat the rows instead (np.repeat(X, w, axis=0))")
+        if self.vertical_growth:
+            self._refuse_pca("vertical_growth=True")
+        if self.sharded_input or dist_info()[1] > 1:
+            self._refuse_pca("sharded_input or a process group of more than one rank", "it takes one process")
 
     # -- rows with missing entries in fit (missing_values="nan-fit") ---------------------------------
     _incomplete_fit = False   # this fit runs in incomplete mode: X is dense and holds at least one NaN
@@ -651,12 +713,7 @@ class BaseSom(BaseEstimator):
             self._col_s2 = None
             self.growing_threshold_ = self._calculate_growing_threshold(data)
             self._total_variance = np.nanvar(data, axis=0).sum()
-            rng = np.random.default_rng(seed=self.random_state)
-            start = data[rng.choice(n_total, size=4, replace=False)]
-            fill = np.nanmean(data, axis=0, dtype=np.float64).astype(data.dtype)
-            start = np.where(np.isnan(start), fill[None, :], start)
-            self._lattice = GrowingLattice(start)
-            self._sync_views(refresh_weights=True)
+            self._build_lattice(*self._start_prototypes(data))
             return
         # np.var / np.std over the samples (two host passes over X, 1.4 s at 1e6 x 784) from the
         # resident copy when it is the whole data set: same values bit for bit (f-1)
@@ -703,6 +760,48 @@ class BaseSom(BaseEstimator):
         else:
             self._total_variance = np.var(data, axis=0).sum()
         self._col_s2 = None
+        self._build_lattice(*self._start_prototypes(data))
+
+    _CORNERS = [(0, 0), (0, 1), (1, 0), (1, 1)]
+
+    def _build_lattice(self, nodes, W) -> None:
+        """The start lattice from ``_start_prototypes``' (nodes, W): the nodes are a full rows x cols rectangle in
+        row-major order, W their prototypes in that order."""
+        nodes = [tuple(int(v) for v in n) for n in nodes]
+        rows, cols = max(a for a, _ in nodes) + 1, max(b for _, b in nodes) + 1
+        if nodes != [(a, b) for a in range(rows) for b in range(cols)] or len(W) != len(nodes):
+            raise ValueError("a start is a full rows x cols rectangle of nodes in row-major order, one prototype each")
+        self._lattice = GrowingLattice(W) if (rows, cols) == (2, 2) else GrowingLattice.grid(rows, cols, W)
+        self._sync_views(refresh_weights=True)
+
+    def _start_prototypes(self, data):
+        """The start of a fit -> (nodes, W): lattice nodes ``(a, b)`` of a rows x cols rectangle in row-major order
+        and their prototypes.  ``init="random"``: four random rows of X on the 2 x 2 square, in X's dtype.
+        ``init="pca"``: the ``initial_shape`` grid on the plane of the two leading principal directions of the resident
+        rows, float64 (``linear_init``); sets ``init_mean_``, ``init_directions_``, ``init_variances_`` and
+        ``init_n_passes_``.  ``_initialize_som`` builds the lattice from what this returns, whatever it is."""
+        for name in ("init_mean_", "init_directions_", "init_variances_", "init_n_passes_"):
+            if hasattr(self, name):
+                delattr(self, name)
+        if self._init_kind() == "pca":
+            from . import linear_init
+
+            rows, cols = (int(v) for v in self.initial_shape)
+            plane = linear_init.principal_plane(self._engine(), self._n_total, int(data.shape[1]))
+            self.init_mean_, self.init_directions_ = plane.mean, plane.directions
+            self.init_variances_, self.init_n_passes_ = plane.variances, plane.n_passes
+            nodes = [(a, b) for a in range(rows) for b in range(cols)]
+            return nodes, linear_init.grid_prototypes(plane, rows, cols)
+        engine = self._engine()
+        rank, world = dist_info()
+        n_total = self._n_total
+        if self._incomplete_fit:
+            rng = np.random.default_rng(seed=self.random_state)
+            start = data[rng.choice(n_total, size=4, replace=False)]
+            fill = np.nanmean(data, axis=0, dtype=np.float64).astype(data.dtype)
+            return list(self._CORNERS), np.where(np.isnan(start), fill[None, :], start)
+        on_device = isinstance(data, DeviceSamples)
+        sparse = is_sparse(data)
         seed = self.random_state
         if world > 1 and seed is None:
             # every rank must start from the same four prototypes: rank 0 draws the seed
@@ -731,8 +830,7 @@ class BaseSom(BaseEstimator):
                 start = self._all_reduce_f64(start).astype(data.dtype)   # one owner per row: exact
         else:
             start = rng.choice(a=data, size=4, replace=False)
-        self._lattice = GrowingLattice(start)
-        self._sync_views(refresh_weights=True)
+        return list(self._CORNERS), start
 
     def _draw_weighted_rows(self, rng) -> np.ndarray:
         """The four start rows under weights.  All weights integers: the rows that

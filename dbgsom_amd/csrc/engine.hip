@@ -3126,6 +3126,41 @@ int dbgsom_ctx_weighted_column_sums(dbgsom_ctx *c, const double *mean_host, doub
     return sync(c);
 }
 
+// Z = C^T (C V) and the column sums of C = X - mean over the resident rows (covariance.hip): what it needs is what the
+// Manhattan and cosine calls need (metric_ready), in the same words
+int dbgsom_ctx_covariance_apply(dbgsom_ctx *c, const double *mean_host, const double *V_host, int p, double *Z_host,
+                                double *colsum_host) {
+    CTX_CHECK(c);
+    const char *fn = __func__;
+    TRY(loaded(c, fn));
+    if (c->xs.csr) { set_error("%s: CSR residents have no covariance pass", fn); return DBGSOM_EINVAL; }
+    if (c->xs.dtype == DBGSOM_BF16) { set_error("%s: bfloat16 storage has no covariance pass", fn); return DBGSOM_EINVAL; }
+    const char *why = nullptr;
+    if (c->incomplete) why = "the resident rows have missing entries (option \"incomplete\")";
+    else if (c->has_weights) why = "sample weights are attached";
+    else if (c->coll_nranks > 1 || c->allreduce) why = "more than one rank";
+    if (why) { set_error("%s: %s", fn, why); return DBGSOM_EINVAL; }
+    DBGSOM_REQUIRE(p >= 1 && p <= DBGSOM_MAX_DIRECTIONS, "p must be 1 .. DBGSOM_MAX_DIRECTIONS");
+    DBGSOM_REQUIRE(V_host && Z_host && colsum_host, "null pointer");
+    Samples &s = c->xs;
+    const size_t vec = align_up((size_t)s.d * 8), blk = align_up((size_t)s.d * p * 8);
+    const size_t ws_bytes = dbgsom_covariance_apply_workspace_bytes(s.N, s.d, p);
+    TRY(c->stage_dev.reserve(2 * vec + 2 * blk + ws_bytes));
+    char *base = c->stage_dev.as<char>();
+    double *mean_dev = reinterpret_cast<double *>(base), *colsum_dev = reinterpret_cast<double *>(base + vec);
+    double *V_dev = reinterpret_cast<double *>(base + 2 * vec), *Z_dev = reinterpret_cast<double *>(base + 2 * vec + blk);
+    void *ws = base + 2 * vec + 2 * blk;
+    if (mean_host) DBGSOM_HIP_CHECK(hipMemcpyAsync(mean_dev, mean_host, (size_t)s.d * 8, hipMemcpyHostToDevice, c->stream));
+    DBGSOM_HIP_CHECK(hipMemcpyAsync(V_dev, V_host, (size_t)s.d * p * 8, hipMemcpyHostToDevice, c->stream));
+    c->x_up((size_t)s.d * (p + (mean_host ? 1 : 0)) * 8);
+    TRY(dbgsom_covariance_apply(s.X, s.dtype, s.N, s.d, s.dp, mean_host ? mean_dev : nullptr, V_dev, p, Z_dev, colsum_dev,
+                                ws, ws_bytes, c->stream));
+    DBGSOM_HIP_CHECK(hipMemcpyAsync(Z_host, Z_dev, (size_t)s.d * p * 8, hipMemcpyDeviceToHost, c->stream));
+    DBGSOM_HIP_CHECK(hipMemcpyAsync(colsum_host, colsum_dev, (size_t)s.d * 8, hipMemcpyDeviceToHost, c->stream));
+    c->x_down((size_t)s.d * (p + 1) * 8);
+    return sync(c);
+}
+
 static int reduce_small(dbgsom_ctx *c, double *buf_dev, int64_t n, double *out_host) {
     TRY(run_allreduce(c, buf_dev, n));
     DBGSOM_HIP_CHECK(hipMemcpyAsync(out_host, buf_dev, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));

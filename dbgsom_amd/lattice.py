@@ -41,6 +41,36 @@ class GrowingLattice:
         self._hops = None
         self._overwritten = []  # rows of already occupied positions a growth step rewrote
 
+    @classmethod
+    def grid(cls, rows: int, cols: int, W: np.ndarray):
+        """rows x cols start rectangle: nodes (a, b) in row-major order with the prototypes W (rows * cols of them,
+        in that order), edges between nodes one step apart.  ``grid(2, 2, W)`` is ``GrowingLattice(W)``."""
+        rows, cols = int(rows), int(cols)
+        W = np.array(W)
+        if rows < 2 or cols < 2 or W.ndim != 2 or W.shape[0] != rows * cols:
+            raise ValueError(f"a {rows} x {cols} grid (both >= 2) needs {rows * cols} prototype rows, got {W.shape}")
+        lat = cls.__new__(cls)
+        nodes = [(a, b) for a in range(rows) for b in range(cols)]
+        g = nx.Graph()
+        g.add_nodes_from(nodes)
+        # (edges in the order that gives the 2 x 2 square the adjacency lists of __init__: growth reads their order)
+        for b in range(cols):
+            for a in range(rows):
+                if b + 1 < cols:
+                    g.add_edge((a, b), (a, b + 1))
+                if a + 1 < rows:
+                    g.add_edge((a, b), (a + 1, b))
+        m = len(nodes)
+        lat.graph = g
+        lat.W = W
+        lat.error = np.zeros(m)
+        lat.has_error = np.zeros(m, dtype=bool)
+        lat.epoch_created = np.zeros(m, dtype=np.int64)
+        lat._index = {n: i for i, n in enumerate(nodes)}
+        lat._hops = None
+        lat._overwritten = []
+        return lat
+
     # -- views ----------------------------------------------------------------------------------
     @property
     def nodes(self):

@@ -1128,6 +1128,27 @@ int dbgsom_ctx_node_statistics(dbgsom_ctx *ctx, const double *W_host, int64_t M,
 int dbgsom_ctx_class_histogram(dbgsom_ctx *ctx, const int64_t *idx_host, int64_t n_classes,
                                int64_t M, int64_t *hist_host);
 
+/* ---- covariance times a block of directions: the pass of the linear initialisation (covariance.hip) ---- */
+#define DBGSOM_MAX_DIRECTIONS 8
+/* With c_ik = x_ik - mean_k (x widened to float64, the difference rounded once):
+ *   Z[l, j] = sum_i c_il y_ij,  y_ij = sum_k c_ik V[k, j];   colsum[l] = sum_i c_il
+ * X: N x d, DBGSOM_F32 or DBGSOM_F64, rows ldx >= d elements apart; no alignment is asked of X or ldx, and the
+ * elements between d and ldx of a row are never read.  mean: d float64 (NULL: zeros).  V, Z: d x p row-major float64,
+ * 1 <= p <= DBGSOM_MAX_DIRECTIONS; colsum: d float64.  d <= 2^30.  Float64 throughout, no atomics: the result is the
+ * same bits for the same (N, d, p) and values, whatever ldx, the alignment of the base, or the run.  A NaN or an
+ * infinity in a row goes into Z.  Argument errors are DBGSOM_EINVAL, a short workspace DBGSOM_ENOMEM, both before any
+ * launch; N == 0 gives zeros. */
+size_t dbgsom_covariance_apply_workspace_bytes(int64_t N, int64_t d, int p);
+int dbgsom_covariance_apply(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *mean_dev,
+                            const double *V_dev, int p, double *Z_dev, double *colsum_dev, void *workspace_dev,
+                            size_t workspace_bytes, void *stream);
+/* The same on the resident rows; mean (may be NULL), V, Z and colsum are host arrays.  Dense float32 / float64
+ * residents only: CSR residents, bfloat16 storage, rows with missing entries, attached sample weights and more than
+ * one rank are DBGSOM_EINVAL.  2 d p + 2 d doubles cross PCIe per call ("x_upload_bytes" / "x_download_bytes"),
+ * nothing of size N. */
+int dbgsom_ctx_covariance_apply(dbgsom_ctx *ctx, const double *mean_host, const double *V_host, int p, double *Z_host,
+                                double *colsum_host);
+
 /* ---- vertical growth on Voronoi subsets (BaseSom.py:157-179) ------------------------------------ */
 /* BMU of every resident sample under W (NULL = resident prototypes) + stable bucket order;
  * counts_host[M] = samples per neuron on this rank; idx_host (N, may be NULL) = the winners. */
