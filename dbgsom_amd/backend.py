@@ -470,6 +470,91 @@ def _x_dtype_code(dt) -> int:
     raise ValueError(f"samples must be float32 or float64, got {dt}")
 
 
+_DTYPE_CODES = {"float32": _native.F32, "float64": _native.F64, "bfloat16": _native.BF16}   # by dtype_name()
+_CODE_DTYPES = {_native.F32: np.dtype(np.float32), _native.F64: np.dtype(np.float64), _native.BF16: "bf16"}
+
+
+def host_rows(X):
+    """X as the host-array calls take it: C-contiguous, float32 / float64 kept, anything else (integer / half
+    input) as float64, as check_array would."""
+    X = np.ascontiguousarray(X)
+    return X if X.dtype in (np.float32, np.float64) else X.astype(np.float64)
+
+
+def round_f32(x_dtype, W) -> int:
+    """float32 samples AND float32 prototypes: the reference's engine returns float32-rounded distances (epoch 0
+    of a float32 fit).  Every other mix is full float64.  ``x_dtype``: the rows' dtype or its name."""
+    return int(str(x_dtype) == "float32" and W is not RESIDENT and np.asarray(W).dtype == np.float32)
+
+
+HOST, DEVICE, CSR = "", "_device", "_csr"   # the three forms of a query's rows: the suffix of their entry points
+
+
+class _QueryRows:
+    """The rows X of a query as the C ABI takes them, and the only place that tells the three forms apart: a host
+    array (converted by ``host_rows``), an array in HBM (``is_device_array``, taken as it is) or a scipy sparse
+    matrix (made canonical CSR).  ``suffix`` selects the entry point, ``N``, ``d`` and ``dtype`` (a name) are what a
+    caller checks W against -- both None when X is not 2-D, which no W matches --, ``args()`` is the head of the C
+    argument list, ``empty`` / ``full`` / ``ptr`` make and pass outputs next to X, ``before_call`` is what has to
+    happen right in front of the call.  ``forms``: what the caller accepts; ``name`` says whose refusal it is.
+
+    Device rows are validated (``_device_rows``) and sparse rows made canonical when the object is made, or with
+    ``defer`` when they are first needed -- ``empty`` on device rows, ``args`` -- for the callers that check W and
+    their own arguments against X's shape first, and return without a call, before ``canonical_csr`` would refuse
+    them, when X has no rows."""
+
+    def __init__(self, backend, X, forms, name, defer):
+        self.suffix = CSR if is_sparse(X) else DEVICE if is_device_array(X) else HOST
+        if self.suffix == CSR and CSR not in forms:
+            raise TypeError(f"the {name} calls take dense rows")
+        if self.suffix == DEVICE and DEVICE not in forms:
+            raise TypeError(f"the {name} calls take host rows")
+        self._backend, self._args = backend, None
+        self.X = host_rows(X) if self.suffix == HOST else X
+        self.N, self.d = (int(v) for v in self.X.shape) if len(self.X.shape) == 2 else (None, None)
+        self.dtype = dtype_name(self.X)
+        if not defer:
+            self.args()
+
+    def args(self, null_when_empty=False):
+        """host: (ptr, code, N, d); device: (ptr, code, N, d, ldx); CSR: (indptr, indices, data, code, N, d, nnz)"""
+        if self._args is None:
+            X = self.X
+            if self.suffix == DEVICE:
+                self._args = (ctypes.c_void_p(X.data_ptr()),) + self._backend._device_rows(X)
+            elif self.suffix == CSR:
+                csr, indptr, indices, data = canonical_csr(X)
+                self._keep = (indptr, indices, data)
+                self._args = (indptr.ctypes.data, indices.ctypes.data, data.ctypes.data, _x_dtype_code(data.dtype),
+                              csr.shape[0], csr.shape[1], data.size)
+            else:
+                self._args = (X.ctypes.data, _x_dtype_code(X.dtype), self.N, self.d)
+        return (None,) + self._args[1:] if null_when_empty and not self.N else self._args
+
+    def empty(self, shape, dtype: str):
+        if self.suffix != DEVICE:
+            return np.empty(shape, dtype=dtype)
+        self.args()   # (rows that _device_rows refuses get no output)
+        return device_empty(self.X, shape, dtype)
+
+    def full(self, shape, value, dtype: str):
+        if self.suffix != DEVICE:
+            return np.full(shape, value, dtype=dtype)
+        ns = array_namespace(self.X)
+        return ns.full(shape, value, dtype=getattr(ns, dtype), device=self.X.device)
+
+    def ptr(self, out):
+        return ctypes.c_void_p(out.data_ptr()) if self.suffix == DEVICE else out.ctypes.data
+
+    def ld(self, n):
+        """The row stride that follows a matrix output of n columns: only the device calls take one."""
+        return (n,) if self.suffix == DEVICE else ()
+
+    def before_call(self):
+        if self.suffix == DEVICE:
+            self._backend._producer_done(self.X)
+
+
 class _Resident:
     """Stands for "the prototypes resident in HBM" wherever a weight matrix is expected."""
 
@@ -550,8 +635,7 @@ class HipBackend(HotPathBackend):
         self.phase_log = None       # bench hook: a list collects the per-epoch phase times (ms)
         if _ctx is not None:
             self._N, self._d = self._get("n_samples"), self._get("features")
-            self._x_np_dtype = {_native.F32: np.dtype(np.float32), _native.F64: np.dtype(np.float64),
-                                _native.BF16: "bf16"}[self._get("storage")]
+            self._x_np_dtype = _CODE_DTYPES[self._get("storage")]
         self._install_collective()
 
     # -- plumbing -------------------------------------------------------------------------------
@@ -748,9 +832,7 @@ class HipBackend(HotPathBackend):
             self._after_load(csr.shape, data.dtype)
             self._borrowed = None
             return self
-        X = np.ascontiguousarray(X)
-        if X.dtype not in (np.float32, np.float64):  # integer / half input: as check_array would
-            X = X.astype(np.float64)
+        X = host_rows(X)
         code = _x_dtype_code(X.dtype)
         if X.ndim != 2 or X.shape[0] < 1:
             raise ValueError("X must be a non-empty 2-D array")
@@ -781,7 +863,7 @@ class HipBackend(HotPathBackend):
 
     def _device_rows(self, X_dev, dtypes=("float32", "float64")):
         """-> (dtype code, N, d, row stride) of rows in HBM a *_device entry point can take as they are."""
-        code = {"float32": _native.F32, "float64": _native.F64, "bfloat16": _native.BF16}.get(dtype_name(X_dev))
+        code = _DTYPE_CODES.get(dtype_name(X_dev))
         if code is None or dtype_name(X_dev) not in dtypes or len(X_dev.shape) != 2:
             raise ValueError("device rows must be a 2-D array of " + " / ".join(dtypes))
         N, d = int(X_dev.shape[0]), int(X_dev.shape[1])
@@ -797,8 +879,7 @@ class HipBackend(HotPathBackend):
         and a float32 / float64 / bfloat16 dtype (a torch tensor; bench: generated on the device).
         The caller's writes must have completed; the array is borrowed when its rows are a
         multiple of 16 features, copied (padded) otherwise."""
-        name = str(X_dev.dtype).split(".")[-1]
-        code = {"float32": _native.F32, "float64": _native.F64, "bfloat16": _native.BF16}.get(name)
+        code = _DTYPE_CODES.get(dtype_name(X_dev))
         if code is None or len(X_dev.shape) != 2 or X_dev.stride(1) != 1:
             raise ValueError("X_dev must be a 2-D float32/float64/bfloat16 array with unit column stride")
         N, d = int(X_dev.shape[0]), int(X_dev.shape[1])
@@ -808,8 +889,7 @@ class HipBackend(HotPathBackend):
         self._producer_done(X_dev)
         self._call("dbgsom_ctx_load_device", self._ctx, ctypes.c_void_p(X_dev.data_ptr()), code, N, d,
                    int(X_dev.stride(0)))
-        self._after_load((N, d), {_native.F32: np.dtype(np.float32), _native.F64: np.dtype(np.float64),
-                                  _native.BF16: "bf16"}[code])
+        self._after_load((N, d), _CODE_DTYPES[code])
         self._borrowed = X_dev
         return self
 
@@ -834,12 +914,6 @@ class HipBackend(HotPathBackend):
         return out
 
     # -- prototypes -----------------------------------------------------------------------------
-    def _round_f32(self, W):
-        # float32 samples AND float32 prototypes: the reference's engine returns float32-rounded
-        # distances (epoch 0 of a float32 fit).  Every other mix is full float64.
-        return int(W is not RESIDENT and not isinstance(self._x_np_dtype, str)
-                   and self._x_np_dtype == np.float32 and np.asarray(W).dtype == np.float32)
-
     def _w_arg(self, W, d=None):
         """-> (keep-alive array, pointer or None, M, round_f32) for a weight argument."""
         if W is RESIDENT:
@@ -847,7 +921,7 @@ class HipBackend(HotPathBackend):
             if M < 1:
                 raise RuntimeError("no prototypes resident in HBM yet")
             return None, None, M, 0
-        rf = self._round_f32(W) if d is None else 0
+        rf = round_f32(self._x_np_dtype, W) if d is None else 0
         W64 = np.ascontiguousarray(W, dtype=np.float64)
         if W64.ndim != 2 or W64.shape[1] != (self._d if d is None else d):
             raise ValueError("prototype / sample feature mismatch")
@@ -901,58 +975,59 @@ class HipBackend(HotPathBackend):
                 self._call("dbgsom_ctx_bmu_masked", self._ctx, p, M, int(k), idx.ctypes.data, dist.ctypes.data)
             else:
                 self._call("dbgsom_ctx_bmu", self._ctx, p, M, int(k), rf, idx.ctypes.data, dist.ctypes.data)
-        elif is_device_array(X):
-            return self._bmu_device(W, k, X)
-        elif is_sparse(X):
-            csr, indptr, indices, data = canonical_csr(X)
-            W = np.asarray(W)
-            if W.ndim != 2 or W.shape[1] != csr.shape[1]:
-                raise ValueError("prototype / sample feature mismatch")
-            rf = int(data.dtype == np.float32 and W.dtype == np.float32)
-            W64 = np.ascontiguousarray(W, dtype=np.float64)
-            N = csr.shape[0]
-            idx = np.empty((N, k), dtype=np.int64)
-            dist = np.empty((N, k), dtype=np.float64)
-            self._call("dbgsom_ctx_bmu_query_csr", self._ctx, indptr.ctypes.data, indices.ctypes.data, data.ctypes.data,
-                       _x_dtype_code(data.dtype), N, csr.shape[1], data.size, W64.ctypes.data, W64.shape[0], int(k), rf,
-                       idx.ctypes.data, dist.ctypes.data)
         else:
-            X = np.ascontiguousarray(X)
-            if X.dtype not in (np.float32, np.float64):
-                X = X.astype(np.float64)
-            W = np.asarray(W)
-            if X.ndim != 2 or W.ndim != 2 or W.shape[1] != X.shape[1]:
-                raise ValueError("prototype / sample feature mismatch")
-            rf = int(X.dtype == np.float32 and W.dtype == np.float32)
-            W64 = np.ascontiguousarray(W, dtype=np.float64)
-            N = X.shape[0]
-            idx = np.empty((N, k), dtype=np.int64)
-            dist = np.empty((N, k), dtype=np.float64)
-            self._call("dbgsom_ctx_bmu_query", self._ctx, X.ctypes.data, _x_dtype_code(X.dtype), N,
-                       X.shape[1], W64.ctypes.data, W64.shape[0], int(k), rf, idx.ctypes.data,
-                       dist.ctypes.data)
-        if k == 1:
-            return dist.reshape(-1), idx.reshape(-1)
-        return dist, idx
+            return self._bmu_query("euclidean", W, k, X)
+        return self._bmu_shapes(dist, idx, k)
 
-    def _bmu_device(self, W, k, X):
-        """``bmu(W, k, X=X)`` for rows in HBM (dbgsom_ctx_bmu_query_device): the searches of the host-array call on
-        X's own bytes; distances and winners are arrays on X's device that the search writes itself."""
-        code, N, d, ldx = self._device_rows(X)
-        W = np.asarray(W)
-        if W.ndim != 2 or W.shape[1] != d:
-            raise ValueError("prototype / sample feature mismatch")
-        rf = int(code == _native.F32 and W.dtype == np.float32)
+    @staticmethod
+    def _bmu_shapes(dist, idx, k):
+        """(N, k) results in ``bmu``'s shapes: (N,) for k = 1"""
+        return (dist.reshape(-1), idx.reshape(-1)) if k == 1 else (dist, idx)
+
+    # -- queries on other rows: one marshaller for host arrays, arrays in HBM and CSR ------------------------
+    _DENSE = (HOST, DEVICE)
+    _QUERY_ROWS = {"euclidean": ((HOST, DEVICE, CSR), None), "manhattan": (_DENSE, "Manhattan"),
+                   "cosine": (_DENSE, "cosine"), "masked": ((HOST,), "masked"), "sparse coding": (_DENSE, "sparse coding"),
+                   "topographic function": (_DENSE, "topographic function")}   # what takes which rows
+
+    def _query_rows(self, X, kind="euclidean", defer=False):
+        return _QueryRows(self, X, *self._QUERY_ROWS[kind], defer)
+
+    def _query(self, op, metric, rows, *rest, null_when_empty=False):
+        """The one call of a query: dbgsom_ctx_<op>[_<metric>][_device | _csr](ctx, the rows, rest...); with
+        ``null_when_empty`` rows that are none go as a null pointer."""
+        infix = "" if metric == "euclidean" else "_" + metric
+        rows.before_call()
+        self._call(f"dbgsom_ctx_{op}{infix}{rows.suffix}", self._ctx, *rows.args(null_when_empty), *rest)
+
+    @staticmethod
+    def _w64(W, d):
+        """-> (W as contiguous float64, M), checked against rows of d features"""
         W64 = np.ascontiguousarray(W, dtype=np.float64)
-        idx = device_empty(X, (N, k), "int64")
-        dist = device_empty(X, (N, k), "float64")
-        self._producer_done(X)
-        self._call("dbgsom_ctx_bmu_query_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code, N, d, ldx,
-                   W64.ctypes.data, W64.shape[0], int(k), rf, ctypes.c_void_p(idx.data_ptr()),
-                   ctypes.c_void_p(dist.data_ptr()))
-        if k == 1:
-            return dist.reshape(-1), idx.reshape(-1)
-        return dist, idx
+        if W64.ndim != 2 or W64.shape[1] != d:
+            raise ValueError("prototype / sample feature mismatch")
+        return W64, W64.shape[0]
+
+    def _bmu_query(self, metric, W, k, X, want_filled=False):
+        """``bmu(W, k, X=X)`` under ``metric`` ("euclidean", "manhattan", "cosine", or "masked": over the observed
+        entries) on the device: host rows go up in chunks (``masked_chunk_rows`` rows for the other metrics), CSR rows
+        are searched as they are (dbgsom_ctx_bmu_query_csr); for rows in HBM the searches run on X's own bytes and
+        distances and winners are arrays on X's device that the search writes itself.  ``want_filled`` ("masked"):
+        the filled rows are a third result."""
+        euclidean = metric == "euclidean"
+        rows = self._query_rows(X, metric)
+        W64, M = self._w64(W, rows.d)
+        k = int(k)
+        filled = np.empty_like(rows.X) if want_filled else None
+        idx, dist = rows.empty((rows.N, k), "int64"), rows.empty((rows.N, k), "float64")
+        rf = (round_f32(rows.dtype, W),) if euclidean else ()     # (only the Euclidean search rounds to float32)
+        extra = (None if filled is None else filled.ctypes.data,) if metric == "masked" else ()
+        # (the other metrics take rows that are none as a null pointer from the host and launch nothing for them in HBM)
+        if euclidean or rows.N or rows.suffix == HOST:
+            self._query("bmu_query", metric, rows, W64.ctypes.data, M, k, *rf, rows.ptr(idx), rows.ptr(dist), *extra,
+                        null_when_empty=not euclidean)
+        dist, idx = self._bmu_shapes(dist, idx, k)
+        return (dist, idx, filled) if want_filled else (dist, idx)
 
     def resident_winners(self, W):
         """``bmu(W, 1)[1]`` of the resident samples without the distances' trip to the host."""
@@ -985,7 +1060,7 @@ class HipBackend(HotPathBackend):
     def bmu_masked(self, W, k, X, want_filled=False):
         """The search over the observed entries of every row on the device (csrc/masked.hip), in chunks of
         ``masked_chunk_rows`` rows; with ``want_filled`` each chunk is filled there after its search."""
-        return self._metric_bmu("masked", W, k, X, want_filled)
+        return self._bmu_query("masked", W, k, X, want_filled)
 
     # -- the distance matrix of a query ----------------------------------------------------------------
     # rows per chunk of the host-array calls (0, the default: as many as keep a chunk's staged result at 256 MiB)
@@ -997,38 +1072,22 @@ class HipBackend(HotPathBackend):
         reduced.  Host rows go up and the matrix comes down in chunks of ``distances_chunk_rows`` rows; CSR rows are
         expanded on the device chunk by chunk; for rows in HBM the result is a float64 array on their device that
         the kernel writes itself (dbgsom_ctx_distances_query_device)."""
-        W64 = np.ascontiguousarray(W, dtype=np.float64)
-        if W64.ndim != 2 or len(X.shape) != 2 or W64.shape[1] != X.shape[1]:
-            raise ValueError("prototype / sample feature mismatch")
-        M, N = W64.shape[0], int(X.shape[0])
-        if is_device_array(X):
-            code, N, d, ldx = self._device_rows(X)
-            out = device_empty(X, (N, M), "float64")
-            if N:
-                self._producer_done(X)
-                self._call("dbgsom_ctx_distances_query_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code, N, d, ldx,
-                           W64.ctypes.data, M, ctypes.c_void_p(out.data_ptr()), M)
-            return out
-        out = np.empty((N, M), dtype=np.float64)
-        if N == 0:
-            return out
-        if is_sparse(X):
-            csr, indptr, indices, data = canonical_csr(X)
-            self._call("dbgsom_ctx_distances_query_csr", self._ctx, indptr.ctypes.data, indices.ctypes.data,
-                       data.ctypes.data, _x_dtype_code(data.dtype), N, csr.shape[1], data.size, W64.ctypes.data, M,
-                       out.ctypes.data)
-            return out
-        X = np.ascontiguousarray(X)
-        if X.dtype not in (np.float32, np.float64):
-            X = X.astype(np.float64)
-        self._call("dbgsom_ctx_distances_query", self._ctx, X.ctypes.data, _x_dtype_code(X.dtype), N, X.shape[1],
-                   W64.ctypes.data, M, out.ctypes.data)
+        return self._distances("euclidean", W, X)
+
+    def _distances(self, metric, W, X):
+        """``distances`` under ``metric``.  The Euclidean call checks W against X's shape before it looks at the rows
+        (and so do ``kneighbors`` and the calls below it), the other metrics after."""
+        rows = self._query_rows(X, metric, defer=metric == "euclidean")
+        W64, M = self._w64(W, rows.d)
+        out = rows.empty((rows.N, M), "float64")
+        if rows.N:
+            self._query("distances_query", metric, rows, W64.ctypes.data, M, rows.ptr(out), *rows.ld(M))
         return out
 
     def distances_masked(self, W, X):
         """The distances over the observed entries of every row on the device (csrc/distances.hip), in chunks of
         ``distances_chunk_rows`` rows."""
-        return self._metric_distances("masked", W, X)
+        return self._distances("masked", W, X)
 
     # -- the k nearest prototypes of a query -----------------------------------------------------------
     # rows per slab of squared distances (0, the default: as many, in multiples of 128, as keep the slab at 64 MiB)
@@ -1048,39 +1107,24 @@ class HipBackend(HotPathBackend):
         (rows, k) distances and indices are the result.  Host rows go up in chunks of ``distances_chunk_rows``
         rows; CSR rows are expanded on the device chunk by chunk; for rows in HBM both results are arrays on their
         device that the kernel writes itself (dbgsom_ctx_kneighbors_query_device)."""
-        W64 = np.ascontiguousarray(W, dtype=np.float64)
-        if W64.ndim != 2 or len(X.shape) != 2 or W64.shape[1] != X.shape[1]:
-            raise ValueError("prototype / sample feature mismatch")
-        M, N, k = W64.shape[0], int(X.shape[0]), int(k)
+        return self._kneighbors("euclidean", W, k, X)
+
+    def _kneighbors(self, metric, W, k, X):
+        """``kneighbors`` under ``metric``: the selection kernel reads a slab of that metric's distances back and
+        stores what it selected on."""
+        rows = self._query_rows(X, metric, defer=metric == "euclidean")
+        W64, M = self._w64(W, rows.d)
+        k = int(k)
         self._check_neighbors(k, M)
-        if is_device_array(X):
-            code, N, d, ldx = self._device_rows(X)
-            dist, idx = device_empty(X, (N, k), "float64"), device_empty(X, (N, k), "int64")
-            if N:
-                self._producer_done(X)
-                self._call("dbgsom_ctx_kneighbors_query_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code, N, d,
-                           ldx, W64.ctypes.data, M, k, ctypes.c_void_p(idx.data_ptr()), ctypes.c_void_p(dist.data_ptr()))
-            return dist, idx
-        dist, idx = np.empty((N, k), dtype=np.float64), np.empty((N, k), dtype=np.int64)
-        if N == 0:
-            return dist, idx
-        if is_sparse(X):
-            csr, indptr, indices, data = canonical_csr(X)
-            self._call("dbgsom_ctx_kneighbors_query_csr", self._ctx, indptr.ctypes.data, indices.ctypes.data,
-                       data.ctypes.data, _x_dtype_code(data.dtype), N, csr.shape[1], data.size, W64.ctypes.data, M, k,
-                       idx.ctypes.data, dist.ctypes.data)
-            return dist, idx
-        X = np.ascontiguousarray(X)
-        if X.dtype not in (np.float32, np.float64):
-            X = X.astype(np.float64)
-        self._call("dbgsom_ctx_kneighbors_query", self._ctx, X.ctypes.data, _x_dtype_code(X.dtype), N, X.shape[1],
-                   W64.ctypes.data, M, k, idx.ctypes.data, dist.ctypes.data)
+        dist, idx = rows.empty((rows.N, k), "float64"), rows.empty((rows.N, k), "int64")
+        if rows.N:
+            self._query("kneighbors_query", metric, rows, W64.ctypes.data, M, k, rows.ptr(idx), rows.ptr(dist))
         return dist, idx
 
     def kneighbors_masked(self, W, k, X):
         """The k nearest prototypes over the observed entries of every row on the device (csrc/kneighbors.hip on the
         masked chain of csrc/distances.hip), in chunks of ``distances_chunk_rows`` rows."""
-        return self._metric_kneighbors("masked", W, k, X)
+        return self._kneighbors("masked", W, k, X)
 
     # -- the distortion measure of a query -------------------------------------------------------------
     def neighborhood_energy(self, W, H, X):
@@ -1090,36 +1134,15 @@ class HipBackend(HotPathBackend):
         in chunks of ``distances_chunk_rows`` rows; CSR rows are expanded on the device chunk by chunk; for rows in
         HBM both results are arrays on their device that the kernel writes itself
         (dbgsom_ctx_distortion_query_device)."""
-        W64 = np.ascontiguousarray(W, dtype=np.float64)
-        if W64.ndim != 2 or len(X.shape) != 2 or W64.shape[1] != X.shape[1]:
-            raise ValueError("prototype / sample feature mismatch")
-        M, N = W64.shape[0], int(X.shape[0])
+        rows = self._query_rows(X, defer=True)
+        W64, M = self._w64(W, rows.d)
         H64 = np.ascontiguousarray(H, dtype=np.float64)
         if H64.shape != (M, M):
             raise ValueError(f"H must be ({M}, {M}), one row per prototype, got {H64.shape}")
-        if is_device_array(X):
-            code, N, d, ldx = self._device_rows(X)
-            e, bmu = device_empty(X, (N,), "float64"), device_empty(X, (N,), "int64")
-            if N:
-                self._producer_done(X)
-                self._call("dbgsom_ctx_distortion_query_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code, N, d,
-                           ldx, W64.ctypes.data, M, H64.ctypes.data, ctypes.c_void_p(bmu.data_ptr()),
-                           ctypes.c_void_p(e.data_ptr()))
-            return e, bmu
-        e, bmu = np.empty(N, dtype=np.float64), np.empty(N, dtype=np.int64)
-        if N == 0:
-            return e, bmu
-        if is_sparse(X):
-            csr, indptr, indices, data = canonical_csr(X)
-            self._call("dbgsom_ctx_distortion_query_csr", self._ctx, indptr.ctypes.data, indices.ctypes.data,
-                       data.ctypes.data, _x_dtype_code(data.dtype), N, csr.shape[1], data.size, W64.ctypes.data, M,
-                       H64.ctypes.data, bmu.ctypes.data, e.ctypes.data)
-            return e, bmu
-        X = np.ascontiguousarray(X)
-        if X.dtype not in (np.float32, np.float64):
-            X = X.astype(np.float64)
-        self._call("dbgsom_ctx_distortion_query", self._ctx, X.ctypes.data, _x_dtype_code(X.dtype), N, X.shape[1],
-                   W64.ctypes.data, M, H64.ctypes.data, bmu.ctypes.data, e.ctypes.data)
+        e, bmu = rows.empty((rows.N,), "float64"), rows.empty((rows.N,), "int64")
+        if rows.N:
+            self._query("distortion_query", "euclidean", rows, W64.ctypes.data, M, H64.ctypes.data, rows.ptr(bmu),
+                        rows.ptr(e))
         return e, bmu
 
     # -- the k nearest rows to every prototype ---------------------------------------------------------
@@ -1131,37 +1154,15 @@ class HipBackend(HotPathBackend):
         under its first row's number; CSR rows are expanded on the device chunk by chunk; rows of W x k x 16 bytes
         come down, once.  For rows in HBM both results are arrays on their device that the kernel writes itself
         (dbgsom_ctx_exemplars_query_device).  X without rows: all ``(inf, -1)``, no launch."""
-        W64 = np.ascontiguousarray(W, dtype=np.float64)
-        if W64.ndim != 2 or len(X.shape) != 2 or W64.shape[1] != X.shape[1]:
-            raise ValueError("prototype / sample feature mismatch")
-        M, N, k, own = W64.shape[0], int(X.shape[0]), int(k), int(bool(own_cell))
+        rows = self._query_rows(X, defer=True)
+        W64, M = self._w64(W, rows.d)
+        k, own = int(k), int(bool(own_cell))
         if not 1 <= k <= _native.MAX_NEIGHBORS:
             raise ValueError(f"need 1 <= k <= DBGSOM_MAX_NEIGHBORS = {_native.MAX_NEIGHBORS}, got k = {k}")
-        if is_device_array(X):
-            if N == 0:
-                ns = array_namespace(X)
-                return (ns.full((M, k), float("inf"), dtype=ns.float64, device=X.device),
-                        ns.full((M, k), -1, dtype=ns.int64, device=X.device))
-            code, N, d, ldx = self._device_rows(X)
-            dist, idx = device_empty(X, (M, k), "float64"), device_empty(X, (M, k), "int64")
-            self._producer_done(X)
-            self._call("dbgsom_ctx_exemplars_query_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code, N, d, ldx,
-                       W64.ctypes.data, M, k, own, ctypes.c_void_p(idx.data_ptr()), ctypes.c_void_p(dist.data_ptr()))
-            return dist, idx
-        if N == 0:
-            return np.full((M, k), np.inf), np.full((M, k), -1, dtype=np.int64)
-        dist, idx = np.empty((M, k), dtype=np.float64), np.empty((M, k), dtype=np.int64)
-        if is_sparse(X):
-            csr, indptr, indices, data = canonical_csr(X)
-            self._call("dbgsom_ctx_exemplars_query_csr", self._ctx, indptr.ctypes.data, indices.ctypes.data,
-                       data.ctypes.data, _x_dtype_code(data.dtype), N, csr.shape[1], data.size, W64.ctypes.data, M, k,
-                       own, idx.ctypes.data, dist.ctypes.data)
-            return dist, idx
-        X = np.ascontiguousarray(X)
-        if X.dtype not in (np.float32, np.float64):
-            X = X.astype(np.float64)
-        self._call("dbgsom_ctx_exemplars_query", self._ctx, X.ctypes.data, _x_dtype_code(X.dtype), N, X.shape[1],
-                   W64.ctypes.data, M, k, own, idx.ctypes.data, dist.ctypes.data)
+        if rows.N == 0:
+            return rows.full((M, k), float("inf"), "float64"), rows.full((M, k), -1, "int64")
+        dist, idx = rows.empty((M, k), "float64"), rows.empty((M, k), "int64")
+        self._query("exemplars_query", "euclidean", rows, W64.ctypes.data, M, k, own, rows.ptr(idx), rows.ptr(dist))
         return dist, idx
 
     # -- weighted geodesics and the combined error of a query ------------------------------------------
@@ -1196,37 +1197,15 @@ class HipBackend(HotPathBackend):
         the rows kernel behind it reads a chunk's pairs and distances where the search left them.  Host rows go up
         in chunks; CSR rows are expanded on the device chunk by chunk; for rows in HBM both results are arrays on
         their device that the kernels write themselves (dbgsom_ctx_combined_error_query_device)."""
-        W64 = np.ascontiguousarray(W, dtype=np.float64)
-        if W64.ndim != 2 or len(X.shape) != 2 or W64.shape[1] != X.shape[1]:
-            raise ValueError("prototype / sample feature mismatch")
-        M, N = W64.shape[0], int(X.shape[0])
+        rows = self._query_rows(X, defer=True)
+        W64, M = self._w64(W, rows.d)
         if M < 2:
             raise ValueError("the combined error needs a map of at least two prototypes")
         E = self._edge_array(edges, M)
-        ep, ne = (E.ctypes.data if len(E) else None), len(E)
-        if is_device_array(X):
-            code, N, d, ldx = self._device_rows(X)
-            e, units = device_empty(X, (N,), "float64"), device_empty(X, (N, 2), "int64")
-            if N:
-                self._producer_done(X)
-                self._call("dbgsom_ctx_combined_error_query_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code, N, d,
-                           ldx, W64.ctypes.data, M, ep, ne, ctypes.c_void_p(units.data_ptr()),
-                           ctypes.c_void_p(e.data_ptr()))
-            return e, units
-        e, units = np.empty(N, dtype=np.float64), np.empty((N, 2), dtype=np.int64)
-        if N == 0:
-            return e, units
-        if is_sparse(X):
-            csr, indptr, indices, data = canonical_csr(X)
-            self._call("dbgsom_ctx_combined_error_query_csr", self._ctx, indptr.ctypes.data, indices.ctypes.data,
-                       data.ctypes.data, _x_dtype_code(data.dtype), N, csr.shape[1], data.size, W64.ctypes.data, M,
-                       ep, ne, units.ctypes.data, e.ctypes.data)
-            return e, units
-        X = np.ascontiguousarray(X)
-        if X.dtype not in (np.float32, np.float64):
-            X = X.astype(np.float64)
-        self._call("dbgsom_ctx_combined_error_query", self._ctx, X.ctypes.data, _x_dtype_code(X.dtype), N, X.shape[1],
-                   W64.ctypes.data, M, ep, ne, units.ctypes.data, e.ctypes.data)
+        e, units = rows.empty((rows.N,), "float64"), rows.empty((rows.N, 2), "int64")
+        if rows.N:
+            self._query("combined_error_query", "euclidean", rows, W64.ctypes.data, M, E.ctypes.data if len(E) else None,
+                        len(E), rows.ptr(units), rows.ptr(e))
         return e, units
 
     # -- metric="manhattan" (csrc/manhattan.hip) --------------------------------------------------------
@@ -1234,91 +1213,6 @@ class HipBackend(HotPathBackend):
     _cosine = property(lambda self: self._metric == "cosine")
     _other_metric = property(lambda self: self._metric != "euclidean")   # the resident search is not the Euclidean one
     _METRIC_NAME = {"manhattan": "Manhattan", "cosine": "cosine", "masked": "masked"}
-
-    def _dense_rows_args(self, W, X, form):
-        """The arguments of a query on dense rows, host or device ("masked": host only)
-        -> (W64, X as the calls take it, on_device, (code, N, d, ldx))"""
-        W64 = np.ascontiguousarray(W, dtype=np.float64)
-        name = self._METRIC_NAME[form]
-        if is_sparse(X):
-            raise TypeError(f"the {name} calls take dense rows")
-        if is_device_array(X):
-            if form == "masked":
-                raise TypeError("the masked calls take host rows")
-            rows = self._device_rows(X)
-            on_device = True
-        else:
-            X = np.ascontiguousarray(X)
-            if X.dtype not in (np.float32, np.float64):
-                X = X.astype(np.float64)
-            if X.ndim != 2:
-                raise ValueError("prototype / sample feature mismatch")
-            rows = (_x_dtype_code(X.dtype), X.shape[0], X.shape[1], X.shape[1])
-            on_device = False
-        if W64.ndim != 2 or W64.shape[1] != rows[2]:
-            raise ValueError("prototype / sample feature mismatch")
-        return W64, X, on_device, rows
-
-    def _metric_bmu(self, metric, W, k, X, want_filled=False):
-        """The search of ``metric`` ("manhattan", "cosine", or "masked": over the observed entries) on the device, host
-        rows in chunks of ``masked_chunk_rows`` rows; for rows in HBM distances and winners are arrays on X's device
-        that the search writes itself.  ``want_filled`` ("masked"): the filled rows are a third result."""
-        W64, X, on_device, (code, N, d, ldx) = self._dense_rows_args(W, X, metric)
-        k = int(k)
-        filled = np.empty_like(X) if want_filled else None
-        extra = (None if filled is None else filled.ctypes.data,) if metric == "masked" else ()
-        if on_device:
-            idx, dist = device_empty(X, (N, k), "int64"), device_empty(X, (N, k), "float64")
-            if N:
-                self._producer_done(X)
-                self._call(f"dbgsom_ctx_bmu_query_{metric}_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code, N, d,
-                           ldx, W64.ctypes.data, W64.shape[0], k, ctypes.c_void_p(idx.data_ptr()),
-                           ctypes.c_void_p(dist.data_ptr()))
-        else:
-            idx, dist = np.empty((N, k), dtype=np.int64), np.empty((N, k), dtype=np.float64)
-            self._call(f"dbgsom_ctx_bmu_query_{metric}", self._ctx, X.ctypes.data if N else None, code, N, d,
-                       W64.ctypes.data, W64.shape[0], k, idx.ctypes.data, dist.ctypes.data, *extra)
-        if k == 1:
-            dist, idx = dist.reshape(-1), idx.reshape(-1)
-        return (dist, idx, filled) if want_filled else (dist, idx)
-
-    def _metric_distances(self, metric, W, X):
-        """Every distance of that search, stored: host rows in chunks of ``distances_chunk_rows`` rows; for rows in
-        HBM the result is a float64 array on their device that the kernel writes itself."""
-        W64, X, on_device, (code, N, d, ldx) = self._dense_rows_args(W, X, metric)
-        M = W64.shape[0]
-        if on_device:
-            out = device_empty(X, (N, M), "float64")
-            if N:
-                self._producer_done(X)
-                self._call(f"dbgsom_ctx_distances_query_{metric}_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code,
-                           N, d, ldx, W64.ctypes.data, M, ctypes.c_void_p(out.data_ptr()), M)
-            return out
-        out = np.empty((N, M), dtype=np.float64)
-        if N:
-            self._call(f"dbgsom_ctx_distances_query_{metric}", self._ctx, X.ctypes.data, code, N, d, W64.ctypes.data, M,
-                       out.ctypes.data)
-        return out
-
-    def _metric_kneighbors(self, metric, W, k, X):
-        """The k nearest prototypes under that distance: a slab of ``kneighbors_slab_rows`` rows of distances stays
-        on the device, the selection kernel of csrc/kneighbors.hip reads it back and stores what it selected on."""
-        W64, X, on_device, (code, N, d, ldx) = self._dense_rows_args(W, X, metric)
-        M, k = W64.shape[0], int(k)
-        self._check_neighbors(k, M)
-        if on_device:
-            dist, idx = device_empty(X, (N, k), "float64"), device_empty(X, (N, k), "int64")
-            if N:
-                self._producer_done(X)
-                self._call(f"dbgsom_ctx_kneighbors_query_{metric}_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code,
-                           N, d, ldx, W64.ctypes.data, M, k, ctypes.c_void_p(idx.data_ptr()),
-                           ctypes.c_void_p(dist.data_ptr()))
-            return dist, idx
-        dist, idx = np.empty((N, k), dtype=np.float64), np.empty((N, k), dtype=np.int64)
-        if N:
-            self._call(f"dbgsom_ctx_kneighbors_query_{metric}", self._ctx, X.ctypes.data, code, N, d, W64.ctypes.data, M, k,
-                       idx.ctypes.data, dist.ctypes.data)
-        return dist, idx
 
     def _metric_epoch(self, metric, W, hop, sigma, gamma, layout, want_assignments, n_classes):
         """One epoch under ``metric`` as ONE call of the C ABI: its search of the resident rows (csrc/manhattan.hip;
@@ -1343,26 +1237,26 @@ class HipBackend(HotPathBackend):
         return res
 
     def bmu_manhattan(self, W, k, X):
-        return self._metric_bmu("manhattan", W, k, X)
+        return self._bmu_query("manhattan", W, k, X)
 
     def distances_manhattan(self, W, X):
-        return self._metric_distances("manhattan", W, X)
+        return self._distances("manhattan", W, X)
 
     def kneighbors_manhattan(self, W, k, X):
-        return self._metric_kneighbors("manhattan", W, k, X)
+        return self._kneighbors("manhattan", W, k, X)
 
     def epoch_manhattan(self, W, hop, sigma, gamma, layout="compact", want_assignments=False, n_classes=0):
         return self._metric_epoch("manhattan", W, hop, sigma, gamma, layout, want_assignments, n_classes)
 
     # -- metric="cosine" (csrc/cosine.hip and the cosine forms of bmu.hip, bmu_dma.hip, distances.hip) ----
     def bmu_cosine(self, W, k, X):
-        return self._metric_bmu("cosine", W, k, X)
+        return self._bmu_query("cosine", W, k, X)
 
     def distances_cosine(self, W, X):
-        return self._metric_distances("cosine", W, X)
+        return self._distances("cosine", W, X)
 
     def kneighbors_cosine(self, W, k, X):
-        return self._metric_kneighbors("cosine", W, k, X)
+        return self._kneighbors("cosine", W, k, X)
 
     def epoch_cosine(self, W, hop, sigma, gamma, layout="compact", want_assignments=False, n_classes=0):
         return self._metric_epoch("cosine", W, hop, sigma, gamma, layout, want_assignments, n_classes)
@@ -1382,13 +1276,7 @@ class HipBackend(HotPathBackend):
         like scikit-learn, one ConvergenceWarning when a row skipped a degenerate regressor or
         stopped early.  Rows in HBM (``is_device_array``) are coded where they lie, chunk by chunk, and the
         result is an array on their device that the coder writes itself (dbgsom_ctx_sparse_code_device)."""
-        on_device = is_device_array(X)
-        if on_device:
-            code, N, d_x, ldx = self._device_rows(X)
-        else:
-            X = np.ascontiguousarray(X)
-            if X.dtype not in (np.float32, np.float64):
-                X = X.astype(np.float64)
+        rows = self._query_rows(X, "sparse coding")
         if W is RESIDENT:
             self._require_loaded()
             keep, p, M = None, None, self._get("prototypes")
@@ -1398,9 +1286,8 @@ class HipBackend(HotPathBackend):
             if keep.ndim != 2:
                 raise ValueError("W must be 2-D")
             p, (M, d) = keep.ctypes.data, keep.shape
-        if len(X.shape) != 2 or X.shape[1] != d:
+        if rows.d != d:
             raise ValueError("prototype / sample feature mismatch")
-        N = X.shape[0]
         counts = np.zeros(len(_native.SC_COUNTS), dtype=np.uint64)
         if P is None:
             Pc, C = None, 0
@@ -1409,19 +1296,11 @@ class HipBackend(HotPathBackend):
             if Pc.ndim != 2 or Pc.shape[0] != M:
                 raise ValueError("P must have one row per prototype")
             C = Pc.shape[1]
-        if on_device:
-            out = device_empty(X, (N, M if P is None else C), "float64")
-            out_p = ctypes.c_void_p(out.data_ptr()) if N else None
-            self._producer_done(X)
-            self._call("dbgsom_ctx_sparse_code_device", self._ctx, ctypes.c_void_p(X.data_ptr()) if N else None, code, N,
-                       d, ldx, p, M, int(max_iter), None if Pc is None else Pc.ctypes.data, C,
-                       out_p if P is None else None, None if P is None else out_p, counts.ctypes.data)
-        else:
-            out = np.empty((N, M if P is None else C))
-            out_p = out.ctypes.data
-            self._call("dbgsom_ctx_sparse_code", self._ctx, X.ctypes.data if N else None, _x_dtype_code(X.dtype), N, d,
-                       p, M, int(max_iter), None if Pc is None else Pc.ctypes.data, C, out_p if P is None else None,
-                       None if P is None else out_p, counts.ctypes.data)
+        out = rows.empty((rows.N, M if P is None else C), "float64")
+        # (rows that are none go as a null pointer, and for rows in HBM so does their output)
+        out_p = rows.ptr(out) if rows.N or rows.suffix == HOST else None
+        self._query("sparse_code", "euclidean", rows, p, M, int(max_iter), None if Pc is None else Pc.ctypes.data, C,
+                    out_p if P is None else None, None if P is None else out_p, counts.ctypes.data, null_when_empty=True)
         self.sparse_code_counts = dict(zip(_native.SC_COUNTS, (int(v) for v in counts)))
         if counts[4] or counts[5]:
             import warnings
@@ -1439,35 +1318,17 @@ class HipBackend(HotPathBackend):
         ``bmu(W, 2, X=X)``, the edge set, a breadth-first search from every neuron and the histograms,
         with the pairs never leaving HBM.  Rows in HBM (``is_device_array``) are searched where they lie
         (dbgsom_ctx_topographic_function_device); the histograms are host arrays either way."""
-        on_device = is_device_array(X)
-        if on_device:
-            code, N, d_x, ldx = self._device_rows(X)
-        else:
-            X = np.ascontiguousarray(X)
-            if X.dtype not in (np.float32, np.float64):
-                X = X.astype(np.float64)
-        W = np.asarray(W)
-        if len(X.shape) != 2 or W.ndim != 2 or W.shape[1] != X.shape[1]:
-            raise ValueError("prototype / sample feature mismatch")
+        rows = self._query_rows(X, "topographic function")
+        W64, M = self._w64(W, rows.d)
         xy = np.ascontiguousarray(coords, dtype=np.int32).reshape(-1, 2)
-        M = W.shape[0]
         if xy.shape[0] != M:
             raise ValueError("coords must be (M, 2)")
-        rf = int(dtype_name(X) == "float32" and W.dtype == np.float32)
-        W64 = np.ascontiguousarray(W, dtype=np.float64)
         n_pos = int((xy.astype(np.int64).max(axis=0) - xy.astype(np.int64).min(axis=0)).max()) + 1
         hist_pos = np.empty(n_pos, dtype=np.int64)
         hist_neg = np.empty(M + 1, dtype=np.int64)
         D = np.empty((M, M), dtype=np.int32) if want_distances else None
-        if on_device:
-            self._producer_done(X)
-            self._call("dbgsom_ctx_topographic_function_device", self._ctx, ctypes.c_void_p(X.data_ptr()), code, N, d_x,
-                       ldx, W64.ctypes.data, M, rf, xy.ctypes.data, n_pos, hist_pos.ctypes.data, hist_neg.ctypes.data,
-                       None if D is None else D.ctypes.data)
-            return hist_pos, hist_neg, D
-        self._call("dbgsom_ctx_topographic_function", self._ctx, X.ctypes.data, _x_dtype_code(X.dtype),
-                   X.shape[0], X.shape[1], W64.ctypes.data, M, rf, xy.ctypes.data, n_pos, hist_pos.ctypes.data,
-                   hist_neg.ctypes.data, None if D is None else D.ctypes.data)
+        self._query("topographic_function", "euclidean", rows, W64.ctypes.data, M, round_f32(rows.dtype, W), xy.ctypes.data,
+                    n_pos, hist_pos.ctypes.data, hist_neg.ctypes.data, None if D is None else D.ctypes.data)
         return hist_pos, hist_neg, D
 
     # -- a2 -------------------------------------------------------------------------------------
