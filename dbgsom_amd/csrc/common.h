@@ -28,6 +28,17 @@ void set_error(const char *fmt, ...);
         }                                                           \
     } while (0)
 
+#define TRY_STATUS(expr) do { int _rc = (expr); if (_rc != DBGSOM_OK) return _rc; } while (0)
+
+// `fn`: the public call whose workspace it is
+inline int workspace_check(const char *fn, size_t have, size_t need) {
+    if (have < need) {
+        set_error("%s: workspace of %zu bytes, %zu needed", fn, have, need);
+        return DBGSOM_ENOMEM;
+    }
+    return DBGSOM_OK;
+}
+
 inline int launch_status(const char *what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -220,6 +231,21 @@ int64_t kneighbors_slab_rows(int64_t N, int64_t M, int64_t slab_rows);
 // rows of a slab are M rounded up to even apart, so that every row starts on 16 bytes
 inline int64_t kneighbors_slab_ld(int64_t M) { return M + (M & 1); }
 size_t kneighbors_workspace_bytes(int64_t N, int64_t M, int64_t slab_rows);
+// The slab loop of every kneighbors launcher: the rows in slabs of kneighbors_slab_rows, fill(rows, r0, n, slab, ldr)
+// stores what is selected on for the n rows from r0 on (`rows`: the first of them) into `slab`, rows ldr apart, then
+// `select` (launch_topk_rows: the slab holds squared values; launch_topk_rows_plain: what is reported) on the slab.
+template <typename Fill>
+int kneighbors_slabs(const void *X, int x_dtype, int64_t N, int64_t ldx, int64_t M, int k, int64_t slab_rows, double *slab,
+                     decltype(launch_topk_rows) *select, int64_t *idx, double *dist, hipStream_t s, Fill fill) {
+    const int64_t rows = kneighbors_slab_rows(N, M, slab_rows), ldr = kneighbors_slab_ld(M);
+    const size_t es = dtype_size(x_dtype);
+    for (int64_t r0 = 0; r0 < N; r0 += rows) {
+        const int64_t n = rows < N - r0 ? rows : N - r0;
+        TRY_STATUS(fill(static_cast<const char *>(X) + (size_t)r0 * ldx * es, r0, n, slab, ldr));
+        TRY_STATUS(select(slab, n, M, ldr, k, idx + r0 * k, dist + r0 * k, s));
+    }
+    return DBGSOM_OK;
+}
 size_t kneighbors_masked_workspace_bytes(int x_dtype, int64_t N, int64_t d, int64_t M, int64_t slab_rows);
 int launch_kneighbors(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx, const double *W,
                       int64_t M, const double *ww, int k, int64_t slab_rows, int64_t *idx, double *dist, void *ws,

@@ -17,7 +17,7 @@
 //     across the workgroup.  More than 256 prototypes go in blocks of 256, ascending, so that a lane
 //     meets its candidates with ascending index and the strict '<' of Best<K> keeps the lowest one.
 //     The epilogue is that of bmu_kernel: clamp at 0, NaN never wins, ties to the lowest j, sqrt, the
-//     optional float32 rounding;
+//     optional float32 rounding (DBGSOM_STORE_WINNERS with RootFinish, direct_rows.h);
 //   * sums: the CSR sibling of segsum_kernel -- one workgroup per chunk of <= CH rows of one neuron,
 //     rows in list order, each stored entry added to its column's partial with the fused multiply-add
 //     that segsum_kernel's `acc += w * v` compiles to (v_fmac_f64).  A slab row is d float64 wide and
@@ -27,13 +27,14 @@
 //     dense pipeline's own (accumulate.hip).
 #include <math.h>
 
-#include "bmu_common.h"
+#include "direct_rows.h"
 
 namespace dbgsom {
 
 constexpr int CR = 4;      // rows per workgroup of the search = independent chains per lane
 constexpr int CT = 256;    // threads per workgroup (= prototypes per block of the search)
 constexpr int CCH = 128;   // rows per chunk of the sums: accumulate.hip's CH
+static_assert(CT == MT, "the winners' tail of direct_rows.h is that of a workgroup of MT lanes");
 
 int64_t csr_wt_ld(int64_t M) { return (M + CT - 1) / CT * CT; }
 
@@ -78,9 +79,7 @@ __global__ __launch_bounds__(CT) void bmu_csr_kernel(
     const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices, const T *__restrict__ data,
     int64_t N, const double *__restrict__ xx, const double *__restrict__ Wt, int64_t ldwt, int M,
     const double *__restrict__ ww, int round_f32, int64_t *__restrict__ idx_out, double *__restrict__ dist_out) {
-    __shared__ double mv[CT / 64][CR][K];
-    __shared__ int mj[CT / 64][CR][K];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int64_t i0 = (int64_t)blockIdx.x * CR;
     int64_t p0[CR];
     int len[CR];
@@ -127,47 +126,9 @@ __global__ __launch_bounds__(CT) void bmu_csr_kernel(
             }
         }
     }
-    // the lanes of a wavefront, then the wavefronts, hold different prototypes of the same rows
-#pragma unroll
-    for (int r = 0; r < CR; ++r) {
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            double ov[K];
-            int oj[K];
-#pragma unroll
-            for (int t = 0; t < K; ++t) {
-                ov[t] = __shfl_xor(best[r].v[t], m, 64);
-                oj[t] = __shfl_xor(best[r].j[t], m, 64);
-            }
-            best[r].merge(ov, oj);
-        }
-        if (lane == 0) {
-#pragma unroll
-            for (int t = 0; t < K; ++t) { mv[wave][r][t] = best[r].v[t]; mj[wave][r][t] = best[r].j[t]; }
-        }
-    }
-    __syncthreads();
-    if (tid < CR && i0 + tid < N) {
-        Best<K> b;
-#pragma unroll
-        for (int t = 0; t < K; ++t) { b.v[t] = mv[0][tid][t]; b.j[t] = mj[0][tid][t]; }
-#pragma unroll
-        for (int w = 1; w < CT / 64; ++w) {
-            double ov[K];
-            int oj[K];
-#pragma unroll
-            for (int t = 0; t < K; ++t) { ov[t] = mv[w][tid][t]; oj[t] = mj[w][tid][t]; }
-            b.merge(ov, oj);
-        }
-        const int64_t i = i0 + tid;
-#pragma unroll
-        for (int t = 0; t < K; ++t) {
-            double dv = sqrt(b.v[t]);
-            if (round_f32) dv = (double)(float)dv;
-            idx_out[i * K + t] = (b.j[t] == 0x7fffffff) ? (int64_t)-1 : (int64_t)b.j[t];
-            dist_out[i * K + t] = dv;
-        }
-    }
+    const int nrows = (int)min((int64_t)CR, N - i0);
+    const RootFinish fin{round_f32};
+    DBGSOM_STORE_WINNERS(K, CR, best, i0, nrows, 0, fin, idx_out, dist_out);
 }
 
 // ---- sums: one workgroup sums one chunk (<= CCH rows of one neuron) in list order -------------------

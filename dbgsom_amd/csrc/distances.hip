@@ -23,17 +23,14 @@
 // a workgroup shifts W, ww and out to its first prototype and runs the unchanged loop on its share.  A pair's chain does not depend on the
 // workgroup that runs it.
 //
-// Rows with missing entries: sibling of masked_bmu_kernel (masked.hip).  The lanes own prototypes there, so the 256
-// distances of a row and prototype block are one coalesced store; same chain, same d / n_obs scale, same square root.
+// Rows with missing entries and metric="manhattan" have their matrices in masked.hip and manhattan.hip
+// (direct_dist_kernel, direct_rows.h).
 #include <math.h>
 
 #include <algorithm>
 
 #include "bmu_common.h"
 #include "bmu_tiles.h"
-#include "masked_common.h"
-
-#define TRY_STATUS(expr) do { int _rc = (expr); if (_rc != DBGSOM_OK) return _rc; } while (0)
 
 namespace dbgsom {
 
@@ -388,42 +385,6 @@ __global__ __launch_bounds__(NT, 2) void dist_dma_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------
-// rows with missing entries: the chain of masked_bmu_kernel, every (row, prototype) stored
-// ---------------------------------------------------------------------------------------------
-template <int R, bool SQ>
-__global__ __launch_bounds__(MT) void masked_dist_kernel(const double *__restrict__ X, int64_t N, int d, int64_t ldx,
-                                                         const int32_t *__restrict__ nobs,
-                                                         const double *__restrict__ Wt, int64_t ldwt, int M,
-                                                         double *__restrict__ out, int64_t ldo) {
-    const int tid = threadIdx.x;
-    const int64_t i0 = (int64_t)blockIdx.x * R;
-    const int nrows = (int)min((int64_t)R, N - i0);
-    const double *__restrict__ xb = X + i0 * ldx;
-    uint32_t off[R];   // (rows behind the last one repeat it: computed, never written; R ldx < 2^32 is required)
-    double scale[R];   // (no observed entry: 0 * inf, the distance is NaN)
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        off[r] = (uint32_t)min(r, nrows - 1) * (uint32_t)ldx;
-        scale[r] = (double)d / (double)nobs[i0 + min(r, nrows - 1)];
-    }
-    for (int jb = 0; jb < M; jb += MT) {
-        const int j = jb + tid;            // (j < ldwt: the columns behind M hold zeros)
-        const double *__restrict__ wcol = Wt + j;
-        double acc[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] = 0.0;
-        int e = 0;
-        for (; e + MU <= d; e += MU) masked_step<R, MU>(xb, off, e, wcol, ldwt, acc);
-        for (; e < d; ++e) masked_step<R, 1>(xb, off, e, wcol, ldwt, acc);
-        if (j < M) {
-#pragma unroll
-            for (int r = 0; r < R; ++r)
-                if (r < nrows) put<SQ>(SQ ? acc[r] * scale[r] : sqrt(acc[r] * scale[r]), out + (i0 + r) * ldo + j);
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
 static int distances_check(int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, int64_t ldo) {
     DBGSOM_REQUIRE(valid_dtype(x_dtype), "x_dtype must be DBGSOM_F32/F64/BF16");
     DBGSOM_REQUIRE(N >= 0 && d >= 1 && ldx >= d && d <= 0x7fffffff, "bad sample shape");
@@ -505,53 +466,6 @@ int launch_distances_cosine_slab(const void *X, int x_dtype, int64_t N, int64_t 
     return launch_distances_form<true, Metric::COSINE>(X, x_dtype, N, d, ldx, u, W, M, v, out, ldo, s);
 }
 
-static int distances_masked_check(int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, int64_t ldo) {
-    TRY_STATUS(masked_check_shape(x_dtype, N, d, ldx, M, 1));
-    DBGSOM_REQUIRE(M <= DBGSOM_MAX_PROTOTYPES, "need 1 <= M <= DBGSOM_MAX_PROTOTYPES");
-    DBGSOM_REQUIRE(ldo >= M, "ldo must be >= M");
-    return DBGSOM_OK;
-}
-
-// the distances of N rows to the transposed prototypes launch_masked_weights left in front of `ws` (the workspace
-// of bmu_masked_workspace_bytes: [Wt | n_obs | float32 rows only: their float64 copy])
-template <bool SQ>
-static int launch_distances_masked_form(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M,
-                                        double *out, int64_t ldo, void *ws, size_t ws_bytes, hipStream_t s) {
-    TRY_STATUS(distances_masked_check(x_dtype, N, d, ldx, M, ldo));
-    if (N == 0) return DBGSOM_OK;
-    DBGSOM_REQUIRE(X && out && ws, "null pointer");
-    if (ws_bytes < bmu_masked_workspace_bytes(x_dtype, N, d, M)) {
-        set_error("dbgsom_distances_masked: workspace of %zu bytes, %zu needed", ws_bytes,
-                  bmu_masked_workspace_bytes(x_dtype, N, d, M));
-        return DBGSOM_ENOMEM;
-    }
-    char *p = static_cast<char *>(ws);
-    const double *Wt = reinterpret_cast<const double *>(p);
-    int32_t *nobs = reinterpret_cast<int32_t *>(p + masked_weights_bytes(d, M));
-    double *Xw = reinterpret_cast<double *>(p + masked_weights_bytes(d, M) + align_up((size_t)N * 4));
-    const bool f32 = x_dtype == DBGSOM_F32;
-    TRY_STATUS(launch_masked_prepare(X, x_dtype, N, d, ldx, nobs, f32 ? Xw : nullptr, s));
-    const double *X64 = f32 ? Xw : static_cast<const double *>(X);
-    const int64_t ld64 = f32 ? d : ldx, ldwt = csr_wt_ld(M);
-    if (N < MASKED_FEW_ROWS)
-        hipLaunchKernelGGL((masked_dist_kernel<MRS, SQ>), dim3((unsigned)((N + MRS - 1) / MRS)), dim3(MT), 0, s, X64, N, (int)d,
-                           ld64, nobs, Wt, ldwt, (int)M, out, ldo);
-    else
-        hipLaunchKernelGGL((masked_dist_kernel<MR, SQ>), dim3((unsigned)((N + MR - 1) / MR)), dim3(MT), 0, s, X64, N, (int)d,
-                           ld64, nobs, Wt, ldwt, (int)M, out, ldo);
-    return launch_status("masked_dist_kernel");
-}
-
-int launch_distances_masked_rows(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, double *out,
-                                 int64_t ldo, void *ws, size_t ws_bytes, hipStream_t s) {
-    return launch_distances_masked_form<false>(X, x_dtype, N, d, ldx, M, out, ldo, ws, ws_bytes, s);
-}
-
-int launch_distances_masked_rows_squared(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M,
-                                         double *out, int64_t ldo, void *ws, size_t ws_bytes, hipStream_t s) {
-    return launch_distances_masked_form<true>(X, x_dtype, N, d, ldx, M, out, ldo, ws, ws_bytes, s);
-}
-
 }  // namespace dbgsom
 
 using namespace dbgsom;
@@ -561,23 +475,6 @@ extern "C" {
 int dbgsom_distances(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx_dev,
                      const double *W_dev, int64_t M, const double *ww_dev, double *out_dev, int64_t ldo, void *stream) {
     return launch_distances(X_dev, x_dtype, N, d, ldx, xx_dev, W_dev, M, ww_dev, out_dev, ldo, (hipStream_t)stream);
-}
-
-int dbgsom_distances_masked(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *W_dev,
-                            int64_t M, int64_t ldw, double *out_dev, int64_t ldo, void *workspace_dev,
-                            size_t workspace_bytes, void *stream) {
-    TRY_STATUS(distances_masked_check(x_dtype, N, d, ldx, M, ldo));
-    DBGSOM_REQUIRE(ldw >= d, "ldw must be >= d");
-    if (N == 0) return DBGSOM_OK;
-    DBGSOM_REQUIRE(X_dev && W_dev && out_dev && workspace_dev, "null pointer");
-    if (workspace_bytes < bmu_masked_workspace_bytes(x_dtype, N, d, M)) {
-        set_error("dbgsom_distances_masked: workspace of %zu bytes, %zu needed", workspace_bytes,
-                  bmu_masked_workspace_bytes(x_dtype, N, d, M));
-        return DBGSOM_ENOMEM;
-    }
-    TRY_STATUS(launch_masked_weights(W_dev, M, d, ldw, workspace_dev, (hipStream_t)stream));
-    return launch_distances_masked_rows(X_dev, x_dtype, N, d, ldx, M, out_dev, ldo, workspace_dev, workspace_bytes,
-                                        (hipStream_t)stream);
 }
 
 }  // extern "C"

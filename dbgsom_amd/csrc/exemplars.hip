@@ -35,8 +35,6 @@
 
 #include "wave_lex.h"
 
-#define TRY_STATUS(expr) do { int _rc = (expr); if (_rc != DBGSOM_OK) return _rc; } while (0)
-
 namespace dbgsom {
 
 constexpr int COLS_NT = 256;       // four wavefronts per workgroup

@@ -36,8 +36,6 @@
 
 #include "common.h"
 
-#define TRY_STATUS(expr) do { int _rc = (expr); if (_rc != DBGSOM_OK) return _rc; } while (0)
-
 namespace dbgsom {
 
 namespace {

@@ -24,8 +24,6 @@
 #include "bmu_common.h"
 #include "wave_lex.h"
 
-#define TRY_STATUS(expr) do { int _rc = (expr); if (_rc != DBGSOM_OK) return _rc; } while (0)
-
 namespace dbgsom {
 
 constexpr int TOPK_NT = 256;              // four wavefronts, four rows per workgroup
@@ -113,14 +111,12 @@ int launch_topk_rows_plain(const double *R, int64_t N, int64_t M, int64_t ldr, i
     return launch_topk_form<false>(R, N, M, ldr, k, idx, dist, s);
 }
 
-static int64_t slab_ld(int64_t M) { return kneighbors_slab_ld(M); }
-
 // The default: as many rows, in multiples of 128, as keep the slab at 64 MiB -- and where that is more than one full
 // grid of the product kernel (KNEIGHBORS_WAVE_ROWS: two workgroups of 128 rows on each of 256 CUs), whole grids only:
 // 655 workgroups run as long as 1024 do.
 int64_t kneighbors_slab_rows(int64_t N, int64_t M, int64_t slab_rows) {
     if (slab_rows < 1) {
-        slab_rows = std::max<int64_t>(128, KNEIGHBORS_SLAB_BYTES / (slab_ld(M) * 8) / 128 * 128);
+        slab_rows = std::max<int64_t>(128, KNEIGHBORS_SLAB_BYTES / (kneighbors_slab_ld(M) * 8) / 128 * 128);
         if (slab_rows > KNEIGHBORS_WAVE_ROWS) slab_rows = slab_rows / KNEIGHBORS_WAVE_ROWS * KNEIGHBORS_WAVE_ROWS;
     }
     return std::max<int64_t>(1, std::min(slab_rows, N));
@@ -128,16 +124,12 @@ int64_t kneighbors_slab_rows(int64_t N, int64_t M, int64_t slab_rows) {
 
 size_t kneighbors_workspace_bytes(int64_t N, int64_t M, int64_t slab_rows) {
     if (N < 1 || M < 1) return 0;
-    return align_up((size_t)kneighbors_slab_rows(N, M, slab_rows) * (size_t)slab_ld(M) * 8);
+    return align_up((size_t)kneighbors_slab_rows(N, M, slab_rows) * (size_t)kneighbors_slab_ld(M) * 8);
 }
 
 static int kneighbors_workspace_check(const char *fn, int64_t N, int64_t M, int64_t slab_rows, const void *ws,
                                       size_t ws_bytes, size_t in_front) {
-    const size_t need = in_front + kneighbors_workspace_bytes(N, M, slab_rows);
-    if (ws_bytes < need) {
-        set_error("%s: workspace of %zu bytes, %zu needed", fn, ws_bytes, need);
-        return DBGSOM_ENOMEM;
-    }
+    TRY_STATUS(workspace_check(fn, ws_bytes, in_front + kneighbors_workspace_bytes(N, M, slab_rows)));
     if (!is_aligned(ws, 16)) {
         set_error("%s: workspace_dev must be 16-byte aligned", fn);
         return DBGSOM_EINVAL;
@@ -155,16 +147,11 @@ int launch_kneighbors(const void *X, int x_dtype, int64_t N, int64_t d, int64_t 
     if (N == 0) return DBGSOM_OK;
     DBGSOM_REQUIRE(X && xx && W && ww && idx && dist && ws, "null pointer");
     TRY_STATUS(kneighbors_workspace_check("dbgsom_kneighbors", N, M, slab_rows, ws, ws_bytes, 0));
-    const int64_t rows = kneighbors_slab_rows(N, M, slab_rows), ldr = slab_ld(M);
     double *slab = static_cast<double *>(ws);
-    const size_t es = dtype_size(x_dtype);
-    for (int64_t r0 = 0; r0 < N; r0 += rows) {
-        const int64_t n = std::min(rows, N - r0);
-        TRY_STATUS(launch_distances_squared(static_cast<const char *>(X) + (size_t)r0 * ldx * es, x_dtype, n, d, ldx,
-                                            xx + r0, W, M, ww, slab, ldr, s));
-        TRY_STATUS(launch_topk_rows(slab, n, M, ldr, k, idx + r0 * k, dist + r0 * k, s));
-    }
-    return DBGSOM_OK;
+    return kneighbors_slabs(X, x_dtype, N, ldx, M, k, slab_rows, slab, launch_topk_rows, idx, dist, s,
+                            [&](const void *rows, int64_t r0, int64_t n, double *out, int64_t ldr) {
+                                return launch_distances_squared(rows, x_dtype, n, d, ldx, xx + r0, W, M, ww, out, ldr, s);
+                            });
 }
 
 // metric="cosine": slabs of the cosine matrix (u, v: cosine.hip), then the selection that stores what it selected on
@@ -178,16 +165,11 @@ int launch_kneighbors_cosine(const void *X, int x_dtype, int64_t N, int64_t d, i
     if (N == 0) return DBGSOM_OK;
     DBGSOM_REQUIRE(X && u && W && v && idx && dist && ws, "null pointer");
     TRY_STATUS(kneighbors_workspace_check("dbgsom_kneighbors_cosine", N, M, slab_rows, ws, ws_bytes, 0));
-    const int64_t rows = kneighbors_slab_rows(N, M, slab_rows), ldr = slab_ld(M);
     double *slab = static_cast<double *>(ws);
-    const size_t es = dtype_size(x_dtype);
-    for (int64_t r0 = 0; r0 < N; r0 += rows) {
-        const int64_t n = std::min(rows, N - r0);
-        TRY_STATUS(launch_distances_cosine_slab(static_cast<const char *>(X) + (size_t)r0 * ldx * es, x_dtype, n, d, ldx,
-                                                u + r0, W, M, v, slab, ldr, s));
-        TRY_STATUS(launch_topk_rows_plain(slab, n, M, ldr, k, idx + r0 * k, dist + r0 * k, s));
-    }
-    return DBGSOM_OK;
+    return kneighbors_slabs(X, x_dtype, N, ldx, M, k, slab_rows, slab, launch_topk_rows_plain, idx, dist, s,
+                            [&](const void *rows, int64_t r0, int64_t n, double *out, int64_t ldr) {
+                                return launch_distances_cosine_slab(rows, x_dtype, n, d, ldx, u + r0, W, M, v, out, ldr, s);
+                            });
 }
 
 // workspace: [that of bmu_masked_workspace_bytes for one slab of rows, Wt in front | the slab]
@@ -211,18 +193,13 @@ int launch_kneighbors_masked_rows(const void *X, int x_dtype, int64_t N, int64_t
     TRY_STATUS(kneighbors_masked_check(x_dtype, N, d, ldx, M, k, slab_rows));
     if (N == 0) return DBGSOM_OK;
     DBGSOM_REQUIRE(X && idx && dist && ws, "null pointer");
-    const int64_t rows = kneighbors_slab_rows(N, M, slab_rows), ldr = slab_ld(M);
-    const size_t front = align_up(bmu_masked_workspace_bytes(x_dtype, rows, d, M));
+    const size_t front = align_up(bmu_masked_workspace_bytes(x_dtype, kneighbors_slab_rows(N, M, slab_rows), d, M));
     TRY_STATUS(kneighbors_workspace_check("dbgsom_kneighbors_masked", N, M, slab_rows, ws, ws_bytes, front));
     double *slab = reinterpret_cast<double *>(static_cast<char *>(ws) + front);
-    const size_t es = dtype_size(x_dtype);
-    for (int64_t r0 = 0; r0 < N; r0 += rows) {
-        const int64_t n = std::min(rows, N - r0);
-        TRY_STATUS(launch_distances_masked_rows_squared(static_cast<const char *>(X) + (size_t)r0 * ldx * es, x_dtype, n,
-                                                        d, ldx, M, slab, ldr, ws, front, s));
-        TRY_STATUS(launch_topk_rows(slab, n, M, ldr, k, idx + r0 * k, dist + r0 * k, s));
-    }
-    return DBGSOM_OK;
+    return kneighbors_slabs(X, x_dtype, N, ldx, M, k, slab_rows, slab, launch_topk_rows, idx, dist, s,
+                            [&](const void *rows, int64_t, int64_t n, double *out, int64_t ldr) {
+                                return launch_distances_masked_rows_squared(rows, x_dtype, n, d, ldx, M, out, ldr, ws, front, s);
+                            });
 }
 
 }  // namespace dbgsom

@@ -10,20 +10,15 @@
 // per entry that NumPy restates bit for bit.  Winners: lexicographic minimum on (dist, index) as everywhere in this
 // library; a pair whose distance is not below +inf (a NaN or an infinity in the row) is never a winner (Best::push).
 //
-// Layout (that of masked_bmu_kernel, masked.hip): the lanes of a workgroup own prototypes and read Wt, the transposed
-// float64 prototypes (d x ldwt, zeros behind column M), so one feature is one coalesced 512-byte read per wavefront,
-// shared by the R rows the workgroup walks.  The rows' entries are the same for every lane: they arrive by scalar
-// loads, the next row's in flight.  What the vector unit issues per (row, prototype, feature) is two v_add_f64: the
+// Kernels: direct_bmu_kernel and direct_dist_kernel (direct_rows.h, the layout in which the lanes own prototypes)
+// with AbsTerm and PlainFinish.  What the vector unit issues per (row, prototype, feature) is two v_add_f64: the
 // negation of w and the absolute value of t are source modifiers.  float32 rows are widened (exactly) into the
 // workspace first: widening inside the loop would be a third vector instruction per entry and wavefront.
 #include <math.h>
 
 #include <algorithm>
 
-#include "bmu_common.h"
-#include "masked_common.h"
-
-#define TRY_STATUS(expr) do { int _rc = (expr); if (_rc != DBGSOM_OK) return _rc; } while (0)
+#include "direct_rows.h"
 
 namespace dbgsom {
 
@@ -37,141 +32,9 @@ __global__ __launch_bounds__(256) void l1_prepare_kernel(const float *__restrict
     for (int c = lane; c < d; c += 64) Xw[i * (int64_t)d + c] = widen(x[c]);
 }
 
-// U features of R rows against this lane's prototype: acc[r] goes on along its chain, k ascending
-// (uniform: the same entries for every lane; the next row's load is in flight while this row is worked on)
-template <int R, int U>
-__device__ __forceinline__ void l1_step(const double *__restrict__ xb, const uint32_t (&off)[R], int e,
-                                        const double *__restrict__ wcol, int64_t ldwt, double (&acc)[R]) {
-    double w[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) w[u] = wcol[(int64_t)(e + u) * ldwt];
-    double x[U], xn[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) xn[u] = (xb + (off[0] + (uint32_t)e))[u];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) x[u] = xn[u];
-        if (r + 1 < R) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) xn[u] = (xb + (off[r + 1] + (uint32_t)e))[u];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) acc[r] = acc[r] + fabs(x[u] - w[u]);
-    }
-}
-
-template <int K, int R>
-__global__ __launch_bounds__(MT) void l1_bmu_kernel(const double *__restrict__ X, int64_t N, int d, int64_t ldx,
-                                                    const double *__restrict__ Wt, int64_t ldwt, int M,
-                                                    int64_t *__restrict__ idx_out, double *__restrict__ dist_out) {
-    __shared__ double mv[MT / 64][R][K];
-    __shared__ int mj[MT / 64][R][K];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t i0 = (int64_t)blockIdx.x * R;
-    const int nrows = (int)min((int64_t)R, N - i0);
-    const double *__restrict__ xb = X + i0 * ldx;
-    uint32_t off[R];   // (rows behind the last one repeat it: computed, never written; R ldx < 2^32 is required)
-#pragma unroll
-    for (int r = 0; r < R; ++r) off[r] = (uint32_t)min(r, nrows - 1) * (uint32_t)ldx;
-    Best<K> best[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) best[r].init();
-
-    for (int jb = 0; jb < M; jb += MT) {
-        const int j = jb + tid;            // (j < ldwt: the columns behind M hold zeros)
-        const double *__restrict__ wcol = Wt + j;
-        double acc[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] = 0.0;
-        int e = 0;
-        for (; e + MU <= d; e += MU) l1_step<R, MU>(xb, off, e, wcol, ldwt, acc);
-        for (; e < d; ++e) l1_step<R, 1>(xb, off, e, wcol, ldwt, acc);
-        if (j < M) {
-#pragma unroll
-            for (int r = 0; r < R; ++r) best[r].push(acc[r], j);
-        }
-    }
-    // the lanes of a wavefront, then the wavefronts, hold different prototypes of the same rows
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            double ov[K];
-            int oj[K];
-#pragma unroll
-            for (int t = 0; t < K; ++t) {
-                ov[t] = __shfl_xor(best[r].v[t], m, 64);
-                oj[t] = __shfl_xor(best[r].j[t], m, 64);
-            }
-            best[r].merge(ov, oj);
-        }
-        if (lane == 0) {
-#pragma unroll
-            for (int t = 0; t < K; ++t) { mv[wave][r][t] = best[r].v[t]; mj[wave][r][t] = best[r].j[t]; }
-        }
-    }
-    __syncthreads();
-    if (tid < nrows) {
-        Best<K> b;
-#pragma unroll
-        for (int t = 0; t < K; ++t) { b.v[t] = mv[0][tid][t]; b.j[t] = mj[0][tid][t]; }
-#pragma unroll
-        for (int w = 1; w < MT / 64; ++w) {
-            double ov[K];
-            int oj[K];
-#pragma unroll
-            for (int t = 0; t < K; ++t) { ov[t] = mv[w][tid][t]; oj[t] = mj[w][tid][t]; }
-            b.merge(ov, oj);
-        }
-        const int64_t i = i0 + tid;
-#pragma unroll
-        for (int t = 0; t < K; ++t) {
-            idx_out[i * K + t] = (b.j[t] == 0x7fffffff) ? (int64_t)-1 : (int64_t)b.j[t];
-            dist_out[i * K + t] = b.v[t];
-        }
-    }
-}
-
-// ---- the same loop, every (row, prototype) stored -------------------------------------------------------
-// The lanes own prototypes, so the 256 distances of a row and prototype block are contiguous: one 8-byte store per
-// lane is a coalesced 512-byte store per wavefront whatever the alignment of `out` and ldo.  The full matrix is never
-// read again here (non-temporal stores); the slab of the selection is read back at once (ordinary stores).  A slab has
-// few rows (64 MiB of it at M = 1024 are 8192 rows: 512 workgroups), so its launch also divides the prototype blocks
-// over blockIdx.y; a pair's chain does not depend on the workgroup that runs it.
+// A slab of the selection has few rows (64 MiB of it at M = 1024 are 8192 rows: 512 workgroups), so its launch also
+// divides the prototype blocks over blockIdx.y.
 constexpr int64_t L1_SLAB_FILL_BLOCKS = 2048;   // slab form: the grid the launcher aims at (8 workgroups x 256 CUs)
-template <int R, bool SLAB>
-__global__ __launch_bounds__(MT) void l1_dist_kernel(const double *__restrict__ X, int64_t N, int d, int64_t ldx,
-                                                     const double *__restrict__ Wt, int64_t ldwt, int M,
-                                                     double *__restrict__ out, int64_t ldo) {
-    const int tid = threadIdx.x;
-    const int64_t i0 = (int64_t)blockIdx.x * R;
-    const int nrows = (int)min((int64_t)R, N - i0);
-    const double *__restrict__ xb = X + i0 * ldx;
-    uint32_t off[R];   // (rows behind the last one repeat it: computed, never written; R ldx < 2^32 is required)
-#pragma unroll
-    for (int r = 0; r < R; ++r) off[r] = (uint32_t)min(r, nrows - 1) * (uint32_t)ldx;
-    for (int jb = (int)blockIdx.y * MT; jb < M; jb += (int)gridDim.y * MT) {
-        const int j = jb + tid;            // (j < ldwt: the columns behind M hold zeros)
-        const double *__restrict__ wcol = Wt + j;
-        double acc[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] = 0.0;
-        int e = 0;
-        for (; e + MU <= d; e += MU) l1_step<R, MU>(xb, off, e, wcol, ldwt, acc);
-        for (; e < d; ++e) l1_step<R, 1>(xb, off, e, wcol, ldwt, acc);
-        if (j < M) {
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                if (r < nrows) {
-                    double *p = out + (i0 + r) * ldo + j;
-                    if constexpr (SLAB) *p = acc[r];
-                    else __builtin_nontemporal_store(acc[r], p);
-                }
-            }
-        }
-    }
-}
 
 // -------------------------------------------------------------------------------------------------------
 // workspace: [Wt: d x ldwt float64 | float32 rows only: N x d float64]
@@ -184,14 +47,6 @@ size_t bmu_manhattan_workspace_bytes(int x_dtype, int64_t N, int64_t d, int64_t 
 
 int launch_manhattan_weights(const double *W, int64_t M, int64_t d, int64_t ldw, void *ws, hipStream_t s) {
     return launch_transpose_weights(W, M, d, ldw, static_cast<double *>(ws), csr_wt_ld(M), s);
-}
-
-static int l1_workspace_check(const char *fn, size_t have, size_t need) {
-    if (have < need) {
-        set_error("%s: workspace of %zu bytes, %zu needed", fn, have, need);
-        return DBGSOM_ENOMEM;
-    }
-    return DBGSOM_OK;
 }
 
 // the rows as float64: float64 rows as they are, float32 rows widened behind Wt in the workspace
@@ -207,25 +62,22 @@ static int l1_rows64(const void *X, int x_dtype, int64_t N, int64_t d, int64_t l
     return launch_status("l1_prepare_kernel");
 }
 
+template <int K, int R>
+struct L1Search { static constexpr auto kernel = direct_bmu_kernel<AbsTerm, PlainFinish, K, R>; };
+
 // the search of N rows against the transposed prototypes launch_manhattan_weights left in front of `ws`
 int launch_bmu_manhattan_rows(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, int k,
                               int64_t *idx, double *dist, void *ws, size_t ws_bytes, hipStream_t s) {
     TRY_STATUS(masked_check_shape(x_dtype, N, d, ldx, M, k));
     if (N == 0) return DBGSOM_OK;
     DBGSOM_REQUIRE(X && idx && dist && ws, "null pointer");
-    TRY_STATUS(l1_workspace_check("dbgsom_bmu_manhattan", ws_bytes, bmu_manhattan_workspace_bytes(x_dtype, N, d, M)));
+    TRY_STATUS(workspace_check("dbgsom_bmu_manhattan", ws_bytes, bmu_manhattan_workspace_bytes(x_dtype, N, d, M)));
     const double *X64;
     int64_t ld64;
     TRY_STATUS(l1_rows64(X, x_dtype, N, d, ldx, M, ws, &X64, &ld64, s));
-    const double *Wt = static_cast<const double *>(ws);
-    const int64_t ldwt = csr_wt_ld(M);
-#define DBGSOM_BMU_L1(KK, RR)                                                                                   \
-    hipLaunchKernelGGL((l1_bmu_kernel<KK, RR>), dim3((unsigned)((N + RR - 1) / RR)), dim3(MT), 0, s, X64, N, (int)d, \
-                       ld64, Wt, ldwt, (int)M, idx, dist)
-    if (N < MASKED_FEW_ROWS) { if (k == 1) DBGSOM_BMU_L1(1, MRS); else DBGSOM_BMU_L1(2, MRS); }
-    else { if (k == 1) DBGSOM_BMU_L1(1, MR); else DBGSOM_BMU_L1(2, MR); }
-#undef DBGSOM_BMU_L1
-    return launch_status("l1_bmu_kernel");
+    launch_bmu_rows<L1Search>(N, k, s, X64, N, (int)d, ld64, static_cast<const double *>(ws), csr_wt_ld(M), (int)M, idx, dist,
+                              PlainFinish{});
+    return launch_status("l1_bmu_kernel");   // (the text as it always was; the kernel is direct_bmu_kernel)
 }
 
 static int distances_manhattan_check(int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, int64_t ldo) {
@@ -242,22 +94,16 @@ static int launch_distances_manhattan_form(const char *fn, const void *X, int x_
     if (N == 0) return DBGSOM_OK;
     DBGSOM_REQUIRE(X && out && ws, "null pointer");
     DBGSOM_REQUIRE(is_aligned(out, 8), "out_dev must be 8-byte aligned");
-    TRY_STATUS(l1_workspace_check(fn, ws_bytes, bmu_manhattan_workspace_bytes(x_dtype, N, d, M)));
+    TRY_STATUS(workspace_check(fn, ws_bytes, bmu_manhattan_workspace_bytes(x_dtype, N, d, M)));
     const double *X64;
     int64_t ld64;
     TRY_STATUS(l1_rows64(X, x_dtype, N, d, ldx, M, ws, &X64, &ld64, s));
-    const double *Wt = static_cast<const double *>(ws);
-    const int64_t ldwt = csr_wt_ld(M);
     const int64_t rb = N < MASKED_FEW_ROWS ? (N + MRS - 1) / MRS : (N + MR - 1) / MR, pb = (M + MT - 1) / MT;
     // slab form: as many shares of the prototype blocks as bring the grid to L1_SLAB_FILL_BLOCKS workgroups
     const unsigned gy = SLAB ? (unsigned)std::max<int64_t>(1, std::min(pb, (L1_SLAB_FILL_BLOCKS + rb - 1) / rb)) : 1u;
-    if (N < MASKED_FEW_ROWS)
-        hipLaunchKernelGGL((l1_dist_kernel<MRS, SLAB>), dim3((unsigned)rb, gy), dim3(MT), 0, s, X64, N, (int)d, ld64, Wt, ldwt,
-                           (int)M, out, ldo);
-    else
-        hipLaunchKernelGGL((l1_dist_kernel<MR, SLAB>), dim3((unsigned)rb, gy), dim3(MT), 0, s, X64, N, (int)d, ld64, Wt, ldwt,
-                           (int)M, out, ldo);
-    return launch_status("l1_dist_kernel");
+    launch_direct_dist<AbsTerm, PlainFinish, SLAB, true>(X64, N, d, ld64, static_cast<const double *>(ws), M, out, ldo,
+                                                         PlainFinish{}, gy, s);
+    return launch_status("l1_dist_kernel");   // (the text as it always was; the kernel is direct_dist_kernel)
 }
 
 int launch_distances_manhattan_rows(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, double *out,
@@ -267,9 +113,6 @@ int launch_distances_manhattan_rows(const void *X, int x_dtype, int64_t N, int64
 }
 
 // ---- the k nearest prototypes: slabs of rows, the selection of kneighbors.hip without its square root --------
-// rows of the slab M rounded up to even apart, so that every row starts on 16 bytes (as the squared forms)
-static int64_t l1_slab_ld(int64_t M) { return M + (M & 1); }
-
 // workspace: [that of bmu_manhattan_workspace_bytes for one slab of rows, Wt in front | the slab]
 size_t kneighbors_manhattan_workspace_bytes(int x_dtype, int64_t N, int64_t d, int64_t M, int64_t slab_rows) {
     if (N < 1 || M < 1 || d < 1) return 0;
@@ -293,21 +136,16 @@ int launch_kneighbors_manhattan_rows(const void *X, int x_dtype, int64_t N, int6
     TRY_STATUS(kneighbors_manhattan_check(x_dtype, N, d, ldx, M, k, slab_rows));
     if (N == 0) return DBGSOM_OK;
     DBGSOM_REQUIRE(X && idx && dist && ws, "null pointer");
-    TRY_STATUS(l1_workspace_check("dbgsom_kneighbors_manhattan", ws_bytes,
-                                  kneighbors_manhattan_workspace_bytes(x_dtype, N, d, M, slab_rows)));
+    TRY_STATUS(workspace_check("dbgsom_kneighbors_manhattan", ws_bytes,
+                               kneighbors_manhattan_workspace_bytes(x_dtype, N, d, M, slab_rows)));
     DBGSOM_REQUIRE(is_aligned(ws, 16), "workspace_dev must be 16-byte aligned");
-    const int64_t rows = kneighbors_slab_rows(N, M, slab_rows), ldr = l1_slab_ld(M);
-    const size_t front = align_up(bmu_manhattan_workspace_bytes(x_dtype, rows, d, M));
+    const size_t front = align_up(bmu_manhattan_workspace_bytes(x_dtype, kneighbors_slab_rows(N, M, slab_rows), d, M));
     double *slab = reinterpret_cast<double *>(static_cast<char *>(ws) + front);
-    const size_t es = dtype_size(x_dtype);
-    for (int64_t r0 = 0; r0 < N; r0 += rows) {
-        const int64_t n = std::min(rows, N - r0);
-        TRY_STATUS(launch_distances_manhattan_form<true>("dbgsom_kneighbors_manhattan",
-                                                         static_cast<const char *>(X) + (size_t)r0 * ldx * es, x_dtype, n, d,
-                                                         ldx, M, slab, ldr, ws, front, s));
-        TRY_STATUS(launch_topk_rows_plain(slab, n, M, ldr, k, idx + r0 * k, dist + r0 * k, s));
-    }
-    return DBGSOM_OK;
+    return kneighbors_slabs(X, x_dtype, N, ldx, M, k, slab_rows, slab, launch_topk_rows_plain, idx, dist, s,
+                            [&](const void *rows, int64_t, int64_t n, double *out, int64_t ldr) {
+                                return launch_distances_manhattan_form<true>("dbgsom_kneighbors_manhattan", rows, x_dtype, n,
+                                                                             d, ldx, M, out, ldr, ws, front, s);
+                            });
 }
 
 }  // namespace dbgsom
@@ -327,7 +165,7 @@ int dbgsom_bmu_manhattan(const void *X_dev, int x_dtype, int64_t N, int64_t d, i
     DBGSOM_REQUIRE(ldw >= d, "ldw must be >= d");
     if (N == 0) return DBGSOM_OK;
     DBGSOM_REQUIRE(X_dev && W_dev && idx_dev && dist_dev && workspace_dev, "null pointer");
-    TRY_STATUS(l1_workspace_check("dbgsom_bmu_manhattan", workspace_bytes, bmu_manhattan_workspace_bytes(x_dtype, N, d, M)));
+    TRY_STATUS(workspace_check("dbgsom_bmu_manhattan", workspace_bytes, bmu_manhattan_workspace_bytes(x_dtype, N, d, M)));
     TRY_STATUS(launch_manhattan_weights(W_dev, M, d, ldw, workspace_dev, (hipStream_t)stream));
     return launch_bmu_manhattan_rows(X_dev, x_dtype, N, d, ldx, M, k, idx_dev, dist_dev, workspace_dev, workspace_bytes,
                                      (hipStream_t)stream);
@@ -341,8 +179,8 @@ int dbgsom_distances_manhattan(const void *X_dev, int x_dtype, int64_t N, int64_
     if (N == 0) return DBGSOM_OK;
     DBGSOM_REQUIRE(X_dev && W_dev && out_dev && workspace_dev, "null pointer");
     DBGSOM_REQUIRE(is_aligned(out_dev, 8), "out_dev must be 8-byte aligned");
-    TRY_STATUS(l1_workspace_check("dbgsom_distances_manhattan", workspace_bytes,
-                                  bmu_manhattan_workspace_bytes(x_dtype, N, d, M)));
+    TRY_STATUS(workspace_check("dbgsom_distances_manhattan", workspace_bytes,
+                               bmu_manhattan_workspace_bytes(x_dtype, N, d, M)));
     TRY_STATUS(launch_manhattan_weights(W_dev, M, d, ldw, workspace_dev, (hipStream_t)stream));
     return launch_distances_manhattan_rows(X_dev, x_dtype, N, d, ldx, M, out_dev, ldo, workspace_dev, workspace_bytes,
                                            (hipStream_t)stream);
@@ -359,8 +197,8 @@ int dbgsom_kneighbors_manhattan(const void *X_dev, int x_dtype, int64_t N, int64
     DBGSOM_REQUIRE(ldw >= d, "ldw must be >= d");
     if (N == 0) return DBGSOM_OK;
     DBGSOM_REQUIRE(X_dev && W_dev && idx_dev && dist_dev && workspace_dev, "null pointer");
-    TRY_STATUS(l1_workspace_check("dbgsom_kneighbors_manhattan", workspace_bytes,
-                                  kneighbors_manhattan_workspace_bytes(x_dtype, N, d, M, slab_rows)));
+    TRY_STATUS(workspace_check("dbgsom_kneighbors_manhattan", workspace_bytes,
+                               kneighbors_manhattan_workspace_bytes(x_dtype, N, d, M, slab_rows)));
     DBGSOM_REQUIRE(is_aligned(workspace_dev, 16), "workspace_dev must be 16-byte aligned");
     TRY_STATUS(launch_manhattan_weights(W_dev, M, d, ldw, workspace_dev, (hipStream_t)stream));
     return launch_kneighbors_manhattan_rows(X_dev, x_dtype, N, d, ldx, M, k, slab_rows, idx_dev, dist_dev, workspace_dev,

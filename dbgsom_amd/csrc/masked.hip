@@ -11,19 +11,16 @@
 // the rows that share a workgroup or the position of the prototype among the others.  Winners: lexicographic
 // minimum on (sum, index) as everywhere in this library, then the scale and the square root.
 //
-// Layout (that of bmu_csr_kernel): the lanes of a workgroup own prototypes and read Wt, the transposed
-// float64 prototypes (d x ldwt, zeros behind column M), so one feature is one coalesced 512-byte read per
-// wavefront, shared by the R rows the workgroup walks.  The rows' entries are the same for every lane: they
-// arrive by scalar loads, the NaN test is integer arithmetic on the scalar unit and a missing entry is a
-// uniform skip.  What the vector unit issues per (row, prototype, observed entry) is one v_add_f64 and one
-// v_fma_f64.  float32 rows are widened (exactly) into the workspace first: widening inside the loop would be
-// a third vector instruction per entry and wavefront.
+// The N x M matrix of these distances is the same chain with every (row, prototype) stored.
+//
+// Kernels: masked_bmu_kernel below and direct_dist_kernel, on the pieces of direct_rows.h (the layout in which the
+// lanes own prototypes) with SquaredObservedTerm and ObservedFinish.  The rows' entries arrive by scalar loads, the
+// NaN test is integer arithmetic on the scalar unit and a missing entry is a uniform skip.  What the vector unit
+// issues per (row, prototype, observed entry) is one v_add_f64 and one v_fma_f64.  float32 rows are widened (exactly)
+// into the workspace first: widening inside the loop would be a third vector instruction per entry and wavefront.
 #include <math.h>
 
-#include "bmu_common.h"
-#include "masked_common.h"
-
-#define TRY_STATUS(expr) do { int _rc = (expr); if (_rc != DBGSOM_OK) return _rc; } while (0)
+#include "direct_rows.h"
 
 namespace dbgsom {
 
@@ -45,14 +42,15 @@ __global__ __launch_bounds__(256) void masked_prepare_kernel(const T *__restrict
     if (lane == 0) nobs[i] = n;
 }
 
+// ---- search: direct_bmu_kernel (direct_rows.h) with SquaredObservedTerm and ObservedFinish, n_obs among its
+// arguments.  A kernel of its own: merged into that one (n_obs behind the other arguments, inside the finish) it
+// measured 0.2 % slower on 2e5 x 784 rows at 50 % missing, against the same library in the same visit.
 template <int K, int R>
 __global__ __launch_bounds__(MT) void masked_bmu_kernel(const double *__restrict__ X, int64_t N, int d, int64_t ldx,
                                                         const int32_t *__restrict__ nobs,
                                                         const double *__restrict__ Wt, int64_t ldwt, int M,
                                                         int64_t *__restrict__ idx_out, double *__restrict__ dist_out) {
-    __shared__ double mv[MT / 64][R][K];
-    __shared__ int mj[MT / 64][R][K];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int64_t i0 = (int64_t)blockIdx.x * R;
     const int nrows = (int)min((int64_t)R, N - i0);
     const double *__restrict__ xb = X + i0 * ldx;
@@ -70,54 +68,18 @@ __global__ __launch_bounds__(MT) void masked_bmu_kernel(const double *__restrict
 #pragma unroll
         for (int r = 0; r < R; ++r) acc[r] = 0.0;
         int e = 0;
-        for (; e + MU <= d; e += MU) masked_step<R, MU>(xb, off, e, wcol, ldwt, acc);
-        for (; e < d; ++e) masked_step<R, 1>(xb, off, e, wcol, ldwt, acc);
+        for (; e + MU <= d; e += MU) dense_step<SquaredObservedTerm, R, MU>(xb, off, e, wcol, ldwt, acc);
+        for (; e < d; ++e) dense_step<SquaredObservedTerm, R, 1>(xb, off, e, wcol, ldwt, acc);
         if (j < M) {
 #pragma unroll
             for (int r = 0; r < R; ++r) best[r].push(acc[r], j);
         }
     }
-    // the lanes of a wavefront, then the wavefronts, hold different prototypes of the same rows
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            double ov[K];
-            int oj[K];
-#pragma unroll
-            for (int t = 0; t < K; ++t) {
-                ov[t] = __shfl_xor(best[r].v[t], m, 64);
-                oj[t] = __shfl_xor(best[r].j[t], m, 64);
-            }
-            best[r].merge(ov, oj);
-        }
-        if (lane == 0) {
-#pragma unroll
-            for (int t = 0; t < K; ++t) { mv[wave][r][t] = best[r].v[t]; mj[wave][r][t] = best[r].j[t]; }
-        }
-    }
-    __syncthreads();
-    if (tid < nrows) {
-        Best<K> b;
-#pragma unroll
-        for (int t = 0; t < K; ++t) { b.v[t] = mv[0][tid][t]; b.j[t] = mj[0][tid][t]; }
-#pragma unroll
-        for (int w = 1; w < MT / 64; ++w) {
-            double ov[K];
-            int oj[K];
-#pragma unroll
-            for (int t = 0; t < K; ++t) { ov[t] = mv[w][tid][t]; oj[t] = mj[w][tid][t]; }
-            b.merge(ov, oj);
-        }
-        const int64_t i = i0 + tid;
-        const double scale = (double)d / (double)nobs[i];   // (no observed entry: 0 * inf, the distance is NaN)
-#pragma unroll
-        for (int t = 0; t < K; ++t) {
-            idx_out[i * K + t] = (b.j[t] == 0x7fffffff) ? (int64_t)-1 : (int64_t)b.j[t];
-            dist_out[i * K + t] = sqrt(b.v[t] * scale);
-        }
-    }
+    const ObservedFinish<false> fin{nobs};
+    DBGSOM_STORE_WINNERS(K, R, best, i0, nrows, d, fin, idx_out, dist_out);
 }
+template <int K, int R>
+struct MaskedSearch { static constexpr auto kernel = masked_bmu_kernel<K, R>; };
 
 // ---- X[i][c] = (T) W[idx[i]][c] wherever X[i][c] is NaN ---------------------------------------------------
 template <typename T>
@@ -162,46 +124,9 @@ int launch_masked_weights(const double *W, int64_t M, int64_t d, int64_t ldw, vo
     return launch_transpose_weights(W, M, d, ldw, static_cast<double *>(ws), csr_wt_ld(M), s);
 }
 
-// the search of N rows against the transposed prototypes launch_masked_weights left in front of `ws`
-int launch_bmu_masked_rows(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, int k,
-                           int64_t *idx, double *dist, void *ws, size_t ws_bytes, hipStream_t s) {
-    TRY_STATUS(masked_check_shape(x_dtype, N, d, ldx, M, k));
-    if (N == 0) return DBGSOM_OK;
-    DBGSOM_REQUIRE(X && idx && dist && ws, "null pointer");
-    if (ws_bytes < bmu_masked_workspace_bytes(x_dtype, N, d, M)) {
-        set_error("dbgsom_bmu_masked: workspace of %zu bytes, %zu needed", ws_bytes,
-                  bmu_masked_workspace_bytes(x_dtype, N, d, M));
-        return DBGSOM_ENOMEM;
-    }
-    char *p = static_cast<char *>(ws);
-    const double *Wt = reinterpret_cast<const double *>(p);
-    int32_t *nobs = reinterpret_cast<int32_t *>(p + masked_wt_bytes(d, M));
-    double *Xw = reinterpret_cast<double *>(p + masked_wt_bytes(d, M) + masked_nobs_bytes(N));
-    const dim3 pgrid((unsigned)((N + 3) / 4));
-    const double *X64;
-    int64_t ld64;
-    if (x_dtype == DBGSOM_F32) {
-        hipLaunchKernelGGL(masked_prepare_kernel<float>, pgrid, dim3(256), 0, s, (const float *)X, N, (int)d, ldx, nobs, Xw);
-        X64 = Xw; ld64 = d;
-    } else {
-        hipLaunchKernelGGL(masked_prepare_kernel<double>, pgrid, dim3(256), 0, s, (const double *)X, N, (int)d, ldx, nobs,
-                           (double *)nullptr);
-        X64 = (const double *)X; ld64 = ldx;
-    }
-    TRY_STATUS(launch_status("masked_prepare_kernel"));
-    const int64_t ldwt = csr_wt_ld(M);
-#define DBGSOM_BMU_MASKED(KK, RR)                                                                                \
-    hipLaunchKernelGGL((masked_bmu_kernel<KK, RR>), dim3((unsigned)((N + RR - 1) / RR)), dim3(MT), 0, s, X64, N, \
-                       (int)d, ld64, nobs, Wt, ldwt, (int)M, idx, dist)
-    if (N < MASKED_FEW_ROWS) { if (k == 1) DBGSOM_BMU_MASKED(1, MRS); else DBGSOM_BMU_MASKED(2, MRS); }
-    else { if (k == 1) DBGSOM_BMU_MASKED(1, MR); else DBGSOM_BMU_MASKED(2, MR); }
-#undef DBGSOM_BMU_MASKED
-    return launch_status("masked_bmu_kernel");
-}
-
-// The two halves of launch_bmu_masked_rows on their own, for rows that stay where they are (the resident rows of a
-// fit on incomplete data): what depends on the rows alone -- n_obs and, for float32 rows, the float64 copy
-// (N x d, no padding) -- is made once per load, and every search reads it.
+// The halves of a search, on their own for rows that stay where they are (the resident rows of a fit on incomplete
+// data): what depends on the rows alone -- n_obs and, for float32 rows, the float64 copy (N x d, no padding) -- is
+// made once per load, and every search reads it.
 int launch_masked_prepare(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int32_t *nobs, double *Xw,
                           hipStream_t s) {
     TRY_STATUS(masked_check_shape(x_dtype, N, d, ldx, 1, 1));
@@ -222,14 +147,71 @@ int launch_bmu_masked_prepared(const double *X64, int64_t N, int64_t d, int64_t 
     TRY_STATUS(masked_check_shape(DBGSOM_F64, N, d, ld64, M, k));
     if (N == 0) return DBGSOM_OK;
     DBGSOM_REQUIRE(X64 && nobs && Wt && idx && dist, "null pointer");
-    const int64_t ldwt = csr_wt_ld(M);
-#define DBGSOM_BMU_MASKED(KK, RR)                                                                                \
-    hipLaunchKernelGGL((masked_bmu_kernel<KK, RR>), dim3((unsigned)((N + RR - 1) / RR)), dim3(MT), 0, s, X64, N, \
-                       (int)d, ld64, nobs, Wt, ldwt, (int)M, idx, dist)
-    if (N < MASKED_FEW_ROWS) { if (k == 1) DBGSOM_BMU_MASKED(1, MRS); else DBGSOM_BMU_MASKED(2, MRS); }
-    else { if (k == 1) DBGSOM_BMU_MASKED(1, MR); else DBGSOM_BMU_MASKED(2, MR); }
-#undef DBGSOM_BMU_MASKED
+    launch_bmu_rows<MaskedSearch>(N, k, s, X64, N, (int)d, ld64, nobs, Wt, csr_wt_ld(M), (int)M, idx, dist);
     return launch_status("masked_bmu_kernel");
+}
+
+// The workspace of N rows, Wt in front of it, and the prepared rows in it.
+struct MaskedRows {
+    const double *Wt;    // launch_masked_weights' output
+    int32_t *nobs;
+    const double *X64;   // float64 rows as they are, float32 rows widened behind n_obs
+    int64_t ld64;
+    int prepare(const char *fn, const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, void *ws,
+                size_t ws_bytes, hipStream_t s) {
+        TRY_STATUS(workspace_check(fn, ws_bytes, bmu_masked_workspace_bytes(x_dtype, N, d, M)));
+        char *p = static_cast<char *>(ws);
+        Wt = reinterpret_cast<const double *>(p);
+        nobs = reinterpret_cast<int32_t *>(p + masked_wt_bytes(d, M));
+        double *Xw = reinterpret_cast<double *>(p + masked_wt_bytes(d, M) + masked_nobs_bytes(N));
+        const bool f32 = x_dtype == DBGSOM_F32;
+        X64 = f32 ? Xw : static_cast<const double *>(X);
+        ld64 = f32 ? d : ldx;
+        return launch_masked_prepare(X, x_dtype, N, d, ldx, nobs, f32 ? Xw : nullptr, s);
+    }
+};
+
+// the search of N rows against the transposed prototypes launch_masked_weights left in front of `ws`
+int launch_bmu_masked_rows(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, int k,
+                           int64_t *idx, double *dist, void *ws, size_t ws_bytes, hipStream_t s) {
+    TRY_STATUS(masked_check_shape(x_dtype, N, d, ldx, M, k));
+    if (N == 0) return DBGSOM_OK;
+    DBGSOM_REQUIRE(X && idx && dist && ws, "null pointer");
+    MaskedRows r;
+    TRY_STATUS(r.prepare("dbgsom_bmu_masked", X, x_dtype, N, d, ldx, M, ws, ws_bytes, s));
+    return launch_bmu_masked_prepared(r.X64, N, d, r.ld64, r.nobs, r.Wt, M, k, idx, dist, s);
+}
+
+// ---- the N x M matrix: the same chain, same d / n_obs scale, same square root, every pair stored -------
+static int distances_masked_check(int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, int64_t ldo) {
+    TRY_STATUS(masked_check_shape(x_dtype, N, d, ldx, M, 1));
+    DBGSOM_REQUIRE(M <= DBGSOM_MAX_PROTOTYPES, "need 1 <= M <= DBGSOM_MAX_PROTOTYPES");
+    DBGSOM_REQUIRE(ldo >= M, "ldo must be >= M");
+    return DBGSOM_OK;
+}
+
+// SQ: the slab form of kneighbors.hip (the scaled sum without its square root, ordinary stores)
+template <bool SQ>
+static int launch_distances_masked_form(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M,
+                                        double *out, int64_t ldo, void *ws, size_t ws_bytes, hipStream_t s) {
+    TRY_STATUS(distances_masked_check(x_dtype, N, d, ldx, M, ldo));
+    if (N == 0) return DBGSOM_OK;
+    DBGSOM_REQUIRE(X && out && ws, "null pointer");
+    MaskedRows r;
+    TRY_STATUS(r.prepare("dbgsom_distances_masked", X, x_dtype, N, d, ldx, M, ws, ws_bytes, s));
+    launch_direct_dist<SquaredObservedTerm, ObservedFinish<SQ>, SQ, false>(r.X64, N, d, r.ld64, r.Wt, M, out, ldo,
+                                                                          ObservedFinish<SQ>{r.nobs}, 1u, s);
+    return launch_status("masked_dist_kernel");   // (the text as it always was; the kernel is direct_dist_kernel)
+}
+
+int launch_distances_masked_rows(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, double *out,
+                                 int64_t ldo, void *ws, size_t ws_bytes, hipStream_t s) {
+    return launch_distances_masked_form<false>(X, x_dtype, N, d, ldx, M, out, ldo, ws, ws_bytes, s);
+}
+
+int launch_distances_masked_rows_squared(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M,
+                                         double *out, int64_t ldo, void *ws, size_t ws_bytes, hipStream_t s) {
+    return launch_distances_masked_form<true>(X, x_dtype, N, d, ldx, M, out, ldo, ws, ws_bytes, s);
 }
 
 size_t masked_weights_bytes(int64_t d, int64_t M) { return masked_wt_bytes(d, M); }
@@ -266,14 +248,23 @@ int dbgsom_bmu_masked(const void *X_dev, int x_dtype, int64_t N, int64_t d, int6
     DBGSOM_REQUIRE(ldw >= d, "ldw must be >= d");
     if (N == 0) return DBGSOM_OK;
     DBGSOM_REQUIRE(X_dev && W_dev && idx_dev && dist_dev && workspace_dev, "null pointer");
-    if (workspace_bytes < bmu_masked_workspace_bytes(x_dtype, N, d, M)) {
-        set_error("dbgsom_bmu_masked: workspace of %zu bytes, %zu needed", workspace_bytes,
-                  bmu_masked_workspace_bytes(x_dtype, N, d, M));
-        return DBGSOM_ENOMEM;
-    }
+    TRY_STATUS(workspace_check("dbgsom_bmu_masked", workspace_bytes, bmu_masked_workspace_bytes(x_dtype, N, d, M)));
     TRY_STATUS(launch_masked_weights(W_dev, M, d, ldw, workspace_dev, (hipStream_t)stream));
     return launch_bmu_masked_rows(X_dev, x_dtype, N, d, ldx, M, k, idx_dev, dist_dev, workspace_dev, workspace_bytes,
                                   (hipStream_t)stream);
+}
+
+int dbgsom_distances_masked(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *W_dev,
+                            int64_t M, int64_t ldw, double *out_dev, int64_t ldo, void *workspace_dev,
+                            size_t workspace_bytes, void *stream) {
+    TRY_STATUS(distances_masked_check(x_dtype, N, d, ldx, M, ldo));
+    DBGSOM_REQUIRE(ldw >= d, "ldw must be >= d");
+    if (N == 0) return DBGSOM_OK;
+    DBGSOM_REQUIRE(X_dev && W_dev && out_dev && workspace_dev, "null pointer");
+    TRY_STATUS(workspace_check("dbgsom_distances_masked", workspace_bytes, bmu_masked_workspace_bytes(x_dtype, N, d, M)));
+    TRY_STATUS(launch_masked_weights(W_dev, M, d, ldw, workspace_dev, (hipStream_t)stream));
+    return launch_distances_masked_rows(X_dev, x_dtype, N, d, ldx, M, out_dev, ldo, workspace_dev, workspace_bytes,
+                                        (hipStream_t)stream);
 }
 
 int dbgsom_fill_missing(void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *W_dev, int64_t M,

@@ -16,8 +16,6 @@
 // or NaN of a raw caller) is loaded with the last 16-byte piece at most and never added or stored.
 #include "common.h"
 
-#define TRY_STATUS(expr) do { int _rc = (expr); if (_rc != DBGSOM_OK) return _rc; } while (0)
-
 namespace dbgsom {
 
 constexpr int FT = 256;    // threads per workgroup

@@ -58,8 +58,10 @@ CASES = [
 ]
 CASE_IDS = ["%s-N%d-M%d-d%d-pad%d-xoff%d-ldo+%d-ooff%d" % c for c in CASES]
 
-# dbgsom_distances_masked: make_case shapes of tests/test_missing_cpu.py
-MASKED_SHAPES = [(7, 3, 2), (257, 17, 5), (1000, 64, 129)]
+# dbgsom_distances_masked: make_case shapes of tests/test_missing_cpu.py.  The last one reaches the 16-row store kernel
+# (N >= 8192), rooted and squared: a last workgroup with one row, a feature tail behind one step of four, one
+# prototype block
+MASKED_SHAPES = [(7, 3, 2), (257, 17, 5), (1000, 64, 129), (8192 + 17, 5, 3)]
 MASKED_FRACS = [0.3, 0.9]
 
 

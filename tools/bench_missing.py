@@ -7,6 +7,8 @@ Each line:
   device_ms        dbgsom_bmu_masked on the whole batch in HBM, HIP events around the call on its stream: the
                    transposition of W, the pass that counts the observed entries (and widens float32 rows) and the
                    search; median of --steps
+  matrix_ms        dbgsom_distances_masked writing the N x M matrix, and knn_ms: dbgsom_kneighbors_masked with k = 8 (or M)
+                   at the default slab; HIP events as device_ms, median of --steps
   call_ms          HipBackend.bmu_masked from host arrays (chunked upload, search, download), host clock around the
                    blocking call; median of --steps
   rows_per_s       N / device_ms, and call_rows_per_s = N / call_ms
@@ -33,7 +35,7 @@ sys.path.insert(0, ROOT)
 
 SHAPES = {"wide": (200000, 784, 1024), "narrow": (200000, 64, 256)}
 PEAK_F64_VECTOR_FLOPS = 78.6e12
-ROWS_PER_WORKGROUP = 16   # csrc/masked.hip: MR (batches of 8192 rows and more)
+ROWS_PER_WORKGROUP = 16   # csrc/direct_rows.h: MR (batches of 8192 rows and more)
 
 
 def make(N, d, M, frac, seed=0):
@@ -118,6 +120,21 @@ def main():
                 "dbgsom_bmu_masked", Xt.data_ptr(), _native.F32, N, d, d, Wt.data_ptr(), M, d, 1, idx.data_ptr(),
                 dist.data_ptr(), ws.data_ptr(), nbytes, stream)), a.steps, a.warmup)
             dev_idx, dev_dist = idx.cpu().numpy().reshape(-1), dist.cpu().numpy().reshape(-1)
+            # the siblings that store every pair: the N x M matrix, and the k nearest through slabs of it
+            out = torch.empty((N, M), dtype=torch.float64, device="cuda")
+            matrix = median_ms(timed(lambda: _native.call(
+                "dbgsom_distances_masked", Xt.data_ptr(), _native.F32, N, d, d, Wt.data_ptr(), M, d, out.data_ptr(), M,
+                ws.data_ptr(), nbytes, stream)), a.steps, a.warmup)
+            del out
+            kk = min(8, M)
+            kbytes = lib.dbgsom_kneighbors_masked_workspace_bytes(_native.F32, N, d, M, 0)
+            kws = torch.empty(kbytes, dtype=torch.uint8, device="cuda")
+            kidx = torch.empty((N, kk), dtype=torch.int64, device="cuda")
+            kdist = torch.empty((N, kk), dtype=torch.float64, device="cuda")
+            knn = median_ms(timed(lambda: _native.call(
+                "dbgsom_kneighbors_masked", Xt.data_ptr(), _native.F32, N, d, d, Wt.data_ptr(), M, d, kk, 0,
+                kidx.data_ptr(), kdist.data_ptr(), kws.data_ptr(), kbytes, stream)), a.steps, a.warmup)
+            del kws, kidx, kdist
             call = median_ms(walled(lambda: hip.bmu_masked(W, 1, X)), a.steps, a.warmup)
             # for scale: the all-pairs search on the zero-filled rows
             X0 = np.nan_to_num(X, nan=0.0)
@@ -144,6 +161,8 @@ def main():
             line = {"shape": name, "N": N, "d": d, "M": M, "dtype": "float32", "missing": frac,
                     "observed_cells": observed,
                     "device_ms": round(dev[0], 3), "device_ms_min_max": [round(dev[1], 3), round(dev[2], 3)],
+                    "matrix_ms": round(matrix[0], 3), "matrix_ms_min_max": [round(matrix[1], 3), round(matrix[2], 3)],
+                    "knn_ms": round(knn[0], 3), "knn_ms_min_max": [round(knn[1], 3), round(knn[2], 3)], "knn_k": kk,
                     "call_ms": round(call[0], 3), "call_ms_min_max": [round(call[1], 3), round(call[2], 3)],
                     "rows_per_s": round(N / (dev[0] * 1e-3)), "call_rows_per_s": round(N / (call[0] * 1e-3)),
                     "pairs_per_s": round(pairs / (dev[0] * 1e-3)),

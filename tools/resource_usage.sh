@@ -1,6 +1,6 @@
 # registers, scratch, occupancy and LDS of every kernel of a source file, from the compiler's own remarks
 #   bash tools/resource_usage.sh filter      (CPU only: hipcc cross-compiles)
-#   bash tools/resource_usage.sh manhattan   (the table of DESIGN 4j)
+#   bash tools/resource_usage.sh manhattan   (the table of DESIGN 4j; masked: 4e and 4i; csr: 4d)
 #   bash tools/resource_usage.sh bmu_dma     (with bmu, distances, cosine: the table of DESIGN 4k)
 f=${1:-filter}
 cd "$(dirname "$0")/../dbgsom_amd/csrc"
