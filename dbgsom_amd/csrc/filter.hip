@@ -2932,6 +2932,7 @@ int dbgsom_filter_prepare(const void *X_dev, int x_dtype, int64_t N, int64_t d, 
                           void *planes_dev, size_t planes_bytes, void *stream) {
     DBGSOM_REQUIRE(valid_dtype(x_dtype) && N >= 1 && d >= 1 && ldx >= d && N < 0x7fffffff,
                    "bad samples");
+    DBGSOM_REQUIRE(d <= FILTER_MAX_D, "rows longer than 2^31 - 64 values");   // (d and its padded form are the kernel's int)
     DBGSOM_REQUIRE(X_dev && planes_dev && is_aligned(planes_dev, 256), "bad pointer");
     if (planes_bytes < dbgsom_filter_planes_bytes(N, d)) {
         set_error("dbgsom_filter_prepare: planes buffer too small");
@@ -3407,6 +3408,7 @@ int dbgsom::launch_bmu_filtered(const FilteredCall &call) {
     DBGSOM_REQUIRE(call.x_dtype == DBGSOM_F32 || call.x_dtype == DBGSOM_F64, "the filtered search takes float32 or float64 samples");
     DBGSOM_REQUIRE(call.N >= 1 && call.N < 0x7fffffff && call.d >= 1 && call.d % KT == 0 && call.ldx >= call.d,
                    "bad sample shape (d must be a multiple of 16)");
+    DBGSOM_REQUIRE(call.d <= FILTER_MAX_D, "rows longer than 2^31 - 64 values");
     DBGSOM_REQUIRE(call.M >= 1 && call.M <= SW_MAX_M, "M outside [1, 16000]");
     const bool seeds_only = call.seeds_out != nullptr;
     DBGSOM_REQUIRE(call.X && call.xx && call.xplanes && call.W && call.ww && call.ws, "null pointer");

@@ -17,6 +17,8 @@ constexpr int SW_MAX_KT = 1024;     // k-tiles that selection handles (d <= 6553
 constexpr int PRUNE_MAX_M = 8192;   // the gap matrix of the pruning form: 4 M^2 bytes (256 MB here)
 constexpr int SWEEP4_MAX_M = 8192;  // bitmask of the two-per-CU sweep's marked prototypes: 1 KB of its LDS
 
+constexpr int64_t FILTER_MAX_D = 0x7fffffc0;   // the kernels take d and filter_dpad(d) as int: the hosts refuse longer rows
+
 // plane rows are padded to whole k-tiles, at least two of them (the sweep's ring runs three tiles
 // ahead and keeps three chunk tables)
 inline int64_t filter_dpad(int64_t d) {
