@@ -33,6 +33,7 @@ LAYOUTS = {"compact": CENTRES_COMPACT, "aligned": CENTRES_ALIGNED}
 MAX_PROTOTYPES = 16000
 MAX_NEIGHBORS = 32      # DBGSOM_MAX_NEIGHBORS
 MAX_DIRECTIONS = 8      # DBGSOM_MAX_DIRECTIONS
+MAX_RADII = 32          # DBGSOM_MAX_RADII
 # counters of dbgsom_sparse_code / dbgsom_ctx_sparse_code (DBGSOM_SC_COUNTS, in this order)
 SC_COUNTS = ("samples", "iterations", "max_iterations", "drops", "degenerate", "early_stops", "aa_retries",
              "overflow", "max_active", "multi_drops", "g_rows")
@@ -172,6 +173,12 @@ SIGNATURES = {
     "dbgsom_ctx_exemplars_query": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _ci, _ci, _vp, _vp]),
     "dbgsom_ctx_exemplars_query_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _ci, _ci, _vp, _vp]),
     "dbgsom_ctx_exemplars_query_csr": (_ci, [_vp, _vp, _vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _ci, _ci, _vp, _vp]),
+    "dbgsom_range_count_cols": (_ci, [_vp, _i64, _i64, _i64, _vp, _ci, _vp, _vp]),
+    "dbgsom_range_counts_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "dbgsom_range_counts": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _ci, _i64, _vp, _vp, _sz, _vp]),
+    "dbgsom_ctx_range_counts_query": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _vp, _ci, _vp]),
+    "dbgsom_ctx_range_counts_query_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _vp, _ci, _vp]),
+    "dbgsom_ctx_range_counts_query_csr": (_ci, [_vp, _vp, _vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _vp, _ci, _vp]),
     "dbgsom_edge_lengths": (_ci, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
     "dbgsom_geodesics_workspace_bytes": (_sz, [_i64, _i64]),
     "dbgsom_geodesics": (_ci, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _sz, _vp]),

@@ -68,6 +68,30 @@ def _group_is_up() -> bool:
         return False
 
 
+def squared_threshold(rho) -> float:
+    """The largest float64 ``t`` with ``sqrt(t) <= rho`` under correctly rounded ``sqrt``, for a finite ``rho >= 0``:
+    ``rho * rho`` stepped with ``nextafter`` until ``sqrt(t) <= rho < sqrt(nextafter(t, inf))``.  ``sqrt`` is monotone and
+    correctly rounded on the host and on the device, so ``r <= t`` is exactly ``sqrt(r) <= rho`` for every ``r >= 0``:
+    ``range_counts`` compares squared values and takes no root per pair.  (A ``rho`` whose square overflows gives the
+    largest finite float64: no finite ``r`` has a root above it.)"""
+    rho = float(rho)
+    if not (np.isfinite(rho) and rho >= 0.0):
+        raise ValueError(f"a radius must be finite and >= 0, got {rho!r}")
+    big = float(np.finfo(np.float64).max)
+    with np.errstate(over="ignore", under="ignore"):
+        t = min(float(np.float64(rho) * np.float64(rho)), big)
+    while np.sqrt(t) > rho:
+        t = float(np.nextafter(t, -np.inf))
+    while t < big and np.sqrt(np.nextafter(t, np.inf)) <= rho:
+        t = float(np.nextafter(t, np.inf))
+    return t
+
+
+def squared_thresholds(radii) -> np.ndarray:
+    """``squared_threshold`` of every radius, as a contiguous float64 vector"""
+    return np.array([squared_threshold(r) for r in np.asarray(radii, dtype=np.float64).reshape(-1)], dtype=np.float64)
+
+
 class HotPathBackend:
     """Epoch template shared by the HIP backend and the test-only oracle backend:
     local per-prototype sums -> (all-reduce across sample shards) -> smoothing.
@@ -138,6 +162,25 @@ class HotPathBackend:
         is a total order: the result does not depend on chunks or slabs.  X as for ``distances``; the results are
         NumPy arrays, next to X for a device array."""
         raise NotImplementedError
+
+    def range_counts(self, W, thresholds_squared, X):
+        """The rows of X within a radius of every prototype -> counts, (rows of W, thresholds) int64:
+        ``counts[j, t] = #{ i : r_ij <= thresholds_squared[t] }``, r the squared value of ``bmu(W, k, X=X)``'s
+        arithmetic (what ``kneighbors`` selects on); 1 .. MAX_RADII thresholds in any order.  A pair whose r is NaN
+        is never counted.  Integer counts: the result does not depend on chunks or slabs.  X as for ``distances``; the
+        result is a NumPy array, next to X for a device array.
+
+        This default counts on the host over ``distances(W, X)``, whose entries are ``sqrt(r)``: it is exact for the
+        thresholds ``squared_threshold`` makes, the largest t under their root, for which ``sqrt(r) <= sqrt(t)`` is
+        ``r <= t``.  The HIP backend compares squared values on the device and holds no N x M matrix."""
+        thr = np.ascontiguousarray(thresholds_squared, dtype=np.float64).reshape(-1)
+        if not 1 <= thr.size <= _native.MAX_RADII:
+            raise ValueError(f"need 1 .. DBGSOM_MAX_RADII = {_native.MAX_RADII} thresholds, got {thr.size}")
+        D = self.distances(W, X)
+        D = D if isinstance(D, np.ndarray) else D.cpu().numpy()
+        with np.errstate(invalid="ignore"):
+            rho = np.sqrt(thr)
+            return np.stack([np.count_nonzero(D <= r, axis=0) for r in rho], axis=1).astype(np.int64)
 
     def geodesics(self, W, edges):
         """The weighted geodesics of the lattice -> G, (rows of W, rows of W) float64.  ``edges`` is an (E, 2) integer
@@ -1164,6 +1207,27 @@ class HipBackend(HotPathBackend):
         dist, idx = rows.empty((M, k), "float64"), rows.empty((M, k), "int64")
         self._query("exemplars_query", "euclidean", rows, W64.ctypes.data, M, k, own, rows.ptr(idx), rows.ptr(dist))
         return dist, idx
+
+    # -- the rows within a radius of every prototype ---------------------------------------------------
+    def range_counts(self, W, thresholds_squared, X):
+        """The rows within a radius of every prototype (csrc/density.hip): the squared distances of a slab of
+        ``kneighbors_slab_rows`` rows stay on the device, the fold reads them back from cache down their columns and
+        adds what passes each threshold into (rows of W, thresholds) int64 counts that live on the device for the
+        length of the call, and only those counts are the result.  The thresholds go up once.  Host rows go up in
+        chunks of ``distances_chunk_rows`` rows, every chunk folding into the counts; CSR rows are expanded on the
+        device chunk by chunk; rows of W x thresholds x 8 bytes come down, once.  For rows in HBM the result is an
+        array on their device (dbgsom_ctx_range_counts_query_device).  X without rows: zeros, no launch."""
+        rows = self._query_rows(X, defer=True)
+        W64, M = self._w64(W, rows.d)
+        thr = np.ascontiguousarray(thresholds_squared, dtype=np.float64).reshape(-1)
+        if not 1 <= thr.size <= _native.MAX_RADII:
+            raise ValueError(f"need 1 .. DBGSOM_MAX_RADII = {_native.MAX_RADII} thresholds, got {thr.size}")
+        if rows.N == 0:
+            return rows.full((M, thr.size), 0, "int64")
+        counts = rows.empty((M, thr.size), "int64")
+        self._query("range_counts_query", "euclidean", rows, W64.ctypes.data, M, thr.ctypes.data, thr.size,
+                    rows.ptr(counts))
+        return counts
 
     # -- weighted geodesics and the combined error of a query ------------------------------------------
     @staticmethod

@@ -65,9 +65,9 @@ from sklearn.utils import check_array, check_random_state
 from sklearn.utils.validation import check_is_fitted
 
 from . import schedule
-from ._native import MAX_NEIGHBORS
+from ._native import MAX_NEIGHBORS, MAX_RADII
 from .backend import (RESIDENT, HotPathBackend, array_namespace, dist_info, dtype_name, is_device_array, is_sparse,
-                      shard_bounds)
+                      shard_bounds, squared_thresholds)
 from .lattice import GrowingLattice
 
 
@@ -1416,6 +1416,100 @@ class BaseSom(BaseEstimator):
         else:
             dist, idx = self._engine().exemplars(self.weights_, k, X, own_cell=bool(own_cell))
         return (dist, idx) if return_distance else idx
+
+    @staticmethod
+    def _check_radii(radius):
+        """-> (the radii as a float64 vector, whether the caller gave a single one) for ``prototype_density``"""
+        bad = ValueError(f"radius must be None, a finite real number >= 0 or a 1-D array-like of 1 .. {MAX_RADII} of "
+                         f"them, got {radius!r}")
+        if isinstance(radius, (bool, np.bool_, str, bytes)):
+            raise bad
+        try:
+            rho = np.asarray(radius)
+        except (TypeError, ValueError):
+            raise bad from None
+        if not (np.issubdtype(rho.dtype, np.floating) or np.issubdtype(rho.dtype, np.integer)) or rho.ndim > 1:
+            raise bad
+        scalar = rho.ndim == 0
+        rho = rho.astype(np.float64).reshape(-1)
+        if rho.size == 0:
+            raise bad
+        if rho.size > MAX_RADII:
+            raise ValueError(f"{rho.size} radii are above the {MAX_RADII} the count on the GPU keeps per prototype: "
+                             "use several calls, or prototype_distances(X) and counts of one's own")
+        if not (np.isfinite(rho).all() and (rho >= 0.0).all()):
+            raise bad
+        return rho, scalar
+
+    def prototype_density(self, X, radius=None):
+        """The data density at the prototypes: ``counts[j]`` is the number of rows of X within ``radius`` of
+        prototype ``j``, whatever cell they fell into -- Ultsch's P-matrix, the second half of the U*-matrix, and what
+        tells a large U-height across an empty gap from one inside a dense region.  int64, ``(len(weights_),)`` for a
+        single radius and ``(len(weights_), len(radius))`` for a 1-D array-like of 1 .. 32 radii, columns in the
+        caller's order (any order, duplicates allowed): the whole step-kernel profile in one pass over X, as choosing
+        a radius (Ultsch's Pareto radius) needs it.
+
+        ``radius=None`` is the mean of the fitted map's U-matrix, the bandwidth of the per-node ``density`` statistic;
+        the value used is kept in ``density_radius_``.  Every radius is finite and ``>= 0``.
+
+        ``counts[j, t] = #{ i : sqrt(r_ij) <= radius[t] }`` with ``r_ij = max((|x_i|^2 + (-2 <x_i, w_j>)) + |w_j|^2,
+        0)`` the squared value of the best-matching-unit search's own arithmetic, the one ``kneighbors`` and
+        ``prototype_exemplars`` select on.  Invariant, integer for integer: ``counts[:, t] ==
+        np.count_nonzero(prototype_distances(X) <= radius[t], axis=0)``.  The comparison runs on the squared values
+        against the largest float64 under whose correctly rounded root the radius lies, which is the same condition;
+        a pair whose ``r`` is NaN is never counted.  Integer counts do not depend on chunks, slabs or where X lives: a
+        host array, a tensor and CSR rows of the same data give the same result.
+
+        X is what ``prototype_exemplars`` takes under the Euclidean metric: a dense array (a NumPy result;
+        ``len(weights_) * n_radii * 8`` bytes come down, once), a tensor on the estimator's GPU (an int64 tensor on
+        X's device that the GPU writes; nothing of X or the result touches the host), scipy sparse rows (the dense
+        call's result on ``X.toarray()``).  X without rows gives zeros without a launch.  The N x M matrix is never
+        held.  Refused with a ``ValueError``: ``metric="manhattan"`` / ``"cosine"``, rows with NaN (also under
+        ``missing_values``: impute them first), a feature-count mismatch, a bad ``radius``; above 32 radii
+        ``prototype_distances(X)`` is the route.  Only this map's prototypes are used (not the child maps of vertical
+        growth); the call is local to the process."""
+        check_is_fitted(self)
+        if radius is None:
+            rho, scalar = np.array([float(self._get_u_matrix().mean())]), True
+        else:
+            rho, scalar = self._check_radii(radius)
+        kind = self._search_metric()
+        if kind:
+            self._refuse_metric(kind, "prototype_density / u_star_matrix",
+                                "the count runs on the squared Euclidean distances of the search")
+        if not is_device_array(X) and not is_sparse(X) and np.ndim(X) == 2 and np.shape(X)[0] == 0:
+            X = check_array(X, dtype=[np.float64, np.float32], ensure_min_samples=0)   # (no rows: no launch)
+        else:
+            X = self._check_query(X)
+        if X.shape[1] != self.n_features_in_:
+            raise ValueError(f"X has {X.shape[1]} features, but {type(self).__name__} is expecting "
+                             f"{self.n_features_in_} features as input")
+        if isinstance(X, np.ndarray) and np.isnan(X).any():   # (passed _check_query: missing_values is set)
+            raise ValueError(f"X holds NaN: the density at a prototype is not defined on rows with missing entries "
+                             f"(missing_values={self.missing_values!r}); impute them first (impute(X))")
+        M = len(self.weights_)
+        if X.shape[0] == 0 and not is_device_array(X):
+            counts = np.zeros((M, rho.size), dtype=np.int64)
+        else:
+            counts = self._engine().range_counts(self.weights_, squared_thresholds(rho), X)
+        self.density_radius_ = float(rho[0]) if scalar else rho.copy()
+        return counts[:, 0] if scalar else counts
+
+    def u_star_matrix(self, X, radius=None) -> np.ndarray:
+        """The U*-matrix of Ultsch (2003): the U-matrix damped where the data is dense, an ``(len(weights_),)``
+        float64 NumPy array.  ``U* = U * scale`` with U the mean input-space distance from every prototype to its
+        lattice neighbours and ``scale_j = (P_j - mean(P)) / (mean(P) - max(P)) + 1``, ``P = prototype_density(X,
+        radius)`` (a single radius; ``None``: its default): 1 at the mean density, 0 at the densest unit, above 1 in
+        sparse regions; 1 everywhere when ``max(P) == mean(P)``.  Computed on the host from ``len(weights_)`` counts.
+        X and the refusals are ``prototype_density``'s."""
+        if radius is not None and not self._check_radii(radius)[1]:
+            raise ValueError(f"u_star_matrix takes one radius, got {radius!r}")
+        P = self._host(self.prototype_density(X, radius)).astype(np.float64)
+        U = self._get_u_matrix()
+        mean, top = P.mean(), P.max()
+        if top == mean:
+            return U * np.ones_like(P)
+        return U * ((P - mean) / (mean - top) + 1.0)
 
     def _lattice_edges(self) -> np.ndarray:
         """The undirected edges of the fitted lattice as an (E, 2) int32 array of indices into ``weights_`` /

@@ -278,6 +278,18 @@ int launch_exemplars_store(const double *state_r, const int64_t *state_i, int64_
 int launch_exemplars(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx, const double *W,
                      int64_t M, const double *ww, int k, int own_cell, int64_t slab_rows, int64_t *idx, double *dist,
                      void *ws, size_t ws_bytes, hipStream_t s);
+// the rows within a radius of every prototype (density.hip): the fold down the columns of a matrix of squared values --
+// counts (M x n_radii int64) += #{ i : r_ij <= thr[t] } --, the slab loop of launch_kneighbors with that fold behind the
+// product (into a caller's counts, which it does not zero), and the whole call, which does
+size_t range_counts_workspace_bytes(int64_t N, int64_t M, int64_t slab_rows);
+int launch_range_count_cols(const double *R, int64_t N, int64_t M, int64_t ldr, const double *thr, int n_radii,
+                            int64_t *counts, hipStream_t s);
+int launch_range_counts_fold(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx, const double *W,
+                             int64_t M, const double *ww, const double *thr, int n_radii, int64_t slab_rows, int64_t *counts,
+                             void *ws, size_t ws_bytes, hipStream_t s);
+int launch_range_counts(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx, const double *W,
+                        int64_t M, const double *ww, const double *thr, int n_radii, int64_t slab_rows, int64_t *counts,
+                        void *ws, size_t ws_bytes, hipStream_t s);
 // weighted geodesics over the lattice and the combined error read off them (geodesics.hip).  `status` is a zeroed
 // device word the kernels OR their findings into; geodesics_status reads it back (blocking) and names the call `what`
 size_t geodesics_workspace_bytes(int64_t M, int64_t E);

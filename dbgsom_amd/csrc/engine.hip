@@ -294,6 +294,9 @@ struct dbgsom_ctx {
     // the k nearest rows to every prototype (exemplars.hip): the state of the call's fold, [r: M x k float64 | i: M x k
     // int64] (the slab and the fold's scratch are kn_ws; a host-facing call's result is staged in kn_idx and kn_dist)
     DevBuf ex_state;
+    // the rows within a radius of every prototype (density.hip): the state of the call's fold, [counts: M x n_radii int64
+    // | the thresholds: n_radii float64] (the slab is kn_ws; the counts come down from here, nothing is staged)
+    DevBuf rc_state;
     // The resident rows have missing entries (NaN): option "incomplete", set after a load and cleared by the next one.
     // What depends on the rows alone is made when the option is set, once per load: n_obs per row (mf_nobs) and, for
     // float32 rows, their float64 copy (mf_x64, N x d x 8 bytes of HBM).  The ordinary calls then refuse to compute
@@ -1269,7 +1272,7 @@ int dbgsom_ctx_create(int device, dbgsom_ctx **out) {
      &(c)->shard_gather, &(c)->sw, &(c)->wh_order, &(c)->wh_ws, &(c)->sc_ws, &(c)->sc_x, &(c)->sc_w, &(c)->sc_p, &(c)->sc_code, &(c)->sc_proba, &(c)->sc_cnt, &(c)->wt,  \
      &(c)->mk_ws, &(c)->mk_x, &(c)->mk_w, &(c)->mk_idx, &(c)->mk_dist, &(c)->mf_nobs, &(c)->mf_x64, &(c)->mf_wt, &(c)->mf_w,   \
      &(c)->mf_wn, &(c)->mf_idx, &(c)->mf_dist, &(c)->mf_kw, &(c)->mf_sums, &(c)->mf_acc_ws, &(c)->mf_sm_ws, &(c)->mf_scal, \
-     &(c)->pd_out, &(c)->kn_ws, &(c)->kn_idx, &(c)->kn_dist, &(c)->de_h, &(c)->ce_g, &(c)->ce_ws, &(c)->ex_state, &(c)->l1_ws, &(c)->cos_u, &(c)->cos_v}
+     &(c)->pd_out, &(c)->kn_ws, &(c)->kn_idx, &(c)->kn_dist, &(c)->de_h, &(c)->ce_g, &(c)->ce_ws, &(c)->ex_state, &(c)->rc_state, &(c)->l1_ws, &(c)->cos_u, &(c)->cos_v}
 
 int dbgsom_ctx_destroy(dbgsom_ctx *c) {
     if (!c) return DBGSOM_OK;
@@ -1860,8 +1863,8 @@ int dbgsom_ctx_bmu_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const in
 // prototypes under every metric, and the search itself over rows with missing entries and under metric="manhattan"
 // and metric="cosine" -- is one of two loops over chunks of rows:
 //   raw_rows_query     masked / Manhattan / cosine: kernels that read the rows as they are stored (any row pitch)
-//   placed_rows_query  Euclidean distances, neighbours, distortion and exemplars: the rows go through the query placement
-//                      first
+//   placed_rows_query  Euclidean distances, neighbours, distortion, exemplars and range counts: the rows go through the
+//                      query placement first
 // A chunk of host rows goes up, its result is staged on the device and comes down behind the kernel; rows in HBM are
 // read where they are and the kernels write the caller's device arrays.  Both drivers synchronise before they return,
 // on error too (W_host and the rows are pageable), and end on drop_large_query_scratch.  The exported calls further
@@ -1869,7 +1872,7 @@ int dbgsom_ctx_bmu_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const in
 // ------------------------------------------------------------------------------------------
 namespace {
 
-enum QueryOp { Q_BMU, Q_DISTANCES, Q_KNEIGHBORS, Q_DISTORTION, Q_EXEMPLARS, Q_COMBINED };
+enum QueryOp { Q_BMU, Q_DISTANCES, Q_KNEIGHBORS, Q_DISTORTION, Q_EXEMPLARS, Q_COMBINED, Q_RANGE_COUNTS };
 enum RowsForm { ROWS_MASKED, ROWS_MANHATTAN, ROWS_COSINE };
 
 // DBGSOM_REQUIRE under the name of the exported call `fn` (checks shared by several of them)
@@ -1897,6 +1900,10 @@ int query_args(const char *fn, const dbgsom_ctx *c, QueryOp op, int x_dtype, boo
     REQUIRE_FN(fn, Nq >= 0 && Nq < 0x7fffffff && d >= 1 && d <= 0x7fffffff, "bad sample shape");
     REQUIRE_FN(fn, M >= 1 && M <= DBGSOM_MAX_PROTOTYPES, "need 1 <= M <= DBGSOM_MAX_PROTOTYPES");
     if (op == Q_DISTANCES || op == Q_DISTORTION) return DBGSOM_OK;
+    if (op == Q_RANGE_COUNTS) {   // (k counts thresholds)
+        REQUIRE_FN(fn, k >= 1 && k <= DBGSOM_MAX_RADII, "need 1 <= n_radii <= DBGSOM_MAX_RADII");
+        return DBGSOM_OK;
+    }
     if (op == Q_EXEMPLARS) REQUIRE_FN(fn, k >= 1, "need k >= 1");   // (k counts rows: it may exceed M, and Nq)
     else REQUIRE_FN(fn, k >= 1 && k <= M, "need 1 <= k <= M");
     REQUIRE_FN(fn, k <= DBGSOM_MAX_NEIGHBORS, "k must be <= DBGSOM_MAX_NEIGHBORS");
@@ -1929,6 +1936,7 @@ void drop_large_query_scratch(dbgsom_ctx *c) {
     if (c->ce_g.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->ce_g.release();
     if (c->ce_ws.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->ce_ws.release();
     if (c->ex_state.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->ex_state.release();
+    if (c->rc_state.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->rc_state.release();
 }
 
 // the end of both drivers
@@ -2145,18 +2153,25 @@ struct CsrHost {
 // Q_EXEMPLARS (csrc/exemplars.hip): every chunk folds into the state in ex_state with row0 the chunk's first row --
 // nothing per chunk is staged or copied down --, and after the last one the state is stored as the M x k result: into
 // kn_idx / kn_dist and down in one piece (M * k * 16 bytes), or into the caller's device arrays.
+// Q_RANGE_COUNTS (csrc/density.hip; k = the number of thresholds, thr_host): the thresholds go up once behind the
+// counts in rc_state, the counts are zeroed in front of the chunks and every chunk folds into them -- nothing per chunk
+// is staged or copied down --; after the last one they come down in one piece (M * k * 8 bytes) into idx_out, or are
+// copied into the caller's device array.
 // Q_COMBINED (csrc/geodesics.hip; k = 2): the geodesics of the map are queued once in front of the chunks (edges_host,
 // E); a chunk's all-pairs search leaves its pairs in idx (staged: kn_idx) and its distances in ce_ws, the rows kernel
 // reads both and G and writes e (one value per row; staged: kn_dist).  The status word is read after the last chunk.
 int placed_rows_query(dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHost *csr, int x_dtype, int64_t Nq, int64_t d,
                       const double *W_host, int64_t M, int k, int64_t *idx_out, double *dist_out, int64_t ldo,
-                      const double *H_host, int own_cell, const int32_t *edges_host = nullptr, int64_t E = 0) {
+                      const double *H_host, int own_cell, const int32_t *edges_host = nullptr, int64_t E = 0,
+                      const double *thr_host = nullptr) {
     Samples &s = c->xq;
     DevBuf Wq, wwq;
     const int64_t dp = pad16(d);
     const size_t es = dtype_size(x_dtype);
     const bool staged = !q.on_device, knn = op != Q_DISTANCES;   // (knn: a slab per chunk, k values per row and array)
     const bool cols = op == Q_EXEMPLARS;                         // (the result is M x k, after the last chunk)
+    const bool range = op == Q_RANGE_COUNTS;                     // (likewise: M x k counts)
+    const size_t rc_bytes = (size_t)M * k * 8;
     const int64_t chunk = staged ? distances_chunk(c, Nq, M, dp * (int64_t)es) : Nq;
     const bool comb = op == Q_COMBINED;
     const int64_t per_row = comb ? 1 : (knn ? k : M);   // values of a row's result (beside its k indices)
@@ -2179,6 +2194,14 @@ int placed_rows_query(dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHo
             if ((rc = queue_geodesics(c, Wq.as<double>(), M, d, dp, edges_host, E, (size_t)chunk * 16))) break;
             if (staged && (rc = c->kn_idx.reserve((size_t)chunk * 16))) break;
             if (staged && (rc = c->kn_dist.reserve((size_t)chunk * 8))) break;
+        } else if (range) {
+            if ((rc = c->kn_ws.reserve(range_counts_workspace_bytes(chunk, M, c->kneighbors_slab_rows)))) break;
+            if ((rc = c->rc_state.reserve(align_up(rc_bytes) + (size_t)k * 8))) break;
+            hipError_t e = hipMemcpyAsync(static_cast<char *>(c->rc_state.p) + align_up(rc_bytes), thr_host, (size_t)k * 8,
+                                          hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemsetAsync(c->rc_state.p, 0, rc_bytes, c->stream);
+            if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
+            c->x_up((size_t)k * 8);
         } else if (cols) {
             if ((rc = c->kn_ws.reserve(exemplars_fold_workspace_bytes(chunk, M, k, c->kneighbors_slab_rows)))) break;
             if ((rc = c->ex_state.reserve((size_t)M * k * 16))) break;
@@ -2208,6 +2231,13 @@ int placed_rows_query(dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHo
             if (rc) break;
             int64_t *idx = staged ? c->kn_idx.as<int64_t>() : idx_out;
             double *res = !staged ? dist_out : (knn ? c->kn_dist.as<double>() : c->pd_out.as<double>());
+            if (range) {
+                const double *thr = reinterpret_cast<const double *>(static_cast<char *>(c->rc_state.p) + align_up(rc_bytes));
+                rc = launch_range_counts_fold(s.Xb, s.bdtype, n, dp, dp, s.xx.as<double>(), Wq.as<double>(), M, wwq.as<double>(),
+                                              thr, k, c->kneighbors_slab_rows, c->rc_state.as<int64_t>(), c->kn_ws.p,
+                                              c->kn_ws.cap, c->stream);
+                continue;
+            }
             if (cols) {
                 rc = launch_exemplars_fold(s.Xb, s.bdtype, n, dp, dp, s.xx.as<double>(), Wq.as<double>(), M, wwq.as<double>(), k,
                                            own_cell, c->kneighbors_slab_rows, r0, c->ex_state.as<double>(),
@@ -2240,6 +2270,12 @@ int placed_rows_query(dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHo
             c->x_down(comb ? (size_t)n * 24 : (size_t)n * per_row * (knn ? 16 : 8));
         }
         if (rc == DBGSOM_OK && comb) rc = geodesics_status("dbgsom_ctx_combined_error_query", carve_geodesics(c, E).status, M, c->stream);
+        if (rc == DBGSOM_OK && range) {
+            const hipError_t e = hipMemcpyAsync(idx_out, c->rc_state.p, rc_bytes,
+                                                staged ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream);
+            if (e != hipSuccess) { set_error("copy of the counts failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; }
+            if (staged) c->x_down(rc_bytes);
+        }
         if (rc || !cols) break;
         int64_t *idx = staged ? c->kn_idx.as<int64_t>() : idx_out;
         double *res = staged ? c->kn_dist.as<double>() : dist_out;
@@ -2289,7 +2325,8 @@ int raw_rows_checked(const char *fn, dbgsom_ctx *c, QueryOp op, RowsForm form, c
 // CSR rows
 int placed_rows_checked(const char *fn, dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHost *csr, int x_dtype, int64_t Nq,
                         int64_t d, const double *W_host, int64_t M, int k, int64_t *idx_out, double *dist_out, int64_t ldo,
-                        const double *H_host = nullptr, int own_cell = 0, const int32_t *edges_host = nullptr, int64_t E = 0) {
+                        const double *H_host = nullptr, int own_cell = 0, const int32_t *edges_host = nullptr, int64_t E = 0,
+                        const double *thr_host = nullptr) {
     TRY(query_args(fn, c, op, x_dtype, csr != nullptr, Nq, d, M, k));
     if (op == Q_COMBINED) REQUIRE_FN(fn, E >= 0 && E <= 0x7fffffff, "need 0 <= E < 2^31");
     if (q.on_device) REQUIRE_FN(fn, q.ldx >= d, "ldx must be >= d");
@@ -2299,12 +2336,13 @@ int placed_rows_checked(const char *fn, dbgsom_ctx *c, QueryOp op, const QueryRo
         TRY(dbgsom_csr_check(csr->indptr, csr->indices, Nq, d, csr->nnz));
     }
     if (Nq == 0) return DBGSOM_OK;
-    REQUIRE_FN(fn, (csr || q.p) && W_host && (op == Q_DISTANCES || idx_out) && dist_out, "null pointer");
+    REQUIRE_FN(fn, (csr || q.p) && W_host && (op == Q_DISTANCES || idx_out) && (op == Q_RANGE_COUNTS || dist_out), "null pointer");
+    if (op == Q_RANGE_COUNTS) REQUIRE_FN(fn, thr_host, "null pointer");
     if (op == Q_DISTORTION) REQUIRE_FN(fn, H_host, "null pointer");
     if (op == Q_COMBINED) REQUIRE_FN(fn, E == 0 || edges_host, "null pointer");
     SET_DEVICE(c);
     return placed_rows_query(c, op, q, csr, x_dtype, Nq, d, W_host, M, k, idx_out, dist_out, ldo, H_host, own_cell, edges_host,
-                             E);
+                             E, thr_host);
 }
 
 }  // namespace
@@ -2422,6 +2460,31 @@ int dbgsom_ctx_exemplars_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, co
     const CsrHost csr{indptr_host, indices_host, nnz};
     return placed_rows_checked(__func__, c, Q_EXEMPLARS, QueryRows{data_host, false, d}, &csr, x_dtype, Nq, d, W_host, M, k,
                                idx_host, dist_host, 0, nullptr, own_cell);
+}
+
+// ------------------------------------------------------------------------------------------
+// the rows of a query within a radius of every prototype: csrc/density.hip (counts: M x n_radii; Nq == 0 writes nothing)
+// ------------------------------------------------------------------------------------------
+int dbgsom_ctx_range_counts_query(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d, const double *W_host,
+                                  int64_t M, const double *thr_host, int n_radii, int64_t *counts_host) {
+    return placed_rows_checked(__func__, c, Q_RANGE_COUNTS, QueryRows{Xq_host, false, d}, nullptr, x_dtype, Nq, d, W_host, M,
+                               n_radii, counts_host, nullptr, 0, nullptr, 0, nullptr, 0, thr_host);
+}
+
+int dbgsom_ctx_range_counts_query_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d, int64_t ldx,
+                                         const double *W_host, int64_t M, const double *thr_host, int n_radii,
+                                         int64_t *counts_dev) {
+    return placed_rows_checked(__func__, c, Q_RANGE_COUNTS, QueryRows{Xq_dev, true, ldx}, nullptr, x_dtype, Nq, d, W_host, M,
+                               n_radii, counts_dev, nullptr, 0, nullptr, 0, nullptr, 0, thr_host);
+}
+
+int dbgsom_ctx_range_counts_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const int32_t *indices_host,
+                                      const void *data_host, int x_dtype, int64_t Nq, int64_t d, int64_t nnz,
+                                      const double *W_host, int64_t M, const double *thr_host, int n_radii,
+                                      int64_t *counts_host) {
+    const CsrHost csr{indptr_host, indices_host, nnz};
+    return placed_rows_checked(__func__, c, Q_RANGE_COUNTS, QueryRows{data_host, false, d}, &csr, x_dtype, Nq, d, W_host, M,
+                               n_radii, counts_host, nullptr, 0, nullptr, 0, nullptr, 0, thr_host);
 }
 
 // ------------------------------------------------------------------------------------------

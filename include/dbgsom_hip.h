@@ -764,6 +764,49 @@ int dbgsom_ctx_exemplars_query_csr(dbgsom_ctx *ctx, const int64_t *indptr_host, 
                                    const double *W_host, int64_t M, int k, int own_cell, int64_t *idx_host,
                                    double *dist_host);
 
+/* ---- the rows within a radius of every prototype (csrc/density.hip) ------------------------------------------
+ * The all-pairs search read down its columns into integer counts: counts[j * n_radii + t] is the number of rows i
+ * with r_ij <= thr[t], r_ij = max((|x_i|^2 + (-2 <x_i, w_j>)) + |w_j|^2, 0) the squared value dbgsom_kneighbors
+ * selects on.  The thresholds are squared values, 1 <= n_radii <= DBGSOM_MAX_RADII of them, in any order, passed as
+ * given: a caller that means sqrt(r) <= rho passes the largest float64 t with sqrt(t) <= rho (dbgsom_amd.backend.
+ * squared_threshold), for which the two conditions are the same.  A pair whose r is NaN is never counted, and a
+ * NaN threshold counts nothing.  Integer adds commute: the counts do not depend on slabs, chunks or the order in
+ * which the wavefronts arrive.
+ *
+ * dbgsom_range_count_cols: the fold alone.  R holds N <= 2^31 - 1 rows of M squared values, ldr >= M apart; what
+ * lies in a row past M is never read.  counts_dev (M x n_radii int64) is ADDED to: the caller zeroes it.  N == 0
+ * returns DBGSOM_OK without a launch.
+ * dbgsom_range_counts: arguments as dbgsom_kneighbors with thr_dev / n_radii for k and counts_dev (M x n_radii
+ * int64) for the result: it zeroes the counts and runs that call's slab loop with the fold behind the squared
+ * product.  The workspace, dbgsom_range_counts_workspace_bytes(N, M, slab_rows) bytes, 16-byte aligned, is the
+ * slab.  N == 0 stores zeros.  Argument errors (n_radii out of range, ldr < M, slab_rows < 0, a null or misaligned
+ * pointer; a short workspace: DBGSOM_ENOMEM with both sizes in the message) are reported before anything touches
+ * the device. */
+#define DBGSOM_MAX_RADII 32
+int dbgsom_range_count_cols(const double *R_dev, int64_t N, int64_t M, int64_t ldr, const double *thr_dev, int n_radii,
+                            int64_t *counts_dev, void *stream);
+size_t dbgsom_range_counts_workspace_bytes(int64_t N, int64_t M, int64_t slab_rows);
+int dbgsom_range_counts(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx_dev,
+                        const double *W_dev, int64_t M, const double *ww_dev, const double *thr_dev, int n_radii,
+                        int64_t slab_rows, int64_t *counts_dev, void *workspace_dev, size_t workspace_bytes,
+                        void *stream);
+/* The same on a context, each call staging its rows as its dbgsom_ctx_exemplars_query* namesake does (chunks,
+ * query placement, CSR expanded chunk by chunk, the slab of "kneighbors_slab_rows" rows, status codes).  The
+ * thresholds (thr_host, n_radii float64) go up once and count as upload traffic; the counts live on the device for
+ * the length of the call and every chunk folds into them; nothing per chunk is staged or copied down.  M * n_radii
+ * * 8 bytes of result come down, once, per host-facing call.  _device: counts_dev is written on the device; nothing
+ * of X or of the result crosses PCIe.  Nq == 0 returns DBGSOM_OK and writes nothing. */
+int dbgsom_ctx_range_counts_query(dbgsom_ctx *ctx, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                                  const double *W_host, int64_t M, const double *thr_host, int n_radii,
+                                  int64_t *counts_host);
+int dbgsom_ctx_range_counts_query_device(dbgsom_ctx *ctx, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d,
+                                         int64_t ldx, const double *W_host, int64_t M, const double *thr_host,
+                                         int n_radii, int64_t *counts_dev);
+int dbgsom_ctx_range_counts_query_csr(dbgsom_ctx *ctx, const int64_t *indptr_host, const int32_t *indices_host,
+                                      const void *data_host, int x_dtype, int64_t Nq, int64_t d, int64_t nnz,
+                                      const double *W_host, int64_t M, const double *thr_host, int n_radii,
+                                      int64_t *counts_host);
+
 /* ---- weighted geodesics over the lattice and the combined error (csrc/geodesics.hip) -------------------------
  * The combined error of Kaski and Lagus (1996): e_i = d1_i + G[b1_i, b2_i], the distance of row i to its best
  * matching unit plus the length of the shortest path along the map from that unit to the second-best one, a
