@@ -266,6 +266,7 @@ int dbgsom_covariance_apply(const void *X_dev, int x_dtype, int64_t N, int64_t d
         set_error("dbgsom_covariance_apply: workspace too small (%zu bytes given, %zu needed)", workspace_bytes, need);
         return DBGSOM_ENOMEM;
     }
+    DBGSOM_REQUIRE(is_aligned(workspace_dev, 16), "workspace_dev must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     if (N == 0) {
         DBGSOM_HIP_CHECK(hipMemsetAsync(Z_dev, 0, (size_t)d * p * sizeof(double), s));

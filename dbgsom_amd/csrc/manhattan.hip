@@ -166,6 +166,7 @@ int dbgsom_bmu_manhattan(const void *X_dev, int x_dtype, int64_t N, int64_t d, i
     if (N == 0) return DBGSOM_OK;
     DBGSOM_REQUIRE(X_dev && W_dev && idx_dev && dist_dev && workspace_dev, "null pointer");
     TRY_STATUS(workspace_check("dbgsom_bmu_manhattan", workspace_bytes, bmu_manhattan_workspace_bytes(x_dtype, N, d, M)));
+    DBGSOM_REQUIRE(is_aligned(workspace_dev, 16), "workspace_dev must be 16-byte aligned");
     TRY_STATUS(launch_manhattan_weights(W_dev, M, d, ldw, workspace_dev, (hipStream_t)stream));
     return launch_bmu_manhattan_rows(X_dev, x_dtype, N, d, ldx, M, k, idx_dev, dist_dev, workspace_dev, workspace_bytes,
                                      (hipStream_t)stream);
@@ -181,6 +182,7 @@ int dbgsom_distances_manhattan(const void *X_dev, int x_dtype, int64_t N, int64_
     DBGSOM_REQUIRE(is_aligned(out_dev, 8), "out_dev must be 8-byte aligned");
     TRY_STATUS(workspace_check("dbgsom_distances_manhattan", workspace_bytes,
                                bmu_manhattan_workspace_bytes(x_dtype, N, d, M)));
+    DBGSOM_REQUIRE(is_aligned(workspace_dev, 16), "workspace_dev must be 16-byte aligned");
     TRY_STATUS(launch_manhattan_weights(W_dev, M, d, ldw, workspace_dev, (hipStream_t)stream));
     return launch_distances_manhattan_rows(X_dev, x_dtype, N, d, ldx, M, out_dev, ldo, workspace_dev, workspace_bytes,
                                            (hipStream_t)stream);

@@ -249,6 +249,7 @@ int dbgsom_bmu_masked(const void *X_dev, int x_dtype, int64_t N, int64_t d, int6
     if (N == 0) return DBGSOM_OK;
     DBGSOM_REQUIRE(X_dev && W_dev && idx_dev && dist_dev && workspace_dev, "null pointer");
     TRY_STATUS(workspace_check("dbgsom_bmu_masked", workspace_bytes, bmu_masked_workspace_bytes(x_dtype, N, d, M)));
+    DBGSOM_REQUIRE(is_aligned(workspace_dev, 16), "workspace_dev must be 16-byte aligned");
     TRY_STATUS(launch_masked_weights(W_dev, M, d, ldw, workspace_dev, (hipStream_t)stream));
     return launch_bmu_masked_rows(X_dev, x_dtype, N, d, ldx, M, k, idx_dev, dist_dev, workspace_dev, workspace_bytes,
                                   (hipStream_t)stream);
@@ -262,6 +263,7 @@ int dbgsom_distances_masked(const void *X_dev, int x_dtype, int64_t N, int64_t d
     if (N == 0) return DBGSOM_OK;
     DBGSOM_REQUIRE(X_dev && W_dev && out_dev && workspace_dev, "null pointer");
     TRY_STATUS(workspace_check("dbgsom_distances_masked", workspace_bytes, bmu_masked_workspace_bytes(x_dtype, N, d, M)));
+    DBGSOM_REQUIRE(is_aligned(workspace_dev, 16), "workspace_dev must be 16-byte aligned");
     TRY_STATUS(launch_masked_weights(W_dev, M, d, ldw, workspace_dev, (hipStream_t)stream));
     return launch_distances_masked_rows(X_dev, x_dtype, N, d, ldx, M, out_dev, ldo, workspace_dev, workspace_bytes,
                                         (hipStream_t)stream);

@@ -631,6 +631,7 @@ int dbgsom_sparse_code(const void *Xq, int x_dtype, int64_t Nq, int64_t d, int64
     DBGSOM_REQUIRE(!proba || (P && C >= 1 && C <= 0x7fffffff), "proba needs P and C >= 1");
     DBGSOM_REQUIRE(ws || ws_bytes == 0, "null workspace");
     DBGSOM_REQUIRE(ws_bytes >= dbgsom_sparse_code_workspace_bytes(Nq, d, M, max_iter), "workspace too small");
+    DBGSOM_REQUIRE(is_aligned(ws, 256), "workspace must be 256-byte aligned");
     if (Nq == 0) return DBGSOM_OK;
     ScWs w;
     carve_ws(&w, static_cast<char *>(ws), Nq, d, M, max_iter);

@@ -295,6 +295,7 @@ int dbgsom_sum_f64(const double *v_dev, int64_t n, double *out_dev, void *worksp
         set_error("dbgsom_sum_f64: workspace too small");
         return DBGSOM_ENOMEM;
     }
+    DBGSOM_REQUIRE(is_aligned(workspace_dev, 16), "workspace_dev must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     double *part = (double *)workspace_dev;
     hipLaunchKernelGGL(sum_partial_kernel, dim3(RB), dim3(256), 0, s, v_dev, n, part);
@@ -378,6 +379,7 @@ int dbgsom_weighted_sum_f64(const double *v_dev, const double *w_dev, int64_t n,
         set_error("dbgsom_weighted_sum_f64: workspace too small");
         return DBGSOM_ENOMEM;
     }
+    DBGSOM_REQUIRE(is_aligned(workspace_dev, 16), "workspace_dev must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     double *part = (double *)workspace_dev;
     hipLaunchKernelGGL(wsum_partial_kernel, dim3(RB), dim3(256), 0, s, v_dev, w_dev, n, part);
@@ -393,6 +395,7 @@ int dbgsom_topographic_weight(const int64_t *idx2_dev, const double *w_dev, int6
         set_error("dbgsom_topographic_weight: workspace too small");
         return DBGSOM_ENOMEM;
     }
+    DBGSOM_REQUIRE(is_aligned(workspace_dev, 16), "workspace_dev must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     double *part = (double *)workspace_dev;
     hipLaunchKernelGGL(topographic_w_kernel, dim3(RB), dim3(256), 0, s, idx2_dev, w_dev, n, xy_dev, (int)M, part);
@@ -425,6 +428,7 @@ int dbgsom_weighted_column_sums(const void *X_dev, int x_dtype, int64_t N, int64
         set_error("dbgsom_weighted_column_sums: workspace too small");
         return DBGSOM_ENOMEM;
     }
+    DBGSOM_REQUIRE(is_aligned(workspace_dev, 16), "workspace_dev must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     double *part = (double *)workspace_dev;
     const dim3 grid((unsigned)((d + WC_COLS - 1) / WC_COLS), WC_RB / WC_RL), block(WC_COLS * WC_RL);

@@ -16,6 +16,13 @@
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream).  Device-level
  *     calls only ENQUEUE work on `stream`; the caller synchronises.  Context-level calls
  *     (dbgsom_ctx_*) are blocking.
+ *   - workspaces: a `workspace_dev` / `ws` argument is device scratch of at least the bytes the `dbgsom_*_workspace_bytes`
+ *     function declared beside its entry returns for the same shape (exactly that many is enough).  Each entry states
+ *     its alignment (16 or 256 bytes).  Unless the entry says otherwise -- dbgsom_bmu_filtered and the calls that share
+ *     its workspace are the one exception -- the contents on entry are irrelevant: a buffer may go from call to call,
+ *     from shape to shape and from entry to entry without being cleared.  Nothing outside [ptr, ptr + bytes) is ever
+ *     written.  A short workspace (DBGSOM_ENOMEM; dbgsom_sparse_code: DBGSOM_EINVAL) and a misaligned one
+ *     (DBGSOM_EINVAL) are refused before anything is launched.
  *   - matrices are row-major; `ld*` is the row stride in ELEMENTS.
  *   - handles are not thread-safe; calls are blocking from one host thread per context.
  */
@@ -125,7 +132,9 @@ int dbgsom_exp_similarity(const double *dist_dev, int64_t N, double gamma, doubl
  * sums_dev holds M*(d+3) float64:  [ S (M*d) | K (M) | a (M) | E (M) ]  -- the buffer a
  * sample-sharded multi-GPU run all-reduces (one collective per epoch).
  * status_dev (int32[1], may be NULL) is set non-zero when a winner is outside [0,M) (that
- * sample is skipped). */
+ * sample is skipped).
+ * Workspace: 256-byte aligned, contents on entry irrelevant, nothing outside [workspace_dev, workspace_dev +
+ * workspace_bytes) is written. */
 size_t dbgsom_accumulate_workspace_bytes(int64_t N, int64_t d, int64_t M);
 int dbgsom_accumulate(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx,
                       const int64_t *idx_dev, const double *kw_dev, const double *dist_dev,
@@ -138,7 +147,9 @@ int dbgsom_accumulate(const void *X_dev, int x_dtype, int64_t N, int64_t d, int6
  * a_j is an ordered float64 sum like K_j and E_j (list order, chunk order, group order: bitwise
  * reproducible, independent of the grid); rows of weight 0 are not streamed and contribute to nothing.
  * The first N int32 of the workspace hold the sample ids bucketed by winner as after dbgsom_accumulate
- * (rows of weight 0 included: the sort does not look at weights, the sums skip those rows). */
+ * (rows of weight 0 included: the sort does not look at weights, the sums skip those rows).
+ * Workspace: 256-byte aligned, contents on entry irrelevant, nothing outside [workspace_dev, workspace_dev +
+ * workspace_bytes) is written. */
 size_t dbgsom_accumulate_weighted_workspace_bytes(int64_t N, int64_t d, int64_t M);
 int dbgsom_accumulate_weighted(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx,
                                const int64_t *idx_dev, const double *kw_dev, const double *sw_dev,
@@ -164,7 +175,9 @@ int dbgsom_accumulate_weighted(const void *X_dev, int x_dtype, int64_t N, int64_
  *   is that of the weighted call for both forms.  Bit-identical to the dense call wherever that one adds a column
  *   in list order, which is from 256 pieces per row on: 16-byte pieces when X_dev and ldx are 16-byte aligned and
  *   d is a multiple of the piece (d >= 1024 for float32, >= 512 for float64, as with the context's padded rows),
- *   single elements otherwise (any d >= 256); narrower dense rows are summed over row lanes, in another order. */
+ *   single elements otherwise (any d >= 256); narrower dense rows are summed over row lanes, in another order.
+ *   Workspace: 256-byte aligned, contents on entry irrelevant, nothing outside [workspace_dev, workspace_dev +
+ * workspace_bytes) is written. */
 int dbgsom_csr_check(const int64_t *indptr_host, const int32_t *indices_host, int64_t N, int64_t d, int64_t nnz);
 int dbgsom_csr_row_sqnorms(const int64_t *indptr_dev, const void *data_dev, int x_dtype, int64_t N, double *out_dev,
                            void *stream);
@@ -187,7 +200,9 @@ int dbgsom_accumulate_csr(const int64_t *indptr_dev, const int32_t *indices_dev,
  *   c_j = S_j / K_j placed per `layout`;  h = exp(-(hop^2 / (2 sigma^2)));
  *   W'_i = sum_j h_ij a_j c_j / sum_j h_ij a_j;   change_total = sum_i |W_i - W'_i|_2.
  * hop: M x M float32 lattice hop counts (+inf when disconnected).  W_new may not alias W_old.
- * change_total_dev: one float64 on the device. */
+ * change_total_dev: one float64 on the device.
+ * Workspace: 256-byte aligned, contents on entry irrelevant, nothing outside [workspace_dev, workspace_dev +
+ * workspace_bytes) is written. */
 size_t dbgsom_smooth_workspace_bytes(int64_t M, int64_t d);
 int dbgsom_smooth(const double *sums_dev, int64_t M, int64_t d, const float *hop_dev,
                   double sigma, int layout, const double *W_old_dev, double *W_new_dev,
@@ -222,7 +237,9 @@ size_t dbgsom_filter_planes_bytes(int64_t rows, int64_t d);
 int dbgsom_filter_prepare(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx,
                           void *planes_dev, size_t planes_bytes, void *stream);
 /* The workspace of dbgsom_bmu_filtered must be zero-filled ONCE after it is allocated (its first 256
- * bytes hold self-resetting "last workgroup" tickets); calls leave it ready for the next call. */
+ * bytes hold self-resetting "last workgroup" tickets); calls leave it ready for the next call.  This is the one
+ * workspace whose contents on entry matter; dbgsom_bmu_filtered_anchored and dbgsom_bmu_filtered_anchor_runs share
+ * it.  256-byte aligned; nothing outside [workspace_dev, workspace_dev + workspace_bytes) is written. */
 size_t dbgsom_bmu_filtered_workspace_bytes(int64_t N, int64_t d, int64_t M);
 int dbgsom_bmu_filtered(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx,
                         const double *xx_dev, const void *xplanes_dev, const double *W_dev,
@@ -315,7 +332,9 @@ int dbgsom_bmu_filtered_refine_counts(const void *workspace_dev, int64_t N, int6
 /* ---- post-fit consumers of the BMU step as device reductions (N-sized arrays stay in HBM) ---- */
 
 /* out[0] = sum of v[0..n) with a fixed reduction tree (bitwise reproducible).  Mean BMU distance =
- * BaseSom.calculate_quantization_error  BaseSom.py:904-922. */
+ * BaseSom.calculate_quantization_error  BaseSom.py:904-922.
+ * Workspace: 16-byte aligned, contents on entry irrelevant, nothing outside [workspace_dev, workspace_dev +
+ * workspace_bytes) is written. */
 size_t dbgsom_sum_workspace_bytes(void);
 int dbgsom_sum_f64(const double *v_dev, int64_t n, double *out_dev, void *workspace_dev,
                    size_t workspace_bytes, void *stream);
@@ -349,7 +368,9 @@ int dbgsom_density_terms(const double *dist_dev, int64_t n, double sigma, double
  *       order_dev = the N sample ids bucketed by winner (stable), seg_start_dev = the M + 1 exclusive list starts
  *       (seg_start[M] = N); added in list order
  *   dbgsom_weighted_column_sums  out[j] = sum_i w_i x_ij (mean_dev == NULL) or sum_i w_i (x_ij - mean_j)^2, in
- *       float64 whatever the storage dtype (mean_dev, out_dev: d float64) */
+ *       float64 whatever the storage dtype (mean_dev, out_dev: d float64)
+ * Workspaces (dbgsom_sum_workspace_bytes for the two sums, dbgsom_weighted_column_sums_workspace_bytes): 16-byte
+ * aligned, contents on entry irrelevant, nothing outside [workspace_dev, workspace_dev + workspace_bytes) is written. */
 int dbgsom_weighted_sum_f64(const double *v_dev, const double *w_dev, int64_t n, double *out_dev,
                             void *workspace_dev, size_t workspace_bytes, void *stream);
 int dbgsom_topographic_weight(const int64_t *idx2_dev, const double *w_dev, int64_t n, const int32_t *xy_dev,
@@ -572,7 +593,9 @@ int dbgsom_ctx_bmu_query_csr(dbgsom_ctx *ctx, const int64_t *indptr_host, const 
  *   X: N x d, DBGSOM_F32 or DBGSOM_F64 (DBGSOM_BF16 is DBGSOM_EINVAL), ldx <= 2^27; W: M x d float64.
  *   A row without any observed entry gets dist = NaN (the context call refuses such rows beforehand).
  * dbgsom_fill_missing writes (x_dtype) W[idx[i * idx_stride]][c] into every NaN position (i, c) of X and
- * leaves everything else as it is (rows whose index is outside [0, M) too). */
+ * leaves everything else as it is (rows whose index is outside [0, M) too).
+ * Workspace: 16-byte aligned, contents on entry irrelevant, nothing outside [workspace_dev, workspace_dev +
+ * workspace_bytes) is written. */
 size_t dbgsom_bmu_masked_workspace_bytes(int x_dtype, int64_t N, int64_t d, int64_t M);
 int dbgsom_bmu_masked(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx,
                       const double *W_dev, int64_t M, int64_t ldw, int k, int64_t *idx_dev,
@@ -647,7 +670,9 @@ int dbgsom_ctx_distances_query_masked(dbgsom_ctx *ctx, const void *Xq_host, int 
  * Nothing grows with N x M: dbgsom_kneighbors_workspace_bytes(N, M, slab_rows) is one slab.  The workspace
  * must be 16-byte aligned.
  * dbgsom_kneighbors_masked: rows with missing entries (NaN), arguments as dbgsom_distances_masked; the workspace
- * is that of dbgsom_kneighbors_masked_workspace_bytes (the masked search's for one slab of rows, then the slab). */
+ * is that of dbgsom_kneighbors_masked_workspace_bytes (the masked search's for one slab of rows, then the slab).
+ * Both workspaces: 16-byte aligned, contents on entry irrelevant, nothing outside [workspace_dev, workspace_dev +
+ * workspace_bytes) is written. */
 int dbgsom_topk_rows(const double *R_dev, int64_t N, int64_t M, int64_t ldr, int k, int64_t *idx_dev,
                      double *dist_dev, void *stream);
 size_t dbgsom_kneighbors_workspace_bytes(int64_t N, int64_t M, int64_t slab_rows);
@@ -737,7 +762,8 @@ int dbgsom_ctx_distortion_query_csr(dbgsom_ctx *ctx, const int64_t *indptr_host,
  * and stores (sqrt(r), i).  The workspace, dbgsom_exemplars_workspace_bytes(N, M, k, slab_rows) bytes, 16-byte
  * aligned, covers the slab, the units of one slab, the fold's scratch and the state.  N == 0 stores (inf, -1).
  * Argument errors (k out of range, ldr < M, slab_rows < 0, row0 + N too large, a null or misaligned pointer; a
- * short workspace: DBGSOM_ENOMEM with both sizes in the message) are reported before any launch. */
+ * short workspace: DBGSOM_ENOMEM with both sizes in the message) are reported before any launch.  Both workspaces:
+ * contents on entry irrelevant, nothing outside [workspace_dev, workspace_dev + workspace_bytes) is written. */
 size_t dbgsom_topk_cols_workspace_bytes(int64_t N, int64_t M, int k);
 int dbgsom_topk_cols_init(double *state_r_dev, int64_t *state_i_dev, int64_t M, int k, void *stream);
 int dbgsom_topk_cols(const double *R_dev, int64_t N, int64_t M, int64_t ldr, const int64_t *owner_dev, int64_t row0,
@@ -781,7 +807,8 @@ int dbgsom_ctx_exemplars_query_csr(dbgsom_ctx *ctx, const int64_t *indptr_host, 
  * product.  The workspace, dbgsom_range_counts_workspace_bytes(N, M, slab_rows) bytes, 16-byte aligned, is the
  * slab.  N == 0 stores zeros.  Argument errors (n_radii out of range, ldr < M, slab_rows < 0, a null or misaligned
  * pointer; a short workspace: DBGSOM_ENOMEM with both sizes in the message) are reported before anything touches
- * the device. */
+ * the device.  Workspace contents on entry are irrelevant; nothing outside [workspace_dev, workspace_dev +
+ * workspace_bytes) is written. */
 #define DBGSOM_MAX_RADII 32
 int dbgsom_range_count_cols(const double *R_dev, int64_t N, int64_t M, int64_t ldr, const double *thr_dev, int n_radii,
                             int64_t *counts_dev, void *stream);
@@ -833,8 +860,8 @@ int dbgsom_ctx_range_counts_query_csr(dbgsom_ctx *ctx, const int64_t *indptr_hos
  * edges are harmless, degree is not bounded, +inf is a legal length and connects nothing.  An edge or source index
  * outside [0, M) is DBGSOM_ERANGE (nothing is read or written through it), a length that is NaN or negative is
  * DBGSOM_EINVAL; the result is then unspecified.  The workspace holds dbgsom_geodesics_workspace_bytes(M, E) bytes
- * (0 for a bad M or E), 256-byte aligned; what it holds on entry does not matter.  Blocking: the status word is
- * read back.
+ * (0 for a bad M or E), 256-byte aligned; what it holds on entry does not matter, and nothing outside
+ * [workspace_dev, workspace_dev + workspace_bytes) is written.  Blocking: the status word is read back.
  * dbgsom_combined_error_rows: idx2 holds N pairs (b1, b2) of int64, dist N rows ldd >= 1 apart whose first
  * value is d1.  An index outside [0, M) other than -1 reads nothing, leaves NaN and is DBGSOM_ERANGE.  Blocking.
  * Argument errors (null pointers, M < 1 or M > DBGSOM_MAX_PROTOTYPES, E < 0, ldg < M, a short workspace:
@@ -890,7 +917,9 @@ int dbgsom_ctx_combined_error_query_csr(dbgsom_ctx *ctx, const int64_t *indptr_h
  *   exact integers.  Only the first d columns of a row are data (whatever sits between d and ldx is never
  *   added).  X: DBGSOM_F32 or DBGSOM_F64 (DBGSOM_BF16 is DBGSOM_EINVAL), any ldx >= d, any alignment of its
  *   element type (16-byte aligned rows take the vector loads).  A winner outside [0, M) sets *status_dev (may
- *   be NULL) to 1 and its row is skipped, as in dbgsom_accumulate.  Workspace 256-byte aligned.
+ *   be NULL) to 1 and its row is skipped, as in dbgsom_accumulate.
+ * Both workspaces (dbgsom_accumulate_masked, dbgsom_smooth_masked): 256-byte aligned, contents on entry irrelevant,
+ * nothing outside [workspace_dev, workspace_dev + workspace_bytes) is written.
  * dbgsom_smooth_masked is steps 3-5 on such sums: hop_dev M x M float32, W_old / W_new M x d float64 (no
  * padding; W_new must not alias W_old), change_total_dev one float64. */
 size_t dbgsom_accumulate_masked_workspace_bytes(int64_t N, int64_t d, int64_t M);
@@ -932,7 +961,8 @@ int dbgsom_ctx_epoch_masked(dbgsom_ctx *ctx, const double *W_host, int64_t M, do
  * Device level: the arguments of the _masked namesakes above (X DBGSOM_F32 / DBGSOM_F64 with ldx >= d, W
  * float64 with ldw >= d; k in {1, 2} for the search, 1 <= k <= DBGSOM_MAX_NEIGHBORS for the selection, which
  * stores the distance it selected on).  Workspace: dbgsom_bmu_manhattan_workspace_bytes (search and matrix),
- * dbgsom_kneighbors_manhattan_workspace_bytes (16-byte aligned); a short one is DBGSOM_ENOMEM. */
+ * dbgsom_kneighbors_manhattan_workspace_bytes; both 16-byte aligned, contents on entry irrelevant, nothing outside
+ * [workspace_dev, workspace_dev + workspace_bytes) is written; a short one is DBGSOM_ENOMEM. */
 size_t dbgsom_bmu_manhattan_workspace_bytes(int x_dtype, int64_t N, int64_t d, int64_t M);
 int dbgsom_bmu_manhattan(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *W_dev,
                          int64_t M, int64_t ldw, int k, int64_t *idx_dev, double *dist_dev, void *workspace_dev,
@@ -992,7 +1022,8 @@ int dbgsom_ctx_kneighbors_query_manhattan_device(dbgsom_ctx *ctx, const void *Xq
  * Device level: the arguments of the Euclidean namesakes with u_dev for xx_dev, v_dev for ww_dev and without
  * round_f32; X DBGSOM_F32 / DBGSOM_F64 (DBGSOM_BF16: DBGSOM_EINVAL).  dbgsom_inv_norms: out[i] = inv(sq[i]) for n
  * values (both 8-byte aligned; in place is not supported).  dbgsom_kneighbors_cosine stores the distance it selected
- * on; its workspace is that of dbgsom_kneighbors (16-byte aligned; a short one is DBGSOM_ENOMEM). */
+ * on; its workspace is that of dbgsom_kneighbors (16-byte aligned, contents on entry irrelevant, nothing outside
+ * [workspace_dev, workspace_dev + workspace_bytes) is written; a short one is DBGSOM_ENOMEM). */
 int dbgsom_inv_norms(const double *sq_dev, int64_t n, double *out_dev, void *stream);
 int dbgsom_bmu_cosine(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *u_dev,
                       const double *W_dev, int64_t M, const double *v_dev, int k, int64_t *idx_dev,
@@ -1054,7 +1085,10 @@ int dbgsom_ctx_kneighbors_query_cosine_device(dbgsom_ctx *ctx, const void *Xq_de
  *         [rows, LARS iterations, max iterations of a row, drops, degenerate regressors skipped,
  *          lasso early stops (alpha grew), non-finite AA retries, rows of the overflow pass,
  *          largest active set, steps that dropped more than one prototype at once, G rows read
- *          by corr_eq_dir (sum over the iterations of the active-set size)] */
+ *          by corr_eq_dir (sum over the iterations of the active-set size)]
+ *   workspace 256-byte aligned, contents on entry irrelevant (the call clears the four list counters it reads),
+ *         nothing outside [workspace_dev, workspace_dev + workspace_bytes) is written; a short or misaligned one is
+ *         DBGSOM_EINVAL before anything is launched */
 #define DBGSOM_SC_COUNTS 11
 size_t dbgsom_sparse_code_workspace_bytes(int64_t Nq, int64_t d, int64_t M, int max_iter);
 int dbgsom_sparse_code(const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d, int64_t ldx,
@@ -1098,7 +1132,7 @@ int dbgsom_ctx_sparse_code_device(dbgsom_ctx *ctx, const void *Xq_dev, int x_dty
  * idx2: n x 2 int64 BMU pairs (device); xy: M x 2 int32 lattice coordinates (device), no two alike.
  * M <= DBGSOM_MAX_PROTOTYPES.  ws: dbgsom_topofn_workspace_bytes(M, full) bytes on the device, 256-byte
  * aligned (a misaligned one is DBGSOM_EINVAL, a short one DBGSOM_ENOMEM; both before any launch); its
- * contents on entry do not matter.  The call is blocking (it reads back the kernels' status word):
+ * contents on entry do not matter, and nothing outside [ws, ws + ws_bytes) is written.  The call is blocking (it reads back the kernels' status word):
  * DBGSOM_ERANGE when an index is outside [0, M), DBGSOM_EINVAL when an edge spans >= n_pos or two
  * neurons share coordinates. */
 size_t dbgsom_topofn_workspace_bytes(int64_t M, int full);
@@ -1180,7 +1214,8 @@ int dbgsom_ctx_class_histogram(dbgsom_ctx *ctx, const int64_t *idx_host, int64_t
  * 1 <= p <= DBGSOM_MAX_DIRECTIONS; colsum: d float64.  d <= 2^30.  Float64 throughout, no atomics: the result is the
  * same bits for the same (N, d, p) and values, whatever ldx, the alignment of the base, or the run.  A NaN or an
  * infinity in a row goes into Z.  Argument errors are DBGSOM_EINVAL, a short workspace DBGSOM_ENOMEM, both before any
- * launch; N == 0 gives zeros. */
+ * launch; N == 0 gives zeros.  Workspace: 16-byte aligned, contents on entry irrelevant, nothing outside
+ * [workspace_dev, workspace_dev + workspace_bytes) is written. */
 size_t dbgsom_covariance_apply_workspace_bytes(int64_t N, int64_t d, int p);
 int dbgsom_covariance_apply(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *mean_dev,
                             const double *V_dev, int p, double *Z_dev, double *colsum_dev, void *workspace_dev,

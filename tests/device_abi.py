@@ -77,6 +77,56 @@ def workspace(nbytes):
     return t, (t.data_ptr() + 255) // 256 * 256
 
 
+GUARD_FRONT, GUARD_BACK = 256, 4096      # least guard bytes in front of and behind a guarded workspace's body
+GUARD_BYTE = 0xA5                         # what the guards hold: neither of the body fills below
+BODY_FILL = {"zero": 0x00, "ff": 0xFF}    # "ff": every float reads NaN, every integer -1 or UINT_MAX
+
+
+def guards_intact(image, body_off, nbytes, guard=GUARD_BYTE):
+    """-> (front intact, back intact) of the host image (uint8) of a guarded allocation whose body is
+    image[body_off : body_off + nbytes]: every byte outside the body still holds `guard`"""
+    image = np.asarray(image, dtype=np.uint8)
+    assert 0 <= body_off and body_off + nbytes <= image.size
+    return bool((image[:body_off] == guard).all()), bool((image[body_off + nbytes:] == guard).all())
+
+
+class GuardedWorkspace:
+    """[front guard >= GUARD_FRONT bytes | body of exactly `nbytes` bytes, 256-byte aligned | back guard >=
+    GUARD_BACK bytes] on the device.  The guards hold GUARD_BYTE, the body whatever `fill` / `reguard` left there; an
+    entry is called with (ptr, a size <= nbytes) and `guards_intact` then tells, on the host, whether it wrote in
+    front of or behind what it was given.
+
+    What this cannot see: a stray READ past the end (the guards are ordinary, readable memory, and a kernel that reads
+    them and throws the value away leaves no trace), a write past the back guard's 4096 bytes, and a write of a byte
+    that happens to equal GUARD_BYTE."""
+
+    def __init__(self, nbytes):
+        import torch
+
+        self.nbytes = int(nbytes)
+        self.t = torch.full((GUARD_FRONT + 256 + self.nbytes + GUARD_BACK,), GUARD_BYTE, dtype=torch.uint8, device="cuda")
+        self.off = GUARD_FRONT + (-(self.t.data_ptr() + GUARD_FRONT)) % 256
+        self.ptr = self.t.data_ptr() + self.off
+        assert self.ptr % 256 == 0 and self.off >= GUARD_FRONT
+
+    def fill(self, kind):
+        """the whole body to one of BODY_FILL"""
+        self.t[self.off:self.off + self.nbytes] = BODY_FILL[kind]
+
+    def reguard(self, used):
+        """an entry is about to be given the first `used` bytes only: what lies behind them becomes guard (the first
+        `used` bytes keep what they hold)"""
+        assert 0 <= used <= self.nbytes
+        self.t[self.off + used:] = GUARD_BYTE
+
+    def intact(self, used=None):
+        """-> (front intact, back intact) around the first `used` bytes (default: the whole body)"""
+        import torch
+
+        torch.cuda.synchronize()
+        return guards_intact(self.t.cpu().numpy(), self.off, self.nbytes if used is None else used)
+
+
 def dev(a):
     import torch
 

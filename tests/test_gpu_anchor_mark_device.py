@@ -89,6 +89,7 @@ def run_case(nat, o, X, W, storage, A=256, flags=PRUNE, buckets=None):
     ranchor, rR, rxx = np.full(cap, -7, dtype=np.int32), np.full(cap, np.nan), np.full(cap, np.nan)
     nat.call("dbgsom_anchor_runs_read", rptr, N, A, start.ctypes.data, ranchor.ctypes.data, rR.ctypes.data, rxx.ctypes.data,
              da.stream())
+    assert (tfd._bytes_at(rt, rptr, rbytes + 256)[rbytes:] == 0x7f).all(), "dbgsom_anchor_runs_build wrote behind its table"
     wbytes = tfd._workspace_bytes(nat, N, dp, M)
     ws_t, ws = da.workspace(wbytes)
     idx, dist = tfd._full((N,), -7, "int64"), tfd._full((N,), float("nan"), "float64")
