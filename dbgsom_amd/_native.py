@@ -34,6 +34,7 @@ MAX_PROTOTYPES = 16000
 MAX_NEIGHBORS = 32      # DBGSOM_MAX_NEIGHBORS
 MAX_DIRECTIONS = 8      # DBGSOM_MAX_DIRECTIONS
 MAX_RADII = 32          # DBGSOM_MAX_RADII
+MAX_MIXTURE_VALUES = 16   # DBGSOM_MAX_MIXTURE_VALUES
 # counters of dbgsom_sparse_code / dbgsom_ctx_sparse_code (DBGSOM_SC_COUNTS, in this order)
 SC_COUNTS = ("samples", "iterations", "max_iterations", "drops", "degenerate", "early_stops", "aa_retries",
              "overflow", "max_active", "multi_drops", "g_rows")
@@ -179,6 +180,13 @@ SIGNATURES = {
     "dbgsom_ctx_range_counts_query": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _vp, _ci, _vp]),
     "dbgsom_ctx_range_counts_query_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _vp, _ci, _vp]),
     "dbgsom_ctx_range_counts_query_csr": (_ci, [_vp, _vp, _vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _vp, _ci, _vp]),
+    "dbgsom_mixture_rows": (_ci, [_vp, _i64, _i64, _i64, _vp, _dbl, _vp, _ci, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "dbgsom_mixture": (_ci, [_vp, _ci, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _dbl, _vp, _ci, _i64, _i64, _vp, _vp, _vp,
+                             _i64, _vp, _sz, _vp]),
+    "dbgsom_ctx_mixture_query": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _vp, _dbl, _vp, _ci, _vp, _vp, _vp]),
+    "dbgsom_ctx_mixture_query_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _vp, _dbl, _vp, _ci, _vp, _vp, _vp]),
+    "dbgsom_ctx_mixture_query_csr": (_ci, [_vp, _vp, _vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _vp, _dbl, _vp, _ci, _vp, _vp,
+                                           _vp]),
     "dbgsom_edge_lengths": (_ci, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
     "dbgsom_geodesics_workspace_bytes": (_sz, [_i64, _i64]),
     "dbgsom_geodesics": (_ci, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _sz, _vp]),

@@ -92,6 +92,69 @@ def squared_thresholds(radii) -> np.ndarray:
     return np.array([squared_threshold(r) for r in np.asarray(radii, dtype=np.float64).reshape(-1)], dtype=np.float64)
 
 
+def _lane_sums(A) -> np.ndarray:
+    """The row sums of A (rows x M float64) in the fixed order of the rows kernels (include/dbgsom_hip.h): lane l of 64
+    adds its entries j = l, l + 64, ... ascending from +0.0, then six rounds m = 1 .. 32 in which every lane takes
+    ``p_l + p_(l ^ m)``.  (A partial that starts at +0.0 is never -0.0, so the zeros that pad the last group of 64 change
+    no bit.)"""
+    n, M = A.shape
+    G = -(-M // 64)
+    P = np.zeros((n, G * 64))
+    P[:, :M] = A
+    P = P.reshape(n, G, 64)
+    p = np.zeros((n, 64))
+    for g in range(G):
+        p = p + P[:, g]
+    lanes = np.arange(64)
+    for m in (1, 2, 4, 8, 16, 32):
+        p = p + p[:, lanes ^ m]
+    return p[:, 0]
+
+
+def mixture_rows_host(R, log_prior, c, Y=None):
+    """The arithmetic of csrc/mixture.hip in NumPy on a matrix R (rows x M float64) of squared values -> (unit, lse, q):
+    ``t_j = a_j - (c * r_j)``, two roundings; ``(T, b)`` the largest t_j, lowest j among equals, over ``t_j > -inf`` and
+    not NaN; ``s_j = exp(t_j - T)``; ``S = sum_j s_j`` and ``Q_v = sum_j (s_j * Y[j, v])`` in the order of ``_lane_sums``;
+    ``lse = T + log(S)``, ``q_v = Q_v / S``.  A NaN t_j enters the sums as it is; a row without any t_j above -inf has
+    ``(-1, NaN, NaN)``.  ``Y`` None: q is None.  What differs from the device is the library behind exp and log."""
+    R = np.asarray(R, dtype=np.float64)
+    a = np.asarray(log_prior, dtype=np.float64).reshape(-1)
+    n = R.shape[0]
+    with np.errstate(all="ignore"):
+        t = a[None, :] - (np.float64(c) * R)
+        ok = t > -np.inf
+        has = ok.any(axis=1)
+        b = np.argmax(np.where(ok, t, -np.inf), axis=1)     # the first maximum: the lowest index
+        T = t[np.arange(n), b]
+        s = np.exp(t - T[:, None])
+        S = _lane_sums(s)
+        lse = np.where(has, T + np.log(S), np.nan)
+        q = None
+        if Y is not None:
+            Y = np.asarray(Y, dtype=np.float64)
+            q = np.stack([_lane_sums(s * Y[None, :, v]) / S for v in range(Y.shape[1])], axis=1).reshape(n, Y.shape[1])
+            q[~has] = np.nan
+    return np.where(has, b, -1).astype(np.int64), lse, q
+
+
+def _mixture_args(M, log_prior, c, Y):
+    """-> (a (M,) float64, c as a float, Y (M, V) float64 or None) for ``mixture``, checked"""
+    a = np.ascontiguousarray(log_prior, dtype=np.float64)
+    if a.shape != (M,):
+        raise ValueError(f"log_prior must be ({M},), one value per prototype, got {a.shape}")
+    c = float(c)
+    if not c >= 0.0:
+        raise ValueError(f"c must be >= 0, got {c!r}")
+    if Y is not None:
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if Y.ndim != 2 or Y.shape[0] != M:
+            raise ValueError(f"Y must be ({M}, n_values), one row per prototype, got {Y.shape}")
+        if not 1 <= Y.shape[1] <= _native.MAX_MIXTURE_VALUES:
+            raise ValueError(f"need 1 .. DBGSOM_MAX_MIXTURE_VALUES = {_native.MAX_MIXTURE_VALUES} values per prototype, "
+                             f"got {Y.shape[1]}")
+    return a, c, Y
+
+
 class HotPathBackend:
     """Epoch template shared by the HIP backend and the test-only oracle backend:
     local per-prototype sums -> (all-reduce across sample shards) -> smoothing.
@@ -181,6 +244,36 @@ class HotPathBackend:
         with np.errstate(invalid="ignore"):
             rho = np.sqrt(thr)
             return np.stack([np.count_nonzero(D <= r, axis=0) for r in rho], axis=1).astype(np.int64)
+
+    def mixture(self, W, log_prior, c, Y, X):
+        """The map as an isotropic Gaussian mixture -> (unit, lse, q): (rows of X,) int64, (rows of X,) float64 and
+        (rows of X, n_values) float64, or None for ``Y`` None.  With r the squared value of ``bmu(W, k, X=X)``'s
+        arithmetic (what ``kneighbors`` selects on), ``log_prior`` (rows of W,) float64 (``-inf`` allowed), ``c = 1 /
+        (2 h^2) >= 0`` and ``Y`` (rows of W, 1 .. MAX_MIXTURE_VALUES) float64: ``t_j = log_prior_j - c r_j``, ``unit``
+        the index of the largest t_j (lowest among equals), ``lse = log sum_j exp(t_j)`` and ``q_v = sum_j exp(t_j) Y[j,
+        v] / sum_j exp(t_j)``, evaluated as ``mixture_rows_host`` states it: the roundings and the order of the sums are
+        fixed (include/dbgsom_hip.h).  A row without a t_j above -inf has (-1, NaN, NaN).  X as for ``distances``; the
+        results are NumPy arrays, next to X for a device array.
+
+        This default evaluates ``mixture_rows_host`` on the squares of ``distances(W, X)``, 4096 rows at a time: the
+        square of a correctly rounded root is r to within two roundings, not r itself.  The HIP backend reads r on the
+        device and holds no N x M matrix."""
+        M = len(np.asarray(W))
+        a, c, Y = _mixture_args(M, log_prior, c, Y)
+        D = self.distances(W, X)
+        D = D if isinstance(D, np.ndarray) else D.cpu().numpy()
+        n = D.shape[0]
+        unit, lse = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.float64)
+        q = None if Y is None else np.empty((n, Y.shape[1]), dtype=np.float64)
+        for r0 in range(0, n, 4096):
+            sl = slice(r0, min(n, r0 + 4096))
+            with np.errstate(over="ignore", invalid="ignore"):
+                R = D[sl] * D[sl]
+            res = mixture_rows_host(R, a, c, Y)
+            unit[sl], lse[sl] = res[0], res[1]
+            if q is not None:
+                q[sl] = res[2]
+        return unit, lse, q
 
     def geodesics(self, W, edges):
         """The weighted geodesics of the lattice -> G, (rows of W, rows of W) float64.  ``edges`` is an (E, 2) integer
@@ -1228,6 +1321,25 @@ class HipBackend(HotPathBackend):
         self._query("range_counts_query", "euclidean", rows, W64.ctypes.data, M, thr.ctypes.data, thr.size,
                     rows.ptr(counts))
         return counts
+
+    # -- the map as a Gaussian mixture ---------------------------------------------------------------
+    def mixture(self, W, log_prior, c, Y, X):
+        """The mixture view of every row (csrc/mixture.hip): the squared distances of a slab of
+        ``kneighbors_slab_rows`` rows stay on the device, the mixture kernel reads them back from cache against the
+        log-priors and Y, and only (rows,) units and log-sums and (rows, n_values) posterior means are the result.
+        The log-priors and Y go up once per call.  Host rows go up in chunks of ``distances_chunk_rows`` rows and
+        rows x (16 + 8 n_values) bytes come down; CSR rows are expanded on the device chunk by chunk; for rows in HBM
+        the results are arrays on their device that the kernel writes itself (dbgsom_ctx_mixture_query_device)."""
+        rows = self._query_rows(X, defer=True)
+        W64, M = self._w64(W, rows.d)
+        a, c, Y64 = _mixture_args(M, log_prior, c, Y)
+        V = 0 if Y64 is None else Y64.shape[1]
+        unit, lse = rows.empty((rows.N,), "int64"), rows.empty((rows.N,), "float64")
+        q = rows.empty((rows.N, V), "float64") if V else None
+        if rows.N:
+            self._query("mixture_query", "euclidean", rows, W64.ctypes.data, M, a.ctypes.data, c,
+                        Y64.ctypes.data if V else None, V, rows.ptr(unit), rows.ptr(lse), rows.ptr(q) if V else None)
+        return unit, lse, q
 
     # -- weighted geodesics and the combined error of a query ------------------------------------------
     @staticmethod

@@ -54,7 +54,7 @@ from __future__ import annotations
 
 import copy
 import numbers
-from math import log, pi, sqrt
+from math import fsum, log, pi, sqrt
 
 import networkx as nx
 import numpy as np
@@ -65,7 +65,7 @@ from sklearn.utils import check_array, check_random_state
 from sklearn.utils.validation import check_is_fitted
 
 from . import schedule
-from ._native import MAX_NEIGHBORS, MAX_RADII
+from ._native import MAX_MIXTURE_VALUES, MAX_NEIGHBORS, MAX_RADII
 from .backend import (RESIDENT, HotPathBackend, array_namespace, dist_info, dtype_name, is_device_array, is_sparse,
                       shard_bounds, squared_thresholds)
 from .lattice import GrowingLattice
@@ -1511,6 +1511,187 @@ class BaseSom(BaseEstimator):
             return U * np.ones_like(P)
         return U * ((P - mean) / (mean - top) + 1.0)
 
+    # ------------------------------------------------------------------------------------------
+    # the map as an isotropic Gaussian mixture (csrc/mixture.hip)
+    # ------------------------------------------------------------------------------------------
+    def _mixture_query(self, X, what: str):
+        """The validated rows of a mixture call and its refusals, on the host before anything is uploaded."""
+        check_is_fitted(self)
+        kind = self._search_metric()
+        if kind:
+            self._refuse_metric(kind, what, "the model is Gaussian in the Euclidean distance")
+        if not is_device_array(X) and not is_sparse(X) and np.ndim(X) == 2 and np.shape(X)[0] == 0:
+            X = check_array(X, dtype=[np.float64, np.float32], ensure_min_samples=0)   # (no rows: no launch)
+        else:
+            X = self._check_query(X)
+        if X.shape[1] != self.n_features_in_:
+            raise ValueError(f"X has {X.shape[1]} features, but {type(self).__name__} is expecting "
+                             f"{self.n_features_in_} features as input")
+        if isinstance(X, np.ndarray) and np.isnan(X).any():   # (passed _check_query: missing_values is set)
+            raise ValueError(f"X holds NaN: the mixture density is not defined on rows with missing entries "
+                             f"(missing_values={self.missing_values!r}); impute them first (impute(X))")
+        return X
+
+    @staticmethod
+    def _check_bandwidth(bandwidth) -> float:
+        if isinstance(bandwidth, (bool, np.bool_)) or not isinstance(bandwidth, (numbers.Real, np.floating, np.integer)):
+            raise ValueError(f"bandwidth must be None or a finite float > 0, got {bandwidth!r}")
+        h = float(bandwidth)
+        if not (np.isfinite(h) and h > 0.0 and 0.0 < 2.0 * h * h < np.inf and np.isfinite(1.0 / (2.0 * h * h))):   # (c finite)
+            raise ValueError(f"bandwidth must be None or a finite float > 0, got {bandwidth!r}")
+        return h
+
+    def _mixture_params(self, bandwidth, priors):
+        """-> (log-priors (M,) float64 with -inf for a unit without mass, c = 1 / (2 h^2), h): the arguments, or for
+        each that is None the attribute ``fit_mixture`` set"""
+        M = len(self.weights_)
+        if bandwidth is None:
+            if not hasattr(self, "mixture_bandwidth_"):
+                raise ValueError("no bandwidth: call fit_mixture(X) first, or pass bandwidth")
+            h = float(self.mixture_bandwidth_)
+        else:
+            h = self._check_bandwidth(bandwidth)
+        if priors is None:
+            if not hasattr(self, "mixture_priors_"):
+                raise ValueError("no priors: call fit_mixture(X) first, or pass priors (an array, or 'uniform')")
+            p = np.asarray(self.mixture_priors_, dtype=np.float64)
+            if p.shape != (M,):
+                raise ValueError(f"mixture_priors_ holds {p.shape[0]} shares, the map has {M} prototypes: call "
+                                 "fit_mixture(X) again")
+        elif isinstance(priors, str):
+            if priors != "uniform":
+                raise ValueError(f"priors must be None, 'uniform' or an array-like of shape ({M},), got {priors!r}")
+            p = np.full(M, 1.0 / M)
+        else:
+            try:
+                p = np.asarray(priors, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError(f"priors must be None, 'uniform' or an array-like of shape ({M},), "
+                                 f"got {priors!r}") from None
+            if p.shape != (M,):
+                raise ValueError(f"priors must be None, 'uniform' or an array-like of shape ({M},), got shape {p.shape}")
+            if not (np.isfinite(p).all() and (p >= 0.0).all()):
+                raise ValueError("priors must be finite and non-negative")
+            if abs(fsum(p.tolist()) - 1.0) > 1e-9:
+                raise ValueError(f"priors must sum to 1 within 1e-9, got a sum of {fsum(p.tolist())!r}")
+        with np.errstate(divide="ignore"):
+            return np.log(p), 1.0 / (2.0 * h * h), h
+
+    def fit_mixture(self, X, bandwidth=None):
+        """Read the fitted map as an isotropic Gaussian mixture of X and return ``self``: the prototypes are the
+        centres, ``mixture_priors_`` (``(len(weights_),)`` float64) the shares of the rows of X per best matching unit
+        -- zeros allowed: a unit without mass -- and ``mixture_bandwidth_`` the one standard deviation ``h`` of every
+        component.  This is the reduced-set density estimate: a kernel density estimate on the prototypes, weighted by
+        their hits.
+
+        ``bandwidth=None``: ``h^2 = fsum_i(dist_i^2) / (n d)`` with ``dist`` the ``kneighbors(X, 1)`` distances, the
+        maximum-likelihood variance under hard assignments; ``math.fsum`` makes it independent of the order, so a host
+        array, a tensor and CSR rows of the same data give the same float.  ``h^2 == 0`` (every row sits on a
+        prototype) or a non-finite value is a ``ValueError``.  Otherwise a finite float > 0.  ``2 n x 8`` bytes come to
+        the host.  The map itself, and everything ``fit`` set, is left as it is.  X and the refusals are
+        ``score_samples``'s; X needs at least one row."""
+        X = self._mixture_query(X, "fit_mixture")
+        n, M = X.shape[0], len(self.weights_)
+        if n == 0:
+            check_array(X, dtype=[np.float64, np.float32])   # (no rows: refused in check_array's words)
+        h = None if bandwidth is None else self._check_bandwidth(bandwidth)
+        dist, idx = self._engine().kneighbors(self.weights_, 1, X)
+        dist, idx = self._host(dist).reshape(-1), self._host(idx).reshape(-1)
+        if (idx < 0).any():
+            raise ValueError("a row of X has no prototype at a finite distance")
+        if h is None:
+            h2 = fsum((dist * dist).tolist()) / (n * X.shape[1])
+            if not (np.isfinite(h2) and h2 > 0.0):
+                raise ValueError(f"the bandwidth estimated from X is not a finite value > 0 (h^2 = {h2!r}): pass bandwidth")
+            h = self._check_bandwidth(sqrt(h2))
+        self.mixture_priors_ = np.bincount(idx, minlength=M).astype(np.float64) / n
+        self.mixture_bandwidth_ = h
+        return self
+
+    def _mixture(self, X, what, values, bandwidth, priors):
+        """-> (X, unit, lse, q, h) of the validated rows; no rows: empty host arrays without a launch"""
+        X = self._mixture_query(X, what)
+        a, c, h = self._mixture_params(bandwidth, priors)
+        if X.shape[0] == 0 and not is_device_array(X):
+            q = None if values is None else np.empty((0, values.shape[1]), dtype=np.float64)
+            return X, np.empty(0, dtype=np.int64), np.empty(0, dtype=np.float64), q, h
+        unit, lse, q = self._engine().mixture(self.weights_, a, c, values, X)
+        return X, unit, lse, q, h
+
+    def sample_mixture(self, X, bandwidth=None, priors=None):
+        """``(log_density, map_unit)``, ``(n_samples,)`` float64 and int64: ``score_samples(X)`` and the unit with the
+        largest posterior, ``argmax_j (log prior_j - ||x_i - w_j||^2 / (2 h^2))``, lowest index among equals -- with
+        equal priors ``predict``'s unit for ``SomVQ``.  Both come from one pass.  A row for which no unit has mass has
+        ``(NaN, -1)``.  Arguments, X and the refusals are ``score_samples``'s."""
+        X, unit, lse, _, h = self._mixture(X, "sample_mixture / score_samples", None, bandwidth, priors)
+        return lse - 0.5 * X.shape[1] * log(2.0 * pi * h * h), unit
+
+    def score_samples(self, X, bandwidth=None, priors=None):
+        """The log-density of every row under the map read as an isotropic Gaussian mixture, ``(n_samples,)`` float64:
+        ``log p(x_i) = log sum_j prior_j exp(-||x_i - w_j||^2 / (2 h^2)) - (d / 2) log(2 pi h^2)`` -- a
+        ``score_samples`` in scikit-learn's sense, and a novelty score: low where the map has no prototype nearby.
+
+        ``bandwidth`` / ``priors`` ``None`` take ``mixture_bandwidth_`` / ``mixture_priors_`` (``fit_mixture``);
+        without them a ``ValueError`` says so.  ``bandwidth`` is a finite float > 0; ``priors`` an array-like
+        ``(len(weights_),)``, non-negative and summing to 1 within 1e-9, or ``"uniform"``.
+
+        The squared distances are those of the best-matching-unit search's own arithmetic, ``r_ij = max((|x_i|^2 + (-2
+        <x_i, w_j>)) + |w_j|^2, 0)``, the ones ``kneighbors`` selects on.  ``t_j = log prior_j - (c * r_ij)`` with ``c =
+        1 / (2 h^2)`` (two roundings), the sum is ``T + log(sum_j exp(t_j - T))`` with T the largest ``t_j``, 64
+        strided partials then six xor rounds, in float64 with the device library's ``exp`` and ``log``; the constant
+        is added on the caller's side.  The order is fixed, so the result does not depend on chunks, slabs or where X
+        lives.  The N x M matrix is never held.
+
+        X is what ``sample_distortion`` takes: a dense array (a NumPy result; 16 bytes per row come down), a tensor on
+        the estimator's GPU (a tensor on X's device; X never touches the host), scipy sparse rows (the dense call's
+        result on ``X.toarray()``).  Refused with a ``ValueError``: ``metric="manhattan"`` / ``"cosine"`` (the model is
+        Gaussian in the Euclidean distance), rows with NaN (also under ``missing_values``: impute them first), a
+        feature-count mismatch.  Only this map's prototypes are used (not the child maps of vertical growth); the call
+        is local to the process."""
+        return self.sample_mixture(X, bandwidth, priors)[0]
+
+    def calculate_log_likelihood(self, X, bandwidth=None, priors=None) -> float:
+        """The mean of ``score_samples(X, bandwidth, priors)`` as a float.  The per-row values come to the host (8
+        bytes per row) and NumPy sums them, so a host array and a tensor holding the same rows give the same float."""
+        s = self.score_samples(X, bandwidth, priors)
+        if s.shape[0] == 0:
+            check_array(X, dtype=[np.float64, np.float32])   # (no rows: refused in check_array's words, as a mean is)
+        return float(np.sum(self._host(s))) / s.shape[0]
+
+    def posterior_mean(self, X, values, bandwidth=None, priors=None):
+        """The posterior mean of a per-unit quantity: ``q_i = sum_j p(j | x_i) values[j]`` with ``p(j | x_i)`` the
+        responsibilities of the mixture of ``score_samples`` -- class shares, a component plane, a label, read softly
+        instead of at the best matching unit.  ``values`` is ``(len(weights_),)`` or ``(len(weights_), V)`` with ``V
+        <= 16`` real numbers; the result is ``(n_samples,)`` or ``(n_samples, V)`` float64.  Every column is ``sum_j
+        (s_j * values[j]) / sum_j s_j`` with ``s_j = exp(t_j - T)`` in the fixed order of ``score_samples``, one
+        division per row and column.  A row for which no unit has mass has NaN.  From a dense array ``8 V`` bytes per
+        row come down beside ``score_samples``'s 16.  Arguments, X and the refusals are ``score_samples``'s."""
+        check_is_fitted(self)
+        M = len(self.weights_)
+        try:
+            Y = np.asarray(values, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"values must be real numbers of shape ({M},) or ({M}, V), got {values!r}") from None
+        flat = Y.ndim == 1
+        if flat:
+            Y = Y.reshape(-1, 1)
+        if Y.ndim != 2 or Y.shape[0] != M or Y.shape[1] < 1:
+            raise ValueError(f"values must have shape ({M},) or ({M}, V), one row per prototype, got {np.shape(values)}")
+        if Y.shape[1] > MAX_MIXTURE_VALUES:
+            raise ValueError(f"values has {Y.shape[1]} columns, above the {MAX_MIXTURE_VALUES} the kernel sums per row: "
+                             "use several calls")
+        q = self._mixture(X, "posterior_mean / project", np.ascontiguousarray(Y), bandwidth, priors)[3]
+        return q[:, 0] if flat else q
+
+    def project(self, X, bandwidth=None, priors=None):
+        """The smooth projection of every row onto the lattice, ``(n_samples, 2)`` float64: the posterior mean of the
+        units' lattice coordinates (the node tuples ``neurons_``, in the order of ``weights_``) -- GTM's "mean
+        projection".  Rows between two units land between their nodes instead of collapsing onto one; every position
+        lies inside the bounding box of the lattice.  ``posterior_mean(X, coordinates, bandwidth, priors)``."""
+        check_is_fitted(self)
+        return self.posterior_mean(X, np.asarray(list(self.neurons_), dtype=np.float64).reshape(len(self.weights_), -1),
+                                   bandwidth, priors)
+
     def _lattice_edges(self) -> np.ndarray:
         """The undirected edges of the fitted lattice as an (E, 2) int32 array of indices into ``weights_`` /
         ``neurons_`` (the graph as it is after the dead units were removed; it survives a pickle)."""
@@ -1586,7 +1767,7 @@ class BaseSom(BaseEstimator):
         if self._is_resident(X):
             return self._engine().topographic_error_count(self.weights_, self.neurons_) / self._n_effective()
         _, bmu = self._get_winning_neurons(X, n_bmu=2)
-        pos = np.asarray(self.neurons_, dtype=np.float64)
+        pos = np.asarray(list(self.neurons_), dtype=np.float64)
         apart = np.linalg.norm(pos[bmu[:, 0]] - pos[bmu[:, 1]], axis=1) > 1.5
         return int(np.count_nonzero(apart)) / X.shape[0]
 

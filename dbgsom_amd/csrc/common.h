@@ -260,6 +260,14 @@ int launch_energy_rows(const double *R, int64_t N, int64_t M, int64_t ldr, const
 int launch_neighborhood_energy(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx,
                                const double *W, int64_t M, const double *ww, const double *H, int64_t ldh,
                                int64_t slab_rows, int64_t *bmu, double *e, void *ws, size_t ws_bytes, hipStream_t s);
+// the map as a Gaussian mixture (mixture.hip): per row the unit of the largest t_j = a_j - c r_j, lse = log sum_j exp(t_j)
+// and q_v = sum_j exp(t_j) Y[j, v] / sum_j exp(t_j), on a matrix of squared values, and the driver over slabs of rows
+// (the slabs and the workspace of launch_kneighbors); n_values == 0: Y and q are null
+int launch_mixture_rows(const double *R, int64_t N, int64_t M, int64_t ldr, const double *a, double c, const double *Y,
+                        int n_values, int64_t ldy, int64_t *unit, double *lse, double *q, int64_t ldq, hipStream_t s);
+int launch_mixture(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx, const double *W, int64_t M,
+                   const double *ww, const double *a, double c, const double *Y, int n_values, int64_t ldy, int64_t slab_rows,
+                   int64_t *unit, double *lse, double *q, int64_t ldq, void *ws, size_t ws_bytes, hipStream_t s);
 // the k nearest rows to every prototype (exemplars.hip): the fold down the columns of a matrix of squared values --
 // state_r / state_i (M x k) hold per column the k smallest (r, global row) so far --, the slab loop of launch_kneighbors
 // with that fold behind the product (rows row0 .. row0 + N - 1 into a caller's state), the kernel that stores the state

@@ -286,7 +286,8 @@ struct dbgsom_ctx {
     int64_t kneighbors_slab_rows = 0;
     DevBuf kn_ws, kn_idx, kn_dist;
     // the distortion measure of a query (distortion.hip): the M x M neighbourhood factors of the call (the slab and a
-    // chunk's staged result are kn_ws, kn_idx and kn_dist)
+    // chunk's staged result are kn_ws, kn_idx and kn_dist); the mixture of a query (mixture.hip): [the log-priors | Y] of
+    // the call (its third result is staged in pd_out)
     DevBuf de_h;
     // the combined error of a query (geodesics.hip): the M x M geodesics of the call, and the edges, their lengths and
     // the status word in front of a chunk's distances (the pairs and e are staged in kn_idx / kn_dist)
@@ -1872,7 +1873,17 @@ int dbgsom_ctx_bmu_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const in
 // ------------------------------------------------------------------------------------------
 namespace {
 
-enum QueryOp { Q_BMU, Q_DISTANCES, Q_KNEIGHBORS, Q_DISTORTION, Q_EXEMPLARS, Q_COMBINED, Q_RANGE_COUNTS };
+enum QueryOp { Q_BMU, Q_DISTANCES, Q_KNEIGHBORS, Q_DISTORTION, Q_EXEMPLARS, Q_COMBINED, Q_RANGE_COUNTS, Q_MIXTURE };
+
+// what Q_MIXTURE takes beside the rows and the prototypes (csrc/mixture.hip): the log-priors (M), c, the per-unit values
+// (M x n_values, contiguous) and the third result q (Nq x n_values, contiguous; host or device as the other two)
+struct MixtureArgs {
+    const double *logprior_host;
+    double c;
+    const double *Y_host;
+    int n_values;
+    double *q_out;
+};
 enum RowsForm { ROWS_MASKED, ROWS_MANHATTAN, ROWS_COSINE };
 
 // DBGSOM_REQUIRE under the name of the exported call `fn` (checks shared by several of them)
@@ -1899,7 +1910,7 @@ int query_args(const char *fn, const dbgsom_ctx *c, QueryOp op, int x_dtype, boo
     }
     REQUIRE_FN(fn, Nq >= 0 && Nq < 0x7fffffff && d >= 1 && d <= 0x7fffffff, "bad sample shape");
     REQUIRE_FN(fn, M >= 1 && M <= DBGSOM_MAX_PROTOTYPES, "need 1 <= M <= DBGSOM_MAX_PROTOTYPES");
-    if (op == Q_DISTANCES || op == Q_DISTORTION) return DBGSOM_OK;
+    if (op == Q_DISTANCES || op == Q_DISTORTION || op == Q_MIXTURE) return DBGSOM_OK;
     if (op == Q_RANGE_COUNTS) {   // (k counts thresholds)
         REQUIRE_FN(fn, k >= 1 && k <= DBGSOM_MAX_RADII, "need 1 <= n_radii <= DBGSOM_MAX_RADII");
         return DBGSOM_OK;
@@ -2157,13 +2168,16 @@ struct CsrHost {
 // counts in rc_state, the counts are zeroed in front of the chunks and every chunk folds into them -- nothing per chunk
 // is staged or copied down --; after the last one they come down in one piece (M * k * 8 bytes) into idx_out, or are
 // copied into the caller's device array.
+// Q_MIXTURE (csrc/mixture.hip; k = 1): the neighbours' slab and staging with the mixture kernel behind the product;
+// idx_out / dist_out take a row's unit and its lse, and [the log-priors | Y] (mx: M x (1 + n_values) values) go up once
+// per call into de_h.  The third result, q (n_values per row), is staged in pd_out and comes down behind the other two.
 // Q_COMBINED (csrc/geodesics.hip; k = 2): the geodesics of the map are queued once in front of the chunks (edges_host,
 // E); a chunk's all-pairs search leaves its pairs in idx (staged: kn_idx) and its distances in ce_ws, the rows kernel
 // reads both and G and writes e (one value per row; staged: kn_dist).  The status word is read after the last chunk.
 int placed_rows_query(dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHost *csr, int x_dtype, int64_t Nq, int64_t d,
                       const double *W_host, int64_t M, int k, int64_t *idx_out, double *dist_out, int64_t ldo,
                       const double *H_host, int own_cell, const int32_t *edges_host = nullptr, int64_t E = 0,
-                      const double *thr_host = nullptr) {
+                      const double *thr_host = nullptr, const MixtureArgs *mx = nullptr) {
     Samples &s = c->xq;
     DevBuf Wq, wwq;
     const int64_t dp = pad16(d);
@@ -2189,6 +2203,16 @@ int placed_rows_query(dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHo
             const hipError_t e = hipMemcpyAsync(c->de_h.p, H_host, (size_t)M * M * 8, hipMemcpyHostToDevice, c->stream);
             if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
             c->x_up((size_t)M * M * 8);
+        }
+        if (op == Q_MIXTURE) {
+            const int V = mx->n_values;
+            if ((rc = c->de_h.reserve((size_t)M * (1 + V) * 8))) break;
+            hipError_t e = hipMemcpyAsync(c->de_h.p, mx->logprior_host, (size_t)M * 8, hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess && V)
+                e = hipMemcpyAsync(c->de_h.as<double>() + M, mx->Y_host, (size_t)M * V * 8, hipMemcpyHostToDevice, c->stream);
+            if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
+            c->x_up((size_t)M * (1 + V) * 8);
+            if (staged && V && (rc = c->pd_out.reserve((size_t)chunk * V * 8))) break;
         }
         if (comb) {
             if ((rc = queue_geodesics(c, Wq.as<double>(), M, d, dp, edges_host, E, (size_t)chunk * 16))) break;
@@ -2255,7 +2279,13 @@ int placed_rows_query(dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHo
                 rc = launch_neighborhood_energy(s.Xb, s.bdtype, n, dp, dp, s.xx.as<double>(), Wq.as<double>(), M,
                                                 wwq.as<double>(), c->de_h.as<double>(), M, c->kneighbors_slab_rows, idx, res,
                                                 c->kn_ws.p, c->kn_ws.cap, c->stream);
-            else if (knn)
+            else if (op == Q_MIXTURE) {
+                const int V = mx->n_values;   // (rows in HBM are one chunk: q_out is written from its first row)
+                double *qd = !V ? nullptr : (staged ? c->pd_out.as<double>() : mx->q_out);
+                rc = launch_mixture(s.Xb, s.bdtype, n, dp, dp, s.xx.as<double>(), Wq.as<double>(), M, wwq.as<double>(),
+                                    c->de_h.as<double>(), mx->c, V ? c->de_h.as<double>() + M : nullptr, V, V,
+                                    c->kneighbors_slab_rows, idx, res, qd, V, c->kn_ws.p, c->kn_ws.cap, c->stream);
+            } else if (knn)
                 rc = launch_kneighbors(s.Xb, s.bdtype, n, dp, dp, s.xx.as<double>(), Wq.as<double>(), M, wwq.as<double>(), k,
                                        c->kneighbors_slab_rows, idx, res, c->kn_ws.p, c->kn_ws.cap, c->stream);
             else
@@ -2268,6 +2298,12 @@ int placed_rows_query(dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHo
                 e = hipMemcpyAsync(dist_out + r0 * per_row, res, (size_t)n * per_row * 8, hipMemcpyDeviceToHost, c->stream);
             if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; }
             c->x_down(comb ? (size_t)n * 24 : (size_t)n * per_row * (knn ? 16 : 8));
+            if (op == Q_MIXTURE && mx->n_values && rc == DBGSOM_OK) {
+                const size_t qb = (size_t)n * mx->n_values * 8;
+                e = hipMemcpyAsync(mx->q_out + r0 * mx->n_values, c->pd_out.p, qb, hipMemcpyDeviceToHost, c->stream);
+                if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; }
+                c->x_down(qb);
+            }
         }
         if (rc == DBGSOM_OK && comb) rc = geodesics_status("dbgsom_ctx_combined_error_query", carve_geodesics(c, E).status, M, c->stream);
         if (rc == DBGSOM_OK && range) {
@@ -2326,8 +2362,13 @@ int raw_rows_checked(const char *fn, dbgsom_ctx *c, QueryOp op, RowsForm form, c
 int placed_rows_checked(const char *fn, dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHost *csr, int x_dtype, int64_t Nq,
                         int64_t d, const double *W_host, int64_t M, int k, int64_t *idx_out, double *dist_out, int64_t ldo,
                         const double *H_host = nullptr, int own_cell = 0, const int32_t *edges_host = nullptr, int64_t E = 0,
-                        const double *thr_host = nullptr) {
+                        const double *thr_host = nullptr, const MixtureArgs *mx = nullptr) {
     TRY(query_args(fn, c, op, x_dtype, csr != nullptr, Nq, d, M, k));
+    if (op == Q_MIXTURE) {
+        REQUIRE_FN(fn, mx->n_values >= 0 && mx->n_values <= DBGSOM_MAX_MIXTURE_VALUES,
+                   "need 0 <= n_values <= DBGSOM_MAX_MIXTURE_VALUES");
+        REQUIRE_FN(fn, mx->c >= 0.0, "c must be >= 0");   // (NaN fails)
+    }
     if (op == Q_COMBINED) REQUIRE_FN(fn, E >= 0 && E <= 0x7fffffff, "need 0 <= E < 2^31");
     if (q.on_device) REQUIRE_FN(fn, q.ldx >= d, "ldx must be >= d");
     if (op == Q_DISTANCES) REQUIRE_FN(fn, ldo >= M, "ldo must be >= M");
@@ -2339,10 +2380,11 @@ int placed_rows_checked(const char *fn, dbgsom_ctx *c, QueryOp op, const QueryRo
     REQUIRE_FN(fn, (csr || q.p) && W_host && (op == Q_DISTANCES || idx_out) && (op == Q_RANGE_COUNTS || dist_out), "null pointer");
     if (op == Q_RANGE_COUNTS) REQUIRE_FN(fn, thr_host, "null pointer");
     if (op == Q_DISTORTION) REQUIRE_FN(fn, H_host, "null pointer");
+    if (op == Q_MIXTURE) REQUIRE_FN(fn, mx->logprior_host && (mx->n_values == 0 || (mx->Y_host && mx->q_out)), "null pointer");
     if (op == Q_COMBINED) REQUIRE_FN(fn, E == 0 || edges_host, "null pointer");
     SET_DEVICE(c);
     return placed_rows_query(c, op, q, csr, x_dtype, Nq, d, W_host, M, k, idx_out, dist_out, ldo, H_host, own_cell, edges_host,
-                             E, thr_host);
+                             E, thr_host, mx);
 }
 
 }  // namespace
@@ -2485,6 +2527,35 @@ int dbgsom_ctx_range_counts_query_csr(dbgsom_ctx *c, const int64_t *indptr_host,
     const CsrHost csr{indptr_host, indices_host, nnz};
     return placed_rows_checked(__func__, c, Q_RANGE_COUNTS, QueryRows{data_host, false, d}, &csr, x_dtype, Nq, d, W_host, M,
                                n_radii, counts_host, nullptr, 0, nullptr, 0, nullptr, 0, thr_host);
+}
+
+// ------------------------------------------------------------------------------------------
+// the map as a Gaussian mixture: csrc/mixture.hip (unit, lse: Nq values; q: Nq x n_values)
+// ------------------------------------------------------------------------------------------
+int dbgsom_ctx_mixture_query(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d, const double *W_host,
+                             int64_t M, const double *logprior_host, double cc, const double *Y_host, int n_values,
+                             int64_t *unit_host, double *lse_host, double *q_host) {
+    const MixtureArgs mx{logprior_host, cc, Y_host, n_values, q_host};
+    return placed_rows_checked(__func__, c, Q_MIXTURE, QueryRows{Xq_host, false, d}, nullptr, x_dtype, Nq, d, W_host, M, 1,
+                               unit_host, lse_host, 0, nullptr, 0, nullptr, 0, nullptr, &mx);
+}
+
+int dbgsom_ctx_mixture_query_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d, int64_t ldx,
+                                    const double *W_host, int64_t M, const double *logprior_host, double cc,
+                                    const double *Y_host, int n_values, int64_t *unit_dev, double *lse_dev, double *q_dev) {
+    const MixtureArgs mx{logprior_host, cc, Y_host, n_values, q_dev};
+    return placed_rows_checked(__func__, c, Q_MIXTURE, QueryRows{Xq_dev, true, ldx}, nullptr, x_dtype, Nq, d, W_host, M, 1,
+                               unit_dev, lse_dev, 0, nullptr, 0, nullptr, 0, nullptr, &mx);
+}
+
+int dbgsom_ctx_mixture_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const int32_t *indices_host,
+                                 const void *data_host, int x_dtype, int64_t Nq, int64_t d, int64_t nnz, const double *W_host,
+                                 int64_t M, const double *logprior_host, double cc, const double *Y_host, int n_values,
+                                 int64_t *unit_host, double *lse_host, double *q_host) {
+    const CsrHost csr{indptr_host, indices_host, nnz};
+    const MixtureArgs mx{logprior_host, cc, Y_host, n_values, q_host};
+    return placed_rows_checked(__func__, c, Q_MIXTURE, QueryRows{data_host, false, d}, &csr, x_dtype, Nq, d, W_host, M, 1,
+                               unit_host, lse_host, 0, nullptr, 0, nullptr, 0, nullptr, &mx);
 }
 
 // ------------------------------------------------------------------------------------------

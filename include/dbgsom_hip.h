@@ -834,6 +834,59 @@ int dbgsom_ctx_range_counts_query_csr(dbgsom_ctx *ctx, const int64_t *indptr_hos
                                       const double *W_host, int64_t M, const double *thr_host, int n_radii,
                                       int64_t *counts_host);
 
+/* ---- the map as an isotropic Gaussian mixture (csrc/mixture.hip) ---------------------------------------------
+ * Prototypes w_j, log-priors a_j (logprior, M float64; -inf allowed: a unit without mass) and c = 1 / (2 h^2) >= 0
+ * for one bandwidth h.  With r_ij = max((|x_i|^2 + (-2 <x_i, w_j>)) + |w_j|^2, 0) the squared value
+ * dbgsom_kneighbors selects on, row i has
+ *   t_j   = a_j - (c * r_ij)      the product rounded, then the difference rounded (never a fused multiply-add)
+ *   (T,b) = the largest t_j, lowest j among equals, over t_j > -inf and not NaN
+ *   s_j   = exp(t_j - T)          S = sum_j s_j          Q_v = sum_j (s_j * Y[j * ldy + v])
+ *   unit[i] = b     lse[i] = T + log(S)     q[i * ldq + v] = Q_v / S,   v = 0 .. n_values - 1
+ * so lse - (d / 2) log(2 pi h^2) is the log-density of the row, b its MAP unit (the unit of dbgsom_kneighbors at
+ * k = 1 under equal priors) and q the posterior mean of the per-unit values Y (M x n_values float64, rows ldy
+ * apart).  The order of the sums is that of dbgsom_energy_rows: lane l of 64 adds its terms j = l, l + 64, ...
+ * ascending from +0.0 -- in Q the product rounded and then the sum --, then six rounds m = 1, 2, 4, 8, 16, 32 in
+ * which every lane takes p_l + p_(l ^ m).  exp and log are the device library's float64 functions; Q_v / S is one
+ * division per row and value.  Otherwise plain IEEE: r = +inf gives s = 0; a NaN t_j is never the maximum but
+ * enters the sums as it is, so that row's lse and q are NaN.  A row without any t_j above -inf has (unit, lse, q)
+ * = (-1, NaN, NaN).  0 <= n_values <= DBGSOM_MAX_MIXTURE_VALUES; with n_values == 0 (density only) Y_dev and
+ * q_dev are null.  Argument errors (M, n_values, ldr < M, ldy < n_values, ldq < n_values, c negative or NaN,
+ * slab_rows < 0, a null or misaligned pointer, a short workspace: DBGSOM_ENOMEM with both sizes in the message)
+ * are reported before any launch; N == 0 returns DBGSOM_OK without one.
+ *
+ * dbgsom_mixture_rows: the kernel alone on a caller's matrix R of squared values, N rows of M entries ldr >= M
+ * apart; nothing of a row past M, of a row of Y past n_values or of a row of q past n_values is touched.
+ * dbgsom_mixture: arguments as dbgsom_neighborhood_energy: the rows are worked in the same slabs, in the same
+ * workspace (dbgsom_kneighbors_workspace_bytes(N, M, slab_rows): the slab is sized by that one function, 16-byte
+ * aligned, contents on entry irrelevant). */
+#define DBGSOM_MAX_MIXTURE_VALUES 16
+int dbgsom_mixture_rows(const double *R_dev, int64_t N, int64_t M, int64_t ldr, const double *logprior_dev, double c,
+                        const double *Y_dev, int n_values, int64_t ldy, int64_t *unit_dev, double *lse_dev,
+                        double *q_dev, int64_t ldq, void *stream);
+int dbgsom_mixture(const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx_dev,
+                   const double *W_dev, int64_t M, const double *ww_dev, const double *logprior_dev, double c,
+                   const double *Y_dev, int n_values, int64_t ldy, int64_t slab_rows, int64_t *unit_dev,
+                   double *lse_dev, double *q_dev, int64_t ldq, void *workspace_dev, size_t workspace_bytes,
+                   void *stream);
+/* The same on a context, each call staging its rows as its dbgsom_ctx_distortion_query* namesake does (chunks,
+ * query placement, CSR expanded chunk by chunk, the slab of "kneighbors_slab_rows" rows, status codes).
+ * logprior_host (M) and Y_host (M x n_values, contiguous) go up once per call and count as upload traffic; q is
+ * Nq x n_values, contiguous; Nq x (16 + 8 n_values) bytes of result come down per host-facing call.  _device:
+ * unit_dev / lse_dev / q_dev are written by the kernel; nothing of X or of the result crosses PCIe. */
+int dbgsom_ctx_mixture_query(dbgsom_ctx *ctx, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
+                             const double *W_host, int64_t M, const double *logprior_host, double c,
+                             const double *Y_host, int n_values, int64_t *unit_host, double *lse_host,
+                             double *q_host);
+int dbgsom_ctx_mixture_query_device(dbgsom_ctx *ctx, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d,
+                                    int64_t ldx, const double *W_host, int64_t M, const double *logprior_host,
+                                    double c, const double *Y_host, int n_values, int64_t *unit_dev,
+                                    double *lse_dev, double *q_dev);
+int dbgsom_ctx_mixture_query_csr(dbgsom_ctx *ctx, const int64_t *indptr_host, const int32_t *indices_host,
+                                 const void *data_host, int x_dtype, int64_t Nq, int64_t d, int64_t nnz,
+                                 const double *W_host, int64_t M, const double *logprior_host, double c,
+                                 const double *Y_host, int n_values, int64_t *unit_host, double *lse_host,
+                                 double *q_host);
+
 /* ---- weighted geodesics over the lattice and the combined error (csrc/geodesics.hip) -------------------------
  * The combined error of Kaski and Lagus (1996): e_i = d1_i + G[b1_i, b2_i], the distance of row i to its best
  * matching unit plus the length of the shortest path along the map from that unit to the second-best one, a
