@@ -251,7 +251,8 @@ int dbgsom_bmu_filtered(const void *X_dev, int x_dtype, int64_t N, int64_t d, in
  * ms5 = [slice W + tables, coarse pre-pass, bucket sort, int8 sweep, exact search on candidates] */
 int dbgsom_filter_timing(int enable);
 int dbgsom_bmu_filtered_stage_ms(double *ms5);
-/* diagnostics: candidate-list length of every 128-sample workgroup of the last filtered call */
+/* diagnostics: candidate-list length of every 128-sample workgroup of the last filtered call.  Synchronises the
+ * stream. */
 int dbgsom_bmu_filtered_counts(const void *workspace_dev, int64_t N, int64_t d, int64_t M,
                                uint32_t *counts_host, int64_t n_counts, void *stream);
 /* the same copy queued on `stream` without synchronising: counts_host must be page-locked and is

@@ -727,6 +727,10 @@ def all_cases(contents="any"):
     return [(name, i) for name, r in records().items() if r.contents == contents for i in range(len(r.cases))]
 
 
+# what tests/stream_cases.py shares with this table: the rows of prototype_distances.CASES and the chain norms
+pd_case, row_norms = _pd_case, _norms
+
+
 def case_id(key):
     name, i = key
     return name[len("dbgsom_"):-len("_bytes")].replace("_workspace", "") + ":" + records()[name].cases[i].label
