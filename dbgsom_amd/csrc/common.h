@@ -231,7 +231,33 @@ int64_t kneighbors_slab_rows(int64_t N, int64_t M, int64_t slab_rows);
 // rows of a slab are M rounded up to even apart, so that every row starts on 16 bytes
 inline int64_t kneighbors_slab_ld(int64_t M) { return M + (M & 1); }
 size_t kneighbors_workspace_bytes(int64_t N, int64_t M, int64_t slab_rows);
-// The slab loop of every kneighbors launcher: the rows in slabs of kneighbors_slab_rows, fill(rows, r0, n, slab, ldr)
+// the workspace of a slab loop under the name `fn` of its entry: `beside` bytes and the slab fit, then 16-byte alignment
+static inline int kneighbors_workspace_check(const char *fn, int64_t N, int64_t M, int64_t slab_rows, const void *ws,
+                                             size_t ws_bytes, size_t beside) {
+    TRY_STATUS(workspace_check(fn, ws_bytes, beside + kneighbors_workspace_bytes(N, M, slab_rows)));
+    if (!is_aligned(ws, 16)) {
+        set_error("%s: workspace_dev must be 16-byte aligned", fn);
+        return DBGSOM_EINVAL;
+    }
+    return DBGSOM_OK;
+}
+// The Euclidean slab loop (launch_kneighbors and everything else that reads a slab of squared distances back at once):
+// the rows in slabs of kneighbors_slab_rows, launch_distances_squared of a slab's n rows from r0 on into `slab`, rows
+// kneighbors_slab_ld(M) apart, then consume(r0, n, slab, ldr) on the same stream; the first non-zero status ends it.
+template <typename Consume>
+int euclidean_slabs(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx, const double *W,
+                    int64_t M, const double *ww, int64_t slab_rows, double *slab, hipStream_t s, Consume consume) {
+    const int64_t rows = kneighbors_slab_rows(N, M, slab_rows), ldr = kneighbors_slab_ld(M);
+    const size_t es = dtype_size(x_dtype);
+    for (int64_t r0 = 0; r0 < N; r0 += rows) {
+        const int64_t n = rows < N - r0 ? rows : N - r0;
+        TRY_STATUS(launch_distances_squared(static_cast<const char *>(X) + (size_t)r0 * ldx * es, x_dtype, n, d, ldx,
+                                            xx + r0, W, M, ww, slab, ldr, s));
+        TRY_STATUS(consume(r0, n, slab, ldr));
+    }
+    return DBGSOM_OK;
+}
+// The slab loop of the kneighbors launchers of the other forms (masked, Manhattan, cosine): fill(rows, r0, n, slab, ldr)
 // stores what is selected on for the n rows from r0 on (`rows`: the first of them) into `slab`, rows ldr apart, then
 // `select` (launch_topk_rows: the slab holds squared values; launch_topk_rows_plain: what is reported) on the slab.
 template <typename Fill>

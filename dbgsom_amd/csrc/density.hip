@@ -151,25 +151,18 @@ static int range_counts_check(int x_dtype, int64_t N, int64_t d, int64_t ldx, in
     return DBGSOM_OK;
 }
 
-// the slab loop of launch_kneighbors with the fold behind the product: the N rows are added to a caller's counts
+// the Euclidean slab loop with the fold behind the product: the N rows are added to a caller's counts
 int launch_range_counts_fold(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx, const double *W,
                              int64_t M, const double *ww, const double *thr, int n_radii, int64_t slab_rows, int64_t *counts,
                              void *ws, size_t ws_bytes, hipStream_t s) {
     TRY_STATUS(range_counts_check(x_dtype, N, d, ldx, M, n_radii, slab_rows));
     if (N == 0) return DBGSOM_OK;
     DBGSOM_REQUIRE(X && xx && W && ww && thr && counts && ws, "null pointer");
-    TRY_STATUS(workspace_check("dbgsom_range_counts", ws_bytes, range_counts_workspace_bytes(N, M, slab_rows)));
-    DBGSOM_REQUIRE(is_aligned(ws, 16), "workspace_dev must be 16-byte aligned");
-    const int64_t rows = kneighbors_slab_rows(N, M, slab_rows), ldr = kneighbors_slab_ld(M);
-    double *slab = static_cast<double *>(ws);
-    const size_t es = dtype_size(x_dtype);
-    for (int64_t r0 = 0; r0 < N; r0 += rows) {
-        const int64_t n = std::min(rows, N - r0);
-        TRY_STATUS(launch_distances_squared(static_cast<const char *>(X) + (size_t)r0 * ldx * es, x_dtype, n, d, ldx,
-                                            xx + r0, W, M, ww, slab, ldr, s));
-        TRY_STATUS(launch_range_count_cols(slab, n, M, ldr, thr, n_radii, counts, s));
-    }
-    return DBGSOM_OK;
+    TRY_STATUS(kneighbors_workspace_check("dbgsom_range_counts", N, M, slab_rows, ws, ws_bytes, 0));
+    return euclidean_slabs(X, x_dtype, N, d, ldx, xx, W, M, ww, slab_rows, static_cast<double *>(ws), s,
+                           [&](int64_t, int64_t n, const double *slab, int64_t ldr) {
+                               return launch_range_count_cols(slab, n, M, ldr, thr, n_radii, counts, s);
+                           });
 }
 
 int launch_range_counts(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx, const double *W,

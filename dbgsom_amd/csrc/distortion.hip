@@ -127,7 +127,7 @@ int launch_energy_rows(const double *R, int64_t N, int64_t M, int64_t ldr, const
     return launch_status("energy_rows_kernel");
 }
 
-// the slab loop of launch_kneighbors (same slab size rule, same workspace) with the energy kernel behind the product
+// the Euclidean slab loop (the slab size rule and the workspace of launch_kneighbors) with the energy kernel behind the product
 int launch_neighborhood_energy(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx,
                                const double *W, int64_t M, const double *ww, const double *H, int64_t ldh,
                                int64_t slab_rows, int64_t *bmu, double *e, void *ws, size_t ws_bytes, hipStream_t s) {
@@ -138,22 +138,11 @@ int launch_neighborhood_energy(const void *X, int x_dtype, int64_t N, int64_t d,
     if (N == 0) return DBGSOM_OK;
     DBGSOM_REQUIRE(X && xx && W && ww && H && bmu && e && ws, "null pointer");
     DBGSOM_REQUIRE(is_aligned(H, 8) && is_aligned(bmu, 8) && is_aligned(e, 8), "pointers must be 8-byte aligned");
-    const size_t need = kneighbors_workspace_bytes(N, M, slab_rows);
-    if (ws_bytes < need) {
-        set_error("dbgsom_neighborhood_energy: workspace of %zu bytes, %zu needed", ws_bytes, need);
-        return DBGSOM_ENOMEM;
-    }
-    DBGSOM_REQUIRE(is_aligned(ws, 16), "workspace_dev must be 16-byte aligned");
-    const int64_t rows = kneighbors_slab_rows(N, M, slab_rows), ldr = kneighbors_slab_ld(M);
-    double *slab = static_cast<double *>(ws);
-    const size_t es = dtype_size(x_dtype);
-    for (int64_t r0 = 0; r0 < N; r0 += rows) {
-        const int64_t n = std::min(rows, N - r0);
-        TRY_STATUS(launch_distances_squared(static_cast<const char *>(X) + (size_t)r0 * ldx * es, x_dtype, n, d, ldx,
-                                            xx + r0, W, M, ww, slab, ldr, s));
-        TRY_STATUS(launch_energy_rows(slab, n, M, ldr, H, ldh, bmu + r0, e + r0, s));
-    }
-    return DBGSOM_OK;
+    TRY_STATUS(kneighbors_workspace_check("dbgsom_neighborhood_energy", N, M, slab_rows, ws, ws_bytes, 0));
+    return euclidean_slabs(X, x_dtype, N, d, ldx, xx, W, M, ww, slab_rows, static_cast<double *>(ws), s,
+                           [&](int64_t r0, int64_t n, const double *slab, int64_t ldr) {
+                               return launch_energy_rows(slab, n, M, ldr, H, ldh, bmu + r0, e + r0, s);
+                           });
 }
 
 }  // namespace dbgsom

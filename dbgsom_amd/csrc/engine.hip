@@ -1864,8 +1864,8 @@ int dbgsom_ctx_bmu_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const in
 // prototypes under every metric, and the search itself over rows with missing entries and under metric="manhattan"
 // and metric="cosine" -- is one of two loops over chunks of rows:
 //   raw_rows_query     masked / Manhattan / cosine: kernels that read the rows as they are stored (any row pitch)
-//   placed_rows_query  Euclidean distances, neighbours, distortion, exemplars and range counts: the rows go through the
-//                      query placement first
+//   placed_rows_query  Euclidean distances, neighbours, distortion, exemplars, range counts, mixture view and combined
+//                      error: the rows go through the query placement first
 // A chunk of host rows goes up, its result is staged on the device and comes down behind the kernel; rows in HBM are
 // read where they are and the kernels write the caller's device arrays.  Both drivers synchronise before they return,
 // on error too (W_host and the rows are pageable), and end on drop_large_query_scratch.  The exported calls further
@@ -1874,16 +1874,6 @@ int dbgsom_ctx_bmu_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const in
 namespace {
 
 enum QueryOp { Q_BMU, Q_DISTANCES, Q_KNEIGHBORS, Q_DISTORTION, Q_EXEMPLARS, Q_COMBINED, Q_RANGE_COUNTS, Q_MIXTURE };
-
-// what Q_MIXTURE takes beside the rows and the prototypes (csrc/mixture.hip): the log-priors (M), c, the per-unit values
-// (M x n_values, contiguous) and the third result q (Nq x n_values, contiguous; host or device as the other two)
-struct MixtureArgs {
-    const double *logprior_host;
-    double c;
-    const double *Y_host;
-    int n_values;
-    double *q_out;
-};
 enum RowsForm { ROWS_MASKED, ROWS_MANHATTAN, ROWS_COSINE };
 
 // DBGSOM_REQUIRE under the name of the exported call `fn` (checks shared by several of them)
@@ -1941,13 +1931,8 @@ void drop_large_query_scratch(dbgsom_ctx *c) {
     if (c->mk_ws.cap + c->mk_x.cap > ((size_t)256 << 20)) {
         c->mk_ws.release(); c->mk_x.release(); c->mk_idx.release(); c->mk_dist.release();
     }
-    if (c->pd_out.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->pd_out.release();
-    if (c->kn_ws.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->kn_ws.release();
-    if (c->de_h.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->de_h.release();
-    if (c->ce_g.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->ce_g.release();
-    if (c->ce_ws.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->ce_ws.release();
-    if (c->ex_state.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->ex_state.release();
-    if (c->rc_state.cap > (size_t)DISTANCES_STAGE_BYTES / 2) c->rc_state.release();
+    for (DevBuf *b : {&c->pd_out, &c->kn_ws, &c->de_h, &c->ce_g, &c->ce_ws, &c->ex_state, &c->rc_state})
+        if (b->cap > (size_t)DISTANCES_STAGE_BYTES / 2) b->release();
 }
 
 // the end of both drivers
@@ -1959,6 +1944,19 @@ int finish_query(dbgsom_ctx *c, int rc) {
     }
     drop_large_query_scratch(c);
     return rc;
+}
+
+// Staged result rows down behind their kernel, counted as sample traffic: n x idx_vals indices (where there are any)
+// to idx_host and n x res_vals values to res_host
+static int download_rows(dbgsom_ctx *c, int64_t n, int64_t *idx_host, const int64_t *idx, int64_t idx_vals,
+                         double *res_host, const double *res, int64_t res_vals) {
+    hipError_t e = hipSuccess;
+    if (idx_vals) e = hipMemcpyAsync(idx_host, idx, (size_t)n * idx_vals * 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && res_vals)
+        e = hipMemcpyAsync(res_host, res, (size_t)n * res_vals * 8, hipMemcpyDeviceToHost, c->stream);
+    c->x_down((size_t)n * (idx_vals + res_vals) * 8);
+    if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); return DBGSOM_EHIP; }
+    return DBGSOM_OK;
 }
 
 // One raw-rows query: what it computes, on what, and the scratch that is its form's own.  What the forms do
@@ -2084,20 +2082,15 @@ int raw_rows_query(dbgsom_ctx *c, const char *fn, QueryOp op, RowsForm form, con
             }
             rc = raw_rows_launch(c, r, W, X, n, ldx, idx, res, ld_res);
             if (rc || q.on_device) continue;
-            if (op != Q_DISTANCES) {
-                e = hipMemcpyAsync(idx_out + r0 * k, idx, (size_t)n * k * 8, hipMemcpyDeviceToHost, c->stream);
-                c->x_down((size_t)n * k * 8);
-            }
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(dist_out + r0 * per_row, res, (size_t)n * per_row * 8, hipMemcpyDeviceToHost, c->stream);
-            c->x_down((size_t)n * per_row * 8);
-            if (e == hipSuccess && Xfilled_host) {
+            rc = download_rows(c, n, idx_out ? idx_out + r0 * k : nullptr, idx, op == Q_DISTANCES ? 0 : k,
+                               dist_out + r0 * per_row, res, per_row);
+            if (rc == DBGSOM_OK && Xfilled_host) {
                 if ((rc = launch_fill_missing(c->mk_x.p, x_dtype, n, d, d, W, M, d, idx, k, c->stream))) break;
                 e = hipMemcpyAsync(static_cast<char *>(Xfilled_host) + (size_t)r0 * d * es, c->mk_x.p, (size_t)n * d * es,
                                    hipMemcpyDeviceToHost, c->stream);
                 c->x_down((size_t)n * d * es);
+                if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; }
             }
-            if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; }
         }
     } while (0);
     rc = finish_query(c, rc);
@@ -2154,93 +2147,186 @@ struct CsrHost {
     int64_t nnz;
 };
 
-// The Euclidean distance matrix (csrc/distances.hip) or k nearest prototypes (csrc/kneighbors.hip: a chunk's squared
-// distances live slab by slab in kn_ws and only its n x k result exists) of rows that go through the query placement.
-// Host rows: in chunks of distances_chunk rows, each placed, its result staged (pd_out; kn_idx / kn_dist) and copied
-// down.  Rows in HBM: placed whole, and the kernels write the caller's device arrays (the matrix with rows ldo apart).
-// CSR rows (csr != nullptr): the three arrays go up whole, and chunks of rows are expanded into the dense rows the
-// kernels read.  Q_DISTORTION (csrc/distortion.hip; k = 1): the neighbours' slab and staging with the energy kernel
-// behind the product; idx_out / dist_out take a row's unit and its e, and H_host (M x M) goes up once per call.
-// Q_EXEMPLARS (csrc/exemplars.hip): every chunk folds into the state in ex_state with row0 the chunk's first row --
-// nothing per chunk is staged or copied down --, and after the last one the state is stored as the M x k result: into
-// kn_idx / kn_dist and down in one piece (M * k * 16 bytes), or into the caller's device arrays.
-// Q_RANGE_COUNTS (csrc/density.hip; k = the number of thresholds, thr_host): the thresholds go up once behind the
-// counts in rc_state, the counts are zeroed in front of the chunks and every chunk folds into them -- nothing per chunk
-// is staged or copied down --; after the last one they come down in one piece (M * k * 8 bytes) into idx_out, or are
-// copied into the caller's device array.
-// Q_MIXTURE (csrc/mixture.hip; k = 1): the neighbours' slab and staging with the mixture kernel behind the product;
-// idx_out / dist_out take a row's unit and its lse, and [the log-priors | Y] (mx: M x (1 + n_values) values) go up once
-// per call into de_h.  The third result, q (n_values per row), is staged in pd_out and comes down behind the other two.
-// Q_COMBINED (csrc/geodesics.hip; k = 2): the geodesics of the map are queued once in front of the chunks (edges_host,
-// E); a chunk's all-pairs search leaves its pairs in idx (staged: kn_idx) and its distances in ce_ws, the rows kernel
-// reads both and G and writes e (one value per row; staged: kn_dist).  The status word is read after the last chunk.
-int placed_rows_query(dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHost *csr, int x_dtype, int64_t Nq, int64_t d,
-                      const double *W_host, int64_t M, int k, int64_t *idx_out, double *dist_out, int64_t ldo,
-                      const double *H_host, int own_cell, const int32_t *edges_host = nullptr, int64_t E = 0,
-                      const double *thr_host = nullptr, const MixtureArgs *mx = nullptr) {
+// One placed-rows query: what it computes, on what, the caller's result arrays (on the host for host and CSR rows, on
+// the device for rows in HBM), the operands that are its op's own, and the layout of its result.  What the ops do
+// differently are the four switches below; a new query is a case in each.
+struct PlacedQuery {
+    QueryOp op;
+    int x_dtype;
+    int64_t d, M;
+    int k;   // Q_KNEIGHBORS; Q_COMBINED: the 2 units; Q_EXEMPLARS: rows per prototype; Q_RANGE_COUNTS: thresholds; else 1
+    int64_t *idx_out;
+    double *res_out;
+    int64_t ldo = 0;                       // Q_DISTANCES: rows of res_out are ldo apart (host calls: M)
+    const double *H_host = nullptr;        // Q_DISTORTION: M x M
+    int own_cell = 0;                      // Q_EXEMPLARS
+    const double *thr_host = nullptr;      // Q_RANGE_COUNTS: k squared radii
+    const int32_t *edges_host = nullptr;   // Q_COMBINED: E pairs of units
+    int64_t E = 0;
+    // Q_MIXTURE: the log-priors (M), c, the per-unit values Y (M x n_values, contiguous) and the third result q (Nq x
+    // n_values, contiguous; host or device as the other two)
+    const double *logprior_host = nullptr, *Y_host = nullptr;
+    double c = 0.0, *q_out = nullptr;
+    int n_values = 0;
+    int64_t dp = 0, chunk = 0;   // set by the driver: padded features; rows per chunk (rows in HBM: all of them)
+    // The layout of the result (placed_rows_layout): idx_vals indices and res_vals values per result row, and third_vals
+    // more values in a third array (q_out).  Rows from the host: the indices are staged in kn_idx, the values in
+    // res_stage, the third array in pd_out.  per_call: the result rows are the M prototypes' and exist after the last
+    // chunk only; otherwise every row of X has one and they come down chunk by chunk.
+    int64_t idx_vals = 0, res_vals = 0, third_vals = 0;
+    DevBuf *res_stage = nullptr;
+    bool per_call = false;
+};
+
+static void placed_rows_layout(dbgsom_ctx *c, PlacedQuery &p) {
+    p.idx_vals = p.res_vals = p.k;
+    p.res_stage = &c->kn_dist;
+    switch (p.op) {
+    case Q_DISTANCES: p.idx_vals = 0; p.res_vals = p.M; p.res_stage = &c->pd_out; break;   // the matrix alone
+    case Q_COMBINED: p.res_vals = 1; break;                                                 // a pair of units, one e
+    case Q_MIXTURE: p.third_vals = p.n_values; break;                                       // unit, lse and q
+    case Q_EXEMPLARS: p.per_call = true; break;                                             // M x k (row, distance) pairs
+    // the M x k counts live in rc_state and placed_rows_finish copies them out: nothing goes through the staging
+    case Q_RANGE_COUNTS: p.per_call = true; p.idx_vals = p.res_vals = 0; break;
+    default: break;   // Q_KNEIGHBORS: k and k; Q_DISTORTION (k = 1): unit and e
+    }
+}
+
+// Reserve the scratch of the op (all but the staging of its result) and do what it needs once per call, in front of
+// the chunks.  Wq: the placed prototypes.  What goes up here counts as sample traffic, one upload per op.
+static int placed_rows_setup(dbgsom_ctx *c, const PlacedQuery &p, const double *Wq) {
+    const int64_t M = p.M, slab = c->kneighbors_slab_rows;
+    switch (p.op) {
+    case Q_KNEIGHBORS:   // (csrc/kneighbors.hip) a chunk's squared distances live slab by slab in kn_ws
+        return c->kn_ws.reserve(kneighbors_workspace_bytes(p.chunk, M, slab));
+    case Q_DISTORTION:   // (csrc/distortion.hip) the neighbours' slab; H goes up into de_h
+        TRY(c->de_h.reserve((size_t)M * M * 8));
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(c->de_h.p, p.H_host, (size_t)M * M * 8, hipMemcpyHostToDevice, c->stream));
+        c->x_up((size_t)M * M * 8);
+        return c->kn_ws.reserve(kneighbors_workspace_bytes(p.chunk, M, slab));
+    case Q_MIXTURE: {   // (csrc/mixture.hip) the neighbours' slab; [the log-priors | Y] go up into de_h
+        const size_t V = (size_t)p.n_values;
+        TRY(c->de_h.reserve((size_t)M * (1 + V) * 8));
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(c->de_h.p, p.logprior_host, (size_t)M * 8, hipMemcpyHostToDevice, c->stream));
+        if (V)
+            DBGSOM_HIP_CHECK(hipMemcpyAsync(c->de_h.as<double>() + M, p.Y_host, (size_t)M * V * 8, hipMemcpyHostToDevice,
+                                            c->stream));
+        c->x_up((size_t)M * (1 + V) * 8);
+        return c->kn_ws.reserve(kneighbors_workspace_bytes(p.chunk, M, slab));
+    }
+    case Q_COMBINED:   // (csrc/geodesics.hip) the geodesics of the map are queued; a chunk's n x 2 distances go behind them
+        return queue_geodesics(c, Wq, M, p.d, p.dp, p.edges_host, p.E, (size_t)p.chunk * 16);
+    case Q_EXEMPLARS:   // (csrc/exemplars.hip) every chunk folds into the state in ex_state: [r: M x k | row: M x k]
+        TRY(c->kn_ws.reserve(exemplars_fold_workspace_bytes(p.chunk, M, p.k, slab)));
+        TRY(c->ex_state.reserve((size_t)M * p.k * 16));
+        return launch_topk_cols_init(c->ex_state.as<double>(), c->ex_state.as<int64_t>() + M * p.k, M, p.k, c->stream);
+    case Q_RANGE_COUNTS: {   // (csrc/density.hip) rc_state: [the counts, zeroed here | the thresholds, which go up]
+        const size_t counts = (size_t)M * p.k * 8;
+        TRY(c->kn_ws.reserve(range_counts_workspace_bytes(p.chunk, M, slab)));
+        TRY(c->rc_state.reserve(align_up(counts) + (size_t)p.k * 8));
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(static_cast<char *>(c->rc_state.p) + align_up(counts), p.thr_host, (size_t)p.k * 8,
+                                        hipMemcpyHostToDevice, c->stream));
+        DBGSOM_HIP_CHECK(hipMemsetAsync(c->rc_state.p, 0, counts, c->stream));
+        c->x_up((size_t)p.k * 8);
+        return DBGSOM_OK;
+    }
+    default: return DBGSOM_OK;   // Q_DISTANCES (csrc/distances.hip): no scratch
+    }
+}
+
+// Launch the op on one placed chunk: the n rows in s, rows r0 .. r0 + n - 1 of the query -> idx, res and third, the
+// chunk's part of a result with a row per row of X (a per_call result takes shape in the op's own scratch)
+static int placed_rows_launch(dbgsom_ctx *c, const PlacedQuery &p, const Samples &s, const double *Wq, const double *wwq,
+                              int64_t n, int64_t r0, int64_t *idx, double *res, double *third) {
+    const int64_t M = p.M, dp = p.dp, slab = c->kneighbors_slab_rows;
+    const double *xx = s.xx.as<double>();
+    void *ws = c->kn_ws.p;
+    const size_t cap = c->kn_ws.cap;
+    hipStream_t st = c->stream;
+    switch (p.op) {
+    case Q_DISTANCES: return launch_distances(s.Xb, s.bdtype, n, dp, dp, xx, Wq, M, wwq, res, p.ldo, st);
+    case Q_KNEIGHBORS: return launch_kneighbors(s.Xb, s.bdtype, n, dp, dp, xx, Wq, M, wwq, p.k, slab, idx, res, ws, cap, st);
+    case Q_DISTORTION:   // idx / res: a row's unit and its e
+        return launch_neighborhood_energy(s.Xb, s.bdtype, n, dp, dp, xx, Wq, M, wwq, c->de_h.as<double>(), M, slab, idx, res,
+                                          ws, cap, st);
+    case Q_MIXTURE: {   // idx / res: a row's unit and its lse; third: its q, n_values apart
+        const double *a = c->de_h.as<double>();
+        const int V = p.n_values;
+        return launch_mixture(s.Xb, s.bdtype, n, dp, dp, xx, Wq, M, wwq, a, p.c, V ? a + M : nullptr, V, V, slab, idx, res,
+                              third, V, ws, cap, st);
+    }
+    case Q_COMBINED: {   // the all-pairs search leaves the chunk's pairs in idx and its distances in ce_ws; the rows
+                         // kernel reads both and G and writes e
+        const GeoScratch g = carve_geodesics(c, p.E);
+        double *d2 = reinterpret_cast<double *>(g.tail);
+        TRY(launch_bmu(s.Xb, s.bdtype, n, dp, dp, xx, Wq, M, wwq, 2, 0, idx, d2, st));
+        return launch_combined_error_rows(idx, d2, 2, n, c->ce_g.as<double>(), M, M, res, g.status, st);
+    }
+    case Q_EXEMPLARS:   // row0 = the chunk's first row
+        return launch_exemplars_fold(s.Xb, s.bdtype, n, dp, dp, xx, Wq, M, wwq, p.k, p.own_cell, slab, r0,
+                                     c->ex_state.as<double>(), c->ex_state.as<int64_t>() + M * p.k, ws, cap, st);
+    case Q_RANGE_COUNTS: {
+        const double *thr = reinterpret_cast<const double *>(static_cast<char *>(c->rc_state.p) + align_up((size_t)M * p.k * 8));
+        return launch_range_counts_fold(s.Xb, s.bdtype, n, dp, dp, xx, Wq, M, wwq, thr, p.k, slab, c->rc_state.as<int64_t>(),
+                                        ws, cap, st);
+    }
+    default: return DBGSOM_OK;
+    }
+}
+
+// After the last chunk.  idx / res: where M rows of a per_call result go (staged: the staging, which then comes down
+// in one piece; else the caller's device arrays).
+static int placed_rows_finish(dbgsom_ctx *c, const PlacedQuery &p, bool staged, int64_t *idx, double *res) {
+    const int64_t M = p.M;
+    switch (p.op) {
+    case Q_COMBINED:   // what the geodesics and the rows kernels found
+        return geodesics_status("dbgsom_ctx_combined_error_query", carve_geodesics(c, p.E).status, M, c->stream);
+    case Q_EXEMPLARS:   // the state as the M x k result
+        TRY(launch_exemplars_store(c->ex_state.as<double>(), c->ex_state.as<int64_t>() + M * p.k, M, p.k, idx, res, c->stream));
+        return staged ? download_rows(c, M, p.idx_out, idx, p.k, p.res_out, res, p.k) : DBGSOM_OK;
+    case Q_RANGE_COUNTS:   // the counts, from where they were folded
+        if (staged) return download_rows(c, M, p.idx_out, c->rc_state.as<int64_t>(), p.k, nullptr, nullptr, 0);
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(p.idx_out, c->rc_state.p, (size_t)M * p.k * 8, hipMemcpyDeviceToDevice, c->stream));
+        return DBGSOM_OK;
+    default: return DBGSOM_OK;
+    }
+}
+
+// One Euclidean query of rows that go through the query placement.  Host rows: in chunks of distances_chunk rows, each
+// placed, its result rows staged and copied down behind the kernels.  Rows in HBM: placed whole, and the kernels write
+// the caller's device arrays.  CSR rows (csr != nullptr): the three arrays go up whole, and chunks of rows are
+// expanded into the dense rows the kernels read.  What is launched, on which scratch, is the op's (the switches
+// above); where result rows go and what comes down is read off the layout.
+int placed_rows_query(dbgsom_ctx *c, PlacedQuery &p, const QueryRows &q, const CsrHost *csr, int64_t Nq, const double *W_host) {
     Samples &s = c->xq;
     DevBuf Wq, wwq;
-    const int64_t dp = pad16(d);
+    const int x_dtype = p.x_dtype;
+    const int64_t d = p.d, dp = p.dp = pad16(d);
     const size_t es = dtype_size(x_dtype);
-    const bool staged = !q.on_device, knn = op != Q_DISTANCES;   // (knn: a slab per chunk, k values per row and array)
-    const bool cols = op == Q_EXEMPLARS;                         // (the result is M x k, after the last chunk)
-    const bool range = op == Q_RANGE_COUNTS;                     // (likewise: M x k counts)
-    const size_t rc_bytes = (size_t)M * k * 8;
-    const int64_t chunk = staged ? distances_chunk(c, Nq, M, dp * (int64_t)es) : Nq;
-    const bool comb = op == Q_COMBINED;
-    const int64_t per_row = comb ? 1 : (knn ? k : M);   // values of a row's result (beside its k indices)
+    const bool staged = !q.on_device;
+    p.chunk = staged ? distances_chunk(c, Nq, p.M, dp * (int64_t)es) : Nq;
+    placed_rows_layout(c, p);
+    const bool down = staged && !p.per_call;                              // result rows come down chunk by chunk
+    const size_t stage_rows = !staged ? 0 : (p.per_call ? p.M : p.chunk);   // result rows that are staged at a time
     int rc = DBGSOM_OK;
     do {
         if (csr) {
             s.release();
             if ((rc = upload_csr_arrays(c, s, csr->indptr, csr->indices, q.p, x_dtype, Nq, csr->nnz))) break;
             c->x_up((size_t)csr->nnz * (4 + es) + (size_t)(Nq + 1) * 8);
-            if ((rc = s.own.reserve((size_t)chunk * dp * es))) break;
+            if ((rc = s.own.reserve((size_t)p.chunk * dp * es))) break;
         }
-        if ((rc = place_query_weights(c, Wq, wwq, W_host, M, d, dp))) break;
-        if (op == Q_DISTORTION) {
-            if ((rc = c->de_h.reserve((size_t)M * M * 8))) break;
-            const hipError_t e = hipMemcpyAsync(c->de_h.p, H_host, (size_t)M * M * 8, hipMemcpyHostToDevice, c->stream);
-            if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
-            c->x_up((size_t)M * M * 8);
-        }
-        if (op == Q_MIXTURE) {
-            const int V = mx->n_values;
-            if ((rc = c->de_h.reserve((size_t)M * (1 + V) * 8))) break;
-            hipError_t e = hipMemcpyAsync(c->de_h.p, mx->logprior_host, (size_t)M * 8, hipMemcpyHostToDevice, c->stream);
-            if (e == hipSuccess && V)
-                e = hipMemcpyAsync(c->de_h.as<double>() + M, mx->Y_host, (size_t)M * V * 8, hipMemcpyHostToDevice, c->stream);
-            if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
-            c->x_up((size_t)M * (1 + V) * 8);
-            if (staged && V && (rc = c->pd_out.reserve((size_t)chunk * V * 8))) break;
-        }
-        if (comb) {
-            if ((rc = queue_geodesics(c, Wq.as<double>(), M, d, dp, edges_host, E, (size_t)chunk * 16))) break;
-            if (staged && (rc = c->kn_idx.reserve((size_t)chunk * 16))) break;
-            if (staged && (rc = c->kn_dist.reserve((size_t)chunk * 8))) break;
-        } else if (range) {
-            if ((rc = c->kn_ws.reserve(range_counts_workspace_bytes(chunk, M, c->kneighbors_slab_rows)))) break;
-            if ((rc = c->rc_state.reserve(align_up(rc_bytes) + (size_t)k * 8))) break;
-            hipError_t e = hipMemcpyAsync(static_cast<char *>(c->rc_state.p) + align_up(rc_bytes), thr_host, (size_t)k * 8,
-                                          hipMemcpyHostToDevice, c->stream);
-            if (e == hipSuccess) e = hipMemsetAsync(c->rc_state.p, 0, rc_bytes, c->stream);
-            if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
-            c->x_up((size_t)k * 8);
-        } else if (cols) {
-            if ((rc = c->kn_ws.reserve(exemplars_fold_workspace_bytes(chunk, M, k, c->kneighbors_slab_rows)))) break;
-            if ((rc = c->ex_state.reserve((size_t)M * k * 16))) break;
-            if (staged && (rc = c->kn_idx.reserve((size_t)M * k * 8))) break;
-            if (staged && (rc = c->kn_dist.reserve((size_t)M * k * 8))) break;
-            if ((rc = launch_topk_cols_init(c->ex_state.as<double>(), c->ex_state.as<int64_t>() + M * k, M, k, c->stream))) break;
-        } else if (knn) {
-            if ((rc = c->kn_ws.reserve(kneighbors_workspace_bytes(chunk, M, c->kneighbors_slab_rows)))) break;
-            if (staged && (rc = c->kn_idx.reserve((size_t)chunk * k * 8))) break;
-            if (staged && (rc = c->kn_dist.reserve((size_t)chunk * k * 8))) break;
-        } else if (staged && (rc = c->pd_out.reserve((size_t)chunk * M * 8))) {
-            break;
-        }
-        for (int64_t r0 = 0; r0 < Nq && rc == DBGSOM_OK; r0 += chunk) {
-            const int64_t n = std::min(chunk, Nq - r0);
+        if ((rc = place_query_weights(c, Wq, wwq, W_host, p.M, d, dp))) break;
+        if ((rc = placed_rows_setup(c, p, Wq.as<double>()))) break;
+        if ((rc = c->kn_idx.reserve(stage_rows * p.idx_vals * 8))) break;
+        if ((rc = p.res_stage->reserve(stage_rows * p.res_vals * 8))) break;
+        if ((rc = c->pd_out.reserve(stage_rows * p.third_vals * 8))) break;
+        // (rows in HBM are one chunk: the caller's arrays are written from their first row)
+        int64_t *idx = staged ? c->kn_idx.as<int64_t>() : p.idx_out;
+        double *res = staged ? p.res_stage->as<double>() : p.res_out;
+        double *third = !p.third_vals ? nullptr : (staged ? c->pd_out.as<double>() : p.q_out);
+        for (int64_t r0 = 0; r0 < Nq && rc == DBGSOM_OK; r0 += p.chunk) {
+            const int64_t n = std::min(p.chunk, Nq - r0);
             if (csr) {
                 const CsrView rows{s.indptr.as<int64_t>() + r0, s.indices.as<int32_t>(), s.data.p};   // (indptr is absolute)
                 if ((rc = launch_csr_densify(rows, x_dtype, n, d, dp, s.own.p, c->stream))) break;
@@ -2252,81 +2338,19 @@ int placed_rows_query(dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHo
             } else {
                 rc = place_host_samples(c, s, static_cast<const char *>(q.p) + (size_t)r0 * d * es, x_dtype, n, d, x_dtype);
             }
-            if (rc) break;
-            int64_t *idx = staged ? c->kn_idx.as<int64_t>() : idx_out;
-            double *res = !staged ? dist_out : (knn ? c->kn_dist.as<double>() : c->pd_out.as<double>());
-            if (range) {
-                const double *thr = reinterpret_cast<const double *>(static_cast<char *>(c->rc_state.p) + align_up(rc_bytes));
-                rc = launch_range_counts_fold(s.Xb, s.bdtype, n, dp, dp, s.xx.as<double>(), Wq.as<double>(), M, wwq.as<double>(),
-                                              thr, k, c->kneighbors_slab_rows, c->rc_state.as<int64_t>(), c->kn_ws.p,
-                                              c->kn_ws.cap, c->stream);
-                continue;
-            }
-            if (cols) {
-                rc = launch_exemplars_fold(s.Xb, s.bdtype, n, dp, dp, s.xx.as<double>(), Wq.as<double>(), M, wwq.as<double>(), k,
-                                           own_cell, c->kneighbors_slab_rows, r0, c->ex_state.as<double>(),
-                                           c->ex_state.as<int64_t>() + M * k, c->kn_ws.p, c->kn_ws.cap, c->stream);
-                continue;
-            }
-            if (comb) {
-                const GeoScratch g = carve_geodesics(c, E);
-                double *d2 = reinterpret_cast<double *>(g.tail);
-                rc = launch_bmu(s.Xb, s.bdtype, n, dp, dp, s.xx.as<double>(), Wq.as<double>(), M, wwq.as<double>(), 2, 0, idx,
-                                d2, c->stream);
-                if (rc == DBGSOM_OK)
-                    rc = launch_combined_error_rows(idx, d2, 2, n, c->ce_g.as<double>(), M, M, res, g.status, c->stream);
-            } else if (op == Q_DISTORTION)
-                rc = launch_neighborhood_energy(s.Xb, s.bdtype, n, dp, dp, s.xx.as<double>(), Wq.as<double>(), M,
-                                                wwq.as<double>(), c->de_h.as<double>(), M, c->kneighbors_slab_rows, idx, res,
-                                                c->kn_ws.p, c->kn_ws.cap, c->stream);
-            else if (op == Q_MIXTURE) {
-                const int V = mx->n_values;   // (rows in HBM are one chunk: q_out is written from its first row)
-                double *qd = !V ? nullptr : (staged ? c->pd_out.as<double>() : mx->q_out);
-                rc = launch_mixture(s.Xb, s.bdtype, n, dp, dp, s.xx.as<double>(), Wq.as<double>(), M, wwq.as<double>(),
-                                    c->de_h.as<double>(), mx->c, V ? c->de_h.as<double>() + M : nullptr, V, V,
-                                    c->kneighbors_slab_rows, idx, res, qd, V, c->kn_ws.p, c->kn_ws.cap, c->stream);
-            } else if (knn)
-                rc = launch_kneighbors(s.Xb, s.bdtype, n, dp, dp, s.xx.as<double>(), Wq.as<double>(), M, wwq.as<double>(), k,
-                                       c->kneighbors_slab_rows, idx, res, c->kn_ws.p, c->kn_ws.cap, c->stream);
-            else
-                rc = launch_distances(s.Xb, s.bdtype, n, dp, dp, s.xx.as<double>(), Wq.as<double>(), M, wwq.as<double>(), res,
-                                      staged ? M : ldo, c->stream);
-            if (rc || !staged) continue;
-            hipError_t e = hipSuccess;
-            if (knn) e = hipMemcpyAsync(idx_out + r0 * k, idx, (size_t)n * k * 8, hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(dist_out + r0 * per_row, res, (size_t)n * per_row * 8, hipMemcpyDeviceToHost, c->stream);
-            if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; }
-            c->x_down(comb ? (size_t)n * 24 : (size_t)n * per_row * (knn ? 16 : 8));
-            if (op == Q_MIXTURE && mx->n_values && rc == DBGSOM_OK) {
-                const size_t qb = (size_t)n * mx->n_values * 8;
-                e = hipMemcpyAsync(mx->q_out + r0 * mx->n_values, c->pd_out.p, qb, hipMemcpyDeviceToHost, c->stream);
-                if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; }
-                c->x_down(qb);
-            }
+            if (rc == DBGSOM_OK) rc = placed_rows_launch(c, p, s, Wq.as<double>(), wwq.as<double>(), n, r0, idx, res, third);
+            if (rc == DBGSOM_OK && down)
+                rc = download_rows(c, n, p.idx_out + r0 * p.idx_vals, idx, p.idx_vals, p.res_out + r0 * p.res_vals, res,
+                                   p.res_vals);
+            if (rc == DBGSOM_OK && down && p.third_vals)
+                rc = download_rows(c, n, nullptr, nullptr, 0, p.q_out + r0 * p.third_vals, third, p.third_vals);
         }
-        if (rc == DBGSOM_OK && comb) rc = geodesics_status("dbgsom_ctx_combined_error_query", carve_geodesics(c, E).status, M, c->stream);
-        if (rc == DBGSOM_OK && range) {
-            const hipError_t e = hipMemcpyAsync(idx_out, c->rc_state.p, rc_bytes,
-                                                staged ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream);
-            if (e != hipSuccess) { set_error("copy of the counts failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; }
-            if (staged) c->x_down(rc_bytes);
-        }
-        if (rc || !cols) break;
-        int64_t *idx = staged ? c->kn_idx.as<int64_t>() : idx_out;
-        double *res = staged ? c->kn_dist.as<double>() : dist_out;
-        if ((rc = launch_exemplars_store(c->ex_state.as<double>(), c->ex_state.as<int64_t>() + M * k, M, k, idx, res, c->stream)))
-            break;
-        if (!staged) break;
-        hipError_t e = hipMemcpyAsync(idx_out, idx, (size_t)M * k * 8, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dist_out, res, (size_t)M * k * 8, hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; }
-        c->x_down((size_t)M * k * 16);
+        if (rc == DBGSOM_OK) rc = placed_rows_finish(c, p, staged, idx, res);
     } while (0);
     rc = finish_query(c, rc);
     Wq.release(); wwq.release();
     if (csr) s.release();
-    else drop_query_rows(s, q, chunk * dp * (int64_t)es);
+    else drop_query_rows(s, q, p.chunk * dp * (int64_t)es);
     return rc;
 }
 
@@ -2357,34 +2381,28 @@ int raw_rows_checked(const char *fn, dbgsom_ctx *c, QueryOp op, RowsForm form, c
     return raw_rows_query(c, fn, op, form, q, x_dtype, Nq, d, W_host, M, k, idx_out, dist_out, ldo, nullptr);
 }
 
-// the Euclidean distance matrix, k nearest prototypes, distortion and exemplars of dense rows (csr == nullptr) or host
-// CSR rows
-int placed_rows_checked(const char *fn, dbgsom_ctx *c, QueryOp op, const QueryRows &q, const CsrHost *csr, int x_dtype, int64_t Nq,
-                        int64_t d, const double *W_host, int64_t M, int k, int64_t *idx_out, double *dist_out, int64_t ldo,
-                        const double *H_host = nullptr, int own_cell = 0, const int32_t *edges_host = nullptr, int64_t E = 0,
-                        const double *thr_host = nullptr, const MixtureArgs *mx = nullptr) {
-    TRY(query_args(fn, c, op, x_dtype, csr != nullptr, Nq, d, M, k));
-    if (op == Q_MIXTURE) {
-        REQUIRE_FN(fn, mx->n_values >= 0 && mx->n_values <= DBGSOM_MAX_MIXTURE_VALUES,
-                   "need 0 <= n_values <= DBGSOM_MAX_MIXTURE_VALUES");
-        REQUIRE_FN(fn, mx->c >= 0.0, "c must be >= 0");   // (NaN fails)
-    }
-    if (op == Q_COMBINED) REQUIRE_FN(fn, E >= 0 && E <= 0x7fffffff, "need 0 <= E < 2^31");
-    if (q.on_device) REQUIRE_FN(fn, q.ldx >= d, "ldx must be >= d");
-    if (op == Q_DISTANCES) REQUIRE_FN(fn, ldo >= M, "ldo must be >= M");
+// every Euclidean query of dense rows (csr == nullptr) or host CSR rows
+int placed_rows_checked(const char *fn, dbgsom_ctx *c, PlacedQuery p, const QueryRows &q, const CsrHost *csr, int64_t Nq,
+                        const double *W_host) {
+    const QueryOp op = p.op;
+    TRY(query_args(fn, c, op, p.x_dtype, csr != nullptr, Nq, p.d, p.M, p.k));
+    // (an op that does not take an operand leaves it at its default, which passes)
+    REQUIRE_FN(fn, p.n_values >= 0 && p.n_values <= DBGSOM_MAX_MIXTURE_VALUES, "need 0 <= n_values <= DBGSOM_MAX_MIXTURE_VALUES");
+    REQUIRE_FN(fn, p.c >= 0.0, "c must be >= 0");   // (NaN fails)
+    REQUIRE_FN(fn, p.E >= 0 && p.E <= 0x7fffffff, "need 0 <= E < 2^31");
+    if (q.on_device) REQUIRE_FN(fn, q.ldx >= p.d, "ldx must be >= d");
+    if (op == Q_DISTANCES) REQUIRE_FN(fn, p.ldo >= p.M, "ldo must be >= M");
     if (csr) {
         REQUIRE_FN(fn, csr->indptr && csr->nnz >= 0 && (csr->nnz == 0 || (csr->indices && q.p)), "bad arguments");
-        TRY(dbgsom_csr_check(csr->indptr, csr->indices, Nq, d, csr->nnz));
+        TRY(dbgsom_csr_check(csr->indptr, csr->indices, Nq, p.d, csr->nnz));
     }
     if (Nq == 0) return DBGSOM_OK;
-    REQUIRE_FN(fn, (csr || q.p) && W_host && (op == Q_DISTANCES || idx_out) && (op == Q_RANGE_COUNTS || dist_out), "null pointer");
-    if (op == Q_RANGE_COUNTS) REQUIRE_FN(fn, thr_host, "null pointer");
-    if (op == Q_DISTORTION) REQUIRE_FN(fn, H_host, "null pointer");
-    if (op == Q_MIXTURE) REQUIRE_FN(fn, mx->logprior_host && (mx->n_values == 0 || (mx->Y_host && mx->q_out)), "null pointer");
-    if (op == Q_COMBINED) REQUIRE_FN(fn, E == 0 || edges_host, "null pointer");
+    REQUIRE_FN(fn, (csr || q.p) && W_host && (op == Q_DISTANCES || p.idx_out) && (op == Q_RANGE_COUNTS || p.res_out),
+               "null pointer");
+    REQUIRE_FN(fn, (op != Q_RANGE_COUNTS || p.thr_host) && (op != Q_DISTORTION || p.H_host) && (p.E == 0 || p.edges_host) &&
+                       (op != Q_MIXTURE || (p.logprior_host && (p.n_values == 0 || (p.Y_host && p.q_out)))), "null pointer");
     SET_DEVICE(c);
-    return placed_rows_query(c, op, q, csr, x_dtype, Nq, d, W_host, M, k, idx_out, dist_out, ldo, H_host, own_cell, edges_host,
-                             E, thr_host, mx);
+    return placed_rows_query(c, p, q, csr, Nq, W_host);
 }
 
 }  // namespace
@@ -2416,42 +2434,45 @@ int dbgsom_ctx_kneighbors_query_masked(dbgsom_ctx *c, const void *Xq_host, int x
 // ------------------------------------------------------------------------------------------
 int dbgsom_ctx_distances_query(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
                                const double *W_host, int64_t M, double *out_host) {
-    return placed_rows_checked(__func__, c, Q_DISTANCES, QueryRows{Xq_host, false, d}, nullptr, x_dtype, Nq, d, W_host, M,
-                               1, nullptr, out_host, M);
+    PlacedQuery p{Q_DISTANCES, x_dtype, d, M, 1, nullptr, out_host};
+    p.ldo = M;
+    return placed_rows_checked(__func__, c, p, QueryRows{Xq_host, false, d}, nullptr, Nq, W_host);
 }
 
 int dbgsom_ctx_distances_query_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d, int64_t ldx,
                                       const double *W_host, int64_t M, double *out_dev, int64_t ldo) {
-    return placed_rows_checked(__func__, c, Q_DISTANCES, QueryRows{Xq_dev, true, ldx}, nullptr, x_dtype, Nq, d, W_host, M,
-                               1, nullptr, out_dev, ldo);
+    PlacedQuery p{Q_DISTANCES, x_dtype, d, M, 1, nullptr, out_dev};
+    p.ldo = ldo;
+    return placed_rows_checked(__func__, c, p, QueryRows{Xq_dev, true, ldx}, nullptr, Nq, W_host);
 }
 
 int dbgsom_ctx_distances_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const int32_t *indices_host,
                                    const void *data_host, int x_dtype, int64_t Nq, int64_t d, int64_t nnz,
                                    const double *W_host, int64_t M, double *out_host) {
     const CsrHost csr{indptr_host, indices_host, nnz};
-    return placed_rows_checked(__func__, c, Q_DISTANCES, QueryRows{data_host, false, d}, &csr, x_dtype, Nq, d, W_host, M,
-                               1, nullptr, out_host, M);
+    PlacedQuery p{Q_DISTANCES, x_dtype, d, M, 1, nullptr, out_host};
+    p.ldo = M;
+    return placed_rows_checked(__func__, c, p, QueryRows{data_host, false, d}, &csr, Nq, W_host);
 }
 
 int dbgsom_ctx_kneighbors_query(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
                                 const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host) {
-    return placed_rows_checked(__func__, c, Q_KNEIGHBORS, QueryRows{Xq_host, false, d}, nullptr, x_dtype, Nq, d, W_host, M,
-                               k, idx_host, dist_host, 0);
+    const PlacedQuery p{Q_KNEIGHBORS, x_dtype, d, M, k, idx_host, dist_host};
+    return placed_rows_checked(__func__, c, p, QueryRows{Xq_host, false, d}, nullptr, Nq, W_host);
 }
 
 int dbgsom_ctx_kneighbors_query_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d, int64_t ldx,
                                        const double *W_host, int64_t M, int k, int64_t *idx_dev, double *dist_dev) {
-    return placed_rows_checked(__func__, c, Q_KNEIGHBORS, QueryRows{Xq_dev, true, ldx}, nullptr, x_dtype, Nq, d, W_host, M,
-                               k, idx_dev, dist_dev, 0);
+    const PlacedQuery p{Q_KNEIGHBORS, x_dtype, d, M, k, idx_dev, dist_dev};
+    return placed_rows_checked(__func__, c, p, QueryRows{Xq_dev, true, ldx}, nullptr, Nq, W_host);
 }
 
 int dbgsom_ctx_kneighbors_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const int32_t *indices_host,
                                     const void *data_host, int x_dtype, int64_t Nq, int64_t d, int64_t nnz,
                                     const double *W_host, int64_t M, int k, int64_t *idx_host, double *dist_host) {
     const CsrHost csr{indptr_host, indices_host, nnz};
-    return placed_rows_checked(__func__, c, Q_KNEIGHBORS, QueryRows{data_host, false, d}, &csr, x_dtype, Nq, d, W_host, M,
-                               k, idx_host, dist_host, 0);
+    const PlacedQuery p{Q_KNEIGHBORS, x_dtype, d, M, k, idx_host, dist_host};
+    return placed_rows_checked(__func__, c, p, QueryRows{data_host, false, d}, &csr, Nq, W_host);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2459,15 +2480,17 @@ int dbgsom_ctx_kneighbors_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, c
 // ------------------------------------------------------------------------------------------
 int dbgsom_ctx_distortion_query(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
                                 const double *W_host, int64_t M, const double *H_host, int64_t *bmu_host, double *e_host) {
-    return placed_rows_checked(__func__, c, Q_DISTORTION, QueryRows{Xq_host, false, d}, nullptr, x_dtype, Nq, d, W_host, M,
-                               1, bmu_host, e_host, 0, H_host);
+    PlacedQuery p{Q_DISTORTION, x_dtype, d, M, 1, bmu_host, e_host};
+    p.H_host = H_host;
+    return placed_rows_checked(__func__, c, p, QueryRows{Xq_host, false, d}, nullptr, Nq, W_host);
 }
 
 int dbgsom_ctx_distortion_query_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d, int64_t ldx,
                                        const double *W_host, int64_t M, const double *H_host, int64_t *bmu_dev,
                                        double *e_dev) {
-    return placed_rows_checked(__func__, c, Q_DISTORTION, QueryRows{Xq_dev, true, ldx}, nullptr, x_dtype, Nq, d, W_host, M,
-                               1, bmu_dev, e_dev, 0, H_host);
+    PlacedQuery p{Q_DISTORTION, x_dtype, d, M, 1, bmu_dev, e_dev};
+    p.H_host = H_host;
+    return placed_rows_checked(__func__, c, p, QueryRows{Xq_dev, true, ldx}, nullptr, Nq, W_host);
 }
 
 int dbgsom_ctx_distortion_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const int32_t *indices_host,
@@ -2475,8 +2498,9 @@ int dbgsom_ctx_distortion_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, c
                                     const double *W_host, int64_t M, const double *H_host, int64_t *bmu_host,
                                     double *e_host) {
     const CsrHost csr{indptr_host, indices_host, nnz};
-    return placed_rows_checked(__func__, c, Q_DISTORTION, QueryRows{data_host, false, d}, &csr, x_dtype, Nq, d, W_host, M,
-                               1, bmu_host, e_host, 0, H_host);
+    PlacedQuery p{Q_DISTORTION, x_dtype, d, M, 1, bmu_host, e_host};
+    p.H_host = H_host;
+    return placed_rows_checked(__func__, c, p, QueryRows{data_host, false, d}, &csr, Nq, W_host);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2484,15 +2508,17 @@ int dbgsom_ctx_distortion_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, c
 // ------------------------------------------------------------------------------------------
 int dbgsom_ctx_exemplars_query(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d, const double *W_host,
                                int64_t M, int k, int own_cell, int64_t *idx_host, double *dist_host) {
-    return placed_rows_checked(__func__, c, Q_EXEMPLARS, QueryRows{Xq_host, false, d}, nullptr, x_dtype, Nq, d, W_host, M, k,
-                               idx_host, dist_host, 0, nullptr, own_cell);
+    PlacedQuery p{Q_EXEMPLARS, x_dtype, d, M, k, idx_host, dist_host};
+    p.own_cell = own_cell;
+    return placed_rows_checked(__func__, c, p, QueryRows{Xq_host, false, d}, nullptr, Nq, W_host);
 }
 
 int dbgsom_ctx_exemplars_query_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d, int64_t ldx,
                                       const double *W_host, int64_t M, int k, int own_cell, int64_t *idx_dev,
                                       double *dist_dev) {
-    return placed_rows_checked(__func__, c, Q_EXEMPLARS, QueryRows{Xq_dev, true, ldx}, nullptr, x_dtype, Nq, d, W_host, M, k,
-                               idx_dev, dist_dev, 0, nullptr, own_cell);
+    PlacedQuery p{Q_EXEMPLARS, x_dtype, d, M, k, idx_dev, dist_dev};
+    p.own_cell = own_cell;
+    return placed_rows_checked(__func__, c, p, QueryRows{Xq_dev, true, ldx}, nullptr, Nq, W_host);
 }
 
 int dbgsom_ctx_exemplars_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const int32_t *indices_host,
@@ -2500,8 +2526,9 @@ int dbgsom_ctx_exemplars_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, co
                                    const double *W_host, int64_t M, int k, int own_cell, int64_t *idx_host,
                                    double *dist_host) {
     const CsrHost csr{indptr_host, indices_host, nnz};
-    return placed_rows_checked(__func__, c, Q_EXEMPLARS, QueryRows{data_host, false, d}, &csr, x_dtype, Nq, d, W_host, M, k,
-                               idx_host, dist_host, 0, nullptr, own_cell);
+    PlacedQuery p{Q_EXEMPLARS, x_dtype, d, M, k, idx_host, dist_host};
+    p.own_cell = own_cell;
+    return placed_rows_checked(__func__, c, p, QueryRows{data_host, false, d}, &csr, Nq, W_host);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2509,15 +2536,17 @@ int dbgsom_ctx_exemplars_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, co
 // ------------------------------------------------------------------------------------------
 int dbgsom_ctx_range_counts_query(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d, const double *W_host,
                                   int64_t M, const double *thr_host, int n_radii, int64_t *counts_host) {
-    return placed_rows_checked(__func__, c, Q_RANGE_COUNTS, QueryRows{Xq_host, false, d}, nullptr, x_dtype, Nq, d, W_host, M,
-                               n_radii, counts_host, nullptr, 0, nullptr, 0, nullptr, 0, thr_host);
+    PlacedQuery p{Q_RANGE_COUNTS, x_dtype, d, M, n_radii, counts_host, nullptr};
+    p.thr_host = thr_host;
+    return placed_rows_checked(__func__, c, p, QueryRows{Xq_host, false, d}, nullptr, Nq, W_host);
 }
 
 int dbgsom_ctx_range_counts_query_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d, int64_t ldx,
                                          const double *W_host, int64_t M, const double *thr_host, int n_radii,
                                          int64_t *counts_dev) {
-    return placed_rows_checked(__func__, c, Q_RANGE_COUNTS, QueryRows{Xq_dev, true, ldx}, nullptr, x_dtype, Nq, d, W_host, M,
-                               n_radii, counts_dev, nullptr, 0, nullptr, 0, nullptr, 0, thr_host);
+    PlacedQuery p{Q_RANGE_COUNTS, x_dtype, d, M, n_radii, counts_dev, nullptr};
+    p.thr_host = thr_host;
+    return placed_rows_checked(__func__, c, p, QueryRows{Xq_dev, true, ldx}, nullptr, Nq, W_host);
 }
 
 int dbgsom_ctx_range_counts_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const int32_t *indices_host,
@@ -2525,8 +2554,9 @@ int dbgsom_ctx_range_counts_query_csr(dbgsom_ctx *c, const int64_t *indptr_host,
                                       const double *W_host, int64_t M, const double *thr_host, int n_radii,
                                       int64_t *counts_host) {
     const CsrHost csr{indptr_host, indices_host, nnz};
-    return placed_rows_checked(__func__, c, Q_RANGE_COUNTS, QueryRows{data_host, false, d}, &csr, x_dtype, Nq, d, W_host, M,
-                               n_radii, counts_host, nullptr, 0, nullptr, 0, nullptr, 0, thr_host);
+    PlacedQuery p{Q_RANGE_COUNTS, x_dtype, d, M, n_radii, counts_host, nullptr};
+    p.thr_host = thr_host;
+    return placed_rows_checked(__func__, c, p, QueryRows{data_host, false, d}, &csr, Nq, W_host);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2535,17 +2565,17 @@ int dbgsom_ctx_range_counts_query_csr(dbgsom_ctx *c, const int64_t *indptr_host,
 int dbgsom_ctx_mixture_query(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d, const double *W_host,
                              int64_t M, const double *logprior_host, double cc, const double *Y_host, int n_values,
                              int64_t *unit_host, double *lse_host, double *q_host) {
-    const MixtureArgs mx{logprior_host, cc, Y_host, n_values, q_host};
-    return placed_rows_checked(__func__, c, Q_MIXTURE, QueryRows{Xq_host, false, d}, nullptr, x_dtype, Nq, d, W_host, M, 1,
-                               unit_host, lse_host, 0, nullptr, 0, nullptr, 0, nullptr, &mx);
+    PlacedQuery p{Q_MIXTURE, x_dtype, d, M, 1, unit_host, lse_host};
+    p.logprior_host = logprior_host; p.c = cc; p.Y_host = Y_host; p.n_values = n_values; p.q_out = q_host;
+    return placed_rows_checked(__func__, c, p, QueryRows{Xq_host, false, d}, nullptr, Nq, W_host);
 }
 
 int dbgsom_ctx_mixture_query_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d, int64_t ldx,
                                     const double *W_host, int64_t M, const double *logprior_host, double cc,
                                     const double *Y_host, int n_values, int64_t *unit_dev, double *lse_dev, double *q_dev) {
-    const MixtureArgs mx{logprior_host, cc, Y_host, n_values, q_dev};
-    return placed_rows_checked(__func__, c, Q_MIXTURE, QueryRows{Xq_dev, true, ldx}, nullptr, x_dtype, Nq, d, W_host, M, 1,
-                               unit_dev, lse_dev, 0, nullptr, 0, nullptr, 0, nullptr, &mx);
+    PlacedQuery p{Q_MIXTURE, x_dtype, d, M, 1, unit_dev, lse_dev};
+    p.logprior_host = logprior_host; p.c = cc; p.Y_host = Y_host; p.n_values = n_values; p.q_out = q_dev;
+    return placed_rows_checked(__func__, c, p, QueryRows{Xq_dev, true, ldx}, nullptr, Nq, W_host);
 }
 
 int dbgsom_ctx_mixture_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const int32_t *indices_host,
@@ -2553,9 +2583,9 @@ int dbgsom_ctx_mixture_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, cons
                                  int64_t M, const double *logprior_host, double cc, const double *Y_host, int n_values,
                                  int64_t *unit_host, double *lse_host, double *q_host) {
     const CsrHost csr{indptr_host, indices_host, nnz};
-    const MixtureArgs mx{logprior_host, cc, Y_host, n_values, q_host};
-    return placed_rows_checked(__func__, c, Q_MIXTURE, QueryRows{data_host, false, d}, &csr, x_dtype, Nq, d, W_host, M, 1,
-                               unit_host, lse_host, 0, nullptr, 0, nullptr, 0, nullptr, &mx);
+    PlacedQuery p{Q_MIXTURE, x_dtype, d, M, 1, unit_host, lse_host};
+    p.logprior_host = logprior_host; p.c = cc; p.Y_host = Y_host; p.n_values = n_values; p.q_out = q_host;
+    return placed_rows_checked(__func__, c, p, QueryRows{data_host, false, d}, &csr, Nq, W_host);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2574,11 +2604,7 @@ int dbgsom_ctx_geodesics(dbgsom_ctx *c, const double *W_host, int64_t M, int64_t
     int rc = place_query_weights(c, Wq, wwq, W_host, M, d, dp);
     if (rc == DBGSOM_OK) rc = queue_geodesics(c, Wq.as<double>(), M, d, dp, edges_host, E, 0);
     if (rc == DBGSOM_OK) rc = geodesics_status(__func__, carve_geodesics(c, E).status, M, c->stream);
-    if (rc == DBGSOM_OK) {
-        const hipError_t e = hipMemcpyAsync(G_host, c->ce_g.p, (size_t)M * M * 8, hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; }
-        c->x_down((size_t)M * M * 8);
-    }
+    if (rc == DBGSOM_OK) rc = download_rows(c, M, nullptr, nullptr, 0, G_host, c->ce_g.as<double>(), M);
     rc = finish_query(c, rc);
     Wq.release(); wwq.release();
     return rc;
@@ -2587,15 +2613,17 @@ int dbgsom_ctx_geodesics(dbgsom_ctx *c, const double *W_host, int64_t M, int64_t
 int dbgsom_ctx_combined_error_query(dbgsom_ctx *c, const void *Xq_host, int x_dtype, int64_t Nq, int64_t d,
                                     const double *W_host, int64_t M, const int32_t *edges_host, int64_t E,
                                     int64_t *idx2_host, double *e_host) {
-    return placed_rows_checked(__func__, c, Q_COMBINED, QueryRows{Xq_host, false, d}, nullptr, x_dtype, Nq, d, W_host, M, 2,
-                               idx2_host, e_host, 0, nullptr, 0, edges_host, E);
+    PlacedQuery p{Q_COMBINED, x_dtype, d, M, 2, idx2_host, e_host};
+    p.edges_host = edges_host; p.E = E;
+    return placed_rows_checked(__func__, c, p, QueryRows{Xq_host, false, d}, nullptr, Nq, W_host);
 }
 
 int dbgsom_ctx_combined_error_query_device(dbgsom_ctx *c, const void *Xq_dev, int x_dtype, int64_t Nq, int64_t d, int64_t ldx,
                                            const double *W_host, int64_t M, const int32_t *edges_host, int64_t E,
                                            int64_t *idx2_dev, double *e_dev) {
-    return placed_rows_checked(__func__, c, Q_COMBINED, QueryRows{Xq_dev, true, ldx}, nullptr, x_dtype, Nq, d, W_host, M, 2,
-                               idx2_dev, e_dev, 0, nullptr, 0, edges_host, E);
+    PlacedQuery p{Q_COMBINED, x_dtype, d, M, 2, idx2_dev, e_dev};
+    p.edges_host = edges_host; p.E = E;
+    return placed_rows_checked(__func__, c, p, QueryRows{Xq_dev, true, ldx}, nullptr, Nq, W_host);
 }
 
 int dbgsom_ctx_combined_error_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const int32_t *indices_host,
@@ -2603,8 +2631,9 @@ int dbgsom_ctx_combined_error_query_csr(dbgsom_ctx *c, const int64_t *indptr_hos
                                         const double *W_host, int64_t M, const int32_t *edges_host, int64_t E,
                                         int64_t *idx2_host, double *e_host) {
     const CsrHost csr{indptr_host, indices_host, nnz};
-    return placed_rows_checked(__func__, c, Q_COMBINED, QueryRows{data_host, false, d}, &csr, x_dtype, Nq, d, W_host, M, 2,
-                               idx2_host, e_host, 0, nullptr, 0, edges_host, E);
+    PlacedQuery p{Q_COMBINED, x_dtype, d, M, 2, idx2_host, e_host};
+    p.edges_host = edges_host; p.E = E;
+    return placed_rows_checked(__func__, c, p, QueryRows{data_host, false, d}, &csr, Nq, W_host);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -196,11 +196,7 @@ int launch_topk_cols(const double *R, int64_t N, int64_t M, int64_t ldr, const i
     DBGSOM_REQUIRE(R && state_r && state_i && ws, "null pointer");
     DBGSOM_REQUIRE(is_aligned(R, 8) && is_aligned(owner, 8) && is_aligned(state_r, 8) && is_aligned(state_i, 8),
                    "pointers must be 8-byte aligned");
-    const size_t need = topk_cols_workspace_bytes(N, M, k);
-    if (ws_bytes < need) {
-        set_error("dbgsom_topk_cols: workspace of %zu bytes, %zu needed", ws_bytes, need);
-        return DBGSOM_ENOMEM;
-    }
+    TRY_STATUS(workspace_check("dbgsom_topk_cols", ws_bytes, topk_cols_workspace_bytes(N, M, k)));
     DBGSOM_REQUIRE(is_aligned(ws, 16), "workspace_dev must be 16-byte aligned");
     const int K = cols_instance(k);
     const int64_t S = cols_segments(N, K), G = (M + 63) / 64, Q = S * K, P = cols_parts(Q);
@@ -279,37 +275,26 @@ static int exemplars_check(int x_dtype, int64_t N, int64_t d, int64_t ldx, int64
     return DBGSOM_OK;
 }
 
-// the slab loop of launch_kneighbors with the fold behind the product: rows row0 .. row0 + N - 1 into the state
+// the Euclidean slab loop with the fold behind the product: rows row0 .. row0 + N - 1 into the state
 int launch_exemplars_fold(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx, const double *W,
                           int64_t M, const double *ww, int k, int own_cell, int64_t slab_rows, int64_t row0, double *state_r,
                           int64_t *state_i, void *ws, size_t ws_bytes, hipStream_t s) {
     TRY_STATUS(exemplars_check(x_dtype, N, d, ldx, M, k, slab_rows, row0));
     if (N == 0) return DBGSOM_OK;
     DBGSOM_REQUIRE(X && xx && W && ww && state_r && state_i && ws, "null pointer");
-    const size_t need = exemplars_fold_workspace_bytes(N, M, k, slab_rows);
-    if (ws_bytes < need) {
-        set_error("dbgsom_exemplars: workspace of %zu bytes, %zu needed", ws_bytes, need);
-        return DBGSOM_ENOMEM;
-    }
-    DBGSOM_REQUIRE(is_aligned(ws, 16), "workspace_dev must be 16-byte aligned");
-    const int64_t rows = kneighbors_slab_rows(N, M, slab_rows), ldr = kneighbors_slab_ld(M);
     const size_t slab_bytes = kneighbors_workspace_bytes(N, M, slab_rows), own_bytes = exemplars_owner_bytes(N, M, slab_rows);
+    const size_t scratch_bytes = topk_cols_workspace_bytes(kneighbors_slab_rows(N, M, slab_rows), M, k);
+    TRY_STATUS(kneighbors_workspace_check("dbgsom_exemplars", N, M, slab_rows, ws, ws_bytes, 2 * own_bytes + scratch_bytes));
     char *base = static_cast<char *>(ws);
-    double *slab = reinterpret_cast<double *>(base);
     int64_t *own = reinterpret_cast<int64_t *>(base + slab_bytes);
     double *own_dist = reinterpret_cast<double *>(base + slab_bytes + own_bytes);
     void *scratch = base + slab_bytes + 2 * own_bytes;
-    const size_t scratch_bytes = topk_cols_workspace_bytes(rows, M, k);
-    const size_t es = dtype_size(x_dtype);
-    for (int64_t r0 = 0; r0 < N; r0 += rows) {
-        const int64_t n = std::min(rows, N - r0);
-        TRY_STATUS(launch_distances_squared(static_cast<const char *>(X) + (size_t)r0 * ldx * es, x_dtype, n, d, ldx,
-                                            xx + r0, W, M, ww, slab, ldr, s));
-        if (own_cell) TRY_STATUS(launch_topk_rows(slab, n, M, ldr, 1, own, own_dist, s));
-        TRY_STATUS(launch_topk_cols(slab, n, M, ldr, own_cell ? own : nullptr, row0 + r0, k, state_r, state_i, scratch,
-                                    scratch_bytes, s));
-    }
-    return DBGSOM_OK;
+    return euclidean_slabs(X, x_dtype, N, d, ldx, xx, W, M, ww, slab_rows, reinterpret_cast<double *>(base), s,
+                           [&](int64_t r0, int64_t n, const double *slab, int64_t ldr) {
+                               if (own_cell) TRY_STATUS(launch_topk_rows(slab, n, M, ldr, 1, own, own_dist, s));
+                               return launch_topk_cols(slab, n, M, ldr, own_cell ? own : nullptr, row0 + r0, k, state_r,
+                                                       state_i, scratch, scratch_bytes, s);
+                           });
 }
 
 int launch_exemplars(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx, const double *W,
@@ -319,10 +304,7 @@ int launch_exemplars(const void *X, int x_dtype, int64_t N, int64_t d, int64_t l
     DBGSOM_REQUIRE(idx && dist && ws && (N == 0 || (X && xx && W && ww)), "null pointer");
     DBGSOM_REQUIRE(is_aligned(idx, 8) && is_aligned(dist, 8), "pointers must be 8-byte aligned");
     const size_t front = exemplars_fold_workspace_bytes(N, M, k, slab_rows), need = exemplars_workspace_bytes(N, M, k, slab_rows);
-    if (ws_bytes < need) {
-        set_error("dbgsom_exemplars: workspace of %zu bytes, %zu needed", ws_bytes, need);
-        return DBGSOM_ENOMEM;
-    }
+    TRY_STATUS(workspace_check("dbgsom_exemplars", ws_bytes, need));
     DBGSOM_REQUIRE(is_aligned(ws, 16), "workspace_dev must be 16-byte aligned");
     double *state_r = reinterpret_cast<double *>(static_cast<char *>(ws) + front);
     int64_t *state_i = reinterpret_cast<int64_t *>(static_cast<char *>(ws) + front + exemplars_state_bytes(M, k));

@@ -127,16 +127,6 @@ size_t kneighbors_workspace_bytes(int64_t N, int64_t M, int64_t slab_rows) {
     return align_up((size_t)kneighbors_slab_rows(N, M, slab_rows) * (size_t)kneighbors_slab_ld(M) * 8);
 }
 
-static int kneighbors_workspace_check(const char *fn, int64_t N, int64_t M, int64_t slab_rows, const void *ws,
-                                      size_t ws_bytes, size_t in_front) {
-    TRY_STATUS(workspace_check(fn, ws_bytes, in_front + kneighbors_workspace_bytes(N, M, slab_rows)));
-    if (!is_aligned(ws, 16)) {
-        set_error("%s: workspace_dev must be 16-byte aligned", fn);
-        return DBGSOM_EINVAL;
-    }
-    return DBGSOM_OK;
-}
-
 int launch_kneighbors(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx, const double *W,
                       int64_t M, const double *ww, int k, int64_t slab_rows, int64_t *idx, double *dist, void *ws,
                       size_t ws_bytes, hipStream_t s) {
@@ -147,11 +137,10 @@ int launch_kneighbors(const void *X, int x_dtype, int64_t N, int64_t d, int64_t 
     if (N == 0) return DBGSOM_OK;
     DBGSOM_REQUIRE(X && xx && W && ww && idx && dist && ws, "null pointer");
     TRY_STATUS(kneighbors_workspace_check("dbgsom_kneighbors", N, M, slab_rows, ws, ws_bytes, 0));
-    double *slab = static_cast<double *>(ws);
-    return kneighbors_slabs(X, x_dtype, N, ldx, M, k, slab_rows, slab, launch_topk_rows, idx, dist, s,
-                            [&](const void *rows, int64_t r0, int64_t n, double *out, int64_t ldr) {
-                                return launch_distances_squared(rows, x_dtype, n, d, ldx, xx + r0, W, M, ww, out, ldr, s);
-                            });
+    return euclidean_slabs(X, x_dtype, N, d, ldx, xx, W, M, ww, slab_rows, static_cast<double *>(ws), s,
+                           [&](int64_t r0, int64_t n, const double *slab, int64_t ldr) {
+                               return launch_topk_rows(slab, n, M, ldr, k, idx + r0 * k, dist + r0 * k, s);
+                           });
 }
 
 // metric="cosine": slabs of the cosine matrix (u, v: cosine.hip), then the selection that stores what it selected on

@@ -200,7 +200,7 @@ int launch_mixture_rows(const double *R, int64_t N, int64_t M, int64_t ldr, cons
     return launch_status("mixture_rows_kernel");
 }
 
-// the slab loop of launch_neighborhood_energy (same slab size rule, same workspace) with the mixture kernel behind the
+// the Euclidean slab loop (the slab size rule and the workspace of launch_kneighbors) with the mixture kernel behind the
 // product
 int launch_mixture(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const double *xx, const double *W, int64_t M,
                    const double *ww, const double *a, double c, const double *Y, int n_values, int64_t ldy, int64_t slab_rows,
@@ -212,23 +212,12 @@ int launch_mixture(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx
     if (N == 0) return DBGSOM_OK;
     DBGSOM_REQUIRE(X && xx && W && ww && ws, "null pointer");
     TRY_STATUS(mixture_check_pointers(a, Y, n_values, unit, lse, q));
-    const size_t need = kneighbors_workspace_bytes(N, M, slab_rows);
-    if (ws_bytes < need) {
-        set_error("dbgsom_mixture: workspace of %zu bytes, %zu needed", ws_bytes, need);
-        return DBGSOM_ENOMEM;
-    }
-    DBGSOM_REQUIRE(is_aligned(ws, 16), "workspace_dev must be 16-byte aligned");
-    const int64_t rows = kneighbors_slab_rows(N, M, slab_rows), ldr = kneighbors_slab_ld(M);
-    double *slab = static_cast<double *>(ws);
-    const size_t es = dtype_size(x_dtype);
-    for (int64_t r0 = 0; r0 < N; r0 += rows) {
-        const int64_t n = std::min(rows, N - r0);
-        TRY_STATUS(launch_distances_squared(static_cast<const char *>(X) + (size_t)r0 * ldx * es, x_dtype, n, d, ldx,
-                                            xx + r0, W, M, ww, slab, ldr, s));
-        TRY_STATUS(launch_mixture_rows(slab, n, M, ldr, a, c, Y, n_values, ldy, unit + r0, lse + r0,
-                                       q ? q + r0 * ldq : nullptr, ldq, s));
-    }
-    return DBGSOM_OK;
+    TRY_STATUS(kneighbors_workspace_check("dbgsom_mixture", N, M, slab_rows, ws, ws_bytes, 0));
+    return euclidean_slabs(X, x_dtype, N, d, ldx, xx, W, M, ww, slab_rows, static_cast<double *>(ws), s,
+                           [&](int64_t r0, int64_t n, const double *slab, int64_t ldr) {
+                               return launch_mixture_rows(slab, n, M, ldr, a, c, Y, n_values, ldy, unit + r0, lse + r0,
+                                                          q ? q + r0 * ldq : nullptr, ldq, s);
+                           });
 }
 
 }  // namespace dbgsom
