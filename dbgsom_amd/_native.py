@@ -35,6 +35,7 @@ MAX_NEIGHBORS = 32      # DBGSOM_MAX_NEIGHBORS
 MAX_DIRECTIONS = 8      # DBGSOM_MAX_DIRECTIONS
 MAX_RADII = 32          # DBGSOM_MAX_RADII
 MAX_MIXTURE_VALUES = 16   # DBGSOM_MAX_MIXTURE_VALUES
+MAX_SCAN_FEATURES = 8192  # DBGSOM_MAX_SCAN_FEATURES
 # counters of dbgsom_sparse_code / dbgsom_ctx_sparse_code (DBGSOM_SC_COUNTS, in this order)
 SC_COUNTS = ("samples", "iterations", "max_iterations", "drops", "degenerate", "early_stops", "aa_retries",
              "overflow", "max_active", "multi_drops", "g_rows")
@@ -246,6 +247,11 @@ SIGNATURES = {
     "dbgsom_ctx_class_histogram": (_ci, [_vp, _vp, _i64, _i64, _vp]),
     "dbgsom_ctx_partition": (_ci, [_vp, _vp, _i64, _ci, _vp, _vp]),
     "dbgsom_ctx_subset_create": (_ci, [_vp, _i64, ctypes.POINTER(_vp)]),
+    "dbgsom_ctx_read_partition": (_ci, [_vp, _vp, _vp]),
+    "dbgsom_ctx_scan_cells_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _ci, _i64, _i64, _vp,
+                                           _ci, _ci, _vp, _vp]),
+    "dbgsom_ctx_row_neighbors_query": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _i64, _ci, _ci, _vp, _vp]),
+    "dbgsom_ctx_row_neighbors_query_device": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _i64, _ci, _ci, _vp, _vp]),
     "dbgsom_ctx_epoch_info": (_ci, [_vp, _vp]),
     "dbgsom_ctx_arm_ms": (_ci, [_vp, _vp]),
     "dbgsom_ctx_filter_counts": (_ci, [_vp, _vp, _i64]),

@@ -111,6 +111,49 @@ def _lane_sums(A) -> np.ndarray:
     return p[:, 0]
 
 
+def rho_rows(X, q) -> np.ndarray:
+    """The direct-form squared distance of every row of X (n x d) to q (d,) in float64, bit for bit what
+    csrc/row_neighbors.hip computes (include/dbgsom_hip.h): float32 values widened exactly; partial l of 64 takes the
+    features l, l + 64, ... ascending with ``t = x_k - q_k``, ``p_l = p_l + t * t``, every operation rounded on its own;
+    then six rounds ``p_l = p_l + p_(l ^ s)`` for s = 32, 16, 8, 4, 2, 1."""
+    X, q = np.asarray(X, np.float64), np.asarray(q, np.float64)
+    p = np.zeros((len(X), 64))
+    with np.errstate(all="ignore"):
+        for k0 in range(0, X.shape[1], 64):
+            w = min(64, X.shape[1] - k0)
+            t = X[:, k0:k0 + w] - q[k0:k0 + w]
+            p[:, :w] = p[:, :w] + t * t
+        for s in (32, 16, 8, 4, 2, 1):
+            p = p + p[:, np.arange(64) ^ s]
+    return p[:, 0]
+
+
+def check_row_neighbors(k, n_probe, M) -> None:
+    """The limits of ``row_neighbors``: rows listed per query and units probed per query"""
+    if not 1 <= k <= _native.MAX_NEIGHBORS:
+        raise ValueError(f"need 1 <= k <= DBGSOM_MAX_NEIGHBORS = {_native.MAX_NEIGHBORS}, got k = {k}")
+    if not 1 <= n_probe <= min(M, _native.MAX_NEIGHBORS):
+        raise ValueError(f"need 1 <= n_probe <= min({M} prototypes, DBGSOM_MAX_NEIGHBORS = {_native.MAX_NEIGHBORS}), "
+                         f"got n_probe = {n_probe}")
+
+
+def nearest_rows_host(X, winners, probes, Q, k):
+    """The statement of ``row_neighbors`` in NumPy -> (dist, idx), both (rows of Q, k): the candidates of query q are
+    the rows i of X whose unit ``winners[i]`` is among ``probes[q]`` (entries < 0 skipped); of those with
+    ``rho_rows < +inf`` the k smallest ``(rho, i)`` in lexicographic order, ``dist = sqrt(rho)``; the rest ``(inf, -1)``."""
+    X, Q = np.asarray(X), np.asarray(Q)
+    winners, probes = np.asarray(winners, dtype=np.int64), np.asarray(probes, dtype=np.int64)
+    dist, idx = np.full((len(Q), k), np.inf), np.full((len(Q), k), -1, dtype=np.int64)
+    for qi in range(len(Q)):
+        rows = np.flatnonzero(np.isin(winners, probes[qi][probes[qi] >= 0]))
+        rho = rho_rows(X[rows], Q[qi])
+        ok = rho < np.inf
+        rows, rho = rows[ok], rho[ok]
+        first = np.lexsort((rows, rho))[:k]
+        idx[qi, :first.size], dist[qi, :first.size] = rows[first], np.sqrt(rho[first])
+    return dist, idx
+
+
 def mixture_rows_host(R, log_prior, c, Y=None):
     """The arithmetic of csrc/mixture.hip in NumPy on a matrix R (rows x M float64) of squared values -> (unit, lse, q):
     ``t_j = a_j - (c * r_j)``, two roundings; ``(T, b)`` the largest t_j, lowest j among equals, over ``t_j > -inf`` and
@@ -244,6 +287,51 @@ class HotPathBackend:
         with np.errstate(invalid="ignore"):
             rho = np.sqrt(thr)
             return np.stack([np.count_nonzero(D <= r, axis=0) for r in rho], axis=1).astype(np.int64)
+
+    # goes up whenever the resident rows are replaced or dropped (a backend that keeps a count: HipBackend): what an
+    # index of the resident rows is held against
+    resident_serial = 0
+
+    def partition(self, W, want_winners=False):
+        """The resident rows bucketed by their unit, ``bmu(W, 1)``'s winner -> (rows per unit (rows of W,) int64, the
+        winners or None).  The partition stays with the backend until the resident rows change: ``row_neighbors``
+        searches it.  This default keeps the winners on the host."""
+        win = np.asarray(self.bmu(W, 1)[1], dtype=np.int64).reshape(-1)
+        self._partition = (self.resident_serial, len(np.asarray(W)), win)
+        counts = np.bincount(win, minlength=len(np.asarray(W))).astype(np.int64)
+        return counts, (win if want_winners else None)
+
+    def _resident_rows(self) -> np.ndarray:
+        """The resident rows on the host, for the NumPy defaults."""
+        X = getattr(self, "_X", None)
+        if X is None:
+            raise ValueError("no resident rows: call load(X) first")
+        return X.toarray() if is_sparse(X) else np.asarray(X)
+
+    def row_neighbors(self, W, k, n_probe, Q):
+        """The k nearest resident rows of every row of Q among the rows filed under its n_probe nearest units ->
+        (dist, idx), both (rows of Q, k), float64 and int64 (row numbers of the resident rows).  The units of row q
+        are ``kneighbors(W, n_probe, Q)``'s indices (-1 skipped), its candidates the resident rows whose unit under
+        the last ``partition`` is among them, and the result the candidates with the smallest ``(rho, i)`` in
+        lexicographic order, ascending, ``rho = rho_rows`` (direct form, float64, fixed order) and ``dist =
+        sqrt(rho)`` taken after the selection.  Only ``rho < +inf`` is listed; unfilled slots hold ``(inf, -1)``.
+        ``1 <= k <= MAX_NEIGHBORS``, ``1 <= n_probe <= min(rows of W, MAX_NEIGHBORS)``.  ``ValueError`` without a
+        partition of the rows that are resident now, on these many units.  Q: a dense host array or (a backend that
+        takes them) a device array; the results are NumPy arrays, next to Q for a device array.
+
+        This default is the statement of the semantics in NumPy (``nearest_rows_host``); the HIP backend scans the
+        probed cells on the device (csrc/row_neighbors.hip)."""
+        M = len(np.asarray(W))
+        k, n_probe = int(k), int(n_probe)
+        check_row_neighbors(k, n_probe, M)
+        part = getattr(self, "_partition", None)
+        if part is None or part[0] != self.resident_serial or part[1] != M:
+            raise ValueError("no partition of the resident rows on these prototypes: call partition(W) after load(X)")
+        if is_sparse(Q):
+            raise TypeError("the row_neighbors calls take dense rows")
+        Q = host_rows(Q)
+        probes = np.asarray(self.kneighbors(W, n_probe, Q)[1]) if len(Q) else np.empty((0, n_probe), dtype=np.int64)
+        return nearest_rows_host(self._resident_rows(), part[2], probes, Q, k)
 
     def mixture(self, W, log_prior, c, Y, X):
         """The map as an isotropic Gaussian mixture -> (unit, lse, q): (rows of X,) int64, (rows of X,) float64 and
@@ -1033,6 +1121,7 @@ class HipBackend(HotPathBackend):
         self._N, self._d = int(shape[0]), int(shape[1])
         self._x_np_dtype = np_dtype
         self._loaded = True
+        self.resident_serial += 1
         self._hop_key = None
         self._last_M = 0
         self._y = None
@@ -1124,7 +1213,8 @@ class HipBackend(HotPathBackend):
     _DENSE = (HOST, DEVICE)
     _QUERY_ROWS = {"euclidean": ((HOST, DEVICE, CSR), None), "manhattan": (_DENSE, "Manhattan"),
                    "cosine": (_DENSE, "cosine"), "masked": ((HOST,), "masked"), "sparse coding": (_DENSE, "sparse coding"),
-                   "topographic function": (_DENSE, "topographic function")}   # what takes which rows
+                   "topographic function": (_DENSE, "topographic function"),
+                   "row_neighbors": (_DENSE, "row_neighbors")}   # what takes which rows
 
     def _query_rows(self, X, kind="euclidean", defer=False):
         return _QueryRows(self, X, *self._QUERY_ROWS[kind], defer)
@@ -1833,7 +1923,46 @@ class HipBackend(HotPathBackend):
         win = np.empty(self._N, dtype=np.int64) if want_winners else None
         self._call("dbgsom_ctx_partition", self._ctx, p, M, rf, counts.ctypes.data,
                    None if win is None else win.ctypes.data)
+        self._part_M = M
         return counts, win
+
+    def read_partition(self):
+        """The bucket order ``partition`` left on the device -> (order (rows,) int32, seg_start (units + 1,) uint32):
+        unit j's rows are ``order[seg_start[j]:seg_start[j + 1]]``, ascending."""
+        self._require_loaded()
+        M = int(self._part_M)
+        order, seg = np.empty(self._N, dtype=np.int32), np.empty(M + 1, dtype=np.uint32)
+        self._call("dbgsom_ctx_read_partition", self._ctx, order.ctypes.data, seg.ctypes.data)
+        return order, seg
+
+    # -- the nearest resident rows of a query, through the partition -----------------------------------
+    def row_neighbors(self, W, k, n_probe, Q):
+        """The k nearest resident rows among those filed under a row's n_probe nearest units
+        (csrc/kneighbors.hip, then csrc/row_neighbors.hip): the unit search of a chunk leaves its probe lists on the
+        device and one workgroup per row scans the rows ``partition`` filed under them.  Host rows go up in chunks
+        of ``distances_chunk_rows`` rows and rows x k x 16 bytes come down; for rows in HBM both results are arrays on
+        their device that the kernel writes itself (dbgsom_ctx_row_neighbors_query_device).  Dense float32 /
+        float64 residents only."""
+        self._require_loaded()
+        rows = self._query_rows(Q, "row_neighbors", defer=True)
+        W64, M = self._w64(W, rows.d)
+        k, n_probe = int(k), int(n_probe)
+        check_row_neighbors(k, n_probe, M)
+        if rows.d != self._d:
+            raise ValueError(f"Q has {rows.d} features, the resident rows {self._d}")
+        if rows.d > _native.MAX_SCAN_FEATURES:
+            raise ValueError(f"rows of more than DBGSOM_MAX_SCAN_FEATURES = {_native.MAX_SCAN_FEATURES} features are "
+                             f"not scanned, got {rows.d}")
+        dist, idx = rows.empty((rows.N, k), "float64"), rows.empty((rows.N, k), "int64")
+        if rows.N:
+            try:
+                self._query("row_neighbors_query", "euclidean", rows, W64.ctypes.data, M, n_probe, k, rows.ptr(idx),
+                            rows.ptr(dist))
+            except _native.DbgsomNativeError as e:
+                if e.code == -4:   # DBGSOM_ESTATE: the message says what is missing
+                    raise ValueError(f"{e}: call partition(W) on dense float32 / float64 residents first") from None
+                raise
+        return dist, idx
 
     def subset(self, neuron):
         """A backend whose resident samples are the Voronoi set of `neuron` (gathered in HBM)."""
@@ -1859,6 +1988,7 @@ class HipBackend(HotPathBackend):
                 self._set(k, v)
             self._install_collective()
         self._loaded = False
+        self.resident_serial += 1
         self._borrowed = None
         self._hop_key = None
         self._weighted = False

@@ -65,7 +65,7 @@ from sklearn.utils import check_array, check_random_state
 from sklearn.utils.validation import check_is_fitted
 
 from . import schedule
-from ._native import MAX_MIXTURE_VALUES, MAX_NEIGHBORS, MAX_RADII
+from ._native import MAX_MIXTURE_VALUES, MAX_NEIGHBORS, MAX_RADII, MAX_SCAN_FEATURES
 from .backend import (RESIDENT, HotPathBackend, array_namespace, dist_info, dtype_name, is_device_array, is_sparse,
                       shard_bounds, squared_thresholds)
 from .lattice import GrowingLattice
@@ -168,6 +168,7 @@ class BaseSom(BaseEstimator):
         state = dict(state)
         state.pop("_backend_obj", None)  # device handles are not picklable
         state.pop("_resident", None)
+        state.pop("_index", None)        # (the index of index_rows is device state: it goes with the backend)
         for k in ("_sw", "_sw_global"):
             state.pop(k, None)
         return state
@@ -209,6 +210,7 @@ class BaseSom(BaseEstimator):
         self._accepts_nan()   # (validates the parameter)
         self._incomplete_fit = False
         self._metric_fit = None
+        self._index = None        # (the rows index_rows made resident are replaced)
         if isinstance(X, DeviceSamples):   # a Voronoi subset that already lives in HBM (f-4)
             if y is not None:
                 y = np.asarray(y)
@@ -1415,6 +1417,110 @@ class BaseSom(BaseEstimator):
             dist, idx = np.full((M, k), np.inf), np.full((M, k), -1, dtype=np.int64)
         else:
             dist, idx = self._engine().exemplars(self.weights_, k, X, own_cell=bool(own_cell))
+        return (dist, idx) if return_distance else idx
+
+    # ------------------------------------------------------------------------------------------
+    # nearest stored rows through the map: an inverted-file index over the units
+    # ------------------------------------------------------------------------------------------
+    _index = None   # (backend, its resident_serial, weights_) of the last index_rows
+
+    def _check_index_input(self, X, what: str):
+        """The refusals index_rows and row_neighbors share, in front of any upload -> the validated rows"""
+        kind = self._search_metric()
+        if kind:
+            self._refuse_metric(kind, what, "rows are compared by the squared Euclidean distance; use metric='euclidean'")
+        if self.sharded_input or dist_info()[1] > 1:
+            raise ValueError(f"{what} takes one process: no sharded_input, no process group of more than one rank")
+        if is_sparse(X) or getattr(X, "is_sparse", False):
+            raise TypeError(f"{what} takes dense rows: pass X.toarray() (the stored rows are scanned as dense rows)")
+        if self.n_features_in_ > MAX_SCAN_FEATURES:
+            raise ValueError(f"{what} scans rows of at most {MAX_SCAN_FEATURES} features (the widened query lives in "
+                             f"64 KiB of LDS), this map has {self.n_features_in_}: reduce the features first")
+        if not is_device_array(X) and np.ndim(X) == 2 and np.shape(X)[0] == 0 and what == "row_neighbors":
+            X = check_array(X, dtype=[np.float64, np.float32], ensure_min_samples=0)   # (no rows: no launch)
+        else:
+            X = self._check_query(X, accept_sparse=False)
+        if X.shape[1] != self.n_features_in_:
+            raise ValueError(f"X has {X.shape[1]} features, but {type(self).__name__} is expecting "
+                             f"{self.n_features_in_} features as input")
+        if isinstance(X, np.ndarray) and np.isnan(X).any():   # (passed _check_query: missing_values is set)
+            raise ValueError(f"X holds NaN: {what} is not defined on rows with missing entries "
+                             f"(missing_values={self.missing_values!r}); impute them first (impute(X))")
+        return X
+
+    def index_rows(self, X):
+        """File the rows of X under their best matching units and keep them in HBM: the index ``row_neighbors``
+        searches.  X is made resident the way ``fit`` does it -- a host array is uploaded once, a tensor on the
+        estimator's GPU is read in place when it is float32 / float64 with contiguous rows of a multiple of 16
+        features (do not write to it while the index is in use), else pad-copied on the device -- and bucketed by
+        unit on the GPU.  Sets ``index_counts_``, the rows per unit as ``(len(weights_),)`` int64, and
+        ``n_indexed_``; the map and everything ``fit`` set stay as they are.  The index lives until the next
+        ``index_rows`` or ``fit``, and is not pickled.  Refused: sparse X (``TypeError``), ``metric`` other than the
+        Euclidean one, NaN (also under ``missing_values``), more than one rank or ``sharded_input``, a tensor on
+        another GPU, more than 8192 features."""
+        check_is_fitted(self)
+        X = self._check_index_input(X, "index_rows")
+        engine = self._engine()
+        self._index = None
+        if is_device_array(X):
+            if not hasattr(engine, "load_device"):
+                raise TypeError(f"the {engine.name} backend takes host arrays only: pass X.cpu().numpy()")
+            engine.load_device(X)
+        else:
+            engine.load(X)
+        counts, _ = engine.partition(self.weights_)
+        self.index_counts_ = np.asarray(counts, dtype=np.int64)
+        self.n_indexed_ = int(X.shape[0])
+        self._index = (engine, engine.resident_serial, self.weights_)
+        return self
+
+    def row_neighbors(self, Q, n_neighbors=5, n_probe=8, return_distance=True):
+        """The ``n_neighbors`` nearest indexed rows of every row of Q, looked for under its ``n_probe`` nearest units
+        only: ``(dist, idx)``, or ``idx`` alone with ``return_distance=False``, both ``(len(Q), n_neighbors)``,
+        float64 and int64 (row numbers of the X given to ``index_rows``) -- WEBSOM-style retrieval, the map as an
+        inverted-file index.
+
+        The units of row q are ``kneighbors(Q, n_probe)``'s indices (a ``-1`` slot is skipped); its candidates are
+        the indexed rows ``i`` whose unit, ``predict(X)[i]``, is among them.  ``rho(i, q)`` is the direct-form
+        squared distance in float64 (float32 values widened exactly) in a fixed order, ``backend.rho_rows`` bit for
+        bit.  Row q of the result holds the candidates with the smallest ``(rho, i)`` in lexicographic order,
+        ascending; ``dist = sqrt(rho)`` is taken after the selection; only ``rho < +inf`` is listed and unfilled
+        slots hold ``(inf, -1)``.  ``(rho, i)`` is a total order: the result does not depend on chunks, on the order
+        of rows inside a cell or on where Q lives.  With ``n_probe = len(weights_)`` the search is exact.
+
+        ``1 <= n_neighbors <= 32``, ``1 <= n_probe <= min(len(weights_), 32)``.  Q is a dense host array (NumPy
+        results; ``len(Q) * n_neighbors * 16`` bytes come down) or a tensor on the estimator's GPU (tensors on its
+        device that the GPU writes itself; nothing of Q or the results crosses PCIe).  Refused with a
+        ``ValueError`` (sparse Q: ``TypeError``): no index (``index_rows`` not called, a later ``fit``, a pickle
+        round trip, the backend's resident rows replaced since), and everything ``index_rows`` refuses."""
+        check_is_fitted(self)
+        for name, v in (("n_neighbors", n_neighbors), ("n_probe", n_probe)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (numbers.Integral, np.integer)):
+                raise ValueError("%s does not take %s value, enter integer value" % (name, type(v)))
+            if int(v) <= 0:
+                raise ValueError("Expected %s > 0. Got %d" % (name, int(v)))
+        k, n_probe = int(n_neighbors), int(n_probe)
+        M = len(self.weights_)
+        if k > MAX_NEIGHBORS:
+            raise ValueError(f"n_neighbors = {k} is above the {MAX_NEIGHBORS} the selection on the GPU keeps per row")
+        if n_probe > M:
+            raise ValueError("Expected n_probe <= n_samples_fit, but n_probe = %d, n_samples_fit = %d (the prototypes)"
+                             % (n_probe, M))
+        if n_probe > MAX_NEIGHBORS:
+            raise ValueError(f"n_probe = {n_probe} is above the {MAX_NEIGHBORS} units a row can probe")
+        Q = self._check_index_input(Q, "row_neighbors")
+        index = self._index
+        if index is None:
+            raise ValueError("row_neighbors needs an index: call index_rows(X) first (the index is device state: it is "
+                             "dropped by fit and by pickling)")
+        engine = self._engine()
+        if index[0] is not engine or index[1] != engine.resident_serial or index[2] is not self.weights_:
+            raise ValueError("the rows index_rows made resident have been replaced since (or the map has changed): call "
+                             "index_rows(X) again")
+        if Q.shape[0] == 0 and not is_device_array(Q):
+            dist, idx = np.empty((0, k), dtype=np.float64), np.empty((0, k), dtype=np.int64)
+        else:
+            dist, idx = engine.row_neighbors(self.weights_, k, n_probe, Q)
         return (dist, idx) if return_distance else idx
 
     @staticmethod

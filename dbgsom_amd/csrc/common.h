@@ -227,6 +227,13 @@ int launch_topk_rows(const double *R, int64_t N, int64_t M, int64_t ldr, int k, 
                      hipStream_t s);
 int launch_topk_rows_plain(const double *R, int64_t N, int64_t M, int64_t ldr, int k, int64_t *idx, double *dist,
                            hipStream_t s);   // (no square root behind the selection: R holds distances)
+// row_neighbors.hip: the k nearest rows of X to every query among the rows filed under its probed units (`fn`: the
+// exported call the argument errors are reported under)
+int launch_scan_cells(const char *fn, const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx, const int32_t *order,
+                      const uint32_t *seg_start, int64_t M, const void *Q, int q_dtype, int64_t Nq, int64_t ldq,
+                      const int64_t *probe, int n_probe, int k, int64_t *idx, double *dist, hipStream_t s);
+int scan_cells_check(const char *fn, int x_dtype, int64_t N, int64_t d, int64_t ldx, int64_t M, int q_dtype, int64_t Nq,
+                     int64_t ldq, int n_probe, int k);
 int64_t kneighbors_slab_rows(int64_t N, int64_t M, int64_t slab_rows);
 // rows of a slab are M rounded up to even apart, so that every row starts on 16 bytes
 inline int64_t kneighbors_slab_ld(int64_t M) { return M + (M & 1); }

@@ -1864,8 +1864,8 @@ int dbgsom_ctx_bmu_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const in
 // prototypes under every metric, and the search itself over rows with missing entries and under metric="manhattan"
 // and metric="cosine" -- is one of two loops over chunks of rows:
 //   raw_rows_query     masked / Manhattan / cosine: kernels that read the rows as they are stored (any row pitch)
-//   placed_rows_query  Euclidean distances, neighbours, distortion, exemplars, range counts, mixture view and combined
-//                      error: the rows go through the query placement first
+//   placed_rows_query  Euclidean distances, neighbours, distortion, exemplars, range counts, mixture view, combined
+//                      error and the nearest resident rows: the rows go through the query placement first
 // A chunk of host rows goes up, its result is staged on the device and comes down behind the kernel; rows in HBM are
 // read where they are and the kernels write the caller's device arrays.  Both drivers synchronise before they return,
 // on error too (W_host and the rows are pageable), and end on drop_large_query_scratch.  The exported calls further
@@ -1873,7 +1873,8 @@ int dbgsom_ctx_bmu_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, const in
 // ------------------------------------------------------------------------------------------
 namespace {
 
-enum QueryOp { Q_BMU, Q_DISTANCES, Q_KNEIGHBORS, Q_DISTORTION, Q_EXEMPLARS, Q_COMBINED, Q_RANGE_COUNTS, Q_MIXTURE };
+enum QueryOp { Q_BMU, Q_DISTANCES, Q_KNEIGHBORS, Q_DISTORTION, Q_EXEMPLARS, Q_COMBINED, Q_RANGE_COUNTS, Q_MIXTURE,
+               Q_ROW_NEIGHBORS };
 enum RowsForm { ROWS_MASKED, ROWS_MANHATTAN, ROWS_COSINE };
 
 // DBGSOM_REQUIRE under the name of the exported call `fn` (checks shared by several of them)
@@ -1905,7 +1906,7 @@ int query_args(const char *fn, const dbgsom_ctx *c, QueryOp op, int x_dtype, boo
         REQUIRE_FN(fn, k >= 1 && k <= DBGSOM_MAX_RADII, "need 1 <= n_radii <= DBGSOM_MAX_RADII");
         return DBGSOM_OK;
     }
-    if (op == Q_EXEMPLARS) REQUIRE_FN(fn, k >= 1, "need k >= 1");   // (k counts rows: it may exceed M, and Nq)
+    if (op == Q_EXEMPLARS || op == Q_ROW_NEIGHBORS) REQUIRE_FN(fn, k >= 1, "need k >= 1");   // (k counts rows: it may exceed M, and Nq)
     else REQUIRE_FN(fn, k >= 1 && k <= M, "need 1 <= k <= M");
     REQUIRE_FN(fn, k <= DBGSOM_MAX_NEIGHBORS, "k must be <= DBGSOM_MAX_NEIGHBORS");
     return DBGSOM_OK;
@@ -2168,6 +2169,7 @@ struct PlacedQuery {
     const double *logprior_host = nullptr, *Y_host = nullptr;
     double c = 0.0, *q_out = nullptr;
     int n_values = 0;
+    int n_probe = 0;                       // Q_ROW_NEIGHBORS: units probed per row (k: the rows listed per row)
     int64_t dp = 0, chunk = 0;   // set by the driver: padded features; rows per chunk (rows in HBM: all of them)
     // The layout of the result (placed_rows_layout): idx_vals indices and res_vals values per result row, and third_vals
     // more values in a third array (q_out).  Rows from the host: the indices are staged in kn_idx, the values in
@@ -2230,6 +2232,10 @@ static int placed_rows_setup(dbgsom_ctx *c, const PlacedQuery &p, const double *
         c->x_up((size_t)p.k * 8);
         return DBGSOM_OK;
     }
+    case Q_ROW_NEIGHBORS:   // (csrc/row_neighbors.hip) the neighbours' slab; a chunk's probe lists live in ex_state:
+                            // [units: chunk x n_probe int64 | their distances: chunk x n_probe]
+        TRY(c->ex_state.reserve((size_t)p.chunk * p.n_probe * 16));
+        return c->kn_ws.reserve(kneighbors_workspace_bytes(p.chunk, M, slab));
     default: return DBGSOM_OK;   // Q_DISTANCES (csrc/distances.hip): no scratch
     }
 }
@@ -2269,6 +2275,15 @@ static int placed_rows_launch(dbgsom_ctx *c, const PlacedQuery &p, const Samples
         const double *thr = reinterpret_cast<const double *>(static_cast<char *>(c->rc_state.p) + align_up((size_t)M * p.k * 8));
         return launch_range_counts_fold(s.Xb, s.bdtype, n, dp, dp, xx, Wq, M, wwq, thr, p.k, slab, c->rc_state.as<int64_t>(),
                                         ws, cap, st);
+    }
+    case Q_ROW_NEIGHBORS: {   // the chunk's nearest units, then the scan of the resident rows filed under them
+        const Samples &x = c->xs;
+        int64_t *units = c->ex_state.as<int64_t>();
+        double *udist = reinterpret_cast<double *>(units + p.chunk * p.n_probe);
+        TRY(launch_kneighbors(s.Xb, s.bdtype, n, dp, dp, xx, Wq, M, wwq, p.n_probe, slab, units, udist, ws, cap, st));
+        return launch_scan_cells("dbgsom_ctx_row_neighbors_query", x.X, x.dtype, x.N, x.d, x.dp,
+                                 c->part_order.as<int32_t>(), bucket_sort_seg_start(c->part_ws.p, x.N, c->partM), M, s.Xb,
+                                 s.bdtype, n, dp, units, p.n_probe, p.k, idx, res, st);
     }
     default: return DBGSOM_OK;
     }
@@ -2473,6 +2488,62 @@ int dbgsom_ctx_kneighbors_query_csr(dbgsom_ctx *c, const int64_t *indptr_host, c
     const CsrHost csr{indptr_host, indices_host, nnz};
     const PlacedQuery p{Q_KNEIGHBORS, x_dtype, d, M, k, idx_host, dist_host};
     return placed_rows_checked(__func__, c, p, QueryRows{data_host, false, d}, &csr, Nq, W_host);
+}
+
+// ------------------------------------------------------------------------------------------
+// the nearest resident rows of a query, through the partition: csrc/kneighbors.hip, csrc/row_neighbors.hip
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// what the scan needs of the context: dense float32 / float64 residents and the partition of dbgsom_ctx_partition on M units
+int row_neighbors_state(const char *fn, const dbgsom_ctx *c, int64_t d, int64_t M) {
+    TRY(loaded(c, fn));
+    const char *why = nullptr;
+    if (c->xs.csr) why = "the resident samples are CSR (load dense rows)";
+    else if (c->xs.dtype == DBGSOM_BF16) why = "the resident samples are stored as bfloat16 (load them in their own dtype)";
+    else if (!c->part_valid) why = "no valid partition of the resident samples (call dbgsom_ctx_partition after the load)";
+    else if (c->partM != M) why = "M is not the partition's (call dbgsom_ctx_partition with these prototypes)";
+    if (why) { set_error("%s: %s", fn, why); return DBGSOM_ESTATE; }
+    REQUIRE_FN(fn, d == c->xs.d, "d must be the resident rows'");
+    return DBGSOM_OK;
+}
+
+int row_neighbors_checked(const char *fn, dbgsom_ctx *c, const QueryRows &q, int q_dtype, int64_t Nq, int64_t d,
+                          const double *W_host, int64_t M, int n_probe, int k, int64_t *idx_out, double *dist_out) {
+    // (the scan's own argument checks need no context: they come first)
+    TRY(scan_cells_check(fn, DBGSOM_F32, 0, d, d, M, q_dtype, Nq, q.ldx, n_probe, k));
+    if (!c) { set_error("%s: null context", fn); return DBGSOM_EINVAL; }
+    TRY(row_neighbors_state(fn, c, d, M));
+    PlacedQuery p{Q_ROW_NEIGHBORS, q_dtype, d, M, k, idx_out, dist_out};
+    p.n_probe = n_probe;
+    return placed_rows_checked(fn, c, p, q, nullptr, Nq, W_host);
+}
+
+}  // namespace
+
+int dbgsom_ctx_row_neighbors_query(dbgsom_ctx *c, const void *Q_host, int q_dtype, int64_t Nq, int64_t d,
+                                   const double *W_host, int64_t M, int n_probe, int k, int64_t *idx_host,
+                                   double *dist_host) {
+    return row_neighbors_checked(__func__, c, QueryRows{Q_host, false, d}, q_dtype, Nq, d, W_host, M, n_probe, k, idx_host,
+                                 dist_host);
+}
+
+int dbgsom_ctx_row_neighbors_query_device(dbgsom_ctx *c, const void *Q_dev, int q_dtype, int64_t Nq, int64_t d, int64_t ldq,
+                                          const double *W_host, int64_t M, int n_probe, int k, int64_t *idx_dev,
+                                          double *dist_dev) {
+    return row_neighbors_checked(__func__, c, QueryRows{Q_dev, true, ldq}, q_dtype, Nq, d, W_host, M, n_probe, k, idx_dev,
+                                 dist_dev);
+}
+
+int dbgsom_ctx_scan_cells_device(dbgsom_ctx *c, const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx,
+                                 const int32_t *order_dev, const uint32_t *seg_start_dev, int64_t M, const void *Q_dev,
+                                 int q_dtype, int64_t Nq, int64_t ldq, const int64_t *probe_dev, int n_probe, int k,
+                                 int64_t *idx_dev, double *dist_dev) {
+    TRY(scan_cells_check(__func__, x_dtype, N, d, ldx, M, q_dtype, Nq, ldq, n_probe, k));
+    CTX_CHECK(c);
+    if (Nq == 0) return DBGSOM_OK;
+    return finish_query(c, launch_scan_cells(__func__, X_dev, x_dtype, N, d, ldx, order_dev, seg_start_dev, M, Q_dev, q_dtype,
+                                             Nq, ldq, probe_dev, n_probe, k, idx_dev, dist_dev, c->stream));
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3496,6 +3567,19 @@ int dbgsom_ctx_partition(dbgsom_ctx *c, const double *W_host, int64_t M, int rou
     c->partM = M;
     c->part_valid = true;
     return DBGSOM_OK;
+}
+
+int dbgsom_ctx_read_partition(dbgsom_ctx *c, int32_t *order_host, uint32_t *seg_start_host) {
+    CTX_CHECK(c);
+    TRY(loaded(c, __func__));
+    if (!c->part_valid) { set_error("dbgsom_ctx_read_partition: call dbgsom_ctx_partition first"); return DBGSOM_ESTATE; }
+    const Samples &s = c->xs;
+    if (order_host)
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(order_host, c->part_order.p, (size_t)s.N * 4, hipMemcpyDeviceToHost, c->stream));
+    if (seg_start_host)
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(seg_start_host, bucket_sort_seg_start(c->part_ws.p, s.N, c->partM),
+                                        (size_t)(c->partM + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+    return sync(c);
 }
 
 int dbgsom_ctx_subset_create(dbgsom_ctx *c, int64_t neuron, dbgsom_ctx **child_out) {

@@ -1289,6 +1289,46 @@ int dbgsom_ctx_partition(dbgsom_ctx *ctx, const double *W_host, int64_t M, int r
 /* a new context whose resident samples are the rows of neuron j's Voronoi set (sample order kept),
  * gathered on the device; labels follow when the parent has them */
 int dbgsom_ctx_subset_create(dbgsom_ctx *ctx, int64_t neuron, dbgsom_ctx **child);
+/* the bucket order dbgsom_ctx_partition left on the device, for tests: order_host[N] int32, the resident rows grouped
+ * by unit, ascending inside a unit; seg_start_host[M + 1] uint32, unit j's rows are order[seg_start[j] ..
+ * seg_start[j + 1]).  Either may be NULL.  DBGSOM_ESTATE without a valid partition. */
+int dbgsom_ctx_read_partition(dbgsom_ctx *ctx, int32_t *order_host, uint32_t *seg_start_host);
+
+/* ---- the nearest stored rows of a query, through the map (csrc/row_neighbors.hip) -------------------- */
+/* An inverted-file search: the rows X are filed under units (order / seg_start as above, any order inside a unit), a
+ * query q names n_probe units, and its candidates are the rows filed under them.  rho(i, q) is the direct-form squared
+ * distance in float64, float32 values widened exactly, in a fixed order: partial l (0 .. 63) takes the features
+ * k = l, l + 64, ... ascending, t = x_k - q_k, p_l = p_l + t * t, the difference, the product and the sum each rounded
+ * on its own; then six rounds p_l = p_l + p_(l ^ s), s = 32, 16, 8, 4, 2, 1.  Row q of the result holds the k
+ * candidates with the smallest (rho, i) in lexicographic order, ascending: idx the row numbers (int64), dist =
+ * sqrt(rho) taken after the selection.  Only rho < +inf is listed (never NaN, never an overflow); slots left unfilled
+ * hold (inf, -1).  (rho, i) is a total order: the result does not depend on the order inside a unit.
+ *
+ * dbgsom_ctx_scan_cells_device: the kernel on the caller's device buffers, on the context's stream, waited for.  X: N
+ * rows of d features, ldx >= d apart, x_dtype DBGSOM_F32 / DBGSOM_F64; Q likewise (q_dtype, Nq, ldq), the two dtypes
+ * independent; bases aligned to their item size.  probe_dev: Nq x n_probe int64, distinct units of a row; an entry
+ * outside [0, M) (-1) is skipped.  1 <= n_probe <= min(M, DBGSOM_MAX_NEIGHBORS), 1 <= k <= DBGSOM_MAX_NEIGHBORS,
+ * 1 <= d <= DBGSOM_MAX_SCAN_FEATURES (the widened query lives in 64 KiB of LDS); idx_dev / dist_dev: Nq x k.  Entries of
+ * order outside [0, N) and segment bounds above N are skipped, never followed.  Argument errors are DBGSOM_EINVAL
+ * before any launch; Nq == 0 does nothing.
+ *
+ * dbgsom_ctx_row_neighbors_query[_device]: the k-nearest-units search of the query (dbgsom_ctx_kneighbors_query: its
+ * n_probe indices are the probe list), then the scan over the resident rows and the partition dbgsom_ctx_partition
+ * left.  Host rows go up in chunks of "distances_chunk_rows" rows and Nq x k x 16 bytes come down; rows in HBM are
+ * read where they are and the kernels write the caller's device arrays.  DBGSOM_ESTATE: no valid partition (none yet,
+ * or the samples were loaded again since), M is not the partition's, CSR residents, bfloat16 storage.  d must be the
+ * resident rows'. */
+#define DBGSOM_MAX_SCAN_FEATURES 8192
+int dbgsom_ctx_scan_cells_device(dbgsom_ctx *ctx, const void *X_dev, int x_dtype, int64_t N, int64_t d, int64_t ldx,
+                                 const int32_t *order_dev, const uint32_t *seg_start_dev, int64_t M, const void *Q_dev,
+                                 int q_dtype, int64_t Nq, int64_t ldq, const int64_t *probe_dev, int n_probe, int k,
+                                 int64_t *idx_dev, double *dist_dev);
+int dbgsom_ctx_row_neighbors_query(dbgsom_ctx *ctx, const void *Q_host, int q_dtype, int64_t Nq, int64_t d,
+                                   const double *W_host, int64_t M, int n_probe, int k, int64_t *idx_host,
+                                   double *dist_host);
+int dbgsom_ctx_row_neighbors_query_device(dbgsom_ctx *ctx, const void *Q_dev, int q_dtype, int64_t Nq, int64_t d,
+                                          int64_t ldq, const double *W_host, int64_t M, int n_probe, int k,
+                                          int64_t *idx_dev, double *dist_dev);
 
 /* ---- diagnostics ----------------------------------------------------------------------------- */
 /* info8 = [filtered search ran (0/1), mean candidate-list length, digit planes used (0 = no sweep:
