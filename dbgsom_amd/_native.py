@@ -36,6 +36,7 @@ MAX_DIRECTIONS = 8      # DBGSOM_MAX_DIRECTIONS
 MAX_RADII = 32          # DBGSOM_MAX_RADII
 MAX_MIXTURE_VALUES = 16   # DBGSOM_MAX_MIXTURE_VALUES
 MAX_SCAN_FEATURES = 8192  # DBGSOM_MAX_SCAN_FEATURES
+DEVIATIONS_SQUARES, DEVIATIONS_NORM = 0, 1   # DBGSOM_DEVIATIONS_*
 # counters of dbgsom_sparse_code / dbgsom_ctx_sparse_code (DBGSOM_SC_COUNTS, in this order)
 SC_COUNTS = ("samples", "iterations", "max_iterations", "drops", "degenerate", "early_stops", "aa_retries",
              "overflow", "max_active", "multi_drops", "g_rows")
@@ -245,6 +246,12 @@ SIGNATURES = {
     "dbgsom_ctx_topographic_count": (_ci, [_vp, _vp, _i64, _ci, _vp, _vp]),
     "dbgsom_ctx_node_statistics": (_ci, [_vp, _vp, _i64, _ci, _dbl, _vp, _vp]),
     "dbgsom_ctx_class_histogram": (_ci, [_vp, _vp, _i64, _i64, _vp]),
+    "dbgsom_ctx_unit_sums": (_ci, [_vp, _vp, _vp, _vp, _i64, _i64, _ci, _vp, _vp]),
+    "dbgsom_ctx_unit_sums_device": (_ci, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _ci, _vp, _vp, _i64]),
+    "dbgsom_ctx_unit_deviations_device": (_ci, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _ci, _ci, _vp, _i64]),
+    "dbgsom_ctx_set_targets": (_ci, [_vp, _vp, _i64, _ci]),
+    "dbgsom_ctx_set_targets_device": (_ci, [_vp, _vp, _i64, _i64, _ci]),
+    "dbgsom_ctx_target_statistics": (_ci, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "dbgsom_ctx_partition": (_ci, [_vp, _vp, _i64, _ci, _vp, _vp]),
     "dbgsom_ctx_subset_create": (_ci, [_vp, _i64, ctypes.POINTER(_vp)]),
     "dbgsom_ctx_read_partition": (_ci, [_vp, _vp, _vp]),

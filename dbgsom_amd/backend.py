@@ -198,6 +198,87 @@ def _mixture_args(M, log_prior, c, Y):
     return a, c, Y
 
 
+UNIT_BLOCK = 128          # list positions per block of the per-unit sums: CH of csrc/accumulate.hip
+DEVIATIONS_SQUARES, DEVIATIONS_NORM = _native.DEVIATIONS_SQUARES, _native.DEVIATIONS_NORM
+
+
+def _unit_args(units, Y, w):
+    units = np.ascontiguousarray(units, dtype=np.int64).reshape(-1)
+    Y = np.ascontiguousarray(Y, dtype=np.float64)
+    Y = Y[:, None] if Y.ndim == 1 else Y
+    if Y.ndim != 2 or Y.shape[0] != units.shape[0]:
+        raise ValueError("one row of values per unit index")
+    if not 1 <= Y.shape[1] <= _native.MAX_MIXTURE_VALUES:
+        raise ValueError(f"1 .. {_native.MAX_MIXTURE_VALUES} values per row, got {Y.shape[1]}")
+    if w is not None:
+        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+        if w.shape != units.shape:
+            raise ValueError("one weight per row")
+    return units, Y, w
+
+
+def unit_fold(units, Z, w, M):
+    """The per-unit sums of csrc/unit_sums.hip in NumPy, bit for bit -> (mass (M,), sums (M, V)).
+
+    The list of unit j holds the rows i with ``units[i] == j``, ascending, without rows of weight 0; a row's term is
+    ``Z[i, v]`` or the rounded product ``w[i] * Z[i, v]``, its mass term 1.0 or ``w[i]``.  The list is cut into
+    blocks of UNIT_BLOCK positions, a block's terms are added in list order from +0.0, and the blocks' partial sums
+    are added ascending from +0.0 (``np.add.accumulate`` is sequential).  A block is padded with +0.0 here: adding
+    +0.0 to a chain that started at +0.0 changes no bit."""
+    units, Z = np.asarray(units, dtype=np.int64), np.asarray(Z, dtype=np.float64)
+    N, V = Z.shape
+    M = int(M)
+    keep = (units >= 0) & (units < M)
+    if w is not None:
+        keep &= np.asarray(w) != 0
+    rows = np.flatnonzero(keep)
+    order = rows[np.argsort(units[rows], kind="stable")]
+    counts = np.bincount(units[order], minlength=M)
+    seg = np.concatenate([[0], np.cumsum(counts)])
+    nblk = -(-counts // UNIT_BLOCK)
+    pre = np.concatenate([[0], np.cumsum(nblk)])
+    B = int(pre[-1])
+    of = np.repeat(np.arange(M), nblk)
+    start = seg[of] + UNIT_BLOCK * (np.arange(B) - pre[of])
+    end = np.minimum(start + UNIT_BLOCK, seg[of + 1])
+    P = np.zeros((B, V + 1))
+    with np.errstate(all="ignore"):
+        for b0 in range(0, B, 1024):
+            b1 = min(B, b0 + 1024)
+            pos = start[b0:b1, None] + np.arange(UNIT_BLOCK)[None, :]
+            ok = pos < end[b0:b1, None]
+            r = order[np.where(ok, pos, 0)]
+            T = np.zeros((b1 - b0, UNIT_BLOCK + 1, V + 1))
+            if w is None:
+                zt, mt = Z[r], np.ones(r.shape)
+            else:
+                mt = w[r]
+                zt = mt[..., None] * Z[r]
+            T[:, 1:, :V] = np.where(ok[..., None], zt, 0.0)
+            T[:, 1:, V] = np.where(ok, mt, 0.0)
+            P[b0:b1] = np.add.accumulate(T, axis=1)[:, -1]
+        out = np.zeros((M, V + 1))
+        for j in np.flatnonzero(nblk):
+            out[j] = np.add.accumulate(np.concatenate([np.zeros((1, V + 1)), P[pre[j]:pre[j + 1]]]), axis=0)[-1]
+    return np.ascontiguousarray(out[:, V]), np.ascontiguousarray(out[:, :V])
+
+
+def unit_deviations(units, Y, C, mode):
+    """Row i with unit j inside [0, len(C)): ``(Y[i, v] - C[j, v])^2`` (N x V) under DEVIATIONS_SQUARES, the root of
+    their sum over v ascending from +0.0 (N,) under DEVIATIONS_NORM; +0.0 for the other rows."""
+    units, Y, C = np.asarray(units, dtype=np.int64), np.asarray(Y, dtype=np.float64), np.asarray(C, dtype=np.float64)
+    inside = (units >= 0) & (units < len(C))
+    with np.errstate(all="ignore"):
+        df = Y - C[np.where(inside, units, 0)]
+        sq = df * df
+        if mode == DEVIATIONS_SQUARES:
+            return np.where(inside[:, None], sq, 0.0)
+        s = np.zeros(len(units))
+        for v in range(Y.shape[1]):
+            s = s + sq[:, v]
+        return np.where(inside, np.sqrt(s), 0.0)
+
+
 class HotPathBackend:
     """Epoch template shared by the HIP backend and the test-only oracle backend:
     local per-prototype sums -> (all-reduce across sample shards) -> smoothing.
@@ -557,6 +638,39 @@ class HotPathBackend:
         np.add.at(h, (winners, self._y), 1.0 if self._sw is None else self._sw)
         h = self._reduce_host(h.reshape(-1)).reshape(M, n_classes)
         return h if self._sw is not None else h.astype(np.int64)
+
+    # -- per-unit statistics of a per-row quantity (BaseSom.unit_means, SomRegressor); host default ------
+    def unit_statistics(self, units, Y, w, M, want_std=False, want_err=False):
+        """Per-unit statistics of the rows Y (N x V float64) filed under ``units`` (N int64; entries outside
+        [0, M) are skipped), with weights w (N float64) or None -> (mass (M,), mean (M, V), std (M, V) | None,
+        err (M,) | None): ``mean = sums / mass`` (NaN for a unit without mass), ``std = sqrt(fold((y - mean)^2) /
+        mass)``, ``err = fold(||y - mean||_2)``, every fold in the order of ``unit_fold``.  This NumPy default is
+        the restatement of csrc/unit_sums.hip."""
+        units, Y, w = _unit_args(units, Y, w)
+        mass, sums = unit_fold(units, Y, w, M)
+        with np.errstate(all="ignore"):
+            mean = sums / mass[:, None]
+            std = err = None
+            if want_std:
+                m2, sq = unit_fold(units, unit_deviations(units, Y, mean, DEVIATIONS_SQUARES), w, M)
+                std = np.sqrt(sq / m2[:, None])
+            if want_err:
+                err = unit_fold(units, unit_deviations(units, Y, mean, DEVIATIONS_NORM)[:, None], w, M)[1][:, 0]
+        return mass, mean, std, err
+
+    _targets = None
+
+    def set_targets(self, Y):
+        """Attach float64 targets (N x V) of the resident rows (growth_criterion="target_error"); None detaches."""
+        self._targets = None if Y is None else np.ascontiguousarray(Y, dtype=np.float64).reshape(len(Y), -1)
+
+    def target_statistics(self, winners, M, want_std=False, want_err=False):
+        """``unit_statistics`` of the attached targets under the attached sample weights; one process only."""
+        if dist_info()[1] > 1:
+            raise ValueError("target statistics take one process")
+        if self._targets is None:
+            raise RuntimeError("no targets attached: call set_targets(Y) first")
+        return HotPathBackend.unit_statistics(self, winners, self._targets, self._sw, M, want_std, want_err)
 
     # -- sparse coding (BaseSom.transform, SomClassifier.predict_proba); host default ----------------
     def sparse_code(self, W, X, P=None, max_iter=1000, n_jobs=None):
@@ -1129,6 +1243,8 @@ class HipBackend(HotPathBackend):
         self._weighted = False
         self._incomplete = False
         self._metric = "euclidean"
+        self._targets = None     # (and the targets)
+        self._targets_attached = False
 
     def read_samples(self, rows):
         """Rows of the resident samples as float64 (exactly widened)."""
@@ -1914,6 +2030,129 @@ class HipBackend(HotPathBackend):
                    int(n_classes), int(M), hist.ctypes.data)
         return hist
 
+    # -- per-unit statistics of a per-row quantity (csrc/unit_sums.hip) ----------------------------------
+    def _unit_fold_host(self, units, Z, w, M):
+        mass, sums = np.empty(M), np.empty((M, Z.shape[1]))
+        self._call("dbgsom_ctx_unit_sums", self._ctx, units.ctypes.data, Z.ctypes.data, None if w is None else w.ctypes.data,
+                   units.size, int(M), Z.shape[1], mass.ctypes.data, sums.ctypes.data)
+        return mass, sums
+
+    def _unit_fold_device(self, units, Z, w, M):
+        V = int(Z.shape[1])
+        mass, sums = device_empty(Z, (M,), "float64"), device_empty(Z, (M, V), "float64")
+        self._producer_done(Z)
+        self._call("dbgsom_ctx_unit_sums_device", self._ctx, ctypes.c_void_p(units.data_ptr()),
+                   ctypes.c_void_p(Z.data_ptr()), int(Z.stride(0)) if Z.shape[0] > 1 else V,
+                   None if w is None else ctypes.c_void_p(w.data_ptr()), int(Z.shape[0]), int(M), V,
+                   ctypes.c_void_p(mass.data_ptr()), ctypes.c_void_p(sums.data_ptr()), V)
+        return mass, sums
+
+    def _unit_deviations_device(self, units, Y, C, mode):
+        N, V = int(Y.shape[0]), int(Y.shape[1])
+        out = device_empty(Y, (N, V) if mode == DEVIATIONS_SQUARES else (N, 1), "float64")
+        self._producer_done(Y)
+        self._call("dbgsom_ctx_unit_deviations_device", self._ctx, ctypes.c_void_p(units.data_ptr()),
+                   ctypes.c_void_p(Y.data_ptr()), int(Y.stride(0)) if N > 1 else V, N, ctypes.c_void_p(C.data_ptr()), V,
+                   int(C.shape[0]), V, int(mode), ctypes.c_void_p(out.data_ptr()), V)
+        return out
+
+    def _unit_device_arg(self, a, like, dtype, what):
+        """`a` as a contiguous array of `dtype` next to `like`: host arrays go up with ``put``"""
+        if a is None:
+            return None
+        if not is_device_array(a):
+            return self.put(np.ascontiguousarray(a, dtype=dtype), like)
+        if dtype_name(a) != dtype:
+            raise ValueError(f"{what} on the device must be {dtype}, got {dtype_name(a)}")
+        index = getattr(a.device, "index", None)
+        if index is not None and index != self.device_index:
+            raise ValueError(f"{what} lives on GPU {index}, this backend runs on GPU {self.device_index}")
+        return a.contiguous()
+
+    def unit_statistics(self, units, Y, w, M, want_std=False, want_err=False):
+        """The folds on the device (csrc/unit_sums.hip).  Host arrays: units, Y and w go up and M x (1 + V) doubles
+        come down per fold (dbgsom_ctx_unit_sums); the deviations between two folds are elementwise NumPy.  With
+        units, Y or w on this backend's device everything stays there (dbgsom_ctx_unit_sums_device,
+        dbgsom_ctx_unit_deviations_device; arguments given on the host are moved with ``put``) and the results
+        are arrays on that device."""
+        M = int(M)
+        if not 1 <= M <= _native.MAX_PROTOTYPES:
+            raise ValueError(f"M must be 1 .. {_native.MAX_PROTOTYPES}, got {M}")
+        like = next((a for a in (Y, units, w) if a is not None and is_device_array(a)), None)
+        if like is None:
+            units, Y, w = _unit_args(units, Y, w)
+            mass, sums = self._unit_fold_host(units, Y, w, M)
+            with np.errstate(all="ignore"):
+                mean = sums / mass[:, None]
+                std = err = None
+                if want_std:
+                    m2, sq = self._unit_fold_host(units, unit_deviations(units, Y, mean, DEVIATIONS_SQUARES), w, M)
+                    std = np.sqrt(sq / m2[:, None])
+                if want_err:
+                    dev = np.ascontiguousarray(unit_deviations(units, Y, mean, DEVIATIONS_NORM)[:, None])
+                    err = self._unit_fold_host(units, dev, w, M)[1][:, 0]
+            return mass, mean, std, err
+        units = self._unit_device_arg(units, like, "int64", "units").reshape(-1)
+        Y = self._unit_device_arg(Y, like, "float64", "the values")
+        Y = Y.reshape(int(units.shape[0]), -1)
+        w = self._unit_device_arg(w, like, "float64", "the weights")
+        if not 1 <= int(Y.shape[1]) <= _native.MAX_MIXTURE_VALUES:
+            raise ValueError(f"1 .. {_native.MAX_MIXTURE_VALUES} values per row, got {int(Y.shape[1])}")
+        if w is not None and tuple(w.shape) != tuple(units.shape):
+            raise ValueError("one weight per row")
+        ns = array_namespace(like)
+        mass, sums = self._unit_fold_device(units, Y, w, M)
+        mean = sums / mass[:, None]
+        std = err = None
+        if want_std:
+            m2, sq = self._unit_fold_device(units, self._unit_deviations_device(units, Y, mean, DEVIATIONS_SQUARES), w, M)
+            std = ns.sqrt(sq / m2[:, None])
+        if want_err:
+            err = self._unit_fold_device(units, self._unit_deviations_device(units, Y, mean, DEVIATIONS_NORM), w, M)[1][:, 0]
+        return mass, mean, std, err
+
+    def set_targets(self, Y):
+        """float64 targets (N x V) of the resident rows, copied next to them in HBM (a host array or an array on this
+        device); None detaches."""
+        if Y is None:
+            super().set_targets(None)
+            self._call("dbgsom_ctx_set_targets", self._ctx, None, 0, 0)
+            self._targets_attached = False
+            return
+        self._require_loaded()
+        if is_device_array(Y):
+            Yd = self._unit_device_arg(Y, Y, "float64", "the targets")
+            Yd = Yd.reshape(int(Yd.shape[0]), -1)
+            self._producer_done(Yd)
+            self._call("dbgsom_ctx_set_targets_device", self._ctx, ctypes.c_void_p(Yd.data_ptr()), int(Yd.shape[0]),
+                       int(Yd.shape[1]), int(Yd.shape[1]))
+            self._targets = Y     # (the host fallback of target_statistics fetches it when it is needed)
+        else:
+            super().set_targets(Y)
+            self._call("dbgsom_ctx_set_targets", self._ctx, self._targets.ctypes.data, self._targets.shape[0],
+                       self._targets.shape[1])
+        self._targets_attached = True
+
+    _targets_attached = False
+
+    def target_statistics(self, winners, M, want_std=False, want_err=False):
+        """-> (mass, mean, std | None, err | None) of the attached targets per unit, host arrays
+        (dbgsom_ctx_target_statistics); winners=None: the last epoch's (still in HBM)."""
+        if self._incomplete or self._other_metric:
+            if is_device_array(self._targets):
+                self._targets = self.fetch(self._targets).reshape(self._N, -1)
+            return super().target_statistics(winners, M, want_std, want_err)
+        if not self._targets_attached:
+            raise RuntimeError("no targets attached: call set_targets(Y) first")
+        M, V = int(M), int(self._targets.shape[1]) if len(self._targets.shape) > 1 else 1
+        idx = None if winners is None else np.ascontiguousarray(winners, dtype=np.int64)
+        mass, mean = np.empty(M), np.empty((M, V))
+        std = np.empty((M, V)) if want_std else None
+        err = np.empty(M) if want_err else None
+        self._call("dbgsom_ctx_target_statistics", self._ctx, None if idx is None else idx.ctypes.data, M, mass.ctypes.data,
+                   mean.ctypes.data, None if std is None else std.ctypes.data, None if err is None else err.ctypes.data)
+        return mass, mean, std, err
+
     # -- vertical growth on Voronoi subsets (f-4) -------------------------------------------------
     def partition(self, W, want_winners=False):
         """BMU of every resident sample + bucket order -> (samples per neuron, winners | None)."""
@@ -1995,6 +2234,8 @@ class HipBackend(HotPathBackend):
         self._incomplete = False
         self._metric = "euclidean"
         self._sw = None
+        self._targets = None
+        self._targets_attached = False
 
     def __del__(self):
         try:

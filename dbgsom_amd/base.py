@@ -222,9 +222,11 @@ class BaseSom(BaseEstimator):
             self._metric_fit = self._check_metric_fit(X, sample_weight)
             self._incomplete_fit = self._check_incomplete_fit(X, sample_weight)
             sample_weight = self._check_sample_weight(sample_weight, X)
+        if self.growth_criterion == "target_error" and not self._GROWS_ON_TARGETS:
+            raise ValueError(f"growth_criterion='target_error' needs a continuous target: it is SomRegressor's; "
+                             f"{type(self).__name__} takes 'quantization_error' or 'entropy'")
         if y is not None:
-            classes, y = np.unique(y, return_inverse=True)
-            self.classes_ = np.array(classes)
+            y = self._encode_targets(y)
         self.random_state_ = check_random_state(self.random_state)
         engine = self._engine()
         if is_device_array(X):
@@ -260,8 +262,19 @@ class BaseSom(BaseEstimator):
             self._sw = self._sw_global = None
             if hasattr(engine, "set_sample_weight") and getattr(engine, "_sw", None) is not None:
                 engine.set_sample_weight(None)   # (the backend object may serve another fit)
+            if getattr(engine, "_targets", None) is not None:
+                engine.set_targets(None)
             engine.release()
         return self
+
+    _GROWS_ON_TARGETS = False   # growth_criterion="target_error" (SomRegressor)
+
+    def _encode_targets(self, y):
+        """What ``fit`` makes of y before the map is trained -> the y handed on to ``_grow_som``, ``_label_prototypes``
+        and ``_grow_vertical``.  Default: class codes, the classes in ``classes_``."""
+        classes, y = np.unique(y, return_inverse=True)
+        self.classes_ = np.array(classes)
+        return y
 
     # -- metric="manhattan", metric="cosine" -------------------------------------------------------------
     _MANHATTAN = ("manhattan", "cityblock", "l1")
@@ -854,6 +867,8 @@ class BaseSom(BaseEstimator):
     def _calculate_growing_threshold(self, data: np.ndarray) -> float:
         if self.growth_criterion == "entropy":
             return self.spreading_factor
+        if self.growth_criterion == "target_error":
+            return self._target_growing_threshold()
         if self.threshold_method == "classical":
             return -data.shape[1] * log(self.spreading_factor)
         if self.threshold_method == "se":
@@ -866,6 +881,26 @@ class BaseSom(BaseEstimator):
                 spread = np.sqrt(np.true_divide(self._col_s2, max(self._n_effective() - 1, 0)))
             else:
                 spread = np.std(data, axis=0, ddof=1)
+            return float(150 * -log(self.spreading_factor) * np.linalg.norm(spread))
+        raise ValueError("threshold_method not supported. Must be 'se' or 'classical'.")
+
+    def _target_growing_threshold(self) -> float:
+        """``growing_threshold_`` under ``growth_criterion="target_error"``: the formula of the quantization-error
+        criterion with the targets in the place of X -- "se": ``150 * -log(spreading_factor) * ||std(y, ddof=1)||_2``
+        (weighted: divisor ``sum w - 1``, in float64), "classical": ``-T * log(spreading_factor)``."""
+        Y = self._fit_targets
+        if self.threshold_method == "classical":
+            return -Y.shape[1] * log(self.spreading_factor)
+        if self.threshold_method == "se":
+            if self._sw is None:
+                spread = np.std(Y, axis=0, ddof=1)
+            else:
+                if not self._w_total > 1:
+                    raise ValueError("threshold_method='se' needs a summed sample_weight above 1 "
+                                     "(frequency weights: the divisor is sum w - 1)")
+                w = self._sw[:, None]
+                mean = (w * Y).sum(axis=0) / self._w_total
+                spread = np.sqrt((w * (Y - mean) ** 2).sum(axis=0) / (self._w_total - 1))
             return float(150 * -log(self.spreading_factor) * np.linalg.norm(spread))
         raise ValueError("threshold_method not supported. Must be 'se' or 'classical'.")
 
@@ -887,6 +922,7 @@ class BaseSom(BaseEstimator):
 
             epochs = tqdm(iterable=epochs, unit=" epochs")
         need_assign = self.growth_criterion == "entropy"
+        on_targets = self.growth_criterion == "target_error"
         n_classes = 0
         if need_assign:
             if isinstance(data, DeviceSamples):
@@ -909,6 +945,13 @@ class BaseSom(BaseEstimator):
         manhattan = self._metric_fit == "manhattan"
         cosine = self._metric_fit == "cosine"
         resident = hasattr(engine, "write_weight_rows") and not incomplete and not self._metric_fit
+        # growth on the target's error: the targets go next to the rows once; an epoch that leaves its winners in HBM
+        # is followed by target_statistics on them, every other epoch hands its winners over
+        assign = {}
+        if on_targets:
+            engine.set_targets(y)
+            if not resident:
+                assign = {"want_assignments": True}
         on_device = False     # the current prototypes are in HBM, lat.W is stale
         ran = False
         self._growth_epochs = []
@@ -921,20 +964,20 @@ class BaseSom(BaseEstimator):
 
             if incomplete:
                 res = engine.epoch_masked(w_in, self._distance_matrix, self._calculate_current_sigma(),
-                                          self._gamma(), n_classes=n_classes if need_assign else 0)
+                                          self._gamma(), n_classes=n_classes if need_assign else 0, **assign)
             elif manhattan:
                 res = engine.epoch_manhattan(w_in, self._distance_matrix, self._calculate_current_sigma(),
                                              self._gamma(), self.centres_layout,
-                                             n_classes=n_classes if need_assign else 0)
+                                             n_classes=n_classes if need_assign else 0, **assign)
             elif cosine:
                 res = engine.epoch_cosine(w_in, self._distance_matrix, self._calculate_current_sigma(),
                                           self._gamma(), self.centres_layout,
-                                          n_classes=n_classes if need_assign else 0)
+                                          n_classes=n_classes if need_assign else 0, **assign)
             else:
                 res = engine.epoch(w_in, self._distance_matrix, self._calculate_current_sigma(),
                                    self._gamma(), self.centres_layout,
                                    n_classes=n_classes if need_assign else 0,
-                                   **({"keep_on_device": True} if resident else {}))
+                                   **({"keep_on_device": True} if resident else {}), **assign)
             ran = True
             if manhattan and not np.isfinite(res.new_weights).all():
                 # L1 distances grow with the number of features while gamma = 1 / total variance does not: once
@@ -964,6 +1007,9 @@ class BaseSom(BaseEstimator):
                 lat.set_errors(np.array([scipy.stats.entropy(row[: np.flatnonzero(row).max() + 1]
                                                              if row.any() else row[:0], base=2)
                                          for row in res.class_hist]))
+            elif on_targets:  # err_j = sum over the unit's rows of w_i ||y_i - mean_j||_2
+                lat.set_errors(np.asarray(engine.target_statistics(None if resident else res.winners, len(lat),
+                                                                   want_err=True)[3]))
             else:
                 lat.set_errors(res.errors)
 
@@ -1774,6 +1820,7 @@ class BaseSom(BaseEstimator):
         row come down beside ``score_samples``'s 16.  Arguments, X and the refusals are ``score_samples``'s."""
         check_is_fitted(self)
         M = len(self.weights_)
+        values = self._host(values)   # (a per-unit result that lives in HBM, unit_means of a tensor)
         try:
             Y = np.asarray(values, dtype=np.float64)
         except (TypeError, ValueError):
@@ -1797,6 +1844,99 @@ class BaseSom(BaseEstimator):
         check_is_fitted(self)
         return self.posterior_mean(X, np.asarray(list(self.neurons_), dtype=np.float64).reshape(len(self.weights_), -1),
                                    bandwidth, priors)
+
+    # ------------------------------------------------------------------------------------------
+    # a per-row quantity on the map
+    # ------------------------------------------------------------------------------------------
+    def _check_row_values(self, values, n, on_device, name="values"):
+        """-> (float64 (n, V) values, flat): a host array, or with ``on_device`` a tensor left where it is"""
+        say = (f"{name} must be real numbers of shape ({n},) or ({n}, V) with V <= {MAX_MIXTURE_VALUES}, one row per "
+               f"row of X")
+        if on_device and is_device_array(values):
+            Z = values
+            kind = dtype_name(Z)
+            if not kind.startswith(("float", "bfloat", "int", "uint", "bool")):
+                raise ValueError(f"{say}; got dtype {kind}")
+            shape = tuple(int(v) for v in Z.shape)
+        else:
+            try:
+                Z = np.asarray(self._host(values))
+            except (TypeError, ValueError):
+                raise ValueError(f"{say}; got {values!r}") from None
+            if Z.dtype.kind not in "fiub":
+                raise ValueError(f"{say}; got dtype {Z.dtype}")
+            shape = Z.shape
+        if len(shape) not in (1, 2):
+            raise ValueError(f"{say}; got {len(shape)} dimensions (shape {shape})")
+        if shape[0] != n:
+            raise ValueError(f"{say}; got {shape[0]} rows for {n} rows of X")
+        flat = len(shape) == 1
+        V = 1 if flat else shape[1]
+        if V < 1:
+            raise ValueError(f"{say}; got no column")
+        if V > MAX_MIXTURE_VALUES:
+            raise ValueError(f"{name} has {V} columns, above the {MAX_MIXTURE_VALUES} the kernel sums per row: use "
+                             "several calls")
+        if isinstance(Z, np.ndarray):
+            return np.ascontiguousarray(Z, dtype=np.float64).reshape(n, V), flat
+        return (Z if dtype_name(Z) == "float64" else Z.double()).reshape(n, V), flat
+
+    def _check_row_weights(self, sample_weight, n, on_device):
+        """-> None or float64 (n,) weights, non-negative and finite: a host array, or with ``on_device`` a tensor"""
+        if sample_weight is None:
+            return None
+        say = f"sample_weight must be {n} finite numbers >= 0, one per row of X"
+        if on_device and is_device_array(sample_weight):
+            w = sample_weight
+            if len(w.shape) != 1 or int(w.shape[0]) != n:
+                raise ValueError(f"{say}; got shape {tuple(int(v) for v in w.shape)}")
+            w = w if dtype_name(w) == "float64" else w.double()
+            ns = array_namespace(w)
+            if not bool(ns.isfinite(w).all()) or not bool((w >= 0).all()):
+                raise ValueError(f"{say}; got a negative or non-finite weight")
+            return w
+        try:
+            w = np.asarray(self._host(sample_weight), dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{say}; got {sample_weight!r}") from None
+        if w.shape != (n,):
+            raise ValueError(f"{say}; got shape {w.shape}")
+        if not np.isfinite(w).all() or not (w >= 0).all():
+            raise ValueError(f"{say}; got a negative or non-finite weight")
+        return np.ascontiguousarray(w)
+
+    def unit_means(self, X, values, sample_weight=None, return_std=False, return_mass=False):
+        """The component plane of an external variable: for every unit the weighted mean of ``values`` over the rows
+        of X whose best matching unit it is -- ``(len(weights_),)`` for ``values`` of shape ``(n,)``, ``(len(weights_),
+        V)`` for ``(n, V)`` with ``V <= 16``, float64, NaN for a unit without mass.  ``return_std`` adds the per-unit
+        standard deviation ``sqrt(sum w (z - mean)^2 / sum w)`` in the same shape, ``return_mass`` the mass ``sum w``
+        (the number of rows without weights), ``(len(weights_),)``: the result is then a tuple ``(mean[, std][,
+        mass])``.  ``posterior_mean(Q, som.unit_means(X, z))`` reads the plane back at new rows.
+
+        The units are ``predict``'s, so X is whatever ``predict`` takes: a host array, a tensor on the estimator's GPU
+        (the results are tensors on its device; ``values`` and ``sample_weight`` may be host arrays or tensors), scipy
+        sparse rows, rows with NaN under ``missing_values``, any ``metric``.  A row without a unit (-1) takes no part, a
+        row of weight 0 neither (a NaN stored under weight 0 is never read); NaN and infinities in ``values`` are
+        plain IEEE and reach their own (unit, column) only.
+
+        The sums run on the GPU in a fixed order (csrc/unit_sums.hip): a unit's rows ascending, blocks of 128 added
+        from +0.0, then the blocks ascending; the term of a row is ``w * z`` rounded once.  So a host array, a tensor and
+        CSR rows of the same data give the same bits, and all-ones weights give the bits of no weights.  ``mean = sums /
+        mass``, one division.  Refused with a ``ValueError``: ``values`` of the wrong length, rank or dtype or with more
+        than 16 columns; a negative, non-finite or wrong-length ``sample_weight``."""
+        check_is_fitted(self)
+        X = self._check_query(X)
+        n, on_device = int(X.shape[0]), is_device_array(X)
+        Z, flat = self._check_row_values(values, n, on_device)
+        w = self._check_row_weights(sample_weight, n, on_device)
+        units = self._get_winning_neurons(X, n_bmu=1)[1]
+        mass, mean, std, _ = self._engine().unit_statistics(units, Z, w, len(self.weights_), want_std=bool(return_std))
+        out = [mean[:, 0] if flat else mean]
+        if return_std:
+            out.append(std[:, 0] if flat else std)
+        if return_mass:
+            out.append(mass)
+        return out[0] if len(out) == 1 else tuple(out)
 
     def _lattice_edges(self) -> np.ndarray:
         """The undirected edges of the fitted lattice as an (E, 2) int32 array of indices into ``weights_`` /

@@ -384,6 +384,13 @@ size_t bucket_sort_workspace_bytes(int64_t N, int64_t M);
 int launch_bucket_sort(const int64_t *idx, int64_t N, int64_t M, int32_t *order, void *ws,
                        hipStream_t s);
 const uint32_t *bucket_sort_seg_start(const void *ws, int64_t N, int64_t M);
+// per-unit sums of N x V float64 values over the stable bucket order, blocks of 128 list rows and a fold over the
+// blocks, and the elementwise deviations from M x V centres (unit_sums.hip); arguments checked by the callers
+size_t unit_sums_workspace_bytes(int64_t N, int64_t M, int V, bool weighted);
+int launch_unit_sums(const int64_t *unit, const double *Z, int64_t ldz, const double *w, int64_t N, int64_t M, int V,
+                     double *mass, double *sums, int64_t lds, void *ws, size_t ws_bytes, hipStream_t s);
+int launch_unit_deviations(const int64_t *unit, const double *Y, int64_t ldy, int64_t N, const double *C, int64_t ldc,
+                           int64_t M, int V, int mode, double *out, int64_t ldo, hipStream_t s);
 // the filtered search with everything the engine may add to the public dbgsom_bmu_filtered call
 // optional per-stage timing of dbgsom_bmu_filtered (bench / profiling): events on the caller's stream
 struct StageTimer {

@@ -321,6 +321,11 @@ struct dbgsom_ctx {
     // reductions then run their weighted forms
     DevBuf sw, wh_order, wh_ws;
     bool has_weights = false;
+    // float64 targets of the resident rows (dbgsom_ctx_set_targets: N x target_V, contiguous), and the buffers of the
+    // per-unit sums (unit_sums.hip): workspace, staged host inputs, the small per-unit results, per-row deviations
+    DevBuf ty, us_ws, us_in, us_out, us_dev;
+    bool has_targets = false;
+    int target_V = 0;
     // topology
     int64_t topoM = 0;
     DevBuf hop, hop_stage;
@@ -1273,7 +1278,8 @@ int dbgsom_ctx_create(int device, dbgsom_ctx **out) {
      &(c)->shard_gather, &(c)->sw, &(c)->wh_order, &(c)->wh_ws, &(c)->sc_ws, &(c)->sc_x, &(c)->sc_w, &(c)->sc_p, &(c)->sc_code, &(c)->sc_proba, &(c)->sc_cnt, &(c)->wt,  \
      &(c)->mk_ws, &(c)->mk_x, &(c)->mk_w, &(c)->mk_idx, &(c)->mk_dist, &(c)->mf_nobs, &(c)->mf_x64, &(c)->mf_wt, &(c)->mf_w,   \
      &(c)->mf_wn, &(c)->mf_idx, &(c)->mf_dist, &(c)->mf_kw, &(c)->mf_sums, &(c)->mf_acc_ws, &(c)->mf_sm_ws, &(c)->mf_scal, \
-     &(c)->pd_out, &(c)->kn_ws, &(c)->kn_idx, &(c)->kn_dist, &(c)->de_h, &(c)->ce_g, &(c)->ce_ws, &(c)->ex_state, &(c)->rc_state, &(c)->l1_ws, &(c)->cos_u, &(c)->cos_v}
+     &(c)->pd_out, &(c)->kn_ws, &(c)->kn_idx, &(c)->kn_dist, &(c)->de_h, &(c)->ce_g, &(c)->ce_ws, &(c)->ex_state, &(c)->rc_state, &(c)->l1_ws, &(c)->cos_u, &(c)->cos_v,   \
+     &(c)->ty, &(c)->us_ws, &(c)->us_in, &(c)->us_out, &(c)->us_dev}
 
 int dbgsom_ctx_destroy(dbgsom_ctx *c) {
     if (!c) return DBGSOM_OK;
@@ -1463,6 +1469,7 @@ static void reset_training_state(dbgsom_ctx *c) {
     c->hint_valid = c->last_idx_valid = c->part_valid = false;
     c->has_labels = false;
     c->has_weights = false;
+    c->has_targets = false;
     c->incomplete = false;
     c->cos_u_ready = false;   // (u belongs to the rows that were resident)
     c->policy.reset();
@@ -3540,6 +3547,174 @@ int dbgsom_ctx_class_histogram_weighted(dbgsom_ctx *c, const int64_t *idx_host, 
                                         c->sw.as<double>(), s.N, M, n_classes, hd, c->stream));
     TRY(run_allreduce(c, hd, n));
     DBGSOM_HIP_CHECK(hipMemcpyAsync(hist_host, hd, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    return sync(c);
+}
+
+// ------------------------------------------------------------------------------------------
+// per-unit sums of a per-row quantity, and the statistics of attached targets: csrc/unit_sums.hip
+// ------------------------------------------------------------------------------------------
+namespace {
+
+int unit_args_check(const char *fn, bool pointers, int64_t N, int64_t M, int n_values, int64_t ld_in, int64_t ld_out) {
+    const char *why = nullptr;
+    if (!pointers) why = "null pointer";
+    else if (N < 0 || N > 0x7fffffffLL) why = "N must be 0 .. 2^31 - 1";
+    else if (M < 1 || M > DBGSOM_MAX_PROTOTYPES) why = "M must be 1 .. DBGSOM_MAX_PROTOTYPES";
+    else if (n_values < 1 || n_values > DBGSOM_MAX_MIXTURE_VALUES) why = "n_values must be 1 .. DBGSOM_MAX_MIXTURE_VALUES";
+    else if (ld_in < n_values) why = "a row stride of the input is below n_values";
+    else if (ld_out < n_values) why = "a row stride of the output is below n_values";
+    if (why) { set_error("%s: %s", fn, why); return DBGSOM_EINVAL; }
+    return DBGSOM_OK;
+}
+
+// the fold on device buffers, on the context's stream, not waited for
+int unit_sums_launch(dbgsom_ctx *c, const int64_t *unit, const double *Z, int64_t ldz, const double *w, int64_t N, int64_t M,
+                     int V, double *mass, double *sums, int64_t lds) {
+    TRY(c->us_ws.reserve(unit_sums_workspace_bytes(N, M, V, w != nullptr)));
+    return launch_unit_sums(unit, Z, ldz, w, N, M, V, mass, sums, lds, c->us_ws.p, c->us_ws.cap, c->stream);
+}
+
+// out[j, v] = num[j, v] / mass[j], or its square root: one division (and one root) per entry
+__global__ __launch_bounds__(256) void unit_ratio_kernel(const double *num, const double *__restrict__ mass, int64_t M,
+                                                         int V, int root, double *out) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= M * V) return;
+    const double q = num[e] / mass[e / V];
+    out[e] = root ? __dsqrt_rn(q) : q;
+}
+
+}  // namespace
+
+int dbgsom_ctx_unit_sums(dbgsom_ctx *c, const int64_t *unit_host, const double *Z_host, const double *w_host, int64_t N,
+                         int64_t M, int n_values, double *mass_host, double *sums_host) {
+    TRY(unit_args_check(__func__, mass_host && sums_host && (N == 0 || (unit_host && Z_host)), N, M, n_values, n_values,
+                        n_values));
+    CTX_CHECK(c);
+    const int V = n_values;
+    const size_t bu = align_up((size_t)N * 8), bz = align_up((size_t)N * V * 8), bw = w_host ? bu : 0;
+    TRY(c->us_in.reserve(bu + bz + bw + 256));
+    TRY(c->us_out.reserve(align_up((size_t)M * (V + 1) * 8)));
+    char *base = c->us_in.as<char>();
+    int64_t *unit = reinterpret_cast<int64_t *>(base);
+    double *Z = reinterpret_cast<double *>(base + bu);
+    double *w = w_host ? reinterpret_cast<double *>(base + bu + bz) : nullptr;
+    if (N) {
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(unit, unit_host, (size_t)N * 8, hipMemcpyHostToDevice, c->stream));
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(Z, Z_host, (size_t)N * V * 8, hipMemcpyHostToDevice, c->stream));
+        if (w) DBGSOM_HIP_CHECK(hipMemcpyAsync(w, w_host, (size_t)N * 8, hipMemcpyHostToDevice, c->stream));
+        c->x_up((size_t)N * 8 * (1 + V + (w ? 1 : 0)));
+    }
+    double *mass = c->us_out.as<double>(), *sums = mass + M;
+    int rc = unit_sums_launch(c, unit, Z, V, w, N, M, V, mass, sums, V);
+    if (rc == DBGSOM_OK) {
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(mass_host, mass, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(sums_host, sums, (size_t)M * V * 8, hipMemcpyDeviceToHost, c->stream));
+        c->x_down((size_t)M * (V + 1) * 8);
+    }
+    return finish_query(c, rc);
+}
+
+int dbgsom_ctx_unit_sums_device(dbgsom_ctx *c, const int64_t *unit_dev, const double *Z_dev, int64_t ldz, const double *w_dev,
+                                int64_t N, int64_t M, int n_values, double *mass_dev, double *sums_dev, int64_t lds) {
+    TRY(unit_args_check(__func__, mass_dev && sums_dev && (N == 0 || (unit_dev && Z_dev)), N, M, n_values, ldz, lds));
+    CTX_CHECK(c);
+    return finish_query(c, unit_sums_launch(c, unit_dev, Z_dev, ldz, w_dev, N, M, n_values, mass_dev, sums_dev, lds));
+}
+
+int dbgsom_ctx_unit_deviations_device(dbgsom_ctx *c, const int64_t *unit_dev, const double *Y_dev, int64_t ldy, int64_t N,
+                                      const double *C_dev, int64_t ldc, int64_t M, int n_values, int mode, double *out_dev,
+                                      int64_t ldo) {
+    DBGSOM_REQUIRE(mode == DBGSOM_DEVIATIONS_SQUARES || mode == DBGSOM_DEVIATIONS_NORM,
+                   "mode must be DBGSOM_DEVIATIONS_SQUARES or DBGSOM_DEVIATIONS_NORM");
+    TRY(unit_args_check(__func__, N == 0 || (unit_dev && Y_dev && C_dev && out_dev), N, M, n_values, ldy < ldc ? ldy : ldc,
+                        mode == DBGSOM_DEVIATIONS_SQUARES ? ldo : n_values));
+    CTX_CHECK(c);
+    return finish_query(c, launch_unit_deviations(unit_dev, Y_dev, ldy, N, C_dev, ldc, M, n_values, mode, out_dev, ldo,
+                                                  c->stream));
+}
+
+int dbgsom_ctx_set_targets(dbgsom_ctx *c, const double *Y_host, int64_t N, int n_values) {
+    if (!Y_host) {
+        CTX_CHECK(c);
+        c->has_targets = false;
+        return DBGSOM_OK;
+    }
+    DBGSOM_REQUIRE(n_values >= 1 && n_values <= DBGSOM_MAX_MIXTURE_VALUES, "n_values must be 1 .. DBGSOM_MAX_MIXTURE_VALUES");
+    CTX_CHECK(c);
+    TRY(loaded(c, __func__));
+    DBGSOM_REQUIRE(N == c->xs.N, "one row of targets per resident sample");
+    c->has_targets = false;
+    TRY(c->ty.reserve((size_t)N * n_values * 8));
+    DBGSOM_HIP_CHECK(hipMemcpyAsync(c->ty.p, Y_host, (size_t)N * n_values * 8, hipMemcpyHostToDevice, c->stream));
+    c->x_up((size_t)N * n_values * 8);
+    c->target_V = n_values;
+    c->has_targets = true;
+    return sync(c);
+}
+
+int dbgsom_ctx_set_targets_device(dbgsom_ctx *c, const double *Y_dev, int64_t N, int64_t ldy, int n_values) {
+    DBGSOM_REQUIRE(Y_dev, "null pointer");
+    DBGSOM_REQUIRE(n_values >= 1 && n_values <= DBGSOM_MAX_MIXTURE_VALUES, "n_values must be 1 .. DBGSOM_MAX_MIXTURE_VALUES");
+    DBGSOM_REQUIRE(ldy >= n_values, "ldy below n_values");
+    CTX_CHECK(c);
+    TRY(loaded(c, __func__));
+    DBGSOM_REQUIRE(N == c->xs.N, "one row of targets per resident sample");
+    c->has_targets = false;
+    TRY(c->ty.reserve((size_t)N * n_values * 8));
+    DBGSOM_HIP_CHECK(hipMemcpy2DAsync(c->ty.p, (size_t)n_values * 8, Y_dev, (size_t)ldy * 8, (size_t)n_values * 8, (size_t)N,
+                                      hipMemcpyDeviceToDevice, c->stream));
+    c->target_V = n_values;
+    c->has_targets = true;
+    return sync(c);
+}
+
+int dbgsom_ctx_target_statistics(dbgsom_ctx *c, const int64_t *idx_host, int64_t M, double *mass_host, double *mean_host,
+                                 double *std_host, double *err_host) {
+    DBGSOM_REQUIRE(mass_host && mean_host, "null pointer");
+    DBGSOM_REQUIRE(M >= 1 && M <= DBGSOM_MAX_PROTOTYPES, "M must be 1 .. DBGSOM_MAX_PROTOTYPES");
+    CTX_CHECK(c);
+    TRY(loaded(c, __func__));
+    DBGSOM_REQUIRE(c->coll_nranks == 1 && !c->allreduce, "more than one rank");
+    if (!c->has_targets) { set_error("target statistics requested but no targets attached (dbgsom_ctx_set_targets)"); return DBGSOM_ESTATE; }
+    Samples &s = c->xs;
+    const int64_t N = s.N;
+    const int V = c->target_V;
+    const int64_t *idx = nullptr;
+    if (idx_host) {
+        TRY(c->qidx.reserve((size_t)N * 8));
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(c->qidx.p, idx_host, (size_t)N * 8, hipMemcpyHostToDevice, c->stream));
+        idx = c->qidx.as<int64_t>();
+    } else {
+        if (!c->last_idx_valid) { set_error("no winners of a previous epoch in HBM"); return DBGSOM_ESTATE; }
+        idx = c->idx[c->icur].as<int64_t>();
+    }
+    // [mass | sums | mean | mass of the second fold | squares / std | err]
+    const size_t mv = (size_t)M * V;
+    TRY(c->us_out.reserve((3 * mv + 3 * (size_t)M) * 8));
+    if (std_host || err_host) TRY(c->us_dev.reserve((size_t)N * V * 8));
+    double *mass = c->us_out.as<double>(), *sums = mass + M, *mean = sums + mv, *mass2 = mean + mv, *sq = mass2 + M,
+           *err = sq + mv;
+    const double *Y = c->ty.as<double>(), *w = c->has_weights ? c->sw.as<double>() : nullptr;
+    double *dev = c->us_dev.as<double>();
+    TRY(unit_sums_launch(c, idx, Y, V, w, N, M, V, mass, sums, V));
+    hipLaunchKernelGGL(unit_ratio_kernel, dim3(grid1d((int64_t)mv)), dim3(256), 0, c->stream, (const double *)sums,
+                       (const double *)mass, M, V, 0, mean);
+    TRY(launch_status("unit_ratio_kernel"));
+    DBGSOM_HIP_CHECK(hipMemcpyAsync(mass_host, mass, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
+    DBGSOM_HIP_CHECK(hipMemcpyAsync(mean_host, mean, mv * 8, hipMemcpyDeviceToHost, c->stream));
+    if (std_host) {
+        TRY(launch_unit_deviations(idx, Y, V, N, mean, V, M, V, DBGSOM_DEVIATIONS_SQUARES, dev, V, c->stream));
+        TRY(unit_sums_launch(c, idx, dev, V, w, N, M, V, mass2, sq, V));
+        hipLaunchKernelGGL(unit_ratio_kernel, dim3(grid1d((int64_t)mv)), dim3(256), 0, c->stream, (const double *)sq,
+                           (const double *)mass2, M, V, 1, sq);
+        TRY(launch_status("unit_ratio_kernel"));
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(std_host, sq, mv * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (err_host) {
+        TRY(launch_unit_deviations(idx, Y, V, N, mean, V, M, V, DBGSOM_DEVIATIONS_NORM, dev, 1, c->stream));
+        TRY(unit_sums_launch(c, idx, dev, 1, w, N, M, 1, mass2, err, 1));
+        DBGSOM_HIP_CHECK(hipMemcpyAsync(err_host, err, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
+    }
     return sync(c);
 }
 

@@ -1259,6 +1259,53 @@ int dbgsom_ctx_node_statistics(dbgsom_ctx *ctx, const double *W_host, int64_t M,
 int dbgsom_ctx_class_histogram(dbgsom_ctx *ctx, const int64_t *idx_host, int64_t n_classes,
                                int64_t M, int64_t *hist_host);
 
+/* ---- per-unit sums of a per-row quantity: a target or an external variable on the map (csrc/unit_sums.hip) ---- */
+/* unit: N int64; Z: N x n_values float64, rows ldz >= n_values apart, 1 <= n_values <= DBGSOM_MAX_MIXTURE_VALUES (the
+ * result is a legal Y of dbgsom_mixture); w: N float64 weights or NULL; 1 <= M <= DBGSOM_MAX_PROTOTYPES.
+ * The list L_j of unit j holds the rows i with unit[i] == j, ascending in i, without the rows with w_i == 0 (a NaN
+ * stored under weight 0 is never read).  A row's term is z_iv, or w_i * z_iv rounded once and never fused; its mass
+ * term 1.0 or w_i.  L_j is cut into blocks of 128 consecutive list positions, and
+ *   P[b][v]    = (((+0.0 + t_0) + t_1) + ...)            the terms of block b in list order, every add rounded
+ *   sums[j][v] = (((+0.0 + P[0][v]) + P[1][v]) + ...)    the blocks of unit j ascending;  mass[j] likewise
+ * An empty list gives +0.0 bitwise.  Rows whose unit lies outside [0, M) (the -1 of a search that found nothing) are
+ * skipped, never followed.  NaN and infinities are plain IEEE: they reach their own (unit, column) only.  The order
+ * depends on (unit, Z, w) alone; all weights 1.0 give the bits of no weights.
+ *
+ * None of these calls takes a stream: each runs on the context's stream and waits for it.  Argument errors -- a null
+ * pointer, M or n_values out of range, a row stride below n_values, N < 0 or N >= 2^31, a bad mode -- are DBGSOM_EINVAL
+ * before any launch.  N == 0 writes +0.0 sums and masses and launches nothing else.
+ *
+ * dbgsom_ctx_unit_sums: host arrays; unit, Z (contiguous) and w go up ("x_upload_bytes"), mass (M) and sums (M x
+ * n_values, contiguous) come down ("x_download_bytes").  No resident rows are needed.
+ * dbgsom_ctx_unit_sums_device: everything in HBM, nothing crosses PCIe; sums rows lds >= n_values apart; nothing of a
+ * row of Z or of sums past n_values is touched.
+ * dbgsom_ctx_unit_deviations_device: for row i with unit j inside [0, M) and centres C (M x n_values, rows ldc apart),
+ * mode DBGSOM_DEVIATIONS_SQUARES writes (y_iv - C_jv)^2 to out (N x n_values, rows ldo apart), mode
+ * DBGSOM_DEVIATIONS_NORM writes sqrt(sum_v (y_iv - C_jv)^2) to out (N values; ldo is not read): the sum over v
+ * ascending from +0.0, difference, square and add each rounded, the root correctly rounded.  Rows outside [0, M) get
+ * +0.0. */
+#define DBGSOM_DEVIATIONS_SQUARES 0
+#define DBGSOM_DEVIATIONS_NORM 1
+int dbgsom_ctx_unit_sums(dbgsom_ctx *ctx, const int64_t *unit_host, const double *Z_host, const double *w_host, int64_t N,
+                         int64_t M, int n_values, double *mass_host, double *sums_host);
+int dbgsom_ctx_unit_sums_device(dbgsom_ctx *ctx, const int64_t *unit_dev, const double *Z_dev, int64_t ldz,
+                                const double *w_dev, int64_t N, int64_t M, int n_values, double *mass_dev,
+                                double *sums_dev, int64_t lds);
+int dbgsom_ctx_unit_deviations_device(dbgsom_ctx *ctx, const int64_t *unit_dev, const double *Y_dev, int64_t ldy,
+                                      int64_t N, const double *C_dev, int64_t ldc, int64_t M, int n_values, int mode,
+                                      double *out_dev, int64_t ldo);
+/* Targets of the resident rows: N x n_values float64 (host: contiguous; device: rows ldy apart) copied next to the
+ * rows; the copy belongs to the context.  N must be the resident N.  (NULL, 0, 0) detaches; a reload detaches too. */
+int dbgsom_ctx_set_targets(dbgsom_ctx *ctx, const double *Y_host, int64_t N, int n_values);
+int dbgsom_ctx_set_targets_device(dbgsom_ctx *ctx, const double *Y_dev, int64_t N, int64_t ldy, int n_values);
+/* Per-unit statistics of the attached targets.  The winners are idx_host (N int64), or with NULL those the last epoch
+ * left in HBM (DBGSOM_ESTATE without them, as dbgsom_ctx_class_histogram); the weights are the attached sample weights,
+ * if any.  mass (M), mean (M x n_values) = sums / mass, one division, NaN for an empty unit; std (may be NULL)
+ * std_jv = sqrt(fold(SQUARES)_jv / mass_j); err (M, may be NULL) err_j = fold(NORM)_j: the weighted sum over the
+ * unit's rows of ||y_i - mean_j||_2.  DBGSOM_ESTATE without targets; more than one rank: DBGSOM_EINVAL. */
+int dbgsom_ctx_target_statistics(dbgsom_ctx *ctx, const int64_t *idx_host, int64_t M, double *mass_host,
+                                 double *mean_host, double *std_host, double *err_host);
+
 /* ---- covariance times a block of directions: the pass of the linear initialisation (covariance.hip) ---- */
 #define DBGSOM_MAX_DIRECTIONS 8
 /* With c_ik = x_ik - mean_k (x widened to float64, the difference rounded once):
