@@ -18,8 +18,7 @@
 
 #include "anchor_chain.h"
 #include "common.h"
-#include "lean_gate.h"
-#include "search_policy.h"
+#include "epoch_control.h"
 
 namespace dbgsom {
 
@@ -341,9 +340,7 @@ struct dbgsom_ctx {
     DevBuf wt;
     int64_t csr_densify_below = 1024;
     int icur = 0;            // idx[icur]: winners of the last epoch (the hint)
-    bool hint_valid = false;
-    int64_t hintM = 0;
-    bool last_idx_valid = false;  // idx[icur] holds the winners of the last epoch / partition
+    ResidentSearchState search;   // what the last search left in idx[icur], `dist` and the bucket order (epoch_control.h)
     int64_t sumsM = 0;
     // partition (vertical growth)
     DevBuf part_order, part_ws, part_counts;
@@ -351,12 +348,7 @@ struct dbgsom_ctx {
     bool part_valid = false;
     // which form of the filtered search runs next, and what it has learnt (search_policy.h)
     SearchPolicy policy;
-    // `dist` holds the exact distances of the resident samples to the rows idx[icur] of Wb[distW_buf]
-    // (distW_M rows) as the last epoch's search left them: the hinted pruning bound (filter.hip 2c)
-    bool dist_bound_valid = false;
-    int distW_buf = 0;
-    int64_t distW_M = 0;
-    DevBuf shiftb;
+    DevBuf shiftb;   // the prototypes' shifts of the hinted pruning bound (filter.hip 2c)
     // last epoch
     bool last_filtered = false;
     int64_t last_filter_M = 0, last_filter_N = 0, last_filter_d = 0;
@@ -396,19 +388,9 @@ struct dbgsom_ctx {
     FilterAux faux;   // this context's stage timer and side streams of the filtered search (FilteredCall::aux)
     // anchor buckets seed the stateless pruning search of the resident samples ("anchor_seeds", default on)
     int anchor_seeds = 1;
-    int64_t anchor_builds = 0, anchor_searches = 0;   // buckets built / searches seeded from them so far
-    bool anchors_built_now = false;     // the running epoch built the buckets: its clock is not the arm's
-    bool last_anchor_seeded = false;    // the last filtered search of an epoch took its seeds from the anchors
-    // the lean form of the anchor-seeded search (DBGSOM_ANCHOR_LISTS_ONLY): when an epoch takes it (lean_gate.h),
-    // whether the last search did, the plan of the last search, and how many epochs did so far ("lean_searches")
-    LeanGate lean_gate;
-    bool last_lean = false;
-    int last_plan_key = 0;
-    int64_t lean_searches = 0;
-    // mean list length of the last pruning epoch the cheap pre-pass seeded, and the map it ran on: what the
-    // anchors' lists are held against (dbgsom_ctx_epoch)
-    double prepass_mean = NAN;
-    int64_t prepass_M = 0;
+    // buckets built / searches seeded from them / epochs that took the lean form of such a search so far
+    int64_t anchor_builds = 0, anchor_searches = 0, lean_searches = 0;
+    AnchorControl anchor;   // when the anchors seed a search, in which form, and the valve (epoch_control.h)
 };
 
 namespace {
@@ -577,6 +559,16 @@ int gather_anchor_rows(dbgsom_ctx *c, Samples &s, const std::vector<int64_t> &ro
     return DBGSOM_OK;
 }
 
+// a filtered search of the samples `s` under the M x s.dp prototypes W (norms ww) on the context's stream
+FilteredCall filtered_call(dbgsom_ctx *c, Samples &s, const double *W, int64_t M, const double *ww) {
+    FilteredCall call;
+    call.aux = &c->faux;
+    call.X = s.Xb; call.x_dtype = s.bdtype; call.N = s.N; call.d = s.dp; call.ldx = s.dp;
+    call.xx = s.xx.as<double>(); call.xplanes = s.planes.p; call.W = W; call.M = M; call.ww = ww;
+    call.stream = c->stream;
+    return call;
+}
+
 int ensure_anchors(dbgsom_ctx *c, Samples &s) {
     if (s.anchor_state != 0) return DBGSOM_OK;
     TRY(ensure_planes(c, s));
@@ -601,13 +593,10 @@ int ensure_anchors(dbgsom_ctx *c, Samples &s) {
     } else {
         TRY(launch_row_sqnorms(anchors, DBGSOM_F64, A, dp, dp, anorm, c->stream));
         TRY(c->filt_ws.reserve_zeroed(dbgsom_bmu_filtered_workspace_bytes(s.N, dp, A), c->stream));
-        FilteredCall call;
-        call.aux = &c->faux;
-        call.X = s.Xb; call.x_dtype = s.bdtype; call.N = s.N; call.d = dp; call.ldx = dp;
-        call.xx = s.xx.as<double>(); call.xplanes = s.planes.p; call.W = anchors; call.M = A; call.ww = anorm;
+        FilteredCall call = filtered_call(c, s, anchors, A, anorm);
         call.seed_stride = DBGSOM_SEED_FULL; call.sweep_planes = 1;
         call.seeds_out = s.anchor_of.as<int32_t>(); call.order_out = s.anchor_order.as<int32_t>();
-        call.ws = c->filt_ws.p; call.ws_bytes = c->filt_ws.cap; call.stream = c->stream;
+        call.ws = c->filt_ws.p; call.ws_bytes = c->filt_ws.cap;
         TRY(launch_bmu_filtered(call));
     }
     // the run table of the bucket order: what the candidate lists need of the samples, once per load (the stored
@@ -618,7 +607,7 @@ int ensure_anchors(dbgsom_ctx *c, Samples &s) {
     s.n_anchors = A;
     s.anchor_state = 1;
     ++c->anchor_builds;
-    c->anchors_built_now = true;
+    c->anchor.anchors_built();
     return DBGSOM_OK;
 }
 
@@ -630,7 +619,7 @@ bool filter_applies(const dbgsom_ctx *c, int64_t M) {
 }
 
 // the previous epoch's winners seed the search of the resident samples
-bool hint_applies(const dbgsom_ctx *c, int64_t M) { return c->policy.takes_hint() && c->hint_valid && c->hintM <= M; }
+bool hint_applies(const dbgsom_ctx *c, int64_t M) { return c->search.hint_applies(c->policy.takes_hint(), M); }
 
 // prototypes: make W (host, or the resident ones) the consumed matrix Wb[cur]; norms into ww
 int stage_weights(dbgsom_ctx *c, const double *W_host, int64_t M, int64_t d, int64_t dp) {
@@ -638,7 +627,7 @@ int stage_weights(dbgsom_ctx *c, const double *W_host, int64_t M, int64_t d, int
     if (W_host) {
         TRY(c->Wb[c->cur].reserve((size_t)M * dp * 8));
         TRY(upload_padded(c, c->Wb[c->cur].p, W_host, M, d, dp, 8));
-        if (c->distW_buf == c->cur) c->dist_bound_valid = false;  // the matrix the hint's distances refer to is gone
+        c->search.weights_replaced(c->cur);
         c->M = M;
         ++c->w_up_calls; c->w_up_bytes += M * d * 8;
     } else if (c->M != M) {
@@ -656,53 +645,33 @@ int run_filtered(dbgsom_ctx *c, Samples &s, DevBuf &ws, const double *W, int64_t
                  bool allow_defer = false) {
     TRY(ensure_planes(c, s));
     TRY(ws.reserve_zeroed(dbgsom_bmu_filtered_workspace_bytes(s.N, s.dp, M), c->stream));
-    const bool bound_usable = c->dist_bound_valid && dist == c->dist.as<double>() && c->Wb[c->distW_buf].p;
+    const ResidentSearchState &st = c->search;   // (the bound: the last epoch's distances under Wb[st.distW_buf])
+    const bool bound_usable = st.bound_usable(dist == c->dist.as<double>(), c->Wb[st.distW_buf].p != nullptr);
     const SearchPolicy::Plan plan = c->policy.plan(M, s.N, s.dp, prev_idx != nullptr, may_probe, bound_usable);
-    FilteredCall call;
-    call.aux = &c->faux;
+    FilteredCall call = filtered_call(c, s, W, M, c->ww.as<double>());
     if (plan.hint_bound) {
         TRY(c->shiftb.reserve((size_t)M * 8));
-        const int64_t rows = c->distW_M < M ? c->distW_M : M;
+        const int64_t rows = st.distW_M < M ? st.distW_M : M;
         hipLaunchKernelGGL(row_shift_kernel, dim3((unsigned)M), dim3(64), 0, c->stream, W,
-                           c->Wb[c->distW_buf].as<double>(), s.dp, s.dp, rows, M, c->shiftb.as<double>());
+                           c->Wb[st.distW_buf].as<double>(), s.dp, s.dp, rows, M, c->shiftb.as<double>());
         TRY(launch_status("row_shift_kernel"));
         call.hint_dist = c->dist.as<double>();
         call.hint_shift = c->shiftb.as<double>();
     }
-    call.X = s.Xb; call.x_dtype = s.bdtype; call.N = s.N; call.d = s.dp; call.ldx = s.dp;
-    call.xx = s.xx.as<double>(); call.xplanes = s.planes.p; call.W = W; call.M = M; call.ww = c->ww.as<double>();
     call.prev_idx = prev_idx; call.order = order; call.seed_stride = plan.seed_stride; call.sweep_planes = plan.sweep_planes;
-    // A stateless search of the resident samples in the pruning form with the cheap seeds: the seeds come from the
-    // anchor buckets instead of the pre-pass.  Nothing the policy sees changes: it planned a stateless call.
-    // Only once the pre-pass has seeded a pruning epoch (or a counting-only pruning launch) of this sample set on a
-    // map about this size: what it left is what the anchors' lists are held against (the valve, dbgsom_ctx_epoch),
-    // and the policy's own first looks at the arm -- are its cheap seeds poor, does it need the re-seeding passes --
-    // are looks at the pre-pass.
-    c->last_anchor_seeded = false;
-    c->last_lean = false;
-    // (without the re-seeding bit: an epoch whose re-seeding passes found nothing to do is evidence for the same
-    //  plan without them, which is what the policy plans next; a plan WITH them is never lean)
-    c->last_plan_key = LeanGate::plan_key(plan.seed_stride & ~DBGSOM_PRUNE_RETRY, plan.sweep_planes);
-    const bool has_ref = c->prepass_mean == c->prepass_mean && SearchPolicy::near_size(M, c->prepass_M);
-    if (!prev_idx && &s == &c->xs && c->anchor_seeds && s.anchor_state != 2 && has_ref && plan.planes == 0 &&
-        !plan.seed_full && (plan.seed_stride & DBGSOM_PRUNE)) {
+    // seeds from the anchor buckets instead of the pre-pass, and the lean form behind them: AnchorControl decides
+    if (c->anchor.wants_anchors(plan, prev_idx != nullptr, &s == &c->xs, c->anchor_seeds != 0, s.anchor_state, M)) {
         TRY(ensure_anchors(c, s));   // (may grow `ws` for its own call: call.ws is taken below)
         ++c->anchor_searches;
         call.anchors = s.anchors.as<double>(); call.n_anchors = (int)s.n_anchors;
         call.anchor_of = s.anchor_of.as<int32_t>(); call.order = s.anchor_order.as<int32_t>();
         call.anchor_runs = s.anchor_runs.p;
-        c->last_anchor_seeded = true;
-        // The search of an epoch behind an anchor-seeded epoch of the same samples, map size and plan that handed
-        // nothing to the per-sample pass: nothing is made for that pass (the lean form).  (ensure_anchors above has
-        // bumped the generation if it had to build the buckets: that epoch is a full one.)
-        if (may_probe && c->lean_gate.allows(M, s.anchor_generation, c->last_plan_key, plan.retry, plan.refine)) {
+        if (c->anchor.anchor_seeded(plan, M, may_probe, s.anchor_generation)) {
             call.seed_stride |= DBGSOM_ANCHOR_LISTS_ONLY;
-            c->last_lean = true;
             ++c->lean_searches;
         }
     }
     call.round_f32 = round_f32; call.idx = idx; call.dist = dist; call.ws = ws.p; call.ws_bytes = ws.cap;
-    call.stream = c->stream;
     call.refine_rows = plan.refine_rows;
     c->last_refined = plan.refine;
     // an epoch's accumulate step can evaluate the distances of the samples the refinement decided without
@@ -931,9 +900,7 @@ int epoch_bmu(dbgsom_ctx *c, int64_t M, int round_f32) {
         c->last_filtered = false;
         TRY(csr_search(c, s, W, M, 1, round_f32, out, c->dist.as<double>()));
         c->icur ^= 1;
-        c->hint_valid = false;
-        c->last_idx_valid = true;
-        c->dist_bound_valid = false;
+        c->search.foreign_search_done();
         return DBGSOM_OK;
     }
     if (filter_applies(c, M)) {
@@ -948,9 +915,7 @@ int epoch_bmu(dbgsom_ctx *c, int64_t M, int round_f32) {
                        out, c->dist.as<double>(), c->stream));
     }
     c->icur ^= 1;
-    c->hint_valid = false;  // re-established by the accumulate step that follows
-    c->last_idx_valid = true;
-    c->dist_bound_valid = true; c->distW_buf = c->cur; c->distW_M = M;
+    c->search.dense_search_done(c->cur, M);
     return DBGSOM_OK;
 }
 
@@ -1217,16 +1182,13 @@ int resident_bmu(dbgsom_ctx *c, const double *W_host, int64_t M, int k, int roun
         const bool hint = hint_applies(c, M);
         TRY(ensure_planes(c, s));
         TRY(c->filt_ws.reserve_zeroed(dbgsom_bmu_filtered_workspace_bytes(s.N, s.dp, M), c->stream));
-        FilteredCall call;
-        call.aux = &c->faux;
-        call.X = s.Xb; call.x_dtype = s.bdtype; call.N = s.N; call.d = s.dp; call.ldx = s.dp;
-        call.xx = s.xx.as<double>(); call.xplanes = s.planes.p; call.W = W; call.M = M; call.ww = c->ww.as<double>();
+        FilteredCall call = filtered_call(c, s, W, M, c->ww.as<double>());
         call.prev_idx = hint ? c->idx[c->icur].as<int64_t>() : nullptr;
         call.order = hint ? c->acc_ws.as<int32_t>() : nullptr;
         call.seed_stride = c->policy.k2_seed_stride(hint);
         call.sweep_planes = 1; call.round_f32 = round_f32; call.k = 2;
         call.idx = c->qidx.as<int64_t>(); call.dist = c->qdist.as<double>();
-        call.ws = c->filt_ws.p; call.ws_bytes = c->filt_ws.cap; call.stream = c->stream;
+        call.ws = c->filt_ws.p; call.ws_bytes = c->filt_ws.cap;
         c->last_k2_filtered = true;
         return launch_bmu_filtered(call);
     }
@@ -1416,7 +1378,7 @@ int dbgsom_ctx_get_option(dbgsom_ctx *c, const char *name, int64_t *v) {
     else if (!strcmp(name, "anchor_state")) *v = c->xs.dtype < 0 ? 0 : c->xs.anchor_state;
     else if (!strcmp(name, "planes_used")) *v = c->policy.planes_used;
     else if (!strcmp(name, "planes_next")) *v = c->policy.planes_for_call();
-    else if (!strcmp(name, "hint_valid")) *v = c->hint_valid ? 1 : 0;
+    else if (!strcmp(name, "hint_valid")) *v = c->search.hint_valid ? 1 : 0;
     else if (!strcmp(name, "filter_backoff")) *v = c->policy.filter_backoff;
     else if (!strcmp(name, "plane_hold")) *v = c->policy.plane_hold;
     else if (!strcmp(name, "seed_mode")) *v = c->policy.seed_mode;
@@ -1466,16 +1428,15 @@ static void set_tight(dbgsom_ctx *c, bool tight) {
 }
 
 static void reset_training_state(dbgsom_ctx *c) {
-    c->hint_valid = c->last_idx_valid = c->part_valid = false;
+    c->search.reset();
+    c->part_valid = false;
     c->has_labels = false;
     c->has_weights = false;
     c->has_targets = false;
     c->incomplete = false;
     c->cos_u_ready = false;   // (u belongs to the rows that were resident)
     c->policy.reset();
-    c->prepass_mean = NAN;
-    c->last_anchor_seeded = false;
-    c->dist_bound_valid = false;
+    c->anchor.reset();
     c->last_filtered = false;
     c->sumsM = 0;
     // the resident prototypes were laid out for the old samples' padded row length: gone with them
@@ -1694,7 +1655,7 @@ int dbgsom_ctx_set_weights(dbgsom_ctx *c, const double *W_host, int64_t M) {
     DBGSOM_REQUIRE(W_host && M >= 1, "bad prototypes");
     TRY(c->Wb[c->cur].reserve((size_t)M * c->xs.dp * 8));
     TRY(upload_padded(c, c->Wb[c->cur].p, W_host, M, c->xs.d, c->xs.dp, 8));
-    if (c->distW_buf == c->cur) c->dist_bound_valid = false;
+    c->search.weights_replaced(c->cur);
     c->M = M;
     ++c->w_up_calls; c->w_up_bytes += M * c->xs.d * 8;
     return sync(c);
@@ -1741,7 +1702,7 @@ int dbgsom_ctx_write_weight_rows(dbgsom_ctx *c, int64_t row0, int64_t n, const d
     TRY(c->Wb[c->cur].reserve_keep((size_t)newM * dp * 8, (size_t)c->M * dp * 8, c->stream));
     double *dst = c->Wb[c->cur].as<double>() + row0 * dp;
     TRY(upload_padded(c, dst, rows_host, n, d, dp, 8));
-    if (c->distW_buf == c->cur) c->dist_bound_valid = false;
+    c->search.weights_replaced(c->cur);
     c->M = newM;
     c->w_row_writes += n;
     return sync(c);
@@ -3040,11 +3001,10 @@ int metric_epoch(dbgsom_ctx *c, const char *fn, Metric metric, const double *W_h
         int64_t *idx = c->idx[c->icur ^ 1].as<int64_t>();
         c->last_filtered = false;
         c->last_deferred = false;
-        c->hint_valid = false;
-        c->dist_bound_valid = false;
+        c->search.foreign_search_begun();
         if ((rc = resident_bmu_metric(c, metric, c->Wb[c->cur].as<double>(), s.dp, M, 1, idx, c->dist.as<double>()))) break;
         c->icur ^= 1;
-        c->last_idx_valid = true;
+        c->search.foreign_search_done();
         if ((rc = accumulate_and_reduce(c, idx, nullptr, gamma, c->dist.as<double>(), M))) break;
         rc = smooth_and_fetch(c, M, sigma, layout, 0, W_new_host, change_total_host, errors_host, activations_host, idx,
                               idx_host, dist_host);
@@ -3191,7 +3151,7 @@ int dbgsom_ctx_epoch(dbgsom_ctx *c, const double *W_host, int64_t M, int round_f
         if ((rc = stage_weights(c, W_host, M, s.d, s.dp))) break;
         mark(c, 0);
         const auto t_begin = std::chrono::steady_clock::now();
-        c->anchors_built_now = false;
+        c->anchor.begin_epoch();
         if ((rc = epoch_bmu(c, M, round_f32))) break;
         mark(c, 1);
         const int measuring = c->policy.take_timing_form();   // (the refinement's policy: this epoch times one of the two forms)
@@ -3199,8 +3159,7 @@ int dbgsom_ctx_epoch(dbgsom_ctx *c, const double *W_host, int64_t M, int round_f
         if ((rc = accumulate_and_reduce(c, idx, nullptr, gamma, c->dist.as<double>(), M))) break;
         // the next epoch's filter visits the samples bucketed by this epoch's winners: the stable
         // counting sort the accumulate step just did (first N int32 of its workspace)
-        c->hint_valid = true;
-        c->hintM = M;
+        c->search.sums_made(M);
         mark(c, 2);
         rc = smooth_and_fetch(c, M, sigma, layout, flags, W_new_host, change_total_host, errors_host, activations_host,
                               idx, idx_host, dist_host);
@@ -3209,45 +3168,21 @@ int dbgsom_ctx_epoch(dbgsom_ctx *c, const double *W_host, int64_t M, int round_f
         if (measuring >= 0)   // wall clock of the blocking call behind the upload of W: BMU + sums + smoothing
             pol.refine_timed(measuring, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
         if (c->last_filtered) {
-            // (a clean measurement of the arm: nothing rode along -- see SearchPolicy::arm_ms)
-            // (... and the epoch did not build the anchor buckets on the way)
             const double *counted = c->tail.as<double>() + 2 * M + 2;   // (pack_results_kernel: lists, probe, groups to re-seed, handed over)
-            // A lean epoch that kept long lists guessed wrong: what it measured is neither what the anchors' lists
-            // cost (the per-sample pass would have shortened them) nor a clock of the arm.  The next one is full.
-            const bool lean_missed = c->last_lean && counted[3] > 0.0;
-            if (c->last_anchor_seeded) c->lean_gate.record(M, s.anchor_generation, c->last_plan_key, counted[3], counted[2]);
-            else c->lean_gate.forget();
-            const bool clean = !pol.last_probed && !pol.last_guarded && measuring < 0 && !W_new_host && !idx_host && !dist_host &&
-                               !c->anchors_built_now && !lean_missed;
+            // the lean gate's record, the clock's verdict and the valve of the anchor seeds: AnchorControl
+            const AnchorControl::Verdict v = c->anchor.after_filtered_epoch(counted, s.N, M, s.anchor_generation, pol, measuring,
+                                                                            W_new_host || idx_host || dist_host);
             const double epoch_ms =
-                clean ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count() : NAN;
-            // The valve of the anchor seeds: their lists against those of the last pruning epoch the cheap pre-pass
-            // seeded on a map within a quarter of this size (run_filtered waits for one).  More than 1.25 times
-            // that -- a quarter of the exact stage lost at the most -- and the pre-pass seeds this sample set
-            // again.  (An epoch whose long lists the policy is about to re-seed is not what either form costs.)
-            const int64_t nb = (s.N + 127) / 128;
-            const bool settled = !(counted[2] > 0.0 && !pol.last_retry) && !lean_missed;
-            if (pol.last_probed && !pol.last_hinted && !pol.last_seed_full && settled) {
-                // (a counting-only pruning launch beside a sweep: the lists the pre-pass's seeds would have left)
-                c->prepass_mean = counted[1] / (double)nb;
-                c->prepass_M = M;
-            }
-            if (pol.planes_used == 0 && !pol.last_hinted && !pol.last_seed_full && settled) {
-                const double mean = counted[0] / (double)nb;
-                if (c->last_anchor_seeded) {   // (run_filtered took them because a reference exists)
-                    if (mean > 1.25 * c->prepass_mean) s.drop_anchors(2);
-                } else {
-                    c->prepass_mean = mean;
-                    c->prepass_M = M;
-                }
-            }
-            pol.observe(counted[0], counted[1], counted[2], nb, M, s.dp, (flags & DBGSOM_EPOCH_FROZEN) != 0, epoch_ms);
+                v.clean ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count() : NAN;
+            if (v.drop_anchors) s.drop_anchors(2);
+            pol.observe(counted[0], counted[1], counted[2], (s.N + 127) / 128, M, s.dp, (flags & DBGSOM_EPOCH_FROZEN) != 0,
+                        epoch_ms);
         } else {
-            c->lean_gate.forget();
+            c->anchor.after_unfiltered_epoch();
             pol.observe_unfiltered();
         }
     } while (0);
-    if (rc != DBGSOM_OK && rc != DBGSOM_ERANGE) { (void)hipStreamSynchronize(c->stream); c->hint_valid = false; }
+    if (rc != DBGSOM_OK && rc != DBGSOM_ERANGE) { (void)hipStreamSynchronize(c->stream); c->search.epoch_failed(); }
     return rc;
 }
 
@@ -3267,8 +3202,7 @@ int dbgsom_ctx_update(dbgsom_ctx *c, const double *W_host, int64_t M, const int6
         if ((rc = c->idx[1].reserve((size_t)s.N * 8))) break;
         if ((rc = c->dist.reserve((size_t)s.N * 8))) break;
         if ((rc = c->kw.reserve((size_t)s.N * 8))) break;
-        c->hint_valid = false;
-        c->dist_bound_valid = false;  // (the caller's distances: nothing a bound may rest on)
+        c->search.foreign_search_begun();  // (the caller's distances: nothing a bound may rest on)
         c->icur ^= 1;
         int64_t *idx = c->idx[c->icur].as<int64_t>();
         hipError_t e = hipMemcpyAsync(idx, idx_host, (size_t)s.N * 8, hipMemcpyHostToDevice, c->stream);
@@ -3276,7 +3210,7 @@ int dbgsom_ctx_update(dbgsom_ctx *c, const double *W_host, int64_t M, const int6
         if (e == hipSuccess) e = hipMemcpyAsync(c->dist.p, dist_host, (size_t)s.N * 8, hipMemcpyHostToDevice, c->stream);
         if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = DBGSOM_EHIP; break; }
         c->last_filtered = false;
-        c->last_idx_valid = true;
+        c->search.caller_winners_taken();
         if ((rc = accumulate_and_reduce(c, idx, c->kw.as<double>(), 0.0, c->dist.as<double>(), M))) break;
         rc = smooth_and_fetch(c, M, sigma, layout, 0, W_new_host, change_total_host, errors_host, activations_host, idx,
                               nullptr, nullptr);
@@ -3301,9 +3235,7 @@ int dbgsom_ctx_set_hint(dbgsom_ctx *c, const int64_t *idx_host, int64_t M) {
     DBGSOM_HIP_CHECK(hipMemcpyAsync(idx, idx_host, (size_t)s.N * 8, hipMemcpyHostToDevice, c->stream));
     TRY(launch_bucket_sort(idx, s.N, M, c->acc_ws.as<int32_t>(), c->part_ws.p, c->stream));
     TRY(sync(c));
-    c->hint_valid = true;
-    c->dist_bound_valid = false;
-    c->hintM = M;
+    c->search.hint_seeded(M);
     c->part_valid = false;
     return DBGSOM_OK;
 }
@@ -3463,7 +3395,7 @@ int dbgsom_ctx_node_statistics(dbgsom_ctx *c, const double *W_host, int64_t M, i
     TRY(c->kw.reserve((size_t)s.N * 8));
     TRY(dbgsom_density_terms(c->qdist.as<double>(), s.N, sigma, c->kw.as<double>(), c->stream));
     // K = density sums, a = hit counts of the fused buffer; the bucket order of the training hint is rewritten
-    c->hint_valid = false;
+    c->search.bucket_order_rewritten();
     DBGSOM_REQUIRE(M <= DBGSOM_MAX_PROTOTYPES, "M exceeds DBGSOM_MAX_PROTOTYPES");
     const int64_t count = M * (s.dp + 3);
     TRY(c->sums.reserve((size_t)(count + 1) * 8));
@@ -3500,7 +3432,7 @@ int dbgsom_ctx_class_histogram(dbgsom_ctx *c, const int64_t *idx_host, int64_t n
         DBGSOM_HIP_CHECK(hipMemcpyAsync(c->qidx.p, idx_host, (size_t)s.N * 8, hipMemcpyHostToDevice, c->stream));
         idx = c->qidx.as<int64_t>();
     } else {
-        if (!c->last_idx_valid) { set_error("no winners of a previous epoch in HBM"); return DBGSOM_ESTATE; }
+        if (!c->search.last_idx_valid) { set_error("no winners of a previous epoch in HBM"); return DBGSOM_ESTATE; }
         idx = c->idx[c->icur].as<int64_t>();
     }
     const int64_t n = M * n_classes;
@@ -3534,7 +3466,7 @@ int dbgsom_ctx_class_histogram_weighted(dbgsom_ctx *c, const int64_t *idx_host, 
         DBGSOM_HIP_CHECK(hipMemcpyAsync(c->qidx.p, idx_host, (size_t)s.N * 8, hipMemcpyHostToDevice, c->stream));
         idx = c->qidx.as<int64_t>();
     } else {
-        if (!c->last_idx_valid) { set_error("no winners of a previous epoch in HBM"); return DBGSOM_ESTATE; }
+        if (!c->search.last_idx_valid) { set_error("no winners of a previous epoch in HBM"); return DBGSOM_ESTATE; }
         idx = c->idx[c->icur].as<int64_t>();
     }
     const int64_t n = M * n_classes;
@@ -3685,7 +3617,7 @@ int dbgsom_ctx_target_statistics(dbgsom_ctx *c, const int64_t *idx_host, int64_t
         DBGSOM_HIP_CHECK(hipMemcpyAsync(c->qidx.p, idx_host, (size_t)N * 8, hipMemcpyHostToDevice, c->stream));
         idx = c->qidx.as<int64_t>();
     } else {
-        if (!c->last_idx_valid) { set_error("no winners of a previous epoch in HBM"); return DBGSOM_ESTATE; }
+        if (!c->search.last_idx_valid) { set_error("no winners of a previous epoch in HBM"); return DBGSOM_ESTATE; }
         idx = c->idx[c->icur].as<int64_t>();
     }
     // [mass | sums | mean | mass of the second fold | squares / std | err]
@@ -3867,7 +3799,7 @@ int dbgsom_ctx_read_anchors(dbgsom_ctx *c, int64_t *n_anchors, double *anchors_h
     TRY(complete_rows(c, __func__));
     Samples &s = c->xs;
     if (s.anchor_state != 1) { set_error("dbgsom_ctx_read_anchors: the resident samples have no anchor buckets"); return DBGSOM_ESTATE; }
-    if (aseed_host && !(c->last_anchor_seeded && c->last_filter_ws)) {
+    if (aseed_host && !(c->anchor.last_anchor_seeded && c->last_filter_ws)) {
         set_error("dbgsom_ctx_read_anchors: the last search was not seeded from the anchors");
         return DBGSOM_ESTATE;
     }
