@@ -968,6 +968,7 @@ class HipBackend(HotPathBackend):
         self._cb = None
         self._cb_error = None
         self._last_M = 0
+        self._part_M = 0            # (units of the last partition; none yet: dbgsom_ctx_read_partition refuses)
         self._x_traffic = {k: 0 for k in self._X_TRAFFIC}   # of contexts released since, and of fetch / put
         self.filter_log = []        # (epoch kind, mean candidates, digit planes) of the last epochs
         self.phase_log = None       # bench hook: a list collects the per-epoch phase times (ms)
@@ -1238,6 +1239,7 @@ class HipBackend(HotPathBackend):
         self.resident_serial += 1
         self._hop_key = None
         self._last_M = 0
+        self._part_M = 0            # (units of the last partition; none yet: dbgsom_ctx_read_partition refuses)
         self._y = None
         self._sw = None          # (a load detaches the weights of the rows that were resident)
         self._weighted = False

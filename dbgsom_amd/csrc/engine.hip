@@ -390,6 +390,7 @@ struct dbgsom_ctx {
     int anchor_seeds = 1;
     // buckets built / searches seeded from them / epochs that took the lean form of such a search so far
     int64_t anchor_builds = 0, anchor_searches = 0, lean_searches = 0;
+    int64_t hint_bound_searches = 0;   // searches that took the hinted pruning bound (plan.hint_bound)
     AnchorControl anchor;   // when the anchors seed a search, in which form, and the valve (epoch_control.h)
 };
 
@@ -650,6 +651,7 @@ int run_filtered(dbgsom_ctx *c, Samples &s, DevBuf &ws, const double *W, int64_t
     const SearchPolicy::Plan plan = c->policy.plan(M, s.N, s.dp, prev_idx != nullptr, may_probe, bound_usable);
     FilteredCall call = filtered_call(c, s, W, M, c->ww.as<double>());
     if (plan.hint_bound) {
+        ++c->hint_bound_searches;
         TRY(c->shiftb.reserve((size_t)M * 8));
         const int64_t rows = st.distW_M < M ? st.distW_M : M;
         hipLaunchKernelGGL(row_shift_kernel, dim3((unsigned)M), dim3(64), 0, c->stream, W,
@@ -1375,6 +1377,7 @@ int dbgsom_ctx_get_option(dbgsom_ctx *c, const char *name, int64_t *v) {
     else if (!strcmp(name, "anchor_builds")) *v = c->anchor_builds;
     else if (!strcmp(name, "anchor_searches")) *v = c->anchor_searches;
     else if (!strcmp(name, "lean_searches")) *v = c->lean_searches;
+    else if (!strcmp(name, "hint_bound_searches")) *v = c->hint_bound_searches;
     else if (!strcmp(name, "anchor_state")) *v = c->xs.dtype < 0 ? 0 : c->xs.anchor_state;
     else if (!strcmp(name, "planes_used")) *v = c->policy.planes_used;
     else if (!strcmp(name, "planes_next")) *v = c->policy.planes_for_call();

@@ -127,8 +127,9 @@ struct __attribute__((visibility("hidden"))) ResidentSearchState {
     // the accumulate step of dbgsom_ctx_epoch has left the bucket order of the winners (M prototypes)
     void sums_made(int64_t M) { hint_valid = true; hintM = M; }
     void epoch_failed() { hint_valid = false; }
-    // the caller's seeds and their bucket order are in place (dbgsom_ctx_set_hint): no distances go with them
-    void hint_seeded(int64_t M) { hint_valid = true; hintM = M; dist_bound_valid = false; }
+    // the caller's seeds and their bucket order are in place (dbgsom_ctx_set_hint): no distances go with them, and
+    // idx[icur] now holds seeds, not the winners of an epoch -- what reads "the last epoch's winners" must refuse
+    void hint_seeded(int64_t M) { hint_valid = true; hintM = M; dist_bound_valid = last_idx_valid = false; }
     // Wb[buf] was overwritten: if the bound's distances refer to it, it is gone
     void weights_replaced(int buf) { if (distW_buf == buf) dist_bound_valid = false; }
     void bucket_order_rewritten() { hint_valid = false; }   // (dbgsom_ctx_node_statistics)

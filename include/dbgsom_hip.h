@@ -429,7 +429,7 @@ int dbgsom_ctx_destroy(dbgsom_ctx *ctx);
  * call; 0: the pre-pass.  Results do not depend on it).
  * Readable besides those: "resident_csr", "resident_nnz", "refined", "defer_epochs" (epochs whose sums kernel evaluated distances), "shard_epochs", "n_samples", "features", "padded_features", "prototypes",
  * "planes_cached", "planes_used" / "planes_next" (0 = no sweep), "seed_mode", "prune_retry", "hint_valid",
- * "filter_backoff", "plane_hold", "device_bytes", "anchor_builds" (anchor buckets built so far), "anchor_searches" (searches seeded from them), "lean_searches" (of those, epochs in the lean form DBGSOM_ANCHOR_LISTS_ONLY), "anchor_state" (of
+ * "filter_backoff", "plane_hold", "device_bytes", "anchor_builds" (anchor buckets built so far), "anchor_searches" (searches seeded from them), "lean_searches" (of those, epochs in the lean form DBGSOM_ANCHOR_LISTS_ONLY), "hint_bound_searches" (searches that took the hinted pruning bound), "anchor_state" (of
  * the resident samples: 0 none, 1 in use, 2 dropped -- their lists came out longer than the pre-pass's), and the
  * PCIe traffic of the prototypes since the context was created: "w_upload_calls" / "w_upload_bytes"
  * (whole matrices host -> HBM), "w_download_calls" / "w_download_bytes", "w_row_writes", "w_row_reads";

@@ -129,9 +129,13 @@ static void legacy_epoch_sums_made(Legacy *c, int64_t M) {
     c->hintM = M;
 }
 static void legacy_epoch_error_tail(Legacy *c) { c->hint_valid = false; }
+// (the text at 2d7f700 left last_idx_valid alone: dbgsom_ctx_class_histogram(NULL) and dbgsom_ctx_target_statistics(NULL)
+//  behind a dbgsom_ctx_set_hint then folded the caller's seeds as if they were the last epoch's winners -- corrected here
+//  and in the header together; tests/test_gpu_call_order.py holds the sequence)
 static void legacy_set_hint(Legacy *c, int64_t M) {
     c->hint_valid = true;
     c->dist_bound_valid = false;
+    c->last_idx_valid = false;
     c->hintM = M;
 }
 static void legacy_stage_weights(Legacy *c, int cur) { if (c->distW_buf == cur) c->dist_bound_valid = false; }
