@@ -1009,14 +1009,10 @@ class HipBackend(HotPathBackend):
     # the first epochs of a map size with and without it and keeps the faster form
     refine = property(lambda self: self._get("refine"), lambda self, v: self._set("refine", int(v)))
     refined = property(lambda self: bool(self._get("refined")))   # what the last filtered search ran
-    # with the refinement: the distance of a sample it decided is evaluated inside the sums kernel of the
-    # epoch (one pass over the float rows for distance and sums) -- 1 / 0 (the engine's default: experimental, off)
-    defer = property(lambda self: bool(self._get("defer")), lambda self, v: self._set("defer", int(bool(v))))
     # neighbourhood smoothing sharded over the ranks (reduce-scatter of column blocks of the sums, all-gather of
     # the new prototypes): 0 never, 1 whenever the collective can, 2 (default) on large maps
     shard_smooth = property(lambda self: self._get("shard_smooth"), lambda self, v: self._set("shard_smooth", int(v)))
     shard_epochs = property(lambda self: self._get("shard_epochs"))
-    defer_epochs = property(lambda self: self._get("defer_epochs"))
     # CSR input of fewer features than this is expanded into dense rows on the device (0: never); results do
     # not depend on it.  resident_csr: whether the loaded samples are a CSR resident
     csr_densify_below = property(lambda self: self._get("csr_densify_below"),
@@ -2213,8 +2209,8 @@ class HipBackend(HotPathBackend):
         sub._weighted = self._weighted   # (dbgsom_ctx_subset_create gathered the rows' weights)
         return sub
 
-    _SETTABLE = ("algorithm", "sweep_planes", "seed_stride", "timing", "graph", "refine", "defer",
-                 "filter_min_query_rows", "max_mean_candidates", "shard_smooth", "csr_densify_below", "anchor_seeds")
+    _SETTABLE = ("algorithm", "sweep_planes", "seed_stride", "timing", "refine", "filter_min_query_rows",
+                 "max_mean_candidates", "shard_smooth", "csr_densify_below", "anchor_seeds")
 
     def release(self):
         """Give the device memory back (the backend can be loaded again afterwards; options stay)."""

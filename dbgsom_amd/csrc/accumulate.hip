@@ -24,8 +24,6 @@
 // that search fall back to all pairs -- 24 ms against 2.1 at C4 with a third of the rows at 0); a row
 // of weight 0 keeps its slot in its neuron's list and is skipped there: never streamed, added to
 // nothing, so a neuron that only such rows chose keeps exact zeros.
-#include <type_traits>
-
 #include "common.h"
 
 namespace dbgsom {
@@ -444,8 +442,8 @@ __device__ __forceinline__ void load_vec(const XT *__restrict__ src, double (&v)
 }
 
 // ---- 5. one workgroup sums one chunk (<= CH rows of one neuron) in list order ----------------
-// (WGT: per row the factor w kw on the x-sum and K -- one rounded product, formed the same way here
-//  and in segsum_chain_kernel --, w dist on E, and the third scalar partial sum w)
+// (WGT: per row the factor w kw on the x-sum and K -- one rounded product --, w dist on E, and the
+//  third scalar partial sum w)
 template <typename XT, int VEC, bool WGT>
 __global__ __launch_bounds__(AT) void segsum_kernel(
     const XT *__restrict__ X, int d, int64_t ldx, const int32_t *__restrict__ order,
@@ -551,315 +549,6 @@ __global__ __launch_bounds__(AT) void segsum_kernel(
                 double s = red[q * VEC + e];
                 for (int u = 1; u < RL; ++u) s += red[(u * Q + q) * VEC + e];
                 out[q * VEC + e] = s;
-            }
-        }
-    }
-}
-// ---- 5b. the same chunk, with the distances of the rows that do not have one yet ----------------------
-// The refinement of the filtered search (filter.hip 2d) knows the winner of a sample whose candidates it
-// could narrow down to ONE without ever touching the sample's float rows; its distance is the float64 chain
-// against that one prototype -- against THIS chunk's prototype.  Such rows arrive with dist == -1.  The float
-// rows are streamed ONCE for the distance and the sums (pair kernel + segsum_kernel: twice):
-//
-//  * a chunk is walked in slices of SR = 16 rows; every thread loads its column group (16 bytes) of the
-//    slice's rows into REGISTERS -- as in segsum_kernel, 16 loads in flight per thread -- and keeps them;
-//  * the chain acc = fma(w_k, x_k, acc), k ascending, runs on the matrix cores of ONE wavefront:
-//    v_mfma_f64_4x4x4_4b (four 4x4x4 blocks, 16 B-columns per instruction = the slice's 16 rows against the
-//    chunk's prototype in every A row) is that chain bit for bit, like the 16x16x4 form of the exact kernels,
-//    at a quarter of its pipe time (tools/probe_mfma_f64_4x4.hip: 17.6 cycles per instruction, 43.6 cycles from
-//    one dependent instruction to the next -- 26 without the loop branch, 51 with B read from LDS and widened in
-//    front of it, tools/probe_mfma_chain.hip).  The operands reach it through LDS in ranges of 64 column groups:
-//    the threads of range r + 1 write their registers (raw 16-byte pieces, row pitch 65 pieces: no bank
-//    conflicts on either side) while the chain walks range r; one barrier per range.  (Ranges of values already
-//    widened to float64 by their owners were measured: twice the LDS bytes and a second conversion of every
-//    value -- slower, C4 1.27 against 1.12 ms, the C5 shard 2.33 against 1.38.);
-//  * the distances and the sample kernel follow, then all threads form the weighted sums FROM THEIR REGISTERS
-//    in list order.  Sums, their order of additions and the scalar partials are those of segsum_kernel bit
-//    for bit (the two search forms must leave bit-identical prototypes).
-// A slice none of whose rows needs a distance skips the chain altogether.
-constexpr int CHAIN_CB = 4;    // k-steps per batch of the chain's operand ring
-constexpr int CHAIN_OCC = 3;   // wavefronts per SIMD the one-group kernel is compiled for
-constexpr int SR = 16;     // rows per slice = B-columns of one matrix instruction
-constexpr int SRG = 64;    // column groups (16-byte pieces) per range
-constexpr int SRP = (SRG + 1) * 16;   // bytes per row of a range buffer (one piece of padding)
-
-struct ChainLds {   // byte offsets inside the one dynamic LDS object (see refine.h: one object, no alias waits)
-    int o_w, o_rows, o_kw, o_dist, o_xx, o_info, total;   // (the two range buffers sit at 0; `red` reuses them)
-};
-static ChainLds chain_lds(int64_t d) {
-    ChainLds l;
-    l.o_w = 2 * SR * SRP;
-    l.o_rows = l.o_w + (int)d * 8;
-    l.o_kw = l.o_rows + CH * 4;
-    l.o_dist = l.o_kw + CH * 8;
-    l.o_xx = l.o_dist + CH * 8;
-    l.o_info = l.o_xx + CH * 8;
-    l.total = l.o_info + 32;
-    return l;
-}
-
-typedef unsigned raw4_t __attribute__((ext_vector_type(4)));
-template <typename XT, int VEC>
-__device__ __forceinline__ void raw_vec(const raw4_t r, double (&v)[VEC]) {
-    if constexpr (sizeof(XT) == 4 && VEC == 4) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = (double)__uint_as_float(r[e]);
-    } else if constexpr (sizeof(XT) == 8 && VEC == 2) {
-        v[0] = __hiloint2double((int)r[1], (int)r[0]);
-        v[1] = __hiloint2double((int)r[3], (int)r[2]);
-    } else {
-        static_assert(sizeof(XT) == 2 && VEC == 8, "unsupported vector width");
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            v[2 * e] = (double)__uint_as_float(r[e] << 16);
-            v[2 * e + 1] = (double)__uint_as_float(r[e] & 0xffff0000u);
-        }
-    }
-}
-
-// G = column groups per thread (rows of more than AT groups: q = tid + g AT)
-// (WGT: the rows' weights sit in CH doubles behind ChainLds::total -- the launch asks for them)
-template <typename XT, int VEC, int G, bool WGT>
-__global__ __launch_bounds__(AT, G == 1 ? CHAIN_OCC : 2) void segsum_chain_kernel(
-    const XT *__restrict__ X, int d, int64_t ldx, const int32_t *__restrict__ order, double gamma,
-    double *__restrict__ dist, const uint32_t *__restrict__ seg_start, const uint32_t *__restrict__ count,
-    const uint32_t *__restrict__ chunk_pre, int M, double *__restrict__ slab, const double *__restrict__ W,
-    const double *__restrict__ ww, const double *__restrict__ xx, int round_f32, ChainLds L, WeightArg<WGT> wa) {
-    constexpr int NS = WGT ? 3 : 2;   // scalar partials behind the d columns of a slab row
-    extern __shared__ __attribute__((aligned(16))) char dyn[];
-    [[maybe_unused]] double *sw_s = reinterpret_cast<double *>(dyn + L.total);
-    double *w_s = reinterpret_cast<double *>(dyn + L.o_w);
-    int32_t *rows_s = reinterpret_cast<int32_t *>(dyn + L.o_rows);
-    double *kw_s = reinterpret_cast<double *>(dyn + L.o_kw), *dist_s = reinterpret_cast<double *>(dyn + L.o_dist);
-    double *xx_s = reinterpret_cast<double *>(dyn + L.o_xx);
-    double *red = reinterpret_cast<double *>(dyn);
-    uint32_t *info = reinterpret_cast<uint32_t *>(dyn + L.o_info);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint32_t c = blockIdx.x;
-    if (c >= chunk_pre[M]) return;  // uniform per workgroup
-    {   // the chunk's neuron: the one j with chunk_pre[j] <= c < chunk_pre[j + 1] -- every thread looks at its share of
-        // the table at once (one round trip instead of the ten of a binary search by one thread)
-        const int per = (M + AT - 1) / AT;
-        for (int u = 0; u < per; ++u) {
-            const int jj = tid * per + u;
-            if (jj < M && chunk_pre[jj] <= c && c < chunk_pre[jj + 1]) {
-                const uint32_t begin = seg_start[jj] + (c - chunk_pre[jj]) * CH;
-                const uint32_t end = min(begin + (uint32_t)CH, seg_start[jj] + count[jj]);
-                info[0] = begin; info[1] = end - begin; info[2] = (uint32_t)jj;
-            }
-        }
-        if (tid == 0) info[3] = 0u;
-    }
-    __syncthreads();
-    const uint32_t begin = info[0];
-    const int n = (int)info[1], j = (int)info[2];
-    if (tid < n) {
-        const int32_t r = order[begin + tid];
-        rows_s[tid] = r;
-        const double dd = dist[r];   // (-1: to be computed here)
-        dist_s[tid] = dd;
-        xx_s[tid] = xx[r];
-        if constexpr (WGT) sw_s[tid] = wa.sw[r];
-        // the sample kernel of BaseSom._calculate_exp_similarity (BaseSom.py:533-538), the arithmetic of
-        // exp_similarity_kernel (bmu.hip) and of segsum_kernel
-        kw_s[tid] = 1.0 - sqrt(1.0 - exp(-gamma * (dd * dd)));
-        if (dd == -1.0) atomicOr(&info[3], 1u << (tid / SR));   // slices with a row that needs its distance
-    }
-    for (int k = tid; k < d; k += AT) w_s[k] = W[(size_t)j * d + k];
-    const double ww_j = ww[j];
-    __syncthreads();
-    const uint32_t need_mask = info[3];
-    const int Q = d / VEC;                       // column groups (VEC divides d by construction)
-    const bool wide = Q >= AT;
-    const int RL = wide ? 1 : AT / Q;            // row lanes side by side on the same column group (segsum_kernel)
-    const int rl = wide ? 0 : tid / Q, q0 = wide ? tid : tid - rl * Q;
-    const bool active = wide || rl < RL;
-    const int NR = (Q + SRG - 1) / SRG;          // ranges of 64 column groups
-    const int cw = (int)((c >> 8) & 3u);        // the chain's wavefront: spread over the SIMDs (chunks resident on one CU
-                                                 // share c mod 256 -- XCD, then CU, round robin -- so the bits above decide)
-    const int lr = lane & 15, lq = lane >> 4;    // B operand: column (row of the slice) lr, k = lq
-    double acc[G][VEC];
-#pragma unroll
-    for (int g = 0; g < G; ++g)
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) acc[g][e] = 0.0;
-    double *out = slab + (size_t)c * (d + NS);
-    int my_range[G], my_off[G];   // where this thread's column groups go in the range buffers
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        const int q = q0 + g * AT;
-        my_range[g] = (active && q < Q) ? q / SRG : -1;
-        my_off[g] = (q % SRG) * 16;
-    }
-
-    for (int s0 = 0; s0 < n; s0 += SR) {
-        const int nrow = min(SR, n - s0);
-        // ---- the slice's rows into registers (a thread's row lane: rows p = rl, rl + RL, ... of the chunk)
-        raw4_t raw[SR][G];
-        // bit i: row s0 + i is one of this thread's (its row lane: rows p = rl, rl + RL, ... of the chunk)
-        uint32_t mine = 0u;
-        if (active) {
-            if (RL == 1) mine = 0xffffu;
-            else for (int i = (rl - s0 % RL + RL) % RL; i < SR; i += RL) mine |= 1u << i;
-            mine &= (1u << nrow) - 1u;
-        }
-#pragma unroll
-        for (int i = 0; i < SR; ++i) {
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                raw[i][g] = raw4_t{0u, 0u, 0u, 0u};
-                if (((mine >> i) & 1u) && my_range[g] >= 0)
-                    raw[i][g] = *reinterpret_cast<const raw4_t *>(X + (int64_t)rows_s[s0 + i] * ldx + (int64_t)(q0 + g * AT) * VEC);
-            }
-        }
-        if ((need_mask >> (s0 / SR)) & 1u) {   // (uniform)
-            // ---- the chain: ranges of 64 column groups through two LDS buffers
-            // (rows behind the slice's end: zeros, written by row lane 0 -- never garbage in a B column)
-            const uint32_t wmask = mine | ((active && rl == 0) ? (0xffffu & ~((1u << nrow) - 1u)) : 0u);
-            auto write_range = [&](int r) {
-#pragma unroll
-                for (int g = 0; g < G; ++g) {
-                    if (my_range[g] == r) {
-                        char *dst = dyn + (r & 1) * (SR * SRP) + my_off[g];
-#pragma unroll
-                        for (int i = 0; i < SR; ++i) {
-                            if ((wmask >> i) & 1u) *reinterpret_cast<raw4_t *>(dst + i * SRP) = raw[i][g];
-                        }
-                    }
-                }
-            };
-            double a4 = 0.0;   // the chain's accumulator: lanes 0 .. 15 = rows of the slice
-            write_range(0);
-            __syncthreads();
-            for (int r = 0; r < NR; ++r) {
-                if (r + 1 < NR) write_range(r + 1);
-                if (wave == cw) {
-                    const char *buf = dyn + (r & 1) * (SR * SRP) + lr * SRP + lq * (int)sizeof(XT);   // B: row lr, feature k0 + lq
-                    const int nstep = min(SRG, Q - r * SRG) * VEC / 4;                 // k-steps of 4 features in this range
-                    const double *wk = w_s + (size_t)r * SRG * VEC + lq;               // A: w[k0 + lq] in every A row
-                    auto ld_a = [&](int st) { return wk[4 * st]; };
-                    // (B stays as it was read until its matrix instruction: widened at the point of the read, the
-                    //  conversion -- and with it the wait for the NEXT batch's reads -- would sit in front of this
-                    //  batch's instructions)
-                    typedef typename std::conditional<sizeof(XT) == 8, double, unsigned>::type braw_t;
-                    auto ld_b = [&](int st) -> braw_t {
-                        if constexpr (sizeof(XT) == 4) return *reinterpret_cast<const unsigned *>(buf + st * 16);
-                        else if constexpr (sizeof(XT) == 8) return *reinterpret_cast<const double *>(buf + st * 32);
-                        else return (unsigned)*reinterpret_cast<const unsigned short *>(buf + st * 8);
-                    };
-                    auto wid = [&](braw_t v) -> double {
-                        if constexpr (sizeof(XT) == 4) return (double)__uint_as_float(v);
-                        else if constexpr (sizeof(XT) == 8) return v;
-                        else return (double)__uint_as_float(v << 16);
-                    };
-                    // double batches of 2 CB steps: the next batch's LDS reads are in flight under this batch's dependent
-                    // matrix instructions.  Every read of the loop is unconditional (the last one runs a batch past the
-                    // range: still inside this workgroup's LDS, never used): with reads under a condition the compiler's
-                    // wait counts merge the two paths and every batch waits for the reads just issued (71 cycles per
-                    // step instead of ~55)
-                    constexpr int CB = CHAIN_CB;
-                    const int npair = nstep / (2 * CB);
-                    if (npair) {
-                        double a0[CB], a1[CB];
-                        braw_t b0[CB], b1[CB];
-#pragma unroll
-                        for (int u = 0; u < CB; ++u) { a0[u] = ld_a(u); b0[u] = ld_b(u); }
-                        for (int it = 0, st = 0; it < npair; ++it, st += 2 * CB) {
-#pragma unroll
-                            for (int u = 0; u < CB; ++u) { a1[u] = ld_a(st + CB + u); b1[u] = ld_b(st + CB + u); }
-                            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                            for (int u = 0; u < CB; ++u) a4 = __builtin_amdgcn_mfma_f64_4x4x4f64(a0[u], wid(b0[u]), a4, 0, 0, 0);
-                            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                            for (int u = 0; u < CB; ++u) { a0[u] = ld_a(st + 2 * CB + u); b0[u] = ld_b(st + 2 * CB + u); }
-                            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                            for (int u = 0; u < CB; ++u) a4 = __builtin_amdgcn_mfma_f64_4x4x4f64(a1[u], wid(b1[u]), a4, 0, 0, 0);
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-                    }
-                    for (int st = npair * 2 * CB; st < nstep; ++st)
-                        a4 = __builtin_amdgcn_mfma_f64_4x4x4f64(ld_a(st), wid(ld_b(st)), a4, 0, 0, 0);
-                }
-                __syncthreads();
-            }
-            if (wave == cw && lane < nrow) {
-                const int p = s0 + lane;
-                if (dist_s[p] == -1.0) {
-                    double rv = (xx_s[p] + (-2.0 * a4)) + ww_j;
-                    if (!(rv > 0.0)) rv = (rv != rv) ? rv : 0.0;
-                    double dv = sqrt(rv);
-                    if (round_f32) dv = (double)(float)dv;
-                    dist_s[p] = dv;
-                    dist[rows_s[p]] = dv;
-                    kw_s[p] = 1.0 - sqrt(1.0 - exp(-gamma * (dv * dv)));
-                }
-            }
-            __syncthreads();
-        }
-        // ---- the weighted sums of the slice's rows, in list order (segsum_kernel's order), from the registers
-        if (mine) {
-#pragma unroll
-            for (int i = 0; i < SR; ++i) {
-                if ((mine >> i) & 1u) {
-                    double w = kw_s[s0 + i];
-                    if constexpr (WGT) {
-                        // (weight 0: in no sum, as in segsum_kernel; its row was loaded in case its distance was open)
-                        if (sw_s[s0 + i] == 0.0) continue;
-                        w = __dmul_rn(sw_s[s0 + i], w);
-                    }
-#pragma unroll
-                    for (int g = 0; g < G; ++g) {
-                        double v[VEC];
-                        // (laundered: the compiler must not keep the values widened for the range buffers alive until
-                        //  here -- 16 rows of them are 128 registers -- but widen the raw pieces once more)
-                        unsigned r0 = raw[i][g][0], r1 = raw[i][g][1], r2 = raw[i][g][2], r3 = raw[i][g][3];
-                        asm volatile("" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3));
-                        raw_vec<XT, VEC>(raw4_t{r0, r1, r2, r3}, v);
-#pragma unroll
-                        for (int e = 0; e < VEC; ++e) acc[g][e] += w * v[e];
-                    }
-                }
-            }
-        }
-    }
-    __syncthreads();
-    if (tid == AT - 1) {  // the scalar partials, in list order
-        double sk = 0.0, se = 0.0;
-        if constexpr (WGT) {
-            double sa = 0.0;
-            for (int p = 0; p < n; ++p) {
-                sk += __dmul_rn(sw_s[p], kw_s[p]); se += __dmul_rn(sw_s[p], dist_s[p]); sa += sw_s[p];
-            }
-            out[d + 2] = sa;
-        } else {
-            for (int p = 0; p < n; ++p) { sk += kw_s[p]; se += dist_s[p]; }
-        }
-        out[d] = sk;
-        out[d + 1] = se;
-    }
-    if (wide) {
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const int q = tid + g * AT;
-            if (q < Q)
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) out[q * VEC + e] = acc[g][e];
-        }
-    } else {
-        if (rl < RL) {
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) red[(rl * Q + q0) * VEC + e] = acc[0][e];
-        }
-        __syncthreads();
-        if (rl == 0) {  // row lanes are added in lane order
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) {
-                double s = red[q0 * VEC + e];
-                for (int u = 1; u < RL; ++u) s += red[(u * Q + q0) * VEC + e];
-                out[q0 * VEC + e] = s;
             }
         }
     }
@@ -1017,35 +706,10 @@ int launch_bucket_sort(const int64_t *idx, int64_t N, int64_t M, int32_t *order,
 }
 
 // ---------------------------------------------------------------------------------------------
-bool accumulate_can_fill_distances(int x_dtype, int64_t d) {
-    if (d % 16 != 0) return false;
-    const int vec = x_dtype == DBGSOM_F32 ? 4 : (x_dtype == DBGSOM_F64 ? 2 : 8);
-    if (d / vec > 2 * (int64_t)AT) return false;              // (two column groups per thread at most)
-    return chain_lds(d).total <= 96 * 1024 && (size_t)AT * vec * 8 <= (size_t)2 * SR * SRP;   // (`red` reuses the range buffers)
-}
-
-// one instantiation of segsum_chain_kernel: its dynamic LDS is above the default limit (asked for once), the
-// weighted form keeps the rows' weights in CH doubles behind ChainLds::total
-template <typename XT, int V, int G, bool WGT>
-static int launch_chain(dim3 grid, const XT *X, int d, int64_t ldx, const AccWs &w, double gamma, double *dist, int M,
-                        const DistFill &fill, const ChainLds &L, WeightArg<WGT> wa, hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        DBGSOM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&segsum_chain_kernel<XT, V, G, WGT>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        attr_set = true;
-    }
-    const size_t lds = (size_t)L.total + (WGT ? CH * 8 : 0);
-    hipLaunchKernelGGL((segsum_chain_kernel<XT, V, G, WGT>), grid, dim3(AT), lds, s, X, d, ldx, w.order, gamma, dist,
-                       w.seg_start, w.count, w.chunk_pre, M, w.slab, fill.W, fill.ww, fill.xx, fill.round_f32, L, wa);
-    return DBGSOM_OK;
-}
-
 static int accumulate_impl(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx,
                            const int64_t *idx, const double *kw, double gamma, const double *dist, int64_t M,
                            double *sums, int32_t *status, bool status_behind_sums, void *ws,
-                           size_t ws_bytes, hipStream_t s, const DistFill *fill = nullptr, const double *sw = nullptr,
-                           const CsrView *csr = nullptr) {
+                           size_t ws_bytes, hipStream_t s, const double *sw = nullptr, const CsrView *csr = nullptr) {
     DBGSOM_REQUIRE(valid_dtype(x_dtype), "x_dtype must be DBGSOM_F32/F64/BF16");
     DBGSOM_REQUIRE(N >= 0 && N < 0x7fffffff && d >= 1 && d <= 0x7ffffff0 && ldx >= d, "bad sample shape");
     DBGSOM_REQUIRE(M >= 1 && M <= DBGSOM_MAX_PROTOTYPES, "M outside [1, DBGSOM_MAX_PROTOTYPES]");
@@ -1092,29 +756,9 @@ static int accumulate_impl(const void *X, int x_dtype, int64_t N, int64_t d, int
     } while (0)
     if (csr) {
         // CSR samples: the chunk kernel of csr.hip writes the same slab rows; everything around it is shared
-        DBGSOM_REQUIRE(!fill, "distances cannot be filled in for CSR samples");
         const int rc = launch_segsum_csr(*csr, x_dtype, d, w.order, kw, gamma, dist, w.seg_start, w.count, w.chunk_pre, M,
                                          w.slab, sw, w.maxchunks, s);
         if (rc != DBGSOM_OK) return rc;
-    } else if (fill) {
-        // rows with dist == -1 get their distance (to their winner: this chunk's prototype) on the way
-        DBGSOM_REQUIRE(!kw && al16 && accumulate_can_fill_distances(x_dtype, d) && fill->W && fill->ww && fill->xx,
-                       "distances cannot be filled in for this shape");
-        const ChainLds L = chain_lds(d);
-        const bool two = d / (x_dtype == DBGSOM_F32 ? 4 : (x_dtype == DBGSOM_F64 ? 2 : 8)) > AT;
-#define DBGSOM_SEGDIST(XT, V, G_)                                                                        \
-    do {                                                                                                 \
-        if (sw) TRY_LAUNCH((launch_chain<XT, V, G_, true>(grid, (const XT *)X, di, ldx, w, gamma, const_cast<double *>(dist), \
-                                                          Mi, *fill, L, WeightArg<true>{sw}, s)));      \
-        else TRY_LAUNCH((launch_chain<XT, V, G_, false>(grid, (const XT *)X, di, ldx, w, gamma, const_cast<double *>(dist), \
-                                                        Mi, *fill, L, WeightArg<false>{}, s)));         \
-    } while (0)
-#define TRY_LAUNCH(expr) do { const int rc_ = (expr); if (rc_ != DBGSOM_OK) return rc_; } while (0)
-        if (x_dtype == DBGSOM_F32) { if (two) DBGSOM_SEGDIST(float, 4, 2); else DBGSOM_SEGDIST(float, 4, 1); }
-        else if (x_dtype == DBGSOM_F64) { if (two) DBGSOM_SEGDIST(double, 2, 2); else DBGSOM_SEGDIST(double, 2, 1); }
-        else { if (two) DBGSOM_SEGDIST(bf16_t, 8, 2); else DBGSOM_SEGDIST(bf16_t, 8, 1); }
-#undef TRY_LAUNCH
-#undef DBGSOM_SEGDIST
     } else if (x_dtype == DBGSOM_F32) {
         if (al16 && d % 4 == 0) DBGSOM_SEGSUM(float, 4); else DBGSOM_SEGSUM(float, 1);
     } else if (x_dtype == DBGSOM_F64) {
@@ -1153,9 +797,8 @@ int launch_accumulate(const void *X, int x_dtype, int64_t N, int64_t d, int64_t 
 
 int launch_accumulate_epoch(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx,
                             const int64_t *idx, double gamma, const double *dist, int64_t M,
-                            double *sums, int32_t *status, void *ws, size_t ws_bytes, hipStream_t s,
-                            const DistFill *fill) {
-    return accumulate_impl(X, x_dtype, N, d, ldx, idx, nullptr, gamma, dist, M, sums, status, true, ws, ws_bytes, s, fill);
+                            double *sums, int32_t *status, void *ws, size_t ws_bytes, hipStream_t s) {
+    return accumulate_impl(X, x_dtype, N, d, ldx, idx, nullptr, gamma, dist, M, sums, status, true, ws, ws_bytes, s);
 }
 
 // the weighted forms: `sw` = one weight per row (finite, >= 0: the caller has checked); workspace of
@@ -1164,15 +807,14 @@ int launch_accumulate_weighted(const void *X, int x_dtype, int64_t N, int64_t d,
                                const int64_t *idx, const double *kw, const double *sw, const double *dist, int64_t M,
                                double *sums, int32_t *status, void *ws, size_t ws_bytes, hipStream_t s) {
     DBGSOM_REQUIRE(N == 0 || (kw && sw), "null sample weights");
-    return accumulate_impl(X, x_dtype, N, d, ldx, idx, kw, 0.0, dist, M, sums, status, false, ws, ws_bytes, s, nullptr, sw);
+    return accumulate_impl(X, x_dtype, N, d, ldx, idx, kw, 0.0, dist, M, sums, status, false, ws, ws_bytes, s, sw);
 }
 
 int launch_accumulate_epoch_weighted(const void *X, int x_dtype, int64_t N, int64_t d, int64_t ldx,
                                      const int64_t *idx, double gamma, const double *sw, const double *dist, int64_t M,
-                                     double *sums, int32_t *status, void *ws, size_t ws_bytes, hipStream_t s,
-                                     const DistFill *fill) {
+                                     double *sums, int32_t *status, void *ws, size_t ws_bytes, hipStream_t s) {
     DBGSOM_REQUIRE(N == 0 || sw, "null sample weights");
-    return accumulate_impl(X, x_dtype, N, d, ldx, idx, nullptr, gamma, dist, M, sums, status, true, ws, ws_bytes, s, fill, sw);
+    return accumulate_impl(X, x_dtype, N, d, ldx, idx, nullptr, gamma, dist, M, sums, status, true, ws, ws_bytes, s, sw);
 }
 
 int launch_accumulate_csr(const CsrView &x, int x_dtype, int64_t N, int64_t d, const int64_t *idx, const double *kw,
@@ -1181,7 +823,7 @@ int launch_accumulate_csr(const CsrView &x, int x_dtype, int64_t N, int64_t d, c
     DBGSOM_REQUIRE(x_dtype == DBGSOM_F32 || x_dtype == DBGSOM_F64, "CSR data must be DBGSOM_F32 or DBGSOM_F64");
     DBGSOM_REQUIRE(N == 0 || x.indptr, "null CSR arrays");
     return accumulate_impl(nullptr, x_dtype, N, d, d, idx, kw, gamma, dist, M, sums, status, status_behind_sums, ws,
-                           ws_bytes, s, nullptr, sw, &x);
+                           ws_bytes, s, sw, &x);
 }
 
 }  // namespace dbgsom

@@ -262,12 +262,6 @@ struct dbgsom_ctx {
     hipStream_t stream = nullptr;
     // options
     int timing = 0;
-    int use_graph = 0;
-    int defer = 0;                  // with the refinement: distances of decided samples inside the sums kernel
-                                    // (experimental, off: one chain wavefront per CU cannot keep up -- NOTES.md)
-    bool last_deferred = false;
-    int64_t defer_epochs = 0;       // epochs whose sums kernel also evaluated the distances the refinement left open
-    int last_round_f32 = 0;
     bool last_refined = false;
     bool last_k2_filtered = false;  // the last k = 2 search went through the pruning form
     int64_t filter_min_query_rows = 32768;
@@ -642,8 +636,7 @@ int stage_weights(dbgsom_ctx *c, const double *W_host, int64_t M, int64_t d, int
 
 // k = 1 search through the int8 filter, in the form the policy plans; seeds = previous winners when `prev_idx`
 int run_filtered(dbgsom_ctx *c, Samples &s, DevBuf &ws, const double *W, int64_t M, int round_f32,
-                 const int64_t *prev_idx, const int32_t *order, int64_t *idx, double *dist, bool may_probe = false,
-                 bool allow_defer = false) {
+                 const int64_t *prev_idx, const int32_t *order, int64_t *idx, double *dist, bool may_probe = false) {
     TRY(ensure_planes(c, s));
     TRY(ws.reserve_zeroed(dbgsom_bmu_filtered_workspace_bytes(s.N, s.dp, M), c->stream));
     const ResidentSearchState &st = c->search;   // (the bound: the last epoch's distances under Wb[st.distW_buf])
@@ -676,12 +669,6 @@ int run_filtered(dbgsom_ctx *c, Samples &s, DevBuf &ws, const double *W, int64_t
     call.round_f32 = round_f32; call.idx = idx; call.dist = dist; call.ws = ws.p; call.ws_bytes = ws.cap;
     call.refine_rows = plan.refine_rows;
     c->last_refined = plan.refine;
-    // an epoch's accumulate step can evaluate the distances of the samples the refinement decided without
-    // looking at their float rows: one pass over those rows for the distance AND the sums
-    call.defer_dist = plan.refine && allow_defer && c->defer && M < 0xffff &&
-                      accumulate_can_fill_distances(s.dtype, s.dp);
-    c->last_deferred = call.defer_dist;
-    c->last_round_f32 = round_f32;
     if (s.dtype == DBGSOM_BF16) { call.X_store = s.X; call.store_dtype = DBGSOM_BF16; call.ld_store = s.dp; }
     call.guard_mean = plan.guard_mean;
     const int rc_f = launch_bmu_filtered(call);
@@ -689,7 +676,6 @@ int run_filtered(dbgsom_ctx *c, Samples &s, DevBuf &ws, const double *W, int64_t
     if (rc_f == DBGSOM_LISTS_LONG) {
         c->policy.on_guarded();
         c->last_refined = false;
-        c->last_deferred = false;
         return launch_bmu(s.Xb, s.bdtype, s.N, s.dp, s.dp, s.xx.as<double>(), W, M, c->ww.as<double>(), 1, round_f32, idx,
                           dist, c->stream);
     }
@@ -897,7 +883,6 @@ int epoch_bmu(dbgsom_ctx *c, int64_t M, int round_f32) {
     int64_t *out = c->idx[c->icur ^ 1].as<int64_t>();
     const double *W = c->Wb[c->cur].as<double>();
     c->policy.begin_epoch();
-    c->last_deferred = false;
     if (s.csr) {
         c->last_filtered = false;
         TRY(csr_search(c, s, W, M, 1, round_f32, out, c->dist.as<double>()));
@@ -909,7 +894,7 @@ int epoch_bmu(dbgsom_ctx *c, int64_t M, int round_f32) {
         const bool hint = hint_applies(c, M);
         c->last_filtered = true;
         TRY(run_filtered(c, s, c->filt_ws, W, M, round_f32, hint ? c->idx[c->icur].as<int64_t>() : nullptr,
-                         hint ? c->acc_ws.as<int32_t>() : nullptr, out, c->dist.as<double>(), true, true));
+                         hint ? c->acc_ws.as<int32_t>() : nullptr, out, c->dist.as<double>(), true));
     } else {
         c->last_filtered = false;
         c->policy.on_exact_epoch();
@@ -957,18 +942,12 @@ int accumulate_and_reduce(dbgsom_ctx *c, const int64_t *idx, const double *kw, d
         hipLaunchKernelGGL(status_to_f64_kernel, dim3(1), dim3(1), 0, c->stream, status, c->sums.as<double>() + count);
         TRY(launch_status("status_to_f64_kernel"));
     } else {
-        DistFill fill;
-        fill.W = c->Wb[c->cur].as<double>(); fill.ww = c->ww.as<double>(); fill.xx = s.xx.as<double>();
-        fill.round_f32 = c->last_round_f32;
         if (sw)
             TRY(launch_accumulate_epoch_weighted(s.X, s.dtype, s.N, s.dp, s.dp, idx, gamma, sw, dist, M, c->sums.as<double>(),
-                                                 status, c->acc_ws.p, c->acc_ws.cap, c->stream,
-                                                 c->last_deferred ? &fill : nullptr));
+                                                 status, c->acc_ws.p, c->acc_ws.cap, c->stream));
         else
             TRY(launch_accumulate_epoch(s.X, s.dtype, s.N, s.dp, s.dp, idx, gamma, dist, M, c->sums.as<double>(), status,
-                                        c->acc_ws.p, c->acc_ws.cap, c->stream, c->last_deferred ? &fill : nullptr));
-        if (c->last_deferred) ++c->defer_epochs;
-        c->last_deferred = false;
+                                        c->acc_ws.p, c->acc_ws.cap, c->stream));
     }
     c->sumsM = M;
     c->sums_sharded = false;
@@ -1278,10 +1257,6 @@ int dbgsom_ctx_set_option(dbgsom_ctx *c, const char *name, int64_t v) {
         c->ev_valid = false;
         c->faux.timer.enabled = c->timing != 0;
         c->faux.timer.valid = false;
-    } else if (!strcmp(name, "graph")) {
-        c->use_graph = v != 0;
-    } else if (!strcmp(name, "defer")) {
-        c->defer = v != 0;
     } else if (!strcmp(name, "shard_smooth")) {
         DBGSOM_REQUIRE(v >= 0 && v <= 2, "shard_smooth must be 0 (never), 1 (whenever the collective can) or 2 (large maps)");
         c->shard_smooth = (int)v;
@@ -1345,13 +1320,10 @@ int dbgsom_ctx_get_option(dbgsom_ctx *c, const char *name, int64_t *v) {
     else if (!strcmp(name, "sweep_planes")) *v = c->policy.sweep_planes;
     else if (!strcmp(name, "seed_stride")) *v = c->policy.seed_stride;
     else if (!strcmp(name, "timing")) *v = c->timing;
-    else if (!strcmp(name, "graph")) *v = c->use_graph;
     else if (!strcmp(name, "refine")) *v = c->policy.refine;
     else if (!strcmp(name, "refined")) *v = c->last_refined ? 1 : 0;
-    else if (!strcmp(name, "defer")) *v = c->defer;
     else if (!strcmp(name, "shard_smooth")) *v = c->shard_smooth;
     else if (!strcmp(name, "shard_epochs")) *v = c->shard_epochs;
-    else if (!strcmp(name, "defer_epochs")) *v = c->defer_epochs;
     else if (!strcmp(name, "guarded_calls")) *v = c->policy.guarded_calls;
     else if (!strcmp(name, "collective_rank")) *v = c->coll_rank;
     else if (!strcmp(name, "collective_ranks")) *v = c->coll_nranks;
@@ -3003,7 +2975,6 @@ int metric_epoch(dbgsom_ctx *c, const char *fn, Metric metric, const double *W_h
         if ((rc = c->dist.reserve((size_t)s.N * 8))) break;
         int64_t *idx = c->idx[c->icur ^ 1].as<int64_t>();
         c->last_filtered = false;
-        c->last_deferred = false;
         c->search.foreign_search_begun();
         if ((rc = resident_bmu_metric(c, metric, c->Wb[c->cur].as<double>(), s.dp, M, 1, idx, c->dist.as<double>()))) break;
         c->icur ^= 1;

@@ -2836,7 +2836,7 @@ static size_t carve_filter(FilterWs *out, char *base, int64_t N, int64_t d, int6
     take(f.tile_part, (size_t)TS_RB * 2 * dpad * 8);
     take(f.ulist, (size_t)nb * Mpad * 2); take(f.ucount, (size_t)nb * 4);
     take(f.seed, (size_t)N * 8); take(f.order, (size_t)N * 4);
-    take(f.sort_ws, bucket_sort_workspace_bytes(N, M + 1));   // (+ 1: the "decided" bucket of the deferred form, 2d)
+    take(f.sort_ws, bucket_sort_workspace_bytes(N, M));
     take(f.sched, (size_t)nb * 4); take(f.sched_ctr, (size_t)(SCHED_CTR + 2 * RF_CTR + 4) * 4);
     f.rf_ctr = base ? reinterpret_cast<unsigned long long *>(f.sched_ctr + SCHED_CTR) : nullptr;   // (behind the schedule's)
     f.rf_qlen = base ? f.sched_ctr + SCHED_CTR + 2 * RF_CTR : nullptr;
@@ -3289,14 +3289,13 @@ struct FilterRun {
         // beyond its tiles: a few long chains on a mostly idle chip): all of it on the second stream, beside the
         // refinement and the pair kernel on the caller's; the samples whose candidates overflowed on the third.
         hipStream_t s_mfma = refine ? s2 : s;
-        const int defer_M = (refine && c.defer_dist) ? (int)M : 0;
         const dim3 fill_grid((unsigned)((f.nb + 255) / 256));
         if (refine)
             // list-length classes of the refinement: a small tile for the bulk (what the caller expects the
             // lists to be), the largest for the rest; workgroups in neither stay the matrix-core stage's
             hipLaunchKernelGGL(class_fill_kernel, fill_grid, dim3(256), 0, s, f.ucount, (int)f.nb, fm.rows0,
                                RF_SEGS * (int)RefineCfg<2, 4>::MAX_CNT, f.rf_queue, f.rf_qlen, f.gflag, f.sched_ctr, order, seeds,
-                               N, (int)M, f.cand, f.rbest, defer_M);
+                               N, (int)M, f.cand, f.rbest);
         else
             // (the bin counts were added up by the sweep's workgroups as they wrote their list lengths)
             hipLaunchKernelGGL(sched_fill_kernel, fill_grid, dim3(256), 0, s, f.ucount, (int)f.nb, f.sched_ctr, f.sched,
@@ -3320,23 +3319,21 @@ struct FilterRun {
                 hipLaunchKernelGGL(kernel, dim3((unsigned)(nb8 < wgs ? nb8 : wgs)), dim3(nj * 256), 0, s, xb.planes, xb.scale,
                                    xb.res16, c.xx, N, d, dpad, f.wt, (int)f.Mpad, f.wscale, c.ww, f.summary, order, f.ulist,
                                    (int)f.Mpad, f.ucount, f.rf_queue + (size_t)cls * f.nb, f.rf_qlen + cls, f.cand, f.rbest,
-                                   f.rf_ctr, f.ovf, f.rf_qlen + 2, f.ovf_cand, defer_M, c.idx, c.dist);
+                                   f.rf_ctr, f.ovf, f.rf_qlen + 2, f.ovf_cand);
             };
             if (fm.rows0 == 32) refine_launch(refine_i8_kernel<1, 1>, 1, 0, 1024);
             else if (fm.rows0 == 64) refine_launch(refine_i8_kernel<1, 2>, 1, 0, 1024);
             else if (fm.rows0 == 128) refine_launch(refine_i8_kernel<2, 2>, 2, 0, 512);
             refine_launch(refine_i8_kernel<2, 4>, 2, 1, 512);
             // the samples by their refined best prototype: a workgroup of the pair kernel then shares its candidates
-            const int64_t Mk = defer_M ? M + 1 : M;   // (deferred: the decided samples behind every real bucket)
-            const int rc = launch_bucket_sort(f.rbest, N, Mk, f.order2, f.sort_ws, s);
+            const int rc = launch_bucket_sort(f.rbest, N, M, f.order2, f.sort_ws, s);
             if (rc != DBGSOM_OK) return rc;
-            const uint32_t *n_active = defer_M ? bucket_sort_seg_start(f.sort_ws, N, Mk) + M : (const uint32_t *)nullptr;
             // (bfloat16-resident samples: the pair kernel reads the stored rows -- half the bytes of the widened
             //  copy the matrix kernels use, the same values)
             auto pair_launch = [&](auto kernel, auto *rows, int64_t ld) {
                 const unsigned pgrid = (unsigned)(((N + PS - 1) / PS + 7) / 8 * 8);   // (whole rounds of the 8 XCDs: xcd_group)
                 hipLaunchKernelGGL(kernel, dim3(pgrid), dim3(256), 0, s, rows, N, d, ld, c.xx, c.W, c.ww, f.order2, f.cand,
-                                   c.round_f32, c.idx, c.dist, f.rf_ctr, n_active);
+                                   c.round_f32, c.idx, c.dist, f.rf_ctr);
             };
             if (c.X_store && c.store_dtype == DBGSOM_BF16 && c.x_dtype == DBGSOM_F32)
                 pair_launch(pair_exact_kernel<bf16_t, 32, 128>, (const bf16_t *)c.X_store, c.ld_store);
@@ -3399,8 +3396,8 @@ struct FilterRun {
 
 int dbgsom::launch_bmu_filtered(const FilteredCall &call) {
     FilterForm form;
-    const char *rejected = form.resolve(call.seed_stride, call.sweep_planes, call.k, call.refine_rows, call.defer_dist, call.N,
-                                        call.d, call.M, call.prev_idx != nullptr, call.anchor_of != nullptr,
+    const char *rejected = form.resolve(call.seed_stride, call.sweep_planes, call.k, call.refine_rows, call.N, call.d,
+                                        call.M, call.prev_idx != nullptr, call.anchor_of != nullptr,
                                         call.anchor_runs != nullptr);
     DBGSOM_REQUIRE(!rejected, rejected);
     DBGSOM_REQUIRE(!call.anchor_runs || (call.anchor_of && is_aligned(call.anchor_runs, 256)),

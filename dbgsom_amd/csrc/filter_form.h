@@ -105,15 +105,14 @@ struct __attribute__((visibility("hidden"))) FilterForm {
     // DBGSOM_ANCHOR_LISTS_ONLY OR-ed in;
     // has_hint: the caller brings previous winners (no seed pre-pass).  The shape itself (N, d, M in range) is
     // the launcher's to check.  has_anchors / has_runs: the call brings anchor buckets / their run table.
-    const char *resolve(int flags, int planes, int k, int refine_rows, bool defer, int64_t N, int64_t d, int64_t M,
-                        bool has_hint, bool has_anchors = false, bool has_runs = false) {
+    const char *resolve(int flags, int planes, int k, int refine_rows, int64_t N, int64_t d, int64_t M, bool has_hint,
+                        bool has_anchors = false, bool has_runs = false) {
         seed_full = (flags & DBGSOM_SEED_FULL) != 0;
         prune = (flags & DBGSOM_PRUNE) != 0 && M <= PRUNE_MAX_M;
         prune_probe = !prune && (flags & DBGSOM_PRUNE_PROBE) != 0 && M <= PRUNE_MAX_M;
         prune_retry = (flags & DBGSOM_PRUNE_RETRY) != 0 && !seed_full && !has_hint;
         k2 = k == 2;
         if (!(k == 1 || k == 2)) return "k must be 1 or 2";
-        if (!(!defer || (refine_rows > 0 && M < 0xffff))) return "deferred distances need the refinement";
         if (!(!k2 || (prune && refine_rows == 0 && M >= 2)))
             return "k = 2 needs the pruning form (DBGSOM_PRUNE, M <= 8192) without the refinement";
         seed_stride = flags & ~(DBGSOM_PRUNE | DBGSOM_PRUNE_PROBE | DBGSOM_PRUNE_RETRY | DBGSOM_ANCHOR_LISTS_ONLY);

@@ -420,14 +420,12 @@ int dbgsom_ctx_destroy(dbgsom_ctx *ctx);
  * 1..3 fixed digit planes of the candidate sweep, 4 = no sweep: candidates from the triangle
  * inequality, DBGSOM_PRUNE), "seed_stride" (0 = library default),
  * "timing" (1: HIP events around the phases of an epoch and the stages of the filter),
- * "filter_min_query_rows", "max_mean_candidates", "graph" (reserved: accepted and stored, no effect in this
- * build -- an epoch is 22-23 back-to-back launches on the context's stream and two forked ones), "refine" (0 off,
- * 1 on, 2 by measurement: the per-sample refinement in front of the exact stage), "defer" (with the refinement: the
- * distance of a sample it decided is evaluated inside the epoch's sums kernel; off by default), "shard_smooth",
+ * "filter_min_query_rows", "max_mean_candidates", "refine" (0 off,
+ * 1 on, 2 by measurement: the per-sample refinement in front of the exact stage), "shard_smooth",
  * "csr_densify_below" (see dbgsom_ctx_load_csr), "anchor_seeds" (1, the default: a stateless search of the resident
  * samples in the pruning form takes its seeds from anchor buckets built once per load instead of a seed pre-pass per
  * call; 0: the pre-pass.  Results do not depend on it).
- * Readable besides those: "resident_csr", "resident_nnz", "refined", "defer_epochs" (epochs whose sums kernel evaluated distances), "shard_epochs", "n_samples", "features", "padded_features", "prototypes",
+ * Readable besides those: "resident_csr", "resident_nnz", "refined", "shard_epochs", "n_samples", "features", "padded_features", "prototypes",
  * "planes_cached", "planes_used" / "planes_next" (0 = no sweep), "seed_mode", "prune_retry", "hint_valid",
  * "filter_backoff", "plane_hold", "device_bytes", "anchor_builds" (anchor buckets built so far), "anchor_searches" (searches seeded from them), "lean_searches" (of those, epochs in the lean form DBGSOM_ANCHOR_LISTS_ONLY), "hint_bound_searches" (searches that took the hinted pruning bound), "anchor_state" (of
  * the resident samples: 0 none, 1 in use, 2 dropped -- their lists came out longer than the pre-pass's), and the

@@ -288,7 +288,7 @@ def raw_call_args(case):
 def form_line(flag_arg, planes, N, d, M, hinted):
     """one input line of tests/filter_form_check.cpp for a raw call (k = 1; dbgsom_bmu_filtered strips DBGSOM_REFINE
     and asks for the refinement's 192-entry tile instead)"""
-    return f"{flag_arg & ~REFINE:#x} {planes} 1 {192 if flag_arg & REFINE else 0} 0 {N} {d} {M} {int(hinted)}"
+    return f"{flag_arg & ~REFINE:#x} {planes} 1 {192 if flag_arg & REFINE else 0} {N} {d} {M} {int(hinted)}"
 
 
 FORM_FIELDS = ("seed_full", "prune", "prune_probe", "prune_retry", "k2", "seed_stride", "Msub", "Msubpad", "nkt_full",

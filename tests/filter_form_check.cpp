@@ -1,5 +1,5 @@
 // Resolves calls of the filtered search (dbgsom_amd/csrc/filter_form.h) on the CPU: one call per line on stdin,
-//   FLAGS PLANES K REFINE_ROWS DEFER N D M HAS_HINT
+//   FLAGS PLANES K REFINE_ROWS N D M HAS_HINT
 // (FLAGS: the seed stride with DBGSOM_SEED_FULL / DBGSOM_PRUNE / DBGSOM_PRUNE_PROBE / DBGSOM_PRUNE_RETRY OR-ed in),
 // one line of output each: "error MESSAGE", or
 //   ok seed_full prune prune_probe prune_retry k2 seed_stride Msub Msubpad nkt_full nkt_used sweep_planes marking
@@ -12,11 +12,11 @@
 int main() {
     static const char *const marking[] = {"prune", "sweep4", "sweep_1_4", "sweep_2_2", "sweep_3_1"};
     static const char *const exact[] = {"k2", "beside_refine", "split", "all"};
-    int flags, planes, k, refine_rows, defer, has_hint;
+    int flags, planes, k, refine_rows, has_hint;
     long long N, d, M;
-    while (scanf("%i %d %d %d %d %lld %lld %lld %d", &flags, &planes, &k, &refine_rows, &defer, &N, &d, &M, &has_hint) == 9) {
+    while (scanf("%i %d %d %d %lld %lld %lld %d", &flags, &planes, &k, &refine_rows, &N, &d, &M, &has_hint) == 8) {
         dbgsom::FilterForm f;
-        const char *err = f.resolve(flags, planes, k, refine_rows, defer != 0, N, d, M, has_hint != 0);
+        const char *err = f.resolve(flags, planes, k, refine_rows, N, d, M, has_hint != 0);
         if (err) {
             printf("error %s\n", err);
             continue;

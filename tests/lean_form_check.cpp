@@ -27,7 +27,7 @@ int main() {
             if (scanf("%i %d %d %d %lld %d %d %d", &flags, &planes, &k, &refine_rows, &M, &has_hint, &has_anchors, &has_runs) != 8)
                 return 2;
             dbgsom::FilterForm f;
-            const char *err = f.resolve(flags, planes, k, refine_rows, false, 100000, 784, M, has_hint != 0, has_anchors != 0,
+            const char *err = f.resolve(flags, planes, k, refine_rows, 100000, 784, M, has_hint != 0, has_anchors != 0,
                                         has_runs != 0);
             if (err) {
                 printf("error %s\n", err);

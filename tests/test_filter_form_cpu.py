@@ -3,6 +3,7 @@ is compiled with the host C++ compiler.  The expected answers were derived by ha
 before the arithmetic moved into the header: the same conditions, the same messages.
 """
 import os
+import re
 import shutil
 import subprocess
 
@@ -24,8 +25,8 @@ def resolve(tmp_path_factory):
     subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "dbgsom_amd", "csrc"),
                     "-o", exe, os.path.join(ROOT, "tests", "filter_form_check.cpp")], check=True)
 
-    def run(flags=0, planes=0, k=1, refine_rows=0, defer=False, N=3000, d=32, M=1024, has_hint=False):
-        line = f"{flags:#x} {planes} {k} {refine_rows} {int(defer)} {N} {d} {M} {int(has_hint)}\n"
+    def run(flags=0, planes=0, k=1, refine_rows=0, N=3000, d=32, M=1024, has_hint=False):
+        line = f"{flags:#x} {planes} {k} {refine_rows} {N} {d} {M} {int(has_hint)}\n"
         out = subprocess.run([exe], input=line, capture_output=True, text=True, check=True).stdout.strip()
         head, _, rest = out.partition(" ")
         if head == "error":
@@ -44,6 +45,32 @@ def test_header_is_host_only():
     assert includes == ["<stdint.h>", '"../../include/dbgsom_hip.h"']
     for word in ("hipStream_t", "hipError_t", "hip_runtime", "__global__", "__device__"):
         assert word not in text, word
+
+
+def test_nothing_of_the_deferred_distance_path_is_left():
+    """The sums kernel that also evaluated distances, its option and what threaded it through the search are gone
+    ("The winner's distance inside this kernel"), and so is the option "graph" that selected nothing."""
+    words = ("segsum_chain_kernel", "DistFill", "defer_dist", "defer_M", "n_active", "accumulate_can_fill_distances",
+             "allow_defer", "last_deferred", "use_graph")
+    sources = (".py", ".h", ".hip", ".cpp", ".sh", "Makefile")
+    seen = 0
+    for top in ("dbgsom_amd", "include", "tools"):
+        for folder, _, names in os.walk(os.path.join(ROOT, top)):
+            for name in names:
+                if not name.endswith(sources) or (top == "tools" and name.startswith("probe_") and name.endswith(".hip")):
+                    continue
+                text = open(os.path.join(folder, name), encoding="utf-8").read()
+                seen += 1
+                for word in words:
+                    assert word not in text, (os.path.join(folder, name), word)
+    assert seen > 40   # (the walk found the sources)
+    # the option and property names (backend.py's _QueryRows takes an unrelated `defer=` keyword)
+    for path in (("include", "dbgsom_hip.h"), ("dbgsom_amd", "csrc", "engine.hip"), ("dbgsom_amd", "csrc", "filter_form.h")):
+        text = open(os.path.join(ROOT, *path)).read()
+        assert not re.search(r"\bdefer(_epochs)?\b", text), path
+    text = open(os.path.join(ROOT, "dbgsom_amd", "backend.py")).read()
+    assert not re.search(r"""["']defer(_epochs)?["']|^\s*defer(_epochs)?\s*=|\.defer(_epochs)?\b""", text, re.M)
+    assert '"graph"' not in text
 
 
 def test_flags_are_the_headers():
@@ -126,16 +153,12 @@ def test_two_nearest_prototypes_need_the_pruning_form(resolve):
 
 
 def test_rejected_options(resolve):
-    assert resolve(defer=True) == "deferred distances need the refinement"
-    assert resolve(defer=True, refine_rows=192, M=0xffff) == "deferred distances need the refinement"
-    assert resolve(defer=True, refine_rows=192)["refine"] == 1
     assert resolve(flags=65) == "seed_stride outside [0, 64]"
     assert resolve(flags=0x1000) == "seed_stride outside [0, 64]"        # (DBGSOM_REFINE is the ABI wrapper's to strip)
     assert resolve(flags=SEED_FULL | 65)["seed_stride"] == 1              # (full seeds: the stride is not looked at)
     assert resolve(planes=4) == "sweep_planes must be 0 .. 3" and resolve(planes=-1) == "sweep_planes must be 0 .. 3"
-    # the order of the checks: k, deferral, k = 2, stride, planes
-    assert resolve(k=3, defer=True, flags=65, planes=4) == "k must be 1 or 2"
-    assert resolve(k=2, defer=True, flags=65, planes=4) == "deferred distances need the refinement"
+    # the order of the checks: k, k = 2, stride, planes
+    assert resolve(k=3, flags=65, planes=4) == "k must be 1 or 2"
     assert resolve(k=2, flags=65, planes=4) == K2_MESSAGE
     assert resolve(flags=65, planes=4) == "seed_stride outside [0, 64]"
 

@@ -1351,9 +1351,6 @@ def test_refinement_at_the_edges_of_its_shapes(N, d, M, kind):
         fi = HipBackend(algorithm="filtered").load(X)
         fi.refine = 1
         fi.sweep_planes = planes
-        # (experimental, off by default: the distance of a sample the refinement decided evaluated inside
-        #  the sums kernel of the epoch -- segsum_dist_kernel; the same bits)
-        fi.defer = planes == 2
         for e in range(2):
             re_ = ex.epoch(W, hop, 1.0, 1e-3, "aligned", True)
             rf = fi.epoch(W, hop, 1.0, 1e-3, "aligned", True)
@@ -1367,14 +1364,13 @@ def test_refinement_at_the_edges_of_its_shapes(N, d, M, kind):
 @pytest.mark.parametrize("dt,d,M", [("f32", 784, 300), ("f32", 256, 200), ("f32", 1040, 260), ("f32", 2048, 300),
                                     ("bf16", 2048, 400), ("bf16", 512, 300), ("bf16", 4096, 200), ("f64", 320, 300),
                                     ("f64", 784, 260), ("f32", 48, 200)])
-def test_distances_of_decided_samples_inside_the_sums_kernel(o, dt, d, M):
-    """`defer`: a sample the refinement narrows down to ONE candidate has its winner without its float row ever
-    being read; its distance is the chain against that prototype, evaluated by the epoch's sums kernel
-    (accumulate.hip: segsum_chain_kernel -- rows in registers, the chain on v_mfma_f64_4x4x4 through LDS ranges)
-    on the one pass it makes over the rows anyway.  Winners, distances AND the new prototypes are the all-pairs
-    search's bit for bit, for three storage types, rows of one and two column groups per thread, narrow rows with
-    several row lanes (d = 256: the sums' order of additions must be segsum_kernel's), chunks with and without rows
-    that need a distance, duplicated prototypes (undecided samples go through the pair kernel), ragged N."""
+def test_refined_epochs_across_storage_types(o, dt, d, M):
+    """Three epochs through the refinement behind the pruning form (refine = 1, sweep_planes = 4), stateless and
+    then hinted: the refinement, the pair kernel on the candidates it leaves and segsum_kernel on the winners.
+    Winners, distances AND the new prototypes are the all-pairs search's bit for bit, for three storage types
+    (float32, float64, bfloat16 rows), rows wider and narrower than a workgroup's column groups (d = 256 and 48:
+    several row lanes of the sums kernel), duplicated prototypes (samples with more than one candidate go through
+    the pair kernel), ragged N; a sample of the first epoch also against the oracle's chain."""
     import torch
     from dbgsom_amd.backend import HipBackend
 
@@ -1390,7 +1386,7 @@ def test_distances_of_decided_samples_inside_the_sums_kernel(o, dt, d, M):
     hop = np.abs(np.subtract.outer(np.arange(M), np.arange(M))).astype(np.float64)
     ex = HipBackend(algorithm="exact").load(X, storage=storage)
     fi = HipBackend(algorithm="filtered").load(X, storage=storage)
-    fi.refine, fi.defer, fi.sweep_planes = 1, 1, 4
+    fi.refine, fi.sweep_planes = 1, 4
     for e in range(3):
         re_ = ex.epoch(W, hop, 1.5, 1e-3, "compact" if e else "aligned", True)
         rf = fi.epoch(W, hop, 1.5, 1e-3, "compact" if e else "aligned", True)
@@ -1407,8 +1403,23 @@ def test_distances_of_decided_samples_inside_the_sums_kernel(o, dt, d, M):
             assert np.array_equal(rf.winners[pick], ri) and np.array_equal(rf.distances[pick], rd)
         W = np.nan_to_num(re_.new_weights)
         fi.algorithm = "filtered_hint"
-    assert fi.defer_epochs == 3, fi.defer_epochs
     ex.release(); fi.release()
+
+
+def test_removed_options_are_unknown():
+    """"defer", "defer_epochs" and "graph" left with the deferred-distance path: the library
+    answers them like any other unknown name, and the options that stayed still set."""
+    from dbgsom_amd.backend import HipBackend
+
+    be = HipBackend()
+    for name, access in (("defer", lambda: be._set("defer", 1)), ("defer_epochs", lambda: be._get("defer_epochs")),
+                         ("graph", lambda: be._set("graph", 1))):
+        # (DBGSOM_EINVAL: the binding raises it as a ValueError with the library's message)
+        with pytest.raises(ValueError, match=rf"failed \(-1\): dbgsom_ctx_[sg]et_option: unknown option '{name}'"):
+            access()
+    be._set("refine", 1)
+    assert be._get("refine") == 1
+    be.release()
 
 
 def test_refinement_with_non_finite_rows_and_extreme_scales():

@@ -108,10 +108,10 @@ def test_weighted_epoch_matches_the_oracle_on_repeated_rows(o, dt, N, d, M):
     be.release()
 
 
-# segsum_chain_kernel (the sums kernel that also fills in the distances the refinement left open): one and two
-# column groups per thread, three storage types, M on both sides of the second-level sum
+# the weighted epoch behind the refined search (refinement, pair kernel, then the weighted segsum_kernel): rows
+# narrower and wider than a workgroup's column groups, three storage types, M on both sides of the second-level sum
 @pytest.mark.parametrize("dt,d,M", [("f32", 256, 200), ("f64", 320, 300), ("bf16", 4096, 200), ("f32", 1280, 600)])
-def test_weighted_epoch_through_the_fused_chain_kernel(o, dt, d, M):
+def test_weighted_epoch_behind_the_refined_search(o, dt, d, M):
     from dbgsom_amd.backend import HipBackend
 
     N = 9003
@@ -124,12 +124,11 @@ def test_weighted_epoch_through_the_fused_chain_kernel(o, dt, d, M):
     ex.set_sample_weight(w)
     re_ = ex.epoch(W, hop, 1.5, 1e-3, "compact", True, frozen=True)      # weighted, segsum_kernel
     fi = HipBackend(algorithm="filtered").load(X, storage=storage)
-    fi.refine, fi.defer, fi.sweep_planes = 1, 1, 4
+    fi.refine, fi.sweep_planes = 1, 4
     fi.set_sample_weight(w)
-    n0 = fi.defer_epochs
     rf = _check_against_repeated_rows(o, fi, Xr, W, hop, w, 1.5, TV, r0.winners, r0.distances)
-    assert fi.filter_log[-1][0] == "filtered" and fi.refined and fi.defer_epochs == n0 + 1
-    # the two forms of the sums kernel leave the same bits
+    assert fi.filter_log[-1][0] == "filtered" and fi.refined
+    # the refined and the exact backend's weighted epochs leave the same bits
     assert np.array_equal(rf.new_weights, re_.new_weights, equal_nan=True)
     assert np.array_equal(rf.errors, re_.errors) and np.array_equal(rf.activations, re_.activations)
     rf2 = fi.epoch(W, hop, 1.5, 1e-3, "compact", True, frozen=True)

@@ -95,7 +95,7 @@ if __name__ == "__main__":
               spreading_factor=float(opts.get("spreading_factor", 0.9)),
               convergence_iter=int(opts.get("convergence_iter", 1)),
               coarse_training_frac=float(opts.get("coarse_training_frac", 0.7)))
-    bopts = {k: opts[k] for k in ("algorithm", "refine", "sweep_planes", "defer") if k in opts}
+    bopts = {k: opts[k] for k in ("algorithm", "refine", "sweep_planes") if k in opts}
     fit_profile(X[:4000], **dict(kw, n_iter=10))   # warm up the library
     if os.environ.get("DBGSOM_FIT_CPROFILE"):
         import cProfile

@@ -20,7 +20,7 @@ M = rows * cols
 dev = torch.device("cuda", 0)
 hip = HipBackend(0, algorithm=algo)
 take = 0
-for opt in sys.argv[4:]:   # e.g. refine=1 defer=0 sweep_planes=4; rows=125000: a rank's share of the workload
+for opt in sys.argv[4:]:   # e.g. refine=1 sweep_planes=4; rows=125000: a rank's share of the workload
     k, v = opt.split("=")
     if k == "rows":
         take = int(v)
